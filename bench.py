@@ -1,7 +1,15 @@
 #!/usr/bin/env python
 """Headline benchmark: frames/sec of the Context-Aware PoseFormer hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (frames/s, ms_per_step, the configuration and the
+end-to-end TFLOP/s from the plan's FLOP count).  --full adds everything else listed below (roofline passes, sustained and overlapped
+runs, the alternative plans, the training phase split, the CPU oracle's timing and accuracy); none of it changes `value`.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32): `joints` (B x 1 x 17 x 3) for inference;
+for --train also `loss` and a fixed, seeded sample of the flat lifter parameters after the step's AdamW update
+(`lifter_params_sample`, at most 4 M elements).  Inputs, weights and the DropPath draws are seeded, so two builds can be compared
+output for output.
 
 N > 1: one process per GPU over RCCL.  Either the driver launches the ranks (`python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`: RANK / LOCAL_RANK / WORLD_SIZE come from the environment) or,
@@ -14,7 +22,7 @@ HRNet-32, 256x256, fp32.  The other configurations are selected with --config 0.
 --batch / --height / --width / --dtype / --train); frames are independent, so N ranks share nothing on the data path
 (weak scaling, no collective) except the one gradient all-reduce of the training configuration.
 
-Rank 0 prints ONE JSON line: whole-job frames/s plus
+Rank 0 prints ONE JSON line: whole-job frames/s plus, with --full,
   roofline     — for the dominant kernel: algorithmic FLOPs (and algorithmic HBM bytes) of its launches / their summed
                  duration, measured with HIP event pairs on the launch stream (capf_forward_profile_launches), against
                  the dense MFMA peak for the dtype and the 8 TB/s HBM peak (MI355X_MICROARCH.md); `bound` names the
@@ -28,8 +36,8 @@ Rank 0 prints ONE JSON line: whole-job frames/s plus
                  frames; --lifter-fp32 (plan flag CAPF_PLAN_LIFTER_FP32) keeps the lifter's projections fp32 under --dtype bf16.
 fp32 configurations: the 3x3 stride-1 convs run on the bf16 matrix pipe with every fp32 operand split EXACTLY into three bf16 numbers
 (csrc/igemm_f32x3_ws.hip: results as close to fp64 as the direct fp32 MFMA kernel's); --no-f32x3 (CAPF_PLAN_NO_F32X3) times
-round 3's plan (Winograd on the fp32 pipe) for comparison, and every fp32 inference line carries that plan's rate for the same K steps as
-`fp32_pipe_plan` (never `value`).  `dtype` stays "f32": that is the arithmetic the path computes in.
+round 3's plan (Winograd on the fp32 pipe) for comparison, and every fp32 inference line of --full carries that plan's rate for the same K
+steps as `fp32_pipe_plan` (never `value`).  `dtype` stays "f32": that is the arithmetic the path computes in.
 """
 import argparse
 import copy
@@ -106,7 +114,15 @@ def parse(argv=None):
                          "GLOBAL batch, split evenly across the ranks (shard_bounds), so total work is fixed as N grows")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous, sharding, barriers, max-over-ranks and the JSON line "
                     "with a sleep instead of the GPU step (CPU smoke test of the N>1 flow)")
+    ap.add_argument("--full", action="store_true", help="after the headline measurement also run the per-kernel roofline passes, the "
+                    "sustained / overlapped / alternative-plan runs, the training phase split and the CPU oracle's timing and accuracy")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32, rank 0's shard)")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.kernel_table and not a.full:
+        ap.error("--kernel-table prints the per-kernel table of the --full profile passes: add --full")
     base = dict(CONFIGS[a.config if a.config is not None else 1])
     if a.train and a.config is None:
         base.update(batch=512, train=True)
@@ -134,7 +150,7 @@ def workload_string(a, tag):
                "each operand split exactly into three bf16 pieces, six piece products on the bf16 matrix pipe (CAPF_PLAN_F32X3_EXACT)" if getattr(a, "x3_exact", False) else
                "each operand as two fp16 pieces under exact power-of-two block scales (to 2^-23), three piece products on the 16-bit matrix pipe -- same "
                "measured distance to fp64 as the direct fp32 MFMA kernel; Inf / NaN / |x| >= 1.5e23 give NaN (igemm_f32h2_ws); the exact-operand and "
-               "fp32-pipe plans are timed on the same line (exact_split_plan, fp32_pipe_plan)") +
+               "fp32-pipe plans are timed on the --full line (exact_split_plan, fp32_pipe_plan)") +
               ("; every other conv / GEMM: fp32 MFMA" if getattr(a, "no_f32x3", False) else
                "; the other convs and the lifter's projections (LayerNorm-folded ones included): the same two-piece arithmetic (igemm_f32h2g); "
                "pointwise layer1 convs, the stem and the lifter's embed_proj / feat_embed rows: fp32 MFMA")) if a.dtype == "f32" else
@@ -168,7 +184,7 @@ def vs_fp32_oracle(backbone, sd_cpu, img, k2d, kc, got, others=None):
     import capf_oracle as oracle
     B = img.shape[0]
     idx = sorted({0, B // 3, (2 * B) // 3, B - 1})
-    torch.set_num_threads(min(32, os.cpu_count() or 1))
+    torch.set_num_threads(min(32, host_threads()))
     with torch.no_grad():
         want = oracle.ca_pf_forward(sd_cpu, img[idx].cpu(), k2d[idx].cpu(), kc[idx].cpu().clone(), backbone=backbone)
     d = got[idx].cpu().float() - want
@@ -204,7 +220,7 @@ def cpu_baseline(backbone, H, W, sd_cpu, budget_s=24.0):
     import torch
     import capf_oracle as oracle
     from capf import synth
-    host = os.cpu_count() or 1
+    host = host_threads()
     t_start = time.perf_counter()
 
     def run(B, threads, reps):
@@ -247,6 +263,42 @@ def cpu_baseline(backbone, H, W, sd_cpu, budget_s=24.0):
 def input_seed(rank):
     """Every rank draws its OWN shard of synthetic frames (data parallel: different frames per GPU)."""
     return 1000 + rank
+
+
+def host_threads():
+    """CPU threads this process may use: the affinity mask, capped by OMP_NUM_THREADS when the launcher sets it."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "0")) or n)
+    except ValueError:
+        pass
+    return max(1, n)
+
+
+DUMP_SAMPLE = 1 << 22            # elements of a flat buffer kept by --dump-outputs (fixed, seeded positions)
+DUMP_LIMIT = 64 << 20            # bytes written by --dump-outputs at most
+
+
+def dump_sample_index(n, dev):
+    """Fixed positions of a flat buffer of n elements: all of them up to DUMP_SAMPLE, else a seeded sorted sample."""
+    import numpy as np
+    import torch
+    if n <= DUMP_SAMPLE:
+        return None
+    idx = np.sort(np.random.Generator(np.random.Philox(key=[2024, n])).choice(n, size=DUMP_SAMPLE, replace=False))
+    return torch.from_numpy(idx).to(dev)
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: one float32 .npy per array, at most DUMP_LIMIT bytes in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def main():
@@ -345,6 +397,7 @@ def main():
         opt = FusedAdamW(flat_p, lr=6.4e-4, weight_decay=0.1)                # train.py:345, human36m.yaml:58
         model.flat_grad_only = True                                          # gradient -> all-reduce -> AdamW on the flat buffer
         crit = MPJPE()
+        last_loss = [None]                                                    # (--dump-outputs: the last step's loss)
 
         phase_ev = None                                                       # (after the timed region: event pairs around the phases)
 
@@ -354,6 +407,7 @@ def main():
             kc_work.copy_(kc0)
             pred = model(img, k2d, kc_work)                                  # DropPath active (dpr 0..0.2)
             loss = crit(pred, gt)
+            last_loss[0] = loss.detach()
             mark()
             model.zero_grad(set_to_none=True)
             loss.backward()
@@ -376,6 +430,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
+    torch.manual_seed(input_seed(rank))                    # DropPath's draws (training): the same on every run
     with (torch.enable_grad() if a.train else torch.no_grad()):
         for _ in range(a.warmup):
             out = step()
@@ -388,8 +443,15 @@ def main():
         fence()
         elapsed = time.perf_counter() - t0                     # bracketed by barrier + synchronize on both sides
     assert torch.isfinite(out).all()
+    if a.dump_outputs and rank == 0:                       # what the last timed step computed, before any extra measurement below
+        dumped = {"joints": out.detach().float().cpu().numpy()}
+        if a.train:
+            idx = dump_sample_index(flat_p.numel(), dev)
+            dumped["loss"] = last_loss[0].float().cpu().numpy()
+            dumped["lifter_params_sample"] = (flat_p if idx is None else flat_p[idx]).detach().float().cpu().numpy()
+        write_outputs(a.dump_outputs, dumped)
     train_phases = None
-    if a.train:                                            # untimed extra steps: where a training step's time goes (HIP events on the stream)
+    if a.train and a.full:                                 # untimed extra steps: where a training step's time goes (HIP events on the stream)
         acc_ms = [0.0, 0.0, 0.0, 0.0]
         nrep = 3
         with torch.enable_grad():
@@ -547,8 +609,28 @@ def main():
     ms_per_step = elapsed / a.steps * 1e3
     fps = global_frames * a.steps / elapsed
 
+    def headline(n_launches=None):
+        # the keys of every line, plain and --full: the timed steps' rate and what they ran (the plan's FLOP count is a table lookup)
+        _, flops = model.engine_for(img).stats(B)
+        par = f"dp{world} (independent frames, " + ("one flat-gradient all-reduce per step)" if a.train else "no collective)")
+        config = {"workload": workload_string(a, tag), "baseline_config": tag, "frames_per_step": global_frames, "frames_per_gpu": B,
+                  "parallelism": par}
+        if n_launches is not None:                         # (counted by the --full profile passes)
+            config["launches_per_forward"] = n_launches
+        config.update(forward_gflop_per_frame=round(flops / B / 1e9, 3), plan_flags=pflags)
+        return {
+            "metric": "frames/sec", "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": a.steps,
+            "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": a.scaling,
+            "vs_baseline": None, "dtype": a.dtype, "data": "synthetic", "config": config,
+            "end_to_end_forward_tflops": round(fps * flops / B / 1e12, 2),
+        }
+
     result = None
-    if rank == 0:
+    if rank == 0 and not a.full:
+        result = headline()
+        if dist_info is not None:
+            result["distributed"] = dist_info
+    elif rank == 0:
         eng = model.engine_for(img)
         # ---- per-kernel event timing on the launch stream (separate, untimed passes over the FORWARD schedule; in
         # the training configuration the frozen-backbone forward is 90 % of the step and owns the dominant kernel)
@@ -683,18 +765,8 @@ def main():
                                             "split EXACTLY into three bf16 pieces, six piece products per fp32 product; not the headline")
         fp32_pipe_plan = measure_alt_plan(PLAN_NO_F32X3 | PLAN_NO_F32H2_GEMM, "fp32_pipe_plan", "plan_flags |= CAPF_PLAN_NO_F32X3 | CAPF_PLAN_NO_F32H2_GEMM: every conv / GEMM on "
                                           "the fp32 matrix pipe (3x3: Winograd from batch 24, direct below) -- round 3's plan; not the headline")
-        launches, flops = eng.stats(B)
-        par = f"dp{world} (independent frames, " + ("one flat-gradient all-reduce per step)" if a.train else "no collective)")
-        result = {
-            "metric": "frames/sec", "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": a.scaling,
-            "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
-            "config": {"workload": workload_string(a, tag), "baseline_config": tag, "frames_per_step": global_frames, "frames_per_gpu": B,
-                       "parallelism": par, "launches_per_forward": n_launches, "forward_gflop_per_frame": round(flops / B / 1e9, 3),
-                       "plan_flags": pflags},
-            "end_to_end_forward_tflops": round(fps * flops / B / 1e12, 2),
-            "roofline": roofline,
-        }
+        result = headline(n_launches)
+        result["roofline"] = roofline
         if dist_info is not None:
             result["distributed"] = dist_info
         if sustained is not None:

@@ -201,3 +201,45 @@ def test_bench_labels_follow_the_arguments():
     assert (a.backbone, a.height, a.width, a.dtype, a.batch) == ("cpn", 384, 288, "bf16", 128)
     a = bench.parse(["--batch", "32"])
     assert bench.config_tag(a) is None and bench.workload_string(a, None).startswith("custom")
+
+
+def _bench_module():
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_full_and_dump_options():
+    """A plain run is the headline only (--full off by default); --kernel-table needs the --full profile passes; --steps counts."""
+    import pytest
+    bench = _bench_module()
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "d", "--kernel-table"])
+    assert a.full and a.dump_outputs == "d" and a.kernel_table
+    for bad in (["--kernel-table"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_bench_dump_writes_float32_within_the_limit(tmp_path):
+    import numpy as np
+    import pytest
+    bench = _bench_module()
+    j = np.random.default_rng(0).standard_normal((4, 1, 17, 3))
+    bench.write_outputs(str(tmp_path / "out"), {"joints": j, "loss": np.float64(0.5)})
+    got = np.load(tmp_path / "out" / "joints.npy")
+    assert got.dtype == np.float32 and got.shape == (4, 1, 17, 3) and np.array_equal(got, j.astype(np.float32))
+    assert np.load(tmp_path / "out" / "loss.npy").dtype == np.float32
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT // 4 + 1, np.float32)})
+    assert not (tmp_path / "big").exists()
+    # the sample of a large flat buffer: fixed positions (same on every run), sorted, distinct, DUMP_SAMPLE of them
+    assert bench.dump_sample_index(1000, "cpu") is None
+    n = 14094147
+    i1, i2 = bench.dump_sample_index(n, "cpu"), bench.dump_sample_index(n, "cpu")
+    assert torch.equal(i1, i2) and i1.numel() == bench.DUMP_SAMPLE
+    assert bool((i1[1:] > i1[:-1]).all()) and int(i1[0]) >= 0 and int(i1[-1]) < n
