@@ -375,7 +375,7 @@ bool bneck0_bf16_ok(const GemmArgs& c1, const GemmArgs& c2, const GemmArgs& ds, 
                g.omap.G == 1 && g.omap.S1 == n && g.omap.off == 0 && !g.rscale && !g.ln_g && !g.up && g.splits <= 1 && g.Ho == g.H && g.Wo == g.W;
     };
     if (!base(c1, 1, 0, 64, 64, ACT_RELU) || !base(c2, 3, 1, 64, 64, ACT_RELU) || !base(ds, 1, 0, 64, 256, ACT_NONE) || !base(c3, 1, 0, 64, 256, ACT_RELU)) return false;
-    // (who reads whom is the caller's statement -- Engine::bneck0_head compares buffer ids; the launcher compares the pointers)
+    // (who reads whom is the caller's statement -- Engine::fused_at compares buffer ids; the launcher compares the pointers)
     if (c1.res || c2.res || ds.res || c3.rmap.G != 1 || c3.rmap.S1 != 256 || c3.rmap.off != 0) return false;
     if (c1.H != c2.H || c1.W != c2.W || c1.H != c3.H || c1.W != c3.W || c1.H != ds.H || c1.W != ds.W || c1.M != c2.M || c1.M != c3.M || c1.M != ds.M) return false;
     if (c1.H % 8 != 0 || c1.W % 8 != 0 || c1.M % (c1.H * c1.W) != 0) return false;

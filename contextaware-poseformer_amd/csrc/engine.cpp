@@ -195,57 +195,82 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes) const {
     return a;
 }
 
-bool Engine::bneck0_head(int i, int batch, int last_op, int m[4]) const {
-    if (!use_bneck || !bf16() || i < 0 || i >= (int)ops.size() || ops[i].kind != OP_FORK || ops[i].i0 != 2 || ops[i].region < 0) return false;
-    const int j = regions[ops[i].region].second;                 // the join; conv3 follows it
-    if (j != i + 4 || j + 1 >= last_op || j + 1 >= (int)ops.size()) return false;
-    int c1 = -1, c2 = -1, ds = -1;
-    for (int k = i + 1; k < j; ++k) {
-        const Op& o = ops[k];
-        if (o.kind != OP_GEMM || !o.conv || o.bf16 != 1) return false;
-        if (o.lane == 1) ds = k; else if (c1 < 0) c1 = k; else c2 = k;
+// Fused launches, the priority among them written out here: at a fork, a first bottleneck; at a conv, an identity bottleneck, else a
+// pointwise pair -- which never starts inside a fused bottleneck, nor takes the conv1 of one (the conv3 of a fused bottleneck does not chain
+// into the next block; a fused next block runs its own conv1).  Both bottlenecks need 64 Ki pixels: below, the 256 persistent blocks get
+// fewer than four tiles each and the separate launches win.
+Engine::FusedLaunch Engine::fused_at(int i, int batch, int last_op, bool bneck_only) const {
+    const int n_all = (int)ops.size();
+    if (i < 0 || i >= n_all) return {};
+    const Op& o = ops[i];
+    if (o.kind == OP_FORK) {                                   // conv1, conv2 | downsample inside the region, conv3 right after its join
+        if (!use_bneck || !bf16() || o.i0 != 2 || o.region < 0) return {};
+        const int j = regions[o.region].second;
+        if (j != i + 4 || j + 1 >= last_op || j + 1 >= n_all) return {};
+        int c1 = -1, c2 = -1, ds = -1;
+        for (int k = i + 1; k < j; ++k) {
+            const Op& g = ops[k];
+            if (g.kind != OP_GEMM || !g.conv || g.bf16 != 1) return {};
+            if (g.lane == 1) ds = k; else if (c1 < 0) c1 = k; else c2 = k;
+        }
+        const int c3 = j + 1;
+        if (c1 < 0 || c2 < 0 || ds < 0 || ops[c3].kind != OP_GEMM || !ops[c3].conv || ops[c3].bf16 != 1) return {};
+        if (ops[c2].in[0] != ops[c1].out || ops[ds].in[0] != ops[c1].in[0] || ops[c3].in[0] != ops[c2].out || ops[c3].aux != ops[ds].out) return {};
+        if (ops[c1].rows_per_frame * batch < 65536) return {};
+        if (!bneck0_bf16_ok(gemm_args(ops[c1], batch), gemm_args(ops[c2], batch), gemm_args(ops[ds], batch), gemm_args(ops[c3], batch))) return {};
+        return {Fusion::BNECK0, 4, {c1, c2, ds, c3}};
     }
-    const int c3 = j + 1;
-    if (c1 < 0 || c2 < 0 || ds < 0 || ops[c3].kind != OP_GEMM || !ops[c3].conv || ops[c3].bf16 != 1) return false;
-    if (ops[c2].in[0] != ops[c1].out || ops[ds].in[0] != ops[c1].in[0] || ops[c3].in[0] != ops[c2].out || ops[c3].aux != ops[ds].out) return false;
-    // (from 64 Ki pixels: below, the 256 persistent blocks get fewer than four tiles each and the five launches win)
-    if (ops[c1].rows_per_frame * batch < 65536) return false;
-    m[0] = c1; m[1] = c2; m[2] = ds; m[3] = c3;
-    return bneck0_bf16_ok(gemm_args(ops[c1], batch), gemm_args(ops[c2], batch), gemm_args(ops[ds], batch), gemm_args(ops[c3], batch));
-}
-
-int Engine::bneck0_member(int i, int batch) const {
-    int m[4];
-    for (int f = i - 5; f < i; ++f)
-        if (f >= 0 && bneck0_head(f, batch, (int)ops.size(), m) && (i == m[0] || i == m[1] || i == m[2] || i == m[3])) return f;
-    return -1;
-}
-
-bool Engine::bneck1_head(int i, int batch, int last_op) const {
-    if (!use_bneck || !bf16() || i < 0 || i + 2 >= last_op || i + 2 >= (int)ops.size()) return false;
-    const Op &c1 = ops[i], &c2 = ops[i + 1], &c3 = ops[i + 2];
-    for (const Op* o : {&c1, &c2, &c3})
-        if (o->kind != OP_GEMM || !o->conv || o->bf16 != 1 || o->region != c1.region || o->lane != c1.lane || o->in[1] >= 0) return false;
-    if (c1.bneck_c3 != i + 2 || c2.in[0] != c1.out || c3.in[0] != c2.out || c3.aux != c1.in[0] || c1.aux >= 0 || c2.aux >= 0) return false;
-    if (c1.rows_per_frame * batch < 65536) return false;
-    return bneck1_bf16_ok(gemm_args(c1, batch), gemm_args(c2, batch), gemm_args(c3, batch));
-}
-
-int Engine::bneck1_member(int i, int batch) const {
-    for (int f = i - 2; f <= i; ++f)
-        if (f >= 0 && bneck1_head(f, batch, (int)ops.size())) return f;
-    return -1;
-}
-
-bool Engine::pwchain_head(int i, int batch, int last_op) const {
-    if (!use_pwchain || i < 0 || i + 1 >= last_op || i + 1 >= (int)ops.size()) return false;
-    const Op& a = ops[i];
+    if (o.kind != OP_GEMM) return {};
+    if (use_bneck && bf16() && i + 2 < last_op && i + 2 < n_all) {
+        const Op &c2 = ops[i + 1], &c3 = ops[i + 2];
+        bool ok = o.bneck_c3 == i + 2 && c2.in[0] == o.out && c3.in[0] == c2.out && c3.aux == o.in[0] && o.aux < 0 && c2.aux < 0 &&
+                  o.rows_per_frame * batch >= 65536;
+        for (const Op* g : {&o, &c2, &c3})
+            ok = ok && g->kind == OP_GEMM && g->conv && g->bf16 == 1 && g->region == o.region && g->lane == o.lane && g->in[1] < 0;
+        if (ok && bneck1_bf16_ok(gemm_args(o, batch), gemm_args(c2, batch), gemm_args(c3, batch))) return {Fusion::BNECK1, 3, {i, i + 1, i + 2}};
+    }
+    if (bneck_only || !use_pwchain || i + 1 >= last_op || i + 1 >= n_all) return {};
     const Op& b = ops[i + 1];
-    if (a.kind != OP_GEMM || !a.conv || b.kind != OP_GEMM || !b.conv || a.bf16 != b.bf16 || a.bf16 > 1) return false;
-    if (b.in[0] != a.out || b.region != a.region || b.lane != a.lane) return false;
-    if (a.bf16 && (bneck0_member(i, batch) >= 0 || bneck1_member(i, batch) >= 0 || bneck1_head(i + 1, batch, last_op))) return false;   // (the conv3 of a
-                                                      // fused bottleneck does not chain into the next block; a fused next block runs its own conv1)
-    return a.bf16 ? gemm_bf16_pwchain_ok(gemm_args(a, batch), gemm_args(b, batch)) : gemm_f32_pwchain_ok(gemm_args(a, batch), gemm_args(b, batch));
+    if (!o.conv || b.kind != OP_GEMM || !b.conv || o.bf16 != b.bf16 || o.bf16 > 1 || b.in[0] != o.out || b.region != o.region || b.lane != o.lane) return {};
+    if (o.bf16 && (fused_leader(i, batch, true).n || fused_at(i + 1, batch, last_op, true).n)) return {};
+    const GemmArgs ga = gemm_args(o, batch), gb = gemm_args(b, batch);
+    if (!(o.bf16 ? gemm_bf16_pwchain_ok(ga, gb) : gemm_f32_pwchain_ok(ga, gb))) return {};
+    return {Fusion::PWCHAIN, 2, {i, i + 1}};
+}
+
+Engine::FusedLaunch Engine::fused_leader(int i, int batch, bool bneck_only) const {
+    for (int f = i - 5; f <= i; ++f) {                         // (the longest launch spans fork, conv1, conv2, downsample, join, conv3)
+        const FusedLaunch l = fused_at(f, batch, (int)ops.size(), bneck_only);
+        for (int k = 0; k < l.n; ++k)
+            if (l.m[k] == i) return l;
+    }
+    return {};
+}
+
+Engine::Family Engine::gemm_family(const Op& op, int batch) const {
+    return op.bf16 == 2 ? Family::BF16_ROWS : op.bf16 ? Family::BF16 : wino_now(op, batch) ? Family::WINO : Family::F32;
+}
+
+// FLOPs the MFMA pipe is asked to execute (2 x MACs issued, K padding included, tile-edge padding not): the Winograd kernels issue 18
+// (F(4,3), per four outputs) or 12 (F(2,3), per two) MACs per (cin, cout) where the direct conv issues 36 / 18, i.e. 1/2 or 2/3 of the
+// algorithmic count; the split-fp32 tiles three fp16 / six bf16 piece products per fp32 product, the two-fp16-piece GEMM three -- on the
+// 16-bit pipe, whose peak is 16 x the fp32 pipe's
+Engine::OpRoute Engine::op_route(const Op& op, int batch) const {
+    static const char* kn[] = {"", "fuse_sum", "maxpool3x3s2", "bilinear_resize", "prep_embed", "sample_ref",
+                               "layernorm", "deform_sample", "attention", "head", "", "", "embed", "ctx_attn", "res_chain", "mlp_chain"};
+    if (op.kind != OP_GEMM) return {Family::NONE, kn[op.kind], op.flops_per_frame * batch};
+    const Pack& pk = packs[op.pack];
+    const double MN = 2.0 * (double)op.rows_per_frame * batch * op.N;
+    const Family f = gemm_family(op, batch);
+    if (f == Family::BF16_ROWS) return {f, gemm_bf16_rows_kernel_name((int)(op.rows_per_frame * batch), op.N), MN * (pk.direct ? op.K : pk.Kpad)};
+    const GemmArgs a = gemm_args(op, batch);
+    if (f == Family::BF16)                                     // (the row-halo layout has no K padding: decided per launch, a lower bound)
+        return {f, gemm_bf16_kernel_name(a), MN * (pk.rh || pk.direct ? op.K : pk.Kpad)};
+    if (f == Family::WINO)
+        return {f, gemm_wino_kernel_name(a), gemm_wino_route(a) == WinoPath::X3 ? (x3_h2 ? 3.0 : 6.0) * MN * op.K
+                                                                                : MN * op.Cin * (pk.Kpad == 18 * pk.Cin ? 4.5 : 6.0)};
+    return {f, gemm_f32_kernel_name(a), gemm_f32_route(a).path == F32Path::H2G ? 3.0 * MN * pk.KpadH        // (small batch: a Winograd conv on
+                                        : MN * (op.wino ? pk.Kpad2 : pk.direct ? op.K : pk.Kpad)};           // the direct layout)
 }
 
 FuseSumArgs Engine::fuse_args(const Op& op, int batch) const {
@@ -269,12 +294,15 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
     };
     switch (op.kind) {
         case OP_GEMM: {
-            if (op.bf16 == 2) {
-                const GemmArgs a = gemm_args(op, batch);
-                HIP_TRY(launch_gemm_bf16_rows(a.A, a.Wp, a.bias, a.M, a.N, a.K, a.Kpad, a.out, a.omap, a.res, a.rmap, op.out_bf16, s));
-            } else if (op.bf16) HIP_TRY(launch_gemm_bf16(gemm_args(op, batch), s));
-            else if (wino_now(op, batch)) HIP_TRY(launch_gemm_wino(gemm_args(op, batch), s));
-            else HIP_TRY(launch_gemm_f32(gemm_args(op, batch), s));
+            const GemmArgs a = gemm_args(op, batch);
+            switch (gemm_family(op, batch)) {
+                case Family::BF16_ROWS:
+                    HIP_TRY(launch_gemm_bf16_rows(a.A, a.Wp, a.bias, a.M, a.N, a.K, a.Kpad, a.out, a.omap, a.res, a.rmap, op.out_bf16, s));
+                    break;
+                case Family::BF16: HIP_TRY(launch_gemm_bf16(a, s)); break;
+                case Family::WINO: HIP_TRY(launch_gemm_wino(a, s)); break;
+                default: HIP_TRY(launch_gemm_f32(a, s));
+            }
             break;
         }
         case OP_FUSE: {
@@ -396,20 +424,23 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
     auto mine = [&](const Op& op) { return ((lane_mask >> op.lane) & 1u) != 0; };
     auto groupable = [&](const Op& op, const GemmArgs& a) {
         if (op.kind != OP_GEMM) return false;
-        if (op.bf16) return gemm_bf16_groupable(a);
-        if (wino_now(op, batch)) return gemm_wino_ok(a);
-        return gemm_f32_groupable(a);
+        switch (gemm_family(op, batch)) {
+            case Family::BF16: return gemm_bf16_groupable(a);
+            case Family::WINO: return gemm_wino_ok(a);
+            case Family::F32: return gemm_f32_groupable(a);
+            default: return false;
+        }
     };
     for (const std::vector<int>& level : region_levels[region]) {
-        for (int pass = 0; pass < 3; ++pass) {           // pass 0: direct fp32 convs, 1: bf16 convs, 2: Winograd fp32 convs
+        for (Family pass : {Family::F32, Family::BF16, Family::WINO}) {
             GemmArgs group[MAXG];
             int members[MAXG];
             int n = 0;
             auto flush = [&]() -> int {
                 if (n == 0) return CAPF_OK;
                 if (log) HIP_TRY(log->mark(s, members, n));
-                if (pass == 0) HIP_TRY(launch_gemm_f32_group(group, n, s));
-                else if (pass == 1) {
+                if (pass == Family::F32) HIP_TRY(launch_gemm_f32_group(group, n, s));
+                else if (pass == Family::BF16) {
                     int v = -1;
                     HIP_TRY(launch_gemm_bf16_group(group, n, s, &v));
                     if (log && !log->op_variant.empty()) log->op_variant[members[0]] = v;
@@ -420,9 +451,7 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
             };
             for (int oi : level) {
                 const Op& op = ops[oi];
-                if (op.kind != OP_GEMM || !mine(op)) continue;
-                const int kind = op.bf16 ? 1 : (wino_now(op, batch) ? 2 : 0);
-                if (kind != pass) continue;
+                if (op.kind != OP_GEMM || !mine(op) || gemm_family(op, batch) != pass) continue;
                 const GemmArgs a = gemm_args(op, batch);
                 if (!groupable(op, a)) continue;
                 group[n] = a;
@@ -479,18 +508,22 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
         const Op& op = ops[oi];
         s = (par && op.lane > 0) ? side[op.lane - 1] : main_stream;
         if (ev) HIP_TRY(hipEventRecord(ev[oi], s));
+        if (const FusedLaunch f = ev ? FusedLaunch{} : fused_at(oi, batch, last_op); f.n) {
+            // several ops as one launch (bneck_bf16.hip, igemm_*_pwchain.hip); prefix runs (the layer-wise tests' capf_forward_prefix) and
+            // debug runs take the bottleneck variant that also stores the inner convs' outputs where the separate launches would have
+            const bool tap = debug || last_op < (int)ops.size();
+            GemmArgs m[4];
+            for (int k = 0; k < f.n; ++k) m[k] = gemm_args(ops[f.m[k]], batch);
+            if (log) HIP_TRY(log->mark(s, f.m, f.n));
+            if (f.kind == Fusion::BNECK0) HIP_TRY(launch_bneck0_bf16(m[0], m[1], m[2], m[3], tap, s));
+            else if (f.kind == Fusion::BNECK1) HIP_TRY(launch_bneck1_bf16(m[0], m[1], m[2], tap, s));
+            else if (op.bf16) HIP_TRY(launch_gemm_bf16_pwchain(m[0], m[1], s));
+            else HIP_TRY(launch_gemm_f32_pwchain(m[0], m[1], s));
+            oi = f.m[f.n - 1];
+            continue;
+        }
         switch (op.kind) {
             case OP_FORK: {
-                int bm[4];
-                if (!ev && bneck0_head(oi, batch, last_op, bm)) {
-                    // a first bottleneck as one launch; prefix runs (the layer-wise tests' capf_forward_prefix) and debug runs take the variant
-                    // that also stores conv1's / conv2's / the shortcut's outputs where the five launches would have
-                    if (log) HIP_TRY(log->mark(main_stream, bm, 4));
-                    HIP_TRY(launch_bneck0_bf16(gemm_args(ops[bm[0]], batch), gemm_args(ops[bm[1]], batch), gemm_args(ops[bm[2]], batch),
-                                               gemm_args(ops[bm[3]], batch), debug || last_op < (int)ops.size(), main_stream));
-                    oi = bm[3];
-                    break;
-                }
                 if (grouped && regions[op.region].second <= last_op) {
                     // lanes == 3: the lanes of a region as TWO grouped chains on two streams (lanes 0 + 3 on the caller's, 1 + 2 on a
                     // side stream), so that one chain's launch ramp / tail overlaps the other's body.  Measured at batch 64 (one
@@ -532,23 +565,6 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
                 break;
             default: {
                 if (op.kind == OP_FUSE && op.i0 == 1 && !debug) break;
-                if (!ev && op.kind == OP_GEMM && bneck1_head(oi, batch, last_op)) {      // an identity bottleneck as one launch (bneck_bf16.hip, DS = false)
-                    const int tri[3] = {oi, oi + 1, oi + 2};
-                    if (log) HIP_TRY(log->mark(s, tri, 3));
-                    HIP_TRY(launch_bneck1_bf16(gemm_args(op, batch), gemm_args(ops[oi + 1], batch), gemm_args(ops[oi + 2], batch),
-                                               debug || last_op < (int)ops.size(), s));
-                    oi += 2;
-                    break;
-                }
-                // a 64 -> 256 pointwise conv directly followed by the 256 -> 64 one that reads it (layer1's conv3 -> next conv1): one launch
-                if (!ev && pwchain_head(oi, batch, last_op)) {
-                    const int pair[2] = {oi, oi + 1};
-                    if (log) HIP_TRY(log->mark(s, pair, 2));
-                    if (op.bf16) HIP_TRY(launch_gemm_bf16_pwchain(gemm_args(op, batch), gemm_args(ops[oi + 1], batch), s));
-                    else HIP_TRY(launch_gemm_f32_pwchain(gemm_args(op, batch), gemm_args(ops[oi + 1], batch), s));
-                    ++oi;
-                    break;
-                }
                 if (log) HIP_TRY(log->mark(s, &oi, 1));
                 int rc = exec_op(op, s, batch);
                 if (rc) return rc;
@@ -1276,54 +1292,22 @@ int capf_num_ops(const capf_handle* h) { return h ? (int)h->e.ops.size() : CAPF_
 int capf_op_info(const capf_handle* h, int index, int batch, const char** name, const char** kernel, double* flops) {
     if (!h || index < 0 || index >= (int)h->e.ops.size() || batch <= 0) return CAPF_ERR_INVALID;
     const capf::Op& op = h->e.ops[index];
-    static const char* kn[] = {"", "fuse_sum", "maxpool3x3s2", "bilinear_resize", "prep_embed", "sample_ref",
-                               "layernorm", "deform_sample", "attention", "head", "", "", "embed", "ctx_attn", "res_chain", "mlp_chain"};
     if (name) *name = op.name.c_str();
-    const int n_all = (int)h->e.ops.size();
-    if (kernel && op.kind == capf::OP_GEMM && h->e.bneck1_member(index, batch) >= 0) {
-        *kernel = capf::bneck1_bf16_kernel_name();                      // (the block's three convs ride in one launch)
-        if (flops) *flops = op.flops_per_frame * batch;
-        return CAPF_OK;
-    }
-    if (kernel && op.kind == capf::OP_GEMM && h->e.bneck0_member(index, batch) >= 0) {
-        *kernel = capf::bneck0_bf16_kernel_name();                      // (the block's four convs ride in one launch)
-        if (flops) *flops = op.flops_per_frame * batch;
-        return CAPF_OK;
-    }
-    if (kernel && (h->e.pwchain_head(index, batch, n_all) || h->e.pwchain_head(index - 1, batch, n_all))) {
-        *kernel = op.bf16 ? capf::gemm_bf16_pwchain_kernel_name() : capf::gemm_f32_pwchain_kernel_name();      // (both ops ride in one launch)
-        if (name) *name = op.name.c_str();
-        if (flops) *flops = op.flops_per_frame * batch;
-        return CAPF_OK;
-    }
-    if (kernel) *kernel = op.kind != capf::OP_GEMM ? kn[op.kind] : (op.bf16 == 2 ? capf::gemm_bf16_rows_kernel_name((int)(op.rows_per_frame * batch), op.N)
-                                                                      : op.bf16 ? capf::gemm_bf16_kernel_name(h->e.gemm_args(op, batch))
-                                                                      : h->e.wino_now(op, batch) ? capf::gemm_wino_kernel_name(h->e.gemm_args(op, batch))
-                                                                              : capf::gemm_f32_kernel_name(h->e.gemm_args(op, batch)));
     if (flops) *flops = op.flops_per_frame * batch;
+    if (kernel) {                                                  // (the ops of a fused launch are named by that launch)
+        const capf::Engine::FusedLaunch f = h->e.fused_leader(index, batch);
+        *kernel = f.kind == capf::Engine::Fusion::BNECK0 ? capf::bneck0_bf16_kernel_name()
+                  : f.kind == capf::Engine::Fusion::BNECK1 ? capf::bneck1_bf16_kernel_name()
+                  : f.kind == capf::Engine::Fusion::PWCHAIN ? (op.bf16 ? capf::gemm_bf16_pwchain_kernel_name() : capf::gemm_f32_pwchain_kernel_name())
+                  : h->e.op_route(op, batch).kernel;
+    }
     return CAPF_OK;
 }
 
-// FLOPs the MFMA pipe is asked to execute for one op at `batch` (2 x MACs issued, K padding included, tile-edge padding
-// not): the Winograd kernels issue 18 (F(4,3), per four outputs) or 12 (F(2,3), per two) MACs per (cin, cout) where the
-// direct conv issues 36 / 18, i.e. 1/2 or 2/3 of the algorithmic count capf_op_info reports; the split-fp32 tile (igemm_f32x3_ws.hip)
-// issues six bf16 MACs per fp32 MAC -- on the bf16 pipe, whose peak is 16 x the fp32 pipe's.
+// FLOPs the MFMA pipe is asked to execute for one op at `batch` (Engine::op_route)
 int capf_op_executed_flops(const capf_handle* h, int index, int batch, double* flops) {
     if (!h || index < 0 || index >= (int)h->e.ops.size() || batch <= 0 || !flops) return CAPF_ERR_INVALID;
-    const capf::Engine& e = h->e;
-    const capf::Op& op = e.ops[index];
-    *flops = op.flops_per_frame * batch;
-    if (op.kind != capf::OP_GEMM) return CAPF_OK;
-    const capf::Pack& pk = e.packs[op.pack];
-    const double MN = 2.0 * (double)op.rows_per_frame * batch * op.N;
-    if (op.conv && e.wino_now(op, batch) && pk.x3 && capf::gemm_f32x3_wanted(e.gemm_args(op, batch)))
-        *flops = (e.x3_h2 ? 3.0 : 6.0) * MN * op.K;               // split-fp32 tiles: three fp16 / six bf16 piece products per fp32 product, on the 16-bit pipe
-    else if (op.conv && e.wino_now(op, batch)) *flops = MN * op.Cin * (pk.Kpad == 18 * pk.Cin ? 4.5 : 6.0);
-    else if (const capf::GemmArgs ga = e.gemm_args(op, batch); !op.bf16 && capf::gemm_f32_on_h2g(ga))
-        *flops = 3.0 * MN * pk.KpadH;                              // two-fp16-piece GEMM: three piece products per fp32 product, on the 16-bit pipe
-    else if (op.wino) *flops = MN * pk.Kpad2;                      // small batch: the direct kernel on the direct layout
-    else if (pk.rh && op.conv) *flops = MN * op.K;                 // row-halo layout has no K padding (decided per launch; lower bound)
-    else *flops = MN * (pk.direct ? op.K : pk.Kpad);
+    *flops = h->e.op_route(h->e.ops[index], batch).flops;
     return CAPF_OK;
 }
 

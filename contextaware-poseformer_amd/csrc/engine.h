@@ -304,8 +304,21 @@ struct Engine {
     int run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t* ev = nullptr, LaunchLog* log = nullptr);
     int exec_op(const Op& op, hipStream_t s, int batch);
     FuseSumArgs fuse_args(const Op& op, int batch) const;
-    // op i and op i + 1 are a 64 -> 256 / 256 -> 64 pointwise conv pair that runs as ONE launch at this batch (igemm_f32_pwchain.hip)
-    bool pwchain_head(int i, int batch, int last_op) const;
+    // ---- launch routes: pure functions of (op, batch) and the plan, like wino_now
+    // Which family's launcher runs a GEMM op (exec_op; run_region_grouped's pass that may group it), and what the op reports: the kernel that
+    // runs it on its own (capf_op_info) and the FLOPs that kernel issues (capf_op_executed_flops)
+    enum class Family { NONE = -1, F32, BF16, WINO, BF16_ROWS };
+    struct OpRoute { Family family; const char* kernel; double flops; };
+    Family gemm_family(const Op& op, int batch) const;
+    OpRoute op_route(const Op& op, int batch) const;
+    // Several ops as ONE launch: a first bottleneck (bneck_bf16.hip; at its fork op, m = {conv1, conv2, downsample, conv3}), an identity
+    // bottleneck (256 -> 64 -> 64 -> 256, y = relu(conv3 + x); m = {conv1, conv2, conv3}), a 64 -> 256 / 256 -> 64 pointwise conv pair
+    // (igemm_*_pwchain.hip; m = {a, b}).  fused_at: the launch that starts at op i in a run ending before last_op (n = 0: none; bneck_only:
+    // bottlenecks alone).  fused_leader: the launch op i rides in in a whole forward (its leader is m[0])
+    enum class Fusion { NONE, BNECK0, BNECK1, PWCHAIN };
+    struct FusedLaunch { Fusion kind = Fusion::NONE; int n = 0; int m[4] = {-1, -1, -1, -1}; };
+    FusedLaunch fused_at(int i, int batch, int last_op, bool bneck_only = false) const;
+    FusedLaunch fused_leader(int i, int batch, bool bneck_only = false) const;
     bool use_pwchain = true;       // plan_flags & CAPF_PLAN_NO_PWCHAIN clears it
     bool has_res_chain = false;    // the plan holds an OP_RES_CHAIN (lifter_chain.hip): its two-piece packs are needed at every batch
     std::vector<unsigned> utab_host;     // the unit tables of the two-fp16-piece conv tile, one per map geometry (H, W, Cin) of the plan (build())
@@ -313,13 +326,6 @@ struct Engine {
     bool utab_on_device = false;
     bool use_bneck = true;         // plan_flags & CAPF_PLAN_NO_BNECK clears it
     bool batch_reduce = true;      // plan_flags & CAPF_PLAN_NO_BATCHED_REDUCE clears it: the backward's second-stage reductions one launch each
-    // op i opens the fork / join region of a first bottleneck (conv1, conv2 | downsample) directly followed by its conv3, and the block runs as
-    // ONE launch at this batch (bneck_bf16.hip); m = {conv1, conv2, downsample, conv3}
-    bool bneck0_head(int i, int batch, int last_op, int m[4]) const;
-    int bneck0_member(int i, int batch) const;       // op i rides in such a launch: index of its fork op, -1 otherwise
-    // ops i, i + 1, i + 2 are an identity bottleneck (conv1 256 -> 64, conv2 3x3, conv3 64 -> 256 + conv1's input) that runs as ONE launch at this batch
-    bool bneck1_head(int i, int batch, int last_op) const;
-    int bneck1_member(int i, int batch) const;       // op i rides in such a launch: index of its conv1, -1 otherwise
     bool use_upadd = true;         // plan_flags & CAPF_PLAN_NO_UPADD clears it (CPN bf16: lateral conv + upsampled add in one launch)
     int run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* log, unsigned lane_mask = ~0u);
     GemmArgs gemm_args(const Op& op, int batch, bool planes = true) const;

@@ -1499,13 +1499,24 @@ bool gemm_bf16_upadd_ok(const GemmArgs& a) {
            (double)(a.M / (a.Ho * a.Wo)) * a.up_H * a.up_W * a.N * 2.0 < 2.0e9;
 }
 
+Bf16Route gemm_bf16_route(const GemmArgs& a) {
+    if (gemm_bf16_ws_wanted(a)) return {Bf16Path::WS, false};
+    const bool pp = (long)((a.M + 127) / 128) * ((a.N + 63) / 64) >= pp_min_tiles();
+    if (pp && a.Wp2 && gemm_bf16_rh_cw(a)) return {Bf16Path::RH, true};
+    if (a.N <= 32) return {Bf16Path::T128x32, pp};
+    if (a.N <= 64) return {(long)a.M >= 128L * 512 ? Bf16Path::T128x64 : Bf16Path::T64x64, pp};
+    return {(long)((a.M + 127) / 128) * ((a.N + 127) / 128) >= 512 ? Bf16Path::T128x128 : Bf16Path::T64x64, pp};
+}
+
 const char* gemm_bf16_kernel_name(const GemmArgs& a) {
-    if (gemm_bf16_ws_wanted(a)) return gemm_bf16_ws_kernel_name(a);
-    if (a.Wp2 && gemm_bf16_rh_cw(a) && (long)((a.M + 127) / 128) * ((a.N + 63) / 64) >= pp_min_tiles()) return "igemm_bf16_rh<w4,126x64,conv>";
-    if (a.N <= 32) return "igemm_bf16<w4,128x32,conv>";
-    if (a.N <= 64) return ((long)a.M >= 128L * 512) ? "igemm_bf16<w4,128x64,conv>" : "igemm_bf16<w4,64x64,conv>";
-    if ((long)((a.M + 127) / 128) * ((a.N + 127) / 128) >= 512) return "igemm_bf16<w4,128x128,conv>";
-    return "igemm_bf16<w4,64x64,conv>";
+    switch (gemm_bf16_route(a).path) {
+        case Bf16Path::WS: return gemm_bf16_ws_kernel_name(a);
+        case Bf16Path::RH: return "igemm_bf16_rh<w4,126x64,conv>";
+        case Bf16Path::T128x32: return "igemm_bf16<w4,128x32,conv>";
+        case Bf16Path::T128x64: return "igemm_bf16<w4,128x64,conv>";
+        case Bf16Path::T128x128: return "igemm_bf16<w4,128x128,conv>";
+        default: return "igemm_bf16<w4,64x64,conv>";
+    }
 }
 
 // bf16 NHWC conv: A / res / out are bf16, Wp bf16 [N][Kpad] (Kpad % 64 == 0), bias fp32.  Cin % 8 == 0, N % 4 == 0.
@@ -1534,7 +1545,7 @@ hipError_t launch_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t s, in
         GemmArgs wsl[MAXG], rest[MAXG];
         int nws = 0, nrest = 0;
         for (int i = 0; i < n; ++i) {
-            if (gemm_bf16_ws_wanted(list[i])) wsl[nws++] = list[i];
+            if (gemm_bf16_route(list[i]).path == Bf16Path::WS) wsl[nws++] = list[i];
             else rest[nrest++] = list[i];
         }
         if (nws) {
@@ -1610,28 +1621,29 @@ hipError_t launch_gemm_bf16(const GemmArgs& a_in, hipStream_t s) {
         a_in.ks * a_in.ks > 32)   // 32-bit tap masks
         return hipErrorInvalidValue;
     GemmArgs a = a_in;
-    a.fd_hw = make_fastdiv((unsigned)(a.Ho * a.Wo));
-    a.fd_wo = make_fastdiv((unsigned)a.Wo);
-    a.spread = 0ull;
-    for (int kh = 0; kh < a.ks && kh * a.ks < 64; ++kh) a.spread |= 1ull << (kh * a.ks);
+    prep_conv_b(a);
     if (a.up && !gemm_bf16_upadd_ok(a)) return hipErrorInvalidValue;
-    if (gemm_bf16_ws_wanted(a)) return launch_gemm_bf16_ws(a, s);
-    const long tiles128 = (long)((a.M + 127) / 128) * ((a.N + 63) / 64);
-    if (tiles128 >= pp_min_tiles()) {
-        if (a.Wp2 && gemm_bf16_rh_cw(a)) {
+    const Bf16Route r = gemm_bf16_route(a);
+    switch (r.path) {
+        case Bf16Path::WS: return launch_gemm_bf16_ws(a, s);
+        case Bf16Path::RH:
             a.Wp = a.Wp2;
             a.Kpad = 9 * a.Cin;
             return launch_gemm_bf16_rh(a, s);
-        }
-        if (a.N <= 32) return launch_cfg_b<128, 32, 32, 32, 1>(a, s);
-        if (a.N <= 64) return ((long)a.M >= 128L * 512) ? launch_cfg_b<128, 64, 64, 32, 1>(a, s) : launch_cfg_b<64, 64, 32, 32, 1>(a, s);
-        if ((long)((a.M + 127) / 128) * ((a.N + 127) / 128) >= 512) return launch_cfg_b<128, 128, 64, 64, 1>(a, s);
-        return launch_cfg_b<64, 64, 32, 32, 1>(a, s);
+        default: break;
     }
-    if (a.N <= 32) return launch_cfg_b<128, 32, 32, 32, 3>(a, s);
-    if (a.N <= 64) return ((long)a.M >= 128L * 512) ? launch_cfg_b<128, 64, 64, 32, 3>(a, s) : launch_cfg_b<64, 64, 32, 32, 3>(a, s);
-    if ((long)((a.M + 127) / 128) * ((a.N + 127) / 128) >= 512) return launch_cfg_b<128, 128, 64, 64, 2>(a, s);
-    return launch_cfg_b<64, 64, 32, 32, 3>(a, s);
+    if (r.pp) switch (r.path) {                                  // (one K stage: the ping-pong schedule)
+        case Bf16Path::T128x32: return launch_cfg_b<128, 32, 32, 32, 1>(a, s);
+        case Bf16Path::T128x64: return launch_cfg_b<128, 64, 64, 32, 1>(a, s);
+        case Bf16Path::T64x64: return launch_cfg_b<64, 64, 32, 32, 1>(a, s);
+        default: return launch_cfg_b<128, 128, 64, 64, 1>(a, s);
+    }
+    switch (r.path) {
+        case Bf16Path::T128x32: return launch_cfg_b<128, 32, 32, 32, 3>(a, s);
+        case Bf16Path::T128x64: return launch_cfg_b<128, 64, 64, 32, 3>(a, s);
+        case Bf16Path::T64x64: return launch_cfg_b<64, 64, 32, 32, 3>(a, s);
+        default: return launch_cfg_b<128, 128, 64, 64, 2>(a, s);
+    }
 }
 
 // The lifter's projections on the bf16 MFMA path: out[omap(m) + n] = f(A[m, :K] . W[n, :K] + bias[n]) with A bf16 [M][K]

@@ -1004,24 +1004,6 @@ static bool stem_on_bf16(const GemmArgs& a) {
 // either kernel, tools/bench_pw_h2.py), everything else with a two-piece pack leaves the fp32 pipe (256 -> 64: 106 -> 75 us at batch 64,
 // 687 -> 524 at 512; the fuse layers' 1x1 convs at batch 512, which as a GROUP never reached the pointwise kernel anyway)
 static bool pw_preferred(const GemmArgs& a) { return gemm_f32_pw_ok(a) && (!gemm_f32h2g_ok(a) || a.N >= 4 * a.K); }
-bool gemm_f32_on_h2g(const GemmArgs& a) { return gemm_f32h2g_ok(a) && !pw_preferred(a); }
-
-const char* gemm_f32_kernel_name(const GemmArgs& a) {
-    static char buf[N_TILES][2][48];
-    static bool init = false;
-    if (!init) {
-        const char* modes[2] = {"rows", "conv"};
-        for (int t = 0; t < N_TILES; ++t)
-            for (int m = 0; m < 2; ++m) snprintf(buf[t][m], sizeof(buf[t][m]), "igemm_f32<%s,%s>", kTileNames[t], modes[m]);
-        init = true;
-    }
-    if (a.conv && a.Cin % 4 != 0)
-        return stem_on_bf16(a) ? gemm_bf16_smallc_kernel_name(a) : (stem_stream_f32_ok(a) ? "igemm_f32_stem_stream<w4,64x64>" : "igemm_f32_smallc<w4,128x64>");
-    if (pw_preferred(a)) return gemm_f32_pw_kernel_name();
-    if (gemm_f32h2g_ok(a)) return gemm_f32h2g_kernel_name(a, false);
-    if (gemm_f32_rows_splitk(a)) return "igemm_f32_rows_splitk";
-    return buf[pick_tile(a)][a.conv ? 1 : 0];
-}
 
 template <int NW, int BM, int BN, int WM, int WN, int S>
 static hipError_t launch_cfg(const GemmArgs& a, hipStream_t s) {
@@ -1109,16 +1091,47 @@ bool gemm_f32_rows_splitk(const GemmArgs& a) {
     return sp > 1 && (long)a.M * a.N * sp <= a.split_ws_elems && tiles <= a.split_cnt_elems && (double)a.M * (double)a.omap.S1 < 4.0e9;
 }
 
+F32Route gemm_f32_route(const GemmArgs& a) {
+    if (pw_preferred(a)) return {F32Path::PW, 0};
+    if (gemm_f32h2g_ok(a)) return {F32Path::H2G, 0};
+    if (worth_splitting(a)) return {F32Path::SPLITK_GROUP, 0};
+    if (gemm_f32_rows_splitk(a)) return {F32Path::ROWS_SPLITK, 0};
+    if (a.conv && a.Cin % 4 != 0) return {stem_on_bf16(a) ? F32Path::STEM_BF16 : stem_stream_f32_ok(a) ? F32Path::STEM_STREAM : F32Path::SMALLC, 0};
+    return {F32Path::TILE, pick_tile(a)};
+}
+
+const char* gemm_f32_kernel_name(const GemmArgs& a) {
+    static char buf[N_TILES][2][48];
+    static bool init = false;
+    if (!init) {
+        const char* modes[2] = {"rows", "conv"};
+        for (int t = 0; t < N_TILES; ++t)
+            for (int m = 0; m < 2; ++m) snprintf(buf[t][m], sizeof(buf[t][m]), "igemm_f32<%s,%s>", kTileNames[t], modes[m]);
+        init = true;
+    }
+    const F32Route r = gemm_f32_route(a);
+    switch (r.path) {
+        case F32Path::PW: return gemm_f32_pw_kernel_name();
+        case F32Path::H2G: return gemm_f32h2g_kernel_name(a, false);
+        case F32Path::SPLITK_GROUP: return "igemm_f32_group";
+        case F32Path::ROWS_SPLITK: return "igemm_f32_rows_splitk";
+        case F32Path::STEM_BF16: return gemm_bf16_smallc_kernel_name(a);
+        case F32Path::STEM_STREAM: return "igemm_f32_stem_stream<w4,64x64>";
+        case F32Path::SMALLC: return "igemm_f32_smallc<w4,128x64>";
+        default: return buf[r.tile][a.conv ? 1 : 0];
+    }
+}
+
 hipError_t launch_gemm_f32_group(const GemmArgs* list, int n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    if (n == 1 && !worth_splitting(list[0])) return launch_gemm_f32(list[0], s);
+    if (n == 1 && gemm_f32_route(list[0]).path != F32Path::SPLITK_GROUP) return launch_gemm_f32(list[0], s);
     if (n > MAXG) return hipErrorInvalidValue;
     {   // problems that carry the two-fp16-piece pack (GemmArgs::Wh2, igemm_f32h2.hip) go out as their own grid; the HBM-bound pointwise
         // convs keep their kernel (launch_gemm_f32 routes them)
         GemmArgs h2[MAXG], rest[MAXG];
         int nh = 0, nr = 0;
         for (int i = 0; i < n; ++i) {
-            if (gemm_f32_on_h2g(list[i])) h2[nh++] = list[i];
+            if (gemm_f32_route(list[i]).path == F32Path::H2G) h2[nh++] = list[i];
             else rest[nr++] = list[i];
         }
         if (nh) {
@@ -1220,20 +1233,24 @@ hipError_t launch_gemm_f32_group(const GemmArgs* list, int n, hipStream_t s) {
 hipError_t launch_gemm_f32(const GemmArgs& a_in, hipStream_t s) {
     if (a_in.M <= 0 || a_in.N <= 0) return hipSuccess;
     if (a_in.Kpad % BK != 0) return hipErrorInvalidValue;
-    if (pw_preferred(a_in)) return launch_gemm_f32_pw(a_in, s);
-    if (gemm_f32h2g_ok(a_in)) return launch_gemm_f32h2g(a_in, s);
-    if (a_in.splits <= 1 && worth_splitting(a_in)) return launch_gemm_f32_group(&a_in, 1, s);
+    const F32Route r = gemm_f32_route(a_in);
     GemmArgs a = a_in;
-    if (gemm_f32_rows_splitk(a_in)) {                                      // a handful of tiles with a long K loop: slices + in-launch reduction
-        const int chunks = a.Kpad / BK, tiles = ((a.M + 63) / 64) * ((a.N + 63) / 64);
-        int sp = std::min(8, chunks / 6);
-        a.cps = (chunks + sp - 1) / sp;
-        a.splits = (chunks + a.cps - 1) / a.cps;
-        a.split_stride = (long)a.M * a.N;
-        if (a.rs_div <= 0) a.rs_div = 1;
-        if (a.act == ACT_GELU) hipLaunchKernelGGL(igemm_f32_rows_splitk_kernel<true>, dim3(tiles * a.splits), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(igemm_f32_rows_splitk_kernel<false>, dim3(tiles * a.splits), dim3(256), 0, s, a);
-        return hipGetLastError();
+    switch (r.path) {
+        case F32Path::PW: return launch_gemm_f32_pw(a_in, s);
+        case F32Path::H2G: return launch_gemm_f32h2g(a_in, s);
+        case F32Path::SPLITK_GROUP: return launch_gemm_f32_group(&a_in, 1, s);
+        case F32Path::ROWS_SPLITK: {                                           // a handful of tiles with a long K loop: slices + in-launch reduction
+            const int chunks = a.Kpad / BK, tiles = ((a.M + 63) / 64) * ((a.N + 63) / 64);
+            int sp = std::min(8, chunks / 6);
+            a.cps = (chunks + sp - 1) / sp;
+            a.splits = (chunks + a.cps - 1) / a.cps;
+            a.split_stride = (long)a.M * a.N;
+            if (a.rs_div <= 0) a.rs_div = 1;
+            if (a.act == ACT_GELU) hipLaunchKernelGGL(igemm_f32_rows_splitk_kernel<true>, dim3(tiles * a.splits), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(igemm_f32_rows_splitk_kernel<false>, dim3(tiles * a.splits), dim3(256), 0, s, a);
+            return hipGetLastError();
+        }
+        default: break;
     }
     a.split_ws = nullptr; a.split_cnt = nullptr;                           // (the in-kernel reduction belongs to the grouped / split kernels)
     if (a.splits <= 1) { a.splits = 1; a.cps = a.Kpad / BK; a.split_stride = 0; }
@@ -1247,23 +1264,24 @@ hipError_t launch_gemm_f32(const GemmArgs& a_in, hipStream_t s) {
         const double span = ((double)a.M / g + 1.0) * (double)a.amap.S1 + g * (double)a.amap.S2 + (double)a.amap.off + a.Kpad;
         if (span * 4.0 >= 4.0e9) return hipErrorInvalidValue;
     }
-    if (a.conv) {
-        if (!prep_conv(a)) return hipErrorInvalidValue;
-        if (a.Cin % 4 != 0) {
-            if (stem_on_bf16(a)) return launch_gemm_bf16_smallc(a, s);
-            if (stem_stream_f32_ok(a)) {
-                const int ntiles = (a.M + 63) / 64;
-                int blocks = 512;                          // two per CU
-                while (blocks > 8 && blocks / 2 >= ntiles) blocks /= 2;
-                hipLaunchKernelGGL((igemm_f32_stem_stream_kernel<3>), dim3(blocks), dim3(256), 0, s, a, ntiles);
-                return hipGetLastError();
-            }
+    if (a.conv && !prep_conv(a)) return hipErrorInvalidValue;
+    switch (r.path) {
+        case F32Path::STEM_BF16: return launch_gemm_bf16_smallc(a, s);
+        case F32Path::STEM_STREAM: {
+            const int ntiles = (a.M + 63) / 64;
+            int blocks = 512;                          // two per CU
+            while (blocks > 8 && blocks / 2 >= ntiles) blocks /= 2;
+            hipLaunchKernelGGL((igemm_f32_stem_stream_kernel<3>), dim3(blocks), dim3(256), 0, s, a, ntiles);
+            return hipGetLastError();
+        }
+        case F32Path::SMALLC: {
             dim3 grid(((a.M + 127) / 128) * ((a.N + 63) / 64)), block(256);
             hipLaunchKernelGGL((igemm_f32_smallc_kernel<128, 64, 64, 32>), grid, block, 0, s, a);
             return hipGetLastError();
         }
+        default: break;
     }
-    switch (pick_tile(a)) {
+    switch (r.tile) {
         case W4_128x64: return launch_cfg<4, 128, 64, 64, 32, 2>(a, s);
         case W4_64x64: return launch_cfg<4, 64, 64, 32, 32, 3>(a, s);
         case W4_128x128: return launch_cfg<4, 128, 128, 64, 64, 2>(a, s);

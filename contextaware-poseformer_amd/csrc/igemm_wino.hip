@@ -1462,24 +1462,30 @@ static hipError_t launch_wino43_group(const GemmArgs* prep, const int* cfgs, int
     return hipGetLastError();
 }
 
+// (large launches: the split-fp32 tile, igemm_f32x3_ws.hip; F(4,3) problems, alone or grouped, run igemm_wino43_group_kernel)
+WinoPath gemm_wino_route(const GemmArgs& a) {
+    if (gemm_f32x3_wanted(a)) return WinoPath::X3;
+    return is43(a) && wino43_short() ? WinoPath::F43_GROUP : WinoPath::WINO;
+}
+
+const char* gemm_wino_kernel_name(const GemmArgs& a) {
+    const WinoPath p = gemm_wino_route(a);
+    return p == WinoPath::X3 ? gemm_f32x3_kernel_name(a) : p == WinoPath::F43_GROUP ? "igemm_wino43_group" : "igemm_wino<w4,F(2,3)>";
+}
+
 hipError_t launch_gemm_wino(const GemmArgs& a_in, hipStream_t s) {
-    if (gemm_f32x3_wanted(a_in)) return launch_gemm_f32x3(a_in, s);       // (large launches: the split-fp32 tile, igemm_f32x3_ws.hip)
+    const WinoPath path = gemm_wino_route(a_in);
+    if (path == WinoPath::X3) return launch_gemm_f32x3(a_in, s);
     GemmArgs a = a_in;
     if (!wino_prepare(a)) return hipErrorInvalidValue;
     hipError_t r = wino_attr();
     if (r != hipSuccess) return r;
     const int cfg = wino_cfg(a);
-    if (cfg >= 3 && wino43_short()) return launch_wino43_group(&a, &cfg, 1, s);
+    if (path == WinoPath::F43_GROUP) return launch_wino43_group(&a, &cfg, 1, s);
     const int nb = wino_tiles(a, cfg);
     if (wino_mode() == 1) hipLaunchKernelGGL(igemm_wino_kernel<false>, dim3(nb), dim3(256), WLDS * sizeof(float), s, a, cfg);
     else hipLaunchKernelGGL(igemm_wino_kernel<true>, dim3(nb), dim3(256), kWLDS[cfg] * sizeof(float), s, a, cfg);
     return hipGetLastError();
-}
-
-// what rocprofv3 will call the launch: F(4,3) problems (alone or grouped) run igemm_wino43_group_kernel
-const char* gemm_wino_kernel_name(const GemmArgs& a) {
-    if (gemm_f32x3_wanted(a)) return gemm_f32x3_kernel_name(a);
-    return (a.Kpad == 18 * a.Cin && wino43_short()) ? "igemm_wino43_group" : "igemm_wino<w4,F(2,3)>";
 }
 
 hipError_t launch_gemm_wino_group(const GemmArgs* list, int n, hipStream_t s) {
@@ -1490,7 +1496,7 @@ hipError_t launch_gemm_wino_group(const GemmArgs* list, int n, hipStream_t s) {
         GemmArgs x3[MAXG], rest[MAXG];
         int nx = 0, nrest = 0;
         for (int i = 0; i < n; ++i) {
-            if (gemm_f32x3_wanted(list[i])) x3[nx++] = list[i];
+            if (gemm_wino_route(list[i]) == WinoPath::X3) x3[nx++] = list[i];
             else rest[nrest++] = list[i];
         }
         if (nx) {
@@ -1511,8 +1517,7 @@ hipError_t launch_gemm_wino_group(const GemmArgs* list, int n, hipStream_t s) {
         for (int i = 0; i < n; ++i) {
             GemmArgs a = list[i];
             if (!wino_prepare(a)) return hipErrorInvalidValue;
-            const int cfg = wino_cfg(a);
-            if (cfg >= 3) { p43[n43] = a; c43[n43++] = cfg; }
+            if (gemm_wino_route(list[i]) == WinoPath::F43_GROUP) { p43[n43] = a; c43[n43++] = wino_cfg(a); }
             else rest[nrest++] = list[i];
         }
         if (n43) {

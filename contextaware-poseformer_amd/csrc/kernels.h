@@ -165,7 +165,13 @@ static constexpr int MAXG = 8;
 bool gemm_f32_groupable(const GemmArgs& a);
 bool gemm_f32_rows_splitk(const GemmArgs& a);        // rows-mode GEMM that launch_gemm_f32 splits along K (few tiles, long K, scratch lent)
 hipError_t launch_gemm_f32_group(const GemmArgs* list, int n, hipStream_t s);
-const char* gemm_f32_kernel_name(const GemmArgs& a);   // which template instantiation launch_gemm_f32 picks
+// The path launch_gemm_f32 takes for a problem, in its order: the pointwise kernel, the two-fp16-piece GEMM (igemm_f32h2.hip), a lone conv
+// split along K on the grouped kernel, a rows-mode GEMM split along K, the Cin = 3 stem (bf16 MFMA / streaming / small-C kernel), the tile
+// kernel (tile = its configuration).  One decision: the launcher switches on it, gemm_f32_kernel_name names it, the engine counts by it
+enum class F32Path { PW, H2G, SPLITK_GROUP, ROWS_SPLITK, STEM_BF16, STEM_STREAM, SMALLC, TILE };
+struct F32Route { F32Path path; int tile; };
+F32Route gemm_f32_route(const GemmArgs& a);
+const char* gemm_f32_kernel_name(const GemmArgs& a);   // what rocprofv3 calls the launch of launch_gemm_f32
 // fp32 pointwise (1x1 / stride 1) conv for the HBM-bound bottleneck convs of layer1 (igemm_f32_pw.hip): ping-pong schedule,
 // coalesced epilogue with prefetched residual; launch_gemm_f32 routes eligible problems (>= 2048 tiles) to it
 bool gemm_f32_pw_ok(const GemmArgs& a);
@@ -195,6 +201,9 @@ const char* gemm_bf16_pwchain_kernel_name();
 bool gemm_wino_ok(const GemmArgs& a);
 hipError_t launch_gemm_wino(const GemmArgs& a, hipStream_t s);
 hipError_t launch_gemm_wino_group(const GemmArgs* list, int n, hipStream_t s);
+// the path launch_gemm_wino takes: the split-fp32 tile (gemm_f32x3_wanted), the F(4,3) group kernel, the single-problem Winograd kernel
+enum class WinoPath { X3, F43_GROUP, WINO };
+WinoPath gemm_wino_route(const GemmArgs& a);
 const char* gemm_wino_kernel_name(const GemmArgs& a);
 hipError_t launch_pack_conv_wino(const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
                                  float eps, float* Wp, float* bias, int Cout, int Cin, hipStream_t s, int variant = 23);
@@ -217,6 +226,11 @@ bool gemm_bf16_upadd_ok(const GemmArgs& a);      // a.up (post-activation upsamp
 // 1 ping-pong (igemm_bf16_group_pp_kernel), 2 ping-pong with row-halo tiles (igemm_bf16_group_rh_kernel), 3 the 2-D halo tile
 // (igemm_bf16_group_ws_kernel; problems of the list it cannot take go out as a second, ring / ping-pong launch), -1 single launch
 hipError_t launch_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t s, int* variant = nullptr);
+// the path launch_gemm_bf16 takes: the 2-D halo tile (gemm_bf16_ws_wanted), the row-halo tile, or one of the four tile shapes of
+// igemm_bf16_kernel; pp: a launch of >= 2048 tiles (ping-pong schedule, the row-halo tile's condition)
+enum class Bf16Path { WS, RH, T128x32, T128x64, T64x64, T128x128 };
+struct Bf16Route { Bf16Path path; bool pp; };
+Bf16Route gemm_bf16_route(const GemmArgs& a);
 const char* gemm_bf16_kernel_name(const GemmArgs& a);
 // row-halo variant of the 3x3 / stride-1 bf16 conv (one staged A tile serves the three kw taps): chunk width 64 / 48 / 32 or
 // 0 = not eligible; weights packed by launch_pack_conv_bf16_rh ([N][9 * Cin], K order (kh, Cin / CW, kw, CW))
@@ -270,7 +284,6 @@ hipError_t launch_pack_conv_f32h2(const float* w, const float* gamma, const floa
 // 32 rows and 32-deep chunk); weights packed by launch_pack_f32h2_gemm over the fp32 pack's geometry (GemmArgs::Wh2)
 long f32h2_gemm_pack_elems(int N, int Kpad);            // floats
 bool gemm_f32h2g_ok(const GemmArgs& a);
-bool gemm_f32_on_h2g(const GemmArgs& a);               // ... and launch_gemm_f32 / _group send it there (igemm_f32.hip: not the pointwise kernel's expansions)
 hipError_t launch_gemm_f32h2g(const GemmArgs& a, hipStream_t s);
 hipError_t launch_gemm_f32h2g_group(const GemmArgs* list, int n, hipStream_t s);     // convs with plain row maps, one grid
 const char* gemm_f32h2g_kernel_name(const GemmArgs& a, bool grouped);

@@ -213,7 +213,7 @@ static Tensor hr_basic_block(Engine& e, const std::string& p, const Tensor& x) {
     return out;
 }
 
-// A first bottleneck whose five ops may run as ONE kernel (bneck_bf16.hip; Engine::bneck0_head decides per batch): that kernel reads x while it
+// A first bottleneck whose five ops may run as ONE kernel (bneck_bf16.hip; Engine::fused_at decides per batch): that kernel reads x while it
 // writes y and -- in the variant the layer-wise tests run -- conv1's, conv2's and the shortcut's outputs too, so all five tensors stay alive
 // (no two of them share workspace) from conv1 to conv3; the ops remember conv3 (capf_op_describe: their checkpoint is the whole block).
 // `fork` = index of the region's fork op: fork, conv1, conv2, downsample, join, conv3.

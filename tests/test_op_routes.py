@@ -1,0 +1,41 @@
+"""CPU: the engine's launch routes -- the kernel capf_op_info names for every op, its algorithmic FLOPs, capf_op_bytes and
+capf_op_executed_flops -- equal tests/golden/op_routes.npz exactly, for every plan and batch of tools/dump_op_routes.py's matrix
+(HRNet-32 / HRNet-48 / CPN, fp32 and bf16, the plan flags that move routes, batches 1 .. 512).  The fixture comes from this
+engine at the commit it names (`base_commit`), not from the reference.
+
+A change that moves a route on purpose regenerates the fixture and says in its description which rows moved:
+
+    python -c "import __graft_entry__ as g; g.build()" && python tools/dump_op_routes.py
+"""
+import importlib.util
+import os
+
+import numpy as np
+
+from conftest import ROOT, load_golden
+
+
+def _tool():
+    spec = importlib.util.spec_from_file_location("dump_op_routes", os.path.join(ROOT, "tools", "dump_op_routes.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_op_routes_match_fixture():
+    tool = _tool()
+    want = load_golden("op_routes")
+    got = tool.to_arrays(tool.collect())
+    assert list(want["batches"]) == list(got["batches"])
+    ws, gs = want["strings"], got["strings"]
+    keys = sorted(k for k in got if "." in k)
+    assert keys == sorted(k for k in want.files if "." in k)
+    for k in keys:
+        w, g = want[k], got[k]
+        assert w.shape == g.shape, k
+        if k.endswith(".op") or k.endswith(".kernel"):
+            bad = np.argwhere(ws[w] != gs[g])
+            assert bad.size == 0, f"{k}: {len(bad)} rows differ, first {tuple(bad[0])}: {ws[w][tuple(bad[0])]!r} -> {gs[g][tuple(bad[0])]!r}"
+        else:
+            bad = np.argwhere(w != g)
+            assert bad.size == 0, f"{k}: {len(bad)} values differ, first {tuple(bad[0])}: {w[tuple(bad[0])]!r} -> {g[tuple(bad[0])]!r}"
