@@ -135,6 +135,7 @@ struct TrainLayout {
     size_t xhh, rsh, yh;
     size_t dX, gA, gB, gC, cat, dU[4], tA, tB, wT, slabs, red;
     size_t h2w, h2max;                       // the step's weights as two-fp16-piece packs (W and W^T: Engine::t_h2_specs), and their maxima scratch
+    size_t wpad;                             // zero-padded [N][r32(K)] copies of the step's linears whose K (a context map's channel count) is no multiple of 32
     size_t slabs_elems = 0, red_elems = 0;   // capacities of the two scratch areas above (what the weight-gradient slicing may use)
     size_t red_cap = 0;                      // ... and one column reduction's partial sums of red_elems (the same arrangement: t_col_flush)
     size_t slab_cap = 0;                     // what ONE weight gradient's slabs may take of slabs_elems (the slab area holds several layers' slabs

@@ -78,6 +78,10 @@ void Engine::train_layout(int B, TrainLayout& L) const {
     L.red = take(0, L.red_elems);
     L.h2w = take(0, t_h2_elems);
     L.h2max = take(0, t_h2_max_elems);
+    size_t wpad = 0;                                           // feat_embed.l [C][K] and every context block's embed_proj.l [HD][K]
+    for (int l = 0; l < Lv; ++l)
+        if (feat_C[l] % 32) wpad += r64((size_t)C * r32(feat_C[l])) + (cfg.context_blocks ? Lv : 0) * r64((size_t)(C / NH) * r32(feat_C[l]));
+    L.wpad = take(0, wpad);
     L.total = cur;
 }
 
@@ -370,6 +374,19 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
     const float* m_joint = masks ? m_res + (size_t)2 * Lv * B * J : nullptr;
 
     if (int rc = t_h2_prepare(s, L, tw, B)) return rc;
+    // the GEMMs read W as [N][Kpad] with Kpad a multiple of 32; a linear over a context map with K % 32 != 0 (HRNet-48's 48 channels) gets this
+    // step's zero-padded copy of its parameter (the two-piece pack, where the table holds one, is padded by its own packer)
+    float* wpad = tw + L.wpad;
+    auto padded = [&](const float* W, int N, int K, const float** Wp, int* Kpad) -> int {
+        *Wp = W;
+        *Kpad = K;
+        if (K % 32 == 0) return CAPF_OK;
+        *Kpad = r32(K);
+        HIP_TRY(launch_pack_linear(W, wpad, N, K, *Kpad, s));
+        *Wp = wpad;
+        wpad += r64((size_t)N * *Kpad);
+        return CAPF_OK;
+    };
     HIP_TRY(launch_prep_embed(kcrop, k2d, P(*this, V + ".coord_embed.weight"), P(*this, V + ".coord_embed.bias"),
                               P(*this, V + ".Spatial_pos_embed"), X, B, J, L1, C, s));
     const float* pos = P(*this, V + ".Spatial_pos_embed");
@@ -377,9 +394,13 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
         const std::string fe = V + ".feat_embed." + std::to_string(l);
         float* S = tw + L.S[l];
         HIP_TRY(launch_sample_ref(bptr(feat_buf[l], B), kcrop, S, nullptr, B, J, feat_H[l], feat_W[l], feat_C[l], s, bf16() ? 1 : 0));
-        int rc = t_gemm(s, S, row_ld(feat_C[l]), B * J, C, feat_C[l], P(*this, fe + ".weight"), feat_C[l],
+        const float* Wfe = P(*this, fe + ".weight");
+        const float* Wp = nullptr;
+        int Kpad = 0;
+        if (int rc = padded(Wfe, C, feat_C[l], &Wp, &Kpad)) return rc;
+        int rc = t_gemm(s, S, row_ld(feat_C[l]), B * J, C, feat_C[l], Wp, Kpad,
                         P(*this, fe + ".bias"), X, row_ld(D, (long)(1 + l) * C), pos, RowMap{J, 0, C, (long)(1 + l) * J * C},
-                        ACT_NONE, nullptr, 1);
+                        ACT_NONE, nullptr, 1, t_h2_pack(Wfe, false));
         if (rc) return rc;
     }
     const RowMap tok{Lv, D, C, C}, tok0{Lv, D, 0, 0};
@@ -408,8 +429,12 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
         for (int l = 0; l < Lv; ++l) {
             const std::string ep = p + ".embed_proj." + std::to_string(l);
             const RowMap dst{NH, D, HD, (long)(1 + l) * C};
-            rc = t_gemm(s, tw + c.U[l], row_ld(feat_C[l]), B * J * NH, HD, feat_C[l], P(*this, ep + ".weight"), feat_C[l],
-                        P(*this, ep + ".bias"), X, dst, X, dst, ACT_NONE, m1, J * NH);
+            const float* Wep = P(*this, ep + ".weight");
+            const float* Wp = nullptr;
+            int Kpad = 0;
+            if ((rc = padded(Wep, HD, feat_C[l], &Wp, &Kpad))) return rc;
+            rc = t_gemm(s, tw + c.U[l], row_ld(feat_C[l]), B * J * NH, HD, feat_C[l], Wp, Kpad,
+                        P(*this, ep + ".bias"), X, dst, X, dst, ACT_NONE, m1, J * NH, t_h2_pack(Wep, false));
             if (rc) return rc;
         }
         HIP_TRY(launch_layernorm_train(X, tok, nullptr, row_ld(0), P(*this, p + ".norm2.weight"), P(*this, p + ".norm2.bias"),
@@ -593,7 +618,8 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
         rc = t_linear_bwd(s, L, tw, gA, row_ld(64), R, NA + NO, C, tw + c.y1, row_ld(C), pack_arena + pk.w_off, dq,
                           row_ld(C), false, gWcat, gbcat);
         if (rc) return rc;
-        if ((rc = t_slab_flush(s))) return rc;           // (the copies below read the temp: its slabs are summed now, with whatever else waits)
+        if ((rc = t_slab_flush(s))) return rc;           // (the copies below read the temp: its slabs are summed now, with whatever else waits,
+        if ((rc = t_col_flush(s))) return rc;            //  and so is a bias gradient still in partial sums -- t_linear_bwd's fallback defers gbcat)
         HIP_TRY(hipMemcpyAsync(G(p + ".attention_weights.weight"), gWcat, sizeof(float) * NA * C, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipMemcpyAsync(G(p + ".sampling_offsets.weight"), gWcat + (size_t)NA * C, sizeof(float) * NO * C, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipMemcpyAsync(G(p + ".attention_weights.bias"), gbcat, sizeof(float) * NA, hipMemcpyDeviceToDevice, s));

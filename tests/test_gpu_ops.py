@@ -1227,6 +1227,58 @@ def test_f32h2_dynamic_range_inside_a_block(kind, e):
           f" GEMM conv {c2:.1e} | {d2:.1e} [{f2:.1e}]; GEMM linear {c3:.1e} | {d3:.1e} [{f3:.1e}]; weight gradient {c4:.1e} | {d4:.1e} [{f4:.1e}]")
 
 
+WGRAD_M = [1, 17, 31, 33, 85, 221, 1037, 8500]
+# fp32 kernel (N, K multiples of 4): below one 64-wide tile, ragged tiles (48, 68, 96), several tiles, 1920 wide
+WGRAD_F32_NK = [(4, 4), (4, 1920), (48, 128), (128, 48), (68, 96), (96, 640), (640, 68), (1920, 128)]
+# two-piece kernel (N, K multiples of 128)
+WGRAD_H2_NK = [(128, 128), (128, 1920), (384, 640), (640, 384), (1920, 128), (640, 1920)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M", WGRAD_M)
+def test_wgrad_fuzz_against_fp64(M):
+    """capf_op_wgrad (the training step's weight gradient, csrc/train_kernels.hip wgrad_tn_kernel / wgrad_tn_h2_kernel) at M = 1 .. 8500
+    rows: fewer than one 32-row chunk, ragged last chunks, exact multiples; N and K below one 64-wide tile and not multiples of 64 on the
+    fp32 kernel.  Against float64 dY^T X per entry: |error| <= 2e-6 sum|terms| (the range test's weight-gradient base), plus on the
+    two-piece kernel the block-scale term include/capf.h promises (2^-38 of the products of the operand blocks' largest values -- it only
+    matters for an entry whose few terms are tiny next to their block's largest); bias column sums within 1e-5 of the column's mass.  The
+    output buffer is NaN-filled with NaN guard elements behind N K + N: every output is written, nothing behind it is."""
+    from ctypes import c_void_p
+    from capf.lib import load_library
+    lib = load_library()
+    g = torch.Generator().manual_seed(4000 + M)
+    GUARD = 256
+    report = []
+    for two_piece, shapes in ((0, WGRAD_F32_NK), (1, WGRAD_H2_NK)):
+        worst = 0.0
+        for N, K in shapes:
+            dy = torch.randn(M, N, generator=g) * torch.exp2(torch.randint(-3, 4, (1, N), generator=g).float())
+            x = torch.randn(M, K, generator=g)
+            dyc, xc = dy.cuda(), x.cuda()
+            out = torch.full((N * K + N + GUARD,), float("nan"), device="cuda")
+            rc = lib.capf_op_wgrad(c_void_p(torch.cuda.current_stream().cuda_stream), c_void_p(dyc.data_ptr()), c_void_p(xc.data_ptr()),
+                                   M, N, K, c_void_p(out.data_ptr()), two_piece)
+            assert rc == 0, (M, N, K, two_piece, rc)
+            torch.cuda.synchronize()
+            out = out.cpu()
+            assert out[N * K + N:].isnan().all(), f"M={M} N={N} K={K} two_piece={two_piece}: a guard element behind the output was written"
+            gw, gb = out[:N * K].view(N, K).double(), out[N * K:N * K + N].double()
+            assert torch.isfinite(gw).all() and torch.isfinite(gb).all(), (M, N, K, two_piece)
+            dd, xd = dy.double(), x.double()
+            want, mass = dd.t() @ xd, dd.abs().t() @ xd.abs()
+            bound = 2e-6 * mass
+            if two_piece:
+                bound = bound + 2.0 ** -38 * (dd.abs().max() * xd.abs().sum(dim=0)[None, :] + xd.abs().max() * dd.abs().sum(dim=0)[:, None])
+            err = (gw - want).abs()
+            assert (err <= bound).all(), (f"M={M} N={N} K={K} two_piece={two_piece}: {(err / bound).max().item():.2f} of the bound "
+                                          f"at {divmod(int((err / bound).argmax()), K)}")
+            col_mass = dd.abs().sum(dim=0)
+            assert ((gb - dd.sum(dim=0)).abs() <= 1e-5 * col_mass).all(), (M, N, K, two_piece)
+            worst = max(worst, (err / mass).max().item())
+        report.append(f"{'two-piece' if two_piece else 'fp32'} {worst:.1e}")
+    print(f"wgrad M={M}: worst error / sum|terms| -- " + ", ".join(report))
+
+
 @pytest.mark.gpu
 def test_f32h2_scales_do_not_chase_a_chunk_of_zeros_into_overflow():
     """an all-zero chunk (padding taps, dead ReLU channels, DropPath rows) used to pull the running scale to its ceiling; behind a
