@@ -9,7 +9,8 @@ LIB_PATH = os.environ.get("CAPF_LIB") or os.path.join(os.path.dirname(os.path.ab
 HRNET, CPN50 = 0, 1
 F32, BF16 = 0, 1
 PLAN_NO_FUSED_LIFTER, PLAN_NO_WINOGRAD, PLAN_NO_ROW_HALO, PLAN_WINOGRAD_F23_ONLY, PLAN_NO_PWCHAIN, PLAN_NO_WS, PLAN_LIFTER_FP32, PLAN_NO_F32X3, PLAN_F32X3_EXACT, PLAN_NO_F32H2_GEMM, PLAN_NO_UPADD, PLAN_H2_PLANES, PLAN_NO_BNECK, PLAN_NO_BATCHED_REDUCE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192     # capf_plan_flag
-ABI_VERSION = 6        # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
+PLAN_BF16_F32_STREAM = 32768     # (1 << 14 stays unassigned)
+ABI_VERSION = 7        # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
 
 EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.py)
     "capf_create", "capf_destroy", "capf_last_error", "capf_version", "capf_num_params", "capf_param_info",
@@ -359,8 +360,8 @@ class Engine:
         return d
 
     def op_tensor(self, index, slot, shape, dtype_code):
-        """View (no copy) of one operand of op `index` after a forward_prefix: slot 0..3 inputs, 4 residual, 5 output;
-        shape = full [B, ...] shape, dtype_code 0 fp32 / 2 bf16."""
+        """View (no copy) of one operand of op `index` after a forward_prefix: slot 0..3 inputs, 4 residual, 5 output, 6 the output's bf16
+        shadow (PLAN_BF16_F32_STREAM); shape = full [B, ...] shape, dtype_code 0 fp32 / 2 bf16."""
         import torch
         ptr = c_void_p()
         self._check(self.lib.capf_op_tensor(self.h, index, slot, byref(ptr)), f"op_tensor({index}, {slot})")

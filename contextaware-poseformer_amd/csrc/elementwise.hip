@@ -105,7 +105,8 @@ hipError_t launch_pack_linear_quad(const float* w, float* Wq, int N, int K, int 
 // ---- HRNet fuse: out = relu(sum_i nearest_up(in_i))  (pose_hrnet.py:294-301, nn.Upsample nearest) --
 // Input i has resolution (H >> shift_i, W >> shift_i); nearest upsampling by 2^s reads (h>>s, w>>s).
 // V channels per lane: 4 (fp32 16 B, bf16 8 B) or 8 (bf16, 16 B); pixel arithmetic in 32 bits (B * H * W < 2^31, launcher checks)
-template <bool BF, int V>
+// SH (fp32 sums only): also store the bf16 shadow of the result (a.out_sh, may be nullptr), CAPF_PLAN_BF16_F32_STREAM
+template <bool BF, int V, bool SH = false>
 __device__ __forceinline__ void fuse_sum_body(const FuseSumArgs& a, const long first, const long stride) {
     constexpr int Q = V / 4;                                  // 4-channel groups per lane
     const int CV = a.C / V, C4 = a.C >> 2;
@@ -151,6 +152,10 @@ __device__ __forceinline__ void fuse_sum_body(const FuseSumArgs& a, const long f
                                                        pack_bf16x2(acc[Q - 1][0], acc[Q - 1][1]), pack_bf16x2(acc[Q - 1][2], acc[Q - 1][3])};
         } else {
             store4<BF>(a.out, i, acc[0]);
+            if (SH && a.out_sh) {
+                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+                reinterpret_cast<u32x2*>(a.out_sh)[i] = u32x2{pack_bf16x2(acc[0][0], acc[0][1]), pack_bf16x2(acc[0][2], acc[0][3])};
+            }
         }
     }
 }
@@ -158,6 +163,10 @@ __device__ __forceinline__ void fuse_sum_body(const FuseSumArgs& a, const long f
 template <bool BF, int V>
 __global__ void fuse_sum_kernel(FuseSumArgs a) {
     fuse_sum_body<BF, V>(a, blockIdx.x * (long)blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+}
+
+__global__ void fuse_sum_shadow_kernel(FuseSumArgs a) {
+    fuse_sum_body<false, 4, true>(a, blockIdx.x * (long)blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
 }
 
 struct FuseGroupArgs {
@@ -175,14 +184,25 @@ __global__ void fuse_sum_group_kernel(FuseGroupArgs g) {
     fuse_sum_body<BF, V>(g.p[pi], (long)(blockIdx.x - g.bstart[pi]) * blockDim.x + threadIdx.x, (long)nb * blockDim.x);
 }
 
+__global__ void fuse_sum_group_shadow_kernel(FuseGroupArgs g) {
+    int pi = 0;
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (i < g.n && (int)blockIdx.x >= g.bstart[i]) pi = i;
+    const int nb = g.bstart[pi + 1] - g.bstart[pi];
+    fuse_sum_body<false, 4, true>(g.p[pi], (long)(blockIdx.x - g.bstart[pi]) * blockDim.x + threadIdx.x, (long)nb * blockDim.x);
+}
+
 hipError_t launch_fuse_sum(const FuseSumArgs& a, hipStream_t s) {
     if ((long)a.B * a.H * a.W >= (1L << 31)) return hipErrorInvalidValue;
     const int V = (a.bf16 && a.C % 8 == 0) ? 8 : 4;
     const long total = (long)a.B * a.H * a.W * (a.C / V);
     const long want = (total + 255) / 256;
     const int blocks = (int)(want < 16384 ? want : 16384);
+    if (a.out_sh && a.bf16) return hipErrorInvalidValue;
     if (V == 8) hipLaunchKernelGGL((fuse_sum_kernel<true, 8>), dim3(blocks), dim3(256), 0, s, a);
     else if (a.bf16) hipLaunchKernelGGL((fuse_sum_kernel<true, 4>), dim3(blocks), dim3(256), 0, s, a);
+    else if (a.out_sh) hipLaunchKernelGGL(fuse_sum_shadow_kernel, dim3(blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((fuse_sum_kernel<false, 4>), dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }
@@ -194,8 +214,10 @@ hipError_t launch_fuse_sum_group(const FuseSumArgs* a, int n, hipStream_t s) {
     g.n = n;
     const int V = (a[0].bf16 && a[0].C % 8 == 0) ? 8 : 4;
     int blocks = 0;
+    bool shadow = false;
     for (int i = 0; i < n; ++i) {
-        if ((long)a[i].B * a[i].H * a[i].W >= (1L << 31) || a[i].bf16 != a[0].bf16) return hipErrorInvalidValue;
+        if ((long)a[i].B * a[i].H * a[i].W >= (1L << 31) || a[i].bf16 != a[0].bf16 || (a[i].out_sh && a[i].bf16)) return hipErrorInvalidValue;
+        shadow |= a[i].out_sh != nullptr;
         if (((a[i].bf16 && a[i].C % 8 == 0) ? 8 : 4) != V) return hipErrorInvalidValue;
         const long total = (long)a[i].B * a[i].H * a[i].W * (a[i].C / V);
         const long want = (total + 255) / 256;
@@ -207,6 +229,7 @@ hipError_t launch_fuse_sum_group(const FuseSumArgs* a, int n, hipStream_t s) {
     for (int i = n + 1; i < 5; ++i) g.bstart[i] = blocks;
     if (V == 8) hipLaunchKernelGGL((fuse_sum_group_kernel<true, 8>), dim3(blocks), dim3(256), 0, s, g);
     else if (a[0].bf16) hipLaunchKernelGGL((fuse_sum_group_kernel<true, 4>), dim3(blocks), dim3(256), 0, s, g);
+    else if (shadow) hipLaunchKernelGGL(fuse_sum_group_shadow_kernel, dim3(blocks), dim3(256), 0, s, g);
     else hipLaunchKernelGGL((fuse_sum_group_kernel<false, 4>), dim3(blocks), dim3(256), 0, s, g);
     return hipGetLastError();
 }

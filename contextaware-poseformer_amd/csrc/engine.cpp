@@ -164,6 +164,9 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes) const {
     a.amap = op.amap; a.omap = op.omap; a.rmap = op.rmap;
     a.act = op.act;
     a.out_bf16 = op.out_bf16;
+    a.f32s = op.f32s;                                  // (CAPF_PLAN_BF16_F32_STREAM: fp32 residual; fp32 result + bf16 shadow, or bf16 result)
+    a.out_f32 = op.st_f32;
+    a.out_sh = op.sh >= 0 ? ptr(op.sh) : nullptr;
     if (planes && op.h2_role && a.x3_h2 && a.Wp3 && wino_now(op, batch)) {
         // planes between a BasicBlock's two convs: only where BOTH launches go to the two-fp16-piece tile at this batch
         const GemmArgs peer = gemm_args(ops[op.h2_peer], batch, false);
@@ -283,6 +286,7 @@ FuseSumArgs Engine::fuse_args(const Op& op, int batch) const {
     a.out = op.out >= 0 ? bptr(op.out, batch) : nullptr;
     a.B = batch; a.H = op.H; a.W = op.W; a.C = op.C; a.relu = op.relu;
     a.bf16 = op.bf16;
+    a.out_sh = op.sh >= 0 ? bptr(op.sh, batch) : nullptr;
     return a;
 }
 
@@ -322,7 +326,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
             break;
         case OP_SAMPLE_REF:
             HIP_TRY(launch_sample_ref(ptr(op.in[0]), kcrop, ptr(op.out), reinterpret_cast<int*>(ptr(op.aux2)),
-                                      batch, op.i0, op.H, op.W, op.C, s, op.bf16));
+                                      batch, op.i0, op.H, op.W, op.C, s, op.feat_bf16));
             break;
         case OP_LAYERNORM:
             HIP_TRY(launch_layernorm(ptr(op.in[0]), op.amap, ptr(op.aux), op.rmap, params[op.p0].ptr,
@@ -339,7 +343,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
             a.AO = ptr(op.aux);
             a.ref = kcrop;
             a.B = batch; a.J = op.i0; a.L = op.i1; a.NH = op.i2; a.NS = op.i3;
-            a.feat_bf16 = op.bf16;
+            a.feat_bf16 = op.feat_bf16;
             if (debug && op.idxs[0] >= 0) { a.cpos = ptr(op.idxs[0]); a.cidx = reinterpret_cast<int*>(ptr(op.idxs[1])); }
             HIP_TRY(launch_deform_sample(a, s));
             break;
@@ -357,7 +361,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
             }
             a.X = ptr(op.out);
             a.BJ = batch * op.i0; a.J = op.i0; a.L = op.i1; a.L1 = op.i2; a.C = op.C;
-            a.feat_bf16 = op.bf16;
+            a.feat_bf16 = op.feat_bf16;
             HIP_TRY(launch_embed(a, s));
             break;
         }
@@ -375,7 +379,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
             a.ref = kcrop;
             a.X = ptr(op.out);
             a.BJ = batch * op.i0; a.J = op.i0; a.L = op.i1; a.L1 = op.i1 + 1; a.C = op.C; a.NH = op.i2; a.NS = op.i3;
-            a.feat_bf16 = op.bf16;
+            a.feat_bf16 = op.feat_bf16;
             if (debug && op.idxs[0] >= 0) { a.cpos = ptr(op.idxs[0]); a.cidx = reinterpret_cast<int*>(ptr(op.idxs[1])); }
             HIP_TRY(launch_ctx_attn(a, s));
             break;
@@ -607,7 +611,7 @@ int capf_create(const capf_config* cfg, int device, capf_handle** out) {
         delete h;
         return CAPF_ERR_UNSUPPORTED;
     }
-    if (cfg->plan_flags & ~16383) {
+    if (cfg->plan_flags & ~(16383 | CAPF_PLAN_BF16_F32_STREAM)) {
         g_create_error = "unknown capf_plan_flag bits";
         delete h;
         return CAPF_ERR_INVALID;
@@ -1317,6 +1321,7 @@ int capf_op_bytes(const capf_handle* h, int index, int batch, double* bytes) {
     const capf::Engine& e = h->e;
     const capf::Op& op = e.ops[index];
     const double B = batch, act = op.bf16 ? 2.0 : 4.0;
+    const double fact = op.feat_bf16 ? 2.0 : 4.0;                             // the lifter samplers: bytes per context-map element
     double b = 0.0;
     switch (op.kind) {
         case capf::OP_GEMM: {
@@ -1330,14 +1335,14 @@ int capf_op_bytes(const capf_handle* h, int index, int batch, double* bytes) {
             }
             b = in_elems * (op.conv && !op.bf16 ? 4.0 : act)                    // fp32 stem reads the fp32 image
                 + (double)pk.N * pk.K * (pk.bf16 ? 2.0 : 4.0) + (double)pk.N * 4.0
-                + M * op.N * (op.out_bf16 ? 2.0 : act)
-                + ((op.aux >= 0 || op.res_param >= 0) ? M * op.N * act : 0.0)
+                + M * op.N * (op.st_f32 ? 4.0 + (op.sh >= 0 ? 2.0 : 0.0) : op.out_bf16 ? 2.0 : act)   // (fp32 stream: fp32 result + bf16 shadow)
+                + ((op.aux >= 0 || op.res_param >= 0) ? M * op.N * (op.f32s ? 4.0 : act) : 0.0)
                 + ((op.conv && op.in[1] >= 0) ? B * op.i0 * op.i1 * op.N * act : 0.0);      // (the low-resolution map added behind the activation)
             break;
         }
         case capf::OP_FUSE: {
             const double out = B * op.H * op.W * op.C;
-            b = out * act;
+            b = out * act + (op.sh >= 0 ? out * 2.0 : 0.0);
             for (int i = 0; i < op.n_in; ++i) b += out * act / (double)(1 << (2 * op.shift[i]));
             break;
         }
@@ -1352,10 +1357,10 @@ int capf_op_bytes(const capf_handle* h, int index, int batch, double* bytes) {
             b = (double)op.i0 * B * op.i1 * op.i2 * op.i3 * 4.0 * 4.0;          // q, k, v in; o out
             break;
         case capf::OP_SAMPLE_REF:
-            b = B * op.i0 * op.C * (4.0 * act + 4.0);                           // 4 corners per joint + the sampled row
+            b = B * op.i0 * op.C * (4.0 * fact + 4.0);                          // 4 corners per joint + the sampled row
             break;
         case capf::OP_DEFORM:
-            for (int l = 0; l < op.i1; ++l) b += B * op.i0 * op.i2 * op.lvlC[l] * (4.0 * op.i3 * act + 4.0);
+            for (int l = 0; l < op.i1; ++l) b += B * op.i0 * op.i2 * op.lvlC[l] * (4.0 * op.i3 * fact + 4.0);
             b += B * op.i0 * op.i1 * 3.0 * op.i2 * op.i3 * 4.0;
             break;
         case capf::OP_HEAD:
@@ -1372,11 +1377,11 @@ int capf_op_bytes(const capf_handle* h, int index, int batch, double* bytes) {
             break;
         case capf::OP_EMBED:
             b = B * op.i0 * (op.i2 * op.C + 4.0) * 4.0;                          // tokens written
-            for (int l = 0; l < op.i1; ++l) b += B * op.i0 * op.lvlC[l] * 4.0 * act + (double)op.C * op.lvlC[l] * 4.0;
+            for (int l = 0; l < op.i1; ++l) b += B * op.i0 * op.lvlC[l] * 4.0 * fact + (double)op.C * op.lvlC[l] * 4.0;
             break;
         case capf::OP_CTX_ATTN:
             for (int l = 0; l < op.i1; ++l)
-                b += B * op.i0 * op.i2 * op.i3 * op.lvlC[l] * 4.0 * act + (double)(op.C / op.i2) * op.lvlC[l] * 4.0;
+                b += B * op.i0 * op.i2 * op.i3 * op.lvlC[l] * 4.0 * fact + (double)(op.C / op.i2) * op.lvlC[l] * 4.0;
             b += B * op.i0 * (op.i1 + 1 + op.i1) * op.C * 4.0;                    // tokens read, tokens 1..L written
             break;
         default: break;
@@ -1410,6 +1415,7 @@ int capf_op_schedule(const capf_handle* h, int index, int32_t* region, int32_t* 
         writes[0] = op.out;
         writes[1] = op.aux2;
         for (int i = 0; i < 4; ++i) writes[2 + i] = op.outs[i];
+        if (op.sh >= 0) writes[2] = op.sh;          // (a conv / fuse sum writes no outs[]: its bf16 shadow takes the first of those slots)
     }
     return CAPF_OK;
 }
@@ -1456,7 +1462,7 @@ int capf_op_describe(const capf_handle* h, int index, capf_op_desc* d) {
         d->mfma_bf16 = (op.bf16 || op.out_bf16) ? 1 : 0;
         if (op.conv) {
             d->in_dtype = op.in[0] == -2 ? 0 : (op.bf16 ? 2 : 0);
-            d->out_dtype = (op.bf16 || op.out_bf16) ? 2 : 0;
+            d->out_dtype = op.st_f32 ? 0 : (op.bf16 || op.out_bf16) ? 2 : 0;
             d->p_weight = pk.w[0]; d->p_bn_weight = pk.bn_g;
         } else {
             d->in_dtype = op.bf16 == 2 ? 2 : 0;
@@ -1483,6 +1489,7 @@ int capf_op_describe(const capf_handle* h, int index, capf_op_desc* d) {
         d->has_residual = op.kind == capf::OP_RESIZE && op.aux >= 0;      // out = resize(in) + aux
         for (int i = 0; i < 4; ++i) d->shift[i] = op.shift[i];
         if (op.kind == capf::OP_FUSE) { d->Ho = op.H; d->Wo = op.W; }
+        if (op.kind == capf::OP_FUSE && d->backbone) d->in_dtype = d->out_dtype = op.bf16 ? 2 : 0;
     }
     d->checkpoint = (op.bneck_c3 >= 0 ? op.bneck_c3 : op.region >= 0 ? e.regions[op.region].second : index) + 1;
     return CAPF_OK;
@@ -1499,10 +1506,10 @@ int capf_op_describe_sized(const capf_handle* h, int index, void* desc, size_t d
 }
 
 int capf_op_tensor(const capf_handle* h, int index, int slot, const void** dev_ptr) {
-    if (!h || !dev_ptr || index < 0 || index >= (int)h->e.ops.size() || slot < 0 || slot > 5) return CAPF_ERR_INVALID;
+    if (!h || !dev_ptr || index < 0 || index >= (int)h->e.ops.size() || slot < 0 || slot > 6) return CAPF_ERR_INVALID;
     const Engine& e = h->e;
     const capf::Op& op = e.ops[index];
-    const int buf = slot < 4 ? op.in[slot] : slot == 4 ? op.aux : op.out;
+    const int buf = slot < 4 ? op.in[slot] : slot == 4 ? op.aux : slot == 5 ? op.out : op.sh;
     if (buf == -2) { *dev_ptr = e.images; return CAPF_OK; }
     if (buf < 0 || !e.ws || e.last_batch <= 0) return CAPF_ERR_INVALID;
     *dev_ptr = e.bptr(buf, e.last_batch);

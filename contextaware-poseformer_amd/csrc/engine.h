@@ -113,6 +113,10 @@ struct Op {
     std::vector<int> chain;       // OP_RES_CHAIN: per block {pack qkv, proj, fc1, fc2, param norm1.weight, .bias, norm2.weight, .bias};
                                   // OP_MLP_CHAIN: {pack fc1, fc2, param norm2.weight, .bias}, rows through amap
     long h2_utab = -1;            // two-fp16-piece conv tile: word offset of this conv's map geometry in the engine's unit tables (-1: none)
+    // CAPF_PLAN_BF16_F32_STREAM (Engine::plan_f32_stream): f32s = a bf16 conv with the fp32-stream epilogue (its residual, if any, is fp32);
+    // st_f32 = the output is stored fp32 (conv or fuse sum); sh = buffer of its bf16 shadow, what the convs that read it take as operand (-1: none)
+    int f32s = 0, st_f32 = 0, sh = -1;
+    int feat_bf16 = 0;            // lifter samplers (embed, ctx_attn, sample_ref, deform_sample): the context maps are stored bf16
     int bneck_c3 = -1;            // conv1 / conv2 / downsample of a first bottleneck that may run as one kernel with its conv3 (that op's index; plan.cpp bneck0_mark)
     int lane = 0;                 // stream lane inside a fork/join region (0 = the caller's stream)
     int region = -1;              // index of the enclosing fork/join region, -1 outside
@@ -246,6 +250,9 @@ struct Engine {
     bool build();
     void assign_offsets();
     bool bf16() const { return cfg.compute_dtype == CAPF_BF16; }
+    bool f32_stream = false;       // plan_flags & CAPF_PLAN_BF16_F32_STREAM: bf16 only as conv operands, every other backbone tensor fp32
+    bool maps_bf16() const { return bf16() && !f32_stream; }   // the context maps feat0..3 are stored bf16
+    bool plan_f32_stream(const Tensor feats[4]);
     size_t act_elems(size_t n) const { return bf16() ? (n + 1) / 2 : n; }   // backbone activation size in float slots
     void use(int buf);   // mark buffer as read by the op being appended
     void push(Op op);    // append an op, tagging it with the current lane / region

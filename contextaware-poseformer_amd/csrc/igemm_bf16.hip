@@ -68,7 +68,9 @@ __device__ __forceinline__ long rowmap_b(const RowMap& r, int m) {
     return (long)q * r.S1 + (long)(m - q * r.G) * r.S2 + r.off;
 }
 
-template <int BM, int BN, int WM, int WN, int S, bool OUTF32 = false, bool GELU = false, bool UPADD = false>
+// F32S: the epilogue of a CAPF_PLAN_BF16_F32_STREAM conv (GemmArgs::f32s): fp32 residual, fp32 result + its bf16 shadow (out_f32) or a bf16
+// result -- same accumulators, same arithmetic; the main loop is the default one
+template <int BM, int BN, int WM, int WN, int S, bool OUTF32 = false, bool GELU = false, bool UPADD = false, bool F32S = false>
 __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid, unsigned short* __restrict__ lds) {
     constexpr int WAVES_N = BN / WN;
     constexpr int TM = WM / 32, TN = WN / 32;
@@ -222,6 +224,7 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
     const int er = lane >> 2, ec = (lane & 3) * 8;
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     u32x4 rr[TM][TN][2];
+    [[maybe_unused]] u32x4 rr2[TM][TN][2];               // F32S: channels 4..7 of an fp32 residual piece
     f32x4 bb[TN][2];
     // Every access of the vector epilogue is a raw buffer load / store on a block-local descriptor; a piece outside a ragged
     // M / N edge gets an out-of-range offset (reads zeros, store dropped) instead of a branch.  With divergent branches around
@@ -229,16 +232,23 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
     // to complete -- the 2 TM TN stores of a block were serialised round trips.  A null residual / bias is a descriptor of
     // zero records.
     constexpr unsigned OOB_E = 0x80000000u;
+    const long r_tile = (long)m0 * p.rmap.S1 + p.rmap.off + n0, o_tile = (long)m0 * p.omap.S1 + p.omap.off + n0;
     const rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(
-        (Rs && vec_ok) ? (void*)(Rs + (long)m0 * p.rmap.S1 + p.rmap.off + n0) : (void*)Out, 0, (Rs && vec_ok) ? 0x7FFFFF00u : 0u,
+        (Rs && vec_ok) ? (F32S ? (void*)(p.res + r_tile) : (void*)(Rs + r_tile)) : (void*)Out, 0, (Rs && vec_ok) ? 0x7FFFFF00u : 0u,
         0x00020000);
-    const rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc((void*)(Out + (long)m0 * p.omap.S1 + p.omap.off + n0), 0,
-                                                            vec_ok ? 0x7FFFFF00u : 0u, 0x00020000);
+    // F32S: the bf16 stores go to the shadow (fp32 result) or to out (bf16 result), the fp32 stores to out or nowhere (zero records)
+    unsigned short* const Y16 = F32S && p.out_f32 ? reinterpret_cast<unsigned short*>(p.out_sh) : Out;
+    const rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(Y16 ? (void*)(Y16 + o_tile) : (void*)Out, 0,
+                                                            (vec_ok && (!F32S || Y16)) ? 0x7FFFFF00u : 0u, 0x00020000);
+    [[maybe_unused]] rsrc_t rs_out32;
+    if constexpr (F32S)
+        rs_out32 = __builtin_amdgcn_make_buffer_rsrc(p.out_f32 ? (void*)(p.out + o_tile) : (void*)Out, 0,
+                                                     (vec_ok && p.out_f32) ? 0x7FFFFF00u : 0u, 0x00020000);
     const rsrc_t rs_bias = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)(p.bias + n0) : (void*)Out, 0,
                                                              p.bias ? (unsigned)(p.N - n0) * 4u : 0u, 0x00020000);
-    auto piece_off = [&](int i, int j, int h, int S1) -> unsigned {   // byte offset of this lane's 8 channels inside the block's tile
+    auto piece_off = [&](int i, int j, int h, int S1, unsigned es = 2u) -> unsigned {   // byte offset of this lane's 8 channels inside the block's tile
         const int ml = wm0 + i * 32 + h * 16 + er, nl = wn0 + j * 32 + ec;
-        return (m0 + ml < p.M && n0 + nl < p.N) ? (unsigned)(ml * S1 + nl) * 2u : OOB_E;
+        return (m0 + ml < p.M && n0 + nl < p.N) ? (unsigned)(ml * S1 + nl) * es : OOB_E;
     };
     auto prefetch_epilogue = [&]() {
         if (!vec_ok) return;
@@ -250,8 +260,15 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int h = 0; h < 2; ++h)
-                    rr[i][j][h] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, piece_off(i, j, h, (int)p.rmap.S1), 0, 0);
+                for (int h = 0; h < 2; ++h) {
+                    if constexpr (F32S) {
+                        const unsigned o = piece_off(i, j, h, (int)p.rmap.S1, 4u);
+                        rr[i][j][h] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, o, 0, 0);
+                        rr2[i][j][h] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, o + 16u, 0, 0);
+                    } else {
+                        rr[i][j][h] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, piece_off(i, j, h, (int)p.rmap.S1), 0, 0);
+                    }
+                }
         }
     };
 
@@ -479,13 +496,19 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
                         const f32x4 x0 = *reinterpret_cast<const f32x4*>(&ep[row * EPS + ec]);
                         const f32x4 x1 = *reinterpret_cast<const f32x4*>(&ep[row * EPS + ec + 4]);
                         u32x4 o;
+                        [[maybe_unused]] f32x4 y32[2];
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const unsigned rw = rr[i][j][h][q];
                             const float xa = q < 2 ? x0[2 * q] : x1[2 * q - 4], xb = q < 2 ? x0[2 * q + 1] : x1[2 * q - 3];
                             const float ba = q < 2 ? bb[j][0][2 * q] : bb[j][1][2 * q - 4];
                             const float bc = q < 2 ? bb[j][0][2 * q + 1] : bb[j][1][2 * q - 3];
-                            float va = finish(xa + ba + __uint_as_float(rw << 16)), vb = finish(xb + bc + __uint_as_float(rw & 0xFFFF0000u));
+                            float ra = __uint_as_float(rw << 16), rb = __uint_as_float(rw & 0xFFFF0000u);
+                            if constexpr (F32S) {
+                                ra = __uint_as_float(q < 2 ? rr[i][j][h][2 * q] : rr2[i][j][h][2 * q - 4]);
+                                rb = __uint_as_float(q < 2 ? rr[i][j][h][2 * q + 1] : rr2[i][j][h][2 * q - 3]);
+                            }
+                            float va = finish(xa + ba + ra), vb = finish(xb + bc + rb);
                             if constexpr (UPADD) {
                                 const float lh1 = ulh[h], lw1 = ulw[h], lh0 = 1.f - lh1, lw0 = 1.f - lw1;
                                 const unsigned q00 = uq[h][j][0][q], q01 = uq[h][j][1][q], q10 = uq[h][j][2][q], q11 = uq[h][j][3][q];
@@ -495,8 +518,14 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
                                       lh1 * (lw0 * __uint_as_float(q10 & 0xFFFF0000u) + lw1 * __uint_as_float(q11 & 0xFFFF0000u));
                             }
                             o[q] = pack_bf16x2(va, vb);
+                            if constexpr (F32S) { y32[q >> 1][(2 * q) & 3] = va; y32[q >> 1][(2 * q + 1) & 3] = vb; }
                         }
                         __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, piece_off(i, j, h, (int)p.omap.S1), 0, 0);
+                        if constexpr (F32S) {
+                            const unsigned o4 = piece_off(i, j, h, (int)p.omap.S1, 4u);
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y32[0]), rs_out32, o4, 0, 0);
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y32[1]), rs_out32, o4 + 16u, 0, 0);
+                        }
                     }
                 }
             }
@@ -516,8 +545,15 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
                         for (int e = 0; e < 8 && n + e < p.N; ++e) {
                             const float x = e < 4 ? x0[e & 3] : x1[e & 3];
                             const float bsv = p.bias ? p.bias[n + e] : 0.f;
-                            const float rsv = Rs ? bf2f(Rs[(long)m * p.rmap.S1 + p.rmap.off + n + e]) : 0.f;
-                            Out[(long)m * p.omap.S1 + p.omap.off + n + e] = f2bf(finish(x + bsv + rsv));
+                            const long ri = (long)m * p.rmap.S1 + p.rmap.off + n + e, oi = (long)m * p.omap.S1 + p.omap.off + n + e;
+                            const float rsv = Rs ? (F32S ? p.res[ri] : bf2f(Rs[ri])) : 0.f;
+                            const float v = finish(x + bsv + rsv);
+                            if (F32S && p.out_f32) {
+                                p.out[oi] = v;
+                                if (Y16) Y16[oi] = f2bf(v);
+                            } else {
+                                Out[oi] = f2bf(v);
+                            }
                         }
                     }
                 }
@@ -803,6 +839,16 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(GemmArgs p) {
     constexpr int HALVES = S * (BM + BN) * BKH < 4 * 32 * 36 * 2 ? 4 * 32 * 36 * 2 : S * (BM + BN) * BKH;   // >= the epilogue's 18 KiB
     __shared__ __attribute__((aligned(16))) unsigned short lds[HALVES];
     igemm_bf16_tile<BM, BN, WM, WN, S, OUTF32, GELU, UPADD>(p, xcd_remap_b(blockIdx.x, gridDim.x), lds);
+#endif
+}
+
+// the same conv with the fp32-stream epilogue (GemmArgs::f32s, CAPF_PLAN_BF16_F32_STREAM)
+template <int BM, int BN, int WM, int WN, int S>
+__global__ __launch_bounds__(256) void igemm_bf16_stream_kernel(GemmArgs p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int HALVES = S * (BM + BN) * BKH < 4 * 32 * 36 * 2 ? 4 * 32 * 36 * 2 : S * (BM + BN) * BKH;
+    __shared__ __attribute__((aligned(16))) unsigned short lds[HALVES];
+    igemm_bf16_tile<BM, BN, WM, WN, S, false, false, false, true>(p, xcd_remap_b(blockIdx.x, gridDim.x), lds);
 #endif
 }
 
@@ -1420,6 +1466,26 @@ __global__ __launch_bounds__(256) void igemm_bf16_group_kernel(GroupArgsB ga) {
 #endif
 }
 
+// ... with the fp32-stream epilogue (every problem of the launch has GemmArgs::f32s)
+__global__ __launch_bounds__(256) void igemm_bf16_group_stream_kernel(GroupArgsB ga) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ __attribute__((aligned(16))) unsigned short lds[GROUP_LDS_HALVES];
+    const int b = blockIdx.x;
+    int pi = 0;
+    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
+    const int l = b - ga.start[pi];
+    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
+    const int bid = (l & 7) * per_xcd + (l >> 3);
+    if (bid >= ga.tiles[pi]) return;
+    const GemmArgs& p = ga.g[pi];
+    switch (ga.cfg[pi]) {
+        case 0: igemm_bf16_tile<128, 64, 64, 32, CAPF_BF16_GROUP_STAGES, false, false, false, true>(p, bid, lds); break;
+        case 1: igemm_bf16_tile<64, 64, 32, 32, CAPF_BF16_GROUP_STAGES + 1, false, false, false, true>(p, bid, lds); break;
+        default: igemm_bf16_tile<128, 32, 32, 32, CAPF_BF16_GROUP_STAGES, false, false, false, true>(p, bid, lds); break;
+    }
+#endif
+}
+
 // ping-pong variant of the grouped kernel: one stage per block, 24 KiB, up to 5 blocks per CU (register cap 102)
 __global__ __launch_bounds__(256, 5) void igemm_bf16_group_pp_kernel(GroupArgsB ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1436,6 +1502,26 @@ __global__ __launch_bounds__(256, 5) void igemm_bf16_group_pp_kernel(GroupArgsB 
         case 0: igemm_bf16_tile<128, 64, 64, 32, 1>(p, bid, lds); break;
         case 1: igemm_bf16_tile<64, 64, 32, 32, 1>(p, bid, lds); break;
         default: igemm_bf16_tile<128, 32, 32, 32, 1>(p, bid, lds); break;
+    }
+#endif
+}
+
+// (4 blocks per CU, not 5: the fp32 residual and result pieces do not fit the 5-block register cap of 102 without spilling)
+__global__ __launch_bounds__(256, 4) void igemm_bf16_group_pp_stream_kernel(GroupArgsB ga) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ __attribute__((aligned(16))) unsigned short lds[(128 + 64) * BKH];
+    const int b = blockIdx.x;
+    int pi = 0;
+    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
+    const int l = b - ga.start[pi];
+    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
+    const int bid = (l & 7) * per_xcd + (l >> 3);
+    if (bid >= ga.tiles[pi]) return;
+    const GemmArgs& p = ga.g[pi];
+    switch (ga.cfg[pi]) {
+        case 0: igemm_bf16_tile<128, 64, 64, 32, 1, false, false, false, true>(p, bid, lds); break;
+        case 1: igemm_bf16_tile<64, 64, 32, 32, 1, false, false, false, true>(p, bid, lds); break;
+        default: igemm_bf16_tile<128, 32, 32, 32, 1, false, false, false, true>(p, bid, lds); break;
     }
 #endif
 }
@@ -1488,7 +1574,8 @@ static hipError_t launch_cfg_b(const GemmArgs& a, hipStream_t s) {
             return hipErrorInvalidValue;
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, WM, WN, S>), dim3(nbm * nbn), dim3(256), 0, s, a);
+    if (a.f32s) hipLaunchKernelGGL((igemm_bf16_stream_kernel<BM, BN, WM, WN, S>), dim3(nbm * nbn), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, WM, WN, S>), dim3(nbm * nbn), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -1502,7 +1589,7 @@ bool gemm_bf16_upadd_ok(const GemmArgs& a) {
 Bf16Route gemm_bf16_route(const GemmArgs& a) {
     if (gemm_bf16_ws_wanted(a)) return {Bf16Path::WS, false};
     const bool pp = (long)((a.M + 127) / 128) * ((a.N + 63) / 64) >= pp_min_tiles();
-    if (pp && a.Wp2 && gemm_bf16_rh_cw(a)) return {Bf16Path::RH, true};
+    if (pp && a.Wp2 && gemm_bf16_rh_cw(a) && !a.f32s) return {Bf16Path::RH, true};     // (the row-halo tile has no fp32-stream epilogue)
     if (a.N <= 32) return {Bf16Path::T128x32, pp};
     if (a.N <= 64) return {(long)a.M >= 128L * 512 ? Bf16Path::T128x64 : Bf16Path::T64x64, pp};
     return {(long)((a.M + 127) / 128) * ((a.N + 127) / 128) >= 512 ? Bf16Path::T128x128 : Bf16Path::T64x64, pp};
@@ -1557,6 +1644,9 @@ hipError_t launch_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t s, in
         }
     }
     if (n == 1) return launch_gemm_bf16(list[0], s);
+    const bool stream = list[0].f32s != 0;                       // (fp32-stream epilogue: every problem of the launch or none)
+    for (int i = 1; i < n; ++i)
+        if ((list[i].f32s != 0) != stream) return hipErrorInvalidValue;
     static const int BMs[3] = {128, 64, 128}, BNs[3] = {64, 64, 32};
     double total = 0.0;
     for (int i = 0; i < n; ++i) {
@@ -1582,7 +1672,7 @@ hipError_t launch_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t s, in
     if (tiles_small >= pp_min_tiles())
         for (int i = 0; i < n; ++i) {
             const GemmArgs& a = list[it[i].idx];
-            const int cw = a.Wp2 ? gemm_bf16_rh_cw(a) : 0;
+            const int cw = a.Wp2 && !stream ? gemm_bf16_rh_cw(a) : 0;
             if (!cw) continue;
             const int tn = rh_tn(a.N, cw);
             it[i].cfg = cw == 64 ? (tn == 2 ? 3 : 4) : (cw == 48 ? (tn == 2 ? 5 : (tn == 3 ? 6 : 7)) : (tn == 2 ? 8 : 9));
@@ -1610,8 +1700,8 @@ hipError_t launch_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t s, in
     for (int i = n; i < MAXG; ++i) { ga.start[i + 1] = start; ga.tiles[i] = 0; ga.cfg[i] = 0; }
     if (variant) *variant = nrh ? 2 : (start >= pp_min_tiles() ? 1 : 0);
     if (nrh) hipLaunchKernelGGL(igemm_bf16_group_rh_kernel, dim3(start), dim3(256), (size_t)lds_halves * 2, s, ga);
-    else if (start >= pp_min_tiles()) hipLaunchKernelGGL(igemm_bf16_group_pp_kernel, dim3(start), dim3(256), 0, s, ga);
-    else hipLaunchKernelGGL(igemm_bf16_group_kernel, dim3(start), dim3(256), 0, s, ga);
+    else if (start >= pp_min_tiles()) hipLaunchKernelGGL(stream ? igemm_bf16_group_pp_stream_kernel : igemm_bf16_group_pp_kernel, dim3(start), dim3(256), 0, s, ga);
+    else hipLaunchKernelGGL(stream ? igemm_bf16_group_stream_kernel : igemm_bf16_group_kernel, dim3(start), dim3(256), 0, s, ga);
     return hipGetLastError();
 }
 
@@ -1622,7 +1712,7 @@ hipError_t launch_gemm_bf16(const GemmArgs& a_in, hipStream_t s) {
         return hipErrorInvalidValue;
     GemmArgs a = a_in;
     prep_conv_b(a);
-    if (a.up && !gemm_bf16_upadd_ok(a)) return hipErrorInvalidValue;
+    if (a.up && (a.f32s || !gemm_bf16_upadd_ok(a))) return hipErrorInvalidValue;
     const Bf16Route r = gemm_bf16_route(a);
     switch (r.path) {
         case Bf16Path::WS: return launch_gemm_bf16_ws(a, s);

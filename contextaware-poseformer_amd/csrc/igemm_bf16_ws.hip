@@ -21,13 +21,24 @@ static bool ws_from_args(const GemmArgs& a, WsProblem* p) {
         a.omap.G != 1 || (a.res && a.rmap.G != 1) || a.M <= 0 || a.H <= 0 || a.W <= 0 || a.M % (a.H * a.W) != 0)
         return false;
     if ((a.omap.S1 & 7) || (a.omap.off & 7) || (a.res && ((a.rmap.S1 & 7) || (a.rmap.off & 7)))) return false;     // 16-byte pieces
-    if ((double)a.M * (double)a.omap.S1 * 2.0 >= 2.0e9 || (a.res && (double)a.M * (double)a.rmap.S1 * 2.0 >= 2.0e9)) return false;
+    const double es = a.f32s ? 4.0 : 2.0;                                                                  // (fp32 stream: fp32 residual / result)
+    if ((double)a.M * (double)a.omap.S1 * es >= 2.0e9 || (a.res && (double)a.M * (double)a.rmap.S1 * es >= 2.0e9)) return false;
     if (!ws_plan(a.M / (a.H * a.W), a.H, a.W, a.Cin, a.N, p)) return false;
     p->x = reinterpret_cast<const unsigned short*>(a.A);
     p->wp = reinterpret_cast<const unsigned short*>(a.Wp3);
     p->bias = a.bias;
     p->res = a.res ? reinterpret_cast<const unsigned short*>(a.res) + a.rmap.off : nullptr;
     p->y = reinterpret_cast<unsigned short*>(a.out) + a.omap.off;
+    p->res32 = nullptr;
+    p->y32 = nullptr;
+    if (a.f32s) {
+        p->res = nullptr;
+        p->res32 = a.res ? a.res + a.rmap.off : nullptr;
+        if (a.out_f32) {
+            p->y32 = a.out + a.omap.off;
+            p->y = a.out_sh ? static_cast<unsigned short*>(a.out_sh) + a.omap.off : nullptr;
+        }
+    }
     p->ldy = (int)a.omap.S1;
     p->ldr = a.res ? (int)a.rmap.S1 : (int)a.omap.S1;
     p->relu = a.act == ACT_RELU;
@@ -93,14 +104,35 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_group_ws_kernel(WsGroupArgs
 #endif
 }
 
+// ... with the fp32-stream epilogue (every problem of the launch has GemmArgs::f32s)
+__global__ __launch_bounds__(256, 2) void igemm_bf16_group_ws_stream_kernel(WsGroupArgs ga) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    extern __shared__ __attribute__((aligned(16))) unsigned char ws_lds[];
+    const int b = blockIdx.x;
+    int pi = 0;
+    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
+    const int l = b - ga.start[pi];
+    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
+    const int bid = (l & 7) * per_xcd + (l >> 3);
+    if (bid >= ga.tiles[pi]) return;
+    const WsProblem& p = ga.g[pi];
+    switch (p.NS) {
+        case 96: igemm_bf16_ws_tile<3, true>(p, bid, ws_lds); break;
+        case 64: igemm_bf16_ws_tile<2, true>(p, bid, ws_lds); break;
+        default: igemm_bf16_ws_tile<1, true>(p, bid, ws_lds); break;
+    }
+#endif
+}
+
 hipError_t launch_gemm_bf16_ws_group(const GemmArgs* list, int n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n > MAXG) return hipErrorInvalidValue;
     struct Item { WsProblem p; double cost; };
     Item it[MAXG];
     int max_ns = 32;
+    const bool stream = list[0].f32s != 0;
     for (int i = 0; i < n; ++i) {
-        if (!list[i].Wp3 || !ws_from_args(list[i], &it[i].p)) return hipErrorInvalidValue;
+        if (!list[i].Wp3 || !ws_from_args(list[i], &it[i].p) || (list[i].f32s != 0) != stream) return hipErrorInvalidValue;
         it[i].cost = (double)(it[i].p.C / 16) * it[i].p.NS;      // a tile's K loop: longest first, so that the launch does not end on them
         if (it[i].p.NS > max_ns) max_ns = it[i].p.NS;
     }
@@ -118,7 +150,13 @@ hipError_t launch_gemm_bf16_ws_group(const GemmArgs* list, int n, hipStream_t s)
     ga.start[n] = start;
     for (int i = n; i < MAXG; ++i) { ga.start[i + 1] = start; ga.tiles[i] = 0; ga.g[i] = ga.g[0]; }
     const size_t lds_bytes = 2 * (size_t)ws_stage_bytes(max_ns);
-    static DynLdsAttr attr_once;
+    static DynLdsAttr attr_once, attr_stream;
+    if (stream) {
+        const hipError_t attr = attr_stream.ensure(reinterpret_cast<const void*>(&igemm_bf16_group_ws_stream_kernel), 2 * ws_stage_bytes(96));
+        if (attr != hipSuccess) return attr;
+        hipLaunchKernelGGL(igemm_bf16_group_ws_stream_kernel, dim3(start), dim3(256), lds_bytes, s, ga);
+        return hipGetLastError();
+    }
     const hipError_t attr = attr_once.ensure(reinterpret_cast<const void*>(&igemm_bf16_group_ws_kernel), 2 * ws_stage_bytes(96));
     if (attr != hipSuccess) return attr;
     hipLaunchKernelGGL(igemm_bf16_group_ws_kernel, dim3(start), dim3(256), lds_bytes, s, ga);

@@ -47,7 +47,9 @@ struct WsProblem {
     const unsigned short* wp;     // packed by ws_pack: [N slice][C / 16][tap][NS][2 swizzled halves][8] bf16
     const float* bias;            // [N] fp32 or nullptr
     const unsigned short* res;    // [M][ldr] bf16 or nullptr
-    unsigned short* y;            // [M][ldy] bf16
+    unsigned short* y;            // [M][ldy] bf16 (F32S: the bf16 shadow of y32, or nullptr)
+    const float* res32;           // F32S only: [M][ldr] fp32 residual or nullptr ...
+    float* y32;                   // ... and [M][ldy] fp32 result or nullptr (then y holds the result, bf16)
     int B, H, W, C, N;
     int ldy, ldr;                 // row pitch (elements) of y / res
     int relu;
@@ -119,8 +121,10 @@ __device__ __forceinline__ unsigned ws_pack2(float lo, float hi) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{lo, hi}, bf2));
 }
 
-// one tile (logical id `bid` = pixel tile * NSL + slice) with the calling 256-thread block; lds: 2 * ws_stage_bytes(32 TN) bytes
-template <int TN>
+// one tile (logical id `bid` = pixel tile * NSL + slice) with the calling 256-thread block; lds: 2 * ws_stage_bytes(32 TN) bytes.
+// F32S: the epilogue of a CAPF_PLAN_BF16_F32_STREAM conv -- fp32 residual (res32), fp32 result (y32) and / or bf16 (y); the K loop is the default
+// one, the residual is requested behind it (twice the registers of a bf16 one: before the last chunk it would spill)
+template <int TN, bool F32S = false>
 __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int bid, unsigned char* __restrict__ lds) {
     constexpr int NS = 32 * TN;
     constexpr int W_BYTES = 9 * NS * 32;
@@ -212,15 +216,19 @@ __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int
     auto piece_rc = [&](int& er_, int& ec_) { asm volatile("" : "+v"(elane)); er_ = elane >> 2; ec_ = (elane & 3) * 8; };
     const int gp0 = q0 * p.RHW;                            // first flat output pixel of the tile: tile pixel pl is flat pixel gp0 + pl
     const int Mi = (int)p.M;                               // (ws_plan: M * N * 2 < 2^31, so 32-bit offsets throughout)
-    const ws_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(p.res ? (void*)p.res : (void*)p.y, 0, p.res ? 0x7FFFFF00u : 0u, 0x00020000);
-    const ws_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, 0x7FFFFF00u, 0x00020000);
-    auto piece_off = [&](int i, int j, int h, int ld, int er, int ec) -> unsigned {
+    const void* res_ptr = F32S ? (const void*)p.res32 : (const void*)p.res;
+    const ws_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(res_ptr ? (void*)res_ptr : (F32S ? (void*)p.x : (void*)p.y), 0, res_ptr ? 0x7FFFFF00u : 0u, 0x00020000);
+    const ws_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(F32S && !p.y ? (void*)p.x : (void*)p.y, 0, F32S && !p.y ? 0u : 0x7FFFFF00u, 0x00020000);
+    [[maybe_unused]] ws_rsrc_t rs_out32;
+    if constexpr (F32S) rs_out32 = __builtin_amdgcn_make_buffer_rsrc(p.y32 ? (void*)p.y32 : (void*)p.x, 0, p.y32 ? 0x7FFFFF00u : 0u, 0x00020000);
+    auto piece_off = [&](int i, int j, int h, int ld, int er, int ec, unsigned es = 2u) -> unsigned {
         const int pl = (2 * wave + i) * 32 + h * 16 + er, n = slice * NS + j * 32 + ec;
         const int gp = gp0 + pl;
-        return (pl < p.P && gp < Mi && n < p.N) ? (unsigned)(gp * ld + n) * 2u : OOB;
+        return (pl < p.P && gp < Mi && n < p.N) ? (unsigned)(gp * ld + n) * es : OOB;
     };
     // (pixel block 0's rows before the last chunk, block 1's behind it: all twelve pieces that early do not fit in 256 registers)
     ws_u32x4 rr[2][TN][2];
+    [[maybe_unused]] ws_u32x4 rr2[2][TN][2];               // F32S: channels 4..7 of an fp32 piece
     auto prefetch_residual = [&](int i, int j0, int j1) {   // channel blocks j0 .. j1 - 1 of pixel block i
         int er, ec;
         piece_rc(er, ec);
@@ -228,7 +236,15 @@ __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int h = 0; h < 2; ++h)
-                if (j >= j0 && j < j1) rr[i][j][h] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, piece_off(i, j, h, p.ldr, er, ec), 0, 0);
+                if (j >= j0 && j < j1) {
+                    if constexpr (F32S) {
+                        const unsigned o = piece_off(i, j, h, p.ldr, er, ec, 4u);
+                        rr[i][j][h] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, o, 0, 0);
+                        rr2[i][j][h] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, o + 16u, 0, 0);
+                    } else {
+                        rr[i][j][h] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, piece_off(i, j, h, p.ldr, er, ec), 0, 0);
+                    }
+                }
     };
     // TN = 3 runs at the 256-register limit of two waves per SIMD: more than one channel block requested before the last chunk
     // and the compiler spills the loaded rows (load, wait, scratch store -- worse than no prefetch)
@@ -238,7 +254,7 @@ __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int
         constexpr int S = decltype(SC)::value;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the chunk has landed ...
         __builtin_amdgcn_s_barrier();                      // ... everybody's has, and everybody is done reading the other stage
-        if constexpr (decltype(LAST)::value) prefetch_residual(0, 0, EARLY);   // (behind the wait: its latency hides under this chunk's MFMAs)
+        if constexpr (decltype(LAST)::value && !F32S) prefetch_residual(0, 0, EARLY);   // (behind the wait: its latency hides under this chunk's MFMAs)
         const unsigned char* st = lds + S * ST;
         auto read_frags = [&](int t, int buf) {
 #pragma unroll
@@ -280,8 +296,8 @@ __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int
             chunk(S0{}, std::true_type{}, NCC);
         }
     }
-    prefetch_residual(0, EARLY, TN);
-    if constexpr (TN < 3) prefetch_residual(1, 0, TN);     // (TN = 3: behind pixel block 0's stores, when its 48 accumulators are free)
+    prefetch_residual(0, F32S ? 0 : EARLY, TN);
+    if constexpr (TN < 3 && !F32S) prefetch_residual(1, 0, TN);     // (TN = 3: behind pixel block 0's stores, when its 48 accumulators are free)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                          // every wave has read the last stage: the scratch below overlays it
 
@@ -293,7 +309,7 @@ __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int
     auto finish = [&](float t) { return p.relu ? fmaxf(t, 0.f) : t; };
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        if constexpr (TN == 3) { if (i == 1) prefetch_residual(1, 0, TN); }
+        if constexpr (TN == 3 || F32S) { if (i == 1) prefetch_residual(1, 0, TN); }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             __builtin_amdgcn_wave_barrier();
@@ -308,13 +324,27 @@ __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int
                 const ws_f32x4 x0 = *reinterpret_cast<const ws_f32x4*>(&ep[row * EPS + ec]);
                 const ws_f32x4 x1 = *reinterpret_cast<const ws_f32x4*>(&ep[row * EPS + ec + 4]);
                 ws_u32x4 o;
+                [[maybe_unused]] ws_f32x4 y32[2];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const unsigned rw = rr[i][j][h][q];
                     const float xa = q < 2 ? x0[2 * q] : x1[2 * q - 4], xb = q < 2 ? x0[2 * q + 1] : x1[2 * q - 3];
-                    o[q] = ws_pack2(finish(xa + __uint_as_float(rw << 16)), finish(xb + __uint_as_float(rw & 0xFFFF0000u)));
+                    if constexpr (F32S) {
+                        const float va = finish(xa + __uint_as_float(q < 2 ? rr[i][j][h][2 * q] : rr2[i][j][h][2 * q - 4]));
+                        const float vb = finish(xb + __uint_as_float(q < 2 ? rr[i][j][h][2 * q + 1] : rr2[i][j][h][2 * q - 3]));
+                        y32[q >> 1][(2 * q) & 3] = va;
+                        y32[q >> 1][(2 * q + 1) & 3] = vb;
+                        o[q] = ws_pack2(va, vb);
+                    } else {
+                        o[q] = ws_pack2(finish(xa + __uint_as_float(rw << 16)), finish(xb + __uint_as_float(rw & 0xFFFF0000u)));
+                    }
                 }
                 __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, piece_off(i, j, h, p.ldy, er, ec), 0, 0);
+                if constexpr (F32S) {
+                    const unsigned o4 = piece_off(i, j, h, p.ldy, er, ec, 4u);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ws_u32x4, y32[0]), rs_out32, o4, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ws_u32x4, y32[1]), rs_out32, o4 + 16u, 0, 0);
+                }
             }
         }
     }

@@ -145,6 +145,12 @@ struct GemmArgs {
     const int* h2_ein;
     int* h2_eout;
     const unsigned* h2_utab;     // ... and the map geometry's unit table (f32h2_unit_table; nullptr: the prologue computes its addresses)
+    // bf16 convs of a CAPF_PLAN_BF16_F32_STREAM plan (the *_stream kernels of igemm_bf16.hip / igemm_bf16_ws.hip; every problem of a launch or none):
+    // res, if any, is fp32; out_f32 = 1: out is fp32 and out_sh (may be nullptr) receives its bf16 rounding (RNE, the operand the next conv reads);
+    // out_f32 = 0: out is bf16 as usual.  A and the weights stay bf16: the main loops are the default ones, only the epilogue differs
+    int f32s;
+    int out_f32;
+    void* out_sh;
 };
 
 // all res blocks of the lifter as one launch (lifter_chain.hip): per block LayerNorm weights, the two-fp16-piece packs of the four projections
@@ -322,6 +328,7 @@ struct FuseSumArgs {
     int B, H, W, C;
     int relu;
     int bf16;      // tensors are bf16 (arithmetic stays fp32)
+    void* out_sh;  // fp32 sums only (bf16 = 0): bf16 shadow of out (RNE, [B,H,W,C]) written in the same pass, or nullptr
 };
 hipError_t launch_fuse_sum(const FuseSumArgs& a, hipStream_t s);
 // up to 4 independent sums (the outputs of one HRNet fuse module) as ONE launch; same arithmetic per element as launch_fuse_sum

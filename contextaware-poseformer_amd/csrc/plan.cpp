@@ -671,6 +671,7 @@ void Engine::build_lifter(const Tensor feats[4]) {
         op.p2 = pos;
         op.i0 = J; op.i1 = L; op.i2 = L1; op.C = C;
         op.bf16 = bf16() ? 1 : 0;
+        op.feat_bf16 = maps_bf16() ? 1 : 0;
         use(X);
         for (int l = 0; l < L; ++l) {
             const std::string ls = std::to_string(l);
@@ -708,6 +709,7 @@ void Engine::build_lifter(const Tensor feats[4]) {
         op.in[0] = feats[l].buf;
         op.H = feats[l].H; op.W = feats[l].W; op.C = Cl[l]; op.i0 = J;
         op.bf16 = bf16() ? 1 : 0;
+        op.feat_bf16 = maps_bf16() ? 1 : 0;
         use(feats[l].buf);
         const int S = new_buffer((size_t)J * Cl[l], "sampled" + ls);
         const int I = new_buffer((size_t)J * 2, "idx" + ls);
@@ -770,6 +772,7 @@ void Engine::build_lifter(const Tensor feats[4]) {
                 op.flops_per_frame += 2.0 * J * L * (double)C * 3 * NH * NS;
                 op.i0 = J; op.i1 = L; op.i2 = NH; op.i3 = NS; op.C = C;
                 op.bf16 = bf16() ? 1 : 0;
+                op.feat_bf16 = maps_bf16() ? 1 : 0;
                 op.idxs[0] = tap_pos; op.idxs[1] = tap_idx;
                 push(op);
             } else {
@@ -791,6 +794,7 @@ void Engine::build_lifter(const Tensor feats[4]) {
                 }
                 op.i0 = J; op.i1 = L; op.i2 = NH; op.i3 = NS;
                 op.bf16 = bf16() ? 1 : 0;
+                op.feat_bf16 = maps_bf16() ? 1 : 0;
                 op.idxs[0] = tap_pos; op.idxs[1] = tap_idx;
                 push(op);
             }
@@ -930,6 +934,55 @@ void Engine::build_lifter(const Tensor feats[4]) {
     }
 }
 
+// CAPF_PLAN_BF16_F32_STREAM: where each backbone tensor lives, decided from its readers ("bf16 only as MFMA operands, residual stream
+// fp32").  A tensor every reader of which is a conv's operand stays bf16 (conv1 of a BasicBlock, the stem, the ReLU'd middle links of the fuse
+// layers' stride-2 chains, layer1's conv1 / conv2): nobody reads its fp32 value.  A tensor with any other reader -- a residual add, a fuse-sum
+// input, a context map of the lifter -- is stored fp32 by its producer; if convs read it too, the producer also writes its bf16 rounding (the
+// "shadow") in the same epilogue and those convs take that as their operand.  So every conv keeps its bf16 operand path (the 2-D halo tile
+// stages bf16 pixels by LDS-DMA, which cannot convert); only epilogues change.  Every backbone bf16 conv runs the fp32-stream epilogue.
+bool Engine::plan_f32_stream(const Tensor feats[4]) {
+    const int n = (int)ops.size(), nb = (int)bufs.size();
+    std::vector<int> prod(nb, -1), conv_last(nb, -1);
+    std::vector<char> other(nb, 0);
+    for (int i = 0; i < n; ++i) {
+        const Op& op = ops[i];
+        if ((op.kind == OP_GEMM || op.kind == OP_FUSE) && op.out >= 0) prod[op.out] = i;
+        if (op.kind == OP_GEMM) {
+            if (op.in[0] >= 0) conv_last[op.in[0]] = i;
+            if (op.aux >= 0) other[op.aux] = 1;
+        } else if (op.kind == OP_FUSE) {
+            for (int k = 0; k < op.n_in; ++k) other[op.in[k]] = 1;
+        } else if (op.kind != OP_FORK && op.kind != OP_JOIN) {
+            err = "CAPF_PLAN_BF16_F32_STREAM: unexpected backbone op " + op.name;
+            return false;
+        }
+    }
+    for (int l = 0; l < 4; ++l) other[feats[l].buf] = 1;
+    for (int b = 0; b < nb; ++b) {
+        if (!other[b]) continue;
+        if (prod[b] < 0 || !(ops[prod[b]].kind == OP_FUSE || ops[prod[b]].bf16 == 1)) {
+            err = "CAPF_PLAN_BF16_F32_STREAM: a residual / fuse / context-map tensor without a bf16 conv or fuse-sum producer";
+            return false;
+        }
+        Op& p = ops[prod[b]];
+        const size_t elems = p.kind == OP_FUSE ? (size_t)p.H * p.W * p.C : (size_t)p.Ho * p.Wo * p.N;
+        p.st_f32 = 1;
+        bufs[b].elems = round64(elems);
+        if (conv_last[b] < 0) continue;
+        const int sh = new_buffer((elems + 1) / 2, bufs[b].tag + ".bf16");
+        bufs[sh].def_op = prod[b];
+        bufs[sh].last_op = conv_last[b];
+        p.sh = sh;
+        for (int i = prod[b] + 1; i <= conv_last[b]; ++i)
+            if (ops[i].kind == OP_GEMM && ops[i].in[0] == b) ops[i].in[0] = sh;
+    }
+    for (Op& op : ops) {
+        if (op.kind == OP_GEMM && op.bf16 == 1) op.f32s = 1;
+        if (op.kind == OP_FUSE) op.bf16 = 0;             // fp32 terms in, fp32 sum out (+ shadow)
+    }
+    return true;
+}
+
 // Greedy offset assignment over buffer lifetimes (ops run in order on one stream).
 void Engine::assign_offsets() {
     struct Live { size_t off, size; int last; };
@@ -978,7 +1031,7 @@ void Engine::schedule_regions() {
         };
         auto writes = [&](const Op& o, int b) {
             if (b < 0) return false;
-            if (o.out == b || o.aux2 == b) return true;
+            if (o.out == b || o.aux2 == b || o.sh == b) return true;      // (sh: the bf16 shadow of an fp32 output, CAPF_PLAN_BF16_F32_STREAM)
             for (int i = 0; i < 4; ++i) if (o.outs[i] == b) return true;
             return false;
         };
@@ -988,6 +1041,7 @@ void Engine::schedule_regions() {
             if (o.aux >= 0) v.push_back(o.aux);
             if (o.out >= 0) v.push_back(o.out);
             if (o.aux2 >= 0) v.push_back(o.aux2);
+            if (o.sh >= 0) v.push_back(o.sh);
             return v;
         };
         int max_level = 0;
@@ -1048,6 +1102,16 @@ bool Engine::build() {
     if (cfg.plan_flags & CAPF_PLAN_NO_F32X3) use_x3 = false;
     if (cfg.plan_flags & CAPF_PLAN_F32X3_EXACT) x3_h2 = false;
     if (cfg.plan_flags & CAPF_PLAN_NO_F32H2_GEMM) use_h2g = false;
+    if (cfg.plan_flags & CAPF_PLAN_BF16_F32_STREAM) {
+        if (!bf16()) { err = "CAPF_PLAN_BF16_F32_STREAM needs compute_dtype = CAPF_BF16"; return false; }
+        if (cfg.backbone != CAPF_HRNET) { err = "CAPF_PLAN_BF16_F32_STREAM is an HRNet plan (CPN50 is not supported)"; return false; }
+        if (cfg.plan_flags != CAPF_PLAN_BF16_F32_STREAM) { err = "CAPF_PLAN_BF16_F32_STREAM cannot be combined with other plan flags"; return false; }
+        f32_stream = true;
+        // layer1 runs as one launch per conv: the fused bottleneck kernels (bneck_bf16.hip) and the chained pointwise pair have no fp32-stream
+        // epilogue (EXPERIMENTS R7.1 prices it)
+        use_bneck = false;
+        use_pwchain = false;
+    }
     // tuning knobs of the diagnostic build only (diag_env is a constant nullptr in the product library)
     if (const char* fz = diag_env("CAPF_LIFTER_FUSED")) fused_lifter = atoi(fz) != 0;
     if (const char* wz = diag_env("CAPF_WINO")) use_wino = atoi(wz) != 0;
@@ -1070,6 +1134,7 @@ bool Engine::build() {
                 return false;
             }
         build_hrnet(img, feats);
+        if (f32_stream && !plan_f32_stream(feats)) return false;
     } else if (cfg.backbone == CAPF_CPN50) {
         build_cpn(img, feats);
     } else {
@@ -1077,7 +1142,7 @@ bool Engine::build() {
         return false;
     }
     for (int l = 0; l < 4; ++l) {
-        name_tensor(*this, "feat" + std::to_string(l), feats[l].buf, {-1, feats[l].H, feats[l].W, feats[l].C}, bf16() ? 2 : 0);
+        name_tensor(*this, "feat" + std::to_string(l), feats[l].buf, {-1, feats[l].H, feats[l].W, feats[l].C}, maps_bf16() ? 2 : 0);
         const int expect = cfg.backbone == CAPF_CPN50 ? cfg.base_dim : cfg.base_dim << l;
         if (feats[l].C != expect) {
             err = "poseformer.base_dim does not match the backbone's context-map widths";

@@ -103,6 +103,15 @@ enum capf_plan_flag {
                                      * own launch behind its producer (96 launches per step) instead of a handful of batched ones when the scratch
                                      * fills and at the end of capf_backward (csrc/train.cpp t_slab_flush / t_col_flush).  Same summation order per
                                      * element either way: bit-identical gradients (tests/test_gpu_train.py); an A/B aid                        */
+    /* (1 << 14 is unassigned and rejected: tests/test_abi.py pins that an unknown bit is refused) */
+    CAPF_PLAN_BF16_F32_STREAM = 32768, /* OPT-IN, compute_dtype = CAPF_BF16, HRNet (W32 / W48) only: bf16 only as conv operands, every other backbone tensor fp32
+                                     * (capf_oracle BF16_STREAM_FP32).  Weights fold and round as in the default bf16 plan; every activation a conv reads is
+                                     * rounded to bf16 once (RNE); residual adds, ReLU, fuse sums, nearest upsampling and the four context maps stay fp32,
+                                     * the lifter keeps the default bf16 placement and its samplers read the fp32 maps.  Storage is decided per tensor from
+                                     * its readers: conv operands only -> bf16; any residual / fuse-sum / lifter reader -> fp32, plus a bf16 "shadow" written
+                                     * by the same epilogue when convs read it too (capf_op_tensor slot 6; convs take the shadow, every residual is fp32).
+                                     * layer1 runs one launch per conv (no bneck_bf16.hip / pointwise chain).  capf_create refuses it with CAPF_F32, with
+                                     * CAPF_CPN50 and together with any other plan flag (CAPF_ERR_UNSUPPORTED).                                        */
     CAPF_PLAN_F32X3_EXACT = 256     /* ... on round 4's tile instead of the default one: every operand split EXACTLY into three bf16 pieces,
                                      * six piece products per fp32 MAC (igemm_f32x3_ws.hip).  The default (ABI 5) carries an operand as two
                                      * block-scaled fp16 pieces (to 2^-23) and issues three products: half the MFMAs, the same measured
@@ -123,8 +132,9 @@ const char* capf_version(void);
 /* ABI revision of THIS header.  A caller compiled against capf.h checks capf_abi_version() == CAPF_ABI_VERSION before it passes structs
  * (capf_config, capf_conv_desc, capf_op_desc) across the boundary: revision 5 = round 5 (capf_op_desc as declared below -- 240 bytes since
  * revision 4, 104 before --, plan flags up to CAPF_PLAN_F32X3_EXACT, the capf_op_*_f32h2 entry points, capf_op_describe_sized).  The
- * version string carries the same number ("capf 0.5 (gfx950)").                                                                            */
-#define CAPF_ABI_VERSION 6
+ * version string carries the same number ("capf 0.5 (gfx950)").  Revision 7 (additive): CAPF_PLAN_BF16_F32_STREAM and capf_op_tensor slot 6
+ * (an op's bf16 shadow output); struct layouts unchanged.                                                                                  */
+#define CAPF_ABI_VERSION 7
 int capf_abi_version(void);
 
 /* ---- parameter schema == the reference's state_dict ------------- */
@@ -232,7 +242,7 @@ int capf_set_debug(capf_handle* h, int on);
  *   tok_ctx / tok_res / tok_joint   token buffer [B,17,L+1,c] after each block group (layout b p l c)
  * Pointers are into the workspace and valid until the next forward on this handle.
  * Returns 0 for an fp32 tensor, 1 for an int32 tensor, 2 for a bf16 tensor (context maps of a
- * CAPF_BF16 handle), negative on error. */
+ * CAPF_BF16 handle; fp32 under CAPF_PLAN_BF16_F32_STREAM), negative on error. */
 int capf_tensor(const capf_handle* h, const char* name, const void** dev_ptr, int64_t shape[4],
                 int* ndim);
 
@@ -509,7 +519,8 @@ int capf_op_executed_flops(const capf_handle* h, int index, int batch, double* f
 int capf_op_bytes(const capf_handle* h, int index, int batch, double* bytes);
 /* capf_op_schedule: where op `index` sits in the launch schedule: its fork/join region (-1 outside / control op),
  *   its dependency level inside the region (capf_set_lanes mode 2 issues a region level by level), its lane
- *   (mode 1: side stream), and the workspace buffer ids it reads (5 slots) and writes (6 slots), -1 = unused,
+ *   (mode 1: side stream), and the workspace buffer ids it reads (5 slots) and writes (6 slots; a conv's / fuse sum's bf16 shadow under
+ *   CAPF_PLAN_BF16_F32_STREAM in the third), -1 = unused,
  *   -2 = the external image.  Lets host-side tests check that the schedule is a valid topological order. */
 int capf_op_schedule(const capf_handle* h, int index, int32_t* region, int32_t* level, int32_t* lane,
                      int32_t reads[5], int32_t writes[6]);
@@ -523,7 +534,9 @@ int capf_op_schedule(const capf_handle* h, int index, int32_t* region, int32_t* 
  *                         length after which every tensor the op touched is still intact in the workspace (buffers are
  *                         reused along the plan; a fork/join region keeps all of its buffers until its join).
  *   capf_op_tensor      : device pointer of one operand of op `index` after such a prefix (slot 0..3 inputs, 4 residual,
- *                         5 output; the external image for the stem's input).
+ *                         5 output, 6 the bf16 shadow of an fp32 output under CAPF_PLAN_BF16_F32_STREAM -- CAPF_ERR_INVALID where the op
+ *                         writes none; the external image for the stem's input).  Under that flag in_dtype / out_dtype are what is
+ *                         stored (a conv reading a shadow: in_dtype 2), and every residual a conv reads is fp32.
  * tests/test_gpu_layerwise.py recomputes every backbone op on the CPU from the engine's inputs and compares outputs.   */
 typedef struct capf_op_desc {
     int32_t kind;              /* 0 conv / linear on the MFMA kernels, 1 fuse-sum, 2 max-pool 3x3 s2, 3 bilinear resize, 4 LayerNorm over rows,
