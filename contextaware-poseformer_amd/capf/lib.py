@@ -10,7 +10,7 @@ HRNET, CPN50 = 0, 1
 F32, BF16 = 0, 1
 PLAN_NO_FUSED_LIFTER, PLAN_NO_WINOGRAD, PLAN_NO_ROW_HALO, PLAN_WINOGRAD_F23_ONLY, PLAN_NO_PWCHAIN, PLAN_NO_WS, PLAN_LIFTER_FP32, PLAN_NO_F32X3, PLAN_F32X3_EXACT, PLAN_NO_F32H2_GEMM, PLAN_NO_UPADD, PLAN_H2_PLANES, PLAN_NO_BNECK, PLAN_NO_BATCHED_REDUCE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192     # capf_plan_flag
 PLAN_BF16_F32_STREAM = 32768     # (1 << 14 stays unassigned)
-ABI_VERSION = 7        # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
+ABI_VERSION = 8        # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
 
 EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.py)
     "capf_create", "capf_destroy", "capf_last_error", "capf_version", "capf_num_params", "capf_param_info",
@@ -26,6 +26,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_op_conv_f32h2_pack_elems", "capf_op_pack_conv_f32h2", "capf_op_conv_f32h2_group",
     "capf_abi_version", "capf_op_describe_sized",
     "capf_jpeg_info", "capf_jpeg_coefficients", "capf_jpeg_decode",
+    "capf_jpeg_batch_info", "capf_jpeg_decode_batch", "capf_jpeg_coefficients_subseq",
     "capf_op_f32h2_gemm_pack_elems", "capf_op_pack_f32h2_gemm", "capf_op_conv_f32h2g", "capf_op_conv_f32h2g_group", "capf_op_linear_f32h2g", "capf_op_linear_ln_f32h2g", "capf_op_wgrad", "capf_op_conv_f32h2_tiles", "capf_op_conv_f32h2_planes", "capf_op_h2_planes",
 ]
 
@@ -1092,6 +1093,93 @@ def jpeg_decode(data, device="cuda"):
     if rc:
         raise CapfError(f"capf_jpeg_decode failed ({rc})")
     return out
+
+
+def _coef_shapes(width, height, components, h_samp, v_samp):
+    mx, my = -(-width // (8 * h_samp)), -(-height // (8 * v_samp))
+    return [(my * v_samp, mx * h_samp)] + [(my, mx)] * (components - 1)
+
+
+def _split_coefficients(buf, shapes):
+    out, o = [], 0
+    for a, b in shapes:
+        out.append(buf[o:o + a * b * 64].reshape(a, b, 64))
+        o += a * b * 64
+    return out
+
+
+def jpeg_coefficients_subseq(data, subseq_bytes=0):
+    """capf_jpeg_coefficients_subseq: the batched decoder's entropy stage (subsequence lanes, sync rounds, serial fallback) run serially on
+    the CPU; same result layout as jpeg_coefficients.  CapfError where the device would flag the file.  No GPU."""
+    import numpy as np
+    lib = load_library()
+    info = jpeg_info(data)
+    lib.capf_jpeg_coefficients_subseq.argtypes = [c_char_p, c_size_t, c_void_p, c_size_t, c_int]
+    shapes = _coef_shapes(info["width"], info["height"], info["components"], info["h_samp"], info["v_samp"])
+    total = sum(a * b * 64 for a, b in shapes)
+    buf = np.zeros(total, np.int16)
+    rc = lib.capf_jpeg_coefficients_subseq(data, len(data), buf.ctypes.data_as(c_void_p), total, int(subseq_bytes))
+    if rc:
+        raise CapfError(f"capf_jpeg_coefficients_subseq failed ({rc})")
+    return _split_coefficients(buf, shapes)
+
+
+def _byte_arrays(datas):
+    datas = [bytes(d) for d in datas]
+    n = len(datas)
+    ptrs = (ctypes.c_char_p * n)(*datas)
+    sizes = (c_size_t * n)(*[len(d) for d in datas])
+    return datas, ptrs, sizes
+
+
+def jpeg_batch_info(datas, subseq_bytes=0):
+    """-> (list of dict(width, height, components, coef_elems, status) per file, scratch bytes or None when a file is refused).  status is
+    0 or the capf_jpeg_info error of a file outside the supported subset.  Host code, no GPU."""
+    lib = load_library()
+    datas, ptrs, sizes = _byte_arrays(datas)
+    n = len(datas)
+    lib.capf_jpeg_batch_info.argtypes = [c_int, c_void_p, c_void_p, c_int, c_void_p, POINTER(c_size_t)]
+    info = (c_int32 * (5 * max(n, 1)))()
+    sb = c_size_t()
+    rc = lib.capf_jpeg_batch_info(n, ptrs, sizes, int(subseq_bytes), info, byref(sb))
+    rows = [dict(zip(("width", "height", "components", "coef_elems", "status"), info[5 * i:5 * i + 5])) for i in range(n)]
+    return rows, (sb.value if rc == 0 else None)
+
+
+def jpeg_decode_batch(datas, device="cuda", subseq_bytes=0, coefficients=False):
+    """A batch of baseline JPEG files (bytes) decoded in ONE call, Huffman decode included, on the GPU (capf_jpeg_decode_batch) -> (list of
+    uint8 CUDA tensors [H, W, 3] BGR, int32 CUDA status tensor [n][, per file the list of int16 CUDA coefficient tensors [rows, cols, 64]
+    per component]).  Nothing is synchronised: read `status` (0 = decoded) before trusting a file.  CapfError (nothing enqueued) when a
+    file is outside the supported subset."""
+    import torch
+    lib = load_library()
+    datas, ptrs, sizes = _byte_arrays(datas)
+    n = len(datas)
+    rows, scratch_bytes = jpeg_batch_info(datas, subseq_bytes)
+    bad = [i for i, r in enumerate(rows) if r["status"]]
+    if bad or scratch_bytes is None:
+        raise CapfError(f"capf_jpeg_batch_info: files {bad} are not JPEGs this path decodes ({[rows[i]['status'] for i in bad]})")
+    outs = [torch.empty(r["height"], r["width"], 3, dtype=torch.uint8, device=device) for r in rows]
+    status = torch.empty(n, dtype=torch.int32, device=device)
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
+    coef = torch.empty(sum(r["coef_elems"] for r in rows), dtype=torch.int16, device=device) if coefficients else None
+    out_ptrs = (c_void_p * n)(*[o.data_ptr() for o in outs])
+    pitches = (c_size_t * n)(*[o.stride(0) for o in outs])
+    lib.capf_jpeg_decode_batch.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int]
+    rc = lib.capf_jpeg_decode_batch(_stream(status), n, ptrs, sizes, out_ptrs, pitches, _p(coef), _p(scratch), scratch_bytes, _p(status),
+                                    int(subseq_bytes))
+    if rc:
+        raise CapfError(f"capf_jpeg_decode_batch failed ({rc})")
+    # (scratch may be freed on return: the caching allocator hands it out again only to work ordered after these kernels on this stream)
+    if not coefficients:
+        return outs, status
+    coefs, o = [], 0
+    for d, r in zip(datas, rows):
+        info = jpeg_info(d)
+        coefs.append(_split_coefficients(coef[o:o + r["coef_elems"]], _coef_shapes(r["width"], r["height"], r["components"],
+                                                                                     info["h_samp"], info["v_samp"])))
+        o += r["coef_elems"]
+    return outs, status, coefs
 
 
 # ---- N2: evaluation metrics (mvn/models/loss.py:25-101, datasets/human36m.py:358-417) ---------------------------

@@ -35,7 +35,31 @@ def imread(path_or_bytes, device="cuda"):
     return _capf.jpeg_decode(bytes(data), device)
 
 
-def load_and_crop_batch(paths_or_bytes, centers, scales, output_size, device="cuda"):
+def _read_bytes(path_or_bytes):
+    return bytes(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray)) else open(path_or_bytes, "rb").read()
+
+
+def imread_batch(paths_or_bytes, device="cuda", subseq_bytes=0):
+    """imread for a whole batch in ONE call, the Huffman decode on the GPU too (capf_jpeg_decode_batch): list of uint8 CUDA tensors
+    [H_i, W_i, 3], BGR, the same bits as imread.  Synchronises once to read the per-file status and raises CapfError naming the files
+    whose entropy data is corrupt (or, before any GPU work, the files outside the supported subset)."""
+    items = list(paths_or_bytes)
+    datas = [_read_bytes(p) for p in items]
+    outs, status = _capf.jpeg_decode_batch(datas, device, subseq_bytes)
+    bad = [(items[i] if not isinstance(items[i], (bytes, bytearray)) else f"#{i}", int(s)) for i, s in enumerate(status.cpu().tolist()) if s]
+    if bad:
+        raise _capf.CapfError(f"capf_jpeg_decode_batch: corrupt entropy data in {bad} (file, status bits)")
+    return outs
+
+
+def load_and_crop_batch(paths_or_bytes, centers, scales, output_size, device="cuda", decoder="host"):
     """The whole per-sample image path of Human36M.__getitem__ (human36m.py:292-300) for a batch: decode every frame on the GPU, then ONE
-    warp launch for all crops.  Returns uint8 CUDA [B, output_size[1], output_size[0], 3], what the prefetcher (capf_preprocess) consumes."""
-    return crop_image_batch([imread(p, device) for p in paths_or_bytes], centers, scales, output_size)
+    warp launch for all crops.  Returns uint8 CUDA [B, output_size[1], output_size[0], 3], what the prefetcher (capf_preprocess) consumes.
+    decoder="host": one imread per frame (host Huffman walk); "device": one imread_batch for all frames (same bits)."""
+    if decoder == "host":
+        frames = [imread(p, device) for p in paths_or_bytes]
+    elif decoder == "device":
+        frames = imread_batch(paths_or_bytes, device)
+    else:
+        raise ValueError(f"decoder must be 'host' or 'device', not {decoder!r}")
+    return crop_image_batch(frames, centers, scales, output_size)

@@ -133,8 +133,9 @@ const char* capf_version(void);
  * (capf_config, capf_conv_desc, capf_op_desc) across the boundary: revision 5 = round 5 (capf_op_desc as declared below -- 240 bytes since
  * revision 4, 104 before --, plan flags up to CAPF_PLAN_F32X3_EXACT, the capf_op_*_f32h2 entry points, capf_op_describe_sized).  The
  * version string carries the same number ("capf 0.5 (gfx950)").  Revision 7 (additive): CAPF_PLAN_BF16_F32_STREAM and capf_op_tensor slot 6
- * (an op's bf16 shadow output); struct layouts unchanged.                                                                                  */
-#define CAPF_ABI_VERSION 7
+ * (an op's bf16 shadow output); struct layouts unchanged.  Revision 8 (additive): the batched JPEG decode (capf_jpeg_batch_info,
+ * capf_jpeg_decode_batch, capf_jpeg_coefficients_subseq); struct layouts unchanged.                                                      */
+#define CAPF_ABI_VERSION 8
 int capf_abi_version(void);
 
 /* ---- parameter schema == the reference's state_dict ------------- */
@@ -492,6 +493,30 @@ int capf_jpeg_info(const uint8_t* data, size_t n_bytes, int32_t* width, int32_t*
 int capf_jpeg_coefficients(const uint8_t* data, size_t n_bytes, int16_t* coef, size_t coef_elems);
 int capf_jpeg_decode(void* stream, const uint8_t* data, size_t n_bytes, uint8_t* out_bgr, size_t out_pitch_bytes, void* scratch,
                      size_t scratch_bytes);
+/* capf_jpeg_batch_info / capf_jpeg_decode_batch: the same decode for a BATCH of files in one call, the entropy decode included, with the
+ *   output bits of capf_jpeg_decode.  The host parses each file's markers up to SOS and copies the entropy-coded bytes of the whole batch
+ *   to the device in ONE upload; the GPU removes FF 00 stuffing, finds the restart markers and decodes the Huffman stream by
+ *   self-synchronising subsequences (csrc/jpeg_sync.h): each segment (restart interval, or the whole scan) is cut into subsequence_bytes
+ *   pieces, one lane each, whose guessed start states are reconciled in a fixed number of sync rounds, and any segment not yet proven
+ *   after them is finished by one lane decoding serially -- results never depend on convergence.  IDCT, upsampling and colour then run
+ *   as one grid over all blocks / pixels of the batch.
+ *   capf_jpeg_batch_info (host only): info[n][5] = width, height, components, coefficient count (capf_jpeg_coefficients' layout),
+ *   status (CAPF_OK or the file's capf_jpeg_info error); *scratch_bytes = device scratch capf_jpeg_decode_batch needs for this batch at
+ *   this subsequence length.  Returns the first file's error if any file is outside the supported subset.
+ *   capf_jpeg_decode_batch: out_bgr = HOST array of n device pointers (uint8 BGR [height][width][3], row pitch out_pitch_bytes[i]);
+ *   coef_out = optional device int16 buffer receiving every file's coefficients back to back (capf_jpeg_coefficients' layout, files in
+ *   order); scratch = device memory of at least the batch_info size; status = device int32[n], 0 or a bitwise OR of
+ *   1 (a DC category > 11 or an AC size > 10), 2 (a segment's entropy data does not decode to its MCU count), 4 (restart-marker count
+ *   differs from ceil(MCUs / interval) - 1).  A flagged file's pixels are undefined; the other files are unaffected.  The whole batch
+ *   is refused before anything is enqueued if any file is outside the supported subset (its capf_jpeg_info error).  Enqueues on
+ *   `stream` and waits only for its own staging upload, never for the kernels.  subseq_bytes: 0 = the default (256), else 1 .. 2^20.
+ * capf_jpeg_coefficients_subseq: the device algorithm's steps run serially on the CPU (same code, lane by lane, same sync rounds and
+ *   fallback) -> capf_jpeg_coefficients' output, or CAPF_ERR_INVALID where the device would set a status bit (tests; no GPU). */
+int capf_jpeg_batch_info(int n, const uint8_t* const* data, const size_t* n_bytes, int subseq_bytes, int32_t* info, size_t* scratch_bytes);
+int capf_jpeg_decode_batch(void* stream, int n, const uint8_t* const* data, const size_t* n_bytes, uint8_t* const* out_bgr,
+                           const size_t* out_pitch_bytes, int16_t* coef_out, void* scratch, size_t scratch_bytes, int32_t* status,
+                           int subseq_bytes);
+int capf_jpeg_coefficients_subseq(const uint8_t* data, size_t n_bytes, int16_t* coef, size_t coef_elems, int subseq_bytes);
 int capf_affine_from_center_scale(const double center[2], const double scale[2], int out_w, int out_h, double m[6]);
 int capf_warp_affine(void* stream, const uint8_t* const* frames, const int32_t* dims, const double* m, int batch,
                      int out_h, int out_w, uint8_t* out);
