@@ -10,7 +10,7 @@ HRNET, CPN50 = 0, 1
 F32, BF16 = 0, 1
 PLAN_NO_FUSED_LIFTER, PLAN_NO_WINOGRAD, PLAN_NO_ROW_HALO, PLAN_WINOGRAD_F23_ONLY, PLAN_NO_PWCHAIN, PLAN_NO_WS, PLAN_LIFTER_FP32, PLAN_NO_F32X3, PLAN_F32X3_EXACT, PLAN_NO_F32H2_GEMM, PLAN_NO_UPADD, PLAN_H2_PLANES, PLAN_NO_BNECK, PLAN_NO_BATCHED_REDUCE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192     # capf_plan_flag
 PLAN_BF16_F32_STREAM = 32768     # (1 << 14 stays unassigned)
-ABI_VERSION = 8        # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
+ABI_VERSION = 9        # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
 
 EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.py)
     "capf_create", "capf_destroy", "capf_last_error", "capf_version", "capf_num_params", "capf_param_info",
@@ -28,6 +28,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_jpeg_info", "capf_jpeg_coefficients", "capf_jpeg_decode",
     "capf_jpeg_batch_info", "capf_jpeg_decode_batch", "capf_jpeg_coefficients_subseq",
     "capf_op_f32h2_gemm_pack_elems", "capf_op_pack_f32h2_gemm", "capf_op_conv_f32h2g", "capf_op_conv_f32h2g_group", "capf_op_linear_f32h2g", "capf_op_linear_ln_f32h2g", "capf_op_wgrad", "capf_op_conv_f32h2_tiles", "capf_op_conv_f32h2_planes", "capf_op_h2_planes",
+    "capf_fliptest_fuse_swap", "capf_pck_counts",
 ]
 
 
@@ -157,6 +158,8 @@ def load_library():
     lib.capf_pose_errors.argtypes = [P, P, P, c_int, c_int, P, P]
     lib.capf_segment_sums.argtypes = [P, P, P, P, c_int, c_int, P, P]
     lib.capf_keypoints_loss.argtypes = [P, c_int, P, P, P, c_int, c_int, c_float, P, P]
+    lib.capf_fliptest_fuse_swap.argtypes = [P, P, c_int, c_int, POINTER(c_int32), P]
+    lib.capf_pck_counts.argtypes = [P, P, P, c_int, c_int, c_int, c_double, P, c_int, P, P, P]
     _lib = lib
     return lib
 
@@ -996,15 +999,27 @@ def preprocess(images_u8, gt, k2d, kcrop, backbone="hrnet_32", mode=0):
     return img_out, gt_out, k2d_out, kc_out
 
 
-def fliptest_fuse(pred2):
-    """pred2 [2,B,1,17,3] (original, mirrored) -> [B,1,17,3]  (train.py:177-180)."""
+# the 3DHP skeleton's mirror table: joints_left [5, 6, 7, 11, 12, 13] <-> joints_right [2, 3, 4, 8, 9, 10] (ContextPose_mpi/run_3dhp.py:45-46)
+MPI_SWAP = (0, 1, 5, 6, 7, 2, 3, 4, 11, 12, 13, 8, 9, 10, 14, 15, 16)
+
+
+def fliptest_fuse(pred2, swap=None):
+    """pred2 [2,B,1,J,3] (original, mirrored) -> [B,1,J,3]: the mirrored prediction's x negated, its joints swapped, the mean of the
+    two.  swap None: the H36M table of train.py:177-180 (capf_fliptest_fuse, J = 17); else a sequence of J ints, swap[j] = the joint of
+    the mirrored prediction that lands on joint j (MPI_SWAP: run_3dhp.py:169-180), a permutation that is its own inverse."""
     import torch
     lib = load_library()
-    B = pred2.shape[1]
-    out = torch.empty(B, 1, 17, 3, dtype=torch.float32, device=pred2.device)
-    rc = lib.capf_fliptest_fuse(_stream(pred2), _p(pred2.contiguous()), B, _p(out))
+    B, J = pred2.shape[1], pred2.shape[-2]
+    out = torch.empty(B, 1, J, 3, dtype=torch.float32, device=pred2.device)
+    if swap is None:
+        rc = lib.capf_fliptest_fuse(_stream(pred2), _p(pred2.contiguous()), B, _p(out))
+    else:
+        tab = [int(v) for v in swap]
+        if len(tab) != J:
+            raise ValueError(f"swap has {len(tab)} entries for {J} joints")
+        rc = lib.capf_fliptest_fuse_swap(_stream(pred2), _p(pred2.contiguous()), B, J, (c_int32 * J)(*tab), _p(out))
     if rc:
-        raise CapfError(f"capf_fliptest_fuse failed ({rc})")
+        raise CapfError(f"capf_fliptest_fuse{'' if swap is None else '_swap'} failed ({rc})")
     return out
 
 
@@ -1207,6 +1222,30 @@ def segment_sums(err, segment=None, prev=None, n_segments=1):
     if rc:
         raise CapfError(f"capf_segment_sums failed ({rc})")
     return sums, counts
+
+
+PCK_THRESHOLDS = 31     # 0, 5, ..., 150 mm (mpii_compute_3d_pck.m:20)
+
+
+def pck_counts(pred, gt, root=14, to_mm=1.0, segment=None, n_segments=1):
+    """capf_pck_counts.  pred / gt: CUDA fp32 [n, J, 3] in the same unit (to_mm: that unit in mm); segment: CUDA int32 [n] or None.
+    -> (counts int32 [n_segments, J, 31], mpjpe_sums float64 [n_segments, J], frames int32 [n_segments]) on the device."""
+    import torch
+    lib = load_library()
+    n, J, _ = gt.shape
+    dev = gt.device
+    counts = torch.empty(n_segments, J, PCK_THRESHOLDS, dtype=torch.int32, device=dev)
+    sums = torch.empty(n_segments, J, dtype=torch.float64, device=dev)
+    frames = torch.empty(n_segments, dtype=torch.int32, device=dev)
+    if segment is not None:
+        segment = segment.to(torch.int32).contiguous()
+    pred = pred.contiguous()
+    gt = gt.contiguous()
+    rc = lib.capf_pck_counts(_stream(gt), _p(pred) if n else c_void_p(0), _p(gt) if n else c_void_p(0), n, J, int(root), float(to_mm),
+                             _p(segment), n_segments, _p(counts), _p(sums), _p(frames))
+    if rc:
+        raise CapfError(f"capf_pck_counts failed ({rc})")
+    return counts, sums, frames
 
 
 def keypoints_loss(mode, pred, gt, validity, threshold=0.0, want_grad=False):

@@ -591,7 +591,7 @@ static std::string g_create_error;
 
 extern "C" {
 
-const char* capf_version(void) { return "capf 0.8 (gfx950)"; }
+const char* capf_version(void) { return "capf 0.9 (gfx950)"; }
 int capf_abi_version(void) { return CAPF_ABI_VERSION; }
 
 const char* capf_last_error(const capf_handle* h) { return h ? h->e.err.c_str() : g_create_error.c_str(); }
@@ -1259,6 +1259,14 @@ int capf_fliptest_fuse(void* stream, const float* pred2, int batch, float* out) 
     return capf::launch_fliptest_fuse(pred2, batch, out, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
+int capf_fliptest_fuse_swap(void* stream, const float* pred2, int batch, int joints, const int32_t* swap, float* out) {
+    if (!pred2 || !out || !swap || batch <= 0 || joints <= 0 || joints > capf::FLIP_MAX_JOINTS) return CAPF_ERR_INVALID;
+    for (int j = 0; j < joints; ++j)           // a permutation that is its own inverse (left <-> right pairs, the rest fixed)
+        if (swap[j] < 0 || swap[j] >= joints || swap[swap[j]] != j) return CAPF_ERR_INVALID;
+    return capf::launch_fliptest_fuse_swap(pred2, batch, joints, swap, out, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK
+                                                                                                                       : CAPF_ERR_HIP;
+}
+
 int capf_affine_from_center_scale(const double center[2], const double scale[2], int out_w, int out_h, double m[6]) {
     if (!center || !scale || !m || out_w <= 1 || out_h <= 1) return CAPF_ERR_INVALID;
     return capf::affine_from_center_scale(center, scale, out_w, out_h, m) ? CAPF_OK : CAPF_ERR_INVALID;
@@ -1282,6 +1290,15 @@ int capf_segment_sums(void* stream, const float* err, const int32_t* segment, co
     if (!err || !sums || !counts || n <= 0 || n_segments <= 0 || (n_segments > 1 && !segment)) return CAPF_ERR_INVALID;
     return capf::launch_segment_sums(err, segment, prev, n, n_segments, sums, counts, static_cast<hipStream_t>(stream)) == hipSuccess
                ? CAPF_OK : CAPF_ERR_HIP;
+}
+
+int capf_pck_counts(void* stream, const float* pred, const float* gt, int n, int joints, int root, double to_mm, const int32_t* segment,
+                    int n_segments, int32_t* counts, double* mpjpe_sums, int32_t* frames) {
+    if (!counts || !mpjpe_sums || !frames || n < 0 || (n > 0 && (!pred || !gt)) || joints <= 0 || joints > 32 || root < 0 ||
+        root >= joints || n_segments <= 0 || (n_segments > 1 && n > 0 && !segment) || !(to_mm > 0.0))
+        return CAPF_ERR_INVALID;
+    return capf::launch_pck_counts(pred, gt, n, joints, root, to_mm, segment, n_segments, counts, mpjpe_sums, frames,
+                                   static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
 int capf_keypoints_loss(void* stream, int mode, const float* pred, const float* gt, const float* validity, int rows, int dim,

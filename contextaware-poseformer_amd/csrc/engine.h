@@ -134,8 +134,8 @@ struct TrainLayout {
     struct Ctx { size_t xh1, rs1, y1, ao, U[4], xh2, rs2, y2, hp, hg; };
     struct Att { size_t xh1, rs1, y1, qkv, o, xh2, rs2, y2, hp, hg; };
     size_t X, S[4];
-    Ctx ctx[4];
-    Att res[4], joint[4];
+    Ctx ctx[4];                              // (one per context block: levels of them)
+    Att res[8], joint[8];                    // (one per block of each group: depth <= 8 of them)
     size_t xhh, rsh, yh;
     size_t dX, gA, gB, gC, cat, dU[4], tA, tB, wT, slabs, red;
     size_t h2w, h2max;                       // the step's weights as two-fp16-piece packs (W and W^T: Engine::t_h2_specs), and their maxima scratch
@@ -252,6 +252,7 @@ struct Engine {
     bool bf16() const { return cfg.compute_dtype == CAPF_BF16; }
     bool f32_stream = false;       // plan_flags & CAPF_PLAN_BF16_F32_STREAM: bf16 only as conv operands, every other backbone tensor fp32
     bool maps_bf16() const { return bf16() && !f32_stream; }   // the context maps feat0..3 are stored bf16
+    int depth() const { return cfg.depth > 0 ? cfg.depth : cfg.levels; }   // blocks per group (res_blocks / joint_blocks)
     bool plan_f32_stream(const Tensor feats[4]);
     size_t act_elems(size_t n) const { return bf16() ? (n + 1) / 2 : n; }   // backbone activation size in float slots
     void use(int buf);   // mark buffer as read by the op being appended

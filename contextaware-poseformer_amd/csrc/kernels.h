@@ -485,7 +485,10 @@ hipError_t launch_pos_grad(const float* dX, float* dpos, int B, int J, int L1, i
 hipError_t launch_preprocess(const unsigned char* images_bgr, int B, int H, int W, const float mean[3], const float* stdv,
                              int mode, float* images_out, const float* gt_in, float* gt_out, const float* k2d_in,
                              float* k2d_out, const float* kc_in, float* kc_out, hipStream_t s);
-hipError_t launch_fliptest_fuse(const float* pred2, int B, float* out, hipStream_t s);
+hipError_t launch_fliptest_fuse(const float* pred2, int B, float* out, hipStream_t s);     // the H36M table (kSwap)
+// any skeleton: swap[j] = the joint whose mirrored prediction lands on joint j (J <= FLIP_MAX_JOINTS; a kernel argument)
+constexpr int FLIP_MAX_JOINTS = 32;
+hipError_t launch_fliptest_fuse_swap(const float* pred2, int B, int J, const int* swap, float* out, hipStream_t s);
 // N3 (preprocess.hip): get_affine_transform (host) and cv2.warpAffine INTER_LINEAR for 8-bit BGR frames
 bool affine_from_center_scale(const double center[2], const double scale[2], int out_w, int out_h, double M[6]);
 hipError_t launch_warp_affine_u8(const unsigned char* const* frames, const int* dims, const double* M, unsigned char* out,
@@ -495,6 +498,10 @@ hipError_t launch_warp_affine_u8(const unsigned char* const* frames, const int* 
 hipError_t launch_pose_errors(const float* pred, const float* gt, int n, int J, const int* prev, float* err, hipStream_t s);
 hipError_t launch_segment_sums(const float* err, const int* seg, const int* prev, int n, int n_seg, double* sums, int* counts,
                                hipStream_t s);
+// MPI-INF-3DHP PCK / AUC / MPJPE counts: counts [n_seg][J][PCK_THRESHOLDS] int32, sums [n_seg][J] fp64, frames [n_seg] int32
+constexpr int PCK_THRESHOLDS = 31;
+hipError_t launch_pck_counts(const float* pred, const float* gt, int n, int J, int root, double to_mm, const int* seg, int n_seg,
+                             int* counts, double* sums, int* frames, hipStream_t s);
 hipError_t launch_keypoints_loss(const float* pred, const float* gt, const float* validity, int rows, int D, int mode, float thr,
                                  float* loss, float* dpred, hipStream_t s);
 

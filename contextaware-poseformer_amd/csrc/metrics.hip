@@ -197,6 +197,66 @@ hipError_t launch_segment_sums(const float* err, const int* seg, const int* prev
     return hipGetLastError();
 }
 
+// MPI-INF-3DHP evaluation (ContextPose_mpi/3dhp_test/test_util): per pose, the ground truth is made relative to its root joint
+// (mpii_test_predictions_py.m:46), the prediction's root joint is zero (run_3dhp.py:118), and the per-joint Euclidean error in mm
+// (:50-51) is counted against the thresholds 0, 5, ..., 150 with a strict `<` (mpii_compute_3d_pck.m:20, 30) and summed for the
+// MPJPE means (mpii_evaluate_errors.m:26, 47).  One block per (segment, joint); thread t takes poses t, t + 256, ... in order and
+// the block reduces in a fixed tree: integer counts exact, fp64 sums in a fixed order (same bits on every call).  The error is
+// formed in fp64, every operation rounded on its own (no contraction; sqrt correctly rounded), so a float64 restatement
+// ((dx^2 + dy^2) + dz^2, then sqrt, then x to_mm) gets the same numbers and the same counts.
+__global__ __launch_bounds__(256) void pck_counts_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int n, int J,
+                                                         int root, double to_mm, const int* __restrict__ seg, int* __restrict__ counts,
+                                                         double* __restrict__ sums, int* __restrict__ frames) {
+#pragma clang fp contract(off)
+    __shared__ int cnt[256][PCK_THRESHOLDS + 1];          // (+1: the pose count of the segment)
+    __shared__ double red[256];
+    const int sid = blockIdx.x / J, j = blockIdx.x - sid * J, t = threadIdx.x;
+    int c[PCK_THRESHOLDS + 1];
+#pragma unroll
+    for (int k = 0; k <= PCK_THRESHOLDS; ++k) c[k] = 0;
+    double acc = 0.0;
+    for (int i = t; i < n; i += 256) {
+        if (seg && seg[i] != sid) continue;
+        const float* g = gt + ((size_t)i * J + j) * 3;
+        const float* r = gt + ((size_t)i * J + root) * 3;
+        const float* p = pred + ((size_t)i * J + j) * 3;
+        double e2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const double pv = j == root ? 0.0 : (double)p[a];
+            const double d = pv - ((double)g[a] - (double)r[a]);
+            e2 = e2 + d * d;
+        }
+        const double e = sqrt(e2) * to_mm;
+#pragma unroll
+        for (int k = 0; k < PCK_THRESHOLDS; ++k) c[k] += e < 5.0 * k ? 1 : 0;
+        ++c[PCK_THRESHOLDS];
+        acc += e;
+    }
+#pragma unroll
+    for (int k = 0; k <= PCK_THRESHOLDS; ++k) cnt[t][k] = c[k];
+    red[t] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            for (int k = 0; k <= PCK_THRESHOLDS; ++k) cnt[t][k] += cnt[t + o][k];
+            red[t] += red[t + o];
+        }
+        __syncthreads();
+    }
+    if (t < PCK_THRESHOLDS) counts[((size_t)sid * J + j) * PCK_THRESHOLDS + t] = cnt[0][t];
+    if (t == 0) {
+        sums[(size_t)sid * J + j] = red[0];
+        if (j == 0) frames[sid] = cnt[0][PCK_THRESHOLDS];
+    }
+}
+
+hipError_t launch_pck_counts(const float* pred, const float* gt, int n, int J, int root, double to_mm, const int* seg, int n_seg,
+                             int* counts, double* sums, int* frames, hipStream_t s) {
+    if (n < 0 || J <= 0 || J > MAXJ || root < 0 || root >= J || n_seg <= 0 || (long)n_seg * J > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pck_counts_kernel, dim3(n_seg * J), dim3(256), 0, s, pred, gt, n, J, root, to_mm, seg, counts, sums, frames);
+    return hipGetLastError();
+}
+
 // KeypointsMSELoss / KeypointsMSESmoothLoss / KeypointsMAELoss (loss.py:104-137):
 //   loss = sum(f(gt - pred) * validity) / (D * max(1, sum(validity)));  validity is [rows, 1] broadcast over D
 //   mode 0: f = d^2;  1: d^2, and terms above `thr` replaced by term^0.1 * thr^0.9;  2: |d|

@@ -1084,10 +1084,19 @@ bool Engine::build() {
         err = "unsupported lifter configuration (levels must be 4, 4x4 deformable sampling, embed_dim_ratio % 32 == 0)";
         return false;
     }
-    if (cfg.depth != 0 && cfg.depth != cfg.levels && (cfg.depth < 1 || cfg.depth > 8 || cfg.context_blocks || cfg.training)) {
-        err = "depth != levels: 1..8 blocks per group, only for the variant without context blocks (ContextPose_mpi) and only for "
-              "inference plans";
-        return false;
+    // depth != levels: the variant without context blocks (ContextPose_mpi, pose_dformer.py:199).  Inference plans at any width; training
+    // plans at the widths that app builds (run_3dhp.py:219-232 and common/cfg.py:81-82: embed_dim_ratio 64 over base_dim 32, 96 over 48),
+    // whose head dims (8 / 12 res, 40 / 60 joint) tests/test_gpu_mpi_train.py holds to fp64 at depths 1..8
+    if (cfg.depth != 0 && cfg.depth != cfg.levels) {
+        const bool mpi_width = (cfg.base_dim == 32 && cfg.embed_dim_ratio == 64) || (cfg.base_dim == 48 && cfg.embed_dim_ratio == 96);
+        if (cfg.depth < 1 || cfg.depth > 8 || cfg.context_blocks || (cfg.training && !mpi_width)) {
+            err = cfg.context_blocks ? "depth != levels: 1..8 blocks per group, only for the variant without context blocks (ContextPose_mpi) and only for "
+                                       "inference plans"
+                  : (cfg.depth < 1 || cfg.depth > 8) ? "depth != levels: 1..8 blocks per group (the variant without context blocks, ContextPose_mpi)"
+                  : "depth != levels with training = 1: only at the ContextPose_mpi widths (embed_dim_ratio 64 over base_dim 32, 96 over 48); "
+                    "other widths train at depth == levels";
+            return false;
+        }
     }
     if (cfg.plan_flags & CAPF_PLAN_NO_FUSED_LIFTER) fused_lifter = false;
     if (cfg.plan_flags & CAPF_PLAN_NO_WINOGRAD) use_wino = false;

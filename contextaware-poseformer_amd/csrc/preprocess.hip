@@ -4,14 +4,15 @@
 //                   normalised fp32 RGB NHWC (channel flip :45, /255 - mean (/ std) :47-50), root-relative
 //                   ground truth (:52-53), optional train-time horizontal flip with left/right joint swap
 //                   (:55-65) or flip-test stacking of the original and the mirrored sample (:67-80);
-//   fliptest_fuse — ContextPose/train.py:177-180: un-mirror the second prediction and average.
+//   fliptest_fuse — ContextPose/train.py:177-180 (H36M) and ContextPose_mpi/run_3dhp.py:169-180 (3DHP, the caller's
+//                   swap table): un-mirror the second prediction and average.
 // Same fp32 operation order as the reference as it runs on a GPU ((u * (1/255) - mean) / std; 192 - x - 1), so
 // results are bit-identical to the torch expressions.  Built with -ffp-contract=off.
 #include "kernels.h"
 
 namespace capf {
 
-// H36M skeleton: joints_left / joints_right of mvn/datasets/utils.py:12-13 as a swap table
+// H36M skeleton: joints_left / joints_right of mvn/datasets/utils.py:12-13 as a swap table (launch_fliptest_fuse holds a host copy)
 __device__ __constant__ int kSwap[17] = {0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13};
 
 // out[s, b, h, w, c] for s in {0 (as is), 1 (mirrored along W)}; `mirror_first` mirrors sample 0 (train flip)
@@ -88,12 +89,16 @@ hipError_t launch_preprocess(const unsigned char* images_bgr, int B, int H, int 
 }
 
 // out[b, j, :] = 0.5 * (pred[0, b, j, :] + unmirror(pred[1, b, :, :])[j])     (train.py:177-180)
-__global__ void fliptest_fuse_kernel(const float* __restrict__ pred2, float* __restrict__ out, int B) {
+// the swap table travels in the kernel arguments (no per-call device allocation): swap[j] = the joint of the mirrored
+// prediction that lands on joint j
+struct FlipSwap { int j[FLIP_MAX_JOINTS]; };
+
+__global__ void fliptest_fuse_kernel(const float* __restrict__ pred2, float* __restrict__ out, int B, int J, FlipSwap sw) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= B * 17) return;
-    const int j = t % 17, b = t / 17;
-    const float* p = pred2 + ((long)b * 17 + j) * 3;
-    const float* q = pred2 + (((long)B + b) * 17 + kSwap[j]) * 3;
+    if (t >= B * J) return;
+    const int j = t % J, b = t / J;
+    const float* p = pred2 + ((long)b * J + j) * 3;
+    const float* q = pred2 + (((long)B + b) * J + sw.j[j]) * 3;
     float* o = out + (long)t * 3;
     // torch.mean over a dim of size 2: (a + b) / 2
     o[0] = __fdiv_rn(__fadd_rn(p[0], -q[0]), 2.0f);
@@ -101,9 +106,21 @@ __global__ void fliptest_fuse_kernel(const float* __restrict__ pred2, float* __r
     o[2] = __fdiv_rn(__fadd_rn(p[2], q[2]), 2.0f);
 }
 
-hipError_t launch_fliptest_fuse(const float* pred2, int B, float* out, hipStream_t s) {
-    hipLaunchKernelGGL(fliptest_fuse_kernel, dim3((B * 17 + 127) / 128), dim3(128), 0, s, pred2, out, B);
+hipError_t launch_fliptest_fuse_swap(const float* pred2, int B, int J, const int* swap, float* out, hipStream_t s) {
+    if (B <= 0 || J <= 0 || J > FLIP_MAX_JOINTS || (long)B * J > 0x7fffffffL) return hipErrorInvalidValue;
+    FlipSwap sw{};
+    for (int j = 0; j < J; ++j) {
+        if (swap[j] < 0 || swap[j] >= J) return hipErrorInvalidValue;
+        sw.j[j] = swap[j];
+    }
+    hipLaunchKernelGGL(fliptest_fuse_kernel, dim3((B * J + 127) / 128), dim3(128), 0, s, pred2, out, B, J, sw);
     return hipGetLastError();
+}
+
+// the H36M entry: kSwap's table through the same kernel
+hipError_t launch_fliptest_fuse(const float* pred2, int B, float* out, hipStream_t s) {
+    static const int h36m[17] = {0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13};
+    return launch_fliptest_fuse_swap(pred2, B, 17, h36m, out, s);
 }
 
 // ---- N3: the per-frame affine crop (mvn/utils/img.py:16-69, human36m.py:281-302) ------------------------

@@ -34,7 +34,7 @@ static int r32(int n) { return (n + 31) / 32 * 32; }
 // ---------------------------------------------------------------------------------------------------
 void Engine::train_layout(int B, TrainLayout& L) const {
     const int J = cfg.num_joints, Lv = cfg.levels, L1 = Lv + 1, C = cfg.embed_dim_ratio, D = C * L1;
-    const int NH = cfg.deform_heads;
+    const int NH = cfg.deform_heads, DEP = depth();
     size_t cur = 0;
     auto take = [&](size_t pf, size_t fixed = 0) {
         const size_t o = cur;
@@ -51,7 +51,7 @@ void Engine::train_layout(int B, TrainLayout& L) const {
         c.xh2 = take(R * C); c.rs2 = take(R); c.y2 = take(R * C); c.hp = take(R * 2 * C); c.hg = take(R * 2 * C);
     }
     for (int g = 0; g < 2; ++g)
-        for (int i = 0; i < Lv; ++i) {
+        for (int i = 0; i < DEP; ++i) {
             TrainLayout::Att& a = g == 0 ? L.res[i] : L.joint[i];
             const size_t E = (size_t)J * D;       // rows * dim is J*D elements per frame for both groups
             const size_t R = g == 0 ? (size_t)J * L1 : (size_t)J;
@@ -105,7 +105,7 @@ void Engine::t_h2_plan() {
     if (!use_h2g || bf16() || !cfg.training) return;
     const std::string V = "volume_net";
     const int Lv = cfg.levels, L1 = Lv + 1, C = cfg.embed_dim_ratio, D = C * L1;
-    const int NH = cfg.deform_heads, NS = cfg.deform_samples;
+    const int NH = cfg.deform_heads, NS = cfg.deform_samples, DEP = depth();
     auto add = [&](const std::string& name, int N, int K, bool fwd, bool bwd) {
         const auto it = param_index.find(name + ".weight");
         if (it == param_index.end()) return;
@@ -123,7 +123,7 @@ void Engine::t_h2_plan() {
         add(p + ".mlp.fc2", C, 2 * C, true, true);
     }
     for (int g = 0; g < 2; ++g)
-        for (int i = 0; i < Lv; ++i) {
+        for (int i = 0; i < DEP; ++i) {
             const std::string p = V + (g == 0 ? ".res_blocks." : ".joint_blocks.") + std::to_string(i);
             const int dim = g == 0 ? C : D;
             add(p + ".attn.qkv", 3 * dim, dim, true, true);
@@ -358,8 +358,9 @@ static const float* P(const Engine& e, const std::string& n) { return e.params[e
 
 // ---------------------------------------------------------------------------------------------------
 // forward (training): same math as the inference plan, every intermediate kept
-// masks: DropPath multipliers (0 or 1/keep_prob), or nullptr for "no drop":
-//   ctx[i]: m1[B], m2[B]  |  res[i]: m1[B*J], m2[B*J]  |  joint[i]: m1[B], m2[B]      (i = 0..levels-1)
+// masks: DropPath multipliers (0 or 1/keep_prob), or nullptr for "no drop" (include/capf.h, capf_forward_train):
+//   context_blocks = 1:  ctx[i]: m1[B], m2[B]  |  res[i]: m1[B*J], m2[B*J]  |  joint[i]: m1[B], m2[B]      (i = 0..levels-1)
+//   context_blocks = 0:  res[i]: m1[B*J], m2[B*J]  |  joint[i]: m1[B], m2[B]                             (i = 0..depth-1)
 // ---------------------------------------------------------------------------------------------------
 int Engine::forward_train(hipStream_t s, int B, const float* masks) {
     const std::string V = "volume_net";
@@ -369,9 +370,10 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
     train_layout(B, L);
     float* tw = ws + ws_elems_per_frame * (size_t)B;
     float* X = tw + L.X;
+    const int DEP = depth();
     const float* m_ctx = masks;
-    const float* m_res = masks ? masks + (size_t)2 * Lv * B : nullptr;
-    const float* m_joint = masks ? m_res + (size_t)2 * Lv * B * J : nullptr;
+    const float* m_res = masks ? masks + (cfg.context_blocks ? (size_t)2 * Lv * B : 0) : nullptr;
+    const float* m_joint = masks ? m_res + (size_t)2 * DEP * B * J : nullptr;
 
     if (int rc = t_h2_prepare(s, L, tw, B)) return rc;
     // the GEMMs read W as [N][Kpad] with Kpad a multiple of 32; a linear over a context map with K % 32 != 0 (HRNet-48's 48 channels) gets this
@@ -450,7 +452,7 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
     for (int g = 0; g < 2; ++g) {
         const int dim = g == 0 ? C : D, R = g == 0 ? B * J * L1 : B * J;
         const int tokens = g == 0 ? L1 : J, groups = g == 0 ? B * J : B, per = g == 0 ? L1 : J;
-        for (int i = 0; i < Lv; ++i) {
+        for (int i = 0; i < DEP; ++i) {
             const std::string p = V + (g == 0 ? ".res_blocks." : ".joint_blocks.") + std::to_string(i);
             const TrainLayout::Att& a = g == 0 ? L.res[i] : L.joint[i];
             const float* mb = g == 0 ? m_res : m_joint;
@@ -508,9 +510,10 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
     float* gA = tw + L.gA;
     float* gB = tw + L.gB;
     auto G = [&](const std::string& n) { return flat + grad_off[param_index.at(n)]; };
+    const int DEP = depth();
     const float* m_ctx = masks;
-    const float* m_res = masks ? masks + (size_t)2 * Lv * B : nullptr;
-    const float* m_joint = masks ? m_res + (size_t)2 * Lv * B * J : nullptr;
+    const float* m_res = masks ? masks + (cfg.context_blocks ? (size_t)2 * Lv * B : 0) : nullptr;
+    const float* m_joint = masks ? m_res + (size_t)2 * DEP * B * J : nullptr;
 
     HIP_TRY(hipMemsetAsync(dX, 0, sizeof(float) * (size_t)B * J * D, s));
 
@@ -552,7 +555,7 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
     for (int g = 1; g >= 0; --g) {
         const int dim = g == 0 ? C : D, R = g == 0 ? B * J * L1 : B * J;
         const int tokens = g == 0 ? L1 : J, groups = g == 0 ? B * J : B, per = g == 0 ? L1 : J;
-        for (int i = Lv - 1; i >= 0; --i) {
+        for (int i = DEP - 1; i >= 0; --i) {
             const std::string p = V + (g == 0 ? ".res_blocks." : ".joint_blocks.") + std::to_string(i);
             const TrainLayout::Att& a = g == 0 ? L.res[i] : L.joint[i];
             const float* mb = g == 0 ? m_res : m_joint;

@@ -15,13 +15,31 @@ class VolumetricTriangulationNet(CA_PF):
         config.model.backbone["type"] = "hrnet_32" if width == 32 else "hrnet_48"
         pf = config.model.poseformer
         # this variant's PoseTransformer builds `config.depth` blocks per group (pose_dformer.py:199, 217-227): the engine reads it
-        # from the same key (capf_config.depth; inference plans for depth != levels, the shipped configuration has 4 == 4)
+        # from the same key (capf_config.depth, 1..8, inference and, at this app's two widths, training; the shipped configuration has 4 == 4).  Training
+        # (run_3dhp.py:60-101) goes through CA_PF's native step: `out, _ = model(...)` backpropagates into volume_net.
         super().__init__(config, device, compute_dtype=compute_dtype, context_blocks=False)
 
     def forward(self, images, keypoints_2d_cpn, keypoints_2d_cpn_crop):
         x = super().forward(images, keypoints_2d_cpn, keypoints_2d_cpn_crop)       # [B, 1, 17, 3]
+        return self._layout(x), None
+
+    @staticmethod
+    def _layout(x):
         b, _, p, _ = x.shape
-        return x.view(b, 1, p, 3, 1).permute(0, 3, 1, 2, 4).contiguous(), None
+        return x.view(b, 1, p, 3, 1).permute(0, 3, 1, 2, 4).contiguous()
+
+    def forward_flip_test(self, images2, keypoints_2d_cpn2, keypoints_2d_cpn_crop2):
+        """input_augmentation (run_3dhp.py:169-180) as ONE forward of 2B frames: images2 / keypoints [2, B, ...] hold the original
+        view (the reference's img[:, 0], input_2D[:, 0], ...) followed by the already-mirrored one (img[:, 1], ...), as the data
+        loader provides them.  The mirrored prediction is un-mirrored with the 3DHP table (capf.lib.MPI_SWAP: x negated, joints_left
+        and joints_right swapped) and averaged by capf_fliptest_fuse_swap.  Returns (out [B, 3, 1, 17, 1], None) like forward; the
+        crop keypoints are normalised in place."""
+        from capf.lib import MPI_SWAP, fliptest_fuse
+        two, B = images2.shape[0], images2.shape[1]
+        assert two == 2 and images2.is_contiguous() and keypoints_2d_cpn_crop2.is_contiguous()
+        pred = CA_PF.forward(self, images2.view(2 * B, *images2.shape[2:]), keypoints_2d_cpn2.reshape(2 * B, 17, 2),
+                             keypoints_2d_cpn_crop2.view(2 * B, 17, 2))
+        return self._layout(fliptest_fuse(pred.view(2, B, 1, 17, 3), swap=MPI_SWAP)), None
 
 
 def mpi_preset(cfg, backbone):

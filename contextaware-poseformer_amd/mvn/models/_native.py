@@ -62,8 +62,10 @@ def make_capf_config(config, height=256, width=192, context_blocks=True, compute
     c.compute_dtype = 1 if compute_dtype == "bf16" else 0
     c.max_batch = MAX_BATCH
     c.height, c.width = height, width
-    # workspace also holds what capf_backward needs (6.4 MB/frame); the training path is built for depth == levels only
-    c.training = 0 if c.depth not in (0, c.levels) else 1
+    # workspace also holds what capf_backward needs (6.4 MB/frame).  depth != levels trains at the ContextPose_mpi widths only
+    # (run_3dhp.py:219-232: embed 64 over base 32, 96 over 48; csrc/plan.cpp): other widths get an inference plan there
+    mpi_width = (c.base_dim, c.embed_dim_ratio) in ((32, 64), (48, 96))
+    c.training = 1 if c.depth in (0, c.levels) or mpi_width else 0
     c.plan_flags = int(plan_flags)  # 0 = the product plan (capf.lib.PLAN_*: take a kernel family out, parity tests only)
     return c
 

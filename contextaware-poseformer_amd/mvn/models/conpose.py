@@ -194,13 +194,19 @@ class CA_PF(nn.Module):
     def _drop_masks(self, B, device):
         """DropPath multipliers for one training step (timm semantics: keep-mask / keep_prob per sample;
         a 'sample' is one batch element for context / joint blocks and one (frame, joint) row group for the
-        level blocks, whose batch axis is (b p) — pose_dformer.py:231-234).  None when nothing is dropped."""
-        levels = self._config.model.poseformer.levels
+        level blocks, whose batch axis is (b p) — pose_dformer.py:231-234).  None when nothing is dropped.
+        Layout (include/capf.h, capf_forward_train): ctx | res | joint, `levels` blocks each, rates linspace(0, rate, levels)
+        (pose_dformer.py:187); without context blocks res | joint only, `depth` blocks each, res block i and joint block i sharing
+        rate i of linspace(0, rate, depth) (ContextPose_mpi/model/pose_dformer.py:215)."""
+        pf = self._config.model.poseformer
         if not self.training or self.drop_path_rate <= 0.0:
             return None
-        rates = torch.linspace(0, self.drop_path_rate, levels).tolist()
+        if self.context_blocks:
+            rates, pers = torch.linspace(0, self.drop_path_rate, pf.levels).tolist(), (B, B * self.num_joints, B)
+        else:
+            rates, pers = torch.linspace(0, self.drop_path_rate, int(getattr(pf, "depth", pf.levels))).tolist(), (B * self.num_joints, B)
         parts = []
-        for per in (B, B * self.num_joints, B):
+        for per in pers:
             for r in rates:
                 for _ in range(2):
                     if r == 0.0:

@@ -75,8 +75,10 @@ typedef struct capf_config {
     int32_t plan_flags;        /* 0 = the product plan.  capf_plan_flag bits take one kernel family out of the plan (parity
                                   tests compare the two routes; nothing else -- no environment variable -- changes a plan) */
     int32_t depth;             /* blocks per group (res_blocks / joint_blocks).  0 = levels.  The MPI-INF-3DHP variant reads it from
-                                  config.model.poseformer.depth (ContextPose_mpi/model/pose_dformer.py:199, 217-227; 1..8); the H36M
-                                  model has depth == levels by construction, and so does the training path */
+                                  config.model.poseformer.depth (ContextPose_mpi/model/pose_dformer.py:199, 217-227; 1..8).  Inference plans
+                                  at any width; training plans at that app's widths (run_3dhp.py:219-232: embed_dim_ratio 64 over base_dim
+                                  32, 96 over 48), other widths train at depth == levels.  The H36M model (context_blocks = 1) has
+                                  depth == levels by construction */
 } capf_config;
 
 enum capf_plan_flag {
@@ -134,8 +136,10 @@ const char* capf_version(void);
  * revision 4, 104 before --, plan flags up to CAPF_PLAN_F32X3_EXACT, the capf_op_*_f32h2 entry points, capf_op_describe_sized).  The
  * version string carries the same number ("capf 0.5 (gfx950)").  Revision 7 (additive): CAPF_PLAN_BF16_F32_STREAM and capf_op_tensor slot 6
  * (an op's bf16 shadow output); struct layouts unchanged.  Revision 8 (additive): the batched JPEG decode (capf_jpeg_batch_info,
- * capf_jpeg_decode_batch, capf_jpeg_coefficients_subseq); struct layouts unchanged.                                                      */
-#define CAPF_ABI_VERSION 8
+ * capf_jpeg_decode_batch, capf_jpeg_coefficients_subseq); struct layouts unchanged.  Revision 9 (additive): training plans of the variant
+ * without context blocks at any depth 1..8 (its two widths) (its DropPath layout at capf_forward_train), capf_fliptest_fuse_swap, capf_pck_counts; struct
+ * layouts unchanged.                                                                                                                       */
+#define CAPF_ABI_VERSION 9
 int capf_abi_version(void);
 
 /* ---- parameter schema == the reference's state_dict ------------- */
@@ -178,9 +182,12 @@ int capf_backbone_forward(capf_handle* h, void* stream, const float* images_nhwc
 
 /* ---- training step of the lifter (the backbone is frozen, conpose.py:22-25) --
  * capf_forward_train: capf_forward that keeps the lifter's intermediates for capf_backward.
- *     Replaces model(images, k2d, kcrop) under model.train() (train.py:183).  drop_masks: the DropPath
- *     multipliers (0 or 1/keep_prob; timm DropPath, pose_dformer.py:71,101) laid out as
- *     ctx[i]{m1[B],m2[B]} | res[i]{m1[B*17],m2[B*17]} | joint[i]{m1[B],m2[B]}, i = 0..levels-1; NULL = no drop.
+ *     Replaces model(images, k2d, kcrop) under model.train() (train.py:183; run_3dhp.py:79 for the variant without context blocks).
+ *     drop_masks: the DropPath multipliers (0 or 1/keep_prob; timm DropPath, pose_dformer.py:71,101) laid out as
+ *       context_blocks = 1: ctx[i]{m1[B],m2[B]} | res[i]{m1[B*17],m2[B*17]} | joint[i]{m1[B],m2[B]}, i = 0..levels-1;
+ *       context_blocks = 0: res[i]{m1[B*17],m2[B*17]} | joint[i]{m1[B],m2[B]}, i = 0..depth-1 (no context segment; ContextPose_mpi
+ *                           pose_dformer.py:215: res block i and joint block i share rate i of linspace(0, drop_path_rate, depth));
+ *     NULL = no drop.
  * capf_backward: replaces loss.backward() through the lifter (train.py:195): grad_out [B,1,17,3] ->
  *     flat_grad, one fp32 buffer holding the gradient of every volume_net.* parameter in schema order
  *     (capf_grad_info), each written exactly once (no atomics) — so ONE all-reduce covers DDP's traffic.
@@ -446,6 +453,13 @@ int capf_preprocess(void* stream, const uint8_t* images_bgr, int batch, int heig
                     const float* std3, int mode, float* images_out, const float* gt_in, float* gt_out,
                     const float* k2d_in, float* k2d_out, const float* kcrop_in, float* kcrop_out);
 int capf_fliptest_fuse(void* stream, const float* pred2, int batch, float* out);
+/* capf_fliptest_fuse_swap: the same fusion for any skeleton -- ContextPose_mpi/run_3dhp.py:169-180 (input_augmentation: x of the mirrored
+ *   prediction negated, joints_left + joints_right swapped, mean of the two) where capf_fliptest_fuse hard-codes the H36M table.
+ *   pred2 [2,batch,1,joints,3] -> out [batch,1,joints,3]; swap: HOST int32[joints], swap[j] = the joint of the mirrored prediction that
+ *   lands on joint j, a permutation that is its own inverse (3DHP: 2 <-> 5, 3 <-> 6, 4 <-> 7, 8 <-> 11, 9 <-> 12, 10 <-> 13).  The table
+ *   travels in the kernel arguments (no device allocation); joints <= 32.  capf_fliptest_fuse is this entry with the H36M table (same
+ *   bits).  Anything else -- out of range, not involutive -- returns CAPF_ERR_INVALID.                                                   */
+int capf_fliptest_fuse_swap(void* stream, const float* pred2, int batch, int joints, const int32_t* swap, float* out);
 
 /* ---- N2, second half: evaluation metrics over gathered predictions (train.py:381-436) -----------------
  * capf_pose_errors: per pose i of pred / gt [n, joints, 3] (joints <= 32), err[i] = {e_MPJPE, e_P_MPJPE, e_N_MPJPE,
@@ -465,6 +479,17 @@ int capf_segment_sums(void* stream, const float* err, const int32_t* segment, co
                       double* sums, int32_t* counts);
 int capf_keypoints_loss(void* stream, int mode, const float* pred, const float* gt, const float* validity, int rows, int dim,
                         float threshold, float* loss, float* dpred);
+/* capf_pck_counts: the MPI-INF-3DHP evaluation (ContextPose_mpi/3dhp_test/test_util, MATLAB: mpii_test_predictions_py.m,
+ *   mpii_evaluate_errors.m, mpii_compute_3d_pck.m), which callers otherwise export to .mat files and run off the GPU; capf_pose_errors /
+ *   capf_segment_sums serve H36M only.  Per pose i of pred / gt [n, joints, 3] (same unit; to_mm converts it to mm): gt made relative to
+ *   joint `root` (mpii_test_predictions_py.m:46), pred's root joint taken as 0 (run_3dhp.py:118), per-joint error e = |pred - gt| x to_mm
+ *   in fp64 (:50-51).  Outputs per segment s (segment[i], int32 [n]; NULL with n_segments == 1: all poses; ids outside [0, n_segments)
+ *   are skipped): counts[s][j][31] int32 = poses with e < 5 t mm, t = 0..30 (strict <, mpii_compute_3d_pck.m:20, 30), mpjpe_sums[s][j]
+ *   fp64 = sum of e in a fixed order (the same bits on every call), frames[s] int32 = poses.  n may be 0 (zeros out; segment may then
+ *   be NULL).  PCK@150 / AUC per joint group and the MPJPE tables follow on the host from these integers
+ *   (mvn/datasets/mpi_inf_3dhp.py::evaluate).                                                                                          */
+int capf_pck_counts(void* stream, const float* pred, const float* gt, int n, int joints, int root, double to_mm, const int32_t* segment,
+                    int n_segments, int32_t* counts, double* mpjpe_sums, int32_t* frames);
 
 /* ---- N3: the per-frame affine crop in front of the prefetcher ------------------------
  * capf_affine_from_center_scale: get_affine_transform(center, scale, 0, (out_w, out_h)) of
