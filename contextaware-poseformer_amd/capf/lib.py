@@ -55,6 +55,13 @@ class OpDesc(ctypes.Structure):
                                                                          ("up_H", c_int32), ("up_W", c_int32)]
 
 
+class ConvDesc(ctypes.Structure):
+    """mirrors include/capf.h :: capf_conv_desc"""
+    _fields_ = [("x", ctypes.c_void_p), ("w_packed", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+                ("residual", ctypes.c_void_p), ("y", ctypes.c_void_p)] + \
+               [(k, ctypes.c_int32) for k in ("B", "H", "W", "Cin", "Cout", "ks", "stride", "act")]
+
+
 _lib = None
 
 
@@ -155,6 +162,14 @@ def load_library():
     lib.capf_op_pack_conv_wino.argtypes = [P, P, P, P, P, P, c_float, P, P, c_int, c_int, c_int]
     lib.capf_op_conv_wino.argtypes = [P, P, P, P, P, P] + [c_int] * 7
     lib.capf_op_linear_bf16.argtypes = [P, P, P, P, P, P] + [c_int] * 4
+    D = POINTER(ConvDesc)
+    for name in ("capf_op_conv_group", "capf_op_conv_bf16_ws_group", "capf_op_conv_f32x3_group", "capf_op_conv_f32h2_group",
+                 "capf_op_conv_f32h2g_group"):
+        getattr(lib, name).argtypes = [P, c_int, D]
+    lib.capf_op_conv_wino_group.argtypes = [P, c_int, D, c_int]
+    lib.capf_op_conv_bf16_group.argtypes = [P, c_int, D, POINTER(c_void_p), POINTER(c_int32)]
+    lib.capf_op_conv_f32h2_planes.argtypes = [P, D, P, P]
+    lib.capf_op_conv_f32h2_tiles.argtypes = [c_int, c_int, c_int, POINTER(c_int)]
     lib.capf_pose_errors.argtypes = [P, P, P, c_int, c_int, P, P]
     lib.capf_segment_sums.argtypes = [P, P, P, P, c_int, c_int, P, P]
     lib.capf_keypoints_loss.argtypes = [P, c_int, P, P, P, c_int, c_int, c_float, P, P]
@@ -464,49 +479,66 @@ def _stream(t):
     return c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
+def _call(entry, *args):
+    """lib.<entry>(*args); a non-zero status raises CapfError"""
+    rc = getattr(load_library(), entry)(*args)
+    if rc:
+        raise CapfError(f"{entry} failed ({rc})")
+
+
+def _out_hw(H, W, ks, stride):
+    """output size of a conv with padding ks // 2"""
+    pad = ks // 2
+    return (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+
+
+def _conv_out(d, x, wp, bias, residual, cout, ks=3, stride=1, act=0, bf16=False):
+    """Allocate the output [B, Ho, Wo, cout] (fp32, or bf16) of a conv of NHWC x and describe the conv in the ConvDesc d; -> output."""
+    import torch
+    B, H, W, ci = x.shape
+    y = torch.empty(B, *_out_hw(H, W, ks, stride), cout, device=x.device, dtype=torch.bfloat16 if bf16 else torch.float32)
+    d.x, d.w_packed, d.bias, d.residual, d.y = (t.data_ptr() if t is not None else None for t in (x, wp, bias, residual, y))
+    d.B, d.H, d.W, d.Cin, d.Cout, d.ks, d.stride, d.act = B, H, W, ci, cout, ks, stride, act
+    return y
+
+
+def _conv_descs(problems, bf16=False):
+    """problems: (x, wp, bias, residual, cout, ks, stride, act) each -> (ConvDesc array, outputs)"""
+    descs = (ConvDesc * len(problems))()
+    return descs, [_conv_out(d, *p, bf16=bf16) for d, p in zip(descs, problems)]
+
+
+def _pack(entry, w, bn, eps, wp_shape, wp_dtype, *dims, bias="empty"):
+    """BatchNorm-folding weight pack: allocate the packed weights and the fp32 bias [Cout] (torch.<bias>; None: no bias), run lib.<entry>."""
+    import torch
+    wp = torch.empty(wp_shape, device=w.device, dtype=wp_dtype)
+    b_out = getattr(torch, bias)(w.shape[0], device=w.device) if bias else None
+    g, b, m, v = bn if bn is not None else (None, None, None, None)
+    _call(entry, _stream(w), _p(w.contiguous()), _p(g), _p(b), _p(m), _p(v), eps, _p(wp), _p(b_out), *dims)
+    return wp, b_out
+
+
 def pack_conv(w, bn=None, eps=1e-5):
     """w [Cout,Cin,k,k] cuda fp32; bn = (gamma, beta, mean, var) or None -> (w_packed [Cout,Kpad], bias [Cout])."""
     import torch
-    lib = load_library()
     co, ci, ks, _ = w.shape
-    kpad = (ks * ks * ci + 31) // 32 * 32
-    wp = torch.empty(co, kpad, device=w.device)
-    bias = torch.empty(co, device=w.device)
-    g, b, m, v = bn if bn is not None else (None, None, None, None)
-    rc = lib.capf_op_pack_conv(_stream(w), _p(w.contiguous()), _p(g), _p(b), _p(m), _p(v), eps, _p(wp), _p(bias), co, ci, ks)
-    if rc:
-        raise CapfError(f"capf_op_pack_conv failed ({rc})")
-    return wp, bias
+    return _pack("capf_op_pack_conv", w, bn, eps, (co, (ks * ks * ci + 31) // 32 * 32), torch.float32, co, ci, ks)
 
 
 def conv_nhwc(x, wp, bias, ks, stride=1, act=0, residual=None):
     """x [B,H,W,Cin] cuda fp32 NHWC -> [B,Ho,Wo,Cout]."""
-    import torch
-    lib = load_library()
-    B, H, W, ci = x.shape
-    co = wp.shape[0]
-    pad = ks // 2
-    ho, wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
-    y = torch.empty(B, ho, wo, co, device=x.device)
-    rc = lib.capf_op_conv(_stream(x), _p(x), _p(wp), _p(bias), _p(residual), _p(y), B, H, W, ci, co, ks, stride, act)
-    if rc:
-        raise CapfError(f"capf_op_conv failed ({rc})")
+    d = ConvDesc()
+    y = _conv_out(d, x, wp, bias, residual, wp.shape[0], ks, stride, act)
+    _call("capf_op_conv", _stream(x), d.x, d.w_packed, d.bias, d.residual, d.y, d.B, d.H, d.W, d.Cin, d.Cout, ks, stride, act)
     return y
 
 
 def pack_conv_wino(w, bn=None, eps=1e-5, variant=23):
     """w [Cout,Cin,3,3] cuda fp32 -> (Winograd weights [Cout, 12*Cin] for F(2,3) / [Cout, 18*Cin] for F(4,3), bias [Cout])."""
     import torch
-    lib = load_library()
     co, ci, ks, _ = w.shape
     assert ks == 3
-    wp = torch.empty(co, (18 if variant == 43 else 12) * ci, device=w.device)
-    bias = torch.empty(co, device=w.device)
-    g, b, m, v = bn if bn is not None else (None, None, None, None)
-    rc = lib.capf_op_pack_conv_wino(_stream(w), _p(w.contiguous()), _p(g), _p(b), _p(m), _p(v), eps, _p(wp), _p(bias), co, ci, variant)
-    if rc:
-        raise CapfError(f"capf_op_pack_conv_wino failed ({rc})")
-    return wp, bias
+    return _pack("capf_op_pack_conv_wino", w, bn, eps, (co, (18 if variant == 43 else 12) * ci), torch.float32, co, ci, variant)
 
 
 def _wino_variant(wp, ci):
@@ -515,206 +547,94 @@ def _wino_variant(wp, ci):
 
 def conv_nhwc_wino(x, wp, bias, act=0, residual=None):
     """3x3 stride-1 conv through the Winograd kernel (variant from the packed pitch): x [B,H,W,Cin] cuda fp32 NHWC -> [B,H,W,Cout]."""
-    import torch
-    lib = load_library()
-    B, H, W, ci = x.shape
-    co = wp.shape[0]
-    y = torch.empty(B, H, W, co, device=x.device)
-    rc = lib.capf_op_conv_wino(_stream(x), _p(x), _p(wp), _p(bias), _p(residual), _p(y), B, H, W, ci, co, act, _wino_variant(wp, ci))
-    if rc:
-        raise CapfError(f"capf_op_conv_wino failed ({rc})")
+    d = ConvDesc()
+    y = _conv_out(d, x, wp, bias, residual, wp.shape[0], act=act)
+    _call("capf_op_conv_wino", _stream(x), d.x, d.w_packed, d.bias, d.residual, d.y, d.B, d.H, d.W, d.Cin, d.Cout, act,
+          _wino_variant(wp, d.Cin))
     return y
 
 
 def conv_nhwc_wino_group(problems):
     """problems: list of (x, wp_wino, bias, act, residual) -> outputs; ONE grouped Winograd launch."""
-    import torch
-    lib = load_library()
-    lib.capf_op_conv_wino_group.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ConvDesc), ctypes.c_int]
-    descs = (ConvDesc * len(problems))()
-    outs = []
-    for d, (x, wp, bias, act, residual) in zip(descs, problems):
-        B, H, W, ci = x.shape
-        co = wp.shape[0]
-        y = torch.empty(B, H, W, co, device=x.device)
-        outs.append(y)
-        d.x, d.w_packed, d.bias, d.y = x.data_ptr(), wp.data_ptr(), bias.data_ptr(), y.data_ptr()
-        d.residual = residual.data_ptr() if residual is not None else None
-        d.B, d.H, d.W, d.Cin, d.Cout, d.ks, d.stride, d.act = B, H, W, ci, co, 3, 1, act
-    rc = lib.capf_op_conv_wino_group(_stream(problems[0][0]), len(problems), descs, _wino_variant(problems[0][1], problems[0][0].shape[3]))
-    if rc:
-        raise CapfError(f"capf_op_conv_wino_group failed ({rc})")
+    descs, outs = _conv_descs([(x, wp, bias, res, wp.shape[0], 3, 1, act) for x, wp, bias, act, res in problems])
+    x0, wp0 = problems[0][:2]
+    _call("capf_op_conv_wino_group", _stream(x0), len(problems), descs, _wino_variant(wp0, x0.shape[3]))
     return outs
-
-
-class ConvDesc(ctypes.Structure):
-    """mirrors include/capf.h :: capf_conv_desc"""
-    _fields_ = [("x", ctypes.c_void_p), ("w_packed", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("residual", ctypes.c_void_p), ("y", ctypes.c_void_p)] + \
-               [(k, ctypes.c_int32) for k in ("B", "H", "W", "Cin", "Cout", "ks", "stride", "act")]
 
 
 def conv_nhwc_group(problems):
     """problems: list of (x, wp, bias, ks, stride, act, residual) -> list of outputs; ONE grouped launch."""
-    import torch
-    lib = load_library()
-    lib.capf_op_conv_group.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ConvDesc)]
-    lib.capf_op_conv_group.restype = ctypes.c_int
-    descs = (ConvDesc * len(problems))()
-    outs = []
-    for d, (x, wp, bias, ks, stride, act, residual) in zip(descs, problems):
-        B, H, W, ci = x.shape
-        co = wp.shape[0]
-        pad = ks // 2
-        ho, wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
-        y = torch.empty(B, ho, wo, co, device=x.device)
-        outs.append(y)
-        d.x, d.w_packed, d.bias, d.y = x.data_ptr(), wp.data_ptr(), bias.data_ptr(), y.data_ptr()
-        d.residual = residual.data_ptr() if residual is not None else None
-        d.B, d.H, d.W, d.Cin, d.Cout, d.ks, d.stride, d.act = B, H, W, ci, co, ks, stride, act
-    rc = lib.capf_op_conv_group(_stream(problems[0][0]), len(problems), descs)
-    if rc:
-        raise CapfError(f"capf_op_conv_group failed ({rc})")
+    descs, outs = _conv_descs([(x, wp, bias, res, wp.shape[0], ks, stride, act) for x, wp, bias, ks, stride, act, res in problems])
+    _call("capf_op_conv_group", _stream(problems[0][0]), len(problems), descs)
     return outs
 
 
 def pack_conv_bf16(w, bn=None, eps=1e-5):
     """-> (bf16 packed weights [Cout, Kpad64], fp32 bias [Cout])."""
     import torch
-    lib = load_library()
     co, ci, ks, _ = w.shape
-    kpad = (ks * ks * ci + 63) // 64 * 64
-    wp = torch.empty(co, kpad, device=w.device, dtype=torch.bfloat16)
-    bias = torch.empty(co, device=w.device)
-    g, b, m, v = bn if bn is not None else (None, None, None, None)
-    rc = lib.capf_op_pack_conv_bf16(_stream(w), _p(w.contiguous()), _p(g), _p(b), _p(m), _p(v), eps, _p(wp), _p(bias), co, ci, ks)
-    if rc:
-        raise CapfError(f"capf_op_pack_conv_bf16 failed ({rc})")
-    return wp, bias
+    return _pack("capf_op_pack_conv_bf16", w, bn, eps, (co, (ks * ks * ci + 63) // 64 * 64), torch.bfloat16, co, ci, ks)
 
 
 def conv_nhwc_bf16(x, wp, bias, ks, stride=1, act=0, residual=None):
     """x [B,H,W,Cin] cuda bf16 NHWC -> [B,Ho,Wo,Cout] bf16."""
-    import torch
-    lib = load_library()
-    B, H, W, ci = x.shape
-    co = wp.shape[0]
-    pad = ks // 2
-    ho, wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
-    y = torch.empty(B, ho, wo, co, device=x.device, dtype=torch.bfloat16)
-    rc = lib.capf_op_conv_bf16(_stream(x), _p(x), _p(wp), _p(bias), _p(residual), _p(y), B, H, W, ci, co, ks, stride, act)
-    if rc:
-        raise CapfError(f"capf_op_conv_bf16 failed ({rc})")
+    d = ConvDesc()
+    y = _conv_out(d, x, wp, bias, residual, wp.shape[0], ks, stride, act, bf16=True)
+    _call("capf_op_conv_bf16", _stream(x), d.x, d.w_packed, d.bias, d.residual, d.y, d.B, d.H, d.W, d.Cin, d.Cout, ks, stride, act)
     return y
 
 
 def pack_conv_bf16_rh(w, bn=None, eps=1e-5):
     """3x3 weights for the row-halo bf16 conv -> (bf16 [Cout, 9 * Cin] in (kh, Cin / cw, kw, cw) order, fp32 bias, cw)."""
     import torch
-    lib = load_library()
     co, ci, ks, _ = w.shape
-    cw = lib.capf_op_conv_bf16_rh_width(ci)
+    cw = load_library().capf_op_conv_bf16_rh_width(ci)
     if ks != 3 or not cw:
         raise CapfError(f"row-halo conv needs a 3x3 kernel and Cin % 32 == 0 (got ks={ks}, Cin={ci})")
-    wp = torch.empty(co, 9 * ci, device=w.device, dtype=torch.bfloat16)
-    bias = torch.empty(co, device=w.device)
-    g, b, m, v = bn if bn is not None else (None, None, None, None)
-    rc = lib.capf_op_pack_conv_bf16_rh(_stream(w), _p(w.contiguous()), _p(g), _p(b), _p(m), _p(v), eps, _p(wp), _p(bias), co, ci)
-    if rc:
-        raise CapfError(f"capf_op_pack_conv_bf16_rh failed ({rc})")
-    return wp, bias, cw
+    return _pack("capf_op_pack_conv_bf16_rh", w, bn, eps, (co, 9 * ci), torch.bfloat16, co, ci) + (cw,)
 
 
 def conv_nhwc_bf16_rh(x, wp, bias, act=0, residual=None):
     """x [B,H,W,Cin] cuda bf16 NHWC -> [B,H,W,Cout] bf16 (3x3, stride 1, pad 1)."""
-    import torch
-    lib = load_library()
-    B, H, W, ci = x.shape
-    co = wp.shape[0]
-    y = torch.empty(B, H, W, co, device=x.device, dtype=torch.bfloat16)
-    rc = lib.capf_op_conv_bf16_rh(_stream(x), _p(x), _p(wp), _p(bias), _p(residual), _p(y), B, H, W, ci, co, act)
-    if rc:
-        raise CapfError(f"capf_op_conv_bf16_rh failed ({rc})")
+    d = ConvDesc()
+    y = _conv_out(d, x, wp, bias, residual, wp.shape[0], act=act, bf16=True)
+    _call("capf_op_conv_bf16_rh", _stream(x), d.x, d.w_packed, d.bias, d.residual, d.y, d.B, d.H, d.W, d.Cin, d.Cout, act)
     return y
 
 
 def pack_conv_bf16_ws(w, bn=None, eps=1e-5):
     """3x3 weights for the 2-D halo bf16 conv tile (csrc/igemm_bf16_ws.hip) -> (packed bf16 [elems], fp32 bias [Cout])."""
     import torch
-    lib = load_library()
     co, ci, ks, _ = w.shape
-    n = lib.capf_op_conv_bf16_ws_pack_elems(co, ci)
+    n = load_library().capf_op_conv_bf16_ws_pack_elems(co, ci)
     if ks != 3 or n <= 0 or co % 8:
         raise CapfError(f"2-D halo conv needs a 3x3 kernel, Cin % 16 == 0 and Cout % 8 == 0 (got ks={ks}, Cin={ci}, Cout={co})")
-    wp = torch.empty(n, device=w.device, dtype=torch.bfloat16)
-    bias = torch.empty(co, device=w.device)
-    g, b, m, v = bn if bn is not None else (None, None, None, None)
-    rc = lib.capf_op_pack_conv_bf16_ws(_stream(w), _p(w.contiguous()), _p(g), _p(b), _p(m), _p(v), eps, _p(wp), _p(bias), co, ci)
-    if rc:
-        raise CapfError(f"capf_op_pack_conv_bf16_ws failed ({rc})")
-    return wp, bias
+    return _pack("capf_op_pack_conv_bf16_ws", w, bn, eps, n, torch.bfloat16, co, ci)
 
 
 def conv_nhwc_bf16_ws_group(problems):
     """problems: list of (x, wp_ws, bias, act, residual, Cout), x / residual bf16 NHWC -> list of outputs (one grouped launch of the
     2-D halo tile, 3x3 / stride 1 / pad 1)."""
-    import torch
-    lib = load_library()
-    n = len(problems)
-    descs = (ConvDesc * n)()
-    outs = []
-    for i, (x, wp, bias, act, res, co) in enumerate(problems):
-        B, H, W, ci = x.shape
-        y = torch.empty(B, H, W, co, device=x.device, dtype=torch.bfloat16)
-        outs.append(y)
-        d = descs[i]
-        d.x, d.w_packed, d.bias, d.y = x.data_ptr(), wp.data_ptr(), bias.data_ptr(), y.data_ptr()
-        d.residual = res.data_ptr() if res is not None else None
-        d.B, d.H, d.W, d.Cin, d.Cout, d.ks, d.stride, d.act = B, H, W, ci, co, 3, 1, act
-    lib.capf_op_conv_bf16_ws_group.argtypes = [c_void_p, c_int, POINTER(ConvDesc)]
-    rc = lib.capf_op_conv_bf16_ws_group(_stream(problems[0][0]), n, descs)
-    if rc:
-        raise CapfError(f"capf_op_conv_bf16_ws_group failed ({rc})")
+    descs, outs = _conv_descs([(x, wp, bias, res, co, 3, 1, act) for x, wp, bias, act, res, co in problems], bf16=True)
+    _call("capf_op_conv_bf16_ws_group", _stream(problems[0][0]), len(problems), descs)
     return outs
 
 
 def pack_conv_f32x3(w, bn=None, eps=1e-5):
     """3x3 weights for the split-fp32 conv tile (csrc/igemm_f32x3_ws.hip) -> (three bf16 pieces per weight, packed [elems]; fp32 bias [Cout])."""
     import torch
-    lib = load_library()
     co, ci, ks, _ = w.shape
-    n = lib.capf_op_conv_f32x3_pack_elems(co, ci)
+    n = load_library().capf_op_conv_f32x3_pack_elems(co, ci)
     if ks != 3 or n <= 0 or co % 4:
         raise CapfError(f"split-fp32 conv needs a 3x3 kernel, Cin % 16 == 0 and Cout % 4 == 0 (got ks={ks}, Cin={ci}, Cout={co})")
-    wp = torch.empty(n, device=w.device, dtype=torch.bfloat16)
-    bias = torch.empty(co, device=w.device)
-    g, b, m, v = bn if bn is not None else (None, None, None, None)
-    rc = lib.capf_op_pack_conv_f32x3(_stream(w), _p(w.contiguous()), _p(g), _p(b), _p(m), _p(v), eps, _p(wp), _p(bias), co, ci)
-    if rc:
-        raise CapfError(f"capf_op_pack_conv_f32x3 failed ({rc})")
-    return wp, bias
+    return _pack("capf_op_pack_conv_f32x3", w, bn, eps, n, torch.bfloat16, co, ci)
 
 
 def conv_nhwc_f32x3_group(problems):
     """problems: list of (x, wp_x3, bias, act, residual, Cout), x / residual fp32 NHWC -> list of fp32 outputs (one grouped launch of the
     split-fp32 tile, 3x3 / stride 1 / pad 1)."""
-    import torch
-    lib = load_library()
-    n = len(problems)
-    descs = (ConvDesc * n)()
-    outs = []
-    for i, (x, wp, bias, act, res, co) in enumerate(problems):
-        B, H, W, ci = x.shape
-        y = torch.empty(B, H, W, co, device=x.device, dtype=torch.float32)
-        outs.append(y)
-        d = descs[i]
-        d.x, d.w_packed, d.bias, d.y = x.data_ptr(), wp.data_ptr(), bias.data_ptr(), y.data_ptr()
-        d.residual = res.data_ptr() if res is not None else None
-        d.B, d.H, d.W, d.Cin, d.Cout, d.ks, d.stride, d.act = B, H, W, ci, co, 3, 1, act
-    lib.capf_op_conv_f32x3_group.argtypes = [c_void_p, c_int, POINTER(ConvDesc)]
-    rc = lib.capf_op_conv_f32x3_group(_stream(problems[0][0]), n, descs)
-    if rc:
-        raise CapfError(f"capf_op_conv_f32x3_group failed ({rc})")
+    descs, outs = _conv_descs([(x, wp, bias, res, co, 3, 1, act) for x, wp, bias, act, res, co in problems])
+    _call("capf_op_conv_f32x3_group", _stream(problems[0][0]), len(problems), descs)
     return outs
 
 
@@ -722,40 +642,18 @@ def pack_conv_f32h2(w, bn=None, eps=1e-5):
     """3x3 weights for the default split-fp32 conv tile (csrc/igemm_f32h2_ws.hip) -> (packed [elems] int16: two fp16 pieces per weight under
     one power-of-two scale per output channel, then the fp32 inverse scales; fp32 bias [Cout])."""
     import torch
-    lib = load_library()
     co, ci, ks, _ = w.shape
-    n = lib.capf_op_conv_f32h2_pack_elems(co, ci)
+    n = load_library().capf_op_conv_f32h2_pack_elems(co, ci)
     if ks != 3 or n <= 0 or co % 4:
         raise CapfError(f"split-fp32 conv needs a 3x3 kernel, Cin % 16 == 0 and Cout % 4 == 0 (got ks={ks}, Cin={ci}, Cout={co})")
-    wp = torch.empty(n, device=w.device, dtype=torch.int16)
-    bias = torch.empty(co, device=w.device)
-    g, b, m, v = bn if bn is not None else (None, None, None, None)
-    rc = lib.capf_op_pack_conv_f32h2(_stream(w), _p(w.contiguous()), _p(g), _p(b), _p(m), _p(v), eps, _p(wp), _p(bias), co, ci)
-    if rc:
-        raise CapfError(f"capf_op_pack_conv_f32h2 failed ({rc})")
-    return wp, bias
+    return _pack("capf_op_pack_conv_f32h2", w, bn, eps, n, torch.int16, co, ci)
 
 
 def conv_nhwc_f32h2_group(problems):
     """problems: list of (x, wp_h2, bias, act, residual, Cout), x / residual fp32 NHWC -> list of fp32 outputs (the level's launches of the
     two-fp16-piece tile, 3x3 / stride 1 / pad 1)."""
-    import torch
-    lib = load_library()
-    n = len(problems)
-    descs = (ConvDesc * n)()
-    outs = []
-    for i, (x, wp, bias, act, res, co) in enumerate(problems):
-        B, H, W, ci = x.shape
-        y = torch.empty(B, H, W, co, device=x.device, dtype=torch.float32)
-        outs.append(y)
-        d = descs[i]
-        d.x, d.w_packed, d.bias, d.y = x.data_ptr(), wp.data_ptr(), bias.data_ptr(), y.data_ptr()
-        d.residual = res.data_ptr() if res is not None else None
-        d.B, d.H, d.W, d.Cin, d.Cout, d.ks, d.stride, d.act = B, H, W, ci, co, 3, 1, act
-    lib.capf_op_conv_f32h2_group.argtypes = [c_void_p, c_int, POINTER(ConvDesc)]
-    rc = lib.capf_op_conv_f32h2_group(_stream(problems[0][0]), n, descs)
-    if rc:
-        raise CapfError(f"capf_op_conv_f32h2_group failed ({rc})")
+    descs, outs = _conv_descs([(x, wp, bias, res, co, 3, 1, act) for x, wp, bias, act, res, co in problems])
+    _call("capf_op_conv_f32h2_group", _stream(problems[0][0]), len(problems), descs)
     return outs
 
 
@@ -764,28 +662,18 @@ def conv_nhwc_f32h2_planes(x, wp, bias, act, residual, cout, exps_in=None, plane
     [tiles, Cin / 16] table of x's planes (x: the float32-typed tensor a planes_out conv returned); planes_out: y comes back as
     (float32-typed planes tensor, exps).  Use planes_to_fp32 to look at one."""
     import torch
-    lib = load_library()
-    B, H, W, ci = x.shape
-    y = torch.empty(B, H, W, cout, device=x.device, dtype=torch.float32)
     d = ConvDesc()
-    d.x, d.w_packed, d.bias, d.y = x.data_ptr(), wp.data_ptr(), bias.data_ptr(), y.data_ptr()
-    d.residual = residual.data_ptr() if residual is not None else None
-    d.B, d.H, d.W, d.Cin, d.Cout, d.ks, d.stride, d.act = B, H, W, ci, cout, 3, 1, act
-    tiles = lib.capf_op_conv_f32h2_tiles(B, H, W, None)
+    y = _conv_out(d, x, wp, bias, residual, cout, act=act)
+    tiles = load_library().capf_op_conv_f32h2_tiles(d.B, d.H, d.W, None)
     eo = torch.zeros(tiles, cout // 16, device=x.device, dtype=torch.int32) if planes_out else None
-    lib.capf_op_conv_f32h2_planes.argtypes = [c_void_p, POINTER(ConvDesc), c_void_p, c_void_p]
-    rc = lib.capf_op_conv_f32h2_planes(_stream(x), byref(d), _p(exps_in), _p(eo))
-    if rc:
-        raise CapfError(f"capf_op_conv_f32h2_planes failed ({rc})")
+    _call("capf_op_conv_f32h2_planes", _stream(x), byref(d), _p(exps_in), _p(eo))
     return (y, eo) if planes_out else y
 
 
 def f32h2_tile_pixels(B, H, W):
     """output pixels per tile of the two-fp16-piece conv tile at this geometry (flat pixel p belongs to tile p // that)"""
-    lib = load_library()
     px = c_int(0)
-    lib.capf_op_conv_f32h2_tiles.argtypes = [c_int, c_int, c_int, POINTER(c_int)]
-    if lib.capf_op_conv_f32h2_tiles(B, H, W, byref(px)) <= 0:
+    if load_library().capf_op_conv_f32h2_tiles(B, H, W, byref(px)) <= 0:
         raise CapfError("geometry not eligible for the two-fp16-piece tile")
     return px.value
 
@@ -807,135 +695,70 @@ def pack_f32h2_gemm(w, bn=None, eps=1e-5):
     nn.Linear weight [N, K] -> (packed fp32-typed buffer [elems]: [N][Kpad] of {piece 0 | piece 1} chunks + [N] inverse scales; fp32 bias
     [N] for convs, None for linears)."""
     import torch
-    lib = load_library()
     if w.dim() == 4:
         n, ci, ks, _ = w.shape
         k = ks * ks * ci
     else:
         (n, k), ci, ks = w.shape, 0, 0
-    elems = lib.capf_op_f32h2_gemm_pack_elems(n, k)
-    wp = torch.empty(elems, device=w.device, dtype=torch.float32)
-    bias = torch.zeros(n, device=w.device) if w.dim() == 4 else None
-    g, b, m, v = bn if bn is not None else (None, None, None, None)
-    rc = lib.capf_op_pack_f32h2_gemm(_stream(w), _p(w.contiguous()), _p(g), _p(b), _p(m), _p(v), eps, _p(wp), _p(bias), n, ci, ks, k)
-    if rc:
-        raise CapfError(f"capf_op_pack_f32h2_gemm failed ({rc})")
-    return wp, bias
+    elems = load_library().capf_op_f32h2_gemm_pack_elems(n, k)
+    return _pack("capf_op_pack_f32h2_gemm", w, bn, eps, elems, torch.float32, n, ci, ks, k, bias="zeros" if w.dim() == 4 else None)
 
 
 def conv_nhwc_f32h2g(x, wp, bias, ks, stride=1, act=0, residual=None, cout=None):
     """y = act(conv2d(x; two-fp16-piece pack) + bias (+ residual)), NHWC fp32, padding ks // 2, one launch of igemm_f32h2g."""
-    import torch
-    lib = load_library()
-    B, H, W, ci = x.shape
-    co = cout if cout is not None else bias.numel()
-    pad = ks // 2
-    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
-    y = torch.empty(B, Ho, Wo, co, device=x.device, dtype=torch.float32)
-    rc = lib.capf_op_conv_f32h2g(_stream(x), _p(x), _p(wp), _p(bias), _p(residual), _p(y), B, H, W, ci, co, ks, stride, act)
-    if rc:
-        raise CapfError(f"capf_op_conv_f32h2g failed ({rc})")
+    d = ConvDesc()
+    y = _conv_out(d, x, wp, bias, residual, cout if cout is not None else bias.numel(), ks, stride, act)
+    _call("capf_op_conv_f32h2g", _stream(x), d.x, d.w_packed, d.bias, d.residual, d.y, d.B, d.H, d.W, d.Cin, d.Cout, ks, stride, act)
     return y
 
 
 def conv_nhwc_f32h2g_group(problems):
     """problems: list of (x, wp, bias, ks, stride, act, residual, Cout) -> list of outputs, ONE grid of igemm_f32h2g_group_kernel."""
-    import torch
-    lib = load_library()
-    n = len(problems)
-    descs = (ConvDesc * n)()
-    outs = []
-    for i, (x, wp, bias, ks, stride, act, res, co) in enumerate(problems):
-        B, H, W, ci = x.shape
-        pad = ks // 2
-        Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
-        y = torch.empty(B, Ho, Wo, co, device=x.device, dtype=torch.float32)
-        outs.append(y)
-        d = descs[i]
-        d.x, d.w_packed, d.bias, d.y = x.data_ptr(), wp.data_ptr(), bias.data_ptr(), y.data_ptr()
-        d.residual = res.data_ptr() if res is not None else None
-        d.B, d.H, d.W, d.Cin, d.Cout, d.ks, d.stride, d.act = B, H, W, ci, co, ks, stride, act
-    lib.capf_op_conv_f32h2g_group.argtypes = [c_void_p, c_int, POINTER(ConvDesc)]
-    rc = lib.capf_op_conv_f32h2g_group(_stream(problems[0][0]), n, descs)
-    if rc:
-        raise CapfError(f"capf_op_conv_f32h2g_group failed ({rc})")
+    descs, outs = _conv_descs([(x, wp, bias, res, co, ks, stride, act) for x, wp, bias, ks, stride, act, res, co in problems])
+    _call("capf_op_conv_f32h2g_group", _stream(problems[0][0]), len(problems), descs)
     return outs
+
+
+def _rows_out(x, n, dtype=None):
+    import torch
+    return torch.empty(x.shape[0], n, device=x.device, dtype=dtype or torch.float32)
 
 
 def linear_ln_f32h2g(x, gamma, beta, eps, wp, bias, n, act=0, residual=None):
     """y[M, N] = act(LayerNorm(x[M, K]; gamma, beta, eps) @ W^T + bias (+ residual)) on the two-fp16-piece GEMM (K % 32 == 0, K <= 256, N % 4 == 0)."""
-    import torch
-    lib = load_library()
-    M, K = x.shape
-    y = torch.empty(M, n, device=x.device, dtype=torch.float32)
-    rc = lib.capf_op_linear_ln_f32h2g(_stream(x), _p(x), _p(gamma), _p(beta), float(eps), _p(wp), _p(bias), _p(residual), _p(y), M, n, K, act)
-    if rc:
-        raise CapfError(f"capf_op_linear_ln_f32h2g failed ({rc})")
+    (M, K), y = x.shape, _rows_out(x, n)
+    _call("capf_op_linear_ln_f32h2g", _stream(x), _p(x), _p(gamma), _p(beta), float(eps), _p(wp), _p(bias), _p(residual), _p(y), M, n, K, act)
     return y
 
 
 def linear_f32h2g(x, wp, bias, n, act=0, residual=None):
     """y[M, N] = act(x[M, K] @ W^T + bias (+ residual)) on the two-fp16-piece GEMM (K % 32 == 0, N % 4 == 0)."""
-    import torch
-    lib = load_library()
-    M, K = x.shape
-    y = torch.empty(M, n, device=x.device, dtype=torch.float32)
-    rc = lib.capf_op_linear_f32h2g(_stream(x), _p(x), _p(wp), _p(bias), _p(residual), _p(y), M, n, K, act)
-    if rc:
-        raise CapfError(f"capf_op_linear_f32h2g failed ({rc})")
+    (M, K), y = x.shape, _rows_out(x, n)
+    _call("capf_op_linear_f32h2g", _stream(x), _p(x), _p(wp), _p(bias), _p(residual), _p(y), M, n, K, act)
     return y
 
 
 def wgrad(dy, x, two_piece=True):
     """(dW[N, K], db[N]) = (dy[M, N]^T @ x[M, K], column sums of dy) through the training step's weight-gradient kernels."""
     import torch
-    lib = load_library()
-    M, N = dy.shape
-    K = x.shape[1]
+    (M, N), K = dy.shape, x.shape[1]
     out = torch.empty(N * K + N, device=x.device, dtype=torch.float32)
-    rc = lib.capf_op_wgrad(_stream(x), _p(dy), _p(x), M, N, K, _p(out), 1 if two_piece else 0)
-    if rc:
-        raise CapfError(f"capf_op_wgrad failed ({rc})")
+    _call("capf_op_wgrad", _stream(x), _p(dy), _p(x), M, N, K, _p(out), 1 if two_piece else 0)
     return out[:N * K].view(N, K), out[N * K:]
 
 
 def conv_nhwc_bf16_group(problems):
     """problems: list of (x, wp, bias, ks, stride, act, residual, wp_row_halo or None), all bf16 NHWC -> (outputs, variant)."""
-    import torch
-    lib = load_library()
-    n = len(problems)
-    descs = (ConvDesc * n)()
-    rh = (c_void_p * n)()
-    outs = []
-    for i, (x, wp, bias, ks, stride, act, res, wrh) in enumerate(problems):
-        B, H, W, ci = x.shape
-        co = wp.shape[0]
-        pad = ks // 2
-        ho, wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
-        y = torch.empty(B, ho, wo, co, device=x.device, dtype=torch.bfloat16)
-        outs.append(y)
-        d = descs[i]
-        d.x, d.w_packed, d.bias, d.y = x.data_ptr(), wp.data_ptr(), bias.data_ptr(), y.data_ptr()
-        d.residual = res.data_ptr() if res is not None else None
-        d.B, d.H, d.W, d.Cin, d.Cout, d.ks, d.stride, d.act = B, H, W, ci, co, ks, stride, act
-        rh[i] = wrh.data_ptr() if wrh is not None else None
+    descs, outs = _conv_descs([(x, wp, bias, res, wp.shape[0], ks, stride, act) for x, wp, bias, ks, stride, act, res, _ in problems], bf16=True)
+    rh = (c_void_p * len(problems))(*(p[7].data_ptr() if p[7] is not None else None for p in problems))
     variant = c_int32(-1)
-    lib.capf_op_conv_bf16_group.argtypes = [c_void_p, c_int, POINTER(ConvDesc), POINTER(c_void_p), POINTER(c_int32)]
-    rc = lib.capf_op_conv_bf16_group(_stream(problems[0][0]), n, descs, rh, byref(variant))
-    if rc:
-        raise CapfError(f"capf_op_conv_bf16_group failed ({rc})")
+    _call("capf_op_conv_bf16_group", _stream(problems[0][0]), len(problems), descs, rh, byref(variant))
     return outs, variant.value
 
 
 def linear(x, w, bias=None, act=0, residual=None):
-    import torch
-    lib = load_library()
-    M, K = x.shape
-    N = w.shape[0]
-    y = torch.empty(M, N, device=x.device)
-    rc = lib.capf_op_linear(_stream(x), _p(x), _p(w), _p(bias), _p(residual), _p(y), M, N, K, act)
-    if rc:
-        raise CapfError(f"capf_op_linear failed ({rc})")
+    (M, K), y = x.shape, _rows_out(x, w.shape[0])
+    _call("capf_op_linear", _stream(x), _p(x), _p(w), _p(bias), _p(residual), _p(y), M, w.shape[0], K, act)
     return y
 
 
@@ -943,27 +766,19 @@ def bilinear_corners(grid, H, W, border):
     """grid: CUDA fp32 [..., 2] normalised (x, y) -> (idx int32 [..., 2] = NW corner (x0, y0), frac fp32 [..., 2]) by the
     device function both sampling sites of capf_forward use."""
     import torch
-    lib = load_library()
     g = grid.contiguous()
-    n = g.numel() // 2
     idx = torch.empty(g.shape, dtype=torch.int32, device=g.device)
     frac = torch.empty(g.shape, dtype=torch.float32, device=g.device)
-    rc = lib.capf_op_bilinear_corners(_stream(g), _p(g), n, int(H), int(W), 1 if border else 0, _p(idx), _p(frac))
-    if rc:
-        raise CapfError(f"capf_op_bilinear_corners failed ({rc})")
+    _call("capf_op_bilinear_corners", _stream(g), _p(g), g.numel() // 2, int(H), int(W), 1 if border else 0, _p(idx), _p(frac))
     return idx, frac
 
 
 def linear_bf16(x, w, bias=None, residual=None, gelu=False):
     """x bf16 [M,K], w bf16 [N,K] -> fp32 [M,N] (+ fp32 residual), or with gelu=True -> bf16 GELU(x w^T + b)."""
     import torch
-    lib = load_library()
-    M, K = x.shape
-    N = w.shape[0]
-    y = torch.empty(M, N, device=x.device, dtype=torch.bfloat16 if gelu else torch.float32)
-    rc = lib.capf_op_linear_bf16(_stream(x), _p(x.contiguous()), _p(w.contiguous()), _p(bias), _p(residual), _p(y), M, N, K, 1 if gelu else 0)
-    if rc:
-        raise CapfError(f"capf_op_linear_bf16 failed ({rc})")
+    (M, K), N = x.shape, w.shape[0]
+    y = _rows_out(x, N, torch.bfloat16 if gelu else torch.float32)
+    _call("capf_op_linear_bf16", _stream(x), _p(x.contiguous()), _p(w.contiguous()), _p(bias), _p(residual), _p(y), M, N, K, 1 if gelu else 0)
     return y
 
 

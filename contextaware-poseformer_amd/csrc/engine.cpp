@@ -878,78 +878,108 @@ int capf_tensor(const capf_handle* h, const char* name, const void** dev_ptr, in
     return t.is_int;      // 0 fp32, 1 int32, 2 bf16
 }
 
+// ---- stand-alone operators (capf_op_*: op-level tests and micro-benchmarks) ----------------------------------------------------------
+static int hip_rc(hipError_t e, int fail = CAPF_ERR_HIP) { return e == hipSuccess ? CAPF_OK : fail; }
+
+static capf_conv_desc conv_desc(const void* x, const void* wp, const float* bias, const void* residual, void* y, int B, int H, int W,
+                                int Cin, int Cout, int ks, int stride, int act) {
+    return {static_cast<const float*>(x), static_cast<const float*>(wp), bias, static_cast<const float*>(residual), static_cast<float*>(y),
+            B, H, W, Cin, Cout, ks, stride, act};
+}
+
+// one conv as the launchers take it (padding ks / 2): the packed weights go to the family's slot, Kpad = K rounded up to kround
+static capf::GemmArgs conv_args(const capf_conv_desc& d, const float* capf::GemmArgs::*wslot, int kround) {
+    capf::GemmArgs a{};
+    const int pad = d.ks / 2;
+    a.A = d.x; a.*wslot = d.w_packed; a.bias = d.bias; a.res = d.residual; a.out = d.y;
+    a.Ho = (d.H + 2 * pad - d.ks) / d.stride + 1;
+    a.Wo = (d.W + 2 * pad - d.ks) / d.stride + 1;
+    a.M = d.B * a.Ho * a.Wo; a.N = d.Cout; a.K = d.ks * d.ks * d.Cin; a.Kpad = (a.K + kround - 1) / kround * kround;
+    a.conv = 1; a.Cin = d.Cin; a.H = d.H; a.W = d.W; a.ks = d.ks; a.stride = d.stride; a.pad = pad;
+    a.omap = capf::row_ld(d.Cout); a.rmap = capf::row_ld(d.Cout); a.amap = capf::row_ld(0);
+    a.act = d.act;
+    return a;
+}
+
+// y[M, N] = act(x[M, K] W^T + bias (+ residual)), dense rows
+static capf::GemmArgs rows_args(const float* capf::GemmArgs::*wslot, const float* x, const float* w, const float* bias, const float* residual,
+                                float* y, int M, int N, int K, int act) {
+    capf::GemmArgs a{};
+    a.A = x; a.*wslot = w; a.bias = bias; a.res = residual; a.out = y;
+    a.M = M; a.N = N; a.K = K; a.Kpad = K;
+    a.amap = capf::row_ld(K); a.omap = capf::row_ld(N); a.rmap = capf::row_ld(N);
+    a.act = act;
+    return a;
+}
+
+static bool is_3x3_s1(const capf_conv_desc& d) { return d.ks == 3 && d.stride == 1; }
+
+// the steps every *_group entry point shares: n / d validation, build(d[i], i, args) per problem (a CAPF_* status: the family's own
+// checks), one launch
+extern "C++" template <class Build, class Launch>
+static int conv_group(void* stream, int n, const capf_conv_desc* d, Build build, Launch launch) {
+    if (n <= 0 || n > capf::MAXG || !d) return CAPF_ERR_INVALID;
+    capf::GemmArgs g[capf::MAXG];
+    for (int i = 0; i < n; ++i)
+        if (const int rc = build(d[i], i, g[i])) return rc;
+    return hip_rc(launch(g, n, static_cast<hipStream_t>(stream)));
+}
+
+// the 3x3 / stride-1 tiles that take their weights in Wp3 (bf16 2-D halo, fp32 split pieces)
+static int wp3_build(const capf_conv_desc& d, capf::GemmArgs& a, bool (*ok)(const capf::GemmArgs&), int x3_h2) {
+    if (!is_3x3_s1(d)) return CAPF_ERR_UNSUPPORTED;
+    a = conv_args(d, &capf::GemmArgs::Wp3, 1);
+    a.x3_h2 = x3_h2;
+    return ok(a) ? CAPF_OK : CAPF_ERR_UNSUPPORTED;
+}
+
 int capf_op_pack_conv(void* stream, const float* w, const float* gamma, const float* beta, const float* mean,
                       const float* var, float eps, float* wp, float* bias, int Cout, int Cin, int ks) {
     const int Kpad = (ks * ks * Cin + 31) / 32 * 32;
-    return capf::launch_pack_conv(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, ks, Kpad,
-                                  static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return hip_rc(capf::launch_pack_conv(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, ks, Kpad, static_cast<hipStream_t>(stream)));
 }
 
 int capf_op_conv(void* stream, const float* x, const float* wp, const float* bias, const float* residual, float* y,
                  int B, int H, int W, int Cin, int Cout, int ks, int stride, int act) {
-    capf::GemmArgs a{};
-    const int pad = ks / 2;
-    a.A = x; a.Wp = wp; a.bias = bias; a.res = residual; a.out = y;
-    a.Ho = (H + 2 * pad - ks) / stride + 1;
-    a.Wo = (W + 2 * pad - ks) / stride + 1;
-    a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = ks * ks * Cin; a.Kpad = (a.K + 31) / 32 * 32;
-    a.conv = 1; a.Cin = Cin; a.H = H; a.W = W; a.ks = ks; a.stride = stride; a.pad = pad;
-    a.omap = capf::row_ld(Cout); a.rmap = capf::row_ld(Cout); a.amap = capf::row_ld(0);
-    a.act = act;
-    return capf::launch_gemm_f32(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    const capf::GemmArgs a = conv_args(conv_desc(x, wp, bias, residual, y, B, H, W, Cin, Cout, ks, stride, act), &capf::GemmArgs::Wp, 32);
+    return hip_rc(capf::launch_gemm_f32(a, static_cast<hipStream_t>(stream)));
+}
+
+int capf_op_conv_group(void* stream, int n, const capf_conv_desc* d) {
+    return conv_group(stream, n, d, [](const capf_conv_desc& c, int, capf::GemmArgs& a) {
+        a = conv_args(c, &capf::GemmArgs::Wp, 32);
+        return capf::gemm_f32_groupable(a) ? CAPF_OK : CAPF_ERR_UNSUPPORTED;
+    }, capf::launch_gemm_f32_group);
 }
 
 int capf_op_pack_conv_wino(void* stream, const float* w, const float* gamma, const float* beta, const float* mean,
                            const float* var, float eps, float* wp, float* bias, int Cout, int Cin, int variant) {
-    return capf::launch_pack_conv_wino(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, static_cast<hipStream_t>(stream), variant) == hipSuccess
-               ? CAPF_OK : CAPF_ERR_UNSUPPORTED;
+    return hip_rc(capf::launch_pack_conv_wino(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, static_cast<hipStream_t>(stream), variant),
+                  CAPF_ERR_UNSUPPORTED);
 }
 
-static bool wino_desc(capf::GemmArgs& a, const float* x, const float* wp, const float* bias, const float* residual, float* y, int B,
-                      int H, int W, int Cin, int Cout, int act, int variant) {
-    a = capf::GemmArgs{};
-    a.A = x; a.Wp = wp; a.bias = bias; a.res = residual; a.out = y;
-    a.Ho = H; a.Wo = W; a.M = B * H * W; a.N = Cout; a.K = 9 * Cin; a.Kpad = (variant == 43 ? 18 : 12) * Cin;
-    a.conv = 1; a.Cin = Cin; a.H = H; a.W = W; a.ks = 3; a.stride = 1; a.pad = 1;
-    a.omap = capf::row_ld(Cout); a.rmap = capf::row_ld(Cout); a.amap = capf::row_ld(0);
-    a.act = act;
-    return capf::gemm_wino_ok(a);
+// the variant rides in the packed-weight pitch: 12 Cin for F(2,3), 18 Cin for F(4,3)
+static int wino_build(const capf_conv_desc& d, capf::GemmArgs& a, int variant) {
+    if (!is_3x3_s1(d)) return CAPF_ERR_UNSUPPORTED;
+    a = conv_args(d, &capf::GemmArgs::Wp, 1);
+    a.Kpad = (variant == 43 ? 18 : 12) * d.Cin;
+    return capf::gemm_wino_ok(a) ? CAPF_OK : CAPF_ERR_UNSUPPORTED;
 }
+
+static bool wino_variant(int variant) { return variant == 23 || variant == 43; }
 
 int capf_op_conv_wino(void* stream, const float* x, const float* wp, const float* bias, const float* residual, float* y, int B,
                       int H, int W, int Cin, int Cout, int act, int variant) {
     capf::GemmArgs a;
-    if ((variant != 23 && variant != 43) || !wino_desc(a, x, wp, bias, residual, y, B, H, W, Cin, Cout, act, variant)) return CAPF_ERR_UNSUPPORTED;
-    return capf::launch_gemm_wino(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    if (!wino_variant(variant) || wino_build(conv_desc(x, wp, bias, residual, y, B, H, W, Cin, Cout, 3, 1, act), a, variant))
+        return CAPF_ERR_UNSUPPORTED;
+    return hip_rc(capf::launch_gemm_wino(a, static_cast<hipStream_t>(stream)));
 }
 
 int capf_op_conv_wino_group(void* stream, int n, const capf_conv_desc* d, int variant) {
-    if (n <= 0 || n > capf::MAXG || !d || (variant != 23 && variant != 43)) return CAPF_ERR_INVALID;
-    capf::GemmArgs g[capf::MAXG];
-    for (int i = 0; i < n; ++i)
-        if (d[i].ks != 3 || d[i].stride != 1 ||
-            !wino_desc(g[i], d[i].x, d[i].w_packed, d[i].bias, d[i].residual, d[i].y, d[i].B, d[i].H, d[i].W, d[i].Cin, d[i].Cout, d[i].act, variant))
-            return CAPF_ERR_UNSUPPORTED;
-    return capf::launch_gemm_wino_group(g, n, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
-}
-
-int capf_op_conv_group(void* stream, int n, const capf_conv_desc* d) {
-    if (n <= 0 || n > capf::MAXG || !d) return CAPF_ERR_INVALID;
-    capf::GemmArgs g[capf::MAXG];
-    for (int i = 0; i < n; ++i) {
-        capf::GemmArgs a{};
-        const int pad = d[i].ks / 2;
-        a.A = d[i].x; a.Wp = d[i].w_packed; a.bias = d[i].bias; a.res = d[i].residual; a.out = d[i].y;
-        a.Ho = (d[i].H + 2 * pad - d[i].ks) / d[i].stride + 1;
-        a.Wo = (d[i].W + 2 * pad - d[i].ks) / d[i].stride + 1;
-        a.M = d[i].B * a.Ho * a.Wo; a.N = d[i].Cout; a.K = d[i].ks * d[i].ks * d[i].Cin; a.Kpad = (a.K + 31) / 32 * 32;
-        a.conv = 1; a.Cin = d[i].Cin; a.H = d[i].H; a.W = d[i].W; a.ks = d[i].ks; a.stride = d[i].stride; a.pad = pad;
-        a.omap = capf::row_ld(d[i].Cout); a.rmap = capf::row_ld(d[i].Cout); a.amap = capf::row_ld(0);
-        a.act = d[i].act;
-        if (!capf::gemm_f32_groupable(a)) return CAPF_ERR_UNSUPPORTED;
-        g[i] = a;
-    }
-    return capf::launch_gemm_f32_group(g, n, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    if (!wino_variant(variant)) return CAPF_ERR_INVALID;
+    return conv_group(stream, n, d, [variant](const capf_conv_desc& c, int, capf::GemmArgs& a) { return wino_build(c, a, variant); },
+                      capf::launch_gemm_wino_group);
 }
 
 int64_t capf_op_f32h2_gemm_pack_elems(int N, int K) { return N > 0 && K > 0 ? capf::f32h2_gemm_pack_elems(N, (K + 31) / 32 * 32) : 0; }
@@ -957,85 +987,54 @@ int64_t capf_op_f32h2_gemm_pack_elems(int N, int K) { return N > 0 && K > 0 ? ca
 int capf_op_pack_f32h2_gemm(void* stream, const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
                             float eps, float* wp, float* bias, int N, int Cin, int ks, int K) {
     if (!w || !wp || N <= 0 || (N & 3) || K <= 0 || (ks > 0 && K != ks * ks * Cin)) return CAPF_ERR_UNSUPPORTED;
-    return capf::launch_pack_f32h2_gemm(w, gamma, beta, mean, var, eps, wp, bias, N, Cin, ks, K, (K + 31) / 32 * 32,
-                                        static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return hip_rc(capf::launch_pack_f32h2_gemm(w, gamma, beta, mean, var, eps, wp, bias, N, Cin, ks, K, (K + 31) / 32 * 32,
+                                               static_cast<hipStream_t>(stream)));
 }
 
-static capf::GemmArgs h2g_conv_args(const float* x, const float* wp, const float* bias, const float* residual, float* y, int B, int H, int W,
-                                    int Cin, int Cout, int ks, int stride, int act) {
-    capf::GemmArgs a{};
-    const int pad = ks / 2;
-    a.A = x; a.Wh2 = wp; a.bias = bias; a.res = residual; a.out = y;
-    a.Ho = (H + 2 * pad - ks) / stride + 1;
-    a.Wo = (W + 2 * pad - ks) / stride + 1;
-    a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = ks * ks * Cin; a.Kpad = (a.K + 31) / 32 * 32;
-    a.conv = 1; a.Cin = Cin; a.H = H; a.W = W; a.ks = ks; a.stride = stride; a.pad = pad;
-    a.omap = capf::row_ld(Cout); a.rmap = capf::row_ld(Cout); a.amap = capf::row_ld(0);
-    a.act = act;
-    return a;
+static int h2g_build(const capf_conv_desc& d, capf::GemmArgs& a) {
+    if (d.ks < 1 || d.stride < 1) return CAPF_ERR_INVALID;
+    a = conv_args(d, &capf::GemmArgs::Wh2, 32);
+    return capf::gemm_f32h2g_ok(a) ? CAPF_OK : CAPF_ERR_UNSUPPORTED;
 }
 
 int capf_op_conv_f32h2g(void* stream, const float* x, const float* wp, const float* bias, const float* residual, float* y,
                         int B, int H, int W, int Cin, int Cout, int ks, int stride, int act) {
-    if (ks < 1 || stride < 1) return CAPF_ERR_INVALID;
-    const capf::GemmArgs a = h2g_conv_args(x, wp, bias, residual, y, B, H, W, Cin, Cout, ks, stride, act);
-    if (!capf::gemm_f32h2g_ok(a)) return CAPF_ERR_UNSUPPORTED;
-    return capf::launch_gemm_f32h2g(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    capf::GemmArgs a;
+    if (const int rc = h2g_build(conv_desc(x, wp, bias, residual, y, B, H, W, Cin, Cout, ks, stride, act), a)) return rc;
+    return hip_rc(capf::launch_gemm_f32h2g(a, static_cast<hipStream_t>(stream)));
 }
 
 int capf_op_conv_f32h2g_group(void* stream, int n, const capf_conv_desc* d) {
-    if (n <= 0 || n > capf::MAXG || !d) return CAPF_ERR_INVALID;
-    capf::GemmArgs g[capf::MAXG];
-    for (int i = 0; i < n; ++i) {
-        if (d[i].ks < 1 || d[i].stride < 1) return CAPF_ERR_INVALID;
-        g[i] = h2g_conv_args(static_cast<const float*>(d[i].x), static_cast<const float*>(d[i].w_packed), d[i].bias,
-                             static_cast<const float*>(d[i].residual), static_cast<float*>(d[i].y), d[i].B, d[i].H, d[i].W, d[i].Cin, d[i].Cout,
-                             d[i].ks, d[i].stride, d[i].act);
-        if (!capf::gemm_f32h2g_ok(g[i])) return CAPF_ERR_UNSUPPORTED;
-    }
-    return capf::launch_gemm_f32h2g_group(g, n, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return conv_group(stream, n, d, [](const capf_conv_desc& c, int, capf::GemmArgs& a) { return h2g_build(c, a); },
+                      capf::launch_gemm_f32h2g_group);
 }
 
 int capf_op_linear_f32h2g(void* stream, const float* x, const float* wp, const float* bias, const float* residual, float* y,
                           int M, int N, int K, int act) {
     if (K % 32 != 0) return CAPF_ERR_UNSUPPORTED;
-    capf::GemmArgs a{};
-    a.A = x; a.Wh2 = wp; a.bias = bias; a.res = residual; a.out = y;
-    a.M = M; a.N = N; a.K = K; a.Kpad = K;
-    a.amap = capf::row_ld(K); a.omap = capf::row_ld(N); a.rmap = capf::row_ld(N);
-    a.act = act;
+    const capf::GemmArgs a = rows_args(&capf::GemmArgs::Wh2, x, wp, bias, residual, y, M, N, K, act);
     if (!capf::gemm_f32h2g_ok(a)) return CAPF_ERR_UNSUPPORTED;
-    return capf::launch_gemm_f32h2g(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return hip_rc(capf::launch_gemm_f32h2g(a, static_cast<hipStream_t>(stream)));
 }
 
 int capf_op_wgrad(void* stream, const float* dY, const float* X, int M, int N, int K, float* dw_db, int two_piece) {
     if (!dY || !X || !dw_db || M <= 0 || N <= 0 || K <= 0 || N % 4 || K % 4 || (two_piece && (N % 128 || K % 128))) return CAPF_ERR_UNSUPPORTED;
-    return capf::launch_wgrad_tn(dY, N, X, K, M, N, K, dw_db, (long)N * K + N, 1, 1, static_cast<hipStream_t>(stream), two_piece != 0) == hipSuccess
-               ? CAPF_OK : CAPF_ERR_HIP;
+    return hip_rc(capf::launch_wgrad_tn(dY, N, X, K, M, N, K, dw_db, (long)N * K + N, 1, 1, static_cast<hipStream_t>(stream), two_piece != 0));
 }
 
 int capf_op_linear_ln_f32h2g(void* stream, const float* x, const float* ln_gamma, const float* ln_beta, float eps, const float* wp,
                              const float* bias, const float* residual, float* y, int M, int N, int K, int act) {
     if (K % 32 != 0 || !ln_gamma || !ln_beta) return CAPF_ERR_UNSUPPORTED;
-    capf::GemmArgs a{};
-    a.A = x; a.Wh2 = wp; a.bias = bias; a.res = residual; a.out = y;
-    a.M = M; a.N = N; a.K = K; a.Kpad = K;
-    a.amap = capf::row_ld(K); a.omap = capf::row_ld(N); a.rmap = capf::row_ld(N);
-    a.act = act;
+    capf::GemmArgs a = rows_args(&capf::GemmArgs::Wh2, x, wp, bias, residual, y, M, N, K, act);
     a.ln_g = ln_gamma; a.ln_b = ln_beta; a.ln_eps = eps;
     if (!capf::gemm_f32h2g_ok(a)) return CAPF_ERR_UNSUPPORTED;
-    return capf::launch_gemm_f32h2g(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return hip_rc(capf::launch_gemm_f32h2g(a, static_cast<hipStream_t>(stream)));
 }
 
 int capf_op_linear(void* stream, const float* x, const float* w, const float* bias, const float* residual, float* y,
                    int M, int N, int K, int act) {
     if (K % 32 != 0) return CAPF_ERR_UNSUPPORTED;
-    capf::GemmArgs a{};
-    a.A = x; a.Wp = w; a.bias = bias; a.res = residual; a.out = y;
-    a.M = M; a.N = N; a.K = K; a.Kpad = K;
-    a.amap = capf::row_ld(K); a.omap = capf::row_ld(N); a.rmap = capf::row_ld(N);
-    a.act = act;
-    return capf::launch_gemm_f32(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return hip_rc(capf::launch_gemm_f32(rows_args(&capf::GemmArgs::Wp, x, w, bias, residual, y, M, N, K, act), static_cast<hipStream_t>(stream)));
 }
 
 int capf_op_bilinear_corners(void* stream, const float* grid, int n, int H, int W, int border, int32_t* idx, float* frac) {
@@ -1047,55 +1046,31 @@ int capf_op_bilinear_corners(void* stream, const float* grid, int n, int H, int 
 int capf_op_pack_conv_bf16(void* stream, const float* w, const float* gamma, const float* beta, const float* mean,
                            const float* var, float eps, void* wp, float* bias, int Cout, int Cin, int ks) {
     const int Kpad = (ks * ks * Cin + 63) / 64 * 64;
-    return capf::launch_pack_conv_bf16(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, ks, Kpad,
-                                       static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return hip_rc(capf::launch_pack_conv_bf16(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, ks, Kpad, static_cast<hipStream_t>(stream)));
 }
 
+// (the bf16 single-conv entry points report a failed launch as CAPF_ERR_UNSUPPORTED, as they always have)
 int capf_op_conv_bf16(void* stream, const void* x, const void* wp, const float* bias, const void* residual, void* y, int B,
                       int H, int W, int Cin, int Cout, int ks, int stride, int act) {
-    capf::GemmArgs a{};
-    const int pad = ks / 2;
-    a.A = static_cast<const float*>(x); a.Wp = static_cast<const float*>(wp); a.bias = bias;
-    a.res = static_cast<const float*>(residual); a.out = static_cast<float*>(y);
-    a.Ho = (H + 2 * pad - ks) / stride + 1;
-    a.Wo = (W + 2 * pad - ks) / stride + 1;
-    a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = ks * ks * Cin; a.Kpad = (a.K + 63) / 64 * 64;
-    a.conv = 1; a.Cin = Cin; a.H = H; a.W = W; a.ks = ks; a.stride = stride; a.pad = pad;
-    a.omap = capf::row_ld(Cout); a.rmap = capf::row_ld(Cout); a.amap = capf::row_ld(0);
-    a.act = act;
-    return capf::launch_gemm_bf16(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_UNSUPPORTED;
-}
-
-static capf::GemmArgs rh_args(const void* x, const void* wp, const float* bias, const void* residual, void* y, int B, int H,
-                              int W, int Cin, int Cout, int act) {
-    capf::GemmArgs a{};
-    a.A = static_cast<const float*>(x); a.Wp = static_cast<const float*>(wp); a.bias = bias;
-    a.res = static_cast<const float*>(residual); a.out = static_cast<float*>(y);
-    a.Ho = H; a.Wo = W;
-    a.M = B * H * W; a.N = Cout; a.K = 9 * Cin; a.Kpad = 9 * Cin;
-    a.conv = 1; a.Cin = Cin; a.H = H; a.W = W; a.ks = 3; a.stride = 1; a.pad = 1;
-    a.omap = capf::row_ld(Cout); a.rmap = capf::row_ld(Cout); a.amap = capf::row_ld(0);
-    a.act = act;
-    return a;
+    const capf::GemmArgs a = conv_args(conv_desc(x, wp, bias, residual, y, B, H, W, Cin, Cout, ks, stride, act), &capf::GemmArgs::Wp, 64);
+    return hip_rc(capf::launch_gemm_bf16(a, static_cast<hipStream_t>(stream)), CAPF_ERR_UNSUPPORTED);
 }
 
 int capf_op_conv_bf16_rh_width(int Cin) {
-    capf::GemmArgs a = rh_args(nullptr, nullptr, nullptr, nullptr, nullptr, 1, 8, 8, Cin, 8, 0);
-    return capf::gemm_bf16_rh_cw(a);
+    return capf::gemm_bf16_rh_cw(conv_args(conv_desc(nullptr, nullptr, nullptr, nullptr, nullptr, 1, 8, 8, Cin, 8, 3, 1, 0), &capf::GemmArgs::Wp, 1));
 }
 
 int capf_op_pack_conv_bf16_rh(void* stream, const float* w, const float* gamma, const float* beta, const float* mean,
                               const float* var, float eps, void* wp, float* bias, int Cout, int Cin) {
     const int cw = capf_op_conv_bf16_rh_width(Cin);
     if (!cw) return CAPF_ERR_UNSUPPORTED;
-    return capf::launch_pack_conv_bf16_rh(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, cw,
-                                          static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return hip_rc(capf::launch_pack_conv_bf16_rh(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, cw, static_cast<hipStream_t>(stream)));
 }
 
 int capf_op_conv_bf16_rh(void* stream, const void* x, const void* wp, const float* bias, const void* residual, void* y, int B,
                          int H, int W, int Cin, int Cout, int act) {
-    const capf::GemmArgs a = rh_args(x, wp, bias, residual, y, B, H, W, Cin, Cout, act);
-    return capf::launch_gemm_bf16_rh(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_UNSUPPORTED;
+    const capf::GemmArgs a = conv_args(conv_desc(x, wp, bias, residual, y, B, H, W, Cin, Cout, 3, 1, act), &capf::GemmArgs::Wp, 1);
+    return hip_rc(capf::launch_gemm_bf16_rh(a, static_cast<hipStream_t>(stream)), CAPF_ERR_UNSUPPORTED);
 }
 
 int64_t capf_op_conv_bf16_ws_pack_elems(int Cout, int Cin) { return Cin % 16 == 0 && Cout > 0 ? capf::bf16_ws_pack_elems(Cout, Cin) : 0; }
@@ -1103,20 +1078,12 @@ int64_t capf_op_conv_bf16_ws_pack_elems(int Cout, int Cin) { return Cin % 16 == 
 int capf_op_pack_conv_bf16_ws(void* stream, const float* w, const float* gamma, const float* beta, const float* mean,
                               const float* var, float eps, void* wp, float* bias, int Cout, int Cin) {
     if (!w || !wp || Cin % 16 != 0 || Cout % 8 != 0) return CAPF_ERR_UNSUPPORTED;
-    return capf::launch_pack_conv_bf16_ws(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, static_cast<hipStream_t>(stream)) ==
-                   hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return hip_rc(capf::launch_pack_conv_bf16_ws(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, static_cast<hipStream_t>(stream)));
 }
 
 int capf_op_conv_bf16_ws_group(void* stream, int n, const capf_conv_desc* d) {
-    if (n <= 0 || n > capf::MAXG || !d) return CAPF_ERR_INVALID;
-    capf::GemmArgs g[capf::MAXG];
-    for (int i = 0; i < n; ++i) {
-        if (d[i].ks != 3 || d[i].stride != 1) return CAPF_ERR_UNSUPPORTED;
-        g[i] = rh_args(d[i].x, nullptr, d[i].bias, d[i].residual, d[i].y, d[i].B, d[i].H, d[i].W, d[i].Cin, d[i].Cout, d[i].act);
-        g[i].Wp3 = d[i].w_packed;
-        if (!capf::gemm_bf16_ws_ok(g[i])) return CAPF_ERR_UNSUPPORTED;
-    }
-    return capf::launch_gemm_bf16_ws_group(g, n, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return conv_group(stream, n, d, [](const capf_conv_desc& c, int, capf::GemmArgs& a) { return wp3_build(c, a, capf::gemm_bf16_ws_ok, 0); },
+                      capf::launch_gemm_bf16_ws_group);
 }
 
 int64_t capf_op_conv_f32x3_pack_elems(int Cout, int Cin) { return Cin % 16 == 0 && Cout > 0 ? capf::f32x3_pack_elems(Cout, Cin) : 0; }
@@ -1124,32 +1091,12 @@ int64_t capf_op_conv_f32x3_pack_elems(int Cout, int Cin) { return Cin % 16 == 0 
 int capf_op_pack_conv_f32x3(void* stream, const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
                             float eps, void* wp, float* bias, int Cout, int Cin) {
     if (!w || !wp || Cin % 16 != 0 || Cout % 4 != 0) return CAPF_ERR_UNSUPPORTED;
-    return capf::launch_pack_conv_f32x3(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, static_cast<hipStream_t>(stream)) ==
-                   hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return hip_rc(capf::launch_pack_conv_f32x3(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, static_cast<hipStream_t>(stream)));
 }
 
 int capf_op_conv_f32x3_group(void* stream, int n, const capf_conv_desc* d) {
-    if (n <= 0 || n > capf::MAXG || !d) return CAPF_ERR_INVALID;
-    capf::GemmArgs g[capf::MAXG];
-    for (int i = 0; i < n; ++i) {
-        if (d[i].ks != 3 || d[i].stride != 1) return CAPF_ERR_UNSUPPORTED;
-        g[i] = capf::GemmArgs{};
-        g[i].A = static_cast<const float*>(d[i].x);
-        g[i].Wp3 = static_cast<const float*>(d[i].w_packed);
-        g[i].bias = d[i].bias;
-        g[i].res = static_cast<const float*>(d[i].residual);
-        g[i].out = static_cast<float*>(d[i].y);
-        g[i].M = d[i].B * d[i].H * d[i].W;
-        g[i].N = d[i].Cout; g[i].K = 9 * d[i].Cin;
-        g[i].conv = 1;
-        g[i].Cin = d[i].Cin; g[i].H = d[i].H; g[i].W = d[i].W; g[i].Ho = d[i].H; g[i].Wo = d[i].W;
-        g[i].ks = 3; g[i].stride = 1; g[i].pad = 1;
-        g[i].omap = capf::row_ld(d[i].Cout);
-        g[i].rmap = capf::row_ld(d[i].Cout);
-        g[i].act = d[i].act;
-        if (!capf::gemm_f32x3_ok(g[i])) return CAPF_ERR_UNSUPPORTED;
-    }
-    return capf::launch_gemm_f32x3_group(g, n, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return conv_group(stream, n, d, [](const capf_conv_desc& c, int, capf::GemmArgs& a) { return wp3_build(c, a, capf::gemm_f32x3_ok, 0); },
+                      capf::launch_gemm_f32x3_group);
 }
 
 int64_t capf_op_conv_f32h2_pack_elems(int Cout, int Cin) { return Cin % 16 == 0 && Cout > 0 ? capf::f32h2_pack_elems(Cout, Cin) : 0; }
@@ -1157,82 +1104,36 @@ int64_t capf_op_conv_f32h2_pack_elems(int Cout, int Cin) { return Cin % 16 == 0 
 int capf_op_pack_conv_f32h2(void* stream, const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
                             float eps, void* wp, float* bias, int Cout, int Cin) {
     if (!w || !wp || Cin % 16 != 0 || Cout % 4 != 0) return CAPF_ERR_UNSUPPORTED;
-    return capf::launch_pack_conv_f32h2(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, static_cast<hipStream_t>(stream)) ==
-                   hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return hip_rc(capf::launch_pack_conv_f32h2(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, static_cast<hipStream_t>(stream)));
 }
 
 int capf_op_conv_f32h2_group(void* stream, int n, const capf_conv_desc* d) {
-    if (n <= 0 || n > capf::MAXG || !d) return CAPF_ERR_INVALID;
-    capf::GemmArgs g[capf::MAXG];
-    for (int i = 0; i < n; ++i) {
-        if (d[i].ks != 3 || d[i].stride != 1) return CAPF_ERR_UNSUPPORTED;
-        g[i] = capf::GemmArgs{};
-        g[i].A = static_cast<const float*>(d[i].x);
-        g[i].Wp3 = static_cast<const float*>(d[i].w_packed);
-        g[i].x3_h2 = 1;
-        g[i].bias = d[i].bias;
-        g[i].res = static_cast<const float*>(d[i].residual);
-        g[i].out = static_cast<float*>(d[i].y);
-        g[i].M = d[i].B * d[i].H * d[i].W;
-        g[i].N = d[i].Cout; g[i].K = 9 * d[i].Cin;
-        g[i].conv = 1;
-        g[i].Cin = d[i].Cin; g[i].H = d[i].H; g[i].W = d[i].W; g[i].Ho = d[i].H; g[i].Wo = d[i].W;
-        g[i].ks = 3; g[i].stride = 1; g[i].pad = 1;
-        g[i].omap = capf::row_ld(d[i].Cout);
-        g[i].rmap = capf::row_ld(d[i].Cout);
-        g[i].act = d[i].act;
-        if (!capf::gemm_f32x3_ok(g[i])) return CAPF_ERR_UNSUPPORTED;
-    }
-    return capf::launch_gemm_f32h2_group(g, n, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return conv_group(stream, n, d, [](const capf_conv_desc& c, int, capf::GemmArgs& a) { return wp3_build(c, a, capf::gemm_f32x3_ok, 1); },
+                      capf::launch_gemm_f32h2_group);
 }
 
 int capf_op_conv_f32h2_tiles(int B, int H, int W, int* tile_pixels) { return capf::f32h2_tiles_m(B, H, W, tile_pixels); }
 
 int capf_op_conv_f32h2_planes(void* stream, const capf_conv_desc* d, const int32_t* exps_in, int32_t* exps_out) {
-    if (!d || d->ks != 3 || d->stride != 1 || (exps_in && exps_out)) return CAPF_ERR_UNSUPPORTED;
-    capf::GemmArgs g{};
-    g.A = static_cast<const float*>(d->x);
-    g.Wp3 = static_cast<const float*>(d->w_packed);
-    g.x3_h2 = 1;
-    g.bias = d->bias;
-    g.res = static_cast<const float*>(d->residual);
-    g.out = static_cast<float*>(d->y);
-    g.M = d->B * d->H * d->W;
-    g.N = d->Cout; g.K = 9 * d->Cin;
-    g.conv = 1;
-    g.Cin = d->Cin; g.H = d->H; g.W = d->W; g.Ho = d->H; g.Wo = d->W;
-    g.ks = 3; g.stride = 1; g.pad = 1;
-    g.omap = capf::row_ld(d->Cout);
-    g.rmap = capf::row_ld(d->Cout);
-    g.act = d->act;
-    g.h2_ein = exps_in;
-    g.h2_eout = exps_out;
+    if (!d || !is_3x3_s1(*d) || (exps_in && exps_out)) return CAPF_ERR_UNSUPPORTED;
+    capf::GemmArgs g = conv_args(*d, &capf::GemmArgs::Wp3, 1);
+    g.x3_h2 = 1; g.h2_ein = exps_in; g.h2_eout = exps_out;
     if (!capf::gemm_f32x3_ok(g)) return CAPF_ERR_UNSUPPORTED;
     const hipError_t e = capf::launch_gemm_f32h2_group(&g, 1, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CAPF_OK : (e == hipErrorInvalidValue ? CAPF_ERR_UNSUPPORTED : CAPF_ERR_HIP);
+    return hip_rc(e, e == hipErrorInvalidValue ? CAPF_ERR_UNSUPPORTED : CAPF_ERR_HIP);
 }
 
 int capf_op_conv_bf16_group(void* stream, int n, const capf_conv_desc* d, const void* const* w_rh, int32_t* variant) {
-    if (n <= 0 || n > capf::MAXG || !d) return CAPF_ERR_INVALID;
-    capf::GemmArgs g[capf::MAXG];
-    for (int i = 0; i < n; ++i) {
-        capf::GemmArgs a{};
-        const int pad = d[i].ks / 2;
-        a.A = d[i].x; a.Wp = d[i].w_packed; a.bias = d[i].bias; a.res = d[i].residual; a.out = d[i].y;
+    return conv_group(stream, n, d, [w_rh](const capf_conv_desc& c, int i, capf::GemmArgs& a) {
+        a = conv_args(c, &capf::GemmArgs::Wp, 64);
         a.Wp2 = w_rh ? static_cast<const float*>(w_rh[i]) : nullptr;
-        a.Ho = (d[i].H + 2 * pad - d[i].ks) / d[i].stride + 1;
-        a.Wo = (d[i].W + 2 * pad - d[i].ks) / d[i].stride + 1;
-        a.M = d[i].B * a.Ho * a.Wo; a.N = d[i].Cout; a.K = d[i].ks * d[i].ks * d[i].Cin; a.Kpad = (a.K + 63) / 64 * 64;
-        a.conv = 1; a.Cin = d[i].Cin; a.H = d[i].H; a.W = d[i].W; a.ks = d[i].ks; a.stride = d[i].stride; a.pad = pad;
-        a.omap = capf::row_ld(d[i].Cout); a.rmap = capf::row_ld(d[i].Cout); a.amap = capf::row_ld(0);
-        a.act = d[i].act;
-        if (!capf::gemm_bf16_groupable(a)) return CAPF_ERR_UNSUPPORTED;
-        g[i] = a;
-    }
-    int v = -1;
-    const hipError_t e = capf::launch_gemm_bf16_group(g, n, static_cast<hipStream_t>(stream), &v);
-    if (variant) *variant = v;
-    return e == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+        return capf::gemm_bf16_groupable(a) ? CAPF_OK : CAPF_ERR_UNSUPPORTED;
+    }, [variant](const capf::GemmArgs* g, int n, hipStream_t s) {
+        int v = -1;
+        const hipError_t e = capf::launch_gemm_bf16_group(g, n, s, &v);
+        if (variant) *variant = v;
+        return e;
+    });
 }
 
 int capf_op_linear_bf16(void* stream, const void* x_bf16, const void* w_bf16, const float* bias, const float* residual, void* y,

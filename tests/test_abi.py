@@ -208,12 +208,9 @@ def test_tile_choice_avoids_a_second_round_for_the_lifter_gemms():
 
 def test_conv_group_rejects_bad_arguments_without_a_gpu():
     """capf_op_conv_group validates before it launches: the error paths need no device."""
-    import ctypes
     import capf
     from capf.lib import ConvDesc
     lib = capf.load_library()
-    lib.capf_op_conv_group.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ConvDesc)]
-    lib.capf_op_conv_group.restype = ctypes.c_int
     d = (ConvDesc * 9)()
     for i in range(9):
         d[i].x = d[i].w_packed = d[i].bias = d[i].y = 4096          # never dereferenced on these paths
@@ -225,6 +222,111 @@ def test_conv_group_rejects_bad_arguments_without_a_gpu():
     assert lib.capf_op_conv_group(None, 2, d) != 0
     d[1].Cin, d[1].ks = 32, 7                                       # 49 taps do not fit the 32-bit tap mask
     assert lib.capf_op_conv_group(None, 2, d) != 0
+
+
+INVALID, UNSUPPORTED = -1, -2          # include/capf.h :: CAPF_ERR_INVALID, CAPF_ERR_UNSUPPORTED
+
+# The exact status of every error path of the stand-alone conv / linear / pack entry points that returns before a launch (recorded
+# from the library these entry points were first written in).  Each problem below is one that the family's own check rejects, so no
+# call reaches a kernel: the pointers are never dereferenced.
+_GROUP_CALLS = {
+    "capf_op_conv_group": lambda lib, n, d: lib.capf_op_conv_group(None, n, d),
+    "capf_op_conv_wino_group": lambda lib, n, d: lib.capf_op_conv_wino_group(None, n, d, 23),
+    "capf_op_conv_bf16_group": lambda lib, n, d: lib.capf_op_conv_bf16_group(None, n, d, None, None),
+    "capf_op_conv_bf16_ws_group": lambda lib, n, d: lib.capf_op_conv_bf16_ws_group(None, n, d),
+    "capf_op_conv_f32x3_group": lambda lib, n, d: lib.capf_op_conv_f32x3_group(None, n, d),
+    "capf_op_conv_f32h2_group": lambda lib, n, d: lib.capf_op_conv_f32h2_group(None, n, d),
+    "capf_op_conv_f32h2g_group": lambda lib, n, d: lib.capf_op_conv_f32h2g_group(None, n, d),
+}
+# (entry point, field of problem 1, value) -> status; problem 0 is a plain 3x3 conv
+_GROUP_BAD_PROBLEM = {
+    ("capf_op_conv_group", "Cin", 3): UNSUPPORTED,                # Cin % 4
+    ("capf_op_conv_bf16_group", "Cin", 4): UNSUPPORTED,           # Cin % 8
+    ("capf_op_conv_wino_group", "ks", 5): UNSUPPORTED,
+    ("capf_op_conv_wino_group", "stride", 2): UNSUPPORTED,
+    ("capf_op_conv_wino_group", "act", 2): UNSUPPORTED,           # GELU
+    ("capf_op_conv_bf16_ws_group", "ks", 5): UNSUPPORTED,
+    ("capf_op_conv_bf16_ws_group", "stride", 2): UNSUPPORTED,
+    ("capf_op_conv_bf16_ws_group", "act", 2): UNSUPPORTED,
+    ("capf_op_conv_f32x3_group", "ks", 5): UNSUPPORTED,
+    ("capf_op_conv_f32x3_group", "stride", 2): UNSUPPORTED,
+    ("capf_op_conv_f32x3_group", "act", 2): UNSUPPORTED,
+    ("capf_op_conv_f32h2_group", "ks", 5): UNSUPPORTED,
+    ("capf_op_conv_f32h2_group", "stride", 2): UNSUPPORTED,
+    ("capf_op_conv_f32h2_group", "act", 2): UNSUPPORTED,
+    ("capf_op_conv_f32h2g_group", "ks", 0): INVALID,
+    ("capf_op_conv_f32h2g_group", "stride", 0): INVALID,
+    ("capf_op_conv_f32h2g_group", "Cin", 3): UNSUPPORTED,         # Cin % 4
+}
+
+
+def _conv_descs(n, **problem1):
+    from capf.lib import ConvDesc
+    d = (ConvDesc * n)()
+    for c in d:
+        c.x = c.w_packed = c.bias = c.y = 4096
+        c.B, c.H, c.W, c.Cin, c.Cout, c.ks, c.stride, c.act = 1, 8, 8, 32, 32, 3, 1, 0
+    for k, v in problem1.items():
+        setattr(d[1], k, v)
+    return d
+
+
+@pytest.mark.parametrize("name", sorted(_GROUP_CALLS))
+def test_conv_group_entry_points_validate_n_and_d_without_a_gpu(name):
+    import capf
+    lib, call = capf.load_library(), _GROUP_CALLS[name]
+    assert call(lib, 0, _conv_descs(9)) == INVALID                 # empty group
+    assert call(lib, 9, _conv_descs(9)) == INVALID                 # more than MAXG = 8 problems
+    assert call(lib, 2, None) == INVALID
+
+
+@pytest.mark.parametrize("case", sorted(_GROUP_BAD_PROBLEM), ids=lambda c: f"{c[0]}-{c[1]}={c[2]}")
+def test_conv_group_entry_points_reject_a_problem_without_a_gpu(case):
+    import capf
+    name, field, value = case
+    assert _GROUP_CALLS[name](capf.load_library(), 2, _conv_descs(2, **{field: value})) == _GROUP_BAD_PROBLEM[case]
+
+
+def test_standalone_op_pre_launch_return_codes_without_a_gpu():
+    import ctypes
+    import capf
+    lib = capf.load_library()
+    F = 4096
+    assert lib.capf_op_conv_wino_group(None, 2, _conv_descs(2), 22) == INVALID                   # not a Winograd variant
+    conv_wino = lambda Cin=32, act=0, variant=23: lib.capf_op_conv_wino(None, F, F, F, None, F, 1, 8, 8, Cin, 32, act, variant)
+    assert conv_wino(variant=22) == UNSUPPORTED
+    assert conv_wino(Cin=16) == UNSUPPORTED                                                        # Cin % 32
+    assert conv_wino(act=2) == UNSUPPORTED
+    conv_h2g = lambda Cin=32, ks=3, stride=1: lib.capf_op_conv_f32h2g(None, F, F, F, None, F, 1, 8, 8, Cin, 32, ks, stride, 0)
+    assert conv_h2g(ks=0) == INVALID
+    assert conv_h2g(stride=0) == INVALID
+    assert conv_h2g(Cin=3) == UNSUPPORTED
+    planes = lambda d, ein=None, eout=None: lib.capf_op_conv_f32h2_planes(None, d, ein, eout)
+    one = lambda **kw: ctypes.byref(_conv_descs(2, **kw)[1])
+    assert planes(None) == UNSUPPORTED
+    assert planes(one(ks=5)) == UNSUPPORTED
+    assert planes(one(stride=2)) == UNSUPPORTED
+    assert planes(one(act=2)) == UNSUPPORTED
+    assert planes(one(), F, F) == UNSUPPORTED                                                      # planes in and out
+    linear = lambda K=64: lib.capf_op_linear(None, F, F, F, None, F, 16, 32, K, 0)
+    linear_h2g = lambda N=32, K=64: lib.capf_op_linear_f32h2g(None, F, F, F, None, F, 16, N, K, 0)
+    linear_ln = lambda g=F, b=F, K=64: lib.capf_op_linear_ln_f32h2g(None, F, g, b, 1e-5, F, F, None, F, 16, 32, K, 0)
+    assert linear(K=48) == UNSUPPORTED
+    assert linear_h2g(K=48) == UNSUPPORTED
+    assert linear_h2g(N=6) == UNSUPPORTED                                                          # N % 4
+    assert linear_ln(K=48) == UNSUPPORTED
+    assert linear_ln(g=None) == UNSUPPORTED
+    assert linear_ln(b=None) == UNSUPPORTED
+    assert linear_ln(K=512) == UNSUPPORTED                                                         # LayerNorm over more than 256 columns
+    assert lib.capf_op_wgrad(None, F, F, 16, 6, 32, F, 0) == UNSUPPORTED                          # N % 4
+    assert lib.capf_op_wgrad(None, F, F, 16, 64, 64, F, 1) == UNSUPPORTED                         # two pieces: N, K % 128
+    pack = lambda name, *dims: getattr(lib, name)(None, F, None, None, None, None, 1e-5, F, F, *dims)
+    assert pack("capf_op_pack_conv_bf16_rh", 32, 20) == UNSUPPORTED                                # no row-halo channel width for Cin 20
+    assert pack("capf_op_pack_conv_bf16_ws", 32, 8) == UNSUPPORTED                                 # Cin % 16
+    assert pack("capf_op_pack_conv_f32x3", 6, 32) == UNSUPPORTED                                   # Cout % 4
+    assert pack("capf_op_pack_conv_f32h2", 32, 8) == UNSUPPORTED
+    assert pack("capf_op_pack_f32h2_gemm", 6, 32, 3, 288) == UNSUPPORTED                           # N % 4
+    assert pack("capf_op_pack_f32h2_gemm", 32, 32, 3, 64) == UNSUPPORTED                           # K != ks * ks * Cin
 
 
 def test_integration_stub_struct_matches_the_header_and_the_binding():
