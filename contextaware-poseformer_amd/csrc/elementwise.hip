@@ -26,8 +26,7 @@ __device__ __forceinline__ void store4(float* base, long i4, f32x4 v) {
     reinterpret_cast<u32x2_e*>(base)[i4] = u32x2_e{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
 }
 
-// ---- BN fold + re-layout of a conv weight (eval-mode BatchNorm, pose_hrnet.py:72-75 etc.) ---------
-//   y = (conv(x) - mean) / sqrt(var + eps) * gamma + beta  ==  conv_{w*s}(x) + (beta - mean*s)
+// ---- BN fold (kernels.h bn_scale / bn_bias) + re-layout of a conv weight ---------
 template <bool BF>
 __global__ void pack_conv_kernel(const float* __restrict__ w, const float* __restrict__ gamma,
                                  const float* __restrict__ beta, const float* __restrict__ mean,
@@ -38,7 +37,7 @@ __global__ void pack_conv_kernel(const float* __restrict__ w, const float* __res
         const int n = (int)(i / Kpad), k = (int)(i - (long)n * Kpad);
         const int K = ks * ks * Cin;
         float v = 0.f;
-        const float sc = gamma ? gamma[n] / sqrtf(var[n] + eps) : 1.f;
+        const float sc = bn_scale(gamma, var, eps, n);
         if (k < K) {
             const int tap = k / Cin, ci = k - tap * Cin;
             const int kh = tap / ks, kw = tap - kh * ks;
@@ -46,7 +45,7 @@ __global__ void pack_conv_kernel(const float* __restrict__ w, const float* __res
         }
         if (BF) reinterpret_cast<unsigned short*>(Wp)[i] = f2bf_e(v);
         else Wp[i] = v;
-        if (k == 0 && bias) bias[n] = gamma ? beta[n] - mean[n] * sc : 0.f;
+        if (k == 0 && bias) bias[n] = bn_bias(gamma, beta, mean, sc, n);
     }
 }
 
@@ -54,8 +53,7 @@ hipError_t launch_pack_conv(const float* w, const float* gamma, const float* bet
                             const float* var, float eps, float* Wp, float* bias, int Cout, int Cin,
                             int ks, int Kpad, hipStream_t s) {
     const long total = (long)Cout * Kpad;
-    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(pack_conv_kernel<false>, dim3(blocks), dim3(256), 0, s, w, gamma, beta, mean, var, eps, Wp,
+    hipLaunchKernelGGL(pack_conv_kernel<false>, dim3(grid_1d(total, 2048)), dim3(256), 0, s, w, gamma, beta, mean, var, eps, Wp,
                        bias, Cout, Cin, ks, Kpad);
     return hipGetLastError();
 }
@@ -65,8 +63,7 @@ hipError_t launch_pack_conv_bf16(const float* w, const float* gamma, const float
                                  const float* var, float eps, void* Wp_bf16, float* bias, int Cout, int Cin, int ks,
                                  int Kpad, hipStream_t s) {
     const long total = (long)Cout * Kpad;
-    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(pack_conv_kernel<true>, dim3(blocks), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
+    hipLaunchKernelGGL(pack_conv_kernel<true>, dim3(grid_1d(total, 2048)), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
                        reinterpret_cast<float*>(Wp_bf16), bias, Cout, Cin, ks, Kpad);
     return hipGetLastError();
 }

@@ -1416,9 +1416,9 @@ __global__ void pack_conv_bf16_rh_kernel(const float* __restrict__ w, const floa
         const int c = k % CW; k /= CW;
         const int kw = k % 3; k /= 3;
         const int cc = k % ncc, kh = k / ncc;
-        const float sc = gamma ? gamma[n] / sqrtf(var[n] + eps) : 1.f;
+        const float sc = bn_scale(gamma, var, eps, n);
         Wp[i] = f2bf(w[(((long)n * Cin + cc * CW + c) * 3 + kh) * 3 + kw] * sc);
-        if (first && bias) bias[n] = gamma ? beta[n] - mean[n] * sc : 0.f;
+        if (first && bias) bias[n] = bn_bias(gamma, beta, mean, sc, n);
     }
 }
 
@@ -1426,20 +1426,19 @@ hipError_t launch_pack_conv_bf16_rh(const float* w, const float* gamma, const fl
                                     float eps, void* Wp_bf16, float* bias, int Cout, int Cin, int CW, hipStream_t s) {
     if ((CW != 64 && CW != 48 && CW != 32) || Cin % CW != 0) return hipErrorInvalidValue;
     const long total = (long)Cout * 9 * Cin;
-    const long want = (total + 255) / 256;
-    hipLaunchKernelGGL(pack_conv_bf16_rh_kernel, dim3((int)(want < 4096 ? want : 4096)), dim3(256), 0, s, w, gamma, beta, mean, var,
+    hipLaunchKernelGGL(pack_conv_bf16_rh_kernel, dim3(grid_1d(total)), dim3(256), 0, s, w, gamma, beta, mean, var,
                        eps, static_cast<unsigned short*>(Wp_bf16), bias, Cout, Cin, CW);
     return hipGetLastError();
 }
 
-// Grouped launch (see igemm_f32.hip "Grouped launch"): up to MAXG independent bf16 convs in one grid.
+// Grouped launch (see kernels.h "Grouped launch"): up to MAXG independent bf16 convs in one grid.
 struct GroupArgsB {
     GemmArgs g[MAXG];
-    int start[MAXG + 1];
-    int tiles[MAXG];
+    GroupLayout lay;
     int cfg[MAXG];         // 0: 128x64 (S=2), 1: 64x64 (S=3), 2: 128x32 (S=2)
     int n;
 };
+static_assert(sizeof(GroupArgsB) == MAXG * sizeof(GemmArgs) + (3 * MAXG + 2) * sizeof(int), "kernel argument layout");
 #ifndef CAPF_BF16_GROUP_STAGES
 #define CAPF_BF16_GROUP_STAGES 2
 #endif
@@ -1450,18 +1449,13 @@ struct GroupArgsB {
 __global__ __launch_bounds__(256) void igemm_bf16_group_kernel(GroupArgsB ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) unsigned short lds[GROUP_LDS_HALVES];
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);
-    if (bid >= ga.tiles[pi]) return;
-    const GemmArgs& p = ga.g[pi];
-    switch (ga.cfg[pi]) {
-        case 0: igemm_bf16_tile<128, 64, 64, 32, CAPF_BF16_GROUP_STAGES>(p, bid, lds); break;
-        case 1: igemm_bf16_tile<64, 64, 32, 32, CAPF_BF16_GROUP_STAGES + 1>(p, bid, lds); break;
-        default: igemm_bf16_tile<128, 32, 32, 32, CAPF_BF16_GROUP_STAGES>(p, bid, lds); break;
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    const GemmArgs& p = ga.g[t.pi];
+    switch (ga.cfg[t.pi]) {
+        case 0: igemm_bf16_tile<128, 64, 64, 32, CAPF_BF16_GROUP_STAGES>(p, t.bid, lds); break;
+        case 1: igemm_bf16_tile<64, 64, 32, 32, CAPF_BF16_GROUP_STAGES + 1>(p, t.bid, lds); break;
+        default: igemm_bf16_tile<128, 32, 32, 32, CAPF_BF16_GROUP_STAGES>(p, t.bid, lds); break;
     }
 #endif
 }
@@ -1470,18 +1464,13 @@ __global__ __launch_bounds__(256) void igemm_bf16_group_kernel(GroupArgsB ga) {
 __global__ __launch_bounds__(256) void igemm_bf16_group_stream_kernel(GroupArgsB ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) unsigned short lds[GROUP_LDS_HALVES];
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);
-    if (bid >= ga.tiles[pi]) return;
-    const GemmArgs& p = ga.g[pi];
-    switch (ga.cfg[pi]) {
-        case 0: igemm_bf16_tile<128, 64, 64, 32, CAPF_BF16_GROUP_STAGES, false, false, false, true>(p, bid, lds); break;
-        case 1: igemm_bf16_tile<64, 64, 32, 32, CAPF_BF16_GROUP_STAGES + 1, false, false, false, true>(p, bid, lds); break;
-        default: igemm_bf16_tile<128, 32, 32, 32, CAPF_BF16_GROUP_STAGES, false, false, false, true>(p, bid, lds); break;
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    const GemmArgs& p = ga.g[t.pi];
+    switch (ga.cfg[t.pi]) {
+        case 0: igemm_bf16_tile<128, 64, 64, 32, CAPF_BF16_GROUP_STAGES, false, false, false, true>(p, t.bid, lds); break;
+        case 1: igemm_bf16_tile<64, 64, 32, 32, CAPF_BF16_GROUP_STAGES + 1, false, false, false, true>(p, t.bid, lds); break;
+        default: igemm_bf16_tile<128, 32, 32, 32, CAPF_BF16_GROUP_STAGES, false, false, false, true>(p, t.bid, lds); break;
     }
 #endif
 }
@@ -1490,18 +1479,13 @@ __global__ __launch_bounds__(256) void igemm_bf16_group_stream_kernel(GroupArgsB
 __global__ __launch_bounds__(256, 5) void igemm_bf16_group_pp_kernel(GroupArgsB ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) unsigned short lds[(128 + 64) * BKH];
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);
-    if (bid >= ga.tiles[pi]) return;
-    const GemmArgs& p = ga.g[pi];
-    switch (ga.cfg[pi]) {
-        case 0: igemm_bf16_tile<128, 64, 64, 32, 1>(p, bid, lds); break;
-        case 1: igemm_bf16_tile<64, 64, 32, 32, 1>(p, bid, lds); break;
-        default: igemm_bf16_tile<128, 32, 32, 32, 1>(p, bid, lds); break;
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    const GemmArgs& p = ga.g[t.pi];
+    switch (ga.cfg[t.pi]) {
+        case 0: igemm_bf16_tile<128, 64, 64, 32, 1>(p, t.bid, lds); break;
+        case 1: igemm_bf16_tile<64, 64, 32, 32, 1>(p, t.bid, lds); break;
+        default: igemm_bf16_tile<128, 32, 32, 32, 1>(p, t.bid, lds); break;
     }
 #endif
 }
@@ -1510,18 +1494,13 @@ __global__ __launch_bounds__(256, 5) void igemm_bf16_group_pp_kernel(GroupArgsB 
 __global__ __launch_bounds__(256, 4) void igemm_bf16_group_pp_stream_kernel(GroupArgsB ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) unsigned short lds[(128 + 64) * BKH];
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);
-    if (bid >= ga.tiles[pi]) return;
-    const GemmArgs& p = ga.g[pi];
-    switch (ga.cfg[pi]) {
-        case 0: igemm_bf16_tile<128, 64, 64, 32, 1, false, false, false, true>(p, bid, lds); break;
-        case 1: igemm_bf16_tile<64, 64, 32, 32, 1, false, false, false, true>(p, bid, lds); break;
-        default: igemm_bf16_tile<128, 32, 32, 32, 1, false, false, false, true>(p, bid, lds); break;
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    const GemmArgs& p = ga.g[t.pi];
+    switch (ga.cfg[t.pi]) {
+        case 0: igemm_bf16_tile<128, 64, 64, 32, 1, false, false, false, true>(p, t.bid, lds); break;
+        case 1: igemm_bf16_tile<64, 64, 32, 32, 1, false, false, false, true>(p, t.bid, lds); break;
+        default: igemm_bf16_tile<128, 32, 32, 32, 1, false, false, false, true>(p, t.bid, lds); break;
     }
 #endif
 }
@@ -1532,15 +1511,11 @@ __global__ __launch_bounds__(256, 4) void igemm_bf16_group_rh_kernel(GroupArgsB 
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) unsigned short lds_dyn[];
     unsigned short* lds = lds_dyn;
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);
-    if (bid >= ga.tiles[pi]) return;
-    const GemmArgs& p = ga.g[pi];
-    switch (ga.cfg[pi]) {
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    const GemmArgs& p = ga.g[t.pi];
+    const int bid = t.bid;
+    switch (ga.cfg[t.pi]) {
         case 0: igemm_bf16_tile<128, 64, 64, 32, 1>(p, bid, lds); break;
         case 1: igemm_bf16_tile<64, 64, 32, 32, 1>(p, bid, lds); break;
         case 2: igemm_bf16_tile<128, 32, 32, 32, 1>(p, bid, lds); break;
@@ -1654,50 +1629,44 @@ hipError_t launch_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t s, in
         total += (double)list[i].M * list[i].N * (list[i].Kpad / BKH) / 4096.0;
     }
     const double per_cu = total / 256.0;
-    struct Item { int idx, cfg, tiles; double cost; };
-    Item it[MAXG];
+    int cfgs[MAXG], tiles[MAXG], order[MAXG];
+    double cost[MAXG];
     for (int i = 0; i < n; ++i) {
         const GemmArgs& a = list[i];
         const int chunks = a.Kpad / BKH;
         int cfg;
         if (a.N <= 32) cfg = 2;
         else cfg = (chunks * 2.0 * 3.0 <= 0.8 * per_cu && a.M >= 128) ? 0 : 1;
-        it[i] = Item{i, cfg, ((a.M + BMs[cfg] - 1) / BMs[cfg]) * ((a.N + BNs[cfg] - 1) / BNs[cfg]),
-                     chunks * (BMs[cfg] * BNs[cfg] / 4096.0)};
+        cfgs[i] = cfg;
+        tiles[i] = ((a.M + BMs[cfg] - 1) / BMs[cfg]) * ((a.N + BNs[cfg] - 1) / BNs[cfg]);
+        cost[i] = chunks * (BMs[cfg] * BNs[cfg] / 4096.0);
     }
     // ping-pong launches (>= pp_min_tiles tiles at the tile sizes above): 3x3 stride-1 problems that carry the row-halo
     // weight layout move to that tile (126 x 64 outputs)
     int tiles_small = 0, nrh = 0, lds_halves = (128 + 64) * BKH;
-    for (int i = 0; i < n; ++i) tiles_small += (it[i].tiles + 7) & ~7;
+    for (int i = 0; i < n; ++i) tiles_small += (tiles[i] + 7) & ~7;
     if (tiles_small >= pp_min_tiles())
         for (int i = 0; i < n; ++i) {
-            const GemmArgs& a = list[it[i].idx];
+            const GemmArgs& a = list[i];
             const int cw = a.Wp2 && !stream ? gemm_bf16_rh_cw(a) : 0;
             if (!cw) continue;
             const int tn = rh_tn(a.N, cw);
-            it[i].cfg = cw == 64 ? (tn == 2 ? 3 : 4) : (cw == 48 ? (tn == 2 ? 5 : (tn == 3 ? 6 : 7)) : (tn == 2 ? 8 : 9));
-            it[i].tiles = ((a.M + 125) / 126) * ((a.N + 32 * tn - 1) / (32 * tn));
-            it[i].cost = (9.0 * a.Cin / BKH) * tn;
+            cfgs[i] = cw == 64 ? (tn == 2 ? 3 : 4) : (cw == 48 ? (tn == 2 ? 5 : (tn == 3 ? 6 : 7)) : (tn == 2 ? 8 : 9));
+            tiles[i] = ((a.M + 125) / 126) * ((a.N + 32 * tn - 1) / (32 * tn));
+            cost[i] = (9.0 * a.Cin / BKH) * tn;
             if (rh_lds_halves(cw, 1, tn) > lds_halves) lds_halves = rh_lds_halves(cw, 1, tn);
             ++nrh;
         }
-    for (int i = 1; i < n; ++i)
-        for (int j = i; j > 0 && it[j].cost > it[j - 1].cost; --j) { Item t = it[j]; it[j] = it[j - 1]; it[j - 1] = t; }
-    GroupArgsB ga;
+    GroupArgsB ga{};
     ga.n = n;
-    int start = 0;
+    const int start = group_layout(ga.lay, n, tiles, cost, order);
     for (int i = 0; i < n; ++i) {
-        GemmArgs a = list[it[i].idx];
+        GemmArgs a = list[order[i]];
         prep_conv_b(a);
-        if (it[i].cfg >= 3) { a.Wp = a.Wp2; a.Kpad = 9 * a.Cin; }       // (row-halo tile)
+        if (cfgs[order[i]] >= 3) { a.Wp = a.Wp2; a.Kpad = 9 * a.Cin; }       // (row-halo tile)
         ga.g[i] = a;
-        ga.cfg[i] = it[i].cfg;
-        ga.tiles[i] = it[i].tiles;
-        ga.start[i] = start;
-        start += (it[i].tiles + 7) & ~7;
+        ga.cfg[i] = cfgs[order[i]];
     }
-    ga.start[n] = start;
-    for (int i = n; i < MAXG; ++i) { ga.start[i + 1] = start; ga.tiles[i] = 0; ga.cfg[i] = 0; }
     if (variant) *variant = nrh ? 2 : (start >= pp_min_tiles() ? 1 : 0);
     if (nrh) hipLaunchKernelGGL(igemm_bf16_group_rh_kernel, dim3(start), dim3(256), (size_t)lds_halves * 2, s, ga);
     else if (start >= pp_min_tiles()) hipLaunchKernelGGL(stream ? igemm_bf16_group_pp_stream_kernel : igemm_bf16_group_pp_kernel, dim3(start), dim3(256), 0, s, ga);

@@ -17,12 +17,7 @@ long bf16_ws_pack_elems(int Cout, int Cin) {
 
 // GemmArgs -> tile geometry; false = not a problem this tile takes
 static bool ws_from_args(const GemmArgs& a, WsProblem* p) {
-    if (!a.conv || a.ks != 3 || a.stride != 1 || a.pad != 1 || a.Ho != a.H || a.Wo != a.W || a.act == ACT_GELU || a.rscale ||
-        a.omap.G != 1 || (a.res && a.rmap.G != 1) || a.M <= 0 || a.H <= 0 || a.W <= 0 || a.M % (a.H * a.W) != 0)
-        return false;
-    if ((a.omap.S1 & 7) || (a.omap.off & 7) || (a.res && ((a.rmap.S1 & 7) || (a.rmap.off & 7)))) return false;     // 16-byte pieces
-    const double es = a.f32s ? 4.0 : 2.0;                                                                  // (fp32 stream: fp32 residual / result)
-    if ((double)a.M * (double)a.omap.S1 * es >= 2.0e9 || (a.res && (double)a.M * (double)a.rmap.S1 * es >= 2.0e9)) return false;
+    if (!ws_args_ok(a, 7, a.f32s ? 4.0 : 2.0, a.M)) return false;      // (bf16 rows; fp32 stream: fp32 residual / result.  out_bf16 is not looked at)
     if (!ws_plan(a.M / (a.H * a.W), a.H, a.W, a.Cin, a.N, p)) return false;
     p->x = reinterpret_cast<const unsigned short*>(a.A);
     p->wp = reinterpret_cast<const unsigned short*>(a.Wp3);
@@ -70,37 +65,32 @@ bool gemm_bf16_ws_wanted(const GemmArgs& a) {
     return a.Wp3 && a.Ho > 0 && a.Wo > 0 && (long)a.M >= min_batch * a.Ho * a.Wo && 2.0 * (double)a.M * a.N * 9.0 * a.Cin >= min_flop && gemm_bf16_ws_ok(a);
 }
 
-// Problems are laid out one after the other, longest K loop first, each padded to a multiple of 8 blocks so that block b of a
-// problem runs on XCD b % 8 and walks that XCD's contiguous eighth of the tiles (neighbouring tiles share halo rows and, for
-// several channel slices, the pixel tile in L2).  Measured and rejected: dealing the grid out in rounds, every problem in
-// proportion to its size, so that memory-bound (48-channel) and matrix-bound (384-channel) tiles are co-resident throughout:
-// HRNet-48 level at batch 256 224 -> 247 us, cfg2 14.39k -> 13.9k frames/s.
-// Also measured and rejected: two streams -- the matrix-bound problems longest first, the memory-bound 48-channel one dealt evenly
-// between them so that a CU's two slots hold one tile of each kind: 226 -> 228 us.  The tiles are bound by their own serial issue /
-// wait chains (SQ_WAIT_INST_ANY 35-40 %, SQ_WAIT_ANY 30-36 % of the wave-cycles with two waves per SIMD), not by a shared roof.
+// The grid: kernels.h "Grouped launch" (what was measured against it on this kernel stands there).
 struct WsGroupArgs {
     WsProblem g[MAXG];
-    int start[MAXG + 1];
-    int tiles[MAXG];
+    GroupLayout lay;
     int n;
 };
+static_assert(sizeof(WsGroupArgs) == MAXG * sizeof(WsProblem) + (2 * MAXG + 2) * sizeof(int), "kernel argument layout");
+
+template <bool F32S>
+__device__ __forceinline__ void ws_group_body(const WsGroupArgs& ga, unsigned char* ws_lds) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    const WsProblem& p = ga.g[t.pi];
+    switch (p.NS) {
+        case 96: igemm_bf16_ws_tile<3, F32S>(p, t.bid, ws_lds); break;
+        case 64: igemm_bf16_ws_tile<2, F32S>(p, t.bid, ws_lds); break;
+        default: igemm_bf16_ws_tile<1, F32S>(p, t.bid, ws_lds); break;
+    }
+#endif
+}
 
 __global__ __launch_bounds__(256, 2) void igemm_bf16_group_ws_kernel(WsGroupArgs ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) unsigned char ws_lds[];
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);
-    if (bid >= ga.tiles[pi]) return;
-    const WsProblem& p = ga.g[pi];
-    switch (p.NS) {
-        case 96: igemm_bf16_ws_tile<3>(p, bid, ws_lds); break;
-        case 64: igemm_bf16_ws_tile<2>(p, bid, ws_lds); break;
-        default: igemm_bf16_ws_tile<1>(p, bid, ws_lds); break;
-    }
+    ws_group_body<false>(ga, ws_lds);
 #endif
 }
 
@@ -108,47 +98,27 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_group_ws_kernel(WsGroupArgs
 __global__ __launch_bounds__(256, 2) void igemm_bf16_group_ws_stream_kernel(WsGroupArgs ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) unsigned char ws_lds[];
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);
-    if (bid >= ga.tiles[pi]) return;
-    const WsProblem& p = ga.g[pi];
-    switch (p.NS) {
-        case 96: igemm_bf16_ws_tile<3, true>(p, bid, ws_lds); break;
-        case 64: igemm_bf16_ws_tile<2, true>(p, bid, ws_lds); break;
-        default: igemm_bf16_ws_tile<1, true>(p, bid, ws_lds); break;
-    }
+    ws_group_body<true>(ga, ws_lds);
 #endif
 }
 
 hipError_t launch_gemm_bf16_ws_group(const GemmArgs* list, int n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n > MAXG) return hipErrorInvalidValue;
-    struct Item { WsProblem p; double cost; };
-    Item it[MAXG];
-    int max_ns = 32;
+    WsProblem p[MAXG];
+    int tiles[MAXG], order[MAXG], max_ns = 32;
+    double cost[MAXG];
     const bool stream = list[0].f32s != 0;
     for (int i = 0; i < n; ++i) {
-        if (!list[i].Wp3 || !ws_from_args(list[i], &it[i].p) || (list[i].f32s != 0) != stream) return hipErrorInvalidValue;
-        it[i].cost = (double)(it[i].p.C / 16) * it[i].p.NS;      // a tile's K loop: longest first, so that the launch does not end on them
-        if (it[i].p.NS > max_ns) max_ns = it[i].p.NS;
+        if (!list[i].Wp3 || !ws_from_args(list[i], &p[i]) || (list[i].f32s != 0) != stream) return hipErrorInvalidValue;
+        tiles[i] = p[i].tiles_m * p[i].NSL;
+        cost[i] = (double)(p[i].C / 16) * p[i].NS;               // a tile's K loop
+        if (p[i].NS > max_ns) max_ns = p[i].NS;
     }
-    for (int i = 1; i < n; ++i)
-        for (int j = i; j > 0 && it[j].cost > it[j - 1].cost; --j) { Item t = it[j]; it[j] = it[j - 1]; it[j - 1] = t; }
-    WsGroupArgs ga;
+    WsGroupArgs ga{};
     ga.n = n;
-    int start = 0;
-    for (int i = 0; i < n; ++i) {
-        ga.g[i] = it[i].p;
-        ga.tiles[i] = it[i].p.tiles_m * it[i].p.NSL;
-        ga.start[i] = start;
-        start += (ga.tiles[i] + 7) & ~7;
-    }
-    ga.start[n] = start;
-    for (int i = n; i < MAXG; ++i) { ga.start[i + 1] = start; ga.tiles[i] = 0; ga.g[i] = ga.g[0]; }
+    const int start = group_layout(ga.lay, n, tiles, cost, order);
+    for (int i = 0; i < n; ++i) ga.g[i] = p[order[i]];
     const size_t lds_bytes = 2 * (size_t)ws_stage_bytes(max_ns);
     static DynLdsAttr attr_once, attr_stream;
     if (stream) {
@@ -174,29 +144,15 @@ const char* gemm_bf16_ws_kernel_name(const GemmArgs& a) {
     return ns == 96 ? "igemm_bf16_ws<w4,256x96,conv>" : (ns == 64 ? "igemm_bf16_ws<w4,256x64,conv>" : "igemm_bf16_ws<w4,256x32,conv>");
 }
 
-// BN fold + re-layout for the tile: Wp[slice][Cin / 16][tap][n][quad position][8] = bf16(w[slice * NS + n][cc * 16 + 8 h + e][kh][kw] *
-// gamma / sqrt(var + eps)), h = quad position ^ ((n >> 3) & 1) (the LDS image's bank swizzle, so that the DMA is a linear copy),
-// rows beyond Cout zero; bias as launch_pack_conv
+// BN fold + re-layout for the tile: Wp[slice][Cin / 16][tap][n][quad position][8] (ws_pack_decode) = bf16 of the folded fp32 weight
+// (bn_fold_w3x3: rows beyond Cout zero; bias as launch_pack_conv)
 __global__ void pack_conv_bf16_ws_kernel(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ beta,
                                          const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                          unsigned short* __restrict__ Wp, float* __restrict__ bias, int Cout, int Cin, int NS, long total) {
     const int ncc = Cin / 16;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        long k = i;
-        const int e = (int)(k & 7); k >>= 3;
-        const int qp = (int)(k & 1); k >>= 1;
-        const int n = (int)(k % NS); k /= NS;
-        const int tap = (int)(k % 9); k /= 9;
-        const int cc = (int)(k % ncc);
-        const int sl = (int)(k / ncc);
-        const int ng = sl * NS + n, c = cc * 16 + (qp ^ ((n >> 3) & 1)) * 8 + e;
-        float v = 0.f;
-        if (ng < Cout) {
-            const float sc = gamma ? gamma[ng] / sqrtf(var[ng] + eps) : 1.f;
-            v = w[(((long)ng * Cin + c) * 3 + tap / 3) * 3 + tap % 3] * sc;
-            if (bias && cc == 0 && tap == 0 && qp == 0 && e == 0) bias[ng] = gamma ? beta[ng] - mean[ng] * sc : 0.f;
-        }
-        Wp[i] = to_bf16(v);
+        const WsPackIdx d = ws_pack_decode(i, NS, ncc);
+        Wp[i] = to_bf16(bn_fold_w3x3(w, gamma, beta, mean, var, eps, bias, Cout, Cin, d.ng, d.c, d.tap, d.first));
     }
 }
 
@@ -204,8 +160,7 @@ hipError_t launch_pack_conv_bf16_ws(const float* w, const float* gamma, const fl
                                     float eps, void* Wp_bf16, float* bias, int Cout, int Cin, hipStream_t s) {
     if (Cin % 16 != 0 || Cout <= 0) return hipErrorInvalidValue;
     const long total = bf16_ws_pack_elems(Cout, Cin);
-    const long want = (total + 255) / 256;
-    hipLaunchKernelGGL(pack_conv_bf16_ws_kernel, dim3((int)(want < 4096 ? want : 4096)), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
+    hipLaunchKernelGGL(pack_conv_bf16_ws_kernel, dim3(grid_1d(total)), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
                        static_cast<unsigned short*>(Wp_bf16), bias, Cout, Cin, ws_ns(Cout), total);
     return hipGetLastError();
 }

@@ -106,6 +106,28 @@ inline bool ws_plan(int B, int H, int W, int C, int N, WsProblem* p, bool tile_r
     return true;
 }
 
+// The packed weight layout of the three 2-D halo tiles: [slice][Cin / 16][(piece)][tap][n][quad position][8], where the quad position
+// holds the channels cc * 16 + 8 h + e with h = quad position ^ ((n >> 3) & 1) -- the LDS image's bank swizzle, so that the DMA is a
+// linear copy.  Element i of one piece (NS output channels per slice, ncc = Cin / 16) -> its indices, the output channel ng
+// (rows beyond Cout exist: the last slice is padded) and the input channel c; first: the element that also writes the channel's bias
+struct WsPackIdx {
+    int sl, cc, tap, n, qp, e, ng, c;
+    bool first;
+};
+__host__ __device__ __forceinline__ WsPackIdx ws_pack_decode(long i, int NS, int ncc) {
+    WsPackIdx d;
+    d.e = (int)(i & 7); i >>= 3;
+    d.qp = (int)(i & 1); i >>= 1;
+    d.n = (int)(i % NS); i /= NS;
+    d.tap = (int)(i % 9); i /= 9;
+    d.cc = (int)(i % ncc);
+    d.sl = (int)(i / ncc);
+    d.ng = d.sl * NS + d.n;
+    d.c = d.cc * 16 + (d.qp ^ ((d.n >> 3) & 1)) * 8 + d.e;
+    d.first = d.cc == 0 && d.tap == 0 && d.qp == 0 && d.e == 0;
+    return d;
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef float ws_f32x4 __attribute__((ext_vector_type(4)));
 typedef float ws_f32x16 __attribute__((ext_vector_type(16)));

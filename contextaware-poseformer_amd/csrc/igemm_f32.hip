@@ -623,22 +623,16 @@ __global__ __launch_bounds__(256) void igemm_f32_rows_splitk_kernel(GemmArgs p) 
 }
 
 // =====================================================================================================
-// Grouped launch: up to MAXG independent convolutions (the branches of an HRNet module at the same depth,
-// the 1x1 / stride-2 convs of a fuse layer) share ONE grid.  A kernel per conv leaves the chip idle while
-// its last tiles drain and the next kernel's first tiles wait for their first loads (5-10 us out of ~50),
-// and separate streams overlap almost nothing because each kernel fills every CU; inside one grid the
-// block scheduler back-fills every freed slot at once and the problems' prologue / epilogue bursts
-// interleave.  Problems are ordered longest-K first (the 256-channel 8x8 branch has 8x the K loop of the
-// 32-channel 64x64 one); each problem's tile range is padded to a multiple of 8 blocks so that the
-// XCD-contiguous tile order of the single-problem kernel holds per problem.
+// Grouped launch (kernels.h "Grouped launch": the layout every conv family shares): up to MAXG independent
+// convolutions in ONE grid.
 struct GroupArgs {
     GemmArgs g[MAXG];
-    int start[MAXG + 1];   // first physical block of problem i (multiples of 8)
-    int tiles[MAXG];       // real tiles of problem i
+    GroupLayout lay;
     int cfg[MAXG];         // 0: 128x64 (S=2), 1: 64x64 (S=3), 2: 128x32 (S=2)
-    int splits[MAXG];      // split-K slices per tile (1 = none); tiles[] counts blocks = tiles x splits
+    int splits[MAXG];      // split-K slices per tile (1 = none); lay.tiles[] counts blocks = tiles x splits
     int n;
 };
+static_assert(sizeof(GroupArgs) == MAXG * sizeof(GemmArgs) + (4 * MAXG + 2) * sizeof(int), "kernel argument layout");
 static constexpr int GROUP_LDS_FLOATS = 2 * (128 + 64) * BK;   // 48 KiB: 3 blocks per CU for every configuration
 static_assert(3 * (64 + 64) * BK <= GROUP_LDS_FLOATS && 2 * (128 + 32) * BK <= GROUP_LDS_FLOATS, "group LDS");
 
@@ -649,12 +643,9 @@ __global__ __launch_bounds__(256) void igemm_f32_group_kernel(GroupArgs ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) float lds[GROUP_LDS_FLOATS];
     const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;          // block-uniform
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);                 // XCD-contiguous tile order inside the problem
-    if (bid >= ga.tiles[pi]) return;                              // padding block
+    const GroupSlot t = group_slot(ga.lay, ga.n, b);
+    if (!t.live) return;
+    const int pi = t.pi, bid = t.bid;
     const GemmArgs& p = ga.g[pi];
     const int sp = SPLITK ? ga.splits[pi] : 1;
     const int tile = sp > 1 ? bid / sp : bid, ky = sp > 1 ? bid - tile * sp : 0;
@@ -1149,8 +1140,8 @@ hipError_t launch_gemm_f32_group(const GemmArgs* list, int n, hipStream_t s) {
         total += (double)list[i].M * list[i].N * (list[i].Kpad / BK) / 4096.0;
     }
     const double per_cu = total / 256.0;
-    struct Item { int idx, cfg, tiles; double cost; };
-    Item it[MAXG];
+    int cfgs[MAXG], tiles[MAXG], order[MAXG];
+    double cost[MAXG];
     for (int i = 0; i < n; ++i) {
         const GemmArgs& a = list[i];
         const int chunks = a.Kpad / BK;
@@ -1161,11 +1152,11 @@ hipError_t launch_gemm_f32_group(const GemmArgs* list, int n, hipStream_t s) {
             const double big = chunks * 2.0 * 3.0;
             cfg = (big <= 0.8 * per_cu && a.M >= 128) ? 0 : 1;
         }
-        it[i] = Item{i, cfg, ((a.M + BMs[cfg] - 1) / BMs[cfg]) * ((a.N + BNs[cfg] - 1) / BNs[cfg]),
-                     chunks * (BMs[cfg] * BNs[cfg] / 4096.0)};
+        cfgs[i] = cfg;
+        tiles[i] = ((a.M + BMs[cfg] - 1) / BMs[cfg]) * ((a.N + BNs[cfg] - 1) / BNs[cfg]);
+        cost[i] = chunks * (BMs[cfg] * BNs[cfg] / 4096.0);
     }
-    for (int i = 1; i < n; ++i)                  // longest tile first (insertion sort, n <= 8)
-        for (int j = i; j > 0 && it[j].cost > it[j - 1].cost; --j) { Item t = it[j]; it[j] = it[j - 1]; it[j - 1] = t; }
+    group_order(n, cost, order);                 // longest tile first
     // Small batches: a level is a few dozen tiles and its duration is the K loop of the longest problem (72 chunks for the
     // 256-channel 8x8 branch against 9 for the 32-channel one).  A problem with a long K and a handful of tiles is split
     // along K; the slices of a tile meet through the scratch the caller lent (GemmArgs::split_ws / split_cnt), reduced in
@@ -1179,19 +1170,20 @@ hipError_t launch_gemm_f32_group(const GemmArgs* list, int n, hipStream_t s) {
     // 10 % at batch 2 / 4: the device-scope release / acquire around the counter (an L2 write-back on this multi-XCD
     // part) and the second pass over the slabs cost ~15 us, which only a long loop on a handful of tiles repays.
     long ws_used = 0, cnt_used = 0;
-    GroupArgs ga;
+    GroupArgs ga{};
     ga.n = n;
-    int start = 0;
+    int blocks[MAXG];                            // per problem in launch order: tiles x split-K slices
     for (int i = 0; i < n; ++i) {
-        GemmArgs a = list[it[i].idx];
+        const int li = order[i];
+        GemmArgs a = list[li];
         const int chunks = a.Kpad / BK;
         a.splits = 1; a.cps = chunks; a.split_stride = 0;
         float* ws = a.split_ws; int* cnt = a.split_cnt;
         a.split_ws = nullptr; a.split_cnt = nullptr;
-        if (ws && cnt && worth_splitting(list[it[i].idx])) {
+        if (ws && cnt && worth_splitting(list[li])) {
             int sp = std::min(8, chunks / 6);
             const long slab = (long)a.M * a.N;
-            if ((ws_used + slab * sp) > list[it[i].idx].split_ws_elems || cnt_used + it[i].tiles > list[it[i].idx].split_cnt_elems) sp = 1;
+            if ((ws_used + slab * sp) > list[li].split_ws_elems || cnt_used + tiles[li] > list[li].split_cnt_elems) sp = 1;
             if (sp > 1) {
                 a.cps = (chunks + sp - 1) / sp;
                 sp = (chunks + a.cps - 1) / a.cps;
@@ -1200,7 +1192,7 @@ hipError_t launch_gemm_f32_group(const GemmArgs* list, int n, hipStream_t s) {
                 a.split_ws = ws + ws_used;
                 a.split_cnt = cnt + cnt_used;
                 ws_used += slab * sp;
-                cnt_used += it[i].tiles;
+                cnt_used += tiles[li];
             }
         }
         if (a.rs_div <= 0) a.rs_div = 1;
@@ -1208,14 +1200,11 @@ hipError_t launch_gemm_f32_group(const GemmArgs* list, int n, hipStream_t s) {
             return hipErrorInvalidValue;
         if (!prep_conv(a)) return hipErrorInvalidValue;
         ga.g[i] = a;
-        ga.cfg[i] = it[i].cfg;
+        ga.cfg[i] = cfgs[li];
         ga.splits[i] = a.splits;
-        ga.tiles[i] = it[i].tiles * a.splits;
-        ga.start[i] = start;
-        start += (ga.tiles[i] + 7) & ~7;
+        blocks[i] = tiles[li] * a.splits;
     }
-    ga.start[n] = start;
-    for (int i = n; i < MAXG; ++i) { ga.start[i + 1] = start; ga.tiles[i] = 0; ga.cfg[i] = 0; ga.splits[i] = 1; }
+    const int start = group_fill(ga.lay, n, blocks);
     bool any_split = false;
     for (int i = 0; i < n; ++i) any_split |= ga.splits[i] > 1;
 #ifdef CAPF_DIAG

@@ -447,22 +447,18 @@ __global__ __launch_bounds__(256, 2) void igemm_f32h2g_wide_kernel(GemmArgs p) {
 
 struct G2GroupArgs {
     GemmArgs g[MAXG];
-    int start[MAXG + 1];
-    int tiles[MAXG];
+    GroupLayout lay;
     int cfg[MAXG];
     int n;
 };
+static_assert(sizeof(G2GroupArgs) == MAXG * sizeof(GemmArgs) + (3 * MAXG + 2) * sizeof(int), "kernel argument layout");
 
 __global__ __launch_bounds__(256, 3) void igemm_f32h2g_group_kernel(G2GroupArgs ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) float lds[G2_LDS_FLOATS];
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);
-    if (bid >= ga.tiles[pi]) return;
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    const int pi = t.pi, bid = t.bid;
     if (ga.cfg[pi] == 0) igemm_h2_tile<128, 64, 32, 64, 2, 1, true>(ga.g[pi], bid, lds);
     else if (ga.cfg[pi] == 2) igemm_h2_tile<128, 32, 32, 32, 2, 1, true>(ga.g[pi], bid, lds);
     else igemm_h2_tile<64, 64, 32, 32, 3, 1, true>(ga.g[pi], bid, lds);
@@ -556,29 +552,22 @@ hipError_t launch_gemm_f32h2g(const GemmArgs& a_in, hipStream_t s) {
 hipError_t launch_gemm_f32h2g_group(const GemmArgs* list, int n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n > MAXG) return hipErrorInvalidValue;
-    struct Item { GemmArgs a; int cfg, tiles, cost; };
-    Item it[MAXG];
+    GemmArgs a[MAXG];
+    int cfg[MAXG], tiles[MAXG], order[MAXG];
+    double cost[MAXG];
     for (int i = 0; i < n; ++i) {
         if (!gemm_f32h2g_ok(list[i]) || !list[i].conv || !g2_plain(list[i])) return hipErrorInvalidValue;
-        it[i].a = list[i];
-        it[i].a.Wp = list[i].Wh2;
-        g2_fill(it[i].a);
-        it[i].cfg = g2_cfg(it[i].a, true);
-        it[i].tiles = g2_tiles(it[i].a, it[i].cfg);
-        it[i].cost = it[i].a.Kpad;
+        a[i] = list[i];
+        a[i].Wp = list[i].Wh2;
+        g2_fill(a[i]);
+        cfg[i] = g2_cfg(a[i], true);
+        tiles[i] = g2_tiles(a[i], cfg[i]);
+        cost[i] = a[i].Kpad;
     }
-    for (int i = 1; i < n; ++i)
-        for (int j = i; j > 0 && it[j].cost > it[j - 1].cost; --j) { Item t = it[j]; it[j] = it[j - 1]; it[j - 1] = t; }
-    G2GroupArgs ga;
+    G2GroupArgs ga{};
     ga.n = n;
-    int start = 0;
-    for (int i = 0; i < n; ++i) {
-        ga.g[i] = it[i].a; ga.cfg[i] = it[i].cfg; ga.tiles[i] = it[i].tiles;
-        ga.start[i] = start;
-        start += (it[i].tiles + 7) & ~7;
-    }
-    ga.start[n] = start;
-    for (int i = n; i < MAXG; ++i) { ga.start[i + 1] = start; ga.tiles[i] = 0; ga.cfg[i] = 1; ga.g[i] = ga.g[0]; }
+    const int start = group_layout(ga.lay, n, tiles, cost, order);
+    for (int i = 0; i < n; ++i) { ga.g[i] = a[order[i]]; ga.cfg[i] = cfg[order[i]]; }
     hipLaunchKernelGGL(igemm_f32h2g_group_kernel, dim3(start), dim3(256), 0, s, ga);
     return hipGetLastError();
 }
@@ -593,20 +582,28 @@ const char* gemm_f32h2g_kernel_name(const GemmArgs& a, bool grouped) {
 
 // ---- pack: fold (conv: BatchNorm as launch_pack_conv; linear: none) -> one power-of-two scale per output channel -> two fp16 pieces;
 // Wp[n][chunk][piece][32] fp16 over the fp32 pack's geometry ([N][Kpad] floats, k = (kh, kw, ci) for convs), then [N] fp32 inverse scales
+// (one block per row of w [N][K]; blocks n >= N -- the conv tile's pack pads N to whole 32-channel slices -- write scale 1)
 __global__ __launch_bounds__(256) void g2_wscale_kernel(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ var,
                                                         float eps, float* __restrict__ winv, int N, int K) {
     __shared__ float red[256];
     const int n = blockIdx.x;
-    const float sc = gamma ? gamma[n] / sqrtf(var[n] + eps) : 1.f;
     float m = 0.f;
-    for (int i = threadIdx.x; i < K; i += 256) m = fmaxf(m, fabsf(w[(long)n * K + i] * sc));
+    if (n < N) {
+        const float sc = bn_scale(gamma, var, eps, n);
+        for (int i = threadIdx.x; i < K; i += 256) m = fmaxf(m, fabsf(w[(long)n * K + i] * sc));
+    }
     red[threadIdx.x] = m;
     __syncthreads();
     for (int st = 128; st > 0; st >>= 1) {
         if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
         __syncthreads();
     }
-    if (threadIdx.x == 0) winv[n] = __int_as_float((254 - h2_scale_exp(__float_as_int(red[0]))) << 23);
+    if (threadIdx.x == 0) winv[n] = n < N ? __int_as_float((254 - h2_scale_exp(__float_as_int(red[0]))) << 23) : 1.f;
+}
+
+hipError_t launch_f32h2_wscale(const float* w, const float* gamma, const float* var, float eps, float* winv, int rows, int N, int K, hipStream_t s) {
+    hipLaunchKernelGGL(g2_wscale_kernel, dim3(rows), dim3(256), 0, s, w, gamma, var, eps, winv, N, K);
+    return hipGetLastError();
 }
 
 __global__ void g2_pack_kernel(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -616,7 +613,7 @@ __global__ void g2_pack_kernel(const float* __restrict__ w, const float* __restr
         const int n = (int)(i / Kpad), k = (int)(i - (long)n * Kpad);
         float v = 0.f;
         if (k < K) {
-            const float sc = gamma ? gamma[n] / sqrtf(var[n] + eps) : 1.f;
+            const float sc = bn_scale(gamma, var, eps, n);
             long src;
             if (ks > 0) {                                   // conv: k = (kh, kw, ci) of an OIHW filter
                 const int t = k / Cin, c = k - t * Cin;
@@ -626,7 +623,7 @@ __global__ void g2_pack_kernel(const float* __restrict__ w, const float* __restr
             }
             v = w[src] * sc * __uint_as_float(0x7F000000u - __float_as_uint(winv[n]));
         }
-        if (bias && k == 0 && gamma) bias[n] = beta[n] - mean[n] * (gamma[n] / sqrtf(var[n] + eps));
+        if (bias && k == 0 && gamma) bias[n] = bn_bias(gamma, beta, mean, bn_scale(gamma, var, eps, n), n);      // (no BatchNorm: bias untouched)
         const _Float16 p0 = (_Float16)v;
         const _Float16 p1 = (_Float16)(v - (float)p0);
         const long base = ((long)n * (Kpad / 32) + k / 32) * 64 + (k & 31);
@@ -640,10 +637,10 @@ hipError_t launch_pack_f32h2_gemm(const float* w, const float* gamma, const floa
                                   float* Wp, float* bias, int N, int Cin, int ks, int K, int Kpad, hipStream_t s) {
     if (N <= 0 || Kpad % 32 != 0 || K > Kpad) return hipErrorInvalidValue;
     float* winv = Wp + (long)N * Kpad;
-    hipLaunchKernelGGL(g2_wscale_kernel, dim3(N), dim3(256), 0, s, w, gamma, var, eps, winv, N, K);
+    const hipError_t e = launch_f32h2_wscale(w, gamma, var, eps, winv, N, N, K, s);
+    if (e != hipSuccess) return e;
     const long total = (long)N * Kpad;
-    const long want = (total + 255) / 256;
-    hipLaunchKernelGGL(g2_pack_kernel, dim3((int)(want < 4096 ? want : 4096)), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
+    hipLaunchKernelGGL(g2_pack_kernel, dim3(grid_1d(total)), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
                        reinterpret_cast<unsigned short*>(Wp), winv, bias, N, Cin, ks, K, Kpad, total);
     return hipGetLastError();
 }
@@ -651,10 +648,10 @@ hipError_t launch_pack_f32h2_gemm(const float* w, const float* gamma, const floa
 hipError_t launch_pack_f32h2_gemm_rows(const float* w, float* Wp, int n0, int n, int Ntot, int K, int Kpad, hipStream_t s) {
     if (n <= 0 || Kpad % 32 != 0 || K > Kpad || n0 < 0 || n0 + n > Ntot) return hipErrorInvalidValue;
     float* winv = Wp + (long)Ntot * Kpad + n0;
-    hipLaunchKernelGGL(g2_wscale_kernel, dim3(n), dim3(256), 0, s, w, (const float*)nullptr, (const float*)nullptr, 0.f, winv, n, K);
+    const hipError_t e = launch_f32h2_wscale(w, nullptr, nullptr, 0.f, winv, n, n, K, s);
+    if (e != hipSuccess) return e;
     const long total = (long)n * Kpad;
-    const long want = (total + 255) / 256;
-    hipLaunchKernelGGL(g2_pack_kernel, dim3((int)(want < 4096 ? want : 4096)), dim3(256), 0, s, w, (const float*)nullptr, (const float*)nullptr,
+    hipLaunchKernelGGL(g2_pack_kernel, dim3(grid_1d(total)), dim3(256), 0, s, w, (const float*)nullptr, (const float*)nullptr,
                        (const float*)nullptr, (const float*)nullptr, 0.f, reinterpret_cast<unsigned short*>(Wp + (long)n0 * Kpad), winv,
                        (float*)nullptr, n, 0, 0, K, Kpad, total);
     return hipGetLastError();

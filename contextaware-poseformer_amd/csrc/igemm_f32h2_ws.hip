@@ -18,11 +18,7 @@ long f32h2_pack_elems(int Cout, int Cin) { return h2_pack_elems(Cout, Cin); }
 // the chip with them -- at least 512 such tiles; 32 otherwise (three blocks per CU).  Either width computes the same bits: the K order
 // and the block scales do not depend on it.
 static bool h2_from_args(const GemmArgs& a, H2Problem* q) {
-    if (!a.conv || a.ks != 3 || a.stride != 1 || a.pad != 1 || a.Ho != a.H || a.Wo != a.W || a.act == ACT_GELU || a.rscale || a.out_bf16 ||
-        a.omap.G != 1 || (a.res && a.rmap.G != 1) || a.M <= 0 || a.H <= 0 || a.W <= 0 || a.M % (a.H * a.W) != 0)
-        return false;
-    if ((a.omap.S1 & 3) || (a.omap.off & 3) || (a.res && ((a.rmap.S1 & 3) || (a.rmap.off & 3)))) return false;     // 16-byte pieces
-    if ((double)WS_MAX_P * (double)a.omap.S1 * 4.0 >= 2.0e9 || (a.res && (double)WS_MAX_P * (double)a.rmap.S1 * 4.0 >= 2.0e9)) return false;   // (one tile's rows)
+    if (a.out_bf16 || !ws_args_ok(a, 3, 4.0, WS_MAX_P)) return false;  // (fp32 rows, fp32 out only; offsets count from a tile's base: one tile's rows)
     if (!h2_plan(a.M / (a.H * a.W), a.H, a.W, a.Cin, a.N, 32, q)) return false;
     static const long wide_min = [] { const char* e = diag_env("CAPF_H2_WIDE_MIN_TILES"); return e ? atol(e) : 512L; }();      // (diag builds: A/B runs)
     if (a.N % 64 == 0 && (long)q->g.tiles_m * (a.N / 64) >= wide_min) { q->g.NS = 64; q->g.NSL = a.N / 64; }
@@ -63,44 +59,30 @@ bool f32h2_shape_ok(int B, int H, int W, int Cin, int Cout) {
 
 struct H2GroupArgs {
     H2Problem g[MAXG];
-    int start[MAXG + 1];
-    int tiles[MAXG];
+    GroupLayout lay;
     int n;
 };
+static_assert(sizeof(H2GroupArgs) == MAXG * sizeof(H2Problem) + (2 * MAXG + 2) * sizeof(int), "kernel argument layout");
 
 template <int TN, bool PIN = false, bool POUT = false>
 __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void igemm_f32h2_group_ws_kernel(H2GroupArgs ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) unsigned char h2_lds[];
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);          // block b of a problem runs on XCD b % 8: that XCD's contiguous eighth of the tiles
-    if (bid >= ga.tiles[pi]) return;
-    igemm_f32h2_ws_tile<TN, PIN, POUT>(ga.g[pi], bid, h2_lds);
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    igemm_f32h2_ws_tile<TN, PIN, POUT>(ga.g[t.pi], t.bid, h2_lds);
 #endif
 }
 
 template <int TN, bool PIN = false, bool POUT = false>
 static hipError_t h2_launch(const H2Problem* list, int n, hipStream_t s) {
-    struct Item { H2Problem q; int cost; };
-    Item it[MAXG];
-    for (int i = 0; i < n; ++i) { it[i].q = list[i]; it[i].cost = list[i].g.C; }   // a tile's K loop: longest first, so that the launch does not end on them
-    for (int i = 1; i < n; ++i)
-        for (int j = i; j > 0 && it[j].cost > it[j - 1].cost; --j) { Item t = it[j]; it[j] = it[j - 1]; it[j - 1] = t; }
-    H2GroupArgs ga;
+    int tiles[MAXG], order[MAXG];
+    double cost[MAXG];
+    for (int i = 0; i < n; ++i) { tiles[i] = list[i].g.tiles_m * list[i].g.NSL; cost[i] = list[i].g.C; }   // a tile's K loop
+    H2GroupArgs ga{};
     ga.n = n;
-    int start = 0;
-    for (int i = 0; i < n; ++i) {
-        ga.g[i] = it[i].q;
-        ga.tiles[i] = it[i].q.g.tiles_m * it[i].q.g.NSL;
-        ga.start[i] = start;
-        start += (ga.tiles[i] + 7) & ~7;
-    }
-    ga.start[n] = start;
-    for (int i = n; i < MAXG; ++i) { ga.start[i + 1] = start; ga.tiles[i] = 0; ga.g[i] = ga.g[0]; }
+    const int start = group_layout(ga.lay, n, tiles, cost, order);
+    for (int i = 0; i < n; ++i) ga.g[i] = list[order[i]];
     static DynLdsAttr attr;
     const hipError_t e = attr.ensure(reinterpret_cast<const void*>(&igemm_f32h2_group_ws_kernel<TN, PIN, POUT>), h2_lds_bytes(32 * TN));
     if (e != hipSuccess) return e;
@@ -138,49 +120,19 @@ const char* gemm_f32h2_kernel_name(const GemmArgs&) { return "igemm_f32h2_group_
 
 // ---- weight pack: BN fold (the fp32 value v launch_pack_conv folds), one power-of-two scale t per output channel with max |v| t in
 // [2^14, 2^15), two fp16 pieces of v t -- piece 0 = fp16(v t), piece 1 = fp16(v t - piece 0), |v t - piece 0 - piece 1| <= 2^-23 |v t| --
-// at Wp[slice][Cin / 16][piece][tap][n][quad position][8], h = quad position ^ ((n >> 3) & 1) (the LDS image's bank swizzle: the DMA is a
-// linear copy), then the fp32 inverse scales 1 / t [slices * 32]; rows beyond Cout zero with scale 1; bias as launch_pack_conv
-__global__ __launch_bounds__(256) void h2_wscale_kernel(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ var,
-                                                        float eps, float* __restrict__ winv, int Cout, int Cin) {
-    __shared__ float red[256];
-    const int ng = blockIdx.x;
-    float m = 0.f;
-    if (ng < Cout) {
-        const float sc = gamma ? gamma[ng] / sqrtf(var[ng] + eps) : 1.f;
-        for (int i = threadIdx.x; i < Cin * 9; i += 256) m = fmaxf(m, fabsf(w[(long)ng * Cin * 9 + i] * sc));
-    }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) winv[ng] = ng < Cout ? __int_as_float((254 - h2_scale_exp(__float_as_int(red[0]))) << 23) : 1.f;
-}
-
+// at Wp[slice][Cin / 16][piece][tap][n][quad position][8] (ws_pack_decode), then the fp32 inverse scales 1 / t [slices * 32]
+// (launch_f32h2_wscale); rows beyond Cout zero with scale 1; bias as launch_pack_conv
 __global__ void pack_conv_f32h2_kernel(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ beta,
                                        const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                        unsigned short* __restrict__ Wp, const float* __restrict__ winv, float* __restrict__ bias,
                                        int Cout, int Cin, long total) {
     const int ncc = Cin / 16;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {   // i: one weight, its two pieces
-        long k = i;
-        const int e = (int)(k & 7); k >>= 3;
-        const int qp = (int)(k & 1); k >>= 1;
-        const int n = (int)(k & 31); k >>= 5;
-        const int tap = (int)(k % 9); k /= 9;
-        const int cc = (int)(k % ncc);
-        const int sl = (int)(k / ncc);
-        const int ng = sl * 32 + n, c = cc * 16 + (qp ^ ((n >> 3) & 1)) * 8 + e;
-        float v = 0.f;
-        if (ng < Cout) {
-            const float sc = gamma ? gamma[ng] / sqrtf(var[ng] + eps) : 1.f;
-            v = w[(((long)ng * Cin + c) * 3 + tap / 3) * 3 + tap % 3] * sc;
-            if (bias && cc == 0 && tap == 0 && qp == 0 && e == 0) bias[ng] = gamma ? beta[ng] - mean[ng] * sc : 0.f;
-            v *= __uint_as_float(0x7F000000u - __float_as_uint(winv[ng]));      // the channel's scale: 1 / (a power of two), exact
-        }
+        const WsPackIdx d = ws_pack_decode(i, 32, ncc);
+        float v = bn_fold_w3x3(w, gamma, beta, mean, var, eps, bias, Cout, Cin, d.ng, d.c, d.tap, d.first);
+        if (d.ng < Cout) v *= __uint_as_float(0x7F000000u - __float_as_uint(winv[d.ng]));      // the channel's scale: 1 / (a power of two), exact
         const long piece = 9L * 32 * 16;
-        const long base = ((long)(sl * ncc + cc) * 2) * piece + ((long)tap * 32 + n) * 16 + qp * 8 + e;
+        const long base = ((long)(d.sl * ncc + d.cc) * 2) * piece + ((long)d.tap * 32 + d.n) * 16 + d.qp * 8 + d.e;
         const _Float16 p0 = (_Float16)v;
         const _Float16 p1 = (_Float16)(v - (float)p0);
         Wp[base] = __builtin_bit_cast(unsigned short, p0);
@@ -194,10 +146,10 @@ hipError_t launch_pack_conv_f32h2(const float* w, const float* gamma, const floa
     unsigned short* Wp = static_cast<unsigned short*>(Wp_f16);
     float* winv = reinterpret_cast<float*>(Wp + h2_piece_elems(Cout, Cin));
     const int npad = ((Cout + 31) / 32) * 32;
-    hipLaunchKernelGGL(h2_wscale_kernel, dim3(npad), dim3(256), 0, s, w, gamma, var, eps, winv, Cout, Cin);
+    const hipError_t e = launch_f32h2_wscale(w, gamma, var, eps, winv, npad, Cout, Cin * 9, s);      // (padding rows: scale 1)
+    if (e != hipSuccess) return e;
     const long total = h2_piece_elems(Cout, Cin) / 2;
-    const long want = (total + 255) / 256;
-    hipLaunchKernelGGL(pack_conv_f32h2_kernel, dim3((int)(want < 4096 ? want : 4096)), dim3(256), 0, s, w, gamma, beta, mean, var, eps, Wp,
+    hipLaunchKernelGGL(pack_conv_f32h2_kernel, dim3(grid_1d(total)), dim3(256), 0, s, w, gamma, beta, mean, var, eps, Wp,
                        winv, bias, Cout, Cin, total);
     return hipGetLastError();
 }

@@ -16,11 +16,7 @@ long f32x3_pack_elems(int Cout, int Cin) { return x3_pack_elems(Cout, Cin, X3_NS
 
 // GemmArgs -> tile geometry; false = not a problem this tile takes
 static bool x3_from_args(const GemmArgs& a, X3Problem* q) {
-    if (!a.conv || a.ks != 3 || a.stride != 1 || a.pad != 1 || a.Ho != a.H || a.Wo != a.W || a.act == ACT_GELU || a.rscale || a.out_bf16 ||
-        a.omap.G != 1 || (a.res && a.rmap.G != 1) || a.M <= 0 || a.H <= 0 || a.W <= 0 || a.M % (a.H * a.W) != 0)
-        return false;
-    if ((a.omap.S1 & 3) || (a.omap.off & 3) || (a.res && ((a.rmap.S1 & 3) || (a.rmap.off & 3)))) return false;     // 16-byte pieces
-    if ((double)a.M * (double)a.omap.S1 * 4.0 >= 2.0e9 || (a.res && (double)a.M * (double)a.rmap.S1 * 4.0 >= 2.0e9)) return false;
+    if (a.out_bf16 || !ws_args_ok(a, 3, 4.0, a.M)) return false;       // (fp32 rows, fp32 out only)
     if (!x3_plan(a.M / (a.H * a.W), a.H, a.W, a.Cin, a.N, X3_NS, q)) return false;
     q->x = a.A;
     q->g.wp = reinterpret_cast<const unsigned short*>(a.Wp3);
@@ -63,22 +59,17 @@ bool gemm_f32x3_wanted(const GemmArgs& a) {            // (one geometry computat
 
 struct X3GroupArgs {
     X3Problem g[MAXG];
-    int start[MAXG + 1];
-    int tiles[MAXG];
+    GroupLayout lay;
     int n;
 };
+static_assert(sizeof(X3GroupArgs) == MAXG * sizeof(X3Problem) + (2 * MAXG + 2) * sizeof(int), "kernel argument layout");
 
 __global__ __launch_bounds__(256, 2) void igemm_f32x3_group_ws_kernel(X3GroupArgs ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) unsigned char x3_lds[];
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);          // block b of a problem runs on XCD b % 8: that XCD's contiguous eighth of the tiles
-    if (bid >= ga.tiles[pi]) return;
-    igemm_f32x3_ws_tile<X3_NS / 32>(ga.g[pi], bid, x3_lds);
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    igemm_f32x3_ws_tile<X3_NS / 32>(ga.g[t.pi], t.bid, x3_lds);
 #endif
 }
 
@@ -86,25 +77,18 @@ hipError_t launch_gemm_f32x3_group(const GemmArgs* list, int n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n > MAXG) return hipErrorInvalidValue;
     if (list[0].x3_h2) return launch_gemm_f32h2_group(list, n, s);      // (the two-fp16-piece tile: one plan, one kind of pack per engine)
-    struct Item { X3Problem q; int cost; };
-    Item it[MAXG];
+    X3Problem q[MAXG];
+    int tiles[MAXG], order[MAXG];
+    double cost[MAXG];
     for (int i = 0; i < n; ++i) {
-        if (!list[i].Wp3 || !x3_from_args(list[i], &it[i].q)) return hipErrorInvalidValue;
-        it[i].cost = it[i].q.g.C;                           // a tile's K loop: longest first, so that the launch does not end on them
+        if (!list[i].Wp3 || !x3_from_args(list[i], &q[i])) return hipErrorInvalidValue;
+        tiles[i] = q[i].g.tiles_m * q[i].g.NSL;
+        cost[i] = q[i].g.C;                                 // a tile's K loop
     }
-    for (int i = 1; i < n; ++i)
-        for (int j = i; j > 0 && it[j].cost > it[j - 1].cost; --j) { Item t = it[j]; it[j] = it[j - 1]; it[j - 1] = t; }
-    X3GroupArgs ga;
+    X3GroupArgs ga{};
     ga.n = n;
-    int start = 0;
-    for (int i = 0; i < n; ++i) {
-        ga.g[i] = it[i].q;
-        ga.tiles[i] = it[i].q.g.tiles_m * it[i].q.g.NSL;
-        ga.start[i] = start;
-        start += (ga.tiles[i] + 7) & ~7;
-    }
-    ga.start[n] = start;
-    for (int i = n; i < MAXG; ++i) { ga.start[i + 1] = start; ga.tiles[i] = 0; ga.g[i] = ga.g[0]; }
+    const int start = group_layout(ga.lay, n, tiles, cost, order);
+    for (int i = 0; i < n; ++i) ga.g[i] = q[order[i]];
     static DynLdsAttr attr_once;
     const hipError_t attr = attr_once.ensure(reinterpret_cast<const void*>(&igemm_f32x3_group_ws_kernel), x3_lds_bytes(X3_NS));
     if (attr != hipSuccess) return attr;
@@ -116,31 +100,18 @@ hipError_t launch_gemm_f32x3(const GemmArgs& a, hipStream_t s) { return launch_g
 
 const char* gemm_f32x3_kernel_name(const GemmArgs& a) { return a.x3_h2 ? gemm_f32h2_kernel_name(a) : "igemm_f32x3_group_ws"; }
 
-// BN fold + three-way split + re-layout for the tile: with v = w[slice * NS + n][cc * 16 + 8 h + e][kh][kw] * gamma / sqrt(var + eps) (the
-// fp32 value launch_pack_conv folds), piece 0 = bf16(v), piece 1 = bf16(v - piece 0), piece 2 = bf16(v - piece 0 - piece 1) -- exact
-// remainders, v = piece 0 + piece 1 + piece 2 -- at Wp[slice][Cin / 16][piece][tap][n][quad position][8], h = quad position ^ ((n >> 3) & 1)
-// (the LDS image's bank swizzle, so that the DMA is a linear copy); rows beyond Cout zero; bias as launch_pack_conv
+// BN fold + three-way split + re-layout for the tile: with v the folded fp32 weight (bn_fold_w3x3: the value launch_pack_conv folds, rows
+// beyond Cout zero, bias as launch_pack_conv), piece 0 = bf16(v), piece 1 = bf16(v - piece 0), piece 2 = bf16(v - piece 0 - piece 1) -- exact
+// remainders, v = piece 0 + piece 1 + piece 2 -- at Wp[slice][Cin / 16][piece][tap][n][quad position][8] (ws_pack_decode)
 __global__ void pack_conv_f32x3_kernel(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ beta,
                                        const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                        unsigned short* __restrict__ Wp, float* __restrict__ bias, int Cout, int Cin, int NS, long total) {
     const int ncc = Cin / 16;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {   // i: one weight, its three pieces
-        long k = i;
-        const int e = (int)(k & 7); k >>= 3;
-        const int qp = (int)(k & 1); k >>= 1;
-        const int n = (int)(k % NS); k /= NS;
-        const int tap = (int)(k % 9); k /= 9;
-        const int cc = (int)(k % ncc);
-        const int sl = (int)(k / ncc);
-        const int ng = sl * NS + n, c = cc * 16 + (qp ^ ((n >> 3) & 1)) * 8 + e;
-        float v = 0.f;
-        if (ng < Cout) {
-            const float sc = gamma ? gamma[ng] / sqrtf(var[ng] + eps) : 1.f;
-            v = w[(((long)ng * Cin + c) * 3 + tap / 3) * 3 + tap % 3] * sc;
-            if (bias && cc == 0 && tap == 0 && qp == 0 && e == 0) bias[ng] = gamma ? beta[ng] - mean[ng] * sc : 0.f;
-        }
+        const WsPackIdx d = ws_pack_decode(i, NS, ncc);
+        float v = bn_fold_w3x3(w, gamma, beta, mean, var, eps, bias, Cout, Cin, d.ng, d.c, d.tap, d.first);
         const long piece = 9L * NS * 16;
-        const long base = ((long)(sl * ncc + cc) * 3) * piece + ((long)tap * NS + n) * 16 + qp * 8 + e;
+        const long base = ((long)(d.sl * ncc + d.cc) * 3) * piece + ((long)d.tap * NS + d.n) * 16 + d.qp * 8 + d.e;
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) {
             const unsigned short b = to_bf16(v);
@@ -154,8 +125,7 @@ hipError_t launch_pack_conv_f32x3(const float* w, const float* gamma, const floa
                                   void* Wp_bf16, float* bias, int Cout, int Cin, hipStream_t s) {
     if (Cin % 16 != 0 || Cout <= 0) return hipErrorInvalidValue;
     const long total = f32x3_pack_elems(Cout, Cin) / 3;
-    const long want = (total + 255) / 256;
-    hipLaunchKernelGGL(pack_conv_f32x3_kernel, dim3((int)(want < 4096 ? want : 4096)), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
+    hipLaunchKernelGGL(pack_conv_f32x3_kernel, dim3(grid_1d(total)), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
                        static_cast<unsigned short*>(Wp_bf16), bias, Cout, Cin, X3_NS, total);
     return hipGetLastError();
 }

@@ -1244,48 +1244,39 @@ __global__ __launch_bounds__(256, 2) void igemm_wino_kernel(GemmArgs p, int cfg)
 // grouped launch: up to MAXG Winograd problems in one grid (the 3x3 convs of an HRNet level), longest K first
 struct WinoGroupArgs {
     GemmArgs g[MAXG];
-    int start[MAXG + 1];
-    int tiles[MAXG];
+    GroupLayout lay;
     int cfg[MAXG];
     int n;
 };
+static_assert(sizeof(WinoGroupArgs) == MAXG * sizeof(GemmArgs) + (3 * MAXG + 2) * sizeof(int), "kernel argument layout");
 
 template <bool PP>
 __global__ __launch_bounds__(256, 2) void igemm_wino_group_kernel(WinoGroupArgs ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float wlds[];
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);
-    if (bid >= ga.tiles[pi]) return;
-    wino_dispatch<PP>(ga.g[pi], ga.cfg[pi], bid, wlds);
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    wino_dispatch<PP>(ga.g[t.pi], ga.cfg[t.pi], t.bid, wlds);
 #endif
 }
 
 // F(4,3) problems only, 16-channel sub-chunks, THREE blocks per CU (<= 168 registers, 36 KiB of LDS): see wino43s_tile
 struct Wino43GroupArgs {
     GemmArgs g[MAXG];
-    int start[MAXG + 1];
-    int tiles[MAXG];
+    GroupLayout lay;
     int cfg[MAXG];                             // 3: 64 tiles x 32 channels, 4: 32 tiles x 64 channels
     int prio[MAXG];                            // s_setprio level of the problem's waves (see launch_wino43_group)
     int n;
 };
+static_assert(sizeof(Wino43GroupArgs) == MAXG * sizeof(GemmArgs) + (4 * MAXG + 2) * sizeof(int), "kernel argument layout");
 
 [[maybe_unused]] static constexpr int W43S_LDS = 6 * (64 + 32) * 16;              // floats per superstage (36 KiB); device code only
 template <bool DB>
 __device__ __forceinline__ void wino43_group_body(const Wino43GroupArgs& ga, float* wlds) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    const int b = blockIdx.x;
-    int pi = 0;
-    while (pi + 1 < ga.n && b >= ga.start[pi + 1]) ++pi;
-    const int l = b - ga.start[pi];
-    const int per_xcd = (ga.start[pi + 1] - ga.start[pi]) >> 3;
-    const int bid = (l & 7) * per_xcd + (l >> 3);
-    if (bid >= ga.tiles[pi]) return;
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    const int pi = t.pi, bid = t.bid;
     // issue priority by K length (measured: no effect on the level either way; kept switchable in the diagnosis build)
     const int prio = ga.prio[pi];
     if (prio == 3) __builtin_amdgcn_s_setprio(3);
@@ -1323,7 +1314,7 @@ __global__ void pack_conv_wino_kernel(const float* __restrict__ w, const float* 
         const int n = (int)(i / Kw), k = (int)(i - (long)n * Kw);
         const int cl = k % WBK, pq = (k / WBK) % NP, cc = (k / (NP * WBK)) % CC, kh = k / (NP * WBK * CC);
         const int c = cc * WBK + cl;
-        const float sc = gamma ? gamma[n] / sqrtf(var[n] + eps) : 1.f;
+        const float sc = bn_scale(gamma, var, eps, n);
         const float* g = w + (((long)n * Cin + c) * 3 + kh) * 3;
         const float g0 = g[0] * sc, g1 = g[1] * sc, g2 = g[2] * sc;
         float u;
@@ -1341,7 +1332,7 @@ __global__ void pack_conv_wino_kernel(const float* __restrict__ w, const float* 
             else u = g2;
         }
         Wp[i] = u;
-        if (k == 0 && bias) bias[n] = gamma ? beta[n] - mean[n] * sc : 0.f;
+        if (k == 0 && bias) bias[n] = bn_bias(gamma, beta, mean, sc, n);
     }
 }
 
@@ -1351,8 +1342,7 @@ hipError_t launch_pack_conv_wino(const float* w, const float* gamma, const float
     if (Cin % WBK != 0 || (variant != 23 && variant != 43)) return hipErrorInvalidValue;
     const int NP = variant == 43 ? 6 : 4;
     const long total = (long)Cout * 3 * NP * Cin;
-    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(pack_conv_wino_kernel, dim3(blocks), dim3(256), 0, s, w, gamma, beta, mean, var, eps, Wp, bias, Cout, Cin, NP);
+    hipLaunchKernelGGL(pack_conv_wino_kernel, dim3(grid_1d(total, 2048)), dim3(256), 0, s, w, gamma, beta, mean, var, eps, Wp, bias, Cout, Cin, NP);
     return hipGetLastError();
 }
 
@@ -1425,38 +1415,31 @@ static int wino43_prio() {
 }
 
 static hipError_t launch_wino43_group(const GemmArgs* prep, const int* cfgs, int n, hipStream_t s) {
-    struct Item { int idx, tiles; double cost; };
-    Item it[MAXG];
-    for (int i = 0; i < n; ++i)
-        it[i] = Item{i, wino_tiles(prep[i], cfgs[i]), (double)prep[i].Cin};          // both tile shapes do the same work per block
-    for (int i = 1; i < n; ++i)                  // longest tile first
-        for (int j = i; j > 0 && it[j].cost > it[j - 1].cost; --j) { Item t = it[j]; it[j] = it[j - 1]; it[j - 1] = t; }
+    int order[MAXG], tiles[MAXG];
+    double cost[MAXG], sorted[MAXG];
+    for (int i = 0; i < n; ++i) cost[i] = (double)prep[i].Cin;   // both tile shapes do the same work per block
+    group_order(n, cost, order);                 // longest tile first
     if (const char* ord = diag_env("CAPF_WINO43_ORDER")) {       // A/B runs only: dispatch order as a permutation of the cost ranks, e.g. "0312"
-        Item tmp[MAXG];
-        int m = 0;
+        int tmp[MAXG], m = 0;
         for (const char* c = ord; *c && m < n; ++c)
-            if (*c >= '0' && *c - '0' < n) tmp[m++] = it[*c - '0'];
-        if (m == n) for (int i = 0; i < n; ++i) it[i] = tmp[i];
+            if (*c >= '0' && *c - '0' < n) tmp[m++] = order[*c - '0'];
+        if (m == n) for (int i = 0; i < n; ++i) order[i] = tmp[i];
     }
-    Wino43GroupArgs ga;
+    Wino43GroupArgs ga{};
     ga.n = n;
-    int start = 0;
+    for (int i = 0; i < n; ++i) { tiles[i] = wino_tiles(prep[order[i]], cfgs[order[i]]); sorted[i] = cost[order[i]]; }
+    const int start = group_fill(ga.lay, n, tiles);
     for (int i = 0; i < n; ++i) {
-        ga.g[i] = prep[it[i].idx];
-        ga.cfg[i] = cfgs[it[i].idx];
-        ga.tiles[i] = it[i].tiles;
-        ga.start[i] = start;
-        start += (it[i].tiles + 7) & ~7;
+        ga.g[i] = prep[order[i]];
+        ga.cfg[i] = cfgs[order[i]];
         // longest K -> priority 3, next distinct K length 2, ...; problems of the shortest K (and lone problems) stay at 0
         int longer = 0;
         for (int j = 0; j < n; ++j)
-            if (it[j].cost > it[i].cost && (j == 0 || it[j].cost != it[j - 1].cost)) ++longer;
+            if (sorted[j] > sorted[i] && (j == 0 || sorted[j] != sorted[j - 1])) ++longer;
         int shorter = 0;
-        for (int j = 0; j < n; ++j) shorter += it[j].cost < it[i].cost;
+        for (int j = 0; j < n; ++j) shorter += sorted[j] < sorted[i];
         ga.prio[i] = (shorter && wino43_prio()) ? std::max(1, 3 - longer) : 0;
     }
-    ga.start[n] = start;
-    for (int i = n; i < MAXG; ++i) { ga.start[i + 1] = start; ga.tiles[i] = 0; ga.cfg[i] = 4; ga.prio[i] = 0; }
     if (wino43_short() == 2) hipLaunchKernelGGL(igemm_wino43_group_db_kernel, dim3(start), dim3(256), 0, s, ga);
     else hipLaunchKernelGGL(igemm_wino43_group_kernel, dim3(start), dim3(256), 0, s, ga);
     return hipGetLastError();
@@ -1507,8 +1490,8 @@ hipError_t launch_gemm_wino_group(const GemmArgs* list, int n, hipStream_t s) {
     }
     hipError_t r = wino_attr();
     if (r != hipSuccess) return r;
-    struct Item { int idx, cfg, tiles; double cost; };
-    Item it[MAXG];
+    int cfgs[MAXG], tiles[MAXG], order[MAXG];
+    double cost[MAXG];
     GemmArgs prep[MAXG];
     int lds_floats = 0;
     if (wino43_short()) {                        // F(4,3) problems -> their own grid (three resident blocks per CU); the rest below
@@ -1534,22 +1517,14 @@ hipError_t launch_gemm_wino_group(const GemmArgs* list, int n, hipStream_t s) {
         if (!wino_prepare(prep[i])) return hipErrorInvalidValue;
         const int cfg = wino_cfg(prep[i]);
         lds_floats = std::max(lds_floats, kWLDS[cfg]);
-        it[i] = Item{i, cfg, wino_tiles(prep[i], cfg), (double)prep[i].Cin * kWT[cfg] * kWN[cfg] * (cfg >= 3 ? 1.5 : 1.0)};
+        cfgs[i] = cfg;
+        tiles[i] = wino_tiles(prep[i], cfg);
+        cost[i] = (double)prep[i].Cin * kWT[cfg] * kWN[cfg] * (cfg >= 3 ? 1.5 : 1.0);
     }
-    for (int i = 1; i < n; ++i)                  // longest tile first
-        for (int j = i; j > 0 && it[j].cost > it[j - 1].cost; --j) { Item t = it[j]; it[j] = it[j - 1]; it[j - 1] = t; }
-    WinoGroupArgs ga;
+    WinoGroupArgs ga{};
     ga.n = n;
-    int start = 0;
-    for (int i = 0; i < n; ++i) {
-        ga.g[i] = prep[it[i].idx];
-        ga.cfg[i] = it[i].cfg;
-        ga.tiles[i] = it[i].tiles;
-        ga.start[i] = start;
-        start += (it[i].tiles + 7) & ~7;
-    }
-    ga.start[n] = start;
-    for (int i = n; i < MAXG; ++i) { ga.start[i + 1] = start; ga.tiles[i] = 0; ga.cfg[i] = 0; }
+    const int start = group_layout(ga.lay, n, tiles, cost, order);       // longest tile first
+    for (int i = 0; i < n; ++i) { ga.g[i] = prep[order[i]]; ga.cfg[i] = cfgs[order[i]]; }
     if (wino_mode() == 1) hipLaunchKernelGGL(igemm_wino_group_kernel<false>, dim3(start), dim3(256), WLDS * sizeof(float), s, ga);
     else hipLaunchKernelGGL(igemm_wino_group_kernel<true>, dim3(start), dim3(256), lds_floats * sizeof(float), s, ga);
     return hipGetLastError();

@@ -164,10 +164,116 @@ hipError_t launch_res_chain_repack(const float* h2g_pack, float* chain_pack, int
 hipError_t launch_res_chain(float* X, int rows, int tokens, int heads, float eps, const ResBlockW* blk, int nblk, hipStream_t s);
 hipError_t launch_mlp_chain(float* X, RowMap rows_map, int rows, float eps, const ResBlockW& blk, hipStream_t s);     // the MLP half alone, on mapped rows
 
+// 1-D grid of a grid-stride kernel with 256-thread blocks: one thread per element up to `cap` blocks
+inline int grid_1d(long total, int cap = 4096) {
+    const long want = (total + 255) / 256;
+    return (int)(want < cap ? want : cap);
+}
+
+// Eval-mode BatchNorm folded into a conv (pose_hrnet.py:72-75 etc.): y = (conv(x) - mean) / sqrt(var + eps) * gamma + beta ==
+// conv_{w * sc}(x) + (beta - mean * sc); gamma == nullptr: no BatchNorm (scale 1, bias 0).  Every weight pack folds through these two,
+// so that all layouts of one conv hold the same fp32 values (tests/test_gpu_ops.py checks the packs bit for bit against host folds;
+// the expressions are inlined whole, so -ffp-contract sees beta - mean * sc as it always did)
+#if defined(__HIPCC__)
+__device__ __forceinline__ float bn_scale(const float* __restrict__ gamma, const float* __restrict__ var, float eps, int n) {
+    return gamma ? gamma[n] / sqrtf(var[n] + eps) : 1.f;
+}
+__device__ __forceinline__ float bn_bias(const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean, float sc, int n) {
+    return gamma ? beta[n] - mean[n] * sc : 0.f;
+}
+// one folded weight of a 3x3 filter w [Cout][Cin][3][3] for the 2-D halo tiles' packs (igemm_bf16_ws_tile.h ws_pack_decode: output channel
+// ng, input channel c, tap = kh * 3 + kw); rows beyond Cout are zero.  The thread that holds a channel's first element also writes its bias
+__device__ __forceinline__ float bn_fold_w3x3(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                              const float* __restrict__ mean, const float* __restrict__ var, float eps, float* __restrict__ bias,
+                                              int Cout, int Cin, int ng, int c, int tap, bool first) {
+    if (ng >= Cout) return 0.f;
+    const float sc = bn_scale(gamma, var, eps, ng);
+    if (bias && first) bias[ng] = bn_bias(gamma, beta, mean, sc, ng);
+    return w[(((long)ng * Cin + c) * 3 + tap / 3) * 3 + tap % 3] * sc;
+}
+#endif
+
 hipError_t launch_gemm_f32(const GemmArgs& a, hipStream_t s);
-// several independent fp32 convs in one grid (see igemm_f32.hip "Grouped launch"); n <= MAXG, every problem
+// several independent fp32 convs in one grid (see "Grouped launch" below); n <= MAXG, every problem
 // must satisfy gemm_f32_groupable()
 static constexpr int MAXG = 8;
+
+// =====================================================================================================
+// Grouped launch: up to MAXG independent convolutions (the branches of an HRNet module at the same depth,
+// the 1x1 / stride-2 convs of a fuse layer) share ONE grid.  A kernel per conv leaves the chip idle while
+// its last tiles drain and the next kernel's first tiles wait for their first loads (5-10 us out of ~50),
+// and separate streams overlap almost nothing because each kernel fills every CU; inside one grid the
+// block scheduler back-fills every freed slot at once and the problems' prologue / epilogue bursts
+// interleave.  Every conv family lays its grid out the same way, through the three functions below:
+// problems one after the other, longest K loop first (the 256-channel 8x8 branch has 8x the K loop of the
+// 32-channel 64x64 one), so that the launch does not end on them; each problem's range padded to a multiple
+// of 8 blocks, so that block b of a problem runs on XCD b % 8 and walks that XCD's contiguous eighth of the
+// tiles (neighbouring tiles share halo rows and, for several channel slices, the pixel tile in L2) -- the
+// XCD-contiguous tile order of the single-problem kernels, per problem.  The order and the padding are a
+// function of the problems alone: part of the promise that every schedule computes the same bits (capf.h).
+// Measured and rejected (igemm_bf16_group_ws_kernel): dealing the grid out in rounds, every problem in
+// proportion to its size, so that memory-bound (48-channel) and matrix-bound (384-channel) tiles are co-resident throughout:
+// HRNet-48 level at batch 256 224 -> 247 us, cfg2 14.39k -> 13.9k frames/s.
+// Also measured and rejected: two streams -- the matrix-bound problems longest first, the memory-bound 48-channel one dealt evenly
+// between them so that a CU's two slots hold one tile of each kind: 226 -> 228 us.  The tiles are bound by their own serial issue /
+// wait chains (SQ_WAIT_INST_ANY 35-40 %, SQ_WAIT_ANY 30-36 % of the wave-cycles with two waves per SIMD), not by a shared roof.
+// A family's kernel argument is {problems g[MAXG]; GroupLayout; its own per-problem fields; int n}.
+struct GroupLayout {
+    int start[MAXG + 1];   // first physical block of problem i (multiples of 8); start[n] = the grid size
+    int tiles[MAXG];       // real tiles of problem i; blocks beyond them are padding
+};
+// launch order: order[i] = list index of the i-th problem.  Stable insertion sort by cost, descending (ties keep list order)
+inline void group_order(int n, const double* cost, int* order) {
+    for (int i = 0; i < n; ++i) {
+        int j = i;
+        for (; j > 0 && cost[i] > cost[order[j - 1]]; --j) order[j] = order[j - 1];
+        order[j] = i;
+    }
+}
+// tiles[i] = tile count of the i-th problem IN LAUNCH ORDER; returns the grid size.  The unused slots n .. MAXG - 1 are empty
+// ranges at the end of the grid (no block looks at them: pi < n); a family's own fields there stay as value-initialisation left them
+inline int group_fill(GroupLayout& lay, int n, const int* tiles) {
+    int start = 0;
+    for (int i = 0; i < MAXG; ++i) {
+        lay.start[i] = start;
+        lay.tiles[i] = i < n ? tiles[i] : 0;
+        start += (lay.tiles[i] + 7) & ~7;
+    }
+    lay.start[MAXG] = start;
+    return start;
+}
+// ... both at once, for families whose tile counts do not depend on the order (tiles[], cost[] by list index)
+inline int group_layout(GroupLayout& lay, int n, const int* tiles, const double* cost, int* order) {
+    group_order(n, cost, order);
+    int sorted[MAXG];
+    for (int i = 0; i < n; ++i) sorted[i] = tiles[order[i]];
+    return group_fill(lay, n, sorted);
+}
+#if defined(__HIPCC__)
+// physical block b -> problem pi and its tile bid; live = false: a padding block.  (Takes the layout inside the kernel argument by
+// reference: the loads stay scalar kernarg loads)
+struct GroupSlot { int pi, bid; bool live; };
+__device__ __forceinline__ GroupSlot group_slot(const GroupLayout& lay, int n, int b) {
+    int pi = 0;
+    while (pi + 1 < n && b >= lay.start[pi + 1]) ++pi;                 // block-uniform
+    const int l = b - lay.start[pi];
+    const int per_xcd = (lay.start[pi + 1] - lay.start[pi]) >> 3;
+    const int bid = (l & 7) * per_xcd + (l >> 3);                      // XCD-contiguous tile order inside the problem
+    return GroupSlot{pi, bid, bid < lay.tiles[pi]};
+}
+#endif
+
+// What the three 2-D halo tiles (igemm_bf16_ws.hip, igemm_f32x3_ws.hip, igemm_f32h2_ws.hip) ask of a GemmArgs alike: a 3x3 / stride-1 /
+// pad-1 conv with plain row maps, no GELU, no row scale, output / residual rows in 16-byte pieces (align_mask: 7 bf16 or 3 fp32 elements)
+// and byte offsets below 2 GB over `rows` rows of elem_bytes elements (the whole tensor, or one tile's rows where the tile addresses
+// from per-tile bases).  Whether out_bf16 matters is the caller's: the fp32 tiles reject it, the bf16 tile does not look at it
+inline bool ws_args_ok(const GemmArgs& a, int align_mask, double elem_bytes, long rows) {
+    if (!a.conv || a.ks != 3 || a.stride != 1 || a.pad != 1 || a.Ho != a.H || a.Wo != a.W || a.act == ACT_GELU || a.rscale ||
+        a.omap.G != 1 || (a.res && a.rmap.G != 1) || a.M <= 0 || a.H <= 0 || a.W <= 0 || a.M % (a.H * a.W) != 0)
+        return false;
+    if ((a.omap.S1 & align_mask) || (a.omap.off & align_mask) || (a.res && ((a.rmap.S1 & align_mask) || (a.rmap.off & align_mask)))) return false;
+    return (double)rows * (double)a.omap.S1 * elem_bytes < 2.0e9 && (!a.res || (double)rows * (double)a.rmap.S1 * elem_bytes < 2.0e9);
+}
 bool gemm_f32_groupable(const GemmArgs& a);
 bool gemm_f32_rows_splitk(const GemmArgs& a);        // rows-mode GEMM that launch_gemm_f32 splits along K (few tiles, long K, scratch lent)
 hipError_t launch_gemm_f32_group(const GemmArgs* list, int n, hipStream_t s);
@@ -289,6 +395,9 @@ hipError_t launch_pack_conv_f32h2(const float* w, const float* gamma, const floa
 // (igemm_f32h2.hip): the A tile is staged as fp32 exactly as igemm_f32.hip stages it and split by the wave that consumes it (scale per wave,
 // 32 rows and 32-deep chunk); weights packed by launch_pack_f32h2_gemm over the fp32 pack's geometry (GemmArgs::Wh2)
 long f32h2_gemm_pack_elems(int N, int Kpad);            // floats
+// the power-of-two channel scales of both two-piece packs: winv[n] = 1 / t with max_k |w[n][k] * bn_scale| t in [2^14, 2^15) for the rows
+// n < N of w [N][K], 1 for the rows N <= n < rows (one launch, one block per row)
+hipError_t launch_f32h2_wscale(const float* w, const float* gamma, const float* var, float eps, float* winv, int rows, int N, int K, hipStream_t s);
 bool gemm_f32h2g_ok(const GemmArgs& a);
 hipError_t launch_gemm_f32h2g(const GemmArgs& a, hipStream_t s);
 hipError_t launch_gemm_f32h2g_group(const GemmArgs* list, int n, hipStream_t s);     // convs with plain row maps, one grid

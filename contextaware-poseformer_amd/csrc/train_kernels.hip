@@ -405,14 +405,14 @@ __global__ void gelu_bwd_kernel(const float* __restrict__ x, const float* __rest
 }
 
 hipError_t launch_gelu_fwd(const float* x, float* y, long n, hipStream_t s) {
-    const long n4 = n / 4, want = (n4 + 255) / 256;
-    hipLaunchKernelGGL(gelu_fwd_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, x, y, n4);
+    const long n4 = n / 4;
+    hipLaunchKernelGGL(gelu_fwd_kernel, dim3(grid_1d(n4)), dim3(256), 0, s, x, y, n4);
     return hipGetLastError();
 }
 
 hipError_t launch_gelu_bwd(const float* x, const float* dy, float* dx, long n, hipStream_t s) {
-    const long n4 = n / 4, want = (n4 + 255) / 256;
-    hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, x, dy, dx, n4);
+    const long n4 = n / 4;
+    hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_1d(n4)), dim3(256), 0, s, x, dy, dx, n4);
     return hipGetLastError();
 }
 
@@ -987,8 +987,7 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 hipError_t launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                         float wd, int step, hipStream_t s, float gscale) {
     const float bc1 = 1.0f - powf(b1, (float)step), bc2s = sqrtf(1.0f - powf(b2, (float)step));
-    const long want = (n + 255) / 256;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2,
+    hipLaunchKernelGGL(adamw_kernel, dim3(grid_1d(n)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2,
                        eps, wd, bc1, bc2s, gscale);
     return hipGetLastError();
 }
@@ -1005,8 +1004,7 @@ __global__ void scale_rows_kernel(const float* __restrict__ src, RowMap smap, co
 
 hipError_t launch_scale_rows(const float* src, RowMap smap, const float* scale, int div, float* dst, int rows, int C,
                              hipStream_t s) {
-    const long want = ((long)rows * C + 255) / 256;
-    hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, src, smap, scale, div,
+    hipLaunchKernelGGL(scale_rows_kernel, dim3(grid_1d((long)rows * C)), dim3(256), 0, s, src, smap, scale, div,
                        dst, rows, C);
     return hipGetLastError();
 }
@@ -1023,8 +1021,7 @@ __global__ void head_dgrad_kernel(const float* __restrict__ dOut, const float* _
 }
 
 hipError_t launch_head_dgrad(const float* dOut, const float* W, float* dY, int rows, int C, int NO, hipStream_t s) {
-    const long want = ((long)rows * C + 255) / 256;
-    hipLaunchKernelGGL(head_dgrad_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, dOut, W, dY, rows, C, NO);
+    hipLaunchKernelGGL(head_dgrad_kernel, dim3(grid_1d((long)rows * C)), dim3(256), 0, s, dOut, W, dY, rows, C, NO);
     return hipGetLastError();
 }
 

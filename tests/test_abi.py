@@ -355,7 +355,8 @@ def test_integration_stub_struct_matches_the_header_and_the_binding():
 def test_hot_kernels_do_not_spill_registers():
     """Build guard: a spilling MFMA kernel still produces right answers, 5-8x slower (scratch traffic and slow dispatch) --
     the grouped bf16 kernel once went from 16600 to 2000 frames/s that way.  Compile the conv / GEMM sources to assembly for
-    gfx950 and require vgpr_spill_count == 0 for every kernel."""
+    gfx950 and require vgpr_spill_count == 0 for every kernel.  (Not in the list: igemm_bf16_ws -- igemm_bf16_group_ws_kernel reports
+    vgpr_count 256, vgpr_spill_count 17, 52 bytes of scratch with this toolchain; known, and to be fixed on its own.)"""
     import concurrent.futures, re, shutil, subprocess, tempfile
     hipcc = shutil.which("hipcc")
     if hipcc is None:
@@ -375,7 +376,8 @@ def test_hot_kernels_do_not_spill_registers():
         return [(n, c) for n, c in zip(names, counts) if c]
 
     with concurrent.futures.ThreadPoolExecutor(4) as ex:
-        bad = sum(ex.map(spills, ["igemm_bf16", "igemm_f32", "igemm_f32_pw", "igemm_f32_pwchain", "igemm_bf16_pwchain", "igemm_wino"]), [])
+        bad = sum(ex.map(spills, ["igemm_bf16", "igemm_f32", "igemm_f32_pw", "igemm_f32_pwchain", "igemm_bf16_pwchain", "igemm_wino",
+                                  "igemm_f32x3_ws", "igemm_f32h2_ws", "igemm_f32h2"]), [])
     assert not bad, f"kernels with register spills: {bad}"
 
 
