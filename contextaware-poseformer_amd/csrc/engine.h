@@ -69,6 +69,28 @@ struct Pack {
                                    // max_batch): not packed, no arena space; the conv never runs a Winograd kernel (build())
 };
 
+// The lifter's layers (pose_dformer.py:144-241), resolved once where build_lifter registers the schema: parameter indices and shapes.
+// The ONE place the layer list lives -- the plan (plan.cpp) and the training step (train.cpp) read it, neither builds a parameter name
+struct LinearRef { int w = -1, b = -1, N = 0, K = 0; };   // nn.Linear: weight [N][K], bias [N]
+struct LnRef { int w = -1, b = -1; };                      // nn.LayerNorm
+struct LifterMlp { LnRef norm2; LinearRef fc1, fc2; };    // the MLP half of any block: x + fc2(gelu(fc1(norm2(x))))
+struct LifterAtt { LnRef norm1; LinearRef qkv, proj; LifterMlp mlp; };
+struct LifterCtx {
+    LnRef norm1;
+    LinearRef aw, so, embed_proj[4];     // attention_weights, sampling_offsets, embed_proj.l
+    LifterMlp mlp;
+    int ao_pack = -1;                    // pack of [attention_weights | sampling_offsets] in the row layout (the training step's GEMMs)
+    int tap_pos = -1, tap_idx = -1;      // debug tap buffers (sampling positions, NW corner indices)
+};
+struct LifterSchema {
+    int pos = -1;                        // Spatial_pos_embed
+    LinearRef coord, feat_embed[4];
+    LifterAtt res[8], joint[8];          // (depth <= 8 of each)
+    LifterCtx ctx[4];                    // (levels of them; none with context_blocks = 0)
+    LnRef head_ln;
+    LinearRef head;
+};
+
 enum OpKind {
     OP_GEMM = 0, OP_FUSE, OP_MAXPOOL, OP_RESIZE, OP_PREP_EMBED, OP_SAMPLE_REF, OP_LAYERNORM, OP_DEFORM,
     OP_ATTENTION, OP_HEAD, OP_FORK, OP_JOIN, OP_EMBED, OP_CTX_ATTN, OP_RES_CHAIN, OP_MLP_CHAIN
@@ -99,7 +121,7 @@ struct Op {
     int outs[4] = {-1, -1, -1, -1};
     int idxs[4] = {-1, -1, -1, -1};          // OP_EMBED: corner-index tap buffers
     int pq[4] = {-1, -1, -1, -1};   // ... and their quad-interleaved packs
-    int pw[4] = {-1, -1, -1, -1}, pb[4] = {-1, -1, -1, -1};   // per-level linear parameters (OP_EMBED feat_embed, OP_CTX_ATTN embed_proj)
+    int pb[4] = {-1, -1, -1, -1};   // per-level bias parameters (OP_EMBED feat_embed, OP_CTX_ATTN embed_proj)
     int ln_w = -1, ln_b = -1;                // OP_GEMM rows mode: LayerNorm the A rows on the fly (parameter indices), eps in `eps`
     double flops_per_frame = 0.0;
     int bf16 = 0;                 // tensors of this op are bf16 (conv: bf16 MFMA kernel)
@@ -131,8 +153,9 @@ struct NamedTensor {
 
 // float offsets inside the training region of the workspace (train.cpp :: Engine::train_layout)
 struct TrainLayout {
-    struct Ctx { size_t xh1, rs1, y1, ao, U[4], xh2, rs2, y2, hp, hg; };
-    struct Att { size_t xh1, rs1, y1, qkv, o, xh2, rs2, y2, hp, hg; };
+    struct Mlp { size_t xh2, rs2, y2, hp, hg; };   // what the MLP half of a block keeps: LayerNorm x-hat / rstd / output, fc1 output, its GELU
+    struct Ctx { size_t xh1, rs1, y1, ao, U[4]; Mlp mlp; };
+    struct Att { size_t xh1, rs1, y1, qkv, o; Mlp mlp; };
     size_t X, S[4];
     Ctx ctx[4];                              // (one per context block: levels of them)
     Att res[8], joint[8];                    // (one per block of each group: depth <= 8 of them)
@@ -263,8 +286,7 @@ struct Engine {
 
     // ---- training step (train.cpp)
     int feat_buf[4] = {-1, -1, -1, -1}, feat_H[4] = {0, 0, 0, 0}, feat_W[4] = {0, 0, 0, 0}, feat_C[4] = {0, 0, 0, 0};
-    std::vector<int> ctx_ao_pack;        // pack index of [attention_weights | sampling_offsets] per context block
-    std::vector<int> ctx_tap_pos, ctx_tap_idx;   // per context block: debug tap buffers (sampling positions, NW corner indices)
+    LifterSchema lifter;                 // the lifter's layers as parameter indices (filled by build_lifter)
     std::vector<long> grad_off;          // per parameter: offset in the flat lifter gradient, -1 for the backbone
     long grad_elems = 0;
     int train_batch = 0;                 // batch of the forward_train whose activations are still in the workspace (0: none)

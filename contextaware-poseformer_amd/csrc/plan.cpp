@@ -490,12 +490,6 @@ void Engine::build_cpn(Tensor img, Tensor feats[4]) {
 // ---------------------------------------------------------------------------------------------------
 // lifter (pose_dformer.py)
 // ---------------------------------------------------------------------------------------------------
-static int pidx(Engine& e, const std::string& n) { return e.param_index.at(n); }
-
-struct LinearRef {
-    int w, b, N, K;
-};
-
 static LinearRef reg_linear(Engine& e, const std::string& p, int N, int K) {
     LinearRef r;
     r.w = e.add_param(p + ".weight", CAPF_P_LIN_W, {N, K});
@@ -505,22 +499,23 @@ static LinearRef reg_linear(Engine& e, const std::string& p, int N, int K) {
     return r;
 }
 
-static void reg_ln(Engine& e, const std::string& p, int C) {
-    e.add_param(p + ".weight", CAPF_P_LN_W, {C});
-    e.add_param(p + ".bias", CAPF_P_LN_B, {C});
+static LnRef reg_ln(Engine& e, const std::string& p, int C) {
+    LnRef r;
+    r.w = e.add_param(p + ".weight", CAPF_P_LN_W, {C});
+    r.b = e.add_param(p + ".bias", CAPF_P_LN_B, {C});
+    return r;
 }
 
-static int make_linear_pack(Engine& e, const std::vector<std::string>& names, bool as_bf16 = false, bool quad = false) {
+static int make_linear_pack(Engine& e, std::initializer_list<LinearRef> lins, bool as_bf16 = false, bool quad = false) {
     Pack pk;
     pk.kind = 1;
     pk.quad = quad;
-    pk.n_lin = (int)names.size();
     int N = 0, K = 0;
-    for (int i = 0; i < pk.n_lin; ++i) {
-        pk.w[i] = pidx(e, names[i] + ".weight");
-        pk.b[i] = pidx(e, names[i] + ".bias");
-        N += (int)e.params[pk.w[i]].shape[0];
-        K = (int)e.params[pk.w[i]].shape[1];
+    for (const LinearRef& r : lins) {
+        pk.w[pk.n_lin] = r.w;
+        pk.b[pk.n_lin++] = r.b;
+        N += r.N;
+        K = r.K;
     }
     pk.N = N;
     pk.K = K;
@@ -537,8 +532,7 @@ static int make_linear_pack(Engine& e, const std::vector<std::string>& names, bo
 
 // rows-mode GEMM:  out[omap(m) + n] = act(A[amap(m)] . W[n] + b[n] + res[rmap(m) + n])
 static void gemm_rows(Engine& e, const std::string& name, int pack, int a_buf, RowMap amap, long rows_pf, int out_buf,
-                      RowMap omap, int act, int res_buf, RowMap rmap, int res_param = -1, const std::string& ln = "",
-                      float ln_eps = 0.f) {
+                      RowMap omap, int act, int res_buf, RowMap rmap, int res_param = -1, LnRef ln = LnRef{}, float ln_eps = 0.f) {
     const Pack& pk = e.packs[pack];
     Op op;
     op.kind = OP_GEMM;
@@ -554,9 +548,9 @@ static void gemm_rows(Engine& e, const std::string& name, int pack, int a_buf, R
     op.aux = res_buf;
     op.rmap = rmap;
     op.res_param = res_param;
-    if (!ln.empty()) {                       // LayerNorm(A rows) folded into the GEMM's fragment path (igemm_f32.hip, LNA)
-        op.ln_w = pidx(e, ln + ".weight");
-        op.ln_b = pidx(e, ln + ".bias");
+    if (ln.w >= 0) {                         // LayerNorm(A rows) folded into the GEMM's fragment path (igemm_f32.hip, LNA)
+        op.ln_w = ln.w;
+        op.ln_b = ln.b;
         op.eps = ln_eps;
     }
     op.flops_per_frame = 2.0 * rows_pf * (double)pk.N * pk.K;
@@ -570,7 +564,7 @@ static void gemm_rows(Engine& e, const std::string& name, int pack, int a_buf, R
     e.push(op);
 }
 
-static void layernorm(Engine& e, const std::string& name, const std::string& ln, float eps, int in_buf, RowMap imap,
+static void layernorm(Engine& e, const std::string& name, LnRef ln, float eps, int in_buf, RowMap imap,
                       int add_buf, RowMap amap, int out_buf, long rows_pf, int C, bool out_bf16 = false) {
     Op op;
     op.kind = OP_LAYERNORM;
@@ -580,8 +574,8 @@ static void layernorm(Engine& e, const std::string& name, const std::string& ln,
     op.aux = add_buf;
     op.rmap = amap;
     op.out = out_buf;
-    op.p0 = pidx(e, ln + ".weight");
-    op.p1 = pidx(e, ln + ".bias");
+    op.p0 = ln.w;
+    op.p1 = ln.b;
     op.eps = eps;
     op.rows_per_frame = rows_pf;
     op.C = C;
@@ -613,35 +607,44 @@ void Engine::build_lifter(const Tensor feats[4]) {
     int Cl[4];
     for (int l = 0; l < L; ++l) Cl[l] = feats[l].C;
 
-    // ---- schema, in the reference's registration order (pose_dformer.py:174-208)
-    const int pos = add_param(V + ".Spatial_pos_embed", CAPF_P_RAW, {1, L1, J, C});
-    reg_linear(*this, V + ".coord_embed", C, 2);
-    for (int l = 0; l < L; ++l) reg_linear(*this, V + ".feat_embed." + std::to_string(l), C, Cl[l]);
-    auto reg_block = [&](const std::string& p, int dim) {
-        reg_ln(*this, p + ".norm1", dim);
-        reg_linear(*this, p + ".attn.qkv", 3 * dim, dim);
-        reg_linear(*this, p + ".attn.proj", dim, dim);
-        reg_ln(*this, p + ".norm2", dim);
-        reg_linear(*this, p + ".mlp.fc1", 2 * dim, dim);
-        reg_linear(*this, p + ".mlp.fc2", dim, 2 * dim);
+    // ---- schema, in the reference's registration order (pose_dformer.py:174-208), resolved into `lifter`: the only place that spells the
+    // lifter's parameter names -- everything below, and the training step (train.cpp), goes by the indices kept here
+    LifterSchema& net = lifter;
+    net = LifterSchema{};
+    net.pos = add_param(V + ".Spatial_pos_embed", CAPF_P_RAW, {1, L1, J, C});
+    net.coord = reg_linear(*this, V + ".coord_embed", C, 2);
+    for (int l = 0; l < L; ++l) net.feat_embed[l] = reg_linear(*this, V + ".feat_embed." + std::to_string(l), C, Cl[l]);
+    auto reg_mlp = [&](const std::string& p, int dim) {
+        LifterMlp m;
+        m.norm2 = reg_ln(*this, p + ".norm2", dim);
+        m.fc1 = reg_linear(*this, p + ".mlp.fc1", 2 * dim, dim);
+        m.fc2 = reg_linear(*this, p + ".mlp.fc2", dim, 2 * dim);
+        return m;
     };
-    const int DEP = cfg.depth > 0 ? cfg.depth : L;         // blocks per group (ContextPose_mpi pose_dformer.py:199)
-    for (int i = 0; i < DEP; ++i) reg_block(V + ".joint_blocks." + std::to_string(i), D);
-    for (int i = 0; i < DEP; ++i) reg_block(V + ".res_blocks." + std::to_string(i), C);
+    auto reg_block = [&](const std::string& p, int dim) {
+        LifterAtt a;
+        a.norm1 = reg_ln(*this, p + ".norm1", dim);
+        a.qkv = reg_linear(*this, p + ".attn.qkv", 3 * dim, dim);
+        a.proj = reg_linear(*this, p + ".attn.proj", dim, dim);
+        a.mlp = reg_mlp(p, dim);
+        return a;
+    };
+    const int DEP = depth();                               // blocks per group (ContextPose_mpi pose_dformer.py:199)
+    for (int i = 0; i < DEP; ++i) net.joint[i] = reg_block(V + ".joint_blocks." + std::to_string(i), D);
+    for (int i = 0; i < DEP; ++i) net.res[i] = reg_block(V + ".res_blocks." + std::to_string(i), C);
     if (cfg.context_blocks) {
         for (int i = 0; i < L; ++i) {
             const std::string p = V + ".context_blocks." + std::to_string(i);
-            reg_ln(*this, p + ".norm1", C);
-            reg_linear(*this, p + ".attention_weights", NH * NS, C);
-            reg_linear(*this, p + ".sampling_offsets", 2 * NH * NS, C);
-            for (int l = 0; l < L; ++l) reg_linear(*this, p + ".embed_proj." + std::to_string(l), HD, Cl[l]);
-            reg_ln(*this, p + ".norm2", C);
-            reg_linear(*this, p + ".mlp.fc1", 2 * C, C);
-            reg_linear(*this, p + ".mlp.fc2", C, 2 * C);
+            LifterCtx& c = net.ctx[i];
+            c.norm1 = reg_ln(*this, p + ".norm1", C);
+            c.aw = reg_linear(*this, p + ".attention_weights", NH * NS, C);
+            c.so = reg_linear(*this, p + ".sampling_offsets", 2 * NH * NS, C);
+            for (int l = 0; l < L; ++l) c.embed_proj[l] = reg_linear(*this, p + ".embed_proj." + std::to_string(l), HD, Cl[l]);
+            c.mlp = reg_mlp(p, C);
         }
     }
-    reg_ln(*this, V + ".head.0", D);
-    reg_linear(*this, V + ".head.1", 3, D);
+    net.head_ln = reg_ln(*this, V + ".head.0", D);
+    net.head = reg_linear(*this, V + ".head.1", 3, D);
 
     // ---- buffers (per frame)
     const int X = new_buffer((size_t)J * D, "tokens");            // [J, L1, C]  ("b p l c")
@@ -661,14 +664,49 @@ void Engine::build_lifter(const Tensor feats[4]) {
     const bool lb = bf16() && !(cfg.plan_flags & CAPF_PLAN_LIFTER_FP32);
     auto ln_fold_ok = [&](int dim) { return fused_lifter && dim <= 256 && !lb; };
     const bool ln_fold = ln_fold_ok(C);
+    // the MLP half of a block on the rows `xm` of X, x += fc2(gelu(fc1(norm2(x)))), in the form the caller chose: one launch (lifter_chain.hip,
+    // ATTN = false), else norm2 folded into fc1, else a LayerNorm launch in front of fc1.  fc1 and fc2 get their packs in this order in every form
+    auto mlp_half = [&](const LifterMlp& m, const std::string& n, RowMap xm, long rows_pf, int dim, float eps, bool chain, bool ln_fold) {
+        if (chain) {
+            Op op;
+            op.kind = OP_MLP_CHAIN;
+            op.name = n + ".mlp";
+            op.in[0] = X;
+            op.out = X;
+            op.amap = xm;
+            op.C = dim;
+            op.eps = eps;
+            op.rows_per_frame = rows_pf;
+            for (const LinearRef& lin : {m.fc1, m.fc2}) {
+                op.chain.push_back(make_linear_pack(*this, {lin}));
+                packs.back().chain = true;
+            }
+            op.chain.push_back(m.norm2.w);
+            op.chain.push_back(m.norm2.b);
+            op.flops_per_frame = 2.0 * rows_pf * (double)dim * (2 * dim + 2 * dim);
+            use(X);
+            push(op);
+            has_res_chain = true;
+            return;
+        }
+        if (ln_fold) {
+            gemm_rows(*this, n + ".fc1", make_linear_pack(*this, {m.fc1}), X, xm, rows_pf, Hb, row_ld(2 * dim), ACT_GELU, -1, row_ld(0), -1,
+                      m.norm2, eps);
+        } else {
+            layernorm(*this, n + ".norm2", m.norm2, eps, X, xm, -1, row_ld(0), Q, rows_pf, dim, lb);
+            gemm_rows(*this, n + ".fc1", make_linear_pack(*this, {m.fc1}, lb), Q, row_ld(dim), rows_pf, Hb, row_ld(2 * dim), ACT_GELU, -1,
+                      row_ld(0));
+        }
+        gemm_rows(*this, n + ".fc2", make_linear_pack(*this, {m.fc2}, lb), Hb, row_ld(2 * dim), rows_pf, X, xm, ACT_NONE, X, xm);
+    };
     if (fused_lifter) {
         Op op;
         op.kind = OP_EMBED;
         op.name = "embed";
         op.out = X;
-        op.p0 = pidx(*this, V + ".coord_embed.weight");
-        op.p1 = pidx(*this, V + ".coord_embed.bias");
-        op.p2 = pos;
+        op.p0 = net.coord.w;
+        op.p1 = net.coord.b;
+        op.p2 = net.pos;
         op.i0 = J; op.i1 = L; op.i2 = L1; op.C = C;
         op.bf16 = bf16() ? 1 : 0;
         op.feat_bf16 = maps_bf16() ? 1 : 0;
@@ -678,9 +716,8 @@ void Engine::build_lifter(const Tensor feats[4]) {
             op.in[l] = feats[l].buf;
             op.lvlH[l] = feats[l].H; op.lvlW[l] = feats[l].W; op.lvlC[l] = Cl[l];
             use(feats[l].buf);
-            op.pw[l] = pidx(*this, V + ".feat_embed." + ls + ".weight");
-            op.pb[l] = pidx(*this, V + ".feat_embed." + ls + ".bias");
-            op.pq[l] = make_linear_pack(*this, {V + ".feat_embed." + ls}, false, true);
+            op.pb[l] = net.feat_embed[l].b;
+            op.pq[l] = make_linear_pack(*this, {net.feat_embed[l]}, false, true);
             op.outs[l] = new_buffer((size_t)J * Cl[l], "sampled" + ls);
             op.idxs[l] = new_buffer((size_t)J * 2, "idx" + ls);
             name_tensor(*this, "sampled" + ls, op.outs[l], {-1, J, Cl[l]});
@@ -694,9 +731,9 @@ void Engine::build_lifter(const Tensor feats[4]) {
         op.kind = OP_PREP_EMBED;
         op.name = "prep_embed";
         op.out = X;
-        op.p0 = pidx(*this, V + ".coord_embed.weight");
-        op.p1 = pidx(*this, V + ".coord_embed.bias");
-        op.p2 = pos;
+        op.p0 = net.coord.w;
+        op.p1 = net.coord.b;
+        op.p2 = net.pos;
         op.i0 = J; op.i1 = L1; op.C = C;
         use(X);
         push(op);
@@ -718,10 +755,10 @@ void Engine::build_lifter(const Tensor feats[4]) {
         push(op);
         name_tensor(*this, "sampled" + ls, S, {-1, J, Cl[l]});
         name_tensor(*this, "idx" + ls, I, {-1, J, 2}, 1);
-        const int pk = make_linear_pack(*this, {V + ".feat_embed." + ls});
+        const int pk = make_linear_pack(*this, {net.feat_embed[l]});
         // out X[b,p,1+l,:] = S W^T + b + pos[0,1+l,p,:]
         gemm_rows(*this, "feat_embed." + ls, pk, S, row_ld(Cl[l]), J, X, row_ld(D, (long)(1 + l) * C), ACT_NONE, -1,
-                  RowMap{J, 0, C, (long)(1 + l) * J * C}, pos);
+                  RowMap{J, 0, C, (long)(1 + l) * J * C}, net.pos);
     }
     }
 
@@ -737,34 +774,30 @@ void Engine::build_lifter(const Tensor feats[4]) {
         const RowMap tok{L, D, C, C};           // row (b,p,l') -> X[b,p,1+l',:]
         const RowMap tok0{L, D, 0, 0};          // row (b,p,l') -> X[b,p,0,:]
         for (int i = 0; i < L; ++i) {
-            const std::string p = V + ".context_blocks." + std::to_string(i);
+            LifterCtx& c = net.ctx[i];
             const std::string n = "ctx" + std::to_string(i);
-            const int pk_ao = make_linear_pack(*this, {p + ".attention_weights", p + ".sampling_offsets"});
-            ctx_ao_pack.push_back(pk_ao);                   // (row layout: the training step's GEMMs, train.cpp)
+            const int pk_ao = c.ao_pack = make_linear_pack(*this, {c.aw, c.so});   // (row layout: the training step's GEMMs, train.cpp)
             // debug taps of the border-mode sampling site (pose_dformer.py:126-128): positions and NW corner indices
-            const int tap_pos = new_buffer((size_t)J * L * NH * NS * 2, "cpos" + std::to_string(i));
-            const int tap_idx = new_buffer((size_t)J * L * NH * NS * 2, "cidx" + std::to_string(i));
+            const int tap_pos = c.tap_pos = new_buffer((size_t)J * L * NH * NS * 2, "cpos" + std::to_string(i));
+            const int tap_idx = c.tap_idx = new_buffer((size_t)J * L * NH * NS * 2, "cidx" + std::to_string(i));
             name_tensor(*this, "cpos" + std::to_string(i), tap_pos, {-1, J, L * NH * NS, 2});
             name_tensor(*this, "cidx" + std::to_string(i), tap_idx, {-1, J, L * NH * NS, 2}, 1);
-            ctx_tap_pos.push_back(tap_pos);
-            ctx_tap_idx.push_back(tap_idx);
             if (fused_lifter) {
                 Op op;
                 op.kind = OP_CTX_ATTN;
                 op.name = n + ".attn";
-                op.pack = make_linear_pack(*this, {p + ".attention_weights", p + ".sampling_offsets"}, false, true);
+                op.pack = make_linear_pack(*this, {c.aw, c.so}, false, true);
                 op.out = X;
                 use(X);
-                op.p0 = pidx(*this, p + ".norm1.weight");
-                op.p1 = pidx(*this, p + ".norm1.bias");
+                op.p0 = c.norm1.w;
+                op.p1 = c.norm1.b;
                 op.eps = 1e-5f;
                 for (int l = 0; l < L; ++l) {
                     op.in[l] = feats[l].buf;
                     op.lvlH[l] = feats[l].H; op.lvlW[l] = feats[l].W; op.lvlC[l] = Cl[l];
                     use(feats[l].buf);
-                    op.pw[l] = pidx(*this, p + ".embed_proj." + std::to_string(l) + ".weight");
-                    op.pb[l] = pidx(*this, p + ".embed_proj." + std::to_string(l) + ".bias");
-                    op.pq[l] = make_linear_pack(*this, {p + ".embed_proj." + std::to_string(l)}, false, true);
+                    op.pb[l] = c.embed_proj[l].b;
+                    op.pq[l] = make_linear_pack(*this, {c.embed_proj[l]}, false, true);
                     op.outs[l] = U[l];           // (the sample sums cross HBM to the embed_proj launch: lifter_fused.hip ctx_proj_kernel)
                     use(U[l]);
                     op.flops_per_frame += 2.0 * J * NH * (double)HD * Cl[l];
@@ -776,7 +809,7 @@ void Engine::build_lifter(const Tensor feats[4]) {
                 op.idxs[0] = tap_pos; op.idxs[1] = tap_idx;
                 push(op);
             } else {
-            layernorm(*this, n + ".norm1", p + ".norm1", 1e-5f, X, tok, X, tok0, Q, (long)J * L, C);
+            layernorm(*this, n + ".norm1", c.norm1, 1e-5f, X, tok, X, tok0, Q, (long)J * L, C);
             gemm_rows(*this, n + ".attn_off", pk_ao, Q, row_ld(C), (long)J * L, AO, row_ld(3 * NH * NS), ACT_NONE, -1,
                       row_ld(0));
             {
@@ -799,54 +832,23 @@ void Engine::build_lifter(const Tensor feats[4]) {
                 push(op);
             }
             for (int l = 0; l < L; ++l) {
-                const int pk = make_linear_pack(*this, {p + ".embed_proj." + std::to_string(l)});
+                const int pk = make_linear_pack(*this, {c.embed_proj[l]});
                 const RowMap dst{NH, D, HD, (long)(1 + l) * C};    // row (b,p,h) -> X[b,p,1+l,h*HD:]
                 gemm_rows(*this, n + ".embed_proj." + std::to_string(l), pk, U[l], row_ld(Cl[l]), (long)J * NH, X, dst,
                           ACT_NONE, X, dst);
             }
             }
-            if (fused_lifter && use_h2g && !lb && !bf16() && res_chain_ok(C, 5, 8, 1)) {
-                // the MLP half as one launch on the context tokens' rows (lifter_chain.hip, ATTN = false): norm2 -> fc1 + GELU -> fc2 + x
-                Op op;
-                op.kind = OP_MLP_CHAIN;
-                op.name = n + ".mlp";
-                op.in[0] = X;
-                op.out = X;
-                op.amap = tok;
-                op.C = C;
-                op.eps = 1e-5f;
-                op.rows_per_frame = (long)J * L;
-                for (const char* lin : {".mlp.fc1", ".mlp.fc2"}) {
-                    op.chain.push_back(make_linear_pack(*this, {p + lin}));
-                    packs.back().chain = true;
-                }
-                op.chain.push_back(pidx(*this, p + ".norm2.weight"));
-                op.chain.push_back(pidx(*this, p + ".norm2.bias"));
-                op.flops_per_frame = 2.0 * J * L * (double)C * (2 * C + 2 * C);
-                use(X);
-                push(op);
-                has_res_chain = true;
-                continue;
-            }
-            if (ln_fold) {
-                gemm_rows(*this, n + ".fc1", make_linear_pack(*this, {p + ".mlp.fc1"}), X, tok, (long)J * L, Hb,
-                          row_ld(2 * C), ACT_GELU, -1, row_ld(0), -1, p + ".norm2", 1e-5f);
-            } else {
-                layernorm(*this, n + ".norm2", p + ".norm2", 1e-5f, X, tok, -1, row_ld(0), Q, (long)J * L, C, lb);
-                gemm_rows(*this, n + ".fc1", make_linear_pack(*this, {p + ".mlp.fc1"}, lb), Q, row_ld(C), (long)J * L, Hb,
-                          row_ld(2 * C), ACT_GELU, -1, row_ld(0));
-            }
-            gemm_rows(*this, n + ".fc2", make_linear_pack(*this, {p + ".mlp.fc2"}, lb), Hb, row_ld(2 * C), (long)J * L, X, tok,
-                      ACT_NONE, X, tok);
+            // the MLP half as one launch on the context tokens' rows where the chain kernel takes the width
+            const bool mlp_chain = fused_lifter && use_h2g && !lb && !bf16() && res_chain_ok(C, 5, 8, 1);
+            mlp_half(c.mlp, n, tok, (long)J * L, C, 1e-5f, mlp_chain, ln_fold);
         }
     }
     debug_copy(*this, "tok_ctx", X, (size_t)J * D, {-1, J, L1, C});
 
     // ---- Block x L over the L1 level-tokens of each joint, then over the J joint tokens (:231-238)
-    auto attn_blocks = [&](const std::string& group, const std::string& tag, int dim, long rows_pf, int tokens,
-                           int groups_pf) {
+    auto attn_blocks = [&](const LifterAtt* blocks, const std::string& tag, int dim, long rows_pf, int tokens, int groups_pf) {
         const bool ln_fold = ln_fold_ok(dim);
-        const int nblk = cfg.depth > 0 ? cfg.depth : L;
+        const int nblk = DEP;
         // the res blocks (tokens of ONE joint, 128 wide) as one launch: a workgroup takes 6 joints through every block without leaving
         // the CU (lifter_chain.hip); fp32 lifter on the two-piece packs only -- the bf16 plan and CAPF_PLAN_NO_FUSED_LIFTER /
         // CAPF_PLAN_NO_F32H2_GEMM keep one launch per op
@@ -860,12 +862,12 @@ void Engine::build_lifter(const Tensor feats[4]) {
             op.eps = 1e-6f;
             op.rows_per_frame = rows_pf;
             for (int i = 0; i < nblk; ++i) {
-                const std::string p = V + "." + group + "." + std::to_string(i);
-                for (const char* lin : {".attn.qkv", ".attn.proj", ".mlp.fc1", ".mlp.fc2"}) {
-                    op.chain.push_back(make_linear_pack(*this, {p + lin}));
+                const LifterAtt& a = blocks[i];
+                for (const LinearRef& lin : {a.qkv, a.proj, a.mlp.fc1, a.mlp.fc2}) {
+                    op.chain.push_back(make_linear_pack(*this, {lin}));
                     packs.back().chain = true;
                 }
-                for (const char* ln : {".norm1.weight", ".norm1.bias", ".norm2.weight", ".norm2.bias"}) op.chain.push_back(pidx(*this, p + ln));
+                for (int ln : {a.norm1.w, a.norm1.b, a.mlp.norm2.w, a.mlp.norm2.b}) op.chain.push_back(ln);
                 op.flops_per_frame += 2.0 * rows_pf * (double)dim * (3 * dim + dim + 2 * dim + 2 * dim) + 4.0 * groups_pf * tokens * tokens * dim;
             }
             use(X);
@@ -874,14 +876,14 @@ void Engine::build_lifter(const Tensor feats[4]) {
             return;
         }
         for (int i = 0; i < nblk; ++i) {
-            const std::string p = V + "." + group + "." + std::to_string(i);
+            const LifterAtt& a = blocks[i];
             const std::string n = tag + std::to_string(i);
             if (ln_fold) {
-                gemm_rows(*this, n + ".qkv", make_linear_pack(*this, {p + ".attn.qkv"}), X, row_ld(dim), rows_pf, QKV,
-                          row_ld(3 * dim), ACT_NONE, -1, row_ld(0), -1, p + ".norm1", 1e-6f);
+                gemm_rows(*this, n + ".qkv", make_linear_pack(*this, {a.qkv}), X, row_ld(dim), rows_pf, QKV,
+                          row_ld(3 * dim), ACT_NONE, -1, row_ld(0), -1, a.norm1, 1e-6f);
             } else {
-                layernorm(*this, n + ".norm1", p + ".norm1", 1e-6f, X, row_ld(dim), -1, row_ld(0), Q, rows_pf, dim, lb);
-                gemm_rows(*this, n + ".qkv", make_linear_pack(*this, {p + ".attn.qkv"}, lb), Q, row_ld(dim), rows_pf, QKV,
+                layernorm(*this, n + ".norm1", a.norm1, 1e-6f, X, row_ld(dim), -1, row_ld(0), Q, rows_pf, dim, lb);
+                gemm_rows(*this, n + ".qkv", make_linear_pack(*this, {a.qkv}, lb), Q, row_ld(dim), rows_pf, QKV,
                           row_ld(3 * dim), ACT_NONE, -1, row_ld(0));
             }
             {
@@ -896,23 +898,14 @@ void Engine::build_lifter(const Tensor feats[4]) {
                 use(QKV); use(O);
                 push(op);
             }
-            gemm_rows(*this, n + ".proj", make_linear_pack(*this, {p + ".attn.proj"}, lb), O, row_ld(dim), rows_pf, X,
+            gemm_rows(*this, n + ".proj", make_linear_pack(*this, {a.proj}, lb), O, row_ld(dim), rows_pf, X,
                       row_ld(dim), ACT_NONE, X, row_ld(dim));
-            if (ln_fold) {
-                gemm_rows(*this, n + ".fc1", make_linear_pack(*this, {p + ".mlp.fc1"}), X, row_ld(dim), rows_pf, Hb,
-                          row_ld(2 * dim), ACT_GELU, -1, row_ld(0), -1, p + ".norm2", 1e-6f);
-            } else {
-                layernorm(*this, n + ".norm2", p + ".norm2", 1e-6f, X, row_ld(dim), -1, row_ld(0), Q, rows_pf, dim, lb);
-                gemm_rows(*this, n + ".fc1", make_linear_pack(*this, {p + ".mlp.fc1"}, lb), Q, row_ld(dim), rows_pf, Hb,
-                          row_ld(2 * dim), ACT_GELU, -1, row_ld(0));
-            }
-            gemm_rows(*this, n + ".fc2", make_linear_pack(*this, {p + ".mlp.fc2"}, lb), Hb, row_ld(2 * dim), rows_pf, X,
-                      row_ld(dim), ACT_NONE, X, row_ld(dim));
+            mlp_half(a.mlp, n, row_ld(dim), rows_pf, dim, 1e-6f, false, ln_fold);   // (never a chain of its own: inside OP_RES_CHAIN, or unfused)
         }
     };
-    attn_blocks("res_blocks", "res", C, (long)J * L1, L1, J);
+    attn_blocks(net.res, "res", C, (long)J * L1, L1, J);
     debug_copy(*this, "tok_res", X, (size_t)J * D, {-1, J, L1, C});
-    attn_blocks("joint_blocks", "joint", D, (long)J, J, 1);
+    attn_blocks(net.joint, "joint", D, (long)J, J, 1);
     debug_copy(*this, "tok_joint", X, (size_t)J * D, {-1, J, L1, C});
 
     {   // head (:240)
@@ -920,10 +913,10 @@ void Engine::build_lifter(const Tensor feats[4]) {
         op.kind = OP_HEAD;
         op.name = "head";
         op.in[0] = X;
-        op.p0 = pidx(*this, V + ".head.0.weight");
-        op.p1 = pidx(*this, V + ".head.0.bias");
-        op.p2 = pidx(*this, V + ".head.1.weight");
-        op.p3 = pidx(*this, V + ".head.1.bias");
+        op.p0 = net.head_ln.w;
+        op.p1 = net.head_ln.b;
+        op.p2 = net.head.w;
+        op.p3 = net.head.b;
         op.eps = 1e-5f;
         op.rows_per_frame = J;
         op.C = D;

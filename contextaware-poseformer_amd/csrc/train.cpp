@@ -3,10 +3,15 @@
 // context maps are constants here, so gradients flow only into the 191 `volume_net.*` parameters
 // (pose_dformer.py:144-208) — exactly the tensors DDP all-reduces in the reference (train.py:361-362).
 //
-// Every product is an igemm_f32 launch: with dY [M,N], X [M,K], W [N,K] (all row-major),
-//   dX = dY . W        -> A = dY (K' = N),            Wp = W^T  [K][Npad]   (transpose_pad of the weight)
-//   dW = dY^T . X      -> A = dY^T [N][Mpad] (K' = M), Wp = X^T  [K][Mpad]   (split-K over M, slabs summed in order)
-//   db = column sums of dY (two-stage deterministic reduction)
+// Which layers, with which parameters: Engine::lifter (LifterSchema, filled by build_lifter) -- nothing here builds a parameter name.
+// With dY [M,N], X [M,K], W [N,K] (all row-major), per linear (t_linear_bwd):
+//   dW, db = dY^T . X and the column sums of dY in ONE launch straight from the row-major dY and X (wgrad_tn: no transposes).  The rows are
+//            sliced; the slices' slabs wait in the slab area and are summed in order, many layers per launch (t_slab_flush).  Column sums
+//            that are no linear's bias (LayerNorm gamma / beta) are two-stage reductions whose second stages run batched too (t_col_flush)
+//   dX     = dY . W.  From batch 5 up every matrix of the step is packed once as two fp16 pieces, W for the forward's y = x W^T and W^T
+//            for this product (t_h2_plan / t_h2_prepare), and both run on the 16-bit matrix pipe
+// Fallbacks only: a shape or row map wgrad_tn does not take goes through transpose_pad of dY and X and a split-K igemm_f32 launch; a dX
+// without a pack through transpose_pad of the weight.
 // Gradients are written ONCE each (no accumulation, no atomics) into one flat fp32 buffer laid out in
 // state_dict order, so a single RCCL all-reduce covers what DDP sends in three buckets.
 #include <string.h>
@@ -48,7 +53,8 @@ void Engine::train_layout(int B, TrainLayout& L) const {
         const size_t R = (size_t)J * Lv;
         c.xh1 = take(R * C); c.rs1 = take(R); c.y1 = take(R * C); c.ao = take(R * 64);
         for (int l = 0; l < Lv; ++l) c.U[l] = take((size_t)J * NH * feat_C[l]);
-        c.xh2 = take(R * C); c.rs2 = take(R); c.y2 = take(R * C); c.hp = take(R * 2 * C); c.hg = take(R * 2 * C);
+        TrainLayout::Mlp& m = c.mlp;
+        m.xh2 = take(R * C); m.rs2 = take(R); m.y2 = take(R * C); m.hp = take(R * 2 * C); m.hg = take(R * 2 * C);
     }
     for (int g = 0; g < 2; ++g)
         for (int i = 0; i < DEP; ++i) {
@@ -56,7 +62,8 @@ void Engine::train_layout(int B, TrainLayout& L) const {
             const size_t E = (size_t)J * D;       // rows * dim is J*D elements per frame for both groups
             const size_t R = g == 0 ? (size_t)J * L1 : (size_t)J;
             a.xh1 = take(E); a.rs1 = take(R); a.y1 = take(E); a.qkv = take(3 * E); a.o = take(E);
-            a.xh2 = take(E); a.rs2 = take(R); a.y2 = take(E); a.hp = take(2 * E); a.hg = take(2 * E);
+            TrainLayout::Mlp& m = a.mlp;
+            m.xh2 = take(E); m.rs2 = take(R); m.y2 = take(E); m.hp = take(2 * E); m.hg = take(2 * E);
         }
     L.xhh = take((size_t)J * D); L.rsh = take(J); L.yh = take((size_t)J * D);
     // backward scratch
@@ -103,33 +110,27 @@ void Engine::t_h2_plan() {
     t_h2_elems = t_h2_max_elems = 0;
     t_h2_tiles = 0;
     if (!use_h2g || bf16() || !cfg.training) return;
-    const std::string V = "volume_net";
-    const int Lv = cfg.levels, L1 = Lv + 1, C = cfg.embed_dim_ratio, D = C * L1;
-    const int NH = cfg.deform_heads, NS = cfg.deform_samples, DEP = depth();
-    auto add = [&](const std::string& name, int N, int K, bool fwd, bool bwd) {
-        const auto it = param_index.find(name + ".weight");
-        if (it == param_index.end()) return;
-        if (N < 64) fwd = false;                             // (output columns of y = x W^T ...
-        if (K < 64) bwd = false;                             //  ... and of dX = dY W)
-        if (fwd || bwd) t_h2_specs.push_back(H2TrainSpec{it->second, -1, N, K, K, fwd, bwd});
+    const int Lv = cfg.levels, C = cfg.embed_dim_ratio, NH = cfg.deform_heads, NS = cfg.deform_samples, DEP = depth();
+    auto add = [&](const LinearRef& r, bool fwd, bool bwd) {
+        if (r.N < 64) fwd = false;                           // (output columns of y = x W^T ...
+        if (r.K < 64) bwd = false;                           //  ... and of dX = dY W)
+        if (fwd || bwd) t_h2_specs.push_back(H2TrainSpec{r.w, -1, r.N, r.K, r.K, fwd, bwd});
     };
-    for (int l = 0; l < Lv; ++l) add(V + ".feat_embed." + std::to_string(l), C, feat_C[l], true, false);
+    for (int l = 0; l < Lv; ++l) add(lifter.feat_embed[l], true, false);
     for (int i = 0; i < Lv && cfg.context_blocks; ++i) {
-        const std::string p = V + ".context_blocks." + std::to_string(i);
-        if ((size_t)i < ctx_ao_pack.size() && 3 * NH * NS >= 64)
-            t_h2_specs.push_back(H2TrainSpec{-1, ctx_ao_pack[i], 3 * NH * NS, C, packs[ctx_ao_pack[i]].Kpad, true, C >= 64});
-        for (int l = 0; l < Lv; ++l) add(p + ".embed_proj." + std::to_string(l), C / NH, feat_C[l], true, true);
-        add(p + ".mlp.fc1", 2 * C, C, true, true);
-        add(p + ".mlp.fc2", C, 2 * C, true, true);
+        const LifterCtx& c = lifter.ctx[i];
+        if (3 * NH * NS >= 64) t_h2_specs.push_back(H2TrainSpec{-1, c.ao_pack, 3 * NH * NS, C, packs[c.ao_pack].Kpad, true, C >= 64});
+        for (int l = 0; l < Lv; ++l) add(c.embed_proj[l], true, true);
+        add(c.mlp.fc1, true, true);
+        add(c.mlp.fc2, true, true);
     }
     for (int g = 0; g < 2; ++g)
         for (int i = 0; i < DEP; ++i) {
-            const std::string p = V + (g == 0 ? ".res_blocks." : ".joint_blocks.") + std::to_string(i);
-            const int dim = g == 0 ? C : D;
-            add(p + ".attn.qkv", 3 * dim, dim, true, true);
-            add(p + ".attn.proj", dim, dim, true, true);
-            add(p + ".mlp.fc1", 2 * dim, dim, true, true);
-            add(p + ".mlp.fc2", dim, 2 * dim, true, true);
+            const LifterAtt& a = g == 0 ? lifter.res[i] : lifter.joint[i];
+            add(a.qkv, true, true);
+            add(a.proj, true, true);
+            add(a.mlp.fc1, true, true);
+            add(a.mlp.fc2, true, true);
         }
     size_t off = 0, moff = 0;
     int tiles = 0;
@@ -354,16 +355,24 @@ int Engine::t_linear_bwd(hipStream_t s, const TrainLayout& L, float* tw, const f
     return CAPF_OK;
 }
 
-static const float* P(const Engine& e, const std::string& n) { return e.params[e.param_index.at(n)].ptr; }
+// DropPath multipliers (0 or 1/keep_prob) of block i of a group (0 context, 1 res, 2 joint): m1 scales the attention branch, m2 the MLP branch;
+// both nullptr for "no drop" (include/capf.h, capf_forward_train):
+//   context_blocks = 1:  ctx[i]: m1[B], m2[B]  |  res[i]: m1[B*J], m2[B*J]  |  joint[i]: m1[B], m2[B]      (i = 0..levels-1)
+//   context_blocks = 0:  res[i]: m1[B*J], m2[B*J]  |  joint[i]: m1[B], m2[B]                             (i = 0..depth-1)
+struct DropMasks { const float* m1; const float* m2; };
+static DropMasks drop_masks(const Engine& e, const float* masks, int B, int group, int i) {
+    if (!masks) return {nullptr, nullptr};
+    const size_t BJ = (size_t)B * e.cfg.num_joints;
+    const float* m_res = masks + (e.cfg.context_blocks ? (size_t)2 * e.cfg.levels * B : 0);
+    const float* base = group == 0 ? masks : group == 1 ? m_res : m_res + (size_t)2 * e.depth() * BJ;
+    const size_t ms = group == 1 ? BJ : (size_t)B;
+    return {base + (size_t)(2 * i) * ms, base + (size_t)(2 * i + 1) * ms};
+}
 
 // ---------------------------------------------------------------------------------------------------
 // forward (training): same math as the inference plan, every intermediate kept
-// masks: DropPath multipliers (0 or 1/keep_prob), or nullptr for "no drop" (include/capf.h, capf_forward_train):
-//   context_blocks = 1:  ctx[i]: m1[B], m2[B]  |  res[i]: m1[B*J], m2[B*J]  |  joint[i]: m1[B], m2[B]      (i = 0..levels-1)
-//   context_blocks = 0:  res[i]: m1[B*J], m2[B*J]  |  joint[i]: m1[B], m2[B]                             (i = 0..depth-1)
 // ---------------------------------------------------------------------------------------------------
 int Engine::forward_train(hipStream_t s, int B, const float* masks) {
-    const std::string V = "volume_net";
     const int J = cfg.num_joints, Lv = cfg.levels, L1 = Lv + 1, C = cfg.embed_dim_ratio, D = C * L1;
     const int NH = cfg.deform_heads, NS = cfg.deform_samples, HD = C / NH;
     TrainLayout L;
@@ -371,9 +380,7 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
     float* tw = ws + ws_elems_per_frame * (size_t)B;
     float* X = tw + L.X;
     const int DEP = depth();
-    const float* m_ctx = masks;
-    const float* m_res = masks ? masks + (cfg.context_blocks ? (size_t)2 * Lv * B : 0) : nullptr;
-    const float* m_joint = masks ? m_res + (size_t)2 * DEP * B * J : nullptr;
+    auto P = [&](int param) { return params[param].ptr; };
 
     if (int rc = t_h2_prepare(s, L, tw, B)) return rc;
     // the GEMMs read W as [N][Kpad] with Kpad a multiple of 32; a linear over a context map with K % 32 != 0 (HRNet-48's 48 channels) gets this
@@ -389,32 +396,41 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
         wpad += r64((size_t)N * *Kpad);
         return CAPF_OK;
     };
-    HIP_TRY(launch_prep_embed(kcrop, k2d, P(*this, V + ".coord_embed.weight"), P(*this, V + ".coord_embed.bias"),
-                              P(*this, V + ".Spatial_pos_embed"), X, B, J, L1, C, s));
-    const float* pos = P(*this, V + ".Spatial_pos_embed");
+    // out[omap] = A[amap] W^T + b, plus rscale * res[rmap] ... of a linear whose K needs no padding
+    auto linear = [&](const LinearRef& r, const float* A, RowMap amap, int M, float* o, RowMap omap, const float* res, RowMap rmap,
+                      const float* rscale, int rs_div) {
+        return t_gemm(s, A, amap, M, r.N, r.K, P(r.w), r.K, P(r.b), o, omap, res, rmap, ACT_NONE, rscale, rs_div);
+    };
+    // ---- the MLP half of any block on the rows `xm` of X: x += m2 * fc2(gelu(fc1(LN2(x)))), keeping what mlp_bwd reads
+    auto mlp_fwd = [&](const LifterMlp& m, const TrainLayout::Mlp& t, RowMap xm, int R, int dim, float eps, const float* m2, int div) -> int {
+        HIP_TRY(launch_layernorm_train(X, xm, nullptr, row_ld(0), P(m.norm2.w), P(m.norm2.b), eps, tw + t.y2, tw + t.xh2, tw + t.rs2, R, dim, s));
+        int rc = linear(m.fc1, tw + t.y2, row_ld(dim), R, tw + t.hp, row_ld(2 * dim), nullptr, row_ld(0), nullptr, 1);
+        if (rc) return rc;
+        HIP_TRY(launch_gelu_fwd(tw + t.hp, tw + t.hg, (long)R * 2 * dim, s));
+        return linear(m.fc2, tw + t.hg, row_ld(2 * dim), R, X, xm, X, xm, m2, div);
+    };
+
+    const float* pos = P(lifter.pos);
+    HIP_TRY(launch_prep_embed(kcrop, k2d, P(lifter.coord.w), P(lifter.coord.b), pos, X, B, J, L1, C, s));
     for (int l = 0; l < Lv; ++l) {
-        const std::string fe = V + ".feat_embed." + std::to_string(l);
+        const LinearRef& fe = lifter.feat_embed[l];
         float* S = tw + L.S[l];
         HIP_TRY(launch_sample_ref(bptr(feat_buf[l], B), kcrop, S, nullptr, B, J, feat_H[l], feat_W[l], feat_C[l], s, maps_bf16() ? 1 : 0));   // (the maps' stored dtype)
-        const float* Wfe = P(*this, fe + ".weight");
         const float* Wp = nullptr;
         int Kpad = 0;
-        if (int rc = padded(Wfe, C, feat_C[l], &Wp, &Kpad)) return rc;
-        int rc = t_gemm(s, S, row_ld(feat_C[l]), B * J, C, feat_C[l], Wp, Kpad,
-                        P(*this, fe + ".bias"), X, row_ld(D, (long)(1 + l) * C), pos, RowMap{J, 0, C, (long)(1 + l) * J * C},
-                        ACT_NONE, nullptr, 1, t_h2_pack(Wfe, false));
+        if (int rc = padded(P(fe.w), C, feat_C[l], &Wp, &Kpad)) return rc;
+        int rc = t_gemm(s, S, row_ld(feat_C[l]), B * J, C, feat_C[l], Wp, Kpad, P(fe.b), X, row_ld(D, (long)(1 + l) * C), pos,
+                        RowMap{J, 0, C, (long)(1 + l) * J * C}, ACT_NONE, nullptr, 1, t_h2_pack(P(fe.w), false));
         if (rc) return rc;
     }
     const RowMap tok{Lv, D, C, C}, tok0{Lv, D, 0, 0};
     for (int i = 0; i < Lv && cfg.context_blocks; ++i) {
-        const std::string p = V + ".context_blocks." + std::to_string(i);
+        const LifterCtx& cb = lifter.ctx[i];
         const TrainLayout::Ctx& c = L.ctx[i];
         const int R = B * J * Lv;
-        const float* m1 = m_ctx ? m_ctx + (size_t)(2 * i) * B : nullptr;
-        const float* m2 = m_ctx ? m_ctx + (size_t)(2 * i + 1) * B : nullptr;
-        HIP_TRY(launch_layernorm_train(X, tok, X, tok0, P(*this, p + ".norm1.weight"), P(*this, p + ".norm1.bias"), 1e-5f,
-                                       tw + c.y1, tw + c.xh1, tw + c.rs1, R, C, s));
-        const Pack& pk = packs[ctx_ao_pack[i]];
+        const DropMasks dm = drop_masks(*this, masks, B, 0, i);
+        HIP_TRY(launch_layernorm_train(X, tok, X, tok0, P(cb.norm1.w), P(cb.norm1.b), 1e-5f, tw + c.y1, tw + c.xh1, tw + c.rs1, R, C, s));
+        const Pack& pk = packs[cb.ao_pack];
         int rc = t_gemm(s, tw + c.y1, row_ld(C), R, 3 * NH * NS, C, pack_arena + pk.w_off, pk.Kpad, pack_arena + pk.b_off,
                         tw + c.ao, row_ld(64), nullptr, row_ld(64), ACT_NONE, nullptr, 1);
         if (rc) return rc;
@@ -426,63 +442,40 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
         }
         da.AO = tw + c.ao; da.ref = kcrop; da.B = B; da.J = J; da.L = Lv; da.NH = NH; da.NS = NS; da.ld_ao = 64;
         da.feat_bf16 = maps_bf16() ? 1 : 0;
-        if (debug) { da.cpos = bptr(ctx_tap_pos[i], B); da.cidx = reinterpret_cast<int*>(bptr(ctx_tap_idx[i], B)); }
+        if (debug) { da.cpos = bptr(cb.tap_pos, B); da.cidx = reinterpret_cast<int*>(bptr(cb.tap_idx, B)); }
         HIP_TRY(launch_deform_sample(da, s));
         for (int l = 0; l < Lv; ++l) {
-            const std::string ep = p + ".embed_proj." + std::to_string(l);
+            const LinearRef& ep = cb.embed_proj[l];
             const RowMap dst{NH, D, HD, (long)(1 + l) * C};
-            const float* Wep = P(*this, ep + ".weight");
             const float* Wp = nullptr;
             int Kpad = 0;
-            if ((rc = padded(Wep, HD, feat_C[l], &Wp, &Kpad))) return rc;
-            rc = t_gemm(s, tw + c.U[l], row_ld(feat_C[l]), B * J * NH, HD, feat_C[l], Wp, Kpad,
-                        P(*this, ep + ".bias"), X, dst, X, dst, ACT_NONE, m1, J * NH, t_h2_pack(Wep, false));
+            if ((rc = padded(P(ep.w), HD, feat_C[l], &Wp, &Kpad))) return rc;
+            rc = t_gemm(s, tw + c.U[l], row_ld(feat_C[l]), B * J * NH, HD, feat_C[l], Wp, Kpad, P(ep.b), X, dst, X, dst, ACT_NONE, dm.m1,
+                        J * NH, t_h2_pack(P(ep.w), false));
             if (rc) return rc;
         }
-        HIP_TRY(launch_layernorm_train(X, tok, nullptr, row_ld(0), P(*this, p + ".norm2.weight"), P(*this, p + ".norm2.bias"),
-                                       1e-5f, tw + c.y2, tw + c.xh2, tw + c.rs2, R, C, s));
-        rc = t_gemm(s, tw + c.y2, row_ld(C), R, 2 * C, C, P(*this, p + ".mlp.fc1.weight"), C, P(*this, p + ".mlp.fc1.bias"),
-                    tw + c.hp, row_ld(2 * C), nullptr, row_ld(0), ACT_NONE, nullptr, 1);
-        if (rc) return rc;
-        HIP_TRY(launch_gelu_fwd(tw + c.hp, tw + c.hg, (long)R * 2 * C, s));
-        rc = t_gemm(s, tw + c.hg, row_ld(2 * C), R, C, 2 * C, P(*this, p + ".mlp.fc2.weight"), 2 * C,
-                    P(*this, p + ".mlp.fc2.bias"), X, tok, X, tok, ACT_NONE, m2, J * Lv);
-        if (rc) return rc;
+        if ((rc = mlp_fwd(cb.mlp, c.mlp, tok, R, C, 1e-5f, dm.m2, J * Lv))) return rc;
     }
     for (int g = 0; g < 2; ++g) {
         const int dim = g == 0 ? C : D, R = g == 0 ? B * J * L1 : B * J;
         const int tokens = g == 0 ? L1 : J, groups = g == 0 ? B * J : B, per = g == 0 ? L1 : J;
         for (int i = 0; i < DEP; ++i) {
-            const std::string p = V + (g == 0 ? ".res_blocks." : ".joint_blocks.") + std::to_string(i);
+            const LifterAtt& ab = g == 0 ? lifter.res[i] : lifter.joint[i];
             const TrainLayout::Att& a = g == 0 ? L.res[i] : L.joint[i];
-            const float* mb = g == 0 ? m_res : m_joint;
-            const size_t ms = g == 0 ? (size_t)B * J : (size_t)B;
-            const float* m1 = mb ? mb + (size_t)(2 * i) * ms : nullptr;
-            const float* m2 = mb ? mb + (size_t)(2 * i + 1) * ms : nullptr;
-            HIP_TRY(launch_layernorm_train(X, row_ld(dim), nullptr, row_ld(0), P(*this, p + ".norm1.weight"),
-                                           P(*this, p + ".norm1.bias"), 1e-6f, tw + a.y1, tw + a.xh1, tw + a.rs1, R, dim, s));
-            int rc = t_gemm(s, tw + a.y1, row_ld(dim), R, 3 * dim, dim, P(*this, p + ".attn.qkv.weight"), dim,
-                            P(*this, p + ".attn.qkv.bias"), tw + a.qkv, row_ld(3 * dim), nullptr, row_ld(0), ACT_NONE, nullptr, 1);
+            const DropMasks dm = drop_masks(*this, masks, B, 1 + g, i);
+            HIP_TRY(launch_layernorm_train(X, row_ld(dim), nullptr, row_ld(0), P(ab.norm1.w), P(ab.norm1.b), 1e-6f, tw + a.y1, tw + a.xh1,
+                                           tw + a.rs1, R, dim, s));
+            int rc = linear(ab.qkv, tw + a.y1, row_ld(dim), R, tw + a.qkv, row_ld(3 * dim), nullptr, row_ld(0), nullptr, 1);
             if (rc) return rc;
             HIP_TRY(launch_attention(tw + a.qkv, tw + a.o, groups, tokens, cfg.num_heads, dim / cfg.num_heads, s));
-            rc = t_gemm(s, tw + a.o, row_ld(dim), R, dim, dim, P(*this, p + ".attn.proj.weight"), dim,
-                        P(*this, p + ".attn.proj.bias"), X, row_ld(dim), X, row_ld(dim), ACT_NONE, m1, per);
+            rc = linear(ab.proj, tw + a.o, row_ld(dim), R, X, row_ld(dim), X, row_ld(dim), dm.m1, per);
             if (rc) return rc;
-            HIP_TRY(launch_layernorm_train(X, row_ld(dim), nullptr, row_ld(0), P(*this, p + ".norm2.weight"),
-                                           P(*this, p + ".norm2.bias"), 1e-6f, tw + a.y2, tw + a.xh2, tw + a.rs2, R, dim, s));
-            rc = t_gemm(s, tw + a.y2, row_ld(dim), R, 2 * dim, dim, P(*this, p + ".mlp.fc1.weight"), dim,
-                        P(*this, p + ".mlp.fc1.bias"), tw + a.hp, row_ld(2 * dim), nullptr, row_ld(0), ACT_NONE, nullptr, 1);
-            if (rc) return rc;
-            HIP_TRY(launch_gelu_fwd(tw + a.hp, tw + a.hg, (long)R * 2 * dim, s));
-            rc = t_gemm(s, tw + a.hg, row_ld(2 * dim), R, dim, 2 * dim, P(*this, p + ".mlp.fc2.weight"), 2 * dim,
-                        P(*this, p + ".mlp.fc2.bias"), X, row_ld(dim), X, row_ld(dim), ACT_NONE, m2, per);
-            if (rc) return rc;
+            if ((rc = mlp_fwd(ab.mlp, a.mlp, row_ld(dim), R, dim, 1e-6f, dm.m2, per))) return rc;
         }
     }
-    HIP_TRY(launch_layernorm_train(X, row_ld(D), nullptr, row_ld(0), P(*this, V + ".head.0.weight"), P(*this, V + ".head.0.bias"),
-                                   1e-5f, tw + L.yh, tw + L.xhh, tw + L.rsh, B * J, D, s));
-    HIP_TRY(launch_head(X, P(*this, V + ".head.0.weight"), P(*this, V + ".head.0.bias"), 1e-5f, P(*this, V + ".head.1.weight"),
-                        P(*this, V + ".head.1.bias"), out, B * J, D, 3, s));
+    HIP_TRY(launch_layernorm_train(X, row_ld(D), nullptr, row_ld(0), P(lifter.head_ln.w), P(lifter.head_ln.b), 1e-5f, tw + L.yh, tw + L.xhh,
+                                   tw + L.rsh, B * J, D, s));
+    HIP_TRY(launch_head(X, P(lifter.head_ln.w), P(lifter.head_ln.b), 1e-5f, P(lifter.head.w), P(lifter.head.b), out, B * J, D, 3, s));
     train_batch = B;
     return CAPF_OK;
 }
@@ -496,7 +489,6 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
               "a later forward / workspace change overwrote them)";
         return CAPF_ERR_STATE;
     }
-    const std::string V = "volume_net";
     const int J = cfg.num_joints, Lv = cfg.levels, L1 = Lv + 1, C = cfg.embed_dim_ratio, D = C * L1;
     const int NH = cfg.deform_heads, NS = cfg.deform_samples, HD = C / NH;
     TrainLayout L;
@@ -509,29 +501,33 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
     float* dX = tw + L.dX;
     float* gA = tw + L.gA;
     float* gB = tw + L.gB;
-    auto G = [&](const std::string& n) { return flat + grad_off[param_index.at(n)]; };
+    auto P = [&](int param) { return params[param].ptr; };
+    auto G = [&](int param) { return flat + grad_off[param]; };
     const int DEP = depth();
-    const float* m_ctx = masks;
-    const float* m_res = masks ? masks + (cfg.context_blocks ? (size_t)2 * Lv * B : 0) : nullptr;
-    const float* m_joint = masks ? m_res + (size_t)2 * DEP * B * J : nullptr;
+    // gradients of the linear r (weight, bias, and dIn = dY W) from dY and its input Xin
+    auto linear_bwd = [&](const LinearRef& r, const float* dY, RowMap dymap, int rows, const float* Xin, RowMap xmap, float* dIn, RowMap dxmap) {
+        return t_linear_bwd(s, L, tw, dY, dymap, rows, r.N, r.K, Xin, xmap, P(r.w), dIn, dxmap, false, G(r.w), G(r.b));
+    };
+    // gradients of the LayerNorm ln (gamma and beta in one pass) from dY and the kept x-hat; the caller runs launch_layernorm_bwd for dX
+    auto ln_wgrad = [&](LnRef ln, const float* dY, size_t xh, int R, int dim) {
+        return t_colreduce(s, L, tw, dY, row_ld(dim), tw + xh, row_ld(dim), 1, R, dim, G(ln.w), 1, G(ln.b), L.red_cap);
+    };
 
     HIP_TRY(hipMemsetAsync(dX, 0, sizeof(float) * (size_t)B * J * D, s));
 
     // ---- head: out = LN(X) W^T + b
     {
         const int R = B * J;
-        if (int rc2 = t_colreduce(s, L, tw, dOut, row_ld(3), nullptr, row_ld(0), 0, R, 3, G(V + ".head.1.bias"), 1, nullptr, 0)) return rc2;
+        if (int rc2 = t_colreduce(s, L, tw, dOut, row_ld(3), nullptr, row_ld(0), 0, R, 3, G(lifter.head.b), 1, nullptr, 0)) return rc2;
         for (int o = 0; o < 3; ++o)
-            if (int rc2 = t_colreduce(s, L, tw, tw + L.yh, row_ld(D), dOut + o, row_ld(3), 2, R, D, G(V + ".head.1.weight") + (size_t)o * D, 1, nullptr, 0)) return rc2;
-        HIP_TRY(launch_head_dgrad(dOut, P(*this, V + ".head.1.weight"), gA, R, D, 3, s));
-        if (int rc2 = t_colreduce(s, L, tw, gA, row_ld(D), tw + L.xhh, row_ld(D), 1, R, D, G(V + ".head.0.weight"), 1, G(V + ".head.0.bias"), L.red_cap)) return rc2;      // d(gamma) and d(beta) in one pass
-        HIP_TRY(launch_layernorm_bwd(gA, tw + L.xhh, tw + L.rsh, P(*this, V + ".head.0.weight"), dX, row_ld(D), nullptr, row_ld(0), R, 1, D, s));
+            if (int rc2 = t_colreduce(s, L, tw, tw + L.yh, row_ld(D), dOut + o, row_ld(3), 2, R, D, G(lifter.head.w) + (size_t)o * D, 1, nullptr, 0)) return rc2;
+        HIP_TRY(launch_head_dgrad(dOut, P(lifter.head.w), gA, R, D, 3, s));
+        if (int rc2 = ln_wgrad(lifter.head_ln, gA, L.xhh, R, D)) return rc2;
+        HIP_TRY(launch_layernorm_bwd(gA, tw + L.xhh, tw + L.rsh, P(lifter.head_ln.w), dX, row_ld(D), nullptr, row_ld(0), R, 1, D, s));
     }
 
     // ---- the MLP half of any block: x_out = x + m2 * fc2(gelu(fc1(LN2(x))))
-    auto mlp_bwd = [&](const std::string& p, RowMap xm, int R, int dim, float eps_unused, size_t xh2, size_t rs2, size_t y2,
-                       size_t hp, size_t hg, const float* m2, int div) -> int {
-        (void)eps_unused;
+    auto mlp_bwd = [&](const LifterMlp& m, const TrainLayout::Mlp& t, RowMap xm, int R, int dim, const float* m2, int div) -> int {
         const float* dBr = dX;
         RowMap dm = xm;
         if (m2) {      // gradient of the branch output = dX * mask
@@ -539,15 +535,13 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
             dBr = gB;
             dm = row_ld(dim);
         }
-        int rc = t_linear_bwd(s, L, tw, dBr, dm, R, dim, 2 * dim, tw + hg, row_ld(2 * dim), P(*this, p + ".mlp.fc2.weight"), gA,
-                              row_ld(2 * dim), false, G(p + ".mlp.fc2.weight"), G(p + ".mlp.fc2.bias"));
+        int rc = linear_bwd(m.fc2, dBr, dm, R, tw + t.hg, row_ld(2 * dim), gA, row_ld(2 * dim));
         if (rc) return rc;
-        HIP_TRY(launch_gelu_bwd(tw + hp, gA, gA, (long)R * 2 * dim, s));
-        rc = t_linear_bwd(s, L, tw, gA, row_ld(2 * dim), R, 2 * dim, dim, tw + y2, row_ld(dim), P(*this, p + ".mlp.fc1.weight"), gB,
-                          row_ld(dim), false, G(p + ".mlp.fc1.weight"), G(p + ".mlp.fc1.bias"));
+        HIP_TRY(launch_gelu_bwd(tw + t.hp, gA, gA, (long)R * 2 * dim, s));
+        rc = linear_bwd(m.fc1, gA, row_ld(2 * dim), R, tw + t.y2, row_ld(dim), gB, row_ld(dim));
         if (rc) return rc;
-        if (int rc2 = t_colreduce(s, L, tw, gB, row_ld(dim), tw + xh2, row_ld(dim), 1, R, dim, G(p + ".norm2.weight"), 1, G(p + ".norm2.bias"), L.red_cap)) return rc2;      // d(gamma) and d(beta) in one pass
-        HIP_TRY(launch_layernorm_bwd(gB, tw + xh2, tw + rs2, P(*this, p + ".norm2.weight"), dX, xm, nullptr, row_ld(0), R, 1, dim, s));
+        if ((rc = ln_wgrad(m.norm2, gB, t.xh2, R, dim))) return rc;
+        HIP_TRY(launch_layernorm_bwd(gB, tw + t.xh2, tw + t.rs2, P(m.norm2.w), dX, xm, nullptr, row_ld(0), R, 1, dim, s));
         return CAPF_OK;
     };
 
@@ -556,54 +550,46 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
         const int dim = g == 0 ? C : D, R = g == 0 ? B * J * L1 : B * J;
         const int tokens = g == 0 ? L1 : J, groups = g == 0 ? B * J : B, per = g == 0 ? L1 : J;
         for (int i = DEP - 1; i >= 0; --i) {
-            const std::string p = V + (g == 0 ? ".res_blocks." : ".joint_blocks.") + std::to_string(i);
+            const LifterAtt& ab = g == 0 ? lifter.res[i] : lifter.joint[i];
             const TrainLayout::Att& a = g == 0 ? L.res[i] : L.joint[i];
-            const float* mb = g == 0 ? m_res : m_joint;
-            const size_t ms = g == 0 ? (size_t)B * J : (size_t)B;
-            const float* m1 = mb ? mb + (size_t)(2 * i) * ms : nullptr;
-            const float* m2 = mb ? mb + (size_t)(2 * i + 1) * ms : nullptr;
-            int rc = mlp_bwd(p, row_ld(dim), R, dim, 0.f, a.xh2, a.rs2, a.y2, a.hp, a.hg, m2, per);
+            const DropMasks dm = drop_masks(*this, masks, B, 1 + g, i);
+            int rc = mlp_bwd(ab.mlp, a.mlp, row_ld(dim), R, dim, dm.m2, per);
             if (rc) return rc;
             const float* dBr = dX;
-            if (m1) {
-                HIP_TRY(launch_scale_rows(dX, row_ld(dim), m1, per, gB, R, dim, s));
+            if (dm.m1) {
+                HIP_TRY(launch_scale_rows(dX, row_ld(dim), dm.m1, per, gB, R, dim, s));
                 dBr = gB;
             }
-            rc = t_linear_bwd(s, L, tw, dBr, row_ld(dim), R, dim, dim, tw + a.o, row_ld(dim), P(*this, p + ".attn.proj.weight"), gA,
-                              row_ld(dim), false, G(p + ".attn.proj.weight"), G(p + ".attn.proj.bias"));
+            rc = linear_bwd(ab.proj, dBr, row_ld(dim), R, tw + a.o, row_ld(dim), gA, row_ld(dim));
             if (rc) return rc;
             HIP_TRY(launch_attention_bwd(tw + a.qkv, gA, gB, groups, tokens, cfg.num_heads, dim / cfg.num_heads, s));
-            rc = t_linear_bwd(s, L, tw, gB, row_ld(3 * dim), R, 3 * dim, dim, tw + a.y1, row_ld(dim), P(*this, p + ".attn.qkv.weight"),
-                              gA, row_ld(dim), false, G(p + ".attn.qkv.weight"), G(p + ".attn.qkv.bias"));
+            rc = linear_bwd(ab.qkv, gB, row_ld(3 * dim), R, tw + a.y1, row_ld(dim), gA, row_ld(dim));
             if (rc) return rc;
-            if (int rc2 = t_colreduce(s, L, tw, gA, row_ld(dim), tw + a.xh1, row_ld(dim), 1, R, dim, G(p + ".norm1.weight"), 1, G(p + ".norm1.bias"), L.red_cap)) return rc2;      // d(gamma) and d(beta) in one pass
-            HIP_TRY(launch_layernorm_bwd(gA, tw + a.xh1, tw + a.rs1, P(*this, p + ".norm1.weight"), dX, row_ld(dim), nullptr, row_ld(0), R, 1, dim, s));
+            if ((rc = ln_wgrad(ab.norm1, gA, a.xh1, R, dim))) return rc;
+            HIP_TRY(launch_layernorm_bwd(gA, tw + a.xh1, tw + a.rs1, P(ab.norm1.w), dX, row_ld(dim), nullptr, row_ld(0), R, 1, dim, s));
         }
     }
 
     // ---- deformable context blocks
     const RowMap tok{Lv, D, C, C}, tok0{Lv, D, 0, 0};
     for (int i = Lv - 1; i >= 0 && cfg.context_blocks; --i) {
-        const std::string p = V + ".context_blocks." + std::to_string(i);
+        const LifterCtx& cb = lifter.ctx[i];
         const TrainLayout::Ctx& c = L.ctx[i];
         const int R = B * J * Lv;
-        const float* m1 = m_ctx ? m_ctx + (size_t)(2 * i) * B : nullptr;
-        const float* m2 = m_ctx ? m_ctx + (size_t)(2 * i + 1) * B : nullptr;
-        int rc = mlp_bwd(p, tok, R, C, 0.f, c.xh2, c.rs2, c.y2, c.hp, c.hg, m2, J * Lv);
+        const DropMasks dmk = drop_masks(*this, masks, B, 0, i);
+        int rc = mlp_bwd(cb.mlp, c.mlp, tok, R, C, dmk.m2, J * Lv);
         if (rc) return rc;
         DeformArgs da{};
         for (int l = 0; l < Lv; ++l) {
-            const std::string ep = p + ".embed_proj." + std::to_string(l);
             const RowMap src{NH, D, HD, (long)(1 + l) * C};      // row (b,p,h) -> dX[b,p,1+l,h*HD:]
             const float* dBr = dX;
             RowMap dm = src;
-            if (m1) {
-                HIP_TRY(launch_scale_rows(dX, src, m1, J * NH, gB, B * J * NH, HD, s));
+            if (dmk.m1) {
+                HIP_TRY(launch_scale_rows(dX, src, dmk.m1, J * NH, gB, B * J * NH, HD, s));
                 dBr = gB;
                 dm = row_ld(HD);
             }
-            rc = t_linear_bwd(s, L, tw, dBr, dm, B * J * NH, HD, feat_C[l], tw + c.U[l], row_ld(feat_C[l]), P(*this, ep + ".weight"),
-                              tw + L.dU[l], row_ld(feat_C[l]), false, G(ep + ".weight"), G(ep + ".bias"));
+            rc = linear_bwd(cb.embed_proj[l], dBr, dm, B * J * NH, tw + c.U[l], row_ld(feat_C[l]), tw + L.dU[l], row_ld(feat_C[l]));
             if (rc) return rc;
             da.feat[l] = bptr(feat_buf[l], B);
             da.H[l] = feat_H[l]; da.W[l] = feat_W[l]; da.C[l] = feat_C[l];
@@ -613,7 +599,7 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
         da.feat_bf16 = maps_bf16() ? 1 : 0;
         HIP_TRY(launch_deform_bwd(da, gA, 64, s));                                  // gA = dAO [R, 64]
         // [attention_weights | sampling_offsets] were one GEMM with N = 48: gradients land in a [48, C] temp
-        const Pack& pk = packs[ctx_ao_pack[i]];
+        const Pack& pk = packs[cb.ao_pack];
         const int NA = NH * NS, NO = 2 * NH * NS;
         float* gWcat = tw + L.cat;                      // [48][C]
         float* gbcat = gWcat + (size_t)(NH * NS * 3) * C;   // [48], right behind the weight gradient: one launch leaves both
@@ -623,27 +609,25 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
         if (rc) return rc;
         if ((rc = t_slab_flush(s))) return rc;           // (the copies below read the temp: its slabs are summed now, with whatever else waits,
         if ((rc = t_col_flush(s))) return rc;            //  and so is a bias gradient still in partial sums -- t_linear_bwd's fallback defers gbcat)
-        HIP_TRY(hipMemcpyAsync(G(p + ".attention_weights.weight"), gWcat, sizeof(float) * NA * C, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(G(p + ".sampling_offsets.weight"), gWcat + (size_t)NA * C, sizeof(float) * NO * C, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(G(p + ".attention_weights.bias"), gbcat, sizeof(float) * NA, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(G(p + ".sampling_offsets.bias"), gbcat + NA, sizeof(float) * NO, hipMemcpyDeviceToDevice, s));
-        if (int rc2 = t_colreduce(s, L, tw, dq, row_ld(C), tw + c.xh1, row_ld(C), 1, R, C, G(p + ".norm1.weight"), 1, G(p + ".norm1.bias"), L.red_cap)) return rc2;      // d(gamma) and d(beta) in one pass
-        HIP_TRY(launch_layernorm_bwd(dq, tw + c.xh1, tw + c.rs1, P(*this, p + ".norm1.weight"), dX, tok, dX, tok0, R, Lv, C, s));
+        HIP_TRY(hipMemcpyAsync(G(cb.aw.w), gWcat, sizeof(float) * NA * C, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(G(cb.so.w), gWcat + (size_t)NA * C, sizeof(float) * NO * C, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(G(cb.aw.b), gbcat, sizeof(float) * NA, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(G(cb.so.b), gbcat + NA, sizeof(float) * NO, hipMemcpyDeviceToDevice, s));
+        if ((rc = ln_wgrad(cb.norm1, dq, c.xh1, R, C))) return rc;
+        HIP_TRY(launch_layernorm_bwd(dq, tw + c.xh1, tw + c.rs1, P(cb.norm1.w), dX, tok, dX, tok0, R, Lv, C, s));
     }
 
     // ---- embeddings: X[b,p,0] = coord_embed(k2d) + pos[0,p];  X[b,p,1+l] = feat_embed_l(S_l) + pos[1+l,p]
     {
         const int R = B * J;
         for (int l = 0; l < Lv; ++l) {
-            const std::string fe = V + ".feat_embed." + std::to_string(l);
-            int rc = t_linear_bwd(s, L, tw, dX, row_ld(D, (long)(1 + l) * C), R, C, feat_C[l], tw + L.S[l], row_ld(feat_C[l]),
-                                  P(*this, fe + ".weight"), nullptr, row_ld(0), false, G(fe + ".weight"), G(fe + ".bias"));
+            int rc = linear_bwd(lifter.feat_embed[l], dX, row_ld(D, (long)(1 + l) * C), R, tw + L.S[l], row_ld(feat_C[l]), nullptr, row_ld(0));
             if (rc) return rc;
         }
-        if (int rc2 = t_colreduce(s, L, tw, dX, row_ld(D), nullptr, row_ld(0), 0, R, C, G(V + ".coord_embed.bias"), 1, nullptr, 0)) return rc2;
+        if (int rc2 = t_colreduce(s, L, tw, dX, row_ld(D), nullptr, row_ld(0), 0, R, C, G(lifter.coord.b), 1, nullptr, 0)) return rc2;
         for (int j = 0; j < 2; ++j)
-            if (int rc2 = t_colreduce(s, L, tw, dX, row_ld(D), k2d + j, row_ld(2), 2, R, C, G(V + ".coord_embed.weight") + j, 2, nullptr, 0)) return rc2;
-        HIP_TRY(launch_pos_grad(dX, G(V + ".Spatial_pos_embed"), B, J, L1, C, s));
+            if (int rc2 = t_colreduce(s, L, tw, dX, row_ld(D), k2d + j, row_ld(2), 2, R, C, G(lifter.coord.w) + j, 2, nullptr, 0)) return rc2;
+        HIP_TRY(launch_pos_grad(dX, G(lifter.pos), B, J, L1, C, s));
     }
     if (int rc = t_col_flush(s)) return rc;                  // every bias / LayerNorm gradient still in partial sums
     return t_slab_flush(s);                                  // every weight gradient still in slabs
