@@ -3,6 +3,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "engine.h"
@@ -18,6 +19,10 @@ namespace capf {
         }                                                                                  \
     } while (0)
 
+Engine::ConvSrc Engine::conv_src(const Pack& pk) const {
+    return {params[pk.w[0]].ptr, params[pk.bn.g].ptr, params[pk.bn.b].ptr, params[pk.bn.m].ptr, params[pk.bn.v].ptr, 1e-5f};
+}
+
 // Rebuild the private packed copies from the borrowed parameters.
 int Engine::repack(hipStream_t s, bool lifter_only) {
     for (const Param& p : params) {
@@ -32,67 +37,44 @@ int Engine::repack(hipStream_t s, bool lifter_only) {
         utab_on_device = true;
     }
     for (const Pack& pk : packs) {                      // the convs' two-fp16-piece copies (igemm_f32h2.hip); the linears' are packed lazily
-        if (!pk.h2g || pk.kind != 0 || lifter_only) continue;
-        HIP_TRY(launch_pack_f32h2_gemm(params[pk.w[0]].ptr, params[pk.bn_g].ptr, params[pk.bn_b].ptr, params[pk.bn_m].ptr, params[pk.bn_v].ptr,
-                                       1e-5f, pack_arena + pk.wh_off, nullptr, pk.N, pk.Cin, pk.ks, pk.K, pk.KpadH, s));
+        if (!pk.h2g || pk.kind != CONV_BN || lifter_only) continue;
+        const ConvSrc c = conv_src(pk);
+        HIP_TRY(launch_pack_f32h2_gemm(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.h2g_off, nullptr, pk.N, pk.Cin, pk.ks, pk.K, pk.h2g_Kpad, s));
     }
     h2g_lifter_dirty = true;
     std::vector<CopySegment> jobs;                      // the packed linears' bias vectors: one launch for all of them (below)
     for (const Pack& pk : packs) {
-        if (pk.direct) continue;
-        if (lifter_only && pk.kind == 0) continue;      // conv+BN packs belong to the frozen backbone
+        if (pk.in_place) continue;
         float* W = pack_arena + pk.w_off;
         float* B = pack_arena + pk.b_off;
-        if (pk.kind == 0 && pk.bf16) {
-            HIP_TRY(launch_pack_conv_bf16(params[pk.w[0]].ptr, params[pk.bn_g].ptr, params[pk.bn_b].ptr, params[pk.bn_m].ptr,
-                                          params[pk.bn_v].ptr, 1e-5f, W, B, pk.N, pk.Cin, pk.ks, pk.Kpad, s));
-            if (pk.rh)
-                HIP_TRY(launch_pack_conv_bf16_rh(params[pk.w[0]].ptr, params[pk.bn_g].ptr, params[pk.bn_b].ptr, params[pk.bn_m].ptr,
-                                                 params[pk.bn_v].ptr, 1e-5f, pack_arena + pk.w2_off, B, pk.N, pk.Cin,
-                                                 bf16_rh_width(pk.Cin), s));
-            if (pk.ws)
-                HIP_TRY(launch_pack_conv_bf16_ws(params[pk.w[0]].ptr, params[pk.bn_g].ptr, params[pk.bn_b].ptr, params[pk.bn_m].ptr,
-                                                 params[pk.bn_v].ptr, 1e-5f, pack_arena + pk.w3_off, B, pk.N, pk.Cin, s));
-        } else if (pk.kind == 0 && pk.wino) {
-            if (!pk.wino_skip)
-            HIP_TRY(launch_pack_conv_wino(params[pk.w[0]].ptr, params[pk.bn_g].ptr, params[pk.bn_b].ptr, params[pk.bn_m].ptr,
-                                          params[pk.bn_v].ptr, 1e-5f, W, B, pk.N, pk.Cin, s, pk.Kpad == 18 * pk.Cin ? 43 : 23));
-            HIP_TRY(launch_pack_conv(params[pk.w[0]].ptr, params[pk.bn_g].ptr, params[pk.bn_b].ptr, params[pk.bn_m].ptr,
-                                     params[pk.bn_v].ptr, 1e-5f, pack_arena + pk.w2_off, B, pk.N, pk.Cin, pk.ks, pk.Kpad2, s));
-            if (pk.x3)
-                HIP_TRY((x3_h2 ? launch_pack_conv_f32h2 : launch_pack_conv_f32x3)(params[pk.w[0]].ptr, params[pk.bn_g].ptr, params[pk.bn_b].ptr,
-                                                                                  params[pk.bn_m].ptr, params[pk.bn_v].ptr, 1e-5f,
-                                                                                  pack_arena + pk.w3_off, B, pk.N, pk.Cin, s));
-        } else if (pk.kind == 0) {
-            HIP_TRY(launch_pack_conv(params[pk.w[0]].ptr, params[pk.bn_g].ptr, params[pk.bn_b].ptr,
-                                     params[pk.bn_m].ptr, params[pk.bn_v].ptr, 1e-5f, W, B, pk.N, pk.Cin, pk.ks,
-                                     pk.Kpad, s));
-        } else if (pk.bf16) {            // linear weights as bf16 [N][Kpad] (a 1x1 "conv" without BatchNorm), bias fp32
-            int n0 = 0;
-            for (int i = 0; i < pk.n_lin; ++i) {
-                const int n = (int)params[pk.w[i]].shape[0];
-                unsigned short* Wb = reinterpret_cast<unsigned short*>(W) + (size_t)n0 * pk.Kpad;
-                HIP_TRY(launch_pack_conv_bf16(params[pk.w[i]].ptr, nullptr, nullptr, nullptr, nullptr, 0.f, Wb, nullptr, n, pk.K, 1,
-                                              pk.Kpad, s));
-                jobs.push_back(CopySegment{params[pk.b[i]].ptr, B + n0, n, 0});
-                n0 += n;
+        if (pk.kind == CONV_BN) {
+            if (lifter_only) continue;                  // conv+BN packs belong to the frozen backbone
+            const ConvSrc c = conv_src(pk);
+            if (pk.bf16) {
+                HIP_TRY(launch_pack_conv_bf16(c.w, c.g, c.b, c.m, c.v, c.eps, W, B, pk.N, pk.Cin, pk.ks, pk.Kpad, s));
+                if (pk.rh) HIP_TRY(launch_pack_conv_bf16_rh(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.rh_off, B, pk.N, pk.Cin, bf16_rh_width(pk.Cin), s));
+                if (pk.ws) HIP_TRY(launch_pack_conv_bf16_ws(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.ws_off, B, pk.N, pk.Cin, s));
+            } else if (pk.wino) {
+                if (!pk.wino_skip) HIP_TRY(launch_pack_conv_wino(c.w, c.g, c.b, c.m, c.v, c.eps, W, B, pk.N, pk.Cin, s, pk.Kpad == 18 * pk.Cin ? 43 : 23));
+                HIP_TRY(launch_pack_conv(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.direct_off, B, pk.N, pk.Cin, pk.ks, pk.direct_Kpad, s));
+                if (pk.x3)
+                    HIP_TRY((plan.x3_h2 ? launch_pack_conv_f32h2 : launch_pack_conv_f32x3)(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.x3_off, B, pk.N, pk.Cin, s));
+            } else {
+                HIP_TRY(launch_pack_conv(c.w, c.g, c.b, c.m, c.v, c.eps, W, B, pk.N, pk.Cin, pk.ks, pk.Kpad, s));
             }
-        } else if (pk.quad) {            // fused lifter kernels: Wq[k / 4][n][4], the linears concatenated along n
-            int n0 = 0;
-            for (int i = 0; i < pk.n_lin; ++i) {
-                const int n = (int)params[pk.w[i]].shape[0];
-                HIP_TRY(launch_pack_linear_quad(params[pk.w[i]].ptr, W, n, pk.K, n0, pk.N, s));
-                jobs.push_back(CopySegment{params[pk.b[i]].ptr, B + n0, n, 0});
-                n0 += n;
-            }
-        } else {
-            int n0 = 0;
-            for (int i = 0; i < pk.n_lin; ++i) {
-                const int n = (int)params[pk.w[i]].shape[0];
-                HIP_TRY(launch_pack_linear(params[pk.w[i]].ptr, W + (size_t)n0 * pk.Kpad, n, pk.K, pk.Kpad, s));
-                jobs.push_back(CopySegment{params[pk.b[i]].ptr, B + n0, n, 0});
-                n0 += n;
-            }
+            continue;
+        }
+        int n0 = 0;                                     // linears, concatenated along N: each into its rows of the pack's layout
+        for (int i = 0; i < pk.n_lin; ++i) {
+            const int n = (int)params[pk.w[i]].shape[0];
+            const float* w = params[pk.w[i]].ptr;
+            if (pk.bf16)                                // bf16 [N][Kpad] (a 1x1 "conv" without BatchNorm), bias fp32
+                HIP_TRY(launch_pack_conv_bf16(w, nullptr, nullptr, nullptr, nullptr, 0.f, reinterpret_cast<unsigned short*>(W) + (size_t)n0 * pk.Kpad,
+                                              nullptr, n, pk.K, 1, pk.Kpad, s));
+            else if (pk.quad) HIP_TRY(launch_pack_linear_quad(w, W, n, pk.K, n0, pk.N, s));     // fused lifter kernels: Wq[k / 4][n][4]
+            else HIP_TRY(launch_pack_linear(w, W + (size_t)n0 * pk.Kpad, n, pk.K, pk.Kpad, s));
+            jobs.push_back(CopySegment{params[pk.b[i]].ptr, B + n0, n, 0});
+            n0 += n;
         }
     }
     if (!jobs.empty()) {
@@ -116,14 +98,14 @@ int Engine::repack(hipStream_t s, bool lifter_only) {
 int Engine::ensure_h2g_lifter(hipStream_t s) {
     if (!h2g_lifter_dirty) return CAPF_OK;
     for (const Pack& pk : packs) {
-        if (!pk.h2g || pk.kind != 1) continue;
+        if (!pk.h2g || pk.kind != LINEAR) continue;
         int n0 = 0;
         for (int i = 0; i < pk.n_lin; ++i) {
             const int n = (int)params[pk.w[i]].shape[0];
-            HIP_TRY(launch_pack_f32h2_gemm_rows(params[pk.w[i]].ptr, pack_arena + pk.wh_off, n0, n, pk.N, pk.K, pk.KpadH, s));
+            HIP_TRY(launch_pack_f32h2_gemm_rows(params[pk.w[i]].ptr, pack_arena + pk.h2g_off, n0, n, pk.N, pk.K, pk.h2g_Kpad, s));
             n0 += n;
         }
-        if (pk.chain) HIP_TRY(launch_res_chain_repack(pack_arena + pk.wh_off, pack_arena + pk.wc_off, pk.N, pk.KpadH, s));
+        if (pk.chain) HIP_TRY(launch_res_chain_repack(pack_arena + pk.h2g_off, pack_arena + pk.chain_off, pk.N, pk.h2g_Kpad, s));
     }
     h2g_lifter_dirty = false;
     return CAPF_OK;
@@ -134,7 +116,7 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes) const {
     const Pack& pk = packs[op.pack];
     GemmArgs a{};
     a.A = op.in[0] == -2 ? images : ptr(op.in[0]);
-    if (pk.direct) {
+    if (pk.in_place) {
         a.Wp = params[pk.w[0]].ptr;
         a.bias = params[pk.b[0]].ptr;
     } else {
@@ -145,16 +127,16 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes) const {
     a.out = ptr(op.out);
     a.M = (int)(op.rows_per_frame * batch);
     a.N = op.N; a.K = op.K; a.Kpad = pk.Kpad;
-    if (pk.rh) a.Wp2 = pack_arena + pk.w2_off;
-    if (pk.ws || pk.x3) a.Wp3 = pack_arena + pk.w3_off;
-    a.x3_h2 = pk.x3 && x3_h2;
+    if (pk.rh) a.Wp2 = pack_arena + pk.rh_off;
+    if (pk.ws || pk.x3) a.Wp3 = pack_arena + (pk.ws ? pk.ws_off : pk.x3_off);
+    a.x3_h2 = pk.x3 && plan.x3_h2;
     if (a.x3_h2 && op.h2_utab >= 0 && utab_on_device) a.h2_utab = reinterpret_cast<const unsigned*>(pack_arena + utab_off) + op.h2_utab;
     // the plain fp32 MFMA kernels' problems on the two-fp16-piece GEMM from batch 5 (launch_gemm_f32 / _group route them; below, the fp32
     // kernels with split-K win); LayerNorm folds of up to 256 columns included (igemm_f32h2.hip, LNA)
-    if (pk.h2g && batch >= H2G_MIN_BATCH && !op.bf16 && !op.pw_pair && !(op.wino && wino_now(op, batch))) a.Wh2 = pack_arena + pk.wh_off;
+    if (pk.h2g && batch >= H2G_MIN_BATCH && !op.bf16 && !op.pw_pair && !(op.wino && wino_now(op, batch))) a.Wh2 = pack_arena + pk.h2g_off;
     if (op.wino && !wino_now(op, batch)) {           // small batch: the direct kernel on the direct-layout copy of the weights
-        a.Wp = pack_arena + pk.w2_off;
-        a.Kpad = pk.Kpad2;
+        a.Wp = pack_arena + pk.direct_off;
+        a.Kpad = pk.direct_Kpad;
     } else if (op.wino && pk.wino_skip) {
         a.Wp = nullptr;                              // no Winograd layout was packed: only a split-fp32 tile (Wp3) may take this launch
     }
@@ -178,21 +160,21 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes) const {
             if (op.h2_role == 1) a.h2_eout = e; else a.h2_ein = e;
         }
     }
-    if (op.conv && op.in[1] >= 0) {                    // + bilinear_upsample(in[1]) behind the activation (build_cpn: lateral + upsampled path)
-        a.up = ptr(op.in[1]);
-        a.up_H = op.i0; a.up_W = op.i1;
-        a.up_sh = op.Ho > 1 ? (float)(op.i0 - 1) / (float)(op.Ho - 1) : 0.f;
-        a.up_sw = op.Wo > 1 ? (float)(op.i1 - 1) / (float)(op.Wo - 1) : 0.f;
+    if (op.conv && op.up_in >= 0) {                    // + bilinear_upsample(up_in) behind the activation (build_cpn: lateral + upsampled path)
+        a.up = ptr(op.up_in);
+        a.up_H = op.up_H; a.up_W = op.up_W;
+        a.up_sh = op.Ho > 1 ? (float)(op.up_H - 1) / (float)(op.Ho - 1) : 0.f;
+        a.up_sw = op.Wo > 1 ? (float)(op.up_W - 1) / (float)(op.Wo - 1) : 0.f;
     }
     static const bool splitk_on = [] { const char* e = diag_env("CAPF_SPLITK"); return !e || atoi(e) != 0; }();   // A/B runs only
-    if ((op.conv || (op.kind == OP_GEMM && op.ln_w < 0 && op.res_param < 0)) && !op.bf16 && split_ws && lanes != 1 && splitk_on) {   // one stream: launches use the scratch one after the other
+    if ((op.conv || (op.kind == OP_GEMM && op.ln.w < 0 && op.res_param < 0)) && !op.bf16 && split_ws && lanes != 1 && splitk_on) {   // one stream: launches use the scratch one after the other
         a.split_ws = on_side_chain ? split_ws_side : split_ws;
         a.split_cnt = on_side_chain ? split_cnt_side : split_cnt;
         a.split_ws_elems = SPLIT_WS_ELEMS; a.split_cnt_elems = SPLIT_CNT_ELEMS;
     }
-    if (op.ln_w >= 0) {
-        a.ln_g = params[op.ln_w].ptr;
-        a.ln_b = params[op.ln_b].ptr;
+    if (op.ln.w >= 0) {
+        a.ln_g = params[op.ln.w].ptr;
+        a.ln_b = params[op.ln.b].ptr;
         a.ln_eps = op.eps;
     }
     return a;
@@ -207,7 +189,7 @@ Engine::FusedLaunch Engine::fused_at(int i, int batch, int last_op, bool bneck_o
     if (i < 0 || i >= n_all) return {};
     const Op& o = ops[i];
     if (o.kind == OP_FORK) {                                   // conv1, conv2 | downsample inside the region, conv3 right after its join
-        if (!use_bneck || !bf16() || o.i0 != 2 || o.region < 0) return {};
+        if (!plan.use_bneck || !bf16() || o.fork.lanes != 2 || o.region < 0) return {};
         const int j = regions[o.region].second;
         if (j != i + 4 || j + 1 >= last_op || j + 1 >= n_all) return {};
         int c1 = -1, c2 = -1, ds = -1;
@@ -224,15 +206,15 @@ Engine::FusedLaunch Engine::fused_at(int i, int batch, int last_op, bool bneck_o
         return {Fusion::BNECK0, 4, {c1, c2, ds, c3}};
     }
     if (o.kind != OP_GEMM) return {};
-    if (use_bneck && bf16() && i + 2 < last_op && i + 2 < n_all) {
+    if (plan.use_bneck && bf16() && i + 2 < last_op && i + 2 < n_all) {
         const Op &c2 = ops[i + 1], &c3 = ops[i + 2];
         bool ok = o.bneck_c3 == i + 2 && c2.in[0] == o.out && c3.in[0] == c2.out && c3.aux == o.in[0] && o.aux < 0 && c2.aux < 0 &&
                   o.rows_per_frame * batch >= 65536;
         for (const Op* g : {&o, &c2, &c3})
-            ok = ok && g->kind == OP_GEMM && g->conv && g->bf16 == 1 && g->region == o.region && g->lane == o.lane && g->in[1] < 0;
+            ok = ok && g->kind == OP_GEMM && g->conv && g->bf16 == 1 && g->region == o.region && g->lane == o.lane && g->up_in < 0;
         if (ok && bneck1_bf16_ok(gemm_args(o, batch), gemm_args(c2, batch), gemm_args(c3, batch))) return {Fusion::BNECK1, 3, {i, i + 1, i + 2}};
     }
-    if (bneck_only || !use_pwchain || i + 1 >= last_op || i + 1 >= n_all) return {};
+    if (bneck_only || !plan.use_pwchain || i + 1 >= last_op || i + 1 >= n_all) return {};
     const Op& b = ops[i + 1];
     if (!o.conv || b.kind != OP_GEMM || !b.conv || o.bf16 != b.bf16 || o.bf16 > 1 || b.in[0] != o.out || b.region != o.region || b.lane != o.lane) return {};
     if (o.bf16 && (fused_leader(i, batch, true).n || fused_at(i + 1, batch, last_op, true).n)) return {};
@@ -265,15 +247,15 @@ Engine::OpRoute Engine::op_route(const Op& op, int batch) const {
     const Pack& pk = packs[op.pack];
     const double MN = 2.0 * (double)op.rows_per_frame * batch * op.N;
     const Family f = gemm_family(op, batch);
-    if (f == Family::BF16_ROWS) return {f, gemm_bf16_rows_kernel_name((int)(op.rows_per_frame * batch), op.N), MN * (pk.direct ? op.K : pk.Kpad)};
+    if (f == Family::BF16_ROWS) return {f, gemm_bf16_rows_kernel_name((int)(op.rows_per_frame * batch), op.N), MN * (pk.in_place ? op.K : pk.Kpad)};
     const GemmArgs a = gemm_args(op, batch);
     if (f == Family::BF16)                                     // (the row-halo layout has no K padding: decided per launch, a lower bound)
-        return {f, gemm_bf16_kernel_name(a), MN * (pk.rh || pk.direct ? op.K : pk.Kpad)};
+        return {f, gemm_bf16_kernel_name(a), MN * (pk.rh || pk.in_place ? op.K : pk.Kpad)};
     if (f == Family::WINO)
-        return {f, gemm_wino_kernel_name(a), gemm_wino_route(a) == WinoPath::X3 ? (x3_h2 ? 3.0 : 6.0) * MN * op.K
+        return {f, gemm_wino_kernel_name(a), gemm_wino_route(a) == WinoPath::X3 ? (plan.x3_h2 ? 3.0 : 6.0) * MN * op.K
                                                                                 : MN * op.Cin * (pk.Kpad == 18 * pk.Cin ? 4.5 : 6.0)};
-    return {f, gemm_f32_kernel_name(a), gemm_f32_route(a).path == F32Path::H2G ? 3.0 * MN * pk.KpadH        // (small batch: a Winograd conv on
-                                        : MN * (op.wino ? pk.Kpad2 : pk.direct ? op.K : pk.Kpad)};           // the direct layout)
+    return {f, gemm_f32_kernel_name(a), gemm_f32_route(a).path == F32Path::H2G ? 3.0 * MN * pk.h2g_Kpad       // (small batch: a Winograd conv on
+                                        : MN * (op.wino ? pk.direct_Kpad : pk.in_place ? op.K : pk.Kpad)};        // the direct layout)
 }
 
 FuseSumArgs Engine::fuse_args(const Op& op, int batch) const {
@@ -310,7 +292,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
             break;
         }
         case OP_FUSE: {
-            if (op.i0 == 1 && !debug) break;
+            if (skipped(op)) break;
             HIP_TRY(launch_fuse_sum(fuse_args(op, batch), s));
             break;
         }
@@ -321,46 +303,46 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
             HIP_TRY(launch_bilinear_resize(ptr(op.in[0]), ptr(op.out), batch, op.H, op.W, op.C, op.Ho, op.Wo, s, op.bf16, ptr(op.aux)));
             break;
         case OP_PREP_EMBED:
-            HIP_TRY(launch_prep_embed(kcrop, k2d, params[op.p0].ptr, params[op.p1].ptr, params[op.p2].ptr,
-                                      ptr(op.out), batch, op.i0, op.i1, op.C, s));
+            HIP_TRY(launch_prep_embed(kcrop, k2d, params[op.coord.w].ptr, params[op.coord.b].ptr, params[op.pos].ptr,
+                                      ptr(op.out), batch, op.smp.J, op.smp.L1, op.C, s));
             break;
         case OP_SAMPLE_REF:
-            HIP_TRY(launch_sample_ref(ptr(op.in[0]), kcrop, ptr(op.out), reinterpret_cast<int*>(ptr(op.aux2)),
-                                      batch, op.i0, op.H, op.W, op.C, s, op.feat_bf16));
+            HIP_TRY(launch_sample_ref(ptr(op.in[0]), kcrop, ptr(op.out), reinterpret_cast<int*>(ptr(op.idx_out)),
+                                      batch, op.smp.J, op.H, op.W, op.C, s, op.feat_bf16));
             break;
         case OP_LAYERNORM:
-            HIP_TRY(launch_layernorm(ptr(op.in[0]), op.amap, ptr(op.aux), op.rmap, params[op.p0].ptr,
-                                     params[op.p1].ptr, op.eps, ptr(op.out), (int)(op.rows_per_frame * batch),
+            HIP_TRY(launch_layernorm(ptr(op.in[0]), op.amap, ptr(op.aux), op.rmap, params[op.ln.w].ptr,
+                                     params[op.ln.b].ptr, op.eps, ptr(op.out), (int)(op.rows_per_frame * batch),
                                      op.C, s, op.out_bf16));
             break;
         case OP_DEFORM: {
             DeformArgs a{};
-            for (int l = 0; l < op.i1; ++l) {
+            for (int l = 0; l < op.smp.L; ++l) {
                 a.feat[l] = ptr(op.in[l]);
                 a.H[l] = op.lvlH[l]; a.W[l] = op.lvlW[l]; a.C[l] = op.lvlC[l];
                 a.U[l] = ptr(op.outs[l]);
             }
             a.AO = ptr(op.aux);
             a.ref = kcrop;
-            a.B = batch; a.J = op.i0; a.L = op.i1; a.NH = op.i2; a.NS = op.i3;
+            a.B = batch; a.J = op.smp.J; a.L = op.smp.L; a.NH = op.smp.NH; a.NS = op.smp.NS;
             a.feat_bf16 = op.feat_bf16;
-            if (debug && op.idxs[0] >= 0) { a.cpos = ptr(op.idxs[0]); a.cidx = reinterpret_cast<int*>(ptr(op.idxs[1])); }
+            if (debug && op.tap_pos >= 0) { a.cpos = ptr(op.tap_pos); a.cidx = reinterpret_cast<int*>(ptr(op.tap_idx)); }
             HIP_TRY(launch_deform_sample(a, s));
             break;
         }
         case OP_EMBED: {
             EmbedArgs a{};
             a.kcrop = kcrop; a.k2d = k2d;
-            a.cw = params[op.p0].ptr; a.cb = params[op.p1].ptr; a.pos = params[op.p2].ptr;
-            for (int l = 0; l < op.i1; ++l) {
+            a.cw = params[op.coord.w].ptr; a.cb = params[op.coord.b].ptr; a.pos = params[op.pos].ptr;
+            for (int l = 0; l < op.smp.L; ++l) {
                 a.feat[l] = ptr(op.in[l]);
                 a.H[l] = op.lvlH[l]; a.W[l] = op.lvlW[l]; a.Cl[l] = op.lvlC[l];
                 a.fw[l] = pack_arena + packs[op.pq[l]].w_off; a.fb[l] = params[op.pb[l]].ptr;
                 a.sampled[l] = ptr(op.outs[l]);
-                a.idx[l] = reinterpret_cast<int*>(ptr(op.idxs[l]));
+                a.idx[l] = reinterpret_cast<int*>(ptr(op.idx_lvl[l]));
             }
             a.X = ptr(op.out);
-            a.BJ = batch * op.i0; a.J = op.i0; a.L = op.i1; a.L1 = op.i2; a.C = op.C;
+            a.BJ = batch * op.smp.J; a.J = op.smp.J; a.L = op.smp.L; a.L1 = op.smp.L1; a.C = op.C;
             a.feat_bf16 = op.feat_bf16;
             HIP_TRY(launch_embed(a, s));
             break;
@@ -368,51 +350,53 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
         case OP_CTX_ATTN: {
             CtxAttnArgs a{};
             const Pack& pk = packs[op.pack];
-            for (int l = 0; l < op.i1; ++l) {
+            for (int l = 0; l < op.smp.L; ++l) {
                 a.feat[l] = ptr(op.in[l]);
                 a.H[l] = op.lvlH[l]; a.W[l] = op.lvlW[l]; a.Cl[l] = op.lvlC[l];
                 a.Wp[l] = pack_arena + packs[op.pq[l]].w_off; a.bp[l] = params[op.pb[l]].ptr;
                 a.U[l] = op.outs[l] >= 0 ? ptr(op.outs[l]) : nullptr;
             }
             a.Wao = pack_arena + pk.w_off; a.bao = pack_arena + pk.b_off; a.ldw = pk.Kpad;
-            a.ln_g = params[op.p0].ptr; a.ln_b = params[op.p1].ptr; a.eps = op.eps;
+            a.ln_g = params[op.ln.w].ptr; a.ln_b = params[op.ln.b].ptr; a.eps = op.eps;
             a.ref = kcrop;
             a.X = ptr(op.out);
-            a.BJ = batch * op.i0; a.J = op.i0; a.L = op.i1; a.L1 = op.i1 + 1; a.C = op.C; a.NH = op.i2; a.NS = op.i3;
+            a.BJ = batch * op.smp.J; a.J = op.smp.J; a.L = op.smp.L; a.L1 = op.smp.L + 1; a.C = op.C; a.NH = op.smp.NH; a.NS = op.smp.NS;
             a.feat_bf16 = op.feat_bf16;
-            if (debug && op.idxs[0] >= 0) { a.cpos = ptr(op.idxs[0]); a.cidx = reinterpret_cast<int*>(ptr(op.idxs[1])); }
+            if (debug && op.tap_pos >= 0) { a.cpos = ptr(op.tap_pos); a.cidx = reinterpret_cast<int*>(ptr(op.tap_idx)); }
             HIP_TRY(launch_ctx_attn(a, s));
             break;
         }
         case OP_ATTENTION:
-            HIP_TRY(launch_attention(ptr(op.in[0]), ptr(op.out), op.i0 * batch, op.i1, op.i2, op.i3, s, op.out_bf16));
+            HIP_TRY(launch_attention(ptr(op.in[0]), ptr(op.out), op.attn.groups * batch, op.attn.tokens, op.attn.heads, op.attn.head_dim, s, op.out_bf16));
             break;
         case OP_RES_CHAIN: {
             ResBlockW blk[8];
-            for (int i = 0; i < op.i2; ++i) {
-                const int* c = &op.chain[8 * i];
-                const Pack *q = &packs[c[0]], *pr = &packs[c[1]], *f1 = &packs[c[2]], *f2 = &packs[c[3]];
-                if (!q->chain || !pr->chain || !f1->chain || !f2->chain || q->KpadH != q->K || f2->KpadH != f2->K) return CAPF_ERR_STATE;
-                blk[i] = ResBlockW{params[c[4]].ptr, params[c[5]].ptr, pack_arena + q->wc_off, params[q->b[0]].ptr, pack_arena + pr->wc_off,
-                                   params[pr->b[0]].ptr, params[c[6]].ptr, params[c[7]].ptr, pack_arena + f1->wc_off, params[f1->b[0]].ptr,
-                                   pack_arena + f2->wc_off, params[f2->b[0]].ptr};
+            const int nblk = (int)op.blocks.size();
+            for (int i = 0; i < nblk; ++i) {
+                const ChainBlock& c = op.blocks[i];
+                const Pack *q = &packs[c.qkv], *pr = &packs[c.proj], *f1 = &packs[c.fc1], *f2 = &packs[c.fc2];
+                if (!q->chain || !pr->chain || !f1->chain || !f2->chain || q->h2g_Kpad != q->K || f2->h2g_Kpad != f2->K) return CAPF_ERR_STATE;
+                blk[i] = ResBlockW{params[c.norm1.w].ptr, params[c.norm1.b].ptr, pack_arena + q->chain_off, params[q->b[0]].ptr, pack_arena + pr->chain_off,
+                                   params[pr->b[0]].ptr, params[c.norm2.w].ptr, params[c.norm2.b].ptr, pack_arena + f1->chain_off, params[f1->b[0]].ptr,
+                                   pack_arena + f2->chain_off, params[f2->b[0]].ptr};
             }
-            HIP_TRY(launch_res_chain(ptr(op.out), (int)(op.rows_per_frame * batch), op.i0, op.i1, op.eps, blk, op.i2, s));
+            HIP_TRY(launch_res_chain(ptr(op.out), (int)(op.rows_per_frame * batch), op.attn.tokens, op.attn.heads, op.eps, blk, nblk, s));
             break;
         }
         case OP_MLP_CHAIN: {
-            const Pack *f1 = &packs[op.chain[0]], *f2 = &packs[op.chain[1]];
-            if (!f1->chain || !f2->chain || f1->KpadH != f1->K || f2->KpadH != f2->K) return CAPF_ERR_STATE;
+            const ChainBlock& c = op.blocks[0];
+            const Pack *f1 = &packs[c.fc1], *f2 = &packs[c.fc2];
+            if (!f1->chain || !f2->chain || f1->h2g_Kpad != f1->K || f2->h2g_Kpad != f2->K) return CAPF_ERR_STATE;
             ResBlockW w{};
-            w.ln2_g = params[op.chain[2]].ptr; w.ln2_b = params[op.chain[3]].ptr;
-            w.wfc1 = pack_arena + f1->wc_off; w.bfc1 = params[f1->b[0]].ptr;
-            w.wfc2 = pack_arena + f2->wc_off; w.bfc2 = params[f2->b[0]].ptr;
+            w.ln2_g = params[c.norm2.w].ptr; w.ln2_b = params[c.norm2.b].ptr;
+            w.wfc1 = pack_arena + f1->chain_off; w.bfc1 = params[f1->b[0]].ptr;
+            w.wfc2 = pack_arena + f2->chain_off; w.bfc2 = params[f2->b[0]].ptr;
             HIP_TRY(launch_mlp_chain(ptr(op.out), op.amap, (int)(op.rows_per_frame * batch), op.eps, w, s));
             break;
         }
         case OP_HEAD:
-            HIP_TRY(launch_head(ptr(op.in[0]), params[op.p0].ptr, params[op.p1].ptr, op.eps, params[op.p2].ptr,
-                                params[op.p3].ptr, out, (int)(op.rows_per_frame * batch), op.C, op.i0, s));
+            HIP_TRY(launch_head(ptr(op.in[0]), params[op.ln.w].ptr, params[op.ln.b].ptr, op.eps, params[op.head.w].ptr,
+                                params[op.head.b].ptr, out, (int)(op.rows_per_frame * batch), op.C, op.head.N, s));
             break;
         default: break;
     }
@@ -470,7 +454,7 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
             int fm[4], nf = 0;
             for (int oi : level) {
                 const Op& op = ops[oi];
-                if (op.kind != OP_FUSE || (op.i0 == 1 && !debug) || !mine(op)) continue;
+                if (op.kind != OP_FUSE || skipped(op) || !mine(op)) continue;
                 if (nf > 0 && (op.bf16 != ops[fm[0]].bf16 || (op.C % 8 == 0) != (ops[fm[0]].C % 8 == 0))) continue;
                 if (nf == 4) break;
                 fg[nf] = fuse_args(op, batch);
@@ -485,7 +469,7 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
                 const Op& op = ops[oi];
                 if (!mine(op)) continue;
                 if (op.kind == OP_GEMM && groupable(op, gemm_args(op, batch))) continue;
-                if (op.kind == OP_FUSE && op.i0 == 1 && !debug) continue;
+                if (skipped(op)) continue;
                 bool done = false;
                 for (int k = 0; k < nf; ++k) done |= fm[k] == oi;
                 if (done) continue;
@@ -502,7 +486,7 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
 // the product schedule (grouped launches included).
 int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t* ev, LaunchLog* log) {
     hipStream_t main_stream = s;
-    if (use_h2g && (batch >= H2G_MIN_BATCH || has_res_chain) && last_op > n_backbone_ops && !bf16()) {      // (the fused res blocks read the packs at every batch)
+    if (plan.use_h2g && (batch >= H2G_MIN_BATCH || has_res_chain) && last_op > n_backbone_ops && !bf16()) {      // (the fused res blocks read the packs at every batch)
         const int rc = ensure_h2g_lifter(s);
         if (rc) return rc;
     }
@@ -535,18 +519,18 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
                     // {0}|{1,2,3} 6398.  Across the configurations: cfg1 +0.4..1.2 %, cfg2 +0.9 %, cfg4 +1.3 %, but -0.8 % at batch 512 (every launch already fills
                     // the chip many times over), and below batch 16 a region is a handful of tiles (and may use the split-K scratch):
                     // one chain outside 16..256.
-                    const bool two = lanes == 3 && !log && side[0] && op.i0 >= 2 && batch >= 16 && batch <= 256;
+                    const bool two = lanes == 3 && !log && side[0] && op.fork.lanes >= 2 && batch >= 16 && batch <= 256;
                     if (two) {
-                        HIP_TRY(hipEventRecord(events[op.i1], main_stream));
-                        HIP_TRY(hipStreamWaitEvent(side[0], events[op.i1], 0));
+                        HIP_TRY(hipEventRecord(events[op.fork.first_event], main_stream));
+                        HIP_TRY(hipStreamWaitEvent(side[0], events[op.fork.first_event], 0));
                         on_side_chain = true;
                         int rc = run_region_grouped(side[0], batch, op.region, nullptr, 0x6u);
                         on_side_chain = false;
                         if (rc) return rc;
                         rc = run_region_grouped(main_stream, batch, op.region, nullptr, ~0x6u);
                         if (rc) return rc;
-                        HIP_TRY(hipEventRecord(events[op.i1 + 1], side[0]));
-                        HIP_TRY(hipStreamWaitEvent(main_stream, events[op.i1 + 1], 0));
+                        HIP_TRY(hipEventRecord(events[op.fork.first_event + 1], side[0]));
+                        HIP_TRY(hipStreamWaitEvent(main_stream, events[op.fork.first_event + 1], 0));
                         oi = regions[op.region].second;
                         break;
                     }
@@ -554,21 +538,21 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
                     if (rc) return rc;
                     oi = regions[op.region].second;      // continue after the join
                 } else if (par) {
-                    HIP_TRY(hipEventRecord(events[op.i1], main_stream));
-                    for (int l = 1; l < op.i0; ++l) HIP_TRY(hipStreamWaitEvent(side[l - 1], events[op.i1], 0));
+                    HIP_TRY(hipEventRecord(events[op.fork.first_event], main_stream));
+                    for (int l = 1; l < op.fork.lanes; ++l) HIP_TRY(hipStreamWaitEvent(side[l - 1], events[op.fork.first_event], 0));
                 }
                 break;
             }
             case OP_JOIN:
                 if (par) {
-                    for (int l = 1; l < op.i0; ++l) {
-                        HIP_TRY(hipEventRecord(events[op.i1 + l], side[l - 1]));
-                        HIP_TRY(hipStreamWaitEvent(main_stream, events[op.i1 + l], 0));
+                    for (int l = 1; l < op.fork.lanes; ++l) {
+                        HIP_TRY(hipEventRecord(events[op.fork.first_event + l], side[l - 1]));
+                        HIP_TRY(hipStreamWaitEvent(main_stream, events[op.fork.first_event + l], 0));
                     }
                 }
                 break;
             default: {
-                if (op.kind == OP_FUSE && op.i0 == 1 && !debug) break;
+                if (skipped(op)) break;
                 if (log) HIP_TRY(log->mark(s, &oi, 1));
                 int rc = exec_op(op, s, batch);
                 if (rc) return rc;
@@ -1240,6 +1224,8 @@ int capf_op_bytes(const capf_handle* h, int index, int batch, double* bytes) {
     const capf::Op& op = e.ops[index];
     const double B = batch, act = op.bf16 ? 2.0 : 4.0;
     const double fact = op.feat_bf16 ? 2.0 : 4.0;                             // the lifter samplers: bytes per context-map element
+    const capf::Sampler& sm = op.smp;
+    const capf::Attn& at = op.attn;
     double b = 0.0;
     switch (op.kind) {
         case capf::OP_GEMM: {
@@ -1255,7 +1241,7 @@ int capf_op_bytes(const capf_handle* h, int index, int batch, double* bytes) {
                 + (double)pk.N * pk.K * (pk.bf16 ? 2.0 : 4.0) + (double)pk.N * 4.0
                 + M * op.N * (op.st_f32 ? 4.0 + (op.sh >= 0 ? 2.0 : 0.0) : op.out_bf16 ? 2.0 : act)   // (fp32 stream: fp32 result + bf16 shadow)
                 + ((op.aux >= 0 || op.res_param >= 0) ? M * op.N * (op.f32s ? 4.0 : act) : 0.0)
-                + ((op.conv && op.in[1] >= 0) ? B * op.i0 * op.i1 * op.N * act : 0.0);      // (the low-resolution map added behind the activation)
+                + ((op.conv && op.up_in >= 0) ? B * op.up_H * op.up_W * op.N * act : 0.0);    // (the low-resolution map added behind the activation)
             break;
         }
         case capf::OP_FUSE: {
@@ -1272,35 +1258,35 @@ int capf_op_bytes(const capf_handle* h, int index, int batch, double* bytes) {
             b = (double)op.rows_per_frame * B * op.C * 4.0 * (op.aux >= 0 ? 3.0 : 2.0);
             break;
         case capf::OP_ATTENTION:
-            b = (double)op.i0 * B * op.i1 * op.i2 * op.i3 * 4.0 * 4.0;          // q, k, v in; o out
+            b = (double)at.groups * B * at.tokens * at.heads * at.head_dim * 4.0 * 4.0;       // q, k, v in; o out
             break;
         case capf::OP_SAMPLE_REF:
-            b = B * op.i0 * op.C * (4.0 * fact + 4.0);                          // 4 corners per joint + the sampled row
+            b = B * sm.J * op.C * (4.0 * fact + 4.0);                       // 4 corners per joint + the sampled row
             break;
         case capf::OP_DEFORM:
-            for (int l = 0; l < op.i1; ++l) b += B * op.i0 * op.i2 * op.lvlC[l] * (4.0 * op.i3 * fact + 4.0);
-            b += B * op.i0 * op.i1 * 3.0 * op.i2 * op.i3 * 4.0;
+            for (int l = 0; l < sm.L; ++l) b += B * sm.J * sm.NH * op.lvlC[l] * (4.0 * sm.NS * fact + 4.0);
+            b += B * sm.J * sm.L * 3.0 * sm.NH * sm.NS * 4.0;
             break;
         case capf::OP_HEAD:
             b = (double)op.rows_per_frame * B * (op.C + 3.0) * 4.0;
             break;
         case capf::OP_RES_CHAIN:                                                 // the token rows in and out, the blocks' weights once
-            b = (double)op.rows_per_frame * B * op.C * 4.0 * 2.0 + (double)op.i2 * 8.0 * op.C * op.C * 4.0;
+            b = (double)op.rows_per_frame * B * op.C * 4.0 * 2.0 + (double)op.blocks.size() * 8.0 * op.C * op.C * 4.0;
             break;
         case capf::OP_MLP_CHAIN:
             b = (double)op.rows_per_frame * B * op.C * 4.0 * 2.0 + 4.0 * op.C * op.C * 4.0;
             break;
         case capf::OP_PREP_EMBED:
-            b = B * op.i0 * (op.C + 4.0) * 4.0;
+            b = B * sm.J * (op.C + 4.0) * 4.0;
             break;
         case capf::OP_EMBED:
-            b = B * op.i0 * (op.i2 * op.C + 4.0) * 4.0;                          // tokens written
-            for (int l = 0; l < op.i1; ++l) b += B * op.i0 * op.lvlC[l] * 4.0 * fact + (double)op.C * op.lvlC[l] * 4.0;
+            b = B * sm.J * (sm.L1 * op.C + 4.0) * 4.0;                       // tokens written
+            for (int l = 0; l < sm.L; ++l) b += B * sm.J * op.lvlC[l] * 4.0 * fact + (double)op.C * op.lvlC[l] * 4.0;
             break;
         case capf::OP_CTX_ATTN:
-            for (int l = 0; l < op.i1; ++l)
-                b += B * op.i0 * op.i2 * op.i3 * op.lvlC[l] * 4.0 * fact + (double)(op.C / op.i2) * op.lvlC[l] * 4.0;
-            b += B * op.i0 * (op.i1 + 1 + op.i1) * op.C * 4.0;                    // tokens read, tokens 1..L written
+            for (int l = 0; l < sm.L; ++l)
+                b += B * sm.J * sm.NH * sm.NS * op.lvlC[l] * 4.0 * fact + (double)(op.C / sm.NH) * op.lvlC[l] * 4.0;
+            b += B * sm.J * (sm.L + 1 + sm.L) * op.C * 4.0;                 // tokens read, tokens 1..L written
             break;
         default: break;
     }
@@ -1325,15 +1311,18 @@ int capf_op_schedule(const capf_handle* h, int index, int32_t* region, int32_t* 
                     if (oi == index) *level = (int32_t)l;
         }
     }
+    // The ABI's layout is Op::reads() / writes() without their last slot, which has no column of its own here: the map a conv adds behind
+    // its activation is reported as its second input (a conv has one), the bf16 shadow in the first outs[] column (a conv / fuse sum writes
+    // no outs[])
     if (reads) {
-        for (int i = 0; i < 4; ++i) reads[i] = op.in[i];
-        reads[4] = op.aux;
+        const auto r = op.reads();
+        std::copy(r.begin(), r.begin() + 5, reads);
+        if (r[5] >= 0) reads[1] = r[5];
     }
     if (writes) {
-        writes[0] = op.out;
-        writes[1] = op.aux2;
-        for (int i = 0; i < 4; ++i) writes[2 + i] = op.outs[i];
-        if (op.sh >= 0) writes[2] = op.sh;          // (a conv / fuse sum writes no outs[]: its bf16 shadow takes the first of those slots)
+        const auto w = op.writes();
+        std::copy(w.begin(), w.begin() + 6, writes);
+        if (w[6] >= 0) writes[2] = w[6];
     }
     return CAPF_OK;
 }
@@ -1359,7 +1348,7 @@ int capf_op_describe(const capf_handle* h, int index, capf_op_desc* d) {
     memset(d, 0, sizeof(*d));
     d->kind = op.kind == capf::OP_GEMM ? 0 : op.kind == capf::OP_FUSE ? 1 : op.kind == capf::OP_MAXPOOL ? 2
               : op.kind == capf::OP_RESIZE ? 3 : op.kind == capf::OP_LAYERNORM ? 4 : op.kind == capf::OP_ATTENTION ? 5 : -1;
-    if (op.kind == capf::OP_FUSE && op.i0 == 1) d->kind = -1;          // debug copy
+    if (op.debug_only) d->kind = -1;
     d->backbone = index < e.n_backbone_ops;
     d->p_weight = d->p_bn_weight = d->p_bias = d->p_ln_weight = d->p_ln_bias = -1;
     d->rows_per_frame = (int)op.rows_per_frame;
@@ -1376,29 +1365,30 @@ int capf_op_describe(const capf_handle* h, int index, capf_op_desc* d) {
         d->conv = op.conv; d->Cin = op.conv ? op.Cin : op.K; d->Cout = op.N;
         d->ks = op.ks; d->stride = op.stride; d->pad = op.pad; d->act = op.act;
         d->has_residual = op.aux >= 0 || op.res_param >= 0;
-        if (op.conv && op.in[1] >= 0) { d->up_H = op.i0; d->up_W = op.i1; }
+        if (op.conv && op.up_in >= 0) { d->up_H = op.up_H; d->up_W = op.up_W; }
         d->mfma_bf16 = (op.bf16 || op.out_bf16) ? 1 : 0;
         if (op.conv) {
             d->in_dtype = op.in[0] == -2 ? 0 : (op.bf16 ? 2 : 0);
             d->out_dtype = op.st_f32 ? 0 : (op.bf16 || op.out_bf16) ? 2 : 0;
-            d->p_weight = pk.w[0]; d->p_bn_weight = pk.bn_g;
+            d->p_weight = pk.w[0]; d->p_bn_weight = pk.bn.g;
         } else {
             d->in_dtype = op.bf16 == 2 ? 2 : 0;
             d->out_dtype = op.out_bf16 ? 2 : 0;
             d->p_weight = pk.n_lin == 1 ? pk.w[0] : -1;
             d->p_bias = pk.n_lin == 1 ? pk.b[0] : -1;
-            d->p_ln_weight = op.ln_w; d->p_ln_bias = op.ln_b;
+            d->p_ln_weight = op.ln.w; d->p_ln_bias = op.ln.b;
         }
     } else if (op.kind == capf::OP_LAYERNORM) {
         d->Cin = d->Cout = op.C;
         d->in_dtype = 0; d->out_dtype = op.out_bf16 ? 2 : 0;
         d->has_residual = op.aux >= 0;
-        d->p_ln_weight = op.p0; d->p_ln_bias = op.p1;
+        d->p_ln_weight = op.ln.w; d->p_ln_bias = op.ln.b;
         d->maps[1][0] = 1; d->maps[1][1] = op.C; d->maps[1][2] = 0; d->maps[1][3] = 0;        // normalised rows are written densely
     } else if (op.kind == capf::OP_ATTENTION) {
-        d->attn[0] = op.i0; d->attn[1] = op.i1; d->attn[2] = op.i2; d->attn[3] = op.i3;
-        d->rows_per_frame = op.i0 * op.i1;
-        d->Cin = 3 * op.i2 * op.i3; d->Cout = op.i2 * op.i3;
+        const capf::Attn& at = op.attn;
+        d->attn[0] = at.groups; d->attn[1] = at.tokens; d->attn[2] = at.heads; d->attn[3] = at.head_dim;
+        d->rows_per_frame = at.groups * at.tokens;
+        d->Cin = 3 * at.heads * at.head_dim; d->Cout = at.heads * at.head_dim;
         d->in_dtype = 0; d->out_dtype = op.out_bf16 ? 2 : 0;
         d->maps[0][0] = 1; d->maps[0][1] = d->Cin; d->maps[1][0] = 1; d->maps[1][1] = d->Cout;
     } else {
@@ -1427,7 +1417,9 @@ int capf_op_tensor(const capf_handle* h, int index, int slot, const void** dev_p
     if (!h || !dev_ptr || index < 0 || index >= (int)h->e.ops.size() || slot < 0 || slot > 6) return CAPF_ERR_INVALID;
     const Engine& e = h->e;
     const capf::Op& op = e.ops[index];
-    const int buf = slot < 4 ? op.in[slot] : slot == 4 ? op.aux : slot == 5 ? op.out : op.sh;
+    // slots 0..4: capf_op_schedule's reads (the map a conv adds behind its activation in slot 1), 5: the output, 6: its bf16 shadow
+    const auto r = op.reads();
+    const int buf = slot == 1 && r[5] >= 0 ? r[5] : slot < 5 ? r[slot] : slot == 5 ? op.out : op.sh;
     if (buf == -2) { *dev_ptr = e.images; return CAPF_OK; }
     if (buf < 0 || !e.ws || e.last_batch <= 0) return CAPF_ERR_INVALID;
     *dev_ptr = e.bptr(buf, e.last_batch);
@@ -1506,7 +1498,7 @@ int capf_forward_stats(const capf_handle* h, int batch, int64_t* launches, doubl
     int64_t n = 0;
     double f = 0.0;
     for (const capf::Op& op : h->e.ops) {
-        if (op.kind == capf::OP_FUSE && op.i0 == 1) continue;
+        if (op.debug_only) continue;
         if (op.kind == capf::OP_FORK || op.kind == capf::OP_JOIN) continue;
         ++n;
         f += op.flops_per_frame * batch;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <array>
 #include <map>
 #include <string>
 #include <vector>
@@ -41,32 +42,37 @@ struct Tensor {  // NHWC view of a buffer (per frame), or [rows, C] for the lift
     int H = 0, W = 0, C = 0;
 };
 
-// A private packed copy derived from borrowed parameters (rebuilt by capf_params_changed).
+// nn.BatchNorm2d (eval): weight, bias, running_mean, running_var as parameter indices
+struct BnRef { int g = -1, b = -1, m = -1, v = -1; };
+
+// A private packed copy derived from borrowed parameters (rebuilt by capf_params_changed): one primary layout and, per flag below, further
+// copies of the same weights for the kernels that want them laid out differently.  Every copy has its own offset (elements inside the pack
+// arena) and, where its rows are padded, its own padded K; Engine::build lays them out, Engine::repack fills them, gemm_args hands them out
+enum PackKind { CONV_BN = 0, LINEAR = 1 };   // conv with its eval BatchNorm folded in | nn.Linear (possibly several concatenated along N)
 struct Pack {
-    int kind = 0;            // 0 conv+BN fold, 1 linear (possibly several linears concatenated along N)
+    PackKind kind = CONV_BN;
     int w[4] = {-1, -1, -1, -1}, b[4] = {-1, -1, -1, -1};   // param indices (linear: up to 4 concatenated)
     int n_lin = 0;
-    int bn_g = -1, bn_b = -1, bn_m = -1, bn_v = -1;
-    int N = 0, K = 0, Kpad = 0, Cin = 0, ks = 1;
-    size_t w_off = 0, b_off = 0;   // element offsets inside the pack arena
-    size_t w2_off = 0;             // wino packs: the direct-kernel layout [N][Kpad2] as well (small batches run the direct kernel)
-    int Kpad2 = 0;
-    bool quad = false;             // linear for the fused lifter kernels: Wq[k / 4][n][4] (lanes n read consecutive 16-byte quads)
-    bool direct = false;           // linear with Kpad == K and no concat: use the parameter in place
-    bool bf16 = false;             // conv weights packed as bf16 (Kpad % 64 == 0)
-    bool rh = false;               // bf16 3x3 stride-1 conv: a second copy in the row-halo layout ([N][9 * Cin] bf16) at w2_off
-    bool ws = false;               // bf16 3x3 stride-1 conv: a copy in the 2-D halo tile's layout (igemm_bf16_ws.hip) at w3_off
-    bool x3 = false;               // fp32 3x3 stride-1 conv: a copy for the split-fp32 tiles at w3_off -- two block-scaled fp16 pieces
-                                   // (igemm_f32h2_ws.hip; Engine::x3_h2) or three bf16 pieces (igemm_f32x3_ws.hip)
-    size_t w3_off = 0;
-    bool h2g = false;              // fp32 conv / linear: a copy as two block-scaled fp16 pieces for igemm_f32h2.hip ([N][KpadH] floats + [N] inverse
-    size_t wc_off = 0;             // chain: the h2g pack in MFMA fragment order for lifter_chain.hip (launch_res_chain_repack)
-    bool chain = false;
-    size_t wh_off = 0;             // channel scales) at wh_off; KpadH = the direct fp32 layout's padded K
-    int KpadH = 0;
-    bool wino = false;             // conv weights in the Winograd F(2,3) layout of igemm_wino.hip (Kpad = 12 * Cin)
+    BnRef bn;
+    int N = 0, K = 0, Cin = 0, ks = 1;
+    // ---- the primary layout: [N][Kpad] at w_off, the folded bias (conv) or the concatenated biases (linear) at b_off
+    size_t w_off = 0, b_off = 0;
+    int Kpad = 0;
+    bool in_place = false;         // linear with Kpad == K and no concat: no copy at all, the kernels read the parameter itself
+    bool bf16 = false;             // ... stored as bf16 (Kpad % 64 == 0): conv weights, or a linear for the bf16 MFMA projections
+    bool quad = false;             // ... a linear for the fused lifter kernels: Wq[k / 4][n][4] (lanes n read consecutive 16-byte quads)
+    bool wino = false;             // ... conv weights in the Winograd layout of igemm_wino.hip (Kpad = 12 * Cin for F(2,3), 18 * Cin for F(4,3))
     bool wino_skip = false;        // ... which no batch up to cfg.max_batch can reach (a split-fp32 tile takes the conv from its first Winograd batch to
                                    // max_batch): not packed, no arena space; the conv never runs a Winograd kernel (build())
+    // ---- the further copies: flag, offset, padded K
+    size_t direct_off = 0; int direct_Kpad = 0;                  // wino: the direct kernel's layout [N][direct_Kpad] as well (small batches run the direct kernel)
+    bool rh = false; size_t rh_off = 0; int rh_Kpad = 0;         // bf16 3x3 stride-1 conv: the row-halo layout, [N][rh_Kpad = 9 * Cin] bf16 (igemm_bf16.hip)
+    bool ws = false; size_t ws_off = 0;                          // bf16 3x3 stride-1 conv: the 2-D halo tile's layout (igemm_bf16_ws.hip)
+    bool x3 = false; size_t x3_off = 0;                          // fp32 3x3 stride-1 conv: what the split-fp32 tiles take -- two block-scaled fp16 pieces
+                                                                 // (igemm_f32h2_ws.hip; Engine::plan.x3_h2) or three bf16 pieces (igemm_f32x3_ws.hip)
+    bool h2g = false; size_t h2g_off = 0; int h2g_Kpad = 0;      // fp32 conv / linear: two block-scaled fp16 pieces for igemm_f32h2.hip, [N][h2g_Kpad] floats +
+                                                                 // [N] inverse channel scales; h2g_Kpad = the direct fp32 layout's padded K
+    bool chain = false; size_t chain_off = 0;                    // ... and that copy once more in MFMA fragment order for lifter_chain.hip (launch_res_chain_repack)
 };
 
 // The lifter's layers (pose_dformer.py:144-241), resolved once where build_lifter registers the schema: parameter indices and shapes.
@@ -96,16 +102,29 @@ enum OpKind {
     OP_ATTENTION, OP_HEAD, OP_FORK, OP_JOIN, OP_EMBED, OP_CTX_ATTN, OP_RES_CHAIN, OP_MLP_CHAIN
 };
 
+// Per-kind payloads of an Op, held by value (an op of another kind leaves them at their defaults)
+struct Fork { int lanes = 0, first_event = 0; };                    // OP_FORK / OP_JOIN: lanes of the region, first of its event ids
+struct Sampler { int J = 0, L = 0, L1 = 0, NH = 0, NS = 0; };       // the lifter's samplers: joints, levels, L + 1 tokens, deform heads / samples
+struct Attn { int groups = 0, tokens = 0, heads = 0, head_dim = 0; };   // OP_ATTENTION (groups per frame); OP_RES_CHAIN: tokens and heads
+struct ChainBlock { int qkv = -1, proj = -1, fc1 = -1, fc2 = -1; LnRef norm1, norm2; };   // packs and LayerNorms of one block (lifter_chain.hip)
+
 struct Op {
     OpKind kind = OP_GEMM;
     std::string name;
     // buffers (ids; -1 unused; -2 = external "images" input)
     int in[4] = {-1, -1, -1, -1};
-    int aux = -1;                 // residual / add input
+    int aux = -1;                 // residual / rows added (GEMM, resize, LayerNorm); OP_DEFORM: the attention / offset rows.  An input
+    int up_in = -1, up_H = 0, up_W = 0;   // OP_GEMM conv: the low-resolution map added, upsampled, behind the activation, and its size (build_cpn)
     int out = -1;
-    int aux2 = -1;                // secondary output (idx buffer)
+    int idx_out = -1;             // OP_SAMPLE_REF: the corner-index rows, a second output
+    int outs[4] = {-1, -1, -1, -1};       // per-level outputs: OP_EMBED sampled rows, OP_DEFORM / OP_CTX_ATTN sample sums U
+    // What the op reads and writes, slot by slot (-1: unused) -- the ONE list behind schedule_regions, plan_f32_stream, capf_op_schedule and
+    // capf_op_tensor.  Not listed: the debug taps (tap_pos / tap_idx, written by a debug run only) and OP_EMBED's idx_lvl rows -- named
+    // tensors that live to the end of the forward in memory of their own, which no op reads
+    std::array<int, 6> reads() const { return {in[0], in[1], in[2], in[3], aux, up_in}; }
+    std::array<int, 7> writes() const { return {out, idx_out, outs[0], outs[1], outs[2], outs[3], sh}; }
     // gemm
-    int pack = -1;
+    int pack = -1;                // (OP_CTX_ATTN: the quad pack of [attention_weights | sampling_offsets])
     int conv = 0, Cin = 0, H = 0, W = 0, Ho = 0, Wo = 0, ks = 1, stride = 1, pad = 0;
     long rows_per_frame = 0;      // M = rows_per_frame * batch
     int N = 0, K = 0, act = 0;
@@ -113,16 +132,23 @@ struct Op {
     int res_param = -1;           // residual read from a parameter (pos-embed) instead of a buffer
     // fuse / resize / pool
     int n_in = 0, shift[4] = {0, 0, 0, 0}, relu = 0, C = 0;
-    // lifter misc
-    int p0 = -1, p1 = -1, p2 = -1, p3 = -1;  // parameter indices (meaning depends on kind)
+    bool debug_only = false;      // OP_FUSE as a plain copy into a named tensor: runs under capf_set_debug only (Engine::skipped)
+    Fork fork;
+    // lifter
+    LnRef ln;                     // the LayerNorm this op applies, eps in `eps`: OP_LAYERNORM, OP_CTX_ATTN (norm1), OP_HEAD, and an OP_GEMM in rows
+                                  // mode that normalises its A rows on the fly
     float eps = 0.f;
-    int i0 = 0, i1 = 0, i2 = 0, i3 = 0;      // small ints (meaning depends on kind)
+    Sampler smp;                  // OP_EMBED, OP_PREP_EMBED, OP_SAMPLE_REF, OP_DEFORM, OP_CTX_ATTN (each sets what its kernel takes)
+    LinearRef coord;              // OP_EMBED / OP_PREP_EMBED: coord_embed ...
+    int pos = -1;                 // ... and Spatial_pos_embed
+    LinearRef head;               // OP_HEAD: the head's linear (head.N output columns)
+    Attn attn;
+    std::vector<ChainBlock> blocks;   // OP_RES_CHAIN: its blocks; OP_MLP_CHAIN: one entry {fc1, fc2, norm2}, rows through amap
     int lvlH[4] = {0, 0, 0, 0}, lvlW[4] = {0, 0, 0, 0}, lvlC[4] = {0, 0, 0, 0};
-    int outs[4] = {-1, -1, -1, -1};
-    int idxs[4] = {-1, -1, -1, -1};          // OP_EMBED: corner-index tap buffers
-    int pq[4] = {-1, -1, -1, -1};   // ... and their quad-interleaved packs
-    int pb[4] = {-1, -1, -1, -1};   // per-level bias parameters (OP_EMBED feat_embed, OP_CTX_ATTN embed_proj)
-    int ln_w = -1, ln_b = -1;                // OP_GEMM rows mode: LayerNorm the A rows on the fly (parameter indices), eps in `eps`
+    int idx_lvl[4] = {-1, -1, -1, -1};       // OP_EMBED: corner-index rows per level
+    int tap_pos = -1, tap_idx = -1;          // OP_DEFORM / OP_CTX_ATTN: debug taps of the sampling site (positions as floats, NW corner indices)
+    int pq[4] = {-1, -1, -1, -1};   // per-level quad-interleaved packs (OP_EMBED feat_embed, OP_CTX_ATTN embed_proj) ...
+    int pb[4] = {-1, -1, -1, -1};   // ... and their bias parameters
     double flops_per_frame = 0.0;
     int bf16 = 0;                 // tensors of this op are bf16 (conv: bf16 MFMA kernel)
     int wino = 0;                 // 3x3 stride-1 fp32 conv on the Winograd kernel (igemm_wino.hip)
@@ -132,8 +158,6 @@ struct Op {
     int out_bf16 = 0;             // fp32 stem conv writing bf16 activations
     int h2_exps = -1, h2_role = 0, h2_peer = -1;   // a BasicBlock's conv1 (role 1: writes planes + exponents to buffer h2_exps) / conv2 (role 2: reads them);
                                   // h2_peer = the other op's index: both must run the two-fp16-piece tile at a batch for the pair to use planes
-    std::vector<int> chain;       // OP_RES_CHAIN: per block {pack qkv, proj, fc1, fc2, param norm1.weight, .bias, norm2.weight, .bias};
-                                  // OP_MLP_CHAIN: {pack fc1, fc2, param norm2.weight, .bias}, rows through amap
     long h2_utab = -1;            // two-fp16-piece conv tile: word offset of this conv's map geometry in the engine's unit tables (-1: none)
     // CAPF_PLAN_BF16_F32_STREAM (Engine::plan_f32_stream): f32s = a bf16 conv with the fp32-stream epilogue (its residual, if any, is fp32);
     // st_f32 = the output is stored fp32 (conv or fuse sum); sh = buffer of its bf16 shadow, what the convs that read it take as operand (-1: none)
@@ -198,6 +222,34 @@ struct Engine {
     int device = -1;
     std::string err;
 
+    // ---- plan switches: what cfg.plan_flags (and, in the diagnostic build, the CAPF_* knobs of diag_env) chose.  Set once by
+    // set_plan_switches() before anything is planned; constant afterwards
+    struct PlanSwitches {
+        bool fused_lifter = true;      // fused embed / context-attention kernels + LayerNorm folded into the GEMMs (CAPF_PLAN_NO_FUSED_LIFTER, CAPF_LIFTER_FUSED=0:
+                                       // the one-kernel-per-op plan, for A/B runs)
+        bool use_wino = true;          // Winograd F(2,3) kernel for the eligible 3x3 stride-1 fp32 convs (CAPF_PLAN_NO_WINOGRAD, CAPF_WINO=0: direct kernel everywhere)
+        bool wino_f43 = true;          // F(4,3) where W % 4 == 0, F(2,3) for the other even widths (CAPF_PLAN_WINOGRAD_F23_ONLY, CAPF_WINO_F43=0: F(2,3) everywhere)
+        bool wino_f43_cpn = false;
+        int wino_f43_min_hw = 0, wino_f43_max_hw = 1 << 30;   // F(4,3) only for maps with min <= H * W <= max pixels
+        int wino_min_batch = 24;       // below this batch the Winograd-eligible convs the split-fp32 tile does not take run the direct kernel (with
+                                       // split-K; batch 16: 4.75 vs 5.86 ms per forward, batch 24: 6.08 vs 6.37)
+        bool use_rh = true;            // row-halo layout + kernel for the bf16 3x3 stride-1 convs (CAPF_PLAN_NO_ROW_HALO, CAPF_BF16_RH=0: off, A/B runs)
+        bool use_ws = true;            // 2-D halo layout + kernel for the bf16 3x3 stride-1 convs (CAPF_PLAN_NO_WS clears it)
+        bool use_x3 = true;            // split-fp32 tile for the Winograd-eligible fp32 3x3 stride-1 convs (CAPF_PLAN_NO_F32X3 clears it)
+        bool x3_h2 = true;             // ... the two-fp16-piece tile (three piece products per MAC); CAPF_PLAN_F32X3_EXACT: the three-bf16-piece tile (six)
+        bool use_h2g = true;           // every other fp32 conv / linear of an inference batch >= 5 on the two-fp16-piece GEMM (igemm_f32h2.hip;
+                                       // CAPF_PLAN_NO_F32H2_GEMM clears it)
+        bool use_h2_planes = false;    // CAPF_PLAN_H2_PLANES sets it (opt-in: measured slower, EXPERIMENTS R6.5)
+        bool use_pwchain = true;       // CAPF_PLAN_NO_PWCHAIN clears it
+        bool use_bneck = true;         // CAPF_PLAN_NO_BNECK clears it
+        bool use_upadd = true;         // CAPF_PLAN_NO_UPADD clears it (CPN bf16: lateral conv + upsampled add in one launch)
+        bool batch_reduce = true;      // CAPF_PLAN_NO_BATCHED_REDUCE clears it: the backward's second-stage reductions one launch each
+        bool f32_stream = false;       // CAPF_PLAN_BF16_F32_STREAM: bf16 only as conv operands, every other backbone tensor fp32
+    } plan;
+    bool set_plan_switches();
+    static constexpr int H2G_MIN_BATCH = 5;
+
+    // ---- schema / plan data (plan.cpp)
     std::vector<Param> params;
     std::map<std::string, int> param_index;
     std::vector<Buffer> bufs;
@@ -207,15 +259,45 @@ struct Engine {
     int cur_lane = 0, cur_region = -1, n_regions = 0, n_events = 0;
     std::vector<std::pair<int, int>> regions;   // [fork op, join op]
     std::vector<std::vector<std::vector<int>>> region_levels;   // per region: dependency levels -> op indices
-    void schedule_regions();
     std::map<std::string, NamedTensor> named;
     size_t ws_elems_per_frame = 0;
     size_t pack_elems = 0;
-
-    float* pack_arena = nullptr;   // device, owned
     size_t bias_tab_off = 0;       // inside the arena: the CopySegment table of the packed linears' bias vectors (launch_copy_segments)
-    std::vector<CopySegment> bias_tab;   // its host image (kept alive for the asynchronous upload); rebuilt by every full repack
+    bool has_res_chain = false;    // the plan holds an OP_RES_CHAIN (lifter_chain.hip): its two-piece packs are needed at every batch
+    std::vector<unsigned> utab_host;     // the unit tables of the two-fp16-piece conv tile, one per map geometry (H, W, Cin) of the plan (build())
+    size_t utab_off = 0;                 // ... and their place in the pack arena (uploaded once: they depend on the plan alone)
+    int batch_limit = 0;                 // largest batch the 32-bit tensor addressing of the kernels allows (build())
+    int feat_buf[4] = {-1, -1, -1, -1}, feat_H[4] = {0, 0, 0, 0}, feat_W[4] = {0, 0, 0, 0}, feat_C[4] = {0, 0, 0, 0};
+    LifterSchema lifter;                 // the lifter's layers as parameter indices (filled by build_lifter)
+    std::vector<long> grad_off;          // per parameter: offset in the flat lifter gradient, -1 for the backbone
+    long grad_elems = 0;
+
+    int add_param(const std::string& name, int kind, std::initializer_list<int64_t> shape);
+    int new_buffer(size_t elems, const std::string& tag);
+    Tensor conv_bn(const std::string& conv, const std::string& bn, const Tensor& x, int Cout, int ks, int stride,
+                   int act, const Tensor* residual);
+    void build_hrnet(Tensor img, Tensor feats[4]);
+    void build_cpn(Tensor img, Tensor feats[4]);
+    void build_lifter(const Tensor feats[4]);
+    bool build();
+    void assign_offsets();
+    void schedule_regions();
+    bool bf16() const { return cfg.compute_dtype == CAPF_BF16; }
+    bool maps_bf16() const { return bf16() && !plan.f32_stream; }   // the context maps feat0..3 are stored bf16
+    int depth() const { return cfg.depth > 0 ? cfg.depth : cfg.levels; }   // blocks per group (res_blocks / joint_blocks)
+    bool plan_f32_stream(const Tensor feats[4]);
+    size_t act_elems(size_t n) const { return bf16() ? (n + 1) / 2 : n; }   // backbone activation size in float slots
+    void use(int buf);   // mark buffer as read by the op being appended
+    void push(Op op);    // append an op, tagging it with the current lane / region
+    void fork(int n);    // open a region of n independent lanes (independent branches run on side streams)
+    void set_lane(int l) { cur_lane = l; }
+    void join();
+
+    // ---- device state
+    float* pack_arena = nullptr;   // device, owned
+    std::vector<CopySegment> bias_tab;   // host image of the table at bias_tab_off (kept alive for the asynchronous upload); rebuilt by every full repack
     bool bias_tab_on_device = false;
+    bool utab_on_device = false;
     float* split_ws = nullptr;     // device, owned: split-K slabs + per-tile counters of the small-batch conv launches
     int* split_cnt = nullptr;
     // the two-chain schedule (lanes == 3) runs two grouped chains CONCURRENTLY: the side chain's split-K convs get slabs and
@@ -228,71 +310,57 @@ struct Engine {
     float* ws = nullptr;           // device, borrowed
     size_t ws_bytes = 0;
     bool packed = false;
-    bool debug = false;            // run the debug-copy ops (capf_set_debug)
-    int wino_min_batch = 24;       // below this batch the Winograd-eligible convs the split-fp32 tile does not take run the direct kernel (with
-                                   // split-K; batch 16: 4.75 vs 5.86 ms per forward, batch 24: 6.08 vs 6.37)
-    // does the conv leave the direct kernel (for a split-fp32 tile or a Winograd kernel: launch_gemm_wino decides which) at this batch?
-    // A pure function of the op and the batch: the tile's batch range is precomputed per op by build() (no cache, no mutable state --
-    // const-handle queries on other threads may ask while a forward is being enqueued)
-    bool wino_now(const Op& op, int batch) const {
-        return op.wino && ((batch >= op.x3_lo && batch <= op.x3_hi) || (batch >= wino_min_batch && !packs[op.pack].wino_skip));
-    }
-    bool wino_f43_cpn = false;
-    int wino_f43_min_hw = 0, wino_f43_max_hw = 1 << 30;   // F(4,3) only for maps with min <= H * W <= max pixels
-    bool wino_f43 = true;          // plan: F(4,3) where W % 4 == 0, F(2,3) for the other even widths (CAPF_WINO_F43=0: F(2,3) everywhere, A/B runs)
-    std::vector<int> last_variants;   // capf_forward_profile_launches: grouped-bf16 kernel variant per leader op
-    bool use_rh = true;            // plan: row-halo layout + kernel for the bf16 3x3 stride-1 convs (CAPF_BF16_RH=0: off, A/B runs)
-    bool use_x3 = true;            // plan: split-fp32 tile for the Winograd-eligible fp32 3x3 stride-1 convs (plan_flags & CAPF_PLAN_NO_F32X3 clears it)
-    bool use_h2g = true;           // plan: every other fp32 conv / linear of an inference batch >= 5 on the two-fp16-piece GEMM (igemm_f32h2.hip; plan_flags &
-                                   // CAPF_PLAN_NO_F32H2_GEMM clears it)
-    static constexpr int H2G_MIN_BATCH = 5;
     bool h2g_lifter_dirty = true;  // the linear packs' two-piece copies are stale (parameters changed since they were packed)
-    int ensure_h2g_lifter(hipStream_t s);
-    bool x3_h2 = true;             // ... the two-fp16-piece tile (three piece products per MAC); plan_flags & CAPF_PLAN_F32X3_EXACT: the three-bf16-piece tile (six)
-    bool use_ws = true;            // plan: 2-D halo layout + kernel for the bf16 3x3 stride-1 convs (plan_flags & CAPF_PLAN_NO_WS clears it)
-    bool use_wino = true;          // plan: Winograd F(2,3) kernel for the eligible 3x3 stride-1 fp32 convs (CAPF_WINO=0: direct kernel everywhere, A/B runs)
-    bool fused_lifter = true;      // plan: fused embed / context-attention kernels + LayerNorm folded into the GEMMs (CAPF_LIFTER_FUSED=0: the one-kernel-per-op plan, for A/B runs)
+    bool debug = false;            // run the debug-copy ops (capf_set_debug)
     int lanes = 3;                 // fork/join regions: 0 in program order, 1 one side stream per lane, 2 grouped launches on one stream,
                                    // 3 grouped launches as two chains on two streams (capf_set_lanes)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> events;
+    std::vector<int> last_variants;   // capf_forward_profile_launches: grouped-bf16 kernel variant per leader op
     int last_batch = 0;
     const float* images = nullptr;
     const float* k2d = nullptr;
     float* kcrop = nullptr;
     float* out = nullptr;
 
-    // ---- schema / plan construction (plan.cpp)
-    int add_param(const std::string& name, int kind, std::initializer_list<int64_t> shape);
-    int new_buffer(size_t elems, const std::string& tag);
-    Tensor conv_bn(const std::string& conv, const std::string& bn, const Tensor& x, int Cout, int ks, int stride,
-                   int act, const Tensor* residual);
-    void build_hrnet(Tensor img, Tensor feats[4]);
-    void build_cpn(Tensor img, Tensor feats[4]);
-    void build_lifter(const Tensor feats[4]);
-    bool build();
-    void assign_offsets();
-    bool bf16() const { return cfg.compute_dtype == CAPF_BF16; }
-    bool f32_stream = false;       // plan_flags & CAPF_PLAN_BF16_F32_STREAM: bf16 only as conv operands, every other backbone tensor fp32
-    bool maps_bf16() const { return bf16() && !f32_stream; }   // the context maps feat0..3 are stored bf16
-    int depth() const { return cfg.depth > 0 ? cfg.depth : cfg.levels; }   // blocks per group (res_blocks / joint_blocks)
-    bool plan_f32_stream(const Tensor feats[4]);
-    size_t act_elems(size_t n) const { return bf16() ? (n + 1) / 2 : n; }   // backbone activation size in float slots
-    void use(int buf);   // mark buffer as read by the op being appended
-    void push(Op op);    // append an op, tagging it with the current lane / region
-    void fork(int n);    // open a region of n independent lanes (independent branches run on side streams)
-    void set_lane(int l) { cur_lane = l; }
-    void join();
+    // ---- execution (engine.cpp)
+    float* bptr(int buf, int batch) const { return ws + bufs[buf].offset * (size_t)batch; }
+    struct ConvSrc { const float *w, *g, *b, *m, *v; float eps; };   // what every conv packer folds: the weight and its BatchNorm (eval, eps 1e-5)
+    ConvSrc conv_src(const Pack& pk) const;
+    int repack(hipStream_t s, bool lifter_only = false);
+    int ensure_h2g_lifter(hipStream_t s);
+    int run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t* ev = nullptr, LaunchLog* log = nullptr);
+    int exec_op(const Op& op, hipStream_t s, int batch);
+    bool skipped(const Op& op) const { return op.debug_only && !debug; }   // a debug copy outside a debug run: no launch, no log entry
+    FuseSumArgs fuse_args(const Op& op, int batch) const;
+    // does the conv leave the direct kernel (for a split-fp32 tile or a Winograd kernel: launch_gemm_wino decides which) at this batch?
+    // A pure function of the op and the batch: the tile's batch range is precomputed per op by build() (no cache, no mutable state --
+    // const-handle queries on other threads may ask while a forward is being enqueued)
+    bool wino_now(const Op& op, int batch) const {
+        return op.wino && ((batch >= op.x3_lo && batch <= op.x3_hi) || (batch >= plan.wino_min_batch && !packs[op.pack].wino_skip));
+    }
+    // ---- launch routes: pure functions of (op, batch) and the plan, like wino_now
+    // Which family's launcher runs a GEMM op (exec_op; run_region_grouped's pass that may group it), and what the op reports: the kernel that
+    // runs it on its own (capf_op_info) and the FLOPs that kernel issues (capf_op_executed_flops)
+    enum class Family { NONE = -1, F32, BF16, WINO, BF16_ROWS };
+    struct OpRoute { Family family; const char* kernel; double flops; };
+    Family gemm_family(const Op& op, int batch) const;
+    OpRoute op_route(const Op& op, int batch) const;
+    // Several ops as ONE launch: a first bottleneck (bneck_bf16.hip; at its fork op, m = {conv1, conv2, downsample, conv3}), an identity
+    // bottleneck (256 -> 64 -> 64 -> 256, y = relu(conv3 + x); m = {conv1, conv2, conv3}), a 64 -> 256 / 256 -> 64 pointwise conv pair
+    // (igemm_*_pwchain.hip; m = {a, b}).  fused_at: the launch that starts at op i in a run ending before last_op (n = 0: none; bneck_only:
+    // bottlenecks alone).  fused_leader: the launch op i rides in in a whole forward (its leader is m[0])
+    enum class Fusion { NONE, BNECK0, BNECK1, PWCHAIN };
+    struct FusedLaunch { Fusion kind = Fusion::NONE; int n = 0; int m[4] = {-1, -1, -1, -1}; };
+    FusedLaunch fused_at(int i, int batch, int last_op, bool bneck_only = false) const;
+    FusedLaunch fused_leader(int i, int batch, bool bneck_only = false) const;
+    int run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* log, unsigned lane_mask = ~0u);
+    GemmArgs gemm_args(const Op& op, int batch, bool planes = true) const;
 
     // ---- training step (train.cpp)
-    int feat_buf[4] = {-1, -1, -1, -1}, feat_H[4] = {0, 0, 0, 0}, feat_W[4] = {0, 0, 0, 0}, feat_C[4] = {0, 0, 0, 0};
-    LifterSchema lifter;                 // the lifter's layers as parameter indices (filled by build_lifter)
-    std::vector<long> grad_off;          // per parameter: offset in the flat lifter gradient, -1 for the backbone
-    long grad_elems = 0;
     int train_batch = 0;                 // batch of the forward_train whose activations are still in the workspace (0: none)
     int64_t train_generation = 0;        // bumped by every run that (over)writes the workspace
     void invalidate_train() { train_batch = 0; ++train_generation; t_h2_base = nullptr; }
-    int batch_limit = 0;                 // largest batch the 32-bit tensor addressing of the kernels allows (build())
     void train_layout(int B, TrainLayout& L) const;
     size_t train_elems(int B) const;
     int forward_train(hipStream_t s, int B, const float* masks);
@@ -328,39 +396,6 @@ struct Engine {
     const float* t_h2_pack(const float* W, bool transposed) const;
     int t_linear_bwd(hipStream_t s, const TrainLayout& L, float* tw, const float* dY, RowMap dymap, int rows, int N, int K,
                      const float* Xin, RowMap xmap, const float* W, float* dX, RowMap dxmap, bool acc_dx, float* gW, float* gb);
-
-    // ---- execution (engine.cpp)
-    float* bptr(int buf, int batch) const { return ws + bufs[buf].offset * (size_t)batch; }
-    int repack(hipStream_t s, bool lifter_only = false);
-    int run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t* ev = nullptr, LaunchLog* log = nullptr);
-    int exec_op(const Op& op, hipStream_t s, int batch);
-    FuseSumArgs fuse_args(const Op& op, int batch) const;
-    // ---- launch routes: pure functions of (op, batch) and the plan, like wino_now
-    // Which family's launcher runs a GEMM op (exec_op; run_region_grouped's pass that may group it), and what the op reports: the kernel that
-    // runs it on its own (capf_op_info) and the FLOPs that kernel issues (capf_op_executed_flops)
-    enum class Family { NONE = -1, F32, BF16, WINO, BF16_ROWS };
-    struct OpRoute { Family family; const char* kernel; double flops; };
-    Family gemm_family(const Op& op, int batch) const;
-    OpRoute op_route(const Op& op, int batch) const;
-    // Several ops as ONE launch: a first bottleneck (bneck_bf16.hip; at its fork op, m = {conv1, conv2, downsample, conv3}), an identity
-    // bottleneck (256 -> 64 -> 64 -> 256, y = relu(conv3 + x); m = {conv1, conv2, conv3}), a 64 -> 256 / 256 -> 64 pointwise conv pair
-    // (igemm_*_pwchain.hip; m = {a, b}).  fused_at: the launch that starts at op i in a run ending before last_op (n = 0: none; bneck_only:
-    // bottlenecks alone).  fused_leader: the launch op i rides in in a whole forward (its leader is m[0])
-    enum class Fusion { NONE, BNECK0, BNECK1, PWCHAIN };
-    struct FusedLaunch { Fusion kind = Fusion::NONE; int n = 0; int m[4] = {-1, -1, -1, -1}; };
-    FusedLaunch fused_at(int i, int batch, int last_op, bool bneck_only = false) const;
-    FusedLaunch fused_leader(int i, int batch, bool bneck_only = false) const;
-    bool use_pwchain = true;       // plan_flags & CAPF_PLAN_NO_PWCHAIN clears it
-    bool has_res_chain = false;    // the plan holds an OP_RES_CHAIN (lifter_chain.hip): its two-piece packs are needed at every batch
-    std::vector<unsigned> utab_host;     // the unit tables of the two-fp16-piece conv tile, one per map geometry (H, W, Cin) of the plan (build())
-    size_t utab_off = 0;                 // ... and their place in the pack arena (uploaded once: they depend on the plan alone)
-    bool utab_on_device = false;
-    bool use_bneck = true;         // plan_flags & CAPF_PLAN_NO_BNECK clears it
-    bool batch_reduce = true;      // plan_flags & CAPF_PLAN_NO_BATCHED_REDUCE clears it: the backward's second-stage reductions one launch each
-    bool use_upadd = true;         // plan_flags & CAPF_PLAN_NO_UPADD clears it (CPN bf16: lateral conv + upsampled add in one launch)
-    int run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* log, unsigned lane_mask = ~0u);
-    GemmArgs gemm_args(const Op& op, int batch, bool planes = true) const;
-    bool use_h2_planes = false;    // plan_flags & CAPF_PLAN_H2_PLANES sets it (opt-in: measured slower, EXPERIMENTS R6.5)
 };
 
 }  // namespace capf

@@ -61,8 +61,7 @@ void Engine::fork(int n) {
     Op op;
     op.kind = OP_FORK;
     op.name = "fork";
-    op.i0 = n;
-    op.i1 = n_events;          // first event id of this region: 1 for the fork + (n-1) for the join
+    op.fork = Fork{n, n_events};          // (event ids of this region: 1 for the fork + (n-1) for the join)
     n_events += n;
     cur_region = n_regions++;
     cur_lane = 0;
@@ -74,9 +73,7 @@ void Engine::join() {
     Op op;
     op.kind = OP_JOIN;
     op.name = "join";
-    const Op& f = ops[regions[cur_region].first];
-    op.i0 = f.i0;
-    op.i1 = f.i1;
+    op.fork = ops[regions[cur_region].first].fork;
     cur_lane = 0;
     regions[cur_region].second = (int)ops.size();
     push(op);
@@ -97,6 +94,16 @@ static void name_tensor(Engine& e, const std::string& name, int buf, std::initia
     keep(e, buf);
 }
 
+static BnRef reg_bn(Engine& e, const std::string& bn, int C) {      // nn.BatchNorm2d's state_dict entries, in its order
+    BnRef r;
+    r.g = e.add_param(bn + ".weight", CAPF_P_BN_W, {C});
+    r.b = e.add_param(bn + ".bias", CAPF_P_BN_B, {C});
+    r.m = e.add_param(bn + ".running_mean", CAPF_P_BN_MEAN, {C});
+    r.v = e.add_param(bn + ".running_var", CAPF_P_BN_VAR, {C});
+    e.add_param(bn + ".num_batches_tracked", CAPF_P_BN_NBT, {});
+    return r;
+}
+
 // conv (bias=False) + eval BatchNorm (+ residual) (+ ReLU) as ONE implicit-GEMM launch.
 Tensor Engine::conv_bn(const std::string& conv, const std::string& bn, const Tensor& x, int Cout, int ks,
                        int stride, int act, const Tensor* residual) {
@@ -107,13 +114,9 @@ Tensor Engine::conv_bn(const std::string& conv, const std::string& bn, const Ten
     y.C = Cout;
 
     Pack pk;
-    pk.kind = 0;
+    pk.kind = CONV_BN;
     pk.w[0] = add_param(conv + ".weight", CAPF_P_CONV_W, {Cout, x.C, ks, ks});
-    pk.bn_g = add_param(bn + ".weight", CAPF_P_BN_W, {Cout});
-    pk.bn_b = add_param(bn + ".bias", CAPF_P_BN_B, {Cout});
-    pk.bn_m = add_param(bn + ".running_mean", CAPF_P_BN_MEAN, {Cout});
-    pk.bn_v = add_param(bn + ".running_var", CAPF_P_BN_VAR, {Cout});
-    add_param(bn + ".num_batches_tracked", CAPF_P_BN_NBT, {});
+    pk.bn = reg_bn(*this, bn, Cout);
     pk.N = Cout;
     pk.Cin = x.C;
     pk.ks = ks;
@@ -123,23 +126,23 @@ Tensor Engine::conv_bn(const std::string& conv, const std::string& bn, const Ten
     pk.Kpad = use_bf16 ? round64(pk.K) : round32(pk.K);
     // Winograd F(2,3) along W (igemm_wino.hip) for the 3x3 stride-1 fp32 convs: 1.5x fewer MFMAs; block tiles of 64 x 64,
     // 64 x 32 (32-channel outputs) or 32 x 64 (few tiles) are chosen per problem at launch
-    const bool use_wino = this->use_wino && !use_bf16 && ks == 3 && stride == 1 && x.C % 32 == 0 && x.W % 2 == 0 && Cout % 32 == 0;
-    pk.wino = use_wino;
+    const bool as_wino = plan.use_wino && !use_bf16 && ks == 3 && stride == 1 && x.C % 32 == 0 && x.W % 2 == 0 && Cout % 32 == 0;
+    pk.wino = as_wino;
     // F(4,3) (half the MFMAs of the direct conv) where the row length allows four-pixel tiles, F(2,3) (two thirds) otherwise.
     // HRNet only: F(4,3) pays inside the grouped multi-branch launches (+3.2 % end to end), not for CPN's lone convs (-0.8 %).
-    if (use_wino) { pk.Kpad2 = pk.Kpad; pk.Kpad = ((x.W % 4 == 0 && wino_f43 && (cfg.backbone == CAPF_HRNET || wino_f43_cpn) && x.H * x.W >= wino_f43_min_hw && x.H * x.W <= wino_f43_max_hw) ? 18 : 12) * x.C; }
+    if (as_wino) { pk.direct_Kpad = pk.Kpad; pk.Kpad = ((x.W % 4 == 0 && plan.wino_f43 && (cfg.backbone == CAPF_HRNET || plan.wino_f43_cpn) && x.H * x.W >= plan.wino_f43_min_hw && x.H * x.W <= plan.wino_f43_max_hw) ? 18 : 12) * x.C; }
     // bf16: the 3x3 stride-1 convs also keep their weights in the row-halo layout (igemm_bf16.hip: one staged activation tile
     // for the three kw taps); launches of >= 2048 tiles run that kernel, smaller ones the ring kernel on the standard layout
-    if (use_bf16 && use_rh && ks == 3 && stride == 1 && bf16_rh_width(x.C) && Cout % 4 == 0) { pk.rh = true; pk.Kpad2 = 9 * x.C; }
+    if (use_bf16 && plan.use_rh && ks == 3 && stride == 1 && bf16_rh_width(x.C) && Cout % 4 == 0) { pk.rh = true; pk.rh_Kpad = 9 * x.C; }
     // ... and in the layout of the 2-D halo tile (igemm_bf16_ws.hip), which takes them from 512 tiles per launch
-    if (use_bf16 && use_ws && ks == 3 && stride == 1 && x.C % 16 == 0 && Cout % 8 == 0) pk.ws = true;
+    if (use_bf16 && plan.use_ws && ks == 3 && stride == 1 && x.C % 16 == 0 && Cout % 8 == 0) pk.ws = true;
     // fp32: the Winograd-eligible convs also keep their weights as three bf16 pieces for the split-fp32 tile (igemm_f32x3_ws.hip), which
     // takes them from 370 MFLOP per conv and batch 5 up (f32x3_takes)
-    if (use_wino && use_x3 && x.W <= 256) pk.x3 = true;
+    if (as_wino && plan.use_x3 && x.W <= 256) pk.x3 = true;
     // fp32: every conv with 16-byte-aligned channel counts also keeps its weights as two block-scaled fp16 pieces in the direct layout's
     // geometry (igemm_f32h2.hip): what runs on the plain fp32 MFMA kernel at batch < 5 runs there from batch 5 (1x1 / stride-2 fuse and
     // transition convs, lone convs; the HBM-bound pointwise kernels of layer1 keep theirs)
-    if (!use_bf16 && use_h2g && x.C % 4 == 0 && Cout % 4 == 0) { pk.h2g = true; pk.KpadH = use_wino ? pk.Kpad2 : pk.Kpad; }
+    if (!use_bf16 && plan.use_h2g && x.C % 4 == 0 && Cout % 4 == 0) { pk.h2g = true; pk.h2g_Kpad = as_wino ? pk.direct_Kpad : pk.Kpad; }
     packs.push_back(pk);
 
     Op op;
@@ -161,7 +164,7 @@ Tensor Engine::conv_bn(const std::string& conv, const std::string& bn, const Ten
         use(residual->buf);
     }
     op.bf16 = use_bf16 ? 1 : 0;
-    op.wino = use_wino ? 1 : 0;
+    op.wino = as_wino ? 1 : 0;
     op.out_bf16 = (bf16() && !use_bf16) ? 1 : 0;
     y.buf = new_buffer(act_elems((size_t)y.H * y.W * Cout), conv);
     op.out = y.buf;
@@ -200,7 +203,7 @@ static Tensor hr_basic_block(Engine& e, const std::string& p, const Tensor& x) {
     // conv1's output has ONE reader, conv2, and both convs have the same tiles: where both run the two-fp16-piece tile (a matter of the
     // batch, decided per launch in gemm_args) it travels as split fp16 planes + one scale exponent per (tile, 16-channel chunk) --
     // igemm_f32h2_ws_tile.h PLANES: the consumer's K loop loses its maximum / split / scale-exchange phase.  Same bytes, same buffer.
-    if (e.use_h2_planes && e.x3_h2 && !e.bf16() && x.C % 16 == 0 && e.packs[e.ops[i1].pack].x3 && e.packs[e.ops[i2].pack].x3) {
+    if (e.plan.use_h2_planes && e.plan.x3_h2 && !e.bf16() && x.C % 16 == 0 && e.packs[e.ops[i1].pack].x3 && e.packs[e.ops[i2].pack].x3) {
         const int tiles_pf = f32h2_tiles_m(1, x.H, x.W);
         if (tiles_pf > 0) {
             const int b = e.new_buffer((size_t)tiles_pf * (x.C / 16) + 16, p + ".conv1.exps");
@@ -218,7 +221,7 @@ static Tensor hr_basic_block(Engine& e, const std::string& p, const Tensor& x) {
 // (no two of them share workspace) from conv1 to conv3; the ops remember conv3 (capf_op_describe: their checkpoint is the whole block).
 // `fork` = index of the region's fork op: fork, conv1, conv2, downsample, join, conv3.
 static void bneck0_mark(Engine& e, int fork) {
-    if (!e.use_bneck || !e.bf16() || fork + 5 >= (int)e.ops.size()) return;
+    if (!e.plan.use_bneck || !e.bf16() || fork + 5 >= (int)e.ops.size()) return;
     const int c1 = fork + 1, c2 = fork + 2, ds = fork + 3, c3 = fork + 5;
     const Op &o1 = e.ops[c1], &o3 = e.ops[c3];
     if (e.ops[fork].kind != OP_FORK || e.ops[fork + 4].kind != OP_JOIN || o1.Cin != 64 || o1.N != 64 || o3.N != 256 || e.ops[c2].stride != 1 || e.ops[c2].ks != 3) return;
@@ -232,7 +235,7 @@ static void bneck0_mark(Engine& e, int fork) {
 
 // ... and an identity bottleneck (conv1 at `c1`, conv2, conv3 + x): x, conv1's and conv2's outputs and y alive from conv1 to conv3
 static void bneck1_mark(Engine& e, int c1) {
-    if (!e.use_bneck || !e.bf16() || c1 + 2 >= (int)e.ops.size()) return;
+    if (!e.plan.use_bneck || !e.bf16() || c1 + 2 >= (int)e.ops.size()) return;
     const Op &o1 = e.ops[c1], &o2 = e.ops[c1 + 1], &o3 = e.ops[c1 + 2];
     if (o1.kind != OP_GEMM || o2.kind != OP_GEMM || o3.kind != OP_GEMM || o1.Cin != 256 || o1.N != 64 || o2.ks != 3 || o2.stride != 1 || o3.N != 256 || o3.aux != o1.in[0]) return;
     for (int b : {o1.in[0], o1.out, o2.out, o3.out}) {
@@ -382,11 +385,7 @@ static Tensor pool_or_resize(Engine& e, OpKind kind, const std::string& name, co
 static void register_unused_conv_bn(Engine& e, const std::string& conv, const std::string& bn, int Cout, int Cin,
                                     int ks) {
     e.add_param(conv + ".weight", CAPF_P_CONV_W, {Cout, Cin, ks, ks});
-    e.add_param(bn + ".weight", CAPF_P_BN_W, {Cout});
-    e.add_param(bn + ".bias", CAPF_P_BN_B, {Cout});
-    e.add_param(bn + ".running_mean", CAPF_P_BN_MEAN, {Cout});
-    e.add_param(bn + ".running_var", CAPF_P_BN_VAR, {Cout});
-    e.add_param(bn + ".num_batches_tracked", CAPF_P_BN_NBT, {});
+    reg_bn(e, bn, Cout);
 }
 
 void Engine::build_cpn(Tensor img, Tensor feats[4]) {
@@ -421,7 +420,7 @@ void Engine::build_cpn(Tensor img, Tensor feats[4]) {
     for (int i = 0; i < 4; ++i) {
         const Tensor& src = c[3 - i];
         const std::string lp = G + ".laterals." + std::to_string(i);
-        if (i > 0 && bf16() && use_upadd) {
+        if (i > 0 && bf16() && plan.use_upadd) {
             // bf16: the low-resolution conv of the upsampled path first, then the lateral conv with `+ bilinear_x2(t)` behind its ReLU in the
             // epilogue (igemm_bf16_kernel<.., UPADD>): no resize-add launch, the lateral map never travels to HBM and back on its own
             // (lateral: write + read of 453 MB at the largest level and batch 128), and it meets the upsampled term in fp32
@@ -430,8 +429,7 @@ void Engine::build_cpn(Tensor img, Tensor feats[4]) {
             ops.back().flops_per_frame *= 4.0;
             fms[i] = conv_bn(lp + ".0", lp + ".1", src, 256, 1, 1, ACT_RELU, nullptr);
             Op& lop = ops.back();
-            lop.in[1] = t.buf;                       // (OP_GEMM conv: in[1] = the map added, upsampled, behind the activation; i0 x i1 its size)
-            lop.i0 = t.H; lop.i1 = t.W;
+            lop.up_in = t.buf; lop.up_H = t.H; lop.up_W = t.W;
             bufs[t.buf].last_op = std::max(bufs[t.buf].last_op, (int)ops.size() - 1);
             const std::string pp = G + ".predict." + std::to_string(i);
             register_unused_conv_bn(*this, pp + ".0", pp + ".1", 256, 256, 1);
@@ -508,7 +506,7 @@ static LnRef reg_ln(Engine& e, const std::string& p, int C) {
 
 static int make_linear_pack(Engine& e, std::initializer_list<LinearRef> lins, bool as_bf16 = false, bool quad = false) {
     Pack pk;
-    pk.kind = 1;
+    pk.kind = LINEAR;
     pk.quad = quad;
     int N = 0, K = 0;
     for (const LinearRef& r : lins) {
@@ -521,13 +519,19 @@ static int make_linear_pack(Engine& e, std::initializer_list<LinearRef> lins, bo
     pk.K = K;
     pk.Kpad = as_bf16 ? round64(K) : round32(K);
     if (quad) pk.Kpad = K;                     // (K % 4 == 0: embed dims and level channel counts)
-    pk.direct = !as_bf16 && !quad && (pk.n_lin == 1 && pk.Kpad == K);
+    pk.in_place = !as_bf16 && !quad && (pk.n_lin == 1 && pk.Kpad == K);
     pk.bf16 = as_bf16;                         // bf16 copy [N][Kpad] for the bf16 MFMA projections (compute_dtype = bf16)
     // the fp32 projections also as two fp16 pieces for igemm_f32h2.hip, packed LAZILY (Engine::ensure_h2g_lifter): a training loop changes the
     // weights every step and its forward runs train.cpp's GEMMs, so the copy is rebuilt only when an inference forward needs it
-    if (!as_bf16 && !quad && e.use_h2g && !e.bf16() && K % 4 == 0 && N % 4 == 0) { pk.h2g = true; pk.KpadH = round32(K); }
+    if (!as_bf16 && !quad && e.plan.use_h2g && !e.bf16() && K % 4 == 0 && N % 4 == 0) { pk.h2g = true; pk.h2g_Kpad = round32(K); }
     e.packs.push_back(pk);
     return (int)e.packs.size() - 1;
+}
+
+static int make_chain_pack(Engine& e, const LinearRef& lin) {   // a linear of lifter_chain.hip: the two-piece copy in fragment order as well
+    const int pk = make_linear_pack(e, {lin});
+    e.packs[pk].chain = true;
+    return pk;
 }
 
 // rows-mode GEMM:  out[omap(m) + n] = act(A[amap(m)] . W[n] + b[n] + res[rmap(m) + n])
@@ -549,12 +553,11 @@ static void gemm_rows(Engine& e, const std::string& name, int pack, int a_buf, R
     op.rmap = rmap;
     op.res_param = res_param;
     if (ln.w >= 0) {                         // LayerNorm(A rows) folded into the GEMM's fragment path (igemm_f32.hip, LNA)
-        op.ln_w = ln.w;
-        op.ln_b = ln.b;
+        op.ln = ln;
         op.eps = ln_eps;
     }
     op.flops_per_frame = 2.0 * rows_pf * (double)pk.N * pk.K;
-    if (pk.kind == 1 && pk.bf16) {           // bf16 operands (A buffer holds bf16 rows), fp32 accumulate
+    if (pk.kind == LINEAR && pk.bf16) {           // bf16 operands (A buffer holds bf16 rows), fp32 accumulate
         op.bf16 = 2;
         op.out_bf16 = act == ACT_GELU ? 1 : 0;   // fc1: GELU, bf16 hidden rows; everything else lands in the fp32 stream
     }
@@ -574,8 +577,7 @@ static void layernorm(Engine& e, const std::string& name, LnRef ln, float eps, i
     op.aux = add_buf;
     op.rmap = amap;
     op.out = out_buf;
-    op.p0 = ln.w;
-    op.p1 = ln.b;
+    op.ln = ln;
     op.eps = eps;
     op.rows_per_frame = rows_pf;
     op.C = C;
@@ -593,7 +595,7 @@ static void debug_copy(Engine& e, const std::string& name, int src, size_t elems
     op.n_in = 1;
     op.in[0] = src;
     op.H = 1; op.W = 1; op.C = (int)elems; op.relu = 0;
-    op.i0 = 1;               // debug-only op
+    op.debug_only = true;
     e.use(src);
     op.out = e.new_buffer(elems, name);
     e.push(op);
@@ -662,7 +664,7 @@ void Engine::build_lifter(const Tensor feats[4]) {
     // (compute_dtype = bf16: the projections take bf16 A rows, which the LayerNorm kernel writes directly)
     // lifter projections (qkv / proj / fc1 / fc2) on the bf16 MFMA path; CAPF_PLAN_LIFTER_FP32 keeps them (and their LayerNorm folding) fp32
     const bool lb = bf16() && !(cfg.plan_flags & CAPF_PLAN_LIFTER_FP32);
-    auto ln_fold_ok = [&](int dim) { return fused_lifter && dim <= 256 && !lb; };
+    auto ln_fold_ok = [&](int dim) { return plan.fused_lifter && dim <= 256 && !lb; };
     const bool ln_fold = ln_fold_ok(C);
     // the MLP half of a block on the rows `xm` of X, x += fc2(gelu(fc1(norm2(x)))), in the form the caller chose: one launch (lifter_chain.hip,
     // ATTN = false), else norm2 folded into fc1, else a LayerNorm launch in front of fc1.  fc1 and fc2 get their packs in this order in every form
@@ -677,12 +679,11 @@ void Engine::build_lifter(const Tensor feats[4]) {
             op.C = dim;
             op.eps = eps;
             op.rows_per_frame = rows_pf;
-            for (const LinearRef& lin : {m.fc1, m.fc2}) {
-                op.chain.push_back(make_linear_pack(*this, {lin}));
-                packs.back().chain = true;
-            }
-            op.chain.push_back(m.norm2.w);
-            op.chain.push_back(m.norm2.b);
+            ChainBlock blk;
+            blk.fc1 = make_chain_pack(*this, m.fc1);
+            blk.fc2 = make_chain_pack(*this, m.fc2);
+            blk.norm2 = m.norm2;
+            op.blocks.push_back(blk);
             op.flops_per_frame = 2.0 * rows_pf * (double)dim * (2 * dim + 2 * dim);
             use(X);
             push(op);
@@ -699,15 +700,14 @@ void Engine::build_lifter(const Tensor feats[4]) {
         }
         gemm_rows(*this, n + ".fc2", make_linear_pack(*this, {m.fc2}, lb), Hb, row_ld(2 * dim), rows_pf, X, xm, ACT_NONE, X, xm);
     };
-    if (fused_lifter) {
+    if (plan.fused_lifter) {
         Op op;
         op.kind = OP_EMBED;
         op.name = "embed";
         op.out = X;
-        op.p0 = net.coord.w;
-        op.p1 = net.coord.b;
-        op.p2 = net.pos;
-        op.i0 = J; op.i1 = L; op.i2 = L1; op.C = C;
+        op.coord = net.coord;
+        op.pos = net.pos;
+        op.smp.J = J; op.smp.L = L; op.smp.L1 = L1; op.C = C;
         op.bf16 = bf16() ? 1 : 0;
         op.feat_bf16 = maps_bf16() ? 1 : 0;
         use(X);
@@ -719,9 +719,9 @@ void Engine::build_lifter(const Tensor feats[4]) {
             op.pb[l] = net.feat_embed[l].b;
             op.pq[l] = make_linear_pack(*this, {net.feat_embed[l]}, false, true);
             op.outs[l] = new_buffer((size_t)J * Cl[l], "sampled" + ls);
-            op.idxs[l] = new_buffer((size_t)J * 2, "idx" + ls);
+            op.idx_lvl[l] = new_buffer((size_t)J * 2, "idx" + ls);
             name_tensor(*this, "sampled" + ls, op.outs[l], {-1, J, Cl[l]});
-            name_tensor(*this, "idx" + ls, op.idxs[l], {-1, J, 2}, 1);
+            name_tensor(*this, "idx" + ls, op.idx_lvl[l], {-1, J, 2}, 1);
             op.flops_per_frame += 2.0 * J * (double)C * Cl[l];
         }
         push(op);
@@ -731,10 +731,9 @@ void Engine::build_lifter(const Tensor feats[4]) {
         op.kind = OP_PREP_EMBED;
         op.name = "prep_embed";
         op.out = X;
-        op.p0 = net.coord.w;
-        op.p1 = net.coord.b;
-        op.p2 = net.pos;
-        op.i0 = J; op.i1 = L1; op.C = C;
+        op.coord = net.coord;
+        op.pos = net.pos;
+        op.smp.J = J; op.smp.L1 = L1; op.C = C;
         use(X);
         push(op);
     }
@@ -744,14 +743,14 @@ void Engine::build_lifter(const Tensor feats[4]) {
         op.kind = OP_SAMPLE_REF;
         op.name = "sample_ref." + ls;
         op.in[0] = feats[l].buf;
-        op.H = feats[l].H; op.W = feats[l].W; op.C = Cl[l]; op.i0 = J;
+        op.H = feats[l].H; op.W = feats[l].W; op.C = Cl[l]; op.smp.J = J;
         op.bf16 = bf16() ? 1 : 0;
         op.feat_bf16 = maps_bf16() ? 1 : 0;
         use(feats[l].buf);
         const int S = new_buffer((size_t)J * Cl[l], "sampled" + ls);
         const int I = new_buffer((size_t)J * 2, "idx" + ls);
         op.out = S;
-        op.aux2 = I;
+        op.idx_out = I;
         push(op);
         name_tensor(*this, "sampled" + ls, S, {-1, J, Cl[l]});
         name_tensor(*this, "idx" + ls, I, {-1, J, 2}, 1);
@@ -782,15 +781,14 @@ void Engine::build_lifter(const Tensor feats[4]) {
             const int tap_idx = c.tap_idx = new_buffer((size_t)J * L * NH * NS * 2, "cidx" + std::to_string(i));
             name_tensor(*this, "cpos" + std::to_string(i), tap_pos, {-1, J, L * NH * NS, 2});
             name_tensor(*this, "cidx" + std::to_string(i), tap_idx, {-1, J, L * NH * NS, 2}, 1);
-            if (fused_lifter) {
+            if (plan.fused_lifter) {
                 Op op;
                 op.kind = OP_CTX_ATTN;
                 op.name = n + ".attn";
                 op.pack = make_linear_pack(*this, {c.aw, c.so}, false, true);
                 op.out = X;
                 use(X);
-                op.p0 = c.norm1.w;
-                op.p1 = c.norm1.b;
+                op.ln = c.norm1;
                 op.eps = 1e-5f;
                 for (int l = 0; l < L; ++l) {
                     op.in[l] = feats[l].buf;
@@ -803,10 +801,10 @@ void Engine::build_lifter(const Tensor feats[4]) {
                     op.flops_per_frame += 2.0 * J * NH * (double)HD * Cl[l];
                 }
                 op.flops_per_frame += 2.0 * J * L * (double)C * 3 * NH * NS;
-                op.i0 = J; op.i1 = L; op.i2 = NH; op.i3 = NS; op.C = C;
+                op.smp.J = J; op.smp.L = L; op.smp.NH = NH; op.smp.NS = NS; op.C = C;
                 op.bf16 = bf16() ? 1 : 0;
                 op.feat_bf16 = maps_bf16() ? 1 : 0;
-                op.idxs[0] = tap_pos; op.idxs[1] = tap_idx;
+                op.tap_pos = tap_pos; op.tap_idx = tap_idx;
                 push(op);
             } else {
             layernorm(*this, n + ".norm1", c.norm1, 1e-5f, X, tok, X, tok0, Q, (long)J * L, C);
@@ -825,10 +823,10 @@ void Engine::build_lifter(const Tensor feats[4]) {
                     use(feats[l].buf);
                     use(U[l]);
                 }
-                op.i0 = J; op.i1 = L; op.i2 = NH; op.i3 = NS;
+                op.smp.J = J; op.smp.L = L; op.smp.NH = NH; op.smp.NS = NS;
                 op.bf16 = bf16() ? 1 : 0;
                 op.feat_bf16 = maps_bf16() ? 1 : 0;
-                op.idxs[0] = tap_pos; op.idxs[1] = tap_idx;
+                op.tap_pos = tap_pos; op.tap_idx = tap_idx;
                 push(op);
             }
             for (int l = 0; l < L; ++l) {
@@ -839,7 +837,7 @@ void Engine::build_lifter(const Tensor feats[4]) {
             }
             }
             // the MLP half as one launch on the context tokens' rows where the chain kernel takes the width
-            const bool mlp_chain = fused_lifter && use_h2g && !lb && !bf16() && res_chain_ok(C, 5, 8, 1);
+            const bool mlp_chain = plan.fused_lifter && plan.use_h2g && !lb && !bf16() && res_chain_ok(C, 5, 8, 1);
             mlp_half(c.mlp, n, tok, (long)J * L, C, 1e-5f, mlp_chain, ln_fold);
         }
     }
@@ -852,22 +850,25 @@ void Engine::build_lifter(const Tensor feats[4]) {
         // the res blocks (tokens of ONE joint, 128 wide) as one launch: a workgroup takes 6 joints through every block without leaving
         // the CU (lifter_chain.hip); fp32 lifter on the two-piece packs only -- the bf16 plan and CAPF_PLAN_NO_FUSED_LIFTER /
         // CAPF_PLAN_NO_F32H2_GEMM keep one launch per op
-        if (fused_lifter && use_h2g && !lb && !bf16() && groups_pf > 1 && res_chain_ok(dim, tokens, cfg.num_heads, nblk)) {
+        if (plan.fused_lifter && plan.use_h2g && !lb && !bf16() && groups_pf > 1 && res_chain_ok(dim, tokens, cfg.num_heads, nblk)) {
             Op op;
             op.kind = OP_RES_CHAIN;
             op.name = tag + ".chain";
             op.in[0] = X;
             op.out = X;
-            op.i0 = tokens; op.i1 = cfg.num_heads; op.i2 = nblk; op.C = dim;
+            op.attn.tokens = tokens; op.attn.heads = cfg.num_heads; op.C = dim;
             op.eps = 1e-6f;
             op.rows_per_frame = rows_pf;
             for (int i = 0; i < nblk; ++i) {
                 const LifterAtt& a = blocks[i];
-                for (const LinearRef& lin : {a.qkv, a.proj, a.mlp.fc1, a.mlp.fc2}) {
-                    op.chain.push_back(make_linear_pack(*this, {lin}));
-                    packs.back().chain = true;
-                }
-                for (int ln : {a.norm1.w, a.norm1.b, a.mlp.norm2.w, a.mlp.norm2.b}) op.chain.push_back(ln);
+                ChainBlock blk;
+                blk.qkv = make_chain_pack(*this, a.qkv);
+                blk.proj = make_chain_pack(*this, a.proj);
+                blk.fc1 = make_chain_pack(*this, a.mlp.fc1);
+                blk.fc2 = make_chain_pack(*this, a.mlp.fc2);
+                blk.norm1 = a.norm1;
+                blk.norm2 = a.mlp.norm2;
+                op.blocks.push_back(blk);
                 op.flops_per_frame += 2.0 * rows_pf * (double)dim * (3 * dim + dim + 2 * dim + 2 * dim) + 4.0 * groups_pf * tokens * tokens * dim;
             }
             use(X);
@@ -892,7 +893,7 @@ void Engine::build_lifter(const Tensor feats[4]) {
                 op.name = n + ".attn";
                 op.in[0] = QKV;
                 op.out = O;
-                op.i0 = groups_pf; op.i1 = tokens; op.i2 = cfg.num_heads; op.i3 = dim / cfg.num_heads;
+                op.attn = Attn{groups_pf, tokens, cfg.num_heads, dim / cfg.num_heads};
                 op.flops_per_frame = 4.0 * groups_pf * tokens * tokens * dim;
                 op.out_bf16 = lb ? 1 : 0;      // the attention output is only ever the A operand of proj
                 use(QKV); use(O);
@@ -913,14 +914,11 @@ void Engine::build_lifter(const Tensor feats[4]) {
         op.kind = OP_HEAD;
         op.name = "head";
         op.in[0] = X;
-        op.p0 = net.head_ln.w;
-        op.p1 = net.head_ln.b;
-        op.p2 = net.head.w;
-        op.p3 = net.head.b;
+        op.ln = net.head_ln;
+        op.head = net.head;
         op.eps = 1e-5f;
         op.rows_per_frame = J;
         op.C = D;
-        op.i0 = 3;
         op.flops_per_frame = 2.0 * J * D * 3;
         use(X);
         push(op);
@@ -939,15 +937,17 @@ bool Engine::plan_f32_stream(const Tensor feats[4]) {
     std::vector<char> other(nb, 0);
     for (int i = 0; i < n; ++i) {
         const Op& op = ops[i];
-        if ((op.kind == OP_GEMM || op.kind == OP_FUSE) && op.out >= 0) prod[op.out] = i;
-        if (op.kind == OP_GEMM) {
-            if (op.in[0] >= 0) conv_last[op.in[0]] = i;
-            if (op.aux >= 0) other[op.aux] = 1;
-        } else if (op.kind == OP_FUSE) {
-            for (int k = 0; k < op.n_in; ++k) other[op.in[k]] = 1;
-        } else if (op.kind != OP_FORK && op.kind != OP_JOIN) {
+        if (op.kind == OP_FORK || op.kind == OP_JOIN) continue;
+        if (op.kind != OP_GEMM && op.kind != OP_FUSE) {
             err = "CAPF_PLAN_BF16_F32_STREAM: unexpected backbone op " + op.name;
             return false;
+        }
+        if (op.out >= 0) prod[op.out] = i;
+        const auto rd = op.reads();                      // a conv's first read is its operand; every other read wants the fp32 value
+        for (size_t k = 0; k < rd.size(); ++k) {
+            if (rd[k] < 0) continue;
+            if (op.kind == OP_GEMM && k == 0) conv_last[rd[k]] = i;
+            else other[rd[k]] = 1;
         }
     }
     for (int l = 0; l < 4; ++l) other[feats[l].buf] = 1;
@@ -1017,24 +1017,13 @@ void Engine::schedule_regions() {
     for (size_t r = 0; r < regions.size(); ++r) {
         const int lo = regions[r].first + 1, hi = regions[r].second;
         std::vector<int> level(hi - lo, 0);
-        auto reads = [&](const Op& o, int b) {
-            if (b < 0) return false;
-            for (int i = 0; i < 4; ++i) if (o.in[i] == b) return true;
-            return o.aux == b;
-        };
-        auto writes = [&](const Op& o, int b) {
-            if (b < 0) return false;
-            if (o.out == b || o.aux2 == b || o.sh == b) return true;      // (sh: the bf16 shadow of an fp32 output, CAPF_PLAN_BF16_F32_STREAM)
-            for (int i = 0; i < 4; ++i) if (o.outs[i] == b) return true;
-            return false;
-        };
+        auto has = [](const auto& slots, int b) { return std::find(slots.begin(), slots.end(), b) != slots.end(); };
+        auto reads = [&](const Op& o, int b) { return has(o.reads(), b); };
+        auto writes = [&](const Op& o, int b) { return has(o.writes(), b); };
         auto touched = [&](const Op& o) {
             std::vector<int> v;
-            for (int i = 0; i < 4; ++i) { if (o.in[i] >= 0) v.push_back(o.in[i]); if (o.outs[i] >= 0) v.push_back(o.outs[i]); }
-            if (o.aux >= 0) v.push_back(o.aux);
-            if (o.out >= 0) v.push_back(o.out);
-            if (o.aux2 >= 0) v.push_back(o.aux2);
-            if (o.sh >= 0) v.push_back(o.sh);
+            for (int b : o.reads()) if (b >= 0) v.push_back(b);
+            for (int b : o.writes()) if (b >= 0) v.push_back(b);
             return v;
         };
         int max_level = 0;
@@ -1053,7 +1042,7 @@ void Engine::schedule_regions() {
         // LAST level, where run_region_grouped issues all of a module's sums as one launch instead of 2-4 small ones.
         for (int i = lo; i < hi; ++i) {
             const Op& oi = ops[i];
-            if (oi.kind != OP_FUSE || oi.i0 == 1) continue;
+            if (oi.kind != OP_FUSE || oi.debug_only) continue;
             bool sink = true;
             for (int j = i + 1; j < hi && sink; ++j) {
                 const Op& oj = ops[j];
@@ -1065,6 +1054,49 @@ void Engine::schedule_regions() {
         region_levels[r].assign(max_level + 1, {});
         for (int i = lo; i < hi; ++i) region_levels[r][level[i - lo]].push_back(i);
     }
+}
+
+// The plan switches, in this precedence: cfg.plan_flags; what CAPF_PLAN_BF16_F32_STREAM implies; the diagnostic build's knobs; what the
+// configuration's widths rule out
+bool Engine::set_plan_switches() {
+    PlanSwitches& p = plan;
+    if (cfg.plan_flags & CAPF_PLAN_NO_FUSED_LIFTER) p.fused_lifter = false;
+    if (cfg.plan_flags & CAPF_PLAN_NO_WINOGRAD) p.use_wino = false;
+    if (cfg.plan_flags & CAPF_PLAN_NO_ROW_HALO) p.use_rh = false;
+    if (cfg.plan_flags & CAPF_PLAN_WINOGRAD_F23_ONLY) p.wino_f43 = false;
+    if (cfg.plan_flags & CAPF_PLAN_NO_PWCHAIN) p.use_pwchain = false;
+    if (cfg.plan_flags & CAPF_PLAN_NO_UPADD) p.use_upadd = false;
+    if (cfg.plan_flags & CAPF_PLAN_NO_BNECK) p.use_bneck = false;
+    if (cfg.plan_flags & CAPF_PLAN_NO_BATCHED_REDUCE) p.batch_reduce = false;
+    if (cfg.plan_flags & CAPF_PLAN_H2_PLANES) p.use_h2_planes = true;
+    if (cfg.plan_flags & CAPF_PLAN_NO_WS) p.use_ws = false;
+    if (cfg.plan_flags & CAPF_PLAN_NO_F32X3) p.use_x3 = false;
+    if (cfg.plan_flags & CAPF_PLAN_F32X3_EXACT) p.x3_h2 = false;
+    if (cfg.plan_flags & CAPF_PLAN_NO_F32H2_GEMM) p.use_h2g = false;
+    if (cfg.plan_flags & CAPF_PLAN_BF16_F32_STREAM) {
+        if (!bf16()) { err = "CAPF_PLAN_BF16_F32_STREAM needs compute_dtype = CAPF_BF16"; return false; }
+        if (cfg.backbone != CAPF_HRNET) { err = "CAPF_PLAN_BF16_F32_STREAM is an HRNet plan (CPN50 is not supported)"; return false; }
+        if (cfg.plan_flags != CAPF_PLAN_BF16_F32_STREAM) { err = "CAPF_PLAN_BF16_F32_STREAM cannot be combined with other plan flags"; return false; }
+        p.f32_stream = true;
+        // layer1 runs as one launch per conv: the fused bottleneck kernels (bneck_bf16.hip) and the chained pointwise pair have no fp32-stream
+        // epilogue (EXPERIMENTS R7.1 prices it)
+        p.use_bneck = false;
+        p.use_pwchain = false;
+    }
+    // tuning knobs of the diagnostic build only (diag_env is a constant nullptr in the product library)
+    if (const char* fz = diag_env("CAPF_LIFTER_FUSED")) p.fused_lifter = atoi(fz) != 0;
+    if (const char* wz = diag_env("CAPF_WINO")) p.use_wino = atoi(wz) != 0;
+    if (const char* rz = diag_env("CAPF_BF16_RH")) p.use_rh = atoi(rz) != 0;
+    if (const char* wb = diag_env("CAPF_WINO_MIN_BATCH")) p.wino_min_batch = atoi(wb);
+    if (const char* wf = diag_env("CAPF_WINO_F43")) p.wino_f43 = atoi(wf) != 0;
+    if (const char* wf = diag_env("CAPF_WINO_F43_MINHW")) p.wino_f43_min_hw = atoi(wf);
+    if (const char* wf = diag_env("CAPF_WINO_F43_CPN")) p.wino_f43_cpn = atoi(wf) != 0;
+    if (const char* wf = diag_env("CAPF_WINO_F43_MAXHW")) p.wino_f43_max_hw = atoi(wf);
+    // the fused front half (lifter_fused.hip) holds a token row in 4 values per lane and a sampled row in 2 KiB of LDS: wider
+    // configurations (embed_dim_ratio 272 / 288 / ..., > 512-channel context maps) take the one-kernel-per-op plan instead
+    if (cfg.embed_dim_ratio > 256) p.fused_lifter = false;
+    if (cfg.backbone == CAPF_HRNET && cfg.hr_channels[3] > 512) p.fused_lifter = false;
+    return true;
 }
 
 bool Engine::build() {
@@ -1091,42 +1123,7 @@ bool Engine::build() {
             return false;
         }
     }
-    if (cfg.plan_flags & CAPF_PLAN_NO_FUSED_LIFTER) fused_lifter = false;
-    if (cfg.plan_flags & CAPF_PLAN_NO_WINOGRAD) use_wino = false;
-    if (cfg.plan_flags & CAPF_PLAN_NO_ROW_HALO) use_rh = false;
-    if (cfg.plan_flags & CAPF_PLAN_WINOGRAD_F23_ONLY) wino_f43 = false;
-    if (cfg.plan_flags & CAPF_PLAN_NO_PWCHAIN) use_pwchain = false;
-    if (cfg.plan_flags & CAPF_PLAN_NO_UPADD) use_upadd = false;
-    if (cfg.plan_flags & CAPF_PLAN_NO_BNECK) use_bneck = false;
-    if (cfg.plan_flags & CAPF_PLAN_NO_BATCHED_REDUCE) batch_reduce = false;
-    if (cfg.plan_flags & CAPF_PLAN_H2_PLANES) use_h2_planes = true;
-    if (cfg.plan_flags & CAPF_PLAN_NO_WS) use_ws = false;
-    if (cfg.plan_flags & CAPF_PLAN_NO_F32X3) use_x3 = false;
-    if (cfg.plan_flags & CAPF_PLAN_F32X3_EXACT) x3_h2 = false;
-    if (cfg.plan_flags & CAPF_PLAN_NO_F32H2_GEMM) use_h2g = false;
-    if (cfg.plan_flags & CAPF_PLAN_BF16_F32_STREAM) {
-        if (!bf16()) { err = "CAPF_PLAN_BF16_F32_STREAM needs compute_dtype = CAPF_BF16"; return false; }
-        if (cfg.backbone != CAPF_HRNET) { err = "CAPF_PLAN_BF16_F32_STREAM is an HRNet plan (CPN50 is not supported)"; return false; }
-        if (cfg.plan_flags != CAPF_PLAN_BF16_F32_STREAM) { err = "CAPF_PLAN_BF16_F32_STREAM cannot be combined with other plan flags"; return false; }
-        f32_stream = true;
-        // layer1 runs as one launch per conv: the fused bottleneck kernels (bneck_bf16.hip) and the chained pointwise pair have no fp32-stream
-        // epilogue (EXPERIMENTS R7.1 prices it)
-        use_bneck = false;
-        use_pwchain = false;
-    }
-    // tuning knobs of the diagnostic build only (diag_env is a constant nullptr in the product library)
-    if (const char* fz = diag_env("CAPF_LIFTER_FUSED")) fused_lifter = atoi(fz) != 0;
-    if (const char* wz = diag_env("CAPF_WINO")) use_wino = atoi(wz) != 0;
-    if (const char* rz = diag_env("CAPF_BF16_RH")) use_rh = atoi(rz) != 0;
-    if (const char* wb = diag_env("CAPF_WINO_MIN_BATCH")) wino_min_batch = atoi(wb);
-    if (const char* wf = diag_env("CAPF_WINO_F43")) wino_f43 = atoi(wf) != 0;
-    if (const char* wf = diag_env("CAPF_WINO_F43_MINHW")) wino_f43_min_hw = atoi(wf);
-    if (const char* wf = diag_env("CAPF_WINO_F43_CPN")) wino_f43_cpn = atoi(wf) != 0;
-    if (const char* wf = diag_env("CAPF_WINO_F43_MAXHW")) wino_f43_max_hw = atoi(wf);
-    // the fused front half (lifter_fused.hip) holds a token row in 4 values per lane and a sampled row in 2 KiB of LDS: wider
-    // configurations (embed_dim_ratio 272 / 288 / ..., > 512-channel context maps) take the one-kernel-per-op plan instead
-    if (cfg.embed_dim_ratio > 256) fused_lifter = false;
-    if (cfg.backbone == CAPF_HRNET && cfg.hr_channels[3] > 512) fused_lifter = false;
+    if (!set_plan_switches()) return false;
     Tensor img{EXT_IMAGES, cfg.height, cfg.width, 3};
     Tensor feats[4];
     if (cfg.backbone == CAPF_HRNET) {
@@ -1136,7 +1133,7 @@ bool Engine::build() {
                 return false;
             }
         build_hrnet(img, feats);
-        if (f32_stream && !plan_f32_stream(feats)) return false;
+        if (plan.f32_stream && !plan_f32_stream(feats)) return false;
     } else if (cfg.backbone == CAPF_CPN50) {
         build_cpn(img, feats);
     } else {
@@ -1192,22 +1189,22 @@ bool Engine::build() {
     for (Op& op : ops) {
         if (op.kind != OP_GEMM || !op.wino || !packs[op.pack].x3) continue;
         // (upper end: the three-piece tile addresses whole tensors with 31-bit byte offsets; the two-piece tile only counts pixels)
-        const double cap = x3_h2 ? 2.0e9 / ((double)op.H * op.W) : 2.0e9 / ((double)op.H * op.W * (double)std::max(op.Cin, op.N) * 4.0);
+        const double cap = plan.x3_h2 ? 2.0e9 / ((double)op.H * op.W) : 2.0e9 / ((double)op.H * op.W * (double)std::max(op.Cin, op.N) * 4.0);
         int hi = (int)std::min(1.0e6, cap);
-        while (hi >= 1 && hi > (int)cap - 4 && !f32x3_takes(hi, op.H, op.W, op.Cin, op.N, x3_h2)) --hi;   // (the limit itself is exclusive)
-        if (hi < 1 || !f32x3_takes(hi, op.H, op.W, op.Cin, op.N, x3_h2)) continue;
+        while (hi >= 1 && hi > (int)cap - 4 && !f32x3_takes(hi, op.H, op.W, op.Cin, op.N, plan.x3_h2)) --hi;   // (the limit itself is exclusive)
+        if (hi < 1 || !f32x3_takes(hi, op.H, op.W, op.Cin, op.N, plan.x3_h2)) continue;
         int lo = 1, top = hi;                       // smallest accepted batch by bisection
         while (lo < top) {
             const int mid = lo + (top - lo) / 2;
-            if (f32x3_takes(mid, op.H, op.W, op.Cin, op.N, x3_h2)) top = mid; else lo = mid + 1;
+            if (f32x3_takes(mid, op.H, op.W, op.Cin, op.N, plan.x3_h2)) top = mid; else lo = mid + 1;
         }
         op.x3_lo = lo; op.x3_hi = hi;
         // the Winograd layout of this conv is dead weight when the tile covers every batch the Winograd kernels could be asked for
-        if (lo <= wino_min_batch && hi >= cfg.max_batch) packs[op.pack].wino_skip = true;
+        if (lo <= plan.wino_min_batch && hi >= cfg.max_batch) packs[op.pack].wino_skip = true;
     }
     // unit tables of the two-fp16-piece conv tile: one per map geometry among the convs it can take (igemm_f32h2_ws_tile.h, UNIT TABLE)
     utab_host.clear();
-    if (x3_h2 && use_x3) {
+    if (plan.x3_h2 && plan.use_x3) {
         std::map<std::tuple<int, int, int>, long> seen;
         for (Op& op : ops) {
             if (op.kind != OP_GEMM || !op.wino || !packs[op.pack].x3 || op.x3_hi < op.x3_lo) continue;
@@ -1228,41 +1225,41 @@ bool Engine::build() {
     // pack arena layout
     size_t off = 0;
     for (Pack& pk : packs) {
-        if (pk.direct) continue;
+        if (pk.in_place) continue;
         pk.w_off = off;
         off += pk.wino_skip ? 64 : round64(pk.bf16 ? ((size_t)pk.N * pk.Kpad + 1) / 2 : (size_t)pk.N * pk.Kpad);
         if (pk.wino) {
-            pk.w2_off = off;
-            off += round64((size_t)pk.N * pk.Kpad2);
+            pk.direct_off = off;
+            off += round64((size_t)pk.N * pk.direct_Kpad);
         }
         if (pk.rh) {
-            pk.w2_off = off;
-            off += round64(((size_t)pk.N * pk.Kpad2 + 1) / 2);
+            pk.rh_off = off;
+            off += round64(((size_t)pk.N * pk.rh_Kpad + 1) / 2);
         }
         if (pk.ws) {
-            pk.w3_off = off;
+            pk.ws_off = off;
             off += round64(((size_t)bf16_ws_pack_elems(pk.N, pk.Cin) + 1) / 2);
         }
         if (pk.x3) {
-            pk.w3_off = off;
-            off += round64(((size_t)(x3_h2 ? f32h2_pack_elems(pk.N, pk.Cin) : f32x3_pack_elems(pk.N, pk.Cin)) + 1) / 2);
+            pk.x3_off = off;
+            off += round64(((size_t)(plan.x3_h2 ? f32h2_pack_elems(pk.N, pk.Cin) : f32x3_pack_elems(pk.N, pk.Cin)) + 1) / 2);
         }
         pk.b_off = off;
         off += round64((size_t)pk.N);
     }
     for (Pack& pk : packs)                  // (direct linears included: the h2 copy is a pack of its own)
         if (pk.h2g) {
-            pk.wh_off = off;
-            off += round64((size_t)f32h2_gemm_pack_elems(pk.N, pk.KpadH));
+            pk.h2g_off = off;
+            off += round64((size_t)f32h2_gemm_pack_elems(pk.N, pk.h2g_Kpad));
             if (pk.chain) {
-                pk.wc_off = off;
-                off += round64((size_t)f32h2_gemm_pack_elems(pk.N, pk.KpadH));
+                pk.chain_off = off;
+                off += round64((size_t)f32h2_gemm_pack_elems(pk.N, pk.h2g_Kpad));
             }
         }
     {   // room for the bias-copy table: one CopySegment per linear of every packed (non-direct) linear pack
         size_t nseg = 0;
         for (const Pack& pk : packs)
-            if (pk.kind == 1 && !pk.direct) nseg += (size_t)pk.n_lin;
+            if (pk.kind == LINEAR && !pk.in_place) nseg += (size_t)pk.n_lin;
         bias_tab_off = off;
         off += round64(nseg * (sizeof(CopySegment) / sizeof(float)));
     }

@@ -109,7 +109,7 @@ void Engine::t_h2_plan() {
     t_h2_tab.clear();
     t_h2_elems = t_h2_max_elems = 0;
     t_h2_tiles = 0;
-    if (!use_h2g || bf16() || !cfg.training) return;
+    if (!plan.use_h2g || bf16() || !cfg.training) return;
     const int Lv = cfg.levels, C = cfg.embed_dim_ratio, NH = cfg.deform_heads, NS = cfg.deform_samples, DEP = depth();
     auto add = [&](const LinearRef& r, bool fwd, bool bwd) {
         if (r.N < 64) fwd = false;                           // (output columns of y = x W^T ...
@@ -217,7 +217,7 @@ float* Engine::t_slab_take(hipStream_t s, float* area, size_t cap, size_t elems,
 }
 
 int Engine::t_slab_defer(hipStream_t s, const float* slabs, int nslab, long n, float* dst) {
-    if (!batch_reduce) {                                     // CAPF_PLAN_NO_BATCHED_REDUCE: the per-layer kernel, right away; the area is free again
+    if (!plan.batch_reduce) {                                     // CAPF_PLAN_NO_BATCHED_REDUCE: the per-layer kernel, right away; the area is free again
         HIP_TRY(launch_slab_sum(slabs, nslab, n, dst, s));
         if (t_slab_jobs.count == 0) t_slab_cur = 0;
         return CAPF_OK;
@@ -247,8 +247,8 @@ int Engine::t_colreduce(hipStream_t s, const TrainLayout& L, float* tw, const fl
     }
     float* scratch = tw + L.red + t_col_cur;
     t_col_cur += need;
-    HIP_TRY(launch_colreduce(A, amap, Bm, bmap, bmode, rows, C, dst, dst_stride, 0, scratch, s, dst2, cap_elems, batch_reduce ? &t_col_jobs : nullptr));
-    if (!batch_reduce) t_col_cur = 0;                        // (its second stage ran: the scratch is free again)
+    HIP_TRY(launch_colreduce(A, amap, Bm, bmap, bmode, rows, C, dst, dst_stride, 0, scratch, s, dst2, cap_elems, plan.batch_reduce ? &t_col_jobs : nullptr));
+    if (!plan.batch_reduce) t_col_cur = 0;                        // (its second stage ran: the scratch is free again)
     return CAPF_OK;
 }
 
