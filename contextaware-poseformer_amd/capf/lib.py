@@ -10,7 +10,7 @@ HRNET, CPN50 = 0, 1
 F32, BF16 = 0, 1
 PLAN_NO_FUSED_LIFTER, PLAN_NO_WINOGRAD, PLAN_NO_ROW_HALO, PLAN_WINOGRAD_F23_ONLY, PLAN_NO_PWCHAIN, PLAN_NO_WS, PLAN_LIFTER_FP32, PLAN_NO_F32X3, PLAN_F32X3_EXACT, PLAN_NO_F32H2_GEMM, PLAN_NO_UPADD, PLAN_H2_PLANES, PLAN_NO_BNECK, PLAN_NO_BATCHED_REDUCE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192     # capf_plan_flag
 PLAN_BF16_F32_STREAM = 32768     # (1 << 14 stays unassigned)
-ABI_VERSION = 9        # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
+ABI_VERSION = 10       # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
 
 EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.py)
     "capf_create", "capf_destroy", "capf_last_error", "capf_version", "capf_num_params", "capf_param_info",
@@ -27,6 +27,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_abi_version", "capf_op_describe_sized",
     "capf_jpeg_info", "capf_jpeg_coefficients", "capf_jpeg_decode",
     "capf_jpeg_batch_info", "capf_jpeg_decode_batch", "capf_jpeg_coefficients_subseq",
+    "capf_jpeg_crop_rect", "capf_jpeg_crop_batch_info", "capf_jpeg_decode_crop_batch",
     "capf_op_f32h2_gemm_pack_elems", "capf_op_pack_f32h2_gemm", "capf_op_conv_f32h2g", "capf_op_conv_f32h2g_group", "capf_op_linear_f32h2g", "capf_op_linear_ln_f32h2g", "capf_op_wgrad", "capf_op_conv_f32h2_tiles", "capf_op_conv_f32h2_planes", "capf_op_h2_planes",
     "capf_fliptest_fuse_swap", "capf_pck_counts",
 ]
@@ -1010,6 +1011,75 @@ def jpeg_decode_batch(datas, device="cuda", subseq_bytes=0, coefficients=False):
                                                                                      info["h_samp"], info["v_samp"])))
         o += r["coef_elems"]
     return outs, status, coefs
+
+
+def jpeg_crop_rect(width, height, h_samp, v_samp, mat, output_size):
+    """capf_jpeg_crop_rect: which part of a width x height JPEG (sampling factors as jpeg_info reports them) a crop with the forward 2x3
+    matrix `mat` to output_size = (out_w, out_h) can read -> (pixel_rect [x0, y0, x1, y1), mcu_rect [mx0, my0, mx1, my1)), both all zero
+    when the crop lies wholly outside the image.  Host code, no GPU."""
+    import numpy as np
+    lib = load_library()
+    lib.capf_jpeg_crop_rect.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_double), c_int, c_int, POINTER(c_int32), POINTER(c_int32)]
+    m = (c_double * 6)(*np.asarray(mat, dtype=np.float64).reshape(6).tolist())
+    px, mc = (c_int32 * 4)(), (c_int32 * 4)()
+    rc = lib.capf_jpeg_crop_rect(int(width), int(height), int(h_samp), int(v_samp), m, int(output_size[0]), int(output_size[1]), px, mc)
+    if rc:
+        raise CapfError(f"capf_jpeg_crop_rect failed ({rc})")
+    return tuple(px), tuple(mc)
+
+
+def _crop_batch_info(lib, n, ptrs, sizes, m, out_w, out_h, subseq_bytes):
+    lib.capf_jpeg_crop_batch_info.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_size_t)]
+    info = (c_int32 * (13 * max(n, 1)))()
+    sb = c_size_t()
+    rc = lib.capf_jpeg_crop_batch_info(n, ptrs, sizes, m.ctypes.data_as(c_void_p), out_w, out_h, int(subseq_bytes), info, byref(sb))
+    rows = [dict(zip(("width", "height", "components", "coef_elems", "status"), info[13 * i:13 * i + 5]),
+                 pixel_rect=tuple(info[13 * i + 5:13 * i + 9]), mcu_rect=tuple(info[13 * i + 9:13 * i + 13])) for i in range(n)]
+    return rc, rows, sb.value
+
+
+def jpeg_crop_batch_info(datas, mats, output_size, subseq_bytes=0):
+    """-> (rc, list of dict(width, height, components, coef_elems (kept), status, pixel_rect, mcu_rect) per file, scratch bytes or None
+    when rc != 0).  rc is capf_jpeg_crop_batch_info's return value: 0, CAPF_ERR_INVALID for bad arguments, or the capf_jpeg_info error of
+    the first file outside the supported subset.  Host code, no GPU."""
+    import numpy as np
+    lib = load_library()
+    datas, ptrs, sizes = _byte_arrays(datas)
+    n = len(datas)
+    m = np.ascontiguousarray(np.asarray(mats, dtype=np.float64).reshape(n, 6)) if n else np.zeros((1, 6))
+    rc, rows, sb = _crop_batch_info(lib, n, ptrs, sizes, m, int(output_size[0]), int(output_size[1]), subseq_bytes)
+    return rc, rows, (sb if rc == 0 else None)
+
+
+def jpeg_decode_crop_batch(datas, mats, output_size, device="cuda", subseq_bytes=0):
+    """Files in, affine crops out, in ONE call (capf_jpeg_decode_crop_batch): datas = baseline JPEG files (bytes), mats = [n, 2, 3] float64
+    forward matrices, output_size = (out_w, out_h) -> (uint8 CUDA tensor [n, out_h, out_w, 3] with the bits of
+    warp_affine(jpeg_decode_batch(datas)[0], mats, output_size), int32 CUDA status tensor [n]).  Only the MCUs a crop reads are transformed;
+    no frame is ever materialised.  Nothing is synchronised: read `status` (0 = decoded) before trusting a crop.  CapfError (nothing
+    enqueued) when a file is outside the supported subset."""
+    import numpy as np
+    import torch
+    lib = load_library()
+    datas, ptrs, sizes = _byte_arrays(datas)
+    n = len(datas)
+    out_w, out_h = int(output_size[0]), int(output_size[1])
+    m = np.ascontiguousarray(np.asarray(mats, dtype=np.float64).reshape(n, 6)) if n else np.zeros((1, 6))
+    rc, rows, scratch_bytes = _crop_batch_info(lib, n, ptrs, sizes, m, out_w, out_h, subseq_bytes)
+    bad = [i for i, r in enumerate(rows) if r["status"]]
+    if bad:
+        raise CapfError(f"capf_jpeg_crop_batch_info: files {bad} are not JPEGs this path decodes ({[rows[i]['status'] for i in bad]})")
+    if rc:
+        raise CapfError(f"capf_jpeg_crop_batch_info failed ({rc})")
+    out = torch.empty(n, out_h, out_w, 3, dtype=torch.uint8, device=device)
+    status = torch.empty(n, dtype=torch.int32, device=device)
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
+    lib.capf_jpeg_decode_crop_batch.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_int]
+    rc = lib.capf_jpeg_decode_crop_batch(_stream(out), n, ptrs, sizes, m.ctypes.data_as(c_void_p), out_h, out_w, _p(out), _p(scratch), scratch_bytes,
+                                         _p(status), int(subseq_bytes))
+    if rc:
+        raise CapfError(f"capf_jpeg_decode_crop_batch failed ({rc})")
+    # (scratch may be freed on return: the caching allocator hands it out again only to work ordered after these kernels on this stream)
+    return out, status
 
 
 # ---- N2: evaluation metrics (mvn/models/loss.py:25-101, datasets/human36m.py:358-417) ---------------------------

@@ -575,7 +575,7 @@ static std::string g_create_error;
 
 extern "C" {
 
-const char* capf_version(void) { return "capf 0.9 (gfx950)"; }
+const char* capf_version(void) { return "capf 0.10 (gfx950)"; }
 int capf_abi_version(void) { return CAPF_ABI_VERSION; }
 
 const char* capf_last_error(const capf_handle* h) { return h ? h->e.err.c_str() : g_create_error.c_str(); }

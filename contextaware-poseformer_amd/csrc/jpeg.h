@@ -31,6 +31,9 @@ struct JpegDev {
     int bw[3], bh[3], pw[3], ph[3], dw[3], dh[3];      // blocks, plane size, true ("downsampled") size of each component
     long coef_off[3], plane_off[3];
     unsigned short qt[3][64];
+    // crop-aware route (jpeg_batch.hip) only, 0 elsewhere: the planes hold the image from luma pixel (pox, poy) on -- whole MCUs, bw / bh /
+    // pw / ph are the patch's -- and the output buffer from pixel (ox, oy) on.  W, H, dw, dh stay the image's: edges are image edges.
+    int pox, poy, ox, oy;
 };
 
 // the pixel kernels' view of a parsed header
@@ -101,44 +104,46 @@ __device__ __forceinline__ void jpeg_idct_block(const short* __restrict__ coef, 
 
 // chroma sample at full resolution: jdsample.c fullsize / h2v1_fancy / h2v2_fancy with libjpeg's edge handling (context rows replicated at the
 // top and below the component's last true row; first / last column special-cased)
-__device__ __forceinline__ int jpeg_chroma(const unsigned char* pl, int pw, int dw, int dh, int hs, int vs, int x, int y) {
-    if (hs == 1 && vs == 1) return pl[(long)y * pw + x];
-    const int cx = x >> 1, odd = x & 1;
+__device__ __forceinline__ int jpeg_chroma(const unsigned char* pl, int pw, int dw, int dh, int hs, int vs, int x, int y, int cox, int coy) {
+    // (x, y): image coordinates, which the edge rules are about; pl holds the plane from chroma sample (cox, coy) on
+    if (hs == 1 && vs == 1) return pl[(long)(y - coy) * pw + (x - cox)];
+    const int cx = x >> 1, odd = x & 1, lx = cx - cox;
     if (vs == 1) {                                      // h2v1
-        const unsigned char* r = pl + (long)y * pw;
-        const int v = r[cx];
+        const unsigned char* r = pl + (long)(y - coy) * pw;
+        const int v = r[lx];
         if (dw == 1) return v;
-        if (!odd) return cx == 0 ? v : (v * 3 + r[cx - 1] + 1) >> 2;
-        return cx == dw - 1 ? v : (v * 3 + r[cx + 1] + 2) >> 2;
+        if (!odd) return cx == 0 ? v : (v * 3 + r[lx - 1] + 1) >> 2;
+        return cx == dw - 1 ? v : (v * 3 + r[lx + 1] + 2) >> 2;
     }
     const int cy = y >> 1;                              // h2v2: nearer row cy, farther row cy -/+ 1
     const int fy = min(max((y & 1) ? cy + 1 : cy - 1, 0), dh - 1);
-    const unsigned char* r0 = pl + (long)cy * pw;
-    const unsigned char* r1 = pl + (long)fy * pw;
-    const int cur = r0[cx] * 3 + r1[cx];
+    const unsigned char* r0 = pl + (long)(cy - coy) * pw;
+    const unsigned char* r1 = pl + (long)(fy - coy) * pw;
+    const int cur = r0[lx] * 3 + r1[lx];
     if (!odd) {
         if (cx == 0) return (cur * 4 + 8) >> 4;
-        return (cur * 3 + (r0[cx - 1] * 3 + r1[cx - 1]) + 8) >> 4;
+        return (cur * 3 + (r0[lx - 1] * 3 + r1[lx - 1]) + 8) >> 4;
     }
     if (cx == dw - 1) return (cur * 4 + 7) >> 4;
-    return (cur * 3 + (r0[cx + 1] * 3 + r1[cx + 1]) + 7) >> 4;
+    return (cur * 3 + (r0[lx + 1] * 3 + r1[lx + 1]) + 7) >> 4;
 }
 
 // pixel (x, y) of the image: upsampling + YCbCr -> BGR
 __device__ __forceinline__ void jpeg_color_pixel(const unsigned char* __restrict__ planes, unsigned char* __restrict__ out, const JpegDev& jd, long out_pitch,
                                                  int x, int y) {
-    const int Y = planes[jd.plane_off[0] + (long)y * jd.pw[0] + x];
+    const int Y = planes[jd.plane_off[0] + (long)(y - jd.poy) * jd.pw[0] + (x - jd.pox)];
     int r = Y, g = Y, b = Y;
     if (jd.nc == 3) {
-        const int cb = jpeg_chroma(planes + jd.plane_off[1], jd.pw[1], jd.dw[1], jd.dh[1], jd.hmax, jd.vmax, x, y) - 128;
-        const int cr = jpeg_chroma(planes + jd.plane_off[2], jd.pw[2], jd.dw[2], jd.dh[2], jd.hmax, jd.vmax, x, y) - 128;
+        const int cox = jd.pox / jd.hmax, coy = jd.poy / jd.vmax;
+        const int cb = jpeg_chroma(planes + jd.plane_off[1], jd.pw[1], jd.dw[1], jd.dh[1], jd.hmax, jd.vmax, x, y, cox, coy) - 128;
+        const int cr = jpeg_chroma(planes + jd.plane_off[2], jd.pw[2], jd.dw[2], jd.dh[2], jd.hmax, jd.vmax, x, y, cox, coy) - 128;
         // jdcolor.c build_ycc_rgb_table, SCALEBITS 16: FIX(1.40200) = 91881, FIX(1.77200) = 116130, FIX(0.71414) = 46802, FIX(0.34414) = 22554
         r = Y + ((91881 * cr + 32768) >> 16);
         b = Y + ((116130 * cb + 32768) >> 16);
         g = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
         r = min(max(r, 0), 255); g = min(max(g, 0), 255); b = min(max(b, 0), 255);
     }
-    unsigned char* o = out + (long)y * out_pitch + 3L * x;
+    unsigned char* o = out + (long)(y - jd.oy) * out_pitch + 3L * (x - jd.ox);
     o[0] = (unsigned char)b; o[1] = (unsigned char)g; o[2] = (unsigned char)r;
 }
 

@@ -10,6 +10,11 @@
 //                       block), the block-count / error checks;
 //   jb_dc_kernel        one workgroup per segment: DC differences -> values per component;
 //   jb_idct_kernel, jb_color_kernel: one grid over all blocks / pixels of all images.
+//
+// capf_jpeg_decode_crop_batch is the same up to jb_seg_kernel, for a caller that only wants an affine crop of each file (warp_rule.h says
+// which pixels that reads): the write pass keeps the AC coefficients of the MCUs around those pixels only, in a compact buffer, and every
+// block's DC difference (a DC value needs all differences before it in the segment); IDCT and colour run over that rectangle into a
+// BGR patch, and jb_warp_crop_kernel samples the patch with the image's border.  No full-frame buffer exists on that route.
 // No kernel waits on another workgroup; the host never reads anything back.  A corrupt file sets its status word, the others are unaffected.
 #include <string.h>
 
@@ -20,6 +25,7 @@
 #include "jpeg.h"
 #include "jpeg_sync.h"
 #include "kernels.h"
+#include "warp_rule.h"
 
 namespace capf {
 
@@ -45,6 +51,7 @@ struct JbImage {
     long pitch;
     int* status;
     int raw_len, lane_bound, L, nblocks_idct;
+    JbCrop cr;                           // crop-aware route only: there jd, coef, planes and out (the BGR patch) are the rectangle's
 };
 
 // host side of one file: parsed header, decoder tables, sizes
@@ -53,6 +60,10 @@ struct JbPrep {
     JbTables t;
     const unsigned char* raw = nullptr;
     int raw_len = 0, lane_bound = 0;
+    bool crop = false;                   // crop-aware route: the rectangle, its geometry (jd) and its buffer sizes
+    JbCrop cr{};
+    JpegDev jd{};
+    size_t crop_plane_bytes = 0, patch_pitch = 0, patch_bytes = 0;
 };
 
 static int jb_prepare(const unsigned char* d, size_t n, int L, JbPrep& p) {
@@ -81,6 +92,33 @@ static int jb_prepare(const unsigned char* d, size_t n, int L, JbPrep& p) {
     p.raw_len = (int)(n - h.scan_off);
     p.lane_bound = p.raw_len / L + sc.nseg + 1;          // >= sum over segments of max(1, ceil(bytes / L))
     return CAPF_OK;
+}
+
+// crop-aware route: the source rectangle of crop matrix m (warp_rule.h), its MCUs, and the pixel kernels' geometry over those MCUs alone
+static void jb_prepare_crop(JbPrep& p, const double* m, int out_w, int out_h) {
+    const JpegHeader& h = p.h;
+    JbCrop& cr = p.cr;
+    p.crop = true;
+    memset(&cr, 0, sizeof(cr));
+    memcpy(cr.m, m, sizeof(cr.m));
+    warp_source_rect(h.W, h.H, m, out_w, out_h, cr.rect);
+    warp_mcu_rect(h.W, h.H, h.hmax, h.vmax, cr.rect, cr.mcu);
+    const int rw = cr.mcu[2] - cr.mcu[0], rh = cr.mcu[3] - cr.mcu[1];
+    p.jd = jpeg_dev(h);
+    size_t co = 0, po = 0;
+    for (int i = 0; i < h.nc; ++i) {
+        const JpegComp& c = h.c[i];
+        p.jd.bw[i] = rw * c.h; p.jd.bh[i] = rh * c.v; p.jd.pw[i] = p.jd.bw[i] * 8; p.jd.ph[i] = p.jd.bh[i] * 8;
+        p.jd.coef_off[i] = cr.coef_off[i] = (long)co; co += (size_t)p.jd.bw[i] * p.jd.bh[i] * 64;
+        p.jd.plane_off[i] = (long)po; po += (size_t)p.jd.pw[i] * p.jd.ph[i];
+        cr.cbw[i] = p.jd.bw[i];
+    }
+    cr.coef_elems = (long)co;
+    p.crop_plane_bytes = (po + 15) & ~(size_t)15;
+    p.jd.pox = cr.mcu[0] * 8 * h.hmax; p.jd.poy = cr.mcu[1] * 8 * h.vmax;
+    p.jd.ox = cr.rect[0]; p.jd.oy = cr.rect[1];
+    p.patch_pitch = 3 * (size_t)(cr.rect[2] - cr.rect[0]);
+    p.patch_bytes = (p.patch_pitch * (cr.rect[3] - cr.rect[1]) + 15) & ~(size_t)15;
 }
 
 __host__ __device__ static inline JbSeg jb_segment(const JbScan& sc, const unsigned char* bytes, const int* seg, int s) {
@@ -159,7 +197,7 @@ static int jb_emulate(const JbPrep& p, int L, short* coef) {
             JbState e{};
             if (j) e = f[j - 1];
             e.first = f[j].first;
-            jb_run<true>(g.d, g.nbytes, jb_lane_end(g, L, j), g.nblocks, tabs, sc, e, coef, g.mcu0);
+            jb_run<JB_WRITE>(g.d, g.nbytes, jb_lane_end(g, L, j), g.nblocks, tabs, sc, e, coef, g.mcu0);
         }
         int pred[3] = {0, 0, 0};
         jb_dc_values(sc, g.mcu0, 0, g.nblocks, pred, coef, true);
@@ -237,7 +275,8 @@ __global__ __launch_bounds__(1024) void jb_unstuff_kernel(const JbImage* __restr
     if (t == 0) lane_off[S] = min(lanes, im.lane_bound);
 }
 
-// MODE 0: first pass; 1: sync round `round` (reads st[(round - 1) & 1], writes st[round & 1]); 2: write pass from st[kJbRounds & 1]
+// MODE 0: first pass; 1: sync round `round` (reads st[(round - 1) & 1], writes st[round & 1]); 2: write pass from st[kJbRounds & 1];
+// 3: the crop-aware route's write pass (DC differences of all blocks, AC of the blocks inside im.cr's MCU rectangle)
 template <int MODE>
 __global__ __launch_bounds__(kJbLanesPerWg) void jb_lane_kernel(const JbImage* __restrict__ imgs, const int2* __restrict__ wg, int round) {
     const int2 w = wg[blockIdx.x];                         // (image, first lane)
@@ -264,7 +303,8 @@ __global__ __launch_bounds__(kJbLanesPerWg) void jb_lane_kernel(const JbImage* _
         JbState e{};
         if (j) e = f[j - 1];
         e.first = f[j].first;
-        jb_run<true>(sg.d, sg.nbytes, jb_lane_end(sg, im.L, j), sg.nblocks, lt.tabs, lt.sc, e, im.coef, sg.mcu0);
+        if (MODE == 2) jb_run<JB_WRITE>(sg.d, sg.nbytes, jb_lane_end(sg, im.L, j), sg.nblocks, lt.tabs, lt.sc, e, im.coef, sg.mcu0);
+        else jb_run<JB_WRITE_CROP>(sg.d, sg.nbytes, jb_lane_end(sg, im.L, j), sg.nblocks, lt.tabs, lt.sc, e, im.coef, sg.mcu0, &im.cr);
     }
 }
 
@@ -299,7 +339,9 @@ __global__ __launch_bounds__(256) void jb_seg_kernel(const JbImage* __restrict__
     }
 }
 
-// one workgroup per (image, segment): DC differences -> values, per component, over per-thread runs of blocks
+// one workgroup per (image, segment): DC differences -> values, per component, over per-thread runs of blocks (CROP: differences from
+// im.cr.dc, values into the rectangle's blocks)
+template <bool CROP>
 __global__ __launch_bounds__(256) void jb_dc_kernel(const JbImage* __restrict__ imgs, const int2* __restrict__ wg) {
     const int2 w = wg[blockIdx.x];
     const JbImage& im = imgs[w.x];
@@ -308,11 +350,13 @@ __global__ __launch_bounds__(256) void jb_dc_kernel(const JbImage* __restrict__ 
     __shared__ int part[3][257];
     const int t = threadIdx.x, per = (nb + 255) / 256, a = min(nb, t * per), b = min(nb, a + per);
     int pred[3] = {0, 0, 0};
-    jb_dc_values(sc, mcu0, a, b, pred, im.coef, false);
+    if (CROP) jb_dc_values_crop(sc, im.cr, mcu0, a, b, pred, im.coef, false);
+    else jb_dc_values(sc, mcu0, a, b, pred, im.coef, false);
     for (int ci = 0; ci < 3; ++ci) part[ci][t] = pred[ci];
     for (int ci = 0; ci < 3; ++ci) jb_exclusive_scan(part[ci], 256);
     for (int ci = 0; ci < 3; ++ci) pred[ci] = part[ci][t];
-    jb_dc_values(sc, mcu0, a, b, pred, im.coef, true);
+    if (CROP) jb_dc_values_crop(sc, im.cr, mcu0, a, b, pred, im.coef, true);
+    else jb_dc_values(sc, mcu0, a, b, pred, im.coef, true);
 }
 
 __global__ __launch_bounds__(64) void jb_idct_kernel(const JbImage* __restrict__ imgs) {
@@ -331,28 +375,49 @@ __global__ __launch_bounds__(256) void jb_color_kernel(const JbImage* __restrict
     jpeg_color_pixel(im.planes, im.out, im.jd, im.pitch, x, y);
 }
 
+// crop-aware route: colour over the pixels the warp reads (image coordinates; im.jd places them in the rectangle's planes and patch)
+__global__ __launch_bounds__(256) void jb_color_crop_kernel(const JbImage* __restrict__ imgs) {
+    const JbImage& im = imgs[blockIdx.z];
+    const int x = im.cr.rect[0] + blockIdx.x * 64 + (threadIdx.x & 63), y = im.cr.rect[1] + blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= im.cr.rect[2] || y >= im.cr.rect[3]) return;
+    jpeg_color_pixel(im.planes, im.out, im.jd, im.pitch, x, y);
+}
+
+// crop-aware route: capf_warp_affine's arithmetic (warp_rule.h) on the patch; out = [n, out_h, out_w, 3]
+__global__ __launch_bounds__(256) void jb_warp_crop_kernel(const JbImage* __restrict__ imgs, unsigned char* __restrict__ out, int n, int out_h, int out_w) {
+    const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (t >= (long)n * out_h * out_w) return;
+    const int x = (int)(t % out_w), y = (int)((t / out_w) % out_h);
+    const JbImage& im = imgs[t / ((long)out_w * out_h)];
+    const WarpMap w = warp_inverse(im.cr.m);
+    warp_affine_pixel<true>(im.out, im.jd.H, im.jd.W, im.pitch, im.cr.rect, w, x, y, out + t * 3);
+}
+
 // ---- batch layout -----------------------------------------------------------------------------------------------------------------
 static inline size_t jb_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct JbLayout {
     size_t desc, wg_lane, wg_seg, raw, upload;             // the uploaded prefix
-    size_t bytes, seg, st, coef, planes, total;            // device-only areas
-    std::vector<size_t> raw_off, bytes_off, seg_off, st_off, coef_off, planes_off;
+    size_t bytes, seg, st, coef, dc, planes, patch, total;  // device-only areas (dc, patch: crop-aware route, empty otherwise)
+    std::vector<size_t> raw_off, bytes_off, seg_off, st_off, coef_off, dc_off, planes_off, patch_off;
     int n_wg_lane = 0, n_wg_seg = 0;
 };
 
 static void jb_layout(const std::vector<JbPrep>& p, JbLayout& l) {
     const int n = (int)p.size();
     l.raw_off.resize(n); l.bytes_off.resize(n); l.seg_off.resize(n); l.st_off.resize(n); l.coef_off.resize(n); l.planes_off.resize(n);
-    size_t raw = 0, bytes = 0, seg = 0, st = 0, coef = 0, planes = 0;
+    l.dc_off.resize(n); l.patch_off.resize(n);
+    size_t raw = 0, bytes = 0, seg = 0, st = 0, coef = 0, planes = 0, dc = 0, patch = 0;
     l.n_wg_lane = l.n_wg_seg = 0;
     for (int i = 0; i < n; ++i) {
         l.raw_off[i] = raw; raw += (p[i].raw_len + 15) & ~15;
         l.bytes_off[i] = bytes; bytes += (p[i].raw_len + 15) & ~15;
         l.seg_off[i] = seg; seg += ((3 * (size_t)p[i].t.sc.nseg + 1) * sizeof(int) + 15) & ~(size_t)15;
         l.st_off[i] = st; st += 2 * (size_t)p[i].lane_bound * sizeof(JbState);
-        l.coef_off[i] = coef; coef += (p[i].h.coef_elems * sizeof(short) + 15) & ~(size_t)15;
-        l.planes_off[i] = planes; planes += p[i].h.plane_bytes;
+        l.coef_off[i] = coef; coef += ((p[i].crop ? (size_t)p[i].cr.coef_elems : p[i].h.coef_elems) * sizeof(short) + 15) & ~(size_t)15;
+        l.dc_off[i] = dc; dc += p[i].crop ? ((size_t)p[i].t.sc.mcus * p[i].t.sc.bpm * sizeof(short) + 15) & ~(size_t)15 : 0;
+        l.planes_off[i] = planes; planes += p[i].crop ? p[i].crop_plane_bytes : p[i].h.plane_bytes;
+        l.patch_off[i] = patch; patch += p[i].patch_bytes;
         l.n_wg_lane += (p[i].lane_bound + kJbLanesPerWg - 1) / kJbLanesPerWg;
         l.n_wg_seg += p[i].t.sc.nseg;
     }
@@ -365,13 +430,75 @@ static void jb_layout(const std::vector<JbPrep>& p, JbLayout& l) {
     l.seg = jb_align(l.bytes + bytes);
     l.st = jb_align(l.seg + seg);
     l.coef = jb_align(l.st + st);
-    l.planes = jb_align(l.coef + coef);
-    l.total = jb_align(l.planes + planes);
+    l.dc = jb_align(l.coef + coef);                         // (coef and dc are zeroed together: [l.coef, l.planes))
+    l.planes = jb_align(l.dc + dc);
+    l.patch = jb_align(l.planes + planes);
+    l.total = jb_align(l.patch + patch);
 }
 
 static int jb_subseq(int subseq_bytes) {
     if (subseq_bytes == 0) return kJbSubseqDefault;
     return subseq_bytes >= 1 && subseq_bytes <= (1 << 20) ? subseq_bytes : -1;
+}
+
+// What both routes do with a prepared batch: stage [descriptors | work tables | raw bytes] (fill(i, im) sets the route's own fields of
+// descriptor i), upload once, zero the status words and [zero, zero + zero_bytes), and enqueue the entropy stages up to jb_seg_kernel.
+struct JbCall {
+    hipStream_t s;
+    const JbImage* desc;
+    const int2 *wl, *ws;
+};
+
+template <class Fill>
+static int jb_enqueue_entropy(void* stream, const std::vector<JbPrep>& p, const JbLayout& l, int L, unsigned char* dev, int32_t* status, void* zero,
+                              size_t zero_bytes, Fill fill, JbCall& c, hipEvent_t& uploaded_out) {
+    const int n = (int)p.size();
+    static thread_local std::vector<unsigned char> host;  // (one call at a time per thread: the upload is waited for before returning)
+    host.assign(l.upload, 0);
+    JbImage* desc = reinterpret_cast<JbImage*>(host.data() + l.desc);
+    int2* wl = reinterpret_cast<int2*>(host.data() + l.wg_lane);
+    int2* ws = reinterpret_cast<int2*>(host.data() + l.wg_seg);
+    for (int i = 0, nl = 0, ns = 0; i < n; ++i) {
+        JbImage& im = desc[i];
+        im.t = p[i].t;
+        im.raw = dev + l.raw + l.raw_off[i];
+        im.bytes = dev + l.bytes + l.bytes_off[i];
+        im.seg = reinterpret_cast<int*>(dev + l.seg + l.seg_off[i]);
+        im.st[0] = reinterpret_cast<JbState*>(dev + l.st + l.st_off[i]);
+        im.st[1] = im.st[0] + p[i].lane_bound;
+        im.planes = dev + l.planes + l.planes_off[i];
+        im.status = status + i;
+        im.raw_len = p[i].raw_len;
+        im.lane_bound = p[i].lane_bound;
+        im.L = L;
+        fill(i, im);
+        memcpy(host.data() + l.raw + l.raw_off[i], p[i].raw, p[i].raw_len);
+        for (int w = 0; w < (p[i].lane_bound + kJbLanesPerWg - 1) / kJbLanesPerWg; ++w) wl[nl++] = make_int2(i, w * kJbLanesPerWg);
+        for (int s = 0; s < p[i].t.sc.nseg; ++s) ws[ns++] = make_int2(i, s);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    static thread_local hipEvent_t uploaded = nullptr;
+    if (!uploaded && hipEventCreateWithFlags(&uploaded, hipEventDisableTiming) != hipSuccess) return CAPF_ERR_HIP;
+    uploaded_out = uploaded;
+    if (hipMemcpyAsync(dev, host.data(), l.upload, hipMemcpyHostToDevice, s) != hipSuccess) return CAPF_ERR_HIP;
+    if (hipEventRecord(uploaded, s) != hipSuccess) return CAPF_ERR_HIP;
+    if (hipMemsetAsync(status, 0, n * sizeof(int32_t), s) != hipSuccess) return CAPF_ERR_HIP;
+    if (zero_bytes && hipMemsetAsync(zero, 0, zero_bytes, s) != hipSuccess) return CAPF_ERR_HIP;
+    c.s = s;
+    c.desc = reinterpret_cast<const JbImage*>(dev + l.desc);
+    c.wl = reinterpret_cast<const int2*>(dev + l.wg_lane);
+    c.ws = reinterpret_cast<const int2*>(dev + l.wg_seg);
+    hipLaunchKernelGGL(jb_unstuff_kernel, dim3(n), dim3(1024), 0, s, c.desc);
+    hipLaunchKernelGGL(jb_lane_kernel<0>, dim3(l.n_wg_lane), dim3(kJbLanesPerWg), 0, s, c.desc, c.wl, 0);
+    for (int r = 1; r <= kJbRounds; ++r) hipLaunchKernelGGL(jb_lane_kernel<1>, dim3(l.n_wg_lane), dim3(kJbLanesPerWg), 0, s, c.desc, c.wl, r);
+    hipLaunchKernelGGL(jb_seg_kernel, dim3(l.n_wg_seg), dim3(256), 0, s, c.desc, c.ws);
+    return CAPF_OK;
+}
+
+// the staging buffer is reused by this thread's next call: wait for the upload only, never for the kernels
+static int jb_finish(hipEvent_t uploaded) {
+    if (hipGetLastError() != hipSuccess) return CAPF_ERR_HIP;
+    return hipEventSynchronize(uploaded) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
 }  // namespace capf
@@ -424,59 +551,112 @@ int capf_jpeg_decode_batch(void* stream, int n, const uint8_t* const* data, cons
     jb_layout(p, l);
     if (scratch_bytes < l.total) return CAPF_ERR_INVALID;
     unsigned char* dev = static_cast<unsigned char*>(scratch);
-    static thread_local std::vector<unsigned char> host;  // (one call at a time per thread: the upload is waited for before returning)
-    host.assign(l.upload, 0);
-    JbImage* desc = reinterpret_cast<JbImage*>(host.data() + l.desc);
-    int2* wl = reinterpret_cast<int2*>(host.data() + l.wg_lane);
-    int2* ws = reinterpret_cast<int2*>(host.data() + l.wg_seg);
     size_t coef_base = 0;
     int max_blocks = 0, max_w = 0, max_h = 0;
-    for (int i = 0, nl = 0, ns = 0; i < n; ++i) {
-        JbImage& im = desc[i];
-        im.t = p[i].t;
-        im.jd = jpeg_dev(p[i].h);
-        im.raw = dev + l.raw + l.raw_off[i];
-        im.bytes = dev + l.bytes + l.bytes_off[i];
-        im.seg = reinterpret_cast<int*>(dev + l.seg + l.seg_off[i]);
-        im.st[0] = reinterpret_cast<JbState*>(dev + l.st + l.st_off[i]);
-        im.st[1] = im.st[0] + p[i].lane_bound;
-        im.coef = coef_out ? coef_out + coef_base : reinterpret_cast<short*>(dev + l.coef + l.coef_off[i]);
+    for (int i = 0; i < n; ++i) {
         coef_base += p[i].h.coef_elems;
-        im.planes = dev + l.planes + l.planes_off[i];
-        im.out = out_bgr[i];
-        im.pitch = (long)out_pitch_bytes[i];
-        im.status = status + i;
-        im.raw_len = p[i].raw_len;
-        im.lane_bound = p[i].lane_bound;
-        im.L = L;
-        im.nblocks_idct = (int)(p[i].h.coef_elems / 64);
-        memcpy(host.data() + l.raw + l.raw_off[i], p[i].raw, p[i].raw_len);
-        for (int w = 0; w < (p[i].lane_bound + kJbLanesPerWg - 1) / kJbLanesPerWg; ++w) wl[nl++] = make_int2(i, w * kJbLanesPerWg);
-        for (int s = 0; s < p[i].t.sc.nseg; ++s) ws[ns++] = make_int2(i, s);
-        max_blocks = std::max(max_blocks, im.nblocks_idct);
+        max_blocks = std::max(max_blocks, (int)(p[i].h.coef_elems / 64));
         max_w = std::max(max_w, p[i].h.W);
         max_h = std::max(max_h, p[i].h.H);
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    static thread_local hipEvent_t uploaded = nullptr;
-    if (!uploaded && hipEventCreateWithFlags(&uploaded, hipEventDisableTiming) != hipSuccess) return CAPF_ERR_HIP;
-    if (hipMemcpyAsync(dev, host.data(), l.upload, hipMemcpyHostToDevice, s) != hipSuccess) return CAPF_ERR_HIP;
-    if (hipEventRecord(uploaded, s) != hipSuccess) return CAPF_ERR_HIP;
-    if (hipMemsetAsync(status, 0, n * sizeof(int32_t), s) != hipSuccess) return CAPF_ERR_HIP;
-    if (hipMemsetAsync(coef_out ? (void*)coef_out : (void*)(dev + l.coef), 0, coef_out ? coef_base * sizeof(short) : l.planes - l.coef, s) != hipSuccess)
-        return CAPF_ERR_HIP;
-    const JbImage* d_desc = reinterpret_cast<const JbImage*>(dev + l.desc);
-    const int2* d_wl = reinterpret_cast<const int2*>(dev + l.wg_lane);
-    const int2* d_ws = reinterpret_cast<const int2*>(dev + l.wg_seg);
-    hipLaunchKernelGGL(jb_unstuff_kernel, dim3(n), dim3(1024), 0, s, d_desc);
-    hipLaunchKernelGGL(jb_lane_kernel<0>, dim3(l.n_wg_lane), dim3(kJbLanesPerWg), 0, s, d_desc, d_wl, 0);
-    for (int r = 1; r <= kJbRounds; ++r) hipLaunchKernelGGL(jb_lane_kernel<1>, dim3(l.n_wg_lane), dim3(kJbLanesPerWg), 0, s, d_desc, d_wl, r);
-    hipLaunchKernelGGL(jb_seg_kernel, dim3(l.n_wg_seg), dim3(256), 0, s, d_desc, d_ws);
-    hipLaunchKernelGGL(jb_lane_kernel<2>, dim3(l.n_wg_lane), dim3(kJbLanesPerWg), 0, s, d_desc, d_wl, 0);
-    hipLaunchKernelGGL(jb_dc_kernel, dim3(l.n_wg_seg), dim3(256), 0, s, d_desc, d_ws);
-    hipLaunchKernelGGL(jb_idct_kernel, dim3((max_blocks + 63) / 64, n), dim3(64), 0, s, d_desc);
-    hipLaunchKernelGGL(jb_color_kernel, dim3((max_w + 63) / 64, (max_h + 3) / 4, n), dim3(256), 0, s, d_desc);
-    if (hipGetLastError() != hipSuccess) return CAPF_ERR_HIP;
-    // the staging buffer is reused by this thread's next call: wait for the upload only, never for the kernels
-    return hipEventSynchronize(uploaded) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    size_t coef_at = 0;
+    auto fill = [&](int i, JbImage& im) {
+        im.jd = jpeg_dev(p[i].h);
+        im.coef = coef_out ? coef_out + coef_at : reinterpret_cast<short*>(dev + l.coef + l.coef_off[i]);
+        coef_at += p[i].h.coef_elems;
+        im.out = out_bgr[i];
+        im.pitch = (long)out_pitch_bytes[i];
+        im.nblocks_idct = (int)(p[i].h.coef_elems / 64);
+    };
+    JbCall c;
+    hipEvent_t uploaded;
+    const int rc = jb_enqueue_entropy(stream, p, l, L, dev, status, coef_out ? (void*)coef_out : (void*)(dev + l.coef),
+                                      coef_out ? coef_base * sizeof(short) : l.planes - l.coef, fill, c, uploaded);
+    if (rc != CAPF_OK) return rc;
+    hipLaunchKernelGGL(jb_lane_kernel<2>, dim3(l.n_wg_lane), dim3(kJbLanesPerWg), 0, c.s, c.desc, c.wl, 0);
+    hipLaunchKernelGGL(jb_dc_kernel<false>, dim3(l.n_wg_seg), dim3(256), 0, c.s, c.desc, c.ws);
+    hipLaunchKernelGGL(jb_idct_kernel, dim3((max_blocks + 63) / 64, n), dim3(64), 0, c.s, c.desc);
+    hipLaunchKernelGGL(jb_color_kernel, dim3((max_w + 63) / 64, (max_h + 3) / 4, n), dim3(256), 0, c.s, c.desc);
+    return jb_finish(uploaded);
+}
+
+// ---- crop-aware route ---------------------------------------------------------------------------------------------------------------
+int capf_jpeg_crop_rect(int width, int height, int h_samp, int v_samp, const double m[6], int out_w, int out_h, int32_t pixel_rect[4], int32_t mcu_rect[4]) {
+    const bool sampling = (h_samp == 1 && v_samp == 1) || (h_samp == 2 && v_samp == 1) || (h_samp == 2 && v_samp == 2);
+    if (width <= 0 || height <= 0 || !sampling || !m || out_w <= 0 || out_h <= 0 || !pixel_rect || !mcu_rect) return CAPF_ERR_INVALID;
+    int rect[4], mcu[4];
+    capf::warp_source_rect(width, height, m, out_w, out_h, rect);
+    capf::warp_mcu_rect(width, height, h_samp, v_samp, rect, mcu);
+    for (int k = 0; k < 4; ++k) { pixel_rect[k] = rect[k]; mcu_rect[k] = mcu[k]; }
+    return CAPF_OK;
+}
+
+int capf_jpeg_crop_batch_info(int n, const uint8_t* const* data, const size_t* n_bytes, const double* m, int out_w, int out_h, int subseq_bytes,
+                              int32_t* info, size_t* scratch_bytes) {
+    const int L = capf::jb_subseq(subseq_bytes);
+    if (n <= 0 || !data || !n_bytes || !m || out_w <= 0 || out_h <= 0 || L < 0) return CAPF_ERR_INVALID;
+    std::vector<JbPrep> p(n);
+    int worst = CAPF_OK;
+    for (int i = 0; i < n; ++i) {
+        const int rc = capf::jb_prepare(data[i], n_bytes[i], L, p[i]);
+        if (rc == CAPF_OK) capf::jb_prepare_crop(p[i], m + 6 * (size_t)i, out_w, out_h);
+        if (info) {
+            int32_t* r = info + 13 * i;
+            for (int k = 0; k < 13; ++k) r[k] = 0;
+            r[4] = rc;
+            if (rc == CAPF_OK) {
+                r[0] = p[i].h.W; r[1] = p[i].h.H; r[2] = p[i].h.nc; r[3] = (int32_t)p[i].cr.coef_elems;
+                for (int k = 0; k < 4; ++k) { r[5 + k] = p[i].cr.rect[k]; r[9 + k] = p[i].cr.mcu[k]; }
+            }
+        }
+        if (rc != CAPF_OK && worst == CAPF_OK) worst = rc;
+    }
+    if (worst != CAPF_OK) return worst;
+    capf::JbLayout l;
+    capf::jb_layout(p, l);
+    if (scratch_bytes) *scratch_bytes = l.total;
+    return CAPF_OK;
+}
+
+int capf_jpeg_decode_crop_batch(void* stream, int n, const uint8_t* const* data, const size_t* n_bytes, const double* m, int out_h, int out_w, uint8_t* out,
+                                void* scratch, size_t scratch_bytes, int32_t* status, int subseq_bytes) {
+    using namespace capf;
+    const int L = jb_subseq(subseq_bytes);
+    if (n <= 0 || !data || !n_bytes || !m || out_h <= 0 || out_w <= 0 || !out || !scratch || !status || L < 0) return CAPF_ERR_INVALID;
+    std::vector<JbPrep> p(n);
+    int max_blocks = 0, max_w = 0, max_h = 0;
+    for (int i = 0; i < n; ++i) {                        // the whole batch is checked before anything is enqueued
+        const int rc = jb_prepare(data[i], n_bytes[i], L, p[i]);
+        if (rc != CAPF_OK) return rc;
+        jb_prepare_crop(p[i], m + 6 * (size_t)i, out_w, out_h);
+        max_blocks = std::max(max_blocks, (int)(p[i].cr.coef_elems / 64));
+        max_w = std::max(max_w, p[i].cr.rect[2] - p[i].cr.rect[0]);
+        max_h = std::max(max_h, p[i].cr.rect[3] - p[i].cr.rect[1]);
+    }
+    JbLayout l;
+    jb_layout(p, l);
+    if (scratch_bytes < l.total) return CAPF_ERR_INVALID;
+    unsigned char* dev = static_cast<unsigned char*>(scratch);
+    auto fill = [&](int i, JbImage& im) {
+        im.jd = p[i].jd;
+        im.cr = p[i].cr;
+        im.cr.dc = reinterpret_cast<short*>(dev + l.dc + l.dc_off[i]);
+        im.coef = reinterpret_cast<short*>(dev + l.coef + l.coef_off[i]);
+        im.out = dev + l.patch + l.patch_off[i];
+        im.pitch = (long)p[i].patch_pitch;
+        im.nblocks_idct = (int)(p[i].cr.coef_elems / 64);
+    };
+    JbCall c;
+    hipEvent_t uploaded;
+    const int rc = jb_enqueue_entropy(stream, p, l, L, dev, status, dev + l.coef, l.planes - l.coef, fill, c, uploaded);
+    if (rc != CAPF_OK) return rc;
+    hipLaunchKernelGGL(jb_lane_kernel<3>, dim3(l.n_wg_lane), dim3(kJbLanesPerWg), 0, c.s, c.desc, c.wl, 0);
+    hipLaunchKernelGGL(jb_dc_kernel<true>, dim3(l.n_wg_seg), dim3(256), 0, c.s, c.desc, c.ws);
+    if (max_blocks) {                                    // (no file's crop touches its image: nothing to transform, the warp writes the border)
+        hipLaunchKernelGGL(jb_idct_kernel, dim3((max_blocks + 63) / 64, n), dim3(64), 0, c.s, c.desc);
+        hipLaunchKernelGGL(jb_color_crop_kernel, dim3((max_w + 63) / 64, (max_h + 3) / 4, n), dim3(256), 0, c.s, c.desc);
+    }
+    const long total = (long)n * out_h * out_w;
+    hipLaunchKernelGGL(jb_warp_crop_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.s, c.desc, out, n, out_h, out_w);
+    return jb_finish(uploaded);
 }

@@ -98,28 +98,61 @@ __host__ __device__ inline long jb_block_offset(const JbScan& sc, int mcu0, int 
     return sc.coef_off[ci] + ((long)(my * sc.cv[ci] + sc.bby[bm]) * sc.cbw[ci] + (mx * sc.ch[ci] + sc.bbx[bm])) * 64;
 }
 
+// crop-aware route: which MCUs of the image are kept, and the compact coefficient layout over them -- component after component, blocks
+// [rows][cols][64] over the MCU rectangle, i.e. capf_jpeg_coefficients' layout of an image that is just the rectangle
+struct JbCrop {
+    int mcu[4];                       // kept MCUs [mx0, my0, mx1, my1); empty when the crop reads no pixel of the image
+    int rect[4];                      // the pixels the warp reads, [x0, y0, x1, y1), inside those MCUs
+    long coef_off[3];
+    int cbw[3];                       // blocks per row of the rectangle, per component
+    long coef_elems;
+    short* dc;                        // [mcus * bpm] every block's DC difference, decode order, rectangle or not
+    double m[6];                      // the crop's forward matrix
+};
+
+// offset of block `blk` in the rectangle's coefficient layout, -1 for a block outside the rectangle
+__host__ __device__ inline long jb_crop_offset(const JbScan& sc, const JbCrop& cr, int mcu0, int blk) {
+    const int m = mcu0 + blk / sc.bpm, bm = blk - (blk / sc.bpm) * sc.bpm;
+    const int my = m / sc.mcux, mx = m - my * sc.mcux, ci = sc.bci[bm];
+    if (mx < cr.mcu[0] || mx >= cr.mcu[2] || my < cr.mcu[1] || my >= cr.mcu[3]) return -1;
+    const long off = cr.coef_off[ci] + ((long)((my - cr.mcu[1]) * sc.cv[ci] + sc.bby[bm]) * cr.cbw[ci] + ((mx - cr.mcu[0]) * sc.ch[ci] + sc.bbx[bm])) * 64;
+    return off >= 0 && off + 64 <= cr.coef_elems ? off : -1;
+}
+
 // Decodes the symbols that START before bit `end` from state st (pos, b, k), stopping early once max_blocks blocks are complete.  The
 // count goes to st.nblk.  WRITE: coefficients of block st.first + (completed blocks) while that is < max_blocks -- AC at natural
 // positions, the DC DIFFERENCE at [0] (jb_dc_values turns differences into values).  Loops are bounded by the bit position (every
 // symbol consumes at least one bit) and by max_blocks; writes by the image's coefficient count.
-template <bool WRITE>
+// WRITE = JB_WRITE_CROP (crop-aware route; `coef` is the rectangle's compact buffer): the DC difference of EVERY block goes to crop->dc
+// [mcu0 * bpm + block] -- a block's DC value needs all differences before it in the segment --, AC only for blocks inside the rectangle.
+enum { JB_COUNT = 0, JB_WRITE = 1, JB_WRITE_CROP = 2 };
+template <int WRITE>
 __host__ __device__ inline void jb_run(const unsigned char* d, int nbytes, int end, int max_blocks, const JbHuff* tabs, const JbScan& sc, JbState& st,
-                                       short* coef, int mcu0) {
+                                       short* coef, int mcu0, const JbCrop* crop = nullptr) {
     int pos = st.pos, b = st.b, k = st.k, n = 0;
     st.nblk = 0;
     if (st.err) return;
     short* blk = nullptr;
+    short* dcp = nullptr;             // JB_WRITE_CROP: where this block's DC difference goes; null past the segment's last block
     auto locate = [&]() {
         const int g = st.first + n;
         blk = nullptr;
-        if (g < max_blocks) {
-            const long off = jb_block_offset(sc, mcu0, g);
-            if (off >= 0 && off + 64 <= sc.coef_elems) blk = coef + off;
+        dcp = nullptr;
+        if (g >= 0 && g < max_blocks) {
+            if (WRITE == JB_WRITE_CROP) {
+                dcp = crop->dc + ((long)mcu0 * sc.bpm + g);
+                const long off = jb_crop_offset(sc, *crop, mcu0, g);
+                if (off >= 0) blk = coef + off;
+            } else {
+                const long off = jb_block_offset(sc, mcu0, g);
+                if (off >= 0 && off + 64 <= sc.coef_elems) blk = coef + off;
+            }
         }
     };
     if (WRITE) locate();
     while (pos < end && n < max_blocks) {
-        if (WRITE && !blk) break;
+        if (WRITE == JB_WRITE && !blk) break;
+        if (WRITE == JB_WRITE_CROP && !dcp) break;
         const int ci = sc.bci[b];
         int len;
         if (k == 0) {
@@ -128,7 +161,8 @@ __host__ __device__ inline void jb_run(const unsigned char* d, int nbytes, int e
             pos += len;
             int diff = 0;
             if (s) { diff = jb_extend((int)(jb_bits32(d, nbytes, pos) >> (32 - s)), s); pos += s; }
-            if (WRITE) blk[0] = (short)diff;
+            if (WRITE == JB_WRITE) blk[0] = (short)diff;
+            if (WRITE == JB_WRITE_CROP) *dcp = (short)diff;
             k = 1;
             continue;
         }
@@ -145,7 +179,7 @@ __host__ __device__ inline void jb_run(const unsigned char* d, int nbytes, int e
                 if (sz > 10) { st.err = 1; break; }
                 const int v = jb_extend((int)(jb_bits32(d, nbytes, pos) >> (32 - sz)), sz);
                 pos += sz;
-                if (WRITE) blk[sc.zz[k]] = (short)v;
+                if (WRITE == JB_WRITE || (WRITE == JB_WRITE_CROP && blk)) blk[sc.zz[k]] = (short)v;
                 ++k;
             }
         }
@@ -176,7 +210,7 @@ __host__ __device__ inline int jb_lane_end(const JbSeg& s, int L, int j) {
 // first pass: lane j from its guessed entry
 __host__ __device__ inline void jb_lane_init(const JbSeg& s, int L, int j, const JbHuff* tabs, const JbScan& sc, JbState& out) {
     out.pos = j * L * 8; out.b = 0; out.k = 0; out.err = 0; out.first = 0;
-    jb_run<false>(s.d, s.nbytes, jb_lane_end(s, L, j), s.nblocks, tabs, sc, out, nullptr, 0);
+    jb_run<JB_COUNT>(s.d, s.nbytes, jb_lane_end(s, L, j), s.nblocks, tabs, sc, out, nullptr, 0);
     out.changed = 1;
 }
 
@@ -188,7 +222,7 @@ __host__ __device__ inline void jb_lane_round(const JbSeg& s, int L, int j, cons
     } else {
         e = src[j - 1];
         e.first = 0;
-        jb_run<false>(s.d, s.nbytes, jb_lane_end(s, L, j), s.nblocks, tabs, sc, e, nullptr, 0);
+        jb_run<JB_COUNT>(s.d, s.nbytes, jb_lane_end(s, L, j), s.nblocks, tabs, sc, e, nullptr, 0);
         e.changed = !jb_same(e, src[j]);
     }
     dst[j] = e;
@@ -206,7 +240,7 @@ __host__ __device__ inline void jb_lane_fallback(const JbSeg& s, int L, int j0, 
         if (!proven) {
             t = v;
             t.first = 0;
-            jb_run<false>(s.d, s.nbytes, jb_lane_end(s, L, j), s.nblocks, tabs, sc, t, nullptr, 0);
+            jb_run<JB_COUNT>(s.d, s.nbytes, jb_lane_end(s, L, j), s.nblocks, tabs, sc, t, nullptr, 0);
             t.changed = 0;
             st[j] = t;
         }
@@ -223,6 +257,17 @@ __host__ __device__ inline void jb_dc_values(const JbScan& sc, int mcu0, int b0,
         if (off < 0 || off + 64 > sc.coef_elems) continue;
         pred[ci] += coef[off];
         if (write) coef[off] = (short)pred[ci];
+    }
+}
+
+// the same for the crop-aware route: sums over crop.dc (every block of the segment), values stored only where the block is kept
+__host__ __device__ inline void jb_dc_values_crop(const JbScan& sc, const JbCrop& cr, int mcu0, int b0, int b1, int pred[3], short* coef, bool write) {
+    for (int g = b0; g < b1; ++g) {
+        const int bm = g % sc.bpm, ci = sc.bci[bm];
+        pred[ci] += cr.dc[(long)mcu0 * sc.bpm + g];
+        if (!write) continue;
+        const long off = jb_crop_offset(sc, cr, mcu0, g);
+        if (off >= 0) coef[off] = (short)pred[ci];
     }
 }
 

@@ -9,6 +9,7 @@
 // Same fp32 operation order as the reference as it runs on a GPU ((u * (1/255) - mean) / std; 192 - x - 1), so
 // results are bit-identical to the torch expressions.  Built with -ffp-contract=off.
 #include "kernels.h"
+#include "warp_rule.h"
 
 namespace capf {
 
@@ -177,7 +178,8 @@ bool affine_from_center_scale(const double center[2], const double scale[2], int
 
 // cv2.warpAffine(frame, M, (out_w, out_h), INTER_LINEAR, BORDER_CONSTANT 0) for 8-bit 3-channel frames: OpenCV's
 // fixed-point pipeline (10-bit coordinates, 5-bit fractions, 15-bit weights) restated per output pixel.
-// frames[b]: device pointer of frame b; dims[b] = {rows, cols, row pitch in bytes}; M[b]: forward 2x3 matrix.
+// frames[b]: device pointer of frame b; dims[b] = {rows, cols, row pitch in bytes}; M[b]: forward 2x3 matrix.  The arithmetic itself is
+// warp_rule.h's, shared with the crop-aware JPEG route and with the host rule that bounds what a crop reads.
 __global__ void warp_affine_u8_kernel(const unsigned char* const* __restrict__ frames, const int* __restrict__ dims,
                                       const double* __restrict__ M, unsigned char* __restrict__ out, int B, int out_h, int out_w) {
     const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -186,36 +188,8 @@ __global__ void warp_affine_u8_kernel(const unsigned char* const* __restrict__ f
     const int x = (int)(t % out_w);
     const int y = (int)((t / out_w) % out_h);
     const int b = (int)(t / ((long)out_w * out_h));
-    const double* m = M + (long)b * 6;
-    double d = m[0] * m[4] - m[1] * m[3];
-    d = d != 0.0 ? 1.0 / d : 0.0;
-    const double a00 = m[4] * d, a11 = m[0] * d, a01 = m[1] * -d, a10 = m[3] * -d;
-    const double b0 = -a00 * m[2] - a01 * m[5];
-    const double b1 = -a10 * m[2] - a11 * m[5];
-    const long adelta = __double2ll_rn(a00 * (double)x * 1024.0);
-    const long bdelta = __double2ll_rn(a10 * (double)x * 1024.0);
-    const long X0 = __double2ll_rn((a01 * (double)y + b0) * 1024.0) + 16;
-    const long Y0 = __double2ll_rn((a11 * (double)y + b1) * 1024.0) + 16;
-    const long X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-    long sx = X >> 5, sy = Y >> 5;
-    sx = sx < -32768 ? -32768 : (sx > 32767 ? 32767 : sx);
-    sy = sy < -32768 ? -32768 : (sy > 32767 ? 32767 : sy);
-    const int ax = (int)(X & 31), ay = (int)(Y & 31);
-    const int H = dims[b * 3 + 0], W = dims[b * 3 + 1], pitch = dims[b * 3 + 2];
-    const unsigned char* src = frames[b];
-    const int w00 = (32 - ay) * (32 - ax) * 32, w01 = (32 - ay) * ax * 32, w10 = ay * (32 - ax) * 32, w11 = ay * ax * 32;
-    const bool y0ok = sy >= 0 && sy < H, y1ok = sy + 1 >= 0 && sy + 1 < H;
-    const bool x0ok = sx >= 0 && sx < W, x1ok = sx + 1 >= 0 && sx + 1 < W;
-    unsigned char* o = out + t * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        int acc = 16384;
-        if (y0ok && x0ok) acc += w00 * src[(long)sy * pitch + sx * 3 + c];
-        if (y0ok && x1ok) acc += w01 * src[(long)sy * pitch + (sx + 1) * 3 + c];
-        if (y1ok && x0ok) acc += w10 * src[(long)(sy + 1) * pitch + sx * 3 + c];
-        if (y1ok && x1ok) acc += w11 * src[(long)(sy + 1) * pitch + (sx + 1) * 3 + c];
-        o[c] = (unsigned char)(acc >> 15);
-    }
+    const WarpMap w = warp_inverse(M + (long)b * 6);
+    warp_affine_pixel<false>(frames[b], dims[b * 3 + 0], dims[b * 3 + 1], dims[b * 3 + 2], nullptr, w, x, y, out + t * 3);
 }
 
 hipError_t launch_warp_affine_u8(const unsigned char* const* frames, const int* dims, const double* M, unsigned char* out,

@@ -55,11 +55,21 @@ def imread_batch(paths_or_bytes, device="cuda", subseq_bytes=0):
 def load_and_crop_batch(paths_or_bytes, centers, scales, output_size, device="cuda", decoder="host"):
     """The whole per-sample image path of Human36M.__getitem__ (human36m.py:292-300) for a batch: decode every frame on the GPU, then ONE
     warp launch for all crops.  Returns uint8 CUDA [B, output_size[1], output_size[0], 3], what the prefetcher (capf_preprocess) consumes.
-    decoder="host": one imread per frame (host Huffman walk); "device": one imread_batch for all frames (same bits)."""
+    decoder="host": one imread per frame (host Huffman walk); "device": one imread_batch for all frames (same bits); "device_crop": one
+    capf_jpeg_decode_crop_batch call for files -> crops, which transforms only the MCUs each crop reads and never builds a frame (same
+    bits again; raises CapfError naming corrupt files, as imread_batch does)."""
+    if decoder == "device_crop":
+        items = list(paths_or_bytes)
+        mats = np.stack([get_affine_transform(c, s, 0, output_size) for c, s in zip(centers, scales)])
+        crops, status = _capf.jpeg_decode_crop_batch([_read_bytes(p) for p in items], mats, output_size, device)
+        bad = [(items[i] if not isinstance(items[i], (bytes, bytearray)) else f"#{i}", int(s)) for i, s in enumerate(status.cpu().tolist()) if s]
+        if bad:
+            raise _capf.CapfError(f"capf_jpeg_decode_crop_batch: corrupt entropy data in {bad} (file, status bits)")
+        return crops
     if decoder == "host":
         frames = [imread(p, device) for p in paths_or_bytes]
     elif decoder == "device":
         frames = imread_batch(paths_or_bytes, device)
     else:
-        raise ValueError(f"decoder must be 'host' or 'device', not {decoder!r}")
+        raise ValueError(f"decoder must be 'host', 'device' or 'device_crop', not {decoder!r}")
     return crop_image_batch(frames, centers, scales, output_size)

@@ -138,8 +138,9 @@ const char* capf_version(void);
  * (an op's bf16 shadow output); struct layouts unchanged.  Revision 8 (additive): the batched JPEG decode (capf_jpeg_batch_info,
  * capf_jpeg_decode_batch, capf_jpeg_coefficients_subseq); struct layouts unchanged.  Revision 9 (additive): training plans of the variant
  * without context blocks at any depth 1..8 (its two widths) (its DropPath layout at capf_forward_train), capf_fliptest_fuse_swap, capf_pck_counts; struct
- * layouts unchanged.                                                                                                                       */
-#define CAPF_ABI_VERSION 9
+ * layouts unchanged.  Revision 10 (additive): the crop-aware JPEG route (capf_jpeg_crop_rect, capf_jpeg_crop_batch_info,
+ * capf_jpeg_decode_crop_batch); struct layouts unchanged.                                                                                  */
+#define CAPF_ABI_VERSION 10
 int capf_abi_version(void);
 
 /* ---- parameter schema == the reference's state_dict ------------- */
@@ -542,6 +543,34 @@ int capf_jpeg_decode_batch(void* stream, int n, const uint8_t* const* data, cons
                            const size_t* out_pitch_bytes, int16_t* coef_out, void* scratch, size_t scratch_bytes, int32_t* status,
                            int subseq_bytes);
 int capf_jpeg_coefficients_subseq(const uint8_t* data, size_t n_bytes, int16_t* coef, size_t coef_elems, int subseq_bytes);
+/* capf_jpeg_crop_rect / capf_jpeg_crop_batch_info / capf_jpeg_decode_crop_batch: the crop-aware route -- files in, affine crops out, for a
+ *   caller whose only use of the frames is capf_warp_affine.  For every file whose status word is 0, out[i] equals
+ *   capf_warp_affine(capf_jpeg_decode_batch(file i), m_i) bit for bit, at every subseq_bytes and for any forward matrix (rotation and shear
+ *   included).  The entropy decode is capf_jpeg_decode_batch's (it is serial per segment and has to walk every block); from the write pass
+ *   on only the MCUs the warp can read are kept: AC coefficients of those MCUs in a compact buffer, one DC difference per block of the
+ *   whole image (a DC value is the sum of the differences before it in its segment), then dequantisation, IDCT, upsampling and colour
+ *   over that rectangle into a BGR patch which the warp samples with the rectangle's origin subtracted and the IMAGE's border (constant
+ *   0).  No full-frame buffer is allocated anywhere.
+ *   capf_jpeg_crop_rect (host only): the rule.  pixel_rect = [x0, y0, x1, y1) is the smallest rectangle of a width x height image that
+ *   holds every tap of the out_w x out_h crop with forward matrix m: the warp's own fixed-point coordinates (inverse map in double, rounded
+ *   to 1/1024, taps at the integer part and the integer part + 1) evaluated at the four output corners -- each axis is a sum of one
+ *   monotonic term per output coordinate, so the corners give the exact extremes --, clamped to the image.  All four are 0 when the crop
+ *   lies wholly outside the image (the output is then all border).  mcu_rect = [mx0, my0, mx1, my1) in MCUs of 8 h_samp x 8 v_samp
+ *   pixels: pixel_rect grown by one pixel on the sides along which chroma is subsampled (h_samp / v_samp = 2: "fancy" upsampling
+ *   reads the neighbouring chroma sample and replicates only at true image edges), clamped, then widened to whole MCUs.  h_samp, v_samp:
+ *   capf_jpeg_info's (1,1 / 2,1 / 2,2; grey files report 1,1).
+ *   capf_jpeg_crop_batch_info (host only): m = host double [n][6]; info[n][13] = width, height, components, coefficients kept (64 per
+ *   block of the MCU rectangle), status (CAPF_OK or the file's capf_jpeg_info error), pixel_rect[4], mcu_rect[4]; *scratch_bytes = device
+ *   scratch capf_jpeg_decode_crop_batch needs for these files, matrices, output size and subsequence length.  n >= 1.
+ *   capf_jpeg_decode_crop_batch: m = HOST double [n][6] forward matrices; out = device uint8 [n, out_h, out_w, 3]; scratch, status,
+ *   subseq_bytes, the refusal of a batch holding an unsupported file and the stream behaviour (enqueue, wait only for the staging
+ *   upload) as capf_jpeg_decode_batch.  A flagged file's crop is undefined; the other files are unaffected.                              */
+int capf_jpeg_crop_rect(int width, int height, int h_samp, int v_samp, const double m[6], int out_w, int out_h, int32_t pixel_rect[4],
+                        int32_t mcu_rect[4]);
+int capf_jpeg_crop_batch_info(int n, const uint8_t* const* data, const size_t* n_bytes, const double* m, int out_w, int out_h,
+                              int subseq_bytes, int32_t* info, size_t* scratch_bytes);
+int capf_jpeg_decode_crop_batch(void* stream, int n, const uint8_t* const* data, const size_t* n_bytes, const double* m, int out_h,
+                                int out_w, uint8_t* out, void* scratch, size_t scratch_bytes, int32_t* status, int subseq_bytes);
 int capf_affine_from_center_scale(const double center[2], const double scale[2], int out_w, int out_h, double m[6]);
 int capf_warp_affine(void* stream, const uint8_t* const* frames, const int32_t* dims, const double* m, int batch,
                      int out_h, int out_w, uint8_t* out);
