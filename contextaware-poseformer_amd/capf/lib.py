@@ -10,7 +10,7 @@ HRNET, CPN50 = 0, 1
 F32, BF16 = 0, 1
 PLAN_NO_FUSED_LIFTER, PLAN_NO_WINOGRAD, PLAN_NO_ROW_HALO, PLAN_WINOGRAD_F23_ONLY, PLAN_NO_PWCHAIN, PLAN_NO_WS, PLAN_LIFTER_FP32, PLAN_NO_F32X3, PLAN_F32X3_EXACT, PLAN_NO_F32H2_GEMM, PLAN_NO_UPADD, PLAN_H2_PLANES, PLAN_NO_BNECK, PLAN_NO_BATCHED_REDUCE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192     # capf_plan_flag
 PLAN_BF16_F32_STREAM = 32768     # (1 << 14 stays unassigned)
-ABI_VERSION = 10       # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
+ABI_VERSION = 11       # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
 
 EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.py)
     "capf_create", "capf_destroy", "capf_last_error", "capf_version", "capf_num_params", "capf_param_info",
@@ -30,6 +30,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_jpeg_crop_rect", "capf_jpeg_crop_batch_info", "capf_jpeg_decode_crop_batch",
     "capf_op_f32h2_gemm_pack_elems", "capf_op_pack_f32h2_gemm", "capf_op_conv_f32h2g", "capf_op_conv_f32h2g_group", "capf_op_linear_f32h2g", "capf_op_linear_ln_f32h2g", "capf_op_wgrad", "capf_op_conv_f32h2_tiles", "capf_op_conv_f32h2_planes", "capf_op_h2_planes",
     "capf_fliptest_fuse_swap", "capf_pck_counts",
+    "capf_optim_ctrl_bytes", "capf_optim_ctrl_init", "capf_grad_sumsq", "capf_adamw_step_guarded",
 ]
 
 
@@ -62,6 +63,19 @@ class ConvDesc(ctypes.Structure):
                 ("residual", ctypes.c_void_p), ("y", ctypes.c_void_p)] + \
                [(k, ctypes.c_int32) for k in ("B", "H", "W", "Cin", "Cout", "ks", "stride", "act")]
 
+
+class OptimReport(ctypes.Structure):
+    """mirrors include/capf.h :: capf_optim_report (the head of the guarded AdamW step's control block)"""
+    _fields_ = [(k, c_int64) for k in ("steps_taken", "steps_skipped", "nonfinite_losses", "grad_nonfinite")] + \
+               [(k, c_double) for k in ("grad_sumsq", "grad_norm", "clip_coef", "loss_sum", "loss_rows")]
+
+
+class OptimSegment(ctypes.Structure):
+    """mirrors include/capf.h :: capf_optim_segment"""
+    _fields_ = [("begin", c_int64), ("end", c_int64), ("lr", c_float), ("weight_decay", c_float)]
+
+
+OPTIM_MAX_SEGMENTS = 64       # include/capf.h :: CAPF_OPTIM_MAX_SEGMENTS
 
 _lib = None
 
@@ -133,6 +147,11 @@ def load_library():
     lib.capf_mpjpe.argtypes = [P, P, P, c_int, P, P, c_float]
     lib.capf_mpjpe_nd.argtypes = [P, P, P, c_int, c_int, P, P, c_float]
     lib.capf_adamw_step.argtypes = [P, P, P, P, P, c_int64] + [c_float] * 5 + [c_int, c_float]
+    lib.capf_optim_ctrl_bytes.argtypes = []
+    lib.capf_optim_ctrl_bytes.restype = c_size_t
+    lib.capf_optim_ctrl_init.argtypes = [P, P, c_int64]
+    lib.capf_grad_sumsq.argtypes = [P, P, c_int64, c_float, P]
+    lib.capf_adamw_step_guarded.argtypes = [P, P, P, P, P, c_int64, POINTER(OptimSegment), c_int] + [c_float] * 5 + [c_int64, P, c_int, P]
     lib.capf_op_bilinear_corners.argtypes = [P, P, c_int, c_int, c_int, c_int, P, P]
     lib.capf_op_pack_conv.argtypes = [P, P, P, P, P, P, c_float, P, P, c_int, c_int, c_int]
     lib.capf_op_conv.argtypes = [P, P, P, P, P, P] + [c_int] * 8

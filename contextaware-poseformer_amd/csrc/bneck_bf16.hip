@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256, 1) void bneck_bf16_kernel(Bneck0Args a) {
             for (int g = 0; g < 4; ++g) {
                 float t[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) t[e] = in_img ? fmaxf(acc1[j][4 * g + e], 0.f) : 0.f;
+                for (int e = 0; e < 4; ++e) t[e] = in_img ? relu_f(acc1[j][4 * g + e]) : 0.f;
                 const bn_u32x2 pk = bn_u32x2{pack_bf16x2(t[0], t[1]), pack_bf16x2(t[2], t[3])};
                 if (slot_ok) *reinterpret_cast<bn_u32x2*>(wk + t1_wr + ((((4 * j + g) ^ t1_sw) & 7) * 16)) = pk;
                 if (TAP && a_interior) *reinterpret_cast<bn_u32x2*>(a.t1 + (frame_px + (size_t)ha * a.W + wa) * 64 + 32 * j + 8 * g + 4 * fhalf) = pk;
@@ -248,8 +248,8 @@ __global__ __launch_bounds__(256, 1) void bneck_bf16_kernel(Bneck0Args a) {
         bn_u32x2 t2p[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            t2p[g] = bn_u32x2{pack_bf16x2(fmaxf(acc2[4 * g], 0.f), fmaxf(acc2[4 * g + 1], 0.f)),
-                              pack_bf16x2(fmaxf(acc2[4 * g + 2], 0.f), fmaxf(acc2[4 * g + 3], 0.f))};
+            t2p[g] = bn_u32x2{pack_bf16x2(relu_f(acc2[4 * g]), relu_f(acc2[4 * g + 1])),
+                              pack_bf16x2(relu_f(acc2[4 * g + 2]), relu_f(acc2[4 * g + 3]))};
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();         // every wave is done reading t1: t2 goes over it
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256, 1) void bneck_bf16_kernel(Bneck0Args a) {
                 typedef float f2_t __attribute__((ext_vector_type(2)));
                 const f2_t s01 = f2_t{z[i][4 * g], z[i][4 * g + 1]} + f2_t{__uint_as_float(r01 << 16), __uint_as_float(r01 & 0xFFFF0000u)};
                 const f2_t s23 = f2_t{z[i][4 * g + 2], z[i][4 * g + 3]} + f2_t{__uint_as_float(r23 << 16), __uint_as_float(r23 & 0xFFFF0000u)};
-                const float y0 = fmaxf(s01[0], 0.f), y1 = fmaxf(s01[1], 0.f), y2 = fmaxf(s23[0], 0.f), y3 = fmaxf(s23[1], 0.f);
+                const float y0 = relu_f(s01[0]), y1 = relu_f(s01[1]), y2 = relu_f(s23[0]), y3 = relu_f(s23[1]);
                 if (BN_EXP & 32) __builtin_amdgcn_raw_buffer_store_b64(bn_u32x2{pack_bf16x2(y0, y1), pack_bf16x2(y2, y3)}, rs_y, (unsigned)(((th0 + pr) * a.W + tw0 + pc) * 256 + n0 + 8 * g + 4 * fhalf) * 2u, 0, 0);
                 else *reinterpret_cast<bn_u32x2*>(ep + frow * BN_EP_PITCH + ((g ^ ((frow >> 2) & 3)) * 16) + fhalf * 8) = bn_u32x2{pack_bf16x2(y0, y1), pack_bf16x2(y2, y3)};
                 if (TAP && DS) *reinterpret_cast<bn_u32x2*>(a.r + (frame_px + (size_t)(th0 + pr) * a.W + tw0 + pc) * 256 + n0 + 8 * g + 4 * fhalf) = bn_u32x2{r01, r23};

@@ -139,8 +139,8 @@ __device__ __forceinline__ void fuse_sum_body(const FuseSumArgs& a, const long f
         if (a.relu) {
 #pragma unroll
             for (int q = 0; q < Q; ++q) {
-                acc[q][0] = fmaxf(acc[q][0], 0.f); acc[q][1] = fmaxf(acc[q][1], 0.f);
-                acc[q][2] = fmaxf(acc[q][2], 0.f); acc[q][3] = fmaxf(acc[q][3], 0.f);
+                acc[q][0] = relu_f(acc[q][0]); acc[q][1] = relu_f(acc[q][1]);
+                acc[q][2] = relu_f(acc[q][2]); acc[q][3] = relu_f(acc[q][3]);
             }
         }
         if (V == 8) {

@@ -575,7 +575,7 @@ static std::string g_create_error;
 
 extern "C" {
 
-const char* capf_version(void) { return "capf 0.10 (gfx950)"; }
+const char* capf_version(void) { return "capf 0.11 (gfx950)"; }
 int capf_abi_version(void) { return CAPF_ABI_VERSION; }
 
 const char* capf_last_error(const capf_handle* h) { return h ? h->e.err.c_str() : g_create_error.c_str(); }
@@ -834,6 +834,43 @@ int capf_adamw_step(void* stream, float* params, const float* grads, float* exp_
     if (!params || !grads || !exp_avg || !exp_avg_sq || n <= 0 || step <= 0) return CAPF_ERR_INVALID;
     return capf::launch_adamw(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step,
                               static_cast<hipStream_t>(stream), grad_scale) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+}
+
+size_t capf_optim_ctrl_bytes(void) { return sizeof(capf::OptimCtrl); }
+
+int capf_optim_ctrl_init(void* stream, void* ctrl, int64_t steps_taken) {
+    if (!ctrl || (reinterpret_cast<uintptr_t>(ctrl) & 7) || steps_taken < 0) return CAPF_ERR_INVALID;
+    return capf::launch_optim_ctrl_init(static_cast<capf::OptimCtrl*>(ctrl), steps_taken, static_cast<hipStream_t>(stream)) == hipSuccess
+               ? CAPF_OK : CAPF_ERR_HIP;
+}
+
+int capf_grad_sumsq(void* stream, const float* grads, int64_t n, float grad_scale, void* ctrl) {
+    if (!grads || n <= 0 || !ctrl || (reinterpret_cast<uintptr_t>(ctrl) & 7)) return CAPF_ERR_INVALID;
+    return capf::launch_grad_sumsq(grads, n, grad_scale, static_cast<capf::OptimCtrl*>(ctrl), static_cast<hipStream_t>(stream)) == hipSuccess
+               ? CAPF_OK : CAPF_ERR_HIP;
+}
+
+int capf_adamw_step_guarded(void* stream, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                            const capf_optim_segment* segments, int n_segments, float beta1, float beta2, float eps, float grad_scale,
+                            float max_norm, int64_t attempt, const float* loss, int rows, void* ctrl) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || n <= 0 || !segments || n_segments <= 0 || attempt <= 0 || rows < 0 || !ctrl ||
+        (reinterpret_cast<uintptr_t>(ctrl) & 7))
+        return CAPF_ERR_INVALID;
+    if (n_segments > CAPF_OPTIM_MAX_SEGMENTS) return CAPF_ERR_UNSUPPORTED;
+    capf::AdamwSegments segs = {};
+    int64_t at = 0;
+    for (int k = 0; k < n_segments; ++k) {
+        if (segments[k].begin != at || segments[k].end < at) return CAPF_ERR_INVALID;
+        at = segments[k].end;
+        segs.end[k] = (long)at;
+        segs.lr[k] = segments[k].lr;
+        segs.wd[k] = segments[k].weight_decay;
+    }
+    if (at != n) return CAPF_ERR_INVALID;
+    segs.count = n_segments;
+    return capf::launch_adamw_guarded(params, grads, exp_avg, exp_avg_sq, n, segs, beta1, beta2, eps, grad_scale, max_norm, attempt, loss,
+                                      rows, static_cast<capf::OptimCtrl*>(ctrl), static_cast<hipStream_t>(stream)) == hipSuccess
+               ? CAPF_OK : CAPF_ERR_HIP;
 }
 
 int capf_lifter_forward(capf_handle* h, void* stream, const float* k2d, float* kcrop_inout, int batch, float* out) {

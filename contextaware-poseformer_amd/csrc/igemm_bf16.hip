@@ -439,7 +439,7 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
         float* ep = reinterpret_cast<float*>(lds) + wave * (32 * EPS);
         auto finish = [&](float t) {
             if (GELU) t = 0.5f * t * (1.0f + erff(t * 0.70710678118654752440f));
-            if (p.act == ACT_RELU) t = fmaxf(t, 0.f);
+            if (p.act == ACT_RELU) t = relu_f(t);
             return t;
         };
         auto transpose_block = [&](int i, int j) {
@@ -765,7 +765,7 @@ __device__ __forceinline__ void igemm_bf16_rh_tile(const GemmArgs& p, const int 
     // ---- epilogue: the coalesced bf16 epilogue of igemm_bf16_tile (32x32 blocks transposed through the idle stage)
     constexpr int EPS = 36;
     float* ep = reinterpret_cast<float*>(lds) + wave * (32 * EPS);
-    auto finish = [&](float t) { return p.act == ACT_RELU ? fmaxf(t, 0.f) : t; };
+    auto finish = [&](float t) { return p.act == ACT_RELU ? relu_f(t) : t; };
     auto transpose_block = [&](int i, int j) {
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -975,7 +975,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float t = acc[i][j][4 * g + e] + (p.bias ? p.bias[n + e] : 0.f);
-                    if (p.act == ACT_RELU) t = fmaxf(t, 0.f);
+                    if (p.act == ACT_RELU) t = relu_f(t);
                     v[e] = f2bf(t);
                 }
                 *reinterpret_cast<u16x4*>(Out + o_row + n) = v;
@@ -1098,7 +1098,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 t[e] = acc[i][4 * g + e] + bv[e];
-                if (p.act == ACT_RELU) t[e] = fmaxf(t[e], 0.f);
+                if (p.act == ACT_RELU) t[e] = relu_f(t[e]);
             }
             *reinterpret_cast<u32x2*>(Out + (long)m * p.omap.S1 + p.omap.off + n) = u32x2{pack_bf16x2(t[0], t[1]), pack_bf16x2(t[2], t[3])};
         }
@@ -1286,7 +1286,7 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs
             for (int e = 0; e < 4; ++e) { t[e] = x0[e] + b0[e]; t[4 + e] = x1[e] + b1[e]; }
             if (p.act == ACT_RELU) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) t[e] = fmaxf(t[e], 0.f);
+                for (int e = 0; e < 8; ++e) t[e] = relu_f(t[e]);
             }
             const u32x4 o = u32x4{pack_bf16x2(t[0], t[1]), pack_bf16x2(t[2], t[3]), pack_bf16x2(t[4], t[5]), pack_bf16x2(t[6], t[7])};
             __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, (m0 + ml < p.M && nl < p.N) ? (unsigned)(ml * (int)p.omap.S1 + nl) * 2u : OOB, 0, 0);

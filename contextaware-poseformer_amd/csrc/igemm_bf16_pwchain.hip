@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256, 1) void igemm_bf16_pwchain_kernel(GemmArgs p3,
                 const f32x4 bv = *reinterpret_cast<const f32x4*>(&B3s[32 * j + 8 * g + 4 * fhalf]);
                 float t[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) t[e] = fmaxf((y[j][4 * g + e] + bv[e]) + rv[e], 0.f);
+                for (int e = 0; e < 4; ++e) t[e] = relu_f((y[j][4 * g + e] + bv[e]) + rv[e]);
                 pk[2 * g] = pack_bf16x2(t[0], t[1]);
                 pk[2 * g + 1] = pack_bf16x2(t[2], t[3]);
                 // (the rounded values go back to the scratch as fp32: exact, and the coalesced pass below packs them again)
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256, 1) void igemm_bf16_pwchain_kernel(GemmArgs p3,
                 const f32x4 bv = *reinterpret_cast<const f32x4*>(&B1s[32 * jn + 8 * g + 4 * fhalf]);
                 f32x4 v;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(z[jn][4 * g + e] + bv[e], 0.f);
+                for (int e = 0; e < 4; ++e) v[e] = relu_f(z[jn][4 * g + e] + bv[e]);
                 *reinterpret_cast<f32x4*>(&ep[frow * EPS + 8 * g + 4 * fhalf]) = v;
             }
             __builtin_amdgcn_wave_barrier();

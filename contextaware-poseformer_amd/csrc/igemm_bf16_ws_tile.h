@@ -20,6 +20,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "relu.h"
+
 #include <type_traits>
 
 namespace capf {
@@ -328,7 +330,7 @@ __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int
     int er, ec;
     piece_rc(er, ec);
     float* ep = reinterpret_cast<float*>(lds) + wave * (32 * EPS);
-    auto finish = [&](float t) { return p.relu ? fmaxf(t, 0.f) : t; };
+    auto finish = [&](float t) { return p.relu ? relu_f(t) : t; };
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         if constexpr (TN == 3 || F32S) { if (i == 1) prefetch_residual(1, 0, TN); }

@@ -572,7 +572,7 @@ __device__ __forceinline__ void igemm_tile(const GemmArgs& p, const int bid, con
                 for (int e = 0; e < 4; ++e) {
                     float t = (acc[i][j][4 * g + e] + bv[j][g][e]) * rs[i] + rv[i][j][g][e];
                     if (GELU) { if (p.act == ACT_GELU) t = gelu_erf(t); }
-                    if (p.act == ACT_RELU) t = fmaxf(t, 0.f);
+                    if (p.act == ACT_RELU) t = relu_f(t);
                     v[e] = t;
                 }
                 if (vec_ok) {
@@ -771,7 +771,7 @@ __global__ __launch_bounds__(256) void igemm_f32_smallc_kernel(GemmArgs p) {
                 if (n_ok && m < p.M) {
                     float v = acc[i][j][r] + bv;
                     if (p.res) v += p.res[rowmap(p.rmap, m) + n];
-                    if (p.act == ACT_RELU) v = fmaxf(v, 0.f);
+                    if (p.act == ACT_RELU) v = relu_f(v);
                     if (p.out_bf16) {
                         reinterpret_cast<unsigned short*>(p.out)[rowmap(p.omap, m) + n] = to_bf16(v);
                     } else
@@ -920,7 +920,7 @@ __global__ __launch_bounds__(256, 2) void igemm_f32_stem_stream_kernel(GemmArgs 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 x[e] += bv[e];
-                if (p.act == ACT_RELU) x[e] = fmaxf(x[e], 0.f);
+                if (p.act == ACT_RELU) x[e] = relu_f(x[e]);
             }
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), rs_out,
                                                    (m0 + ml < p.M && nl < p.N) ? (unsigned)(ml * (int)p.omap.S1 + nl) * 4u : OOB, 0, 0);

@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256, 3) void igemm_f32_pw_kernel(GemmArgs p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float t = (x[q][e] + bb[q][e]) + rr[i][h][q][e];
-                    if (p.act == ACT_RELU) t = fmaxf(t, 0.f);
+                    if (p.act == ACT_RELU) t = relu_f(t);
                     x[q][e] = t;
                 }
             if (full || (m < p.M && n < p.N)) {

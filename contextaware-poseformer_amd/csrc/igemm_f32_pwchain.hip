@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256, 1) void igemm_f32_pwchain_kernel(GemmArgs p3, 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float t = (y[j][4 * g + e] + bv[e]) + rv[e];
-                    t = fmaxf(t, 0.f);                      // (both convs end in ReLU: gemm_f32_pwchain_ok)
+                    t = relu_f(t);                      // (both convs end in ReLU: gemm_f32_pwchain_ok)
                     y[j][4 * g + e] = t;
                     v[e] = t;
                 }
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256, 1) void igemm_f32_pwchain_kernel(GemmArgs p3, 
                 const f32x4 bv = *reinterpret_cast<const f32x4*>(&B1s[32 * jn + 8 * g + 4 * fhalf]);
                 f32x4 v;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(z[jn][4 * g + e] + bv[e], 0.f);
+                for (int e = 0; e < 4; ++e) v[e] = relu_f(z[jn][4 * g + e] + bv[e]);
                 *reinterpret_cast<f32x4*>(&ep[frow * EPS + 8 * g + 4 * fhalf]) = v;
             }
             __builtin_amdgcn_wave_barrier();

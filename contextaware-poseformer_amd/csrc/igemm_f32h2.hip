@@ -351,7 +351,7 @@ __device__ __forceinline__ void igemm_h2_tile(const GemmArgs& p, const int bid, 
                     for (int e = 0; e < 4; ++e) {
                         float t = fmaf(fmaf(acc[i][j][4 * g + e], w4[g][e] * inv_s[i], b4[g][e]), rsc[i], r4[i][g][e]);
                         if (p.act == ACT_GELU) t = g2_gelu(t);
-                        if (p.act == ACT_RELU) t = fmaxf(t, 0.f);
+                        if (p.act == ACT_RELU) t = relu_f(t);
                         v[e] = t;
                     }
                     if (mk[i] && (full || n < p.N)) *reinterpret_cast<g2_f32x4*>(p.out + orow[i] + n) = v;
@@ -404,7 +404,7 @@ __device__ __forceinline__ void igemm_h2_tile(const GemmArgs& p, const int bid, 
                 for (int e = 0; e < 4; ++e) {
                     float t = fmaf(fmaf(acc[i][j][4 * g + e], wv[j][g][e] * inv_s, bv[j][g][e]), rs[i], rv[i][j][g][e]);
                     if (p.act == ACT_GELU) t = g2_gelu(t);
-                    if (p.act == ACT_RELU) t = fmaxf(t, 0.f);
+                    if (p.act == ACT_RELU) t = relu_f(t);
                     v[e] = t;
                 }
                 if (m_ok[i] && (full || n < p.N)) *reinterpret_cast<g2_f32x4*>(p.out + o_row[i] + n) = v;

@@ -603,7 +603,7 @@ __device__ __forceinline__ void igemm_f32h2_ws_tile(const H2Problem& q, const in
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float t = POUT ? fmaf(x[e], wv[q][e], bv[q][e]) : fmaf(x[e], wv[q][e], bv[q][e] + rr[i][j][h * 2 + q][e]);
-                        o[e] = p.relu ? fmaxf(t, 0.f) : t;
+                        o[e] = p.relu ? relu_f(t) : t;
                     }
                     if constexpr (POUT) ov[q] = o;
                     else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ws_u32x4, o), rs_out, row_off(pl, j, q, p.ldy), 0, 0);

@@ -328,7 +328,7 @@ __device__ __forceinline__ void igemm_f32x3_ws_tiles(const X3Problem& q, const i
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float t = acc[i][j][4 * g + e] + rr[i][j][g][e];
-                        o[e] = p.relu ? fmaxf(t, 0.f) : t;
+                        o[e] = p.relu ? relu_f(t) : t;
                     }
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ws_u32x4, o), rs_out, piece_off(i, j, g, p.ldy), 0, 0);
                 }

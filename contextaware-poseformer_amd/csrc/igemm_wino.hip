@@ -331,7 +331,7 @@ __device__ __forceinline__ void wino_tile(const GemmArgs& p, const int bid, floa
             const float a0 = acc[0][4 * g + e], a1 = acc[1][4 * g + e], a2 = acc[2][4 * g + e], a3 = acc[3][4 * g + e];
             float s0 = ((a0 + a1) + a2) + bv[g][e] + r0[g][e];
             float s1 = ((a1 - a2) - a3) + bv[g][e] + r1[g][e];
-            if (p.act == ACT_RELU) { s0 = fmaxf(s0, 0.f); s1 = fmaxf(s1, 0.f); }
+            if (p.act == ACT_RELU) { s0 = relu_f(s0); s1 = relu_f(s1); }
             y0[e] = s0; y1[e] = s1;
         }
         if (t_ok && n < p.N) {
@@ -579,7 +579,7 @@ __device__ __forceinline__ void wino_tile_h(const GemmArgs& p, const int bid, fl
             // fixed order whichever wave finishes the group: (pair 0 partial) + (pair 1 partial)
             float s0 = (pp == 0 ? m_s0 + o0[e] : o0[e] + m_s0) + bv[k][e] + r0[k][e];
             float s1 = (pp == 0 ? m_s1 + o1[e] : o1[e] + m_s1) + bv[k][e] + r1[k][e];
-            if (p.act == ACT_RELU) { s0 = fmaxf(s0, 0.f); s1 = fmaxf(s1, 0.f); }
+            if (p.act == ACT_RELU) { s0 = relu_f(s0); s1 = relu_f(s1); }
             y0[e] = s0; y1[e] = s1;
         }
         if (t_ok && n < p.N) {
@@ -866,7 +866,7 @@ __device__ __forceinline__ void wino43_tile(const GemmArgs& p, const int bid, fl
                 const float mine = partial(g, o, e);
                 // fixed order whichever wave finishes the group: (triple 0 partial) + (triple 1 partial)
                 float sv = (pp == 0 ? mine + other[e] : other[e] + mine) + bv[k][e] + rr[k][o][e];
-                if (p.act == ACT_RELU) sv = fmaxf(sv, 0.f);
+                if (p.act == ACT_RELU) sv = relu_f(sv);
                 y[e] = sv;
             }
             if (t_ok && n < p.N) *reinterpret_cast<f32x4*>(p.out + o_row + (long)o * p.omap.S1 + n) = y;
@@ -1200,7 +1200,7 @@ __device__ __forceinline__ void wino43s_tile(const GemmArgs& p, const int bid, f
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             y[e] += rr[i][e];
-            if (p.act == ACT_RELU) y[e] = fmaxf(y[e], 0.f);
+            if (p.act == ACT_RELU) y[e] = relu_f(y[e]);
         }
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, piece_off(i, p.omap.S1), 0, 0);
     }

@@ -5,6 +5,9 @@
 
 #include <stdlib.h>
 
+#include "relu.h"
+#include "capf.h"      // capf_optim_report: the record the guarded AdamW kernel writes is the public one
+
 namespace capf {
 
 // A/B and tuning switches read the environment ONLY in the diagnostic build (make DIAG=1 -> tools/ab/libcapf_diag.so,
@@ -581,6 +584,29 @@ hipError_t launch_mpjpe_nd(const float* pred, const float* gt, int rows, int D, 
                            hipStream_t s);
 hipError_t launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                         float wd, int step, hipStream_t s, float gscale = 1.0f);
+// guarded AdamW (train.py:194-201, run_3dhp.py:260-277): launch_grad_sumsq leaves OPTIM_PARTIALS block sums of (gscale * g[i])^2 (fp64) and
+// non-finite flags in the control block; launch_adamw_guarded adds them in a fixed order in every block, clips by the global norm, skips
+// the whole update when the gradient is not finite, and otherwise runs launch_adamw's arithmetic with lr / weight decay per segment and
+// the bias corrections of the DEVICE's step count (slot[attempt & 1] is written, slot[~attempt & 1] read: no word is read and written
+// within one launch).  The report comes first so that a caller copies sizeof(capf_optim_report) bytes from the block's start.
+constexpr int OPTIM_PARTIALS = 512;          // fixed: the grid of launch_grad_sumsq, whatever the device
+constexpr int ADAMW_MAX_SEGMENTS = 64;
+struct OptimCtrl {
+    capf_optim_report report;
+    capf_optim_report slot[2];
+    double partial[OPTIM_PARTIALS];
+    unsigned nonfinite[OPTIM_PARTIALS];
+};
+struct AdamwSegments {                       // sorted, disjoint, covering [0, n): segment k is [end[k - 1], end[k]) (end[-1] = 0)
+    long end[ADAMW_MAX_SEGMENTS];
+    float lr[ADAMW_MAX_SEGMENTS], wd[ADAMW_MAX_SEGMENTS];
+    int count;
+};
+hipError_t launch_optim_ctrl_init(OptimCtrl* ctrl, long long steps_taken, hipStream_t s);
+hipError_t launch_grad_sumsq(const float* g, long n, float gscale, OptimCtrl* ctrl, hipStream_t s);
+hipError_t launch_adamw_guarded(float* p, const float* g, float* m, float* v, long n, const AdamwSegments& segs, float b1, float b2,
+                                float eps, float gscale, float max_norm, long long attempt, const float* loss, int rows,
+                                OptimCtrl* ctrl, hipStream_t s);
 // dst[r, :] = src[smap(r), :] * scale[r / div]   (DropPath mask on a gradient), width C
 hipError_t launch_scale_rows(const float* src, RowMap smap, const float* scale, int div, float* dst, int rows, int C,
                              hipStream_t s);

@@ -992,6 +992,224 @@ hipError_t launch_adamw(float* p, const float* g, float* m, float* v, long n, fl
     return hipGetLastError();
 }
 
+// ---- guarded AdamW: global-norm clipping, non-finite skip, lr groups (train.py:194-201, run_3dhp.py:260-277) -------------------
+// Two launches over the flat buffer.  grad_sumsq_kernel leaves OPTIM_PARTIALS per-block sums of (gscale * g[i])^2 and per-block
+// non-finite flags in the control block; every block of adamw_guarded_kernel adds those partials in one fixed order (all blocks hold the
+// same bits), derives the clip coefficient and the skip decision from them and either returns or updates its elements.  No atomics, no
+// host read.  Both kernels walk the buffer in float4 units q (elements 4q .. 4q + 3) and then a scalar tail of n % 4 elements; which
+// thread adds which element in which order depends on n alone (an unaligned pointer changes the load instruction, not the order).
+
+__device__ __forceinline__ f32x4 ld4(const float* __restrict__ a, long q, bool vec) {
+    if (vec) return *reinterpret_cast<const f32x4*>(a + 4 * q);
+    f32x4 r = {a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]};
+    return r;
+}
+
+__device__ __forceinline__ void st4(float* __restrict__ a, long q, bool vec, f32x4 r) {
+    if (vec) {
+        *reinterpret_cast<f32x4*>(a + 4 * q) = r;
+    } else {
+        a[4 * q] = r.x; a[4 * q + 1] = r.y; a[4 * q + 2] = r.z; a[4 * q + 3] = r.w;
+    }
+}
+
+__device__ __forceinline__ void sumsq_add(float g, float gscale, double& acc, unsigned& bad) {
+    const float x = g * gscale;
+    bad |= !__builtin_isfinite(x);
+    const double d = (double)x;
+    acc += d * d;
+}
+
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ g, long n, float gscale, bool vec,
+                                                         OptimCtrl* __restrict__ ctrl) {
+    __shared__ double red[256];
+    __shared__ unsigned red_bad[256];
+    const long T = (long)OPTIM_PARTIALS * 256, gid = blockIdx.x * 256L + threadIdx.x, nvec = n >> 2;
+    double acc = 0.0;
+    unsigned bad = 0;
+    for (long q = gid; q < nvec; q += 4 * T) {        // four independent 16-byte loads in flight per lane, added in the order of q
+        f32x4 x[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (q + u * T < nvec) x[u] = ld4(g, q + u * T, vec);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (q + u * T < nvec) {
+                sumsq_add(x[u].x, gscale, acc, bad);
+                sumsq_add(x[u].y, gscale, acc, bad);
+                sumsq_add(x[u].z, gscale, acc, bad);
+                sumsq_add(x[u].w, gscale, acc, bad);
+            }
+    }
+    if (gid < n - 4 * nvec) sumsq_add(g[4 * nvec + gid], gscale, acc, bad);      // the tail: threads 0 .. n % 4 - 1 of block 0
+    red[threadIdx.x] = acc;
+    red_bad[threadIdx.x] = bad;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[threadIdx.x] += red[threadIdx.x + o];
+            red_bad[threadIdx.x] |= red_bad[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        ctrl->partial[blockIdx.x] = red[0];
+        ctrl->nonfinite[blockIdx.x] = red_bad[0];
+    }
+}
+
+hipError_t launch_grad_sumsq(const float* g, long n, float gscale, OptimCtrl* ctrl, hipStream_t s) {
+    const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+    // a FIXED grid (not the device's CU count): the same buffer gives the same partials, hence the same decision, on every box and rank
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(OPTIM_PARTIALS), dim3(256), 0, s, g, n, gscale, vec, ctrl);
+    return hipGetLastError();
+}
+
+__global__ void optim_ctrl_init_kernel(OptimCtrl* ctrl, long long steps_taken) {
+    for (int i = threadIdx.x; i < OPTIM_PARTIALS; i += blockDim.x) {
+        ctrl->partial[i] = 0.0;
+        ctrl->nonfinite[i] = 0u;
+    }
+    if (threadIdx.x == 0) {
+        capf_optim_report r = {};
+        r.steps_taken = steps_taken;
+        r.clip_coef = 1.0;
+        ctrl->report = r;
+        ctrl->slot[0] = r;
+        ctrl->slot[1] = r;
+    }
+}
+
+hipError_t launch_optim_ctrl_init(OptimCtrl* ctrl, long long steps_taken, hipStream_t s) {
+    hipLaunchKernelGGL(optim_ctrl_init_kernel, dim3(1), dim3(256), 0, s, ctrl, steps_taken);
+    return hipGetLastError();
+}
+
+// 1 - beta^t in fp64 (t >= 1) by repeated squaring: what torch.optim.AdamW computes on the host from its own step count
+__device__ __forceinline__ double one_minus_pow(float beta, long long t) {
+    double r = 1.0, b = (double)beta;
+    for (; t > 0; t >>= 1, b *= b)
+        if (t & 1) r *= b;
+    return 1.0 - r;
+}
+
+__global__ void __launch_bounds__(256) adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, long n, AdamwSegments segs, float b1, float b2,
+                                                            float eps, float gscale, float max_norm, int parity,
+                                                            const float* __restrict__ loss, int rows, bool vec,
+                                                            OptimCtrl* __restrict__ ctrl) {
+    __shared__ long s_end[ADAMW_MAX_SEGMENTS];
+    __shared__ float s_lr[ADAMW_MAX_SEGMENTS], s_wd[ADAMW_MAX_SEGMENTS];
+    if ((int)threadIdx.x < segs.count) {
+        s_end[threadIdx.x] = segs.end[threadIdx.x];
+        s_lr[threadIdx.x] = segs.lr[threadIdx.x];
+        s_wd[threadIdx.x] = segs.wd[threadIdx.x];
+    }
+    // every wave of every block: lane l adds partials l, l + 64, ... in index order, then a 64-lane butterfly.  a + b == b + a bit for
+    // bit, so all lanes -- and all blocks -- end with the same fp64 sum
+    const int lane = threadIdx.x & 63;
+    double ss = 0.0;
+    unsigned bad = 0;
+#pragma unroll
+    for (int i = 0; i < OPTIM_PARTIALS / 64; ++i) {
+        ss += ctrl->partial[lane + 64 * i];
+        bad |= ctrl->nonfinite[lane + 64 * i];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    const bool nonfinite = __ballot(bad != 0) != 0;
+    const double norm = sqrt(ss);
+    const bool skip = nonfinite || !__builtin_isfinite(norm);
+    // clip_grad_norm_'s rule (train.py:196-200) in fp64; ONE fp32 factor on top of grad_scale
+    double coef = 1.0;
+    if (max_norm > 0.f && !skip) coef = fmin(1.0, (double)max_norm / (norm + 1e-6));
+    const float cf = (float)coef;
+    // the state the PREVIOUS attempt left: this launch reads slot[parity ^ 1] and (block 0 alone) writes slot[parity] and the report
+    const long long taken = ctrl->slot[parity ^ 1].steps_taken;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        capf_optim_report r = ctrl->slot[parity ^ 1];
+        r.steps_taken += skip ? 0 : 1;
+        r.steps_skipped += skip ? 1 : 0;
+        r.grad_sumsq = ss;
+        r.grad_norm = norm;
+        r.clip_coef = coef;
+        r.grad_nonfinite = nonfinite ? 1 : 0;
+        if (loss) {
+            const float l = loss[0];
+            if (__builtin_isfinite(l)) {
+                r.loss_sum += (double)l * (double)rows;
+                r.loss_rows += (double)rows;
+            } else {
+                r.nonfinite_losses += 1;
+            }
+        }
+        ctrl->slot[parity] = r;
+        ctrl->report = r;
+    }
+    if (skip) return;              // p, m and v keep their bits; the step count does not advance
+    const long long t = taken + 1;
+    const float bc1 = (float)one_minus_pow(b1, t), bc2_sqrt = (float)sqrt(one_minus_pow(b2, t));
+    __syncthreads();
+    const int last = segs.count - 1;
+    int k = 0;
+    long cur_end = s_end[0];
+    float lr = s_lr[0], wd = s_wd[0];
+    auto seek = [&](long i) {      // the segment of element i (i only grows within a thread); empty segments are stepped over
+        while (i >= cur_end && k < last) {
+            ++k;
+            cur_end = s_end[k];
+            lr = s_lr[k];
+            wd = s_wd[k];
+        }
+    };
+    auto update = [&](float& pi, float graw, float& mi, float& vi) {       // adamw_kernel's arithmetic
+        const float gi = graw * gscale * cf;
+        pi = pi * (1.0f - lr * wd);
+        mi = b1 * mi + (1.0f - b1) * gi;
+        vi = b2 * vi + (1.0f - b2) * gi * gi;
+        pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
+    };
+    const long T = (long)gridDim.x * 256, gid = blockIdx.x * 256L + threadIdx.x, nvec = n >> 2;
+    for (long q = gid; q < nvec; q += T) {
+        const f32x4 Pq = ld4(p, q, vec), Gq = ld4(g, q, vec), Mq = ld4(m, q, vec), Vq = ld4(v, q, vec);
+        float P[4] = {Pq.x, Pq.y, Pq.z, Pq.w}, M[4] = {Mq.x, Mq.y, Mq.z, Mq.w}, V[4] = {Vq.x, Vq.y, Vq.z, Vq.w};
+        const float G[4] = {Gq.x, Gq.y, Gq.z, Gq.w};
+        seek(4 * q);
+        if (4 * q + 4 <= cur_end) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) update(P[e], G[e], M[e], V[e]);
+        } else {                   // a segment boundary inside the four elements
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                seek(4 * q + e);
+                update(P[e], G[e], M[e], V[e]);
+            }
+        }
+        st4(m, q, vec, f32x4{M[0], M[1], M[2], M[3]});
+        st4(v, q, vec, f32x4{V[0], V[1], V[2], V[3]});
+        st4(p, q, vec, f32x4{P[0], P[1], P[2], P[3]});
+    }
+    if (gid < n - 4 * nvec) {      // the tail lies behind every float4 unit, so seeking forward from any earlier position is right
+        const long i = 4 * nvec + gid;
+        seek(i);
+        float pi = p[i], mi = m[i], vi = v[i];
+        update(pi, g[i], mi, vi);
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pi;
+    }
+}
+
+hipError_t launch_adamw_guarded(float* p, const float* g, float* m, float* v, long n, const AdamwSegments& segs, float b1, float b2,
+                                float eps, float gscale, float max_norm, long long attempt, const float* loss, int rows,
+                                OptimCtrl* ctrl, hipStream_t s) {
+    const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                       reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    hipLaunchKernelGGL(adamw_guarded_kernel, dim3(grid_1d((n + 3) / 4, 2048)), dim3(256), 0, s, p, g, m, v, n, segs, b1, b2, eps,
+                       gscale, max_norm, (int)(attempt & 1), loss, rows, vec, ctrl);
+    return hipGetLastError();
+}
+
 // dst[r, :] = src[smap(r), :] * scale[r / div]
 __global__ void scale_rows_kernel(const float* __restrict__ src, RowMap smap, const float* __restrict__ scale, int div,
                                   float* __restrict__ dst, int rows, int C) {

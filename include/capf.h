@@ -139,8 +139,10 @@ const char* capf_version(void);
  * capf_jpeg_decode_batch, capf_jpeg_coefficients_subseq); struct layouts unchanged.  Revision 9 (additive): training plans of the variant
  * without context blocks at any depth 1..8 (its two widths) (its DropPath layout at capf_forward_train), capf_fliptest_fuse_swap, capf_pck_counts; struct
  * layouts unchanged.  Revision 10 (additive): the crop-aware JPEG route (capf_jpeg_crop_rect, capf_jpeg_crop_batch_info,
- * capf_jpeg_decode_crop_batch); struct layouts unchanged.                                                                                  */
-#define CAPF_ABI_VERSION 10
+ * capf_jpeg_decode_crop_batch); struct layouts unchanged.  Revision 11 (additive): the guarded AdamW step (capf_optim_ctrl_bytes,
+ * capf_optim_ctrl_init, capf_grad_sumsq, capf_adamw_step_guarded; new structs capf_optim_report, capf_optim_segment); existing struct
+ * layouts unchanged.                                                                                                                       */
+#define CAPF_ABI_VERSION 11
 int capf_abi_version(void);
 
 /* ---- parameter schema == the reference's state_dict ------------- */
@@ -221,6 +223,58 @@ int capf_mpjpe_nd(void* stream, const float* pred, const float* gt, int rows, in
 int capf_adamw_step(void* stream, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
                     int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                     float grad_scale);
+
+/* ---- guarded AdamW step: global-norm clipping, non-finite skip, lr groups, device-side step count ---------------------------------
+ * Replaces the optimizer end of one_epoch_full (train.py:187-206) on the flat gradient of capf_backward, after the all-reduce:
+ *     if not torch.isnan(loss):                                   train.py:194
+ *         clip_grad_norm_(params, grad_clip / volume_net_lr)      train.py:196-200
+ *         optimizer.step()                                        train.py:201, AdamW with per-group lr: run_3dhp.py:260-277
+ *     epoch_loss_3d += rows * loss.item(); N += rows              train.py:191-192
+ * without a host read: two launches over the buffer, decisions taken on the device from a caller-owned control block.
+ * THE GUARD LOOKS AT THE GRADIENT, NOT AT THE LOSS.  A NaN loss means NaN in pred, hence in dpred, hence in the head's gradients, so the
+ * gradient test subsumes train.py:194; after the all-reduce the flat gradient is bit-identical on every rank, so every rank takes the
+ * same decision with no extra collective (the reference's rank-local test lets DDP ranks diverge); and it also catches the NaN / Inf
+ * gradient under a finite loss, which the reference would clip into NaN parameters.
+ * What the guard cannot see is a NaN that never reaches the gradient.  The ReLU of every conv / GEMM epilogue hands a NaN on (relu_f), so
+ * a NaN pixel reaches the loss through the HRNet backbones; the CPN-50 backbone's max pool (elementwise.hip) and the block maximum that
+ * scales the planes-out tile of igemm_f32h2_ws still take fmaxf, which returns the other operand for a NaN: behind those two a poisoned
+ * pixel can be swallowed in front of the lifter, the loss stays finite and the step is taken, as it was before revision 11.
+ * Everything below enqueues on `stream`, allocates nothing and never synchronises. */
+typedef struct capf_optim_report {   /* the first sizeof(capf_optim_report) bytes of the control block: copy them back whenever you like */
+    int64_t steps_taken;             /* updates applied: AdamW's `step` (bias correction is computed from this count, on the device) */
+    int64_t steps_skipped;           /* attempts whose gradient was not finite: parameters and both moments left untouched */
+    int64_t nonfinite_losses;        /* attempts whose `loss` was NaN / Inf (counted, kept out of loss_sum) */
+    int64_t grad_nonfinite;          /* last attempt: 1 when an element of grad_scale * g was NaN / Inf */
+    double grad_sumsq;               /* last attempt: sum of (grad_scale * g[i])^2, fp64 */
+    double grad_norm;                /* last attempt: sqrt(grad_sumsq) */
+    double clip_coef;                /* last attempt: min(1, max_norm / (grad_norm + 1e-6)); 1 without clipping */
+    double loss_sum, loss_rows;      /* sums over attempts with a finite loss: loss * rows, rows (epoch_loss_3d, N of train.py:191-192) */
+} capf_optim_report;
+/* one AdamW parameter group's stretch of the flat buffer (run_3dhp.py:260-277: sampling_offsets at 0.1 x lr) */
+typedef struct capf_optim_segment {
+    int64_t begin, end;              /* elements [begin, end); any offsets, begin == end allowed */
+    float lr, weight_decay;
+} capf_optim_segment;
+#define CAPF_OPTIM_MAX_SEGMENTS 64
+/* bytes of the control block (device memory, 8-byte aligned, caller-owned) */
+size_t capf_optim_ctrl_bytes(void);
+/* zero the block and set the step count (0 for a new run; the `step` of a loaded optimizer.state_dict(), train.py:398-407) */
+int capf_optim_ctrl_init(void* stream, void* ctrl, int64_t steps_taken);
+/* first launch: per-block fp64 sums of (grad_scale * g[i])^2 and non-finite flags into the control block.  The grid is fixed (not
+ * sized by the device), every reduction has a fixed order: the same buffer gives the same bits on every box, rank and run. */
+int capf_grad_sumsq(void* stream, const float* grads, int64_t n, float grad_scale, void* ctrl);
+/* second launch, after capf_grad_sumsq of the same grads / n / grad_scale: every block adds the partial sums in the same order,
+ *     norm = sqrt(sum), coef = min(1, max_norm / (norm + 1e-6)) in fp64 (max_norm <= 0: no clipping),
+ *     skip = a non-finite element was seen or norm is not finite;
+ * skip: params, exp_avg, exp_avg_sq are not written and steps_taken stays; otherwise capf_adamw_step's arithmetic on
+ * (g * grad_scale) * (float)coef with the lr / weight_decay of the element's segment and step = steps_taken + 1.
+ * segments: 1 .. CAPF_OPTIM_MAX_SEGMENTS (more: CAPF_ERR_UNSUPPORTED) sorted, disjoint, covering [0, n) (else CAPF_ERR_INVALID); copied
+ * by value.  attempt: the caller's count of calls on this control block, 1, 2, ... (its parity picks the state slot that is written,
+ * the other one is read).  loss (device, may be NULL) and rows feed loss_sum / loss_rows / nonfinite_losses whether or not the step
+ * is skipped. */
+int capf_adamw_step_guarded(void* stream, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                            const capf_optim_segment* segments, int n_segments, float beta1, float beta2, float eps,
+                            float grad_scale, float max_norm, int64_t attempt, const float* loss, int rows, void* ctrl);
 
 /* Lifter only, on the context maps left in the workspace by the last capf_backbone_forward /
  * capf_forward of the same batch.  Replaces self.volume_net(...) conpose.py:40
