@@ -7,10 +7,10 @@ from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, 
 # CAPF_LIB: an alternative build of the same ABI (A/B timing of kernel variants on one GPU box; tools only)
 LIB_PATH = os.environ.get("CAPF_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libcapf.so")
 HRNET, CPN50 = 0, 1
-F32, BF16 = 0, 1
+F32, BF16, F16 = 0, 1, 2      # capf_dtype
 PLAN_NO_FUSED_LIFTER, PLAN_NO_WINOGRAD, PLAN_NO_ROW_HALO, PLAN_WINOGRAD_F23_ONLY, PLAN_NO_PWCHAIN, PLAN_NO_WS, PLAN_LIFTER_FP32, PLAN_NO_F32X3, PLAN_F32X3_EXACT, PLAN_NO_F32H2_GEMM, PLAN_NO_UPADD, PLAN_H2_PLANES, PLAN_NO_BNECK, PLAN_NO_BATCHED_REDUCE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192     # capf_plan_flag
 PLAN_BF16_F32_STREAM = 32768     # (1 << 14 stays unassigned)
-ABI_VERSION = 11       # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
+ABI_VERSION = 12       # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
 
 EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.py)
     "capf_create", "capf_destroy", "capf_last_error", "capf_version", "capf_num_params", "capf_param_info",
@@ -31,11 +31,27 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_op_f32h2_gemm_pack_elems", "capf_op_pack_f32h2_gemm", "capf_op_conv_f32h2g", "capf_op_conv_f32h2g_group", "capf_op_linear_f32h2g", "capf_op_linear_ln_f32h2g", "capf_op_wgrad", "capf_op_conv_f32h2_tiles", "capf_op_conv_f32h2_planes", "capf_op_h2_planes",
     "capf_fliptest_fuse_swap", "capf_pck_counts",
     "capf_optim_ctrl_bytes", "capf_optim_ctrl_init", "capf_grad_sumsq", "capf_adamw_step_guarded",
+    "capf_op_pack_conv_16", "capf_op_conv_16", "capf_op_conv_16_group", "capf_op_conv_16_ws_group", "capf_op_linear_16", "capf_op_bneck_16",
+    "capf_debug_f16_round",
 ]
 
 
 class CapfError(RuntimeError):
     pass
+
+
+def _bf16():
+    import torch
+    return torch.bfloat16
+
+
+def _f16():
+    import torch
+    return torch.float16
+
+
+_TORCH16 = {2: _bf16, 3: _f16}          # capf_tensor / capf_op_desc dtype code -> torch dtype of a 16-bit tensor
+_TORCH16_OF = {BF16: _bf16, F16: _f16}  # capf_dtype -> the same
 
 
 class CapfConfig(ctypes.Structure):
@@ -188,6 +204,13 @@ def load_library():
         getattr(lib, name).argtypes = [P, c_int, D]
     lib.capf_op_conv_wino_group.argtypes = [P, c_int, D, c_int]
     lib.capf_op_conv_bf16_group.argtypes = [P, c_int, D, POINTER(c_void_p), POINTER(c_int32)]
+    lib.capf_op_pack_conv_16.argtypes = [P, P, P, P, P, P, c_float, P, P] + [c_int] * 5
+    lib.capf_op_conv_16.argtypes = [P, P, P, P, P, P] + [c_int] * 9
+    lib.capf_op_conv_16_group.argtypes = [P, c_int, D, POINTER(c_void_p), POINTER(c_int32), c_int]
+    lib.capf_op_conv_16_ws_group.argtypes = [P, c_int, D, c_int]
+    lib.capf_op_linear_16.argtypes = [P, P, P, P, P, P] + [c_int] * 5
+    lib.capf_op_bneck_16.argtypes = [P, P, POINTER(c_void_p), POINTER(c_void_p), P, P, P, P] + [c_int] * 5
+    lib.capf_debug_f16_round.argtypes = [P, P, c_int]
     lib.capf_op_conv_f32h2_planes.argtypes = [P, D, P, P]
     lib.capf_op_conv_f32h2_tiles.argtypes = [c_int, c_int, c_int, POINTER(c_int)]
     lib.capf_pose_errors.argtypes = [P, P, P, c_int, c_int, P, P]
@@ -352,8 +375,8 @@ class Engine:
         for s in shp:
             n *= s
         off = (ptr.value - self._ws.data_ptr()) // 4
-        if rc == 2:       # bf16 tensor: two elements per float slot
-            return self._ws[off:off + (n + 1) // 2].view(torch.bfloat16)[:n].view(*shp).clone()
+        if rc in (2, 3):  # bf16 / fp16 tensor: two elements per float slot
+            return self._ws[off:off + (n + 1) // 2].view(_TORCH16[rc]())[:n].view(*shp).clone()
         flat = self._ws[off:off + n]
         if rc == 1:
             flat = flat.view(torch.int32)
@@ -400,7 +423,7 @@ class Engine:
 
     def op_tensor(self, index, slot, shape, dtype_code):
         """View (no copy) of one operand of op `index` after a forward_prefix: slot 0..3 inputs, 4 residual, 5 output, 6 the output's bf16
-        shadow (PLAN_BF16_F32_STREAM); shape = full [B, ...] shape, dtype_code 0 fp32 / 2 bf16."""
+        shadow (PLAN_BF16_F32_STREAM); shape = full [B, ...] shape, dtype_code 0 fp32 / 2 bf16 / 3 fp16."""
         import torch
         ptr = c_void_p()
         self._check(self.lib.capf_op_tensor(self.h, index, slot, byref(ptr)), f"op_tensor({index}, {slot})")
@@ -411,8 +434,8 @@ class Engine:
         if img is not None and ptr.value == img.data_ptr():
             return img.view(*shape)
         off = (ptr.value - self._ws.data_ptr()) // 4
-        if dtype_code == 2:
-            return self._ws[off:off + (n + 1) // 2].view(torch.bfloat16)[:n].view(*shape)
+        if dtype_code in (2, 3):
+            return self._ws[off:off + (n + 1) // 2].view(_TORCH16[dtype_code]())[:n].view(*shape)
         return self._ws[off:off + n].view(*shape)
 
     def op_h2_planes(self, index, batch):
@@ -512,20 +535,20 @@ def _out_hw(H, W, ks, stride):
     return (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
 
 
-def _conv_out(d, x, wp, bias, residual, cout, ks=3, stride=1, act=0, bf16=False):
-    """Allocate the output [B, Ho, Wo, cout] (fp32, or bf16) of a conv of NHWC x and describe the conv in the ConvDesc d; -> output."""
+def _conv_out(d, x, wp, bias, residual, cout, ks=3, stride=1, act=0, bf16=False, dtype=None):
+    """Allocate the output [B, Ho, Wo, cout] (fp32, or bf16, or `dtype`) of a conv of NHWC x and describe the conv in the ConvDesc d; -> output."""
     import torch
     B, H, W, ci = x.shape
-    y = torch.empty(B, *_out_hw(H, W, ks, stride), cout, device=x.device, dtype=torch.bfloat16 if bf16 else torch.float32)
+    y = torch.empty(B, *_out_hw(H, W, ks, stride), cout, device=x.device, dtype=dtype or (torch.bfloat16 if bf16 else torch.float32))
     d.x, d.w_packed, d.bias, d.residual, d.y = (t.data_ptr() if t is not None else None for t in (x, wp, bias, residual, y))
     d.B, d.H, d.W, d.Cin, d.Cout, d.ks, d.stride, d.act = B, H, W, ci, cout, ks, stride, act
     return y
 
 
-def _conv_descs(problems, bf16=False):
+def _conv_descs(problems, bf16=False, dtype=None):
     """problems: (x, wp, bias, residual, cout, ks, stride, act) each -> (ConvDesc array, outputs)"""
     descs = (ConvDesc * len(problems))()
-    return descs, [_conv_out(d, *p, bf16=bf16) for d, p in zip(descs, problems)]
+    return descs, [_conv_out(d, *p, bf16=bf16, dtype=dtype) for d, p in zip(descs, problems)]
 
 
 def _pack(entry, w, bn, eps, wp_shape, wp_dtype, *dims, bias="empty"):
@@ -774,6 +797,81 @@ def conv_nhwc_bf16_group(problems):
     variant = c_int32(-1)
     _call("capf_op_conv_bf16_group", _stream(problems[0][0]), len(problems), descs, rh, byref(variant))
     return outs, variant.value
+
+
+# ---- the 16-bit kernel families for either element format: dtype = BF16 (the *_bf16 functions above, bit for bit) or F16 ----------
+def pack_conv_16(w, bn=None, eps=1e-5, layout=0, dtype=F16):
+    """BatchNorm fold + pack of w [Cout,Cin,k,k] in the 16-bit format `dtype`; layout 0: [Cout, Kpad64] (pack_conv_bf16), 1: row-halo
+    [Cout, 9 * Cin] (pack_conv_bf16_rh), 2: the 2-D halo tile's [elems] (pack_conv_bf16_ws) -> (packed weights, fp32 bias [Cout])."""
+    co, ci, ks, _ = w.shape
+    if layout == 0:
+        shape = (co, (ks * ks * ci + 63) // 64 * 64)
+    elif layout == 1:
+        shape = (co, 9 * ci)
+    else:
+        shape = load_library().capf_op_conv_bf16_ws_pack_elems(co, ci)
+        if shape <= 0:
+            raise CapfError(f"2-D halo conv needs Cin % 16 == 0 (got Cin={ci})")
+    return _pack("capf_op_pack_conv_16", w, bn, eps, shape, _TORCH16_OF[dtype](), co, ci, ks, layout, dtype)
+
+
+def conv_nhwc_16(x, wp, bias, ks, stride=1, act=0, residual=None, dtype=F16):
+    """x [B,H,W,Cin] cuda NHWC in the 16-bit format `dtype` -> [B,Ho,Wo,Cout] in the same (conv_nhwc_bf16).  Cin % 8 != 0: the stem of a
+    16-bit plan -- x is the fp32 image, wp / bias the fp32 pack of pack_conv, no residual; the result is 16-bit."""
+    d = ConvDesc()
+    y = _conv_out(d, x, wp, bias, residual, wp.shape[0], ks, stride, act, dtype=_TORCH16_OF[dtype]())
+    _call("capf_op_conv_16", _stream(x), d.x, d.w_packed, d.bias, d.residual, d.y, d.B, d.H, d.W, d.Cin, d.Cout, ks, stride, act, dtype)
+    return y
+
+
+def conv_nhwc_16_group(problems, dtype=F16):
+    """conv_nhwc_bf16_group for either format: (x, wp, bias, ks, stride, act, residual, wp_row_halo or None) each -> (outputs, variant)."""
+    descs, outs = _conv_descs([(x, wp, bias, res, wp.shape[0], ks, stride, act) for x, wp, bias, ks, stride, act, res, _ in problems],
+                              dtype=_TORCH16_OF[dtype]())
+    rh = (c_void_p * len(problems))(*[(p[7].data_ptr() if p[7] is not None else None) for p in problems])
+    variant = c_int32(-1)
+    _call("capf_op_conv_16_group", _stream(problems[0][0]), len(problems), descs, rh, byref(variant), dtype)
+    return outs, variant.value
+
+
+def conv_nhwc_16_ws_group(problems, dtype=F16):
+    """conv_nhwc_bf16_ws_group for either format: (x, wp_ws, bias, act, residual, Cout) each -> outputs (one launch of the 2-D halo tile)."""
+    descs, outs = _conv_descs([(x, wp, bias, res, co, 3, 1, act) for x, wp, bias, act, res, co in problems], dtype=_TORCH16_OF[dtype]())
+    _call("capf_op_conv_16_ws_group", _stream(problems[0][0]), len(problems), descs, dtype)
+    return outs
+
+
+def linear_16(x, w, bias=None, residual=None, gelu=False, dtype=F16):
+    """linear_bf16 for either format: x [M,K], w [N,K] 16-bit -> fp32 [M,N] (+ fp32 residual), or gelu=True -> 16-bit GELU(x w^T + b)."""
+    M, K = x.shape
+    N = w.shape[0]
+    y = _rows_out(x, N, _TORCH16_OF[dtype]() if gelu else None)
+    _call("capf_op_linear_16", _stream(x), _p(x.contiguous()), _p(w.contiguous()), _p(bias), _p(residual), _p(y), M, N, K, 1 if gelu else 0, dtype)
+    return y
+
+
+def bneck_16(x, packs, tap=False, dtype=F16):
+    """A layer1 bottleneck as ONE kernel (csrc/bneck_bf16.hip).  x [B,H,W,64] with packs = [(wp, bias)] * 4 for conv1, conv2, conv3 and the
+    downsample conv (the first bottleneck), or x [B,H,W,256] with three packs (an identity bottleneck); weights from pack_conv_16 layout 0.
+    -> (y [B,H,W,256], t1, t2, shortcut or None): t1 / t2 / shortcut hold conv1's, conv2's and the downsample's outputs only with tap."""
+    import torch
+    B, H, W, _ = x.shape
+    first = len(packs) == 4
+    new = lambda c: torch.empty(B, H, W, c, device=x.device, dtype=x.dtype)
+    t1, t2, y, sc = new(64), new(64), new(256), (new(256) if first else None)
+    w = (c_void_p * 4)(*[packs[i][0].data_ptr() if i < len(packs) else None for i in range(4)])
+    b = (c_void_p * 4)(*[packs[i][1].data_ptr() if i < len(packs) else None for i in range(4)])
+    _call("capf_op_bneck_16", _stream(x), _p(x), w, b, _p(t1), _p(t2), _p(sc), _p(y), B, H, W, 1 if tap else 0, dtype)
+    return y, t1, t2, sc
+
+
+def f16_round_host(values):
+    """The library's float -> fp16 store rule on the host (capf_debug_f16_round): fp32 numpy array -> uint16 bit patterns."""
+    import numpy as np
+    v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    out = np.empty(v.size, dtype=np.uint16)
+    _call("capf_debug_f16_round", v.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p), int(v.size))
+    return out.reshape(np.shape(values))
 
 
 def linear(x, w, bias=None, act=0, residual=None):

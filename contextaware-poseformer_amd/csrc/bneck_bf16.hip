@@ -35,7 +35,6 @@ typedef float bn_f32x4 __attribute__((ext_vector_type(4)));
 typedef float bn_f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned bn_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned bn_u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bn_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __amdgpu_buffer_rsrc_t bn_rsrc_t;
 
 [[maybe_unused]] static constexpr int BN_W2_OFF = 0, BN_W3_OFF = 73728, BN_WD_OFF = 106496, BN_WK_OFF = 139264;
@@ -61,7 +60,7 @@ struct Bneck0Args {
 // DS = false: an IDENTITY bottleneck (256 -> 64 -> 64 -> 256, y = relu(conv3 + x); networks/resnet.py:58-93 without downsample, pose_hrnet.py:98-136):
 // W1 (32 KiB, four [64][64] sub-chunks) takes Wd's place in LDS, conv1 reads 256-channel halo pixels (16 fragment loads per lane, a tile ahead), the
 // residual rows arrive in the coalesced layout (lane = 8 channels of a row) and cross the wave's scratch into the accumulator layout.
-template <bool TAP, bool DS>
+template <bool TAP, bool DS, class F>
 __global__ __launch_bounds__(256, 1) void bneck_bf16_kernel(Bneck0Args a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) unsigned char bn_lds[];
@@ -180,7 +179,7 @@ __global__ __launch_bounds__(256, 1) void bneck_bf16_kernel(Bneck0Args a) {
             for (int st = 0; st < 4; ++st)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
-                    acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bn_bf16x8, w1f[j][st]), __builtin_bit_cast(bn_bf16x8, xa[st]), acc1[j], 0, 0, 0);
+                    acc1[j] = F::mfma(__builtin_bit_cast(typename F::x8, w1f[j][st]), __builtin_bit_cast(typename F::x8, xa[st]), acc1[j]);
         } else {                              // W1 fragments from LDS, the ring of the other loops: step s = (k-step s / 2, channel block s % 2)
             constexpr int DEPTH = 3, NSTEP = 2 * NST;
             bn_u32x4 wfr[DEPTH + 1];
@@ -194,7 +193,7 @@ __global__ __launch_bounds__(256, 1) void bneck_bf16_kernel(Bneck0Args a) {
 #pragma unroll
             for (int s = 0; s < NSTEP; ++s) {
                 if (s + DEPTH < NSTEP) fetch(s + DEPTH);
-                acc1[s & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bn_bf16x8, wfr[s & DEPTH]), __builtin_bit_cast(bn_bf16x8, xa[s >> 1]), acc1[s & 1], 0, 0, 0);
+                acc1[s & 1] = F::mfma(__builtin_bit_cast(typename F::x8, wfr[s & DEPTH]), __builtin_bit_cast(typename F::x8, xa[s >> 1]), acc1[s & 1]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -209,7 +208,7 @@ __global__ __launch_bounds__(256, 1) void bneck_bf16_kernel(Bneck0Args a) {
                 float t[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) t[e] = in_img ? relu_f(acc1[j][4 * g + e]) : 0.f;
-                const bn_u32x2 pk = bn_u32x2{pack_bf16x2(t[0], t[1]), pack_bf16x2(t[2], t[3])};
+                const bn_u32x2 pk = bn_u32x2{F::pack2(t[0], t[1]), F::pack2(t[2], t[3])};
                 if (slot_ok) *reinterpret_cast<bn_u32x2*>(wk + t1_wr + ((((4 * j + g) ^ t1_sw) & 7) * 16)) = pk;
                 if (TAP && a_interior) *reinterpret_cast<bn_u32x2*>(a.t1 + (frame_px + (size_t)ha * a.W + wa) * 64 + 32 * j + 8 * g + 4 * fhalf) = pk;
             }
@@ -241,15 +240,15 @@ __global__ __launch_bounds__(256, 1) void bneck_bf16_kernel(Bneck0Args a) {
 #pragma unroll
             for (int s = 0; s < NSTEP; ++s) {
                 if (s + DEPTH < NSTEP) fetch(s + DEPTH);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bn_bf16x8, bfr[s & DEPTH]), __builtin_bit_cast(bn_bf16x8, afr[s & DEPTH]), acc2, 0, 0, 0);
+                acc2 = F::mfma(__builtin_bit_cast(typename F::x8, bfr[s & DEPTH]), __builtin_bit_cast(typename F::x8, afr[s & DEPTH]), acc2);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
         bn_u32x2 t2p[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            t2p[g] = bn_u32x2{pack_bf16x2(relu_f(acc2[4 * g]), relu_f(acc2[4 * g + 1])),
-                              pack_bf16x2(relu_f(acc2[4 * g + 2]), relu_f(acc2[4 * g + 3]))};
+            t2p[g] = bn_u32x2{F::pack2(relu_f(acc2[4 * g]), relu_f(acc2[4 * g + 1])),
+                              F::pack2(relu_f(acc2[4 * g + 2]), relu_f(acc2[4 * g + 3]))};
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();         // every wave is done reading t1: t2 goes over it
@@ -308,8 +307,8 @@ __global__ __launch_bounds__(256, 1) void bneck_bf16_kernel(Bneck0Args a) {
             for (int s = 0; s < NSTEP; ++s) {
                 const int st = s >> 2, i = s & 3;
                 if (s + DEPTH < NSTEP) fetch(s + DEPTH);
-                z[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bn_bf16x8, f3r[s & DEPTH]), __builtin_bit_cast(bn_bf16x8, a2[st]), z[i], 0, 0, 0);
-                if constexpr (DS) d[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bn_bf16x8, fdr[s & DEPTH]), __builtin_bit_cast(bn_bf16x8, xc[st]), d[i], 0, 0, 0);
+                z[i] = F::mfma(__builtin_bit_cast(typename F::x8, f3r[s & DEPTH]), __builtin_bit_cast(typename F::x8, a2[st]), z[i]);
+                if constexpr (DS) d[i] = F::mfma(__builtin_bit_cast(typename F::x8, fdr[s & DEPTH]), __builtin_bit_cast(typename F::x8, xc[st]), d[i]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -339,17 +338,17 @@ __global__ __launch_bounds__(256, 1) void bneck_bf16_kernel(Bneck0Args a) {
             for (int g = 0; g < 4; ++g) {
                 unsigned r01, r23;
                 if constexpr (DS) {
-                    r01 = pack_bf16x2(d[i][4 * g], d[i][4 * g + 1]);
-                    r23 = pack_bf16x2(d[i][4 * g + 2], d[i][4 * g + 3]);
+                    r01 = F::pack2(d[i][4 * g], d[i][4 * g + 1]);
+                    r23 = F::pack2(d[i][4 * g + 2], d[i][4 * g + 3]);
                 } else {
                     r01 = rres[g][0]; r23 = rres[g][1];
                 }
                 typedef float f2_t __attribute__((ext_vector_type(2)));
-                const f2_t s01 = f2_t{z[i][4 * g], z[i][4 * g + 1]} + f2_t{__uint_as_float(r01 << 16), __uint_as_float(r01 & 0xFFFF0000u)};
-                const f2_t s23 = f2_t{z[i][4 * g + 2], z[i][4 * g + 3]} + f2_t{__uint_as_float(r23 << 16), __uint_as_float(r23 & 0xFFFF0000u)};
+                const f2_t s01 = f2_t{z[i][4 * g], z[i][4 * g + 1]} + f2_t{F::lo(r01), F::hi(r01)};
+                const f2_t s23 = f2_t{z[i][4 * g + 2], z[i][4 * g + 3]} + f2_t{F::lo(r23), F::hi(r23)};
                 const float y0 = relu_f(s01[0]), y1 = relu_f(s01[1]), y2 = relu_f(s23[0]), y3 = relu_f(s23[1]);
-                if (BN_EXP & 32) __builtin_amdgcn_raw_buffer_store_b64(bn_u32x2{pack_bf16x2(y0, y1), pack_bf16x2(y2, y3)}, rs_y, (unsigned)(((th0 + pr) * a.W + tw0 + pc) * 256 + n0 + 8 * g + 4 * fhalf) * 2u, 0, 0);
-                else *reinterpret_cast<bn_u32x2*>(ep + frow * BN_EP_PITCH + ((g ^ ((frow >> 2) & 3)) * 16) + fhalf * 8) = bn_u32x2{pack_bf16x2(y0, y1), pack_bf16x2(y2, y3)};
+                if (BN_EXP & 32) __builtin_amdgcn_raw_buffer_store_b64(bn_u32x2{F::pack2(y0, y1), F::pack2(y2, y3)}, rs_y, (unsigned)(((th0 + pr) * a.W + tw0 + pc) * 256 + n0 + 8 * g + 4 * fhalf) * 2u, 0, 0);
+                else *reinterpret_cast<bn_u32x2*>(ep + frow * BN_EP_PITCH + ((g ^ ((frow >> 2) & 3)) * 16) + fhalf * 8) = bn_u32x2{F::pack2(y0, y1), F::pack2(y2, y3)};
                 if (TAP && DS) *reinterpret_cast<bn_u32x2*>(a.r + (frame_px + (size_t)(th0 + pr) * a.W + tw0 + pc) * 256 + n0 + 8 * g + 4 * fhalf) = bn_u32x2{r01, r23};
             }
             if (BN_EXP & 32) continue;
@@ -383,13 +382,24 @@ bool bneck0_bf16_ok(const GemmArgs& c1, const GemmArgs& c2, const GemmArgs& ds, 
     return true;
 }
 
-const char* bneck0_bf16_kernel_name() { return "bneck0_bf16<8x8>"; }
+const char* bneck0_bf16_kernel_name(int f16) { return fmt_kernel_name("bneck0_bf16<8x8>", f16); }
+
+// one instantiation's launch (its dynamic-LDS attribute is per kernel and device); every conv of a bottleneck carries the same element format
+template <bool TAP, bool DS, class F>
+static hipError_t launch_bneck_t(const Bneck0Args& a, hipStream_t s) {
+    static DynLdsAttr attr;
+    const hipError_t e = attr.ensure(reinterpret_cast<const void*>(&bneck_bf16_kernel<TAP, DS, F>), BN_LDS_BYTES);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((bneck_bf16_kernel<TAP, DS, F>), dim3(256), dim3(256), BN_LDS_BYTES, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_bneck0_bf16(const GemmArgs& c1, const GemmArgs& c2, const GemmArgs& ds, const GemmArgs& c3, bool tap, hipStream_t s) {
     if (!bneck0_bf16_ok(c1, c2, ds, c3)) return hipErrorInvalidValue;
     for (const GemmArgs* g : {&c1, &c2, &ds, &c3})
         if (!g->A || !g->Wp || !g->bias || !g->out) return hipErrorInvalidValue;
     if (c1.A != ds.A || c2.A != c1.out || c3.A != c2.out || c3.res != ds.out) return hipErrorInvalidValue;
+    if (c2.f16 != c1.f16 || ds.f16 != c1.f16 || c3.f16 != c1.f16) return hipErrorInvalidValue;
     typedef const unsigned short* hp;
     Bneck0Args a{};
     a.x = reinterpret_cast<hp>(c1.A);
@@ -399,13 +409,7 @@ hipError_t launch_bneck0_bf16(const GemmArgs& c1, const GemmArgs& c2, const Gemm
     a.t1 = reinterpret_cast<unsigned short*>(c1.out); a.t2 = reinterpret_cast<unsigned short*>(c2.out); a.r = reinterpret_cast<unsigned short*>(ds.out);
     a.H = c1.H; a.W = c1.W; a.B = c1.M / (c1.H * c1.W);
     a.tiles_x = a.W / 8; a.tiles_pf = (a.H / 8) * a.tiles_x; a.ntiles = a.B * a.tiles_pf;
-    static DynLdsAttr attr_p, attr_t;
-    const void* k = tap ? reinterpret_cast<const void*>(&bneck_bf16_kernel<true, true>) : reinterpret_cast<const void*>(&bneck_bf16_kernel<false, true>);
-    const hipError_t e = (tap ? attr_t : attr_p).ensure(k, BN_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    if (tap) hipLaunchKernelGGL((bneck_bf16_kernel<true, true>), dim3(256), dim3(256), BN_LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((bneck_bf16_kernel<false, true>), dim3(256), dim3(256), BN_LDS_BYTES, s, a);
-    return hipGetLastError();
+    return with_fmt(c1.f16, [&](auto f) { return tap ? launch_bneck_t<true, true, decltype(f)>(a, s) : launch_bneck_t<false, true, decltype(f)>(a, s); });
 }
 
 // an identity bottleneck: c1 (1x1 256 -> 64, ReLU), c2 (3x3 pad 1 on c1's output, ReLU), c3 (1x1 64 -> 256 on c2's output + c1's INPUT, ReLU)
@@ -422,13 +426,14 @@ bool bneck1_bf16_ok(const GemmArgs& c1, const GemmArgs& c2, const GemmArgs& c3) 
     return true;
 }
 
-const char* bneck1_bf16_kernel_name() { return "bneck1_bf16<8x8>"; }
+const char* bneck1_bf16_kernel_name(int f16) { return fmt_kernel_name("bneck1_bf16<8x8>", f16); }
 
 hipError_t launch_bneck1_bf16(const GemmArgs& c1, const GemmArgs& c2, const GemmArgs& c3, bool tap, hipStream_t s) {
     if (!bneck1_bf16_ok(c1, c2, c3)) return hipErrorInvalidValue;
     for (const GemmArgs* g : {&c1, &c2, &c3})
         if (!g->A || !g->Wp || !g->bias || !g->out) return hipErrorInvalidValue;
     if (c2.A != c1.out || c3.A != c2.out || c3.res != c1.A || c3.out == c1.A) return hipErrorInvalidValue;
+    if (c2.f16 != c1.f16 || c3.f16 != c1.f16) return hipErrorInvalidValue;
     typedef const unsigned short* hp;
     Bneck0Args a{};
     a.x = reinterpret_cast<hp>(c1.A);
@@ -438,13 +443,7 @@ hipError_t launch_bneck1_bf16(const GemmArgs& c1, const GemmArgs& c2, const Gemm
     a.t1 = reinterpret_cast<unsigned short*>(c1.out); a.t2 = reinterpret_cast<unsigned short*>(c2.out);
     a.H = c1.H; a.W = c1.W; a.B = c1.M / (c1.H * c1.W);
     a.tiles_x = a.W / 8; a.tiles_pf = (a.H / 8) * a.tiles_x; a.ntiles = a.B * a.tiles_pf;
-    static DynLdsAttr attr_p, attr_t;
-    const void* k = tap ? reinterpret_cast<const void*>(&bneck_bf16_kernel<true, false>) : reinterpret_cast<const void*>(&bneck_bf16_kernel<false, false>);
-    const hipError_t e = (tap ? attr_t : attr_p).ensure(k, BN_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    if (tap) hipLaunchKernelGGL((bneck_bf16_kernel<true, false>), dim3(256), dim3(256), BN_LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((bneck_bf16_kernel<false, false>), dim3(256), dim3(256), BN_LDS_BYTES, s, a);
-    return hipGetLastError();
+    return with_fmt(c1.f16, [&](auto f) { return tap ? launch_bneck_t<true, false, decltype(f)>(a, s) : launch_bneck_t<false, false, decltype(f)>(a, s); });
 }
 
 }  // namespace capf

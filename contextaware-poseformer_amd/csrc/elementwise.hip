@@ -8,26 +8,25 @@ namespace capf {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
-// 4 consecutive channels of an NHWC tensor stored as fp32 (16 B) or bf16 (8 B); arithmetic is always fp32
-__device__ __forceinline__ unsigned short f2bf_e(float f) { return to_bf16(f); }
-template <bool BF>
+// 4 consecutive channels of an NHWC tensor stored as fp32 (16 B) or in a 16-bit format F (BF: bf16 / fp16, 8 B); arithmetic is always fp32
+template <bool BF, class F = Bf16Fmt>
 __device__ __forceinline__ f32x4 load4(const float* base, long i4) {
     if (!BF) return reinterpret_cast<const f32x4*>(base)[i4];
     const u16x4 h = reinterpret_cast<const u16x4*>(base)[i4];
     f32x4 v;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = __uint_as_float((unsigned)h[e] << 16);
+    for (int e = 0; e < 4; ++e) v[e] = F::widen(h[e]);
     return v;
 }
-template <bool BF>
+template <bool BF, class F = Bf16Fmt>
 __device__ __forceinline__ void store4(float* base, long i4, f32x4 v) {
     if (!BF) { reinterpret_cast<f32x4*>(base)[i4] = v; return; }
     typedef unsigned u32x2_e __attribute__((ext_vector_type(2)));
-    reinterpret_cast<u32x2_e*>(base)[i4] = u32x2_e{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+    reinterpret_cast<u32x2_e*>(base)[i4] = u32x2_e{F::pack2(v[0], v[1]), F::pack2(v[2], v[3])};
 }
 
 // ---- BN fold (kernels.h bn_scale / bn_bias) + re-layout of a conv weight ---------
-template <bool BF>
+template <bool BF, class F = Bf16Fmt>
 __global__ void pack_conv_kernel(const float* __restrict__ w, const float* __restrict__ gamma,
                                  const float* __restrict__ beta, const float* __restrict__ mean,
                                  const float* __restrict__ var, float eps, float* __restrict__ Wp,
@@ -43,7 +42,7 @@ __global__ void pack_conv_kernel(const float* __restrict__ w, const float* __res
             const int kh = tap / ks, kw = tap - kh * ks;
             v = w[(((long)n * Cin + ci) * ks + kh) * ks + kw] * sc;
         }
-        if (BF) reinterpret_cast<unsigned short*>(Wp)[i] = f2bf_e(v);
+        if (BF) reinterpret_cast<unsigned short*>(Wp)[i] = F::narrow(v);
         else Wp[i] = v;
         if (k == 0 && bias) bias[n] = bn_bias(gamma, beta, mean, sc, n);
     }
@@ -58,13 +57,16 @@ hipError_t launch_pack_conv(const float* w, const float* gamma, const float* bet
     return hipGetLastError();
 }
 
-// same fold, weights written as bf16 [Cout][Kpad] (Kpad a multiple of 64), bias stays fp32
+// same fold, weights written as bf16 (f16 = 1: fp16) [Cout][Kpad] (Kpad a multiple of 64), bias stays fp32
 hipError_t launch_pack_conv_bf16(const float* w, const float* gamma, const float* beta, const float* mean,
                                  const float* var, float eps, void* Wp_bf16, float* bias, int Cout, int Cin, int ks,
-                                 int Kpad, hipStream_t s) {
+                                 int Kpad, hipStream_t s, int f16) {
     const long total = (long)Cout * Kpad;
-    hipLaunchKernelGGL(pack_conv_kernel<true>, dim3(grid_1d(total, 2048)), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
-                       reinterpret_cast<float*>(Wp_bf16), bias, Cout, Cin, ks, Kpad);
+    with_fmt(f16, [&](auto f) {
+        hipLaunchKernelGGL((pack_conv_kernel<true, decltype(f)>), dim3(grid_1d(total, 2048)), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
+                           reinterpret_cast<float*>(Wp_bf16), bias, Cout, Cin, ks, Kpad);
+        return 0;
+    });
     return hipGetLastError();
 }
 
@@ -103,7 +105,7 @@ hipError_t launch_pack_linear_quad(const float* w, float* Wq, int N, int K, int 
 // Input i has resolution (H >> shift_i, W >> shift_i); nearest upsampling by 2^s reads (h>>s, w>>s).
 // V channels per lane: 4 (fp32 16 B, bf16 8 B) or 8 (bf16, 16 B); pixel arithmetic in 32 bits (B * H * W < 2^31, launcher checks)
 // SH (fp32 sums only): also store the bf16 shadow of the result (a.out_sh, may be nullptr), CAPF_PLAN_BF16_F32_STREAM
-template <bool BF, int V, bool SH = false>
+template <bool BF, int V, bool SH = false, class F = Bf16Fmt>
 __device__ __forceinline__ void fuse_sum_body(const FuseSumArgs& a, const long first, const long stride) {
     constexpr int Q = V / 4;                                  // 4-channel groups per lane
     const int CV = a.C / V, C4 = a.C >> 2;
@@ -126,12 +128,12 @@ __device__ __forceinline__ void fuse_sum_body(const FuseSumArgs& a, const long f
                     const u32x4 q = reinterpret_cast<const u32x4*>(a.in[k])[off >> 1];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {               // same order as the reference: ((x0 + x1) + x2) + x3
-                        const float lo = __uint_as_float(q[e] << 16), hi = __uint_as_float(q[e] & 0xFFFF0000u);
+                        const float lo = F::lo(q[e]), hi = F::hi(q[e]);
                         acc[e >> 1][(e & 1) * 2] = k == 0 ? lo : acc[e >> 1][(e & 1) * 2] + lo;
                         acc[e >> 1][(e & 1) * 2 + 1] = k == 0 ? hi : acc[e >> 1][(e & 1) * 2 + 1] + hi;
                     }
                 } else {
-                    const f32x4 v = load4<BF>(a.in[k], off);
+                    const f32x4 v = load4<BF, F>(a.in[k], off);
                     acc[0] = k == 0 ? v : acc[0] + v;
                 }
             }
@@ -145,21 +147,21 @@ __device__ __forceinline__ void fuse_sum_body(const FuseSumArgs& a, const long f
         }
         if (V == 8) {
             typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-            reinterpret_cast<u32x4*>(a.out)[i] = u32x4{pack_bf16x2(acc[0][0], acc[0][1]), pack_bf16x2(acc[0][2], acc[0][3]),
-                                                       pack_bf16x2(acc[Q - 1][0], acc[Q - 1][1]), pack_bf16x2(acc[Q - 1][2], acc[Q - 1][3])};
+            reinterpret_cast<u32x4*>(a.out)[i] = u32x4{F::pack2(acc[0][0], acc[0][1]), F::pack2(acc[0][2], acc[0][3]),
+                                                       F::pack2(acc[Q - 1][0], acc[Q - 1][1]), F::pack2(acc[Q - 1][2], acc[Q - 1][3])};
         } else {
-            store4<BF>(a.out, i, acc[0]);
+            store4<BF, F>(a.out, i, acc[0]);
             if (SH && a.out_sh) {
                 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                reinterpret_cast<u32x2*>(a.out_sh)[i] = u32x2{pack_bf16x2(acc[0][0], acc[0][1]), pack_bf16x2(acc[0][2], acc[0][3])};
+                reinterpret_cast<u32x2*>(a.out_sh)[i] = u32x2{F::pack2(acc[0][0], acc[0][1]), F::pack2(acc[0][2], acc[0][3])};
             }
         }
     }
 }
 
-template <bool BF, int V>
+template <bool BF, int V, class F = Bf16Fmt>
 __global__ void fuse_sum_kernel(FuseSumArgs a) {
-    fuse_sum_body<BF, V>(a, blockIdx.x * (long)blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+    fuse_sum_body<BF, V, false, F>(a, blockIdx.x * (long)blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
 }
 
 __global__ void fuse_sum_shadow_kernel(FuseSumArgs a) {
@@ -171,14 +173,14 @@ struct FuseGroupArgs {
     int bstart[5];     // first block of problem i (bstart[n] = grid size)
     int n;
 };
-template <bool BF, int V>
+template <bool BF, int V, class F = Bf16Fmt>
 __global__ void fuse_sum_group_kernel(FuseGroupArgs g) {
     int pi = 0;
 #pragma unroll
     for (int i = 1; i < 4; ++i)
         if (i < g.n && (int)blockIdx.x >= g.bstart[i]) pi = i;
     const int nb = g.bstart[pi + 1] - g.bstart[pi];
-    fuse_sum_body<BF, V>(g.p[pi], (long)(blockIdx.x - g.bstart[pi]) * blockDim.x + threadIdx.x, (long)nb * blockDim.x);
+    fuse_sum_body<BF, V, false, F>(g.p[pi], (long)(blockIdx.x - g.bstart[pi]) * blockDim.x + threadIdx.x, (long)nb * blockDim.x);
 }
 
 __global__ void fuse_sum_group_shadow_kernel(FuseGroupArgs g) {
@@ -197,8 +199,13 @@ hipError_t launch_fuse_sum(const FuseSumArgs& a, hipStream_t s) {
     const long want = (total + 255) / 256;
     const int blocks = (int)(want < 16384 ? want : 16384);
     if (a.out_sh && a.bf16) return hipErrorInvalidValue;
-    if (V == 8) hipLaunchKernelGGL((fuse_sum_kernel<true, 8>), dim3(blocks), dim3(256), 0, s, a);
-    else if (a.bf16) hipLaunchKernelGGL((fuse_sum_kernel<true, 4>), dim3(blocks), dim3(256), 0, s, a);
+    if (a.bf16)
+        with_fmt(a.f16, [&](auto f) {
+            using F = decltype(f);
+            if (V == 8) hipLaunchKernelGGL((fuse_sum_kernel<true, 8, F>), dim3(blocks), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((fuse_sum_kernel<true, 4, F>), dim3(blocks), dim3(256), 0, s, a);
+            return 0;
+        });
     else if (a.out_sh) hipLaunchKernelGGL(fuse_sum_shadow_kernel, dim3(blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((fuse_sum_kernel<false, 4>), dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -213,7 +220,7 @@ hipError_t launch_fuse_sum_group(const FuseSumArgs* a, int n, hipStream_t s) {
     int blocks = 0;
     bool shadow = false;
     for (int i = 0; i < n; ++i) {
-        if ((long)a[i].B * a[i].H * a[i].W >= (1L << 31) || a[i].bf16 != a[0].bf16 || (a[i].out_sh && a[i].bf16)) return hipErrorInvalidValue;
+        if ((long)a[i].B * a[i].H * a[i].W >= (1L << 31) || a[i].bf16 != a[0].bf16 || a[i].f16 != a[0].f16 || (a[i].out_sh && a[i].bf16)) return hipErrorInvalidValue;
         shadow |= a[i].out_sh != nullptr;
         if (((a[i].bf16 && a[i].C % 8 == 0) ? 8 : 4) != V) return hipErrorInvalidValue;
         const long total = (long)a[i].B * a[i].H * a[i].W * (a[i].C / V);
@@ -224,15 +231,20 @@ hipError_t launch_fuse_sum_group(const FuseSumArgs* a, int n, hipStream_t s) {
     }
     g.bstart[n] = blocks;
     for (int i = n + 1; i < 5; ++i) g.bstart[i] = blocks;
-    if (V == 8) hipLaunchKernelGGL((fuse_sum_group_kernel<true, 8>), dim3(blocks), dim3(256), 0, s, g);
-    else if (a[0].bf16) hipLaunchKernelGGL((fuse_sum_group_kernel<true, 4>), dim3(blocks), dim3(256), 0, s, g);
+    if (a[0].bf16)
+        with_fmt(a[0].f16, [&](auto f) {
+            using F = decltype(f);
+            if (V == 8) hipLaunchKernelGGL((fuse_sum_group_kernel<true, 8, F>), dim3(blocks), dim3(256), 0, s, g);
+            else hipLaunchKernelGGL((fuse_sum_group_kernel<true, 4, F>), dim3(blocks), dim3(256), 0, s, g);
+            return 0;
+        });
     else if (shadow) hipLaunchKernelGGL(fuse_sum_group_shadow_kernel, dim3(blocks), dim3(256), 0, s, g);
     else hipLaunchKernelGGL((fuse_sum_group_kernel<false, 4>), dim3(blocks), dim3(256), 0, s, g);
     return hipGetLastError();
 }
 
 // ---- 3x3 stride-2 pad-1 max pool (networks/resnet.py:104, :140) ----------------------------------
-template <bool BF, int V>      // V channels per lane: 4, or 8 for bf16 (16-byte accesses)
+template <bool BF, int V, class F = Bf16Fmt>      // V channels per lane: 4, or 8 for bf16 (16-byte accesses)
 __global__ void maxpool_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int H, int W,
                                int C, int Ho, int Wo) {
     constexpr int Q = V / 4;
@@ -256,24 +268,25 @@ __global__ void maxpool_kernel(const float* __restrict__ in, float* __restrict__
                 const long off = (((long)b * H + hi) * W + wi) * C4 + cv * Q;
 #pragma unroll
                 for (int q = 0; q < Q; ++q) {
-                    const f32x4 v = load4<BF>(in, off + q);
+                    const f32x4 v = load4<BF, F>(in, off + q);
                     m[q][0] = fmaxf(m[q][0], v[0]); m[q][1] = fmaxf(m[q][1], v[1]);
                     m[q][2] = fmaxf(m[q][2], v[2]); m[q][3] = fmaxf(m[q][3], v[3]);
                 }
             }
         }
 #pragma unroll
-        for (int q = 0; q < Q; ++q) store4<BF>(out, i * Q + q, m[q]);
+        for (int q = 0; q < Q; ++q) store4<BF, F>(out, i * Q + q, m[q]);
     }
 }
 
 hipError_t launch_maxpool3x3s2(const float* in, float* out, int B, int H, int W, int C, int Ho, int Wo,
-                               hipStream_t s, int bf16) {
+                               hipStream_t s, int bf16, int f16) {
     if ((long)B * Ho * Wo >= (1L << 31)) return hipErrorInvalidValue;
     const int V = (bf16 && C % 8 == 0) ? 8 : 4;
     const long total = (long)B * Ho * Wo * (C / V);
     const long want = (total + 255) / 256;
     const dim3 grid((int)(want < 16384 ? want : 16384));
+    if (bf16 && f16) return hipErrorInvalidValue;          // CPN's pool: no fp16 plan has one (CPN is refused under CAPF_F16), so no fp16 instantiation
     if (V == 8) hipLaunchKernelGGL((maxpool_kernel<true, 8>), grid, dim3(256), 0, s, in, out, B, H, W, C, Ho, Wo);
     else if (bf16) hipLaunchKernelGGL((maxpool_kernel<true, 4>), grid, dim3(256), 0, s, in, out, B, H, W, C, Ho, Wo);
     else hipLaunchKernelGGL((maxpool_kernel<false, 4>), grid, dim3(256), 0, s, in, out, B, H, W, C, Ho, Wo);
@@ -283,7 +296,7 @@ hipError_t launch_maxpool3x3s2(const float* in, float* out, int B, int H, int W,
 // ---- bilinear resize, align_corners=True (globalNet.py:40, refineNet.py:61) ----------------------
 // ATen upsample_bilinear2d: src = dst * (in-1)/(out-1) (0 if out == 1); i0 = (int)src, i1 = i0 + (i0 < in-1);
 // l1 = src - i0, l0 = 1 - l1;  out = l0h*(l0w*v00 + l1w*v01) + l1h*(l0w*v10 + l1w*v11).
-template <bool BF, int V>      // V channels per lane: 4 (fp32: 16 B; bf16: 8 B) or 8 (bf16: 16 B)
+template <bool BF, int V, class F = Bf16Fmt>      // V channels per lane: 4 (fp32: 16 B; bf16: 8 B) or 8 (bf16: 16 B)
 __global__ void bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int H, int W,
                                 int C, int Ho, int Wo, float sh, float sw, const float* __restrict__ add) {
     const int CV = C / V;
@@ -310,27 +323,27 @@ __global__ void bilinear_kernel(const float* __restrict__ in, float* __restrict_
             u32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float lo = lh0 * (lw0 * __uint_as_float(q00[e] << 16) + lw1 * __uint_as_float(q01[e] << 16)) +
-                           lh1 * (lw0 * __uint_as_float(q10[e] << 16) + lw1 * __uint_as_float(q11[e] << 16));
-                float hi = lh0 * (lw0 * __uint_as_float(q00[e] & 0xFFFF0000u) + lw1 * __uint_as_float(q01[e] & 0xFFFF0000u)) +
-                           lh1 * (lw0 * __uint_as_float(q10[e] & 0xFFFF0000u) + lw1 * __uint_as_float(q11[e] & 0xFFFF0000u));
-                lo += __uint_as_float(qa[e] << 16);
-                hi += __uint_as_float(qa[e] & 0xFFFF0000u);
-                o[e] = pack_bf16x2(lo, hi);
+                float lo = lh0 * (lw0 * F::lo(q00[e]) + lw1 * F::lo(q01[e])) +
+                           lh1 * (lw0 * F::lo(q10[e]) + lw1 * F::lo(q11[e]));
+                float hi = lh0 * (lw0 * F::hi(q00[e]) + lw1 * F::hi(q01[e])) +
+                           lh1 * (lw0 * F::hi(q10[e]) + lw1 * F::hi(q11[e]));
+                lo += F::lo(qa[e]);
+                hi += F::hi(qa[e]);
+                o[e] = F::pack2(lo, hi);
             }
             reinterpret_cast<u32x4*>(out)[i] = o;
         } else {
-            const f32x4 v00 = load4<BF>(in, o00), v01 = load4<BF>(in, o01), v10 = load4<BF>(in, o10), v11 = load4<BF>(in, o11);
+            const f32x4 v00 = load4<BF, F>(in, o00), v01 = load4<BF, F>(in, o01), v10 = load4<BF, F>(in, o10), v11 = load4<BF, F>(in, o11);
             f32x4 r;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 r[e] = lh0 * (lw0 * v00[e] + lw1 * v01[e]) + lh1 * (lw0 * v10[e] + lw1 * v11[e]);
             if (add) {
-                const f32x4 a = load4<BF>(add, i);
+                const f32x4 a = load4<BF, F>(add, i);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) r[e] += a[e];
             }
-            store4<BF>(out, i, r);
+            store4<BF, F>(out, i, r);
         }
     }
 }
@@ -338,7 +351,7 @@ __global__ void bilinear_kernel(const float* __restrict__ in, float* __restrict_
 // The same, one block per output ROW (b, ho): the row's two source rows and vertical weights are block-uniform (scalar), an
 // item needs one division (by the channel-group count: a shift for the 256-channel CPN maps) instead of three plus 64-bit row
 // arithmetic per element.  Same expression per output element as bilinear_kernel: bit-identical.
-template <bool BF, int V>
+template <bool BF, int V, class F = Bf16Fmt>
 __global__ void bilinear_rows_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W, int C, int Ho, int Wo,
                                      float sh, float sw, const float* __restrict__ add, int cv_shift) {
     const int CV = C / V, C4 = C >> 2;
@@ -367,34 +380,35 @@ __global__ void bilinear_rows_kernel(const float* __restrict__ in, float* __rest
             u32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float lo = lh0 * (lw0 * __uint_as_float(q00[e] << 16) + lw1 * __uint_as_float(q01[e] << 16)) +
-                           lh1 * (lw0 * __uint_as_float(q10[e] << 16) + lw1 * __uint_as_float(q11[e] << 16));
-                float hi = lh0 * (lw0 * __uint_as_float(q00[e] & 0xFFFF0000u) + lw1 * __uint_as_float(q01[e] & 0xFFFF0000u)) +
-                           lh1 * (lw0 * __uint_as_float(q10[e] & 0xFFFF0000u) + lw1 * __uint_as_float(q11[e] & 0xFFFF0000u));
-                lo += __uint_as_float(qa[e] << 16);
-                hi += __uint_as_float(qa[e] & 0xFFFF0000u);
-                o[e] = pack_bf16x2(lo, hi);
+                float lo = lh0 * (lw0 * F::lo(q00[e]) + lw1 * F::lo(q01[e])) +
+                           lh1 * (lw0 * F::lo(q10[e]) + lw1 * F::lo(q11[e]));
+                float hi = lh0 * (lw0 * F::hi(q00[e]) + lw1 * F::hi(q01[e])) +
+                           lh1 * (lw0 * F::hi(q10[e]) + lw1 * F::hi(q11[e]));
+                lo += F::lo(qa[e]);
+                hi += F::hi(qa[e]);
+                o[e] = F::pack2(lo, hi);
             }
             reinterpret_cast<u32x4*>(out)[i] = o;
         } else {
-            const f32x4 v00 = load4<BF>(in, r0 + c0), v01 = load4<BF>(in, r0 + c1), v10 = load4<BF>(in, r1 + c0), v11 = load4<BF>(in, r1 + c1);
+            const f32x4 v00 = load4<BF, F>(in, r0 + c0), v01 = load4<BF, F>(in, r0 + c1), v10 = load4<BF, F>(in, r1 + c0), v11 = load4<BF, F>(in, r1 + c1);
             f32x4 r;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 r[e] = lh0 * (lw0 * v00[e] + lw1 * v01[e]) + lh1 * (lw0 * v10[e] + lw1 * v11[e]);
             if (add) {
-                const f32x4 a = load4<BF>(add, i);
+                const f32x4 a = load4<BF, F>(add, i);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) r[e] += a[e];
             }
-            store4<BF>(out, i, r);
+            store4<BF, F>(out, i, r);
         }
     }
 }
 
 hipError_t launch_bilinear_resize(const float* in, float* out, int B, int H, int W, int C, int Ho, int Wo,
-                                  hipStream_t s, int bf16, const float* add) {
+                                  hipStream_t s, int bf16, const float* add, int f16) {
     if ((long)B * Ho * Wo >= (1L << 31)) return hipErrorInvalidValue;
+    if (bf16 && f16) return hipErrorInvalidValue;          // CPN's resizes: bf16 only, as the pool above
     const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
     const float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
     const int V = (bf16 && C % 8 == 0) ? 8 : 4;

@@ -51,9 +51,9 @@ int Engine::repack(hipStream_t s, bool lifter_only) {
             if (lifter_only) continue;                  // conv+BN packs belong to the frozen backbone
             const ConvSrc c = conv_src(pk);
             if (pk.bf16) {
-                HIP_TRY(launch_pack_conv_bf16(c.w, c.g, c.b, c.m, c.v, c.eps, W, B, pk.N, pk.Cin, pk.ks, pk.Kpad, s));
-                if (pk.rh) HIP_TRY(launch_pack_conv_bf16_rh(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.rh_off, B, pk.N, pk.Cin, bf16_rh_width(pk.Cin), s));
-                if (pk.ws) HIP_TRY(launch_pack_conv_bf16_ws(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.ws_off, B, pk.N, pk.Cin, s));
+                HIP_TRY(launch_pack_conv_bf16(c.w, c.g, c.b, c.m, c.v, c.eps, W, B, pk.N, pk.Cin, pk.ks, pk.Kpad, s, f16()));
+                if (pk.rh) HIP_TRY(launch_pack_conv_bf16_rh(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.rh_off, B, pk.N, pk.Cin, bf16_rh_width(pk.Cin), s, f16()));
+                if (pk.ws) HIP_TRY(launch_pack_conv_bf16_ws(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.ws_off, B, pk.N, pk.Cin, s, f16()));
             } else if (pk.wino) {
                 if (!pk.wino_skip) HIP_TRY(launch_pack_conv_wino(c.w, c.g, c.b, c.m, c.v, c.eps, W, B, pk.N, pk.Cin, s, pk.Kpad == 18 * pk.Cin ? 43 : 23));
                 HIP_TRY(launch_pack_conv(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.direct_off, B, pk.N, pk.Cin, pk.ks, pk.direct_Kpad, s));
@@ -70,7 +70,7 @@ int Engine::repack(hipStream_t s, bool lifter_only) {
             const float* w = params[pk.w[i]].ptr;
             if (pk.bf16)                                // bf16 [N][Kpad] (a 1x1 "conv" without BatchNorm), bias fp32
                 HIP_TRY(launch_pack_conv_bf16(w, nullptr, nullptr, nullptr, nullptr, 0.f, reinterpret_cast<unsigned short*>(W) + (size_t)n0 * pk.Kpad,
-                                              nullptr, n, pk.K, 1, pk.Kpad, s));
+                                              nullptr, n, pk.K, 1, pk.Kpad, s, f16()));
             else if (pk.quad) HIP_TRY(launch_pack_linear_quad(w, W, n, pk.K, n0, pk.N, s));     // fused lifter kernels: Wq[k / 4][n][4]
             else HIP_TRY(launch_pack_linear(w, W + (size_t)n0 * pk.Kpad, n, pk.K, pk.Kpad, s));
             jobs.push_back(CopySegment{params[pk.b[i]].ptr, B + n0, n, 0});
@@ -146,6 +146,7 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes) const {
     a.amap = op.amap; a.omap = op.omap; a.rmap = op.rmap;
     a.act = op.act;
     a.out_bf16 = op.out_bf16;
+    a.f16 = f16();                                     // (the element format of whatever 16-bit kernel takes the problem)
     a.f32s = op.f32s;                                  // (CAPF_PLAN_BF16_F32_STREAM: fp32 residual; fp32 result + bf16 shadow, or bf16 result)
     a.out_f32 = op.st_f32;
     a.out_sh = op.sh >= 0 ? ptr(op.sh) : nullptr;
@@ -189,7 +190,7 @@ Engine::FusedLaunch Engine::fused_at(int i, int batch, int last_op, bool bneck_o
     if (i < 0 || i >= n_all) return {};
     const Op& o = ops[i];
     if (o.kind == OP_FORK) {                                   // conv1, conv2 | downsample inside the region, conv3 right after its join
-        if (!plan.use_bneck || !bf16() || o.fork.lanes != 2 || o.region < 0) return {};
+        if (!plan.use_bneck || !b16() || o.fork.lanes != 2 || o.region < 0) return {};
         const int j = regions[o.region].second;
         if (j != i + 4 || j + 1 >= last_op || j + 1 >= n_all) return {};
         int c1 = -1, c2 = -1, ds = -1;
@@ -206,7 +207,7 @@ Engine::FusedLaunch Engine::fused_at(int i, int batch, int last_op, bool bneck_o
         return {Fusion::BNECK0, 4, {c1, c2, ds, c3}};
     }
     if (o.kind != OP_GEMM) return {};
-    if (plan.use_bneck && bf16() && i + 2 < last_op && i + 2 < n_all) {
+    if (plan.use_bneck && b16() && i + 2 < last_op && i + 2 < n_all) {
         const Op &c2 = ops[i + 1], &c3 = ops[i + 2];
         bool ok = o.bneck_c3 == i + 2 && c2.in[0] == o.out && c3.in[0] == c2.out && c3.aux == o.in[0] && o.aux < 0 && c2.aux < 0 &&
                   o.rows_per_frame * batch >= 65536;
@@ -247,7 +248,7 @@ Engine::OpRoute Engine::op_route(const Op& op, int batch) const {
     const Pack& pk = packs[op.pack];
     const double MN = 2.0 * (double)op.rows_per_frame * batch * op.N;
     const Family f = gemm_family(op, batch);
-    if (f == Family::BF16_ROWS) return {f, gemm_bf16_rows_kernel_name((int)(op.rows_per_frame * batch), op.N), MN * (pk.in_place ? op.K : pk.Kpad)};
+    if (f == Family::BF16_ROWS) return {f, gemm_bf16_rows_kernel_name((int)(op.rows_per_frame * batch), op.N, f16()), MN * (pk.in_place ? op.K : pk.Kpad)};
     const GemmArgs a = gemm_args(op, batch);
     if (f == Family::BF16)                                     // (the row-halo layout has no K padding: decided per launch, a lower bound)
         return {f, gemm_bf16_kernel_name(a), MN * (pk.rh || pk.in_place ? op.K : pk.Kpad)};
@@ -268,6 +269,7 @@ FuseSumArgs Engine::fuse_args(const Op& op, int batch) const {
     a.out = op.out >= 0 ? bptr(op.out, batch) : nullptr;
     a.B = batch; a.H = op.H; a.W = op.W; a.C = op.C; a.relu = op.relu;
     a.bf16 = op.bf16;
+    a.f16 = f16();
     a.out_sh = op.sh >= 0 ? bptr(op.sh, batch) : nullptr;
     return a;
 }
@@ -283,7 +285,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
             const GemmArgs a = gemm_args(op, batch);
             switch (gemm_family(op, batch)) {
                 case Family::BF16_ROWS:
-                    HIP_TRY(launch_gemm_bf16_rows(a.A, a.Wp, a.bias, a.M, a.N, a.K, a.Kpad, a.out, a.omap, a.res, a.rmap, op.out_bf16, s));
+                    HIP_TRY(launch_gemm_bf16_rows(a.A, a.Wp, a.bias, a.M, a.N, a.K, a.Kpad, a.out, a.omap, a.res, a.rmap, op.out_bf16, s, f16()));
                     break;
                 case Family::BF16: HIP_TRY(launch_gemm_bf16(a, s)); break;
                 case Family::WINO: HIP_TRY(launch_gemm_wino(a, s)); break;
@@ -297,10 +299,10 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
             break;
         }
         case OP_MAXPOOL:
-            HIP_TRY(launch_maxpool3x3s2(ptr(op.in[0]), ptr(op.out), batch, op.H, op.W, op.C, op.Ho, op.Wo, s, op.bf16));
+            HIP_TRY(launch_maxpool3x3s2(ptr(op.in[0]), ptr(op.out), batch, op.H, op.W, op.C, op.Ho, op.Wo, s, op.bf16, f16()));
             break;
         case OP_RESIZE:
-            HIP_TRY(launch_bilinear_resize(ptr(op.in[0]), ptr(op.out), batch, op.H, op.W, op.C, op.Ho, op.Wo, s, op.bf16, ptr(op.aux)));
+            HIP_TRY(launch_bilinear_resize(ptr(op.in[0]), ptr(op.out), batch, op.H, op.W, op.C, op.Ho, op.Wo, s, op.bf16, ptr(op.aux), f16()));
             break;
         case OP_PREP_EMBED:
             HIP_TRY(launch_prep_embed(kcrop, k2d, params[op.coord.w].ptr, params[op.coord.b].ptr, params[op.pos].ptr,
@@ -313,7 +315,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
         case OP_LAYERNORM:
             HIP_TRY(launch_layernorm(ptr(op.in[0]), op.amap, ptr(op.aux), op.rmap, params[op.ln.w].ptr,
                                      params[op.ln.b].ptr, op.eps, ptr(op.out), (int)(op.rows_per_frame * batch),
-                                     op.C, s, op.out_bf16));
+                                     op.C, s, op.out_bf16 ? 1 + (int)f16() : 0));
             break;
         case OP_DEFORM: {
             DeformArgs a{};
@@ -367,7 +369,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
             break;
         }
         case OP_ATTENTION:
-            HIP_TRY(launch_attention(ptr(op.in[0]), ptr(op.out), op.attn.groups * batch, op.attn.tokens, op.attn.heads, op.attn.head_dim, s, op.out_bf16));
+            HIP_TRY(launch_attention(ptr(op.in[0]), ptr(op.out), op.attn.groups * batch, op.attn.tokens, op.attn.heads, op.attn.head_dim, s, op.out_bf16 ? 1 + (int)f16() : 0));
             break;
         case OP_RES_CHAIN: {
             ResBlockW blk[8];
@@ -486,7 +488,7 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
 // the product schedule (grouped launches included).
 int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t* ev, LaunchLog* log) {
     hipStream_t main_stream = s;
-    if (plan.use_h2g && (batch >= H2G_MIN_BATCH || has_res_chain) && last_op > n_backbone_ops && !bf16()) {      // (the fused res blocks read the packs at every batch)
+    if (plan.use_h2g && (batch >= H2G_MIN_BATCH || has_res_chain) && last_op > n_backbone_ops && !b16()) {      // (the fused res blocks read the packs at every batch)
         const int rc = ensure_h2g_lifter(s);
         if (rc) return rc;
     }
@@ -575,7 +577,7 @@ static std::string g_create_error;
 
 extern "C" {
 
-const char* capf_version(void) { return "capf 0.11 (gfx950)"; }
+const char* capf_version(void) { return "capf 0.12 (gfx950)"; }
 int capf_abi_version(void) { return CAPF_ABI_VERSION; }
 
 const char* capf_last_error(const capf_handle* h) { return h ? h->e.err.c_str() : g_create_error.c_str(); }
@@ -590,10 +592,20 @@ int capf_create(const capf_config* cfg, int device, capf_handle** out) {
     e.cfg = *cfg;
     e.device = device;
     e.lanes = 2;
-    if (cfg->compute_dtype != CAPF_F32 && cfg->compute_dtype != CAPF_BF16) {
-        g_create_error = "compute_dtype must be CAPF_F32 or CAPF_BF16";
+    if (cfg->compute_dtype != CAPF_F32 && cfg->compute_dtype != CAPF_BF16 && cfg->compute_dtype != CAPF_F16) {
+        g_create_error = "compute_dtype must be CAPF_F32, CAPF_BF16 or CAPF_F16";
         delete h;
         return CAPF_ERR_UNSUPPORTED;
+    }
+    if (cfg->compute_dtype == CAPF_F16) {       // the fp16 plan is the HRNet inference plan; what else a 16-bit plan can do is bf16's until it has tests of its own
+        const char* why = cfg->backbone != CAPF_HRNET ? "compute_dtype = CAPF_F16 is an HRNet plan (CPN50 is not supported)"
+                          : (cfg->plan_flags & CAPF_PLAN_BF16_F32_STREAM) ? "CAPF_PLAN_BF16_F32_STREAM needs compute_dtype = CAPF_BF16 (CAPF_F16 is not supported)"
+                          : cfg->training ? "compute_dtype = CAPF_F16 is an inference plan (training = 1 is not supported)" : nullptr;
+        if (why) {
+            g_create_error = why;
+            delete h;
+            return CAPF_ERR_UNSUPPORTED;
+        }
     }
     if (cfg->plan_flags & ~(16383 | CAPF_PLAN_BF16_F32_STREAM)) {
         g_create_error = "unknown capf_plan_flag bits";
@@ -896,7 +908,7 @@ int capf_tensor(const capf_handle* h, const char* name, const void** dev_ptr, in
     }
     if (ndim) *ndim = t.ndim;
     if (dev_ptr) *dev_ptr = (e.ws && e.last_batch > 0) ? e.bptr(t.buf, e.last_batch) : nullptr;
-    return t.is_int;      // 0 fp32, 1 int32, 2 bf16
+    return t.is_int;      // 0 fp32, 1 int32, 2 bf16, 3 fp16
 }
 
 // ---- stand-alone operators (capf_op_*: op-level tests and micro-benchmarks) ----------------------------------------------------------
@@ -1165,6 +1177,101 @@ int capf_op_linear_bf16(void* stream, const void* x_bf16, const void* w_bf16, co
                ? CAPF_OK : CAPF_ERR_UNSUPPORTED;
 }
 
+// ---- the 16-bit kernel families for either element format (dtype = CAPF_BF16 or CAPF_F16): the entries above are these at CAPF_BF16
+static bool dtype16(int dtype) { return dtype == CAPF_BF16 || dtype == CAPF_F16; }
+
+int capf_op_pack_conv_16(void* stream, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
+                         void* wp, float* bias, int Cout, int Cin, int ks, int layout, int dtype) {
+    if (!w || !wp || !dtype16(dtype) || Cout <= 0 || Cin <= 0) return CAPF_ERR_INVALID;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int f16 = dtype == CAPF_F16;
+    switch (layout) {
+        case 0: return hip_rc(capf::launch_pack_conv_bf16(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, ks, (ks * ks * Cin + 63) / 64 * 64, s, f16));
+        case 1: {
+            const int cw = ks == 3 ? capf_op_conv_bf16_rh_width(Cin) : 0;
+            if (!cw) return CAPF_ERR_UNSUPPORTED;
+            return hip_rc(capf::launch_pack_conv_bf16_rh(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, cw, s, f16));
+        }
+        case 2:
+            if (ks != 3 || Cin % 16 != 0 || Cout % 8 != 0) return CAPF_ERR_UNSUPPORTED;
+            return hip_rc(capf::launch_pack_conv_bf16_ws(w, gamma, beta, mean, var, eps, wp, bias, Cout, Cin, s, f16));
+        default: return CAPF_ERR_INVALID;
+    }
+}
+
+int capf_op_conv_16(void* stream, const void* x, const void* wp, const float* bias, const void* residual, void* y, int B, int H, int W,
+                    int Cin, int Cout, int ks, int stride, int act, int dtype) {
+    if (!dtype16(dtype)) return CAPF_ERR_INVALID;
+    if (Cin % 8 != 0) {         // the stem of a 16-bit plan: fp32 image and fp32 pack (capf_op_pack_conv) in, both rounded on their way into LDS; 16-bit result
+        if (residual) return CAPF_ERR_UNSUPPORTED;
+        capf::GemmArgs a = conv_args(conv_desc(x, wp, bias, nullptr, y, B, H, W, Cin, Cout, ks, stride, act), &capf::GemmArgs::Wp, 32);
+        a.out_bf16 = 1;
+        a.f16 = dtype == CAPF_F16;
+        return hip_rc(capf::launch_gemm_bf16_smallc(a, static_cast<hipStream_t>(stream)), CAPF_ERR_UNSUPPORTED);
+    }
+    capf::GemmArgs a = conv_args(conv_desc(x, wp, bias, residual, y, B, H, W, Cin, Cout, ks, stride, act), &capf::GemmArgs::Wp, 64);
+    a.f16 = dtype == CAPF_F16;
+    return hip_rc(capf::launch_gemm_bf16(a, static_cast<hipStream_t>(stream)), CAPF_ERR_UNSUPPORTED);
+}
+
+int capf_op_conv_16_group(void* stream, int n, const capf_conv_desc* d, const void* const* w_rh, int32_t* variant, int dtype) {
+    if (!dtype16(dtype)) return CAPF_ERR_INVALID;
+    return conv_group(stream, n, d, [w_rh, dtype](const capf_conv_desc& c, int i, capf::GemmArgs& a) {
+        a = conv_args(c, &capf::GemmArgs::Wp, 64);
+        a.Wp2 = w_rh ? static_cast<const float*>(w_rh[i]) : nullptr;
+        a.f16 = dtype == CAPF_F16;
+        return capf::gemm_bf16_groupable(a) ? CAPF_OK : CAPF_ERR_UNSUPPORTED;
+    }, [variant](const capf::GemmArgs* g, int n, hipStream_t s) {
+        int v = -1;
+        const hipError_t e = capf::launch_gemm_bf16_group(g, n, s, &v);
+        if (variant) *variant = v;
+        return e;
+    });
+}
+
+int capf_op_conv_16_ws_group(void* stream, int n, const capf_conv_desc* d, int dtype) {
+    if (!dtype16(dtype)) return CAPF_ERR_INVALID;
+    return conv_group(stream, n, d, [dtype](const capf_conv_desc& c, int, capf::GemmArgs& a) {
+        const int rc = wp3_build(c, a, capf::gemm_bf16_ws_ok, 0);
+        a.f16 = dtype == CAPF_F16;
+        return rc;
+    }, capf::launch_gemm_bf16_ws_group);
+}
+
+int capf_op_linear_16(void* stream, const void* x, const void* w, const float* bias, const float* residual, void* y, int M, int N, int K,
+                      int gelu_out16, int dtype) {
+    if (!x || !w || !y || K % 64 != 0 || !dtype16(dtype)) return CAPF_ERR_INVALID;
+    return hip_rc(capf::launch_gemm_bf16_rows(x, w, bias, M, N, K, K, static_cast<float*>(y), capf::row_ld(N), residual, capf::row_ld(N), gelu_out16,
+                                              static_cast<hipStream_t>(stream), dtype == CAPF_F16), CAPF_ERR_UNSUPPORTED);
+}
+
+int capf_op_bneck_16(void* stream, const void* x, const void* const w[4], const float* const bias[4], void* t1, void* t2, void* shortcut, void* y,
+                     int B, int H, int W, int tap, int dtype) {
+    if (!x || !w || !bias || !t1 || !t2 || !y || !dtype16(dtype) || B <= 0) return CAPF_ERR_INVALID;
+    const bool first = w[3] != nullptr;                  // a downsample conv: the first bottleneck (64 channels in), else the identity one (256 in)
+    if (first && !shortcut) return CAPF_ERR_INVALID;
+    const int cin = first ? 64 : 256;
+    capf::GemmArgs c1 = conv_args(conv_desc(x, w[0], bias[0], nullptr, t1, B, H, W, cin, 64, 1, 1, capf::ACT_RELU), &capf::GemmArgs::Wp, 64);
+    capf::GemmArgs c2 = conv_args(conv_desc(t1, w[1], bias[1], nullptr, t2, B, H, W, 64, 64, 3, 1, capf::ACT_RELU), &capf::GemmArgs::Wp, 64);
+    capf::GemmArgs c3 = conv_args(conv_desc(t2, w[2], bias[2], first ? shortcut : x, y, B, H, W, 64, 256, 1, 1, capf::ACT_RELU), &capf::GemmArgs::Wp, 64);
+    capf::GemmArgs ds = conv_args(conv_desc(x, w[3], bias[3], nullptr, shortcut, B, H, W, 64, 256, 1, 1, capf::ACT_NONE), &capf::GemmArgs::Wp, 64);
+    c1.f16 = c2.f16 = c3.f16 = ds.f16 = dtype == CAPF_F16;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (first) return hip_rc(capf::launch_bneck0_bf16(c1, c2, ds, c3, tap != 0, s), CAPF_ERR_UNSUPPORTED);
+    return hip_rc(capf::launch_bneck1_bf16(c1, c2, c3, tap != 0, s), CAPF_ERR_UNSUPPORTED);
+}
+
+int capf_debug_f16_round(const float* in, uint16_t* out, int n) {
+    if (!in || !out || n < 0) return CAPF_ERR_INVALID;
+    for (int i = 0; i + 1 < n; i += 2) {                   // the two-element pack, as the kernels' epilogues store; an odd tail through the scalar form
+        const unsigned u = capf::F16Fmt::pack2(in[i], in[i + 1]);
+        out[i] = (uint16_t)(u & 0xFFFFu);
+        out[i + 1] = (uint16_t)(u >> 16);
+    }
+    if (n & 1) out[n - 1] = capf::F16Fmt::narrow(in[n - 1]);
+    return CAPF_OK;
+}
+
 int capf_preprocess(void* stream, const uint8_t* images_bgr, int batch, int height, int width, const float mean[3],
                     const float* std3, int mode, float* images_out, const float* gt_in, float* gt_out, const float* k2d_in,
                     float* k2d_out, const float* kcrop_in, float* kcrop_out) {
@@ -1239,9 +1346,9 @@ int capf_op_info(const capf_handle* h, int index, int batch, const char** name, 
     if (flops) *flops = op.flops_per_frame * batch;
     if (kernel) {                                                  // (the ops of a fused launch are named by that launch)
         const capf::Engine::FusedLaunch f = h->e.fused_leader(index, batch);
-        *kernel = f.kind == capf::Engine::Fusion::BNECK0 ? capf::bneck0_bf16_kernel_name()
-                  : f.kind == capf::Engine::Fusion::BNECK1 ? capf::bneck1_bf16_kernel_name()
-                  : f.kind == capf::Engine::Fusion::PWCHAIN ? (op.bf16 ? capf::gemm_bf16_pwchain_kernel_name() : capf::gemm_f32_pwchain_kernel_name())
+        *kernel = f.kind == capf::Engine::Fusion::BNECK0 ? capf::bneck0_bf16_kernel_name(h->e.f16())
+                  : f.kind == capf::Engine::Fusion::BNECK1 ? capf::bneck1_bf16_kernel_name(h->e.f16())
+                  : f.kind == capf::Engine::Fusion::PWCHAIN ? (op.bf16 ? capf::gemm_bf16_pwchain_kernel_name(h->e.f16()) : capf::gemm_f32_pwchain_kernel_name())
                   : h->e.op_route(op, batch).kernel;
     }
     return CAPF_OK;
@@ -1394,7 +1501,8 @@ int capf_op_describe(const capf_handle* h, int index, capf_op_desc* d) {
         const capf::RowMap* m[3] = {&op.amap, &op.omap, &op.rmap};
         for (int k = 0; k < 3; ++k) { d->maps[k][0] = m[k]->G; d->maps[k][1] = m[k]->S1; d->maps[k][2] = m[k]->S2; d->maps[k][3] = m[k]->off; }
     }
-    const int act_dt = e.bf16() ? 2 : 0;
+    const int dt16 = e.dt16();                                 // what a 16-bit tensor of this handle holds: 2 bf16, 3 fp16
+    const int act_dt = e.b16() ? dt16 : 0;
     d->in_dtype = d->out_dtype = (d->backbone ? act_dt : 0);
     d->H = op.H; d->W = op.W; d->Ho = op.Ho; d->Wo = op.Wo;
     if (op.kind == capf::OP_GEMM) {
@@ -1405,19 +1513,19 @@ int capf_op_describe(const capf_handle* h, int index, capf_op_desc* d) {
         if (op.conv && op.up_in >= 0) { d->up_H = op.up_H; d->up_W = op.up_W; }
         d->mfma_bf16 = (op.bf16 || op.out_bf16) ? 1 : 0;
         if (op.conv) {
-            d->in_dtype = op.in[0] == -2 ? 0 : (op.bf16 ? 2 : 0);
-            d->out_dtype = op.st_f32 ? 0 : (op.bf16 || op.out_bf16) ? 2 : 0;
+            d->in_dtype = op.in[0] == -2 ? 0 : (op.bf16 ? dt16 : 0);
+            d->out_dtype = op.st_f32 ? 0 : (op.bf16 || op.out_bf16) ? dt16 : 0;
             d->p_weight = pk.w[0]; d->p_bn_weight = pk.bn.g;
         } else {
-            d->in_dtype = op.bf16 == 2 ? 2 : 0;
-            d->out_dtype = op.out_bf16 ? 2 : 0;
+            d->in_dtype = op.bf16 == 2 ? dt16 : 0;
+            d->out_dtype = op.out_bf16 ? dt16 : 0;
             d->p_weight = pk.n_lin == 1 ? pk.w[0] : -1;
             d->p_bias = pk.n_lin == 1 ? pk.b[0] : -1;
             d->p_ln_weight = op.ln.w; d->p_ln_bias = op.ln.b;
         }
     } else if (op.kind == capf::OP_LAYERNORM) {
         d->Cin = d->Cout = op.C;
-        d->in_dtype = 0; d->out_dtype = op.out_bf16 ? 2 : 0;
+        d->in_dtype = 0; d->out_dtype = op.out_bf16 ? dt16 : 0;
         d->has_residual = op.aux >= 0;
         d->p_ln_weight = op.ln.w; d->p_ln_bias = op.ln.b;
         d->maps[1][0] = 1; d->maps[1][1] = op.C; d->maps[1][2] = 0; d->maps[1][3] = 0;        // normalised rows are written densely
@@ -1426,7 +1534,7 @@ int capf_op_describe(const capf_handle* h, int index, capf_op_desc* d) {
         d->attn[0] = at.groups; d->attn[1] = at.tokens; d->attn[2] = at.heads; d->attn[3] = at.head_dim;
         d->rows_per_frame = at.groups * at.tokens;
         d->Cin = 3 * at.heads * at.head_dim; d->Cout = at.heads * at.head_dim;
-        d->in_dtype = 0; d->out_dtype = op.out_bf16 ? 2 : 0;
+        d->in_dtype = 0; d->out_dtype = op.out_bf16 ? dt16 : 0;
         d->maps[0][0] = 1; d->maps[0][1] = d->Cin; d->maps[1][0] = 1; d->maps[1][1] = d->Cout;
     } else {
         d->Cin = d->Cout = op.C;
@@ -1434,7 +1542,7 @@ int capf_op_describe(const capf_handle* h, int index, capf_op_desc* d) {
         d->has_residual = op.kind == capf::OP_RESIZE && op.aux >= 0;      // out = resize(in) + aux
         for (int i = 0; i < 4; ++i) d->shift[i] = op.shift[i];
         if (op.kind == capf::OP_FUSE) { d->Ho = op.H; d->Wo = op.W; }
-        if (op.kind == capf::OP_FUSE && d->backbone) d->in_dtype = d->out_dtype = op.bf16 ? 2 : 0;
+        if (op.kind == capf::OP_FUSE && d->backbone) d->in_dtype = d->out_dtype = op.bf16 ? dt16 : 0;
     }
     d->checkpoint = (op.bneck_c3 >= 0 ? op.bneck_c3 : op.region >= 0 ? e.regions[op.region].second : index) + 1;
     return CAPF_OK;

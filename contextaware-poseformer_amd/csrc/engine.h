@@ -162,7 +162,7 @@ struct Op {
     // CAPF_PLAN_BF16_F32_STREAM (Engine::plan_f32_stream): f32s = a bf16 conv with the fp32-stream epilogue (its residual, if any, is fp32);
     // st_f32 = the output is stored fp32 (conv or fuse sum); sh = buffer of its bf16 shadow, what the convs that read it take as operand (-1: none)
     int f32s = 0, st_f32 = 0, sh = -1;
-    int feat_bf16 = 0;            // lifter samplers (embed, ctx_attn, sample_ref, deform_sample): the context maps are stored bf16
+    int feat_bf16 = 0;            // lifter samplers (embed, ctx_attn, sample_ref, deform_sample): how the context maps are stored -- 0 fp32, 1 bf16, 2 fp16
     int bneck_c3 = -1;            // conv1 / conv2 / downsample of a first bottleneck that may run as one kernel with its conv3 (that op's index; plan.cpp bneck0_mark)
     int lane = 0;                 // stream lane inside a fork/join region (0 = the caller's stream)
     int region = -1;              // index of the enclosing fork/join region, -1 outside
@@ -282,11 +282,14 @@ struct Engine {
     bool build();
     void assign_offsets();
     void schedule_regions();
-    bool bf16() const { return cfg.compute_dtype == CAPF_BF16; }
-    bool maps_bf16() const { return bf16() && !plan.f32_stream; }   // the context maps feat0..3 are stored bf16
+    bool b16() const { return cfg.compute_dtype == CAPF_BF16 || cfg.compute_dtype == CAPF_F16; }   // a 16-bit plan: one op list, one set of routing rules ...
+    bool f16() const { return cfg.compute_dtype == CAPF_F16; }   // ... and the element format of its 16-bit kernels, tensors and packs (GemmArgs::f16)
+    int dt16() const { return f16() ? 3 : 2; }                    // capf_tensor's code of a 16-bit tensor of this plan (2 bf16, 3 fp16)
+    bool maps_bf16() const { return b16() && !plan.f32_stream; }   // the context maps feat0..3 are stored 16-bit
+    int feat_fmt() const { return maps_bf16() ? 1 + (int)f16() : 0; }   // ... as the samplers take it: 0 fp32, 1 bf16, 2 fp16
     int depth() const { return cfg.depth > 0 ? cfg.depth : cfg.levels; }   // blocks per group (res_blocks / joint_blocks)
     bool plan_f32_stream(const Tensor feats[4]);
-    size_t act_elems(size_t n) const { return bf16() ? (n + 1) / 2 : n; }   // backbone activation size in float slots
+    size_t act_elems(size_t n) const { return b16() ? (n + 1) / 2 : n; }   // backbone activation size in float slots
     void use(int buf);   // mark buffer as read by the op being appended
     void push(Op op);    // append an op, tagging it with the current lane / region
     void fork(int n);    // open a region of n independent lanes (independent branches run on side streams)

@@ -23,9 +23,27 @@
 //   igemm_bf16_stem_kernel (+ igemm_bf16_smallc_kernel)   Cin = 3 stem under compute_dtype = bf16
 #include <stdlib.h>
 
+#include <map>
+#include <mutex>
+#include <string>
+
 #include "kernels.h"
 
 namespace capf {
+const char* fmt_kernel_name(const char* bf16_name, int f16) {
+    if (!f16) return bf16_name;
+    static std::mutex mu;
+    static std::map<std::string, std::string> names;       // (node addresses are stable: the c_str() handed out stays valid)
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = names.find(bf16_name);
+    if (it == names.end()) {
+        std::string n = bf16_name;
+        for (size_t at = n.find("bf16"); at != std::string::npos; at = n.find("bf16", at)) n.erase(at, 1);
+        it = names.emplace(bf16_name, n).first;
+    }
+    return it->second.c_str();
+}
+
 #ifdef CAPF_DIAG   // (diagnosis build) per-block stamps {t_entry, t_prologue_done, t_loop_done, t_stores_issued, t_exit, realtime_entry, load_wait_ticks, realtime_exit}
 __device__ unsigned long long capf_bf16_timeline[8192 * 8];
 #define B16_STAMP(var) var = __builtin_amdgcn_s_memtime()
@@ -36,7 +54,6 @@ __device__ unsigned long long capf_bf16_timeline[8192 * 8];
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
 static constexpr int BKH = 64;     // K chunk in bf16 elements = 128 B per tile row
@@ -44,8 +61,6 @@ static constexpr int BKH = 64;     // K chunk in bf16 elements = 128 B per tile 
 __device__ __forceinline__ int fast_div_b(int n, FastDiv d) {
     return (int)((__umulhi((unsigned)n, d.mul) + (unsigned)n) >> d.shift);
 }
-__device__ __forceinline__ unsigned short f2bf(float f) { return to_bf16(f); }
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
 
 typedef __attribute__((address_space(3))) void* lptr_t;
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
@@ -70,7 +85,7 @@ __device__ __forceinline__ long rowmap_b(const RowMap& r, int m) {
 
 // F32S: the epilogue of a CAPF_PLAN_BF16_F32_STREAM conv (GemmArgs::f32s): fp32 residual, fp32 result + its bf16 shadow (out_f32) or a bf16
 // result -- same accumulators, same arithmetic; the main loop is the default one
-template <int BM, int BN, int WM, int WN, int S, bool OUTF32 = false, bool GELU = false, bool UPADD = false, bool F32S = false>
+template <int BM, int BN, int WM, int WN, int S, bool OUTF32 = false, bool GELU = false, bool UPADD = false, bool F32S = false, class F = Bf16Fmt>
 __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid, unsigned short* __restrict__ lds) {
     constexpr int WAVES_N = BN / WN;
     constexpr int TM = WM / 32, TN = WN / 32;
@@ -279,17 +294,17 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
         // blocks use the matrix pipe meanwhile.  At bf16 MFMA speed a 64-deep chunk is only 256 matrix cycles per wave
         // against ~2500 cycles of load latency under traffic: what matters is how many chunks a CU has in flight (5 of 6
         // slots here; 3 of 6 with the two-stage ring and three blocks).
-        bf16x8 af[2][TM], bfr[2][TN];
+        typename F::x8 af[2][TM], bfr[2][TN];
         auto read_frags = [&](int step, int buf) {
             const unsigned short* As = lds;
             const unsigned short* Bs = As + BM * BKH;
             const int q = ((step * 2) + fhalf) ^ fsw;
 #pragma unroll
             for (int i = 0; i < TM; ++i)
-                af[buf][i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + frow) * BKH + q * 8]));
+                af[buf][i] = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + frow) * BKH + q * 8]));
 #pragma unroll
             for (int j = 0; j < TN; ++j)
-                bfr[buf][j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + j * 32 + frow) * BKH + q * 8]));
+                bfr[buf][j] = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + j * 32 + frow) * BKH + q * 8]));
         };
         B16_STAMP(dbg_t1);
         auto chunk = [&](int c) {
@@ -312,7 +327,7 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[fb][j], af[fb][i], acc[i][j], 0, 0, 0);
+                        acc[i][j] = F::mfma(bfr[fb][j], af[fb][i], acc[i][j]);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();              // every wave has read the stage: the next chunk may overwrite it
@@ -331,17 +346,17 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
     prepare(S - 1);
     // fragments are double buffered: the reads of k-step s+1 (or, at the chunk boundary, of the next chunk's
     // step 0) are issued before the MFMAs of step s
-    bf16x8 af[2][TM], bfr[2][TN];
+    typename F::x8 af[2][TM], bfr[2][TN];
     auto read_frags = [&](int stage, int step, int buf) {
         const unsigned short* As = lds + stage * STAGE;
         const unsigned short* Bs = As + BM * BKH;
         const int q = ((step * 2) + fhalf) ^ fsw;
 #pragma unroll
         for (int i = 0; i < TM; ++i)
-            af[buf][i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + frow) * BKH + q * 8]));
+            af[buf][i] = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + frow) * BKH + q * 8]));
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-            bfr[buf][j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + j * 32 + frow) * BKH + q * 8]));
+            bfr[buf][j] = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + j * 32 + frow) * BKH + q * 8]));
     };
     wait_vmcnt_b<(S - 2) * NLOAD>();
     __builtin_amdgcn_s_barrier();
@@ -364,7 +379,7 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[fb][j], af[fb][i], acc[i][j], 0, 0, 0);
+                    acc[i][j] = F::mfma(bfr[fb][j], af[fb][i], acc[i][j]);
             if (step < 2) {
 #pragma unroll
                 for (int f = 0; f < PER_STEP; ++f) {
@@ -503,7 +518,7 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
                             const float xa = q < 2 ? x0[2 * q] : x1[2 * q - 4], xb = q < 2 ? x0[2 * q + 1] : x1[2 * q - 3];
                             const float ba = q < 2 ? bb[j][0][2 * q] : bb[j][1][2 * q - 4];
                             const float bc = q < 2 ? bb[j][0][2 * q + 1] : bb[j][1][2 * q - 3];
-                            float ra = __uint_as_float(rw << 16), rb = __uint_as_float(rw & 0xFFFF0000u);
+                            float ra = F::lo(rw), rb = F::hi(rw);
                             if constexpr (F32S) {
                                 ra = __uint_as_float(q < 2 ? rr[i][j][h][2 * q] : rr2[i][j][h][2 * q - 4]);
                                 rb = __uint_as_float(q < 2 ? rr[i][j][h][2 * q + 1] : rr2[i][j][h][2 * q - 3]);
@@ -512,12 +527,12 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
                             if constexpr (UPADD) {
                                 const float lh1 = ulh[h], lw1 = ulw[h], lh0 = 1.f - lh1, lw0 = 1.f - lw1;
                                 const unsigned q00 = uq[h][j][0][q], q01 = uq[h][j][1][q], q10 = uq[h][j][2][q], q11 = uq[h][j][3][q];
-                                va += lh0 * (lw0 * __uint_as_float(q00 << 16) + lw1 * __uint_as_float(q01 << 16)) +
-                                      lh1 * (lw0 * __uint_as_float(q10 << 16) + lw1 * __uint_as_float(q11 << 16));
-                                vb += lh0 * (lw0 * __uint_as_float(q00 & 0xFFFF0000u) + lw1 * __uint_as_float(q01 & 0xFFFF0000u)) +
-                                      lh1 * (lw0 * __uint_as_float(q10 & 0xFFFF0000u) + lw1 * __uint_as_float(q11 & 0xFFFF0000u));
+                                va += lh0 * (lw0 * F::lo(q00) + lw1 * F::lo(q01)) +
+                                      lh1 * (lw0 * F::lo(q10) + lw1 * F::lo(q11));
+                                vb += lh0 * (lw0 * F::hi(q00) + lw1 * F::hi(q01)) +
+                                      lh1 * (lw0 * F::hi(q10) + lw1 * F::hi(q11));
                             }
-                            o[q] = pack_bf16x2(va, vb);
+                            o[q] = F::pack2(va, vb);
                             if constexpr (F32S) { y32[q >> 1][(2 * q) & 3] = va; y32[q >> 1][(2 * q + 1) & 3] = vb; }
                         }
                         __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, piece_off(i, j, h, (int)p.omap.S1), 0, 0);
@@ -546,13 +561,13 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
                             const float x = e < 4 ? x0[e & 3] : x1[e & 3];
                             const float bsv = p.bias ? p.bias[n + e] : 0.f;
                             const long ri = (long)m * p.rmap.S1 + p.rmap.off + n + e, oi = (long)m * p.omap.S1 + p.omap.off + n + e;
-                            const float rsv = Rs ? (F32S ? p.res[ri] : bf2f(Rs[ri])) : 0.f;
+                            const float rsv = Rs ? (F32S ? p.res[ri] : F::widen(Rs[ri])) : 0.f;
                             const float v = finish(x + bsv + rsv);
                             if (F32S && p.out_f32) {
                                 p.out[oi] = v;
-                                if (Y16) Y16[oi] = f2bf(v);
+                                if (Y16) Y16[oi] = F::narrow(v);
                             } else {
-                                Out[oi] = f2bf(v);
+                                Out[oi] = F::narrow(v);
                             }
                         }
                     }
@@ -583,7 +598,7 @@ __device__ __forceinline__ void igemm_bf16_tile(const GemmArgs& p, const int bid
 // TN = 32-column blocks per tile (tile = 126 output pixels x 32 TN channels); the four waves split the 128 staged rows, each
 // computing 32 rows x 32 TN columns (1 A + TN B fragment reads per TN MFMAs).  LDS: (128 + 96 TN) x CW halves, at least the
 // epilogue's 18 KiB.
-template <int CW, int TM, int TN>
+template <int CW, int TM, int TN, class F>
 __device__ __forceinline__ void igemm_bf16_rh_tile(const GemmArgs& p, const int bid, unsigned short* __restrict__ lds) {
     constexpr int BMS = 128 * TM, BMO = BMS - 2, BN = 32 * TN;     // staged rows, output pixels, output channels per tile
     constexpr int QPR = CW / 8;                            // 16-byte quads per LDS row
@@ -713,7 +728,7 @@ __device__ __forceinline__ void igemm_bf16_rh_tile(const GemmArgs& p, const int 
                     rr[i][j][h] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, piece_off(i, j, h, (int)p.rmap.S1), 0, 0);
     };
 
-    bf16x8 af[2][TM], bfr[2][TN];
+    typename F::x8 af[2][TM], bfr[2][TN];
     auto read_frags = [&](int u, int buf) {                // u = kw * KS + k-step
         const int kw = u / KS, st = u - kw * KS;
         const int lq = st * 2 + fhalf;
@@ -722,11 +737,11 @@ __device__ __forceinline__ void igemm_bf16_rh_tile(const GemmArgs& p, const int 
             const int r = wm0 + i * 32 + frow + kw;
             f32x4 v = *reinterpret_cast<const f32x4*>(&lds[(r * QPR + (lq ^ swz(r))) * 8]);
             if ((kw == 0 && zl[i]) || (kw == 2 && zr[i])) v = f32x4{0.f, 0.f, 0.f, 0.f};
-            af[buf][i] = __builtin_bit_cast(bf16x8, v);
+            af[buf][i] = __builtin_bit_cast(typename F::x8, v);
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-            bfr[buf][j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(
+            bfr[buf][j] = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(
                                                          &lds[BOFF + ((kw * BN + j * 32 + frow) * QPR + (lq ^ b_sw)) * 8]));
     };
     B16_STAMP(dbg_t1);
@@ -747,7 +762,7 @@ __device__ __forceinline__ void igemm_bf16_rh_tile(const GemmArgs& p, const int 
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[u & 1][j], af[u & 1][i], acc[i][j], 0, 0, 0);
+                    acc[i][j] = F::mfma(bfr[u & 1][j], af[u & 1][i], acc[i][j]);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                      // every wave has read the stage: the next superchunk may overwrite it
@@ -790,7 +805,7 @@ __device__ __forceinline__ void igemm_bf16_rh_tile(const GemmArgs& p, const int 
                     for (int q = 0; q < 4; ++q) {
                         const unsigned rw = rr[i][j][h][q];
                         const float xa = q < 2 ? x0[2 * q] : x1[2 * q - 4], xb = q < 2 ? x0[2 * q + 1] : x1[2 * q - 3];
-                        o[q] = pack_bf16x2(finish(xa + __uint_as_float(rw << 16)), finish(xb + __uint_as_float(rw & 0xFFFF0000u)));
+                        o[q] = F::pack2(finish(xa + F::lo(rw)), finish(xb + F::hi(rw)));
                     }
                     __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, piece_off(i, j, h, (int)p.omap.S1), 0, 0);
                 }
@@ -810,8 +825,8 @@ __device__ __forceinline__ void igemm_bf16_rh_tile(const GemmArgs& p, const int 
                     if (!row_ok(il, m)) continue;
                     for (int e = 0; e < 8 && n + e < p.N; ++e) {
                         const float x = e < 4 ? x0[e & 3] : x1[e & 3];
-                        const float rsv = Rs ? bf2f(Rs[(long)m * p.rmap.S1 + p.rmap.off + n + e]) : 0.f;
-                        Out[(long)m * p.omap.S1 + p.omap.off + n + e] = f2bf(finish(x + rsv));
+                        const float rsv = Rs ? F::widen(Rs[(long)m * p.rmap.S1 + p.rmap.off + n + e]) : 0.f;
+                        Out[(long)m * p.omap.S1 + p.omap.off + n + e] = F::narrow(finish(x + rsv));
                     }
                 }
             }
@@ -833,22 +848,22 @@ __device__ __forceinline__ int xcd_remap_b(int b, int nblk) {   // see igemm_f32
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
 }
 
-template <int BM, int BN, int WM, int WN, int S, bool OUTF32 = false, bool GELU = false, bool UPADD = false>
+template <int BM, int BN, int WM, int WN, int S, bool OUTF32 = false, bool GELU = false, bool UPADD = false, class F = Bf16Fmt>
 __global__ __launch_bounds__(256) void igemm_bf16_kernel(GemmArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int HALVES = S * (BM + BN) * BKH < 4 * 32 * 36 * 2 ? 4 * 32 * 36 * 2 : S * (BM + BN) * BKH;   // >= the epilogue's 18 KiB
     __shared__ __attribute__((aligned(16))) unsigned short lds[HALVES];
-    igemm_bf16_tile<BM, BN, WM, WN, S, OUTF32, GELU, UPADD>(p, xcd_remap_b(blockIdx.x, gridDim.x), lds);
+    igemm_bf16_tile<BM, BN, WM, WN, S, OUTF32, GELU, UPADD, false, F>(p, xcd_remap_b(blockIdx.x, gridDim.x), lds);
 #endif
 }
 
 // the same conv with the fp32-stream epilogue (GemmArgs::f32s, CAPF_PLAN_BF16_F32_STREAM)
-template <int BM, int BN, int WM, int WN, int S>
+template <int BM, int BN, int WM, int WN, int S, class F>
 __global__ __launch_bounds__(256) void igemm_bf16_stream_kernel(GemmArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int HALVES = S * (BM + BN) * BKH < 4 * 32 * 36 * 2 ? 4 * 32 * 36 * 2 : S * (BM + BN) * BKH;
     __shared__ __attribute__((aligned(16))) unsigned short lds[HALVES];
-    igemm_bf16_tile<BM, BN, WM, WN, S, false, false, false, true>(p, xcd_remap_b(blockIdx.x, gridDim.x), lds);
+    igemm_bf16_tile<BM, BN, WM, WN, S, false, false, false, true, F>(p, xcd_remap_b(blockIdx.x, gridDim.x), lds);
 #endif
 }
 
@@ -860,6 +875,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_stream_kernel(GemmArgs p) {
 // =====================================================================================================
 [[maybe_unused]] static constexpr int SPITCH = 40;          // halves per LDS row: 32 k-values + 8 pad (80 B: 16-byte aligned fragment reads)
 
+template <class F>
 __global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BM = 128, BN = 64, WM = 64, WN = 32, SBK = 32;
@@ -934,27 +950,27 @@ __global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) {
 #pragma unroll
         for (int i = 0; i < RA; ++i)
             *reinterpret_cast<u32x2*>(&As[(srow + 32 * i) * SPITCH + kq]) =
-                u32x2{pack_bf16x2(a_reg[i][0], a_reg[i][1]), pack_bf16x2(a_reg[i][2], a_reg[i][3])};
+                u32x2{F::pack2(a_reg[i][0], a_reg[i][1]), F::pack2(a_reg[i][2], a_reg[i][3])};
 #pragma unroll
         for (int i = 0; i < RB; ++i)
             *reinterpret_cast<u32x2*>(&Bs[(srow + 32 * i) * SPITCH + kq]) =
-                u32x2{pack_bf16x2(b_reg[i][0], b_reg[i][1]), pack_bf16x2(b_reg[i][2], b_reg[i][3])};
+                u32x2{F::pack2(b_reg[i][0], b_reg[i][1]), F::pack2(b_reg[i][2], b_reg[i][3])};
         __syncthreads();
         if (c + 1 < nchunks) load_chunk(c + 1);
 #pragma unroll
         for (int step = 0; step < SBK / 16; ++step) {
-            bf16x8 af[TM], bfr[TN];
+            typename F::x8 af[TM], bfr[TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i)
-                af[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + frow) * SPITCH + step * 16 + fhalf * 8]));
+                af[i] = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + frow) * SPITCH + step * 16 + fhalf * 8]));
 #pragma unroll
             for (int j = 0; j < TN; ++j)
-                bfr[j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + j * 32 + frow) * SPITCH + step * 16 + fhalf * 8]));
+                bfr[j] = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + j * 32 + frow) * SPITCH + step * 16 + fhalf * 8]));
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
+                    acc[i][j] = F::mfma(bfr[j], af[i], acc[i][j]);
         }
         __syncthreads();
     }
@@ -976,7 +992,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) {
                 for (int e = 0; e < 4; ++e) {
                     float t = acc[i][j][4 * g + e] + (p.bias ? p.bias[n + e] : 0.f);
                     if (p.act == ACT_RELU) t = relu_f(t);
-                    v[e] = f2bf(t);
+                    v[e] = F::narrow(t);
                 }
                 *reinterpret_cast<u16x4*>(Out + o_row + n) = v;
             }
@@ -988,7 +1004,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) {
 // image (and in the (kh, kw, c)-ordered weights), so a thread fetches one such run with 16-byte loads (dword-aligned
 // addresses) instead of 21 / 9 scalar gathers, zeroes what lies outside the image, and writes it as bf16 into an LDS tile
 // whose K axis is (kh, 24 | 16): the whole K of a 128 x 64 tile is staged once (no chunk loop), then 11 / 3 MFMA k-steps.
-template <int KS, int BM>
+template <int KS, int BM, class F>
 __global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BN = 64, WM = BM / 2, WN = 32, TM = WM / 32;
@@ -1012,7 +1028,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
         unsigned pk[PKH / 2];
 #pragma unroll
         for (int e = 0; e < PKH / 2; ++e)
-            pk[e] = pack_bf16x2(2 * e < NX4 * 4 ? v[2 * e] : 0.f, 2 * e + 1 < NX4 * 4 ? v[2 * e + 1] : 0.f);
+            pk[e] = F::pack2(2 * e < NX4 * 4 ? v[2 * e] : 0.f, 2 * e + 1 < NX4 * 4 ? v[2 * e + 1] : 0.f);
 #pragma unroll
         for (int q = 0; q < PKH / 8; ++q)
             *reinterpret_cast<u32x4*>(dst + kh * PKH + q * 8) = u32x4{pk[4 * q], pk[4 * q + 1], pk[4 * q + 2], pk[4 * q + 3]};
@@ -1074,11 +1090,11 @@ __global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
     const int frow = lane & 31, fhalf = lane >> 5;
 #pragma unroll
     for (int step = 0; step < KP / 16; ++step) {
-        const bf16x8 bfr = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + frow) * PITCH + step * 16 + fhalf * 8]));
+        const typename F::x8 bfr = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + frow) * PITCH + step * 16 + fhalf * 8]));
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-            const bf16x8 af = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + frow) * PITCH + step * 16 + fhalf * 8]));
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr, af, acc[i], 0, 0, 0);
+            const typename F::x8 af = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + frow) * PITCH + step * 16 + fhalf * 8]));
+            acc[i] = F::mfma(bfr, af, acc[i]);
         }
     }
     // transposed accumulator (lane = row m, register group g = channels 8 g + 4 fhalf .. + 3): 8-byte stores
@@ -1100,7 +1116,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
                 t[e] = acc[i][4 * g + e] + bv[e];
                 if (p.act == ACT_RELU) t[e] = relu_f(t[e]);
             }
-            *reinterpret_cast<u32x2*>(Out + (long)m * p.omap.S1 + p.omap.off + n) = u32x2{pack_bf16x2(t[0], t[1]), pack_bf16x2(t[2], t[3])};
+            *reinterpret_cast<u32x2*>(Out + (long)m * p.omap.S1 + p.omap.off + n) = u32x2{F::pack2(t[0], t[1]), F::pack2(t[2], t[3])};
         }
     }
 #endif
@@ -1118,7 +1134,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
 // contiguous per row.  XCD-aware tile order: each XCD walks its own contiguous eighth of the tiles, so the 7 / 3 input rows
 // that vertically adjacent tiles share are fetched into ONE L2.  Only the handful of runs at the very start of the tensor (negative
 // offsets cannot be expressed) are patched element-wise by the blocks that own those pixels.
-template <int KS>
+template <int KS, class F>
 __global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs p, int ntiles) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BM = 64, BN = 64;
@@ -1150,13 +1166,13 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs
         unsigned pk[PKH / 2];
         if (mask == (1u << RUN) - 1u) {              // interior pixel (all but ~1 run in 70): no per-element selects
 #pragma unroll
-            for (int e = 0; e < PKH / 2; ++e) pk[e] = pack_bf16x2(2 * e < RUN ? val(2 * e) : 0.f, 2 * e + 1 < RUN ? val(2 * e + 1) : 0.f);
+            for (int e = 0; e < PKH / 2; ++e) pk[e] = F::pack2(2 * e < RUN ? val(2 * e) : 0.f, 2 * e + 1 < RUN ? val(2 * e + 1) : 0.f);
         } else {
 #pragma unroll
             for (int e = 0; e < PKH / 2; ++e) {
                 const float a = 2 * e < RUN && ((mask >> (2 * e)) & 1u) ? val(2 * e) : 0.f;
                 const float b = 2 * e + 1 < RUN && ((mask >> (2 * e + 1)) & 1u) ? val(2 * e + 1) : 0.f;
-                pk[e] = pack_bf16x2(a, b);
+                pk[e] = F::pack2(a, b);
             }
         }
 #pragma unroll
@@ -1253,7 +1269,7 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs
                     const int wi = wo * p.stride - p.pad + e / 3;
                     float v = 0.f;
                     if (e < RUN && (unsigned)wi < (unsigned)p.W) v = p.A[wi * 3 + e % 3];
-                    As[(m - m0) * PITCH + kh * PKH + e] = f2bf(v);
+                    As[(m - m0) * PITCH + kh * PKH + e] = F::narrow(v);
                 }
             }
         }
@@ -1265,9 +1281,9 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
         for (int step = 0; step < KP / 16; ++step) {
-            const bf16x8 bfr = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + frow) * PITCH + step * 16 + fhalf * 8]));
-            const bf16x8 af = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + frow) * PITCH + step * 16 + fhalf * 8]));
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr, af, acc, 0, 0, 0);
+            const typename F::x8 bfr = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + frow) * PITCH + step * 16 + fhalf * 8]));
+            const typename F::x8 af = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + frow) * PITCH + step * 16 + fhalf * 8]));
+            acc = F::mfma(bfr, af, acc);
         }
         // transposed accumulator (lane = row, register group g = channels 8 g + 4 fhalf ..) -> LDS -> 8 channels of a row per lane
         __builtin_amdgcn_wave_barrier();
@@ -1288,7 +1304,7 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs
 #pragma unroll
                 for (int e = 0; e < 8; ++e) t[e] = relu_f(t[e]);
             }
-            const u32x4 o = u32x4{pack_bf16x2(t[0], t[1]), pack_bf16x2(t[2], t[3]), pack_bf16x2(t[4], t[5]), pack_bf16x2(t[6], t[7])};
+            const u32x4 o = u32x4{F::pack2(t[0], t[1]), F::pack2(t[2], t[3]), F::pack2(t[4], t[5]), F::pack2(t[6], t[7])};
             __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, (m0 + ml < p.M && nl < p.N) ? (unsigned)(ml * (int)p.omap.S1 + nl) * 2u : OOB, 0, 0);
         }
         __syncthreads();                              // every wave has read As: the next tile's runs may overwrite it
@@ -1318,8 +1334,8 @@ static bool stem_stream_ok(const GemmArgs& a) {
 }
 
 const char* gemm_bf16_smallc_kernel_name(const GemmArgs& a) {
-    if (!stem_runs_ks(a)) return "igemm_bf16_smallc<w4,128x64>";
-    return stem_stream_ok(a) ? "igemm_bf16_stem_stream<w4,64x64>" : "igemm_bf16_stem<w4,128x64>";
+    if (!stem_runs_ks(a)) return fmt_kernel_name("igemm_bf16_smallc<w4,128x64>", a.f16);
+    return fmt_kernel_name(stem_stream_ok(a) ? "igemm_bf16_stem_stream<w4,64x64>" : "igemm_bf16_stem<w4,128x64>", a.f16);
 }
 
 hipError_t launch_gemm_bf16_smallc(const GemmArgs& a_in, hipStream_t s) {
@@ -1332,25 +1348,33 @@ hipError_t launch_gemm_bf16_smallc(const GemmArgs& a_in, hipStream_t s) {
         const int ntiles = (a.M + 63) / 64;
         int blocks = 512;                              // two per CU
         while (blocks > 8 && blocks / 2 >= ntiles) blocks /= 2;
-        if (ks == 7) hipLaunchKernelGGL((igemm_bf16_stem_stream_kernel<7>), dim3(blocks), dim3(256), 0, s, a, ntiles);
-        else hipLaunchKernelGGL((igemm_bf16_stem_stream_kernel<3>), dim3(blocks), dim3(256), 0, s, a, ntiles);
+        with_fmt(a.f16, [&](auto f) {
+            using F = decltype(f);
+            if (ks == 7) hipLaunchKernelGGL((igemm_bf16_stem_stream_kernel<7, F>), dim3(blocks), dim3(256), 0, s, a, ntiles);
+            else hipLaunchKernelGGL((igemm_bf16_stem_stream_kernel<3, F>), dim3(blocks), dim3(256), 0, s, a, ntiles);
+            return 0;
+        });
         return hipGetLastError();
     }
     const dim3 grid(((a.M + 127) / 128) * ((a.N + 63) / 64));
     // (64-pixel tiles -- 47 KiB, three blocks per CU for the 7x7 -- measured slower: 0.50 -> 0.59 ms for CPN, 0.30 -> 0.35 for HRNet)
-    if (ks == 7) hipLaunchKernelGGL((igemm_bf16_stem_kernel<7, 128>), grid, dim3(256), 0, s, a);
-    else if (ks == 3) hipLaunchKernelGGL((igemm_bf16_stem_kernel<3, 128>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(igemm_bf16_smallc_kernel, grid, dim3(256), 0, s, a);
+    with_fmt(a.f16, [&](auto f) {
+        using F = decltype(f);
+        if (ks == 7) hipLaunchKernelGGL((igemm_bf16_stem_kernel<7, 128, F>), grid, dim3(256), 0, s, a);
+        else if (ks == 3) hipLaunchKernelGGL((igemm_bf16_stem_kernel<3, 128, F>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(igemm_bf16_smallc_kernel<F>, grid, dim3(256), 0, s, a);
+        return 0;
+    });
     return hipGetLastError();
 }
 
 static constexpr int rh_lds_halves(int cw, int tm, int tn) { return (128 * tm + 96 * tn) * cw < 9216 ? 9216 : (128 * tm + 96 * tn) * cw; }
 
-template <int CW, int TM, int TN>
+template <int CW, int TM, int TN, class F>
 __global__ __launch_bounds__(256, TM == 1 ? 4 : 3) void igemm_bf16_rh_kernel(GemmArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) unsigned short lds[rh_lds_halves(CW, TM, TN)];
-    igemm_bf16_rh_tile<CW, TM, TN>(p, xcd_remap_b(blockIdx.x, gridDim.x), lds);
+    igemm_bf16_rh_tile<CW, TM, TN, F>(p, xcd_remap_b(blockIdx.x, gridDim.x), lds);
 #endif
 }
 
@@ -1393,17 +1417,21 @@ hipError_t launch_gemm_bf16_rh(const GemmArgs& a_in, hipStream_t s) {
     // TM = 2 (254-pixel tiles, wave tile 64 x 32 TN: a third less LDS traffic per MFMA, 2-3 blocks per CU) measured equal or slower
     // on every shape (48 ch 411 -> 398 TFLOP/s, 64 ch 666 -> 527 at CW 64 / 627 at CW 32, 128 ch 806 -> 793): not instantiated
     const dim3 grid(((a.M + 125) / 126) * ((a.N + 32 * tn - 1) / (32 * tn)));
-#define RH_CASE(CW_, TN_) case CW_ * 10 + TN_: hipLaunchKernelGGL((igemm_bf16_rh_kernel<CW_, 1, TN_>), grid, dim3(256), 0, s, a); break;
-    switch (cw * 10 + tn) {
-        RH_CASE(64, 1) RH_CASE(64, 2) RH_CASE(48, 1) RH_CASE(48, 2) RH_CASE(48, 3) RH_CASE(32, 1) RH_CASE(32, 2)
-        default: return hipErrorInvalidValue;
-    }
+#define RH_CASE(CW_, TN_) case CW_ * 10 + TN_: hipLaunchKernelGGL((igemm_bf16_rh_kernel<CW_, 1, TN_, F>), grid, dim3(256), 0, s, a); return true;
+    const bool known = with_fmt(a.f16, [&](auto f) {
+        using F = decltype(f);
+        switch (cw * 10 + tn) {
+            RH_CASE(64, 1) RH_CASE(64, 2) RH_CASE(48, 1) RH_CASE(48, 2) RH_CASE(48, 3) RH_CASE(32, 1) RH_CASE(32, 2)
+            default: return false;
+        }
+    });
 #undef RH_CASE
-    return hipGetLastError();
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // BN fold + re-layout of a 3x3 conv weight for the row-halo kernel: Wp[n][((kh * (Cin / CW) + cc) * 3 + kw) * CW + c] =
 // bf16(w[n][cc * CW + c][kh][kw] * gamma[n] / sqrt(var[n] + eps));  bias as launch_pack_conv
+template <class F>
 __global__ void pack_conv_bf16_rh_kernel(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ beta,
                                          const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                          unsigned short* __restrict__ Wp, float* __restrict__ bias, int Cout, int Cin, int CW) {
@@ -1417,17 +1445,20 @@ __global__ void pack_conv_bf16_rh_kernel(const float* __restrict__ w, const floa
         const int kw = k % 3; k /= 3;
         const int cc = k % ncc, kh = k / ncc;
         const float sc = bn_scale(gamma, var, eps, n);
-        Wp[i] = f2bf(w[(((long)n * Cin + cc * CW + c) * 3 + kh) * 3 + kw] * sc);
+        Wp[i] = F::narrow(w[(((long)n * Cin + cc * CW + c) * 3 + kh) * 3 + kw] * sc);
         if (first && bias) bias[n] = bn_bias(gamma, beta, mean, sc, n);
     }
 }
 
 hipError_t launch_pack_conv_bf16_rh(const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
-                                    float eps, void* Wp_bf16, float* bias, int Cout, int Cin, int CW, hipStream_t s) {
+                                    float eps, void* Wp_bf16, float* bias, int Cout, int Cin, int CW, hipStream_t s, int f16) {
     if ((CW != 64 && CW != 48 && CW != 32) || Cin % CW != 0) return hipErrorInvalidValue;
     const long total = (long)Cout * 9 * Cin;
-    hipLaunchKernelGGL(pack_conv_bf16_rh_kernel, dim3(grid_1d(total)), dim3(256), 0, s, w, gamma, beta, mean, var,
-                       eps, static_cast<unsigned short*>(Wp_bf16), bias, Cout, Cin, CW);
+    with_fmt(f16, [&](auto f) {
+        hipLaunchKernelGGL(pack_conv_bf16_rh_kernel<decltype(f)>, dim3(grid_1d(total)), dim3(256), 0, s, w, gamma, beta, mean, var,
+                           eps, static_cast<unsigned short*>(Wp_bf16), bias, Cout, Cin, CW);
+        return 0;
+    });
     return hipGetLastError();
 }
 
@@ -1446,6 +1477,7 @@ static_assert(sizeof(GroupArgsB) == MAXG * sizeof(GemmArgs) + (3 * MAXG + 2) * s
 // -6.5 % (HRNet-48 B=256), -2 % (CPN), -8 % (HRNet-32 B=64); 64x64 + 128x32 tiles only in 40 KiB / 4 blocks per CU -9 %, -1 %, 0 %.
 #define GROUP_LDS_HALVES (CAPF_BF16_GROUP_STAGES * (128 + 64) * BKH)
 
+template <class F>
 __global__ __launch_bounds__(256) void igemm_bf16_group_kernel(GroupArgsB ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) unsigned short lds[GROUP_LDS_HALVES];
@@ -1453,14 +1485,15 @@ __global__ __launch_bounds__(256) void igemm_bf16_group_kernel(GroupArgsB ga) {
     if (!t.live) return;
     const GemmArgs& p = ga.g[t.pi];
     switch (ga.cfg[t.pi]) {
-        case 0: igemm_bf16_tile<128, 64, 64, 32, CAPF_BF16_GROUP_STAGES>(p, t.bid, lds); break;
-        case 1: igemm_bf16_tile<64, 64, 32, 32, CAPF_BF16_GROUP_STAGES + 1>(p, t.bid, lds); break;
-        default: igemm_bf16_tile<128, 32, 32, 32, CAPF_BF16_GROUP_STAGES>(p, t.bid, lds); break;
+        case 0: igemm_bf16_tile<128, 64, 64, 32, CAPF_BF16_GROUP_STAGES, false, false, false, false, F>(p, t.bid, lds); break;
+        case 1: igemm_bf16_tile<64, 64, 32, 32, CAPF_BF16_GROUP_STAGES + 1, false, false, false, false, F>(p, t.bid, lds); break;
+        default: igemm_bf16_tile<128, 32, 32, 32, CAPF_BF16_GROUP_STAGES, false, false, false, false, F>(p, t.bid, lds); break;
     }
 #endif
 }
 
 // ... with the fp32-stream epilogue (every problem of the launch has GemmArgs::f32s)
+template <class F>
 __global__ __launch_bounds__(256) void igemm_bf16_group_stream_kernel(GroupArgsB ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) unsigned short lds[GROUP_LDS_HALVES];
@@ -1468,14 +1501,15 @@ __global__ __launch_bounds__(256) void igemm_bf16_group_stream_kernel(GroupArgsB
     if (!t.live) return;
     const GemmArgs& p = ga.g[t.pi];
     switch (ga.cfg[t.pi]) {
-        case 0: igemm_bf16_tile<128, 64, 64, 32, CAPF_BF16_GROUP_STAGES, false, false, false, true>(p, t.bid, lds); break;
-        case 1: igemm_bf16_tile<64, 64, 32, 32, CAPF_BF16_GROUP_STAGES + 1, false, false, false, true>(p, t.bid, lds); break;
-        default: igemm_bf16_tile<128, 32, 32, 32, CAPF_BF16_GROUP_STAGES, false, false, false, true>(p, t.bid, lds); break;
+        case 0: igemm_bf16_tile<128, 64, 64, 32, CAPF_BF16_GROUP_STAGES, false, false, false, true, F>(p, t.bid, lds); break;
+        case 1: igemm_bf16_tile<64, 64, 32, 32, CAPF_BF16_GROUP_STAGES + 1, false, false, false, true, F>(p, t.bid, lds); break;
+        default: igemm_bf16_tile<128, 32, 32, 32, CAPF_BF16_GROUP_STAGES, false, false, false, true, F>(p, t.bid, lds); break;
     }
 #endif
 }
 
 // ping-pong variant of the grouped kernel: one stage per block, 24 KiB, up to 5 blocks per CU (register cap 102)
+template <class F>
 __global__ __launch_bounds__(256, 5) void igemm_bf16_group_pp_kernel(GroupArgsB ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) unsigned short lds[(128 + 64) * BKH];
@@ -1483,14 +1517,15 @@ __global__ __launch_bounds__(256, 5) void igemm_bf16_group_pp_kernel(GroupArgsB 
     if (!t.live) return;
     const GemmArgs& p = ga.g[t.pi];
     switch (ga.cfg[t.pi]) {
-        case 0: igemm_bf16_tile<128, 64, 64, 32, 1>(p, t.bid, lds); break;
-        case 1: igemm_bf16_tile<64, 64, 32, 32, 1>(p, t.bid, lds); break;
-        default: igemm_bf16_tile<128, 32, 32, 32, 1>(p, t.bid, lds); break;
+        case 0: igemm_bf16_tile<128, 64, 64, 32, 1, false, false, false, false, F>(p, t.bid, lds); break;
+        case 1: igemm_bf16_tile<64, 64, 32, 32, 1, false, false, false, false, F>(p, t.bid, lds); break;
+        default: igemm_bf16_tile<128, 32, 32, 32, 1, false, false, false, false, F>(p, t.bid, lds); break;
     }
 #endif
 }
 
 // (4 blocks per CU, not 5: the fp32 residual and result pieces do not fit the 5-block register cap of 102 without spilling)
+template <class F>
 __global__ __launch_bounds__(256, 4) void igemm_bf16_group_pp_stream_kernel(GroupArgsB ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) unsigned short lds[(128 + 64) * BKH];
@@ -1498,15 +1533,16 @@ __global__ __launch_bounds__(256, 4) void igemm_bf16_group_pp_stream_kernel(Grou
     if (!t.live) return;
     const GemmArgs& p = ga.g[t.pi];
     switch (ga.cfg[t.pi]) {
-        case 0: igemm_bf16_tile<128, 64, 64, 32, 1, false, false, false, true>(p, t.bid, lds); break;
-        case 1: igemm_bf16_tile<64, 64, 32, 32, 1, false, false, false, true>(p, t.bid, lds); break;
-        default: igemm_bf16_tile<128, 32, 32, 32, 1, false, false, false, true>(p, t.bid, lds); break;
+        case 0: igemm_bf16_tile<128, 64, 64, 32, 1, false, false, false, true, F>(p, t.bid, lds); break;
+        case 1: igemm_bf16_tile<64, 64, 32, 32, 1, false, false, false, true, F>(p, t.bid, lds); break;
+        default: igemm_bf16_tile<128, 32, 32, 32, 1, false, false, false, true, F>(p, t.bid, lds); break;
     }
 #endif
 }
 
 // ping-pong grouped kernel for launches that contain row-halo problems (cfg 3.. = (chunk width, 32-column blocks) (64,2) (64,1)
 // (48,2) (48,3) (48,1) (32,2) (32,1)); the stage size is the largest any problem of the launch needs (dynamic LDS, 18-40 KiB)
+template <class F>
 __global__ __launch_bounds__(256, 4) void igemm_bf16_group_rh_kernel(GroupArgsB ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) unsigned short lds_dyn[];
@@ -1516,16 +1552,16 @@ __global__ __launch_bounds__(256, 4) void igemm_bf16_group_rh_kernel(GroupArgsB 
     const GemmArgs& p = ga.g[t.pi];
     const int bid = t.bid;
     switch (ga.cfg[t.pi]) {
-        case 0: igemm_bf16_tile<128, 64, 64, 32, 1>(p, bid, lds); break;
-        case 1: igemm_bf16_tile<64, 64, 32, 32, 1>(p, bid, lds); break;
-        case 2: igemm_bf16_tile<128, 32, 32, 32, 1>(p, bid, lds); break;
-        case 3: igemm_bf16_rh_tile<64, 1, 2>(p, bid, lds); break;
-        case 4: igemm_bf16_rh_tile<64, 1, 1>(p, bid, lds); break;
-        case 5: igemm_bf16_rh_tile<48, 1, 2>(p, bid, lds); break;
-        case 6: igemm_bf16_rh_tile<48, 1, 3>(p, bid, lds); break;
-        case 7: igemm_bf16_rh_tile<48, 1, 1>(p, bid, lds); break;
-        case 8: igemm_bf16_rh_tile<32, 1, 2>(p, bid, lds); break;
-        default: igemm_bf16_rh_tile<32, 1, 1>(p, bid, lds); break;
+        case 0: igemm_bf16_tile<128, 64, 64, 32, 1, false, false, false, false, F>(p, bid, lds); break;
+        case 1: igemm_bf16_tile<64, 64, 32, 32, 1, false, false, false, false, F>(p, bid, lds); break;
+        case 2: igemm_bf16_tile<128, 32, 32, 32, 1, false, false, false, false, F>(p, bid, lds); break;
+        case 3: igemm_bf16_rh_tile<64, 1, 2, F>(p, bid, lds); break;
+        case 4: igemm_bf16_rh_tile<64, 1, 1, F>(p, bid, lds); break;
+        case 5: igemm_bf16_rh_tile<48, 1, 2, F>(p, bid, lds); break;
+        case 6: igemm_bf16_rh_tile<48, 1, 3, F>(p, bid, lds); break;
+        case 7: igemm_bf16_rh_tile<48, 1, 1, F>(p, bid, lds); break;
+        case 8: igemm_bf16_rh_tile<32, 1, 2, F>(p, bid, lds); break;
+        default: igemm_bf16_rh_tile<32, 1, 1, F>(p, bid, lds); break;
     }
 #endif
 }
@@ -1542,6 +1578,8 @@ static int pp_min_tiles() {
 template <int BM, int BN, int WM, int WN, int S>
 static hipError_t launch_cfg_b(const GemmArgs& a, hipStream_t s) {
     const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
+    // (the upsampled add and the fp32-stream epilogue are bf16 plans' only: CPN and CAPF_PLAN_BF16_F32_STREAM, which capf_create refuses for fp16)
+    if ((a.up || a.f32s) && a.f16) return hipErrorInvalidValue;
     if (a.up) {          // (+ bilinear_upsample(up) behind the activation: the two tile shapes a 256-channel lateral conv can get)
         if constexpr ((BM == 128 && BN == 128) || (BM == 64 && BN == 64))
             hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, WM, WN, S, false, false, true>), dim3(nbm * nbn), dim3(256), 0, s, a);
@@ -1549,7 +1587,8 @@ static hipError_t launch_cfg_b(const GemmArgs& a, hipStream_t s) {
             return hipErrorInvalidValue;
         return hipGetLastError();
     }
-    if (a.f32s) hipLaunchKernelGGL((igemm_bf16_stream_kernel<BM, BN, WM, WN, S>), dim3(nbm * nbn), dim3(256), 0, s, a);
+    if (a.f32s) hipLaunchKernelGGL((igemm_bf16_stream_kernel<BM, BN, WM, WN, S, Bf16Fmt>), dim3(nbm * nbn), dim3(256), 0, s, a);
+    else if (a.f16) hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, WM, WN, S, false, false, false, F16Fmt>), dim3(nbm * nbn), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, WM, WN, S>), dim3(nbm * nbn), dim3(256), 0, s, a);
     return hipGetLastError();
 }
@@ -1573,11 +1612,11 @@ Bf16Route gemm_bf16_route(const GemmArgs& a) {
 const char* gemm_bf16_kernel_name(const GemmArgs& a) {
     switch (gemm_bf16_route(a).path) {
         case Bf16Path::WS: return gemm_bf16_ws_kernel_name(a);
-        case Bf16Path::RH: return "igemm_bf16_rh<w4,126x64,conv>";
-        case Bf16Path::T128x32: return "igemm_bf16<w4,128x32,conv>";
-        case Bf16Path::T128x64: return "igemm_bf16<w4,128x64,conv>";
-        case Bf16Path::T128x128: return "igemm_bf16<w4,128x128,conv>";
-        default: return "igemm_bf16<w4,64x64,conv>";
+        case Bf16Path::RH: return fmt_kernel_name("igemm_bf16_rh<w4,126x64,conv>", a.f16);
+        case Bf16Path::T128x32: return fmt_kernel_name("igemm_bf16<w4,128x32,conv>", a.f16);
+        case Bf16Path::T128x64: return fmt_kernel_name("igemm_bf16<w4,128x64,conv>", a.f16);
+        case Bf16Path::T128x128: return fmt_kernel_name("igemm_bf16<w4,128x128,conv>", a.f16);
+        default: return fmt_kernel_name("igemm_bf16<w4,64x64,conv>", a.f16);
     }
 }
 
@@ -1620,8 +1659,10 @@ hipError_t launch_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t s, in
     }
     if (n == 1) return launch_gemm_bf16(list[0], s);
     const bool stream = list[0].f32s != 0;                       // (fp32-stream epilogue: every problem of the launch or none)
+    const int f16 = list[0].f16;                                 // (one element format per launch)
     for (int i = 1; i < n; ++i)
-        if ((list[i].f32s != 0) != stream) return hipErrorInvalidValue;
+        if ((list[i].f32s != 0) != stream || list[i].f16 != f16) return hipErrorInvalidValue;
+    if (stream && f16) return hipErrorInvalidValue;
     static const int BMs[3] = {128, 64, 128}, BNs[3] = {64, 64, 32};
     double total = 0.0;
     for (int i = 0; i < n; ++i) {
@@ -1668,9 +1709,18 @@ hipError_t launch_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t s, in
         ga.cfg[i] = cfgs[order[i]];
     }
     if (variant) *variant = nrh ? 2 : (start >= pp_min_tiles() ? 1 : 0);
-    if (nrh) hipLaunchKernelGGL(igemm_bf16_group_rh_kernel, dim3(start), dim3(256), (size_t)lds_halves * 2, s, ga);
-    else if (start >= pp_min_tiles()) hipLaunchKernelGGL(stream ? igemm_bf16_group_pp_stream_kernel : igemm_bf16_group_pp_kernel, dim3(start), dim3(256), 0, s, ga);
-    else hipLaunchKernelGGL(stream ? igemm_bf16_group_stream_kernel : igemm_bf16_group_kernel, dim3(start), dim3(256), 0, s, ga);
+    if (stream) {
+        if (start >= pp_min_tiles()) hipLaunchKernelGGL(igemm_bf16_group_pp_stream_kernel<Bf16Fmt>, dim3(start), dim3(256), 0, s, ga);
+        else hipLaunchKernelGGL(igemm_bf16_group_stream_kernel<Bf16Fmt>, dim3(start), dim3(256), 0, s, ga);
+        return hipGetLastError();
+    }
+    with_fmt(f16, [&](auto f) {
+        using F = decltype(f);
+        if (nrh) hipLaunchKernelGGL(igemm_bf16_group_rh_kernel<F>, dim3(start), dim3(256), (size_t)lds_halves * 2, s, ga);
+        else if (start >= pp_min_tiles()) hipLaunchKernelGGL(igemm_bf16_group_pp_kernel<F>, dim3(start), dim3(256), 0, s, ga);
+        else hipLaunchKernelGGL(igemm_bf16_group_kernel<F>, dim3(start), dim3(256), 0, s, ga);
+        return 0;
+    });
     return hipGetLastError();
 }
 
@@ -1710,17 +1760,23 @@ hipError_t launch_gemm_bf16(const GemmArgs& a_in, hipStream_t s) {
 template <int BM, int BN, int WM, int WN, int S>
 static hipError_t launch_rows_b(const GemmArgs& a, int mode, hipStream_t s) {
     const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
-    if (mode == 0) hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, WM, WN, S, true, false>), dim3(nbm * nbn), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, WM, WN, S, false, true>), dim3(nbm * nbn), dim3(256), 0, s, a);
+    with_fmt(a.f16, [&](auto f) {
+        using F = decltype(f);
+        if (mode == 0) hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, WM, WN, S, true, false, false, F>), dim3(nbm * nbn), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, WM, WN, S, false, true, false, F>), dim3(nbm * nbn), dim3(256), 0, s, a);
+        return 0;
+    });
     return hipGetLastError();
 }
 
 static bool rows_b_big(int M, int N) { return (long)((M + 127) / 128) * ((N + 127) / 128) >= 384; }
 
-const char* gemm_bf16_rows_kernel_name(int M, int N) { return rows_b_big(M, N) ? "igemm_bf16<w4,128x128,rows>" : "igemm_bf16<w4,64x64,rows>"; }
+const char* gemm_bf16_rows_kernel_name(int M, int N, int f16) {
+    return fmt_kernel_name(rows_b_big(M, N) ? "igemm_bf16<w4,128x128,rows>" : "igemm_bf16<w4,64x64,rows>", f16);
+}
 
 hipError_t launch_gemm_bf16_rows(const void* A_bf16, const void* W_bf16, const float* bias, int M, int N, int K, int Kpad,
-                                 float* out, RowMap omap, const float* res, RowMap rmap, int gelu_bf16_out, hipStream_t s) {
+                                 float* out, RowMap omap, const float* res, RowMap rmap, int gelu_bf16_out, hipStream_t s, int f16) {
     if (M <= 0 || N <= 0) return hipSuccess;
     if (Kpad % BKH != 0 || K % 8 != 0 || N % 4 != 0 || (double)M * K * 2.0 >= 2.0e9) return hipErrorInvalidValue;
     if (gelu_bf16_out && (res || omap.G != 1)) return hipErrorInvalidValue;
@@ -1728,7 +1784,7 @@ hipError_t launch_gemm_bf16_rows(const void* A_bf16, const void* W_bf16, const f
     a.A = static_cast<const float*>(A_bf16); a.Wp = static_cast<const float*>(W_bf16); a.bias = bias; a.res = res; a.out = out;
     a.M = M; a.N = N; a.K = K; a.Kpad = Kpad;
     a.conv = 1; a.Cin = K; a.H = M; a.W = 1; a.Ho = M; a.Wo = 1; a.ks = 1; a.stride = 1; a.pad = 0;
-    a.omap = omap; a.rmap = rmap; a.act = ACT_NONE;
+    a.omap = omap; a.rmap = rmap; a.act = ACT_NONE; a.f16 = f16;
     prep_conv_b(a);
     if (rows_b_big(M, N)) return launch_rows_b<128, 128, 64, 64, 2>(a, gelu_bf16_out, s);
     return launch_rows_b<64, 64, 32, 32, 3>(a, gelu_bf16_out, s);

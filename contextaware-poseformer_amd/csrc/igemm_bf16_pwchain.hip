@@ -24,10 +24,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
-template <int K1, int N1, int N2>
+// F: the 16-bit element format of every tensor and both weight packs (fmt16.h; GemmArgs::f16 of both convs)
+template <int K1, int N1, int N2, class F>
 __global__ __launch_bounds__(256, 1) void igemm_bf16_pwchain_kernel(GemmArgs p3, GemmArgs p1, int ntiles) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int NT1 = N1 / 32, NT2 = N2 / 32, ST1 = K1 / 16;    // N-tiles of the two convs, 16-deep k-steps of the first
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256, 1) void igemm_bf16_pwchain_kernel(GemmArgs p3,
                 for (int j = 0; j < NT1; ++j) {
                     const int jn = j + 1 < NT1 ? j + 1 : 0, sn = j + 1 < NT1 ? st : (st + 1 < ST1 ? st + 1 : st);
                     const u32x4 nx = w3_frag(sn, jn);
-                    y[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bf), __builtin_bit_cast(bf16x8, a1[st]), y[j], 0, 0, 0);
+                    y[j] = F::mfma(__builtin_bit_cast(typename F::x8, bf), __builtin_bit_cast(typename F::x8, a1[st]), y[j]);
                     bf = nx;
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -133,10 +133,10 @@ __global__ __launch_bounds__(256, 1) void igemm_bf16_pwchain_kernel(GemmArgs p3,
             for (int h = 0; h < 2; ++h) {
                 float* dst = &ep[(16 * h + er) * EPS + ec];
                 const u32x4 q = res[j][h];
-                *reinterpret_cast<f32x4*>(dst) = f32x4{__uint_as_float(q[0] << 16), __uint_as_float(q[0] & 0xFFFF0000u),
-                                                       __uint_as_float(q[1] << 16), __uint_as_float(q[1] & 0xFFFF0000u)};
-                *reinterpret_cast<f32x4*>(dst + 4) = f32x4{__uint_as_float(q[2] << 16), __uint_as_float(q[2] & 0xFFFF0000u),
-                                                           __uint_as_float(q[3] << 16), __uint_as_float(q[3] & 0xFFFF0000u)};
+                *reinterpret_cast<f32x4*>(dst) = f32x4{F::lo(q[0]), F::hi(q[0]),
+                                                       F::lo(q[1]), F::hi(q[1])};
+                *reinterpret_cast<f32x4*>(dst + 4) = f32x4{F::lo(q[2]), F::hi(q[2]),
+                                                           F::lo(q[3]), F::hi(q[3])};
             }
             __builtin_amdgcn_wave_barrier();
             unsigned pk[8];
@@ -148,11 +148,11 @@ __global__ __launch_bounds__(256, 1) void igemm_bf16_pwchain_kernel(GemmArgs p3,
                 float t[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) t[e] = relu_f((y[j][4 * g + e] + bv[e]) + rv[e]);
-                pk[2 * g] = pack_bf16x2(t[0], t[1]);
-                pk[2 * g + 1] = pack_bf16x2(t[2], t[3]);
+                pk[2 * g] = F::pack2(t[0], t[1]);
+                pk[2 * g + 1] = F::pack2(t[2], t[3]);
                 // (the rounded values go back to the scratch as fp32: exact, and the coalesced pass below packs them again)
-                *reinterpret_cast<f32x4*>(cell) = f32x4{__uint_as_float(pk[2 * g] << 16), __uint_as_float(pk[2 * g] & 0xFFFF0000u),
-                                                        __uint_as_float(pk[2 * g + 1] << 16), __uint_as_float(pk[2 * g + 1] & 0xFFFF0000u)};
+                *reinterpret_cast<f32x4*>(cell) = f32x4{F::lo(pk[2 * g]), F::hi(pk[2 * g]),
+                                                        F::lo(pk[2 * g + 1]), F::hi(pk[2 * g + 1])};
             }
             yb[j][0] = u32x4{pk[0], pk[1], pk[2], pk[3]};
             yb[j][1] = u32x4{pk[4], pk[5], pk[6], pk[7]};
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256, 1) void igemm_bf16_pwchain_kernel(GemmArgs p3,
             for (int h = 0; h < 2; ++h) {
                 const float* src = &ep[(16 * h + er) * EPS + ec];
                 const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 4);
-                const u32x4 o = u32x4{pack_bf16x2(x0[0], x0[1]), pack_bf16x2(x0[2], x0[3]), pack_bf16x2(x1[0], x1[1]), pack_bf16x2(x1[2], x1[3])};
+                const u32x4 o = u32x4{F::pack2(x0[0], x0[1]), F::pack2(x0[2], x0[3]), F::pack2(x1[0], x1[1]), F::pack2(x1[2], x1[3])};
                 __builtin_amdgcn_raw_buffer_store_b128(o, rs_y, m0 + 16 * h + er < p3.M ? (unsigned)((16 * h + er) * (int)s_y + 32 * j + ec) * 2u : OOB, 0, 0);
             }
         }
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256, 1) void igemm_bf16_pwchain_kernel(GemmArgs p3,
                         const bool last_n = jn + 1 == NT2, last_s = s == 1;
                         const int n2 = last_n ? 0 : jn + 1, s2 = last_n ? (last_s ? 0 : 1) : s, j2 = last_n && last_s ? (j + 1 < NT1 ? j + 1 : j) : j;
                         const u32x4 nx = w1_frag(j2, s2, n2);
-                        z[jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bf), __builtin_bit_cast(bf16x8, yb[j][s]), z[jn], 0, 0, 0);
+                        z[jn] = F::mfma(__builtin_bit_cast(typename F::x8, bf), __builtin_bit_cast(typename F::x8, yb[j][s]), z[jn]);
                         bf = nx;
                         if (last_s && last_n) request_res(tile + nw, j);     // the next tile's residual, a trickle under this loop
                         __builtin_amdgcn_sched_barrier(0);
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256, 1) void igemm_bf16_pwchain_kernel(GemmArgs p3,
             for (int h = 0; h < 2; ++h) {
                 const float* src = &ep[(16 * h + er) * EPS + ec];
                 const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 4);
-                const u32x4 o = u32x4{pack_bf16x2(x0[0], x0[1]), pack_bf16x2(x0[2], x0[3]), pack_bf16x2(x1[0], x1[1]), pack_bf16x2(x1[2], x1[3])};
+                const u32x4 o = u32x4{F::pack2(x0[0], x0[1]), F::pack2(x0[2], x0[3]), F::pack2(x1[0], x1[1]), F::pack2(x1[2], x1[3])};
                 __builtin_amdgcn_raw_buffer_store_b128(o, rs_t, m0 + 16 * h + er < p3.M ? (unsigned)((16 * h + er) * (int)s_t + 32 * jn + ec) * 2u : OOB, 0, 0);
             }
         }
@@ -239,17 +239,21 @@ bool gemm_bf16_pwchain_ok(const GemmArgs& a, const GemmArgs& b) {
     return a.M >= 32 * 1024 * 4;
 }
 
-const char* gemm_bf16_pwchain_kernel_name() { return "igemm_bf16_pwchain<64,256,64>"; }
+const char* gemm_bf16_pwchain_kernel_name(int f16) { return fmt_kernel_name("igemm_bf16_pwchain<64,256,64>", f16); }
 
 hipError_t launch_gemm_bf16_pwchain(const GemmArgs& a, const GemmArgs& b, hipStream_t s) {
     if (!gemm_bf16_pwchain_ok(a, b)) return hipErrorInvalidValue;
     const int ntiles = (a.M + 31) / 32;
     constexpr size_t lds_bytes = (size_t)(256 * 64 + 64 * 256) * 2 + (size_t)(256 + 64 + 4 * 32 * 36) * 4;
-    static DynLdsAttr attr_once;
-    const hipError_t attr = attr_once.ensure(reinterpret_cast<const void*>(&igemm_bf16_pwchain_kernel<64, 256, 64>), (int)lds_bytes);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((igemm_bf16_pwchain_kernel<64, 256, 64>), dim3(256), dim3(256), lds_bytes, s, a, b, ntiles);
-    return hipGetLastError();
+    if (a.f16 != b.f16) return hipErrorInvalidValue;
+    return with_fmt(a.f16, [&](auto f) {
+        using F = decltype(f);
+        static DynLdsAttr attr_once;              // (one per instantiation of this lambda, i.e. per kernel)
+        const hipError_t attr = attr_once.ensure(reinterpret_cast<const void*>(&igemm_bf16_pwchain_kernel<64, 256, 64, F>), (int)lds_bytes);
+        if (attr != hipSuccess) return attr;
+        hipLaunchKernelGGL((igemm_bf16_pwchain_kernel<64, 256, 64, F>), dim3(256), dim3(256), lds_bytes, s, a, b, ntiles);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace capf

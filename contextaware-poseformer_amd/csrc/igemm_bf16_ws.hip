@@ -73,16 +73,16 @@ struct WsGroupArgs {
 };
 static_assert(sizeof(WsGroupArgs) == MAXG * sizeof(WsProblem) + (2 * MAXG + 2) * sizeof(int), "kernel argument layout");
 
-template <bool F32S>
+template <bool F32S, class F>
 __device__ __forceinline__ void ws_group_body(const WsGroupArgs& ga, unsigned char* ws_lds) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
     if (!t.live) return;
     const WsProblem& p = ga.g[t.pi];
     switch (p.NS) {
-        case 96: igemm_bf16_ws_tile<3, F32S>(p, t.bid, ws_lds); break;
-        case 64: igemm_bf16_ws_tile<2, F32S>(p, t.bid, ws_lds); break;
-        default: igemm_bf16_ws_tile<1, F32S>(p, t.bid, ws_lds); break;
+        case 96: igemm_bf16_ws_tile<3, F32S, F>(p, t.bid, ws_lds); break;
+        case 64: igemm_bf16_ws_tile<2, F32S, F>(p, t.bid, ws_lds); break;
+        default: igemm_bf16_ws_tile<1, F32S, F>(p, t.bid, ws_lds); break;
     }
 #endif
 }
@@ -90,7 +90,15 @@ __device__ __forceinline__ void ws_group_body(const WsGroupArgs& ga, unsigned ch
 __global__ __launch_bounds__(256, 2) void igemm_bf16_group_ws_kernel(WsGroupArgs ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) unsigned char ws_lds[];
-    ws_group_body<false>(ga, ws_lds);
+    ws_group_body<false, Bf16Fmt>(ga, ws_lds);
+#endif
+}
+
+// ... on fp16 elements (GemmArgs::f16)
+__global__ __launch_bounds__(256, 2) void igemm_f16_group_ws_kernel(WsGroupArgs ga) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    extern __shared__ __attribute__((aligned(16))) unsigned char ws_lds[];
+    ws_group_body<false, F16Fmt>(ga, ws_lds);
 #endif
 }
 
@@ -98,7 +106,7 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_group_ws_kernel(WsGroupArgs
 __global__ __launch_bounds__(256, 2) void igemm_bf16_group_ws_stream_kernel(WsGroupArgs ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) unsigned char ws_lds[];
-    ws_group_body<true>(ga, ws_lds);
+    ws_group_body<true, Bf16Fmt>(ga, ws_lds);
 #endif
 }
 
@@ -109,8 +117,10 @@ hipError_t launch_gemm_bf16_ws_group(const GemmArgs* list, int n, hipStream_t s)
     int tiles[MAXG], order[MAXG], max_ns = 32;
     double cost[MAXG];
     const bool stream = list[0].f32s != 0;
+    const int f16 = list[0].f16;                                   // (one element format per launch; the fp32-stream epilogue is bf16 plans' only)
+    if (stream && f16) return hipErrorInvalidValue;
     for (int i = 0; i < n; ++i) {
-        if (!list[i].Wp3 || !ws_from_args(list[i], &p[i]) || (list[i].f32s != 0) != stream) return hipErrorInvalidValue;
+        if (!list[i].Wp3 || !ws_from_args(list[i], &p[i]) || (list[i].f32s != 0) != stream || list[i].f16 != f16) return hipErrorInvalidValue;
         tiles[i] = p[i].tiles_m * p[i].NSL;
         cost[i] = (double)(p[i].C / 16) * p[i].NS;               // a tile's K loop
         if (p[i].NS > max_ns) max_ns = p[i].NS;
@@ -120,11 +130,17 @@ hipError_t launch_gemm_bf16_ws_group(const GemmArgs* list, int n, hipStream_t s)
     const int start = group_layout(ga.lay, n, tiles, cost, order);
     for (int i = 0; i < n; ++i) ga.g[i] = p[order[i]];
     const size_t lds_bytes = 2 * (size_t)ws_stage_bytes(max_ns);
-    static DynLdsAttr attr_once, attr_stream;
+    static DynLdsAttr attr_once, attr_f16, attr_stream;
     if (stream) {
         const hipError_t attr = attr_stream.ensure(reinterpret_cast<const void*>(&igemm_bf16_group_ws_stream_kernel), 2 * ws_stage_bytes(96));
         if (attr != hipSuccess) return attr;
         hipLaunchKernelGGL(igemm_bf16_group_ws_stream_kernel, dim3(start), dim3(256), lds_bytes, s, ga);
+        return hipGetLastError();
+    }
+    if (f16) {
+        const hipError_t attr = attr_f16.ensure(reinterpret_cast<const void*>(&igemm_f16_group_ws_kernel), 2 * ws_stage_bytes(96));
+        if (attr != hipSuccess) return attr;
+        hipLaunchKernelGGL(igemm_f16_group_ws_kernel, dim3(start), dim3(256), lds_bytes, s, ga);
         return hipGetLastError();
     }
     const hipError_t attr = attr_once.ensure(reinterpret_cast<const void*>(&igemm_bf16_group_ws_kernel), 2 * ws_stage_bytes(96));
@@ -141,27 +157,31 @@ hipError_t launch_gemm_bf16_ws(const GemmArgs& a, hipStream_t s) { return launch
 
 const char* gemm_bf16_ws_kernel_name(const GemmArgs& a) {
     const int ns = ws_ns(a.N);
-    return ns == 96 ? "igemm_bf16_ws<w4,256x96,conv>" : (ns == 64 ? "igemm_bf16_ws<w4,256x64,conv>" : "igemm_bf16_ws<w4,256x32,conv>");
+    return fmt_kernel_name(ns == 96 ? "igemm_bf16_ws<w4,256x96,conv>" : (ns == 64 ? "igemm_bf16_ws<w4,256x64,conv>" : "igemm_bf16_ws<w4,256x32,conv>"), a.f16);
 }
 
 // BN fold + re-layout for the tile: Wp[slice][Cin / 16][tap][n][quad position][8] (ws_pack_decode) = bf16 of the folded fp32 weight
 // (bn_fold_w3x3: rows beyond Cout zero; bias as launch_pack_conv)
+template <class F>
 __global__ void pack_conv_bf16_ws_kernel(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ beta,
                                          const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                          unsigned short* __restrict__ Wp, float* __restrict__ bias, int Cout, int Cin, int NS, long total) {
     const int ncc = Cin / 16;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const WsPackIdx d = ws_pack_decode(i, NS, ncc);
-        Wp[i] = to_bf16(bn_fold_w3x3(w, gamma, beta, mean, var, eps, bias, Cout, Cin, d.ng, d.c, d.tap, d.first));
+        Wp[i] = F::narrow(bn_fold_w3x3(w, gamma, beta, mean, var, eps, bias, Cout, Cin, d.ng, d.c, d.tap, d.first));
     }
 }
 
 hipError_t launch_pack_conv_bf16_ws(const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
-                                    float eps, void* Wp_bf16, float* bias, int Cout, int Cin, hipStream_t s) {
+                                    float eps, void* Wp_bf16, float* bias, int Cout, int Cin, hipStream_t s, int f16) {
     if (Cin % 16 != 0 || Cout <= 0) return hipErrorInvalidValue;
     const long total = bf16_ws_pack_elems(Cout, Cin);
-    hipLaunchKernelGGL(pack_conv_bf16_ws_kernel, dim3(grid_1d(total)), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
-                       static_cast<unsigned short*>(Wp_bf16), bias, Cout, Cin, ws_ns(Cout), total);
+    with_fmt(f16, [&](auto f) {
+        hipLaunchKernelGGL(pack_conv_bf16_ws_kernel<decltype(f)>, dim3(grid_1d(total)), dim3(256), 0, s, w, gamma, beta, mean, var, eps,
+                           static_cast<unsigned short*>(Wp_bf16), bias, Cout, Cin, ws_ns(Cout), total);
+        return 0;
+    });
     return hipGetLastError();
 }
 

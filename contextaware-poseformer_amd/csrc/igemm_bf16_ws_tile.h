@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "relu.h"
+#include "fmt16.h"
 
 #include <type_traits>
 
@@ -133,7 +134,7 @@ __host__ __device__ __forceinline__ WsPackIdx ws_pack_decode(long i, int NS, int
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef float ws_f32x4 __attribute__((ext_vector_type(4)));
 typedef float ws_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 ws_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 ws_bf16x8 __attribute__((ext_vector_type(8)));       // (the split-fp32 tile's pieces, igemm_f32x3_ws_tile.h)
 typedef unsigned ws_u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* ws_lptr_t;
 typedef __amdgpu_buffer_rsrc_t ws_rsrc_t;
@@ -148,7 +149,7 @@ __device__ __forceinline__ unsigned ws_pack2(float lo, float hi) {
 // one tile (logical id `bid` = pixel tile * NSL + slice) with the calling 256-thread block; lds: 2 * ws_stage_bytes(32 TN) bytes.
 // F32S: the epilogue of a CAPF_PLAN_BF16_F32_STREAM conv -- fp32 residual (res32), fp32 result (y32) and / or bf16 (y); the K loop is the default
 // one, the residual is requested behind it (twice the registers of a bf16 one: before the last chunk it would spill)
-template <int TN, bool F32S = false>
+template <int TN, bool F32S = false, class F = Bf16Fmt>
 __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int bid, unsigned char* __restrict__ lds) {
     constexpr int NS = 32 * TN;
     constexpr int W_BYTES = 9 * NS * 32;
@@ -271,9 +272,11 @@ __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int
                 }
     };
     // TN = 3 runs at the 256-register limit of two waves per SIMD: more than one channel block requested before the last chunk
-    // and the compiler spills the loaded rows (load, wait, scratch store -- worse than no prefetch)
-    constexpr int EARLY = TN == 3 ? 1 : TN;
-    ws_bf16x8 af[2][2], bfr[2][TN];
+    // and the compiler spills the loaded rows (load, wait, scratch store -- worse than no prefetch).  With ONE block the bf16 instantiation
+    // still spills 17 registers (known, pinned by the build guard in tests/); the fp16 instantiation -- a new kernel, held to no spills at
+    // all -- requests the whole residual behind the K loop, as F32S does: 250 registers, none spilled
+    constexpr int EARLY = TN == 3 ? (F::code == Bf16Fmt::code ? 1 : 0) : TN;
+    typename F::x8 af[2][2], bfr[2][TN];
     auto chunk = [&](auto SC, auto LAST, int cnext) {      // multiply the chunk staged in stage S; fire chunk `cnext` into the other
         constexpr int S = decltype(SC)::value;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the chunk has landed ...
@@ -282,10 +285,10 @@ __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int
         const unsigned char* st = lds + S * ST;
         auto read_frags = [&](int t, int buf) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) af[buf][i] = __builtin_bit_cast(ws_bf16x8, *reinterpret_cast<const ws_f32x4*>(st + a_addr[i][t]));
+            for (int i = 0; i < 2; ++i) af[buf][i] = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const ws_f32x4*>(st + a_addr[i][t]));
 #pragma unroll
             for (int j = 0; j < TN; ++j)
-                bfr[buf][j] = __builtin_bit_cast(ws_bf16x8, *reinterpret_cast<const ws_f32x4*>(st + b_addr + (t * NS + j * 32) * 32));
+                bfr[buf][j] = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const ws_f32x4*>(st + b_addr + (t * NS + j * 32) * 32));
         };
         read_frags(0, 0);
 #pragma unroll
@@ -295,7 +298,7 @@ __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[t & 1][j], af[t & 1][i], acc[i][j], 0, 0, 0);
+                    acc[i][j] = F::mfma(bfr[t & 1][j], af[t & 1][i], acc[i][j]);
             if constexpr (!decltype(LAST)::value) {        // (the last chunk fires nothing: the idle stage becomes the epilogue's scratch)
                 // one or two of the next chunk's pieces behind every tap (all of them behind the first five / three taps, so that the
                 // last has longer to land before the next chunk's wait: measured equal, 210.5 / 215.9 vs 209.5 us per HRNet-48 level)
@@ -358,9 +361,9 @@ __device__ __forceinline__ void igemm_bf16_ws_tile(const WsProblem& p, const int
                         const float vb = finish(xb + __uint_as_float(q < 2 ? rr[i][j][h][2 * q + 1] : rr2[i][j][h][2 * q - 3]));
                         y32[q >> 1][(2 * q) & 3] = va;
                         y32[q >> 1][(2 * q + 1) & 3] = vb;
-                        o[q] = ws_pack2(va, vb);
+                        o[q] = F::pack2(va, vb);
                     } else {
-                        o[q] = ws_pack2(finish(xa + __uint_as_float(rw << 16)), finish(xb + __uint_as_float(rw & 0xFFFF0000u)));
+                        o[q] = F::pack2(finish(xa + F::lo(rw)), finish(xb + F::hi(rw)));
                     }
                 }
                 __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, piece_off(i, j, h, p.ldy, er, ec), 0, 0);

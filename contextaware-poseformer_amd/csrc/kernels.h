@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "relu.h"
+#include "fmt16.h"    // the 16-bit element formats (bf16 / fp16) of the 16-bit kernel families
 #include "capf.h"      // capf_optim_report: the record the guarded AdamW kernel writes is the public one
 
 namespace capf {
@@ -21,20 +22,6 @@ inline const char* diag_env(const char* name) {
     return nullptr;
 #endif
 }
-
-// fp32 -> bf16, round to nearest even: gfx950 has the conversion in hardware (v_cvt_pk_bf16_f32, two values per instruction);
-// the software form (5 integer ops per value) made the bf16 epilogues VALU-bound.  Host passes never call these.
-__host__ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {          // lo in bits 0-15
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
-#else
-    (void)lo; (void)hi;
-    return 0u;
-#endif
-}
-__host__ __device__ __forceinline__ unsigned short to_bf16(float f) { return (unsigned short)(pack_bf16x2(f, 0.f) & 0xFFFFu); }
 
 // Bilinear corner of F.grid_sample(mode='bilinear', align_corners=True) at normalised coordinates (gx, gy): the integer NW
 // corner and the fractional weights of the +1 corners, exactly as ATen computes them (GridSampler.h:27-36, 58-60, 143-171:
@@ -127,6 +114,8 @@ struct GemmArgs {
     int splits, cps;        // split-K (rows mode): grid.y slices of `cps` chunks, slab s at out + s*split_stride
     long split_stride;
     int out_bf16;           // small-Cin stem kernel only: fp32 image in, bf16 activations out
+    int f16;                // 16-bit kernels: the element format of every 16-bit tensor and weight pack of the problem -- 0 bf16, 1 fp16 (Bf16Fmt /
+                            // F16Fmt above; every problem of a grouped launch carries the same one).  The fp32 kernels do not look at it
     // conv-mode split-K with an in-kernel, deterministic reduction (small batches: a long-K conv with a handful of tiles):
     // slice ky writes its raw partial tile to split_ws + ky * split_stride ([M][N]); the LAST slice to finish a tile (a
     // device-scope counter per tile, self-resetting) sums the slices in order 0..splits-1 and runs the epilogue
@@ -301,15 +290,15 @@ const char* gemm_f32_pwchain_kernel_name();
 // shortcut + ReLU, intermediates on chip; tap = also store conv1's, conv2's and the downsample's outputs where the unfused ops write them
 bool bneck0_bf16_ok(const GemmArgs& c1, const GemmArgs& c2, const GemmArgs& ds, const GemmArgs& c3);
 hipError_t launch_bneck0_bf16(const GemmArgs& c1, const GemmArgs& c2, const GemmArgs& ds, const GemmArgs& c3, bool tap, hipStream_t s);
-const char* bneck0_bf16_kernel_name();
+const char* bneck0_bf16_kernel_name(int f16 = 0);
 // ... and an identity bottleneck (256 -> 64 -> 64 -> 256, y = relu(conv3 + x)) the same way
 bool bneck1_bf16_ok(const GemmArgs& c1, const GemmArgs& c2, const GemmArgs& c3);
 hipError_t launch_bneck1_bf16(const GemmArgs& c1, const GemmArgs& c2, const GemmArgs& c3, bool tap, hipStream_t s);
-const char* bneck1_bf16_kernel_name();
+const char* bneck1_bf16_kernel_name(int f16 = 0);
 // the bf16 twin (igemm_bf16_pwchain.hip): CPN's / HRNet's layer1 pairs under compute_dtype = bf16
 bool gemm_bf16_pwchain_ok(const GemmArgs& a, const GemmArgs& b);
 hipError_t launch_gemm_bf16_pwchain(const GemmArgs& a, const GemmArgs& b, hipStream_t s);
-const char* gemm_bf16_pwchain_kernel_name();
+const char* gemm_bf16_pwchain_kernel_name(int f16 = 0);
 
 // Winograd F(2,3)-along-W variant of the 3x3 / stride-1 / pad-1 fp32 conv (igemm_wino.hip): same GemmArgs as the direct conv,
 // Wp = weights packed by launch_pack_conv_wino ([N][12 * Cin]); needs Cin % 32 == 0, even W, N % 4 == 0
@@ -331,7 +320,7 @@ hipError_t launch_pack_conv(const float* w, const float* gamma, const float* bet
 // linear pack: Wp[n][k] = w[n][k] (zero padded to Kpad); rows [n0, n0+N) of the destination
 hipError_t launch_pack_conv_bf16(const float* w, const float* gamma, const float* beta, const float* mean,
                                  const float* var, float eps, void* Wp_bf16, float* bias, int Cout, int Cin, int ks,
-                                 int Kpad, hipStream_t s);
+                                 int Kpad, hipStream_t s, int f16 = 0);
 // bf16 conv (igemm_bf16.hip): A / res / out bf16 NHWC, Wp bf16 [N][Kpad], Kpad % 64 == 0, bias fp32
 hipError_t launch_gemm_bf16(const GemmArgs& a, hipStream_t s);
 int f32h2_tiles_m(int B, int H, int W, int* tile_pixels = nullptr);            // pixel tiles of the two-fp16-piece conv tile (rows of a planes tensor's exponent table); 0: not eligible
@@ -353,7 +342,7 @@ int bf16_rh_width(int Cin);
 int gemm_bf16_rh_cw(const GemmArgs& a);
 hipError_t launch_gemm_bf16_rh(const GemmArgs& a, hipStream_t s);
 hipError_t launch_pack_conv_bf16_rh(const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
-                                    float eps, void* Wp_bf16, float* bias, int Cout, int Cin, int CW, hipStream_t s);
+                                    float eps, void* Wp_bf16, float* bias, int Cout, int Cin, int CW, hipStream_t s, int f16 = 0);
 // "2-D halo" tile of the 3x3 / stride-1 bf16 conv (igemm_bf16_ws.hip, igemm_bf16_ws_tile.h): 256 pixels x 32 / 64 / 96 channels per
 // block with the accumulators resident for the whole K, 16-channel chunks staged once for all nine taps; weights packed by
 // launch_pack_conv_bf16_ws (bf16_ws_pack_elems(Cout, Cin) bf16 elements), passed as GemmArgs::Wp3
@@ -365,7 +354,7 @@ hipError_t launch_gemm_bf16_ws(const GemmArgs& a, hipStream_t s);
 hipError_t launch_gemm_bf16_ws_group(const GemmArgs* list, int n, hipStream_t s);
 const char* gemm_bf16_ws_kernel_name(const GemmArgs& a);
 hipError_t launch_pack_conv_bf16_ws(const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
-                                    float eps, void* Wp_bf16, float* bias, int Cout, int Cin, hipStream_t s);
+                                    float eps, void* Wp_bf16, float* bias, int Cout, int Cin, hipStream_t s, int f16 = 0);
 
 // fp32 3x3 / stride-1 conv on the bf16 matrix pipe (igemm_f32x3_ws.hip, igemm_f32x3_ws_tile.h): fp32 tensors in and out, every operand split
 // losslessly into three bf16 pieces, the six piece products of weight >= 2^-18 accumulated in fp32 -- results to fp32 accumulation
@@ -428,18 +417,19 @@ hipError_t launch_pack_linear_quad(const float* w, float* Wq, int N, int K, int 
 // lifter projections on the bf16 MFMA path (igemm_bf16.hip): A bf16 [M][K], W bf16 [N][Kpad]; gelu_bf16_out = 0: fp32 out
 // (+ fp32 residual) through the row maps; 1: GELU then bf16 out [M][N]
 hipError_t launch_gemm_bf16_rows(const void* A_bf16, const void* W_bf16, const float* bias, int M, int N, int K, int Kpad,
-                                 float* out, RowMap omap, const float* res, RowMap rmap, int gelu_bf16_out, hipStream_t s);
-const char* gemm_bf16_rows_kernel_name(int M, int N);
+                                 float* out, RowMap omap, const float* res, RowMap rmap, int gelu_bf16_out, hipStream_t s, int f16 = 0);
+const char* gemm_bf16_rows_kernel_name(int M, int N, int f16 = 0);
 
 // out = relu( sum_i up_{s_i}(in_i) ), NHWC, s_i = nearest-upsample factor (1 = same resolution)
 struct FuseSumArgs {
     const float* in[4];
     int shift[4];  // log2 of the upsample factor
     int n_in;
+    int f16;       // 16-bit tensors (bf16 below): their element format, 0 bf16 / 1 fp16
     float* out;
     int B, H, W, C;
     int relu;
-    int bf16;      // tensors are bf16 (arithmetic stays fp32)
+    int bf16;      // tensors are 16-bit (arithmetic stays fp32)
     void* out_sh;  // fp32 sums only (bf16 = 0): bf16 shadow of out (RNE, [B,H,W,C]) written in the same pass, or nullptr
 };
 hipError_t launch_fuse_sum(const FuseSumArgs& a, hipStream_t s);
@@ -448,9 +438,9 @@ hipError_t launch_fuse_sum_group(const FuseSumArgs* a, int n, hipStream_t s);
 
 // 3x3 s2 p1 max-pool NHWC (resnet.py:140), bilinear align_corners=True resize NHWC (+ optional add)
 hipError_t launch_maxpool3x3s2(const float* in, float* out, int B, int H, int W, int C, int Ho, int Wo,
-                               hipStream_t s, int bf16 = 0);
+                               hipStream_t s, int bf16 = 0, int f16 = 0);      // bf16: 16-bit tensors, of format f16 (0 bf16, 1 fp16)
 hipError_t launch_bilinear_resize(const float* in, float* out, int B, int H, int W, int C, int Ho, int Wo,
-                                  hipStream_t s, int bf16 = 0, const float* add = nullptr);   // out = resize(in) (+ add, same shape as out)
+                                  hipStream_t s, int bf16 = 0, const float* add = nullptr, int f16 = 0);   // out = resize(in) (+ add, same shape as out)
 
 // n small float copies in one launch; the table ({src, dst, n} per segment) is in device memory
 struct CopySegment {
@@ -469,7 +459,7 @@ hipError_t launch_sample_ref(const float* feat, const float* ref, float* S, int*
                              int W, int C, hipStream_t s, int feat_bf16 = 0);
 // LayerNorm over rows: out[r,:] = LN(in[imap(r)] (+ add[amap(r)]))   width C
 hipError_t launch_layernorm(const float* in, RowMap imap, const float* add, RowMap amap, const float* g,
-                            const float* b, float eps, float* out, int rows, int C, hipStream_t s, int out_bf16 = 0);
+                            const float* b, float eps, float* out, int rows, int C, hipStream_t s, int out_bf16 = 0);   // out_bf16: 16-bit rows out, 1 bf16 / 2 fp16
 // deformable sampling (pose_dformer.py:122-135 minus the embed_proj GEMM):
 //   AO [rows=(b,p,l), NH*NS + 2*NH*NS] = [attention logits | offset pre-activations]
 //   U_l[(b,p,h), :] = sum_s softmax_s(logit[h,s]) * bilinear_border(feat_l, tanh(off[h,s]) + ref[b,p])
@@ -480,7 +470,7 @@ struct DeformArgs {
     const float* AO;
     const float* ref;
     int B, J, L, NH, NS;
-    int feat_bf16;           // the context maps are bf16
+    int feat_bf16;           // storage format of the context maps: 0 fp32, 1 bf16, 2 fp16 (the same code in launch_sample_ref / EmbedArgs / CtxAttnArgs)
     int ld_ao;               // row pitch of AO (0 = 3*NH*NS, the inference layout; 64 in training)
     const float* dU[4];      // backward only: gradient w.r.t. U[l]
     float* cpos;             // optional taps (capf_set_debug): sampling positions pos = tanh(off) + ref, [B*J, L, NH*NS, 2] ...

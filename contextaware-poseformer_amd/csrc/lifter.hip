@@ -67,14 +67,14 @@ hipError_t launch_bilinear_corners(const float* grid, int n, int H, int W, int b
     return hipGetLastError();
 }
 
-// element c of an NHWC pixel stored as fp32 or bf16
-template <bool BF>
+// element c of an NHWC pixel stored as fp32 or in a 16-bit format F (bf16 / fp16)
+template <bool BF, class F = Bf16Fmt>
 __device__ __forceinline__ float ldf(const float* pix, int c) {
     if (!BF) return pix[c];
-    return __uint_as_float((unsigned)reinterpret_cast<const unsigned short*>(pix)[c] << 16);
+    return F::widen(reinterpret_cast<const unsigned short*>(pix)[c]);
 }
 // pointer to pixel `pixel_index` (C channels) of a map stored as fp32 or bf16
-template <bool BF>
+template <bool BF, class F = Bf16Fmt>
 __device__ __forceinline__ const float* pixptr(const float* base, long pixel_index, int C) {
     if (!BF) return base + pixel_index * C;
     return reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(base) + pixel_index * C);
@@ -82,7 +82,7 @@ __device__ __forceinline__ const float* pixptr(const float* base, long pixel_ind
 
 // F.grid_sample(features, ref[B,17,1,2], bilinear, zeros, align_corners=True), pose_dformer.py:216-218.
 // One wave per (b, p); lanes stride over channels.
-template <bool BF>
+template <bool BF, class F = Bf16Fmt>
 __global__ void sample_ref_kernel(const float* __restrict__ feat, const float* __restrict__ ref,
                                   float* __restrict__ S, int* __restrict__ idx, int BJ, int J, int H, int W,
                                   int C) {
@@ -108,23 +108,25 @@ __global__ void sample_ref_kernel(const float* __restrict__ feat, const float* _
     const float* p10 = pixptr<BF>(feat, ib + (long)yb * W + xa, C);
     const float* p11 = pixptr<BF>(feat, ib + (long)yb * W + xb, C);
     for (int c = lane; c < C; c += 64)
-        S[(long)bp * C + c] = ((ldf<BF>(p00, c) * w00 + ldf<BF>(p01, c) * w01) + ldf<BF>(p10, c) * w10) + ldf<BF>(p11, c) * w11;
+        S[(long)bp * C + c] = ((ldf<BF, F>(p00, c) * w00 + ldf<BF, F>(p01, c) * w01) + ldf<BF, F>(p10, c) * w10) + ldf<BF, F>(p11, c) * w11;
 }
 
 hipError_t launch_sample_ref(const float* feat, const float* ref, float* S, int* idx, int B, int J, int H,
                              int W, int C, hipStream_t s, int feat_bf16) {
     const int BJ = B * J;
-    if (feat_bf16)
-        hipLaunchKernelGGL(sample_ref_kernel<true>, dim3((BJ + 3) / 4), dim3(256), 0, s, feat, ref, S, idx, BJ, J, H, W, C);
+    if (feat_bf16)          // (a format code: 0 fp32, 1 bf16, 2 fp16)
+        with_fmt(feat_bf16 == 2, [&](auto f) {
+            hipLaunchKernelGGL((sample_ref_kernel<true, decltype(f)>), dim3((BJ + 3) / 4), dim3(256), 0, s, feat, ref, S, idx, BJ, J, H, W, C);
+            return 0;
+        });
     else
     hipLaunchKernelGGL(sample_ref_kernel<false>, dim3((BJ + 3) / 4), dim3(256), 0, s, feat, ref, S, idx, BJ, J, H, W, C);
     return hipGetLastError();
 }
 
 // ---- LayerNorm, one wave per row (two-pass, like ATen's CPU kernel) -------------------------------
-__device__ __forceinline__ unsigned short f2bf_l(float f) { return to_bf16(f); }    // round-to-nearest-even, like every bf16 store of the path
 // OB: the normalised rows are written as bf16 (the A operand of a bf16 MFMA projection, compute_dtype = bf16)
-template <int MAXV, bool OB = false>
+template <int MAXV, bool OB = false, class F = Bf16Fmt>
 __global__ void layernorm_kernel(const float* __restrict__ in, RowMap imap, const float* __restrict__ add,
                                  RowMap amap, const float* __restrict__ g, const float* __restrict__ b,
                                  float eps, float* __restrict__ out, int rows, int C) {
@@ -160,7 +162,7 @@ __global__ void layernorm_kernel(const float* __restrict__ in, RowMap imap, cons
         const int c = lane + 64 * i;
         if (c < C) {
             const float y = (v[i] - mean) * rstd * g[c] + b[c];
-            if (OB) reinterpret_cast<unsigned short*>(out)[(long)r * C + c] = f2bf_l(y);
+            if (OB) reinterpret_cast<unsigned short*>(out)[(long)r * C + c] = F::narrow(y);
             else out[(long)r * C + c] = y;
         }
     }
@@ -169,15 +171,18 @@ __global__ void layernorm_kernel(const float* __restrict__ in, RowMap imap, cons
 hipError_t launch_layernorm(const float* in, RowMap imap, const float* add, RowMap amap, const float* g,
                             const float* b, float eps, float* out, int rows, int C, hipStream_t s, int out_bf16) {
     dim3 grid((rows + 3) / 4), block(256);
-    if (out_bf16) {
-        if (C <= 128)
-            hipLaunchKernelGGL((layernorm_kernel<2, true>), grid, block, 0, s, in, imap, add, amap, g, b, eps, out, rows, C);
-        else if (C <= 640)
-            hipLaunchKernelGGL((layernorm_kernel<10, true>), grid, block, 0, s, in, imap, add, amap, g, b, eps, out, rows, C);
-        else if (C <= 1536)
-            hipLaunchKernelGGL((layernorm_kernel<24, true>), grid, block, 0, s, in, imap, add, amap, g, b, eps, out, rows, C);
-        else
-            return hipErrorInvalidValue;
+    if (out_bf16) {         // (a format code: 1 bf16, 2 fp16)
+        if (C > 1536) return hipErrorInvalidValue;
+        with_fmt(out_bf16 == 2, [&](auto f) {
+            using F = decltype(f);
+            if (C <= 128)
+                hipLaunchKernelGGL((layernorm_kernel<2, true, F>), grid, block, 0, s, in, imap, add, amap, g, b, eps, out, rows, C);
+            else if (C <= 640)
+                hipLaunchKernelGGL((layernorm_kernel<10, true, F>), grid, block, 0, s, in, imap, add, amap, g, b, eps, out, rows, C);
+            else
+                hipLaunchKernelGGL((layernorm_kernel<24, true, F>), grid, block, 0, s, in, imap, add, amap, g, b, eps, out, rows, C);
+            return 0;
+        });
         return hipGetLastError();
     }
     if (C <= 128)
@@ -198,14 +203,14 @@ hipError_t launch_layernorm(const float* in, RowMap imap, const float* add, RowM
 // so only U = sum_s w_s v_s  [(b,p,h), C_l] is produced here and the projection is a GEMM with
 // M = B*17*4 rows instead of B*17*16 (the [B,17,16,C_l] tensor is never materialised).
 // One block per (b, p); wave w handles level w; lanes stride over channels.
-template <bool BF>
+template <bool BF, class F = Bf16Fmt>
 __device__ __forceinline__ f32x4 ldq(const float* pix, int q) {       // channels 4 q .. 4 q + 3 of a pixel
     if (!BF) return *reinterpret_cast<const f32x4*>(pix + 4 * q);
     const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(pix) + 4 * q);
-    return f32x4{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
+    return f32x4{F::lo(r.x), F::hi(r.x), F::lo(r.y), F::hi(r.y)};
 }
 
-template <int NS, bool BF>
+template <int NS, bool BF, class F = Bf16Fmt>
 __global__ void deform_sample_kernel(DeformArgs a) {
     const int bp = blockIdx.x;
     const int l = threadIdx.x >> 6;
@@ -261,7 +266,7 @@ __global__ void deform_sample_kernel(DeformArgs a) {
             f32x4 u = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
-                const f32x4 f00 = ldq<BF>(p00[s], cq), f01 = ldq<BF>(p01[s], cq), f10 = ldq<BF>(p10[s], cq), f11 = ldq<BF>(p11[s], cq);
+                const f32x4 f00 = ldq<BF, F>(p00[s], cq), f01 = ldq<BF, F>(p01[s], cq), f10 = ldq<BF, F>(p10[s], cq), f11 = ldq<BF, F>(p11[s], cq);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) u[e] += ((f00[e] * w00[s] + f01[e] * w01[s]) + f10[e] * w10[s]) + f11[e] * w11[s];
             }
@@ -274,25 +279,29 @@ hipError_t launch_deform_sample(const DeformArgs& a, hipStream_t s) {
     if (a.NS != 4 || a.L > 4) return hipErrorInvalidValue;
     for (int l = 0; l < a.L; ++l)
         if (a.C[l] < 4 || (a.C[l] & 3)) return hipErrorInvalidValue;
-    if (a.feat_bf16) hipLaunchKernelGGL((deform_sample_kernel<4, true>), dim3(a.B * a.J), dim3(64 * a.L), 0, s, a);
+    if (a.feat_bf16)
+        with_fmt(a.feat_bf16 == 2, [&](auto f) {
+            hipLaunchKernelGGL((deform_sample_kernel<4, true, decltype(f)>), dim3(a.B * a.J), dim3(64 * a.L), 0, s, a);
+            return 0;
+        });
     else hipLaunchKernelGGL((deform_sample_kernel<4, false>), dim3(a.B * a.J), dim3(64 * a.L), 0, s, a);
     return hipGetLastError();
 }
 
 // store 4 consecutive attention outputs as fp32 or (OB) bf16
-template <bool OB>
+template <bool OB, class F = Bf16Fmt>
 __device__ __forceinline__ void st4(float* out, long idx, f32x4 v) {
     if (!OB) { *reinterpret_cast<f32x4*>(out + idx) = v; return; }
     unsigned short* o = reinterpret_cast<unsigned short*>(out) + idx;
     uint2 pk;
-    pk.x = pack_bf16x2(v[0], v[1]);
-    pk.y = pack_bf16x2(v[2], v[3]);
+    pk.x = F::pack2(v[0], v[1]);
+    pk.y = F::pack2(v[2], v[3]);
     *reinterpret_cast<uint2*>(o) = pk;
 }
 
 // ---- tiny attention (Attention.forward pose_dformer.py:46-59): 5 or 17 tokens per group -----------
 // qkv row layout [3][heads][d] (the reshape at :49).  One thread per (group, head, query).
-template <int NMAX, bool OB = false>
+template <int NMAX, bool OB = false, class F = Bf16Fmt>
 __global__ void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int groups, int N,
                                  int heads, int d, float scale) {
     const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -339,7 +348,7 @@ __global__ void attention_kernel(const float* __restrict__ qkv, float* __restric
                 acc += va * (sc[j] * inv);
             }
         }
-        st4<OB>(out, o + c, acc);
+        st4<OB, F>(out, o + c, acc);
     }
 }
 
@@ -347,7 +356,7 @@ __global__ void attention_kernel(const float* __restrict__ qkv, float* __restric
 // q.k dot products are combined with two shuffles, every lane then accumulates its own slice of P.V).
 // 4x the threads of the kernel above for the 17-token joint attention, where B*8*17 threads cannot fill
 // 256 CUs.
-template <int NMAX, int PARTS, bool OB = false>
+template <int NMAX, int PARTS, bool OB = false, class F = Bf16Fmt>
 __global__ void attention_split_kernel(const float* __restrict__ qkv, float* __restrict__ out, int groups, int N,
                                        int heads, int d, float scale) {
     const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -400,14 +409,14 @@ __global__ void attention_split_kernel(const float* __restrict__ qkv, float* __r
                 acc += va * (sc[j] * inv);
             }
         }
-        st4<OB>(out, o + c, acc);
+        st4<OB, F>(out, o + c, acc);
     }
 }
 
 // The 17-token joint attention (B * 8 (group, head) pairs of 17 x 80 floats): one wave per pair, q / k / v
 // staged in LDS with coalesced reads, 17 x 17 scores, one softmax row per lane, P.V with d-contiguous stores.
 // (The per-query kernels above read k / v rows straight from global memory: 36 us per block at B = 64.)
-template <int NMAX, bool OB = false>
+template <int NMAX, bool OB = false, class F = Bf16Fmt>
 __global__ __launch_bounds__(256) void attention_lds_kernel(const float* __restrict__ qkv, float* __restrict__ out, int N,
                                                            int heads, int d, float scale) {
     extern __shared__ float sm[];
@@ -452,7 +461,7 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(const float* __restr
         const int t = idx / d, c = idx - t * d;
         float acc = 0.f;
         for (int j = 0; j < N; ++j) acc += P[t * (NMAX + 1) + j] * v[j * ld + c];
-        if (OB) reinterpret_cast<unsigned short*>(out)[ob + (long)t * (heads * d) + c] = f2bf_l(acc);
+        if (OB) reinterpret_cast<unsigned short*>(out)[ob + (long)t * (heads * d) + c] = F::narrow(acc);
         else out[ob + (long)t * (heads * d) + c] = acc;
     }
 }
@@ -463,7 +472,7 @@ hipError_t launch_attention(const float* qkv, float* out, int groups, int N, int
     if (N > 5 && N <= 17 && (size_t)(3 * 17 * (d + 1) + 17 * 18) * sizeof(float) <= 64 * 1024 && (long)groups * heads <= 0x7fffffffL) {
         const size_t lds = (size_t)(3 * 17 * (d + 1) + 17 * 18) * sizeof(float);
         const dim3 grid((unsigned)((long)groups * heads)), block(256);
-        if (out_bf16) hipLaunchKernelGGL((attention_lds_kernel<17, true>), grid, block, lds, s, qkv, out, N, heads, d, scale);
+        if (out_bf16) with_fmt(out_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((attention_lds_kernel<17, true, decltype(f)>), grid, block, lds, s, qkv, out, N, heads, d, scale); return 0; });
         else hipLaunchKernelGGL((attention_lds_kernel<17, false>), grid, block, lds, s, qkv, out, N, heads, d, scale);
         return hipGetLastError();
     }
@@ -471,10 +480,10 @@ hipError_t launch_attention(const float* qkv, float* out, int groups, int N, int
         const long total = (long)groups * heads * N * 4;
         dim3 grid((unsigned)((total + 255) / 256)), block(256);
         if (N <= 5) {
-            if (out_bf16) hipLaunchKernelGGL((attention_split_kernel<5, 4, true>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale);
+            if (out_bf16) with_fmt(out_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((attention_split_kernel<5, 4, true, decltype(f)>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale); return 0; });
             else hipLaunchKernelGGL((attention_split_kernel<5, 4, false>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale);
         } else {
-            if (out_bf16) hipLaunchKernelGGL((attention_split_kernel<17, 4, true>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale);
+            if (out_bf16) with_fmt(out_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((attention_split_kernel<17, 4, true, decltype(f)>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale); return 0; });
             else hipLaunchKernelGGL((attention_split_kernel<17, 4, false>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale);
         }
         return hipGetLastError();
@@ -482,10 +491,10 @@ hipError_t launch_attention(const float* qkv, float* out, int groups, int N, int
     const long total = (long)groups * heads * N;
     dim3 grid((unsigned)((total + 127) / 128)), block(128);
     if (N <= 5) {
-        if (out_bf16) hipLaunchKernelGGL((attention_kernel<5, true>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale);
+        if (out_bf16) with_fmt(out_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((attention_kernel<5, true, decltype(f)>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale); return 0; });
         else hipLaunchKernelGGL((attention_kernel<5, false>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale);
     } else if (N <= 17) {
-        if (out_bf16) hipLaunchKernelGGL((attention_kernel<17, true>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale);
+        if (out_bf16) with_fmt(out_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((attention_kernel<17, true, decltype(f)>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale); return 0; });
         else hipLaunchKernelGGL((attention_kernel<17, false>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale);
     } else {
         return hipErrorInvalidValue;

@@ -27,12 +27,12 @@ __device__ __forceinline__ float wsum(float v) {
 typedef BilinearCorner CornerF;     // kernels.h: the one corner rule of both sampling sites
 template <bool BORDER>
 __device__ __forceinline__ CornerF corner_f(float gx, float gy, int H, int W) { return bilinear_corner<BORDER>(gx, gy, H, W); }
-template <bool BF>
+template <bool BF, class F = Bf16Fmt>
 __device__ __forceinline__ float ld1(const float* pix, int c) {
     if (!BF) return pix[c];
-    return __uint_as_float((unsigned)reinterpret_cast<const unsigned short*>(pix)[c] << 16);
+    return F::widen(reinterpret_cast<const unsigned short*>(pix)[c]);
 }
-template <bool BF>
+template <bool BF, class F = Bf16Fmt>
 __device__ __forceinline__ const float* pixp(const float* base, long pixel_index, int C) {
     if (!BF) return base + pixel_index * C;
     return reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(base) + pixel_index * C);
@@ -44,7 +44,7 @@ __device__ __forceinline__ const float* pixp(const float* base, long pixel_index
 static constexpr int EG = 1;
 
 // One block = EG consecutive (b, p) pairs; wave l = level l.  X layout [B, J, L1, C] ("b p l c").
-template <bool BF, bool PROJ = true>
+template <bool BF, bool PROJ = true, class F = Bf16Fmt>
 __global__ __launch_bounds__(256) void embed_kernel(EmbedArgs a) {
     __shared__ float S[4][EG][512];           // sampled rows, level l: C_l <= 512 channels
     __shared__ float ref_s[EG][2];
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void embed_kernel(EmbedArgs a) {
         const float* p10 = pixp<BF>(a.feat[l], ib + (long)yb * W + xa, Cl);
         const float* p11 = pixp<BF>(a.feat[l], ib + (long)yb * W + xb, Cl);
         for (int c = lane; c < Cl; c += 64) {
-            const float v = ((ld1<BF>(p00, c) * w00 + ld1<BF>(p01, c) * w01) + ld1<BF>(p10, c) * w10) + ld1<BF>(p11, c) * w11;
+            const float v = ((ld1<BF, F>(p00, c) * w00 + ld1<BF, F>(p01, c) * w01) + ld1<BF, F>(p10, c) * w10) + ld1<BF, F>(p11, c) * w11;
             S[l][g][c] = v;
             if (a.sampled[l]) a.sampled[l][(long)bp * Cl + c] = v;
         }
@@ -146,11 +146,11 @@ hipError_t launch_embed(const EmbedArgs& a, hipStream_t s) {
     bool split = a.C % 32 == 0;
     for (int l = 0; l < a.L; ++l) split = split && a.sampled[l] && a.Cl[l] % 8 == 0 && a.Cl[l] <= 384;
     if (!split) {
-        if (a.feat_bf16) hipLaunchKernelGGL(embed_kernel<true>, grid, block, 0, s, a);
+        if (a.feat_bf16) with_fmt(a.feat_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((embed_kernel<true, true, decltype(f)>), grid, block, 0, s, a); return 0; });
         else hipLaunchKernelGGL(embed_kernel<false>, grid, block, 0, s, a);
         return hipGetLastError();
     }
-    if (a.feat_bf16) hipLaunchKernelGGL((embed_kernel<true, false>), grid, block, 0, s, a);
+    if (a.feat_bf16) with_fmt(a.feat_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((embed_kernel<true, false, decltype(f)>), grid, block, 0, s, a); return 0; });
     else hipLaunchKernelGGL((embed_kernel<false, false>), grid, block, 0, s, a);
     hipLaunchKernelGGL(embed_feat_kernel, dim3((a.BJ + 31) / 32, a.L, a.C / 32), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -168,12 +168,11 @@ static constexpr int CTX_NH = 4, CTX_NS = 4, CTX_NK = CTX_NH * CTX_NS;      // 4
 
 // four consecutive channels (c % 4 == 0) of the NHWC pixel that starts `elem_off` elements after `base`, as fp32
 // (bf16 storage: one 8-byte load)
-template <bool BF>
+template <bool BF, class F = Bf16Fmt>
 __device__ __forceinline__ f32x4 ld4(const float* base, long elem_off, int c) {
     if (!BF) return *reinterpret_cast<const f32x4*>(base + elem_off + c);
     const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + elem_off + c);
-    return f32x4{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
-                 __uint_as_float(r.y & 0xffff0000u)};
+    return f32x4{F::lo(r.x), F::hi(r.x), F::lo(r.y), F::hi(r.y)};
 }
 
 // Work distribution inside a wave (one (b, p, level) per wave).  Everything that is a per-sample scalar in the
@@ -186,7 +185,7 @@ __device__ __forceinline__ f32x4 ld4(const float* base, long elem_off, int c) {
 #ifndef CTX_MIN_BLOCKS
 #define CTX_MIN_BLOCKS 1          // (tools/ab_define.sh: A/B builds)
 #endif
-template <bool BF, bool PROJ = true>
+template <bool BF, bool PROJ = true, class F = Bf16Fmt>
 __global__ __launch_bounds__(256, CTX_MIN_BLOCKS) void ctx_attn_kernel(CtxAttnArgs a) {
     extern __shared__ float sm[];
     // per wave (level): Q [C] | AO [3*NK] | SW [NK][4] weights | SO [NK][4] pixel offsets (int) | U [NH * Cl]
@@ -285,8 +284,8 @@ __global__ __launch_bounds__(256, CTX_MIN_BLOCKS) void ctx_attn_kernel(CtxAttnAr
             for (int k = 0; k < CTX_NS; ++k) {
                 const int kk = h * CTX_NS + k;
                 const f32x4 w = *reinterpret_cast<const f32x4*>(SW + kk * 4);
-                const f32x4 f0 = ld4<BF>(feat, SO[kk * 4 + 0], c), f1 = ld4<BF>(feat, SO[kk * 4 + 1], c);
-                const f32x4 f2 = ld4<BF>(feat, SO[kk * 4 + 2], c), f3 = ld4<BF>(feat, SO[kk * 4 + 3], c);
+                const f32x4 f0 = ld4<BF, F>(feat, SO[kk * 4 + 0], c), f1 = ld4<BF, F>(feat, SO[kk * 4 + 1], c);
+                const f32x4 f2 = ld4<BF, F>(feat, SO[kk * 4 + 2], c), f3 = ld4<BF, F>(feat, SO[kk * 4 + 3], c);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) u[e] += ((f0[e] * w[0] + f1[e] * w[1]) + f2[e] * w[2]) + f3[e] * w[3];
             }
@@ -453,11 +452,11 @@ hipError_t launch_ctx_attn(const CtxAttnArgs& a_in, hipStream_t s) {
     bool split = a.U[0] != nullptr && a.C == CTX_NH * 32;          // (HD = 32: the MFMA's width)
     for (int l = 0; l < a.L; ++l) split = split && a.U[l] && a.Cl[l] % 8 == 0 && a.Cl[l] <= 384;
     if (!split) {
-        if (a.feat_bf16) hipLaunchKernelGGL(ctx_attn_kernel<true>, grid, block, lds, s, a);
+        if (a.feat_bf16) with_fmt(a.feat_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((ctx_attn_kernel<true, true, decltype(f)>), grid, block, lds, s, a); return 0; });
         else hipLaunchKernelGGL(ctx_attn_kernel<false>, grid, block, lds, s, a);
         return hipGetLastError();
     }
-    if (a.feat_bf16) hipLaunchKernelGGL((ctx_attn_kernel<true, false>), grid, block, lds, s, a);
+    if (a.feat_bf16) with_fmt(a.feat_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((ctx_attn_kernel<true, false, decltype(f)>), grid, block, lds, s, a); return 0; });
     else hipLaunchKernelGGL((ctx_attn_kernel<false, false>), grid, block, lds, s, a);
     CtxProjArgs q{};
     for (int l = 0; l < a.L; ++l) { q.U[l] = a.U[l]; q.Wp[l] = a.Wp[l]; q.bp[l] = a.bp[l]; q.Cl[l] = a.Cl[l]; }

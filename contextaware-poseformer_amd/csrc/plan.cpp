@@ -121,7 +121,7 @@ Tensor Engine::conv_bn(const std::string& conv, const std::string& bn, const Ten
     pk.Cin = x.C;
     pk.ks = ks;
     pk.K = ks * ks * x.C;
-    const bool use_bf16 = bf16() && x.C % 8 == 0;       // the Cin = 3 stem stays on the fp32 kernel
+    const bool use_bf16 = b16() && x.C % 8 == 0;       // the Cin = 3 stem stays on the fp32 kernel
     pk.bf16 = use_bf16;
     pk.Kpad = use_bf16 ? round64(pk.K) : round32(pk.K);
     // Winograd F(2,3) along W (igemm_wino.hip) for the 3x3 stride-1 fp32 convs: 1.5x fewer MFMAs; block tiles of 64 x 64,
@@ -165,7 +165,7 @@ Tensor Engine::conv_bn(const std::string& conv, const std::string& bn, const Ten
     }
     op.bf16 = use_bf16 ? 1 : 0;
     op.wino = as_wino ? 1 : 0;
-    op.out_bf16 = (bf16() && !use_bf16) ? 1 : 0;
+    op.out_bf16 = (b16() && !use_bf16) ? 1 : 0;
     y.buf = new_buffer(act_elems((size_t)y.H * y.W * Cout), conv);
     op.out = y.buf;
     push(op);
@@ -184,7 +184,7 @@ static Tensor fuse_sum(Engine& e, const std::string& name, const Tensor* terms, 
         e.use(terms[i].buf);
     }
     op.H = like.H; op.W = like.W; op.C = like.C; op.relu = relu;
-    op.bf16 = e.bf16() ? 1 : 0;
+    op.bf16 = e.b16() ? 1 : 0;
     Tensor y = like;
     y.buf = e.new_buffer(e.act_elems((size_t)like.H * like.W * like.C), name);
     op.out = y.buf;
@@ -203,7 +203,7 @@ static Tensor hr_basic_block(Engine& e, const std::string& p, const Tensor& x) {
     // conv1's output has ONE reader, conv2, and both convs have the same tiles: where both run the two-fp16-piece tile (a matter of the
     // batch, decided per launch in gemm_args) it travels as split fp16 planes + one scale exponent per (tile, 16-channel chunk) --
     // igemm_f32h2_ws_tile.h PLANES: the consumer's K loop loses its maximum / split / scale-exchange phase.  Same bytes, same buffer.
-    if (e.plan.use_h2_planes && e.plan.x3_h2 && !e.bf16() && x.C % 16 == 0 && e.packs[e.ops[i1].pack].x3 && e.packs[e.ops[i2].pack].x3) {
+    if (e.plan.use_h2_planes && e.plan.x3_h2 && !e.b16() && x.C % 16 == 0 && e.packs[e.ops[i1].pack].x3 && e.packs[e.ops[i2].pack].x3) {
         const int tiles_pf = f32h2_tiles_m(1, x.H, x.W);
         if (tiles_pf > 0) {
             const int b = e.new_buffer((size_t)tiles_pf * (x.C / 16) + 16, p + ".conv1.exps");
@@ -221,7 +221,7 @@ static Tensor hr_basic_block(Engine& e, const std::string& p, const Tensor& x) {
 // (no two of them share workspace) from conv1 to conv3; the ops remember conv3 (capf_op_describe: their checkpoint is the whole block).
 // `fork` = index of the region's fork op: fork, conv1, conv2, downsample, join, conv3.
 static void bneck0_mark(Engine& e, int fork) {
-    if (!e.plan.use_bneck || !e.bf16() || fork + 5 >= (int)e.ops.size()) return;
+    if (!e.plan.use_bneck || !e.b16() || fork + 5 >= (int)e.ops.size()) return;
     const int c1 = fork + 1, c2 = fork + 2, ds = fork + 3, c3 = fork + 5;
     const Op &o1 = e.ops[c1], &o3 = e.ops[c3];
     if (e.ops[fork].kind != OP_FORK || e.ops[fork + 4].kind != OP_JOIN || o1.Cin != 64 || o1.N != 64 || o3.N != 256 || e.ops[c2].stride != 1 || e.ops[c2].ks != 3) return;
@@ -235,7 +235,7 @@ static void bneck0_mark(Engine& e, int fork) {
 
 // ... and an identity bottleneck (conv1 at `c1`, conv2, conv3 + x): x, conv1's and conv2's outputs and y alive from conv1 to conv3
 static void bneck1_mark(Engine& e, int c1) {
-    if (!e.plan.use_bneck || !e.bf16() || c1 + 2 >= (int)e.ops.size()) return;
+    if (!e.plan.use_bneck || !e.b16() || c1 + 2 >= (int)e.ops.size()) return;
     const Op &o1 = e.ops[c1], &o2 = e.ops[c1 + 1], &o3 = e.ops[c1 + 2];
     if (o1.kind != OP_GEMM || o2.kind != OP_GEMM || o3.kind != OP_GEMM || o1.Cin != 256 || o1.N != 64 || o2.ks != 3 || o2.stride != 1 || o3.N != 256 || o3.aux != o1.in[0]) return;
     for (int b : {o1.in[0], o1.out, o2.out, o3.out}) {
@@ -374,7 +374,7 @@ static Tensor pool_or_resize(Engine& e, OpKind kind, const std::string& name, co
     e.use(x.buf);
     if (add) { op.aux = add->buf; e.use(add->buf); }           // resize only: out = resize(x) + add
     op.H = x.H; op.W = x.W; op.C = x.C; op.Ho = Ho; op.Wo = Wo;
-    op.bf16 = e.bf16() ? 1 : 0;
+    op.bf16 = e.b16() ? 1 : 0;
     Tensor y{-1, Ho, Wo, x.C};
     y.buf = e.new_buffer(e.act_elems((size_t)Ho * Wo * x.C), name);
     op.out = y.buf;
@@ -420,7 +420,7 @@ void Engine::build_cpn(Tensor img, Tensor feats[4]) {
     for (int i = 0; i < 4; ++i) {
         const Tensor& src = c[3 - i];
         const std::string lp = G + ".laterals." + std::to_string(i);
-        if (i > 0 && bf16() && plan.use_upadd) {
+        if (i > 0 && b16() && plan.use_upadd) {
             // bf16: the low-resolution conv of the upsampled path first, then the lateral conv with `+ bilinear_x2(t)` behind its ReLU in the
             // epilogue (igemm_bf16_kernel<.., UPADD>): no resize-add launch, the lateral map never travels to HBM and back on its own
             // (lateral: write + read of 453 MB at the largest level and batch 128), and it meets the upsampled term in fp32
@@ -523,7 +523,7 @@ static int make_linear_pack(Engine& e, std::initializer_list<LinearRef> lins, bo
     pk.bf16 = as_bf16;                         // bf16 copy [N][Kpad] for the bf16 MFMA projections (compute_dtype = bf16)
     // the fp32 projections also as two fp16 pieces for igemm_f32h2.hip, packed LAZILY (Engine::ensure_h2g_lifter): a training loop changes the
     // weights every step and its forward runs train.cpp's GEMMs, so the copy is rebuilt only when an inference forward needs it
-    if (!as_bf16 && !quad && e.plan.use_h2g && !e.bf16() && K % 4 == 0 && N % 4 == 0) { pk.h2g = true; pk.h2g_Kpad = round32(K); }
+    if (!as_bf16 && !quad && e.plan.use_h2g && !e.b16() && K % 4 == 0 && N % 4 == 0) { pk.h2g = true; pk.h2g_Kpad = round32(K); }
     e.packs.push_back(pk);
     return (int)e.packs.size() - 1;
 }
@@ -663,7 +663,7 @@ void Engine::build_lifter(const Tensor feats[4]) {
     // blocks keep their LayerNorm launch
     // (compute_dtype = bf16: the projections take bf16 A rows, which the LayerNorm kernel writes directly)
     // lifter projections (qkv / proj / fc1 / fc2) on the bf16 MFMA path; CAPF_PLAN_LIFTER_FP32 keeps them (and their LayerNorm folding) fp32
-    const bool lb = bf16() && !(cfg.plan_flags & CAPF_PLAN_LIFTER_FP32);
+    const bool lb = b16() && !(cfg.plan_flags & CAPF_PLAN_LIFTER_FP32);
     auto ln_fold_ok = [&](int dim) { return plan.fused_lifter && dim <= 256 && !lb; };
     const bool ln_fold = ln_fold_ok(C);
     // the MLP half of a block on the rows `xm` of X, x += fc2(gelu(fc1(norm2(x)))), in the form the caller chose: one launch (lifter_chain.hip,
@@ -708,8 +708,8 @@ void Engine::build_lifter(const Tensor feats[4]) {
         op.coord = net.coord;
         op.pos = net.pos;
         op.smp.J = J; op.smp.L = L; op.smp.L1 = L1; op.C = C;
-        op.bf16 = bf16() ? 1 : 0;
-        op.feat_bf16 = maps_bf16() ? 1 : 0;
+        op.bf16 = b16() ? 1 : 0;
+        op.feat_bf16 = feat_fmt();
         use(X);
         for (int l = 0; l < L; ++l) {
             const std::string ls = std::to_string(l);
@@ -744,8 +744,8 @@ void Engine::build_lifter(const Tensor feats[4]) {
         op.name = "sample_ref." + ls;
         op.in[0] = feats[l].buf;
         op.H = feats[l].H; op.W = feats[l].W; op.C = Cl[l]; op.smp.J = J;
-        op.bf16 = bf16() ? 1 : 0;
-        op.feat_bf16 = maps_bf16() ? 1 : 0;
+        op.bf16 = b16() ? 1 : 0;
+        op.feat_bf16 = feat_fmt();
         use(feats[l].buf);
         const int S = new_buffer((size_t)J * Cl[l], "sampled" + ls);
         const int I = new_buffer((size_t)J * 2, "idx" + ls);
@@ -802,8 +802,8 @@ void Engine::build_lifter(const Tensor feats[4]) {
                 }
                 op.flops_per_frame += 2.0 * J * L * (double)C * 3 * NH * NS;
                 op.smp.J = J; op.smp.L = L; op.smp.NH = NH; op.smp.NS = NS; op.C = C;
-                op.bf16 = bf16() ? 1 : 0;
-                op.feat_bf16 = maps_bf16() ? 1 : 0;
+                op.bf16 = b16() ? 1 : 0;
+                op.feat_bf16 = feat_fmt();
                 op.tap_pos = tap_pos; op.tap_idx = tap_idx;
                 push(op);
             } else {
@@ -824,8 +824,8 @@ void Engine::build_lifter(const Tensor feats[4]) {
                     use(U[l]);
                 }
                 op.smp.J = J; op.smp.L = L; op.smp.NH = NH; op.smp.NS = NS;
-                op.bf16 = bf16() ? 1 : 0;
-                op.feat_bf16 = maps_bf16() ? 1 : 0;
+                op.bf16 = b16() ? 1 : 0;
+                op.feat_bf16 = feat_fmt();
                 op.tap_pos = tap_pos; op.tap_idx = tap_idx;
                 push(op);
             }
@@ -837,7 +837,7 @@ void Engine::build_lifter(const Tensor feats[4]) {
             }
             }
             // the MLP half as one launch on the context tokens' rows where the chain kernel takes the width
-            const bool mlp_chain = plan.fused_lifter && plan.use_h2g && !lb && !bf16() && res_chain_ok(C, 5, 8, 1);
+            const bool mlp_chain = plan.fused_lifter && plan.use_h2g && !lb && !b16() && res_chain_ok(C, 5, 8, 1);
             mlp_half(c.mlp, n, tok, (long)J * L, C, 1e-5f, mlp_chain, ln_fold);
         }
     }
@@ -850,7 +850,7 @@ void Engine::build_lifter(const Tensor feats[4]) {
         // the res blocks (tokens of ONE joint, 128 wide) as one launch: a workgroup takes 6 joints through every block without leaving
         // the CU (lifter_chain.hip); fp32 lifter on the two-piece packs only -- the bf16 plan and CAPF_PLAN_NO_FUSED_LIFTER /
         // CAPF_PLAN_NO_F32H2_GEMM keep one launch per op
-        if (plan.fused_lifter && plan.use_h2g && !lb && !bf16() && groups_pf > 1 && res_chain_ok(dim, tokens, cfg.num_heads, nblk)) {
+        if (plan.fused_lifter && plan.use_h2g && !lb && !b16() && groups_pf > 1 && res_chain_ok(dim, tokens, cfg.num_heads, nblk)) {
             Op op;
             op.kind = OP_RES_CHAIN;
             op.name = tag + ".chain";
@@ -1074,7 +1074,7 @@ bool Engine::set_plan_switches() {
     if (cfg.plan_flags & CAPF_PLAN_F32X3_EXACT) p.x3_h2 = false;
     if (cfg.plan_flags & CAPF_PLAN_NO_F32H2_GEMM) p.use_h2g = false;
     if (cfg.plan_flags & CAPF_PLAN_BF16_F32_STREAM) {
-        if (!bf16()) { err = "CAPF_PLAN_BF16_F32_STREAM needs compute_dtype = CAPF_BF16"; return false; }
+        if (!b16()) { err = "CAPF_PLAN_BF16_F32_STREAM needs compute_dtype = CAPF_BF16 (not CAPF_F32; CAPF_F16 is refused at capf_create)"; return false; }
         if (cfg.backbone != CAPF_HRNET) { err = "CAPF_PLAN_BF16_F32_STREAM is an HRNet plan (CPN50 is not supported)"; return false; }
         if (cfg.plan_flags != CAPF_PLAN_BF16_F32_STREAM) { err = "CAPF_PLAN_BF16_F32_STREAM cannot be combined with other plan flags"; return false; }
         p.f32_stream = true;
@@ -1141,7 +1141,7 @@ bool Engine::build() {
         return false;
     }
     for (int l = 0; l < 4; ++l) {
-        name_tensor(*this, "feat" + std::to_string(l), feats[l].buf, {-1, feats[l].H, feats[l].W, feats[l].C}, maps_bf16() ? 2 : 0);
+        name_tensor(*this, "feat" + std::to_string(l), feats[l].buf, {-1, feats[l].H, feats[l].W, feats[l].C}, maps_bf16() ? dt16() : 0);
         const int expect = cfg.backbone == CAPF_CPN50 ? cfg.base_dim : cfg.base_dim << l;
         if (feats[l].C != expect) {
             err = "poseformer.base_dim does not match the backbone's context-map widths";

@@ -109,7 +109,7 @@ void Engine::t_h2_plan() {
     t_h2_tab.clear();
     t_h2_elems = t_h2_max_elems = 0;
     t_h2_tiles = 0;
-    if (!plan.use_h2g || bf16() || !cfg.training) return;
+    if (!plan.use_h2g || b16() || !cfg.training) return;
     const int Lv = cfg.levels, C = cfg.embed_dim_ratio, NH = cfg.deform_heads, NS = cfg.deform_samples, DEP = depth();
     auto add = [&](const LinearRef& r, bool fwd, bool bwd) {
         if (r.N < 64) fwd = false;                           // (output columns of y = x W^T ...

@@ -57,15 +57,16 @@ def make_capf_config(config, height=256, width=192, context_blocks=True, compute
     c.deform_heads = 4
     c.deform_samples = 4
     c.context_blocks = 1 if context_blocks else 0
-    if compute_dtype not in ("fp32", "bf16"):
-        raise ValueError("compute_dtype must be 'fp32' or 'bf16'")
-    c.compute_dtype = 1 if compute_dtype == "bf16" else 0
+    if compute_dtype not in ("fp32", "bf16", "fp16"):
+        raise ValueError("compute_dtype must be 'fp32', 'bf16' or 'fp16'")
+    c.compute_dtype = {"fp32": 0, "bf16": 1, "fp16": 2}[compute_dtype]      # capf_dtype
     c.max_batch = MAX_BATCH
     c.height, c.width = height, width
     # workspace also holds what capf_backward needs (6.4 MB/frame).  depth != levels trains at the ContextPose_mpi widths only
     # (run_3dhp.py:219-232: embed 64 over base 32, 96 over 48; csrc/plan.cpp): other widths get an inference plan there
     mpi_width = (c.base_dim, c.embed_dim_ratio) in ((32, 64), (48, 96))
-    c.training = 1 if c.depth in (0, c.levels) or mpi_width else 0
+    # (fp16 is an inference plan: capf_create refuses it with training = 1)
+    c.training = 1 if (c.depth in (0, c.levels) or mpi_width) and compute_dtype != "fp16" else 0
     c.plan_flags = int(plan_flags)  # 0 = the product plan (capf.lib.PLAN_*: take a kernel family out, parity tests only)
     return c
 

@@ -53,9 +53,10 @@ class _LifterStep(torch.autograd.Function):
 
 class CA_PF(nn.Module):
     def __init__(self, config, device="cuda:0", compute_dtype="fp32", context_blocks=True, plan_flags=0):
-        """compute_dtype: 'fp32' (exact fp32 MFMA, the reference's precision) or 'bf16' (backbone convolutions on
+        """compute_dtype: 'fp32' (exact fp32 MFMA, the reference's precision), 'bf16' (backbone convolutions on
         bf16 MFMA with bf16 activations and fp32 accumulation; the lifter stays fp32) — an extension of the
-        reference signature for BASELINE.json's bf16 configurations."""
+        reference signature for BASELINE.json's bf16 configurations — or 'fp16' (the bf16 plan with IEEE fp16 as its
+        16-bit element: same speed, 11 significand bits instead of 8; HRNet backbones, inference only)."""
         super().__init__()
         self.compute_dtype = compute_dtype
         self.plan_flags = plan_flags               # capf.lib.PLAN_* bits: parity tests compare kernel families; 0 = product plan

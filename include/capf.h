@@ -38,7 +38,10 @@ enum capf_status {
 };
 
 enum capf_backbone { CAPF_HRNET = 0, CAPF_CPN50 = 1 };
-enum capf_dtype { CAPF_F32 = 0, CAPF_BF16 = 1 };
+/* CAPF_F16 (HRNet inference plans): the CAPF_BF16 plan -- the same ops, kernels, routing thresholds and plan flags -- with IEEE fp16 in
+ * place of bf16 as the 16-bit element of every activation, weight pack and matrix-pipe operand (11 significand bits instead of 8; see
+ * "fp16 storage" at capf_op_conv_16).  capf_create refuses it for CAPF_CPN50, with CAPF_PLAN_BF16_F32_STREAM and with training = 1. */
+enum capf_dtype { CAPF_F32 = 0, CAPF_BF16 = 1, CAPF_F16 = 2 };
 
 /* parameter kinds reported by capf_param_info (lets the host build matching leaf modules) */
 enum capf_param_kind {
@@ -68,7 +71,7 @@ typedef struct capf_config {
     int32_t deform_heads;      /* 4  (DeformableBlock, pose_dformer.py:202) */
     int32_t deform_samples;    /* 4 */
     int32_t context_blocks;    /* 1 = H36M model; 0 = MPI-INF-3DHP variant without DeformableBlocks */
-    int32_t compute_dtype;     /* capf_dtype: MFMA operand type of the backbone convs / lifter GEMMs */
+    int32_t compute_dtype;     /* capf_dtype: MFMA operand type of the backbone convs / lifter GEMMs (CAPF_BF16 / CAPF_F16: also their activations' storage) */
     int32_t max_batch;         /* workspace is sized for this many frames */
     int32_t height, width;     /* input image size (256x256, 256x192, 384x288, ...) */
     int32_t training;          /* 1: size the workspace for capf_forward_train / capf_backward as well */
@@ -141,8 +144,9 @@ const char* capf_version(void);
  * layouts unchanged.  Revision 10 (additive): the crop-aware JPEG route (capf_jpeg_crop_rect, capf_jpeg_crop_batch_info,
  * capf_jpeg_decode_crop_batch); struct layouts unchanged.  Revision 11 (additive): the guarded AdamW step (capf_optim_ctrl_bytes,
  * capf_optim_ctrl_init, capf_grad_sumsq, capf_adamw_step_guarded; new structs capf_optim_report, capf_optim_segment); existing struct
- * layouts unchanged.                                                                                                                       */
-#define CAPF_ABI_VERSION 11
+ * layouts unchanged.  Revision 12 (additive): compute_dtype = CAPF_F16, tensor dtype code 3 (fp16) in capf_tensor / capf_op_desc, the
+ * capf_op_*_16 entry points (the 16-bit kernels for either element format) and capf_debug_f16_round; struct layouts unchanged.           */
+#define CAPF_ABI_VERSION 12
 int capf_abi_version(void);
 
 /* ---- parameter schema == the reference's state_dict ------------- */
@@ -305,7 +309,8 @@ int capf_set_debug(capf_handle* h, int on);
  *   tok_ctx / tok_res / tok_joint   token buffer [B,17,L+1,c] after each block group (layout b p l c)
  * Pointers are into the workspace and valid until the next forward on this handle.
  * Returns 0 for an fp32 tensor, 1 for an int32 tensor, 2 for a bf16 tensor (context maps of a
- * CAPF_BF16 handle; fp32 under CAPF_PLAN_BF16_F32_STREAM), negative on error. */
+ * CAPF_BF16 handle; fp32 under CAPF_PLAN_BF16_F32_STREAM), 3 for an fp16 tensor (context maps of a
+ * CAPF_F16 handle), negative on error. */
 int capf_tensor(const capf_handle* h, const char* name, const void** dev_ptr, int64_t shape[4],
                 int* ndim);
 
@@ -496,6 +501,38 @@ int capf_op_conv_bf16_group(void* stream, int n, const capf_conv_desc* convs, co
 int capf_op_linear_bf16(void* stream, const void* x_bf16, const void* w_bf16, const float* bias, const float* residual, void* y,
                         int M, int N, int K, int gelu_bf16_out);
 
+/* The 16-bit kernel families for EITHER element format: dtype = CAPF_BF16 (then exactly the capf_op_*_bf16 entries above, bit for bit) or
+ * CAPF_F16 (what a CAPF_F16 handle launches; same tiles, same layouts, same routing, v_mfma_f32_32x32x16_f16 at the bf16 instruction's rate).
+ * Kernel names reported for fp16 launches say f16 where the bf16 ones say bf16 ("igemm_f16_ws<w4,256x96,conv>", "bneck0_f16<8x8>").
+ *   capf_op_pack_conv_16       BatchNorm fold + pack; layout 0: [Cout][Kpad64] (capf_op_pack_conv_bf16), 1: row-halo (.._bf16_rh, ks = 3),
+ *                              2: the 2-D halo tile's (.._bf16_ws, ks = 3).  Weights are the folded fp32 values rounded once to the format.
+ *   capf_op_conv_16            capf_op_conv_bf16; with Cin % 8 != 0 the STEM of a 16-bit plan (csrc/igemm_bf16.hip stem kernels): x is the fp32 image,
+ *                              w_packed the fp32 pack of capf_op_pack_conv, no residual -- image and weights are rounded to the format on their way
+ *                              into LDS (an fp16 stem clamps a pixel value beyond +-65504), y is 16-bit;  capf_op_conv_16_group: capf_op_conv_bf16_group;  capf_op_conv_16_ws_group: .._bf16_ws_group
+ *   capf_op_linear_16          capf_op_linear_bf16 (gelu_out16: GELU, then a 16-bit result)
+ *   capf_op_bneck_16           a layer1 bottleneck as ONE kernel (csrc/bneck_bf16.hip; networks/resnet.py:58-93): w / bias = {conv1, conv2, conv3,
+ *                              downsample} from layout 0.  w[3] != NULL: the first bottleneck, x [B,H,W,64], shortcut [B,H,W,256] required;
+ *                              w[3] == NULL: an identity bottleneck, x [B,H,W,256].  t1 / t2 [B,H,W,64]; y [B,H,W,256]; H % 8 == 0, W % 8 == 0.
+ *                              tap != 0 also stores conv1's, conv2's and the downsample's outputs to t1 / t2 / shortcut (else scratch).
+ * fp16 storage (every fp16 store of these kernels; capf_debug_f16_round runs the same expression on the host, out[i] = fp16 bits of in[i]):
+ * round to nearest even; finite values beyond +-65504 and the infinities saturate to +-65504; NaN stays NaN; results below 2^-14 are stored as
+ * fp16 subnormals (down to 2^-24, then zero).  DYNAMIC RANGE: an fp16 plan relies on what the two-fp16-piece fp32 tiles above rely on --
+ * activations behind a folded BatchNorm and the folded weights are O(1e-3 .. 1e2); unlike those tiles it carries NO scale: a folded weight or an
+ * activation above 65504 is clamped (a wrong but finite value), one below 6e-5 keeps fewer than 11 bits, one below 3e-8 is zero.  Subnormal fp16
+ * operands are multiplied as the values they are: v_mfma_f32_32x32x16_f16 does not flush them (hipcc's kernel mode keeps fp16 denormals), and the
+ * fp32 accumulators never flush (tests/test_gpu_f16_ops.py holds a conv of 1e-6 inputs to the usual bound).  Accumulation is fp32 as for bf16. */
+int capf_op_pack_conv_16(void* stream, const float* w_oihw, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
+                         void* w_packed, float* bias, int Cout, int Cin, int ks, int layout, int dtype);
+int capf_op_conv_16(void* stream, const void* x_nhwc, const void* w_packed, const float* bias, const void* residual, void* y_nhwc, int B, int H,
+                    int W, int Cin, int Cout, int ks, int stride, int act, int dtype);
+int capf_op_conv_16_group(void* stream, int n, const capf_conv_desc* convs, const void* const* w_row_halo, int32_t* variant, int dtype);
+int capf_op_conv_16_ws_group(void* stream, int n, const capf_conv_desc* convs, int dtype);
+int capf_op_linear_16(void* stream, const void* x, const void* w, const float* bias, const float* residual, void* y, int M, int N, int K,
+                      int gelu_out16, int dtype);
+int capf_op_bneck_16(void* stream, const void* x, const void* const w[4], const float* const bias[4], void* t1, void* t2, void* shortcut, void* y,
+                     int B, int H, int W, int tap, int dtype);
+int capf_debug_f16_round(const float* in, uint16_t* out, int n);
+
 /* ---- the steps on either side of the path ---------------------------------
  * capf_preprocess: data_prefetcher.preload (ContextPose/mvn/datasets/utils.py:33-82) as one launch pair:
  *   images_bgr uint8 [B,H,W,3] -> images_out fp32 RGB NHWC ((u/255 - mean) / std; std == NULL: CPN, mean only);
@@ -677,8 +714,8 @@ typedef struct capf_op_desc {
     int32_t backbone;          /* 1: the op belongs to the backbone plan */
     int32_t conv;              /* kind 0: 1 = convolution (NHWC), 0 = rows-mode linear */
     int32_t Cin, H, W, Cout, Ho, Wo, ks, stride, pad, act;   /* act: 0 none, 1 ReLU, 2 GELU */
-    int32_t in_dtype, out_dtype;                             /* capf_tensor convention: 0 fp32, 2 bf16 */
-    int32_t mfma_bf16;         /* operands are rounded to bf16 for the matrix pipe */
+    int32_t in_dtype, out_dtype;                             /* capf_tensor convention: 0 fp32, 2 bf16, 3 fp16 */
+    int32_t mfma_bf16;         /* operands are rounded to the handle's 16-bit compute dtype for the matrix pipe (bf16, or fp16 on a CAPF_F16 handle) */
     int32_t n_in, shift[4], relu;                            /* fuse-sum: inputs, log2 nearest-upsample factors, ReLU */
     int32_t p_weight, p_bn_weight;                           /* capf_param_info indices of <conv>.weight and <bn>.weight; -1 */
     int32_t has_residual;
