@@ -33,6 +33,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_optim_ctrl_bytes", "capf_optim_ctrl_init", "capf_grad_sumsq", "capf_adamw_step_guarded",
     "capf_op_pack_conv_16", "capf_op_conv_16", "capf_op_conv_16_group", "capf_op_conv_16_ws_group", "capf_op_linear_16", "capf_op_bneck_16",
     "capf_debug_f16_round",
+    "capf_op_stream_class",
 ]
 
 
@@ -498,6 +499,12 @@ class Engine:
                                                            c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B,
                                                            c_void_p(out.data_ptr()), ms, leader, n), "forward_profile_launches")
         return list(ms), list(leader)
+
+    def op_stream_classes(self, batch):
+        """Per op at `batch` under the current set_lanes mode: 0 the caller's stream, 1 a side lane's stream (mode 1) or the side chain's
+        (mode 3, batch 16..128): see capf_op_stream_class."""
+        self.lib.capf_op_stream_class.argtypes = [c_void_p, c_int, c_int]
+        return [self._check(self.lib.capf_op_stream_class(self.h, i, batch), "op_stream_class") for i in range(self.lib.capf_num_ops(self.h))]
 
     def profile_variants(self):
         """After forward_profile_launches: the device kernel of every grouped bf16 launch, by leader op (-1 elsewhere)."""

@@ -520,8 +520,9 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
                     // box, frames/s): one chain 6418; {0,3}|{1,2} 6497; {0,1}|{2,3} 5964; {0,2}|{1,3} 6101; {0,1,2}|{3} 6149;
                     // {0}|{1,2,3} 6398.  Across the configurations: cfg1 +0.4..1.2 %, cfg2 +0.9 %, cfg4 +1.3 %, but -0.8 % at batch 512 (every launch already fills
                     // the chip many times over), and below batch 16 a region is a handful of tiles (and may use the split-K scratch):
-                    // one chain outside 16..256.
-                    const bool two = lanes == 3 && !log && side[0] && op.fork.lanes >= 2 && batch >= 16 && batch <= 256;
+                    // one chain outside 16..256 (until round 11).  Round 11, five alternating pairs against one chain per configuration: cfg1 (batch 64) +1.2 % and
+                    // +2.2 % on two boxes, cfg2 (bf16, batch 256) -0.45 % at twice its pair-to-pair spread: two chains up to batch 128 (two_chains()).
+                    const bool two = two_chains(op, batch) && !log && side[0];
                     if (two) {
                         HIP_TRY(hipEventRecord(events[op.fork.first_event], main_stream));
                         HIP_TRY(hipStreamWaitEvent(side[0], events[op.fork.first_event], 0));
@@ -591,7 +592,6 @@ int capf_create(const capf_config* cfg, int device, capf_handle** out) {
     Engine& e = h->e;
     e.cfg = *cfg;
     e.device = device;
-    e.lanes = 2;
     if (cfg->compute_dtype != CAPF_F32 && cfg->compute_dtype != CAPF_BF16 && cfg->compute_dtype != CAPF_F16) {
         g_create_error = "compute_dtype must be CAPF_F32, CAPF_BF16 or CAPF_F16";
         delete h;
@@ -1446,15 +1446,7 @@ int capf_op_schedule(const capf_handle* h, int index, int32_t* region, int32_t* 
     const bool control = op.kind == capf::OP_FORK || op.kind == capf::OP_JOIN;
     if (region) *region = control ? -1 : op.region;
     if (lane) *lane = op.lane;
-    if (level) {
-        *level = -1;
-        if (!control && op.region >= 0) {
-            const auto& lv = e.region_levels[op.region];
-            for (size_t l = 0; l < lv.size(); ++l)
-                for (int oi : lv[l])
-                    if (oi == index) *level = (int32_t)l;
-        }
-    }
+    if (level) *level = control ? -1 : op.level;
     // The ABI's layout is Op::reads() / writes() without their last slot, which has no column of its own here: the map a conv adds behind
     // its activation is reported as its second input (a conv has one), the bf16 shadow in the first outs[] column (a conv / fuse sum writes
     // no outs[])
@@ -1469,6 +1461,16 @@ int capf_op_schedule(const capf_handle* h, int index, int32_t* region, int32_t* 
         if (w[6] >= 0) writes[2] = w[6];
     }
     return CAPF_OK;
+}
+
+int capf_op_stream_class(const capf_handle* h, int index, int batch) {
+    if (!h || index < 0 || index >= (int)h->e.ops.size() || batch <= 0) return CAPF_ERR_INVALID;
+    const capf::Engine& e = h->e;
+    const capf::Op& op = e.ops[index];
+    if (op.region < 0 || op.kind == capf::OP_FORK || op.kind == capf::OP_JOIN || e.lanes == 0) return 0;
+    if (e.lanes == 1) return op.lane > 0 ? 1 : 0;
+    const bool two = e.two_chains(e.ops[e.regions[op.region].first], batch);
+    return two && (op.lane == 1 || op.lane == 2) ? 1 : 0;
 }
 
 int capf_forward_prefix(capf_handle* h, void* stream, const float* images_nhwc, const float* k2d, float* kcrop_inout, int batch,

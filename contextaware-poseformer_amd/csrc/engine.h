@@ -166,6 +166,7 @@ struct Op {
     int bneck_c3 = -1;            // conv1 / conv2 / downsample of a first bottleneck that may run as one kernel with its conv3 (that op's index; plan.cpp bneck0_mark)
     int lane = 0;                 // stream lane inside a fork/join region (0 = the caller's stream)
     int region = -1;              // index of the enclosing fork/join region, -1 outside
+    int level = -1;               // dependency level inside the region (schedule_regions), -1 outside
 };
 
 struct NamedTensor {
@@ -358,6 +359,8 @@ struct Engine {
     FusedLaunch fused_at(int i, int batch, int last_op, bool bneck_only = false) const;
     FusedLaunch fused_leader(int i, int batch, bool bneck_only = false) const;
     int run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* log, unsigned lane_mask = ~0u);
+    // lanes == 3 runs the region behind this fork op as two chains at this batch (on a device: run())
+    bool two_chains(const Op& fork_op, int batch) const { return lanes == 3 && fork_op.fork.lanes >= 2 && batch >= 16 && batch <= 128; }
     GemmArgs gemm_args(const Op& op, int batch, bool planes = true) const;
 
     // ---- training step (train.cpp)

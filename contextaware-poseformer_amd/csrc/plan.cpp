@@ -1052,7 +1052,10 @@ void Engine::schedule_regions() {
             if (sink) level[i - lo] = max_level;
         }
         region_levels[r].assign(max_level + 1, {});
-        for (int i = lo; i < hi; ++i) region_levels[r][level[i - lo]].push_back(i);
+        for (int i = lo; i < hi; ++i) {
+            ops[i].level = level[i - lo];
+            region_levels[r][level[i - lo]].push_back(i);
+        }
     }
 }
 

@@ -291,7 +291,7 @@ int capf_lifter_forward(capf_handle* h, void* stream, const float* k2d, float* k
  *   0 = everything in program order on the caller's stream;
  *   1 = on library-owned side streams, forked from / joined to the caller's stream with events;
  *   2 = by dependency level on the caller's stream, the convolutions of a level sharing ONE grouped launch;
- *   3 = (default) as 2, but at batch 16..256 the lanes of a region form TWO such chains -- lanes 0 + 3 on the caller's stream,
+ *   3 = (default) as 2, but at batch 16..128 the lanes of a region form TWO such chains -- lanes 0 + 3 on the caller's stream,
  *       1 + 2 on a library-owned side stream (fork / join with events) -- so that one chain's launch ramp and tail overlap
  *       the other's body.
  * The results are bit-identical in modes 0, 2 and 3 (mode 1 has no split-K scratch: equal to roundoff at small batches). */
@@ -694,6 +694,11 @@ int capf_op_bytes(const capf_handle* h, int index, int batch, double* bytes);
  *   -2 = the external image.  Lets host-side tests check that the schedule is a valid topological order. */
 int capf_op_schedule(const capf_handle* h, int index, int32_t* region, int32_t* level, int32_t* lane,
                      int32_t reads[5], int32_t writes[6]);
+/* The stream class op `index` is issued on at `batch` under the current capf_set_lanes mode: 0 = the caller's stream, 1 = a library-owned
+ *   stream that runs a lane (mode 1) or the side chain (mode 3 at batch 16..128: lanes 1 + 2 of a region with two or more lanes).  The
+ *   event-bracketed profiling runs (capf_forward_profile*) stay on the caller's stream.  Lets host-side tests and tools
+ *   see which schedule a handle runs.  (Additive to revision 12: struct layouts and every existing entry point unchanged.) */
+int capf_op_stream_class(const capf_handle* h, int index, int batch);
 /* ---- layer-wise ("teacher-forced") parity aids ---------------------------------------------------------------
  * A deep bf16 network is chaotic at the rounding level: two correct implementations that differ only in fp32 summation
  * order drift apart to the full bf16 noise floor after ~50 layers, so an end-to-end comparison cannot be tighter than that
