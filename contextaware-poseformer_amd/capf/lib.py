@@ -34,6 +34,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_op_pack_conv_16", "capf_op_conv_16", "capf_op_conv_16_group", "capf_op_conv_16_ws_group", "capf_op_linear_16", "capf_op_bneck_16",
     "capf_debug_f16_round",
     "capf_op_stream_class",
+    "capf_set_features", "capf_lifter_forward_train", "capf_backward_maps",
 ]
 
 
@@ -153,6 +154,9 @@ def load_library():
     P = c_void_p
     lib.capf_forward_train.argtypes = [H, P, P, P, P, c_int, P, P]
     lib.capf_backward.argtypes = [H, P, P, c_int, P, P]
+    lib.capf_set_features.argtypes = [H, P, POINTER(P), c_int]
+    lib.capf_lifter_forward_train.argtypes = [H, P, P, P, c_int, P, P]
+    lib.capf_backward_maps.argtypes = [H, P, P, c_int, P, P, POINTER(P)]
     lib.capf_train_generation.argtypes = [H]
     lib.capf_train_generation.restype = c_int64
     lib.capf_max_batch.argtypes = [H]
@@ -346,6 +350,43 @@ class Engine:
         self._check(self.lib.capf_backward(self.h, c_void_p(stream), c_void_p(grad_out.data_ptr()), B,
                                            c_void_p(flat_grad.data_ptr()),
                                            c_void_p(masks.data_ptr()) if masks is not None else c_void_p(0)), "backward")
+
+    # ---- the lifter on caller-supplied context maps (capf_set_features / capf_lifter_forward_train / capf_backward_maps)
+    def feature_shapes(self):
+        """[(H_l, W_l, C_l)] of the four context maps feat0..3 (NHWC) of this plan."""
+        if not hasattr(self, "_feature_shapes"):
+            shape, nd, out = (c_int64 * 4)(), c_int(), []
+            for l in range(4):
+                self._check(self.lib.capf_tensor(self.h, f"feat{l}".encode(), None, shape, byref(nd)), f"tensor(feat{l})")
+                out.append((shape[1], shape[2], shape[3]))
+            self._feature_shapes = out
+        return self._feature_shapes
+
+    @staticmethod
+    def _ptrs4(tensors):
+        return (c_void_p * 4)(*[t.data_ptr() for t in tensors])
+
+    def set_features(self, feats_nhwc, stream):
+        """Copy four contiguous fp32 NHWC maps [B, H_l, W_l, C_l] into the workspace's feat0..3."""
+        B = feats_nhwc[0].shape[0]
+        self.ensure_workspace(B)
+        self._check(self.lib.capf_set_features(self.h, c_void_p(stream), self._ptrs4(feats_nhwc), B), "set_features")
+
+    def lifter_forward_train(self, k2d, kcrop, out, stream, masks=None):
+        B = k2d.shape[0]
+        self.ensure_workspace(B)
+        self._check(self.lib.capf_lifter_forward_train(self.h, c_void_p(stream), c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B,
+                                                       c_void_p(out.data_ptr()),
+                                                       c_void_p(masks.data_ptr()) if masks is not None else c_void_p(0)),
+                    "lifter_forward_train")
+
+    def backward_maps(self, grad_out, flat_grad, dfeat_nhwc, stream, masks=None):
+        """capf_backward plus the gradient w.r.t. the context maps, written into four contiguous fp32 NHWC tensors."""
+        B = grad_out.shape[0]
+        self._check(self.lib.capf_backward_maps(self.h, c_void_p(stream), c_void_p(grad_out.data_ptr()), B,
+                                                c_void_p(flat_grad.data_ptr()),
+                                                c_void_p(masks.data_ptr()) if masks is not None else c_void_p(0),
+                                                self._ptrs4(dfeat_nhwc)), "backward_maps")
 
     def backbone_forward(self, images, stream):
         B = images.shape[0]

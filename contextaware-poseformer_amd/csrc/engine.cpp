@@ -564,6 +564,7 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
     }
     if (ev) HIP_TRY(hipEventRecord(ev[last_op], main_stream));
     if (log) HIP_TRY(log->mark(main_stream, nullptr, 0));
+    if (first_op == 0) feat_batch = last_op >= n_backbone_ops ? batch : 0;      // (a prefix run leaves the maps half written)
     return CAPF_OK;
 }
 
@@ -723,6 +724,7 @@ int capf_set_workspace(capf_handle* h, void* dev_ptr, size_t bytes) {
     h->e.ws = static_cast<float*>(dev_ptr);
     h->e.ws_bytes = bytes;
     h->e.invalidate_train();
+    h->e.feat_batch = 0;
     return CAPF_OK;
 }
 
@@ -815,6 +817,77 @@ int capf_forward_train(capf_handle* h, void* stream, const float* images_nhwc, c
 int capf_backward(capf_handle* h, void* stream, const float* grad_out, int batch, float* flat_grad, const float* drop_masks) {
     if (!h || !grad_out || !flat_grad) return CAPF_ERR_INVALID;
     return h->e.backward(static_cast<hipStream_t>(stream), batch, grad_out, flat_grad, drop_masks);
+}
+
+// caller-supplied context maps: fp32 plans only (a 16-bit plan stores feat0..3 in its own element format)
+static int maps_f32_only(Engine& e, const char* who) {
+    if (!e.b16()) return CAPF_OK;
+    e.err = std::string(who) + ": context maps are supplied and differentiated in fp32 only; this handle's compute_dtype is " +
+            (e.f16() ? "fp16" : "bf16");
+    return CAPF_ERR_UNSUPPORTED;
+}
+
+int capf_set_features(capf_handle* h, void* stream, const float* const feat_nhwc[4], int batch) {
+    if (!h || !feat_nhwc) return CAPF_ERR_INVALID;
+    Engine& e = h->e;
+    for (int l = 0; l < e.cfg.levels; ++l)
+        if (!feat_nhwc[l]) return CAPF_ERR_INVALID;
+    int rc = maps_f32_only(e, "capf_set_features");
+    if (rc) return rc;
+    if (batch < 1 || batch > capf_max_batch(h)) {
+        e.err = "capf_set_features: batch out of range (1..capf_max_batch)";
+        return CAPF_ERR_INVALID;
+    }
+    if ((rc = check_run(e, batch))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    e.invalidate_train();
+    e.feat_batch = 0;
+    e.last_batch = batch;
+    for (int l = 0; l < e.cfg.levels; ++l) {
+        const size_t bytes = sizeof(float) * (size_t)batch * e.feat_H[l] * e.feat_W[l] * e.feat_C[l];
+        if (hipMemcpyAsync(e.bptr(e.feat_buf[l], batch), feat_nhwc[l], bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+            e.err = "capf_set_features: hipMemcpyAsync failed";
+            return CAPF_ERR_HIP;
+        }
+    }
+    e.feat_batch = batch;
+    return CAPF_OK;
+}
+
+int capf_lifter_forward_train(capf_handle* h, void* stream, const float* k2d, float* kcrop_inout, int batch, float* out,
+                              const float* drop_masks) {
+    if (!h || !k2d || !kcrop_inout || !out) return CAPF_ERR_INVALID;
+    Engine& e = h->e;
+    if (!e.cfg.training) {
+        e.err = "handle was created with training = 0";
+        return CAPF_ERR_STATE;
+    }
+    int rc = check_run(e, batch);
+    if (rc) return rc;
+    if (e.feat_batch != batch) {
+        e.err = "capf_lifter_forward_train: the workspace holds no context maps of this batch (capf_set_features or capf_backbone_forward "
+                "of the same batch comes first)";
+        return CAPF_ERR_STATE;
+    }
+    e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
+    e.last_batch = batch;
+    e.invalidate_train();
+    return e.forward_train(static_cast<hipStream_t>(stream), batch, drop_masks);
+}
+
+int capf_backward_maps(capf_handle* h, void* stream, const float* grad_out, int batch, float* flat_grad, const float* drop_masks,
+                       float* const dfeat_nhwc[4]) {
+    if (!h || !grad_out || !flat_grad || !dfeat_nhwc || batch < 1) return CAPF_ERR_INVALID;
+    Engine& e = h->e;
+    for (int l = 0; l < e.cfg.levels; ++l)
+        if (!dfeat_nhwc[l]) return CAPF_ERR_INVALID;
+    if (int rc = maps_f32_only(e, "capf_backward_maps")) return rc;
+    for (int l = 0; l < e.cfg.levels; ++l)
+        if ((size_t)dfeat_nhwc[l] & 15) {
+            e.err = "capf_backward_maps: dfeat_nhwc pointers must be 16-byte aligned";
+            return CAPF_ERR_INVALID;
+        }
+    return e.backward(static_cast<hipStream_t>(stream), batch, grad_out, flat_grad, drop_masks, dfeat_nhwc);
 }
 
 int64_t capf_train_generation(const capf_handle* h) { return h ? h->e.train_generation : -1; }

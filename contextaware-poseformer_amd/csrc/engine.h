@@ -367,10 +367,11 @@ struct Engine {
     int train_batch = 0;                 // batch of the forward_train whose activations are still in the workspace (0: none)
     int64_t train_generation = 0;        // bumped by every run that (over)writes the workspace
     void invalidate_train() { train_batch = 0; ++train_generation; t_h2_base = nullptr; }
+    int feat_batch = 0;                  // batch of the context maps feat0..3 in the workspace (a whole backbone run or capf_set_features; 0: none)
     void train_layout(int B, TrainLayout& L) const;
     size_t train_elems(int B) const;
     int forward_train(hipStream_t s, int B, const float* masks);
-    int backward(hipStream_t s, int B, const float* dOut, float* flat_grad, const float* masks);
+    int backward(hipStream_t s, int B, const float* dOut, float* flat_grad, const float* masks, float* const* dfeat = nullptr);
     int t_gemm(hipStream_t s, const float* A, RowMap amap, int M, int N, int K, const float* W, int Kpad, const float* bias,
                float* out, RowMap omap, const float* res, RowMap rmap, int act, const float* rscale, int rs_div, const float* Wh2 = nullptr);
     // The lifter's linears on the two-fp16-piece GEMM during a training step (forward: y = x W^T, backward: dX = dY W): which matrices,

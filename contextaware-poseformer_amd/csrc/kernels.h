@@ -568,6 +568,29 @@ hipError_t launch_transpose_pad(const float* in, RowMap imap, int M, int C, floa
 hipError_t launch_attention_bwd(const float* qkv, const float* dO, float* dqkv, int groups, int N, int heads, int d,
                                 hipStream_t s);
 hipError_t launch_deform_bwd(const DeformArgs& a, float* dAO, int ldd, hipStream_t s);
+// ---- gradient w.r.t. the context maps (capf_backward_maps): the backward of both bilinear samplers w.r.t. the SAMPLED tensor.  g[l] holds
+// the gradient of every sampled vector; each is added to its (up to) four corners of dfeat[l] (fp32 NHWC [B, H, W, C], zeroed first by
+// launch_zero_maps) with fp32 atomic adds, lanes over contiguous channels.  The order of the adds is not fixed: dfeat is not bit-reproducible
+struct MapGradArgs {
+    float* dfeat[4];
+    const float* g[4];       // deform: dU[l] [(b,p,h), C_l];  ref: dS_l [(b,p), C_l]
+    int H[4], W[4], C[4];
+    const float* AO;         // deform only: [attention logits | offset pre-activations] of the block, rows (b,p,l), pitch ld_ao
+    const float* ref;        // [B*J, 2] normalised crop keypoints
+    int B, J, L, NH, NS, ld_ao;
+};
+// pose_dformer.py:128 (padding border): dfeat[corner of sample s of head h] += softmax_s(logit[h,s]) * bilinear weight * dU[(b,p,h)]
+hipError_t launch_deform_scatter(const MapGradArgs& a, hipStream_t s);
+// pose_dformer.py:217 (padding zeros): dfeat[corner of ref[b,p]] += bilinear weight * dS[(b,p)], corners outside the map dropped
+hipError_t launch_ref_scatter(const MapGradArgs& a, hipStream_t s);
+// p[l][0 .. n[l]) = 0 for `count` <= 4 maps in one launch (n[l] % 4 == 0, 16-byte aligned pointers; the launcher fills blk_end)
+struct ZeroMaps {
+    float* p[4];
+    long n[4];
+    int blk_end[4];          // running block count: map l owns blocks [blk_end[l - 1], blk_end[l]), 4096 elements each
+    int count;
+};
+hipError_t launch_zero_maps(ZeroMaps z, hipStream_t s);
 hipError_t launch_mpjpe(const float* pred, const float* gt, int rows, float* loss, float* dpred, float gscale,
                         hipStream_t s);
 hipError_t launch_mpjpe_nd(const float* pred, const float* gt, int rows, int D, float* loss, float* dpred, float gscale,

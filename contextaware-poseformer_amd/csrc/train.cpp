@@ -2,6 +2,8 @@
 // backward itself.  The backbone is frozen (conpose.py:22-25) and runs through the inference plan; its four
 // context maps are constants here, so gradients flow only into the 191 `volume_net.*` parameters
 // (pose_dformer.py:144-208) — exactly the tensors DDP all-reduces in the reference (train.py:361-362).
+// capf_backward_maps adds the one thing a TRAINABLE backbone outside this library needs (conpose.py:22-25 with fix_weights = False): the
+// gradient w.r.t. the four maps, scattered from both samplers with fp32 atomic adds into caller-owned buffers (Engine::backward's dfeat).
 //
 // Which layers, with which parameters: Engine::lifter (LifterSchema, filled by build_lifter) -- nothing here builds a parameter name.
 // With dY [M,N], X [M,K], W [N,K] (all row-major), per linear (t_linear_bwd):
@@ -12,7 +14,7 @@
 //            for this product (t_h2_plan / t_h2_prepare), and both run on the 16-bit matrix pipe
 // Fallbacks only: a shape or row map wgrad_tn does not take goes through transpose_pad of dY and X and a split-K igemm_f32 launch; a dX
 // without a pack through transpose_pad of the weight.
-// Gradients are written ONCE each (no accumulation, no atomics) into one flat fp32 buffer laid out in
+// Parameter gradients are written ONCE each (no accumulation, no atomics) into one flat fp32 buffer laid out in
 // state_dict order, so a single RCCL all-reduce covers what DDP sends in three buckets.
 #include <string.h>
 
@@ -483,7 +485,10 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
 // ---------------------------------------------------------------------------------------------------
 // backward: dOut [B,1,17,3] -> flat_grad (state_dict order of volume_net.*)
 // ---------------------------------------------------------------------------------------------------
-int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const float* masks) {
+// dfeat (capf_backward_maps; nullptr: the launches below are capf_backward's, one for one): four caller-owned fp32 NHWC maps that receive
+// the gradient w.r.t. the context maps.  Its two sources are the deformable samplers (dU[l] of every context block, scattered while it
+// is live) and the reference-point sampler (the input gradient of feat_embed[l], which the parameter step has no use for).
+int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const float* masks, float* const* dfeat) {
     if (B != train_batch) {
         err = "capf_backward: the activations of the matching capf_forward_train are gone (no such call, another batch size, or "
               "a later forward / workspace change overwrote them)";
@@ -514,6 +519,18 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
     };
 
     HIP_TRY(hipMemsetAsync(dX, 0, sizeof(float) * (size_t)B * J * D, s));
+    MapGradArgs mg{};
+    if (dfeat) {
+        ZeroMaps z{};
+        for (int l = 0; l < Lv; ++l) {
+            mg.dfeat[l] = z.p[l] = dfeat[l];
+            mg.H[l] = feat_H[l]; mg.W[l] = feat_W[l]; mg.C[l] = feat_C[l];
+            z.n[l] = (long)B * feat_H[l] * feat_W[l] * feat_C[l];
+        }
+        z.count = Lv;
+        mg.ref = kcrop; mg.B = B; mg.J = J; mg.L = Lv; mg.NH = NH; mg.NS = NS; mg.ld_ao = 64;
+        HIP_TRY(launch_zero_maps(z, s));
+    }
 
     // ---- head: out = LN(X) W^T + b
     {
@@ -598,6 +615,11 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
         da.AO = tw + c.ao; da.ref = kcrop; da.B = B; da.J = J; da.L = Lv; da.NH = NH; da.NS = NS; da.ld_ao = 64;
         da.feat_bf16 = maps_bf16() ? 1 : 0;
         HIP_TRY(launch_deform_bwd(da, gA, 64, s));                                  // gA = dAO [R, 64]
+        if (dfeat) {                                     // the same dU, to the corners it was gathered from
+            for (int l = 0; l < Lv; ++l) mg.g[l] = tw + L.dU[l];
+            mg.AO = tw + c.ao;
+            HIP_TRY(launch_deform_scatter(mg, s));
+        }
         // [attention_weights | sampling_offsets] were one GEMM with N = 48: gradients land in a [48, C] temp
         const Pack& pk = packs[cb.ao_pack];
         const int NA = NH * NS, NO = 2 * NH * NS;
@@ -621,8 +643,15 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
     {
         const int R = B * J;
         for (int l = 0; l < Lv; ++l) {
-            int rc = linear_bwd(lifter.feat_embed[l], dX, row_ld(D, (long)(1 + l) * C), R, tw + L.S[l], row_ld(feat_C[l]), nullptr, row_ld(0));
+            // (the input gradient dS_l [R, C_l] only for the map gradient; it takes dU[l]'s place, dead behind the context blocks)
+            int rc = linear_bwd(lifter.feat_embed[l], dX, row_ld(D, (long)(1 + l) * C), R, tw + L.S[l], row_ld(feat_C[l]),
+                                dfeat ? tw + L.dU[l] : nullptr, row_ld(dfeat ? feat_C[l] : 0));
             if (rc) return rc;
+        }
+        if (dfeat) {
+            for (int l = 0; l < Lv; ++l) mg.g[l] = tw + L.dU[l];
+            mg.AO = nullptr;
+            HIP_TRY(launch_ref_scatter(mg, s));
         }
         if (int rc2 = t_colreduce(s, L, tw, dX, row_ld(D), nullptr, row_ld(0), 0, R, C, G(lifter.coord.b), 1, nullptr, 0)) return rc2;
         for (int j = 0; j < 2; ++j)

@@ -905,6 +905,146 @@ hipError_t launch_deform_bwd(const DeformArgs& a, float* dAO, int ldd, hipStream
     return hipGetLastError();
 }
 
+// ---- backward of both bilinear samplers w.r.t. the SAMPLED maps (capf_backward_maps) -----------------------------------------------
+// forward: v = sum over the four corners of weight * feat[corner]; so dfeat[corner] += weight * dv.  Different (b, p, head, sample)
+// meet in one pixel, hence fp32 atomic adds (one global_atomic_add_f32 each, no compare-and-swap loop).  Shape of a wave-instruction:
+// G lanes (the smallest power of two >= C, at most 64) over the contiguous channels of ONE pixel, 64 / G pixels per instruction -- 256
+// contiguous bytes from 64 channels up, two 128-byte segments at 32; never one lane per row.  A wave waits for its adds after every
+// twelve instructions, so fewer than 16 are outstanding.  The cells, fractions and clamping are bilinear_corner's (kernels.h), the
+// positions tanhf(offset) + ref as deform_sample_kernel forms them: the same cpos / cidx the forward gathered from.
+__device__ __forceinline__ int scatter_lanes(int C) {
+    int G = 64;
+    while (G > 4 && (G >> 1) >= C) G >>= 1;
+    return G;
+}
+
+// g[0 .. C) * wgt added to the C channels of pixel `pix`, by the G lanes of a group (ql: lane inside the group); returns the instructions issued
+__device__ __forceinline__ int scatter_row(float* __restrict__ pix, const float* __restrict__ g, float wgt, int C, int G, int ql, bool on) {
+    if (on)
+        for (int c = ql; c < C; c += G) atomicAdd(pix + c, g[c] * wgt);
+    return (C + G - 1) / G;
+}
+
+__device__ __forceinline__ void scatter_throttle(int& issued) {
+    if (issued >= 12) {                                   // (wave-uniform: every lane counts the same instructions)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        issued = 0;
+    }
+}
+
+// One block per (b, p); wave = level; an item is one corner of one (head, sample): NH * NS * 4 items per wave, 64 / G at a time.
+template <int NS>
+__global__ __launch_bounds__(256) void deform_scatter_kernel(MapGradArgs a) {
+#pragma clang fp contract(off)
+    const int bp = blockIdx.x;
+    const int l = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    if (l >= a.L) return;
+    const int b = bp / a.J;
+    const int H = a.H[l], W = a.W[l], C = a.C[l];
+    float* dfeat = a.dfeat[l] + (long)b * H * W * C;
+    const int nk = a.NH * NS;
+    const float* ao = a.AO + ((long)bp * a.L + l) * a.ld_ao;
+    const float rx = a.ref[bp * 2 + 0], ry = a.ref[bp * 2 + 1];
+    const float* dU = a.g[l] + (long)bp * a.NH * C;
+    const int G = scatter_lanes(C);
+    const int grp = lane / G, ql = lane - grp * G, PP = 64 / G;
+    const int items = nk * 4;
+    int issued = 0;
+    for (int i0 = 0; i0 < items; i0 += PP) {
+        const bool live = i0 + grp < items;
+        const int it = live ? i0 + grp : items - 1;
+        const int k = it >> 2, dx = it & 1, dy = (it >> 1) & 1;
+        const int h = k / NS, s = k - h * NS;
+        float lg[NS], mx = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < NS; ++t) { lg[t] = ao[h * NS + t]; mx = fmaxf(mx, lg[t]); }
+        float den = 0.f, mine = 0.f;
+#pragma unroll
+        for (int t = 0; t < NS; ++t) { const float e = expf(lg[t] - mx); den += e; if (t == s) mine = e; }
+        const float ws = mine / den;
+        const float px = tanhf(ao[nk + 2 * k + 0]) + rx;
+        const float py = tanhf(ao[nk + 2 * k + 1]) + ry;
+        const BilinearCorner q = bilinear_corner<true>(px, py, H, W);
+        // border mode: the +1 corner falls outside only where its weight is exactly 0 (the forward clamps its index, ATen masks the load)
+        const int x = q.x0 + dx, y = q.y0 + dy;
+        const bool inside = x <= W - 1 && y <= H - 1;
+        const float wx = dx ? q.wx1 : 1.0f - q.wx1, wy = dy ? q.wy1 : 1.0f - q.wy1;
+        issued += scatter_row(dfeat + ((long)y * W + x) * C, dU + (long)h * C, ws * (wx * wy), C, G, ql, live && inside);
+        scatter_throttle(issued);
+    }
+}
+
+hipError_t launch_deform_scatter(const MapGradArgs& a, hipStream_t s) {
+    if (a.NS != 4 || a.L > 4 || a.NH * a.NS > 16) return hipErrorInvalidValue;
+    for (int l = 0; l < a.L; ++l)
+        if (a.C[l] < 4 || (a.C[l] & 3)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((deform_scatter_kernel<4>), dim3(a.B * a.J), dim3(64 * a.L), 0, s, a);
+    return hipGetLastError();
+}
+
+// One block per (b, p); wave = level; the items are the four corners of the reference point (padding zeros: sample_ref_kernel's validity
+// tests, a corner outside the map gets nothing).
+__global__ __launch_bounds__(256) void ref_scatter_kernel(MapGradArgs a) {
+#pragma clang fp contract(off)
+    const int bp = blockIdx.x;
+    const int l = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    if (l >= a.L) return;
+    const int b = bp / a.J;
+    const int H = a.H[l], W = a.W[l], C = a.C[l];
+    float* dfeat = a.dfeat[l] + (long)b * H * W * C;
+    const float* dS = a.g[l] + (long)bp * C;
+    const BilinearCorner q = bilinear_corner<false>(a.ref[bp * 2 + 0], a.ref[bp * 2 + 1], H, W);
+    const int G = scatter_lanes(C);
+    const int grp = lane / G, ql = lane - grp * G, PP = 64 / G;
+    int issued = 0;
+    for (int i0 = 0; i0 < 4; i0 += PP) {
+        const bool live = i0 + grp < 4;
+        const int it = live ? i0 + grp : 3;
+        const int dx = it & 1, dy = (it >> 1) & 1;
+        const unsigned x = (unsigned)q.x0 + (unsigned)dx, y = (unsigned)q.y0 + (unsigned)dy;
+        const bool inside = x < (unsigned)W && y < (unsigned)H;
+        const float wx = dx ? q.wx1 : 1.0f - q.wx1, wy = dy ? q.wy1 : 1.0f - q.wy1;
+        const long pixel = inside ? (long)y * W + x : 0;
+        issued += scatter_row(dfeat + pixel * C, dS, wx * wy, C, G, ql, live && inside);
+        scatter_throttle(issued);
+    }
+}
+
+hipError_t launch_ref_scatter(const MapGradArgs& a, hipStream_t s) {
+    if (a.L > 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ref_scatter_kernel, dim3(a.B * a.J), dim3(64 * a.L), 0, s, a);
+    return hipGetLastError();
+}
+
+// a block zeroes 4096 consecutive elements of one map (16 bytes per lane, four stores)
+__global__ __launch_bounds__(256) void zero_maps_kernel(ZeroMaps z) {
+    int j = 0;
+    while (j + 1 < z.count && (int)blockIdx.x >= z.blk_end[j]) ++j;      // (block-uniform: scalar loads from the kernel arguments)
+    const int first = j ? z.blk_end[j - 1] : 0;
+    const long n4 = z.n[j] >> 2;
+    f32x4* __restrict__ p = reinterpret_cast<f32x4*>(z.p[j]);
+    long q = (long)((int)blockIdx.x - first) * 1024 + threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < 4; ++u, q += 256)
+        if (q < n4) p[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+hipError_t launch_zero_maps(ZeroMaps z, hipStream_t s) {
+    if (z.count <= 0 || z.count > 4) return hipErrorInvalidValue;
+    long blocks = 0;
+    for (int j = 0; j < z.count; ++j) {
+        if (z.n[j] < 0 || (z.n[j] & 3) || ((size_t)z.p[j] & 15)) return hipErrorInvalidValue;
+        blocks += (z.n[j] + 4095) / 4096;
+        if (blocks >= (1L << 31)) return hipErrorInvalidValue;
+        z.blk_end[j] = (int)blocks;
+    }
+    if (blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(zero_maps_kernel, dim3((unsigned)blocks), dim3(256), 0, s, z);
+    return hipGetLastError();
+}
+
 // ---- MPJPE (loss.py:16-22): loss = mean_r ||pred_r - gt_r||_2 ; dpred = (pred - gt) / (||.|| * rows) ---
 __global__ void mpjpe_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int rows,
                              float* __restrict__ loss, float* __restrict__ dpred, float gscale) {

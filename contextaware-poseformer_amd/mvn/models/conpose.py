@@ -51,6 +51,45 @@ class _LifterStep(torch.autograd.Function):
         return (None,) * 7 + grads
 
 
+class _FeatureStep(torch.autograd.Function):
+    """_LifterStep on caller-supplied context maps: forward = capf_set_features + capf_lifter_forward_train, backward =
+    capf_backward_maps, which returns the gradient w.r.t. the four maps next to the flat parameter gradient.  The maps arrive as
+    contiguous NHWC tensors (the permute from the backbone's NCHW, and its transpose on the way back, are torch's)."""
+
+    @staticmethod
+    def forward(ctx, owner, eng, k2d, kcrop, masks, names, n_maps, *maps_and_params):
+        feats, params = maps_and_params[:n_maps], maps_and_params[n_maps:]
+        out = torch.empty(k2d.shape[0], 1, owner.num_joints, 3, dtype=torch.float32, device=k2d.device)
+        stream = torch.cuda.current_stream(k2d.device).cuda_stream
+        eng.set_features(feats, stream)
+        eng.lifter_forward_train(k2d, kcrop, out, stream, masks)
+        ctx.token = eng.train_generation()
+        ctx.eng, ctx.masks, ctx.names, ctx.owner, ctx.n_maps = eng, masks, names, owner, n_maps
+        ctx.keep = (k2d, kcrop)     # capf_backward_maps re-reads the keypoints / normalised ref: keep them alive
+        ctx.map_shapes = [f.shape for f in feats]
+        ctx.shapes = [p.shape for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        eng = ctx.eng
+        if eng.train_generation() != ctx.token:
+            raise CapfError("backward of a CA_PF forward whose saved activations were overwritten by a later forward on the "
+                            "same engine (the native step keeps ONE set of activations in its workspace): call backward "
+                            "before the next forward of this model")
+        layout, total = eng.grad_layout_cached()
+        flat = torch.empty(total, dtype=torch.float32, device=grad_out.device)
+        dfeat = [torch.empty(shp, dtype=torch.float32, device=grad_out.device) for shp in ctx.map_shapes]
+        stream = torch.cuda.current_stream(grad_out.device).cuda_stream
+        eng.backward_maps(grad_out.contiguous(), flat, dfeat, stream, ctx.masks)
+        ctx.owner.last_flat_grad = flat
+        dmaps = tuple(g if need else None for g, need in zip(dfeat, ctx.needs_input_grad[7:7 + ctx.n_maps]))
+        if ctx.owner.flat_grad_only:      # the caller consumes last_flat_grad itself (capf.optim.FusedAdamW + capf.dist)
+            return (None,) * 7 + dmaps + (None,) * len(ctx.names)
+        grads = tuple(flat[layout[n][0]: layout[n][0] + layout[n][1]].view(shp) for n, shp in zip(ctx.names, ctx.shapes))
+        return (None,) * 7 + dmaps + grads
+
+
 class CA_PF(nn.Module):
     def __init__(self, config, device="cuda:0", compute_dtype="fp32", context_blocks=True, plan_flags=0):
         """compute_dtype: 'fp32' (exact fp32 MFMA, the reference's precision), 'bf16' (backbone convolutions on
@@ -127,6 +166,10 @@ class CA_PF(nn.Module):
         B, H, W, C = images.shape
         if C != 3:
             raise ValueError("images must be [B,H,W,3] NHWC")
+        return self._engine_at(dev, H, W)
+
+    def _engine_at(self, dev, H, W):
+        """The engine of a device and crop size, bound to the module's current parameters."""
         key = (dev.index, H, W)
         eng = self._engines.get(key)
         if eng is None:
@@ -187,6 +230,79 @@ class CA_PF(nn.Module):
             else:
                 out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=images.device)
                 eng.forward(images, k2d, kcrop, out, stream)
+            if kcrop is not keypoints_2d_cpn_crop:
+                with torch.no_grad():
+                    keypoints_2d_cpn_crop.copy_(kcrop)
+        return out
+
+    # ---- conpose.py:40 on maps of the caller's own backbone ------------------------------------
+    def _feature_geometry(self, H, W):
+        """[(H_l, W_l, C_l)] of the four context maps at crop size H x W, from a plan-only handle (no GPU needed)."""
+        cache = self.__dict__.setdefault("_feature_geometries", {})
+        if (H, W) not in cache:
+            plan = Engine(_native.make_capf_config(self._config, H, W, context_blocks=self.context_blocks), device=None)
+            cache[(H, W)] = plan.feature_shapes()
+            plan.close()
+        return cache[(H, W)]
+
+    def forward_features(self, features_list, keypoints_2d_cpn, keypoints_2d_cpn_crop):
+        """self.volume_net(keypoints_2d_cpn, keypoints_2d_cpn_crop, features_list) (conpose.py:34-40) on context maps the CALLER
+        computed: four fp32 CUDA tensors, NCHW as the reference backbones return them (pose_hrnet.py:501, networks/network.py:16-22),
+        of the configured backbone's geometry at crop size (4 H_0, 4 W_0).  Returns [B,1,17,3]; the third argument is normalised in
+        place exactly as forward does.  With grad enabled, gradients flow into volume_net's parameters AND into every map that
+        requires grad (capf_backward_maps), so a torch backbone in front of the native lifter trains through it; the native backbone
+        is not run.  The map gradients are summed with atomic adds: equal up to fp32 summation order from run to run."""
+        feats = list(features_list)
+        if len(feats) != 4:
+            raise ValueError("features_list must hold 4 context maps, got {}".format(len(feats)))
+        for l, f in enumerate(feats):
+            if not torch.is_tensor(f) or f.dim() != 4:
+                raise ValueError("features_list[{}] must be a [B,C,H,W] tensor".format(l))
+        B, H, W = feats[0].shape[0], 4 * feats[0].shape[2], 4 * feats[0].shape[3]
+        try:
+            geometry = self._feature_geometry(H, W)
+        except CapfError as e:
+            raise ValueError("no {} plan at crop size {}x{} (features_list[0] is {}): {}".format(
+                self._backbone_type, H, W, tuple(feats[0].shape), e))
+        want = ", ".join("[B,{},{},{}]".format(c, h, w) for h, w, c in geometry)
+        for l, (f, (h, w, c)) in enumerate(zip(feats, geometry)):
+            if tuple(f.shape) != (B, c, h, w):
+                raise ValueError("features_list[{}] has shape {}; the {} maps at crop size {}x{} are NCHW {} with one B".format(
+                    l, tuple(f.shape), self._backbone_type, H, W, want))
+            if f.dtype != torch.float32:
+                raise ValueError("features_list[{}] must be float32, got {} (maps are NCHW {})".format(l, f.dtype, want))
+            if f.device != feats[0].device:
+                raise ValueError("features_list[{}] is on {} but features_list[0] is on {} (maps are NCHW {})".format(
+                    l, f.device, feats[0].device, want))
+        dev = feats[0].device
+        if dev.type != "cuda":
+            raise CapfError("CA_PF runs on an MI355X only: inputs are on {} (no CPU fallback)".format(dev))
+        for name, t in (("keypoints_2d_cpn", keypoints_2d_cpn), ("keypoints_2d_cpn_crop", keypoints_2d_cpn_crop)):
+            if t.dtype != torch.float32:
+                raise TypeError("{} must be float32, got {}".format(name, t.dtype))
+            if t.device != dev:
+                raise ValueError("{} is on {} but the maps are on {}".format(name, t.device, dev))
+            if tuple(t.shape) != (B, self.num_joints, 2):
+                raise ValueError("{} must have shape ({}, {}, 2), got {}".format(name, B, self.num_joints, tuple(t.shape)))
+        with torch.cuda.device(dev):
+            eng = self._engine_at(dev, H, W)
+            k2d = keypoints_2d_cpn.contiguous()
+            kcrop = keypoints_2d_cpn_crop if keypoints_2d_cpn_crop.is_contiguous() else keypoints_2d_cpn_crop.contiguous()
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            nhwc = [f.permute(0, 2, 3, 1).contiguous() for f in feats]
+            named = [(n, p) for n, p in self.volume_net.named_parameters()]
+            train_lifter = any(p.requires_grad for _, p in named)
+            if torch.is_grad_enabled() and (train_lifter or any(f.requires_grad for f in feats)):
+                if train_lifter and not all(p.requires_grad for _, p in named):
+                    raise NotImplementedError("partially frozen volume_net is not supported by the native backward")
+                if not train_lifter:
+                    named = []
+                names = tuple("volume_net." + n for n, _ in named)
+                out = _FeatureStep.apply(self, eng, k2d, kcrop, self._drop_masks(B, dev), names, 4, *nhwc, *[p for _, p in named])
+            else:
+                out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=dev)
+                eng.set_features(nhwc, stream)
+                eng.lifter_forward(k2d, kcrop, out, stream)
             if kcrop is not keypoints_2d_cpn_crop:
                 with torch.no_grad():
                     keypoints_2d_cpn_crop.copy_(kcrop)

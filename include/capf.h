@@ -286,6 +286,33 @@ int capf_adamw_step_guarded(void* stream, float* params, const float* grads, flo
 int capf_lifter_forward(capf_handle* h, void* stream, const float* k2d, float* kcrop_inout, int batch,
                         float* out);
 
+/* ---- the lifter on caller-supplied context maps, with gradients to the maps ---------------------------------------------------------
+ * What CA_PF with config.model.backbone.fix_weights = False needs from the lifter (conpose.py:22-25: the backbone is trained through
+ * volume_net, i.e. autograd through the two F.grid_sample sites pose_dformer.py:128 and :217): PoseTransformer.forward on maps that a
+ * backbone OUTSIDE this library produced, and dL/d(maps) next to the parameter gradients.  The native backbone stays frozen.
+ * fp32 plans only: on a handle with compute_dtype bf16 / fp16 capf_set_features and capf_backward_maps return CAPF_ERR_UNSUPPORTED
+ * (capf_last_error says why).
+ *
+ * capf_set_features: replaces `features_list = self.backbone(images)` (conpose.py:38) by a copy of the caller's maps: feat_nhwc[l] is
+ *     fp32 NHWC [batch, H_l, W_l, C_l] of the plan's geometry (capf_tensor("feat0".."feat3") reports it), copied into the workspace's
+ *     feat0..3 on `stream`.  The maps are then valid for `batch`: capf_lifter_forward and capf_lifter_forward_train run on them.
+ *     Like every run it invalidates saved training activations.  NULL pointers, batch < 1 or > capf_max_batch: CAPF_ERR_INVALID.
+ * capf_lifter_forward_train: replaces self.volume_net(...) (conpose.py:40) under model.train(): the lifter half of capf_forward_train
+ *     (same code, same bits: capf_backbone_forward + capf_lifter_forward_train IS capf_forward_train) on the maps in the workspace,
+ *     which capf_set_features or a whole backbone run (capf_backbone_forward, capf_forward*) of the same batch left there; otherwise
+ *     CAPF_ERR_STATE.  drop_masks as capf_forward_train takes them; works without context blocks (`depth` blocks) too.
+ * capf_backward_maps: replaces loss.backward() through volume_net INTO features_list (train.py:195 with a trainable backbone):
+ *     capf_backward -- flat_grad gets the same bits -- plus dfeat_nhwc[l] = dL/d(feat_l), caller-owned fp32 NHWC
+ *     [batch, H_l, W_l, C_l], 16-byte aligned, zeroed and overwritten by this call (garbage on entry is fine).  Valid after
+ *     capf_forward_train or capf_lifter_forward_train, under capf_backward's generation / CAPF_ERR_STATE rules.
+ *     The map gradient is summed with fp32 atomic adds (many samples meet in one pixel), whose order is not fixed: dfeat_nhwc is NOT
+ *     bit-reproducible from run to run (last-bit differences); flat_grad is. */
+int capf_set_features(capf_handle* h, void* stream, const float* const feat_nhwc[4], int batch);
+int capf_lifter_forward_train(capf_handle* h, void* stream, const float* k2d, float* kcrop_inout, int batch, float* out,
+                              const float* drop_masks);
+int capf_backward_maps(capf_handle* h, void* stream, const float* grad_out, int batch, float* flat_grad, const float* drop_masks,
+                       float* const dfeat_nhwc[4]);
+
 /* How the independent branches of the backbone (the 2-4 resolution branches of an HRNet module, the
  * fused outputs, the CPN refine cascades) are issued:
  *   0 = everything in program order on the caller's stream;
