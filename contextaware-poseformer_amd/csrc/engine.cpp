@@ -54,7 +54,7 @@ int Engine::repack(hipStream_t s, bool lifter_only) {
                 HIP_TRY(launch_pack_conv_bf16(c.w, c.g, c.b, c.m, c.v, c.eps, W, B, pk.N, pk.Cin, pk.ks, pk.Kpad, s, f16()));
                 if (pk.rh) HIP_TRY(launch_pack_conv_bf16_rh(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.rh_off, B, pk.N, pk.Cin, bf16_rh_width(pk.Cin), s, f16()));
                 if (pk.ws) HIP_TRY(launch_pack_conv_bf16_ws(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.ws_off, B, pk.N, pk.Cin, s, f16()));
-            } else if (pk.wino) {
+            } else if (pk.fast3x3) {
                 if (!pk.wino_skip) HIP_TRY(launch_pack_conv_wino(c.w, c.g, c.b, c.m, c.v, c.eps, W, B, pk.N, pk.Cin, s, pk.Kpad == 18 * pk.Cin ? 43 : 23));
                 HIP_TRY(launch_pack_conv(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.direct_off, B, pk.N, pk.Cin, pk.ks, pk.direct_Kpad, s));
                 if (pk.x3)
@@ -131,14 +131,15 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes) const {
     if (pk.ws || pk.x3) a.Wp3 = pack_arena + (pk.ws ? pk.ws_off : pk.x3_off);
     a.x3_h2 = pk.x3 && plan.x3_h2;
     if (a.x3_h2 && op.h2_utab >= 0 && utab_on_device) a.h2_utab = reinterpret_cast<const unsigned*>(pack_arena + utab_off) + op.h2_utab;
+    const Family family = gemm_family(op, batch);
     // the plain fp32 MFMA kernels' problems on the two-fp16-piece GEMM from batch 5 (launch_gemm_f32 / _group route them; below, the fp32
     // kernels with split-K win); LayerNorm folds of up to 256 columns included (igemm_f32h2.hip, LNA)
-    if (pk.h2g && batch >= H2G_MIN_BATCH && !op.bf16 && !op.pw_pair && !(op.wino && wino_now(op, batch))) a.Wh2 = pack_arena + pk.h2g_off;
-    if (op.wino && !wino_now(op, batch)) {           // small batch: the direct kernel on the direct-layout copy of the weights
+    if (pk.h2g && batch >= H2G_MIN_BATCH && family == Family::F32 && !op.pw_pair) a.Wh2 = pack_arena + pk.h2g_off;
+    if (op.fast3x3 && family == Family::F32) {       // small batch: the direct kernel on the direct-layout copy of the weights
         a.Wp = pack_arena + pk.direct_off;
         a.Kpad = pk.direct_Kpad;
-    } else if (op.wino && pk.wino_skip) {
-        a.Wp = nullptr;                              // no Winograd layout was packed: only a split-fp32 tile (Wp3) may take this launch
+    } else if (family == Family::F32_TILE && pk.wino_skip) {
+        a.Wp = nullptr;                              // no Winograd layout was packed; the tile reads Wp3
     }
     a.conv = op.conv;
     a.Cin = op.Cin; a.H = op.H; a.W = op.W; a.Ho = op.Ho; a.Wo = op.Wo;
@@ -150,16 +151,10 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes) const {
     a.f32s = op.f32s;                                  // (CAPF_PLAN_BF16_F32_STREAM: fp32 residual; fp32 result + bf16 shadow, or bf16 result)
     a.out_f32 = op.st_f32;
     a.out_sh = op.sh >= 0 ? ptr(op.sh) : nullptr;
-    if (planes && op.h2_role && a.x3_h2 && a.Wp3 && wino_now(op, batch)) {
-        // planes between a BasicBlock's two convs: only where BOTH launches go to the two-fp16-piece tile at this batch
-        const GemmArgs peer = gemm_args(ops[op.h2_peer], batch, false);
-        GemmArgs me = a;
-        me.conv = op.conv; me.Cin = op.Cin; me.H = op.H; me.W = op.W; me.Ho = op.Ho; me.Wo = op.Wo; me.ks = op.ks; me.stride = op.stride; me.pad = op.pad;
-        me.omap = op.omap; me.rmap = op.rmap; me.act = op.act;
-        if (peer.x3_h2 && peer.Wp3 && wino_now(ops[op.h2_peer], batch) && gemm_f32x3_wanted(me) && gemm_f32x3_wanted(peer)) {
-            int* e = reinterpret_cast<int*>(ptr(op.h2_exps));
-            if (op.h2_role == 1) a.h2_eout = e; else a.h2_ein = e;
-        }
+    // planes between a BasicBlock's two convs (hr_basic_block pairs them under the two-fp16-piece plan only): where BOTH run the tile at this batch
+    if (planes && op.h2_role && family == Family::F32_TILE && gemm_family(ops[op.h2_peer], batch) == Family::F32_TILE) {
+        int* e = reinterpret_cast<int*>(ptr(op.h2_exps));
+        if (op.h2_role == 1) a.h2_eout = e; else a.h2_ein = e;
     }
     if (op.conv && op.up_in >= 0) {                    // + bilinear_upsample(up_in) behind the activation (build_cpn: lateral + upsampled path)
         a.up = ptr(op.up_in);
@@ -234,7 +229,20 @@ Engine::FusedLaunch Engine::fused_leader(int i, int batch, bool bneck_only) cons
 }
 
 Engine::Family Engine::gemm_family(const Op& op, int batch) const {
-    return op.bf16 == 2 ? Family::BF16_ROWS : op.bf16 ? Family::BF16 : wino_now(op, batch) ? Family::WINO : Family::F32;
+    if (op.bf16) return op.bf16 == 2 ? Family::BF16_ROWS : Family::BF16;
+    if (batch >= op.x3_lo && batch <= op.x3_hi) return Family::F32_TILE;            // (a fast3x3 conv: build() sets the range for no other)
+    return op.fast3x3 && batch >= plan.wino_min_batch && !packs[op.pack].wino_skip ? Family::WINO : Family::F32;
+}
+
+// Does the plan's split-fp32 tile take this conv at this batch?  From 370 MFLOP and batch 5 up (f32_tile_big_enough), where the tile's launcher
+// accepts the problem as gemm_args describes it -- pointers aside: the test looks at none but whether there is a residual, which a
+// placeholder stands for that nothing reads through.  build() asks this once per op and batch range; nothing on the launch path asks again
+bool Engine::f32_tile_takes(const Op& op, int batch) const {
+    if (!f32_tile_big_enough(batch, op.H, op.W, op.Cin, op.N)) return false;
+    static const float residual = 0.f;
+    GemmArgs a = gemm_args(op, batch, false);
+    if (op.aux >= 0 || op.res_param >= 0) a.res = &residual;
+    return plan.x3_h2 ? gemm_f32h2_ok(a) : gemm_f32x3_ok(a);
 }
 
 // FLOPs the MFMA pipe is asked to execute (2 x MACs issued, K padding included, tile-edge padding not): the Winograd kernels issue 18
@@ -252,11 +260,10 @@ Engine::OpRoute Engine::op_route(const Op& op, int batch) const {
     const GemmArgs a = gemm_args(op, batch);
     if (f == Family::BF16)                                     // (the row-halo layout has no K padding: decided per launch, a lower bound)
         return {f, gemm_bf16_kernel_name(a), MN * (pk.rh || pk.in_place ? op.K : pk.Kpad)};
-    if (f == Family::WINO)
-        return {f, gemm_wino_kernel_name(a), gemm_wino_route(a) == WinoPath::X3 ? (plan.x3_h2 ? 3.0 : 6.0) * MN * op.K
-                                                                                : MN * op.Cin * (pk.Kpad == 18 * pk.Cin ? 4.5 : 6.0)};
-    return {f, gemm_f32_kernel_name(a), gemm_f32_route(a).path == F32Path::H2G ? 3.0 * MN * pk.h2g_Kpad       // (small batch: a Winograd conv on
-                                        : MN * (op.wino ? pk.direct_Kpad : pk.in_place ? op.K : pk.Kpad)};        // the direct layout)
+    if (f == Family::F32_TILE) return {f, plan.x3_h2 ? gemm_f32h2_kernel_name() : gemm_f32x3_kernel_name(), (plan.x3_h2 ? 3.0 : 6.0) * MN * op.K};
+    if (f == Family::WINO) return {f, gemm_wino_kernel_name(a), MN * op.Cin * (pk.Kpad == 18 * pk.Cin ? 4.5 : 6.0)};
+    return {f, gemm_f32_kernel_name(a), gemm_f32_route(a).path == F32Path::H2G ? 3.0 * MN * pk.h2g_Kpad       // (small batch: a fast3x3 conv on
+                                        : MN * (op.fast3x3 ? pk.direct_Kpad : pk.in_place ? op.K : pk.Kpad)};     // the direct layout)
 }
 
 FuseSumArgs Engine::fuse_args(const Op& op, int batch) const {
@@ -288,6 +295,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
                     HIP_TRY(launch_gemm_bf16_rows(a.A, a.Wp, a.bias, a.M, a.N, a.K, a.Kpad, a.out, a.omap, a.res, a.rmap, op.out_bf16, s, f16()));
                     break;
                 case Family::BF16: HIP_TRY(launch_gemm_bf16(a, s)); break;
+                case Family::F32_TILE: HIP_TRY(launch_f32_tile(&a, 1, s)); break;
                 case Family::WINO: HIP_TRY(launch_gemm_wino(a, s)); break;
                 default: HIP_TRY(launch_gemm_f32(a, s));
             }
@@ -416,13 +424,14 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
         if (op.kind != OP_GEMM) return false;
         switch (gemm_family(op, batch)) {
             case Family::BF16: return gemm_bf16_groupable(a);
+            case Family::F32_TILE: return true;
             case Family::WINO: return gemm_wino_ok(a);
             case Family::F32: return gemm_f32_groupable(a);
             default: return false;
         }
     };
     for (const std::vector<int>& level : region_levels[region]) {
-        for (Family pass : {Family::F32, Family::BF16, Family::WINO}) {
+        for (Family pass : {Family::F32, Family::BF16, Family::F32_TILE, Family::WINO}) {
             GemmArgs group[MAXG];
             int members[MAXG];
             int n = 0;
@@ -435,6 +444,7 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
                     HIP_TRY(launch_gemm_bf16_group(group, n, s, &v));
                     if (log && !log->op_variant.empty()) log->op_variant[members[0]] = v;
                 }
+                else if (pass == Family::F32_TILE) HIP_TRY(launch_f32_tile(group, n, s));
                 else HIP_TRY(launch_gemm_wino_group(group, n, s));
                 n = 0;
                 return CAPF_OK;
@@ -1031,7 +1041,7 @@ static int conv_group(void* stream, int n, const capf_conv_desc* d, Build build,
     return hip_rc(launch(g, n, static_cast<hipStream_t>(stream)));
 }
 
-// the 3x3 / stride-1 tiles that take their weights in Wp3 (bf16 2-D halo, fp32 split pieces)
+// the 3x3 / stride-1 tiles that take their weights in Wp3 (bf16 2-D halo, fp32 split pieces; x3_h2: the pieces are the two-fp16-piece tile's)
 static int wp3_build(const capf_conv_desc& d, capf::GemmArgs& a, bool (*ok)(const capf::GemmArgs&), int x3_h2) {
     if (!is_3x3_s1(d)) return CAPF_ERR_UNSUPPORTED;
     a = conv_args(d, &capf::GemmArgs::Wp3, 1);
@@ -1214,7 +1224,7 @@ int capf_op_pack_conv_f32h2(void* stream, const float* w, const float* gamma, co
 }
 
 int capf_op_conv_f32h2_group(void* stream, int n, const capf_conv_desc* d) {
-    return conv_group(stream, n, d, [](const capf_conv_desc& c, int, capf::GemmArgs& a) { return wp3_build(c, a, capf::gemm_f32x3_ok, 1); },
+    return conv_group(stream, n, d, [](const capf_conv_desc& c, int, capf::GemmArgs& a) { return wp3_build(c, a, capf::gemm_f32h2_ok, 1); },
                       capf::launch_gemm_f32h2_group);
 }
 
@@ -1224,7 +1234,7 @@ int capf_op_conv_f32h2_planes(void* stream, const capf_conv_desc* d, const int32
     if (!d || !is_3x3_s1(*d) || (exps_in && exps_out)) return CAPF_ERR_UNSUPPORTED;
     capf::GemmArgs g = conv_args(*d, &capf::GemmArgs::Wp3, 1);
     g.x3_h2 = 1; g.h2_ein = exps_in; g.h2_eout = exps_out;
-    if (!capf::gemm_f32x3_ok(g)) return CAPF_ERR_UNSUPPORTED;
+    if (!capf::gemm_f32h2_ok(g)) return CAPF_ERR_UNSUPPORTED;
     const hipError_t e = capf::launch_gemm_f32h2_group(&g, 1, static_cast<hipStream_t>(stream));
     return hip_rc(e, e == hipErrorInvalidValue ? CAPF_ERR_UNSUPPORTED : CAPF_ERR_HIP);
 }

@@ -61,14 +61,15 @@ struct Pack {
     bool in_place = false;         // linear with Kpad == K and no concat: no copy at all, the kernels read the parameter itself
     bool bf16 = false;             // ... stored as bf16 (Kpad % 64 == 0): conv weights, or a linear for the bf16 MFMA projections
     bool quad = false;             // ... a linear for the fused lifter kernels: Wq[k / 4][n][4] (lanes n read consecutive 16-byte quads)
-    bool wino = false;             // ... conv weights in the Winograd layout of igemm_wino.hip (Kpad = 12 * Cin for F(2,3), 18 * Cin for F(4,3))
-    bool wino_skip = false;        // ... which no batch up to cfg.max_batch can reach (a split-fp32 tile takes the conv from its first Winograd batch to
-                                   // max_batch): not packed, no arena space; the conv never runs a Winograd kernel (build())
+    bool fast3x3 = false;          // a 3x3 / stride-1 fp32 conv with routes besides the direct kernel (Engine::conv_bn has the rule): the primary layout is
+                                   // the Winograd one of igemm_wino.hip (Kpad = 12 * Cin for F(2,3), 18 * Cin for F(4,3)), the direct layout is a further copy
+    bool wino_skip = false;        // ... and no batch up to cfg.max_batch reaches a Winograd kernel (a split-fp32 tile takes the conv from its first Winograd
+                                   // batch to max_batch): the Winograd layout is not packed and has no arena space (build())
     // ---- the further copies: flag, offset, padded K
-    size_t direct_off = 0; int direct_Kpad = 0;                  // wino: the direct kernel's layout [N][direct_Kpad] as well (small batches run the direct kernel)
+    size_t direct_off = 0; int direct_Kpad = 0;                  // fast3x3: the direct kernel's layout [N][direct_Kpad] as well (small batches run the direct kernel)
     bool rh = false; size_t rh_off = 0; int rh_Kpad = 0;         // bf16 3x3 stride-1 conv: the row-halo layout, [N][rh_Kpad = 9 * Cin] bf16 (igemm_bf16.hip)
     bool ws = false; size_t ws_off = 0;                          // bf16 3x3 stride-1 conv: the 2-D halo tile's layout (igemm_bf16_ws.hip)
-    bool x3 = false; size_t x3_off = 0;                          // fp32 3x3 stride-1 conv: what the split-fp32 tiles take -- two block-scaled fp16 pieces
+    bool x3 = false; size_t x3_off = 0;                          // fast3x3: what the plan's split-fp32 tile takes -- two block-scaled fp16 pieces
                                                                  // (igemm_f32h2_ws.hip; Engine::plan.x3_h2) or three bf16 pieces (igemm_f32x3_ws.hip)
     bool h2g = false; size_t h2g_off = 0; int h2g_Kpad = 0;      // fp32 conv / linear: two block-scaled fp16 pieces for igemm_f32h2.hip, [N][h2g_Kpad] floats +
                                                                  // [N] inverse channel scales; h2g_Kpad = the direct fp32 layout's padded K
@@ -151,10 +152,11 @@ struct Op {
     int pb[4] = {-1, -1, -1, -1};   // ... and their bias parameters
     double flops_per_frame = 0.0;
     int bf16 = 0;                 // tensors of this op are bf16 (conv: bf16 MFMA kernel)
-    int wino = 0;                 // 3x3 stride-1 fp32 conv on the Winograd kernel (igemm_wino.hip)
+    int fast3x3 = 0;              // 3x3 stride-1 fp32 conv with routes besides the direct kernel (Pack::fast3x3): the split-fp32 tile at the batches
+                                  // [x3_lo, x3_hi], a Winograd kernel from plan.wino_min_batch (Engine::gemm_family)
     int pw_pair = 0;              // one of a 64 -> 256 / 256 -> 64 pointwise pair that igemm_f32_pwchain.hip can run as one launch: stays on the fp32
                                   // kernels in every plan (the chained and the two-launch routes are bit-identical; test_pointwise_chain_*)
-    int x3_lo = 0, x3_hi = -1;    // batches [x3_lo, x3_hi] at which a split-fp32 tile takes this conv (f32x3_takes; set by build(), empty = never)
+    int x3_lo = 0, x3_hi = -1;    // batches [x3_lo, x3_hi] at which the plan's split-fp32 tile runs this conv (Engine::f32_tile_takes; set by build(), empty = never)
     int out_bf16 = 0;             // fp32 stem conv writing bf16 activations
     int h2_exps = -1, h2_role = 0, h2_peer = -1;   // a BasicBlock's conv1 (role 1: writes planes + exponents to buffer h2_exps) / conv2 (role 2: reads them);
                                   // h2_peer = the other op's index: both must run the two-fp16-piece tile at a batch for the pair to use planes
@@ -228,15 +230,16 @@ struct Engine {
     struct PlanSwitches {
         bool fused_lifter = true;      // fused embed / context-attention kernels + LayerNorm folded into the GEMMs (CAPF_PLAN_NO_FUSED_LIFTER, CAPF_LIFTER_FUSED=0:
                                        // the one-kernel-per-op plan, for A/B runs)
-        bool use_wino = true;          // Winograd F(2,3) kernel for the eligible 3x3 stride-1 fp32 convs (CAPF_PLAN_NO_WINOGRAD, CAPF_WINO=0: direct kernel everywhere)
+        bool use_wino = true;          // the eligible 3x3 stride-1 fp32 convs are fast3x3 (CAPF_PLAN_NO_WINOGRAD, CAPF_WINO=0: none is, the direct kernel
+                                       // everywhere -- no split-fp32 tile either: Engine::conv_bn)
         bool wino_f43 = true;          // F(4,3) where W % 4 == 0, F(2,3) for the other even widths (CAPF_PLAN_WINOGRAD_F23_ONLY, CAPF_WINO_F43=0: F(2,3) everywhere)
         bool wino_f43_cpn = false;
         int wino_f43_min_hw = 0, wino_f43_max_hw = 1 << 30;   // F(4,3) only for maps with min <= H * W <= max pixels
-        int wino_min_batch = 24;       // below this batch the Winograd-eligible convs the split-fp32 tile does not take run the direct kernel (with
+        int wino_min_batch = 24;       // below this batch the fast3x3 convs the split-fp32 tile does not take run the direct kernel (with
                                        // split-K; batch 16: 4.75 vs 5.86 ms per forward, batch 24: 6.08 vs 6.37)
         bool use_rh = true;            // row-halo layout + kernel for the bf16 3x3 stride-1 convs (CAPF_PLAN_NO_ROW_HALO, CAPF_BF16_RH=0: off, A/B runs)
         bool use_ws = true;            // 2-D halo layout + kernel for the bf16 3x3 stride-1 convs (CAPF_PLAN_NO_WS clears it)
-        bool use_x3 = true;            // split-fp32 tile for the Winograd-eligible fp32 3x3 stride-1 convs (CAPF_PLAN_NO_F32X3 clears it)
+        bool use_x3 = true;            // split-fp32 tile for the fast3x3 convs (CAPF_PLAN_NO_F32X3 clears it)
         bool x3_h2 = true;             // ... the two-fp16-piece tile (three piece products per MAC); CAPF_PLAN_F32X3_EXACT: the three-bf16-piece tile (six)
         bool use_h2g = true;           // every other fp32 conv / linear of an inference batch >= 5 on the two-fp16-piece GEMM (igemm_f32h2.hip;
                                        // CAPF_PLAN_NO_F32H2_GEMM clears it)
@@ -337,18 +340,19 @@ struct Engine {
     int exec_op(const Op& op, hipStream_t s, int batch);
     bool skipped(const Op& op) const { return op.debug_only && !debug; }   // a debug copy outside a debug run: no launch, no log entry
     FuseSumArgs fuse_args(const Op& op, int batch) const;
-    // does the conv leave the direct kernel (for a split-fp32 tile or a Winograd kernel: launch_gemm_wino decides which) at this batch?
-    // A pure function of the op and the batch: the tile's batch range is precomputed per op by build() (no cache, no mutable state --
-    // const-handle queries on other threads may ask while a forward is being enqueued)
-    bool wino_now(const Op& op, int batch) const {
-        return op.wino && ((batch >= op.x3_lo && batch <= op.x3_hi) || (batch >= plan.wino_min_batch && !packs[op.pack].wino_skip));
-    }
-    // ---- launch routes: pure functions of (op, batch) and the plan, like wino_now
-    // Which family's launcher runs a GEMM op (exec_op; run_region_grouped's pass that may group it), and what the op reports: the kernel that
-    // runs it on its own (capf_op_info) and the FLOPs that kernel issues (capf_op_executed_flops)
-    enum class Family { NONE = -1, F32, BF16, WINO, BF16_ROWS };
+    // ---- launch routes: pure functions of (op, batch) and the plan (no cache, no mutable state -- const-handle queries on other threads may ask
+    // while a forward is being enqueued).  Which family's launcher runs a GEMM op (exec_op; run_region_grouped's pass that may group it), and
+    // what the op reports: the kernel that runs it on its own (capf_op_info) and the FLOPs that kernel issues (capf_op_executed_flops).
+    // A fast3x3 conv is F32_TILE (the plan's split-fp32 tile: igemm_f32h2_ws.hip, or igemm_f32x3_ws.hip under CAPF_PLAN_F32X3_EXACT) at the
+    // batches build() found the tile to take it, WINO (igemm_wino.hip) at the other batches from plan.wino_min_batch where its Winograd
+    // layout is packed, F32 (the direct kernel on the direct layout) below.  gemm_family is THE decision: the launchers only check it
+    enum class Family { NONE = -1, F32, BF16, F32_TILE, WINO, BF16_ROWS };
     struct OpRoute { Family family; const char* kernel; double flops; };
+    bool f32_tile_takes(const Op& op, int batch) const;      // build()'s question behind [x3_lo, x3_hi]: the size rule and the tile launcher's own test
     Family gemm_family(const Op& op, int batch) const;
+    hipError_t launch_f32_tile(const GemmArgs* list, int n, hipStream_t s) const {      // the F32_TILE problems of one launch, on the plan's tile
+        return (plan.x3_h2 ? launch_gemm_f32h2_group : launch_gemm_f32x3_group)(list, n, s);
+    }
     OpRoute op_route(const Op& op, int batch) const;
     // Several ops as ONE launch: a first bottleneck (bneck_bf16.hip; at its fork op, m = {conv1, conv2, downsample, conv3}), an identity
     // bottleneck (256 -> 64 -> 64 -> 256, y = relu(conv3 + x); m = {conv1, conv2, conv3}), a 64 -> 256 / 256 -> 64 pointwise conv pair

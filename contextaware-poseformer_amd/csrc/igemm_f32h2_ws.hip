@@ -1,8 +1,8 @@
 // fp32 3x3 / stride-1 / pad-1 convolution on the 16-bit matrix pipe, operands as two block-scaled fp16 pieces and three piece products
-// per fp32 MAC (igemm_f32h2_ws_tile.h): launchers, grouped kernels, weight pack.  The default route of the BasicBlock convs of HRNet
-// under compute_dtype = fp32 (pose_hrnet.py:66-95) wherever the three-bf16-piece tile of igemm_f32x3_ws.hip was eligible -- same fp32
-// tensors in and out, half the MFMAs.  Which convs: gemm_f32x3_wanted() (one rule for both tiles); which of the two tiles: GemmArgs::x3_h2
-// (the engine's plan: CAPF_PLAN_F32X3_EXACT keeps the three-piece tile).
+// per fp32 MAC (igemm_f32h2_ws_tile.h): launcher, grouped kernels, weight pack.  The default route of the BasicBlock convs of HRNet
+// under compute_dtype = fp32 (pose_hrnet.py:66-95) -- same fp32 tensors in and out as the three-bf16-piece tile of igemm_f32x3_ws.hip, half
+// the MFMAs.  Which convs at which batches, and which of the two tiles, the engine's plan decides (Engine::gemm_family; CAPF_PLAN_F32X3_EXACT
+// keeps the three-piece tile) and calls this launcher itself: a problem it cannot take is an error, never another kernel.
 // Measured alone on one box (tools/f32h2_ws.hip; three-piece tile in brackets), batch 64: 32 ch 64^2 30.1 us (35.1), 64 ch 32^2 22.1
 // (30.0), 128 ch 16^2 21.9 (30.7), 256 ch 8^2 33.8 (50.7); batch 512: 257 (321), 160 (264), 125 (223), 109 (215) with 64-channel tiles
 // on the three wide branches.
@@ -52,10 +52,6 @@ int f32h2_tiles_m(int B, int H, int W, int* tile_pixels) {
     return q.g.tiles_m;
 }
 bool f32h2_unit_table(int H, int W, int Cin, unsigned* out) { return h2_unit_table(H, W, Cin, out); }
-bool f32h2_shape_ok(int B, int H, int W, int Cin, int Cout) {
-    H2Problem q;
-    return h2_plan(B, H, W, Cin, Cout, 32, &q);
-}
 
 struct H2GroupArgs {
     H2Problem g[MAXG];
@@ -116,7 +112,7 @@ hipError_t launch_gemm_f32h2_group(const GemmArgs* list, int n, hipStream_t s) {
     return e;
 }
 
-const char* gemm_f32h2_kernel_name(const GemmArgs&) { return "igemm_f32h2_group_ws"; }
+const char* gemm_f32h2_kernel_name() { return "igemm_f32h2_group_ws"; }
 
 // ---- weight pack: BN fold (the fp32 value v launch_pack_conv folds), one power-of-two scale t per output channel with max |v| t in
 // [2^14, 2^15), two fp16 pieces of v t -- piece 0 = fp16(v t), piece 1 = fp16(v t - piece 0), |v t - piece 0 - piece 1| <= 2^-23 |v t| --

@@ -1,8 +1,8 @@
 // fp32 3x3 / stride-1 / pad-1 convolution on the bf16 matrix pipe, operands split into three bf16 pieces (igemm_f32x3_ws_tile.h):
-// launchers, grouped kernel, weight pack.  Takes, for launches that fill the chip, the BasicBlock convs of HRNet under
-// compute_dtype = fp32 (pose_hrnet.py:66-95) from the Winograd kernels of igemm_wino.hip -- same fp32 tensors in and out, results
-// to fp32 accumulation order (tools/f32x3_ws.hip: 2.6e-7 of the sum of |terms| at worst against an fp64 evaluation, rms 1.4e-8;
-// the F(4,3) kernel this replaces: 1e-5).
+// launcher, grouped kernel, weight pack.  Under CAPF_PLAN_F32X3_EXACT the engine (Engine::gemm_family) runs the BasicBlock convs of HRNet
+// under compute_dtype = fp32 (pose_hrnet.py:66-95) here wherever a launch fills the chip; the default plan runs them on the two-fp16-piece
+// tile of igemm_f32h2_ws.hip instead.  fp32 tensors in and out, results to fp32 accumulation order (tools/f32x3_ws.hip: 2.6e-7 of the sum
+// of |terms| at worst against an fp64 evaluation, rms 1.4e-8; the F(4,3) Winograd kernel: 1e-5).
 // Measured alone (tools/f32x3_ws.hip; F(4,3) kernel in brackets), batch 64: 32 ch 64^2 37.6 us (43.6), 64 ch 32^2 31.6 (38.0),
 // 128 ch 16^2 30.6 (48.5), 256 ch 8^2 50.8 (81.3); batch 512: 352 (341), 271 (281), 236 (243), 229 (248).
 #include "igemm_f32x3_ws_tile.h"
@@ -30,7 +30,6 @@ static bool x3_from_args(const GemmArgs& a, X3Problem* q) {
 }
 
 bool gemm_f32x3_ok(const GemmArgs& a) {
-    if (a.x3_h2) return gemm_f32h2_ok(a);                  // (the two-piece tile addresses per tile: no 2 GB tensor limit)
     X3Problem q;
     return x3_from_args(a, &q);
 }
@@ -41,20 +40,9 @@ bool gemm_f32x3_ok(const GemmArgs& a) {
 // of rounds 4-5, 400 MFLOP and batch 6, left batch 5 on the direct kernels at 3.62.  Round 4's numbers for the three-piece tile, ms per forward
 // against the direct kernel with split-K / the Winograd kernels: batch 6 3.67 / 3.80 / -, 8 3.76 / 3.90 / 5.47, 16 4.27 / 4.75 / 5.86,
 // 24 4.90 / 6.08 / 6.37; below, the direct kernel wins: batch 4 3.49 / 2.92).  (diag builds: CAPF_F32X3_MIN_MFLOP)
-static bool x3_big_enough(int B, int H, int W, int Cin, int Cout) {
+bool f32_tile_big_enough(int B, int H, int W, int Cin, int Cout) {
     static const double min_flop = [] { const char* e = diag_env("CAPF_F32X3_MIN_MFLOP"); return (e ? atof(e) : 370.0) * 1e6; }();
     return B >= 5 && 2.0 * (double)B * H * W * Cout * 9.0 * Cin >= min_flop;
-}
-
-bool f32x3_takes(int B, int H, int W, int Cin, int Cout, bool h2) {
-    if (!x3_big_enough(B, H, W, Cin, Cout)) return false;
-    if (h2) return f32h2_shape_ok(B, H, W, Cin, Cout);
-    X3Problem q;
-    return x3_plan(B, H, W, Cin, Cout, X3_NS, &q);
-}
-
-bool gemm_f32x3_wanted(const GemmArgs& a) {            // (one geometry computation: this runs on the launch path)
-    return a.Wp3 && a.H > 0 && a.W > 0 && a.M % (a.H * a.W) == 0 && x3_big_enough(a.M / (a.H * a.W), a.H, a.W, a.Cin, a.N) && gemm_f32x3_ok(a);
 }
 
 struct X3GroupArgs {
@@ -76,12 +64,11 @@ __global__ __launch_bounds__(256, 2) void igemm_f32x3_group_ws_kernel(X3GroupArg
 hipError_t launch_gemm_f32x3_group(const GemmArgs* list, int n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n > MAXG) return hipErrorInvalidValue;
-    if (list[0].x3_h2) return launch_gemm_f32h2_group(list, n, s);      // (the two-fp16-piece tile: one plan, one kind of pack per engine)
     X3Problem q[MAXG];
     int tiles[MAXG], order[MAXG];
     double cost[MAXG];
     for (int i = 0; i < n; ++i) {
-        if (!list[i].Wp3 || !x3_from_args(list[i], &q[i])) return hipErrorInvalidValue;
+        if (!list[i].Wp3 || list[i].x3_h2 || !x3_from_args(list[i], &q[i])) return hipErrorInvalidValue;
         tiles[i] = q[i].g.tiles_m * q[i].g.NSL;
         cost[i] = q[i].g.C;                                 // a tile's K loop
     }
@@ -96,9 +83,7 @@ hipError_t launch_gemm_f32x3_group(const GemmArgs* list, int n, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_gemm_f32x3(const GemmArgs& a, hipStream_t s) { return launch_gemm_f32x3_group(&a, 1, s); }
-
-const char* gemm_f32x3_kernel_name(const GemmArgs& a) { return a.x3_h2 ? gemm_f32h2_kernel_name(a) : "igemm_f32x3_group_ws"; }
+const char* gemm_f32x3_kernel_name() { return "igemm_f32x3_group_ws"; }
 
 // BN fold + three-way split + re-layout for the tile: with v the folded fp32 weight (bn_fold_w3x3: the value launch_pack_conv folds, rows
 // beyond Cout zero, bias as launch_pack_conv), piece 0 = bf16(v), piece 1 = bf16(v - piece 0), piece 2 = bf16(v - piece 0 - piece 1) -- exact

@@ -18,10 +18,9 @@
 //       weights u_0..u_3 are laid out in the same (kh, chunk, p, c) order, so the W loader is the direct kernel's too;
 //     * the input transform happens between the LDS read and the MFMA: 4 ds_read_b128 of raw pixels + 16 v_add/v_sub give
 //       the four A fragments of an 8-deep k-step (4 x 4 MFMAs); the output transform is 6 adds per element in the epilogue;
-//     * one barrier per superchunk (64 MFMAs per wave) instead of one per 32-deep chunk (32): the superchunk's 16 DMA
-//       instructions per thread are spread over the 4096 MFMA cycles of the previous one.
+//     * one load phase per superchunk (64 MFMAs per wave) instead of one barrier per 32-deep chunk (32 MFMAs).
 // Block = 4 waves, 64 tiles (128 output pixels) x 64 channels, wave tile 32 tiles x 32 channels x 4 positions (64
-// accumulator registers); LDS = 2 superstages x 4 sub-stages x (64 + 64) rows x 128 B = 128 KiB (one block per CU).
+// accumulator registers); LDS = one superstage of 4 sub-stages x (64 + 64) rows x 128 B = 64 KiB (two blocks per CU, "ping-pong").
 #include <stdlib.h>
 
 #include <algorithm>
@@ -39,7 +38,7 @@ typedef __amdgpu_buffer_rsrc_t rsrc_t;
 static constexpr int WBK = 32;                 // channels per sub-chunk (128 B rows)
 static constexpr int WBT = 64, WBN = 64;       // block tile: 64 tiles x 64 output channels
 static constexpr int WSUB = (WBT + WBN) * WBK; // floats per sub-stage
-static constexpr int WLDS = 2 * 4 * WSUB;      // 2 superstages x 4 sub-stages
+static constexpr int WLDS = 4 * WSUB;          // one superstage of 4 sub-stages
 
 #ifdef CAPF_DIAG   // (diagnosis build) per-block stamps: {t_entry, t_prologue_done, t_loop_done, t_exit, realtime_entry, hw_id, xcc_id, realtime_exit}
 __device__ unsigned long long capf_wino_timeline[8192 * 8];
@@ -58,13 +57,12 @@ __device__ __forceinline__ int fast_div_w(int n, FastDiv d) {
 #if defined(__HIP_DEVICE_COMPILE__)
 // One output tile (logical id `bid`) of problem p.  p.M = number of tiles (B * H * W / 2), p.Ho = H, p.Wo = W / 2 (tile grid),
 // p.Kpad = 12 * Cin, p.fd_hw / p.fd_wo divide by H * (W/2) and W/2.
-// PP = false: two superstages (128 KiB), the next superchunk's DMA instructions ride in the MFMA slots of the current one.
-// PP = true ("ping-pong"): ONE superstage (64 KiB, two blocks per CU).  A block alternates a compute phase (64 MFMAs per wave,
-//   fragments + transforms of the next k-step in the slots) with a load phase (16 DMA instructions per thread, wait, barrier)
-//   and relies on the co-resident block — naturally out of phase, on the same SIMDs — to use the matrix pipe meanwhile; the
-//   partner also covers the ~10 us a tile spends outside its K loop (first-load wait, residual loads, output stores), which
-//   with one block per CU were fully exposed: 2048 tiles of the 64x64 layer-1 conv took 166 us for 82 us of MFMA time.
-template <bool PP>
+// "Ping-pong": ONE superstage (64 KiB, two blocks per CU).  A block alternates a compute phase (64 MFMAs per wave, fragments +
+//   transforms of the next k-step in the slots) with a load phase (16 DMA instructions per thread, wait, barrier) and relies on
+//   the co-resident block — naturally out of phase, on the same SIMDs — to use the matrix pipe meanwhile; the partner also
+//   covers the ~10 us a tile spends outside its K loop (first-load wait, residual loads, output stores), which with one
+//   double-buffered block per CU (128 KiB) were fully exposed: 2048 tiles of the 64x64 layer-1 conv took 166 us for 82 us of
+//   MFMA time.
 __device__ __forceinline__ void wino_tile(const GemmArgs& p, const int bid, float* __restrict__ lds) {
 #ifdef CAPF_DIAG
     unsigned long long dbg_t0 = 0, dbg_t1 = 0, dbg_t2 = 0;
@@ -143,7 +141,7 @@ __device__ __forceinline__ void wino_tile(const GemmArgs& p, const int bid, floa
             if (++u_cc == CC) { u_cc = 0; ++u_kh; }
         }
     };
-    // fire load #idx of the prepared sub-chunk into sub-stage `sub` (0..7)
+    // fire load #idx of the prepared sub-chunk into sub-stage `sub` (0..3)
     auto fire = [&](int idx, int sub) {
         float* As = lds + sub * WSUB;
         if (idx < RA)
@@ -176,21 +174,19 @@ __device__ __forceinline__ void wino_tile(const GemmArgs& p, const int bid, floa
     __builtin_amdgcn_s_barrier();
 
     // K loop.  Per 8-deep k-step a wave issues 16 MFMAs (slot i = 4 e + p: position p, k sub-step e) and, between them, the
-    // step's other work, ONE piece per 64-cycle MFMA slot so that nothing but an LDS-DMA instruction (60-100 cycles of
-    // issue, tools/dma_rate.hip) ever overflows its slot:
+    // step's other work, ONE piece per 64-cycle MFMA slot so that nothing ever overflows its slot:
     //   slots 0-3    the next k-step's fragments, two ds_read_b128 each: (d2, d1) (d0, d3) (u0, u1) (u2, u3)
-    //   slots 4-14   even: one DMA instruction of the NEXT superchunk (16 per superchunk: 6 + 6 + 4 over steps 0-2, each
-    //                sub-chunk's offsets prepared just before its first load); odd 7, 9, 11, 13: the input transform of the
-    //                next fragments, 4 VALU each, in the order their operands were read (v1, v2, v0, v3)
-    //   step 3       no loads before slot 8; there: vmcnt(0) + lgkmcnt(0) + s_barrier (the next superchunk has landed, every
-    //                wave has issued its last read of this one); slots 8-11 read the next superchunk's first fragments,
-    //                slots 12-15 transform them.  The second half of step 3 runs from registers only.
+    //   slots 6, 8, 10, 12   the input transform of the next fragments, 4 VALU each, in the order their operands were read
+    //                (v1, v2, v0, v3)
+    //   step 3       runs from registers only; behind it the load phase: lgkmcnt(0) + s_barrier (every wave has issued its last
+    //                read of the superstage), the next superchunk's 16 DMA instructions (60-100 cycles of issue each,
+    //                tools/dma_rate.hip), vmcnt(0) + s_barrier, then its first fragments and their transforms
     f32x4 dn[4];                               // raw pixels of the next k-step
     f32x4 v[2][4], uf[2][4];                   // transformed activations / weights of the current and next k-step
     const float* const a_ptr = lds + (wm0 + frow) * WBK;
     const float* const b_ptr = lds + WBT * WBK + (wn0 + frow) * WBK;
-    auto rd_a = [&](int ss, int q, int j) { dn[j] = *reinterpret_cast<const f32x4*>(a_ptr + (ss * 4 + j) * WSUB + q * 4); };
-    auto rd_b = [&](int ss, int q, int j, int buf) { uf[buf][j] = *reinterpret_cast<const f32x4*>(b_ptr + (ss * 4 + j) * WSUB + q * 4); };
+    auto rd_a = [&](int q, int j) { dn[j] = *reinterpret_cast<const f32x4*>(a_ptr + j * WSUB + q * 4); };
+    auto rd_b = [&](int q, int j, int buf) { uf[buf][j] = *reinterpret_cast<const f32x4*>(b_ptr + j * WSUB + q * 4); };
     auto xform = [&](int pq, int buf) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -203,7 +199,7 @@ __device__ __forceinline__ void wino_tile(const GemmArgs& p, const int bid, floa
     {
         const int q0 = fhalf ^ fsw;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { rd_a(0, q0, j); rd_b(0, q0, j, 0); }
+        for (int j = 0; j < 4; ++j) { rd_a(q0, j); rd_b(q0, j, 0); }
 #pragma unroll
         for (int pq = 0; pq < 4; ++pq) xform(pq, 0);
     }
@@ -229,99 +225,53 @@ __device__ __forceinline__ void wino_tile(const GemmArgs& p, const int bid, floa
             }
         }
     };
-    if (PP) {
-        for (int sc = 0; sc < nsc; ++sc) {
-            // the last compute phase has no load phase behind it: its 64 MFMAs hide the latency of the residual rows
-            if (sc == nsc - 1) load_epilogue_operands();
-#pragma unroll
-            for (int step = 0; step < 4; ++step) {
-                const int fb = step & 1, nb = fb ^ 1;
-                const int q_next = ((step + 1) * 2 + fhalf) ^ fsw;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int pq = i & 3, e = i >> 2;
-                    acc[pq] = __builtin_amdgcn_mfma_f32_32x32x2f32(uf[fb][pq][e], v[fb][pq][e], acc[pq], 0, 0, 0);
-                    if (step < 3) {
-                        if (i == 0) { rd_a(0, q_next, 2); rd_a(0, q_next, 1); }
-                        else if (i == 1) { rd_a(0, q_next, 0); rd_a(0, q_next, 3); }
-                        else if (i == 2) { rd_b(0, q_next, 0, nb); rd_b(0, q_next, 1, nb); }
-                        else if (i == 3) { rd_b(0, q_next, 2, nb); rd_b(0, q_next, 3, nb); }
-                        else if (i == 6) xform(1, nb);
-                        else if (i == 8) xform(2, nb);
-                        else if (i == 10) xform(0, nb);
-                        else if (i == 12) xform(3, nb);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            if (sc + 1 < nsc) {
-                // load phase: every wave has issued its last read of the superstage -> overwrite it with the next superchunk
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    prepare();
-#pragma unroll
-                    for (int i = 0; i < NSUBLOAD; ++i) fire(i, j);
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                const int q0 = fhalf ^ fsw;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { rd_a(0, q0, j); rd_b(0, q0, j, 0); }
-#pragma unroll
-                for (int pq = 0; pq < 4; ++pq) xform(pq, 0);
-            }
-        }
-    } else
     for (int sc = 0; sc < nsc; ++sc) {
-        const int ss = sc & 1, sn = ss ^ 1;
+        // the last compute phase has no load phase behind it: its 64 MFMAs hide the latency of the residual rows
+        if (sc == nsc - 1) load_epilogue_operands();
 #pragma unroll
         for (int step = 0; step < 4; ++step) {
             const int fb = step & 1, nb = fb ^ 1;
-            const int rs = step < 3 ? ss : sn;                                 // superstage the next fragments come from
-            const int q_next = (((step + 1) & 3) * 2 + fhalf) ^ fsw;
+            const int q_next = ((step + 1) * 2 + fhalf) ^ fsw;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int pq = i & 3, e = i >> 2;
                 acc[pq] = __builtin_amdgcn_mfma_f32_32x32x2f32(uf[fb][pq][e], v[fb][pq][e], acc[pq], 0, 0, 0);
-                if (step == 3 && i == 7) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                }
-                const int ri = step < 3 ? i : i - 8;                           // read / transform slots shift behind the barrier in step 3
-                if (ri == 0) { rd_a(rs, q_next, 2); rd_a(rs, q_next, 1); }
-                else if (ri == 1) { rd_a(rs, q_next, 0); rd_a(rs, q_next, 3); }
-                else if (ri == 2) { rd_b(rs, q_next, 0, nb); rd_b(rs, q_next, 1, nb); }
-                else if (ri == 3) { rd_b(rs, q_next, 2, nb); rd_b(rs, q_next, 3, nb); }
                 if (step < 3) {
-                    if (i >= 4 && (i & 1) == 0) {                              // DMA slots 4, 6, ..., 14
-                        const int k = step * 6 + (i - 4) / 2;                  // DMA instruction 0..15 of the next superchunk
-                        if (k < 16) {
-                            if ((k & 3) == 0) prepare();
-                            fire(k & 3, sn * 4 + (k >> 2));
-                        }
-                    }
-                    if (i == 7) xform(1, nb);
-                    else if (i == 9) xform(2, nb);
-                    else if (i == 11) xform(0, nb);
-                    else if (i == 13) xform(3, nb);
-                } else {
-                    if (i == 12) xform(1, nb);
-                    else if (i == 13) xform(2, nb);
-                    else if (i == 14) xform(0, nb);
-                    else if (i == 15) xform(3, nb);
+                    if (i == 0) { rd_a(q_next, 2); rd_a(q_next, 1); }
+                    else if (i == 1) { rd_a(q_next, 0); rd_a(q_next, 3); }
+                    else if (i == 2) { rd_b(q_next, 0, nb); rd_b(q_next, 1, nb); }
+                    else if (i == 3) { rd_b(q_next, 2, nb); rd_b(q_next, 3, nb); }
+                    else if (i == 6) xform(1, nb);
+                    else if (i == 8) xform(2, nb);
+                    else if (i == 10) xform(0, nb);
+                    else if (i == 12) xform(3, nb);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
+        }
+        if (sc + 1 < nsc) {
+            // load phase: every wave has issued its last read of the superstage -> overwrite it with the next superchunk
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                prepare();
+#pragma unroll
+                for (int i = 0; i < NSUBLOAD; ++i) fire(i, j);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            const int q0 = fhalf ^ fsw;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { rd_a(q0, j); rd_b(q0, j, 0); }
+#pragma unroll
+            for (int pq = 0; pq < 4; ++pq) xform(pq, 0);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     WINO_STAMP(dbg_t2);
 
     // ---- epilogue: output transform + bias (+ residual) (+ ReLU)
-    if (!PP) load_epilogue_operands();
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int n = n0 + wn0 + 4 * (lane >> 5) + 8 * g;
@@ -359,7 +309,7 @@ __device__ __forceinline__ void wino_tile(const GemmArgs& p, const int bid, floa
 // 32 channels each, split along M or N) x 2 POSITION PAIRS: wave (pp, sub) accumulates positions p = 2 pp, 2 pp + 1 — per
 // 8-deep k-step 3 raw-pixel reads (d_pp .. d_pp+2) + 2 weight reads + 8 VALU feed 8 MFMAs — and the two pairs of a sub-tile
 // meet in the epilogue through LDS (each wave finishes two of the four 8-channel register groups).  One superstage
-// (4 x (HBT + HBN) x 128 B = 48 KiB), ping-pong schedule as wino_tile<true>.
+// (4 x (HBT + HBN) x 128 B = 48 KiB), ping-pong schedule as wino_tile.
 template <int HBT, int HBN>
 __device__ __forceinline__ void wino_tile_h(const GemmArgs& p, const int bid, float* __restrict__ lds) {
     constexpr int RPR = 32;
@@ -590,7 +540,6 @@ __device__ __forceinline__ void wino_tile_h(const GemmArgs& p, const int bid, fl
 }
 #endif
 
-#if defined(__HIP_DEVICE_COMPILE__)
 // F(4,3) along W: a tile is FOUR output pixels (w = 4 wt .. 4 wt + 3) computed from six raw pixels d_0..d_5
 // (w_in = 4 wt - 1 + j) through SIX positions:
 //   v = B^T d:  v0 = 4 d0 - 5 d2 + d4          v1 = -4 (d1 + d2) + (d3 + d4)      v2 = 4 (d1 - d2) + (d4 - d3)
@@ -601,306 +550,31 @@ __device__ __forceinline__ void wino_tile_h(const GemmArgs& p, const int bid, fl
 //               y2 = (m1 + m2) + 4 (m3 + m4)     y3 = (m1 - m2) + 8 (m3 - m4) + m5
 // 18 MACs per four outputs = 4.5 per pixel: HALF the MFMAs of the direct conv (F(2,3): two thirds).  fp32 error against
 // an fp64 conv: 4e-6 .. 9e-6 absolute on O(4) outputs (direct: 1e-6 .. 2e-6) — three orders below the 1e-3 bar.
-// Launched on its own it is no faster than F(2,3) (batch 64: 64x64 64->64 162 vs 144 us, the 32x32 / 16x16 / 8x8 branches 39 /
-// 48 / 90 vs 38 / 38 / 48 us, the 32-channel branch 45 vs 48 us): with 48 instead of 64 MFMAs per superchunk the load phase
-// (18 DMA instructions per thread + 8 fragment reads + 60 VALU of first-fragment transforms) outlasts the compute phase — the
-// timeline shows 5.35 us per superchunk per block against 3.25 us of MFMA time, and offsetting the second resident block of a
-// CU by one compute phase at start (LDS_ALLOC base != 0; tried) does not move it.  Inside the grouped launch of an HRNet
-// level, where blocks of four different shapes share the CUs, the saved MFMAs do show: a 4-branch level 157 -> 146 us and
-// 5143 -> 5307 frames/s end to end (selecting it only for the large maps: 5183-5272), so the plan uses it wherever W % 4 == 0.
 // Block = 4 waves = 2 sub-tiles (32 tiles x 32 channels) x 2 position TRIPLES: triple 0 (p0..p2) reads d0..d4, triple 1
-// (p3..p5) reads d1..d5; per 8-deep k-step 5 raw reads + 3 weight reads + 48 VALU feed 12 MFMAs; the triples meet in the
-// epilogue through LDS.  One superstage of six sub-chunks (6 x 96 rows x 128 B = 72 KiB, two blocks per CU), ping-pong
-// schedule as wino_tile<true>.  Block tiles 64 tiles x 32 channels or 32 tiles x 64 channels (= 128 output pixels x 64 / 256 x 32).
-template <int HBT, int HBN>
-__device__ __forceinline__ void wino43_tile(const GemmArgs& p, const int bid, float* __restrict__ lds) {
-#ifdef CAPF_DIAG
-    unsigned long long dbg_t0 = 0, dbg_t1 = 0, dbg_t2 = 0;
-    const unsigned long long dbg_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    WINO_STAMP(dbg_t0);
-    constexpr int RPR = 32;
-    constexpr int RA = HBT / RPR, RB = HBN / RPR, NSUBLOAD = RA + RB;
-    constexpr int HSUB = (HBT + HBN) * WBK;
-    static_assert((HBT == 64 && HBN == 32) || (HBT == 32 && HBN == 64), "F(4,3) tiles");
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    const int nbn = (p.N + HBN - 1) / HBN;
-    const int tile_m = bid / nbn, tile_n = bid - tile_m * nbn;
-    const int m0 = tile_m * HBT, n0 = tile_n * HBN;
-
-    const int srow = tid >> 3;
-    const int kq = (((tid & 7) ^ ((srow >> 1) & 7))) * 4;
-    const int CC = p.Cin / WBK;
-    const int nsc = 3 * CC;
-
-    constexpr unsigned OOB_A = 0x80000000u;
-    long a_base;
-    {
-        const int b = fast_div_w(m0, p.fd_hw), rem = m0 - b * p.Ho * p.Wo;
-        const int h = fast_div_w(rem, p.fd_wo), wt = rem - h * p.Wo;
-        a_base = ((long)b * p.H * p.W + (long)(h - 1) * p.W + (4 * wt - 1)) * p.Cin;
-    }
-    const rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A + a_base), 0, 0x7FFFFF00u, 0x00020000);
-    const rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)(p.Wp + (long)n0 * p.Kpad), 0,
-                                                            (unsigned)(p.N - n0) * (unsigned)p.Kpad * 4u, 0x00020000);
-    unsigned a_rel[RA], a_mask[RA];                      // mask bit kh * 8 + j
-#pragma unroll
-    for (int i = 0; i < RA; ++i) {
-        const int t = m0 + srow + RPR * i;
-        a_rel[i] = 0;
-        a_mask[i] = 0u;
-        if (t < p.M) {
-            const int b = fast_div_w(t, p.fd_hw), rem = t - b * p.Ho * p.Wo;
-            const int h = fast_div_w(rem, p.fd_wo), wt = rem - h * p.Wo;
-            const int h0 = h - 1, w0 = 4 * wt - 1;
-            const long off = ((long)b * p.H * p.W + (long)h0 * p.W + w0) * p.Cin;
-            a_rel[i] = (unsigned)(off - a_base + kq) * 4u;
-            const int j_lo = max(0, -w0), j_hi = min(6, p.W - w0);
-            const int kh_lo = max(0, -h0), kh_hi = min(3, p.H - h0);
-            if (j_hi > j_lo && kh_hi > kh_lo) {
-                const unsigned wbits = ((1u << j_hi) - 1) & ~((1u << j_lo) - 1);
-                const unsigned below_hi = (1u << (kh_hi * 8)) - 1, below_lo = (1u << (kh_lo * 8)) - 1;
-                a_mask[i] = (wbits * 0x10101u) & below_hi & ~below_lo;
-            }
-        }
-    }
-    unsigned w_off[RB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) w_off[i] = (unsigned)((srow + RPR * i) * p.Kpad + kq) * 4u;
-
-    int u_kh = 0, u_cc = 0, u_j = 0;
-    unsigned voff[NSUBLOAD];
-    unsigned soff_a = 0;
-    auto prepare = [&]() {
-        const unsigned bit = u_kh < 3 ? (1u << (u_kh * 8 + u_j)) : 0u;
-        soff_a = __builtin_amdgcn_readfirstlane((unsigned)((u_kh * p.W + u_j) * p.Cin + u_cc * WBK) * 4u);
-#pragma unroll
-        for (int i = 0; i < RA; ++i) voff[i] = (a_mask[i] & bit) ? a_rel[i] : OOB_A;
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            voff[RA + i] = w_off[i];
-            w_off[i] += WBK * 4u;
-        }
-        if (++u_j == 6) {
-            u_j = 0;
-            if (++u_cc == CC) { u_cc = 0; ++u_kh; }
-        }
-    };
-    auto fire = [&](int idx, int sub) {
-        float* As = lds + sub * HSUB;
-        if (idx < RA)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lptr_t)(As + (idx * RPR + wave * 8) * WBK), 16, voff[idx], soff_a, 0, 0);
-        else
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lptr_t)(As + HBT * WBK + ((idx - RA) * RPR + wave * 8) * WBK), 16,
-                                                     voff[idx], 0, 0, 0);
-    };
-    auto load_superchunk = [&]() {
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            prepare();
-#pragma unroll
-            for (int i = 0; i < NSUBLOAD; ++i) fire(i, j);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    };
-
-    f32x16 acc[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-
-    const int pp = wave >> 1;                  // position triple
-    const int sub = wave & 1;                  // sub-tile
-    const int wm0 = HBT == 64 ? sub * 32 : 0;
-    const int wn0 = HBT == 64 ? 0 : sub * 32;
-    const int frow = lane & 31;
-    const int fsw = (frow >> 1) & 7;
-    const int fhalf = lane >> 5;
-
-    load_superchunk();
-
-    f32x4 dn[5];                               // raw pixels d_pp .. d_pp+4 of the next k-step
-    f32x4 v[2][3], uf[2][3];
-    const float* const a_ptr = lds + (wm0 + frow) * WBK + pp * HSUB;
-    const float* const b_ptr = lds + HBT * WBK + (wn0 + frow) * WBK + 3 * pp * HSUB;
-    auto rd_a = [&](int q, int j) { dn[j] = *reinterpret_cast<const f32x4*>(a_ptr + j * HSUB + q * 4); };
-    auto rd_b = [&](int q, int j, int buf) { uf[buf][j] = *reinterpret_cast<const f32x4*>(b_ptr + j * HSUB + q * 4); };
-    // one (position, k sub-step) unit of the input transform: which = 0, 1, 2 = this wave's first / second / third position
-    // (triple 0: p0 p1 p2 on d0..d4; triple 1: p3 p4 p5 on d1..d5), 5 VALU each — small enough to ride in an MFMA shadow
-    // B^T rows of this wave's triple as wave-uniform scalars (SGPRs): no per-lane select between the two triples' formulas
-    float cf[3][5];
-    {
-        const float t0[3][5] = {{4.f, 0.f, -5.f, 0.f, 1.f}, {0.f, -4.f, -4.f, 1.f, 1.f}, {0.f, 4.f, -4.f, -1.f, 1.f}};     // p0 p1 p2 on d0..d4
-        const float t1[3][5] = {{-2.f, -1.f, 2.f, 1.f, 0.f}, {2.f, -1.f, -2.f, 1.f, 0.f}, {4.f, 0.f, -5.f, 0.f, 1.f}};     // p3 p4 p5 on d1..d5
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 5; ++b) cf[a][b] = pp == 0 ? t0[a][b] : t1[a][b];
-    }
-    auto xform1 = [&](int which, int e, int buf) {
-        const float x0 = dn[0][e], x1 = dn[1][e], x2 = dn[2][e], x3 = dn[3][e], x4 = dn[4][e];
-        v[buf][which][e] = ((cf[which][0] * x0 + cf[which][1] * x1) + (cf[which][2] * x2 + cf[which][3] * x3)) + cf[which][4] * x4;
-    };
-    auto xform = [&](int which, int buf) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) xform1(which, e, buf);
-    };
-    auto first_frags = [&]() {
-        const int q0 = fhalf ^ fsw;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) rd_a(q0, j);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) rd_b(q0, j, 0);
-        xform(0, 0); xform(1, 0); xform(2, 0);
-    };
-    first_frags();
-    WINO_STAMP(dbg_t1);
-
-    // epilogue operands of the two register groups this wave finishes (g = 2 pp, 2 pp + 1), four output pixels each
-    const int t = m0 + wm0 + (lane & 31);
-    const bool t_ok = t < p.M;
-    const long o_row = (long)(4 * t) * p.omap.S1 + p.omap.off;
-    const long r_row = (long)(4 * t) * p.rmap.S1 + p.rmap.off;
-    f32x4 bv[2], rr[2][4];
-    auto load_epilogue_operands = [&]() {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int n = n0 + wn0 + 4 * (lane >> 5) + 8 * (2 * pp + k);
-            bv[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int o = 0; o < 4; ++o) rr[k][o] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (n < p.N) {
-                if (p.bias) bv[k] = *reinterpret_cast<const f32x4*>(p.bias + n);
-                if (p.res && t_ok) {
-#pragma unroll
-                    for (int o = 0; o < 4; ++o) rr[k][o] = *reinterpret_cast<const f32x4*>(p.res + r_row + (long)o * p.rmap.S1 + n);
-                }
-            }
-        }
-    };
-
-    for (int sc = 0; sc < nsc; ++sc) {
-        if (sc == nsc - 1) load_epilogue_operands();
-#pragma unroll
-        for (int step = 0; step < 4; ++step) {
-            const int fb = step & 1, nb = fb ^ 1;
-            const int q_next = ((step + 1) * 2 + fhalf) ^ fsw;
-#pragma unroll
-            for (int i = 0; i < 12; ++i) {
-                const int pq = i % 3, e = i / 3;
-                acc[pq] = __builtin_amdgcn_mfma_f32_32x32x2f32(uf[fb][pq][e], v[fb][pq][e], acc[pq], 0, 0, 0);
-                if (step < 3) {
-                    if (i == 0) { rd_a(q_next, 0); rd_a(q_next, 1); }
-                    else if (i == 1) { rd_a(q_next, 2); rd_a(q_next, 3); }
-                    else if (i == 2) { rd_a(q_next, 4); rd_b(q_next, 0, nb); }
-                    else if (i == 3) { rd_b(q_next, 1, nb); rd_b(q_next, 2, nb); }
-                    else if (i >= 6) {                 // 12 transform units over slots 6..11, two per slot
-                        const int u0 = (i - 6) * 2, u1 = u0 + 1;
-                        xform1(u0 / 4, u0 % 4, nb);
-                        xform1(u1 / 4, u1 % 4, nb);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if (sc + 1 < nsc) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            load_superchunk();
-            first_frags();
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    WINO_STAMP(dbg_t2);
-    __builtin_amdgcn_s_barrier();              // every wave is done with the superstage: it becomes the exchange buffer
-
-    // partial output transform of this wave's triple (s[o] = contribution to output pixel o):
-    //   triple 0 (m0 m1 m2): m0 + (m1 + m2),  m1 - m2,        m1 + m2,        m1 - m2
-    //   triple 1 (m3 m4 m5): m3 + m4,         2 (m3 - m4),    4 (m3 + m4),    8 (m3 - m4) + m5
-    float qf[4][3];                            // A^T columns of this wave's triple, wave-uniform
-    {
-        const float t0[4][3] = {{1.f, 1.f, 1.f}, {0.f, 1.f, -1.f}, {0.f, 1.f, 1.f}, {0.f, 1.f, -1.f}};
-        const float t1[4][3] = {{1.f, 1.f, 0.f}, {2.f, -2.f, 0.f}, {4.f, 4.f, 0.f}, {8.f, -8.f, 1.f}};
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) qf[a][b] = pp == 0 ? t0[a][b] : t1[a][b];
-    }
-    auto partial = [&](int g, int o, int e) -> float {      // g, o, e are compile-time after unrolling: static register indices
-        return (qf[o][0] * acc[0][4 * g + e] + qf[o][1] * acc[1][4 * g + e]) + qf[o][2] * acc[2][4 * g + e];
-    };
-    float* const xch = lds;                    // [sub][writer pp][8 slots][64 lanes] f32x4 = 32 KiB
-    {
-        float* dst = xch + (((sub * 2 + pp) * 8) * 64 + lane) * 4;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            if ((g >> 1) == pp) continue;      // (wave-uniform) a group this wave finishes itself
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                f32x4 sv;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sv[e] = partial(g, o, e);
-                *reinterpret_cast<f32x4*>(dst + (4 * (g & 1) + o) * 64 * 4) = sv;
-            }
-        }
-    }
-    __syncthreads();
-    const float* src = xch + (((sub * 2 + (pp ^ 1)) * 8) * 64 + lane) * 4;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if ((g >> 1) != pp) continue;
-        const int k = g & 1;
-        const int n = n0 + wn0 + 4 * (lane >> 5) + 8 * g;
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            const f32x4 other = *reinterpret_cast<const f32x4*>(src + (4 * k + o) * 64 * 4);
-            f32x4 y;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float mine = partial(g, o, e);
-                // fixed order whichever wave finishes the group: (triple 0 partial) + (triple 1 partial)
-                float sv = (pp == 0 ? mine + other[e] : other[e] + mine) + bv[k][e] + rr[k][o][e];
-                if (p.act == ACT_RELU) sv = relu_f(sv);
-                y[e] = sv;
-            }
-            if (t_ok && n < p.N) *reinterpret_cast<f32x4*>(p.out + o_row + (long)o * p.omap.S1 + n) = y;
-        }
-    }
-#ifdef CAPF_DIAG
-    if (tid == 0 && blockIdx.x < 8192) {
-        unsigned long long* d = capf_wino_timeline + (size_t)blockIdx.x * 8;
-        d[0] = dbg_t0; d[1] = dbg_t1; d[2] = dbg_t2; d[3] = __builtin_amdgcn_s_memtime();
-        d[4] = dbg_r0; d[5] = 0; d[6] = 0; d[7] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
-}
-#endif
-
+// (p3..p5) reads d1..d5; per 8-deep k-step 5 raw reads + 3 weight reads feed 12 MFMAs; the triples meet in the epilogue through
+// LDS.  Block tiles 64 tiles x 32 channels or 32 tiles x 64 channels (= 256 output pixels x 32 / 128 x 64).
+// Where it pays (measured with 32-channel sub-chunks, 72 KiB and two blocks per CU: EXPERIMENTS.md 4.1f): launched on its own
+// it is no faster than F(2,3) (batch 64: 64x64 64->64 162 vs 144 us, the 32x32 / 16x16 / 8x8 branches 39 / 48 / 90 vs 38 / 38 /
+// 48 us, the 32-channel branch 45 vs 48 us) -- with 48 instead of 64 MFMAs per superchunk the load phase outlasts the compute
+// phase.  Inside the grouped launch of an HRNet level, where blocks of four different shapes share the CUs, the saved MFMAs do
+// show: a 4-branch level 157 -> 146 us and 5143 -> 5307 frames/s end to end (selecting it only for the large maps: 5183-5272),
+// so the plan uses F(4,3) wherever W % 4 == 0.
 #if defined(__HIP_DEVICE_COMPILE__)
-// F(4,3) with 16-channel sub-chunks ("short" superchunks): the same maths, tile shapes, wave roles and epilogue as wino43_tile,
-// but a superchunk is (kh, 16 channels, 6 raw pixels): 6 x 96 rows x 64 B = 36 KiB of LDS instead of 72, and the kernel that
-// hosts it is built for THREE resident blocks per CU (<= 168 registers).  Why: a ping-pong block alternates a compute phase
-// and a load phase of about the same length and cannot overlap them itself, so a launch lasts (sum of the blocks' serial
-// times) / (resident blocks) unless the matrix pipe saturates first.  With two residents at ~48 % duty each the pipe idles
+// 16-channel sub-chunks ("short" superchunks): a superchunk is (kh, 16 channels, 6 raw pixels): 6 x 96 rows x 64 B = 36 KiB of LDS
+// instead of 72, and the kernel that hosts the tile is built for THREE resident blocks per CU (<= 168 registers).  Why: a ping-pong
+// block alternates a compute phase and a load phase of about the same length and cannot overlap them itself, so a launch lasts
+// (sum of the blocks' serial times) / (resident blocks) unless the matrix pipe saturates first.  With two residents at ~48 % duty each the pipe idles
 // whenever both load and stalls whenever both compute (measured: 0.45 of the nominal MFMA rate, 1.8 blocks resident on
 // average); a third resident fills those holes.  Per superchunk a wave issues 24 MFMAs (2 k-steps of 12) and 9 LDS-DMA
 // instructions (3 per sub-chunk pair).
 //   LDS image of a superchunk: raw-pixel sub-chunks A_0..A_5 (HBT rows x 64 B each), then weight positions W_0..W_5 (HBN rows):
 //   576 rows = 9 DMA rounds of 64 rows (4 lanes per row); 16-byte quad q of row r lives at position q ^ ((r >> 2) & 3):
 //   conflict-free ds_read_b128.
-// The packed weights are wino43_tile's ([N][(kh, 32-channel chunk, p, c)], K'' = 18 Cin): both kernels share one copy.
-// DB = true: TWO superstages (72 KiB, two resident blocks): the 9 DMA instructions of superchunk s + 1 ride in MFMA slots of
-// superchunk s, so a block's own load latency hides behind its own MFMAs and only [wait, barrier, first fragments] stays
-// exposed between compute phases (the partner block covers that).  Measured motive (tools/wino_level_timeline.py, HRNet-32
-// level at batch 64, DB = false): 2.4 - 3.9 us per superchunk per block against 0.79 us of MFMA time -- the launch lasts as
-// long as the 48-superchunk tiles of the 8 x 8 branch take to crawl through their load phases (115 of 133 us).
-template <int HBT, int HBN, bool DB>
+// The packed weights are in 32-channel chunks ([N][(kh, 32-channel chunk, p, c)], K'' = 18 Cin): a superchunk reads one half of one.
+// Measured (tools/wino_level_timeline.py, HRNet-32 level at batch 64): 2.4 - 3.9 us per superchunk per block against 0.79 us of
+// MFMA time -- the launch lasts as long as the 48-superchunk tiles of the 8 x 8 branch take to crawl through their load phases
+// (115 of 133 us).
+template <int HBT, int HBN>
 __device__ __forceinline__ void wino43s_tile(const GemmArgs& p, const int bid, float* __restrict__ lds) {
 #ifdef CAPF_DIAG
     unsigned long long dbg_t0 = 0, dbg_t1 = 0, dbg_t2 = 0, dbg_last = 0;
@@ -961,8 +635,7 @@ __device__ __forceinline__ void wino43s_tile(const GemmArgs& p, const int bid, f
     // weights: row wrow of the block's N range; position p = round's first position + wsub; 16-channel half (cc & 1) of chunk cc >> 1
     const unsigned w_rel = (unsigned)(wrow * p.Kpad + kq + wsub * 32) * 4u;
 
-    // LDS image of a superchunk: A_j (HBT rows x 64 B) at j * PSUB_A, j = 0..5, then W_p (HBN rows) at 6 PSUB_A + p * PSUB_W
-    constexpr int STAGE = 6 * (PSUB_A + PSUB_W);                 // floats per superstage (9216 = 36 KiB)
+    // LDS image of a superchunk (9216 floats = 36 KiB): A_j (HBT rows x 64 B) at j * PSUB_A, j = 0..5, then W_p (HBN rows) at 6 PSUB_A + p * PSUB_W
     int u_kh = 0, u_cc = 0;                                      // walk of the superchunk being staged: chunk fastest, then kh
     unsigned soff_a = 0, soff_w = 0, row_mask = 0;
     auto prepare = [&]() {                                       // offsets of the next superchunk to stage
@@ -1014,9 +687,8 @@ __device__ __forceinline__ void wino43s_tile(const GemmArgs& p, const int bid, f
     f32x4 v[2][3], uf[2][3];
     const float* const a_ptr = lds + (wm0 + frow) * BK + pp * PSUB_A;              // raw pixel j = pp + jj
     const float* const b_ptr = lds + 6 * PSUB_A + (wn0 + frow) * BK + 3 * pp * PSUB_W; // weight position 3 pp + k
-    int so = 0;                                // float offset of the superstage being consumed (DB: 0 / STAGE)
-    auto rd_a = [&](int q, int jj) { dn[jj] = *reinterpret_cast<const f32x4*>(a_ptr + so + jj * PSUB_A + q * 4); };
-    auto rd_b = [&](int q, int k, int buf) { uf[buf][k] = *reinterpret_cast<const f32x4*>(b_ptr + so + k * PSUB_W + q * 4); };
+    auto rd_a = [&](int q, int jj) { dn[jj] = *reinterpret_cast<const f32x4*>(a_ptr + jj * PSUB_A + q * 4); };
+    auto rd_b = [&](int q, int k, int buf) { uf[buf][k] = *reinterpret_cast<const f32x4*>(b_ptr + k * PSUB_W + q * 4); };
     // Input transform of one k sub-step e for this wave's triple, SPECIALISED per triple (a wave-uniform branch picks the loop
     // body): with the B^T rows as run-time scalars every unit cost 6 VALU (two of five coefficients are 0 or +-1 in every row
     // but the compiler cannot know), 72 per k-step; written out they are 8 (triple 0) / 6 (triple 1) per sub-step = 32 / 24:
@@ -1089,8 +761,6 @@ __device__ __forceinline__ void wino43s_tile(const GemmArgs& p, const int bid, f
 
     auto superchunk = [&](auto more_c) {
         constexpr bool more = decltype(more_c)::value;
-        float* const next_stage = lds + (DB ? STAGE - so : 0);
-        if (DB && more) prepare();
 #pragma unroll
         for (int step = 0; step < 2; ++step) {
             const int fb = step & 1, nb = fb ^ 1;
@@ -1106,27 +776,15 @@ __device__ __forceinline__ void wino43s_tile(const GemmArgs& p, const int bid, f
                     else if (i == 3) { rd_b(q_next, 1, nb); rd_b(q_next, 2, nb); }
                     else if (i >= 6 && i < 10) xform_e(ppc, i - 6, nb);      // the next k-step's transforms, one sub-step per slot
                 }
-                if (DB && more) {                      // the next superchunk's nine DMA instructions, one per MFMA slot
-                    const int k = step == 0 ? i - 4 : i + 8;        // step 0 slots 4..11 -> 0..7, step 1 slot 0 -> 8
-                    if (k >= 0 && k < 9) fire(k, next_stage);
-                }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
         WINO_PHASE(0);
         if (more) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (DB) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                WINO_PHASE(3);
-                __builtin_amdgcn_s_barrier();          // the next superchunk has landed; every wave is done reading this one
-                WINO_PHASE(4);
-                so = STAGE - so;
-            } else {
-                __builtin_amdgcn_s_barrier();
-                WINO_PHASE(1);
-                load_superchunk(lds);
-            }
+            __builtin_amdgcn_s_barrier();
+            WINO_PHASE(1);
+            load_superchunk(lds);
             first_frags(ppc);
             WINO_PHASE(5);
         }
@@ -1221,27 +879,23 @@ __device__ __forceinline__ int xcd_remap_w(int b, int nblk) {   // see igemm_f32
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
 }
 
-// tile configuration of a problem: F(2,3): 0 = 64 tiles x 64 channels, 1 = 64 x 32, 2 = 32 x 64; F(4,3): 3 = 64 x 32, 4 = 32 x 64
+// tile configuration of an F(2,3) problem: 0 = 64 tiles x 64 channels, 1 = 64 x 32, 2 = 32 x 64
 #if defined(__HIP_DEVICE_COMPILE__)
-template <bool PP>
 __device__ __forceinline__ void wino_dispatch(const GemmArgs& p, int cfg, int bid, float* lds) {
     if (cfg == 1) wino_tile_h<64, 32>(p, bid, lds);
     else if (cfg == 2) wino_tile_h<32, 64>(p, bid, lds);
-    else if (cfg == 3) wino43_tile<64, 32>(p, bid, lds);
-    else if (cfg == 4) wino43_tile<32, 64>(p, bid, lds);
-    else wino_tile<PP>(p, bid, lds);
+    else wino_tile(p, bid, lds);
 }
 #endif
 
-template <bool PP>
 __global__ __launch_bounds__(256, 2) void igemm_wino_kernel(GemmArgs p, int cfg) {      // 2 blocks per CU: <= 256 registers per wave
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float wlds[];
-    wino_dispatch<PP>(p, cfg, xcd_remap_w(blockIdx.x, gridDim.x), wlds);
+    wino_dispatch(p, cfg, xcd_remap_w(blockIdx.x, gridDim.x), wlds);
 #endif
 }
 
-// grouped launch: up to MAXG Winograd problems in one grid (the 3x3 convs of an HRNet level), longest K first
+// grouped launch: up to MAXG F(2,3) problems in one grid (the 3x3 convs of an HRNet level), longest K first
 struct WinoGroupArgs {
     GemmArgs g[MAXG];
     GroupLayout lay;
@@ -1250,13 +904,12 @@ struct WinoGroupArgs {
 };
 static_assert(sizeof(WinoGroupArgs) == MAXG * sizeof(GemmArgs) + (3 * MAXG + 2) * sizeof(int), "kernel argument layout");
 
-template <bool PP>
 __global__ __launch_bounds__(256, 2) void igemm_wino_group_kernel(WinoGroupArgs ga) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float wlds[];
     const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
     if (!t.live) return;
-    wino_dispatch<PP>(ga.g[t.pi], ga.cfg[t.pi], t.bid, wlds);
+    wino_dispatch(ga.g[t.pi], ga.cfg[t.pi], t.bid, wlds);
 #endif
 }
 
@@ -1265,27 +918,11 @@ struct Wino43GroupArgs {
     GemmArgs g[MAXG];
     GroupLayout lay;
     int cfg[MAXG];                             // 3: 64 tiles x 32 channels, 4: 32 tiles x 64 channels
-    int prio[MAXG];                            // s_setprio level of the problem's waves (see launch_wino43_group)
     int n;
 };
-static_assert(sizeof(Wino43GroupArgs) == MAXG * sizeof(GemmArgs) + (4 * MAXG + 2) * sizeof(int), "kernel argument layout");
+static_assert(sizeof(Wino43GroupArgs) == MAXG * sizeof(GemmArgs) + (3 * MAXG + 2) * sizeof(int), "kernel argument layout");
 
 [[maybe_unused]] static constexpr int W43S_LDS = 6 * (64 + 32) * 16;              // floats per superstage (36 KiB); device code only
-template <bool DB>
-__device__ __forceinline__ void wino43_group_body(const Wino43GroupArgs& ga, float* wlds) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
-    if (!t.live) return;
-    const int pi = t.pi, bid = t.bid;
-    // issue priority by K length (measured: no effect on the level either way; kept switchable in the diagnosis build)
-    const int prio = ga.prio[pi];
-    if (prio == 3) __builtin_amdgcn_s_setprio(3);
-    else if (prio == 2) __builtin_amdgcn_s_setprio(2);
-    else if (prio == 1) __builtin_amdgcn_s_setprio(1);
-    if (ga.cfg[pi] == 3) wino43s_tile<64, 32, DB>(ga.g[pi], bid, wlds);
-    else wino43s_tile<32, 64, DB>(ga.g[pi], bid, wlds);
-#endif
-}
 
 // (the per-triple transform needs no coefficient registers: 128 registers without the residual prefetch, i.e. FOUR residents
 // would fit -- measured: no faster than three (124.7 vs 124.6 us per level, 6122 vs 6177 frames/s): every resident added
@@ -1293,14 +930,10 @@ __device__ __forceinline__ void wino43_group_body(const Wino43GroupArgs& ga, flo
 __global__ __launch_bounds__(256, 3) void igemm_wino43_group_kernel(Wino43GroupArgs ga) {          // ping-pong, three residents
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) float wlds[W43S_LDS];
-    wino43_group_body<false>(ga, wlds);
-#endif
-}
-
-__global__ __launch_bounds__(256, 2) void igemm_wino43_group_db_kernel(Wino43GroupArgs ga) {       // double-buffered, two residents
-#if defined(__HIP_DEVICE_COMPILE__)
-    __shared__ __attribute__((aligned(16))) float wlds[2 * W43S_LDS];
-    wino43_group_body<true>(ga, wlds);
+    const GroupSlot t = group_slot(ga.lay, ga.n, blockIdx.x);
+    if (!t.live) return;
+    if (ga.cfg[t.pi] == 3) wino43s_tile<64, 32>(ga.g[t.pi], t.bid, wlds);
+    else wino43s_tile<32, 64>(ga.g[t.pi], t.bid, wlds);
 #endif
 }
 
@@ -1369,31 +1002,20 @@ static bool wino_prepare(GemmArgs& a) {
     return true;
 }
 
-static hipError_t wino_attr() {          // (per device: DynLdsAttr)
-    static DynLdsAttr big[2], half[2];
-    const int big_bytes = WLDS * (int)sizeof(float), half_bytes = 6 * (64 + 32) * WBK * (int)sizeof(float);
-    hipError_t r = big[0].ensure(reinterpret_cast<const void*>(igemm_wino_kernel<false>), big_bytes);
-    if (r == hipSuccess) r = big[1].ensure(reinterpret_cast<const void*>(igemm_wino_group_kernel<false>), big_bytes);
-    if (r == hipSuccess) r = half[0].ensure(reinterpret_cast<const void*>(igemm_wino_kernel<true>), half_bytes);
-    if (r == hipSuccess) r = half[1].ensure(reinterpret_cast<const void*>(igemm_wino_group_kernel<true>), half_bytes);
+static hipError_t wino_attr() {          // (per device: DynLdsAttr; the 64 x 64 tile's 64 KiB is the limit without it)
+    static DynLdsAttr one, group;
+    hipError_t r = one.ensure(reinterpret_cast<const void*>(igemm_wino_kernel), WLDS * (int)sizeof(float));
+    if (r == hipSuccess) r = group.ensure(reinterpret_cast<const void*>(igemm_wino_group_kernel), WLDS * (int)sizeof(float));
     return r;
 }
 
-// CAPF_WINO_MODE (A/B runs only): 0 (default) ping-pong, 64 KiB, two blocks per CU; 1: double-buffered 64 x 64 tile, 128 KiB
-static int wino_mode() {
-    static const int m = [] { const char* e = diag_env("CAPF_WINO_MODE"); return e ? atoi(e) : 0; }();
-    return m;
-}
-
 static const int kWT[5] = {64, 64, 32, 64, 32}, kWN[5] = {64, 32, 64, 32, 64};
-static const int kWLDS[5] = {WLDS / 2, 4 * (64 + 32) * WBK, 4 * (64 + 32) * WBK, 6 * (64 + 32) * WBK, 6 * (64 + 32) * WBK};   // floats
+static const int kWLDS[3] = {WLDS, 4 * (64 + 32) * WBK, 4 * (64 + 32) * WBK};   // floats of dynamic LDS (F(2,3) tiles; the F(4,3) kernel's is static)
 
 // tile configuration for a prepared problem (a.M = tiles).  F(2,3): narrow outputs -> 64 x 32; few tiles -> 32 x 64 (twice the
 // blocks).  F(4,3): 32 tiles x 64 channels, or 64 x 32 for outputs that are not a multiple of 64 wide.
 static int wino_cfg(const GemmArgs& a) {
-    static const int forced = [] { const char* e = diag_env("CAPF_WINO_CFG"); return e ? atoi(e) : -1; }();   // tuning only
     if (is43(a)) return a.N % 64 != 0 ? 3 : 4;
-    if (forced == 1 || (forced == 2 && a.N % 64 == 0)) return forced;
     if (a.N % 64 != 0) return 1;
     const long blocks = (long)((a.M + 63) / 64) * (a.N / 64);
     return blocks < 512 ? 2 : 0;
@@ -1401,132 +1023,69 @@ static int wino_cfg(const GemmArgs& a) {
 
 static int wino_tiles(const GemmArgs& a, int cfg) { return ((a.M + kWT[cfg] - 1) / kWT[cfg]) * ((a.N + kWN[cfg] - 1) / kWN[cfg]); }
 
-// F(4,3) problems take the three-resident kernel (16-channel sub-chunks need Cin % 32 == 0 for the shared weight layout: always)
-static int wino43_short() {
-    // 0: the 72 KiB ping-pong tiles of igemm_wino_group_kernel; 1: 16-channel superchunks, ping-pong, three residents;
-    // 2: 16-channel superchunks, double-buffered, two residents
-    static const int v = [] { const char* e = diag_env("CAPF_WINO43_SHORT"); return e ? atoi(e) : 1; }();     // A/B runs only
-    return v;
-}
-
-static int wino43_prio() {
-    static const int v = [] { const char* e = diag_env("CAPF_WINO43_PRIO"); return e ? atoi(e) : 0; }();       // A/B runs only
-    return v;
-}
-
+// F(4,3) problems, alone or grouped, take the three-resident kernel (igemm_wino43_group_kernel)
 static hipError_t launch_wino43_group(const GemmArgs* prep, const int* cfgs, int n, hipStream_t s) {
     int order[MAXG], tiles[MAXG];
-    double cost[MAXG], sorted[MAXG];
+    double cost[MAXG];
     for (int i = 0; i < n; ++i) cost[i] = (double)prep[i].Cin;   // both tile shapes do the same work per block
     group_order(n, cost, order);                 // longest tile first
-    if (const char* ord = diag_env("CAPF_WINO43_ORDER")) {       // A/B runs only: dispatch order as a permutation of the cost ranks, e.g. "0312"
-        int tmp[MAXG], m = 0;
-        for (const char* c = ord; *c && m < n; ++c)
-            if (*c >= '0' && *c - '0' < n) tmp[m++] = order[*c - '0'];
-        if (m == n) for (int i = 0; i < n; ++i) order[i] = tmp[i];
-    }
     Wino43GroupArgs ga{};
     ga.n = n;
-    for (int i = 0; i < n; ++i) { tiles[i] = wino_tiles(prep[order[i]], cfgs[order[i]]); sorted[i] = cost[order[i]]; }
+    for (int i = 0; i < n; ++i) tiles[i] = wino_tiles(prep[order[i]], cfgs[order[i]]);
     const int start = group_fill(ga.lay, n, tiles);
-    for (int i = 0; i < n; ++i) {
-        ga.g[i] = prep[order[i]];
-        ga.cfg[i] = cfgs[order[i]];
-        // longest K -> priority 3, next distinct K length 2, ...; problems of the shortest K (and lone problems) stay at 0
-        int longer = 0;
-        for (int j = 0; j < n; ++j)
-            if (sorted[j] > sorted[i] && (j == 0 || sorted[j] != sorted[j - 1])) ++longer;
-        int shorter = 0;
-        for (int j = 0; j < n; ++j) shorter += sorted[j] < sorted[i];
-        ga.prio[i] = (shorter && wino43_prio()) ? std::max(1, 3 - longer) : 0;
-    }
-    if (wino43_short() == 2) hipLaunchKernelGGL(igemm_wino43_group_db_kernel, dim3(start), dim3(256), 0, s, ga);
-    else hipLaunchKernelGGL(igemm_wino43_group_kernel, dim3(start), dim3(256), 0, s, ga);
+    for (int i = 0; i < n; ++i) { ga.g[i] = prep[order[i]]; ga.cfg[i] = cfgs[order[i]]; }
+    hipLaunchKernelGGL(igemm_wino43_group_kernel, dim3(start), dim3(256), 0, s, ga);
     return hipGetLastError();
 }
 
-// (large launches: the split-fp32 tile, igemm_f32x3_ws.hip; F(4,3) problems, alone or grouped, run igemm_wino43_group_kernel)
-WinoPath gemm_wino_route(const GemmArgs& a) {
-    if (gemm_f32x3_wanted(a)) return WinoPath::X3;
-    return is43(a) && wino43_short() ? WinoPath::F43_GROUP : WinoPath::WINO;
-}
-
-const char* gemm_wino_kernel_name(const GemmArgs& a) {
-    const WinoPath p = gemm_wino_route(a);
-    return p == WinoPath::X3 ? gemm_f32x3_kernel_name(a) : p == WinoPath::F43_GROUP ? "igemm_wino43_group" : "igemm_wino<w4,F(2,3)>";
-}
+const char* gemm_wino_kernel_name(const GemmArgs& a) { return is43(a) ? "igemm_wino43_group" : "igemm_wino<w4,F(2,3)>"; }
 
 hipError_t launch_gemm_wino(const GemmArgs& a_in, hipStream_t s) {
-    const WinoPath path = gemm_wino_route(a_in);
-    if (path == WinoPath::X3) return launch_gemm_f32x3(a_in, s);
     GemmArgs a = a_in;
     if (!wino_prepare(a)) return hipErrorInvalidValue;
     hipError_t r = wino_attr();
     if (r != hipSuccess) return r;
     const int cfg = wino_cfg(a);
-    if (path == WinoPath::F43_GROUP) return launch_wino43_group(&a, &cfg, 1, s);
-    const int nb = wino_tiles(a, cfg);
-    if (wino_mode() == 1) hipLaunchKernelGGL(igemm_wino_kernel<false>, dim3(nb), dim3(256), WLDS * sizeof(float), s, a, cfg);
-    else hipLaunchKernelGGL(igemm_wino_kernel<true>, dim3(nb), dim3(256), kWLDS[cfg] * sizeof(float), s, a, cfg);
+    if (is43(a)) return launch_wino43_group(&a, &cfg, 1, s);
+    hipLaunchKernelGGL(igemm_wino_kernel, dim3(wino_tiles(a, cfg)), dim3(256), kWLDS[cfg] * sizeof(float), s, a, cfg);
     return hipGetLastError();
 }
 
-hipError_t launch_gemm_wino_group(const GemmArgs* list, int n, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    if (n == 1) return launch_gemm_wino(list[0], s);
-    if (n > MAXG) return hipErrorInvalidValue;
-    {   // the problems the split-fp32 tile wants (a per-problem rule: igemm_f32x3_ws.hip) leave in one launch of their own
-        GemmArgs x3[MAXG], rest[MAXG];
-        int nx = 0, nrest = 0;
-        for (int i = 0; i < n; ++i) {
-            if (gemm_wino_route(list[i]) == WinoPath::X3) x3[nx++] = list[i];
-            else rest[nrest++] = list[i];
-        }
-        if (nx) {
-            const hipError_t rx = launch_gemm_f32x3_group(x3, nx, s);
-            if (rx != hipSuccess || nrest == 0) return rx;
-            return launch_gemm_wino_group(rest, nrest, s);
-        }
-    }
+hipError_t launch_gemm_wino_group(const GemmArgs* list, int n_all, hipStream_t s) {
+    if (n_all <= 0) return hipSuccess;
+    if (n_all == 1) return launch_gemm_wino(list[0], s);
+    if (n_all > MAXG) return hipErrorInvalidValue;
     hipError_t r = wino_attr();
     if (r != hipSuccess) return r;
+    // F(4,3) problems -> their own grid (three resident blocks per CU); the F(2,3) ones -> the grid below, a lone one its own kernel
+    GemmArgs p43[MAXG], prep[MAXG];
+    int c43[MAXG], n43 = 0, n = 0, lone = -1;
+    for (int i = 0; i < n_all; ++i) {
+        GemmArgs a = list[i];
+        if (!wino_prepare(a)) return hipErrorInvalidValue;
+        if (is43(a)) { p43[n43] = a; c43[n43++] = wino_cfg(a); }
+        else { prep[n++] = a; lone = i; }
+    }
+    if (n43) {
+        r = launch_wino43_group(p43, c43, n43, s);
+        if (r != hipSuccess) return r;
+    }
+    if (n <= 1) return n ? launch_gemm_wino(list[lone], s) : hipSuccess;
     int cfgs[MAXG], tiles[MAXG], order[MAXG];
     double cost[MAXG];
-    GemmArgs prep[MAXG];
     int lds_floats = 0;
-    if (wino43_short()) {                        // F(4,3) problems -> their own grid (three resident blocks per CU); the rest below
-        GemmArgs p43[MAXG], rest[MAXG];
-        int c43[MAXG], n43 = 0, nrest = 0;
-        for (int i = 0; i < n; ++i) {
-            GemmArgs a = list[i];
-            if (!wino_prepare(a)) return hipErrorInvalidValue;
-            if (gemm_wino_route(list[i]) == WinoPath::F43_GROUP) { p43[n43] = a; c43[n43++] = wino_cfg(a); }
-            else rest[nrest++] = list[i];
-        }
-        if (n43) {
-            r = launch_wino43_group(p43, c43, n43, s);
-            if (r != hipSuccess || nrest == 0) return r;
-            if (nrest == 1) return launch_gemm_wino(rest[0], s);
-            list = rest;                         // (local copies live until the launch below returns)
-            n = nrest;
-            return launch_gemm_wino_group(list, n, s);
-        }
-    }
     for (int i = 0; i < n; ++i) {
-        prep[i] = list[i];
-        if (!wino_prepare(prep[i])) return hipErrorInvalidValue;
         const int cfg = wino_cfg(prep[i]);
         lds_floats = std::max(lds_floats, kWLDS[cfg]);
         cfgs[i] = cfg;
         tiles[i] = wino_tiles(prep[i], cfg);
-        cost[i] = (double)prep[i].Cin * kWT[cfg] * kWN[cfg] * (cfg >= 3 ? 1.5 : 1.0);
+        cost[i] = (double)prep[i].Cin * kWT[cfg] * kWN[cfg];
     }
     WinoGroupArgs ga{};
     ga.n = n;
     const int start = group_layout(ga.lay, n, tiles, cost, order);       // longest tile first
     for (int i = 0; i < n; ++i) { ga.g[i] = prep[order[i]]; ga.cfg[i] = cfgs[order[i]]; }
-    if (wino_mode() == 1) hipLaunchKernelGGL(igemm_wino_group_kernel<false>, dim3(start), dim3(256), WLDS * sizeof(float), s, ga);
-    else hipLaunchKernelGGL(igemm_wino_group_kernel<true>, dim3(start), dim3(256), lds_floats * sizeof(float), s, ga);
+    hipLaunchKernelGGL(igemm_wino_group_kernel, dim3(start), dim3(256), lds_floats * sizeof(float), s, ga);
     return hipGetLastError();
 }
 

@@ -92,10 +92,11 @@ struct GemmArgs {
                         // nullptr; launch_gemm_bf16 / _group switch to that kernel for launches of >= 2048 tiles
     const float* Wp3;   // bf16 3x3 stride-1 convs: the same weights in the 2-D halo tile's layout (igemm_bf16_ws.hip), or nullptr;
                         // launch_gemm_bf16 / _group run the problems gemm_bf16_ws_wanted() accepts on that kernel.
-                        // fp32 3x3 stride-1 convs: the weights as three bf16 pieces (igemm_f32x3_ws.hip), or nullptr;
-                        // launch_gemm_wino / _group run the problems gemm_f32x3_wanted() accepts on that kernel
-    int x3_h2;          // fp32 3x3 stride-1 convs: Wp3 holds two block-scaled fp16 pieces (igemm_f32h2_ws.hip, launch_pack_conv_f32h2) and the
-                        // problems gemm_f32x3_wanted() accepts run on THAT tile (three piece products per fp32 MAC instead of six)
+                        // fp32 3x3 stride-1 convs: the weights as the split-fp32 tile's pieces, or nullptr -- three bf16 pieces
+                        // (igemm_f32x3_ws.hip, launch_pack_conv_f32x3) or, with x3_h2 set, two block-scaled fp16 pieces (igemm_f32h2_ws.hip,
+                        // launch_pack_conv_f32h2).  Read by the tile launchers alone; who calls them decides (Engine::gemm_family)
+    int x3_h2;          // which pieces Wp3 holds: each tile launcher refuses the other's pack.  (GemmArgs is the fp32 / bf16 / Winograd kernels'
+                        // argument: a member in front of the ones they read cannot leave without moving those and changing their code)
     const float* Wh2;   // the same weights as the two-fp16-piece pack of igemm_f32h2.hip (launch_pack_f32h2_gemm: Wp's [N][Kpad] geometry, then [N]
                         // inverse channel scales), or nullptr: launch_gemm_f32 / _group run the problem on that kernel where gemm_f32h2g_ok()
                         // accepts it (the HBM-bound pointwise kernels keep theirs)
@@ -300,14 +301,13 @@ bool gemm_bf16_pwchain_ok(const GemmArgs& a, const GemmArgs& b);
 hipError_t launch_gemm_bf16_pwchain(const GemmArgs& a, const GemmArgs& b, hipStream_t s);
 const char* gemm_bf16_pwchain_kernel_name(int f16 = 0);
 
-// Winograd F(2,3)-along-W variant of the 3x3 / stride-1 / pad-1 fp32 conv (igemm_wino.hip): same GemmArgs as the direct conv,
-// Wp = weights packed by launch_pack_conv_wino ([N][12 * Cin]); needs Cin % 32 == 0, even W, N % 4 == 0
+// Winograd-along-W variants of the 3x3 / stride-1 / pad-1 fp32 conv (igemm_wino.hip): same GemmArgs as the direct conv, Wp = weights packed
+// by launch_pack_conv_wino -- [N][12 * Cin]: F(2,3), even W; [N][18 * Cin]: F(4,3), W % 4 == 0 (the variant rides in Kpad); needs
+// Cin % 32 == 0, N % 4 == 0.  An F(4,3) problem, alone or in a list, runs the F(4,3) group kernel, an F(2,3) one the single-problem or the
+// grouped F(2,3) kernel; a problem that is neither is an error
 bool gemm_wino_ok(const GemmArgs& a);
 hipError_t launch_gemm_wino(const GemmArgs& a, hipStream_t s);
 hipError_t launch_gemm_wino_group(const GemmArgs* list, int n, hipStream_t s);
-// the path launch_gemm_wino takes: the split-fp32 tile (gemm_f32x3_wanted), the F(4,3) group kernel, the single-problem Winograd kernel
-enum class WinoPath { X3, F43_GROUP, WINO };
-WinoPath gemm_wino_route(const GemmArgs& a);
 const char* gemm_wino_kernel_name(const GemmArgs& a);
 hipError_t launch_pack_conv_wino(const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
                                  float eps, float* Wp, float* bias, int Cout, int Cin, hipStream_t s, int variant = 23);
@@ -360,27 +360,27 @@ hipError_t launch_pack_conv_bf16_ws(const float* w, const float* gamma, const fl
 // losslessly into three bf16 pieces, the six piece products of weight >= 2^-18 accumulated in fp32 -- results to fp32 accumulation
 // order.  Any width up to 256, Cin % 16 == 0, Cout % 4 == 0; weights packed by launch_pack_conv_f32x3 (f32x3_pack_elems(Cout, Cin)
 // bf16 elements), passed as GemmArgs::Wp3
+// (_ok: what the launcher accepts, Wp3 aside -- a test of the geometry, the row maps and whether there is a residual; no pointer is read through)
 bool gemm_f32x3_ok(const GemmArgs& a);
-bool gemm_f32x3_wanted(const GemmArgs& a);             // eligible, carries Wp3, and large enough for this tile (a function of the conv alone)
-bool f32x3_takes(int B, int H, int W, int Cin, int Cout, bool h2);   // the shape half of that rule (what the engine asks before it picks a weight layout)
+// the size from which either split-fp32 tile pays: 370 MFLOP per conv and batch 5.  The engine's plan applies it (Engine::f32_tile_takes); the
+// launchers run what they are handed
+bool f32_tile_big_enough(int B, int H, int W, int Cin, int Cout);
 long f32x3_pack_elems(int Cout, int Cin);
-hipError_t launch_gemm_f32x3(const GemmArgs& a, hipStream_t s);
 hipError_t launch_gemm_f32x3_group(const GemmArgs* list, int n, hipStream_t s);
-const char* gemm_f32x3_kernel_name(const GemmArgs& a);
+const char* gemm_f32x3_kernel_name();
 hipError_t launch_pack_conv_f32x3(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
                                   void* Wp_bf16, float* bias, int Cout, int Cin, hipStream_t s);
 // the same convs with HALF the MFMAs (igemm_f32h2_ws.hip, igemm_f32h2_ws_tile.h): every operand as two fp16 pieces under an exact power-of-two
 // block scale (per output channel for the weights, per block and 16-channel chunk for the pixels, found in the kernel), three piece products
 // per fp32 MAC, fp32 accumulation; operands to 2^-23, one product to 2^-21 -- below the fp32 accumulation error of the dot product it
-// belongs to.  Same eligibility and size rule (gemm_f32x3_wanted); the problems of a list with GemmArgs::x3_h2 set run on this tile
-// (launch_gemm_f32x3_group forwards them).  Weights packed by launch_pack_conv_f32h2 (f32h2_pack_elems(Cout, Cin) 16-bit elements)
+// belongs to.  The plan's default tile (Engine::plan.x3_h2); tensors of any size (it addresses from per-tile bases).  Weights packed by
+// launch_pack_conv_f32h2 (f32h2_pack_elems(Cout, Cin) 16-bit elements), passed as GemmArgs::Wp3 with GemmArgs::x3_h2 set
 long f32h2_pack_elems(int Cout, int Cin);
 hipError_t launch_gemm_f32h2_group(const GemmArgs* list, int n, hipStream_t s);
 bool gemm_f32h2_ok(const GemmArgs& a);
 static constexpr int F32H2_UNIT_TABLE_WORDS = 7 * 256;
 bool f32h2_unit_table(int H, int W, int Cin, unsigned* out);     // the tile's unit table of a map geometry (igemm_f32h2_ws_tile.h); false: none, the kernel computes
-bool f32h2_shape_ok(int B, int H, int W, int Cin, int Cout);     // (tensors of any size: the tile addresses from per-tile bases)
-const char* gemm_f32h2_kernel_name(const GemmArgs& a);
+const char* gemm_f32h2_kernel_name();
 hipError_t launch_pack_conv_f32h2(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
                                   void* Wp_f16, float* bias, int Cout, int Cin, hipStream_t s);
 // ... and everything else that is fp32 and MFMA-shaped -- 1x1 / stride-2 / lone convs, the lifter's linears -- on the same two-piece arithmetic

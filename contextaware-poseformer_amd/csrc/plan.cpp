@@ -124,25 +124,27 @@ Tensor Engine::conv_bn(const std::string& conv, const std::string& bn, const Ten
     const bool use_bf16 = b16() && x.C % 8 == 0;       // the Cin = 3 stem stays on the fp32 kernel
     pk.bf16 = use_bf16;
     pk.Kpad = use_bf16 ? round64(pk.K) : round32(pk.K);
-    // Winograd F(2,3) along W (igemm_wino.hip) for the 3x3 stride-1 fp32 convs: 1.5x fewer MFMAs; block tiles of 64 x 64,
-    // 64 x 32 (32-channel outputs) or 32 x 64 (few tiles) are chosen per problem at launch
-    const bool as_wino = plan.use_wino && !use_bf16 && ks == 3 && stride == 1 && x.C % 32 == 0 && x.W % 2 == 0 && Cout % 32 == 0;
-    pk.wino = as_wino;
+    // The 3x3 stride-1 fp32 convs that may leave the direct kernel (Op::fast3x3; Engine::gemm_family routes them per batch): to the plan's
+    // split-fp32 tile, or to Winograd along W (igemm_wino.hip: 1.5x fewer MFMAs with F(2,3)).  ONE eligibility rule for both routes, the
+    // Winograd kernels': Cin % 32 == 0, Cout % 32 == 0, even W -- the tile is offered to no other conv (HRNet-48's 48-channel branch stays on
+    // the direct kernel), and CAPF_PLAN_NO_WINOGRAD takes the tile away with the Winograd kernels
+    const bool fast3x3 = plan.use_wino && !use_bf16 && ks == 3 && stride == 1 && x.C % 32 == 0 && x.W % 2 == 0 && Cout % 32 == 0;
+    pk.fast3x3 = fast3x3;
     // F(4,3) (half the MFMAs of the direct conv) where the row length allows four-pixel tiles, F(2,3) (two thirds) otherwise.
     // HRNet only: F(4,3) pays inside the grouped multi-branch launches (+3.2 % end to end), not for CPN's lone convs (-0.8 %).
-    if (as_wino) { pk.direct_Kpad = pk.Kpad; pk.Kpad = ((x.W % 4 == 0 && plan.wino_f43 && (cfg.backbone == CAPF_HRNET || plan.wino_f43_cpn) && x.H * x.W >= plan.wino_f43_min_hw && x.H * x.W <= plan.wino_f43_max_hw) ? 18 : 12) * x.C; }
+    if (fast3x3) { pk.direct_Kpad = pk.Kpad; pk.Kpad = ((x.W % 4 == 0 && plan.wino_f43 && (cfg.backbone == CAPF_HRNET || plan.wino_f43_cpn) && x.H * x.W >= plan.wino_f43_min_hw && x.H * x.W <= plan.wino_f43_max_hw) ? 18 : 12) * x.C; }
     // bf16: the 3x3 stride-1 convs also keep their weights in the row-halo layout (igemm_bf16.hip: one staged activation tile
     // for the three kw taps); launches of >= 2048 tiles run that kernel, smaller ones the ring kernel on the standard layout
     if (use_bf16 && plan.use_rh && ks == 3 && stride == 1 && bf16_rh_width(x.C) && Cout % 4 == 0) { pk.rh = true; pk.rh_Kpad = 9 * x.C; }
     // ... and in the layout of the 2-D halo tile (igemm_bf16_ws.hip), which takes them from 512 tiles per launch
     if (use_bf16 && plan.use_ws && ks == 3 && stride == 1 && x.C % 16 == 0 && Cout % 8 == 0) pk.ws = true;
-    // fp32: the Winograd-eligible convs also keep their weights as three bf16 pieces for the split-fp32 tile (igemm_f32x3_ws.hip), which
-    // takes them from 370 MFLOP per conv and batch 5 up (f32x3_takes)
-    if (as_wino && plan.use_x3 && x.W <= 256) pk.x3 = true;
+    // fp32: the fast3x3 convs also keep their weights as the pieces the plan's split-fp32 tile takes (igemm_f32h2_ws.hip / igemm_f32x3_ws.hip),
+    // which runs them from 370 MFLOP per conv and batch 5 up (build() finds the batches: f32_tile_takes)
+    if (fast3x3 && plan.use_x3 && x.W <= 256) pk.x3 = true;
     // fp32: every conv with 16-byte-aligned channel counts also keeps its weights as two block-scaled fp16 pieces in the direct layout's
     // geometry (igemm_f32h2.hip): what runs on the plain fp32 MFMA kernel at batch < 5 runs there from batch 5 (1x1 / stride-2 fuse and
     // transition convs, lone convs; the HBM-bound pointwise kernels of layer1 keep theirs)
-    if (!use_bf16 && plan.use_h2g && x.C % 4 == 0 && Cout % 4 == 0) { pk.h2g = true; pk.h2g_Kpad = as_wino ? pk.direct_Kpad : pk.Kpad; }
+    if (!use_bf16 && plan.use_h2g && x.C % 4 == 0 && Cout % 4 == 0) { pk.h2g = true; pk.h2g_Kpad = fast3x3 ? pk.direct_Kpad : pk.Kpad; }
     packs.push_back(pk);
 
     Op op;
@@ -164,7 +166,7 @@ Tensor Engine::conv_bn(const std::string& conv, const std::string& bn, const Ten
         use(residual->buf);
     }
     op.bf16 = use_bf16 ? 1 : 0;
-    op.wino = as_wino ? 1 : 0;
+    op.fast3x3 = fast3x3 ? 1 : 0;
     op.out_bf16 = (b16() && !use_bf16) ? 1 : 0;
     y.buf = new_buffer(act_elems((size_t)y.H * y.W * Cout), conv);
     op.out = y.buf;
@@ -1187,19 +1189,19 @@ bool Engine::build() {
         if (b.in[0] != a.out || b.region != a.region || b.lane != a.lane || a.aux < 0 || b.aux >= 0) continue;
         a.pw_pair = b.pw_pair = 1;
     }
-    // at which batches a split-fp32 tile takes a Winograd-eligible conv (Engine::wino_now): f32x3_takes is monotone in the batch up to the
-    // tile's 2 GB tensor limit, so the range is [first batch it accepts, last batch it accepts]
+    // at which batches the plan's split-fp32 tile runs a fast3x3 conv (Engine::gemm_family).  f32_tile_takes -- the size rule and the tile
+    // launcher's own test -- is monotone in the batch up to the tile's 2 GB limit, so the range is [first batch it accepts, last batch it accepts]
     for (Op& op : ops) {
-        if (op.kind != OP_GEMM || !op.wino || !packs[op.pack].x3) continue;
+        if (op.kind != OP_GEMM || !op.fast3x3 || !packs[op.pack].x3) continue;
         // (upper end: the three-piece tile addresses whole tensors with 31-bit byte offsets; the two-piece tile only counts pixels)
         const double cap = plan.x3_h2 ? 2.0e9 / ((double)op.H * op.W) : 2.0e9 / ((double)op.H * op.W * (double)std::max(op.Cin, op.N) * 4.0);
         int hi = (int)std::min(1.0e6, cap);
-        while (hi >= 1 && hi > (int)cap - 4 && !f32x3_takes(hi, op.H, op.W, op.Cin, op.N, plan.x3_h2)) --hi;   // (the limit itself is exclusive)
-        if (hi < 1 || !f32x3_takes(hi, op.H, op.W, op.Cin, op.N, plan.x3_h2)) continue;
+        while (hi >= 1 && hi > (int)cap - 4 && !f32_tile_takes(op, hi)) --hi;   // (the limit itself is exclusive)
+        if (hi < 1 || !f32_tile_takes(op, hi)) continue;
         int lo = 1, top = hi;                       // smallest accepted batch by bisection
         while (lo < top) {
             const int mid = lo + (top - lo) / 2;
-            if (f32x3_takes(mid, op.H, op.W, op.Cin, op.N, plan.x3_h2)) top = mid; else lo = mid + 1;
+            if (f32_tile_takes(op, mid)) top = mid; else lo = mid + 1;
         }
         op.x3_lo = lo; op.x3_hi = hi;
         // the Winograd layout of this conv is dead weight when the tile covers every batch the Winograd kernels could be asked for
@@ -1210,7 +1212,7 @@ bool Engine::build() {
     if (plan.x3_h2 && plan.use_x3) {
         std::map<std::tuple<int, int, int>, long> seen;
         for (Op& op : ops) {
-            if (op.kind != OP_GEMM || !op.wino || !packs[op.pack].x3 || op.x3_hi < op.x3_lo) continue;
+            if (op.kind != OP_GEMM || !op.fast3x3 || !packs[op.pack].x3 || op.x3_hi < op.x3_lo) continue;
             const auto key = std::make_tuple(op.H, op.W, op.Cin);
             auto it = seen.find(key);
             if (it == seen.end()) {
@@ -1231,7 +1233,7 @@ bool Engine::build() {
         if (pk.in_place) continue;
         pk.w_off = off;
         off += pk.wino_skip ? 64 : round64(pk.bf16 ? ((size_t)pk.N * pk.Kpad + 1) / 2 : (size_t)pk.N * pk.Kpad);
-        if (pk.wino) {
+        if (pk.fast3x3) {
             pk.direct_off = off;
             off += round64((size_t)pk.N * pk.direct_Kpad);
         }

@@ -4,7 +4,11 @@ the caller's stream computes, bit for bit.
 HRNet-32 at 64 x 64 is the smallest input at which all four branches and the three-hop fuse chains exist.  Batch 2 runs a
 region as one chain in either mode, batch 16 is where mode 3 switches to two chains.  Same kernels on the same operands in
 every schedule compared here, so every comparison is torch.equal: a launch that starts before its producer has finished, or a
-join that is missing, shows up as a difference (from the other schedule, or from call to call)."""
+join that is missing, shows up as a difference (from the other schedule, or from call to call).
+
+Batch 24 at 64 x 64 and at 96 x 96 are the engine-level runs of levels that mix kernel families: an F(4,3) Winograd group with a
+lone F(2,3) conv (W = 2), and at 96 x 96 with the two-fp16-piece GEMM too (W = 3 is odd).  Batch 80 at 64 x 64 runs the
+split-fp32 tile on the 16 x 16 .. 2 x 2 maps, which it takes from batch 79."""
 import contextlib
 import copy
 import io
@@ -35,8 +39,8 @@ def models():
     return {"default": _model(), "one_chain": _model()}
 
 
-def _inputs(B):
-    img, k2d, kc = synth.synth_inputs(B, H, W, seed=5, crop_range=(W, H))
+def _inputs(B, size=H):
+    img, k2d, kc = synth.synth_inputs(B, size, size, seed=5, crop_range=(size, size))
     return img.cuda(), k2d.cuda(), kc.cuda()
 
 
@@ -67,9 +71,10 @@ def _fuse_sums(model, inputs):
     return got
 
 
-@pytest.mark.parametrize("B", [2, 16])
-def test_the_default_schedule_equals_one_chain(models, B):
-    inputs = _inputs(B)
+@pytest.mark.parametrize("B, size", [pytest.param(2, 64, id="2"), pytest.param(16, 64, id="16"), pytest.param(24, 64, id="24"),
+                                     pytest.param(24, 96, id="96x96-24"), pytest.param(80, 64, id="80")])
+def test_the_default_schedule_equals_one_chain(models, B, size):
+    inputs = _inputs(B, size)
     eng = models["default"].engine_for(inputs[0])               # (no set_lanes call on this engine: the handle's default)
     assert (1 in eng.op_stream_classes(B)) == (B >= 16)
     one = models["one_chain"].engine_for(inputs[0])

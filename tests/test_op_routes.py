@@ -1,7 +1,9 @@
 """CPU: the engine's launch routes -- the kernel capf_op_info names for every op, its algorithmic FLOPs, capf_op_bytes and
 capf_op_executed_flops -- equal tests/golden/op_routes.npz exactly, for every plan and batch of tools/dump_op_routes.py's matrix
-(HRNet-32 / HRNet-48 / CPN, fp32 and bf16, the plan flags that move routes, batches 1 .. 512).  The fixture comes from this
-engine at the commit it names (`base_commit`), not from the reference.
+(HRNet-32 / HRNet-48 / CPN, fp32 and bf16, the plan flags that move routes, batches 1 .. 512), and tests/golden/op_routes_small.npz
+for its small-map matrix (HRNet-32 fp32 at 64 x 64 and 96 x 96: levels that mix the F(4,3) and F(2,3) Winograd kernels and the
+two-piece GEMM, and the batches at which the split-fp32 tile takes over).  The fixtures come from this engine at the commit
+they name (`base_commit`), not from the reference.
 
 A change that moves a route on purpose regenerates the fixture and says in its description which rows moved:
 
@@ -24,8 +26,17 @@ def _tool():
 
 def test_op_routes_match_fixture():
     tool = _tool()
-    want = load_golden("op_routes")
-    got = tool.to_arrays(tool.collect())
+    _compare(load_golden("op_routes"), tool.to_arrays(tool.collect()))
+
+
+def test_small_map_op_routes_match_fixture():
+    tool = _tool()
+    want = load_golden("op_routes_small")
+    assert 79 in want["batches"] and 80 in want["batches"]      # 64 x 64: the tile's first batch
+    _compare(want, tool.to_arrays(tool.collect(tool.small_cases(), tool.SMALL_BATCHES), tool.SMALL_BATCHES))
+
+
+def _compare(want, got):
     assert list(want["batches"]) == list(got["batches"])
     ws, gs = want["strings"], got["strings"]
     keys = sorted(k for k in got if "." in k)
