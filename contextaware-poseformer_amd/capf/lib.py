@@ -548,7 +548,8 @@ class Engine:
         return [self._check(self.lib.capf_op_stream_class(self.h, i, batch), "op_stream_class") for i in range(self.lib.capf_num_ops(self.h))]
 
     def profile_variants(self):
-        """After forward_profile_launches: the device kernel of every grouped bf16 launch, by leader op (-1 elsewhere)."""
+        """After forward_profile_launches: the device kernel of every grouped bf16 launch and of every 2-D halo tile launch (3), by leader op
+        (-1 elsewhere)."""
         n = self.lib.capf_num_ops(self.h)
         v = (c_int32 * n)()
         self._check(self.lib.capf_forward_profile_variants(self.h, v, n), "forward_profile_variants")

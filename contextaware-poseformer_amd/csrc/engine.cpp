@@ -229,20 +229,22 @@ Engine::FusedLaunch Engine::fused_leader(int i, int batch, bool bneck_only) cons
 }
 
 Engine::Family Engine::gemm_family(const Op& op, int batch) const {
-    if (op.bf16) return op.bf16 == 2 ? Family::BF16_ROWS : Family::BF16;
-    if (batch >= op.x3_lo && batch <= op.x3_hi) return Family::F32_TILE;            // (a fast3x3 conv: build() sets the range for no other)
+    const bool tile = batch >= op.tile_lo && batch <= op.tile_hi;                   // (build() sets the range for 3x3 stride-1 convs with a tile pack alone)
+    if (op.bf16) return op.bf16 == 2 ? Family::BF16_ROWS : tile ? Family::BF16_TILE : Family::BF16;
+    if (tile) return Family::F32_TILE;
     return op.fast3x3 && batch >= plan.wino_min_batch && !packs[op.pack].wino_skip ? Family::WINO : Family::F32;
 }
 
-// Does the plan's split-fp32 tile take this conv at this batch?  From 370 MFLOP and batch 5 up (f32_tile_big_enough), where the tile's launcher
-// accepts the problem as gemm_args describes it -- pointers aside: the test looks at none but whether there is a residual, which a
-// placeholder stands for that nothing reads through.  build() asks this once per op and batch range; nothing on the launch path asks again
-bool Engine::f32_tile_takes(const Op& op, int batch) const {
-    if (!f32_tile_big_enough(batch, op.H, op.W, op.Cin, op.N)) return false;
+// Does the plan's halo tile take this conv at this batch?  Where it is big enough for the tile to pay -- a 16-bit conv from 1 GFLOP and batch
+// 24 (bf16_tile_big_enough), an fp32 one from 370 MFLOP and batch 5 (f32_tile_big_enough) -- and the tile's launcher accepts the problem as
+// gemm_args describes it -- pointers aside: the test looks at none but whether there is a residual, which a placeholder stands for that
+// nothing reads through.  build() asks this once per op and batch range; nothing on the launch path asks again
+bool Engine::tile_takes(const Op& op, int batch) const {
+    if (!(op.bf16 ? bf16_tile_big_enough : f32_tile_big_enough)(batch, op.H, op.W, op.Cin, op.N)) return false;
     static const float residual = 0.f;
     GemmArgs a = gemm_args(op, batch, false);
     if (op.aux >= 0 || op.res_param >= 0) a.res = &residual;
-    return plan.x3_h2 ? gemm_f32h2_ok(a) : gemm_f32x3_ok(a);
+    return op.bf16 ? gemm_bf16_ws_ok(a) : plan.x3_h2 ? gemm_f32h2_ok(a) : gemm_f32x3_ok(a);
 }
 
 // FLOPs the MFMA pipe is asked to execute (2 x MACs issued, K padding included, tile-edge padding not): the Winograd kernels issue 18
@@ -260,6 +262,9 @@ Engine::OpRoute Engine::op_route(const Op& op, int batch) const {
     const GemmArgs a = gemm_args(op, batch);
     if (f == Family::BF16)                                     // (the row-halo layout has no K padding: decided per launch, a lower bound)
         return {f, gemm_bf16_kernel_name(a), MN * (pk.rh || pk.in_place ? op.K : pk.Kpad)};
+    // (the tile issues op.K: its pack has no K padding.  The count stays the one these ops had as BF16 ops -- the standard layout's padded K
+    // under CAPF_PLAN_NO_ROW_HALO, where K = 9 * Cin is no multiple of 64 -- so that tests/golden/op_routes.npz stands as recorded)
+    if (f == Family::BF16_TILE) return {f, gemm_bf16_ws_kernel_name(a), MN * (pk.rh || pk.in_place ? op.K : pk.Kpad)};
     if (f == Family::F32_TILE) return {f, plan.x3_h2 ? gemm_f32h2_kernel_name() : gemm_f32x3_kernel_name(), (plan.x3_h2 ? 3.0 : 6.0) * MN * op.K};
     if (f == Family::WINO) return {f, gemm_wino_kernel_name(a), MN * op.Cin * (pk.Kpad == 18 * pk.Cin ? 4.5 : 6.0)};
     return {f, gemm_f32_kernel_name(a), gemm_f32_route(a).path == F32Path::H2G ? 3.0 * MN * pk.h2g_Kpad       // (small batch: a fast3x3 conv on
@@ -295,6 +300,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
                     HIP_TRY(launch_gemm_bf16_rows(a.A, a.Wp, a.bias, a.M, a.N, a.K, a.Kpad, a.out, a.omap, a.res, a.rmap, op.out_bf16, s, f16()));
                     break;
                 case Family::BF16: HIP_TRY(launch_gemm_bf16(a, s)); break;
+                case Family::BF16_TILE: HIP_TRY(launch_gemm_bf16_ws_group(&a, 1, s)); break;
                 case Family::F32_TILE: HIP_TRY(launch_f32_tile(&a, 1, s)); break;
                 case Family::WINO: HIP_TRY(launch_gemm_wino(a, s)); break;
                 default: HIP_TRY(launch_gemm_f32(a, s));
@@ -413,8 +419,9 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
     return CAPF_OK;
 }
 
-// Fork/join region as dependency levels on ONE stream: the fp32 convs of a level (one per HRNet branch, or
-// the many small convs of a fuse layer) go out as grouped launches, everything else one by one.  Any
+// Fork/join region as dependency levels on ONE stream: the convs of a level (one per HRNet branch, or
+// the many small convs of a fuse layer) go out as grouped launches, one per kernel family (gemm_family; a
+// level's 2-D halo tile convs ahead of its other 16-bit convs), everything else one by one.  Any
 // topological order is valid on a single stream, and no two buffers of a region share memory
 // (assign_offsets keeps them alive for the whole region).  With `log` every launch is bracketed by
 // events (profiling): log gets (event index, leader op) pairs and member ops point at their leader.
@@ -424,14 +431,14 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
         if (op.kind != OP_GEMM) return false;
         switch (gemm_family(op, batch)) {
             case Family::BF16: return gemm_bf16_groupable(a);
-            case Family::F32_TILE: return true;
+            case Family::BF16_TILE: case Family::F32_TILE: return true;
             case Family::WINO: return gemm_wino_ok(a);
             case Family::F32: return gemm_f32_groupable(a);
             default: return false;
         }
     };
     for (const std::vector<int>& level : region_levels[region]) {
-        for (Family pass : {Family::F32, Family::BF16, Family::F32_TILE, Family::WINO}) {
+        for (Family pass : {Family::F32, Family::BF16_TILE, Family::BF16, Family::F32_TILE, Family::WINO}) {
             GemmArgs group[MAXG];
             int members[MAXG];
             int n = 0;
@@ -439,6 +446,10 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
                 if (n == 0) return CAPF_OK;
                 if (log) HIP_TRY(log->mark(s, members, n));
                 if (pass == Family::F32) HIP_TRY(launch_gemm_f32_group(group, n, s));
+                else if (pass == Family::BF16_TILE) {
+                    HIP_TRY(launch_gemm_bf16_ws_group(group, n, s));
+                    if (log && !log->op_variant.empty()) log->op_variant[members[0]] = 3;
+                }
                 else if (pass == Family::BF16) {
                     int v = -1;
                     HIP_TRY(launch_gemm_bf16_group(group, n, s, &v));
@@ -566,7 +577,11 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
                 break;
             default: {
                 if (skipped(op)) break;
-                if (log) HIP_TRY(log->mark(s, &oi, 1));
+                if (log) {
+                    HIP_TRY(log->mark(s, &oi, 1));
+                    // (a lone 2-D halo tile conv is a one-problem launch of the tile's grouped kernel: the log says so, as for a region's)
+                    if (!log->op_variant.empty() && op.kind == OP_GEMM && gemm_family(op, batch) == Family::BF16_TILE) log->op_variant[oi] = 3;
+                }
                 int rc = exec_op(op, s, batch);
                 if (rc) return rc;
             }

@@ -68,7 +68,8 @@ struct Pack {
     // ---- the further copies: flag, offset, padded K
     size_t direct_off = 0; int direct_Kpad = 0;                  // fast3x3: the direct kernel's layout [N][direct_Kpad] as well (small batches run the direct kernel)
     bool rh = false; size_t rh_off = 0; int rh_Kpad = 0;         // bf16 3x3 stride-1 conv: the row-halo layout, [N][rh_Kpad = 9 * Cin] bf16 (igemm_bf16.hip)
-    bool ws = false; size_t ws_off = 0;                          // bf16 3x3 stride-1 conv: the 2-D halo tile's layout (igemm_bf16_ws.hip)
+    bool ws = false; size_t ws_off = 0;                          // bf16 3x3 stride-1 conv: the 2-D halo tile's layout (igemm_bf16_ws.hip), run at the
+                                                                 // batches [Op::tile_lo, Op::tile_hi]
     bool x3 = false; size_t x3_off = 0;                          // fast3x3: what the plan's split-fp32 tile takes -- two block-scaled fp16 pieces
                                                                  // (igemm_f32h2_ws.hip; Engine::plan.x3_h2) or three bf16 pieces (igemm_f32x3_ws.hip)
     bool h2g = false; size_t h2g_off = 0; int h2g_Kpad = 0;      // fp32 conv / linear: two block-scaled fp16 pieces for igemm_f32h2.hip, [N][h2g_Kpad] floats +
@@ -153,10 +154,11 @@ struct Op {
     double flops_per_frame = 0.0;
     int bf16 = 0;                 // tensors of this op are bf16 (conv: bf16 MFMA kernel)
     int fast3x3 = 0;              // 3x3 stride-1 fp32 conv with routes besides the direct kernel (Pack::fast3x3): the split-fp32 tile at the batches
-                                  // [x3_lo, x3_hi], a Winograd kernel from plan.wino_min_batch (Engine::gemm_family)
+                                  // [tile_lo, tile_hi], a Winograd kernel from plan.wino_min_batch (Engine::gemm_family)
     int pw_pair = 0;              // one of a 64 -> 256 / 256 -> 64 pointwise pair that igemm_f32_pwchain.hip can run as one launch: stays on the fp32
                                   // kernels in every plan (the chained and the two-launch routes are bit-identical; test_pointwise_chain_*)
-    int x3_lo = 0, x3_hi = -1;    // batches [x3_lo, x3_hi] at which the plan's split-fp32 tile runs this conv (Engine::f32_tile_takes; set by build(), empty = never)
+    int tile_lo = 0, tile_hi = -1;   // batches [tile_lo, tile_hi] at which this 3x3 stride-1 conv runs its plan's halo tile -- the 2-D halo tile of a 16-bit
+                                  // conv (Pack::ws), the split-fp32 tile of a fast3x3 one (Pack::x3) -- (Engine::tile_takes; set by build(), empty = never)
     int out_bf16 = 0;             // fp32 stem conv writing bf16 activations
     int h2_exps = -1, h2_role = 0, h2_peer = -1;   // a BasicBlock's conv1 (role 1: writes planes + exponents to buffer h2_exps) / conv2 (role 2: reads them);
                                   // h2_peer = the other op's index: both must run the two-fp16-piece tile at a batch for the pair to use planes
@@ -203,7 +205,8 @@ struct LaunchLog {
     std::vector<hipEvent_t> ev;
     std::vector<int> leader;
     std::vector<int> op_leader;
-    std::vector<int> op_variant;       // per leader op: which device kernel a grouped bf16 launch chose (kernels.h), -1 otherwise
+    std::vector<int> op_variant;       // per leader op: which device kernel a grouped 16-bit launch ran -- 0 / 1 / 2 as launch_gemm_bf16_group chose
+                                       // (kernels.h), 3 the 2-D halo tile (a BF16_TILE launch) --, -1 otherwise
     hipError_t mark(hipStream_t s, const int* members, int n) {
         hipEvent_t e;
         hipError_t r = hipEventCreate(&e);
@@ -345,10 +348,12 @@ struct Engine {
     // what the op reports: the kernel that runs it on its own (capf_op_info) and the FLOPs that kernel issues (capf_op_executed_flops).
     // A fast3x3 conv is F32_TILE (the plan's split-fp32 tile: igemm_f32h2_ws.hip, or igemm_f32x3_ws.hip under CAPF_PLAN_F32X3_EXACT) at the
     // batches build() found the tile to take it, WINO (igemm_wino.hip) at the other batches from plan.wino_min_batch where its Winograd
-    // layout is packed, F32 (the direct kernel on the direct layout) below.  gemm_family is THE decision: the launchers only check it
-    enum class Family { NONE = -1, F32, BF16, F32_TILE, WINO, BF16_ROWS };
+    // layout is packed, F32 (the direct kernel on the direct layout) below.  A 16-bit conv is BF16_TILE (the 2-D halo tile, igemm_bf16_ws.hip)
+    // at the batches build() found that tile to take it, BF16 (igemm_bf16.hip) at every other: which of that file's kernels is the launcher's
+    // choice, by the tile count of the whole launch.  gemm_family is THE decision: the launchers only check it
+    enum class Family { NONE = -1, F32, BF16, BF16_TILE, F32_TILE, WINO, BF16_ROWS };
     struct OpRoute { Family family; const char* kernel; double flops; };
-    bool f32_tile_takes(const Op& op, int batch) const;      // build()'s question behind [x3_lo, x3_hi]: the size rule and the tile launcher's own test
+    bool tile_takes(const Op& op, int batch) const;          // build()'s question behind [tile_lo, tile_hi]: the size rule and the tile launcher's own test
     Family gemm_family(const Op& op, int batch) const;
     hipError_t launch_f32_tile(const GemmArgs* list, int n, hipStream_t s) const {      // the F32_TILE problems of one launch, on the plan's tile
         return (plan.x3_h2 ? launch_gemm_f32h2_group : launch_gemm_f32x3_group)(list, n, s);

@@ -1601,7 +1601,6 @@ bool gemm_bf16_upadd_ok(const GemmArgs& a) {
 }
 
 Bf16Route gemm_bf16_route(const GemmArgs& a) {
-    if (gemm_bf16_ws_wanted(a)) return {Bf16Path::WS, false};
     const bool pp = (long)((a.M + 127) / 128) * ((a.N + 63) / 64) >= pp_min_tiles();
     if (pp && a.Wp2 && gemm_bf16_rh_cw(a) && !a.f32s) return {Bf16Path::RH, true};     // (the row-halo tile has no fp32-stream epilogue)
     if (a.N <= 32) return {Bf16Path::T128x32, pp};
@@ -1611,7 +1610,6 @@ Bf16Route gemm_bf16_route(const GemmArgs& a) {
 
 const char* gemm_bf16_kernel_name(const GemmArgs& a) {
     switch (gemm_bf16_route(a).path) {
-        case Bf16Path::WS: return gemm_bf16_ws_kernel_name(a);
         case Bf16Path::RH: return fmt_kernel_name("igemm_bf16_rh<w4,126x64,conv>", a.f16);
         case Bf16Path::T128x32: return fmt_kernel_name("igemm_bf16<w4,128x32,conv>", a.f16);
         case Bf16Path::T128x64: return fmt_kernel_name("igemm_bf16<w4,128x64,conv>", a.f16);
@@ -1641,22 +1639,6 @@ hipError_t launch_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t s, in
     if (variant) *variant = -1;
     if (n <= 0) return hipSuccess;
     if (n > MAXG) return hipErrorInvalidValue;
-    {   // the 3x3 stride-1 problems the 2-D halo tile wants (a per-problem rule, igemm_bf16_ws.hip) share one grid of that kernel;
-        // whatever else the level holds follows as a second launch on the kernels below
-        GemmArgs wsl[MAXG], rest[MAXG];
-        int nws = 0, nrest = 0;
-        for (int i = 0; i < n; ++i) {
-            if (gemm_bf16_route(list[i]).path == Bf16Path::WS) wsl[nws++] = list[i];
-            else rest[nrest++] = list[i];
-        }
-        if (nws) {
-            const hipError_t e = launch_gemm_bf16_ws_group(wsl, nws, s);
-            if (e != hipSuccess) return e;
-            if (variant) *variant = 3;
-            int v2 = -1;
-            return nrest ? launch_gemm_bf16_group(rest, nrest, s, &v2) : hipSuccess;
-        }
-    }
     if (n == 1) return launch_gemm_bf16(list[0], s);
     const bool stream = list[0].f32s != 0;                       // (fp32-stream epilogue: every problem of the launch or none)
     const int f16 = list[0].f16;                                 // (one element format per launch)
@@ -1734,7 +1716,6 @@ hipError_t launch_gemm_bf16(const GemmArgs& a_in, hipStream_t s) {
     if (a.up && (a.f32s || !gemm_bf16_upadd_ok(a))) return hipErrorInvalidValue;
     const Bf16Route r = gemm_bf16_route(a);
     switch (r.path) {
-        case Bf16Path::WS: return launch_gemm_bf16_ws(a, s);
         case Bf16Path::RH:
             a.Wp = a.Wp2;
             a.Kpad = 9 * a.Cin;

@@ -45,24 +45,20 @@ bool gemm_bf16_ws_ok(const GemmArgs& a) {
     return ws_from_args(a, &p);
 }
 
-int gemm_bf16_ws_tiles(const GemmArgs& a) {
-    WsProblem p;
-    return ws_from_args(a, &p) ? p.tiles_m * p.NSL : 0;
-}
-
 // Which kernel a conv runs on is a function of the conv ALONE (its shape and batch), never of what else shares its launch: the
 // engine's schedules (one chain, two chains, program order) group a level's convs differently and promise identical bits
 // (capf.h, tests/test_gpu_ops.py::test_two_chain_schedule_is_bit_identical_to_one_chain).  The HRNet branches of a level have equal
 // FLOPs and very different tile counts (1024 ... 64 at batch 64), so the rule is on the problem's work: the tile takes a conv from
 // 1 GFLOP up -- below that (HRNet-32 under batch ~14, HRNet-48 under ~6) a level is a handful of 256-pixel tiles and the ring
-// kernel's 64 x 64 tiles fill the chip better.  (diag builds: CAPF_BF16_WS_MIN_MFLOP)
+// kernel's 64 x 64 tiles fill the chip better.  (diag builds: CAPF_BF16_WS_MIN_MFLOP, CAPF_BF16_WS_MIN_BATCH)
 // Round 6 (tools/sweep_thresholds.py, tools/ws_sweep.py -> profiles/r06_threshold_sweep.txt): the FLOP rule alone let the tile in far too
 // early -- HRNet-48 at batch 8 / 16 ran 21 % / 10 % SLOWER with it than on the row-halo / ring kernels, CPN at batch 4 - 16 5 %; the three
 // backbones cross over between batch 16 and 32, where a launch's 256-pixel tiles start to fill the chip's 512 slots.  So: 1 GFLOP AND batch 24.
-bool gemm_bf16_ws_wanted(const GemmArgs& a) {
+// The engine's plan applies the rule, once per conv (Engine::tile_takes); the launcher runs what it is handed
+bool bf16_tile_big_enough(int B, int H, int W, int Cin, int Cout) {
     static const double min_flop = [] { const char* e = diag_env("CAPF_BF16_WS_MIN_MFLOP"); return (e ? atof(e) : 1000.0) * 1e6; }();
     static const long min_batch = [] { const char* e = diag_env("CAPF_BF16_WS_MIN_BATCH"); return e ? atol(e) : 24L; }();
-    return a.Wp3 && a.Ho > 0 && a.Wo > 0 && (long)a.M >= min_batch * a.Ho * a.Wo && 2.0 * (double)a.M * a.N * 9.0 * a.Cin >= min_flop && gemm_bf16_ws_ok(a);
+    return B >= min_batch && 2.0 * (double)B * H * W * Cout * 9.0 * Cin >= min_flop;
 }
 
 // The grid: kernels.h "Grouped launch" (what was measured against it on this kernel stands there).
@@ -153,7 +149,6 @@ hipError_t launch_gemm_bf16_ws_group(const GemmArgs* list, int n, hipStream_t s)
 // for the narrow branch (Cin 48: whole filter staged once, the next tile's pixels in flight under the current tile, one barrier per
 // tile) -- bit-identical, 92 -> 83 us alone, but nothing end to end (cfg2 14.23k vs 14.19k frames/s): with one wave per SIMD its K
 // loop, its VALU-heavy epilogue and its waits are strictly serial.
-hipError_t launch_gemm_bf16_ws(const GemmArgs& a, hipStream_t s) { return launch_gemm_bf16_ws_group(&a, 1, s); }
 
 const char* gemm_bf16_ws_kernel_name(const GemmArgs& a) {
     const int ns = ws_ns(a.N);

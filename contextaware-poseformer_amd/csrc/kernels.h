@@ -90,8 +90,7 @@ struct GemmArgs {
     const float* Wp;    // packed weights [N][Kpad], K-contiguous, zero padded to Kpad (multiple of 32)
     const float* Wp2;   // bf16 3x3 stride-1 convs: the same weights in the row-halo layout ([N][9 * Cin], igemm_bf16.hip), or
                         // nullptr; launch_gemm_bf16 / _group switch to that kernel for launches of >= 2048 tiles
-    const float* Wp3;   // bf16 3x3 stride-1 convs: the same weights in the 2-D halo tile's layout (igemm_bf16_ws.hip), or nullptr;
-                        // launch_gemm_bf16 / _group run the problems gemm_bf16_ws_wanted() accepts on that kernel.
+    const float* Wp3;   // bf16 3x3 stride-1 convs: the same weights in the 2-D halo tile's layout (igemm_bf16_ws.hip), or nullptr.
                         // fp32 3x3 stride-1 convs: the weights as the split-fp32 tile's pieces, or nullptr -- three bf16 pieces
                         // (igemm_f32x3_ws.hip, launch_pack_conv_f32x3) or, with x3_h2 set, two block-scaled fp16 pieces (igemm_f32h2_ws.hip,
                         // launch_pack_conv_f32h2).  Read by the tile launchers alone; who calls them decides (Engine::gemm_family)
@@ -327,12 +326,12 @@ int f32h2_tiles_m(int B, int H, int W, int* tile_pixels = nullptr);            /
 bool gemm_bf16_groupable(const GemmArgs& a);
 bool gemm_bf16_upadd_ok(const GemmArgs& a);      // a.up (post-activation upsampled add) can run in igemm_bf16_kernel<.., UPADD>
 // bf16 twin of launch_gemm_f32_group; *variant (optional) = the device kernel it chose: 0 ring (igemm_bf16_group_kernel),
-// 1 ping-pong (igemm_bf16_group_pp_kernel), 2 ping-pong with row-halo tiles (igemm_bf16_group_rh_kernel), 3 the 2-D halo tile
-// (igemm_bf16_group_ws_kernel; problems of the list it cannot take go out as a second, ring / ping-pong launch), -1 single launch
+// 1 ping-pong (igemm_bf16_group_pp_kernel), 2 ping-pong with row-halo tiles (igemm_bf16_group_rh_kernel), -1 single launch.  (3 is the
+// 2-D halo tile's number in the engine's launch log: a launch of launch_gemm_bf16_ws_group, which who routes the convs calls itself)
 hipError_t launch_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t s, int* variant = nullptr);
-// the path launch_gemm_bf16 takes: the 2-D halo tile (gemm_bf16_ws_wanted), the row-halo tile, or one of the four tile shapes of
-// igemm_bf16_kernel; pp: a launch of >= 2048 tiles (ping-pong schedule, the row-halo tile's condition)
-enum class Bf16Path { WS, RH, T128x32, T128x64, T64x64, T128x128 };
+// the path launch_gemm_bf16 takes: the row-halo tile, or one of the four tile shapes of igemm_bf16_kernel; pp: a launch of >= 2048
+// tiles (ping-pong schedule, the row-halo tile's condition)
+enum class Bf16Path { RH, T128x32, T128x64, T64x64, T128x128 };
 struct Bf16Route { Bf16Path path; bool pp; };
 Bf16Route gemm_bf16_route(const GemmArgs& a);
 const char* gemm_bf16_kernel_name(const GemmArgs& a);
@@ -346,11 +345,12 @@ hipError_t launch_pack_conv_bf16_rh(const float* w, const float* gamma, const fl
 // "2-D halo" tile of the 3x3 / stride-1 bf16 conv (igemm_bf16_ws.hip, igemm_bf16_ws_tile.h): 256 pixels x 32 / 64 / 96 channels per
 // block with the accumulators resident for the whole K, 16-channel chunks staged once for all nine taps; weights packed by
 // launch_pack_conv_bf16_ws (bf16_ws_pack_elems(Cout, Cin) bf16 elements), passed as GemmArgs::Wp3
+// (_ok: what the launcher accepts, Wp3 aside; it refuses every other problem -- an error, never another kernel)
 bool gemm_bf16_ws_ok(const GemmArgs& a);
-int gemm_bf16_ws_tiles(const GemmArgs& a);              // blocks the problem needs (0 = not eligible)
-bool gemm_bf16_ws_wanted(const GemmArgs& a);            // eligible, carries Wp3, and large enough for this tile (a function of the conv alone)
+// the size from which the tile pays: 1 GFLOP per conv and batch 24.  The engine's plan applies it (Engine::tile_takes); the launcher runs
+// what it is handed
+bool bf16_tile_big_enough(int B, int H, int W, int Cin, int Cout);
 long bf16_ws_pack_elems(int Cout, int Cin);
-hipError_t launch_gemm_bf16_ws(const GemmArgs& a, hipStream_t s);
 hipError_t launch_gemm_bf16_ws_group(const GemmArgs* list, int n, hipStream_t s);
 const char* gemm_bf16_ws_kernel_name(const GemmArgs& a);
 hipError_t launch_pack_conv_bf16_ws(const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
@@ -362,7 +362,7 @@ hipError_t launch_pack_conv_bf16_ws(const float* w, const float* gamma, const fl
 // bf16 elements), passed as GemmArgs::Wp3
 // (_ok: what the launcher accepts, Wp3 aside -- a test of the geometry, the row maps and whether there is a residual; no pointer is read through)
 bool gemm_f32x3_ok(const GemmArgs& a);
-// the size from which either split-fp32 tile pays: 370 MFLOP per conv and batch 5.  The engine's plan applies it (Engine::f32_tile_takes); the
+// the size from which either split-fp32 tile pays: 370 MFLOP per conv and batch 5.  The engine's plan applies it (Engine::tile_takes); the
 // launchers run what they are handed
 bool f32_tile_big_enough(int B, int H, int W, int Cin, int Cout);
 long f32x3_pack_elems(int Cout, int Cin);

@@ -136,10 +136,11 @@ Tensor Engine::conv_bn(const std::string& conv, const std::string& bn, const Ten
     // bf16: the 3x3 stride-1 convs also keep their weights in the row-halo layout (igemm_bf16.hip: one staged activation tile
     // for the three kw taps); launches of >= 2048 tiles run that kernel, smaller ones the ring kernel on the standard layout
     if (use_bf16 && plan.use_rh && ks == 3 && stride == 1 && bf16_rh_width(x.C) && Cout % 4 == 0) { pk.rh = true; pk.rh_Kpad = 9 * x.C; }
-    // ... and in the layout of the 2-D halo tile (igemm_bf16_ws.hip), which takes them from 512 tiles per launch
+    // ... and in the layout of the 2-D halo tile (igemm_bf16_ws.hip), which runs them from 1 GFLOP per conv and batch 24 up (build() finds
+    // the batches: tile_takes)
     if (use_bf16 && plan.use_ws && ks == 3 && stride == 1 && x.C % 16 == 0 && Cout % 8 == 0) pk.ws = true;
     // fp32: the fast3x3 convs also keep their weights as the pieces the plan's split-fp32 tile takes (igemm_f32h2_ws.hip / igemm_f32x3_ws.hip),
-    // which runs them from 370 MFLOP per conv and batch 5 up (build() finds the batches: f32_tile_takes)
+    // which runs them from 370 MFLOP per conv and batch 5 up (build() finds the batches: tile_takes)
     if (fast3x3 && plan.use_x3 && x.W <= 256) pk.x3 = true;
     // fp32: every conv with 16-byte-aligned channel counts also keeps its weights as two block-scaled fp16 pieces in the direct layout's
     // geometry (igemm_f32h2.hip): what runs on the plain fp32 MFMA kernel at batch < 5 runs there from batch 5 (1x1 / stride-2 fuse and
@@ -1104,6 +1105,24 @@ bool Engine::set_plan_switches() {
     return true;
 }
 
+// The batches [*lo, *hi] at which a halo tile takes a conv (false: none), from `takes` -- the tile's size rule and its launcher's own test
+// (Engine::tile_takes) -- and `cap`, the batch at which the largest tensor the tile addresses with 31-bit byte offsets reaches 2 GB (exclusive).
+// The accepted set is an interval: the size rules only fail downwards; the tiles' geometry (ws_plan) does not depend on the batch, and their
+// 2 GB tests and ws_args_ok's only fail upwards.  So: the last accepted batch, just under the cap, then the first by bisection
+template <class Takes>
+static bool tile_batches(double cap, const Takes& takes, int* lo, int* hi) {
+    int last = (int)std::min(1.0e6, cap);
+    while (last >= 1 && last > (int)cap - 4 && !takes(last)) --last;   // (the limit itself is exclusive)
+    if (last < 1 || !takes(last)) return false;
+    int first = 1, top = last;
+    while (first < top) {
+        const int mid = first + (top - first) / 2;
+        if (takes(mid)) top = mid; else first = mid + 1;
+    }
+    *lo = first; *hi = last;
+    return true;
+}
+
 bool Engine::build() {
     if (cfg.height % 32 != 0 || cfg.width % 32 != 0) {
         err = "height and width must be multiples of 32";
@@ -1189,30 +1208,26 @@ bool Engine::build() {
         if (b.in[0] != a.out || b.region != a.region || b.lane != a.lane || a.aux < 0 || b.aux >= 0) continue;
         a.pw_pair = b.pw_pair = 1;
     }
-    // at which batches the plan's split-fp32 tile runs a fast3x3 conv (Engine::gemm_family).  f32_tile_takes -- the size rule and the tile
-    // launcher's own test -- is monotone in the batch up to the tile's 2 GB limit, so the range is [first batch it accepts, last batch it accepts]
+    // at which batches a 3x3 stride-1 conv runs its plan's halo tile (Engine::gemm_family): the split-fp32 tile for a fast3x3 conv, the 2-D
+    // halo tile for a 16-bit one
     for (Op& op : ops) {
-        if (op.kind != OP_GEMM || !op.fast3x3 || !packs[op.pack].x3) continue;
-        // (upper end: the three-piece tile addresses whole tensors with 31-bit byte offsets; the two-piece tile only counts pixels)
-        const double cap = plan.x3_h2 ? 2.0e9 / ((double)op.H * op.W) : 2.0e9 / ((double)op.H * op.W * (double)std::max(op.Cin, op.N) * 4.0);
-        int hi = (int)std::min(1.0e6, cap);
-        while (hi >= 1 && hi > (int)cap - 4 && !f32_tile_takes(op, hi)) --hi;   // (the limit itself is exclusive)
-        if (hi < 1 || !f32_tile_takes(op, hi)) continue;
-        int lo = 1, top = hi;                       // smallest accepted batch by bisection
-        while (lo < top) {
-            const int mid = lo + (top - lo) / 2;
-            if (f32_tile_takes(op, mid)) top = mid; else lo = mid + 1;
-        }
-        op.x3_lo = lo; op.x3_hi = hi;
+        if (op.kind != OP_GEMM || !(op.bf16 == 1 ? packs[op.pack].ws : op.fast3x3 && packs[op.pack].x3)) continue;
+        // bytes per pixel of the largest tensor the tile addresses with 31-bit offsets: the 2-D halo tile whole tensors of 16-bit rows (the
+        // fp32-stream epilogue's output and residual rows count 4 bytes an element), the three-piece tile whole fp32 tensors; the two-piece
+        // tile only counts pixels
+        const double eb = op.f32s ? 4.0 : 2.0;
+        const double row = op.bf16 ? std::max({2.0 * op.Cin, 2.0 * op.N, eb * op.omap.S1, op.aux >= 0 || op.res_param >= 0 ? eb * op.rmap.S1 : 0.0})
+                           : plan.x3_h2 ? 1.0 : 4.0 * std::max(op.Cin, op.N);
+        if (!tile_batches(2.0e9 / ((double)op.H * op.W * row), [&](int batch) { return tile_takes(op, batch); }, &op.tile_lo, &op.tile_hi)) continue;
         // the Winograd layout of this conv is dead weight when the tile covers every batch the Winograd kernels could be asked for
-        if (lo <= plan.wino_min_batch && hi >= cfg.max_batch) packs[op.pack].wino_skip = true;
+        if (op.fast3x3 && op.tile_lo <= plan.wino_min_batch && op.tile_hi >= cfg.max_batch) packs[op.pack].wino_skip = true;
     }
     // unit tables of the two-fp16-piece conv tile: one per map geometry among the convs it can take (igemm_f32h2_ws_tile.h, UNIT TABLE)
     utab_host.clear();
     if (plan.x3_h2 && plan.use_x3) {
         std::map<std::tuple<int, int, int>, long> seen;
         for (Op& op : ops) {
-            if (op.kind != OP_GEMM || !op.fast3x3 || !packs[op.pack].x3 || op.x3_hi < op.x3_lo) continue;
+            if (op.kind != OP_GEMM || !op.fast3x3 || !packs[op.pack].x3 || op.tile_hi < op.tile_lo) continue;
             const auto key = std::make_tuple(op.H, op.W, op.Cin);
             auto it = seen.find(key);
             if (it == seen.end()) {

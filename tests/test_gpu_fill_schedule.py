@@ -8,10 +8,18 @@ join that is missing, shows up as a difference (from the other schedule, or from
 
 Batch 24 at 64 x 64 and at 96 x 96 are the engine-level runs of levels that mix kernel families: an F(4,3) Winograd group with a
 lone F(2,3) conv (W = 2), and at 96 x 96 with the two-fp16-piece GEMM too (W = 3 is odd).  Batch 80 at 64 x 64 runs the
-split-fp32 tile on the 16 x 16 .. 2 x 2 maps, which it takes from batch 79."""
+split-fp32 tile on the 16 x 16 .. 2 x 2 maps, which it takes from batch 79.
+
+HRNet-32 bf16 at 128 x 128 is the 16-bit model beside them: the smallest runs in which the engine routes convs to the 2-D halo
+tile (Engine::gemm_family: BF16_TILE, from 1 GFLOP per conv and batch 24).  What capf_op_info names there (checked below):
+at batch 24 the tile runs layer1's four conv2 and transition1's 256 -> 32 conv -- the latter in ONE level with transition1's
+stride-2 conv, which it does not run -- while every branch conv is still on igemm_bf16.hip's kernels; at batch 56 (the branch
+convs reach 1 GFLOP at 53) the branch levels are tile launches on both concurrent chains.  (layer1's conv2 shares no level with
+another conv at either batch: its block's downsample conv sits one level earlier, beside conv1.)"""
 import contextlib
 import copy
 import io
+import re
 
 import pytest
 import torch
@@ -37,6 +45,19 @@ def _model(flags=0, dtype="fp32"):
 @pytest.fixture(scope="module")
 def models():
     return {"default": _model(), "one_chain": _model()}
+
+
+@pytest.fixture(scope="module")
+def models16():
+    return {"default": _model(dtype="bf16"), "one_chain": _model(dtype="bf16")}
+
+
+TILE_KERNEL = re.compile(r"^igemm_\w+_ws<")
+
+
+def _tile_ops(eng, B):
+    """names of the ops capf_op_info puts on the 2-D halo tile at batch B"""
+    return {name for name, kern, _ in eng.op_table(B) if TILE_KERNEL.match(kern)}
 
 
 def _inputs(B, size=H):
@@ -74,6 +95,48 @@ def _fuse_sums(model, inputs):
 @pytest.mark.parametrize("B, size", [pytest.param(2, 64, id="2"), pytest.param(16, 64, id="16"), pytest.param(24, 64, id="24"),
                                      pytest.param(24, 96, id="96x96-24"), pytest.param(80, 64, id="80")])
 def test_the_default_schedule_equals_one_chain(models, B, size):
+    _default_equals_one_chain(models, B, size)
+
+
+@pytest.mark.parametrize("B", [24, 56])
+def test_the_default_schedule_equals_one_chain_with_2d_halo_tile_launches(models16, B):
+    eng = models16["default"].engine_for(_inputs(B, 128)[0])
+    tile = _tile_ops(eng, B)
+    assert "backbone.transition1.0.0" in tile and "backbone.transition1.1.0.0" not in tile and "backbone.layer1.1.conv2" in tile
+    sched = {name: s[:2] for (name, _, _), s in zip(eng.op_table(B), eng.op_schedule())}
+    assert sched["backbone.transition1.0.0"] == sched["backbone.transition1.1.0.0"]          # one region, one level
+    branch = {name for name in sched if ".branches." in name and ".conv" in name}
+    assert len(branch) == 208 and (branch <= tile if B == 56 else not branch & tile)
+    _default_equals_one_chain(models16, B, 128)
+
+
+def test_a_launch_is_2d_halo_tile_convs_or_none_and_its_variant_says_which(models16):
+    """Batch 24 at 128 x 128, the launch log of the product schedule: the members of every bracket (the ops that share a leader) are
+    either all named igemm_*_ws<...> by capf_op_info or none is, and the bracket's variant is 3 exactly when they are.  (Until the
+    engine routed these convs itself, transition1's level was one bracket of variant 3 around a tile launch and a ring launch.)"""
+    B = 24
+    img, k2d, kc = _inputs(B, 128)
+    model = models16["default"]
+    with torch.no_grad():
+        out = model(img, k2d, kc.clone())
+    eng = model.engine_for(img)
+    _, leader = eng.forward_profile_launches(img, k2d, kc.clone(), torch.empty_like(out), torch.cuda.current_stream().cuda_stream)
+    variants = eng.profile_variants()
+    table = eng.op_table(B)
+    members = {}
+    for i, l in enumerate(leader):
+        if l >= 0:
+            members.setdefault(l, []).append(i)
+    n_tile = 0
+    for l, ops in members.items():
+        on_tile = [bool(TILE_KERNEL.match(table[i][1])) for i in ops]
+        assert all(on_tile) or not any(on_tile), [table[i][:2] for i in ops]
+        assert (variants[l] == 3) == all(on_tile), (table[l][:2], variants[l])
+        n_tile += all(on_tile)
+    assert n_tile == 5                                         # layer1's four conv2, transition1's 256 -> 32 conv
+
+
+def _default_equals_one_chain(models, B, size):
     inputs = _inputs(B, size)
     eng = models["default"].engine_for(inputs[0])               # (no set_lanes call on this engine: the handle's default)
     assert (1 in eng.op_stream_classes(B)) == (B >= 16)
