@@ -35,6 +35,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_debug_f16_round",
     "capf_op_stream_class",
     "capf_set_features", "capf_lifter_forward_train", "capf_backward_maps",
+    "capf_set_map_grad_mode", "capf_map_grad_mode",
 ]
 
 
@@ -157,6 +158,9 @@ def load_library():
     lib.capf_set_features.argtypes = [H, P, POINTER(P), c_int]
     lib.capf_lifter_forward_train.argtypes = [H, P, P, P, c_int, P, P]
     lib.capf_backward_maps.argtypes = [H, P, P, c_int, P, P, POINTER(P)]
+    lib.capf_set_map_grad_mode.argtypes = [H, c_int]
+    lib.capf_map_grad_mode.argtypes = [H]
+    lib.capf_map_grad_mode.restype = c_int
     lib.capf_train_generation.argtypes = [H]
     lib.capf_train_generation.restype = c_int64
     lib.capf_max_batch.argtypes = [H]
@@ -387,6 +391,13 @@ class Engine:
                                                 c_void_p(flat_grad.data_ptr()),
                                                 c_void_p(masks.data_ptr()) if masks is not None else c_void_p(0),
                                                 self._ptrs4(dfeat_nhwc)), "backward_maps")
+
+    def set_map_grad_mode(self, mode):
+        """How capf_backward_maps sums the map gradient: 0 fp32 atomic adds (default), 1 the ordered, bit-reproducible sum."""
+        self._check(self.lib.capf_set_map_grad_mode(self.h, int(mode)), "set_map_grad_mode")
+
+    def map_grad_mode(self):
+        return self.lib.capf_map_grad_mode(self.h)
 
     def backbone_forward(self, images, stream):
         B = images.shape[0]

@@ -915,6 +915,20 @@ int capf_backward_maps(capf_handle* h, void* stream, const float* grad_out, int 
     return e.backward(static_cast<hipStream_t>(stream), batch, grad_out, flat_grad, drop_masks, dfeat_nhwc);
 }
 
+int capf_set_map_grad_mode(capf_handle* h, int mode) {
+    if (!h) return CAPF_ERR_INVALID;
+    Engine& e = h->e;
+    if (mode != 0 && mode != 1) {
+        e.err = "capf_set_map_grad_mode: mode is 0 (atomic) or 1 (ordered)";
+        return CAPF_ERR_INVALID;
+    }
+    if (int rc = maps_f32_only(e, "capf_set_map_grad_mode")) return rc;
+    e.map_grad_mode = mode;
+    return CAPF_OK;
+}
+
+int capf_map_grad_mode(const capf_handle* h) { return h ? h->e.map_grad_mode : -1; }
+
 int64_t capf_train_generation(const capf_handle* h) { return h ? h->e.train_generation : -1; }
 
 int64_t capf_grad_elems(const capf_handle* h) { return h ? h->e.grad_elems : -1; }

@@ -324,6 +324,7 @@ struct Engine {
     bool debug = false;            // run the debug-copy ops (capf_set_debug)
     int lanes = 3;                 // fork/join regions: 0 in program order, 1 one side stream per lane, 2 grouped launches on one stream,
                                    // 3 grouped launches as two chains on two streams (capf_set_lanes)
+    int map_grad_mode = 0;         // dfeat of capf_backward_maps: 0 fp32 atomic adds, 1 the ordered sum (capf_set_map_grad_mode)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> events;
     std::vector<int> last_variants;   // capf_forward_profile_launches: grouped-bf16 kernel variant per leader op

@@ -27,7 +27,9 @@ inline const char* diag_env(const char* name) {
 // corner and the fractional weights of the +1 corners, exactly as ATen computes them (GridSampler.h:27-36, 58-60, 143-171:
 // ((g + 1) / 2) * (size - 1); padding 'border' clips the COORDINATE to [0, size - 1] before floor, 'zeros' keeps it).  The
 // result feeds an index gather that must be bit-exact, so every translation unit that instantiates this is built with
-// -ffp-contract=off (csrc/Makefile: lifter.hip, lifter_fused.hip) -- no FMA contraction, IEEE division.
+// -ffp-contract=off (csrc/Makefile: lifter.hip, lifter_fused.hip) -- no FMA contraction, IEEE division.  The function also switches
+// contraction off for itself: train_kernels.hip is built without that flag, and there x - floor(x) of a product became an fma in one
+// kernel and not in another (the two summation forms of the map gradient must get the same weights, the forward's).
 struct BilinearCorner {
     int x0, y0;
     float wx1, wy1;
@@ -35,6 +37,7 @@ struct BilinearCorner {
 #if defined(__HIPCC__)
 template <bool BORDER>
 __device__ __forceinline__ BilinearCorner bilinear_corner(float gx, float gy, int H, int W) {
+#pragma clang fp contract(off)
     float x = ((gx + 1.0f) / 2.0f) * (float)(W - 1);
     float y = ((gy + 1.0f) / 2.0f) * (float)(H - 1);
     if (BORDER) {   // clip_coordinates: min(size - 1, max(x, 0)) before floor
@@ -570,7 +573,9 @@ hipError_t launch_attention_bwd(const float* qkv, const float* dO, float* dqkv, 
 hipError_t launch_deform_bwd(const DeformArgs& a, float* dAO, int ldd, hipStream_t s);
 // ---- gradient w.r.t. the context maps (capf_backward_maps): the backward of both bilinear samplers w.r.t. the SAMPLED tensor.  g[l] holds
 // the gradient of every sampled vector; each is added to its (up to) four corners of dfeat[l] (fp32 NHWC [B, H, W, C], zeroed first by
-// launch_zero_maps) with fp32 atomic adds, lanes over contiguous channels.  The order of the adds is not fixed: dfeat is not bit-reproducible
+// launch_zero_maps), lanes over contiguous channels.  Two summation forms of the same sources into the same destinations:
+//   atomic  (launch_deform_scatter / launch_ref_scatter): fp32 atomic adds; the order of the adds is not fixed: dfeat is not bit-reproducible
+//   ordered (launch_deform_scatter_ordered / launch_ref_scatter_ordered): no atomics, a fixed expression -- see below
 struct MapGradArgs {
     float* dfeat[4];
     const float* g[4];       // deform: dU[l] [(b,p,h), C_l];  ref: dS_l [(b,p), C_l]
@@ -583,6 +588,22 @@ struct MapGradArgs {
 hipError_t launch_deform_scatter(const MapGradArgs& a, hipStream_t s);
 // pose_dformer.py:217 (padding zeros): dfeat[corner of ref[b,p]] += bilinear weight * dS[(b,p)], corners outside the map dropped
 hipError_t launch_ref_scatter(const MapGradArgs& a, hipStream_t s);
+// The ordered form.  An ITEM is one corner of one sample: it = ((p * NH + h) * NS + s) * 4 + dy * 2 + dx (deformable, source row dU[(b,p,h)],
+// weight softmax_s * wx * wy) or it = p * 4 + dy * 2 + dx (reference point, source row dS[(b,p)], weight wx * wy); cells, weights and the
+// inside test are the atomic form's, from one device function.  One launch adds, to every pixel that any of its items falls into,
+//     S[pixel][c] = sum over that pixel's items, IN ASCENDING it, in fp32 without contraction, of weight_it * row_it[c]
+// by a plain load and a plain store: dfeat[pixel][c] = dfeat[pixel][c] + S[pixel][c].  Inside a launch every pixel has exactly one owner
+// (a workgroup owns a frame, a level and 64 channels; it sorts the frame's (pixel, it) keys in LDS), so with the stream-ordered launches
+// of Engine::backward the whole gradient is ONE fixed expression,
+//     dfeat = ((((0 + S_ctx[Lv-1]) + S_ctx[Lv-2]) + ...) + S_ctx[0]) + S_ref,
+// bit-identical from run to run; pixels that no item falls into keep launch_zero_maps' 0.  No global scratch.
+// Limits: launch_deform_scatter's (NS == 4, NH * NS <= 16, L <= 4, C_l % 4 == 0), J * NH * NS * 4 <= MAPGRAD_ORDERED_MAX_ITEMS items per
+// (frame, level) in the deformable pass (J <= 32 at NH * NS = 16) and J <= MAPGRAD_ORDERED_MAX_JOINTS in the reference pass,
+// H_l * W_l <= 2^20, dfeat 16-byte aligned; anything else: hipErrorInvalidValue.
+constexpr int MAPGRAD_ORDERED_MAX_ITEMS = 2048;
+constexpr int MAPGRAD_ORDERED_MAX_JOINTS = 64;
+hipError_t launch_deform_scatter_ordered(const MapGradArgs& a, hipStream_t s);
+hipError_t launch_ref_scatter_ordered(const MapGradArgs& a, hipStream_t s);
 // p[l][0 .. n[l]) = 0 for `count` <= 4 maps in one launch (n[l] % 4 == 0, 16-byte aligned pointers; the launcher fills blk_end)
 struct ZeroMaps {
     float* p[4];

@@ -3,7 +3,8 @@
 // context maps are constants here, so gradients flow only into the 191 `volume_net.*` parameters
 // (pose_dformer.py:144-208) — exactly the tensors DDP all-reduces in the reference (train.py:361-362).
 // capf_backward_maps adds the one thing a TRAINABLE backbone outside this library needs (conpose.py:22-25 with fix_weights = False): the
-// gradient w.r.t. the four maps, scattered from both samplers with fp32 atomic adds into caller-owned buffers (Engine::backward's dfeat).
+// gradient w.r.t. the four maps, scattered from both samplers into caller-owned buffers (Engine::backward's dfeat) with fp32 atomic adds or,
+// under capf_set_map_grad_mode 1, as an ordered sum without atomics.
 //
 // Which layers, with which parameters: Engine::lifter (LifterSchema, filled by build_lifter) -- nothing here builds a parameter name.
 // With dY [M,N], X [M,K], W [N,K] (all row-major), per linear (t_linear_bwd):
@@ -488,6 +489,7 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
 // dfeat (capf_backward_maps; nullptr: the launches below are capf_backward's, one for one): four caller-owned fp32 NHWC maps that receive
 // the gradient w.r.t. the context maps.  Its two sources are the deformable samplers (dU[l] of every context block, scattered while it
 // is live) and the reference-point sampler (the input gradient of feat_embed[l], which the parameter step has no use for).
+// map_grad_mode picks the summation form at those two places (kernels.h, MapGradArgs): 0 atomic adds, 1 the ordered sum; nothing else differs.
 int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const float* masks, float* const* dfeat) {
     if (B != train_batch) {
         err = "capf_backward: the activations of the matching capf_forward_train are gone (no such call, another batch size, or "
@@ -618,7 +620,7 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
         if (dfeat) {                                     // the same dU, to the corners it was gathered from
             for (int l = 0; l < Lv; ++l) mg.g[l] = tw + L.dU[l];
             mg.AO = tw + c.ao;
-            HIP_TRY(launch_deform_scatter(mg, s));
+            HIP_TRY(map_grad_mode ? launch_deform_scatter_ordered(mg, s) : launch_deform_scatter(mg, s));
         }
         // [attention_weights | sampling_offsets] were one GEMM with N = 48: gradients land in a [48, C] temp
         const Pack& pk = packs[cb.ao_pack];
@@ -651,7 +653,7 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
         if (dfeat) {
             for (int l = 0; l < Lv; ++l) mg.g[l] = tw + L.dU[l];
             mg.AO = nullptr;
-            HIP_TRY(launch_ref_scatter(mg, s));
+            HIP_TRY(map_grad_mode ? launch_ref_scatter_ordered(mg, s) : launch_ref_scatter(mg, s));
         }
         if (int rc2 = t_colreduce(s, L, tw, dX, row_ld(D), nullptr, row_ld(0), 0, R, C, G(lifter.coord.b), 1, nullptr, 0)) return rc2;
         for (int j = 0; j < 2; ++j)

@@ -932,6 +932,52 @@ __device__ __forceinline__ void scatter_throttle(int& issued) {
     }
 }
 
+// One corner of one sample, as BOTH summation forms of the map gradient see it: the destination pixel (y * W + x), the weight of the
+// source row and whether the corner exists.  Contraction is off: the cells are the forward's, bit for bit.
+struct MapItem {
+    int pixel;
+    float w;
+    bool inside;
+};
+
+// deformable sampler (padding border): corner dy * 2 + dx of sample s of head h (k = h * NS + s) of the row ao = [logits | offsets]
+template <int NS>
+__device__ __forceinline__ MapItem deform_map_item(const float* __restrict__ ao, int nk, float rx, float ry, int H, int W, int k, int dx, int dy) {
+#pragma clang fp contract(off)
+    const int h = k / NS, s = k - h * NS;
+    float lg[NS], mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < NS; ++t) { lg[t] = ao[h * NS + t]; mx = fmaxf(mx, lg[t]); }
+    float den = 0.f, mine = 0.f;
+#pragma unroll
+    for (int t = 0; t < NS; ++t) { const float e = expf(lg[t] - mx); den += e; if (t == s) mine = e; }
+    const float ws = mine / den;
+    const float px = tanhf(ao[nk + 2 * k + 0]) + rx;
+    const float py = tanhf(ao[nk + 2 * k + 1]) + ry;
+    const BilinearCorner q = bilinear_corner<true>(px, py, H, W);
+    // border mode: the +1 corner falls outside only where its weight is exactly 0 (the forward clamps its index, ATen masks the load)
+    const int x = q.x0 + dx, y = q.y0 + dy;
+    const float wx = dx ? q.wx1 : 1.0f - q.wx1, wy = dy ? q.wy1 : 1.0f - q.wy1;
+    MapItem m;
+    m.inside = x <= W - 1 && y <= H - 1;
+    m.pixel = y * W + x;
+    m.w = ws * (wx * wy);
+    return m;
+}
+
+// reference-point sampler (padding zeros: sample_ref_kernel's validity tests, a corner outside the map gets nothing; its pixel reads 0)
+__device__ __forceinline__ MapItem ref_map_item(float rx, float ry, int H, int W, int dx, int dy) {
+#pragma clang fp contract(off)
+    const BilinearCorner q = bilinear_corner<false>(rx, ry, H, W);
+    const unsigned x = (unsigned)q.x0 + (unsigned)dx, y = (unsigned)q.y0 + (unsigned)dy;
+    const float wx = dx ? q.wx1 : 1.0f - q.wx1, wy = dy ? q.wy1 : 1.0f - q.wy1;
+    MapItem m;
+    m.inside = x < (unsigned)W && y < (unsigned)H;
+    m.pixel = m.inside ? (int)(y * (unsigned)W + x) : 0;
+    m.w = wx * wy;
+    return m;
+}
+
 // One block per (b, p); wave = level; an item is one corner of one (head, sample): NH * NS * 4 items per wave, 64 / G at a time.
 template <int NS>
 __global__ __launch_bounds__(256) void deform_scatter_kernel(MapGradArgs a) {
@@ -954,23 +1000,9 @@ __global__ __launch_bounds__(256) void deform_scatter_kernel(MapGradArgs a) {
     for (int i0 = 0; i0 < items; i0 += PP) {
         const bool live = i0 + grp < items;
         const int it = live ? i0 + grp : items - 1;
-        const int k = it >> 2, dx = it & 1, dy = (it >> 1) & 1;
-        const int h = k / NS, s = k - h * NS;
-        float lg[NS], mx = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < NS; ++t) { lg[t] = ao[h * NS + t]; mx = fmaxf(mx, lg[t]); }
-        float den = 0.f, mine = 0.f;
-#pragma unroll
-        for (int t = 0; t < NS; ++t) { const float e = expf(lg[t] - mx); den += e; if (t == s) mine = e; }
-        const float ws = mine / den;
-        const float px = tanhf(ao[nk + 2 * k + 0]) + rx;
-        const float py = tanhf(ao[nk + 2 * k + 1]) + ry;
-        const BilinearCorner q = bilinear_corner<true>(px, py, H, W);
-        // border mode: the +1 corner falls outside only where its weight is exactly 0 (the forward clamps its index, ATen masks the load)
-        const int x = q.x0 + dx, y = q.y0 + dy;
-        const bool inside = x <= W - 1 && y <= H - 1;
-        const float wx = dx ? q.wx1 : 1.0f - q.wx1, wy = dy ? q.wy1 : 1.0f - q.wy1;
-        issued += scatter_row(dfeat + ((long)y * W + x) * C, dU + (long)h * C, ws * (wx * wy), C, G, ql, live && inside);
+        const int k = it >> 2;
+        const MapItem m = deform_map_item<NS>(ao, nk, rx, ry, H, W, k, it & 1, (it >> 1) & 1);
+        issued += scatter_row(dfeat + (long)m.pixel * C, dU + (long)(k / NS) * C, m.w, C, G, ql, live && m.inside);
         scatter_throttle(issued);
     }
 }
@@ -995,19 +1027,15 @@ __global__ __launch_bounds__(256) void ref_scatter_kernel(MapGradArgs a) {
     const int H = a.H[l], W = a.W[l], C = a.C[l];
     float* dfeat = a.dfeat[l] + (long)b * H * W * C;
     const float* dS = a.g[l] + (long)bp * C;
-    const BilinearCorner q = bilinear_corner<false>(a.ref[bp * 2 + 0], a.ref[bp * 2 + 1], H, W);
+    const float rx = a.ref[bp * 2 + 0], ry = a.ref[bp * 2 + 1];
     const int G = scatter_lanes(C);
     const int grp = lane / G, ql = lane - grp * G, PP = 64 / G;
     int issued = 0;
     for (int i0 = 0; i0 < 4; i0 += PP) {
         const bool live = i0 + grp < 4;
         const int it = live ? i0 + grp : 3;
-        const int dx = it & 1, dy = (it >> 1) & 1;
-        const unsigned x = (unsigned)q.x0 + (unsigned)dx, y = (unsigned)q.y0 + (unsigned)dy;
-        const bool inside = x < (unsigned)W && y < (unsigned)H;
-        const float wx = dx ? q.wx1 : 1.0f - q.wx1, wy = dy ? q.wy1 : 1.0f - q.wy1;
-        const long pixel = inside ? (long)y * W + x : 0;
-        issued += scatter_row(dfeat + pixel * C, dS, wx * wy, C, G, ql, live && inside);
+        const MapItem m = ref_map_item(rx, ry, H, W, it & 1, (it >> 1) & 1);
+        issued += scatter_row(dfeat + (long)m.pixel * C, dS, m.w, C, G, ql, live && m.inside);
         scatter_throttle(issued);
     }
 }
@@ -1017,6 +1045,163 @@ hipError_t launch_ref_scatter(const MapGradArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(ref_scatter_kernel, dim3(a.B * a.J), dim3(64 * a.L), 0, s, a);
     return hipGetLastError();
 }
+
+// ---- the same gradient as an ORDERED sum, no atomics (capf_set_map_grad_mode 1; the contract is at launch_deform_scatter_ordered) -----------
+// A workgroup owns one (frame, level, chunk of 64 channels) of ONE launch, hence every destination pixel of its chunk: the inverted
+// index is built on chip.  Phases: (A) the frame's source rows of the chunk into LDS (every row is read NS * 4 times); (B) every item's
+// key (pixel << 11 | it) and weight from deform_map_item / ref_map_item, items that do not exist get the largest key; (C) a bitonic sort
+// of the keys, so that the items of a pixel are adjacent and in ascending it; (D) the segment heads, compacted in position order
+// with wave ballots (no LDS atomics: nothing in this kernel depends on arrival order); (E) a group of 16 lanes, 16 bytes each, sums a
+// pixel's items in that order in fp32 and adds the sum to dfeat with one plain load and one plain store.
+// LDS: 53 KB (deformable: 2048 keys, 128 rows of 256 bytes) or 19 KB (reference: 256 keys, 64 rows): three workgroups per CU or more.
+constexpr int OS_ITEMS = MAPGRAD_ORDERED_MAX_ITEMS;      // 2048: it takes the low 11 bits of a key, the pixel the upper 21
+constexpr int OS_CW = 64;                                // channels per chunk
+constexpr unsigned OS_NONE = 0xffffffffu;
+struct OrderedChunks {
+    int end[4];              // running chunk count: level l owns chunks [end[l - 1], end[l]) of blockIdx.y
+    int P;                   // keys sorted: a power of two, 256 <= P <= OS_ITEMS, >= the item count
+};
+
+template <int NS, bool DEFORM>
+__global__ __launch_bounds__(256) void ordered_scatter_kernel(MapGradArgs a, OrderedChunks ch) {
+#pragma clang fp contract(off)
+    constexpr int CAP = DEFORM ? OS_ITEMS : MAPGRAD_ORDERED_MAX_JOINTS * 4;      // keys: J * NH * NS * 4 or J * 4, padded to a power of two
+    constexpr int ROWS = DEFORM ? OS_ITEMS / (NS * 4) : MAPGRAD_ORDERED_MAX_JOINTS;   // source rows of a frame: J * NH or J
+    static_assert(CAP >= 256 && CAP % 256 == 0, "the head scan walks 256 positions a round");
+    __shared__ unsigned keys[CAP];
+    __shared__ float wts[CAP];
+    __shared__ unsigned short heads[CAP + 1];
+    __shared__ f32x4 rows[ROWS * (OS_CW / 4)];
+    __shared__ int cnt[CAP / 256][4];
+    __shared__ int nvalid_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x;
+    int l = 0;
+    while (l + 1 < a.L && (int)blockIdx.y >= ch.end[l]) ++l;               // (block-uniform)
+    const int H = a.H[l], W = a.W[l], C = a.C[l];
+    const int c0 = ((int)blockIdx.y - (l ? ch.end[l - 1] : 0)) * OS_CW;
+    const int cw = min(OS_CW, C - c0);
+    const int nk = a.NH * NS;
+    const int per_joint = DEFORM ? nk * 4 : 4;                             // items of one (b, p)
+    const int items = a.J * per_joint;
+    const int nrows = DEFORM ? a.J * a.NH : a.J;
+    constexpr int ROW_SHIFT = DEFORM ? 4 : 2;                              // source row of item it: it / (NS * 4) or it / 4
+    static_assert(NS == 4, "it >> 4 is the row (p, h)");
+    const int P = ch.P;
+
+    // (A) rows [nrows][cw] of this frame's gradient, pitch 64 floats
+    {
+        const float* src = a.g[l] + (long)b * nrows * C + c0;
+        if (((size_t)src & 15) == 0) {
+            for (int e = tid; e < nrows * (OS_CW / 4); e += 256) {
+                const int r = e >> 4, q = e & 15;
+                if (q * 4 < cw) rows[e] = *reinterpret_cast<const f32x4*>(src + (long)r * C + q * 4);
+            }
+        } else {
+            float* rf = reinterpret_cast<float*>(rows);
+            for (int e = tid; e < nrows * OS_CW; e += 256) {
+                const int r = e >> 6, q = e & 63;
+                if (q < cw) rf[e] = src[(long)r * C + q];
+            }
+        }
+    }
+    // (B) keys and weights
+    if (tid == 0) nvalid_s = 0;
+    for (int it = tid; it < P; it += 256) {
+        unsigned key = OS_NONE;
+        if (it < items) {
+            const int p = it / per_joint, rem = it - p * per_joint;
+            const int bp = b * a.J + p;
+            const float rx = a.ref[bp * 2 + 0], ry = a.ref[bp * 2 + 1];
+            MapItem m;
+            if (DEFORM) m = deform_map_item<NS>(a.AO + ((long)bp * a.L + l) * a.ld_ao, nk, rx, ry, H, W, rem >> 2, rem & 1, (rem >> 1) & 1);
+            else m = ref_map_item(rx, ry, H, W, rem & 1, (rem >> 1) & 1);
+            if (m.inside) key = ((unsigned)m.pixel << 11) | (unsigned)it;
+            wts[it] = m.w;
+        }
+        keys[it] = key;
+    }
+    // (C) bitonic sort, ascending
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            __syncthreads();
+            for (int t = tid; t < (P >> 1); t += 256) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), ixj = i | j;
+                const unsigned x = keys[i], y = keys[ixj];
+                if ((x > y) == ((i & k) == 0)) { keys[i] = y; keys[ixj] = x; }
+            }
+        }
+    __syncthreads();
+    // (D) segment heads in position order; heads[number of segments] = number of keys that exist
+    const int rounds = P >> 8;
+    auto is_head = [&](int i) {
+        const unsigned key = keys[i];
+        return key != OS_NONE && (i == 0 || (keys[i - 1] >> 11) != (key >> 11));
+    };
+    for (int r = 0; r < rounds; ++r) {
+        const int i = r * 256 + tid;
+        const unsigned long long m = __ballot(is_head(i));
+        if (lane == 0) cnt[r][wave] = __popcll(m);
+        if (keys[i] != OS_NONE && (i == P - 1 || keys[i + 1] == OS_NONE)) nvalid_s = i + 1;
+    }
+    __syncthreads();
+    int nseg = 0;
+    for (int r = 0; r < rounds; ++r) {
+        const int i = r * 256 + tid;
+        const bool f = is_head(i);
+        const unsigned long long m = __ballot(f);
+        int base = nseg;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) base += cnt[r][w];
+            nseg += cnt[r][w];
+        }
+        if (f) heads[base + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)i;
+    }
+    if (tid == 0) heads[nseg] = (unsigned short)nvalid_s;
+    __syncthreads();
+    // (E) one pixel per group of 16 lanes at a time
+    const int grp = tid >> 4, ql = tid & 15;
+    if (ql * 4 >= cw) return;
+    float* dst = a.dfeat[l] + (long)b * H * W * C + c0 + ql * 4;
+    for (int sg = grp; sg < nseg; sg += 16) {
+        const int beg = heads[sg], end = heads[sg + 1];
+        const unsigned pixel = keys[beg] >> 11;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int j = beg; j < end; ++j) {
+            const unsigned it = keys[j] & (OS_ITEMS - 1);
+            const float w = wts[it];
+            const f32x4 v = rows[(it >> ROW_SHIFT) * (OS_CW / 4) + ql];
+            acc.x = acc.x + w * v.x; acc.y = acc.y + w * v.y; acc.z = acc.z + w * v.z; acc.w = acc.w + w * v.w;
+        }
+        f32x4* p = reinterpret_cast<f32x4*>(dst + (long)pixel * C);
+        f32x4 d = *p;
+        d.x = d.x + acc.x; d.y = d.y + acc.y; d.z = d.z + acc.z; d.w = d.w + acc.w;
+        *p = d;
+    }
+}
+
+template <bool DEFORM>
+static hipError_t launch_ordered(const MapGradArgs& a, hipStream_t s) {
+    if (a.L < 1 || a.L > 4 || a.B < 1 || a.J < 1) return hipErrorInvalidValue;
+    if (DEFORM && (a.NS != 4 || a.NH < 1 || a.NH * a.NS > 16)) return hipErrorInvalidValue;
+    const long items = DEFORM ? (long)a.J * a.NH * a.NS * 4 : (long)a.J * 4;
+    if (items > (DEFORM ? OS_ITEMS : MAPGRAD_ORDERED_MAX_JOINTS * 4)) return hipErrorInvalidValue;      // (bounds the source rows in LDS too)
+    OrderedChunks ch{};
+    int chunks = 0;
+    for (int l = 0; l < a.L; ++l) {
+        if (a.C[l] < 4 || (a.C[l] & 3) || a.H[l] < 1 || a.W[l] < 1 || (long)a.H[l] * a.W[l] > (1L << 20)) return hipErrorInvalidValue;
+        if (!a.dfeat[l] || ((size_t)a.dfeat[l] & 15) || !a.g[l]) return hipErrorInvalidValue;
+        chunks += (a.C[l] + OS_CW - 1) / OS_CW;
+        ch.end[l] = chunks;
+    }
+    ch.P = 256;
+    while (ch.P < items) ch.P <<= 1;
+    hipLaunchKernelGGL((ordered_scatter_kernel<4, DEFORM>), dim3(a.B, chunks), dim3(256), 0, s, a, ch);
+    return hipGetLastError();
+}
+
+hipError_t launch_deform_scatter_ordered(const MapGradArgs& a, hipStream_t s) { return launch_ordered<true>(a, s); }
+hipError_t launch_ref_scatter_ordered(const MapGradArgs& a, hipStream_t s) { return launch_ordered<false>(a, s); }
 
 // a block zeroes 4096 consecutive elements of one map (16 bytes per lane, four stores)
 __global__ __launch_bounds__(256) void zero_maps_kernel(ZeroMaps z) {

@@ -51,6 +51,19 @@ class _LifterStep(torch.autograd.Function):
         return (None,) * 7 + grads
 
 
+MAP_GRAD_MODES = {"atomic": 0, "ordered": 1}
+
+
+def resolve_map_grad_mode(value):
+    """CA_PF.map_grad_mode -> capf_set_map_grad_mode's argument.  None follows torch: the library has a deterministic form of the map
+    gradient, so torch.use_deterministic_algorithms(True) selects it."""
+    if value is None:
+        return 1 if torch.are_deterministic_algorithms_enabled() else 0
+    if not isinstance(value, str) or value not in MAP_GRAD_MODES:
+        raise ValueError("map_grad_mode must be None, 'atomic' or 'ordered', got {!r}".format(value))
+    return MAP_GRAD_MODES[value]
+
+
 class _FeatureStep(torch.autograd.Function):
     """_LifterStep on caller-supplied context maps: forward = capf_set_features + capf_lifter_forward_train, backward =
     capf_backward_maps, which returns the gradient w.r.t. the four maps next to the flat parameter gradient.  The maps arrive as
@@ -65,6 +78,7 @@ class _FeatureStep(torch.autograd.Function):
         eng.lifter_forward_train(k2d, kcrop, out, stream, masks)
         ctx.token = eng.train_generation()
         ctx.eng, ctx.masks, ctx.names, ctx.owner, ctx.n_maps = eng, masks, names, owner, n_maps
+        ctx.map_grad_mode = resolve_map_grad_mode(owner.map_grad_mode)      # (the step's mode is the one in force at its forward)
         ctx.keep = (k2d, kcrop)     # capf_backward_maps re-reads the keypoints / normalised ref: keep them alive
         ctx.map_shapes = [f.shape for f in feats]
         ctx.shapes = [p.shape for p in params]
@@ -81,6 +95,8 @@ class _FeatureStep(torch.autograd.Function):
         flat = torch.empty(total, dtype=torch.float32, device=grad_out.device)
         dfeat = [torch.empty(shp, dtype=torch.float32, device=grad_out.device) for shp in ctx.map_shapes]
         stream = torch.cuda.current_stream(grad_out.device).cuda_stream
+        if eng.map_grad_mode() != ctx.map_grad_mode:      # a state change of the handle: once per change, not per step
+            eng.set_map_grad_mode(ctx.map_grad_mode)
         eng.backward_maps(grad_out.contiguous(), flat, dfeat, stream, ctx.masks)
         ctx.owner.last_flat_grad = flat
         dmaps = tuple(g if need else None for g, need in zip(dfeat, ctx.needs_input_grad[7:7 + ctx.n_maps]))
@@ -124,6 +140,10 @@ class CA_PF(nn.Module):
         # into its parameter's .grad: 191 small device copies per step that a flat optimizer never reads; they overlap the rest of
         # the step -- no measurable change of a 512-frame step, the point is not to materialise a second copy of the gradient)
         self.flat_grad_only = False
+        # how forward_features' backward sums the gradient w.r.t. the context maps (capf_set_map_grad_mode): "atomic" (fp32 atomic
+        # adds, not bit-reproducible), "ordered" (a fixed summation order, bit-reproducible), or None: ordered when
+        # torch.are_deterministic_algorithms_enabled(), else atomic
+        self.map_grad_mode = None
         self._engines = {}          # (device index, H, W) -> Engine
         # Parameter-change tracking.  `_generation` counts events that may have replaced parameter STORAGE or frozen
         # (backbone) VALUES: load_state_dict on the model or either child, .to()/._apply, params_changed().  Every engine
@@ -251,7 +271,11 @@ class CA_PF(nn.Module):
         of the configured backbone's geometry at crop size (4 H_0, 4 W_0).  Returns [B,1,17,3]; the third argument is normalised in
         place exactly as forward does.  With grad enabled, gradients flow into volume_net's parameters AND into every map that
         requires grad (capf_backward_maps), so a torch backbone in front of the native lifter trains through it; the native backbone
-        is not run.  The map gradients are summed with atomic adds: equal up to fp32 summation order from run to run."""
+        is not run.  self.map_grad_mode picks how the map gradients are summed: "atomic" -- fp32 atomic adds, equal up to fp32 summation
+        order from run to run; "ordered" -- one fixed expression (include/capf.h, capf_set_map_grad_mode), bit-identical from run to
+        run; None (default) -- ordered under torch.use_deterministic_algorithms(True), otherwise atomic.  Anything else: ValueError.
+        The parameter gradients have the same bits in both."""
+        resolve_map_grad_mode(self.map_grad_mode)
         feats = list(features_list)
         if len(feats) != 4:
             raise ValueError("features_list must hold 4 context maps, got {}".format(len(feats)))

@@ -145,7 +145,8 @@ const char* capf_version(void);
  * capf_jpeg_decode_crop_batch); struct layouts unchanged.  Revision 11 (additive): the guarded AdamW step (capf_optim_ctrl_bytes,
  * capf_optim_ctrl_init, capf_grad_sumsq, capf_adamw_step_guarded; new structs capf_optim_report, capf_optim_segment); existing struct
  * layouts unchanged.  Revision 12 (additive): compute_dtype = CAPF_F16, tensor dtype code 3 (fp16) in capf_tensor / capf_op_desc, the
- * capf_op_*_16 entry points (the 16-bit kernels for either element format) and capf_debug_f16_round; struct layouts unchanged.           */
+ * capf_op_*_16 entry points (the 16-bit kernels for either element format) and capf_debug_f16_round; struct layouts unchanged
+ * (additive: capf_set_map_grad_mode, capf_map_grad_mode).                                                                                */
 #define CAPF_ABI_VERSION 12
 int capf_abi_version(void);
 
@@ -305,13 +306,28 @@ int capf_lifter_forward(capf_handle* h, void* stream, const float* k2d, float* k
  *     capf_backward -- flat_grad gets the same bits -- plus dfeat_nhwc[l] = dL/d(feat_l), caller-owned fp32 NHWC
  *     [batch, H_l, W_l, C_l], 16-byte aligned, zeroed and overwritten by this call (garbage on entry is fine).  Valid after
  *     capf_forward_train or capf_lifter_forward_train, under capf_backward's generation / CAPF_ERR_STATE rules.
- *     The map gradient is summed with fp32 atomic adds (many samples meet in one pixel), whose order is not fixed: dfeat_nhwc is NOT
- *     bit-reproducible from run to run (last-bit differences); flat_grad is. */
+ *     Many samples meet in one pixel, and capf_set_map_grad_mode picks how their contributions are summed; flat_grad has the same,
+ *     reproducible bits in both modes.  Mode 0 (default): fp32 atomic adds, whose order is not fixed -- dfeat_nhwc is NOT bit-reproducible
+ *     from run to run (last-bit differences).  Mode 1: the ordered sum below -- bit-identical from run to run and from handle to handle
+ *     on the same inputs.
+ * capf_set_map_grad_mode: 0 = atomic (default), 1 = ordered; any other value CAPF_ERR_INVALID.  A state change only (plan-only handles
+ *     take it too); it affects nothing but the dfeat_nhwc half of capf_backward_maps.  CAPF_ERR_UNSUPPORTED on a bf16 / fp16 handle.
+ *     The ordered sum: an item is one corner (dy, dx) of one bilinear sample, numbered it = ((p * heads + h) * samples + s) * 4 + dy * 2 + dx
+ *     at a deformable sampler (joint p, head h, sample s; weight softmax_s * wx * wy, source row dL/dU[b, p, h]) and it = p * 4 + dy * 2 + dx
+ *     at the reference-point sampler (weight wx * wy, source row dL/dS_l[b, p]; corners outside the map dropped).  For one sampler pass,
+ *     S[pixel][c] = sum over the items that fall into the pixel, in ascending it, in fp32, of weight_it * row_it[c], and
+ *         dfeat = ((((0 + S_ctx[levels-1]) + S_ctx[levels-2]) + ...) + S_ctx[0]) + S_ref
+ *     (context blocks in the order the backward visits them, then the reference pass; without context blocks dfeat = 0 + S_ref).  No
+ *     atomics, no extra workspace: capf_workspace_bytes is the same in both modes.  At most 2048 items per frame and level in a pass
+ *     (joints * heads * samples * 4; 1088 at the shipped configurations), otherwise capf_backward_maps returns CAPF_ERR_HIP.
+ * capf_map_grad_mode: the current mode (-1 for a NULL handle). */
 int capf_set_features(capf_handle* h, void* stream, const float* const feat_nhwc[4], int batch);
 int capf_lifter_forward_train(capf_handle* h, void* stream, const float* k2d, float* kcrop_inout, int batch, float* out,
                               const float* drop_masks);
 int capf_backward_maps(capf_handle* h, void* stream, const float* grad_out, int batch, float* flat_grad, const float* drop_masks,
                        float* const dfeat_nhwc[4]);
+int capf_set_map_grad_mode(capf_handle* h, int mode);
+int capf_map_grad_mode(const capf_handle* h);
 
 /* How the independent branches of the backbone (the 2-4 resolution branches of an HRNet module, the
  * fused outputs, the CPN refine cascades) are issued:

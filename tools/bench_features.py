@@ -1,6 +1,7 @@
-"""capf_backward vs capf_backward_maps on one engine, in one process (EXPERIMENTS.md R12.1).
+"""capf_backward vs capf_backward_maps in both summation modes on one engine, in one process (EXPERIMENTS.md R12.1, R15.1).
 
-HRNet-32, fp32, 256 x 256, batches 64 and 512: one capf_forward_train, then the two backwards alternate on its saved activations (a
+HRNet-32, fp32, 256 x 256, batches 64 and 512: one capf_forward_train, then the three backwards -- capf_backward, capf_backward_maps
+with atomic adds (capf_set_map_grad_mode 0) and with the ordered sum (mode 1) -- alternate on its saved activations (a
 backward only reads them), each call bracketed by device events; medians and (max - min) / median over the repeats.  Also printed: the
 bytes the map gradient adds with atomics (every in-range corner of every deformable sample and of every reference point, 4 bytes per
 channel) and the rate that the time difference implies, next to the chip-wide rate of fp32 atomic adds (about 1.3 TB/s of added bytes).
@@ -46,11 +47,17 @@ def main():
         dfeat = [torch.empty(B, h, w, c, device="cuda") for h, w, c in eng.feature_shapes()]
         dout = torch.randn(B, 1, 17, 3, generator=torch.Generator().manual_seed(3)).cuda() / (17 * B)
         eng.forward_train(img, k2d, kc, out, s, None)
-        runs = {"backward": lambda: eng.backward(dout, flat, s, None),
-                "backward_maps": lambda: eng.backward_maps(dout, flat, dfeat, s, None)}
+        def maps(mode):
+            eng.set_map_grad_mode(mode)                     # (a host-side state change, outside the events)
+            return lambda: eng.backward_maps(dout, flat, dfeat, s, None)
+
+        runs = {"backward": lambda: (lambda: eng.backward(dout, flat, s, None)),
+                "backward_maps": lambda: maps(0),
+                "backward_maps_ordered": lambda: maps(1)}
         times = {k: [] for k in runs}
         for it in range(args.warmup + args.repeats):
-            for name, run in runs.items():                      # alternating: both see the same drift of the box
+            for name, prepare in runs.items():                  # alternating: all see the same drift of the box
+                run = prepare()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 run()
@@ -64,9 +71,13 @@ def main():
         # upper count: every corner in range (a clamped +1 corner and a reference corner outside the map add nothing)
         added = B * 17 * (4 * 16 * 4 + 4) * C * 4
         extra_ms = med["backward_maps"] - med["backward"]
+        extra_ordered_ms = med["backward_maps_ordered"] - med["backward"]
+        eng.set_map_grad_mode(0)
         zeroed = sum(t.numel() for t in dfeat) * 4
         print(json.dumps({"batch": B, "backward_ms": round(med["backward"], 4), "backward_maps_ms": round(med["backward_maps"], 4),
+                          "backward_maps_ordered_ms": round(med["backward_maps_ordered"], 4),
                           "spread": {k: round(v, 4) for k, v in spread.items()}, "extra_ms": round(extra_ms, 4),
+                          "extra_ordered_ms": round(extra_ordered_ms, 4),
                           "atomic_bytes": added, "zeroed_bytes": zeroed,
                           "atomic_TBps_if_all_extra_time": round(added / (extra_ms * 1e-3) / 1e12, 3) if extra_ms > 0 else None,
                           "ms_at_1.3TBps": round(added / 1.3e12 * 1e3, 4), "repeats": args.repeats}))
