@@ -1133,9 +1133,17 @@ bool Engine::build() {
         err = "unsupported lifter configuration (levels must be 4, 4x4 deformable sampling, embed_dim_ratio % 32 == 0)";
         return false;
     }
-    // depth != levels: the variant without context blocks (ContextPose_mpi, pose_dformer.py:199).  Inference plans at any width; training
-    // plans at the widths that app builds (run_3dhp.py:219-232 and common/cfg.py:81-82: embed_dim_ratio 64 over base_dim 32, 96 over 48),
-    // whose head dims (8 / 12 res, 40 / 60 joint) tests/test_gpu_mpi_train.py holds to fp64 at depths 1..8
+    // the LayerNorm and head kernels (lifter.hip, train_kernels.hip) hold a joint row of (levels + 1) * embed_dim_ratio values in 24 values
+    // per lane of one wave: 1536 at the most, i.e. embed_dim_ratio <= 288 -- refused here, not by a launcher in the middle of a forward
+    if (cfg.embed_dim_ratio * (cfg.levels + 1) > 1536) {
+        err = "embed_dim_ratio * (levels + 1) must not exceed 1536 (embed_dim_ratio <= 288 at 4 levels): the LayerNorm and head kernels hold a "
+              "joint row in 24 values per lane of a 64-lane wave";
+        return false;
+    }
+    // depth != levels: the variant without context blocks (ContextPose_mpi, pose_dformer.py:199).  Inference plans at any width up to that
+    // limit; training plans at the widths that app builds (run_3dhp.py:219-232 and common/cfg.py:81-82: embed_dim_ratio 64 over base_dim 32,
+    // 96 over 48), whose head dims (8 / 12 res, 40 / 60 joint) tests/test_gpu_mpi_train.py holds to fp64 at depths 1..8.  "Other widths train
+    // at depth == levels": tests/test_gpu_train_widths.py holds a step of the H36M model to fp64 at 32, 64, 96, 160, 256 and 288
     if (cfg.depth != 0 && cfg.depth != cfg.levels) {
         const bool mpi_width = (cfg.base_dim == 32 && cfg.embed_dim_ratio == 64) || (cfg.base_dim == 48 && cfg.embed_dim_ratio == 96);
         if (cfg.depth < 1 || cfg.depth > 8 || cfg.context_blocks || (cfg.training && !mpi_width)) {

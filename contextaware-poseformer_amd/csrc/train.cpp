@@ -76,9 +76,15 @@ void Engine::train_layout(int B, TrainLayout& L) const {
     L.gC = take((size_t)J * 3 * D);
     L.cat = take(0, (size_t)64 * (C + 1));
     for (int l = 0; l < Lv; ++l) L.dU[l] = take((size_t)J * NH * feat_C[l]);
-    const size_t maxNR = (size_t)J * 3 * D;                    // max over linears of (N or K) * rows per frame
-    L.tA = take(maxNR, (size_t)3 * D * 32);
-    L.tB = take(maxNR, (size_t)3 * D * 32);
+    // max over linears of (N or K) * rows per frame: qkv's 3 D columns over J joint rows, or -- wider than that below embed_dim_ratio 128 --
+    // a context map's channels over the J * NH sampled rows of an embed_proj (its row map keeps it off wgrad_tn: t_linear_bwd's fallback)
+    int maxC = 0;
+    for (int l = 0; l < Lv; ++l) maxC = std::max(maxC, feat_C[l]);
+    const size_t ctxNR = cfg.context_blocks ? (size_t)J * NH * maxC : 0;
+    const size_t maxNR = std::max((size_t)J * 3 * D, ctxNR);
+    const size_t padNR = (size_t)std::max(3 * D, cfg.context_blocks ? maxC : 0) * 32;     // (rows are padded to a multiple of 32)
+    L.tA = take(maxNR, padNR);
+    L.tB = take(maxNR, padNR);
     L.wT = take(0, (size_t)3 * D * D + 64 * 2 * D);            // largest transposed weight [K][Npad]
     L.slab_cap = (size_t)16 * (3 * D * D + 3 * D);             // split-K slabs of the largest weight gradient (+ its bias gradient) ...
     L.slabs_elems = 8 * L.slab_cap;                            // ... and room for several layers' slabs: their sums are deferred (t_slab_flush)

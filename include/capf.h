@@ -64,7 +64,8 @@ typedef struct capf_config {
     int32_t hr_modules[3];     /* NUM_MODULES of stage2..4: {1,4,3} */
     int32_t hr_blocks;         /* NUM_BLOCKS per branch: 4 */
     int32_t base_dim;          /* poseformer.base_dim: 32 / 48 / 256(cpn) */
-    int32_t embed_dim_ratio;   /* 128 */
+    int32_t embed_dim_ratio;   /* 128.  A multiple of 32 with embed_dim_ratio * (levels + 1) <= 1536, i.e. at most 288: the LayerNorm and head
+                                  kernels hold a joint row in 24 values per lane of a 64-lane wave; capf_create refuses a wider one */
     int32_t levels;            /* 4 feature levels (H36M model: also the depth of every block group, pose_dformer.py:169) */
     int32_t num_joints;        /* 17 */
     int32_t num_heads;         /* 8  (Block) */
@@ -79,7 +80,7 @@ typedef struct capf_config {
                                   tests compare the two routes; nothing else -- no environment variable -- changes a plan) */
     int32_t depth;             /* blocks per group (res_blocks / joint_blocks).  0 = levels.  The MPI-INF-3DHP variant reads it from
                                   config.model.poseformer.depth (ContextPose_mpi/model/pose_dformer.py:199, 217-227; 1..8).  Inference plans
-                                  at any width; training plans at that app's widths (run_3dhp.py:219-232: embed_dim_ratio 64 over base_dim
+                                  at any accepted width; training plans at that app's widths (run_3dhp.py:219-232: embed_dim_ratio 64 over base_dim
                                   32, 96 over 48), other widths train at depth == levels.  The H36M model (context_blocks = 1) has
                                   depth == levels by construction */
 } capf_config;

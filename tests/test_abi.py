@@ -514,3 +514,46 @@ def test_depth_is_a_plan_parameter_of_the_variant_without_context_blocks():
     for bad in ((2, True, 0), (2, False, 1), (9, False, 0), (-1, False, 0)):
         with pytest.raises(CapfError):
             plan(*bad)
+
+
+def test_a_lifter_row_wider_than_the_layernorm_kernels_hold_is_refused_at_creation():
+    """Engine::build (csrc/plan.cpp): embed_dim_ratio * (levels + 1) <= 1536 -- the LayerNorm and head launchers (lifter.hip, train_kernels.hip)
+    hold a joint row in 24 values per lane and return a bare HIP error for a wider one, so 320 is refused when the plan is made, for
+    inference and training plans alike, with the reason in capf_last_error(NULL); 288 is the widest plan.  No forward runs here."""
+    from capf import Engine
+    from capf.lib import CapfError, load_library
+    from mvn.models import _native
+
+    def config(embed, training):
+        cfg = _cfg("hrnet_32")
+        cfg.model.poseformer.embed_dim_ratio = embed
+        c = _native.make_capf_config(cfg, 128, 96)
+        c.training = training
+        return c
+
+    for training in (0, 1):
+        with pytest.raises(CapfError, match=r"must not exceed 1536.*LayerNorm and head kernels.*24 values per lane"):
+            Engine(config(320, training), device=None)
+        assert b"24 values per lane" in load_library().capf_last_error(None)
+        eng = Engine(config(288, training), device=None)
+        assert dict((n, s) for n, s, _ in eng.schema())["volume_net.Spatial_pos_embed"][-1] == 288
+        assert eng.workspace_bytes(2) > 0
+        eng.close()
+
+
+@pytest.mark.parametrize("backbone", ["hrnet_32", "hrnet_48", "cpn"])
+def test_two_piece_table_of_a_training_plan_follows_the_restated_rule_at_every_width(backbone):
+    """capf_train_h2_matrices of a plan-only engine == the rule tests/test_gpu_train_widths.py restates from t_h2_plan (csrc/train.cpp), at
+    every embed_dim_ratio % 32 == 0 up to 288; none under bf16."""
+    from capf import Engine
+    from mvn.models import _native
+    from test_gpu_train_widths import MAP_CHANNELS, WIDTHS, h2_table
+    for dtype in ("fp32", "bf16"):
+        for embed in WIDTHS:
+            cfg = _cfg(backbone)
+            cfg.model.poseformer.embed_dim_ratio = embed
+            eng = Engine(_native.make_capf_config(cfg, 128, 96, compute_dtype=dtype), device=None)
+            want = h2_table(embed, MAP_CHANNELS[backbone], dtype)
+            assert eng.lib.capf_train_h2_matrices(eng.h) == len(want), (dtype, embed)
+            assert (len(want) == 0) == (dtype == "bf16")
+            eng.close()

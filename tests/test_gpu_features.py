@@ -21,7 +21,8 @@ import torch
 import capf_oracle as oracle
 from capf import synth
 from conftest import make_model
-from train_yardstick import GRAD_L2_BOUND, GRAD_MAX_BOUND, check_gradients, engine_cells, lifter64
+from lifter_models import lifter_model
+from train_yardstick import GRAD_L2_BOUND, GRAD_MAX_BOUND, check_gradients, engine_cells, engine_clip_sides, lifter64
 
 pytestmark = pytest.mark.gpu
 
@@ -209,19 +210,34 @@ CASES = [
     ("cpn", (256, 192), 2, 0.0, None),
     ("hrnet_32", (128, 96), 3, 0.0, 2),
 ]
+# the two ends of the widths a plan accepts (tests/test_gpu_train_widths.py holds the parameter step there): feat_embed's input gradient is a
+# dX GEMM with N = embed_dim_ratio that no parameter step runs (csrc/train.cpp backward, "embeddings").  At 32 the matrix is in no two-piece
+# table (N < 64), at 288 it is no multiple of 64 columns; the narrow one sums the maps in the ordered mode
+WIDTH_CASES = [
+    # ... embed_dim_ratio (None: the preset's 128), capf_set_map_grad_mode (None: as the engine comes, atomic)
+    ("hrnet_32", (128, 96), 6, 0.0, None, 32, 1),
+    ("hrnet_32", (128, 96), 6, 0.0, None, 288, 0),
+]
 
 
-@pytest.mark.parametrize("backbone,hw,B,drop,depth", CASES,
-                         ids=["hrnet_32-B2", "hrnet_32-B6-droppath", "hrnet_48-B5-Kpad", "cpn-B2", "mpi-hrnet_32-d2-B3"])
-def test_map_gradients_vs_fp64(backbone, hw, B, drop, depth):
+@pytest.mark.parametrize("backbone,hw,B,drop,depth,embed,mode", [c + (None, None) for c in CASES] + WIDTH_CASES,
+                         ids=["hrnet_32-B2", "hrnet_32-B6-droppath", "hrnet_48-B5-Kpad", "cpn-B2", "mpi-hrnet_32-d2-B3",
+                              "hrnet_32-E32-B6-ordered", "hrnet_32-E288-B6"])
+def test_map_gradients_vs_fp64(backbone, hw, B, drop, depth, embed, mode):
     torch.set_num_threads(min(16, torch.get_num_threads()))
     H, W = hw
-    model = _mpi(51 + B, depth) if depth else _hrnet(backbone, 51 + B, drop)
+    if embed:
+        model = _train_mode(lifter_model(backbone, embed=embed, wseed=51 + B + embed)[0], drop)
+    else:
+        model = _mpi(51 + B, depth) if depth else _hrnet(backbone, 51 + B, drop)
     map_hw = (64, 48) if backbone == "cpn" else (H // 4, W // 4)
     img, k2d, kc, gt = _inputs(B, H, W, 52 + B, map_hw)
     img, k2d = img.cuda(), k2d.cuda()
     eng = model.engine_for(img)
     eng.set_debug(True)                                        # cidx taps of the deformable samplers
+    if mode is not None:
+        eng.set_map_grad_mode(mode)
+        assert eng.map_grad_mode() == mode
     masks = _masks(model, B, 7) if drop else None
     dfeat = _empty_like_maps(eng, B)
     pred, loss, ref, flat = _engine_step(model, eng, img, k2d, kc, gt, masks, dfeat)
@@ -230,7 +246,7 @@ def test_map_gradients_vs_fp64(backbone, hw, B, drop, depth):
     feats = [m.cpu().double().permute(0, 3, 1, 2).contiguous().requires_grad_(True) for m in _maps(eng, B)]
     assert [tuple(f.shape[1:]) for f in feats] == [(c, h, w) for h, w, c in eng.feature_shapes()]
     params = {"volume_net." + n: p for n, p in model.volume_net.named_parameters()}
-    tag = f"{'mpi ' if depth else ''}{backbone} {H}x{W} B={B} DropPath {drop}"
+    tag = f"{'mpi ' if depth else ''}{backbone} {H}x{W} B={B} DropPath {drop}" + (f" E={embed} map_grad_mode {mode}" if embed else "")
     if depth:
         Q = {k: v.detach().cpu().double().clone().requires_grad_(True) for k, v in params.items()}
         w64 = oracle.lifter_forward(Q, k2d.cpu().double(), ref.double(), feats, context_blocks=False, depth=depth)
@@ -238,7 +254,7 @@ def test_map_gradients_vs_fp64(backbone, hw, B, drop, depth):
         l64.backward()
         g64, w64, l64 = {k: q.grad for k, q in Q.items()}, w64.detach(), l64.item()
     else:
-        g64, w64, l64 = lifter64(params, k2d, ref, gt, feats, engine_cells(eng, B), masks)
+        g64, w64, l64 = lifter64(params, k2d, ref, gt, feats, engine_cells(eng, B), masks, engine_clip_sides(eng, B))
     perr, lerr = (pred.double() - w64).abs().max().item(), abs(loss - l64) / abs(l64)
     print(f"  {tag}: prediction max|hip - fp64| {perr:.2e}, loss {loss:.6f} (relative error {lerr:.2e})")
     assert perr <= 1e-5 and lerr <= 1e-6, (perr, lerr)
@@ -256,6 +272,10 @@ def test_map_gradients_vs_fp64(backbone, hw, B, drop, depth):
     else:
         pl2, pmx = check_gradients(tag, got, g64)
     print(f"  {tag}: worst map gradient {l2:.2e} relative L2, {mx:.2e} of max; worst parameter gradient {pl2:.2e}, {pmx:.2e}")
+    if embed:                                                  # (the training workspace grows with the width squared: 3.7 GB at 288)
+        for e in model._engines.values():
+            e.close()
+        model._engines.clear()
 
 
 # ---- 4. dfeat is overwritten, not accumulated into -------------------------------------------------------------------------------------

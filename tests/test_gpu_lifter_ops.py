@@ -8,10 +8,6 @@ token buffer is read after capf_forward_prefix(i), the op's result after capf_fo
   The context sampler's cells (cidx taps) are ATen's index rule on its own positions (cpos taps) bit for bit, the positions agree with
   the float64 ones within the bound, and the samples are recomputed in those cells (a position on a cell boundary by roundoff is no error).
 Every point asserts the route its plan takes from op_table's kernel names, and that every lifter op of the schedule was checked."""
-import contextlib
-import copy
-import io
-
 import numpy as np
 import pytest
 import torch
@@ -20,34 +16,11 @@ import capf_oracle as oracle
 import op_oracle
 from capf import synth
 from capf.lib import PLAN_NO_F32H2_GEMM, PLAN_NO_FUSED_LIFTER
+from lifter_models import lifter_model as _model
 
 pytestmark = pytest.mark.gpu
 
 V = "volume_net"
-
-
-def _model(backbone, dtype="fp32", embed=None, plan_flags=0, mpi=False, depth=None, wseed=81, tweak=None):
-    from mvn.utils.cfg import backbone_preset, config
-    if mpi:
-        from model.conpose import VolumetricTriangulationNet, mpi_preset
-        cfg = mpi_preset(copy.deepcopy(config), backbone)
-        if depth:
-            cfg.model.poseformer.depth = depth
-        with contextlib.redirect_stdout(io.StringIO()):
-            model = VolumetricTriangulationNet(cfg, compute_dtype=dtype).eval()
-    else:
-        from mvn.models.conpose import CA_PF
-        cfg = backbone_preset(copy.deepcopy(config), backbone)
-        cfg.model.backbone.fix_weights = True
-        if embed:
-            cfg.model.poseformer.embed_dim_ratio = embed
-        with contextlib.redirect_stdout(io.StringIO()):
-            model = CA_PF(cfg, compute_dtype=dtype, plan_flags=plan_flags).eval()
-    sd = synth.load_synthetic(model, seed=wseed, bn_mode="random")
-    if tweak is not None:
-        tweak(sd)
-        model.load_state_dict(sd, strict=True)
-    return model.cuda(), sd
 
 
 # ---- the template instance an op reaches (csrc/lifter.hip launch_attention / launch_layernorm / launch_head)

@@ -252,6 +252,38 @@ def test_grid_sample_in_cells_is_grid_sample_with_the_cells_given():
     assert (dl - dr).abs().max().item() > 1e-3
 
 
+def test_grid_sample_in_cells_takes_the_clip_side_it_is_given():
+    """grid_sample_in_cells(unclipped=...): with every coordinate's own side (0 < x < size - 1) it is the function without the argument,
+    value and both gradients; a coordinate a roundoff INSIDE the last pixel that the implementation under test clipped (its fp32
+    position is the border itself: found on a 4 x 3 map, test_gpu_train_widths.py) passes no gradient and moves the value by that
+    roundoff; one a roundoff OUTSIDE that it left unclipped keeps the gradient of the last cell."""
+    torch.manual_seed(1)
+    f = torch.randn(2, 5, 4, 3, dtype=torch.float64, requires_grad=True)
+    g = (torch.rand(2, 3, 4, 2, dtype=torch.float64) * 2.4 - 1.2).requires_grad_(True)
+    c = oracle.bilinear_corners(g.detach().numpy(), 4, 3, "border")
+    ix0, iy0 = torch.from_numpy(c["ix0"].astype(np.int64)), torch.from_numpy(c["iy0"].astype(np.int64))
+    u = (g.detach() + 1) / 2 * torch.tensor([2.0, 3.0], dtype=torch.float64)
+    own = (u > 0) & (u < torch.tensor([2.0, 3.0], dtype=torch.float64))
+    assert own.any() and not own.all()
+    a, b = oracle.grid_sample_in_cells(f, g, ix0, iy0), oracle.grid_sample_in_cells(f, g, ix0, iy0, own)
+    assert torch.equal(a, b)
+    ga, gb = torch.autograd.grad(a.square().sum(), [f, g]), torch.autograd.grad(b.square().sum(), [f, g])
+    assert torch.equal(ga[0], gb[0]) and torch.equal(ga[1], gb[1])
+    # y = 3 - 2.6e-7 of 0..3 (what float64 made of an fp32 position that is 3.0 itself), in the last cell (NW corner y0 = 2)
+    eps = 2.6e-7
+    for dy, free in ((-eps, False), (+eps, True)):
+        gy = torch.tensor([[[[0.2, 2 * (3 + dy) / 3 - 1]]]], dtype=torch.float64).expand(2, 1, 1, 2).clone().requires_grad_(True)
+        cells = (torch.full((2, 1, 1), 1), torch.full((2, 1, 1), 2))
+        mine = oracle.grid_sample_in_cells(f, gy, *cells)
+        told = oracle.grid_sample_in_cells(f, gy, *cells, torch.tensor([True, free]).expand(2, 1, 1, 2))
+        assert (mine - told).abs().max().item() < 4 * eps * f.abs().max().item()
+        d_mine = torch.autograd.grad(mine.sum(), gy, retain_graph=True)[0]
+        d_told = torch.autograd.grad(told.sum(), gy)[0]
+        assert (d_mine[..., 0] - d_told[..., 0]).abs().max().item() < 5 * 4 * eps * f.abs().max().item()      # (x is nowhere near a border; 5 channels)
+        assert (d_mine[..., 1] != 0).all() == (not free) and (d_told[..., 1] != 0).all() == free
+        assert (d_mine[..., 1] == 0).all() == free and (d_told[..., 1] == 0).all() == (not free)
+
+
 @pytest.mark.parametrize("name", ["w48_256x256_b1", "cpn_384x288_b1"])
 def test_bf16_emulation_sits_between_the_references_two_bf16_evaluations(name):
     """The bf16-emulating oracle (the yardstick of the end-to-end bf16 GPU tests, bf16_report.py) against what the REAL reference does

@@ -6,6 +6,11 @@ Two things would make a naive comparison meaningless (derivation: test_gpu_fulls
       gradient, not to an fp32 evaluation;
   (b) grid_sample's derivative w.r.t. the position is one-sided at cell boundaries -- the yardstick evaluates its deformable samplers IN
       THE CELLS THE ENGINE USED (its cidx taps, themselves checked bit for bit against ATen's index rule: check_cells_against_index_rule).
+  (c) the border clip is one-sided in the same way: a coordinate clipped to 0 or size - 1 passes no gradient (ATen's
+      clip_coordinates_set_grad), one a roundoff inside does -- the yardstick clips the coordinates THE ENGINE'S POSITIONS clip under
+      ATen's rule in fp32 (engine_clip_sides: from the cpos taps, not from any flag of the kernels).  On maps as small as 4 x 3, where
+      most samples sit on a border, a step in a few hundred has such a coordinate; without this its one sample's derivative shows as an error
+      of 2e-4 in that block's sampling_offsets and norm1 gradients (found at embed_dim_ratio 160, B = 6: test_gpu_train_widths.py).
 engine_yardstick() also takes the engine's own context maps (feat{l} taps, upcast to float64; bf16 maps upcast exactly), so the bound
 measures the lifter alone, whatever the backbone and its dtype."""
 import numpy as np
@@ -59,11 +64,29 @@ def engine_cells(eng, B):
     return [eng.tensor(f"cidx{i}")[:B].cpu().view(B, 17, 4, 16, 2).long() for i in range(4)]
 
 
-def lifter64(params, k2d, ref, gt, feats, cells=None, drop_masks=None):
+def engine_clip_sides(eng, B):
+    """Which coordinates of the deformable samplers the border clip left alone, by ATen's rule (0 < x < size - 1 on the unnormalised
+    coordinate) in the kernels' fp32 arithmetic on the positions the engine computed (cpos{i} taps of a set_debug(True) step): bool
+    [B, 17, 4, 16, 2] per block."""
+    out = []
+    for i in range(4):
+        pos = eng.tensor(f"cpos{i}")[:B].cpu().view(B, 17, 4, 16, 2).numpy()
+        free = np.zeros(pos.shape, dtype=bool)
+        for l in range(4):
+            f = eng.tensor(f"feat{l}")
+            for axis, size in ((0, f.shape[2]), (1, f.shape[1])):
+                x = ((pos[:, :, l, :, axis] + np.float32(1)) / np.float32(2)) * np.float32(size - 1)
+                assert x.dtype == np.float32
+                free[:, :, l, :, axis] = (x > 0) & (x < size - 1)
+        out.append(torch.from_numpy(free))
+    return out
+
+
+def lifter64(params, k2d, ref, gt, feats, cells=None, drop_masks=None, sides=None):
     """oracle.lifter_forward in float64 on `feats` (NCHW), MPJPE against gt, backward.  params: name -> tensor (the volume_net.* entries
-    are used).  Returns ({name: fp64 gradient}, fp64 prediction, fp64 loss)."""
+    are used).  cells / sides: engine_cells / engine_clip_sides.  Returns ({name: fp64 gradient}, fp64 prediction, fp64 loss)."""
     Q = {k: v.detach().cpu().double().clone().requires_grad_(True) for k, v in params.items() if k.startswith("volume_net.")}
-    w = oracle.lifter_forward(Q, k2d.cpu().double(), ref.cpu().double(), feats, cells=cells,
+    w = oracle.lifter_forward(Q, k2d.cpu().double(), ref.cpu().double(), feats, cells=cells, unclipped=sides,
                               drop_masks=drop_masks.cpu().double() if drop_masks is not None else None)
     loss = oracle.mpjpe(w, gt.cpu().double())
     loss.backward()
@@ -76,7 +99,7 @@ def engine_yardstick(model, eng, B, k2d, ref, gt, drop_masks=None):
     third argument after it returned).  Returns ({'volume_net.<name>': fp64 gradient}, fp64 prediction, fp64 loss)."""
     feats = [eng.tensor(f"feat{l}")[:B].cpu().double().permute(0, 3, 1, 2).contiguous() for l in range(4)]
     params = {"volume_net." + n: p for n, p in model.volume_net.named_parameters()}
-    return lifter64(params, k2d, ref, gt, feats, engine_cells(eng, B), drop_masks)
+    return lifter64(params, k2d, ref, gt, feats, engine_cells(eng, B), drop_masks, engine_clip_sides(eng, B))
 
 
 def engine_gradients(model, eng):
