@@ -38,9 +38,9 @@ def _compare_f32(got, want, mass, term):
     return {"max_err": (d / (allowed + 1e-30)).max().item(), "ok": not bool(bad.any()), "weight_flips": flips}
 
 
-def stream_layerwise(backbone, B, rows, wseed=81, iseed=82):
+def stream_layerwise(backbone, B, rows, wseed=81, iseed=82, H=256, W=256):
     model, sd = _model(backbone, "bf16", wseed, _flag())
-    img, k2d, kc = synth.synth_inputs(B, 256, 256, seed=iseed, crop_range=(256, 256))
+    img, k2d, kc = synth.synth_inputs(B, H, W, seed=iseed, crop_range=(W, H))
     img_d = img.cuda()
     eng = model.engine_for(img_d)
     names = [n for n, _, _ in eng.schema()]

@@ -31,7 +31,7 @@ def layerwise(backbone, dtype, B, H, W, rows, wseed=71, iseed=72, plan_flags=0):
     todo = [i for i, d in enumerate(descs) if d.backbone and d.kind in (0, 1, 2, 3)]
     stream = torch.cuda.current_stream().cuda_stream
     bf = dtype == "bf16"
-    worst, kernels, n_checked, flips, n_up, n_planes = {}, set(), 0, 0, 0, 0
+    worst, kernels, n_checked, flips, n_up, n_planes, resized = {}, set(), 0, 0, 0, 0, set()
     for cp in sorted(set(descs[i].checkpoint for i in todo)):
         eng.forward_prefix(img_d, cp, stream)
         torch.cuda.synchronize()
@@ -59,6 +59,7 @@ def layerwise(backbone, dtype, B, H, W, rows, wseed=71, iseed=72, plan_flags=0):
                     want = op_oracle.maxpool(take(0, d.H, d.W, d.Cin, d.in_dtype))
                 else:
                     add = take(4, d.Ho, d.Wo, d.Cout, d.out_dtype) if d.has_residual else None
+                    resized.add((d.H, d.W, d.Ho, d.Wo))
                     want = op_oracle.resize(take(0, d.H, d.W, d.Cin, d.in_dtype), d.Ho, d.Wo, out_bf, add)
             r = op_oracle.compare(got, want, out_bf, mass, term)
             flips += r["weight_flips"]
@@ -79,6 +80,8 @@ def layerwise(backbone, dtype, B, H, W, rows, wseed=71, iseed=72, plan_flags=0):
     assert n_checked == len(todo) and n_checked > 85
     layerwise.fused_upsample_adds = n_up
     layerwise.planes_consumers = n_planes
+    layerwise.resizes = resized                        # (source H, W, result H, W) of every resize checked
+    layerwise.worst = worst
     return kernels
 
 
@@ -121,7 +124,7 @@ def test_layerwise_small_batches_take_the_other_kernels():
     layerwise("cpn", "fp32", 2, 384, 288, [0, 1])
 
 
-def lifter_layerwise(backbone, B, H, W, frames, wseed=73, iseed=74):
+def lifter_layerwise(backbone, B, H, W, frames, wseed=73, iseed=74, kcrop=None):
     """The lifter half of the tight check under compute_dtype = bf16: every LayerNorm (bf16 writer), attention (bf16 writer) and qkv / proj /
     fc1 + GELU / fc2 launch of the three block groups (pose_dformer.py:15-79) recomputed on the CPU from the rows the ENGINE produced.
     proj and fc2 update the token stream in place, so an op's operands are read after capf_forward_prefix(i) and its result after
@@ -129,6 +132,8 @@ def lifter_layerwise(backbone, B, H, W, frames, wseed=73, iseed=74):
     same or the adjacent bf16 number."""
     model, sd = _model(backbone, "bf16", wseed)
     img, k2d, kc = synth.synth_inputs(B, H, W, seed=iseed, crop_range=(W, H))
+    if kcrop is not None:
+        kc = kcrop
     img_d, k2d_d, kc_d = img.cuda(), k2d.cuda(), kc.cuda()
     out = torch.empty(B, 1, 17, 3, device="cuda")
     eng = model.engine_for(img_d)
