@@ -502,17 +502,15 @@ def test_row_halo_engine_path_agrees_with_the_direct_bf16_kernels():
         assert rel < 1.5e-2
 
 
-def test_conv_fuzz_against_torch():
-    """Seeded random conv shapes (ragged M and N, odd image sizes, stride 1 / 2, 1x1 / 3x3 / 5x5, channel counts
-    that are and are not multiples of 32, with and without bias / residual / ReLU) against PyTorch on the CPU, and
-    the same problems again as grouped launches (bit-identical to the single launches)."""
-    from capf import lib as capf
+def _ri(rng):
+    return lambda lo, hi: int(torch.randint(lo, hi + 1, (1,), generator=rng))
+
+
+def conv_fuzz_problems():
+    """the seeded problems of test_conv_fuzz_against_torch (also driven by tests/test_gpu_op_guards.py):
+    (case, ci, co, ks, st, H, W, B, act, res, x NCHW, w, bn) each"""
     rng = torch.Generator().manual_seed(20260928)
-
-    def ri(lo, hi):
-        return int(torch.randint(lo, hi + 1, (1,), generator=rng))
-
-    probs, singles = [], []
+    ri = _ri(rng)
     for case in range(36):
         ci = 4 * ri(1, 40)
         co = 4 * ri(1, 40) if case % 5 else ri(1, 67)          # every fifth case: N not a multiple of 4
@@ -524,6 +522,16 @@ def test_conv_fuzz_against_torch():
         w = torch.randn(co, ci, ks, ks, generator=rng) / (ci * ks * ks) ** 0.5
         bn = (torch.rand(co, generator=rng) + 0.5, torch.randn(co, generator=rng) * 0.1,
               torch.randn(co, generator=rng) * 0.1, torch.rand(co, generator=rng) * 0.4 + 0.8)
+        yield case, ci, co, ks, st, H, W, B, act, res, x, w, bn
+
+
+def test_conv_fuzz_against_torch():
+    """Seeded random conv shapes (ragged M and N, odd image sizes, stride 1 / 2, 1x1 / 3x3 / 5x5, channel counts
+    that are and are not multiples of 32, with and without bias / residual / ReLU) against PyTorch on the CPU, and
+    the same problems again as grouped launches (bit-identical to the single launches)."""
+    from capf import lib as capf
+    probs, singles = [], []
+    for case, ci, co, ks, st, H, W, B, act, res, x, w, bn in conv_fuzz_problems():
         want = F.batch_norm(F.conv2d(x, w, None, st, ks // 2), bn[2], bn[3], bn[0], bn[1], False, 0.0, 1e-5)
         r = torch.randn_like(want) if res else None
         if res:
@@ -545,14 +553,10 @@ def test_conv_fuzz_against_torch():
             assert torch.equal(a, b)
 
 
-def test_linear_fuzz_against_torch():
-    """Seeded random (M, N, K) with K % 32 == 0, ragged M / N, bias / residual / ReLU / GELU against PyTorch (CPU)."""
-    from capf import lib as capf
+def linear_fuzz_problems():
+    """the seeded problems of test_linear_fuzz_against_torch: (case, M, N, K, act, res, has_b, x, w, b, r) each"""
     rng = torch.Generator().manual_seed(777)
-
-    def ri(lo, hi):
-        return int(torch.randint(lo, hi + 1, (1,), generator=rng))
-
+    ri = _ri(rng)
     for case in range(24):
         M, N, K = ri(1, 700), ri(1, 300), 32 * ri(1, 20)
         act, res, has_b = ri(0, 2), bool(ri(0, 1)), bool(ri(0, 1))
@@ -560,6 +564,13 @@ def test_linear_fuzz_against_torch():
         w = torch.randn(N, K, generator=rng) / K ** 0.5
         b = torch.randn(N, generator=rng) if has_b else None
         r = torch.randn(M, N, generator=rng) if res else None
+        yield case, M, N, K, act, res, has_b, x, w, b, r
+
+
+def test_linear_fuzz_against_torch():
+    """Seeded random (M, N, K) with K % 32 == 0, ragged M / N, bias / residual / ReLU / GELU against PyTorch (CPU)."""
+    from capf import lib as capf
+    for case, M, N, K, act, res, has_b, x, w, b, r in linear_fuzz_problems():
         want = F.linear(x, w, b)
         if res:
             want = want + r                      # epilogue order of the kernel: + bias, + residual, activation
@@ -705,16 +716,10 @@ def test_grouped_bf16_launch_with_row_halo_tiles_matches_torch(chans, B):
         assert (got - want).abs().max().item() <= tol
 
 
-def test_row_halo_fuzz_against_torch():
-    """Seeded random 3x3 problems through the row-halo kernel: every chunk width (Cin multiples of 32 / 48 / 64), ragged Cout
-    (multiples of 4 and of 8), image sizes from 1x1 up, widths that are not multiples of anything, with and without residual /
-    ReLU -- tiles of 126 flat pixels cross image rows and images in almost every case."""
-    from capf import lib as capf
+def row_halo_fuzz_problems():
+    """the seeded problems of test_row_halo_fuzz_against_torch: (case, ci, co, H, W, B, act, res, x NCHW bf16, w, bnp) each"""
     rng = torch.Generator().manual_seed(20260929)
-
-    def ri(lo, hi):
-        return int(torch.randint(lo, hi + 1, (1,), generator=rng))
-
+    ri = _ri(rng)
     for case in range(24):
         ci = (32, 48, 64, 96, 128, 160, 192)[ri(0, 6)]
         co = 4 * ri(1, 50) if case % 3 else 8 * ri(1, 30)
@@ -724,6 +729,15 @@ def test_row_halo_fuzz_against_torch():
         w = torch.randn(co, ci, 3, 3, generator=rng) / (ci * 9) ** 0.5
         bnp = (torch.rand(co, generator=rng) + 0.5, torch.randn(co, generator=rng) * 0.1, torch.randn(co, generator=rng) * 0.1,
                torch.rand(co, generator=rng) * 0.4 + 0.8)
+        yield case, ci, co, H, W, B, act, res, x, w, bnp
+
+
+def test_row_halo_fuzz_against_torch():
+    """Seeded random 3x3 problems through the row-halo kernel: every chunk width (Cin multiples of 32 / 48 / 64), ragged Cout
+    (multiples of 4 and of 8), image sizes from 1x1 up, widths that are not multiples of anything, with and without residual /
+    ReLU -- tiles of 126 flat pixels cross image rows and images in almost every case."""
+    from capf import lib as capf
+    for case, ci, co, H, W, B, act, res, x, w, bnp in row_halo_fuzz_problems():
         wp, bias, cw = capf.pack_conv_bf16_rh(w.cuda(), tuple(t.cuda() for t in bnp))
         w_fold = wp.float().cpu().view(co, 3, ci // cw, 3, cw).permute(0, 2, 4, 1, 3).reshape(co, ci, 3, 3)
         want = F.conv2d(x.float(), w_fold, bias.cpu(), 1, 1)
@@ -752,17 +766,10 @@ def _ws_fold(wp, co, ci):
     return w.reshape(co, ci, 3, 3).contiguous()
 
 
-def test_ws_fuzz_against_torch():
-    """Seeded random 3x3 / stride-1 problems through the 2-D halo tile (csrc/igemm_bf16_ws.hip): every channel-slice width (Cout
-    <= 32, multiples of 96, everything else on 64 with padded rows), Cin multiples of 16, image sizes whose tiles are part rows,
-    whole images and several images, ragged last tiles, with and without residual / ReLU -- against fp32 F.conv2d of the same
-    bf16-rounded operands (the folded weights are read back from the packed layout, which also checks the pack)."""
-    from capf import lib as capf
+def ws_fuzz_problems():
+    """the seeded problems of test_ws_fuzz_against_torch: (case, ci, co, H, W, B, act, res, x NCHW bf16, w, bnp) each"""
     rng = torch.Generator().manual_seed(20260930)
-
-    def ri(lo, hi):
-        return int(torch.randint(lo, hi + 1, (1,), generator=rng))
-
+    ri = _ri(rng)
     for case in range(28):
         ci = 16 * ri(1, 14)
         co = (8 * ri(1, 4), 96 * ri(1, 3), 8 * ri(5, 40))[case % 3]
@@ -776,6 +783,16 @@ def test_ws_fuzz_against_torch():
         w = torch.randn(co, ci, 3, 3, generator=rng) / (ci * 9) ** 0.5
         bnp = (torch.rand(co, generator=rng) + 0.5, torch.randn(co, generator=rng) * 0.1, torch.randn(co, generator=rng) * 0.1,
                torch.rand(co, generator=rng) * 0.4 + 0.8)
+        yield case, ci, co, H, W, B, act, res, x, w, bnp
+
+
+def test_ws_fuzz_against_torch():
+    """Seeded random 3x3 / stride-1 problems through the 2-D halo tile (csrc/igemm_bf16_ws.hip): every channel-slice width (Cout
+    <= 32, multiples of 96, everything else on 64 with padded rows), Cin multiples of 16, image sizes whose tiles are part rows,
+    whole images and several images, ragged last tiles, with and without residual / ReLU -- against fp32 F.conv2d of the same
+    bf16-rounded operands (the folded weights are read back from the packed layout, which also checks the pack)."""
+    from capf import lib as capf
+    for case, ci, co, H, W, B, act, res, x, w, bnp in ws_fuzz_problems():
         wp, bias = capf.pack_conv_bf16_ws(w.cuda(), tuple(t.cuda() for t in bnp))
         w_fold = _ws_fold(wp, co, ci)
         want = F.conv2d(x.float(), w_fold, bias.cpu(), 1, 1)
@@ -889,19 +906,10 @@ def _x3_check(got_nhwc, x, w_fold, bias, res, act, what, direct=None):
 _x3_check.pairs = []
 
 
-def test_f32x3_fuzz_against_torch():
-    """Seeded random 3x3 / stride-1 fp32 problems through the split-fp32 tile (csrc/igemm_f32x3_ws.hip): Cin multiples of 16, Cout
-    multiples of 4 (ragged last channel slice), widths that are and are not multiples of 16 (closed-form and dealt-out pixel-to-column
-    assignment), part rows / whole images / several images per tile, ragged last tiles, with and without residual / ReLU -- against an
-    fp64 F.conv2d of the same fp32 operands with full-mantissa values.  The folded weights are read back from the packed pieces (which
-    checks the pack: the three pieces must add up to the fp32 fold) and compared with the CPU's own BatchNorm fold."""
-    from capf import lib as capf
-    rng = torch.Generator().manual_seed(20261001)
-
-    def ri(lo, hi):
-        return int(torch.randint(lo, hi + 1, (1,), generator=rng))
-
-    worst = 0.0
+def split_tile_fuzz_shapes(rng):
+    """the 30 seeded shapes test_f32x3_fuzz_against_torch and test_f32h2_fuzz_against_torch share, drawn from `rng` between the caller's own
+    draws of the tensors: (case, ci, co, H, W, B, act, res) each"""
+    ri = _ri(rng)
     for case in range(30):
         ci = 16 * ri(1, 12)
         co = 4 * ri(1, 48)
@@ -915,16 +923,36 @@ def test_f32x3_fuzz_against_torch():
         if case == 8:
             H, W, B, ci, co = 16, 16, 3, 128, 128
         act, res = ri(0, 1), bool(ri(0, 1))
+        yield case, ci, co, H, W, B, act, res
+
+
+def f32x3_fuzz_problems():
+    """the seeded problems of test_f32x3_fuzz_against_torch (test_f32h2_fuzz_against_torch draws the same through _h2_problem):
+    (case, ci, co, H, W, B, act, res, x NCHW, w, bnp, r) each"""
+    rng = torch.Generator().manual_seed(20261001)
+    for case, ci, co, H, W, B, act, res in split_tile_fuzz_shapes(rng):
         x = torch.randn(B, ci, H, W, generator=rng) * torch.rand(B, ci, H, W, generator=rng).pow(3)     # magnitudes over several binades
         w = torch.randn(co, ci, 3, 3, generator=rng) / (ci * 9) ** 0.5
         bnp = (torch.rand(co, generator=rng) + 0.5, torch.randn(co, generator=rng) * 0.1, torch.randn(co, generator=rng) * 0.1,
                torch.rand(co, generator=rng) * 0.4 + 0.8)
+        r = torch.randn(B, co, H, W, generator=rng) if res else None
+        yield case, ci, co, H, W, B, act, res, x, w, bnp, r
+
+
+def test_f32x3_fuzz_against_torch():
+    """Seeded random 3x3 / stride-1 fp32 problems through the split-fp32 tile (csrc/igemm_f32x3_ws.hip): Cin multiples of 16, Cout
+    multiples of 4 (ragged last channel slice), widths that are and are not multiples of 16 (closed-form and dealt-out pixel-to-column
+    assignment), part rows / whole images / several images per tile, ragged last tiles, with and without residual / ReLU -- against an
+    fp64 F.conv2d of the same fp32 operands with full-mantissa values.  The folded weights are read back from the packed pieces (which
+    checks the pack: the three pieces must add up to the fp32 fold) and compared with the CPU's own BatchNorm fold."""
+    from capf import lib as capf
+    worst = 0.0
+    for case, ci, co, H, W, B, act, res, x, w, bnp, r in f32x3_fuzz_problems():
         wp, bias = capf.pack_conv_f32x3(w.cuda(), tuple(t.cuda() for t in bnp))
         w_fold = _x3_fold(wp, co, ci)
         sc = bnp[0].double() / torch.sqrt(bnp[3].double() + 1e-5)
         assert torch.allclose(w_fold, w.double() * sc.view(-1, 1, 1, 1), rtol=1e-6, atol=1e-9)
         assert torch.equal(w_fold.float().double(), w_fold)                    # an fp32 number: the pieces lose nothing
-        r = torch.randn(B, co, H, W, generator=rng) if res else None
         got, = capf.conv_nhwc_f32x3_group([(x.permute(0, 2, 3, 1).contiguous().cuda(), wp, bias, act,
                                             r.permute(0, 2, 3, 1).contiguous().cuda() if res else None, co)])
         wd, bd = capf.pack_conv(w.cuda(), tuple(t.cuda() for t in bnp))
@@ -1046,24 +1074,8 @@ def test_f32h2_fuzz_against_torch():
     pieces of a weight, unscaled, are within 2^-23 of the fp32 fold; the scales are powers of two."""
     from capf import lib as capf
     rng = torch.Generator().manual_seed(20261001)
-
-    def ri(lo, hi):
-        return int(torch.randint(lo, hi + 1, (1,), generator=rng))
-
     worst, n0 = 0.0, len(_x3_check.pairs)
-    for case in range(30):
-        ci = 16 * ri(1, 12)
-        co = 4 * ri(1, 48)
-        H, W, B = ri(1, 40), ri(1, 70), ri(1, 5)
-        if case == 5:
-            H, W, B = 8, 8, 9
-        if case == 6:
-            H, W, B = 64, 64, 2
-        if case == 7:
-            H, W, B = 12, 9, 5
-        if case == 8:
-            H, W, B, ci, co = 16, 16, 3, 128, 128
-        act, res = ri(0, 1), bool(ri(0, 1))
+    for case, ci, co, H, W, B, act, res in split_tile_fuzz_shapes(rng):
         x, w, bnp, wp, bias, w_fold, r, xg, rg = _h2_problem(rng, ci, co, H, W, B, act, res)
         got, = capf.conv_nhwc_f32h2_group([(xg, wp, bias, act, rg, co)])
         wd, bd = capf.pack_conv(w.cuda(), tuple(t.cuda() for t in bnp))
@@ -1403,18 +1415,10 @@ def _h2g_conv_check(got_nhwc, x, w_fold, bias, res, act, stride, what, direct):
     return err, err32
 
 
-def test_f32h2g_conv_fuzz_against_torch():
-    """1x1 / 3x3 / 5x5 convs, stride 1 and 2, channel counts that are and are not multiples of 32 (block-uniform and per-thread tap walk),
-    ragged M and N tiles, with and without residual / ReLU, through the two-fp16-piece GEMM (csrc/igemm_f32h2.hip) against an fp64 F.conv2d
-    of the same fp32 operands -- 1e-6 of the sum of |terms|, and at most 2 x the error of this library's direct fp32 MFMA kernel on the same
-    problem.  The pack is read back: (piece 0 + piece 1) / scale is within 2^-23 of the fp32 fold the fp32 pack holds."""
-    from capf import lib as capf
+def f32h2g_conv_fuzz_problems():
+    """the seeded problems of test_f32h2g_conv_fuzz_against_torch: (case, ks, stride, ci, co, H, W, B, act, res, x NCHW, w, bnp, r) each"""
     rng = torch.Generator().manual_seed(20261002)
-
-    def ri(lo, hi):
-        return int(torch.randint(lo, hi + 1, (1,), generator=rng))
-
-    worst, worst32 = 0.0, 0.0
+    ri = _ri(rng)
     for case in range(24):
         ks = (1, 3, 3, 5)[ri(0, 3)]
         stride = ri(1, 2)
@@ -1426,6 +1430,20 @@ def test_f32h2g_conv_fuzz_against_torch():
         w = torch.randn(co, ci, ks, ks, generator=rng) / (ci * ks * ks) ** 0.5
         bnp = (torch.rand(co, generator=rng) + 0.5, torch.randn(co, generator=rng) * 0.1, torch.randn(co, generator=rng) * 0.1,
                torch.rand(co, generator=rng) * 0.4 + 0.8)
+        pad = ks // 2
+        Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+        r = torch.randn(B, co, Ho, Wo, generator=rng) if res else None
+        yield case, ks, stride, ci, co, H, W, B, act, res, x, w, bnp, r
+
+
+def test_f32h2g_conv_fuzz_against_torch():
+    """1x1 / 3x3 / 5x5 convs, stride 1 and 2, channel counts that are and are not multiples of 32 (block-uniform and per-thread tap walk),
+    ragged M and N tiles, with and without residual / ReLU, through the two-fp16-piece GEMM (csrc/igemm_f32h2.hip) against an fp64 F.conv2d
+    of the same fp32 operands -- 1e-6 of the sum of |terms|, and at most 2 x the error of this library's direct fp32 MFMA kernel on the same
+    problem.  The pack is read back: (piece 0 + piece 1) / scale is within 2^-23 of the fp32 fold the fp32 pack holds."""
+    from capf import lib as capf
+    worst, worst32 = 0.0, 0.0
+    for case, ks, stride, ci, co, H, W, B, act, res, x, w, bnp, r in f32h2g_conv_fuzz_problems():
         bn_cuda = tuple(t.cuda() for t in bnp)
         wd, bd = capf.pack_conv(w.cuda(), bn_cuda)                                   # the fp32 pack: [Cout][Kpad], k = (kh, kw, ci)
         k = ks * ks * ci
@@ -1437,9 +1455,6 @@ def test_f32h2g_conv_fuzz_against_torch():
         cmax = flat.abs().amax(dim=1, keepdim=True)
         assert ((w_h2 - flat).abs() <= 2.0 ** -23 * flat.abs() + 2.0 ** -38 * cmax).all()
         assert torch.equal(torch.log2(winv), torch.log2(winv).round())
-        pad = ks // 2
-        Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
-        r = torch.randn(B, co, Ho, Wo, generator=rng) if res else None
         xg = x.permute(0, 2, 3, 1).contiguous().cuda()
         rg = r.permute(0, 2, 3, 1).contiguous().cuda() if res else None
         got = capf.conv_nhwc_f32h2g(xg, wp, bias, ks, stride, act, rg, co)
