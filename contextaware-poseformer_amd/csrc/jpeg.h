@@ -103,15 +103,17 @@ __device__ __forceinline__ void jpeg_idct_block(const short* __restrict__ coef, 
 }
 
 // chroma sample at full resolution: jdsample.c fullsize / h2v1_fancy / h2v2_fancy with libjpeg's edge handling (context rows replicated at the
-// top and below the component's last true row; first / last column special-cased)
+// top and below the component's last true row; first / last column special-cased).  jinit_upsampler picks the fancy routines only for a
+// component with downsampled_width > 2; a narrower one goes through h2v1_upsample / h2v2_upsample, which replicate each sample -- no
+// filter along either axis, no context row.
 __device__ __forceinline__ int jpeg_chroma(const unsigned char* pl, int pw, int dw, int dh, int hs, int vs, int x, int y, int cox, int coy) {
     // (x, y): image coordinates, which the edge rules are about; pl holds the plane from chroma sample (cox, coy) on
     if (hs == 1 && vs == 1) return pl[(long)(y - coy) * pw + (x - cox)];
+    if (dw <= 2) return pl[(long)(y / vs - coy) * pw + (x / hs - cox)];
     const int cx = x >> 1, odd = x & 1, lx = cx - cox;
     if (vs == 1) {                                      // h2v1
         const unsigned char* r = pl + (long)(y - coy) * pw;
         const int v = r[lx];
-        if (dw == 1) return v;
         if (!odd) return cx == 0 ? v : (v * 3 + r[lx - 1] + 1) >> 2;
         return cx == dw - 1 ? v : (v * 3 + r[lx + 1] + 2) >> 2;
     }

@@ -11,7 +11,13 @@
 //     rounding) and h2v2 (9/16, 3/16, 3/16, 1/16 with +8 / +7), edge rows / columns replicated;
 //   * colour: jdcolor.c ycc_rgb_convert: 16-bit fixed point tables, R = y + 1.40200 cr, G = y - 0.34414 cb - 0.71414 cr, B = y + 1.77200 cb.
 // Supported: baseline / extended sequential Huffman (SOF0 / SOF1), 8 bit, 1 or 3 components in ONE interleaved scan, sampling
-// 1x1 (4:4:4), 2x1 (4:2:2), 2x2 (4:2:0) with 1x1 chroma, restart intervals.  Progressive / arithmetic / CMYK: CAPF_ERR_UNSUPPORTED.
+// 1x1 (4:4:4), 2x1 (4:2:2), 2x2 (4:2:0) with 1x1 chroma, restart intervals; three components mean YCbCr by libjpeg's rule (a JFIF APP0,
+// or an Adobe APP14 with transform 1 / 2, or neither and component ids other than 'R','G','B').  Progressive / arithmetic / CMYK, and
+// three-component RGB files (no JFIF and Adobe transform 0, or no JFIF, no Adobe and ids 'R','G','B'): CAPF_ERR_UNSUPPORTED.  A
+// quantisation-table selector above 3 in SOF: CAPF_ERR_INVALID.  Chroma narrower than three samples (downsampled_width <= 2) is replicated,
+// not filtered, as jinit_upsampler chooses.
+// Not pinned beyond IDCT outputs in [-512, 511]: the range limit here is the C code's range_limit[x & 1023], which wraps farther values;
+// libjpeg-turbo's SIMD IDCT is believed to saturate them.  No encoder makes such blocks from 8-bit pixels (EXPERIMENTS R18.2).
 #include <string.h>
 
 #include <vector>
@@ -26,7 +32,8 @@ namespace capf {
 int jpeg_parse(const unsigned char* d, size_t n, JpegHeader& h) {
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return CAPF_ERR_INVALID;
     size_t p = 2;
-    bool have_sof = false;
+    bool have_sof = false, saw_jfif = false, saw_adobe = false;
+    int adobe_transform = 0;
     while (p + 4 <= n) {
         if (d[p] != 0xFF) return CAPF_ERR_INVALID;
         while (p < n && d[p] == 0xFF) ++p;            // fill bytes
@@ -44,7 +51,8 @@ int jpeg_parse(const unsigned char* d, size_t n, JpegHeader& h) {
             h.H = (s[1] << 8) | s[2]; h.W = (s[3] << 8) | s[4]; h.nc = s[5];
             if (h.W <= 0 || h.H <= 0 || (h.nc != 1 && h.nc != 3) || sl < (size_t)(6 + 3 * h.nc)) return CAPF_ERR_UNSUPPORTED;
             for (int i = 0; i < h.nc; ++i) {
-                h.c[i].id = s[6 + 3 * i]; h.c[i].h = s[7 + 3 * i] >> 4; h.c[i].v = s[7 + 3 * i] & 15; h.c[i].tq = s[8 + 3 * i] & 3;
+                h.c[i].id = s[6 + 3 * i]; h.c[i].h = s[7 + 3 * i] >> 4; h.c[i].v = s[7 + 3 * i] & 15; h.c[i].tq = s[8 + 3 * i];
+                if (h.c[i].tq > 3) return CAPF_ERR_INVALID;   // (libjpeg: "no quantization table"; T.81 B.2.2 allows 0..3)
             }
             have_sof = true;
         } else if (m == 0xC2 || (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC)) {
@@ -82,6 +90,10 @@ int jpeg_parse(const unsigned char* d, size_t n, JpegHeader& h) {
                 h.have_ht[tc][th] = true;
                 q += 17 + cnt;
             }
+        } else if (m == 0xE0) {                        // jdmarker.c examine_app0 / examine_app14: what default_decompress_parms goes by
+            if (len >= 16 && memcmp(s, "JFIF\0", 5) == 0) saw_jfif = true;
+        } else if (m == 0xEE) {
+            if (len >= 14 && memcmp(s, "Adobe", 5) == 0) { saw_adobe = true; adobe_transform = s[11]; }
         } else if (m == 0xDD) {
             if (sl < 2) return CAPF_ERR_INVALID;
             h.restart = (s[0] << 8) | s[1];
@@ -98,6 +110,13 @@ int jpeg_parse(const unsigned char* d, size_t n, JpegHeader& h) {
         p += len;
     }
     if (!have_sof || !h.scan_off) return CAPF_ERR_INVALID;
+    // colour space of a three-component file (jdapimin.c default_decompress_parms): JFIF says YCbCr; else Adobe's transform byte decides
+    // (0: RGB, anything else: YCbCr); else the component ids do ('R','G','B': RGB, anything else: YCbCr).  RGB is stored unconverted --
+    // the colour kernel always converts, so such a file is refused, not misdecoded.
+    if (h.nc == 3 && !saw_jfif) {
+        const bool rgb_ids = h.c[0].id == 'R' && h.c[1].id == 'G' && h.c[2].id == 'B';
+        if (saw_adobe ? adobe_transform == 0 : rgb_ids) return CAPF_ERR_UNSUPPORTED;
+    }
     if (h.nc == 1) { h.c[0].h = h.c[0].v = 1; }
     else {
         if (h.c[1].h != 1 || h.c[1].v != 1 || h.c[2].h != 1 || h.c[2].v != 1) return CAPF_ERR_UNSUPPORTED;

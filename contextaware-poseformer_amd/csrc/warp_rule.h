@@ -85,6 +85,8 @@ __host__ __device__ inline bool warp_source_rect(int W, int H, const double* m, 
 // the h2v1 / h2v2 triangle filters (jpeg.h jpeg_chroma) read the chroma sample next to the pixel's own -- left of an even column, right
 // of an odd one, likewise for rows under h2v2 -- and replicate only at the true image edge.  The neighbouring sample covers the pixel
 // next to the rectangle, so one pixel of margin reaches exactly the MCUs the filter reads.  mcu = [mx0, my0, mx1, my1), MCU units.
+// Chroma narrower than three samples is replicated, not filtered (jpeg_chroma, downsampled_width <= 2), and reads no neighbour; the
+// margin is kept there all the same -- such an image is one MCU wide, and a margin that is too large only keeps an MCU it need not.
 __host__ __device__ inline void warp_mcu_rect(int W, int H, int hs, int vs, const int rect[4], int mcu[4]) {
     mcu[0] = mcu[1] = mcu[2] = mcu[3] = 0;
     if (rect[0] >= rect[2] || rect[1] >= rect[3]) return;

@@ -645,8 +645,9 @@ int capf_pck_counts(void* stream, const float* pred, const float* gt, int n, int
  *   integer IDCT (jidctint.c), "fancy" triangle upsampling (jdsample.c), 16-bit fixed point colour conversion (jdcolor.c) -- which is what
  *   cv2.imread and Pillow run: the result is bit-exact against Pillow's libjpeg-turbo decode (tests/test_jpeg.py; OpenCV itself is not
  *   in the image).  Baseline / extended sequential Huffman, 8 bit, grey or YCbCr in one interleaved scan, 4:4:4 / 4:2:2 / 4:2:0, restart
- *   intervals; anything else (progressive, arithmetic, CMYK, other sampling) returns CAPF_ERR_UNSUPPORTED and the caller keeps its host
- *   decoder.  capf_jpeg_info: geometry + the scratch bytes capf_jpeg_decode needs (device memory, 16-byte aligned).  capf_jpeg_decode
+ *   intervals; anything else (progressive, arithmetic, CMYK, other sampling, and three-component files libjpeg takes for RGB: no JFIF
+ *   APP0 and an Adobe APP14 with transform 0, or neither marker and component ids 'R','G','B') returns CAPF_ERR_UNSUPPORTED and the
+ *   caller keeps its host decoder.  capf_jpeg_info: geometry + the scratch bytes capf_jpeg_decode needs (device memory, 16-byte aligned).  capf_jpeg_decode
  *   enqueues on `stream` and waits for the coefficient upload (it reuses a per-thread host staging buffer): a loader-side call, never
  *   part of capf_forward.  capf_jpeg_coefficients: the host half alone -- quantised coefficients in natural order, component after
  *   component, blocks [rows][cols][64] over the MCU-padded image (no GPU needed).                                                      */

@@ -3,7 +3,8 @@ second half of cv2.imread / PIL.Image.open(...).convert for a baseline JPEG (ref
 cv2.imread(path, IMREAD_COLOR | IMREAD_IGNORE_ORIENTATION)).  The reference delegates the decode to OpenCV -> libjpeg(-turbo); neither is part
 of /root/reference, so the algorithm is restated from libjpeg's published sources (IJG libjpeg 6b / libjpeg-turbo 3.x):
     jidctint.c   jpeg_idct_islow        13-bit fixed point inverse DCT, two passes, range limit (JDCT_ISLOW is the default dct_method)
-    jdsample.c   h2v1 / h2v2 fancy      triangle-filter chroma upsampling (do_fancy_upsampling = TRUE is the default)
+    jdsample.c   h2v1 / h2v2 fancy      triangle-filter chroma upsampling (do_fancy_upsampling = TRUE is the default); jinit_upsampler takes
+                                        it only for downsampled_width > 2 -- narrower chroma goes through h2v1 / h2v2_upsample: replicated
     jdcolor.c    ycc_rgb_convert        16-bit fixed point YCbCr -> RGB
     jdmainct.c                          context rows: the row above the first and below the last TRUE chroma row are replicas
 PINNED: tests/test_jpeg.py checks this restatement bit for bit against Pillow 12.2's bundled libjpeg-turbo (the third-party decoder the
@@ -57,6 +58,8 @@ def upsample_fancy(pl, dw, dh, hs, vs, W, H):
     p = pl[:dh, :dw].astype(np.int64)
     if hs == 1 and vs == 1:
         return p[:H, :W]
+    if dw <= 2:                                                                       # jinit_upsampler: fancy only when downsampled_width > 2;
+        return np.repeat(np.repeat(p, vs, 0), hs, 1)[:H, :W]                         # h2v1_upsample / h2v2_upsample replicate
     if vs == 1:
         prev = np.concatenate([p[:, :1], p[:, :-1]], 1)
         nxt = np.concatenate([p[:, 1:], p[:, -1:]], 1)

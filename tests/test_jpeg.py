@@ -22,27 +22,10 @@ def _golden():
 
 
 def _quant_tables(data):
-    """natural-order quantisation tables per component, parsed from the file's DQT / SOF segments (independent of Pillow)."""
-    import jpeg_oracle as jo
-    tabs, comp_tq, p = {}, [], 2
-    while p < len(data):
-        assert data[p] == 0xFF
-        m, ln = data[p + 1], (data[p + 2] << 8) | data[p + 3]
-        seg = data[p + 4:p + 2 + ln]
-        if m == 0xDB:
-            q = 0
-            while q < len(seg):
-                assert seg[q] >> 4 == 0
-                t = np.zeros(64, np.int64)
-                t[jo.ZIGZAG] = np.frombuffer(bytes(seg[q + 1:q + 65]), np.uint8)
-                tabs[seg[q] & 15] = t
-                q += 65
-        elif m in (0xC0, 0xC1):
-            comp_tq = [seg[6 + 3 * i + 2] for i in range(seg[5])]
-        elif m == 0xDA:
-            break
-        p += 2 + ln
-    return [tabs[t] for t in comp_tq]
+    """natural-order quantisation tables per component, parsed from the file's DQT / SOF segments (independent of Pillow): the tests' one
+    marker parser, tests/jpeg_writer.py, which also takes 16-bit tables and fill bytes."""
+    import jpeg_writer
+    return jpeg_writer.quant_tables(data)
 
 
 def _oracle_decode(data):
@@ -117,6 +100,17 @@ def test_files_outside_the_supported_subset_are_refused_not_misdecoded():
     good = _golden()["rgb444_q90:jpeg"].tobytes()
     with pytest.raises(CapfError):
         capf.jpeg_info(good[:40])                                       # truncated inside the tables
+    # three-component files libjpeg takes for RGB (no colour conversion; this path always converts) and a quantisation-table selector of 5
+    s = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_streams.npz"), allow_pickle=False)
+    refused = [i for i, n in enumerate(s["names"]) if str(n).startswith("refused/")]
+    assert len(refused) == 9
+    for i in refused:
+        with pytest.raises(CapfError):
+            capf.jpeg_info(s["jpeg"][s["jpeg_off"][i]:s["jpeg_off"][i + 1]].tobytes())
+    buf = io.BytesIO()
+    Image.fromarray(img).save(buf, "JPEG", quality=80, keep_rgb=True)
+    with pytest.raises(CapfError):
+        capf.jpeg_info(buf.getvalue())                                  # Adobe APP14 transform 0, ids R, G, B
 
 
 def _dht_segments(data):
