@@ -36,6 +36,8 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_op_stream_class",
     "capf_set_features", "capf_lifter_forward_train", "capf_backward_maps",
     "capf_set_map_grad_mode", "capf_map_grad_mode",
+    "capf_forward_u8", "capf_backbone_forward_u8", "capf_forward_train_u8", "capf_preprocess_points", "capf_input_rule_host",
+    "capf_op_conv_u8", "capf_op_conv_u8_kernel_name", "capf_op_conv_stem_kernel_name",
 ]
 
 
@@ -227,6 +229,17 @@ def load_library():
     lib.capf_keypoints_loss.argtypes = [P, c_int, P, P, P, c_int, c_int, c_float, P, P]
     lib.capf_fliptest_fuse_swap.argtypes = [P, P, c_int, c_int, POINTER(c_int32), P]
     lib.capf_pck_counts.argtypes = [P, P, P, c_int, c_int, c_int, c_double, P, c_int, P, P, P]
+    F3 = POINTER(c_float)
+    lib.capf_forward_u8.argtypes = [H, P, P, F3, F3, c_int, P, P, c_int, P]
+    lib.capf_backbone_forward_u8.argtypes = [H, P, P, F3, F3, c_int, c_int]
+    lib.capf_forward_train_u8.argtypes = [H, P, P, F3, F3, c_int, P, P, c_int, P, P]
+    lib.capf_preprocess_points.argtypes = [P, c_int, c_int, P, P, P, P, P, P]
+    lib.capf_input_rule_host.argtypes = [P, c_int, c_int, F3, F3, P]
+    lib.capf_op_conv_u8.argtypes = [P, P, P, P, P] + [c_int] * 8 + [F3, F3, c_int]
+    lib.capf_op_conv_u8_kernel_name.argtypes = [c_int] * 8
+    lib.capf_op_conv_u8_kernel_name.restype = c_char_p
+    lib.capf_op_conv_stem_kernel_name.argtypes = [c_int] * 7
+    lib.capf_op_conv_stem_kernel_name.restype = c_char_p
     _lib = lib
     return lib
 
@@ -315,6 +328,31 @@ class Engine:
         self._check(self.lib.capf_forward(self.h, c_void_p(stream), c_void_p(images.data_ptr()),
                                           c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B,
                                           c_void_p(out.data_ptr())), "forward")
+
+    # ---- the same from uint8 BGR crops [Bsrc,H,W,3] (capf_forward_u8 ...): mode 0 as is, 1 mirrored, 2 flip-test pair (2 * Bsrc engine frames);
+    # mean / std: (c_float * 3) arrays (input_constants), std None = mean only.  k2d / kcrop / out hold the ENGINE frames
+    @staticmethod
+    def _u8_batch(images_u8, mode):
+        return images_u8.shape[0] * (2 if mode == 2 else 1)
+
+    def forward_u8(self, images_u8, mean, std, mode, k2d, kcrop, out, stream):
+        B = self._u8_batch(images_u8, mode)
+        self.ensure_workspace(B)
+        self._check(self.lib.capf_forward_u8(self.h, c_void_p(stream), c_void_p(images_u8.data_ptr()), mean, std, int(mode),
+                                             c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B, c_void_p(out.data_ptr())), "forward_u8")
+
+    def backbone_forward_u8(self, images_u8, mean, std, mode, stream):
+        B = self._u8_batch(images_u8, mode)
+        self.ensure_workspace(B)
+        self._check(self.lib.capf_backbone_forward_u8(self.h, c_void_p(stream), c_void_p(images_u8.data_ptr()), mean, std, int(mode), B),
+                    "backbone_forward_u8")
+
+    def forward_train_u8(self, images_u8, mean, std, mode, k2d, kcrop, out, stream, masks=None):
+        B = self._u8_batch(images_u8, mode)
+        self.ensure_workspace(B)
+        self._check(self.lib.capf_forward_train_u8(self.h, c_void_p(stream), c_void_p(images_u8.data_ptr()), mean, std, int(mode),
+                                                   c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B, c_void_p(out.data_ptr()),
+                                                   c_void_p(masks.data_ptr()) if masks is not None else c_void_p(0)), "forward_train_u8")
 
     # ---- training step
     def grad_layout(self):
@@ -990,6 +1028,67 @@ def preprocess(images_u8, gt, k2d, kcrop, backbone="hrnet_32", mode=0):
     if rc:
         raise CapfError(f"capf_preprocess failed ({rc})")
     return img_out, gt_out, k2d_out, kc_out
+
+
+def input_constants(backbone="hrnet_32"):
+    """(mean, std) of data_prefetcher for a backbone as (c_float * 3) arrays in RGB order; std None: mean only (cpn).  The values preprocess() uses."""
+    import torch
+    if backbone == "cpn":
+        mean, std = torch.tensor([122.7717, 115.9465, 102.9801]) / 255.0, None       # fp32 division, like the reference
+    else:
+        mean, std = torch.tensor(HRNET_MEAN), torch.tensor(HRNET_STD)
+    return (c_float * 3)(*mean.tolist()), ((c_float * 3)(*std.tolist()) if std is not None else None)
+
+
+def preprocess_points(gt, k2d, kcrop, mode=0):
+    """The points half of preprocess() alone (capf_preprocess_points): -> (gt root-relative or None, k2d, kcrop), [2,B,17,2] in mode 2."""
+    import torch
+    B = k2d.shape[0]
+    shape = (2, B, 17, 2) if mode == 2 else (B, 17, 2)
+    k2d_out = torch.empty(shape, dtype=torch.float32, device=k2d.device)
+    kc_out = torch.empty_like(k2d_out)
+    gt_out = torch.empty_like(gt) if gt is not None else None
+    _call("capf_preprocess_points", _stream(k2d), B, int(mode), _p(gt.contiguous()) if gt is not None else c_void_p(0), _p(gt_out),
+          _p(k2d.contiguous()), _p(k2d_out), _p(kcrop.contiguous()), _p(kc_out))
+    return gt_out, k2d_out, kc_out
+
+
+def input_rule_host(u, channel, mean, std=None):
+    """The input normalisation rule on the host (capf_input_rule_host): uint8 numpy array, RGB channel index, mean / std sequences of 3
+    floats (std None: mean only) -> fp32 numpy array of the same shape."""
+    import numpy as np
+    v = np.ascontiguousarray(u, dtype=np.uint8).reshape(-1)
+    out = np.empty(v.size, dtype=np.float32)
+    m3 = (c_float * 3)(*[float(x) for x in mean])
+    s3 = (c_float * 3)(*[float(x) for x in std]) if std is not None else None
+    _call("capf_input_rule_host", v.ctypes.data_as(c_void_p), int(v.size), int(channel), m3, s3, out.ctypes.data_as(c_void_p))
+    return out.reshape(np.shape(u))
+
+
+def op_conv_u8(images_u8, wp, bias, ks, stride=1, act=0, mode=0, mean=HRNET_MEAN, std=HRNET_STD, dtype=F32):
+    """The stem conv from a uint8 BGR image [Bsrc,H,W,3] (CUDA, any alignment; a view at a byte offset of a larger buffer is fine as long as
+    it is dense): wp / bias from pack_conv (Cin = 3) -> [frames,Ho,Wo,Cout] of `dtype` (F32 / BF16 / F16), frames = Bsrc or 2 * Bsrc (mode 2)."""
+    import torch
+    Bsrc, H, W, _ = images_u8.shape
+    if images_u8.dtype != torch.uint8 or not images_u8.is_contiguous():
+        raise CapfError("op_conv_u8 needs a dense uint8 [Bsrc,H,W,3] tensor")
+    frames = Bsrc * (2 if mode == 2 else 1)
+    y = torch.empty(frames, *_out_hw(H, W, ks, stride), wp.shape[0], device=images_u8.device,
+                    dtype=torch.float32 if dtype == F32 else _TORCH16_OF[dtype]())
+    m3 = (c_float * 3)(*[float(x) for x in mean])
+    s3 = (c_float * 3)(*[float(x) for x in std]) if std is not None else None
+    _call("capf_op_conv_u8", _stream(images_u8), _p(images_u8), _p(wp), _p(bias), _p(y), Bsrc, int(mode), H, W, wp.shape[0], ks, stride, act,
+          m3, s3, dtype)
+    return y
+
+
+def op_conv_u8_kernel_name(Bsrc, mode, H, W, cout, ks, stride, dtype=F32):
+    """The kernel op_conv_u8 launches for this problem; stem_kernel_name: the float stem op's (conv_nhwc / conv_nhwc_16 on an fp32 image)."""
+    return load_library().capf_op_conv_u8_kernel_name(Bsrc, mode, H, W, cout, ks, stride, dtype).decode()
+
+
+def stem_kernel_name(B, H, W, cout, ks, stride, dtype=F32):
+    return load_library().capf_op_conv_stem_kernel_name(B, H, W, cout, ks, stride, dtype).decode()
 
 
 # the 3DHP skeleton's mirror table: joints_left [5, 6, 7, 11, 12, 13] <-> joints_right [2, 3, 4, 8, 9, 10] (ContextPose_mpi/run_3dhp.py:45-46)

@@ -303,7 +303,9 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
                 case Family::BF16_TILE: HIP_TRY(launch_gemm_bf16_ws_group(&a, 1, s)); break;
                 case Family::F32_TILE: HIP_TRY(launch_f32_tile(&a, 1, s)); break;
                 case Family::WINO: HIP_TRY(launch_gemm_wino(a, s)); break;
-                default: HIP_TRY(launch_gemm_f32(a, s));
+                default:
+                    if (op.in[0] == -2 && !images && u8in.img) HIP_TRY(launch_gemm_f32_u8(a, u8in, s));   // the stem from the uint8 crop: same route, U8 form
+                    else HIP_TRY(launch_gemm_f32(a, s));
             }
             break;
         }
@@ -831,6 +833,83 @@ int capf_forward_train(capf_handle* h, void* stream, const float* images_nhwc, c
     int rc = check_run(e, batch);
     if (rc) return rc;
     e.images = images_nhwc; e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
+    e.last_batch = batch;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    e.invalidate_train();
+    rc = e.run(s, batch, 0, e.n_backbone_ops);
+    if (rc) return rc;
+    return e.forward_train(s, batch, drop_masks);
+}
+
+// ---- the same three entries from the uint8 BGR crop: nothing but the stem's load differs (launch_gemm_f32_u8), so every check, every other
+// launch and every result bit is the float entry's on capf_preprocess's output
+static int u8_begin(capf_handle* h, const uint8_t* images_bgr_u8, const float* mean, const float* std3, int mode, int batch) {
+    if (!h || !images_bgr_u8 || !mean) return CAPF_ERR_INVALID;
+    Engine& e = h->e;
+    if (mode < 0 || mode > 2) {
+        e.err = "mode must be 0 (as is), 1 (every frame mirrored) or 2 (flip test: [orig | mirrored])";
+        return CAPF_ERR_INVALID;
+    }
+    if (mode == 2 && (batch & 1)) {
+        e.err = "mode 2 runs 2 * Bsrc engine frames: batch must be even";
+        return CAPF_ERR_INVALID;
+    }
+    const int rc = check_run(e, batch);
+    if (rc) return rc;
+    const capf::Op* stem = nullptr;
+    for (const auto& op : e.ops)
+        if (op.kind == capf::OP_GEMM && op.in[0] == -2) {
+            if (stem || e.gemm_family(op, batch) != Engine::Family::F32) stem = nullptr;
+            else stem = &op;
+            if (!stem) break;
+        }
+    if (!stem || stem->Cin != 3) {
+        e.err = "this plan has no single Cin = 3 stem conv reading the image";
+        return CAPF_ERR_UNSUPPORTED;
+    }
+    e.images = nullptr;
+    e.u8in = capf::U8Input{};
+    e.u8in.img = images_bgr_u8;
+    e.u8in.Bsrc = mode == 2 ? batch / 2 : batch;
+    e.u8in.mode = mode;
+    for (int c = 0; c < 3; ++c) { e.u8in.mean[c] = mean[c]; e.u8in.stdv[c] = std3 ? std3[c] : 1.f; }
+    e.u8in.use_std = std3 ? 1 : 0;
+    return CAPF_OK;
+}
+
+int capf_forward_u8(capf_handle* h, void* stream, const uint8_t* images_bgr_u8, const float mean[3], const float* std3, int mode,
+                    const float* k2d, float* kcrop_inout, int batch, float* out) {
+    if (!h || !k2d || !kcrop_inout || !out) return CAPF_ERR_INVALID;
+    Engine& e = h->e;
+    int rc = u8_begin(h, images_bgr_u8, mean, std3, mode, batch);
+    if (rc) return rc;
+    e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
+    e.last_batch = batch;
+    e.invalidate_train();
+    return e.run(static_cast<hipStream_t>(stream), batch, 0, (int)e.ops.size());
+}
+
+int capf_backbone_forward_u8(capf_handle* h, void* stream, const uint8_t* images_bgr_u8, const float mean[3], const float* std3, int mode,
+                             int batch) {
+    int rc = u8_begin(h, images_bgr_u8, mean, std3, mode, batch);
+    if (rc) return rc;
+    Engine& e = h->e;
+    e.last_batch = batch;
+    e.invalidate_train();
+    return e.run(static_cast<hipStream_t>(stream), batch, 0, e.n_backbone_ops);
+}
+
+int capf_forward_train_u8(capf_handle* h, void* stream, const uint8_t* images_bgr_u8, const float mean[3], const float* std3, int mode,
+                          const float* k2d, float* kcrop_inout, int batch, float* out, const float* drop_masks) {
+    if (!h || !k2d || !kcrop_inout || !out) return CAPF_ERR_INVALID;
+    Engine& e = h->e;
+    if (!e.cfg.training) {
+        e.err = "handle was created with training = 0";
+        return CAPF_ERR_STATE;
+    }
+    int rc = u8_begin(h, images_bgr_u8, mean, std3, mode, batch);
+    if (rc) return rc;
+    e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
     e.last_batch = batch;
     hipStream_t s = static_cast<hipStream_t>(stream);
     e.invalidate_train();
@@ -1393,6 +1472,65 @@ int capf_preprocess(void* stream, const uint8_t* images_bgr, int batch, int heig
     return capf::launch_preprocess(images_bgr, batch, height, width, mean, std3, mode, images_out, gt_in, gt_out, k2d_in,
                                    k2d_out, kcrop_in, kcrop_out, static_cast<hipStream_t>(stream)) == hipSuccess
                ? CAPF_OK : CAPF_ERR_HIP;
+}
+
+int capf_preprocess_points(void* stream, int batch, int mode, const float* gt_in, float* gt_out, const float* k2d_in, float* k2d_out,
+                           const float* kcrop_in, float* kcrop_out) {
+    if (!k2d_in || !k2d_out || !kcrop_in || !kcrop_out || batch <= 0 || mode < 0 || mode > 2 || (gt_in && !gt_out)) return CAPF_ERR_INVALID;
+    return hip_rc(capf::launch_preprocess_points(batch, mode, gt_in, gt_out, k2d_in, k2d_out, kcrop_in, kcrop_out, static_cast<hipStream_t>(stream)));
+}
+
+int capf_input_rule_host(const uint8_t* u, int n, int channel, const float mean[3], const float* std3, float* out) {
+    if (!u || !out || !mean || n < 0 || channel < 0 || channel > 2) return CAPF_ERR_INVALID;
+    for (int i = 0; i < n; ++i) out[i] = capf::pixel_rule(u[i], channel, mean, std3);
+    return CAPF_OK;
+}
+
+// the stem conv as the plan's stem op runs it from a uint8 crop: the float op's problem (capf_op_conv / capf_op_conv_16's Cin = 3 branch) with the
+// image descriptor beside it, through the same dispatch
+static int conv_u8_args(const float* wp, const float* bias, void* y, int Bsrc, int mode, int H, int W, int Cout, int ks, int stride, int act,
+                        const float* mean, const float* std3, int out_dtype, capf::GemmArgs& a, capf::U8Input& in) {
+    if (Bsrc <= 0 || mode < 0 || mode > 2 || H <= 0 || W <= 0 || Cout <= 0 || ks <= 0 || stride <= 0 || !mean ||
+        (out_dtype != CAPF_F32 && !dtype16(out_dtype)))
+        return CAPF_ERR_INVALID;
+    const int frames = mode == 2 ? 2 * Bsrc : Bsrc;
+    a = conv_args(conv_desc(nullptr, wp, bias, nullptr, y, frames, H, W, 3, Cout, ks, stride, act), &capf::GemmArgs::Wp, 32);
+    if (out_dtype != CAPF_F32) { a.out_bf16 = 1; a.f16 = out_dtype == CAPF_F16; }
+    in = capf::U8Input{};
+    in.Bsrc = Bsrc; in.mode = mode;
+    for (int c = 0; c < 3; ++c) { in.mean[c] = mean[c]; in.stdv[c] = std3 ? std3[c] : 1.f; }
+    in.use_std = std3 ? 1 : 0;
+    return CAPF_OK;
+}
+
+int capf_op_conv_u8(void* stream, const uint8_t* images_bgr_u8, const float* wp, const float* bias, void* y, int Bsrc, int mode, int H, int W,
+                    int Cout, int ks, int stride, int act, const float mean[3], const float* std3, int out_dtype) {
+    if (!images_bgr_u8 || !wp || !y) return CAPF_ERR_INVALID;
+    capf::GemmArgs a;
+    capf::U8Input in;
+    if (const int rc = conv_u8_args(wp, bias, y, Bsrc, mode, H, W, Cout, ks, stride, act, mean, std3, out_dtype, a, in)) return rc;
+    in.img = images_bgr_u8;
+    if (out_dtype != CAPF_F32 && !capf::gemm_bf16_smallc_ok(a)) return CAPF_ERR_UNSUPPORTED;
+    return hip_rc(capf::launch_gemm_f32_u8(a, in, static_cast<hipStream_t>(stream)), CAPF_ERR_UNSUPPORTED);
+}
+
+const char* capf_op_conv_u8_kernel_name(int Bsrc, int mode, int H, int W, int Cout, int ks, int stride, int out_dtype) {
+    static const float zero[3] = {0.f, 0.f, 0.f};
+    capf::GemmArgs a;
+    capf::U8Input in;
+    if (conv_u8_args(nullptr, nullptr, nullptr, Bsrc, mode, H, W, Cout, ks, stride, 0, zero, nullptr, out_dtype, a, in)) return "";
+    if (out_dtype != CAPF_F32 && !capf::gemm_bf16_smallc_ok(a)) return "";
+    return capf::gemm_f32_u8_kernel_name(a);
+}
+
+// ... and of the float stem op of the same shape at B frames (capf_op_conv; capf_op_conv_16's Cin = 3 branch)
+const char* capf_op_conv_stem_kernel_name(int B, int H, int W, int Cout, int ks, int stride, int out_dtype) {
+    static const float zero[3] = {0.f, 0.f, 0.f};
+    capf::GemmArgs a;
+    capf::U8Input in;
+    if (conv_u8_args(nullptr, nullptr, nullptr, B, 0, H, W, Cout, ks, stride, 0, zero, nullptr, out_dtype, a, in)) return "";
+    if (out_dtype != CAPF_F32) return capf::gemm_bf16_smallc_ok(a) ? capf::gemm_bf16_smallc_kernel_name(a) : "";
+    return capf::gemm_f32_kernel_name(a);
 }
 
 int capf_fliptest_fuse(void* stream, const float* pred2, int batch, float* out) {

@@ -330,6 +330,8 @@ struct Engine {
     std::vector<int> last_variants;   // capf_forward_profile_launches: grouped-bf16 kernel variant per leader op
     int last_batch = 0;
     const float* images = nullptr;
+    U8Input u8in{};                // capf_forward_u8 and its siblings: the uint8 crop the stem reads instead (they leave `images` null; the float
+                                   // entries always set it, so a null `images` with u8in.img set is what selects the stem's U8 form)
     const float* k2d = nullptr;
     float* kcrop = nullptr;
     float* out = nullptr;

@@ -875,15 +875,23 @@ __global__ __launch_bounds__(256) void igemm_bf16_stream_kernel(GemmArgs p) {
 // =====================================================================================================
 [[maybe_unused]] static constexpr int SPITCH = 40;          // halves per LDS row: 32 k-values + 8 pad (80 B: 16-byte aligned fragment reads)
 
-template <class F>
-__global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) {
+// U8 (all three stem kernels below): the uint8 forms -- the image is the BGR crop itself, see igemm_f32_smallc_body (igemm_f32.hip) for the
+// scheme: a per-block value table filled with pixel_rule(), one byte load per tap with its own validity, the same tile / K order / MFMA
+// sequence as the float form, the descriptor as an extra argument of the *_u8_kernel entry points.
+template <class F, bool U8>
+__device__ __forceinline__ void igemm_bf16_smallc_body(const GemmArgs& p, const U8Input* u8) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BM = 128, BN = 64, WM = 64, WN = 32, SBK = 32;
     constexpr int WAVES_N = BN / WN, TM = WM / 32, TN = WN / 32, RA = BM / 32, RB = BN / 32;
-    __shared__ __attribute__((aligned(16))) unsigned short lds[(BM + BN) * SPITCH];
+    __shared__ __attribute__((aligned(16))) unsigned short lds[(BM + BN) * SPITCH + (U8 ? 2 * U8_TAB : 0)];
     unsigned short* As = lds;
     unsigned short* Bs = lds + BM * SPITCH;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* tab = reinterpret_cast<const float*>(lds + (BM + BN) * SPITCH);
+    if (U8) {
+        u8_fill_table(reinterpret_cast<float*>(lds + (BM + BN) * SPITCH), *u8, tid, 256);
+        __syncthreads();
+    }
     const int nbn = (p.N + BN - 1) / BN;
     const int bid = xcd_remap_b(blockIdx.x, gridDim.x);
     const int tile_m = bid / nbn, tile_n = bid - tile_m * nbn;
@@ -891,14 +899,15 @@ __global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) {
     const int srow = tid >> 3, kq = (tid & 7) * 4;
 
     long a_base[RA];
-    int a_h0[RA], a_w0[RA];
+    int a_h0[RA], a_w0[RA], a_f[RA];                  // (a_f: the frame, read by the U8 form alone)
 #pragma unroll
     for (int i = 0; i < RA; ++i) {
         const int m = m0 + srow + 32 * i;
-        a_base[i] = 0; a_h0[i] = -(1 << 20); a_w0[i] = 0;
+        a_base[i] = 0; a_h0[i] = -(1 << 20); a_w0[i] = 0; a_f[i] = 0;
         if (m < p.M) {
             const int b = fast_div_b(m, p.fd_hw), rem = m - b * p.Ho * p.Wo;
             const int ho = fast_div_b(rem, p.fd_wo), wo = rem - ho * p.Wo;
+            a_f[i] = b;
             a_base[i] = (long)b * p.H * p.W * p.Cin;
             a_h0[i] = ho * p.stride - p.pad;
             a_w0[i] = wo * p.stride - p.pad;
@@ -907,7 +916,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) {
     float a_reg[RA][4];
     f32x4 b_reg[RB];
     auto load_chunk = [&](int c) {
-        int dh[4], dw[4], doff[4];
+        int dh[4], dw[4], doff[4], dc[4];
         bool kok[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {          // the (kh, kw, c) of this thread's four k-values: the same for every row
@@ -917,6 +926,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) {
             dw[e] = t - dh[e] * p.ks;
             doff[e] = (dh[e] * p.W + dw[e]) * p.Cin + c1;
             kok[e] = ke < p.K;
+            dc[e] = kok[e] ? c1 : 0;
         }
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
@@ -924,7 +934,9 @@ __global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int hi = a_h0[i] + dh[e], wi = a_w0[i] + dw[e];
-                a_reg[i][e] = (kok[e] && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W) ? p.A[row + doff[e]] : 0.f;
+                const bool ok = kok[e] && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
+                if (U8) a_reg[i][e] = u8_value(tab, ok, u8_load(*u8, ok, u8_pixel(*u8, a_f[i], hi, wi, p.H, p.W), dc[e]), dc[e]);
+                else a_reg[i][e] = ok ? p.A[row + doff[e]] : 0.f;
             }
         }
 #pragma unroll
@@ -1000,12 +1012,17 @@ __global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) {
 #endif
 }
 
+template <class F>
+__global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) { igemm_bf16_smallc_body<F, false>(p, nullptr); }
+template <class F>
+__global__ __launch_bounds__(256) void igemm_bf16_smallc_u8_kernel(GemmArgs p, U8Input in) { igemm_bf16_smallc_body<F, true>(p, &in); }
+
 // Stem, second version (Cin = 3, k = 7 or 3): for a fixed (output pixel, kh) the 3 k input values are CONTIGUOUS in the NHWC
 // image (and in the (kh, kw, c)-ordered weights), so a thread fetches one such run with 16-byte loads (dword-aligned
 // addresses) instead of 21 / 9 scalar gathers, zeroes what lies outside the image, and writes it as bf16 into an LDS tile
 // whose K axis is (kh, 24 | 16): the whole K of a 128 x 64 tile is staged once (no chunk loop), then 11 / 3 MFMA k-steps.
-template <int KS, int BM, class F>
-__global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
+template <int KS, int BM, class F, bool U8>
+__device__ __forceinline__ void igemm_bf16_stem_body(const GemmArgs& p, const U8Input* u8) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BN = 64, WM = BM / 2, WN = 32, TM = WM / 32;
     constexpr int RUN = KS * 3;                      // contiguous floats per (pixel, kh)
@@ -1013,7 +1030,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
     constexpr int PKH = (RUN + 7) / 8 * 8;           // halves per kh in LDS (24 / 16)
     constexpr int KP = (KS * PKH + 15) / 16 * 16;    // staged K (176 / 48)
     constexpr int PITCH = KP + 8;                    // halves per LDS row: 16-byte aligned, conflict-free b128 reads
-    __shared__ __attribute__((aligned(16))) unsigned short lds[(BM + BN) * PITCH];
+    __shared__ __attribute__((aligned(16))) unsigned short lds[(BM + BN) * PITCH + (U8 ? 2 * U8_TAB : 0)];
     unsigned short* As = lds;
     unsigned short* Bs = lds + BM * PITCH;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1023,6 +1040,11 @@ __global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const long total = (long)(p.M / (p.Ho * p.Wo)) * p.H * p.W * 3;
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const float* tab = reinterpret_cast<const float*>(lds + (BM + BN) * PITCH);
+    if (U8) {
+        u8_fill_table(reinterpret_cast<float*>(lds + (BM + BN) * PITCH), *u8, tid, 256);
+        __syncthreads();
+    }
 
     auto put_run = [&](unsigned short* dst, const float (&v)[NX4 * 4], int kh) {     // RUN values (+ zero padding) -> LDS as bf16
         unsigned pk[PKH / 2];
@@ -1045,7 +1067,15 @@ __global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
             const int b = fast_div_b(m, p.fd_hw), rem = m - b * p.Ho * p.Wo;
             const int ho = fast_div_b(rem, p.fd_wo), wo = rem - ho * p.Wo;
             const int hi = ho * p.stride - p.pad + kh, wi0 = wo * p.stride - p.pad;
-            if ((unsigned)hi < (unsigned)p.H) {
+            if (U8 && (unsigned)hi < (unsigned)p.H) {
+#pragma unroll
+                for (int kw = 0; kw < KS; ++kw) {
+                    const bool ok = (unsigned)(wi0 + kw) < (unsigned)p.W;
+                    const long px = u8_pixel(*u8, b, hi, wi0 + kw, p.H, p.W);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) v[3 * kw + c] = u8_value(tab, ok, u8_load(*u8, ok, px, c), c);
+                }
+            } else if ((unsigned)hi < (unsigned)p.H) {
                 const long src = (((long)b * p.H + hi) * p.W + wi0) * 3;
 #pragma unroll
                 for (int x = 0; x < NX4; ++x) {
@@ -1122,6 +1152,11 @@ __global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
 #endif
 }
 
+template <int KS, int BM, class F>
+__global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) { igemm_bf16_stem_body<KS, BM, F, false>(p, nullptr); }
+template <int KS, int BM, class F>
+__global__ __launch_bounds__(256) void igemm_bf16_stem_u8_kernel(GemmArgs p, U8Input in) { igemm_bf16_stem_body<KS, BM, F, true>(p, &in); }
+
 // Stem, third version: PERSISTENT blocks with the weights staged once and the next tile's runs in flight while the current
 // tile is multiplied and stored.  The second version above is one latency chain per block -- gather (6 x 16-byte loads per run
 // behind per-quad branches, i.e. one L2 round trip after the other), LDS, 11 MFMAs, 8-byte strided stores -- with only two
@@ -1134,8 +1169,11 @@ __global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) {
 // contiguous per row.  XCD-aware tile order: each XCD walks its own contiguous eighth of the tiles, so the 7 / 3 input rows
 // that vertically adjacent tiles share are fetched into ONE L2.  Only the handful of runs at the very start of the tensor (negative
 // offsets cannot be expressed) are patched element-wise by the blocks that own those pixels.
-template <int KS, class F>
-__global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs p, int ntiles) {
+// U8: issue() requests the runs' 21 / 9 bytes one by one -- in flight across the previous tile's MFMAs and stores like the float form's
+// loads -- and the table turns them into the float run just before put_run.  Every byte carries its own validity, so the patch of the runs
+// that start before the tensor has nothing to do in that form.
+template <int KS, class F, bool U8>
+__device__ __forceinline__ void igemm_bf16_stem_stream_body(const GemmArgs& p, const int ntiles, const U8Input* u8) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BM = 64, BN = 64;
     constexpr int RUN = KS * 3;                      // contiguous floats per (pixel, kh)
@@ -1148,16 +1186,18 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs
     constexpr int NT = (BM * KS + 255) / 256;        // runs per thread and tile (2 / 1)
     constexpr int EPS = 36;
     constexpr unsigned OOB = 0x80000000u;
-    __shared__ __attribute__((aligned(16))) unsigned short lds[(BM + BN) * PITCH + 4 * 32 * EPS * 2];
+    __shared__ __attribute__((aligned(16))) unsigned short lds[(BM + BN) * PITCH + 4 * 32 * EPS * 2 + (U8 ? 2 * U8_TAB : 0)];
     unsigned short* As = lds;
     unsigned short* Bs = lds + BM * PITCH;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float* ep = reinterpret_cast<float*>(lds + (BM + BN) * PITCH) + wave * (32 * EPS);
+    const float* tab = reinterpret_cast<const float*>(lds + (BM + BN) * PITCH + 4 * 32 * EPS * 2);
+    if (U8) u8_fill_table(reinterpret_cast<float*>(lds + (BM + BN) * PITCH + 4 * 32 * EPS * 2), *u8, tid, 256);   // (its barrier: in front of the tile loop)
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     unsigned short* Out = reinterpret_cast<unsigned short*>(p.out);
     const long total = (long)(p.M / (p.Ho * p.Wo)) * p.H * p.W * 3;              // floats of the image tensor (< 2^29: launcher)
-    const rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (unsigned)(total * 4), 0x00020000);
+    const rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(U8 ? (void*)Out : (void*)p.A, 0, U8 ? 0u : (unsigned)(total * 4), 0x00020000);
     const rsrc_t rs_bias = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)p.bias : (void*)Out, 0,
                                                              p.bias ? (unsigned)p.N * 4u : 0u, 0x00020000);
 
@@ -1205,6 +1245,7 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs
     f32x4 q[NT][NX4];
     float qlast[NT];
     unsigned mask[NT];
+    unsigned raw[NT][RUN];                           // U8: the runs' bytes, (kw, c) order like the float runs
     // run i of this thread; a thread without an i-th run repeats another one (same loads, the same LDS bytes written twice) --
     // a branch around put_run would leave "maybe pending" loads behind it and cost a vmcnt(0) in front of the next requests
     auto run_of = [&](int i) { return (tid + 256 * i) % (BM * KS); };
@@ -1226,6 +1267,16 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs
             const int lo = max(0, -wi0), hn = max(lo, min(KS, p.W - wi0));
             const unsigned mk = ((1u << (3 * hn)) - 1u) & ~((1u << (3 * lo)) - 1u);
             mask[i] = ok ? mk : 0u;
+            if (U8) {
+#pragma unroll
+                for (int kw = 0; kw < KS; ++kw) {
+                    const bool v = (mask[i] >> (3 * kw)) & 1u;
+                    const long px = u8_pixel(*u8, b, hi, wi0 + kw, p.H, p.W);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) raw[i][3 * kw + c] = u8_load(*u8, v, px, c);
+                }
+                continue;
+            }
 #pragma unroll
             for (int x = 0; x < NX4; ++x)
                 q[i][x] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
@@ -1247,16 +1298,24 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs
         __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, rs_none, OOB, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, rs_none, OOB + 16u, 0, 0);   // (distinct: identical stores are merged)
     }
+    if (U8) __syncthreads();                          // the value table is complete
     for (; tile < t_end; tile += nslots) {
         const int m0 = tile * BM;
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
             const int t = run_of(i);
             const int kh = t / BM, row = t - kh * BM;
+            if (U8) {                                  // bytes -> the float run (masked elements are zeroed by put_run)
+#pragma unroll
+                for (int e = 0; e < RUN; ++e) {
+                    const float v = tab[(e % 3) * 256 + raw[i][e]];
+                    if (e < NX4 * 4) q[i][e >> 2][e & 3] = v; else qlast[i] = v;
+                }
+            }
             put_run(As + row * PITCH, q[i], qlast[i], mask[i], kh);
         }
         const int ho_max = p.pad / p.stride;           // output rows (of frame 0) with a window row on input row 0
-        if (m0 < (ho_max + 1) * p.Wo) {
+        if (!U8 && m0 < (ho_max + 1) * p.Wo) {
             // Frame 0, input row 0, window starting left of the image: the run begins at a NEGATIVE offset from the tensor start,
             // which a buffer offset cannot express -- its first quads were requested out of range above.  The few such runs
             // (output rows ho = (pad - kh) / stride, columns wo * stride < pad) are rewritten here element by element.
@@ -1312,6 +1371,15 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs
 #endif
 }
 
+template <int KS, class F>
+__global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs p, int ntiles) {
+    igemm_bf16_stem_stream_body<KS, F, false>(p, ntiles, nullptr);
+}
+template <int KS, class F>
+__global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_u8_kernel(GemmArgs p, int ntiles, U8Input in) {
+    igemm_bf16_stem_stream_body<KS, F, true>(p, ntiles, &in);
+}
+
 // fp32 NHWC image (Cin % 4 != 0), fp32 packed weights [N][Kpad32], bf16 NHWC result; no residual.
 bool gemm_bf16_smallc_ok(const GemmArgs& a) {
     return a.conv && a.out_bf16 && !a.res && a.omap.G == 1 && a.N % 4 == 0 && a.omap.S1 % 4 == 0 && a.omap.off % 4 == 0 &&
@@ -1363,6 +1431,42 @@ hipError_t launch_gemm_bf16_smallc(const GemmArgs& a_in, hipStream_t s) {
         if (ks == 7) hipLaunchKernelGGL((igemm_bf16_stem_kernel<7, 128, F>), grid, dim3(256), 0, s, a);
         else if (ks == 3) hipLaunchKernelGGL((igemm_bf16_stem_kernel<3, 128, F>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(igemm_bf16_smallc_kernel<F>, grid, dim3(256), 0, s, a);
+        return 0;
+    });
+    return hipGetLastError();
+}
+
+// ... and from the uint8 crop: the same decisions (stem_runs_ks, stem_stream_ok), the U8 form of the kernel they name
+const char* gemm_bf16_smallc_u8_kernel_name(const GemmArgs& a) {
+    if (!stem_runs_ks(a)) return fmt_kernel_name("igemm_bf16_smallc<w4,128x64,u8>", a.f16);
+    return fmt_kernel_name(stem_stream_ok(a) ? "igemm_bf16_stem_stream<w4,64x64,u8>" : "igemm_bf16_stem<w4,128x64,u8>", a.f16);
+}
+
+hipError_t launch_gemm_bf16_smallc_u8(const GemmArgs& a_in, const U8Input& in, hipStream_t s) {
+    if (!gemm_bf16_smallc_ok(a_in) || !gemm_u8_ok(a_in, in)) return hipErrorInvalidValue;
+    GemmArgs a = a_in;
+    a.A = nullptr;
+    a.fd_hw = make_fastdiv((unsigned)(a.Ho * a.Wo));
+    a.fd_wo = make_fastdiv((unsigned)a.Wo);
+    const int ks = stem_runs_ks(a);
+    if (ks && stem_stream_ok(a)) {
+        const int ntiles = (a.M + 63) / 64;
+        int blocks = 512;                              // two per CU
+        while (blocks > 8 && blocks / 2 >= ntiles) blocks /= 2;
+        with_fmt(a.f16, [&](auto f) {
+            using F = decltype(f);
+            if (ks == 7) hipLaunchKernelGGL((igemm_bf16_stem_stream_u8_kernel<7, F>), dim3(blocks), dim3(256), 0, s, a, ntiles, in);
+            else hipLaunchKernelGGL((igemm_bf16_stem_stream_u8_kernel<3, F>), dim3(blocks), dim3(256), 0, s, a, ntiles, in);
+            return 0;
+        });
+        return hipGetLastError();
+    }
+    const dim3 grid(((a.M + 127) / 128) * ((a.N + 63) / 64));
+    with_fmt(a.f16, [&](auto f) {
+        using F = decltype(f);
+        if (ks == 7) hipLaunchKernelGGL((igemm_bf16_stem_u8_kernel<7, 128, F>), grid, dim3(256), 0, s, a, in);
+        else if (ks == 3) hipLaunchKernelGGL((igemm_bf16_stem_u8_kernel<3, 128, F>), grid, dim3(256), 0, s, a, in);
+        else hipLaunchKernelGGL(igemm_bf16_smallc_u8_kernel<F>, grid, dim3(256), 0, s, a, in);
         return 0;
     });
     return hipGetLastError();

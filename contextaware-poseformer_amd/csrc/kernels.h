@@ -7,6 +7,7 @@
 
 #include "relu.h"
 #include "fmt16.h"    // the 16-bit element formats (bf16 / fp16) of the 16-bit kernel families
+#include "pixel_rule.h"   // the input normalisation rule and the uint8 image descriptor of the stem kernels' U8 forms
 #include "capf.h"      // capf_optim_report: the record the guarded AdamW kernel writes is the public one
 
 namespace capf {
@@ -413,6 +414,14 @@ hipError_t launch_pack_f32h2_train(const H2TrainW* tab_dev, int n, int tiles, fl
 bool gemm_bf16_smallc_ok(const GemmArgs& a);            // the stem conv (Cin = 3) with a bf16 result
 hipError_t launch_gemm_bf16_smallc(const GemmArgs& a, hipStream_t s);
 const char* gemm_bf16_smallc_kernel_name(const GemmArgs& a);
+// The stem conv straight from the uint8 BGR crop (pixel_rule.h U8Input; GemmArgs::A is not read): launch_gemm_f32's route for the same
+// problem, the U8 form of that route's kernel, bit-identical to the float kernel on launch_preprocess's output.  The names are the float
+// kernels' with a ",u8" tag.  launch_gemm_bf16_smallc_u8: the 16-bit stems (what launch_gemm_f32_u8 forwards an out_bf16 problem to)
+bool gemm_u8_ok(const GemmArgs& a, const U8Input& in);
+hipError_t launch_gemm_f32_u8(const GemmArgs& a, const U8Input& in, hipStream_t s);
+const char* gemm_f32_u8_kernel_name(const GemmArgs& a);
+hipError_t launch_gemm_bf16_smallc_u8(const GemmArgs& a, const U8Input& in, hipStream_t s);
+const char* gemm_bf16_smallc_u8_kernel_name(const GemmArgs& a);
 hipError_t launch_pack_linear(const float* w, float* Wp, int N, int K, int Kpad, hipStream_t s);
 // quad-interleaved pack for the fused lifter kernels: Wq[(k / 4) * Ntot + n0 + n][k % 4] = w[n][k]  (K % 4 == 0): lane n of a
 // wave reads the 16-byte quad next to lane n - 1's instead of a row K floats away
@@ -654,6 +663,9 @@ hipError_t launch_pos_grad(const float* dX, float* dpos, int B, int J, int L1, i
 hipError_t launch_preprocess(const unsigned char* images_bgr, int B, int H, int W, const float mean[3], const float* stdv,
                              int mode, float* images_out, const float* gt_in, float* gt_out, const float* k2d_in,
                              float* k2d_out, const float* kc_in, float* kc_out, hipStream_t s);
+// ... its keypoint / ground-truth half alone (one launch; what launch_preprocess runs behind the image kernel)
+hipError_t launch_preprocess_points(int B, int mode, const float* gt_in, float* gt_out, const float* k2d_in, float* k2d_out,
+                                    const float* kc_in, float* kc_out, hipStream_t s);
 hipError_t launch_fliptest_fuse(const float* pred2, int B, float* out, hipStream_t s);     // the H36M table (kSwap)
 // any skeleton: swap[j] = the joint whose mirrored prediction lands on joint j (J <= FLIP_MAX_JOINTS; a kernel argument)
 constexpr int FLIP_MAX_JOINTS = 32;

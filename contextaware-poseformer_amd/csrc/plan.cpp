@@ -1180,6 +1180,15 @@ bool Engine::build() {
             return false;
         }
     }
+    for (const Op& op : ops)        // "stem": the output of the conv that reads the image.  NOT kept alive (name_tensor would pin 64 channels at half
+        if (op.kind == OP_GEMM && op.in[0] == EXT_IMAGES) {       // resolution per frame in every workspace): later ops of a run reuse its memory, so what it
+            NamedTensor t{};                                       // holds after a run is a function of the run alone -- two routes of one plan compare bit for bit
+            t.buf = op.out;
+            t.ndim = 4;
+            t.shape[0] = -1; t.shape[1] = op.Ho; t.shape[2] = op.Wo; t.shape[3] = op.N;
+            t.is_int = op.st_f32 ? 0 : (op.out_bf16 ? dt16() : 0);
+            named["stem"] = t;
+        }
     n_backbone_ops = (int)ops.size();
     for (int l = 0; l < 4; ++l) {
         feat_buf[l] = feats[l].buf; feat_H[l] = feats[l].H; feat_W[l] = feats[l].W; feat_C[l] = feats[l].C;

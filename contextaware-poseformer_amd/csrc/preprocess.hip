@@ -10,6 +10,7 @@
 // results are bit-identical to the torch expressions.  Built with -ffp-contract=off.
 #include "kernels.h"
 #include "warp_rule.h"
+#include "pixel_rule.h"
 
 namespace capf {
 
@@ -28,15 +29,11 @@ __global__ void preprocess_images_kernel(const unsigned char* __restrict__ in, f
         const long row = pix / W;
         const bool mirror = set == 1 || (set == 0 && mirror_first);
         const long src = (row * W + (mirror ? W - 1 - w : w)) * 3;
-        const float b = (float)in[src + 0], g = (float)in[src + 1], r = (float)in[src + 2];   // BGR in memory
-        // `images / 255.0` with a Python scalar is a multiplication by the fp32 reciprocal on the GPU the
-        // reference's prefetcher runs on (ATen div_true_kernel_cuda, CPU-scalar fast path); mean / std are tensors
-        const float inv255 = 1.0f / 255.0f;
-        float o0 = __fsub_rn(__fmul_rn(r, inv255), m0), o1 = __fsub_rn(__fmul_rn(g, inv255), m1),
-              o2 = __fsub_rn(__fmul_rn(b, inv255), m2);
-        if (use_std) { o0 = __fdiv_rn(o0, s0); o1 = __fdiv_rn(o1, s1); o2 = __fdiv_rn(o2, s2); }
+        // BGR in memory; the arithmetic is pixel_rule.h's, shared with the stem kernels' uint8 forms and with capf_input_rule_host
+        const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
         float* o = out + i * 3;
-        o[0] = o0; o[1] = o1; o[2] = o2;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = pixel_rule(in[src + 2 - c], c, mean, use_std ? stdv : nullptr);
     }
 }
 
@@ -83,6 +80,13 @@ hipError_t launch_preprocess(const unsigned char* images_bgr, int B, int H, int 
     hipLaunchKernelGGL(preprocess_images_kernel, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, s, images_bgr,
                        images_out, B, H, W, mean[0], mean[1], mean[2], stdv ? stdv[0] : 1.f, stdv ? stdv[1] : 1.f,
                        stdv ? stdv[2] : 1.f, stdv ? 1 : 0, nsets, mirror_first);
+    return launch_preprocess_points(B, mode, gt_in, gt_out, k2d_in, k2d_out, kc_in, kc_out, s);
+}
+
+// the points half alone (the image-less route: capf_forward_u8 reads the crop itself, the keypoints still want their mirror / stacking)
+hipError_t launch_preprocess_points(int B, int mode, const float* gt_in, float* gt_out, const float* k2d_in, float* k2d_out,
+                                    const float* kc_in, float* kc_out, hipStream_t s) {
+    const int nsets = mode == 2 ? 2 : 1, mirror_first = mode == 1 ? 1 : 0;
     const int np = nsets * B * 17;
     hipLaunchKernelGGL(preprocess_points_kernel, dim3((np + 127) / 128), dim3(128), 0, s, gt_in, gt_out, k2d_in, k2d_out, kc_in,
                        kc_out, B, nsets, mirror_first);

@@ -23,6 +23,10 @@ class VolumetricTriangulationNet(CA_PF):
         x = super().forward(images, keypoints_2d_cpn, keypoints_2d_cpn_crop)       # [B, 1, 17, 3]
         return self._layout(x), None
 
+    def forward_u8(self, images_u8, keypoints_2d_cpn, keypoints_2d_cpn_crop, mirror="none"):
+        """CA_PF.forward_u8 (the forward from uint8 BGR crops) in this variant's output layout: (x [B, 3, 1, 17, 1], None)."""
+        return self._layout(super().forward_u8(images_u8, keypoints_2d_cpn, keypoints_2d_cpn_crop, mirror)), None
+
     def forward_features(self, features_list, keypoints_2d_cpn, keypoints_2d_cpn_crop):
         """CA_PF.forward_features in this variant's output layout: (x [B, 3, 1, 17, 1], None)."""
         return self._layout(super().forward_features(features_list, keypoints_2d_cpn, keypoints_2d_cpn_crop)), None

@@ -17,6 +17,19 @@ from capf.lib import CapfError, Engine
 from . import _native
 
 
+class _U8Images:
+    """The `images` argument of _LifterStep on the uint8 route (CA_PF.forward_u8): the uint8 BGR crops with the normalisation
+    constants and capf_preprocess's mode; shape[0] counts engine frames (2 * Bsrc for a flip-test pair)."""
+
+    def __init__(self, crops, mean, std, mode):
+        self.crops, self.mean, self.std, self.mode = crops, mean, std, mode
+        self.device = crops.device
+        self.shape = (crops.shape[0] * (2 if mode == 2 else 1),) + tuple(crops.shape[1:])
+
+
+MIRROR_MODES = {"none": 0, "all": 1, "pair": 2}       # CA_PF.forward_u8's `mirror` -> capf_preprocess's mode
+
+
 class _LifterStep(torch.autograd.Function):
     """Autograd boundary of the native training step: forward = capf_forward_train, backward =
     capf_backward into one flat gradient buffer whose slices are returned as the parameter gradients
@@ -26,7 +39,10 @@ class _LifterStep(torch.autograd.Function):
     def forward(ctx, owner, eng, images, k2d, kcrop, masks, names, *params):
         out = torch.empty(images.shape[0], 1, owner.num_joints, 3, dtype=torch.float32, device=images.device)
         stream = torch.cuda.current_stream(images.device).cuda_stream
-        eng.forward_train(images, k2d, kcrop, out, stream, masks)
+        if isinstance(images, _U8Images):     # the uint8 route: the same step, the stem reads the crops (nothing in the backward reads the image)
+            eng.forward_train_u8(images.crops, images.mean, images.std, images.mode, k2d, kcrop, out, stream, masks)
+        else:
+            eng.forward_train(images, k2d, kcrop, out, stream, masks)
         ctx.token = eng.train_generation()
         ctx.eng, ctx.masks, ctx.names, ctx.owner = eng, masks, names, owner
         ctx.keep = (k2d, kcrop)     # capf_backward re-reads the keypoints / normalised ref: keep them alive
@@ -250,6 +266,59 @@ class CA_PF(nn.Module):
             else:
                 out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=images.device)
                 eng.forward(images, k2d, kcrop, out, stream)
+            if kcrop is not keypoints_2d_cpn_crop:
+                with torch.no_grad():
+                    keypoints_2d_cpn_crop.copy_(kcrop)
+        return out
+
+    # ---- the same forward from uint8 crops: normalisation, BGR flip and mirror in the stem conv's load (capf_forward_u8) ----------
+    def forward_u8(self, images_u8, keypoints_2d_cpn, keypoints_2d_cpn_crop, mirror="none"):
+        """forward() on the uint8 BGR crops themselves: images_u8 is a contiguous uint8 CUDA tensor [B,H,W,3] as the loader / the crop
+        decoder delivers it; no fp32 image is materialised.  Mean and std are the configured backbone's, as data_prefetcher picks them
+        (datasets/utils.py:24-29, 45-50).  mirror: "none" -- as is; "all" -- every frame mirrored (the train-time flip, :55-56);
+        "pair" -- the flip test (:67-68): 2B engine frames, the B crops followed by their mirrors; the keypoints are then [2B,17,2] in
+        capf_preprocess mode 2's layout ([2,B,17,2] flattened: capf.lib.preprocess_points) and the result is [2B,1,17,3].  The keypoints
+        are NOT mirrored here (preprocess_points does that); the third argument is normalised in place like forward's.  Under grad the
+        native training step runs.  Every result bit equals forward() on capf.lib.preprocess()'s images."""
+        from capf.lib import input_constants
+        if not isinstance(mirror, str) or mirror not in MIRROR_MODES:
+            raise ValueError("mirror must be 'none', 'all' or 'pair', got {!r}".format(mirror))
+        mode = MIRROR_MODES[mirror]
+        if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8:
+            raise TypeError("images_u8 must be uint8, got {}".format(getattr(images_u8, "dtype", type(images_u8))))
+        if images_u8.device.type != "cuda":
+            raise CapfError("CA_PF runs on an MI355X only: inputs are on {} (no CPU fallback)".format(images_u8.device))
+        if images_u8.dim() != 4 or images_u8.shape[3] != 3:
+            raise ValueError("images_u8 must be [B,H,W,3] NHWC, got {}".format(tuple(images_u8.shape)))
+        if not images_u8.is_contiguous():
+            raise ValueError("images_u8 must be contiguous (a copy would be the image round trip this entry removes)")
+        dev = images_u8.device
+        Bsrc, H, W, _ = images_u8.shape
+        B = 2 * Bsrc if mode == 2 else Bsrc
+        for name, t in (("keypoints_2d_cpn", keypoints_2d_cpn), ("keypoints_2d_cpn_crop", keypoints_2d_cpn_crop)):
+            if t.dtype != torch.float32:
+                raise TypeError("{} must be float32, got {}".format(name, t.dtype))
+            if t.device != dev:
+                raise ValueError("{} is on {} but images are on {}".format(name, t.device, dev))
+            if tuple(t.shape) != (B, self.num_joints, 2):
+                raise ValueError("{} must have shape ({}, {}, 2){}, got {}".format(
+                    name, B, self.num_joints, " for mirror='pair' (two sets of {} frames)".format(Bsrc) if mode == 2 else "", tuple(t.shape)))
+        mean, std = input_constants("cpn" if self._backbone_type == "cpn" else "hrnet_32")
+        with torch.cuda.device(dev):
+            eng = self._engine_at(dev, H, W)
+            k2d = keypoints_2d_cpn.contiguous()
+            kcrop = keypoints_2d_cpn_crop if keypoints_2d_cpn_crop.is_contiguous() else keypoints_2d_cpn_crop.contiguous()
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if torch.is_grad_enabled() and any(p.requires_grad for p in self.volume_net.parameters()):
+                named = [(n, p) for n, p in self.volume_net.named_parameters()]
+                if not all(p.requires_grad for _, p in named):
+                    raise NotImplementedError("partially frozen volume_net is not supported by the native backward")
+                names = tuple("volume_net." + n for n, _ in named)
+                out = _LifterStep.apply(self, eng, _U8Images(images_u8, mean, std, mode), k2d, kcrop, self._drop_masks(B, dev),
+                                        names, *[p for _, p in named])
+            else:
+                out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=dev)
+                eng.forward_u8(images_u8, mean, std, mode, k2d, kcrop, out, stream)
             if kcrop is not keypoints_2d_cpn_crop:
                 with torch.no_grad():
                     keypoints_2d_cpn_crop.copy_(kcrop)

@@ -351,6 +351,9 @@ int capf_set_debug(capf_handle* h, int on);
  *   cpos0..3       with capf_set_debug: sampling positions of DeformableBlock i, fp32 [B,17,L*16,2] (level, head*4+sample)
  *   cidx0..3       ... and the int32 NW corner (ix0, iy0) of each, padding_mode='border' (pose_dformer.py:126-128)
  *   tok_ctx / tok_res / tok_joint   token buffer [B,17,L+1,c] after each block group (layout b p l c)
+ *   stem           where the conv that reads the image writes, NHWC [B,H/2,W/2,64] in the plan's activation format.  Unlike the names above
+ *                  its memory is NOT reserved: later ops of the same run reuse it, so after a run it holds a function of that run alone
+ *                  (two routes of one plan and batch -- capf_forward / capf_forward_u8 -- compare bit for bit; it is not the conv's output)
  * Pointers are into the workspace and valid until the next forward on this handle.
  * Returns 0 for an fp32 tensor, 1 for an int32 tensor, 2 for a bf16 tensor (context maps of a
  * CAPF_BF16 handle; fp32 under CAPF_PLAN_BF16_F32_STREAM), 3 for an fp16 tensor (context maps of a
@@ -590,6 +593,40 @@ int capf_preprocess(void* stream, const uint8_t* images_bgr, int batch, int heig
                     const float* std3, int mode, float* images_out, const float* gt_in, float* gt_out,
                     const float* k2d_in, float* k2d_out, const float* kcrop_in, float* kcrop_out);
 int capf_fliptest_fuse(void* stream, const float* pred2, int batch, float* out);
+
+/* ---- N1 / A2 fused into the stem conv's load: the forward from uint8 crops (additive inside revision 12) -----------------------------
+ * The channel flip, the normalisation and the mirror of data_prefetcher.preload (ContextPose/mvn/datasets/utils.py:45-50, 55-56, 67-68)
+ * happen where the stem conv gathers its taps: no fp32 image is written or read (0.79 MB each way per 256x256 frame; 403 MB at 512 frames,
+ * twice that for a flip-test pair).  The stem runs the uint8 form of the kernel the float route would pick at the same shape, batch and
+ * dtype (kernel names: the float kernel's with a ",u8" tag); every result bit equals capf_preprocess + the float entry.
+ *   images_bgr_u8 [Bsrc,H,W,3] uint8, BGR in memory, any alignment; mean[3] / std3[3] HOST floats in RGB order (std3 == NULL: mean only, CPN);
+ *   mode: capf_preprocess's -- 0 as is, 1 every frame mirrored, 2 flip test: engine frame f < Bsrc is source frame f, frame Bsrc + f its
+ *   mirror.  `batch` counts ENGINE frames: Bsrc in modes 0 / 1, 2 * Bsrc in mode 2 (an odd batch: CAPF_ERR_INVALID).  A mode outside
+ *   0 / 1 / 2: CAPF_ERR_INVALID.  Every check of the float entries applies.  k2d / kcrop_inout / out / drop_masks: as in capf_forward /
+ *   capf_forward_train, [batch, ...] -- already mirrored / stacked (capf_preprocess_points).  capf_backward after capf_forward_train_u8
+ *   works unchanged: nothing in the backward reads the image.
+ * capf_preprocess_points: the keypoint / ground-truth half of capf_preprocess alone (one launch, the same bits).
+ * capf_input_rule_host: the normalisation rule on the host -- out[i] = ((float)u[i] * (1.0f / 255.0f) - mean[channel]) (/ std3[channel]),
+ *   every step one rounded fp32 operation; the expression the device kernels evaluate (csrc/pixel_rule.h).  channel: RGB index 0..2.
+ * capf_op_conv_u8: the stem conv alone (ks x ks, padding ks / 2, folded BatchNorm, optional ReLU; no residual) from a uint8 image:
+ *   w_packed / bias from capf_op_pack_conv (Cin = 3), y [frames,Ho,Wo,Cout] of out_dtype CAPF_F32 / CAPF_BF16 / CAPF_F16, frames = Bsrc
+ *   (modes 0 / 1) or 2 * Bsrc (mode 2) -- through the dispatch of the plan's stem op.  capf_op_conv_u8_kernel_name names the kernel it
+ *   launches, capf_op_conv_stem_kernel_name the one capf_op_conv / capf_op_conv_16 launch for the float image at B frames ("" where the
+ *   arguments are invalid).
+ * The accounting entries (capf_op_bytes, capf_forward_stats, the roofline figures) keep describing the float-image route.               */
+int capf_forward_u8(capf_handle* h, void* stream, const uint8_t* images_bgr_u8, const float mean[3], const float* std3, int mode,
+                    const float* k2d, float* kcrop_inout, int batch, float* out);
+int capf_backbone_forward_u8(capf_handle* h, void* stream, const uint8_t* images_bgr_u8, const float mean[3], const float* std3, int mode,
+                             int batch);
+int capf_forward_train_u8(capf_handle* h, void* stream, const uint8_t* images_bgr_u8, const float mean[3], const float* std3, int mode,
+                          const float* k2d, float* kcrop_inout, int batch, float* out, const float* drop_masks);
+int capf_preprocess_points(void* stream, int batch, int mode, const float* gt_in, float* gt_out, const float* k2d_in, float* k2d_out,
+                           const float* kcrop_in, float* kcrop_out);
+int capf_input_rule_host(const uint8_t* u, int n, int channel, const float mean[3], const float* std3, float* out);
+int capf_op_conv_u8(void* stream, const uint8_t* images_bgr_u8, const float* w_packed, const float* bias, void* y_nhwc, int Bsrc, int mode,
+                    int H, int W, int Cout, int ks, int stride, int act, const float mean[3], const float* std3, int out_dtype);
+const char* capf_op_conv_u8_kernel_name(int Bsrc, int mode, int H, int W, int Cout, int ks, int stride, int out_dtype);
+const char* capf_op_conv_stem_kernel_name(int B, int H, int W, int Cout, int ks, int stride, int out_dtype);
 /* capf_fliptest_fuse_swap: the same fusion for any skeleton -- ContextPose_mpi/run_3dhp.py:169-180 (input_augmentation: x of the mirrored
  *   prediction negated, joints_left + joints_right swapped, mean of the two) where capf_fliptest_fuse hard-codes the H36M table.
  *   pred2 [2,batch,1,joints,3] -> out [batch,1,joints,3]; swap: HOST int32[joints], swap[j] = the joint of the mirrored prediction that
