@@ -1081,6 +1081,11 @@ int capf_lifter_forward(capf_handle* h, void* stream, const float* k2d, float* k
     Engine& e = h->e;
     int rc = check_run(e, batch);
     if (rc) return rc;
+    if (e.feat_batch != batch) {      // (every buffer lives at offset * batch: maps of another batch are not where this call would sample)
+        e.err = "capf_lifter_forward: the workspace holds no context maps of this batch (capf_set_features or capf_backbone_forward "
+                "of the same batch comes first)";
+        return CAPF_ERR_STATE;
+    }
     e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
     e.last_batch = batch;
     e.invalidate_train();

@@ -283,8 +283,11 @@ int capf_adamw_step_guarded(void* stream, float* params, const float* grads, flo
                             float grad_scale, float max_norm, int64_t attempt, const float* loss, int rows, void* ctrl);
 
 /* Lifter only, on the context maps left in the workspace by the last capf_backbone_forward /
- * capf_forward of the same batch.  Replaces self.volume_net(...) conpose.py:40
- * (PoseTransformer.forward pose_dformer.py:210-241).  kcrop_inout is normalised in place. */
+ * capf_forward of the same batch (or copied there by capf_set_features).  Replaces self.volume_net(...) conpose.py:40
+ * (PoseTransformer.forward pose_dformer.py:210-241).  kcrop_inout is normalised in place.
+ * CAPF_ERR_STATE (capf_last_error says why), like capf_lifter_forward_train, when the workspace holds no whole set of maps of THIS batch:
+ * after a run of another batch (every buffer lives at offset * batch), after a capf_forward_prefix that ended inside the backbone, after
+ * capf_set_workspace.  A refused call launches nothing and leaves the saved training step and capf_train_generation as they were. */
 int capf_lifter_forward(capf_handle* h, void* stream, const float* k2d, float* kcrop_inout, int batch,
                         float* out);
 
