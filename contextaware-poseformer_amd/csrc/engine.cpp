@@ -111,11 +111,11 @@ int Engine::ensure_h2g_lifter(hipStream_t s) {
     return CAPF_OK;
 }
 
-GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes) const {
+GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes, bool side_chain) const {
     auto ptr = [&](int buf) -> float* { return (buf >= 0 && ws) ? bptr(buf, batch) : nullptr; };
     const Pack& pk = packs[op.pack];
     GemmArgs a{};
-    a.A = op.in[0] == -2 ? images : ptr(op.in[0]);
+    a.A = op.in[0] == -2 ? ses.images() : ptr(op.in[0]);
     if (pk.in_place) {
         a.Wp = params[pk.w[0]].ptr;
         a.bias = params[pk.b[0]].ptr;
@@ -164,8 +164,8 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes) const {
     }
     static const bool splitk_on = [] { const char* e = diag_env("CAPF_SPLITK"); return !e || atoi(e) != 0; }();   // A/B runs only
     if ((op.conv || (op.kind == OP_GEMM && op.ln.w < 0 && op.res_param < 0)) && !op.bf16 && split_ws && lanes != 1 && splitk_on) {   // one stream: launches use the scratch one after the other
-        a.split_ws = on_side_chain ? split_ws_side : split_ws;
-        a.split_cnt = on_side_chain ? split_cnt_side : split_cnt;
+        a.split_ws = side_chain ? split_ws_side : split_ws;
+        a.split_cnt = side_chain ? split_cnt_side : split_cnt;
         a.split_ws_elems = SPLIT_WS_ELEMS; a.split_cnt_elems = SPLIT_CNT_ELEMS;
     }
     if (op.ln.w >= 0) {
@@ -287,14 +287,16 @@ FuseSumArgs Engine::fuse_args(const Op& op, int batch) const {
 }
 
 // one non-control op on stream s
-int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
+int Engine::exec_op(const Op& op, hipStream_t s, int batch, bool side_chain) {
     auto ptr = [&](int buf) -> float* {
         if (buf >= 0) return bptr(buf, batch);
         return nullptr;
     };
+    const float* const k2d = ses.k2d;
+    float* const kcrop = ses.kcrop;
     switch (op.kind) {
         case OP_GEMM: {
-            const GemmArgs a = gemm_args(op, batch);
+            const GemmArgs a = gemm_args(op, batch, true, side_chain);
             switch (gemm_family(op, batch)) {
                 case Family::BF16_ROWS:
                     HIP_TRY(launch_gemm_bf16_rows(a.A, a.Wp, a.bias, a.M, a.N, a.K, a.Kpad, a.out, a.omap, a.res, a.rmap, op.out_bf16, s, f16()));
@@ -304,7 +306,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
                 case Family::F32_TILE: HIP_TRY(launch_f32_tile(&a, 1, s)); break;
                 case Family::WINO: HIP_TRY(launch_gemm_wino(a, s)); break;
                 default:
-                    if (op.in[0] == -2 && !images && u8in.img) HIP_TRY(launch_gemm_f32_u8(a, u8in, s));   // the stem from the uint8 crop: same route, U8 form
+                    if (op.in[0] == -2 && ses.u8()) HIP_TRY(launch_gemm_f32_u8(a, *ses.u8(), s));   // the stem from the uint8 crop: same route, U8 form
                     else HIP_TRY(launch_gemm_f32(a, s));
             }
             break;
@@ -414,7 +416,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
         }
         case OP_HEAD:
             HIP_TRY(launch_head(ptr(op.in[0]), params[op.ln.w].ptr, params[op.ln.b].ptr, op.eps, params[op.head.w].ptr,
-                                params[op.head.b].ptr, out, (int)(op.rows_per_frame * batch), op.C, op.head.N, s));
+                                params[op.head.b].ptr, ses.out, (int)(op.rows_per_frame * batch), op.C, op.head.N, s));
             break;
         default: break;
     }
@@ -427,7 +429,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch) {
 // topological order is valid on a single stream, and no two buffers of a region share memory
 // (assign_offsets keeps them alive for the whole region).  With `log` every launch is bracketed by
 // events (profiling): log gets (event index, leader op) pairs and member ops point at their leader.
-int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* log, unsigned lane_mask) {
+int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* log, unsigned lane_mask, bool side_chain) {
     auto mine = [&](const Op& op) { return ((lane_mask >> op.lane) & 1u) != 0; };
     auto groupable = [&](const Op& op, const GemmArgs& a) {
         if (op.kind != OP_GEMM) return false;
@@ -465,7 +467,7 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
             for (int oi : level) {
                 const Op& op = ops[oi];
                 if (op.kind != OP_GEMM || !mine(op) || gemm_family(op, batch) != pass) continue;
-                const GemmArgs a = gemm_args(op, batch);
+                const GemmArgs a = gemm_args(op, batch, true, side_chain);
                 if (!groupable(op, a)) continue;
                 group[n] = a;
                 members[n++] = oi;
@@ -499,7 +501,7 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
                 for (int k = 0; k < nf; ++k) done |= fm[k] == oi;
                 if (done) continue;
                 if (log) HIP_TRY(log->mark(s, &oi, 1));
-                int rc = exec_op(op, s, batch);
+                int rc = exec_op(op, s, batch, side_chain);
                 if (rc) return rc;
             }
         }
@@ -549,9 +551,7 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
                     if (two) {
                         HIP_TRY(hipEventRecord(events[op.fork.first_event], main_stream));
                         HIP_TRY(hipStreamWaitEvent(side[0], events[op.fork.first_event], 0));
-                        on_side_chain = true;
-                        int rc = run_region_grouped(side[0], batch, op.region, nullptr, 0x6u);
-                        on_side_chain = false;
+                        int rc = run_region_grouped(side[0], batch, op.region, nullptr, 0x6u, true);
                         if (rc) return rc;
                         rc = run_region_grouped(main_stream, batch, op.region, nullptr, ~0x6u);
                         if (rc) return rc;
@@ -591,7 +591,78 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
     }
     if (ev) HIP_TRY(hipEventRecord(ev[last_op], main_stream));
     if (log) HIP_TRY(log->mark(main_stream, nullptr, 0));
-    if (first_op == 0) feat_batch = last_op >= n_backbone_ops ? batch : 0;      // (a prefix run leaves the maps half written)
+    if (first_op == 0) ses.maps_written(last_op >= n_backbone_ops ? batch : 0);      // (a prefix run leaves the maps half written)
+    return CAPF_OK;
+}
+
+Engine::~Engine() {
+    for (void* p : {(void*)pack_arena, (void*)split_ws, (void*)split_cnt, (void*)split_ws_side, (void*)split_cnt_side})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t x : events)
+        if (x) (void)hipEventDestroy(x);
+    for (hipStream_t st : side)
+        if (st) (void)hipStreamDestroy(st);
+}
+
+int Engine::check_run(int batch) {
+    if (device < 0) {
+        err = "plan-only handle (device < 0)";
+        return CAPF_ERR_STATE;
+    }
+    if (batch <= 0 || batch > cfg.max_batch) {
+        err = "batch out of range (1..max_batch)";
+        return CAPF_ERR_INVALID;
+    }
+    if (batch > batch_limit) {
+        err = "batch too large for this input size: the kernels address one activation tensor with 32-bit offsets (limit " +
+              std::to_string(batch_limit) + " frames)";
+        return CAPF_ERR_UNSUPPORTED;
+    }
+    if (!packed) {
+        err = "capf_params_changed has not been called since the last capf_set_param";
+        return CAPF_ERR_STATE;
+    }
+    if (!ws || ws_bytes < workspace_bytes(batch)) {
+        err = "workspace missing or too small";
+        return CAPF_ERR_STATE;
+    }
+    return CAPF_OK;
+}
+
+// The checks in the order every entry has always made them: training, the uint8 source's own (capf_forward_u8 and its siblings: nothing but
+// the stem's load differs from the float entries, launch_gemm_f32_u8), check_run, the maps, the uint8 stem.  Then, and only then, the state
+int Engine::begin(const Call& c) {
+    if (c.training && !cfg.training) {
+        err = "handle was created with training = 0";
+        return CAPF_ERR_STATE;
+    }
+    const U8Input* u8 = std::get_if<U8Input>(&c.image);
+    if (u8) {
+        if (!u8->img) return CAPF_ERR_INVALID;             // (a null image or mean: u8_source)
+        if (u8->mode < 0 || u8->mode > 2) {
+            err = "mode must be 0 (as is), 1 (every frame mirrored) or 2 (flip test: [orig | mirrored])";
+            return CAPF_ERR_INVALID;
+        }
+        if (u8->mode == 2 && (c.batch & 1)) {
+            err = "mode 2 runs 2 * Bsrc engine frames: batch must be even";
+            return CAPF_ERR_INVALID;
+        }
+    }
+    if (const int rc = check_run(c.batch)) return rc;
+    if (c.maps && ses.feat_batch != c.batch) {      // (every buffer lives at offset * batch: maps of another batch are not where this call would sample)
+        err = std::string(c.who) + ": the workspace holds no context maps of this batch (capf_set_features or capf_backbone_forward "
+              "of the same batch comes first)";
+        return CAPF_ERR_STATE;
+    }
+    if (u8 && (stem_op < 0 || gemm_family(ops[stem_op], c.batch) != Family::F32 || ops[stem_op].Cin != 3)) {
+        err = "this plan has no single Cin = 3 stem conv reading the image";
+        return CAPF_ERR_UNSUPPORTED;
+    }
+    ses.image = c.image;
+    ses.k2d = c.k2d; ses.kcrop = c.kcrop; ses.out = c.out;
+    ses.last_batch = c.batch;
+    if (c.maps) ses.invalidate_train();
+    else ses.drop_maps();                                  // (until run() or capf_set_features has written them)
     return CAPF_OK;
 }
 
@@ -673,19 +744,7 @@ int capf_create(const capf_config* cfg, int device, capf_handle** out) {
     return CAPF_OK;
 }
 
-void capf_destroy(capf_handle* h) {
-    if (!h) return;
-    if (h->e.pack_arena) (void)hipFree(h->e.pack_arena);
-    if (h->e.split_ws) (void)hipFree(h->e.split_ws);
-    if (h->e.split_cnt) (void)hipFree(h->e.split_cnt);
-    if (h->e.split_ws_side) (void)hipFree(h->e.split_ws_side);
-    if (h->e.split_cnt_side) (void)hipFree(h->e.split_cnt_side);
-    for (auto& x : h->e.events)
-        if (x) (void)hipEventDestroy(x);
-    for (auto& st : h->e.side)
-        if (st) (void)hipStreamDestroy(st);
-    delete h;
-}
+void capf_destroy(capf_handle* h) { delete h; }      // (~Engine releases what the handle owns on the device)
 
 int capf_max_batch(const capf_handle* h) { return h ? (h->e.batch_limit < h->e.cfg.max_batch ? h->e.batch_limit : h->e.cfg.max_batch) : CAPF_ERR_INVALID; }
 
@@ -739,19 +798,13 @@ int capf_params_changed(capf_handle* h, void* stream) {
     return h->e.repack(static_cast<hipStream_t>(stream));
 }
 
-size_t capf_workspace_bytes(const capf_handle* h, int batch) {
-    if (!h || batch <= 0) return 0;
-    size_t n = h->e.ws_elems_per_frame * (size_t)batch;
-    if (h->e.cfg.training) n += h->e.train_elems(batch);
-    return n * sizeof(float);
-}
+size_t capf_workspace_bytes(const capf_handle* h, int batch) { return h && batch > 0 ? h->e.workspace_bytes(batch) : 0; }
 
 int capf_set_workspace(capf_handle* h, void* dev_ptr, size_t bytes) {
     if (!h) return CAPF_ERR_INVALID;
     h->e.ws = static_cast<float*>(dev_ptr);
     h->e.ws_bytes = bytes;
-    h->e.invalidate_train();
-    h->e.feat_batch = 0;
+    h->e.ses.drop_maps();
     return CAPF_OK;
 }
 
@@ -768,154 +821,78 @@ int capf_set_debug(capf_handle* h, int on) {
     return CAPF_OK;
 }
 
-static size_t capf_workspace_bytes_impl(const Engine& e, int batch) {
-    size_t n = e.ws_elems_per_frame * (size_t)batch;
-    if (e.cfg.training) n += e.train_elems(batch);
-    return n * sizeof(float);
+// ---- the run entries.  Each makes its own null checks, describes itself as a Call and hands it to begin(): the order of the checks and the
+// session state are begin()'s alone.  begin_and_run: begin(), the call's op span, and behind it the training step's lifter where the call is one
+using capf::Call;
+
+static int begin_and_run(Engine& e, void* stream, const Call& c, const float* drop_masks = nullptr) {
+    if (const int rc = e.begin(c)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = e.run(s, c.batch, c.first, c.last)) return rc;
+    return c.training ? e.forward_train(s, c.batch, drop_masks) : CAPF_OK;
 }
 
-static int check_run(Engine& e, int batch) {
-    if (e.device < 0) {
-        e.err = "plan-only handle (device < 0)";
-        return CAPF_ERR_STATE;
-    }
-    if (batch <= 0 || batch > e.cfg.max_batch) {
-        e.err = "batch out of range (1..max_batch)";
-        return CAPF_ERR_INVALID;
-    }
-    if (batch > e.batch_limit) {
-        e.err = "batch too large for this input size: the kernels address one activation tensor with 32-bit offsets (limit " +
-                std::to_string(e.batch_limit) + " frames)";
-        return CAPF_ERR_UNSUPPORTED;
-    }
-    if (!e.packed) {
-        e.err = "capf_params_changed has not been called since the last capf_set_param";
-        return CAPF_ERR_STATE;
-    }
-    if (!e.ws || e.ws_bytes < capf_workspace_bytes_impl(e, batch)) {
-        e.err = "workspace missing or too small";
-        return CAPF_ERR_STATE;
-    }
-    return CAPF_OK;
+// the uint8 BGR crop of capf_forward_u8 and its siblings as an image source.  A null image or mean gives a source without an image, which
+// begin() refuses where these entries always have: behind the training check, in front of the mode's
+static capf::ImageSource u8_source(const uint8_t* images_bgr_u8, const float* mean, const float* std3, int mode, int batch) {
+    capf::U8Input u{};
+    if (!images_bgr_u8 || !mean) return u;
+    u.img = images_bgr_u8;
+    u.Bsrc = mode == 2 ? batch / 2 : batch;
+    u.mode = mode;
+    for (int c = 0; c < 3; ++c) { u.mean[c] = mean[c]; u.stdv[c] = std3 ? std3[c] : 1.f; }
+    u.use_std = std3 ? 1 : 0;
+    return u;
 }
 
 int capf_forward(capf_handle* h, void* stream, const float* images_nhwc, const float* k2d, float* kcrop_inout,
                  int batch, float* out) {
     if (!h || !images_nhwc || !k2d || !kcrop_inout || !out) return CAPF_ERR_INVALID;
-    Engine& e = h->e;
-    int rc = check_run(e, batch);
-    if (rc) return rc;
-    e.images = images_nhwc; e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
-    e.last_batch = batch;
-    e.invalidate_train();
-    return e.run(static_cast<hipStream_t>(stream), batch, 0, (int)e.ops.size());
+    return begin_and_run(h->e, stream, {"capf_forward", images_nhwc, k2d, kcrop_inout, out, batch, 0, (int)h->e.ops.size()});
 }
 
 int capf_backbone_forward(capf_handle* h, void* stream, const float* images_nhwc, int batch) {
     if (!h || !images_nhwc) return CAPF_ERR_INVALID;
-    Engine& e = h->e;
-    int rc = check_run(e, batch);
-    if (rc) return rc;
-    e.images = images_nhwc;
-    e.last_batch = batch;
-    e.invalidate_train();
-    return e.run(static_cast<hipStream_t>(stream), batch, 0, e.n_backbone_ops);
+    return begin_and_run(h->e, stream, {"capf_backbone_forward", images_nhwc, nullptr, nullptr, nullptr, batch, 0, h->e.n_backbone_ops});
 }
 
 int capf_forward_train(capf_handle* h, void* stream, const float* images_nhwc, const float* k2d, float* kcrop_inout,
                        int batch, float* out, const float* drop_masks) {
     if (!h || !images_nhwc || !k2d || !kcrop_inout || !out) return CAPF_ERR_INVALID;
-    Engine& e = h->e;
-    if (!e.cfg.training) {
-        e.err = "handle was created with training = 0";
-        return CAPF_ERR_STATE;
-    }
-    int rc = check_run(e, batch);
-    if (rc) return rc;
-    e.images = images_nhwc; e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
-    e.last_batch = batch;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    e.invalidate_train();
-    rc = e.run(s, batch, 0, e.n_backbone_ops);
-    if (rc) return rc;
-    return e.forward_train(s, batch, drop_masks);
-}
-
-// ---- the same three entries from the uint8 BGR crop: nothing but the stem's load differs (launch_gemm_f32_u8), so every check, every other
-// launch and every result bit is the float entry's on capf_preprocess's output
-static int u8_begin(capf_handle* h, const uint8_t* images_bgr_u8, const float* mean, const float* std3, int mode, int batch) {
-    if (!h || !images_bgr_u8 || !mean) return CAPF_ERR_INVALID;
-    Engine& e = h->e;
-    if (mode < 0 || mode > 2) {
-        e.err = "mode must be 0 (as is), 1 (every frame mirrored) or 2 (flip test: [orig | mirrored])";
-        return CAPF_ERR_INVALID;
-    }
-    if (mode == 2 && (batch & 1)) {
-        e.err = "mode 2 runs 2 * Bsrc engine frames: batch must be even";
-        return CAPF_ERR_INVALID;
-    }
-    const int rc = check_run(e, batch);
-    if (rc) return rc;
-    const capf::Op* stem = nullptr;
-    for (const auto& op : e.ops)
-        if (op.kind == capf::OP_GEMM && op.in[0] == -2) {
-            if (stem || e.gemm_family(op, batch) != Engine::Family::F32) stem = nullptr;
-            else stem = &op;
-            if (!stem) break;
-        }
-    if (!stem || stem->Cin != 3) {
-        e.err = "this plan has no single Cin = 3 stem conv reading the image";
-        return CAPF_ERR_UNSUPPORTED;
-    }
-    e.images = nullptr;
-    e.u8in = capf::U8Input{};
-    e.u8in.img = images_bgr_u8;
-    e.u8in.Bsrc = mode == 2 ? batch / 2 : batch;
-    e.u8in.mode = mode;
-    for (int c = 0; c < 3; ++c) { e.u8in.mean[c] = mean[c]; e.u8in.stdv[c] = std3 ? std3[c] : 1.f; }
-    e.u8in.use_std = std3 ? 1 : 0;
-    return CAPF_OK;
+    return begin_and_run(h->e, stream, {"capf_forward_train", images_nhwc, k2d, kcrop_inout, out, batch, 0, h->e.n_backbone_ops, true}, drop_masks);
 }
 
 int capf_forward_u8(capf_handle* h, void* stream, const uint8_t* images_bgr_u8, const float mean[3], const float* std3, int mode,
                     const float* k2d, float* kcrop_inout, int batch, float* out) {
     if (!h || !k2d || !kcrop_inout || !out) return CAPF_ERR_INVALID;
-    Engine& e = h->e;
-    int rc = u8_begin(h, images_bgr_u8, mean, std3, mode, batch);
-    if (rc) return rc;
-    e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
-    e.last_batch = batch;
-    e.invalidate_train();
-    return e.run(static_cast<hipStream_t>(stream), batch, 0, (int)e.ops.size());
+    return begin_and_run(h->e, stream, {"capf_forward_u8", u8_source(images_bgr_u8, mean, std3, mode, batch), k2d, kcrop_inout, out, batch, 0,
+                                        (int)h->e.ops.size()});
 }
 
 int capf_backbone_forward_u8(capf_handle* h, void* stream, const uint8_t* images_bgr_u8, const float mean[3], const float* std3, int mode,
                              int batch) {
-    int rc = u8_begin(h, images_bgr_u8, mean, std3, mode, batch);
-    if (rc) return rc;
-    Engine& e = h->e;
-    e.last_batch = batch;
-    e.invalidate_train();
-    return e.run(static_cast<hipStream_t>(stream), batch, 0, e.n_backbone_ops);
+    if (!h) return CAPF_ERR_INVALID;
+    return begin_and_run(h->e, stream, {"capf_backbone_forward_u8", u8_source(images_bgr_u8, mean, std3, mode, batch), nullptr, nullptr, nullptr,
+                                        batch, 0, h->e.n_backbone_ops});
 }
 
 int capf_forward_train_u8(capf_handle* h, void* stream, const uint8_t* images_bgr_u8, const float mean[3], const float* std3, int mode,
                           const float* k2d, float* kcrop_inout, int batch, float* out, const float* drop_masks) {
     if (!h || !k2d || !kcrop_inout || !out) return CAPF_ERR_INVALID;
-    Engine& e = h->e;
-    if (!e.cfg.training) {
-        e.err = "handle was created with training = 0";
-        return CAPF_ERR_STATE;
-    }
-    int rc = u8_begin(h, images_bgr_u8, mean, std3, mode, batch);
-    if (rc) return rc;
-    e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
-    e.last_batch = batch;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    e.invalidate_train();
-    rc = e.run(s, batch, 0, e.n_backbone_ops);
-    if (rc) return rc;
-    return e.forward_train(s, batch, drop_masks);
+    return begin_and_run(h->e, stream, {"capf_forward_train_u8", u8_source(images_bgr_u8, mean, std3, mode, batch), k2d, kcrop_inout, out, batch, 0,
+                                        h->e.n_backbone_ops, true}, drop_masks);
+}
+
+int capf_lifter_forward(capf_handle* h, void* stream, const float* k2d, float* kcrop_inout, int batch, float* out) {
+    if (!h || !k2d || !kcrop_inout || !out) return CAPF_ERR_INVALID;
+    return begin_and_run(h->e, stream, {"capf_lifter_forward", {}, k2d, kcrop_inout, out, batch, h->e.n_backbone_ops, (int)h->e.ops.size(), false, true});
+}
+
+int capf_lifter_forward_train(capf_handle* h, void* stream, const float* k2d, float* kcrop_inout, int batch, float* out,
+                              const float* drop_masks) {
+    if (!h || !k2d || !kcrop_inout || !out) return CAPF_ERR_INVALID;
+    const int nb = h->e.n_backbone_ops;                    // (an empty span: the training step's lifter is all that runs)
+    return begin_and_run(h->e, stream, {"capf_lifter_forward_train", {}, k2d, kcrop_inout, out, batch, nb, nb, true, true}, drop_masks);
 }
 
 int capf_backward(capf_handle* h, void* stream, const float* grad_out, int batch, float* flat_grad, const float* drop_masks) {
@@ -942,11 +919,8 @@ int capf_set_features(capf_handle* h, void* stream, const float* const feat_nhwc
         e.err = "capf_set_features: batch out of range (1..capf_max_batch)";
         return CAPF_ERR_INVALID;
     }
-    if ((rc = check_run(e, batch))) return rc;
+    if ((rc = e.begin({"capf_set_features", {}, nullptr, nullptr, nullptr, batch, 0, 0}))) return rc;      // (no op runs: the copies below write the maps)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    e.invalidate_train();
-    e.feat_batch = 0;
-    e.last_batch = batch;
     for (int l = 0; l < e.cfg.levels; ++l) {
         const size_t bytes = sizeof(float) * (size_t)batch * e.feat_H[l] * e.feat_W[l] * e.feat_C[l];
         if (hipMemcpyAsync(e.bptr(e.feat_buf[l], batch), feat_nhwc[l], bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) {
@@ -954,29 +928,8 @@ int capf_set_features(capf_handle* h, void* stream, const float* const feat_nhwc
             return CAPF_ERR_HIP;
         }
     }
-    e.feat_batch = batch;
+    e.ses.maps_written(batch);
     return CAPF_OK;
-}
-
-int capf_lifter_forward_train(capf_handle* h, void* stream, const float* k2d, float* kcrop_inout, int batch, float* out,
-                              const float* drop_masks) {
-    if (!h || !k2d || !kcrop_inout || !out) return CAPF_ERR_INVALID;
-    Engine& e = h->e;
-    if (!e.cfg.training) {
-        e.err = "handle was created with training = 0";
-        return CAPF_ERR_STATE;
-    }
-    int rc = check_run(e, batch);
-    if (rc) return rc;
-    if (e.feat_batch != batch) {
-        e.err = "capf_lifter_forward_train: the workspace holds no context maps of this batch (capf_set_features or capf_backbone_forward "
-                "of the same batch comes first)";
-        return CAPF_ERR_STATE;
-    }
-    e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
-    e.last_batch = batch;
-    e.invalidate_train();
-    return e.forward_train(static_cast<hipStream_t>(stream), batch, drop_masks);
 }
 
 int capf_backward_maps(capf_handle* h, void* stream, const float* grad_out, int batch, float* flat_grad, const float* drop_masks,
@@ -1008,7 +961,7 @@ int capf_set_map_grad_mode(capf_handle* h, int mode) {
 
 int capf_map_grad_mode(const capf_handle* h) { return h ? h->e.map_grad_mode : -1; }
 
-int64_t capf_train_generation(const capf_handle* h) { return h ? h->e.train_generation : -1; }
+int64_t capf_train_generation(const capf_handle* h) { return h ? h->e.ses.train_generation : -1; }
 
 int64_t capf_grad_elems(const capf_handle* h) { return h ? h->e.grad_elems : -1; }
 
@@ -1076,22 +1029,6 @@ int capf_adamw_step_guarded(void* stream, float* params, const float* grads, flo
                ? CAPF_OK : CAPF_ERR_HIP;
 }
 
-int capf_lifter_forward(capf_handle* h, void* stream, const float* k2d, float* kcrop_inout, int batch, float* out) {
-    if (!h || !k2d || !kcrop_inout || !out) return CAPF_ERR_INVALID;
-    Engine& e = h->e;
-    int rc = check_run(e, batch);
-    if (rc) return rc;
-    if (e.feat_batch != batch) {      // (every buffer lives at offset * batch: maps of another batch are not where this call would sample)
-        e.err = "capf_lifter_forward: the workspace holds no context maps of this batch (capf_set_features or capf_backbone_forward "
-                "of the same batch comes first)";
-        return CAPF_ERR_STATE;
-    }
-    e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
-    e.last_batch = batch;
-    e.invalidate_train();
-    return e.run(static_cast<hipStream_t>(stream), batch, e.n_backbone_ops, (int)e.ops.size());
-}
-
 int capf_tensor(const capf_handle* h, const char* name, const void** dev_ptr, int64_t shape[4], int* ndim) {
     if (!h || !name) return CAPF_ERR_INVALID;
     const Engine& e = h->e;
@@ -1100,10 +1037,10 @@ int capf_tensor(const capf_handle* h, const char* name, const void** dev_ptr, in
     const capf::NamedTensor& t = it->second;
     if (shape) {
         for (int i = 0; i < 4; ++i) shape[i] = t.shape[i];
-        shape[0] = e.last_batch;
+        shape[0] = e.ses.last_batch;
     }
     if (ndim) *ndim = t.ndim;
-    if (dev_ptr) *dev_ptr = (e.ws && e.last_batch > 0) ? e.bptr(t.buf, e.last_batch) : nullptr;
+    if (dev_ptr) *dev_ptr = (e.ws && e.ses.last_batch > 0) ? e.bptr(t.buf, e.ses.last_batch) : nullptr;
     return t.is_int;      // 0 fp32, 1 int32, 2 bf16, 3 fp16
 }
 
@@ -1734,12 +1671,7 @@ int capf_forward_prefix(capf_handle* h, void* stream, const float* images_nhwc, 
     Engine& e = h->e;
     if (n_ops < 0 || n_ops > (int)e.ops.size()) return CAPF_ERR_INVALID;
     if (n_ops > e.n_backbone_ops && (!k2d || !kcrop_inout || !out)) return CAPF_ERR_INVALID;
-    int rc = check_run(e, batch);
-    if (rc) return rc;
-    e.images = images_nhwc; e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
-    e.last_batch = batch;
-    e.invalidate_train();
-    return e.run(static_cast<hipStream_t>(stream), batch, 0, n_ops);
+    return begin_and_run(e, stream, {"capf_forward_prefix", images_nhwc, k2d, kcrop_inout, out, batch, 0, n_ops});
 }
 
 int capf_op_describe(const capf_handle* h, int index, capf_op_desc* d) {
@@ -1822,9 +1754,9 @@ int capf_op_tensor(const capf_handle* h, int index, int slot, const void** dev_p
     // slots 0..4: capf_op_schedule's reads (the map a conv adds behind its activation in slot 1), 5: the output, 6: its bf16 shadow
     const auto r = op.reads();
     const int buf = slot == 1 && r[5] >= 0 ? r[5] : slot < 5 ? r[slot] : slot == 5 ? op.out : op.sh;
-    if (buf == -2) { *dev_ptr = e.images; return CAPF_OK; }
-    if (buf < 0 || !e.ws || e.last_batch <= 0) return CAPF_ERR_INVALID;
-    *dev_ptr = e.bptr(buf, e.last_batch);
+    if (buf == -2) { *dev_ptr = e.ses.images(); return CAPF_OK; }
+    if (buf < 0 || !e.ws || e.ses.last_batch <= 0) return CAPF_ERR_INVALID;
+    *dev_ptr = e.bptr(buf, e.ses.last_batch);
     return CAPF_OK;
 }
 
@@ -1848,20 +1780,18 @@ int capf_forward_profile(capf_handle* h, void* stream, const float* images_nhwc,
     Engine& e = h->e;
     const int n = (int)e.ops.size();
     if (n_ops < n) return CAPF_ERR_INVALID;
-    int rc = check_run(e, batch);
+    int rc = e.begin({"capf_forward_profile", images_nhwc, k2d, kcrop_inout, out, batch, 0, n});
     if (rc) return rc;
-    e.images = images_nhwc; e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
-    e.last_batch = batch;
-    e.invalidate_train();
-    std::vector<hipEvent_t> ev(n + 1);
+    std::vector<hipEvent_t> ev(n + 1, nullptr);
     for (auto& x : ev)
-        if (hipEventCreate(&x) != hipSuccess) return CAPF_ERR_HIP;
+        if (rc == CAPF_OK && hipEventCreate(&x) != hipSuccess) rc = CAPF_ERR_HIP;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = e.run(s, batch, 0, n, ev.data());
+    if (rc == CAPF_OK) rc = e.run(s, batch, 0, n, ev.data());
     if (rc == CAPF_OK && hipStreamSynchronize(s) != hipSuccess) rc = CAPF_ERR_HIP;
     for (int i = 0; i < n && rc == CAPF_OK; ++i)
         if (hipEventElapsedTime(&op_ms[i], ev[i], ev[i + 1]) != hipSuccess) rc = CAPF_ERR_HIP;
-    for (auto& x : ev) (void)hipEventDestroy(x);
+    for (auto& x : ev)                                     // (on every path: the events made before one could not be)
+        if (x) (void)hipEventDestroy(x);
     return rc;
 }
 
@@ -1871,17 +1801,14 @@ int capf_forward_profile_launches(capf_handle* h, void* stream, const float* ima
     Engine& e = h->e;
     const int n = (int)e.ops.size();
     if (n_ops < n) return CAPF_ERR_INVALID;
-    int rc = check_run(e, batch);
+    int rc = e.begin({"capf_forward_profile_launches", images_nhwc, k2d, kcrop_inout, out, batch, 0, n});
     if (rc) return rc;
-    e.images = images_nhwc; e.k2d = k2d; e.kcrop = kcrop_inout; e.out = out;
-    e.last_batch = batch;
-    e.invalidate_train();
     capf::LaunchLog log;
     log.op_leader.assign(n, -1);
     log.op_variant.assign(n, -1);
     hipStream_t s = static_cast<hipStream_t>(stream);
     rc = e.run(s, batch, 0, n, nullptr, &log);
-    e.last_variants = log.op_variant;
+    e.ses.last_variants = log.op_variant;
     if (rc == CAPF_OK && hipStreamSynchronize(s) != hipSuccess) rc = CAPF_ERR_HIP;
     for (int i = 0; i < n; ++i) { op_ms[i] = 0.f; op_leader[i] = log.op_leader[i]; }
     for (size_t k = 0; k < log.leader.size() && rc == CAPF_OK; ++k)
@@ -1890,8 +1817,8 @@ int capf_forward_profile_launches(capf_handle* h, void* stream, const float* ima
 }
 
 int capf_forward_profile_variants(const capf_handle* h, int32_t* op_variant, int n_ops) {
-    if (!h || !op_variant || n_ops < (int)h->e.last_variants.size()) return CAPF_ERR_INVALID;
-    for (size_t i = 0; i < h->e.last_variants.size(); ++i) op_variant[i] = h->e.last_variants[i];
+    if (!h || !op_variant || n_ops < (int)h->e.ses.last_variants.size()) return CAPF_ERR_INVALID;
+    for (size_t i = 0; i < h->e.ses.last_variants.size(); ++i) op_variant[i] = h->e.ses.last_variants[i];
     return CAPF_OK;
 }
 

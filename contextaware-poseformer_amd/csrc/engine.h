@@ -7,6 +7,7 @@
 #include <array>
 #include <map>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "capf.h"
@@ -223,7 +224,45 @@ struct LaunchLog {
     }
 };
 
+// Where a run's stem reads the image: nowhere (a lifter-only call, capf_set_features), an fp32 NHWC tensor, or a uint8 BGR crop
+using ImageSource = std::variant<std::monostate, const float*, U8Input>;
+
+// What a call leaves behind for the next one.  Engine::begin writes it, in one place and only after every check of the call has passed;
+// the other writers are the mutators below, the training step (train_batch, t_h2_base: train.cpp) and capf_forward_profile_launches
+// (last_variants), all behind a begin() that passed -- a refused call changes nothing here
+struct Session {
+    ImageSource image;
+    const float* k2d = nullptr;          // the lifter's pointers (null behind a call that ran no lifter op)
+    float* kcrop = nullptr;
+    float* out = nullptr;
+    int last_batch = 0;                  // batch of the tensors capf_tensor / capf_op_tensor hand out
+    int feat_batch = 0;                  // batch of the context maps feat0..3 in the workspace (a whole backbone run or capf_set_features; 0: none)
+    int train_batch = 0;                 // batch of the forward_train whose activations are still in the workspace (0: none)
+    int64_t train_generation = 0;        // bumped by every run that (over)writes the workspace
+    float* t_h2_base = nullptr;          // the saved step's W / W^T packs (set by t_h2_prepare; nullptr: the step runs on the fp32 matrix pipe)
+    std::vector<int> last_variants;      // capf_forward_profile_launches: grouped-bf16 kernel variant per leader op
+
+    const float* images() const { const auto* p = std::get_if<const float*>(&image); return p ? *p : nullptr; }
+    const U8Input* u8() const { return std::get_if<U8Input>(&image); }
+    void invalidate_train() { train_batch = 0; ++train_generation; t_h2_base = nullptr; }    // the workspace is about to be (over)written
+    void drop_maps() { invalidate_train(); feat_batch = 0; }                                   // ... its context maps included
+    void maps_written(int batch) { feat_batch = batch; }     // the end of run() and of capf_set_features (0: a prefix run left them half written)
+};
+
+// One call of a run entry as begin() sees it
+struct Call {
+    const char* who;                     // the entry's name, as the messages spell it
+    ImageSource image;
+    const float* k2d; float* kcrop; float* out;      // the lifter's pointers (all null: the call runs no lifter op)
+    int batch;
+    int first, last;                     // the op span [first, last) it runs
+    bool training = false;               // the training step's lifter forward follows the span: refused by a handle created with training = 0
+    bool maps = false;                   // reads context maps of this batch that an earlier call left (otherwise it writes the maps itself)
+};
+
 struct Engine {
+    Engine() = default;
+    Engine(const Engine&) = delete;
     capf_config cfg{};
     int device = -1;
     std::string err;
@@ -263,6 +302,7 @@ struct Engine {
     std::vector<Pack> packs;
     std::vector<Op> ops;
     int n_backbone_ops = 0;
+    int stem_op = -1;              // the one conv that reads the image (-1: none, -2: several)
     int cur_lane = 0, cur_region = -1, n_regions = 0, n_events = 0;
     std::vector<std::pair<int, int>> regions;   // [fork op, join op]
     std::vector<std::vector<std::vector<int>>> region_levels;   // per region: dependency levels -> op indices
@@ -314,7 +354,6 @@ struct Engine {
     // counters of their own (a conv splits or not by its shape alone, so both chains may hold splitting convs at once)
     float* split_ws_side = nullptr;
     int* split_cnt_side = nullptr;
-    bool on_side_chain = false;    // set around run_region_grouped(side[0], ...)
     static constexpr long SPLIT_WS_ELEMS = 4L << 20;
     static constexpr int SPLIT_CNT_ELEMS = 16384;
     float* ws = nullptr;           // device, borrowed
@@ -327,14 +366,8 @@ struct Engine {
     int map_grad_mode = 0;         // dfeat of capf_backward_maps: 0 fp32 atomic adds, 1 the ordered sum (capf_set_map_grad_mode)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> events;
-    std::vector<int> last_variants;   // capf_forward_profile_launches: grouped-bf16 kernel variant per leader op
-    int last_batch = 0;
-    const float* images = nullptr;
-    U8Input u8in{};                // capf_forward_u8 and its siblings: the uint8 crop the stem reads instead (they leave `images` null; the float
-                                   // entries always set it, so a null `images` with u8in.img set is what selects the stem's U8 form)
-    const float* k2d = nullptr;
-    float* kcrop = nullptr;
-    float* out = nullptr;
+    Session ses;                   // what the last call left behind (begin())
+    ~Engine();                     // the ONE release path of the device resources above (capf_destroy, and capf_create where it fails half-way)
 
     // ---- execution (engine.cpp)
     float* bptr(int buf, int batch) const { return ws + bufs[buf].offset * (size_t)batch; }
@@ -342,8 +375,11 @@ struct Engine {
     ConvSrc conv_src(const Pack& pk) const;
     int repack(hipStream_t s, bool lifter_only = false);
     int ensure_h2g_lifter(hipStream_t s);
+    size_t workspace_bytes(int batch) const { return (ws_elems_per_frame * (size_t)batch + (cfg.training ? train_elems(batch) : 0)) * sizeof(float); }
+    int check_run(int batch);      // can this handle run this batch at all: a device, the batch range, fresh packs, a workspace that holds it
+    int begin(const Call& c);      // every precondition of a run entry, then -- all passed -- the session state of the call
     int run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t* ev = nullptr, LaunchLog* log = nullptr);
-    int exec_op(const Op& op, hipStream_t s, int batch);
+    int exec_op(const Op& op, hipStream_t s, int batch, bool side_chain = false);
     bool skipped(const Op& op) const { return op.debug_only && !debug; }   // a debug copy outside a debug run: no launch, no log entry
     FuseSumArgs fuse_args(const Op& op, int batch) const;
     // ---- launch routes: pure functions of (op, batch) and the plan (no cache, no mutable state -- const-handle queries on other threads may ask
@@ -370,16 +406,14 @@ struct Engine {
     struct FusedLaunch { Fusion kind = Fusion::NONE; int n = 0; int m[4] = {-1, -1, -1, -1}; };
     FusedLaunch fused_at(int i, int batch, int last_op, bool bneck_only = false) const;
     FusedLaunch fused_leader(int i, int batch, bool bneck_only = false) const;
-    int run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* log, unsigned lane_mask = ~0u);
+    // side_chain: the launches belong to the second of two concurrent chains and take its split-K scratch (default: the main chain's, which
+    // is what every query about an op sees)
+    int run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* log, unsigned lane_mask = ~0u, bool side_chain = false);
     // lanes == 3 runs the region behind this fork op as two chains at this batch (on a device: run())
     bool two_chains(const Op& fork_op, int batch) const { return lanes == 3 && fork_op.fork.lanes >= 2 && batch >= 16 && batch <= 128; }
-    GemmArgs gemm_args(const Op& op, int batch, bool planes = true) const;
+    GemmArgs gemm_args(const Op& op, int batch, bool planes = true, bool side_chain = false) const;
 
     // ---- training step (train.cpp)
-    int train_batch = 0;                 // batch of the forward_train whose activations are still in the workspace (0: none)
-    int64_t train_generation = 0;        // bumped by every run that (over)writes the workspace
-    void invalidate_train() { train_batch = 0; ++train_generation; t_h2_base = nullptr; }
-    int feat_batch = 0;                  // batch of the context maps feat0..3 in the workspace (a whole backbone run or capf_set_features; 0: none)
     void train_layout(int B, TrainLayout& L) const;
     size_t train_elems(int B) const;
     int forward_train(hipStream_t s, int B, const float* masks);
@@ -409,7 +443,6 @@ struct Engine {
     int t_colreduce(hipStream_t s, const TrainLayout& L, float* tw, const float* A, RowMap amap, const float* Bm, RowMap bmap, int bmode,
                     int rows, int C, float* dst, long dst_stride, float* dst2, size_t cap_elems);
     int t_col_flush(hipStream_t s);
-    float* t_h2_base = nullptr;          // this step's packs (set by t_h2_prepare; nullptr: the step runs on the fp32 matrix pipe)
     void t_h2_plan();
     int t_h2_prepare(hipStream_t s, const TrainLayout& L, float* tw, int B);
     const float* t_h2_pack(const float* W, bool transposed) const;

@@ -1183,6 +1183,7 @@ bool Engine::build() {
     for (const Op& op : ops)        // "stem": the output of the conv that reads the image.  NOT kept alive (name_tensor would pin 64 channels at half
         if (op.kind == OP_GEMM && op.in[0] == EXT_IMAGES) {       // resolution per frame in every workspace): later ops of a run reuse its memory, so what it
             NamedTensor t{};                                       // holds after a run is a function of the run alone -- two routes of one plan compare bit for bit
+            stem_op = stem_op == -1 ? (int)(&op - ops.data()) : -2;
             t.buf = op.out;
             t.ndim = 4;
             t.shape[0] = -1; t.shape[1] = op.Ho; t.shape[2] = op.Wo; t.shape[3] = op.N;

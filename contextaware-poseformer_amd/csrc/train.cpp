@@ -162,7 +162,7 @@ void Engine::t_h2_plan() {
 
 // pack every matrix of the table from the CURRENT parameters (three launches); the packs live until the next forward_train
 int Engine::t_h2_prepare(hipStream_t s, const TrainLayout& L, float* tw, int B) {
-    t_h2_base = nullptr;
+    ses.t_h2_base = nullptr;
     t_h2_index.clear();
     if (t_h2_specs.empty() || B < H2G_MIN_BATCH) return CAPF_OK;
     bool same = t_h2_on_device;
@@ -185,16 +185,16 @@ int Engine::t_h2_prepare(hipStream_t s, const TrainLayout& L, float* tw, int B) 
     }
     HIP_TRY(launch_pack_f32h2_train(tab_dev, (int)t_h2_tab.size(), t_h2_tiles, tw + L.h2w, reinterpret_cast<int*>(tw + L.h2max),
                                     (long)t_h2_max_elems, s));
-    t_h2_base = tw + L.h2w;
+    ses.t_h2_base = tw + L.h2w;
     return CAPF_OK;
 }
 
 const float* Engine::t_h2_pack(const float* W, bool transposed) const {
-    if (!t_h2_base) return nullptr;
+    if (!ses.t_h2_base) return nullptr;
     const auto it = t_h2_index.find(W);
     if (it == t_h2_index.end()) return nullptr;
     const long off = transposed ? t_h2_tab[it->second].bwd_off : t_h2_tab[it->second].fwd_off;
-    return off < 0 ? nullptr : t_h2_base + off;
+    return off < 0 ? nullptr : ses.t_h2_base + off;
 }
 
 int Engine::t_gemm(hipStream_t s, const float* A, RowMap amap, int M, int N, int K, const float* W, int Kpad,
@@ -288,7 +288,7 @@ int Engine::t_linear_bwd(hipStream_t s, const TrainLayout& L, float* tw, const f
         if (gb && !bias_here) {
             if (int rc = t_colreduce(s, L, tw, dY, dymap, nullptr, row_ld(0), 0, rows, N, gb, 1, nullptr, L.red_cap)) return rc;
         }
-        const bool h2 = t_h2_base && N % 128 == 0 && K % 128 == 0;      // (this step runs its products on the 16-bit matrix pipe)
+        const bool h2 = ses.t_h2_base && N % 128 == 0 && K % 128 == 0;      // (this step runs its products on the 16-bit matrix pipe)
         const int tiles = h2 ? (N / 128) * (K / 128) : ((N + 63) / 64) * ((K + 63) / 64), chunks = (rows + 31) / 32;
         const long slab = (long)N * K + (bias_here ? N : 0);
         // row slices: ~2048 blocks per launch (four rounds of two per CU, so that a tile count that is no multiple of 256 costs a few per
@@ -388,6 +388,8 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
     train_layout(B, L);
     float* tw = ws + ws_elems_per_frame * (size_t)B;
     float* X = tw + L.X;
+    const float* const k2d = ses.k2d;                        // (the call's pointers: Engine::begin)
+    float *const kcrop = ses.kcrop, *const out = ses.out;
     const int DEP = depth();
     auto P = [&](int param) { return params[param].ptr; };
 
@@ -485,7 +487,7 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
     HIP_TRY(launch_layernorm_train(X, row_ld(D), nullptr, row_ld(0), P(lifter.head_ln.w), P(lifter.head_ln.b), 1e-5f, tw + L.yh, tw + L.xhh,
                                    tw + L.rsh, B * J, D, s));
     HIP_TRY(launch_head(X, P(lifter.head_ln.w), P(lifter.head_ln.b), 1e-5f, P(lifter.head.w), P(lifter.head.b), out, B * J, D, 3, s));
-    train_batch = B;
+    ses.train_batch = B;
     return CAPF_OK;
 }
 
@@ -497,7 +499,7 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
 // is live) and the reference-point sampler (the input gradient of feat_embed[l], which the parameter step has no use for).
 // map_grad_mode picks the summation form at those two places (kernels.h, MapGradArgs): 0 atomic adds, 1 the ordered sum; nothing else differs.
 int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const float* masks, float* const* dfeat) {
-    if (B != train_batch) {
+    if (B != ses.train_batch) {
         err = "capf_backward: the activations of the matching capf_forward_train are gone (no such call, another batch size, or "
               "a later forward / workspace change overwrote them)";
         return CAPF_ERR_STATE;
@@ -507,6 +509,8 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
     TrainLayout L;
     train_layout(B, L);
     float* tw = ws + ws_elems_per_frame * (size_t)B;
+    const float* const k2d = ses.k2d;                        // (the pointers of the saved step's forward)
+    const float* const kcrop = ses.kcrop;
     t_slab_jobs.count = 0;                                   // (an earlier backward that failed half-way may have left jobs behind)
     t_slab_cur = 0;
     t_col_jobs.count = 0;

@@ -4,7 +4,7 @@ plan: plain data plus the helpers that made it.
 CA_PF keeps one engine per (device, H, W) for the life of the process and sends it every batch size and every entry point its caller uses.
 The engine carries state from call to call -- routes and weight packs are a function of the batch, every workspace buffer lives at
 offset * batch inside an arena that only grows, lazy pack flags (h2g_lifter_dirty), self-resetting split-K counters, the stem's input
-selector (u8in), feat_batch / train_batch / t_h2_base / last_batch, debug, lanes, the fork / join events -- so a session here is an ordered
+selector (Session::image), feat_batch / train_batch / t_h2_base / last_batch, debug, lanes, the fork / join events -- so a session here is an ordered
 list of calls whose every result must have the bits of a fresh engine that made that one call alone.
 
     Step    = (kind, batch, options)           options: sorted (name, value) pairs; batch 0 where the kind has none

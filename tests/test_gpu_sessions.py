@@ -539,6 +539,80 @@ def test_refused_calls_leave_no_trace():
     COVERED.add("refused")
 
 
+def test_every_entry_refuses_before_it_changes_anything(monkeypatch):
+    """each of the twelve run entries (the C entries) on one engine of the fp32 64 x 64 plan with max_batch 4: batch 0 and batch 5 are
+    CAPF_ERR_INVALID; a call between capf_set_param and capf_params_changed, and a call on a workspace one byte too small, are
+    CAPF_ERR_STATE.  Behind every refusal capf_train_generation is what it was, the NaN-filled output and the crop keypoints are untouched;
+    at the end `forward 2` has the bits of the fresh twin (tests/test_call_prologue.py: the refusals that need no device)."""
+    from capf.lib import input_constants
+    from mvn.models import _native
+    plan, MAXB = sc.F32, 4
+    _, H, W, _, _ = plan
+    st2 = sc.s("forward", 2)
+    want = _twin("h36m", plan, "synthetic", None, st2, 3)
+    monkeypatch.setattr(_native, "MAX_BATCH", MAXB)
+    model = _new_model("h36m", plan)
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    try:
+        eng = model.engine_for(torch.empty(1, H, W, 3, device="cuda"))
+        lib, h = eng.lib, eng.h
+        assert lib.capf_max_batch(h) == MAXB
+        S = lambda: ctypes.c_void_p(_stream())
+        img, k2d, kc, _ = _inputs(sc.s("forward", MAXB + 1), H, W)
+        img, k2d, kc = img.cuda(), k2d.cuda(), kc.cuda()
+        kept = kc.clone()
+        out = torch.full((MAXB + 1, 1, J, 3), float("nan"), device="cuda")
+        crops = _crops(sc.s("forward_u8", MAXB + 1), H, W).cuda()
+        mean, std = input_constants("hrnet_32")
+        maps = _maps(eng, sc.s("features", MAXB + 1))
+        n = lib.capf_num_ops(h)
+        ms, leader = (ctypes.c_float * n)(), (ctypes.c_int32 * n)()
+        entries = {
+            "capf_forward": lambda B: lib.capf_forward(h, S(), P(img), P(k2d), P(kc), B, P(out)),
+            "capf_backbone_forward": lambda B: lib.capf_backbone_forward(h, S(), P(img), B),
+            "capf_forward_train": lambda B: lib.capf_forward_train(h, S(), P(img), P(k2d), P(kc), B, P(out), None),
+            "capf_forward_u8": lambda B: lib.capf_forward_u8(h, S(), P(crops), mean, std, 0, P(k2d), P(kc), B, P(out)),
+            "capf_backbone_forward_u8": lambda B: lib.capf_backbone_forward_u8(h, S(), P(crops), mean, std, 0, B),
+            "capf_forward_train_u8": lambda B: lib.capf_forward_train_u8(h, S(), P(crops), mean, std, 0, P(k2d), P(kc), B, P(out), None),
+            "capf_lifter_forward": lambda B: lib.capf_lifter_forward(h, S(), P(k2d), P(kc), B, P(out)),
+            "capf_lifter_forward_train": lambda B: lib.capf_lifter_forward_train(h, S(), P(k2d), P(kc), B, P(out), None),
+            "capf_set_features": lambda B: lib.capf_set_features(h, S(), eng._ptrs4(maps), B),
+            "capf_forward_prefix": lambda B: lib.capf_forward_prefix(h, S(), P(img), P(k2d), P(kc), B, P(out), n),
+            "capf_forward_profile": lambda B: lib.capf_forward_profile(h, S(), P(img), P(k2d), P(kc), B, P(out), ms, n),
+            "capf_forward_profile_launches": lambda B: lib.capf_forward_profile_launches(h, S(), P(img), P(k2d), P(kc), B, P(out), ms, leader, n),
+        }
+        assert len(entries) == 12
+
+        def all_refuse(B, code, *words):
+            gen = lib.capf_train_generation(h)
+            for name, call in entries.items():
+                rc = call(B)
+                msg = lib.capf_last_error(h).decode()
+                assert rc == code and all(w in msg for w in words), (name, B, rc, msg)
+                assert lib.capf_train_generation(h) == gen, name
+            torch.cuda.synchronize()
+            assert bool(torch.isnan(out).all()) and torch.equal(kc, kept)
+
+        eng.ensure_workspace(MAXB)
+        eng.forward_train(img[:2], k2d[:2], kc[:2].clone(), torch.empty(2, 1, J, 3, device="cuda"), _stream(), None)      # a saved step to lose
+        for B in (0, MAXB + 1):
+            all_refuse(B, INVALID, "batch out of range")
+        name, shape, _ = eng.schema()[0]
+        shp = (ctypes.c_int64 * 4)(*(list(shape) + [0] * (4 - len(shape))))
+        assert lib.capf_set_param(h, name.encode(), ctypes.c_void_p(eng._bound[name]), shp, len(shape)) == 0
+        all_refuse(2, STATE, "capf_params_changed has not been called")
+        assert lib.capf_params_changed(h, S()) == 0
+        assert lib.capf_set_workspace(h, P(eng._ws), eng.workspace_bytes(3) - 1) == 0
+        all_refuse(3, STATE, "workspace missing or too small")
+        assert lib.capf_set_workspace(h, P(eng._ws), eng.workspace_bytes(eng._ws_batch)) == 0
+        got, _ = _run_step(model, "h36m", plan, st2)
+        bad = _differing(got, want)
+        assert not bad, f"forward 2 behind the refused calls: {bad} differ from the fresh twin's"
+    finally:
+        torch.cuda.synchronize()
+        _close(model)
+
+
 # ---- what ran --------------------------------------------------------------------------------------------------------------------------------
 def test_coverage():
     """(this test runs last: the whole module in one session)  The sessions together reached every step kind, and at every (plan, batch) that

@@ -120,7 +120,7 @@ def test_every_u8_step_has_the_single_three_channel_stem(plans):
             stems = [i for i, d in enumerate(descs) if d.kind == 0 and d.conv and d.backbone and d.Cin == 3]
             assert len(stems) == 1 and descs[stems[0]].in_dtype == 0, (sess.id, stems)
             kern = _kernels(eng, st.batch)[stems[0]]
-            assert kern.startswith(("igemm_f32_stem_stream<", "igemm_f32_smallc<", "igemm_f32<")), kern      # Family::F32: the route u8_begin requires
+            assert kern.startswith(("igemm_f32_stem_stream<", "igemm_f32_smallc<", "igemm_f32<")), kern      # Family::F32: the route Engine::begin requires
             assert sc.opt(st, "mode", 0) != 2 or st.batch % 2 == 0
             n += 1
     assert n >= 2

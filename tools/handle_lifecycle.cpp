@@ -1,0 +1,84 @@
+// Host sanitizer check of a handle's life, no GPU needed: creates and destroys plan-only handles of the three backbones, asks each the
+// questions a host asks before it has a device (schema, workspace size, op table), makes every run entry refuse it, and lets capf_create
+// fail both in front of the plan (a refused configuration) and behind it (a device that is not there: the branch that releases what a
+// handle already owns).  Built by `make -C contextaware-poseformer_amd/csrc hostcheck`: the engine's host sources with
+// -fsanitize=address,undefined, the device objects of the product build; it runs on the build machine and is not loaded into Python.
+#include <stdio.h>
+#include <string.h>
+
+#include "capf.h"
+
+static capf_config config(int backbone, int width, int dtype, int training) {
+    capf_config c;
+    memset(&c, 0, sizeof(c));
+    c.backbone = backbone;
+    for (int i = 0; i < 4; ++i) c.hr_channels[i] = width << i;
+    c.hr_modules[0] = 1; c.hr_modules[1] = 4; c.hr_modules[2] = 3;
+    c.hr_blocks = 4;
+    c.base_dim = backbone == CAPF_CPN50 ? 256 : width;
+    c.embed_dim_ratio = 128;
+    c.levels = 4; c.num_joints = 17; c.num_heads = 8; c.deform_heads = 4; c.deform_samples = 4; c.context_blocks = 1;
+    c.compute_dtype = dtype;
+    c.max_batch = 64;
+    c.height = 64; c.width = 64;
+    c.training = training;
+    return c;
+}
+
+#define CHECK(cond)                                                        \
+    do {                                                                   \
+        if (!(cond)) {                                                     \
+            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
+            return 1;                                                      \
+        }                                                                  \
+    } while (0)
+
+int main() {
+    float mem[64] = {0};
+    const uint8_t bytes[16] = {0};
+    const float* maps[4] = {mem, mem, mem, mem};
+    int handles = 0;
+    for (int backbone : {CAPF_HRNET, CAPF_CPN50})
+        for (int width : {32, 48})
+            for (int dtype : {CAPF_F32, CAPF_BF16}) {
+                if (backbone == CAPF_CPN50 && width == 48) continue;
+                const capf_config c = config(backbone, width, dtype, 1);
+                capf_handle* h = nullptr;
+                CHECK(capf_create(&c, -1, &h) == CAPF_OK && h);
+                const int n = capf_num_ops(h);
+                CHECK(n > 0 && capf_num_params(h) > 0 && capf_workspace_bytes(h, 2) > 0 && capf_workspace_bytes(h, 0) == 0);
+                for (int i = 0; i < n; ++i) {
+                    const char *name, *kernel;
+                    double flops;
+                    CHECK(capf_op_info(h, i, 24, &name, &kernel, &flops) == CAPF_OK);
+                }
+                CHECK(capf_forward(h, nullptr, mem, mem, mem, 2, mem) == CAPF_ERR_STATE);
+                CHECK(capf_backbone_forward(h, nullptr, mem, 2) == CAPF_ERR_STATE);
+                CHECK(capf_forward_train(h, nullptr, mem, mem, mem, 2, mem, nullptr) == CAPF_ERR_STATE);
+                CHECK(capf_forward_u8(h, nullptr, bytes, mem, nullptr, 2, mem, mem, 2, mem) == CAPF_ERR_STATE);
+                CHECK(capf_backbone_forward_u8(h, nullptr, bytes, mem, mem, 3, 2) == CAPF_ERR_INVALID);
+                CHECK(capf_forward_train_u8(h, nullptr, bytes, nullptr, nullptr, 0, mem, mem, 2, mem, nullptr) == CAPF_ERR_INVALID);
+                CHECK(capf_lifter_forward(h, nullptr, mem, mem, 2, mem) == CAPF_ERR_STATE);
+                CHECK(capf_lifter_forward_train(h, nullptr, mem, mem, 2, mem, nullptr) == CAPF_ERR_STATE);
+                CHECK(capf_set_features(h, nullptr, maps, 2) == (dtype == CAPF_F32 ? CAPF_ERR_STATE : CAPF_ERR_UNSUPPORTED));
+                CHECK(capf_forward_prefix(h, nullptr, mem, nullptr, nullptr, 2, nullptr, 1) == CAPF_ERR_STATE);
+                CHECK(capf_forward_profile(h, nullptr, mem, mem, mem, 2, mem, mem, n - 1) == CAPF_ERR_INVALID);
+                CHECK(capf_set_workspace(h, mem, sizeof(mem)) == CAPF_OK && capf_train_generation(h) == 1);
+                capf_destroy(h);
+                ++handles;
+            }
+    capf_destroy(nullptr);
+    // refused in front of the plan, inside it, and behind it (no device 0 on a machine without a GPU: what the handle owns is released)
+    capf_handle* h = nullptr;
+    capf_config c = config(CAPF_HRNET, 32, 7, 0);
+    CHECK(capf_create(&c, -1, &h) == CAPF_ERR_UNSUPPORTED && !h);
+    c = config(CAPF_HRNET, 32, CAPF_F32, 0);
+    c.height = 72;
+    CHECK(capf_create(&c, -1, &h) == CAPF_ERR_UNSUPPORTED && !h && strstr(capf_last_error(nullptr), "multiples of 32"));
+    c.height = 64;
+    const int rc = capf_create(&c, 0, &h);
+    if (rc == CAPF_OK) capf_destroy(h);      // (a machine with a GPU: the handle's device resources, allocated and released)
+    else CHECK(rc == CAPF_ERR_HIP && !h);
+    printf("handle_lifecycle: %d plan-only handles created and destroyed, 2 configurations refused, capf_create(device 0) -> %d\n", handles, rc);
+    return 0;
+}
