@@ -10,6 +10,7 @@ HRNET, CPN50 = 0, 1
 F32, BF16, F16 = 0, 1, 2      # capf_dtype
 PLAN_NO_FUSED_LIFTER, PLAN_NO_WINOGRAD, PLAN_NO_ROW_HALO, PLAN_WINOGRAD_F23_ONLY, PLAN_NO_PWCHAIN, PLAN_NO_WS, PLAN_LIFTER_FP32, PLAN_NO_F32X3, PLAN_F32X3_EXACT, PLAN_NO_F32H2_GEMM, PLAN_NO_UPADD, PLAN_H2_PLANES, PLAN_NO_BNECK, PLAN_NO_BATCHED_REDUCE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192     # capf_plan_flag
 PLAN_BF16_F32_STREAM = 32768     # (1 << 14 stays unassigned)
+PLAN_BN_BATCH_STATS = 65536      # opt-in: the handle also carries the batch-statistics backbone route (capf_backbone_forward_bn)
 ABI_VERSION = 12       # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
 
 EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.py)
@@ -38,6 +39,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_set_map_grad_mode", "capf_map_grad_mode",
     "capf_forward_u8", "capf_backbone_forward_u8", "capf_forward_train_u8", "capf_preprocess_points", "capf_input_rule_host",
     "capf_op_conv_u8", "capf_op_conv_u8_kernel_name", "capf_op_conv_stem_kernel_name",
+    "capf_backbone_forward_bn", "capf_op_bn_stats_scratch_bytes", "capf_op_bn_stats", "capf_op_bn_apply",
 ]
 
 
@@ -136,6 +138,11 @@ def load_library():
     lib.capf_set_workspace.argtypes = [H, c_void_p, c_size_t]
     lib.capf_forward.argtypes = [H, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
     lib.capf_backbone_forward.argtypes = [H, c_void_p, c_void_p, c_int]
+    lib.capf_backbone_forward_bn.argtypes = [H, c_void_p, c_void_p, c_int, c_float]
+    lib.capf_op_bn_stats_scratch_bytes.argtypes = [c_int64, c_int]
+    lib.capf_op_bn_stats_scratch_bytes.restype = c_size_t
+    lib.capf_op_bn_stats.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_float, c_float] + [c_void_p] * 5 + [c_size_t]
+    lib.capf_op_bn_apply.argtypes = [c_void_p] * 6 + [c_int64, c_int, c_int]
     lib.capf_lifter_forward.argtypes = [H, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
     lib.capf_set_debug.argtypes = [H, c_int]
     lib.capf_set_lanes.argtypes = [H, c_int]
@@ -442,6 +449,14 @@ class Engine:
         self.ensure_workspace(B)
         self._check(self.lib.capf_backbone_forward(self.h, c_void_p(stream), c_void_p(images.data_ptr()), B),
                     "backbone_forward")
+
+    def backbone_forward_bn(self, images, stream, momentum=0.1):
+        """capf_backbone_forward_bn: the backbone with batch statistics (a PLAN_BN_BATCH_STATS handle); the bound running_mean /
+        running_var tensors are updated in place."""
+        B = images.shape[0]
+        self.ensure_workspace(B)
+        self._check(self.lib.capf_backbone_forward_bn(self.h, c_void_p(stream), c_void_p(images.data_ptr()), B, float(momentum)),
+                    "backbone_forward_bn")
 
     def lifter_forward(self, k2d, kcrop, out, stream):
         B = k2d.shape[0]
@@ -987,6 +1002,29 @@ def bilinear_corners(grid, H, W, border):
     frac = torch.empty(g.shape, dtype=torch.float32, device=g.device)
     _call("capf_op_bilinear_corners", _stream(g), _p(g), g.numel() // 2, int(H), int(W), 1 if border else 0, _p(idx), _p(frac))
     return idx, frac
+
+
+def bn_stats(x, gamma, beta, eps=1e-5, momentum=0.1, running_mean=None, running_var=None):
+    """Batch statistics of x [rows, C] (fp32, contiguous) as capf_backbone_forward_bn takes them (capf_op_bn_stats): returns
+    (scale, shift) with scale = gamma / sqrt(var + eps), shift = beta - mean * scale; running_mean / running_var are updated in place."""
+    import torch
+    rows, C = x.shape
+    nbytes = load_library().capf_op_bn_stats_scratch_bytes(rows, C)
+    scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=x.device)
+    scale = torch.empty(C, dtype=torch.float32, device=x.device)
+    shift = torch.empty(C, dtype=torch.float32, device=x.device)
+    _call("capf_op_bn_stats", _stream(x), _p(x), rows, C, _p(gamma), _p(beta), float(eps), float(momentum), _p(running_mean), _p(running_var),
+          _p(scale), _p(shift), _p(scratch), nbytes)
+    return scale, shift
+
+
+def bn_apply(x, scale, shift, residual=None, relu=False, out=None):
+    """y = act(x * scale[c] + shift[c] + residual) on x [rows, C] (capf_op_bn_apply); out may be x (in place)."""
+    import torch
+    rows, C = x.shape
+    y = torch.empty_like(x) if out is None else out
+    _call("capf_op_bn_apply", _stream(x), _p(x), _p(scale), _p(shift), _p(residual), _p(y), rows, C, 1 if relu else 0)
+    return y
 
 
 def linear_bf16(x, w, bias=None, residual=None, gelu=False):

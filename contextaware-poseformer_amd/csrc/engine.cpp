@@ -20,6 +20,7 @@ namespace capf {
     } while (0)
 
 Engine::ConvSrc Engine::conv_src(const Pack& pk) const {
+    if (pk.raw) return {params[pk.w[0]].ptr, nullptr, nullptr, nullptr, nullptr, 1e-5f};     // (no BatchNorm: the packers fold scale 1, bias 0)
     return {params[pk.w[0]].ptr, params[pk.bn.g].ptr, params[pk.bn.b].ptr, params[pk.bn.m].ptr, params[pk.bn.v].ptr, 1e-5f};
 }
 
@@ -36,15 +37,17 @@ int Engine::repack(hipStream_t s, bool lifter_only) {
         HIP_TRY(hipMemcpy(pack_arena + utab_off, utab_host.data(), utab_host.size() * sizeof(unsigned), hipMemcpyHostToDevice));
         utab_on_device = true;
     }
-    for (const Pack& pk : packs) {                      // the convs' two-fp16-piece copies (igemm_f32h2.hip); the linears' are packed lazily
-        if (!pk.h2g || pk.kind != CONV_BN || lifter_only) continue;
-        const ConvSrc c = conv_src(pk);
-        HIP_TRY(launch_pack_f32h2_gemm(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.h2g_off, nullptr, pk.N, pk.Cin, pk.ks, pk.K, pk.h2g_Kpad, s));
-    }
+    for (const std::vector<Pack>* list : {&packs, &raw_packs})       // (raw_packs: the batch-statistics route's unfolded copies of the conv packs)
+        for (const Pack& pk : *list) {                  // the convs' two-fp16-piece copies (igemm_f32h2.hip); the linears' are packed lazily
+            if (!pk.h2g || pk.kind != CONV_BN || lifter_only || (list == &raw_packs && !pk.raw)) continue;
+            const ConvSrc c = conv_src(pk);
+            HIP_TRY(launch_pack_f32h2_gemm(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.h2g_off, nullptr, pk.N, pk.Cin, pk.ks, pk.K, pk.h2g_Kpad, s));
+        }
     h2g_lifter_dirty = true;
     std::vector<CopySegment> jobs;                      // the packed linears' bias vectors: one launch for all of them (below)
-    for (const Pack& pk : packs) {
-        if (pk.in_place) continue;
+    for (const std::vector<Pack>* list : {&packs, &raw_packs})
+    for (const Pack& pk : *list) {
+        if (pk.in_place || (list == &raw_packs && !pk.raw)) continue;
         float* W = pack_arena + pk.w_off;
         float* B = pack_arena + pk.b_off;
         if (pk.kind == CONV_BN) {
@@ -113,7 +116,9 @@ int Engine::ensure_h2g_lifter(hipStream_t s) {
 
 GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes, bool side_chain) const {
     auto ptr = [&](int buf) -> float* { return (buf >= 0 && ws) ? bptr(buf, batch) : nullptr; };
-    const Pack& pk = packs[op.pack];
+    const bool raw = bn_run && bn_unit_of[&op - ops.data()] >= 0;      // a raw conv of the batch-statistics route: unfolded weights, zero bias,
+    const Pack& pk = raw ? raw_packs[op.pack] : packs[op.pack];      // no residual, no activation, no planes (bn_post applies them behind the statistics)
+    if (raw) planes = false;
     GemmArgs a{};
     a.A = op.in[0] == -2 ? ses.images() : ptr(op.in[0]);
     if (pk.in_place) {
@@ -123,7 +128,7 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes, bool side_chain
         a.Wp = pack_arena + pk.w_off;
         a.bias = pack_arena + pk.b_off;
     }
-    a.res = op.res_param >= 0 ? params[op.res_param].ptr : ptr(op.aux);
+    a.res = raw ? nullptr : op.res_param >= 0 ? params[op.res_param].ptr : ptr(op.aux);
     a.out = ptr(op.out);
     a.M = (int)(op.rows_per_frame * batch);
     a.N = op.N; a.K = op.K; a.Kpad = pk.Kpad;
@@ -145,7 +150,7 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes, bool side_chain
     a.Cin = op.Cin; a.H = op.H; a.W = op.W; a.Ho = op.Ho; a.Wo = op.Wo;
     a.ks = op.ks; a.stride = op.stride; a.pad = op.pad;
     a.amap = op.amap; a.omap = op.omap; a.rmap = op.rmap;
-    a.act = op.act;
+    a.act = raw ? ACT_NONE : op.act;
     a.out_bf16 = op.out_bf16;
     a.f16 = f16();                                     // (the element format of whatever 16-bit kernel takes the problem)
     a.f32s = op.f32s;                                  // (CAPF_PLAN_BF16_F32_STREAM: fp32 residual; fp32 result + bf16 shadow, or bf16 result)
@@ -182,7 +187,7 @@ GemmArgs Engine::gemm_args(const Op& op, int batch, bool planes, bool side_chain
 // fewer than four tiles each and the separate launches win.
 Engine::FusedLaunch Engine::fused_at(int i, int batch, int last_op, bool bneck_only) const {
     const int n_all = (int)ops.size();
-    if (i < 0 || i >= n_all) return {};
+    if (i < 0 || i >= n_all || bn_run) return {};              // (the batch-statistics route: no launch crosses a BatchNorm)
     const Op& o = ops[i];
     if (o.kind == OP_FORK) {                                   // conv1, conv2 | downsample inside the region, conv3 right after its join
         if (!plan.use_bneck || !b16() || o.fork.lanes != 2 || o.region < 0) return {};
@@ -308,6 +313,10 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch, bool side_chain) {
                 default:
                     if (op.in[0] == -2 && ses.u8()) HIP_TRY(launch_gemm_f32_u8(a, *ses.u8(), s));   // the stem from the uint8 crop: same route, U8 form
                     else HIP_TRY(launch_gemm_f32(a, s));
+            }
+            if (bn_run) {
+                const int oi = (int)(&op - ops.data());
+                if (const int rc = bn_post(s, batch, &oi, 1)) return rc;
             }
             break;
         }
@@ -461,6 +470,8 @@ int Engine::run_region_grouped(hipStream_t s, int batch, int region, LaunchLog* 
                 }
                 else if (pass == Family::F32_TILE) HIP_TRY(launch_f32_tile(group, n, s));
                 else HIP_TRY(launch_gemm_wino_group(group, n, s));
+                if (bn_run)
+                    if (const int rc = bn_post(s, batch, members, n)) return rc;
                 n = 0;
                 return CAPF_OK;
             };
@@ -518,7 +529,7 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
         if (rc) return rc;
     }
     const bool grouped = (lanes == 2 || lanes == 3) && !ev;
-    const bool par = lanes == 1 && !ev && !log && side[0];
+    const bool par = lanes == 1 && !ev && !log && side[0] && !bn_run;      // (the batch-statistics route shares its scratch slots: one stream)
     for (int oi = first_op; oi < last_op; ++oi) {
         const Op& op = ops[oi];
         s = (par && op.lane > 0) ? side[op.lane - 1] : main_stream;
@@ -547,7 +558,7 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
                     // the chip many times over), and below batch 16 a region is a handful of tiles (and may use the split-K scratch):
                     // one chain outside 16..256 (until round 11).  Round 11, five alternating pairs against one chain per configuration: cfg1 (batch 64) +1.2 % and
                     // +2.2 % on two boxes, cfg2 (bf16, batch 256) -0.45 % at twice its pair-to-pair spread: two chains up to batch 128 (two_chains()).
-                    const bool two = two_chains(op, batch) && !log && side[0];
+                    const bool two = two_chains(op, batch) && !log && side[0] && !bn_run;
                     if (two) {
                         HIP_TRY(hipEventRecord(events[op.fork.first_event], main_stream));
                         HIP_TRY(hipStreamWaitEvent(side[0], events[op.fork.first_event], 0));
@@ -592,6 +603,50 @@ int Engine::run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t*
     if (ev) HIP_TRY(hipEventRecord(ev[last_op], main_stream));
     if (log) HIP_TRY(log->mark(main_stream, nullptr, 0));
     if (first_op == 0) ses.maps_written(last_op >= n_backbone_ops ? batch : 0);      // (a prefix run leaves the maps half written)
+    return CAPF_OK;
+}
+
+size_t Engine::bn_slot_elems(int batch) const {
+    size_t worst = 0;
+    for (const BnUnit& u : bn_units) {
+        const Op& op = ops[u.op];
+        worst = std::max(worst, 2 * (size_t)op.N + bn_scratch_elems(op.rows_per_frame * batch, op.N));
+    }
+    return (worst + 63) / 64 * 64;
+}
+
+// Behind raw convs of the batch-statistics route: per unit the statistics of the conv's output (two launches: slab partials, then their
+// combination into scale / shift and the running statistics, written through the pointers capf_set_param borrowed) and the normalise /
+// residual / ReLU pass in place over it -- up to BN_SLOTS units per launch, slot k = {scale | shift | slab partials} of the k-th
+int Engine::bn_post(hipStream_t s, int batch, const int* members, int n) {
+    float* const base = ws + bn_base(batch);
+    const size_t slot = bn_slot_elems(batch);
+    for (int i = 0; i < n;) {
+        BnStatsArgs st[BN_SLOTS];
+        BnApplyArgs ap[BN_SLOTS];
+        int k = 0;
+        for (; i < n && k < BN_SLOTS; ++i) {
+            const int ui = bn_unit_of[members[i]];
+            if (ui < 0) continue;
+            const Op& op = ops[members[i]];
+            const BnRef& bn = bn_units[ui].bn;
+            float* const sl = base + slot * k;
+            BnStatsArgs& a = st[k];
+            a = BnStatsArgs{};
+            a.x = bptr(op.out, batch);
+            a.gamma = params[bn.g].ptr; a.beta = params[bn.b].ptr;
+            a.rmean = const_cast<float*>(params[bn.m].ptr); a.rvar = const_cast<float*>(params[bn.v].ptr);
+            a.scale = sl; a.shift = sl + op.N;
+            a.part = reinterpret_cast<double*>(sl + 2 * (size_t)op.N);
+            a.rows = op.rows_per_frame * batch; a.C = op.N;
+            a.eps = 1e-5f; a.momentum = bn_momentum;
+            ap[k] = BnApplyArgs{a.x, op.aux >= 0 ? bptr(op.aux, batch) : nullptr, bptr(op.out, batch), a.scale, a.shift, a.rows, a.C, op.act == ACT_RELU};
+            ++k;
+        }
+        if (k == 0) continue;
+        HIP_TRY(launch_bn_stats_group(st, k, s));
+        HIP_TRY(launch_bn_apply_group(ap, k, s));
+    }
     return CAPF_OK;
 }
 
@@ -648,7 +703,23 @@ int Engine::begin(const Call& c) {
             return CAPF_ERR_INVALID;
         }
     }
+    if (c.bn && !plan.bn_batch) {
+        err = std::string(c.who) + ": the handle was created without CAPF_PLAN_BN_BATCH_STATS";
+        return CAPF_ERR_STATE;
+    }
     if (const int rc = check_run(c.batch)) return rc;
+    if (c.bn) {
+        if (!(c.momentum >= 0.f && c.momentum <= 1.f)) {
+            err = std::string(c.who) + ": momentum must lie in [0, 1]";
+            return CAPF_ERR_INVALID;
+        }
+        for (const BnUnit& u : bn_units)
+            if (ops[u.op].rows_per_frame * c.batch < 2) {
+                err = std::string(c.who) + ": expected more than 1 value per channel when training: " + ops[u.op].name + " has " +
+                      std::to_string(ops[u.op].Ho) + " x " + std::to_string(ops[u.op].Wo) + " outputs per frame at batch " + std::to_string(c.batch);
+                return CAPF_ERR_INVALID;
+            }
+    }
     if (c.maps && ses.feat_batch != c.batch) {      // (every buffer lives at offset * batch: maps of another batch are not where this call would sample)
         err = std::string(c.who) + ": the workspace holds no context maps of this batch (capf_set_features or capf_backbone_forward "
               "of the same batch comes first)";
@@ -696,6 +767,17 @@ int capf_create(const capf_config* cfg, int device, capf_handle** out) {
         delete h;
         return CAPF_ERR_UNSUPPORTED;
     }
+    if (cfg->plan_flags & CAPF_PLAN_BN_BATCH_STATS) {      // the batch-statistics route: HRNet, fp32, training handles
+        const char* why = cfg->backbone != CAPF_HRNET ? "CAPF_PLAN_BN_BATCH_STATS is an HRNet plan (CPN50 is not supported)"
+                          : cfg->compute_dtype != CAPF_F32 ? "CAPF_PLAN_BN_BATCH_STATS needs compute_dtype = CAPF_F32 (bf16 / fp16 batch statistics are not supported)"
+                          : !cfg->training ? "CAPF_PLAN_BN_BATCH_STATS needs training = 1 (batch statistics belong to a training handle)"
+                          : (cfg->plan_flags & CAPF_PLAN_BF16_F32_STREAM) ? "CAPF_PLAN_BN_BATCH_STATS cannot be combined with CAPF_PLAN_BF16_F32_STREAM" : nullptr;
+        if (why) {
+            g_create_error = why;
+            delete h;
+            return CAPF_ERR_UNSUPPORTED;
+        }
+    }
     if (cfg->compute_dtype == CAPF_F16) {       // the fp16 plan is the HRNet inference plan; what else a 16-bit plan can do is bf16's until it has tests of its own
         const char* why = cfg->backbone != CAPF_HRNET ? "compute_dtype = CAPF_F16 is an HRNet plan (CPN50 is not supported)"
                           : (cfg->plan_flags & CAPF_PLAN_BF16_F32_STREAM) ? "CAPF_PLAN_BF16_F32_STREAM needs compute_dtype = CAPF_BF16 (CAPF_F16 is not supported)"
@@ -706,7 +788,7 @@ int capf_create(const capf_config* cfg, int device, capf_handle** out) {
             return CAPF_ERR_UNSUPPORTED;
         }
     }
-    if (cfg->plan_flags & ~(16383 | CAPF_PLAN_BF16_F32_STREAM)) {
+    if (cfg->plan_flags & ~(16383 | CAPF_PLAN_BF16_F32_STREAM | CAPF_PLAN_BN_BATCH_STATS)) {
         g_create_error = "unknown capf_plan_flag bits";
         delete h;
         return CAPF_ERR_INVALID;
@@ -854,6 +936,20 @@ int capf_forward(capf_handle* h, void* stream, const float* images_nhwc, const f
 int capf_backbone_forward(capf_handle* h, void* stream, const float* images_nhwc, int batch) {
     if (!h || !images_nhwc) return CAPF_ERR_INVALID;
     return begin_and_run(h->e, stream, {"capf_backbone_forward", images_nhwc, nullptr, nullptr, nullptr, batch, 0, h->e.n_backbone_ops});
+}
+
+int capf_backbone_forward_bn(capf_handle* h, void* stream, const float* images_nhwc, int batch, float momentum) {
+    if (!h || !images_nhwc) return CAPF_ERR_INVALID;
+    Engine& e = h->e;
+    Call c{"capf_backbone_forward_bn", images_nhwc, nullptr, nullptr, nullptr, batch, 0, e.n_backbone_ops};
+    c.bn = true;
+    c.momentum = momentum;
+    if (const int rc = e.begin(c)) return rc;
+    e.bn_run = true;                     // (the second op list: Engine::gemm_args, fused_at, exec_op, run_region_grouped)
+    e.bn_momentum = momentum;
+    const int rc = e.run(static_cast<hipStream_t>(stream), batch, c.first, c.last);
+    e.bn_run = false;
+    return rc;
 }
 
 int capf_forward_train(capf_handle* h, void* stream, const float* images_nhwc, const float* k2d, float* kcrop_inout,
@@ -1201,6 +1297,29 @@ int capf_op_linear(void* stream, const float* x, const float* w, const float* bi
                    int M, int N, int K, int act) {
     if (K % 32 != 0) return CAPF_ERR_UNSUPPORTED;
     return hip_rc(capf::launch_gemm_f32(rows_args(&capf::GemmArgs::Wp, x, w, bias, residual, y, M, N, K, act), static_cast<hipStream_t>(stream)));
+}
+
+size_t capf_op_bn_stats_scratch_bytes(int64_t rows, int C) { return capf::bn_scratch_elems((long)rows, C) * sizeof(float); }
+
+int capf_op_bn_stats(void* stream, const float* x, int64_t rows, int C, const float* gamma, const float* beta, float eps, float momentum,
+                     float* running_mean, float* running_var, float* scale, float* shift, void* scratch, size_t scratch_bytes) {
+    if (!x || !gamma || !beta || !scale || !shift || !scratch || rows < 2) return CAPF_ERR_INVALID;      // (rows < 2: no variance of one value)
+    const size_t need = capf_op_bn_stats_scratch_bytes(rows, C);
+    if (need == 0) return CAPF_ERR_UNSUPPORTED;
+    if (scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 7)) return CAPF_ERR_INVALID;
+    capf::BnStatsArgs a{};
+    a.x = x; a.gamma = gamma; a.beta = beta; a.rmean = running_mean; a.rvar = running_var;
+    a.part = static_cast<double*>(scratch); a.scale = scale; a.shift = shift;
+    a.rows = (long)rows; a.C = C; a.eps = eps; a.momentum = momentum;
+    return capf::launch_bn_stats_group(&a, 1, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+}
+
+int capf_op_bn_apply(void* stream, const float* x, const float* scale, const float* shift, const float* residual, float* y, int64_t rows, int C,
+                     int act) {
+    if (!x || !scale || !shift || !y || rows < 1 || (act != 0 && act != 1)) return CAPF_ERR_INVALID;
+    if (C < 4 || C % 4 != 0 || C > 1024 || rows * (C / 4) >= (int64_t(1) << 31)) return CAPF_ERR_UNSUPPORTED;
+    const capf::BnApplyArgs a{x, residual, y, scale, shift, (long)rows, C, act};
+    return capf::launch_bn_apply_group(&a, 1, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
 int capf_op_bilinear_corners(void* stream, const float* grid, int n, int H, int W, int border, int32_t* idx, float* frac) {

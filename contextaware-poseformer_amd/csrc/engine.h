@@ -76,7 +76,12 @@ struct Pack {
     bool h2g = false; size_t h2g_off = 0; int h2g_Kpad = 0;      // fp32 conv / linear: two block-scaled fp16 pieces for igemm_f32h2.hip, [N][h2g_Kpad] floats +
                                                                  // [N] inverse channel scales; h2g_Kpad = the direct fp32 layout's padded K
     bool chain = false; size_t chain_off = 0;                    // ... and that copy once more in MFMA fragment order for lifter_chain.hip (launch_res_chain_repack)
+    bool raw = false;              // an entry of Engine::raw_packs: the same conv WITHOUT its BatchNorm folded in (scale 1, bias 0), in the same layouts
 };
+
+// One conv -> BatchNorm (-> + residual) (-> ReLU) unit of the batch-statistics route (CAPF_PLAN_BN_BATCH_STATS): the plan's conv op, run raw
+// (Engine::raw_packs, no bias, no residual, no activation), the statistics of its output, and the normalise / residual / ReLU pass over it
+struct BnUnit { int op = -1; BnRef bn; };
 
 // The lifter's layers (pose_dformer.py:144-241), resolved once where build_lifter registers the schema: parameter indices and shapes.
 // The ONE place the layer list lives -- the plan (plan.cpp) and the training step (train.cpp) read it, neither builds a parameter name
@@ -258,6 +263,8 @@ struct Call {
     int first, last;                     // the op span [first, last) it runs
     bool training = false;               // the training step's lifter forward follows the span: refused by a handle created with training = 0
     bool maps = false;                   // reads context maps of this batch that an earlier call left (otherwise it writes the maps itself)
+    bool bn = false;                     // the backbone span runs the batch-statistics route (capf_backbone_forward_bn) ...
+    float momentum = 0.1f;               // ... moving the running statistics with this momentum
 };
 
 struct Engine {
@@ -291,6 +298,7 @@ struct Engine {
         bool use_upadd = true;         // CAPF_PLAN_NO_UPADD clears it (CPN bf16: lateral conv + upsampled add in one launch)
         bool batch_reduce = true;      // CAPF_PLAN_NO_BATCHED_REDUCE clears it: the backward's second-stage reductions one launch each
         bool f32_stream = false;       // CAPF_PLAN_BF16_F32_STREAM: bf16 only as conv operands, every other backbone tensor fp32
+        bool bn_batch = false;         // CAPF_PLAN_BN_BATCH_STATS: the handle also carries the batch-statistics route of the backbone (bn_units)
     } plan;
     bool set_plan_switches();
     static constexpr int H2G_MIN_BATCH = 5;
@@ -301,6 +309,15 @@ struct Engine {
     std::vector<Buffer> bufs;
     std::vector<Pack> packs;
     std::vector<Op> ops;
+    // The batch-statistics route (capf_backbone_forward_bn; empty without CAPF_PLAN_BN_BATCH_STATS): the backbone's second op list.  It walks the
+    // plan's backbone ops, with every conv replaced by its BnUnit -- so the raw convs keep the kernel family and the grouped launch per level that
+    // the plan routes their geometry and batch to -- and without the launches that cross a BatchNorm (fused_at: none; no planes between convs).
+    // raw_packs[i] is packs[i] unfolded (conv packs only), at offsets of its own behind the plan's packs; bn_unit_of[op] indexes bn_units (-1)
+    std::vector<BnUnit> bn_units;
+    std::vector<int> bn_unit_of;
+    std::vector<Pack> raw_packs;
+    bool bn_run = false;                 // a capf_backbone_forward_bn is being enqueued: gemm_args / fused_at / exec_op describe the second list
+    float bn_momentum = 0.1f;
     int n_backbone_ops = 0;
     int stem_op = -1;              // the one conv that reads the image (-1: none, -2: several)
     int cur_lane = 0, cur_region = -1, n_regions = 0, n_events = 0;
@@ -375,7 +392,16 @@ struct Engine {
     ConvSrc conv_src(const Pack& pk) const;
     int repack(hipStream_t s, bool lifter_only = false);
     int ensure_h2g_lifter(hipStream_t s);
-    size_t workspace_bytes(int batch) const { return (ws_elems_per_frame * (size_t)batch + (cfg.training ? train_elems(batch) : 0)) * sizeof(float); }
+    size_t workspace_bytes(int batch) const {
+        const size_t plain = ws_elems_per_frame * (size_t)batch + (cfg.training ? train_elems(batch) : 0);
+        return (plan.bn_batch ? bn_base(batch) + BN_SLOTS * bn_slot_elems(batch) : plain) * sizeof(float);
+    }
+    // scratch of the batch-statistics route, behind the training region: BN_SLOTS slots (one per BatchNorm of a grouped launch; everything runs
+    // on the caller's stream, so the next launch group reuses them), each {slab partials | scale | shift} of the plan's largest unit
+    static constexpr int BN_SLOTS = 4;
+    size_t bn_base(int batch) const { return (ws_elems_per_frame * (size_t)batch + (cfg.training ? train_elems(batch) : 0) + 63) / 64 * 64; }
+    size_t bn_slot_elems(int batch) const;
+    int bn_post(hipStream_t s, int batch, const int* members, int n);    // statistics + apply behind the raw convs `members` (ops; others skipped)
     int check_run(int batch);      // can this handle run this batch at all: a device, the batch range, fresh packs, a workspace that holds it
     int begin(const Call& c);      // every precondition of a run entry, then -- all passed -- the session state of the call
     int run(hipStream_t s, int batch, int first_op, int last_op, hipEvent_t* ev = nullptr, LaunchLog* log = nullptr);

@@ -448,6 +448,36 @@ hipError_t launch_fuse_sum(const FuseSumArgs& a, hipStream_t s);
 // up to 4 independent sums (the outputs of one HRNet fuse module) as ONE launch; same arithmetic per element as launch_fuse_sum
 hipError_t launch_fuse_sum_group(const FuseSumArgs* a, int n, hipStream_t s);
 
+// Training-mode BatchNorm2d of a raw conv output x [rows = B * H * W][C] fp32 (bn_train.hip): batch statistics without atomics -- slab
+// partials (fp64 mean / M2 per slab and channel, bn_scratch_elems floats at `part`, 8-byte aligned), combined by a second launch in one fixed
+// order -- into scale = gamma / sqrt(var + eps), shift = beta - mean * scale and the running statistics (updated in place; nullptr: none);
+// then y = act(x * scale[c] + shift[c] + res).  C % 4 == 0, C <= 1024, rows >= 2 for the statistics.  The launchers fill slab_rows / nslab
+static constexpr int BN_MAX_SLABS = 1024;
+struct BnStatsArgs {
+    const float* x;
+    const float *gamma, *beta;
+    float *rmean, *rvar;
+    double* part;
+    float *scale, *shift;
+    long rows;
+    int C, slab_rows, nslab;
+    float eps, momentum;
+};
+struct BnApplyArgs {
+    const float* x;
+    const float* res;      // [rows][C] or nullptr
+    float* y;              // may be x
+    const float *scale, *shift;
+    long rows;
+    int C, act;            // act: 0 none, 1 ReLU (relu_f)
+};
+int bn_slab_rows(long rows, int C);
+int bn_num_slabs(long rows, int C);
+size_t bn_scratch_elems(long rows, int C);     // 0: a shape the kernels do not take
+// up to 4 independent BatchNorms (the branches of an HRNet level) per launch: statistics = two launches, apply = one
+hipError_t launch_bn_stats_group(const BnStatsArgs* a, int n, hipStream_t s);
+hipError_t launch_bn_apply_group(const BnApplyArgs* a, int n, hipStream_t s);
+
 // 3x3 s2 p1 max-pool NHWC (resnet.py:140), bilinear align_corners=True resize NHWC (+ optional add)
 hipError_t launch_maxpool3x3s2(const float* in, float* out, int B, int H, int W, int C, int Ho, int Wo,
                                hipStream_t s, int bf16 = 0, int f16 = 0);      // bf16: 16-bit tensors, of format f16 (0 bf16, 1 fp16)

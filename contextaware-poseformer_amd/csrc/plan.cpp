@@ -1089,6 +1089,7 @@ bool Engine::set_plan_switches() {
         p.use_bneck = false;
         p.use_pwchain = false;
     }
+    if (cfg.plan_flags & CAPF_PLAN_BN_BATCH_STATS) p.bn_batch = true;      // (capf_create has refused what the route does not cover)
     // tuning knobs of the diagnostic build only (diag_env is a constant nullptr in the product library)
     if (const char* fz = diag_env("CAPF_LIFTER_FUSED")) p.fused_lifter = atoi(fz) != 0;
     if (const char* wz = diag_env("CAPF_WINO")) p.use_wino = atoi(wz) != 0;
@@ -1306,6 +1307,40 @@ bool Engine::build() {
     off += round64(t_h2_specs.size() * (sizeof(H2TrainW) / sizeof(float)) + 16);
     utab_off = off;
     off += round64(utab_host.size() + 16);
+    // CAPF_PLAN_BN_BATCH_STATS: the backbone's second op list -- one unit per conv of the plan -- and the unfolded packs its raw convs read, in
+    // every layout the plan keeps for that conv (the route per geometry and batch stays the plan's), behind everything the plan itself packs
+    if (plan.bn_batch) {
+        bn_unit_of.assign(ops.size(), -1);
+        raw_packs = packs;
+        for (int i = 0; i < n_backbone_ops; ++i) {
+            const Op& op = ops[i];
+            if (op.kind == OP_FORK || op.kind == OP_JOIN || op.kind == OP_FUSE) continue;
+            if (op.kind != OP_GEMM || !op.conv || op.bf16 || op.up_in >= 0 || packs[op.pack].kind != CONV_BN || packs[op.pack].in_place) {
+                err = "CAPF_PLAN_BN_BATCH_STATS: unexpected backbone op " + op.name;
+                return false;
+            }
+            bn_unit_of[i] = (int)bn_units.size();
+            bn_units.push_back(BnUnit{i, packs[op.pack].bn});
+            Pack& pk = raw_packs[op.pack];
+            pk.raw = true;
+            pk.w_off = off;
+            off += pk.wino_skip ? 64 : round64((size_t)pk.N * pk.Kpad);
+            if (pk.fast3x3) {
+                pk.direct_off = off;
+                off += round64((size_t)pk.N * pk.direct_Kpad);
+            }
+            if (pk.x3) {
+                pk.x3_off = off;
+                off += round64(((size_t)(plan.x3_h2 ? f32h2_pack_elems(pk.N, pk.Cin) : f32x3_pack_elems(pk.N, pk.Cin)) + 1) / 2);
+            }
+            pk.b_off = off;
+            off += round64((size_t)pk.N);
+            if (pk.h2g) {
+                pk.h2g_off = off;
+                off += round64((size_t)f32h2_gemm_pack_elems(pk.N, pk.h2g_Kpad));
+            }
+        }
+    }
     pack_elems = off;
     return true;
 }

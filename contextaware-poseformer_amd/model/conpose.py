@@ -7,7 +7,7 @@ from mvn.models.conpose import CA_PF
 
 
 class VolumetricTriangulationNet(CA_PF):
-    def __init__(self, config, device="cuda:0", compute_dtype="fp32"):
+    def __init__(self, config, device="cuda:0", compute_dtype="fp32", backbone_bn="running"):
         # ContextPose_mpi/common/cfg.py has no backbone.type key: the width list names the backbone
         width = config.model.backbone.STAGE2.NUM_CHANNELS[0]
         if width not in (32, 48):
@@ -17,7 +17,8 @@ class VolumetricTriangulationNet(CA_PF):
         # this variant's PoseTransformer builds `config.depth` blocks per group (pose_dformer.py:199, 217-227): the engine reads it
         # from the same key (capf_config.depth, 1..8, inference and, at this app's two widths, training; the shipped configuration has 4 == 4).  Training
         # (run_3dhp.py:60-101) goes through CA_PF's native step: `out, _ = model(...)` backpropagates into volume_net.
-        super().__init__(config, device, compute_dtype=compute_dtype, context_blocks=False)
+        # backbone_bn="batch": the frozen backbone's BatchNorm follows backbone.training as in run_3dhp.py:31-35 (CA_PF.__init__)
+        super().__init__(config, device, compute_dtype=compute_dtype, context_blocks=False, backbone_bn=backbone_bn)
 
     def forward(self, images, keypoints_2d_cpn, keypoints_2d_cpn_crop):
         x = super().forward(images, keypoints_2d_cpn, keypoints_2d_cpn_crop)       # [B, 1, 17, 3]

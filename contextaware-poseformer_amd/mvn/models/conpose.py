@@ -12,7 +12,7 @@ There is no eager / CPU fallback: CPU tensors or a missing libcapf.so raise.
 import torch
 from torch import nn
 
-from capf.lib import CapfError, Engine
+from capf.lib import PLAN_BN_BATCH_STATS, CapfError, Engine
 
 from . import _native
 
@@ -41,6 +41,9 @@ class _LifterStep(torch.autograd.Function):
         stream = torch.cuda.current_stream(images.device).cuda_stream
         if isinstance(images, _U8Images):     # the uint8 route: the same step, the stem reads the crops (nothing in the backward reads the image)
             eng.forward_train_u8(images.crops, images.mean, images.std, images.mode, k2d, kcrop, out, stream, masks)
+        elif owner._bn_batch_active():        # backbone_bn="batch", backbone in train mode: batch statistics, then the same lifter step on its maps
+            owner._backbone_forward_bn(eng, images, stream)
+            eng.lifter_forward_train(k2d, kcrop, out, stream, masks)
         else:
             eng.forward_train(images, k2d, kcrop, out, stream, masks)
         ctx.token = eng.train_generation()
@@ -68,6 +71,8 @@ class _LifterStep(torch.autograd.Function):
 
 
 MAP_GRAD_MODES = {"atomic": 0, "ordered": 1}
+BACKBONE_BN_MODES = ("running", "batch")
+BN_MOMENTUM = 0.1      # nn.BatchNorm2d's default, which every BatchNorm of the reference backbones keeps (pose_hrnet.py BN_MOMENTUM = 0.1)
 
 
 def resolve_map_grad_mode(value):
@@ -123,13 +128,27 @@ class _FeatureStep(torch.autograd.Function):
 
 
 class CA_PF(nn.Module):
-    def __init__(self, config, device="cuda:0", compute_dtype="fp32", context_blocks=True, plan_flags=0):
-        """compute_dtype: 'fp32' (exact fp32 MFMA, the reference's precision), 'bf16' (backbone convolutions on
+    def __init__(self, config, device="cuda:0", compute_dtype="fp32", context_blocks=True, plan_flags=0, backbone_bn="running"):
+        """backbone_bn: what the frozen backbone's BatchNorm layers do while `self.backbone.training` is set.  "running" (default): the
+        running statistics, folded into the convs, whatever the mode -- i.e. a frozen backbone left in .train() silently gets eval-mode
+        BatchNorm.  "batch" (HRNet, fp32): the module honours self.backbone.training as torch does -- in train mode every forward
+        normalises with the statistics of the batch, moves running_mean / running_var with momentum 0.1 and counts num_batches_tracked
+        (capf_backbone_forward_bn; what ContextPose_mpi/run_3dhp.py:31-35 computes, which never calls backbone.eval()); in eval mode
+        (an explicit backbone.eval() wins) today's route, on the statistics as they then stand.  No gradient reaches the backbone.
+        compute_dtype: 'fp32' (exact fp32 MFMA, the reference's precision), 'bf16' (backbone convolutions on
         bf16 MFMA with bf16 activations and fp32 accumulation; the lifter stays fp32) — an extension of the
         reference signature for BASELINE.json's bf16 configurations — or 'fp16' (the bf16 plan with IEEE fp16 as its
         16-bit element: same speed, 11 significand bits instead of 8; HRNet backbones, inference only)."""
+        if not isinstance(backbone_bn, str) or backbone_bn not in BACKBONE_BN_MODES:
+            raise ValueError("backbone_bn must be 'running' or 'batch', got {!r}".format(backbone_bn))
+        if backbone_bn == "batch" and (compute_dtype != "fp32" or config.model.backbone.type not in ("hrnet_32", "hrnet_48")):
+            raise ValueError("backbone_bn='batch' needs an HRNet backbone and compute_dtype='fp32' (got {!r}, {!r})".format(
+                config.model.backbone.type, compute_dtype))
         super().__init__()
         self.compute_dtype = compute_dtype
+        self.backbone_bn = backbone_bn
+        if backbone_bn == "batch":
+            plan_flags |= PLAN_BN_BATCH_STATS
         self.plan_flags = plan_flags               # capf.lib.PLAN_* bits: parity tests compare kernel families; 0 = product plan
         self.context_blocks = context_blocks       # False: the MPI-INF-3DHP variant (model/conpose.py)
         self.num_joints = config.model.backbone.num_joints
@@ -195,6 +214,24 @@ class CA_PF(nn.Module):
             if eng._bound:
                 eng.lifter_params_changed(stream)
 
+    # ---- backbone_bn="batch" ---------------------------------------------------------------------
+    def _bn_batch_active(self):
+        """This forward normalises with batch statistics: backbone_bn="batch" and the backbone is in train mode."""
+        return self.backbone_bn == "batch" and self.backbone.training
+
+    def _backbone_forward_bn(self, eng, images, stream):
+        """capf_backbone_forward_bn, and what torch's BatchNorm2d does next to it: num_batches_tracked += 1, on the device.  The running
+        statistics moved under every engine's folded packs: each refolds once, before its next running-statistics forward."""
+        eng.backbone_forward_bn(images, stream, BN_MOMENTUM)
+        with torch.no_grad():
+            gen, nbt = self.__dict__.get("_bn_counters", (None, None))
+            if gen != self._generation:      # (.to() replaces the buffers: _apply bumps the generation)
+                nbt = [b for n, b in self.backbone.named_buffers() if n.endswith("num_batches_tracked")]
+                self.__dict__["_bn_counters"] = (self._generation, nbt)
+            torch._foreach_add_(nbt, 1)
+        for e in self._engines.values():
+            e._bn_stale = True
+
     def _engine(self, images):
         dev = images.device
         if dev.type != "cuda":
@@ -213,6 +250,7 @@ class CA_PF(nn.Module):
                                                   compute_dtype=self.compute_dtype, plan_flags=self.plan_flags), device=dev.index)
             eng._bound_generation = None
             eng._lifter_print = None
+            eng._bn_stale = False
             self._engines[key] = eng
         lifter = list(self.volume_net.parameters())
         ptrs = tuple(p.data_ptr() for p in lifter)
@@ -228,10 +266,15 @@ class CA_PF(nn.Module):
             eng.bind_state({k: v.data for k, v in state.items()}, torch.cuda.current_stream(dev).cuda_stream)
             eng._bound_generation = self._generation
             eng._lifter_print = (ptrs, versions)
+            eng._bn_stale = False
             eng.rebinds = getattr(eng, "rebinds", 0) + 1
         elif eng._lifter_print[1] != versions:
             eng.lifter_params_changed(torch.cuda.current_stream(dev).cuda_stream)      # only volume_net values moved (optimizer step)
             eng._lifter_print = (ptrs, versions)
+        if eng._bn_stale and not self._bn_batch_active():
+            # batch-statistics forwards moved the running statistics: fold them again, once, on leaving train mode
+            eng.params_changed(torch.cuda.current_stream(dev).cuda_stream)
+            eng._bn_stale = False
         return eng
 
     # ---- conpose.py:30-42 --------------------------------------------------------------------
@@ -265,7 +308,11 @@ class CA_PF(nn.Module):
                                         names, *[p for _, p in named])
             else:
                 out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=images.device)
-                eng.forward(images, k2d, kcrop, out, stream)
+                if self._bn_batch_active():
+                    self._backbone_forward_bn(eng, images, stream)
+                    eng.lifter_forward(k2d, kcrop, out, stream)
+                else:
+                    eng.forward(images, k2d, kcrop, out, stream)
             if kcrop is not keypoints_2d_cpn_crop:
                 with torch.no_grad():
                     keypoints_2d_cpn_crop.copy_(kcrop)
@@ -284,6 +331,9 @@ class CA_PF(nn.Module):
         if not isinstance(mirror, str) or mirror not in MIRROR_MODES:
             raise ValueError("mirror must be 'none', 'all' or 'pair', got {!r}".format(mirror))
         mode = MIRROR_MODES[mirror]
+        if self._bn_batch_active():
+            raise NotImplementedError("forward_u8 has no batch-statistics route (backbone_bn='batch' with the backbone in train mode): "
+                                      "call backbone.eval(), or forward() on capf.lib.preprocess()'s fp32 images")
         if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8:
             raise TypeError("images_u8 must be uint8, got {}".format(getattr(images_u8, "dtype", type(images_u8))))
         if images_u8.device.type != "cuda":

@@ -118,6 +118,12 @@ enum capf_plan_flag {
                                      * by the same epilogue when convs read it too (capf_op_tensor slot 6; convs take the shadow, every residual is fp32).
                                      * layer1 runs one launch per conv (no bneck_bf16.hip / pointwise chain).  capf_create refuses it with CAPF_F32, with
                                      * CAPF_CPN50 and together with any other plan flag (CAPF_ERR_UNSUPPORTED).                                        */
+    CAPF_PLAN_BN_BATCH_STATS = 65536, /* OPT-IN, CAPF_HRNET + CAPF_F32 + training = 1 only (anything else: CAPF_ERR_UNSUPPORTED): the handle also carries the
+                                     * BATCH-STATISTICS route of the backbone, capf_backbone_forward_bn -- what a frozen backbone computes when it is
+                                     * left in train mode (ContextPose_mpi/run_3dhp.py:31-35 never calls backbone.eval()).  The plan itself -- ops,
+                                     * capf_num_ops, capf_op_info, the accounting entries, every other entry's bits -- is the flagless handle's and
+                                     * describes the running-statistics route; capf_workspace_bytes grows by the statistics scratch and the pack arena
+                                     * by an unfolded copy of every conv pack.  Cannot be combined with CAPF_PLAN_BF16_F32_STREAM.                  */
     CAPF_PLAN_F32X3_EXACT = 256     /* ... on round 4's tile instead of the default one: every operand split EXACTLY into three bf16 pieces,
                                      * six piece products per fp32 MAC (igemm_f32x3_ws.hip).  The default (ABI 5) carries an operand as two
                                      * block-scaled fp16 pieces (to 2^-23) and issues three products: half the MFMAs, the same measured
@@ -147,7 +153,8 @@ const char* capf_version(void);
  * capf_optim_ctrl_init, capf_grad_sumsq, capf_adamw_step_guarded; new structs capf_optim_report, capf_optim_segment); existing struct
  * layouts unchanged.  Revision 12 (additive): compute_dtype = CAPF_F16, tensor dtype code 3 (fp16) in capf_tensor / capf_op_desc, the
  * capf_op_*_16 entry points (the 16-bit kernels for either element format) and capf_debug_f16_round; struct layouts unchanged
- * (additive: capf_set_map_grad_mode, capf_map_grad_mode).                                                                                */
+ * (additive: capf_set_map_grad_mode, capf_map_grad_mode; CAPF_PLAN_BN_BATCH_STATS, capf_backbone_forward_bn, capf_op_bn_stats_scratch_bytes,
+ * capf_op_bn_stats, capf_op_bn_apply).                                                                                                   */
 #define CAPF_ABI_VERSION 12
 int capf_abi_version(void);
 
@@ -157,6 +164,8 @@ int capf_param_info(const capf_handle* h, int index, const char** name, int64_t 
                     int* ndim, int* kind);
 
 /* Borrow a device pointer for one state_dict entry (fp32; BN num_batches_tracked is ignored).
+ * On a handle with CAPF_PLAN_BN_BATCH_STATS the backbone's running_mean / running_var buffers must be WRITABLE: capf_backbone_forward_bn
+ * updates them in place through these pointers.
  * Replaces nn.Module parameter lookup during forward.  The pointer must stay valid until the
  * next capf_set_param for that name or capf_destroy. */
 int capf_set_param(capf_handle* h, const char* name, const void* dev_ptr, const int64_t* shape,
@@ -188,6 +197,29 @@ int capf_forward(capf_handle* h, void* stream, const float* images_nhwc, const f
 /* Backbone only: writes nothing to `out`; the four context maps stay in the workspace (NHWC) and
  * can be read through capf_tensor("feat0".."feat3").  Replaces self.backbone(images) conpose.py:38. */
 int capf_backbone_forward(capf_handle* h, void* stream, const float* images_nhwc, int batch);
+
+/* capf_backbone_forward with BATCH statistics in every BatchNorm2d: replaces self.backbone(images) while the backbone is in train mode
+ * (nn.BatchNorm2d.forward with self.training: F.batch_norm(..., training=True, momentum, eps = 1e-5)), for a handle created with
+ * CAPF_PLAN_BN_BATCH_STATS (any other handle: CAPF_ERR_STATE).  It leaves feat0..3 in the workspace, valid for `batch`, exactly as
+ * capf_backbone_forward does: capf_lifter_forward / capf_lifter_forward_train / capf_backward / capf_backward_maps run on them unchanged,
+ * and like every backbone run it invalidates a saved training step.  Batch range, workspace, unpacked parameters and plan-only handles are
+ * refused as by the other run entries.  Gradients do not reach the backbone (it stays frozen).
+ * Per BatchNorm, with n = batch * H * W values per channel of the raw conv output x:
+ *     mean, var (biased) over the batch;   y = (x - mean) / sqrt(var + 1e-5) * gamma + beta  (+ residual) (ReLU);
+ *     running_mean <- (1 - momentum) * running_mean + momentum * mean;
+ *     running_var  <- (1 - momentum) * running_var  + momentum * var * n / (n - 1).
+ * THE RUNNING STATISTICS ARE WRITTEN IN PLACE through the pointers capf_set_param borrowed: on such a handle the running_mean / running_var
+ * buffers must be writable device memory.  num_batches_tracked stays ignored; the host counts it.  The folded packs of the plan are NOT
+ * refreshed: the next running-statistics run (capf_forward, capf_backbone_forward, ...) sees the moved statistics only after
+ * capf_params_changed.  If a BatchNorm has n < 2 at this batch and input size (batch 1 at a 32x32 input: the deepest map is 1x1) the call
+ * returns CAPF_ERR_INVALID -- torch's "Expected more than 1 value per channel when training" -- and nothing is launched or written.
+ * Every unit conv -> BatchNorm (-> + residual) (-> ReLU) runs as the raw convolution (unfolded weights, on the kernel family and in the
+ * grouped launch per dependency level that the plan routes its geometry and batch to), the statistics (two launches, no atomics, one fixed
+ * summation order: the same inputs give the same bits on every run, handle and capf_set_lanes mode) and one normalise pass in place; the
+ * launches that cross a BatchNorm (chained pointwise pairs, CAPF_PLAN_H2_PLANES) are not used.  Everything is enqueued on `stream` alone.
+ * Measured (EXPERIMENTS R22.1, HRNet-32, 256x256): the backbone takes 24.6 against 14.7 ms at batch 160 and 11.2 against 5.7 ms at batch 64
+ * (491 / 427 launches against 170 / 184; 106 launches each of the two statistics stages and of the apply pass), a training step 1.58x / 1.62x. */
+int capf_backbone_forward_bn(capf_handle* h, void* stream, const float* images_nhwc, int batch, float momentum);
 
 /* ---- training step of the lifter (the backbone is frozen, conpose.py:22-25) --
  * capf_forward_train: capf_forward that keeps the lifter's intermediates for capf_backward.
@@ -412,6 +444,18 @@ int capf_op_conv_wino(void* stream, const float* x, const float* wp, const float
 int capf_op_conv_wino_group(void* stream, int n, const capf_conv_desc* d, int variant);
 int capf_op_linear(void* stream, const float* x, const float* w, const float* bias, const float* residual,
                    float* y, int M, int N, int K, int act);
+/* Training-mode BatchNorm2d as capf_backbone_forward_bn runs it (csrc/bn_train.hip), on x [rows = B * H * W, C] NHWC fp32; C % 4 == 0, C <= 1024.
+ * capf_op_bn_stats: the batch statistics of x -- per-slab fp64 partial means / sums of squared deviations, combined by a second launch in a
+ *     fixed order, no atomics: bit-identical from run to run -- into scale[c] = gamma[c] / sqrt(var[c] + eps) and
+ *     shift[c] = beta[c] - mean[c] * scale[c]; running_mean / running_var (each may be NULL) are updated in place with `momentum` as above.
+ *     scratch: capf_op_bn_stats_scratch_bytes(rows, C) bytes of device memory, 8-byte aligned (0: a shape the kernels do not take).
+ *     rows < 2: CAPF_ERR_INVALID.
+ * capf_op_bn_apply: y = act(x * scale[c] + shift[c] + residual); y may be x, residual may be NULL; act 0 none, 1 ReLU (a NaN stays a NaN). */
+size_t capf_op_bn_stats_scratch_bytes(int64_t rows, int C);
+int capf_op_bn_stats(void* stream, const float* x, int64_t rows, int C, const float* gamma, const float* beta, float eps, float momentum,
+                     float* running_mean, float* running_var, float* scale, float* shift, void* scratch, size_t scratch_bytes);
+int capf_op_bn_apply(void* stream, const float* x, const float* scale, const float* shift, const float* residual, float* y, int64_t rows, int C,
+                     int act);
 /* capf_op_bilinear_corners: the corner rule of both sampling sites (F.grid_sample, bilinear, align_corners=True) on
  * caller-supplied normalised coordinates grid [n,2] = (x, y): idx [n,2] = NW corner (x0, y0), frac [n,2] = weights of the
  * +1 corners.  border = 1: padding_mode='border' (DeformableBlock, pose_dformer.py:128), 0: 'zeros' (:217).  The same

@@ -40,9 +40,12 @@ int main() {
     int handles = 0;
     for (int backbone : {CAPF_HRNET, CAPF_CPN50})
         for (int width : {32, 48})
-            for (int dtype : {CAPF_F32, CAPF_BF16}) {
+            for (int dtype : {CAPF_F32, CAPF_BF16})
+            for (int flags : {0, (int)CAPF_PLAN_BN_BATCH_STATS}) {      // (the flag: the batch-statistics route's units and unfolded packs next to the plan)
                 if (backbone == CAPF_CPN50 && width == 48) continue;
-                const capf_config c = config(backbone, width, dtype, 1);
+                if (flags && (backbone != CAPF_HRNET || dtype != CAPF_F32)) continue;
+                capf_config c = config(backbone, width, dtype, 1);
+                c.plan_flags = flags;
                 capf_handle* h = nullptr;
                 CHECK(capf_create(&c, -1, &h) == CAPF_OK && h);
                 const int n = capf_num_ops(h);
@@ -54,6 +57,7 @@ int main() {
                 }
                 CHECK(capf_forward(h, nullptr, mem, mem, mem, 2, mem) == CAPF_ERR_STATE);
                 CHECK(capf_backbone_forward(h, nullptr, mem, 2) == CAPF_ERR_STATE);
+                CHECK(capf_backbone_forward_bn(h, nullptr, mem, 2, 0.1f) == CAPF_ERR_STATE);
                 CHECK(capf_forward_train(h, nullptr, mem, mem, mem, 2, mem, nullptr) == CAPF_ERR_STATE);
                 CHECK(capf_forward_u8(h, nullptr, bytes, mem, nullptr, 2, mem, mem, 2, mem) == CAPF_ERR_STATE);
                 CHECK(capf_backbone_forward_u8(h, nullptr, bytes, mem, mem, 3, 2) == CAPF_ERR_INVALID);
