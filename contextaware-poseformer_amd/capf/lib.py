@@ -40,6 +40,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_forward_u8", "capf_backbone_forward_u8", "capf_forward_train_u8", "capf_preprocess_points", "capf_input_rule_host",
     "capf_op_conv_u8", "capf_op_conv_u8_kernel_name", "capf_op_conv_stem_kernel_name",
     "capf_backbone_forward_bn", "capf_op_bn_stats_scratch_bytes", "capf_op_bn_stats", "capf_op_bn_apply",
+    "capf_backward_points",
 ]
 
 
@@ -167,6 +168,7 @@ def load_library():
     lib.capf_set_features.argtypes = [H, P, POINTER(P), c_int]
     lib.capf_lifter_forward_train.argtypes = [H, P, P, P, c_int, P, P]
     lib.capf_backward_maps.argtypes = [H, P, P, c_int, P, P, POINTER(P)]
+    lib.capf_backward_points.argtypes = [H, P, P, c_int, P, P, POINTER(P), P, P]
     lib.capf_set_map_grad_mode.argtypes = [H, c_int]
     lib.capf_map_grad_mode.argtypes = [H]
     lib.capf_map_grad_mode.restype = c_int
@@ -436,6 +438,16 @@ class Engine:
                                                 c_void_p(flat_grad.data_ptr()),
                                                 c_void_p(masks.data_ptr()) if masks is not None else c_void_p(0),
                                                 self._ptrs4(dfeat_nhwc)), "backward_maps")
+
+    def backward_points(self, grad_out, flat_grad, stream, masks=None, dfeat_nhwc=None, dk2d=None, dref=None):
+        """capf_backward plus any of: the map gradient (four contiguous fp32 NHWC tensors, as backward_maps), dk2d and dref (contiguous
+        fp32 [B, J, 2]; dref is w.r.t. the NORMALISED crop keypoints).  None: that output is not computed."""
+        B = grad_out.shape[0]
+        ptr = lambda t: c_void_p(t.data_ptr()) if t is not None else c_void_p(0)
+        self._check(self.lib.capf_backward_points(self.h, c_void_p(stream), c_void_p(grad_out.data_ptr()), B,
+                                                  c_void_p(flat_grad.data_ptr()), ptr(masks),
+                                                  self._ptrs4(dfeat_nhwc) if dfeat_nhwc is not None else None, ptr(dk2d), ptr(dref)),
+                    "backward_points")
 
     def set_map_grad_mode(self, mode):
         """How capf_backward_maps sums the map gradient: 0 fp32 atomic adds (default), 1 the ordered, bit-reproducible sum."""

@@ -1043,6 +1043,26 @@ int capf_backward_maps(capf_handle* h, void* stream, const float* grad_out, int 
     return e.backward(static_cast<hipStream_t>(stream), batch, grad_out, flat_grad, drop_masks, dfeat_nhwc);
 }
 
+// keypoint gradients: fp32 plans only (the position gradients are formed from fp32 maps; a 16-bit plan stores feat0..3 in its own format)
+int capf_backward_points(capf_handle* h, void* stream, const float* grad_out, int batch, float* flat_grad, const float* drop_masks,
+                         float* const dfeat_nhwc[4], float* dk2d, float* dref) {
+    if (!h || !grad_out || !flat_grad || batch < 1) return CAPF_ERR_INVALID;
+    Engine& e = h->e;
+    for (int l = 0; dfeat_nhwc && l < e.cfg.levels; ++l)
+        if (!dfeat_nhwc[l]) return CAPF_ERR_INVALID;
+    if (e.b16()) {
+        e.err = std::string("capf_backward_points: keypoint gradients are computed on fp32 plans only; this handle's compute_dtype is ") +
+                (e.f16() ? "fp16" : "bf16");
+        return CAPF_ERR_UNSUPPORTED;
+    }
+    for (int l = 0; dfeat_nhwc && l < e.cfg.levels; ++l)
+        if ((size_t)dfeat_nhwc[l] & 15) {
+            e.err = "capf_backward_points: dfeat_nhwc pointers must be 16-byte aligned";
+            return CAPF_ERR_INVALID;
+        }
+    return e.backward(static_cast<hipStream_t>(stream), batch, grad_out, flat_grad, drop_masks, dfeat_nhwc, dk2d, dref);
+}
+
 int capf_set_map_grad_mode(capf_handle* h, int mode) {
     if (!h) return CAPF_ERR_INVALID;
     Engine& e = h->e;

@@ -443,7 +443,8 @@ struct Engine {
     void train_layout(int B, TrainLayout& L) const;
     size_t train_elems(int B) const;
     int forward_train(hipStream_t s, int B, const float* masks);
-    int backward(hipStream_t s, int B, const float* dOut, float* flat_grad, const float* masks, float* const* dfeat = nullptr);
+    int backward(hipStream_t s, int B, const float* dOut, float* flat_grad, const float* masks, float* const* dfeat = nullptr,
+                 float* dk2d = nullptr, float* dref = nullptr);
     int t_gemm(hipStream_t s, const float* A, RowMap amap, int M, int N, int K, const float* W, int Kpad, const float* bias,
                float* out, RowMap omap, const float* res, RowMap rmap, int act, const float* rscale, int rs_div, const float* Wh2 = nullptr);
     // The lifter's linears on the two-fp16-piece GEMM during a training step (forward: y = x W^T, backward: dX = dY W): which matrices,

@@ -609,7 +609,26 @@ hipError_t launch_gelu_bwd(const float* x, const float* dy, float* dx, long n, h
 hipError_t launch_transpose_pad(const float* in, RowMap imap, int M, int C, float* out, int Mp, hipStream_t s);
 hipError_t launch_attention_bwd(const float* qkv, const float* dO, float* dqkv, int groups, int N, int heads, int d,
                                 hipStream_t s);
-hipError_t launch_deform_bwd(const DeformArgs& a, float* dAO, int ldd, hipStream_t s);
+// dref (optional, capf_backward_points; fp32 maps only): [B*J, 2], the block's position gradients are added to it -- the kernel's PTS form
+hipError_t launch_deform_bwd(const DeformArgs& a, float* dAO, int ldd, hipStream_t s, float* dref = nullptr);
+// ---- gradient w.r.t. the keypoints (capf_backward_points).  dref [B*J, 2] is dL/d(normalised crop keypoints): zeroed by the caller, then
+//     dref = ((((0 + c[Lv-1]) + c[Lv-2]) + ...) + c[0]) + r_ref
+// with c[i] added by context block i's launch_deform_bwd (the order Engine::backward visits them) and r_ref by launch_points_grad: every
+// term a fixed fp32 expression (train_kernels.hip), every add a plain load and store by the one block that owns (b, p).  Bit-reproducible.
+struct PointsGradArgs {
+    const float* feat[4];    // fp32 NHWC context maps
+    int H[4], W[4], C[4];
+    const float* dS[4];      // input gradient of feat_embed[l], [B*J, C_l]
+    const float* ref;        // [B*J, 2] normalised crop keypoints
+    const float* dX;         // token gradient; row (b, p) at dX + (b * J + p) * ldx, token 0 = its first Ce floats
+    long ldx;
+    const float* cw;         // coord_embed.weight [Ce, 2]
+    int Ce;
+    float* dref;             // [B*J, 2] or null: dref += r_ref
+    float* dk2d;             // [B*J, 2] or null: dk2d = dX[:, 0, :] coord_embed.weight
+    int B, J, L;
+};
+hipError_t launch_points_grad(const PointsGradArgs& a, hipStream_t s);
 // ---- gradient w.r.t. the context maps (capf_backward_maps): the backward of both bilinear samplers w.r.t. the SAMPLED tensor.  g[l] holds
 // the gradient of every sampled vector; each is added to its (up to) four corners of dfeat[l] (fp32 NHWC [B, H, W, C], zeroed first by
 // launch_zero_maps), lanes over contiguous channels.  Two summation forms of the same sources into the same destinations:

@@ -498,7 +498,12 @@ int Engine::forward_train(hipStream_t s, int B, const float* masks) {
 // the gradient w.r.t. the context maps.  Its two sources are the deformable samplers (dU[l] of every context block, scattered while it
 // is live) and the reference-point sampler (the input gradient of feat_embed[l], which the parameter step has no use for).
 // map_grad_mode picks the summation form at those two places (kernels.h, MapGradArgs): 0 atomic adds, 1 the ordered sum; nothing else differs.
-int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const float* masks, float* const* dfeat) {
+// dk2d, dref (capf_backward_points; nullptr: nothing below changes): the gradient w.r.t. the 2-D keypoints (coord_embed's input) and w.r.t.
+// the NORMALISED crop keypoints, [B, J, 2] each.  dref has three sources: the positions pos = tanh(offset) + ref of every deformable sampler
+// (launch_deform_bwd's PTS form adds each block's share while it is live) and the reference-point sampler's grid (launch_points_grad, from the
+// same dS_l the map gradient scatters); kernels.h, PointsGradArgs, states the one expression they form.
+int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const float* masks, float* const* dfeat, float* dk2d,
+                     float* dref) {
     if (B != ses.train_batch) {
         err = "capf_backward: the activations of the matching capf_forward_train are gone (no such call, another batch size, or "
               "a later forward / workspace change overwrote them)";
@@ -531,6 +536,7 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
     };
 
     HIP_TRY(hipMemsetAsync(dX, 0, sizeof(float) * (size_t)B * J * D, s));
+    if (dref) HIP_TRY(hipMemsetAsync(dref, 0, sizeof(float) * (size_t)B * J * 2, s));
     MapGradArgs mg{};
     if (dfeat) {
         ZeroMaps z{};
@@ -626,7 +632,7 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
         }
         da.AO = tw + c.ao; da.ref = kcrop; da.B = B; da.J = J; da.L = Lv; da.NH = NH; da.NS = NS; da.ld_ao = 64;
         da.feat_bf16 = maps_bf16() ? 1 : 0;
-        HIP_TRY(launch_deform_bwd(da, gA, 64, s));                                  // gA = dAO [R, 64]
+        HIP_TRY(launch_deform_bwd(da, gA, 64, s, dref));                            // gA = dAO [R, 64]
         if (dfeat) {                                     // the same dU, to the corners it was gathered from
             for (int l = 0; l < Lv; ++l) mg.g[l] = tw + L.dU[l];
             mg.AO = tw + c.ao;
@@ -655,10 +661,22 @@ int Engine::backward(hipStream_t s, int B, const float* dOut, float* flat, const
     {
         const int R = B * J;
         for (int l = 0; l < Lv; ++l) {
-            // (the input gradient dS_l [R, C_l] only for the map gradient; it takes dU[l]'s place, dead behind the context blocks)
+            // (the input gradient dS_l [R, C_l] only for the map and reference-point gradients; it takes dU[l]'s place, dead behind the context blocks)
+            const bool want_dS = dfeat || dref;
             int rc = linear_bwd(lifter.feat_embed[l], dX, row_ld(D, (long)(1 + l) * C), R, tw + L.S[l], row_ld(feat_C[l]),
-                                dfeat ? tw + L.dU[l] : nullptr, row_ld(dfeat ? feat_C[l] : 0));
+                                want_dS ? tw + L.dU[l] : nullptr, row_ld(want_dS ? feat_C[l] : 0));
             if (rc) return rc;
+        }
+        if (dk2d || dref) {
+            PointsGradArgs pg{};
+            for (int l = 0; l < Lv; ++l) {
+                pg.feat[l] = bptr(feat_buf[l], B);
+                pg.H[l] = feat_H[l]; pg.W[l] = feat_W[l]; pg.C[l] = feat_C[l];
+                pg.dS[l] = tw + L.dU[l];
+            }
+            pg.ref = kcrop; pg.dX = dX; pg.ldx = D; pg.cw = P(lifter.coord.w); pg.Ce = C;
+            pg.dref = dref; pg.dk2d = dk2d; pg.B = B; pg.J = J; pg.L = Lv;
+            HIP_TRY(launch_points_grad(pg, s));
         }
         if (dfeat) {
             for (int l = 0; l < Lv; ++l) mg.g[l] = tw + L.dU[l];

@@ -808,8 +808,14 @@ __device__ __forceinline__ f32x4 ld4_t(const float* pix, int q) {      // channe
 // (16-byte corner loads; G = the largest power of two <= min(64, C / 4)): at 32 channels eight pairs' corners are in flight per wave
 // instead of one pair on half the lanes, and a pair's three sums reduce over G lanes instead of 64.  The pairs' results meet in 384 bytes
 // of LDS per wave for the softmax backward.
-template <int NS, bool BF>
-__global__ void deform_bwd_kernel(DeformArgs a, float* __restrict__ dAO, int ldd) {
+// PTS (capf_backward_points): the block also adds its samples' position gradients -- part[l][k][1..2], i.e. dL/dpos with the softmax weight,
+// the (size - 1) / 2 factor and the border-clip mask, BEFORE the tanh factor -- to dref[b, p], since pos = tanh(offset) + ref:
+//     c[b, p] = one running fp32 sum, from 0, over l ascending and inside a level over k = h * NS + s ascending;   dref[b, p] = dref[b, p] + c
+// by one lane per coordinate of wave 0, with a plain load and a plain store: block (b, p) is the only writer of its two floats in a launch
+// and the launches of successive context blocks are ordered on the stream.  The block-level barrier needs every thread of the block:
+// the launcher starts exactly 64 * L threads, so nothing leaves at the `l >= a.L` test.  The instantiations without PTS never read dref.
+template <int NS, bool BF, bool PTS>
+__global__ void deform_bwd_kernel(DeformArgs a, float* __restrict__ dAO, int ldd, float* __restrict__ dref) {
     __shared__ float part[4][16][6];                  // [level][pair]: dw, gx, gy, softmax weight, tanh(ox), tanh(oy)
     const int bp = blockIdx.x;
     const int l = threadIdx.x >> 6;
@@ -883,6 +889,15 @@ __global__ void deform_bwd_kernel(DeformArgs a, float* __restrict__ dAO, int ldd
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();                      // (a wave reads back only what it wrote itself)
+    if (PTS) {
+        __syncthreads();                                  // (... except wave 0 here, which reads every level's rows)
+        if (l == 0 && lane < 2) {
+            float c = 0.f;
+            for (int ll = 0; ll < a.L; ++ll)
+                for (int k = 0; k < nk; ++k) c += part[ll][k][1 + lane];
+            dref[bp * 2 + lane] = dref[bp * 2 + lane] + c;
+        }
+    }
     if (lane < nk) {
         const int k = lane, h = k / NS;
         float dotw = 0.f;
@@ -896,12 +911,107 @@ __global__ void deform_bwd_kernel(DeformArgs a, float* __restrict__ dAO, int ldd
     for (int k = 3 * nk + lane; k < ldd; k += 64) dao[k] = 0.f;      // padding columns of the 64-wide row
 }
 
-hipError_t launch_deform_bwd(const DeformArgs& a, float* dAO, int ldd, hipStream_t s) {
-    if (a.NS != 4 || a.L > 4 || a.NH * a.NS > 16) return hipErrorInvalidValue;
+hipError_t launch_deform_bwd(const DeformArgs& a, float* dAO, int ldd, hipStream_t s, float* dref) {
+    if (a.NS != 4 || a.L < 1 || a.L > 4 || a.NH * a.NS > 16) return hipErrorInvalidValue;
     for (int l = 0; l < a.L; ++l)
         if (a.C[l] < 4 || (a.C[l] & 3)) return hipErrorInvalidValue;
-    if (a.feat_bf16) hipLaunchKernelGGL((deform_bwd_kernel<4, true>), dim3(a.B * a.J), dim3(64 * a.L), 0, s, a, dAO, ldd);
-    else hipLaunchKernelGGL((deform_bwd_kernel<4, false>), dim3(a.B * a.J), dim3(64 * a.L), 0, s, a, dAO, ldd);
+    float* const none = nullptr;
+    if (dref) {
+        if (a.feat_bf16) return hipErrorInvalidValue;     // (keypoint gradients: fp32 maps only)
+        hipLaunchKernelGGL((deform_bwd_kernel<4, false, true>), dim3(a.B * a.J), dim3(64 * a.L), 0, s, a, dAO, ldd, dref);
+    } else if (a.feat_bf16) hipLaunchKernelGGL((deform_bwd_kernel<4, true, false>), dim3(a.B * a.J), dim3(64 * a.L), 0, s, a, dAO, ldd, none);
+    else hipLaunchKernelGGL((deform_bwd_kernel<4, false, false>), dim3(a.B * a.J), dim3(64 * a.L), 0, s, a, dAO, ldd, none);
+    return hipGetLastError();
+}
+
+// ---- gradient w.r.t. the keypoints, the part outside the context blocks (capf_backward_points) ---------------------------------------------
+// One block per (b, p), 64 * L threads; wave l = level l.
+// dref: the reference-point sampler, F.grid_sample(feat_l, ref, bilinear, padding zeros, align_corners=True) (pose_dformer.py:217), w.r.t.
+// its grid.  Cells and fractions are bilinear_corner<false>'s, the forward's; a corner outside the map reads 0 and there is NO clip mask
+// (zeros padding does not clip: ATen grid_sampler_compute_source_index_set_grad multiplies by (size - 1) / 2 only):
+//     gx_l = (W_l - 1) / 2 * sum_c dS_l[c] * ((f01 - f00) * wy0 + (f11 - f10) * wy1)
+//     gy_l = (H_l - 1) / 2 * sum_c dS_l[c] * ((f10 - f00) * wx0 + (f11 - f01) * wx1)
+// (a 1 x 1 map: factor 0, nothing divides by a size).  G lanes, one channel quad each as in deform_bwd_kernel, reduce by the xor tree; then
+//     dref[b, p] = dref[b, p] + (((g_0 + g_1) + g_2) + g_3)          (levels ascending; wave 0, plain load and store)
+// dk2d: coord_embed (pose_dformer.py:214) w.r.t. its input, dk2d[b, p, j] = sum_c dX[b, p, 0, c] * W[c, j]: wave 0, lane i sums the channels
+// c = i, i + 64, ... ascending, then the xor tree over the 64 lanes (offsets 32, 16, ... 1).  Both are fixed expressions: no atomics.
+__global__ __launch_bounds__(256) void points_grad_kernel(PointsGradArgs a) {
+    __shared__ float gl[4][2];
+    const int bp = blockIdx.x;
+    const int l = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    if (l >= a.L) return;                                 // (never: exactly 64 * L threads, every one reaches the barrier)
+    if (a.dref) {
+        const int b = bp / a.J;
+        const int H = a.H[l], W = a.W[l], C = a.C[l];
+        const float* feat = a.feat[l] + (long)b * H * W * C;
+        const float* dS = a.dS[l] + (long)bp * C;
+        const BilinearCorner q = bilinear_corner<false>(a.ref[bp * 2 + 0], a.ref[bp * 2 + 1], H, W);
+        const float wx1 = q.wx1, wy1 = q.wy1, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+        const unsigned xa = (unsigned)q.x0, xb = xa + 1u, ya = (unsigned)q.y0, yb = ya + 1u;     // (a negative cell wraps past every size)
+        const bool vxa = xa < (unsigned)W, vxb = xb < (unsigned)W, vya = ya < (unsigned)H, vyb = yb < (unsigned)H;
+        const unsigned cxa = vxa ? xa : 0u, cxb = vxb ? xb : 0u, cya = vya ? ya : 0u, cyb = vyb ? yb : 0u;     // (addresses stay inside the map)
+        const float* p00 = feat + ((long)cya * W + cxa) * C;
+        const float* p01 = feat + ((long)cya * W + cxb) * C;
+        const float* p10 = feat + ((long)cyb * W + cxa) * C;
+        const float* p11 = feat + ((long)cyb * W + cxb) * C;
+        const bool v00 = vxa && vya, v01 = vxb && vya, v10 = vxa && vyb, v11 = vxb && vyb;
+        const int Q = C >> 2;
+        int G = 64;
+        while (G > Q) G >>= 1;
+        float a_gx = 0.f, a_gy = 0.f;
+        if (lane < G && (v00 || v01 || v10 || v11)) {
+            const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int qd = lane; qd < Q; qd += G) {
+                const f32x4 g = *reinterpret_cast<const f32x4*>(dS + 4 * qd);
+                const f32x4 f00 = v00 ? ld4_t<false>(p00, qd) : zero, f01 = v01 ? ld4_t<false>(p01, qd) : zero,
+                            f10 = v10 ? ld4_t<false>(p10, qd) : zero, f11 = v11 ? ld4_t<false>(p11, qd) : zero;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    a_gx += g[e] * ((f01[e] - f00[e]) * wy0 + (f11[e] - f10[e]) * wy1);
+                    a_gy += g[e] * ((f10[e] - f00[e]) * wx0 + (f11[e] - f01[e]) * wx1);
+                }
+            }
+        }
+        for (int o = G >> 1; o > 0; o >>= 1) {
+            a_gx += __shfl_xor(a_gx, o, 64);
+            a_gy += __shfl_xor(a_gy, o, 64);
+        }
+        if (lane == 0) {
+            gl[l][0] = a_gx * (0.5f * (float)(W - 1));
+            gl[l][1] = a_gy * (0.5f * (float)(H - 1));
+        }
+        __syncthreads();
+        if (l == 0 && lane < 2) {
+            float r = gl[0][lane];
+            for (int ll = 1; ll < a.L; ++ll) r += gl[ll][lane];
+            a.dref[bp * 2 + lane] = a.dref[bp * 2 + lane] + r;
+        }
+    }
+    if (a.dk2d && l == 0) {
+        const float* dx = a.dX + (long)bp * a.ldx;
+        float sx = 0.f, sy = 0.f;
+        for (int c = lane; c < a.Ce; c += 64) {
+            const float d = dx[c];
+            sx += d * a.cw[2 * c + 0];
+            sy += d * a.cw[2 * c + 1];
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            sx += __shfl_xor(sx, o, 64);
+            sy += __shfl_xor(sy, o, 64);
+        }
+        if (lane == 0) {
+            a.dk2d[bp * 2 + 0] = sx;
+            a.dk2d[bp * 2 + 1] = sy;
+        }
+    }
+}
+
+hipError_t launch_points_grad(const PointsGradArgs& a, hipStream_t s) {
+    if (a.L < 1 || a.L > 4 || (!a.dref && !a.dk2d)) return hipErrorInvalidValue;
+    for (int l = 0; l < a.L && a.dref; ++l)
+        if (a.C[l] < 4 || (a.C[l] & 3)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(points_grad_kernel, dim3(a.B * a.J), dim3(64 * a.L), 0, s, a);
     return hipGetLastError();
 }
 

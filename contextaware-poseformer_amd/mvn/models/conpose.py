@@ -28,17 +28,34 @@ class _U8Images:
 
 
 MIRROR_MODES = {"none": 0, "all": 1, "pair": 2}       # CA_PF.forward_u8's `mirror` -> capf_preprocess's mode
+CROP_HALF = (192 // 2, 256 // 2)                      # conpose.py:34: ref = kcrop / (96, 128) - 1, so d(ref)/d(kcrop) = 1 / (96, 128)
+
+
+def _private_ref(ctx, index, kcrop):
+    """The buffer a step hands to the engine as kcrop_inout: the caller's tensor (normalised in place, conpose.py:34-35), unless it takes
+    part in the graph -- then a private contiguous copy, because the in-place write would raise on a leaf and corrupt a non-leaf."""
+    return kcrop.detach().clone(memory_format=torch.contiguous_format) if ctx.needs_input_grad[index] else kcrop
+
+
+def _crop_grad(owner, dref):
+    """dL/d(crop keypoints in pixels) from dL/d(ref): one division by (96, 128)."""
+    scale = owner.__dict__.setdefault("_crop_half", {})
+    if dref.device not in scale:
+        scale[dref.device] = torch.tensor(CROP_HALF, dtype=torch.float32, device=dref.device)
+    return dref / scale[dref.device]
 
 
 class _LifterStep(torch.autograd.Function):
     """Autograd boundary of the native training step: forward = capf_forward_train, backward =
     capf_backward into one flat gradient buffer whose slices are returned as the parameter gradients
-    (so torch optimizers, DDP hooks and `capf.dist.allreduce_mean_` all see ordinary .grad tensors)."""
+    (so torch optimizers, DDP hooks and `capf.dist.allreduce_mean_` all see ordinary .grad tensors).  When k2d or kcrop takes part in the
+    graph, backward = capf_backward_points and their gradients are returned too (kcrop's w.r.t. the pixel values the caller passed)."""
 
     @staticmethod
     def forward(ctx, owner, eng, images, k2d, kcrop, masks, names, *params):
         out = torch.empty(images.shape[0], 1, owner.num_joints, 3, dtype=torch.float32, device=images.device)
         stream = torch.cuda.current_stream(images.device).cuda_stream
+        kcrop = _private_ref(ctx, 4, kcrop)
         if isinstance(images, _U8Images):     # the uint8 route: the same step, the stem reads the crops (nothing in the backward reads the image)
             eng.forward_train_u8(images.crops, images.mean, images.std, images.mode, k2d, kcrop, out, stream, masks)
         elif owner._bn_batch_active():        # backbone_bn="batch", backbone in train mode: batch statistics, then the same lifter step on its maps
@@ -62,12 +79,21 @@ class _LifterStep(torch.autograd.Function):
         layout, total = eng.grad_layout_cached()
         flat = torch.empty(total, dtype=torch.float32, device=grad_out.device)
         stream = torch.cuda.current_stream(grad_out.device).cuda_stream
-        eng.backward(grad_out.contiguous(), flat, stream, ctx.masks)
+        need_k2d, need_ref = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        dk2d = dkcrop = None
+        if need_k2d or need_ref:
+            dk2d = torch.empty_like(ctx.keep[0]) if need_k2d else None
+            dref = torch.empty_like(ctx.keep[1]) if need_ref else None
+            eng.backward_points(grad_out.contiguous(), flat, stream, ctx.masks, None, dk2d, dref)
+            dkcrop = _crop_grad(ctx.owner, dref) if need_ref else None
+        else:
+            eng.backward(grad_out.contiguous(), flat, stream, ctx.masks)
         ctx.owner.last_flat_grad = flat
+        head = (None, None, None, dk2d, dkcrop, None, None)
         if ctx.owner.flat_grad_only:      # the caller consumes last_flat_grad itself (capf.optim.FusedAdamW + capf.dist)
-            return (None,) * (7 + len(ctx.names))
+            return head + (None,) * len(ctx.names)
         grads = tuple(flat[layout[n][0]: layout[n][0] + layout[n][1]].view(shp) for n, shp in zip(ctx.names, ctx.shapes))
-        return (None,) * 7 + grads
+        return head + grads
 
 
 MAP_GRAD_MODES = {"atomic": 0, "ordered": 1}
@@ -88,13 +114,15 @@ def resolve_map_grad_mode(value):
 class _FeatureStep(torch.autograd.Function):
     """_LifterStep on caller-supplied context maps: forward = capf_set_features + capf_lifter_forward_train, backward =
     capf_backward_maps, which returns the gradient w.r.t. the four maps next to the flat parameter gradient.  The maps arrive as
-    contiguous NHWC tensors (the permute from the backbone's NCHW, and its transpose on the way back, are torch's)."""
+    contiguous NHWC tensors (the permute from the backbone's NCHW, and its transpose on the way back, are torch's).  When k2d or kcrop takes
+    part in the graph, backward = capf_backward_points with the same four maps, and their gradients are returned too."""
 
     @staticmethod
     def forward(ctx, owner, eng, k2d, kcrop, masks, names, n_maps, *maps_and_params):
         feats, params = maps_and_params[:n_maps], maps_and_params[n_maps:]
         out = torch.empty(k2d.shape[0], 1, owner.num_joints, 3, dtype=torch.float32, device=k2d.device)
         stream = torch.cuda.current_stream(k2d.device).cuda_stream
+        kcrop = _private_ref(ctx, 3, kcrop)
         eng.set_features(feats, stream)
         eng.lifter_forward_train(k2d, kcrop, out, stream, masks)
         ctx.token = eng.train_generation()
@@ -118,13 +146,22 @@ class _FeatureStep(torch.autograd.Function):
         stream = torch.cuda.current_stream(grad_out.device).cuda_stream
         if eng.map_grad_mode() != ctx.map_grad_mode:      # a state change of the handle: once per change, not per step
             eng.set_map_grad_mode(ctx.map_grad_mode)
-        eng.backward_maps(grad_out.contiguous(), flat, dfeat, stream, ctx.masks)
+        need_k2d, need_ref = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        dk2d = dkcrop = None
+        if need_k2d or need_ref:
+            dk2d = torch.empty_like(ctx.keep[0]) if need_k2d else None
+            dref = torch.empty_like(ctx.keep[1]) if need_ref else None
+            eng.backward_points(grad_out.contiguous(), flat, stream, ctx.masks, dfeat, dk2d, dref)
+            dkcrop = _crop_grad(ctx.owner, dref) if need_ref else None
+        else:
+            eng.backward_maps(grad_out.contiguous(), flat, dfeat, stream, ctx.masks)
         ctx.owner.last_flat_grad = flat
+        head = (None, None, dk2d, dkcrop, None, None, None)
         dmaps = tuple(g if need else None for g, need in zip(dfeat, ctx.needs_input_grad[7:7 + ctx.n_maps]))
         if ctx.owner.flat_grad_only:      # the caller consumes last_flat_grad itself (capf.optim.FusedAdamW + capf.dist)
-            return (None,) * 7 + dmaps + (None,) * len(ctx.names)
+            return head + dmaps + (None,) * len(ctx.names)
         grads = tuple(flat[layout[n][0]: layout[n][0] + layout[n][1]].view(shp) for n, shp in zip(ctx.names, ctx.shapes))
-        return (None,) * 7 + dmaps + grads
+        return head + dmaps + grads
 
 
 class CA_PF(nn.Module):
@@ -277,8 +314,47 @@ class CA_PF(nn.Module):
             eng._bn_stale = False
         return eng
 
+    # ---- keypoints that take part in the graph ---------------------------------------------------
+    def _keypoint_grads(self, keypoints_2d_cpn, keypoints_2d_cpn_crop):
+        """True when this call must return gradients w.r.t. a keypoint tensor (grad mode on and one of them requires grad).  The native
+        backward has them on fp32 plans only: a 16-bit model refuses here instead of dropping them."""
+        need = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (keypoints_2d_cpn, keypoints_2d_cpn_crop))
+        if need and self.compute_dtype != "fp32":
+            raise NotImplementedError("gradients w.r.t. the keypoints need compute_dtype='fp32' (capf_backward_points); this model's "
+                                      "compute_dtype is {!r}: detach the keypoint tensors or build the model in fp32".format(self.compute_dtype))
+        return need
+
+    @staticmethod
+    def _crop_buffer(keypoints_2d_cpn_crop):
+        """(the tensor handed on as the third argument, whether the caller's tensor receives the normalised values).  A tensor that does
+        not require grad is normalised IN PLACE (conpose.py:34-35; a non-contiguous view through a contiguous staging copy that is
+        written back).  One that requires grad is never mutated -- the reference's in-place division would raise on such a leaf: the step
+        normalises a private contiguous copy (_private_ref; under no_grad the copy is made here)."""
+        t = keypoints_2d_cpn_crop
+        if t.requires_grad:
+            if not torch.is_grad_enabled():
+                return t.detach().clone(memory_format=torch.contiguous_format), False
+            return t.contiguous(), False
+        return (t if t.is_contiguous() else t.contiguous()), True
+
+    def _lifter_step_params(self, keypoint_grads):
+        """[(name, parameter)] of volume_net when this call runs the native training step (None: the plain forward): grad mode on and
+        either the lifter trains or a keypoint tensor needs its gradient (then with a frozen lifter: no parameter gradients)."""
+        if not torch.is_grad_enabled():
+            return None
+        named = [(n, p) for n, p in self.volume_net.named_parameters()]
+        if any(p.requires_grad for _, p in named):
+            if not all(p.requires_grad for _, p in named):
+                raise NotImplementedError("partially frozen volume_net is not supported by the native backward")
+            return named
+        return [] if keypoint_grads else None
+
     # ---- conpose.py:30-42 --------------------------------------------------------------------
     def forward(self, images, keypoints_2d_cpn, keypoints_2d_cpn_crop):
+        """conpose.py:30-42.  The third argument is normalised in place (conpose.py:34-35) unless it requires grad: then it is left
+        untouched, a private contiguous copy is normalised, and its .grad is w.r.t. the pixel values passed.  With grad enabled,
+        gradients reach volume_net's parameters and any keypoint tensor that requires grad (fp32 models; 16-bit: NotImplementedError)."""
+        kp_grads = self._keypoint_grads(keypoints_2d_cpn, keypoints_2d_cpn_crop)
         if images.dtype != torch.float32:
             raise TypeError("images must be float32")
         if images.device.type != "cuda":
@@ -297,12 +373,10 @@ class CA_PF(nn.Module):
             k2d = keypoints_2d_cpn.contiguous()
             # the third argument is normalised IN PLACE (conpose.py:34-35); a non-contiguous view (which the reference
             # accepts) goes through a contiguous staging copy that is written back
-            kcrop = keypoints_2d_cpn_crop if keypoints_2d_cpn_crop.is_contiguous() else keypoints_2d_cpn_crop.contiguous()
+            kcrop, write_back = self._crop_buffer(keypoints_2d_cpn_crop)
             stream = torch.cuda.current_stream(images.device).cuda_stream
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self.volume_net.parameters()):
-                named = [(n, p) for n, p in self.volume_net.named_parameters()]
-                if not all(p.requires_grad for _, p in named):
-                    raise NotImplementedError("partially frozen volume_net is not supported by the native backward")
+            named = self._lifter_step_params(kp_grads)
+            if named is not None:
                 names = tuple("volume_net." + n for n, _ in named)
                 out = _LifterStep.apply(self, eng, images, k2d, kcrop, self._drop_masks(B, images.device),
                                         names, *[p for _, p in named])
@@ -313,7 +387,7 @@ class CA_PF(nn.Module):
                     eng.lifter_forward(k2d, kcrop, out, stream)
                 else:
                     eng.forward(images, k2d, kcrop, out, stream)
-            if kcrop is not keypoints_2d_cpn_crop:
+            if write_back and kcrop is not keypoints_2d_cpn_crop:
                 with torch.no_grad():
                     keypoints_2d_cpn_crop.copy_(kcrop)
         return out
@@ -331,6 +405,7 @@ class CA_PF(nn.Module):
         if not isinstance(mirror, str) or mirror not in MIRROR_MODES:
             raise ValueError("mirror must be 'none', 'all' or 'pair', got {!r}".format(mirror))
         mode = MIRROR_MODES[mirror]
+        kp_grads = self._keypoint_grads(keypoints_2d_cpn, keypoints_2d_cpn_crop)
         if self._bn_batch_active():
             raise NotImplementedError("forward_u8 has no batch-statistics route (backbone_bn='batch' with the backbone in train mode): "
                                       "call backbone.eval(), or forward() on capf.lib.preprocess()'s fp32 images")
@@ -357,19 +432,17 @@ class CA_PF(nn.Module):
         with torch.cuda.device(dev):
             eng = self._engine_at(dev, H, W)
             k2d = keypoints_2d_cpn.contiguous()
-            kcrop = keypoints_2d_cpn_crop if keypoints_2d_cpn_crop.is_contiguous() else keypoints_2d_cpn_crop.contiguous()
+            kcrop, write_back = self._crop_buffer(keypoints_2d_cpn_crop)
             stream = torch.cuda.current_stream(dev).cuda_stream
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self.volume_net.parameters()):
-                named = [(n, p) for n, p in self.volume_net.named_parameters()]
-                if not all(p.requires_grad for _, p in named):
-                    raise NotImplementedError("partially frozen volume_net is not supported by the native backward")
+            named = self._lifter_step_params(kp_grads)
+            if named is not None:
                 names = tuple("volume_net." + n for n, _ in named)
                 out = _LifterStep.apply(self, eng, _U8Images(images_u8, mean, std, mode), k2d, kcrop, self._drop_masks(B, dev),
                                         names, *[p for _, p in named])
             else:
                 out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=dev)
                 eng.forward_u8(images_u8, mean, std, mode, k2d, kcrop, out, stream)
-            if kcrop is not keypoints_2d_cpn_crop:
+            if write_back and kcrop is not keypoints_2d_cpn_crop:
                 with torch.no_grad():
                     keypoints_2d_cpn_crop.copy_(kcrop)
         return out
@@ -393,8 +466,11 @@ class CA_PF(nn.Module):
         is not run.  self.map_grad_mode picks how the map gradients are summed: "atomic" -- fp32 atomic adds, equal up to fp32 summation
         order from run to run; "ordered" -- one fixed expression (include/capf.h, capf_set_map_grad_mode), bit-identical from run to
         run; None (default) -- ordered under torch.use_deterministic_algorithms(True), otherwise atomic.  Anything else: ValueError.
-        The parameter gradients have the same bits in both."""
+        The parameter gradients have the same bits in both.  A keypoint tensor that requires grad receives its gradient too
+        (capf_backward_points: a keypoint head on the same backbone trains through the lifter); the third argument is then NOT
+        mutated -- a private contiguous copy is normalised -- and its gradient is w.r.t. the pixel values passed."""
         resolve_map_grad_mode(self.map_grad_mode)
+        kp_grads = self._keypoint_grads(keypoints_2d_cpn, keypoints_2d_cpn_crop)
         feats = list(features_list)
         if len(feats) != 4:
             raise ValueError("features_list must hold 4 context maps, got {}".format(len(feats)))
@@ -430,12 +506,12 @@ class CA_PF(nn.Module):
         with torch.cuda.device(dev):
             eng = self._engine_at(dev, H, W)
             k2d = keypoints_2d_cpn.contiguous()
-            kcrop = keypoints_2d_cpn_crop if keypoints_2d_cpn_crop.is_contiguous() else keypoints_2d_cpn_crop.contiguous()
+            kcrop, write_back = self._crop_buffer(keypoints_2d_cpn_crop)
             stream = torch.cuda.current_stream(dev).cuda_stream
             nhwc = [f.permute(0, 2, 3, 1).contiguous() for f in feats]
             named = [(n, p) for n, p in self.volume_net.named_parameters()]
             train_lifter = any(p.requires_grad for _, p in named)
-            if torch.is_grad_enabled() and (train_lifter or any(f.requires_grad for f in feats)):
+            if torch.is_grad_enabled() and (train_lifter or kp_grads or any(f.requires_grad for f in feats)):
                 if train_lifter and not all(p.requires_grad for _, p in named):
                     raise NotImplementedError("partially frozen volume_net is not supported by the native backward")
                 if not train_lifter:
@@ -446,7 +522,7 @@ class CA_PF(nn.Module):
                 out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=dev)
                 eng.set_features(nhwc, stream)
                 eng.lifter_forward(k2d, kcrop, out, stream)
-            if kcrop is not keypoints_2d_cpn_crop:
+            if write_back and kcrop is not keypoints_2d_cpn_crop:
                 with torch.no_grad():
                     keypoints_2d_cpn_crop.copy_(kcrop)
         return out

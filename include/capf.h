@@ -365,6 +365,39 @@ int capf_backward_maps(capf_handle* h, void* stream, const float* grad_out, int 
 int capf_set_map_grad_mode(capf_handle* h, int mode);
 int capf_map_grad_mode(const capf_handle* h);
 
+/* ---- gradients w.r.t. the keypoints ---------------------------------------------------------------------------------------------------
+ * PoseTransformer.forward is differentiable in its two keypoint inputs as well: coord_embed(keypoints_2d) (pose_dformer.py:214),
+ * grid_sample(features, ref) (:217) and pos = offsets + ref in every DeformableBlock (:125).  A model whose keypoints come out of a
+ * trainable network (a soft-argmax head on the backbone that capf_set_features serves) needs them.
+ * capf_backward_points: capf_backward -- flat_grad gets the same bits -- plus up to three optional outputs, each NULL or caller-owned:
+ *     dfeat_nhwc  NULL, or the four maps of capf_backward_maps, with its bits (exactly in map_grad_mode 1, the same sums in mode 0);
+ *     dk2d        [batch, joints, 2] fp32: dL/d(k2d) = dL/dX[b, p, 0, :] coord_embed.weight, overwritten;
+ *     dref        [batch, joints, 2] fp32: dL/d(ref), the gradient w.r.t. the NORMALISED reference points, i.e. the values kcrop_inout
+ *                 holds after the forward; overwritten.  The caller who wants the gradient w.r.t. the crop pixels it passed divides by
+ *                 (96, 128), the constants of conpose.py:34 (CA_PF does).
+ *     With all three NULL the call is capf_backward, launch for launch.  Valid after capf_forward_train / capf_forward_train_u8 /
+ *     capf_lifter_forward_train under capf_backward's rules (generation, CAPF_ERR_STATE, batch); NULL grad_out / flat_grad, a NULL
+ *     among the four dfeat_nhwc pointers or a misaligned one: CAPF_ERR_INVALID.  fp32 plans only: CAPF_ERR_UNSUPPORTED on a bf16 / fp16
+ *     handle (capf_last_error names the entry and the dtype).  No extra workspace; second derivatives are not provided.
+ *     dref is ONE fixed fp32 expression, bit-identical from run to run and from handle to handle on the same inputs (no atomics):
+ *         dref = ((((0 + c[levels-1]) + c[levels-2]) + ...) + c[0]) + r_ref              (without context blocks: dref = 0 + r_ref)
+ *     c[i][b, p]: context block i's samplers, a running sum from 0 over level l ascending and, inside a level, k = head * samples + sample
+ *         ascending of dL/dpos[l][k] = softmax weight * (size_l - 1) / 2 * [coordinate not clipped by the border] * sum_c dL/dU * dv/dpos
+ *         (ATen's clip_coordinates_set_grad mask; the blocks in the order the backward visits them);
+ *     r_ref[b, p] = ((g_0 + g_1) + g_2) + g_3, g_l = (size_l - 1) / 2 * sum_c dL/dS_l[c] * d(bilinear, zeros padding)/d(ref): a corner
+ *         outside the map reads 0, no clip mask; a point wholly outside a map, or a 1 x 1 map, contributes exactly 0.
+ *     dk2d is a fixed expression too (lane i of 64 sums channels i, i + 64, ... ascending, then an xor tree).
+ *     grid_sample's derivative w.r.t. a position is one-sided at cell boundaries and at the border clip: dref is the derivative in the
+ *     cells and on the clip sides the forward used.
+ *     Cost (MI355X, HRNet-32 fp32 256 x 256, medians of 20, tools/bench_points_grad.py, EXPERIMENTS.md R23.1): with all three outputs
+ *     3.929 ms against capf_backward_maps' 3.910 ms at batch 64 and 12.260 against 11.986 ms at batch 512 (atomic mode; ordered: 3.568
+ *     against 3.542 and 10.323 against 10.024); with dk2d and dref alone 3.188 ms against capf_backward's 3.137 ms at batch 64 and 8.589
+ *     against 8.282 ms at batch 512 (feat_embed's input gradient, one small launch, a block barrier in four launches).  capf_backward
+ *     itself, this revision against the one before it in alternating processes of one session: 3.127 - 3.133 against 3.136 - 3.151 ms at
+ *     batch 64, 8.716 - 8.747 against 8.759 - 8.764 ms at batch 512 (spread of a series 1.3 - 2.1 %): unchanged. */
+int capf_backward_points(capf_handle* h, void* stream, const float* grad_out, int batch, float* flat_grad, const float* drop_masks,
+                         float* const dfeat_nhwc[4], float* dk2d, float* dref);
+
 /* How the independent branches of the backbone (the 2-4 resolution branches of an HRNet module, the
  * fused outputs, the CPN refine cascades) are issued:
  *   0 = everything in program order on the caller's stream;
