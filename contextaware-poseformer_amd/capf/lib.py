@@ -41,6 +41,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_op_conv_u8", "capf_op_conv_u8_kernel_name", "capf_op_conv_stem_kernel_name",
     "capf_backbone_forward_bn", "capf_op_bn_stats_scratch_bytes", "capf_op_bn_stats", "capf_op_bn_apply",
     "capf_backward_points",
+    "capf_kp_head_scratch_bytes", "capf_kp_head_forward", "capf_kp_head_backward",
 ]
 
 
@@ -249,6 +250,10 @@ def load_library():
     lib.capf_op_conv_u8_kernel_name.restype = c_char_p
     lib.capf_op_conv_stem_kernel_name.argtypes = [c_int] * 7
     lib.capf_op_conv_stem_kernel_name.restype = c_char_p
+    lib.capf_kp_head_scratch_bytes.argtypes = [c_int] * 6
+    lib.capf_kp_head_scratch_bytes.restype = c_size_t
+    lib.capf_kp_head_forward.argtypes = [P, P, c_int, P, P] + [c_int] * 6 + [c_float, F3, P, P, P, P, P, P, c_size_t]
+    lib.capf_kp_head_backward.argtypes = [P, P, P, P, c_int, P, P] + [c_int] * 6 + [c_float, F3, P, P, P, P, c_int, P, c_size_t]
     _lib = lib
     return lib
 
@@ -499,6 +504,24 @@ class Engine:
         if rc == 1:
             flat = flat.view(torch.int32)
         return flat.view(*shp).clone()
+
+    def tensor_view(self, name, batch):
+        """A named intermediate of the last forward of `batch` frames as a VIEW into the workspace (no copy; fp32 / bf16 / fp16 names only):
+        valid until the next run on this handle overwrites it.  The keypoint head reads feat0 through it."""
+        ptr, shape, nd = c_void_p(), (c_int64 * 4)(), c_int()
+        rc = self._check(self.lib.capf_tensor(self.h, name.encode(), byref(ptr), shape, byref(nd)), f"tensor({name})")
+        if rc == 1:
+            raise CapfError(f"tensor_view({name}): an int32 tensor has no floating-point view")
+        shp = [shape[i] for i in range(nd.value)]
+        if shp[0] != batch:
+            raise CapfError(f"tensor_view({name}): the workspace holds {shp[0]} frames, not {batch}")
+        n = 1
+        for s in shp:
+            n *= s
+        off = (ptr.value - self._ws.data_ptr()) // 4
+        if rc in (2, 3):
+            return self._ws[off:off + (n + 1) // 2].view(_TORCH16[rc]())[:n].view(*shp)
+        return self._ws[off:off + n].view(*shp)
 
     def op_table(self, batch):
         """[(op name, kernel name, algorithmic flops at `batch`)] in launch order."""
@@ -1039,6 +1062,75 @@ def bn_apply(x, scale, shift, residual=None, relu=False, out=None):
     return y
 
 
+KP_ARGMAX, KP_INTEGRAL = 0, 1     # capf_kp_head_forward's `mode`
+KP_MODES = {"argmax": KP_ARGMAX, "integral": KP_INTEGRAL}
+
+
+def _kp_map_dtype(x):
+    """capf_dtype of a map tensor (fp32 / bf16 / fp16); anything else is refused here, not converted"""
+    import torch
+    code = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}.get(x.dtype)
+    if code is None or x.dim() != 4 or not x.is_contiguous():
+        raise CapfError(f"the keypoint head takes a contiguous NHWC map [B, H, W, C] of fp32 / bf16 / fp16, not {tuple(x.shape)} {x.dtype}")
+    return code
+
+
+def _kp_common(x, weight, decode, to_image, backward):
+    import torch
+    B, H, W, C = x.shape
+    w = weight.reshape(weight.shape[0], -1)
+    if w.shape[1] != C or w.dtype != torch.float32 or not w.is_contiguous():
+        raise CapfError(f"the keypoint head's weight must be contiguous fp32 [J, {C}] (or [J, {C}, 1, 1]), not {tuple(weight.shape)} {weight.dtype}")
+    J = w.shape[0]
+    if to_image is not None and (tuple(to_image.shape) != (B, 2, 3) or to_image.dtype != torch.float32 or not to_image.is_contiguous()):
+        raise CapfError(f"to_image must be contiguous fp32 [{B}, 2, 3], not {tuple(to_image.shape)} {to_image.dtype}")
+    nbytes = load_library().capf_kp_head_scratch_bytes(B, H, W, C, J, 1 if backward else 0)
+    scratch = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
+    return (B, H, W, C, J), w, (c_float * 4)(*[float(v) for v in decode]), scratch, nbytes
+
+
+def kp_head_forward(x, weight, bias=None, mode=KP_ARGMAX, beta=1.0, decode=(1.0, 0.0, 1.0, 0.0), to_image=None, want_score=True,
+                    want_heat=False):
+    """capf_kp_head_forward on a contiguous NHWC map x [B, H, W, C] (fp32 / bf16 / fp16): the 1x1 conv weight [J, C] (+ bias [J]) and the
+    heatmap decode (mode KP_ARGMAX / KP_INTEGRAL with `beta`) in one pass.  decode = (sx, ox, sy, oy) maps heatmap to crop coordinates;
+    to_image [B, 2, 3] fp32 (crop_to_image_matrix) maps those to the lifter's normalised image coordinates.
+    Returns (kcrop [B, J, 2], score [B, J] | None, k2d [B, J, 2] | None, heat [B, J, H, W] | None)."""
+    import torch
+    dtype = _kp_map_dtype(x)
+    (B, H, W, C, J), w, dec, scratch, nbytes = _kp_common(x, weight, decode, to_image, False)
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x.device)
+    kcrop = new(B, J, 2)
+    k2d = new(B, J, 2) if to_image is not None else None
+    score = new(B, J) if want_score else None
+    heat = new(B, J, H, W) if want_heat else None
+    _call("capf_kp_head_forward", _stream(x), _p(x), dtype, _p(w), _p(bias), B, H, W, C, J, int(mode), float(beta), dec, _p(to_image),
+          _p(kcrop), _p(k2d), _p(score), _p(heat), _p(scratch), nbytes)
+    return kcrop, score, k2d, heat
+
+
+def kp_head_backward(x, weight, bias=None, dkcrop=None, dk2d=None, beta=1.0, decode=(1.0, 0.0, 1.0, 0.0), to_image=None, want_dmap=False,
+                     dmap=None):
+    """capf_kp_head_backward (integral decode, fp32 map): gradients of sum(dkcrop * kcrop) + sum(dk2d * k2d).  Returns (dweight [J, C],
+    dbias [J] -- exact zeros --, dmap | None).  dmap given: the map gradient is ADDED to it (capf_backward_points' dfeat_nhwc[0]);
+    want_dmap without dmap: a fresh tensor, overwritten."""
+    import torch
+    dtype = _kp_map_dtype(x)
+    (B, H, W, C, J), w, dec, scratch, nbytes = _kp_common(x, weight, decode, to_image, True)
+    for name, g in (("dkcrop", dkcrop), ("dk2d", dk2d)):
+        if g is not None and (tuple(g.shape) != (B, J, 2) or g.dtype != torch.float32 or not g.is_contiguous()):
+            raise CapfError(f"{name} must be contiguous fp32 [{B}, {J}, 2], not {tuple(g.shape)} {g.dtype}")
+    accumulate = dmap is not None
+    if accumulate and (dmap.shape != x.shape or dmap.dtype != torch.float32 or not dmap.is_contiguous()):
+        raise CapfError(f"dmap must be contiguous fp32 {tuple(x.shape)}, not {tuple(dmap.shape)} {dmap.dtype}")
+    if dmap is None and want_dmap:
+        dmap = torch.empty(B, H, W, C, dtype=torch.float32, device=x.device)
+    dw = torch.empty(J, C, dtype=torch.float32, device=x.device)
+    db = torch.empty(J, dtype=torch.float32, device=x.device)
+    _call("capf_kp_head_backward", _stream(x), _p(dkcrop), _p(dk2d), _p(x), dtype, _p(w), _p(bias), B, H, W, C, J, KP_INTEGRAL, float(beta),
+          dec, _p(to_image), _p(dw), _p(db), _p(dmap), 1 if accumulate else 0, _p(scratch), nbytes)
+    return dw, db, dmap
+
+
 def linear_bf16(x, w, bias=None, residual=None, gelu=False):
     """x bf16 [M,K], w bf16 [N,K] -> fp32 [M,N] (+ fp32 residual), or with gelu=True -> bf16 GELU(x w^T + b)."""
     import torch
@@ -1178,6 +1270,19 @@ def affine_from_center_scale(center, scale, output_size):
     if rc:
         raise CapfError(f"capf_affine_from_center_scale failed ({rc})")
     return np.array(list(m), dtype=np.float64).reshape(2, 3)
+
+
+def crop_to_image_matrix(center, scale, output_size, res_w, res_h):
+    """The 2x3 float64 matrix that takes crop pixel coordinates (x, y, 1) of the crop affine_from_center_scale(center, scale, output_size)
+    cuts to the lifter's normalised image coordinates: the inverse of that affine followed by normalize_screen_coordinates
+    (common/camera.py:14-18: X / w * 2 - [1, h / w]) for an image of res_w x res_h pixels.  Host code; one row of kp_head_forward's to_image."""
+    import numpy as np
+    m = np.vstack([affine_from_center_scale(center, scale, output_size), [0.0, 0.0, 1.0]])
+    inv = np.linalg.inv(m)[:2]
+    a = inv * (2.0 / float(res_w))
+    a[0, 2] -= 1.0
+    a[1, 2] -= float(res_h) / float(res_w)
+    return a
 
 
 def warp_affine(frames, mats, output_size):

@@ -1668,6 +1668,54 @@ int capf_keypoints_loss(void* stream, int mode, const float* pred, const float* 
                                        static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
+// ---- the 2-D keypoint head (kp_head.hip): every argument is judged here, before anything is launched ----
+size_t capf_kp_head_scratch_bytes(int B, int H, int W, int C, int J, int backward) {
+    const capf::KpGeom g = capf::kp_geom(B, H, W, C, J);
+    if (!g.ok) return 0;
+    return (g.fwd_elems + (backward ? g.stat_elems + g.bw_elems : 0)) * sizeof(float);
+}
+
+static int kp_head_check(const void* map, int map_dtype, const float* weight, int B, int H, int W, int C, int J, int mode, float beta,
+                         const float* decode, const void* scratch, size_t scratch_bytes, int backward) {
+    if (!map || !weight || !decode || !scratch) return CAPF_ERR_INVALID;
+    if (B < 1 || H < 1 || W < 1 || J < 1 || J > capf::KP_MAX_JOINTS || C < 4 || C % 4 != 0 || C > capf::KP_MAX_CHANNELS) return CAPF_ERR_INVALID;
+    if (!(beta > 0.f) || !std::isfinite(beta)) return CAPF_ERR_INVALID;
+    if ((mode != 0 && mode != 1) || map_dtype < CAPF_F32 || map_dtype > CAPF_F16) return CAPF_ERR_INVALID;
+    if (backward && (mode != 1 || map_dtype != CAPF_F32)) return CAPF_ERR_UNSUPPORTED;
+    const size_t need = capf_kp_head_scratch_bytes(B, H, W, C, J, backward);
+    if (need == 0) return CAPF_ERR_UNSUPPORTED;                                             // (more than 2^24 pixels a frame, a grid beyond 2^31)
+    if (scratch_bytes < need) return CAPF_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(map) & (map_dtype == CAPF_F32 ? 15 : 7)) || (reinterpret_cast<uintptr_t>(scratch) & 3)) return CAPF_ERR_INVALID;
+    return CAPF_OK;
+}
+
+int capf_kp_head_forward(void* stream, const void* map_nhwc, int map_dtype, const float* weight, const float* bias, int B, int H, int W, int C,
+                         int J, int mode, float beta, const float decode[4], const float* to_image, float* kcrop, float* k2d, float* score,
+                         float* heat, void* scratch, size_t scratch_bytes) {
+    if (!kcrop) return CAPF_ERR_INVALID;
+    if (const int rc = kp_head_check(map_nhwc, map_dtype, weight, B, H, W, C, J, mode, beta, decode, scratch, scratch_bytes, 0)) return rc;
+    capf::KpHeadArgs a{};
+    a.x = map_nhwc; a.dtype = map_dtype; a.wt = weight; a.bias = bias; a.to_image = to_image;
+    a.kcrop = kcrop; a.k2d = to_image ? k2d : nullptr; a.score = score; a.heat = heat; a.part = static_cast<float*>(scratch);
+    a.B = B; a.H = H; a.W = W; a.C = C; a.J = J; a.mode = mode; a.beta = beta;
+    for (int i = 0; i < 4; ++i) a.dec[i] = decode[i];
+    return capf::launch_kp_head_forward(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+}
+
+int capf_kp_head_backward(void* stream, const float* dkcrop, const float* dk2d, const void* map_nhwc, int map_dtype, const float* weight,
+                          const float* bias, int B, int H, int W, int C, int J, int mode, float beta, const float decode[4],
+                          const float* to_image, float* dweight, float* dbias, float* dmap, int accumulate, void* scratch, size_t scratch_bytes) {
+    if (!dweight || !dbias || (!dkcrop && !dk2d) || (dk2d && !to_image) || (accumulate != 0 && accumulate != 1)) return CAPF_ERR_INVALID;
+    if (const int rc = kp_head_check(map_nhwc, map_dtype, weight, B, H, W, C, J, mode, beta, decode, scratch, scratch_bytes, 1)) return rc;
+    if (reinterpret_cast<uintptr_t>(dmap) & 15) return CAPF_ERR_INVALID;
+    capf::KpHeadArgs a{};
+    a.x = map_nhwc; a.dtype = map_dtype; a.wt = weight; a.bias = bias; a.to_image = to_image; a.part = static_cast<float*>(scratch);
+    a.B = B; a.H = H; a.W = W; a.C = C; a.J = J; a.mode = mode; a.beta = beta;
+    for (int i = 0; i < 4; ++i) a.dec[i] = decode[i];
+    a.dkcrop = dkcrop; a.dk2d = dk2d; a.dW = dweight; a.dbias = dbias; a.dmap = dmap; a.accumulate = accumulate;
+    return capf::launch_kp_head_backward(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+}
+
 int capf_num_ops(const capf_handle* h) { return h ? (int)h->e.ops.size() : CAPF_ERR_INVALID; }
 
 int capf_op_info(const capf_handle* h, int index, int batch, const char** name, const char** kernel, double* flops) {

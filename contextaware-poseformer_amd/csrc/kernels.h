@@ -735,4 +735,44 @@ hipError_t launch_pck_counts(const float* pred, const float* gt, int n, int J, i
 hipError_t launch_keypoints_loss(const float* pred, const float* gt, const float* validity, int rows, int D, int mode, float thr,
                                  float* loss, float* dpred, hipStream_t s);
 
+// ---- 2-D keypoint head (kp_head.hip): final_layer (1x1 conv) on feat0 + heatmap decode, one pass over the map ------------------------
+constexpr int KP_MAX_JOINTS = 32;
+constexpr int KP_MAX_CHANNELS = 512;
+constexpr int KP_MAX_SLABS = 64;             // forward: slabs of 256-pixel tiles per frame (a function of H * W alone)
+constexpr int KP_BW_SLABS = 8;               // backward: blocks per frame, each leaves one partial of dW
+struct KpGeom {                              // kp_geom: how a shape is cut; ok = false: a shape the kernels do not take
+    int ntiles, slab_tiles, nslab, bw_tiles, nbw;
+    size_t fwd_elems, stat_elems, bw_elems;  // floats of scratch: slab records | (max, sum, x, y) per (frame, joint) | dW partials
+    bool ok;
+};
+KpGeom kp_geom(int B, int H, int W, int C, int J);
+struct KpHeadArgs {
+    const void* x;           // [B, H, W, C] NHWC, dtype 0 fp32 / 1 bf16 / 2 fp16 (capf_dtype)
+    int dtype;
+    const float* wt;         // [J, C]
+    const float* bias;       // [J] or NULL
+    const float* to_image;   // [B, 2, 3] or NULL
+    float* kcrop;            // [B, J, 2]
+    float* k2d;              // [B, J, 2] or NULL
+    float* score;            // [B, J] or NULL
+    float* heat;             // [B, J, H, W] or NULL
+    float* part;             // scratch (fwd_elems floats; the backward: + stat_elems + bw_elems)
+    int B, H, W, C, J, mode; // mode 0 argmax, 1 integral
+    float beta;
+    float dec[4];            // sx, ox, sy, oy
+    // backward (mode 1, fp32 map)
+    const float* dkcrop;     // [B, J, 2] or NULL
+    const float* dk2d;       // [B, J, 2] or NULL (needs to_image)
+    float* dW;               // [J, C]
+    float* dbias;            // [J] or NULL: zeros
+    float* dmap;             // [B, H, W, C] or NULL
+    int accumulate;
+    // filled by the launchers
+    KpGeom g;
+    float* stats;
+    float* bw_part;
+};
+hipError_t launch_kp_head_forward(KpHeadArgs a, hipStream_t s);
+hipError_t launch_kp_head_backward(KpHeadArgs a, hipStream_t s);
+
 }  // namespace capf

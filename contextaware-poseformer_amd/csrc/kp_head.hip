@@ -1,0 +1,378 @@
+// 2-D keypoint head on the highest-resolution context map (gfx950): HRNet's final_layer (a 1x1 conv, pose_hrnet.py:497-501) and the decode
+// of its heatmaps in one pass over the map, plus the backward of the integral decode.  include/capf.h (capf_kp_head_forward) has the rules.
+//
+// Map X [B, H, W, C] NHWC (fp32 / bf16 / fp16, widened on load), Wt [J, C] fp32, bias [J] fp32 or NULL; J <= 32, C % 4 == 0, C <= 512.
+// A logit is ONE fp32 expression, plain FMAs on the vector pipe (no matrix pipe: block scales shared across pixels would tie a frame's argmax
+// to its neighbours in the batch):
+//     z = bias[j];  for c = 0 .. C-1 ascending:  z = fmaf(X[b, y, x, c], Wt[j, c], z)
+// kp_logits (all joints of a pixel) and kp_logit1 (one joint, the argmax's four neighbours) are that chain, so they agree bit for bit.
+//
+// Forward, two launches, no atomics, no hand-off between blocks inside a launch:
+//   slab     a block owns one frame's slab of `slab_tiles` consecutive 256-pixel tiles (row-major pixel index; the tiling depends on H * W
+//            alone, never on the batch).  Per tile: thread t computes the J logits of pixel t into LDS (and into `heat` when asked); then 8 lanes
+//            per joint walk the tile, lane l taking pixels l, l + 8, ... ascending, and keep the running best (argmax) or the online
+//            max / sum / sum * col / sum * row of exp(beta z - max) (integral).  The 8 lanes are combined in ascending l; one record per
+//            (frame, slab, joint) goes to the scratch.  The heatmaps never reach memory.
+//   combine  one thread per (frame, joint) folds the slabs in ascending order, decodes, and writes kcrop / k2d / score.  The argmax's quarter
+//            shift recomputes the winner's four neighbours from the map (4 C values per joint; the only second read).
+// Backward (integral, fp32 map), four launches: slab + combine as above leave (max, sum, x, y) per (frame, joint) in the scratch; kp_bwd_kernel
+// recomputes the logits tile by tile, forms dz in LDS, writes dmap (every element by one thread) and adds per-block partials of dW = sum dz X
+// (pixels ascending inside a tile, tiles ascending inside a block); kp_dw_reduce_kernel sums the partials (part q of 16 takes blocks
+// q, q + 16, ... ascending, the parts ascending) and writes dbias = 0.
+#include <math.h>
+
+#include "kernels.h"
+
+namespace capf {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+static constexpr int KP_THREADS = 256;            // = pixels of a tile
+static constexpr int KP_ZS = KP_THREADS + 8;      // LDS pitch of a joint's tile of logits: the 8 joints x 8 lanes of a wave hit 64 banks
+static constexpr int KP_REC = 8;                  // floats per (frame, slab, joint) record: m, sum, sum_x, sum_y, zmax, nan, idx, -
+static constexpr int KP_RED_PARTS = 16;
+
+struct KpLdF32 {
+    typedef float T;
+    static __device__ __forceinline__ f32x4 ld4(const T* p) { return *reinterpret_cast<const f32x4*>(p); }
+};
+template <class F>
+struct KpLd16 {
+    typedef unsigned short T;
+    static __device__ __forceinline__ f32x4 ld4(const T* p) {
+        const uint2 u = *reinterpret_cast<const uint2*>(p);
+        return f32x4{F::lo(u.x), F::hi(u.x), F::lo(u.y), F::hi(u.y)};
+    }
+};
+
+KpGeom kp_geom(int B, int H, int W, int C, int J) {
+    KpGeom g{};
+    if (B < 1 || H < 1 || W < 1 || J < 1 || J > KP_MAX_JOINTS || C < 4 || C % 4 != 0 || C > KP_MAX_CHANNELS) return g;
+    const long HW = (long)H * W;
+    if (HW > (1L << 24)) return g;                                  // (a pixel index and its row / column are exact in fp32)
+    g.ntiles = (int)((HW + KP_THREADS - 1) / KP_THREADS);
+    g.slab_tiles = (g.ntiles + KP_MAX_SLABS - 1) / KP_MAX_SLABS;
+    g.nslab = (g.ntiles + g.slab_tiles - 1) / g.slab_tiles;
+    g.bw_tiles = (g.ntiles + KP_BW_SLABS - 1) / KP_BW_SLABS;
+    g.nbw = (g.ntiles + g.bw_tiles - 1) / g.bw_tiles;
+    if ((long)B * g.nslab >= (1L << 31) || (long)B * J >= (1L << 31)) return KpGeom{};      // (grid sizes; addresses are 64-bit)
+    g.fwd_elems = (size_t)B * g.nslab * J * KP_REC;
+    g.stat_elems = (size_t)B * J * 4;
+    g.bw_elems = (size_t)B * g.nbw * J * C;
+    g.ok = true;
+    return g;
+}
+
+// the J logits of one pixel: acc[j] = bias[j], then one fmaf per channel, ascending
+template <class L>
+__device__ __forceinline__ void kp_logits(const typename L::T* __restrict__ xp, const float* __restrict__ wt, const float* __restrict__ bias,
+                                          const int C, const int J, float (&acc)[KP_MAX_JOINTS]) {
+#pragma unroll
+    for (int j = 0; j < KP_MAX_JOINTS; ++j) acc[j] = bias ? bias[j < J ? j : J - 1] : 0.f;
+    for (int c = 0; c < C; c += 4) {                                // (loads grouped 16 channels ahead of their FMAs measured no faster: R24.1)
+        const f32x4 v = L::ld4(xp + c);
+#pragma unroll
+        for (int jg = 0; jg < KP_MAX_JOINTS / 4; ++jg) {
+            if (jg * 4 < J) {                                       // (uniform; the joints of a group beyond J compute a copy of joint J - 1)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    const int j = jg * 4 + jj;
+                    const float* __restrict__ w = wt + (size_t)(j < J ? j : J - 1) * C + c;
+                    float z = acc[j];
+                    z = fmaf(v[0], w[0], z);
+                    z = fmaf(v[1], w[1], z);
+                    z = fmaf(v[2], w[2], z);
+                    z = fmaf(v[3], w[3], z);
+                    acc[j] = z;
+                }
+            }
+        }
+    }
+}
+
+template <class L>
+__device__ __forceinline__ float kp_logit1(const typename L::T* __restrict__ xp, const float* __restrict__ w, const float b, const int C) {
+    float z = b;
+    for (int c = 0; c < C; c += 4) {
+        const f32x4 v = L::ld4(xp + c);
+        z = fmaf(v[0], w[c], z);
+        z = fmaf(v[1], w[c + 1], z);
+        z = fmaf(v[2], w[c + 2], z);
+        z = fmaf(v[3], w[c + 3], z);
+    }
+    return z;
+}
+
+struct KpRun {           // a lane's / slab's / frame's running decode state of one joint
+    float m, s, sx, sy;  // integral: max of beta z, sums of e = exp(beta z - m), e col, e row
+    float zm;            // max logit
+    int idx;             // argmax: where zm was first seen
+    int nan;
+};
+__device__ __forceinline__ KpRun kp_run_init() { return KpRun{-INFINITY, 0.f, 0.f, 0.f, -INFINITY, 0, 0}; }
+
+// `o` holds pixels that all come AFTER r's in row-major order, or (lanes of a tile) interleave with them: the index breaks a tie
+template <int MODE>
+__device__ __forceinline__ void kp_run_merge(KpRun& r, const KpRun& o) {
+    r.nan |= o.nan;
+    if (MODE == 0) {
+        if (o.zm > r.zm || (o.zm == r.zm && o.idx < r.idx)) { r.zm = o.zm; r.idx = o.idx; }
+    } else {
+        const float M = o.m > r.m ? o.m : r.m;
+        const float e1 = r.m == M ? 1.f : expf(r.m - M), e2 = o.m == M ? 1.f : expf(o.m - M);
+        r.s = r.s * e1 + o.s * e2;
+        r.sx = r.sx * e1 + o.sx * e2;
+        r.sy = r.sy * e1 + o.sy * e2;
+        r.m = M;
+        if (o.zm > r.zm) r.zm = o.zm;
+    }
+}
+
+template <class L, int MODE>
+__global__ void __launch_bounds__(KP_THREADS) kp_fwd_slab_kernel(const KpHeadArgs a) {
+    __shared__ float zs[KP_MAX_JOINTS * KP_ZS];
+    const int tid = threadIdx.x;
+    const int b = (int)blockIdx.x / a.g.nslab, s = (int)blockIdx.x - b * a.g.nslab;
+    const int HW = a.H * a.W, J = a.J;
+    const typename L::T* __restrict__ xb = static_cast<const typename L::T*>(a.x) + (size_t)b * HW * a.C;
+    const int jl = tid >> 3, l = tid & 7;
+    KpRun r = kp_run_init();
+    const int t0 = s * a.g.slab_tiles;
+    const int t1 = t0 + a.g.slab_tiles < a.g.ntiles ? t0 + a.g.slab_tiles : a.g.ntiles;
+    for (int t = t0; t < t1; ++t) {
+        const int pix = t * KP_THREADS + tid;
+        if (pix < HW) {
+            float acc[KP_MAX_JOINTS];
+            kp_logits<L>(xb + (size_t)pix * a.C, a.wt, a.bias, a.C, J, acc);
+#pragma unroll
+            for (int j = 0; j < KP_MAX_JOINTS; ++j) {
+                if (j < J) {
+                    zs[j * KP_ZS + tid] = acc[j];
+                    if (a.heat) a.heat[((size_t)b * J + j) * HW + pix] = acc[j];
+                }
+            }
+        }
+        __syncthreads();
+        if (jl < J) {
+            const int base = t * KP_THREADS;
+            const int n = HW - base < KP_THREADS ? HW - base : KP_THREADS;
+            for (int p = l; p < n; p += 8) {
+                const float z = zs[jl * KP_ZS + p];
+                const int pp = base + p;
+                if (z != z) r.nan = 1;
+                if (MODE == 0) {
+                    if (z > r.zm) { r.zm = z; r.idx = pp; }
+                } else {
+                    const int row = pp / a.W, col = pp - row * a.W;
+                    const float tz = a.beta * z;
+                    if (tz > r.m) {
+                        const float e = expf(r.m - tz);             // (first pixel: exp(-inf) = 0 on zero sums)
+                        r.s *= e; r.sx *= e; r.sy *= e;
+                        r.m = tz;
+                    }
+                    const float w = expf(tz - r.m);
+                    r.s += w;
+                    r.sx = fmaf(w, (float)col, r.sx);
+                    r.sy = fmaf(w, (float)row, r.sy);
+                    if (z > r.zm) r.zm = z;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // the 8 lanes of a joint, ascending (every thread takes part in the shuffles)
+    KpRun tot = r;
+    for (int q = 1; q < 8; ++q) {
+        KpRun o;
+        o.m = __shfl(r.m, q, 8); o.s = __shfl(r.s, q, 8); o.sx = __shfl(r.sx, q, 8); o.sy = __shfl(r.sy, q, 8);
+        o.zm = __shfl(r.zm, q, 8); o.idx = __shfl(r.idx, q, 8); o.nan = __shfl(r.nan, q, 8);
+        kp_run_merge<MODE>(tot, o);
+    }
+    if (l == 0 && jl < J) {
+        float* rec = a.part + ((size_t)blockIdx.x * J + jl) * KP_REC;
+        rec[0] = tot.m; rec[1] = tot.s; rec[2] = tot.sx; rec[3] = tot.sy;
+        rec[4] = tot.zm; rec[5] = tot.nan ? 1.f : 0.f; rec[6] = __int_as_float(tot.idx); rec[7] = 0.f;
+    }
+}
+
+template <class L, int MODE>
+__global__ void __launch_bounds__(KP_THREADS) kp_fwd_combine_kernel(const KpHeadArgs a) {
+    const int i = (int)blockIdx.x * KP_THREADS + threadIdx.x;
+    if (i >= a.B * a.J) return;
+    const int b = i / a.J, j = i - b * a.J, J = a.J, H = a.H, W = a.W;
+    KpRun r = kp_run_init();
+    r.idx = 0x7fffffff;
+    for (int s = 0; s < a.g.nslab; ++s) {                           // slabs ascending
+        const float* rec = a.part + (((size_t)b * a.g.nslab + s) * J + j) * KP_REC;
+        KpRun o{rec[0], rec[1], rec[2], rec[3], rec[4], __float_as_int(rec[6]), rec[5] != 0.f};
+        kp_run_merge<MODE>(r, o);
+    }
+    float x, y, score = r.zm;
+    if (MODE == 0) {
+        if (r.idx == 0x7fffffff) r.idx = 0;
+        const int py = r.idx / W, px = r.idx - py * W;
+        x = (float)px;
+        y = (float)py;
+        if (!r.nan && 1 < px && px < W - 1 && 1 < py && py < H - 1) {
+            const typename L::T* xp = static_cast<const typename L::T*>(a.x) + ((size_t)b * H * W + r.idx) * a.C;
+            const float* w = a.wt + (size_t)j * a.C;
+            const float bj = a.bias ? a.bias[j] : 0.f;
+            const float dx = kp_logit1<L>(xp + a.C, w, bj, a.C) - kp_logit1<L>(xp - a.C, w, bj, a.C);
+            const float dy = kp_logit1<L>(xp + (size_t)W * a.C, w, bj, a.C) - kp_logit1<L>(xp - (size_t)W * a.C, w, bj, a.C);
+            x += dx > 0.f ? 0.25f : dx < 0.f ? -0.25f : 0.f;
+            y += dy > 0.f ? 0.25f : dy < 0.f ? -0.25f : 0.f;
+        }
+        if (score <= 0.f) x = y = 0.f;
+    } else {
+        x = r.sx / r.s;
+        y = r.sy / r.s;
+    }
+    if (r.nan) x = y = score = __builtin_nanf("");
+    if (a.stats) {
+        float* st = a.stats + (size_t)i * 4;
+        st[0] = r.m; st[1] = r.s; st[2] = x; st[3] = y;
+    }
+    if (!a.kcrop) return;
+    const float kx = __fadd_rn(__fmul_rn(a.dec[0], x), a.dec[1]), ky = __fadd_rn(__fmul_rn(a.dec[2], y), a.dec[3]);
+    a.kcrop[(size_t)i * 2] = kx;
+    a.kcrop[(size_t)i * 2 + 1] = ky;
+    if (a.score) a.score[i] = score;
+    if (a.to_image && a.k2d) {
+        const float* A = a.to_image + (size_t)b * 6;
+        a.k2d[(size_t)i * 2] = __fadd_rn(__fadd_rn(__fmul_rn(A[0], kx), __fmul_rn(A[1], ky)), A[2]);
+        a.k2d[(size_t)i * 2 + 1] = __fadd_rn(__fadd_rn(__fmul_rn(A[3], kx), __fmul_rn(A[4], ky)), A[5]);
+    }
+}
+
+// ---- backward of the integral decode --------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(KP_THREADS) kp_bwd_kernel(const KpHeadArgs a) {
+    __shared__ float zs[KP_MAX_JOINTS * KP_ZS];
+    __shared__ float st[KP_MAX_JOINTS][6];                          // m, 1 / sum, x, y, gx, gy
+    const int tid = threadIdx.x;
+    const int b = (int)blockIdx.x / a.g.nbw, s = (int)blockIdx.x - b * a.g.nbw;
+    const int HW = a.H * a.W, J = a.J, C = a.C;
+    const float* __restrict__ xb = static_cast<const float*>(a.x) + (size_t)b * HW * C;
+    if (tid < J) {
+        const size_t i = (size_t)b * J + tid;
+        const float* sv = a.stats + i * 4;
+        float gx = a.dkcrop ? a.dkcrop[i * 2] : 0.f, gy = a.dkcrop ? a.dkcrop[i * 2 + 1] : 0.f;
+        if (a.dk2d) {                                               // g += A[:, :2]^T dk2d
+            const float* A = a.to_image + (size_t)b * 6;
+            const float d0 = a.dk2d[i * 2], d1 = a.dk2d[i * 2 + 1];
+            gx += A[0] * d0 + A[3] * d1;
+            gy += A[1] * d0 + A[4] * d1;
+        }
+        st[tid][0] = sv[0]; st[tid][1] = 1.f / sv[1]; st[tid][2] = sv[2]; st[tid][3] = sv[3];
+        st[tid][4] = gx * a.dec[0]; st[tid][5] = gy * a.dec[2];
+    }
+    __syncthreads();
+    float* part = a.bw_part + (size_t)blockIdx.x * J * C;
+    const int t0 = s * a.g.bw_tiles;
+    const int t1 = t0 + a.g.bw_tiles < a.g.ntiles ? t0 + a.g.bw_tiles : a.g.ntiles;
+    for (int t = t0; t < t1; ++t) {
+        const int base = t * KP_THREADS, pix = base + tid;
+        const int n = HW - base < KP_THREADS ? HW - base : KP_THREADS;
+        if (pix < HW) {
+            float acc[KP_MAX_JOINTS];
+            kp_logits<KpLdF32>(xb + (size_t)pix * C, a.wt, a.bias, C, J, acc);
+            const int row = pix / a.W, col = pix - row * a.W;
+#pragma unroll
+            for (int j = 0; j < KP_MAX_JOINTS; ++j) {
+                if (j < J) {
+                    const float p = expf(a.beta * acc[j] - st[j][0]) * st[j][1];
+                    const float dz = a.beta * p * (st[j][4] * ((float)col - st[j][2]) + st[j][5] * ((float)row - st[j][3]));
+                    acc[j] = dz;
+                    zs[j * KP_ZS + tid] = dz;
+                }
+            }
+            if (a.dmap) {                                           // dmap[pixel, c] = sum_j dz[j] Wt[j, c], joints ascending
+                float* dp = a.dmap + ((size_t)b * HW + pix) * C;
+                for (int c = 0; c < C; c += 4) {
+                    f32x4 d = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int j = 0; j < KP_MAX_JOINTS; ++j) {
+                        if (j < J) {
+                            const float* __restrict__ w = a.wt + (size_t)j * C + c;
+                            d[0] = fmaf(acc[j], w[0], d[0]);
+                            d[1] = fmaf(acc[j], w[1], d[1]);
+                            d[2] = fmaf(acc[j], w[2], d[2]);
+                            d[3] = fmaf(acc[j], w[3], d[3]);
+                        }
+                    }
+                    f32x4* q = reinterpret_cast<f32x4*>(dp + c);
+                    *q = a.accumulate ? *q + d : d;
+                }
+            }
+        }
+        __syncthreads();
+        for (int o = tid; o < J * C; o += KP_THREADS) {
+            const int j = o / C, c = o - j * C;
+            const float* __restrict__ xc = xb + (size_t)base * C + c;
+            const float* zj = zs + j * KP_ZS;
+            float sum = 0.f;
+#pragma unroll 8
+            for (int p = 0; p < n; ++p) sum = fmaf(zj[p], xc[(size_t)p * C], sum);
+            part[o] = t == t0 ? sum : part[o] + sum;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(KP_THREADS) kp_dw_reduce_kernel(const float* __restrict__ part, const int nparts, const int JC, const int J,
+                                                                  float* __restrict__ dW, float* __restrict__ dbias) {
+    __shared__ float sh[KP_RED_PARTS][16];
+    const int lc = threadIdx.x & 15, q = threadIdx.x >> 4;
+    const int o = (int)blockIdx.x * 16 + lc;
+    float s = 0.f;
+    if (o < JC)
+        for (int p = q; p < nparts; p += KP_RED_PARTS) s += part[(size_t)p * JC + o];
+    sh[q][lc] = s;
+    __syncthreads();
+    if (q == 0 && o < JC) {
+        s = 0.f;
+        for (int p = 0; p < KP_RED_PARTS; ++p) s += sh[p][lc];
+        dW[o] = s;
+    }
+    if (blockIdx.x == 0 && dbias && (int)threadIdx.x < J) dbias[threadIdx.x] = 0.f;     // softmax is shift-invariant: exactly zero
+}
+
+template <class L>
+static void kp_forward_launches(const KpHeadArgs& a, hipStream_t s) {
+    const dim3 g1((unsigned)(a.B * a.g.nslab)), g2((unsigned)((a.B * a.J + KP_THREADS - 1) / KP_THREADS));
+    if (a.mode == 0) {
+        hipLaunchKernelGGL((kp_fwd_slab_kernel<L, 0>), g1, dim3(KP_THREADS), 0, s, a);
+        hipLaunchKernelGGL((kp_fwd_combine_kernel<L, 0>), g2, dim3(KP_THREADS), 0, s, a);
+    } else {
+        hipLaunchKernelGGL((kp_fwd_slab_kernel<L, 1>), g1, dim3(KP_THREADS), 0, s, a);
+        hipLaunchKernelGGL((kp_fwd_combine_kernel<L, 1>), g2, dim3(KP_THREADS), 0, s, a);
+    }
+}
+
+static bool kp_args_ok(const KpHeadArgs& a) {
+    return a.g.ok && a.x && a.wt && a.part && (a.mode == 0 || a.mode == 1) && a.beta > 0.f && a.dtype >= 0 && a.dtype <= 2;
+}
+
+hipError_t launch_kp_head_forward(KpHeadArgs a, hipStream_t s) {
+    a.g = kp_geom(a.B, a.H, a.W, a.C, a.J);
+    if (!kp_args_ok(a) || !a.kcrop) return hipErrorInvalidValue;
+    a.stats = nullptr;
+    if (a.dtype == 0) kp_forward_launches<KpLdF32>(a, s);
+    else if (a.dtype == 1) kp_forward_launches<KpLd16<Bf16Fmt>>(a, s);
+    else kp_forward_launches<KpLd16<F16Fmt>>(a, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_kp_head_backward(KpHeadArgs a, hipStream_t s) {
+    a.g = kp_geom(a.B, a.H, a.W, a.C, a.J);
+    if (!kp_args_ok(a) || a.mode != 1 || a.dtype != 0 || !a.dW || (!a.dkcrop && !a.dk2d) || (a.dk2d && !a.to_image)) return hipErrorInvalidValue;
+    a.stats = a.part + a.g.fwd_elems;
+    a.bw_part = a.stats + a.g.stat_elems;
+    a.kcrop = a.k2d = a.score = a.heat = nullptr;
+    kp_forward_launches<KpLdF32>(a, s);
+    hipLaunchKernelGGL(kp_bwd_kernel, dim3((unsigned)(a.B * a.g.nbw)), dim3(KP_THREADS), 0, s, a);
+    const int JC = a.J * a.C;
+    hipLaunchKernelGGL(kp_dw_reduce_kernel, dim3((unsigned)((JC + 15) / 16)), dim3(KP_THREADS), 0, s, a.bw_part, a.B * a.g.nbw, JC, a.J, a.dW, a.dbias);
+    return hipGetLastError();
+}
+
+}  // namespace capf

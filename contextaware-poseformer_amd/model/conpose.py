@@ -7,7 +7,7 @@ from mvn.models.conpose import CA_PF
 
 
 class VolumetricTriangulationNet(CA_PF):
-    def __init__(self, config, device="cuda:0", compute_dtype="fp32", backbone_bn="running"):
+    def __init__(self, config, device="cuda:0", compute_dtype="fp32", backbone_bn="running", keypoint_head=None, keypoint_beta=1.0):
         # ContextPose_mpi/common/cfg.py has no backbone.type key: the width list names the backbone
         width = config.model.backbone.STAGE2.NUM_CHANNELS[0]
         if width not in (32, 48):
@@ -18,7 +18,9 @@ class VolumetricTriangulationNet(CA_PF):
         # from the same key (capf_config.depth, 1..8, inference and, at this app's two widths, training; the shipped configuration has 4 == 4).  Training
         # (run_3dhp.py:60-101) goes through CA_PF's native step: `out, _ = model(...)` backpropagates into volume_net.
         # backbone_bn="batch": the frozen backbone's BatchNorm follows backbone.training as in run_3dhp.py:31-35 (CA_PF.__init__)
-        super().__init__(config, device, compute_dtype=compute_dtype, context_blocks=False, backbone_bn=backbone_bn)
+        # keypoint_head / keypoint_beta: CA_PF's optional native 2-D keypoint head on feat0 (detect / forward_detect); None: today's module
+        super().__init__(config, device, compute_dtype=compute_dtype, context_blocks=False, backbone_bn=backbone_bn,
+                         keypoint_head=keypoint_head, keypoint_beta=keypoint_beta)
 
     def forward(self, images, keypoints_2d_cpn, keypoints_2d_cpn_crop):
         x = super().forward(images, keypoints_2d_cpn, keypoints_2d_cpn_crop)       # [B, 1, 17, 3]
@@ -31,6 +33,11 @@ class VolumetricTriangulationNet(CA_PF):
     def forward_features(self, features_list, keypoints_2d_cpn, keypoints_2d_cpn_crop):
         """CA_PF.forward_features in this variant's output layout: (x [B, 3, 1, 17, 1], None)."""
         return self._layout(super().forward_features(features_list, keypoints_2d_cpn, keypoints_2d_cpn_crop)), None
+
+    def forward_detect(self, images, to_image):
+        """CA_PF.forward_detect in this variant's output layout: (x [B, 3, 1, 17, 1], kcrop_px, score)."""
+        x, kcrop, score = super().forward_detect(images, to_image)
+        return self._layout(x), kcrop, score
 
     @staticmethod
     def _layout(x):

@@ -12,7 +12,7 @@ There is no eager / CPU fallback: CPU tensors or a missing libcapf.so raise.
 import torch
 from torch import nn
 
-from capf.lib import PLAN_BN_BATCH_STATS, CapfError, Engine
+from capf.lib import KP_INTEGRAL, KP_MODES, PLAN_BN_BATCH_STATS, CapfError, Engine, kp_head_backward, kp_head_forward
 
 from . import _native
 
@@ -25,6 +25,14 @@ class _U8Images:
         self.crops, self.mean, self.std, self.mode = crops, mean, std, mode
         self.device = crops.device
         self.shape = (crops.shape[0] * (2 if mode == 2 else 1),) + tuple(crops.shape[1:])
+
+
+class _WorkspaceMaps:
+    """The `images` argument of _LifterStep when the context maps are already in the workspace (CA_PF.forward_detect ran the backbone and
+    the keypoint head on them): the step is capf_lifter_forward_train alone."""
+
+    def __init__(self, batch, device):
+        self.shape, self.device = (batch,), device
 
 
 MIRROR_MODES = {"none": 0, "all": 1, "pair": 2}       # CA_PF.forward_u8's `mirror` -> capf_preprocess's mode
@@ -56,7 +64,9 @@ class _LifterStep(torch.autograd.Function):
         out = torch.empty(images.shape[0], 1, owner.num_joints, 3, dtype=torch.float32, device=images.device)
         stream = torch.cuda.current_stream(images.device).cuda_stream
         kcrop = _private_ref(ctx, 4, kcrop)
-        if isinstance(images, _U8Images):     # the uint8 route: the same step, the stem reads the crops (nothing in the backward reads the image)
+        if isinstance(images, _WorkspaceMaps):  # forward_detect: the backbone already ran; the maps of this batch are in the workspace
+            eng.lifter_forward_train(k2d, kcrop, out, stream, masks)
+        elif isinstance(images, _U8Images):   # the uint8 route: the same step, the stem reads the crops (nothing in the backward reads the image)
             eng.forward_train_u8(images.crops, images.mean, images.std, images.mode, k2d, kcrop, out, stream, masks)
         elif owner._bn_batch_active():        # backbone_bn="batch", backbone in train mode: batch statistics, then the same lifter step on its maps
             owner._backbone_forward_bn(eng, images, stream)
@@ -94,6 +104,68 @@ class _LifterStep(torch.autograd.Function):
             return head + (None,) * len(ctx.names)
         grads = tuple(flat[layout[n][0]: layout[n][0] + layout[n][1]].view(shp) for n, shp in zip(ctx.names, ctx.shapes))
         return head + grads
+
+
+class KeypointHead(nn.Module):
+    """HRNet's final_layer (nn.Conv2d(C0, num_joints, 1), pose_hrnet.py:497-501) as a parameter holder: a COCO checkpoint's
+    final_layer.weight / final_layer.bias load into it by name.  The module is never called -- the 1x1 conv and the heatmap decode are one
+    native pass over feat0 (capf_kp_head_forward); torch's default Conv2d initialisation serves a head trained from scratch (CPN)."""
+
+    def __init__(self, channels, num_joints):
+        super().__init__()
+        self.final_layer = nn.Conv2d(channels, num_joints, kernel_size=1, stride=1, padding=0)
+
+    def forward(self, *args):
+        raise CapfError("KeypointHead only holds final_layer's parameters: use CA_PF.detect / forward_detect or "
+                        "mvn.models.conpose.keypoint_head (there is no eager path)")
+
+
+class _KeypointHeadFn(torch.autograd.Function):
+    """Autograd boundary of the native keypoint head: forward = capf_kp_head_forward on an NHWC map, backward (integral decode, fp32 map) =
+    capf_kp_head_backward: gradients of final_layer's weight, an exactly zero bias gradient, and dL/d(map) when the map requires grad.
+    `guard`: None for a map tensor of the caller's, or {"eng", "token"} when the map is a view of an engine's workspace -- the backward
+    re-reads it there and refuses, like the lifter's, once a later run has overwritten it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, to_image, mode, beta, decode, guard):
+        kcrop, score, k2d, _ = kp_head_forward(x, weight, bias, mode, beta, decode, to_image)
+        ctx.x, ctx.weight, ctx.bias, ctx.to_image = x, weight.detach(), None if bias is None else bias.detach(), to_image
+        ctx.mode, ctx.beta, ctx.decode, ctx.guard = mode, beta, decode, guard
+        ctx.mark_non_differentiable(score)
+        if k2d is None:
+            k2d = kcrop.new_empty(0)
+            ctx.mark_non_differentiable(k2d)
+        return kcrop, score, k2d
+
+    @staticmethod
+    def backward(ctx, dkcrop, _dscore, dk2d):
+        if ctx.mode != KP_INTEGRAL:
+            raise CapfError("the argmax keypoint head has no derivative: build the model with keypoint_head='integral' to train it")
+        if ctx.x.dtype != torch.float32:
+            raise NotImplementedError("the keypoint head's backward needs an fp32 map (capf_kp_head_backward), got {}".format(ctx.x.dtype))
+        g = ctx.guard
+        if g is not None and g["eng"].train_generation() != g["token"]:
+            raise CapfError("backward of a keypoint head whose map (feat0 in the engine's workspace) was overwritten by a later forward "
+                            "on the same engine: call backward before the next forward of this model")
+        if ctx.to_image is None:
+            dk2d = None
+        want_dmap = ctx.needs_input_grad[0]
+        dw, db, dmap = kp_head_backward(ctx.x.detach(), ctx.weight, ctx.bias, None if dkcrop is None else dkcrop.contiguous(),
+                                        None if dk2d is None else dk2d.contiguous(), ctx.beta, ctx.decode, ctx.to_image, want_dmap)
+        return (dmap, dw.view(ctx.weight.shape) if ctx.needs_input_grad[1] else None,
+                db if ctx.bias is not None and ctx.needs_input_grad[2] else None, None, None, None, None, None)
+
+
+def keypoint_head(map_nhwc, weight, bias=None, to_image=None, mode="integral", beta=1.0, decode=(1.0, 0.0, 1.0, 0.0)):
+    """The native keypoint head as a free function on ANY contiguous NHWC map [B, H, W, C] (fp32; bf16 / fp16 without gradients):
+    returns (kcrop [B, J, 2], score [B, J], k2d [B, J, 2] | None).  With mode="integral" the result is differentiable in weight [J, C]
+    or [J, C, 1, 1], in bias (gradient exactly 0) and in the map: a torch backbone in front of CA_PF.forward_features gets the head's and
+    the lifter's gradients.  decode = (sx, ox, sy, oy): heatmap -> crop pixels; to_image [B, 2, 3]: crop pixels -> the lifter's k2d."""
+    if not isinstance(mode, str) or mode not in KP_MODES:
+        raise ValueError("mode must be 'argmax' or 'integral', got {!r}".format(mode))
+    kcrop, score, k2d = _KeypointHeadFn.apply(map_nhwc, weight, bias, to_image, KP_MODES[mode], float(beta),
+                                              tuple(float(v) for v in decode), None)
+    return kcrop, score, (k2d if to_image is not None else None)
 
 
 MAP_GRAD_MODES = {"atomic": 0, "ordered": 1}
@@ -165,8 +237,14 @@ class _FeatureStep(torch.autograd.Function):
 
 
 class CA_PF(nn.Module):
-    def __init__(self, config, device="cuda:0", compute_dtype="fp32", context_blocks=True, plan_flags=0, backbone_bn="running"):
-        """backbone_bn: what the frozen backbone's BatchNorm layers do while `self.backbone.training` is set.  "running" (default): the
+    def __init__(self, config, device="cuda:0", compute_dtype="fp32", context_blocks=True, plan_flags=0, backbone_bn="running",
+                 keypoint_head=None, keypoint_beta=1.0):
+        """keypoint_head: None (default) -- the module, its state_dict and its engines are exactly the reference's: the 2-D keypoints come
+        from outside.  "argmax" / "integral": the module gains self.keypoint_head.final_layer (weight [J, C0, 1, 1], bias [J]; an HRNet COCO
+        checkpoint's final_layer.* load by name, CPN gets a fresh head on its 256-channel feat0) and detect / forward_detect run it on
+        feat0: "argmax" is the hard decode HRNet checkpoints are evaluated with (no gradient), "integral" the soft-argmax
+        softmax(keypoint_beta * heatmap) whose weights train through the lifter (forward_detect under grad, fp32 models).
+        backbone_bn: what the frozen backbone's BatchNorm layers do while `self.backbone.training` is set.  "running" (default): the
         running statistics, folded into the convs, whatever the mode -- i.e. a frozen backbone left in .train() silently gets eval-mode
         BatchNorm.  "batch" (HRNet, fp32): the module honours self.backbone.training as torch does -- in train mode every forward
         normalises with the statistics of the batch, moves running_mean / running_var with momentum 0.1 and counts num_batches_tracked
@@ -181,9 +259,15 @@ class CA_PF(nn.Module):
         if backbone_bn == "batch" and (compute_dtype != "fp32" or config.model.backbone.type not in ("hrnet_32", "hrnet_48")):
             raise ValueError("backbone_bn='batch' needs an HRNet backbone and compute_dtype='fp32' (got {!r}, {!r})".format(
                 config.model.backbone.type, compute_dtype))
+        if keypoint_head is not None and (not isinstance(keypoint_head, str) or keypoint_head not in KP_MODES):
+            raise ValueError("keypoint_head must be None, 'argmax' or 'integral', got {!r}".format(keypoint_head))
+        if not (isinstance(keypoint_beta, (int, float)) and 0.0 < float(keypoint_beta) < float("inf")):
+            raise ValueError("keypoint_beta must be a positive finite number, got {!r}".format(keypoint_beta))
         super().__init__()
         self.compute_dtype = compute_dtype
         self.backbone_bn = backbone_bn
+        self.keypoint_head_mode = keypoint_head
+        self.keypoint_beta = float(keypoint_beta)
         if backbone_bn == "batch":
             plan_flags |= PLAN_BN_BATCH_STATS
         self.plan_flags = plan_flags               # capf.lib.PLAN_* bits: parity tests compare kernel families; 0 = product plan
@@ -194,12 +278,15 @@ class CA_PF(nn.Module):
         # schema from a plan-only handle (no GPU needed): names == reference state_dict
         plan = Engine(_native.make_capf_config(config, 256, 192, context_blocks=context_blocks), device=None)
         schema = plan.schema()
+        feat0_channels = plan.feature_shapes()[0][2]
         plan.close()
         self.backbone = _native.build_param_tree(_native.Container(), schema, "backbone")
         self.volume_net = _native.build_param_tree(_native.Container(), schema, "volume_net")
         if self._backbone_type == "cpn":
             _native.init_cpn_convs(self.backbone)
         _native.init_deformable_blocks(self.volume_net)
+        if keypoint_head is not None:             # (registered last, and only then: the default module's state_dict is the reference's)
+            self.keypoint_head = KeypointHead(feat0_channels, self.num_joints)
 
         if config.model.backbone.fix_weights:
             print("model backbone weights are fixed")
@@ -446,6 +533,118 @@ class CA_PF(nn.Module):
                 with torch.no_grad():
                     keypoints_2d_cpn_crop.copy_(kcrop)
         return out
+
+    # ---- detector-free: the 2-D keypoints from the native head on feat0 -------------------------
+    def _head_params(self):
+        if self.keypoint_head_mode is None:
+            raise CapfError("this model has no keypoint head: build it with keypoint_head='argmax' or 'integral'")
+        fl = self.keypoint_head.final_layer
+        return fl.weight, fl.bias
+
+    def _head_trains(self):
+        """True when this call must produce gradients of the head's parameters; refuses what the native backward does not cover."""
+        weight, bias = self._head_params()
+        if not (torch.is_grad_enabled() and (weight.requires_grad or bias.requires_grad)):
+            return False
+        if self.keypoint_head_mode != "integral":
+            raise NotImplementedError("the argmax keypoint head has no derivative: build the model with keypoint_head='integral', or freeze "
+                                      "keypoint_head's parameters (requires_grad_(False)) / call under torch.no_grad()")
+        if self.compute_dtype != "fp32":
+            raise NotImplementedError("gradients of the keypoint head need compute_dtype='fp32' (capf_kp_head_backward, capf_backward_points); "
+                                      "this model's compute_dtype is {!r}: freeze keypoint_head's parameters, call under torch.no_grad() or "
+                                      "build the model in fp32".format(self.compute_dtype))
+        return True
+
+    def _detect_inputs(self, images, to_image):
+        if not torch.is_tensor(images) or images.dtype not in (torch.float32, torch.uint8):
+            raise TypeError("images must be float32 or uint8, got {}".format(getattr(images, "dtype", type(images))))
+        if images.device.type != "cuda":
+            raise CapfError("CA_PF runs on an MI355X only: inputs are on {} (no CPU fallback)".format(images.device))
+        if images.dim() != 4 or images.shape[3] != 3:
+            raise ValueError("images must be [B,H,W,3] NHWC, got {}".format(tuple(images.shape)))
+        if images.dtype == torch.uint8 and self._bn_batch_active():
+            raise NotImplementedError("uint8 images have no batch-statistics route (backbone_bn='batch' with the backbone in train mode): "
+                                      "call backbone.eval(), or pass capf.lib.preprocess()'s fp32 images")
+        B = images.shape[0]
+        if to_image is not None:
+            if not torch.is_tensor(to_image) or to_image.dtype != torch.float32 or tuple(to_image.shape) != (B, 2, 3):
+                raise ValueError("to_image must be a float32 tensor [{}, 2, 3] (capf.lib.crop_to_image_matrix per frame), got {}".format(
+                    B, tuple(getattr(to_image, "shape", ()))))
+            if to_image.device != images.device:
+                raise ValueError("to_image is on {} but images are on {}".format(to_image.device, images.device))
+            to_image = to_image.detach().contiguous()
+        return images.contiguous(), to_image
+
+    def _backbone_maps(self, eng, images, stream):
+        """One backbone pass (no gradient reaches it); returns feat0 as a view of the engine's workspace, NHWC in the plan's dtype."""
+        if images.dtype == torch.uint8:
+            from capf.lib import input_constants
+            mean, std = input_constants("cpn" if self._backbone_type == "cpn" else "hrnet_32")
+            eng.backbone_forward_u8(images, mean, std, 0, stream)
+        elif self._bn_batch_active():
+            self._backbone_forward_bn(eng, images, stream)
+        else:
+            eng.backbone_forward(images, stream)
+        return eng.tensor_view("feat0", images.shape[0])
+
+    def _run_head(self, eng, feat0, to_image, H, W, trains):
+        weight, bias = self._head_params()
+        decode = (float(W) / feat0.shape[2], 0.0, float(H) / feat0.shape[1], 0.0)       # HRNet's convention: heatmap cell -> crop pixel
+        guard = {"eng": eng, "token": None} if trains else None
+        with torch.set_grad_enabled(trains):
+            kcrop, score, k2d = _KeypointHeadFn.apply(feat0, weight, bias, to_image, KP_MODES[self.keypoint_head_mode], self.keypoint_beta,
+                                                      decode, guard)
+        return kcrop, score, (k2d if to_image is not None else None), guard
+
+    def detect(self, images, to_image=None):
+        """The 2-D keypoints of the crops from the native head: backbone (one pass), final_layer on feat0 and the heatmap decode.
+        images: [B,H,W,3] float32 (normalised, as forward takes them) or uint8 BGR crops (as forward_u8 takes them; the same bits).
+        to_image: None, or float32 [B, 2, 3] -- per frame the matrix capf.lib.crop_to_image_matrix builds from the crop's center / scale
+        and the camera resolution.  Returns (kcrop_px [B,J,2] in crop pixels, score [B,J], k2d [B,J,2] normalised image coordinates or
+        None): what forward() takes as its third and second argument.  No gradients (see forward_detect)."""
+        self._head_params()
+        images, to_image = self._detect_inputs(images, to_image)
+        dev = images.device
+        with torch.cuda.device(dev), torch.no_grad():
+            eng = self._engine_at(dev, images.shape[1], images.shape[2])
+            feat0 = self._backbone_maps(eng, images, torch.cuda.current_stream(dev).cuda_stream)
+            kcrop, score, k2d, _ = self._run_head(eng, feat0, to_image, images.shape[1], images.shape[2], False)
+        return kcrop, score, k2d
+
+    def forward_detect(self, images, to_image):
+        """forward() without detections from outside: ONE backbone pass, the keypoint head on feat0, the lifter on the maps still in the
+        workspace.  Returns (joints3d [B,1,J,3], kcrop_px [B,J,2], score [B,J]); kcrop_px stays in crop pixels (the lifter normalises a
+        private copy).  The result equals forward(images, k2d, kcrop_px) on detect()'s keypoints bit for bit.
+        With grad enabled the lifter trains as in forward(), and an "integral" head whose parameters require grad trains THROUGH the
+        lifter (fp32 models): the backbone runs once without grad, the head is its own autograd node, capf_backward_points hands it
+        dL/d(k2d) and dL/d(crop keypoints), capf_kp_head_backward turns them into final_layer.weight.grad (bias.grad is exactly 0: softmax
+        ignores a shift).  A loss on kcrop_px itself (KeypointsMSELoss against 2-D labels) trains the head too.  The backward re-reads feat0
+        from the workspace (the lifter's training forward and backward only read the maps): run it before the next forward of this model.
+        An "argmax" head with trainable parameters, or a 16-bit model with a trainable head, raises under grad instead of dropping the
+        gradients."""
+        trains = self._head_trains()
+        if to_image is None:
+            raise ValueError("forward_detect needs to_image [B, 2, 3]: the lifter takes the keypoints in normalised image coordinates too")
+        images, to_image = self._detect_inputs(images, to_image)
+        dev, B, H, W = images.device, images.shape[0], images.shape[1], images.shape[2]
+        with torch.cuda.device(dev):
+            eng = self._engine_at(dev, H, W)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            named = self._lifter_step_params(trains)
+            with torch.no_grad():
+                feat0 = self._backbone_maps(eng, images, stream)
+            kcrop, score, k2d, guard = self._run_head(eng, feat0, to_image, H, W, trains)
+            if named is not None:
+                names = tuple("volume_net." + n for n, _ in named)
+                # (a crop-keypoint tensor outside the graph would be normalised in place by the step: it gets a copy, the caller the pixels)
+                out = _LifterStep.apply(self, eng, _WorkspaceMaps(B, dev), k2d, kcrop if kcrop.requires_grad else kcrop.clone(),
+                                        self._drop_masks(B, dev), names, *[p for _, p in named])
+                if guard is not None:
+                    guard["token"] = eng.train_generation()
+            else:
+                out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=dev)
+                eng.lifter_forward(k2d, kcrop.detach().clone(), out, stream)
+        return out, kcrop, score
 
     # ---- conpose.py:40 on maps of the caller's own backbone ------------------------------------
     def _feature_geometry(self, H, W):

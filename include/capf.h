@@ -154,7 +154,7 @@ const char* capf_version(void);
  * layouts unchanged.  Revision 12 (additive): compute_dtype = CAPF_F16, tensor dtype code 3 (fp16) in capf_tensor / capf_op_desc, the
  * capf_op_*_16 entry points (the 16-bit kernels for either element format) and capf_debug_f16_round; struct layouts unchanged
  * (additive: capf_set_map_grad_mode, capf_map_grad_mode; CAPF_PLAN_BN_BATCH_STATS, capf_backbone_forward_bn, capf_op_bn_stats_scratch_bytes,
- * capf_op_bn_stats, capf_op_bn_apply).                                                                                                   */
+ * capf_op_bn_stats, capf_op_bn_apply; capf_backward_points; capf_kp_head_scratch_bytes, capf_kp_head_forward, capf_kp_head_backward).      */
 #define CAPF_ABI_VERSION 12
 int capf_abi_version(void);
 
@@ -733,6 +733,59 @@ int capf_segment_sums(void* stream, const float* err, const int32_t* segment, co
                       double* sums, int32_t* counts);
 int capf_keypoints_loss(void* stream, int mode, const float* pred, const float* gt, const float* validity, int rows, int dim,
                         float threshold, float* loss, float* dpred);
+
+/* ---- 2-D keypoint head: final_layer + heatmap decode on the highest-resolution context map --------------------------------------------
+ * What an HRNet COCO checkpoint's final_layer (nn.Conv2d(C0, 17, 1), pose_hrnet.py:497-501, commented out in the reference) computes on
+ * y_list[0] = feat0, followed by the decode of its heatmaps, as ONE pass over the map (csrc/kp_head.hip): the producer of the 2-D keypoints that
+ * capf_forward takes and the consumer of capf_backward_points' dk2d / dref.  Stand-alone entries on device pointers (capf_tensor("feat0")
+ * serves the map of a handle; any other NHWC map of the same layout does too).  Additive inside revision 12.
+ *   map_nhwc [B, H, W, C] of map_dtype (capf_dtype: fp32, bf16 or fp16; a 16-bit value is widened exactly and everything after is fp32), 16-byte
+ *   aligned (8 for a 16-bit map); weight [J, C] fp32 (final_layer.weight [J, C, 1, 1]); bias [J] fp32 or NULL.  1 <= J <= 32, C % 4 == 0,
+ *   4 <= C <= 512, H, W >= 1, H * W <= 2^24.
+ * Logits: ONE fixed fp32 expression on the vector pipe (no matrix pipe, no block scales: a frame's result is bit-identical whatever else is in
+ *   the batch and on every run, handle and scratch buffer),
+ *       z[b, j, y, x] = bias[j];  for c = 0 .. C - 1 ascending:  z = fma(map[b, y, x, c], weight[j, c], z).
+ *   The heatmaps are never written unless `heat` [B, J, H, W] (the fp32 logits the decode used, bit for bit) is given.
+ * mode 0, argmax -- the rule HRNet checkpoints are evaluated with: idx = the FIRST maximum of z[b, j] in row-major order (ties go to the smallest
+ *   index), score = z[idx], px = idx % W, py = idx / W, (x, y) = (px, py); if 1 < px < W - 1 and 1 < py < H - 1:
+ *   x += 0.25 sign(z[py][px + 1] - z[py][px - 1]), y += 0.25 sign(z[py + 1][px] - z[py - 1][px]), sign(0) = 0; then, if score <= 0, (x, y) = (0, 0).
+ * mode 1, integral (soft-argmax): p = softmax(beta z[b, j]) over the H * W pixels with the maximum subtracted, x = sum p col, y = sum p row,
+ *   score = max z.  beta > 0 and finite (checked in both modes; pass 1 in mode 0).
+ * NaN: if any logit of a (frame, joint) is NaN, its keypoint (both coordinate systems) and its score are NaN, in both modes; other joints and
+ *   frames are untouched.
+ * Outputs: kcrop[b, j] = (sx x + ox, sy y + oy) with decode = {sx, ox, sy, oy} (HRNet's convention: sx = W_img / W, sy = H_img / H, offsets 0;
+ *   product rounded, then the sum); k2d[b, j] = A_b (kcrop_x, kcrop_y, 1) = ((A00 kx + A01 ky) + A02, (A10 kx + A11 ky) + A12) for
+ *   to_image [B, 2, 3] fp32, the caller's composition of the inverse crop affine and normalize_screen_coordinates (common/camera.py:14-18);
+ *   to_image == NULL: k2d is not written.  score [B, J] and heat are optional (NULL).
+ * Summation orders (integral): pixels are numbered row-major and cut into tiles of 256 and slabs of ceil(tiles / 64) tiles -- a function of H * W
+ *   alone.  Inside a slab 8 lanes share a joint: lane l visits pixels l, l + 8, ... of each tile, tiles ascending, with an online maximum m and
+ *   sums of e = exp(beta z - m), e col, e row (rescaled by exp(m_old - m_new) when m grows); lanes are merged in ascending l, slabs in ascending
+ *   order by a SECOND launch (no atomics, no signalling between workgroups), each merge as s = s1 exp(m1 - M) + s2 exp(m2 - M), M = max(m1, m2).
+ *   The argmax's neighbours are recomputed from the map with the expression above (the only values read twice).
+ * scratch: capf_kp_head_scratch_bytes(B, H, W, C, J, backward) bytes of device memory, 4-byte aligned (0: a shape the kernels do not take).
+ * capf_kp_head_backward (mode 1 and an fp32 map only; mode 0 or a 16-bit map: CAPF_ERR_UNSUPPORTED): for dkcrop / dk2d [B, J, 2] (either may
+ *   be NULL, not both; dk2d needs to_image), g = (sx, sy) * (dkcrop + A_b[:, :2]^T dk2d); logits and softmax statistics are recomputed (the
+ *   forward saves nothing); dz_i = beta p_i (g_x (col_i - x) + g_y (row_i - y));
+ *       dweight [J, C] = sum over frames and pixels of dz X: per block (a frame's eighth of the tiles) pixels ascending inside a tile and tiles
+ *           ascending, then a second launch adds the blocks' partials -- part q of 16 takes blocks q, q + 16, ... ascending, parts ascending;
+ *       dbias [J] is written as EXACT ZEROS: softmax is invariant under a shift of its logits, so the true gradient is 0, and a rounding-level
+ *           residue would be normalised by AdamW into steps of size lr;
+ *       dmap [B, H, W, C] (optional, 16-byte aligned) = sum_j dz Wt[j, c], joints ascending, each element by one thread: accumulate = 1 adds it
+ *           to what is there (capf_backward_points' dfeat_nhwc[0]), accumulate = 0 overwrites.
+ * Refusals, all before anything is launched (no device needed): a NULL map / weight / decode / scratch / kcrop (forward) / dweight / dbias
+ *   (backward), both gradients NULL, dk2d without to_image, B, J, C, H or W out of range, beta <= 0 or not finite, an unknown mode or dtype,
+ *   accumulate not 0 / 1, a misaligned map / dmap, scratch_bytes too small: CAPF_ERR_INVALID.
+ * Cost (MI355X, HRNet-32 fp32 256 x 256, feat0 64 x 64 x 32, medians of 20 around the host call, tools/bench_kp_head.py, EXPERIMENTS.md R24.1): forward
+ *   0.096 (argmax) / 0.076 ms (integral) at batch 64 and 0.318 / 0.313 ms at batch 512, against capf_backbone_forward's 5.89 / 43.4 ms and a one-read
+ *   floor of 0.008 / 0.067 ms (the slab kernel alone: 36 - 48 / 250 - 275 us; bound by instruction issue per 256-pixel tile, not by memory); backward
+ *   0.169 ms (dweight) / 0.233 ms (with dmap) at batch 64, 1.02 / 1.53 ms at batch 512; fp16 HRNet-48 map at batch 256: 0.194 / 0.209 ms. */
+size_t capf_kp_head_scratch_bytes(int B, int H, int W, int C, int J, int backward);
+int capf_kp_head_forward(void* stream, const void* map_nhwc, int map_dtype, const float* weight, const float* bias, int B, int H, int W, int C,
+                         int J, int mode, float beta, const float decode[4], const float* to_image, float* kcrop, float* k2d, float* score,
+                         float* heat, void* scratch, size_t scratch_bytes);
+int capf_kp_head_backward(void* stream, const float* dkcrop, const float* dk2d, const void* map_nhwc, int map_dtype, const float* weight,
+                          const float* bias, int B, int H, int W, int C, int J, int mode, float beta, const float decode[4],
+                          const float* to_image, float* dweight, float* dbias, float* dmap, int accumulate, void* scratch, size_t scratch_bytes);
 /* capf_pck_counts: the MPI-INF-3DHP evaluation (ContextPose_mpi/3dhp_test/test_util, MATLAB: mpii_test_predictions_py.m,
  *   mpii_evaluate_errors.m, mpii_compute_3d_pck.m), which callers otherwise export to .mat files and run off the GPU; capf_pose_errors /
  *   capf_segment_sums serve H36M only.  Per pose i of pred / gt [n, joints, 3] (same unit; to_mm converts it to mm): gt made relative to

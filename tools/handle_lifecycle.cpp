@@ -1,5 +1,6 @@
 // Host sanitizer check of a handle's life, no GPU needed: creates and destroys plan-only handles of the three backbones, asks each the
-// questions a host asks before it has a device (schema, workspace size, op table), makes every run entry refuse it, and lets capf_create
+// questions a host asks before it has a device (schema, workspace size, op table), makes every run entry refuse it, walks the refusal paths
+// of the stand-alone keypoint head entries (capf_kp_head_forward / capf_kp_head_backward: arguments judged before any launch), and lets capf_create
 // fail both in front of the plan (a refused configuration) and behind it (a device that is not there: the branch that releases what a
 // handle already owns).  Built by `make -C contextaware-poseformer_amd/csrc hostcheck`: the engine's host sources with
 // -fsanitize=address,undefined, the device objects of the product build; it runs on the build machine and is not loaded into Python.
@@ -72,6 +73,28 @@ int main() {
                 ++handles;
             }
     capf_destroy(nullptr);
+    // the stand-alone keypoint head entries judge every argument before a launch: each refusal path, none of which touches a device
+    {
+        const float dec[4] = {1.f, 0.f, 1.f, 0.f};
+        const size_t fwd = capf_kp_head_scratch_bytes(2, 8, 8, 32, 17, 0), bwd = capf_kp_head_scratch_bytes(2, 8, 8, 32, 17, 1);
+        CHECK(fwd > 0 && bwd > fwd && capf_kp_head_scratch_bytes(2, 8, 8, 30, 17, 0) == 0 && capf_kp_head_scratch_bytes(2, 8, 8, 32, 33, 1) == 0);
+        alignas(16) static float big[4096];
+        CHECK(capf_kp_head_forward(nullptr, nullptr, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 0, 1.f, dec, nullptr, mem, nullptr, nullptr, nullptr, big, sizeof(big)) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_forward(nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 0, 1.f, dec, nullptr, nullptr, nullptr, nullptr, nullptr, big, sizeof(big)) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_forward(nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 33, 0, 1.f, dec, nullptr, mem, nullptr, nullptr, nullptr, big, sizeof(big)) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_forward(nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 36, 17, 2, 1.f, dec, nullptr, mem, nullptr, nullptr, nullptr, big, sizeof(big)) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_forward(nullptr, big, 3, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, mem, nullptr, nullptr, nullptr, big, sizeof(big)) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_forward(nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 1, 0.f, dec, nullptr, mem, nullptr, nullptr, nullptr, big, sizeof(big)) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_forward(nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, mem, nullptr, nullptr, nullptr, big, fwd - 1) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_forward(nullptr, big + 1, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, mem, nullptr, nullptr, nullptr, big, sizeof(big)) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_backward(nullptr, mem, nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 0, 1.f, dec, nullptr, mem, mem, nullptr, 0, big, sizeof(big)) == CAPF_ERR_UNSUPPORTED);
+        CHECK(capf_kp_head_backward(nullptr, mem, nullptr, big, CAPF_BF16, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, mem, mem, nullptr, 0, big, sizeof(big)) == CAPF_ERR_UNSUPPORTED);
+        CHECK(capf_kp_head_backward(nullptr, nullptr, nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, mem, mem, nullptr, 0, big, sizeof(big)) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_backward(nullptr, nullptr, mem, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, mem, mem, nullptr, 0, big, sizeof(big)) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_backward(nullptr, mem, nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, nullptr, mem, nullptr, 0, big, sizeof(big)) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_backward(nullptr, mem, nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, mem, mem, big + 1, 1, big, sizeof(big)) == CAPF_ERR_INVALID);
+        CHECK(capf_kp_head_backward(nullptr, mem, nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, mem, mem, nullptr, 0, big, fwd) == CAPF_ERR_INVALID);
+    }
     // refused in front of the plan, inside it, and behind it (no device 0 on a machine without a GPU: what the handle owns is released)
     capf_handle* h = nullptr;
     capf_config c = config(CAPF_HRNET, 32, 7, 0);
