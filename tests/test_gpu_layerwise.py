@@ -19,7 +19,9 @@ from test_gpu_fullsize import _model
 pytestmark = pytest.mark.gpu
 
 
-def layerwise(backbone, dtype, B, H, W, rows, wseed=71, iseed=72, plan_flags=0):
+def layerwise(backbone, dtype, B, H, W, rows, wseed=71, iseed=72, plan_flags=0, only=None):
+    """only: the op names to walk (tests/test_gpu_route_cover.py) -- forward_prefix runs for the checkpoints of those ops alone, and exactly
+    those are checked; None: every backbone op of kind 0 - 3."""
     model, sd = _model(backbone, dtype, wseed, plan_flags)
     img, k2d, kc = synth.synth_inputs(B, H, W, seed=iseed, crop_range=(W, H))
     img_d = img.cuda()
@@ -29,7 +31,10 @@ def layerwise(backbone, dtype, B, H, W, rows, wseed=71, iseed=72, plan_flags=0):
     descs = [eng.op_describe(i) for i in range(n_ops)]
     table = eng.op_table(B)
     todo = [i for i, d in enumerate(descs) if d.backbone and d.kind in (0, 1, 2, 3)]
+    if only is not None:
+        todo = [i for i in todo if table[i][0] in only]
     stream = torch.cuda.current_stream().cuda_stream
+    kernel_of = {}
     bf = dtype == "bf16"
     worst, kernels, n_checked, flips, n_up, n_planes, resized = {}, set(), 0, 0, 0, 0, set()
     for cp in sorted(set(descs[i].checkpoint for i in todo)):
@@ -65,6 +70,7 @@ def layerwise(backbone, dtype, B, H, W, rows, wseed=71, iseed=72, plan_flags=0):
             flips += r["weight_flips"]
             kern = table[i][1] or ("fuse_sum", "maxpool", "resize")[d.kind - 1]
             kernels.add(kern)
+            kernel_of[table[i][0]] = kern
             w = worst.setdefault(kern, (0.0, 0.0, ""))
             if r["max_err"] >= w[0]:
                 worst[kern] = (r["max_err"], max(w[1], r["frac_inexact"]), table[i][0])
@@ -77,7 +83,9 @@ def layerwise(backbone, dtype, B, H, W, rows, wseed=71, iseed=72, plan_flags=0):
     assert flips <= 4
     for k, (e, f, name) in sorted(worst.items()):
         print(f"    {k:38s} worst error {e:9.2e} ({'of the allowance' if bf else 'of the range'})   largest inexact fraction {f:8.2e}   ({name})")
-    assert n_checked == len(todo) and n_checked > 85
+    assert n_checked == len(todo) and (n_checked > 85 if only is None else set(kernel_of) == set(only) and n_checked == len(set(only)))
+    layerwise.kernel_of = kernel_of                    # {op name: the kernel the engine named for it} before its workspace existed, and after
+    layerwise.live_kernel_of = {n: k or kernel_of[n] for n, k, _ in eng.op_table(B) if n in kernel_of}
     layerwise.fused_upsample_adds = n_up
     layerwise.planes_consumers = n_planes
     layerwise.resizes = resized                        # (source H, W, result H, W) of every resize checked
