@@ -1155,8 +1155,8 @@ def preprocess(images_u8, gt, k2d, kcrop, backbone="hrnet_32", mode=0):
     dev = images_u8.device
     img_out = torch.empty((nsets, B, H, W, 3) if nsets == 2 else (B, H, W, 3), dtype=torch.float32, device=dev)
     k2d_out = torch.empty((nsets, B, 17, 2) if nsets == 2 else (B, 17, 2), dtype=torch.float32, device=dev)
-    kc_out = torch.empty_like(k2d_out)
-    gt_out = torch.empty_like(gt) if gt is not None else None
+    kc_out = torch.empty(k2d_out.shape, dtype=torch.float32, device=dev)
+    gt_out = torch.empty(gt.shape, dtype=torch.float32, device=dev) if gt is not None else None
     if backbone == "cpn":
         mean = torch.tensor([122.7717, 115.9465, 102.9801]) / 255.0              # fp32 division, like the reference
         std = None
@@ -1571,7 +1571,7 @@ def keypoints_loss(mode, pred, gt, validity, threshold=0.0, want_grad=False):
     D = pred.shape[-1]
     rows = pred.numel() // D
     loss = torch.empty(1, dtype=torch.float32, device=pred.device)
-    dpred = torch.empty_like(pred, memory_format=torch.contiguous_format) if want_grad else None
+    dpred = torch.empty(pred.shape, dtype=torch.float32, device=pred.device) if want_grad else None
     v = validity.to(torch.float32).expand(*pred.shape[:-1], 1).contiguous()
     rc = lib.capf_keypoints_loss(_stream(pred), int(mode), _p(pred.contiguous()), _p(gt.contiguous()), _p(v), rows, D,
                                  float(threshold), _p(loss), _p(dpred))

@@ -105,10 +105,10 @@ __global__ void fliptest_fuse_kernel(const float* __restrict__ pred2, float* __r
     const float* p = pred2 + ((long)b * J + j) * 3;
     const float* q = pred2 + (((long)B + b) * J + sw.j[j]) * 3;
     float* o = out + (long)t * 3;
-    // torch.mean over a dim of size 2: (a + b) / 2
-    o[0] = __fdiv_rn(__fadd_rn(p[0], -q[0]), 2.0f);
-    o[1] = __fdiv_rn(__fadd_rn(p[1], q[1]), 2.0f);
-    o[2] = __fdiv_rn(__fadd_rn(p[2], q[2]), 2.0f);
+    // torch.mean over a dim of size 2: ((0 + a) + b) / 2 -- the sum starts from +0, which shows in one case only: a = b = -0 gives +0
+    o[0] = __fdiv_rn(__fadd_rn(__fadd_rn(0.0f, p[0]), -q[0]), 2.0f);
+    o[1] = __fdiv_rn(__fadd_rn(__fadd_rn(0.0f, p[1]), q[1]), 2.0f);
+    o[2] = __fdiv_rn(__fadd_rn(__fadd_rn(0.0f, p[2]), q[2]), 2.0f);
 }
 
 hipError_t launch_fliptest_fuse_swap(const float* pred2, int B, int J, const int* swap, float* out, hipStream_t s) {

@@ -35,7 +35,9 @@ class _MPJPEFn(torch.autograd.Function):
         dim = pred_c.shape[-1]
         rows = pred_c.numel() // dim
         loss = torch.empty(1, dtype=torch.float32, device=pred.device)
-        dpred = torch.empty_like(pred_c) if ctx.needs_input_grad[0] else None
+        # the loss depends on pred - gt alone: one buffer serves both gradients (dloss/dgt = -dloss/dpred, as autograd gives the reference's
+        # torch.norm(keypoints_pred - keypoints_gt, dim=-1), loss.py:22)
+        dpred = torch.empty(pred_c.shape, dtype=torch.float32, device=pred.device) if any(ctx.needs_input_grad[:2]) else None
         stream = ctypes.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
         P = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
         if dim == 3:
@@ -49,12 +51,14 @@ class _MPJPEFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        return (ctx.dpred * g if ctx.dpred is not None else None), None
+        d = ctx.dpred * g
+        return (d if ctx.needs_input_grad[0] else None), (-d if ctx.needs_input_grad[1] else None)
 
 
 class MPJPE(nn.Module):
     """loss.py:16-22: mean over every leading axis of ||pred - gt||_2 along the last one (any width: 3-D joints, 2-D keypoints).
-    CUDA tensors only — there is no CPU fallback; other float dtypes are computed in fp32 and the loss is cast back to the inputs' dtype."""
+    CUDA tensors only — there is no CPU fallback; other float dtypes are computed in fp32 and the loss is cast back to the inputs' dtype.
+    Differentiable in both arguments, like the reference's expression: a target that requires grad receives the prediction's gradient negated."""
 
     def forward(self, keypoints_pred, keypoints_gt):
         assert keypoints_pred.shape == keypoints_gt.shape
@@ -109,13 +113,15 @@ class _KeypointsLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, gt, validity, mode, threshold):
         from capf.lib import keypoints_loss
-        loss, dpred = keypoints_loss(mode, pred, gt, validity, threshold, want_grad=ctx.needs_input_grad[0])
+        # f(gt - pred): the target's gradient is the prediction's negated (no gradient to the validity mask, which the callers build from labels)
+        loss, dpred = keypoints_loss(mode, pred, gt, validity, threshold, want_grad=any(ctx.needs_input_grad[:2]))
         ctx.dpred = dpred
         return loss[0]
 
     @staticmethod
     def backward(ctx, g):
-        return (ctx.dpred * g if ctx.dpred is not None else None), None, None, None, None
+        d = ctx.dpred * g
+        return (d if ctx.needs_input_grad[0] else None), (-d if ctx.needs_input_grad[1] else None), None, None, None
 
 
 class _KeypointsLoss(nn.Module):

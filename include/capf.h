@@ -721,6 +721,9 @@ int capf_fliptest_fuse_swap(void* stream, const float* pred2, int batch, int joi
  *   host numpy SVD of :48-60 is replaced by Horn's quaternion closed form, fp64 Jacobi per thread);  N_MPJPE
  *   loss.py:71-84;  velocity = |(pred_i - pred_prev) - (gt_i - gt_prev)| with prev = prev[i] (the previous pose of the
  *   same evaluated subset, i.e. np.diff over the masked rows, loss.py:87-101); prev == NULL means i-1; prev[i] < 0: 0.
+ *   A pose that has no such figure gets NaN in that column alone, its other columns and every other pose unaffected: e_P_MPJPE where
+ *   all predicted (or all ground-truth) joints are one point (normX normY = 0; the reference's numpy SVD raises there), e_N_MPJPE where
+ *   the prediction is all zero.  joints > 32: CAPF_ERR_UNSUPPORTED; joints <= 0 or n <= 0: CAPF_ERR_INVALID; nothing is launched.
  * capf_segment_sums: per-action aggregation of evaluate_using_pred (datasets/human36m.py:358-417): sums[a] =
  *   {sum e_MPJPE, sum e_P_MPJPE, sum e_N_MPJPE, sum e_velocity} over poses with segment[i] == a (fp64, fixed order:
  *   deterministic), counts[a] = {poses, poses with a predecessor}.  segment == NULL with n_segments == 1: all poses.

@@ -67,10 +67,105 @@ def n_mpjpe_per_pose(pred, gt):
     return np.linalg.norm(scale[:, None, None] * Y - X, axis=-1).mean(-1)
 
 
-def velocity_errors(pred, gt):
-    """loss.py:87-101 before the mean: [N,J,3] -> [N-1] (float32 first differences, like np.diff on fp32 arrays)."""
-    vp, vg = np.diff(pred, axis=0), np.diff(gt, axis=0)
-    return np.linalg.norm((vp - vg).astype(np.float64), axis=-1).mean(-1)
+def _horn_matrix(pred, gt):
+    """-> (N [n,4,4], nX [n], nY [n], muX, muY, X, Y): the symmetric 4x4 matrix of Horn's closed form for every pose, float64."""
+    X, Y = gt.astype(np.float64), pred.astype(np.float64)
+    muX, muY = X.mean(1, keepdims=True), Y.mean(1, keepdims=True)
+    X0, Y0 = X - muX, Y - muY
+    nX, nY = np.sqrt((X0 ** 2).sum((1, 2))), np.sqrt((Y0 ** 2).sum((1, 2)))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        S = np.matmul(Y0.transpose(0, 2, 1), X0) * (1.0 / (nX * nY))[:, None, None]          # S[a][b] = sum_j Y0[j][a] X0[j][b]
+    N = np.empty((X.shape[0], 4, 4))
+    N[:, 0, 0] = S[:, 0, 0] + S[:, 1, 1] + S[:, 2, 2]
+    N[:, 1, 1] = S[:, 0, 0] - S[:, 1, 1] - S[:, 2, 2]
+    N[:, 2, 2] = -S[:, 0, 0] + S[:, 1, 1] - S[:, 2, 2]
+    N[:, 3, 3] = -S[:, 0, 0] - S[:, 1, 1] + S[:, 2, 2]
+    N[:, 0, 1] = N[:, 1, 0] = S[:, 1, 2] - S[:, 2, 1]
+    N[:, 0, 2] = N[:, 2, 0] = S[:, 2, 0] - S[:, 0, 2]
+    N[:, 0, 3] = N[:, 3, 0] = S[:, 0, 1] - S[:, 1, 0]
+    N[:, 1, 2] = N[:, 2, 1] = S[:, 0, 1] + S[:, 1, 0]
+    N[:, 1, 3] = N[:, 3, 1] = S[:, 2, 0] + S[:, 0, 2]
+    N[:, 2, 3] = N[:, 3, 2] = S[:, 1, 2] + S[:, 2, 1]
+    return N, nX, nY, muX, muY, X, Y
+
+
+def horn_condition(pred, gt):
+    """-> (nX [n], nY [n], gap [n]): the centred norms loss.py:42-43 divides by, and the distance between the two largest
+    eigenvalues of the 4x4 matrix whose top eigenvector csrc/metrics.hip takes (LAPACK eigvalsh): what a test asserts about its
+    inputs before it holds the kernel's eigen-solver to a bound."""
+    N, nX, nY = _horn_matrix(pred, gt)[:3]
+    ok = np.isfinite(N).all((1, 2))                  # (a pose with nX nY == 0 has no matrix: its gap is NaN)
+    gap = np.full(N.shape[0], np.nan)
+    lam = np.linalg.eigvalsh(N[ok])
+    gap[ok] = lam[:, 3] - lam[:, 2]
+    return nX, nY, gap
+
+
+def p_mpjpe_jacobi_per_pose(pred, gt):
+    """loss.py:25-68 by the arithmetic of csrc/metrics.hip, statement for statement (top_eigen4: cyclic Jacobi, at most 12 sweeps,
+    stop below an off-diagonal square sum of 1e-30, rotations skipped below 1e-300; then the quaternion's rotation matrix, the
+    scale and the aligned error), in numpy float64 and batched over the poses: a pose that has converged, and a rotation that is
+    skipped, take c = 1, s = 0, which changes nothing.  -> (per-pose P_MPJPE [n], sweeps used [n])."""
+    A, nX, nY, muX, muY, X, Y = _horn_matrix(pred, gt)
+    n = A.shape[0]
+    V = np.broadcast_to(np.eye(4), (n, 4, 4)).copy()
+    sweeps = np.zeros(n, np.int64)
+    done = np.zeros(n, bool)
+    for sweep in range(12):
+        off = np.zeros(n)
+        for p in range(4):
+            for r in range(p + 1, 4):
+                off += A[:, p, r] * A[:, p, r]
+        done |= off < 1e-30
+        if done.all():
+            break
+        sweeps += ~done
+        for p in range(3):
+            for r in range(p + 1, 4):
+                apr = A[:, p, r]
+                skip = done | (np.abs(apr) < 1e-300)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    theta = (A[:, r, r] - A[:, p, p]) / (2.0 * apr)
+                    t = np.where(theta >= 0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+                c = np.where(skip, 1.0, 1.0 / np.sqrt(t * t + 1.0))
+                s = np.where(skip, 0.0, t * c)
+                c, s = c[:, None], s[:, None]
+                akp, akr = A[:, :, p].copy(), A[:, :, r].copy()                # A <- A J (columns p, r)
+                A[:, :, p], A[:, :, r] = c * akp - s * akr, s * akp + c * akr
+                apk, ark = A[:, p, :].copy(), A[:, r, :].copy()                # A <- J^T A (rows p, r)
+                A[:, p, :], A[:, r, :] = c * apk - s * ark, s * apk + c * ark
+                vkp, vkr = V[:, :, p].copy(), V[:, :, r].copy()
+                V[:, :, p], V[:, :, r] = c * vkp - s * vkr, s * vkp + c * vkr
+    diag = np.stack([A[:, i, i] for i in range(4)], 1)
+    best = np.zeros(n, np.int64)
+    for i in range(1, 4):
+        better = diag[:, i] > diag[np.arange(n), best]
+        best = np.where(better, i, best)
+    q = V[np.arange(n), :, best]
+    tr = diag[np.arange(n), best]
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    R = np.empty((n, 3, 3))
+    R[:, 0, 0], R[:, 0, 1], R[:, 0, 2] = w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y)
+    R[:, 1, 0], R[:, 1, 1], R[:, 1, 2] = 2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x)
+    R[:, 2, 0], R[:, 2, 1], R[:, 2, 2] = 2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z
+    a = tr * nX / nY
+    aligned = a[:, None, None] * np.matmul(Y - muY, R.transpose(0, 2, 1)) + muX
+    return np.linalg.norm(aligned - X, axis=-1).mean(-1), sweeps
+
+
+def velocity_errors(pred, gt, prev=None):
+    """loss.py:87-101 before the mean (float32 first differences, like np.diff on fp32 arrays).  prev None: [N,J,3] -> [N-1], rows
+    i and i-1.  prev [N] ints: row i against row prev[i], the pairing np.diff makes once a boolean mask has selected the rows of
+    one action (human36m.py:371-376) -> [N], 0 where prev[i] < 0 (no predecessor; such a row is in no mean)."""
+    if prev is None:
+        vp, vg = np.diff(pred, axis=0), np.diff(gt, axis=0)
+        return np.linalg.norm((vp - vg).astype(np.float64), axis=-1).mean(-1)
+    prev = np.asarray(prev)
+    has = prev >= 0
+    out = np.zeros(pred.shape[0])
+    vp, vg = pred[has] - pred[prev[has]], gt[has] - gt[prev[has]]
+    out[has] = np.linalg.norm((vp - vg).astype(np.float64), axis=-1).mean(-1)
+    return out
 
 
 def per_action(pred, gt, action_idx, n_actions):
@@ -82,6 +177,34 @@ def per_action(pred, gt, action_idx, n_actions):
         out[a] = [mpjpe_per_pose(pred[m], gt[m]).sum(), p_mpjpe_per_pose(pred[m], gt[m]).sum(),
                   n * velocity_errors(pred[m], gt[m]).mean(), n]
     return out
+
+
+def per_action_scores(pred, gt, action_idx, action_names):
+    """human36m.py:370-416 in float64: per action frame_count * mean of the per-pose errors over the rows a boolean mask selects
+    (:370-384), the '-1' / '-2' trials of an action added up (:386-407), everything divided by the frame count (:409-416).
+    pred / gt [N,J,3], action_idx [N] -> {name: {'MPJPE', 'P_MPJPE', 'MPJVE'}}.  An action without frames has the mean of nothing,
+    NaN, as the reference's `frame_count * e1(empty)` has, and the NaN goes into the merged action.  An action of ONE frame has an
+    MPJVE of NaN (no pair of rows) and finite MPJPE / P_MPJPE: the reference raises there, since `.squeeze()` (:374, :376) drops
+    the frame axis as well; mvn/datasets/human36m.py documents the choice this restates."""
+    action_idx = np.asarray(action_idx)
+    nan = np.float64("nan")
+    scores = {}
+    for a, name in enumerate(action_names):
+        m = action_idx == a
+        n = int(np.count_nonzero(m))
+        p, g = pred[m], gt[m]
+        scores[name] = {"MPJPE": n * mpjpe_per_pose(p, g).mean() if n else nan,
+                        "P_MPJPE": n * p_mpjpe_per_pose(p, g).mean() if n else nan,
+                        "MPJVE": n * velocity_errors(p, g).mean() if n > 1 else nan, "frame_count": n}
+    for base in [name[:-2] for name in action_names if name.endswith("-1")]:
+        combined = {"MPJPE": np.float64(0.0), "P_MPJPE": np.float64(0.0), "MPJVE": np.float64(0.0), "frame_count": 0}
+        for trial in 1, 2:
+            one = scores.pop("%s-%d" % (base, trial))
+            for k in combined:
+                combined[k] = combined[k] + one[k]
+        scores[base] = combined
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return {k: {m: np.float64(v[m]) / np.float64(v["frame_count"]) for m in ("MPJPE", "P_MPJPE", "MPJVE")} for k, v in scores.items()}
 
 
 def keypoints_loss(mode, pred, gt, validity, threshold=0.0):

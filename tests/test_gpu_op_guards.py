@@ -435,6 +435,79 @@ def test_wgrad_guarded(M):
             _twice(f"wgrad M{M} N{N} K{K} two_piece={two_piece}", lambda put: list(capf.wgrad(put(dy), put(x), two_piece)))
 
 
+# ---- the loss, metric and preprocessing kernels (values: tests/test_gpu_metric_edges.py) --------------------------------------------------------
+def test_pose_errors_and_segment_sums_guarded():
+    """capf_pose_errors writes err[n, 4] and reads pose prev[i] and nothing behind the last pose; capf_segment_sums writes sums[S, 4] and
+    counts[S, 2]: n around their blocks of 128 and 256, J from 3 to 32, a predecessor table and none, ids outside the segment table"""
+    import numpy as np
+    from mvn.datasets.human36m import previous_in_segment
+    for n, J, S in ((1, 17, 1), (127, 3, 6), (129, 32, 7), (257, 17, 7), (1000, 16, 6)):
+        rng = np.random.default_rng(n)
+        pred, gt = torch.from_numpy(rng.standard_normal((n, J, 3)).astype(np.float32)), torch.from_numpy(rng.standard_normal((n, J, 3)).astype(np.float32))
+        seg = rng.integers(-1, S + 1, n).astype(np.int32)
+        prev = torch.from_numpy(previous_in_segment(seg))
+        seg = torch.from_numpy(seg)
+
+        def one(put):
+            p, g, pv = put(pred), put(gt), put(prev)
+            err, err0 = capf.pose_errors(p, g, pv), capf.pose_errors(p, g)
+            sums, counts = capf.segment_sums(put(err), put(seg), pv, n_segments=S)
+            sums0, counts0 = capf.segment_sums(put(err0))
+            return [err, err0, sums, counts, sums0, counts0]
+        _twice(f"pose_errors / segment_sums n{n} J{J} S{S}", one)
+
+
+def test_mpjpe_entries_guarded():
+    """capf_mpjpe and capf_mpjpe_nd (a thin ctypes call: mvn.models.loss.MPJPE is their only caller): one loss element, dpred[rows, D]"""
+    import ctypes
+    lib = capf.load_library()
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    g = torch.Generator().manual_seed(13)
+    for rows, D in ((1, 3), (1023, 3), (1025, 3), (8705, 3), (1, 1), (1025, 2), (1023, 7), (2, 4)):
+        pred, gt = torch.randn(rows, D, generator=g), torch.randn(rows, D, generator=g)
+
+        def one(put):
+            p, t = put(pred), put(gt)
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            outs = []
+            for entry in ("capf_mpjpe", "capf_mpjpe_nd") if D == 3 else ("capf_mpjpe_nd",):
+                loss, dpred = torch.empty(1, device="cuda"), torch.empty(rows, D, device="cuda")
+                dims = (rows,) if entry == "capf_mpjpe" else (rows, D)
+                assert getattr(lib, entry)(stream, P(p), P(t), *dims, P(loss), P(dpred), 0.125) == 0
+                outs += [loss, dpred]
+            return outs
+        _twice(f"mpjpe rows {rows} D {D}", one)
+
+
+def test_keypoints_loss_guarded():
+    """capf_keypoints_loss with its gradient in the three modes: rows around its block of 1024, D 1 to 4, validity [rows, 1]"""
+    g = torch.Generator().manual_seed(14)
+    for rows, D in ((1, 3), (17, 1), (1023, 2), (1025, 3), (3000, 4)):
+        pred, gt, v = torch.randn(rows, D, generator=g), torch.randn(rows, D, generator=g), (torch.rand(rows, 1, generator=g) > 0.3).float()
+
+        def one(put):
+            p, t, w = put(pred), put(gt), put(v)
+            return [o for mode in (0, 1, 2) for o in capf.keypoints_loss(mode, p, t, w, 0.5, want_grad=True)]
+        _twice(f"keypoints_loss rows {rows} D {D}", one)
+
+
+def test_preprocess_and_fliptest_fuse_guarded():
+    """capf_preprocess (uint8 crops in, four outputs) at ragged image sizes in its three modes, with and without ground truth; the flip-test
+    fusion at B 1 / 129 with the H36M table and a 32-joint caller table"""
+    g = torch.Generator().manual_seed(15)
+    for B, H, W in ((1, 8, 8), (5, 9, 7), (2, 256, 192)):
+        img = torch.randint(0, 256, (B, H, W, 3), generator=g, dtype=torch.uint8)
+        gt, k2d, kc = torch.randn(B, 1, 17, 3, generator=g), torch.rand(B, 17, 2, generator=g) * 2 - 1, torch.rand(B, 17, 2, generator=g) * 191
+        for mode in (0, 1, 2):
+            for backbone in ("hrnet_32", "cpn"):
+                _twice(f"preprocess {B}x{H}x{W} mode {mode} {backbone}",
+                       lambda put: list(capf.preprocess(put(img), put(gt) if mode != 2 or backbone == "cpn" else None, put(k2d), put(kc), backbone, mode)))
+    swap32 = [j ^ 1 if j < 20 else j for j in range(32)]
+    for B, J, swap in ((1, 17, None), (129, 17, None), (1, 32, swap32), (129, 32, swap32), (3, 1, [0])):
+        p = torch.randn(2, B, 1, J, 3, generator=g)
+        _twice(f"fliptest_fuse B{B} J{J}", lambda put: [capf.fliptest_fuse(put(p), swap)])
+
+
 # ---- the JPEG decoders' scratch (its own contract: capf_jpeg_*_info's scratch_bytes) -----------------------------------------------------------
 def test_jpeg_decoders_stay_inside_an_exact_poisoned_scratch():
     """capf_jpeg_decode and capf_jpeg_decode_batch on the eight goldens of tests/golden/jpeg_cases.npz: the wrappers allocate the scratch
