@@ -262,6 +262,11 @@ PARAM_KINDS = {0: "conv_w", 1: "bn_w", 2: "bn_b", 3: "bn_mean", 4: "bn_var", 5: 
                8: "ln_w", 9: "ln_b", 10: "raw"}
 
 
+def _p(t):
+    """a tensor's device pointer for the C ABI; None -> a null pointer"""
+    return c_void_p(t.data_ptr()) if t is not None else c_void_p(0)
+
+
 class Engine:
     """One native handle.  device=None -> plan-only (schema / workspace queries, no GPU)."""
 
@@ -336,12 +341,16 @@ class Engine:
             self._check(self.lib.capf_set_workspace(self.h, c_void_p(self._ws.data_ptr()), nbytes), "set_workspace")
 
     # ---- hot path
+    def _run(self, entry, batch, stream, *args):
+        """capf_<entry>(handle, stream, *args) with the workspace sized for `batch` frames first (None: a backward, which runs in the
+        workspace of its forward); a negative status raises "<entry> failed (rc): message"."""
+        if batch is not None:
+            self.ensure_workspace(batch)
+        self._check(getattr(self.lib, "capf_" + entry)(self.h, c_void_p(stream), *args), entry)
+
     def forward(self, images, k2d, kcrop, out, stream):
         B = images.shape[0]
-        self.ensure_workspace(B)
-        self._check(self.lib.capf_forward(self.h, c_void_p(stream), c_void_p(images.data_ptr()),
-                                          c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B,
-                                          c_void_p(out.data_ptr())), "forward")
+        self._run("forward", B, stream, _p(images), _p(k2d), _p(kcrop), B, _p(out))
 
     # ---- the same from uint8 BGR crops [Bsrc,H,W,3] (capf_forward_u8 ...): mode 0 as is, 1 mirrored, 2 flip-test pair (2 * Bsrc engine frames);
     # mean / std: (c_float * 3) arrays (input_constants), std None = mean only.  k2d / kcrop / out hold the ENGINE frames
@@ -351,22 +360,15 @@ class Engine:
 
     def forward_u8(self, images_u8, mean, std, mode, k2d, kcrop, out, stream):
         B = self._u8_batch(images_u8, mode)
-        self.ensure_workspace(B)
-        self._check(self.lib.capf_forward_u8(self.h, c_void_p(stream), c_void_p(images_u8.data_ptr()), mean, std, int(mode),
-                                             c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B, c_void_p(out.data_ptr())), "forward_u8")
+        self._run("forward_u8", B, stream, _p(images_u8), mean, std, int(mode), _p(k2d), _p(kcrop), B, _p(out))
 
     def backbone_forward_u8(self, images_u8, mean, std, mode, stream):
         B = self._u8_batch(images_u8, mode)
-        self.ensure_workspace(B)
-        self._check(self.lib.capf_backbone_forward_u8(self.h, c_void_p(stream), c_void_p(images_u8.data_ptr()), mean, std, int(mode), B),
-                    "backbone_forward_u8")
+        self._run("backbone_forward_u8", B, stream, _p(images_u8), mean, std, int(mode), B)
 
     def forward_train_u8(self, images_u8, mean, std, mode, k2d, kcrop, out, stream, masks=None):
         B = self._u8_batch(images_u8, mode)
-        self.ensure_workspace(B)
-        self._check(self.lib.capf_forward_train_u8(self.h, c_void_p(stream), c_void_p(images_u8.data_ptr()), mean, std, int(mode),
-                                                   c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B, c_void_p(out.data_ptr()),
-                                                   c_void_p(masks.data_ptr()) if masks is not None else c_void_p(0)), "forward_train_u8")
+        self._run("forward_train_u8", B, stream, _p(images_u8), mean, std, int(mode), _p(k2d), _p(kcrop), B, _p(out), _p(masks))
 
     # ---- training step
     def grad_layout(self):
@@ -388,12 +390,7 @@ class Engine:
 
     def forward_train(self, images, k2d, kcrop, out, stream, masks=None):
         B = images.shape[0]
-        self.ensure_workspace(B)
-        self._check(self.lib.capf_forward_train(self.h, c_void_p(stream), c_void_p(images.data_ptr()),
-                                                c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B,
-                                                c_void_p(out.data_ptr()),
-                                                c_void_p(masks.data_ptr()) if masks is not None else c_void_p(0)),
-                    "forward_train")
+        self._run("forward_train", B, stream, _p(images), _p(k2d), _p(kcrop), B, _p(out), _p(masks))
 
     def train_generation(self):
         return self.lib.capf_train_generation(self.h)
@@ -402,10 +399,7 @@ class Engine:
         return self.lib.capf_max_batch(self.h)
 
     def backward(self, grad_out, flat_grad, stream, masks=None):
-        B = grad_out.shape[0]
-        self._check(self.lib.capf_backward(self.h, c_void_p(stream), c_void_p(grad_out.data_ptr()), B,
-                                           c_void_p(flat_grad.data_ptr()),
-                                           c_void_p(masks.data_ptr()) if masks is not None else c_void_p(0)), "backward")
+        self._run("backward", None, stream, _p(grad_out), grad_out.shape[0], _p(flat_grad), _p(masks))
 
     # ---- the lifter on caller-supplied context maps (capf_set_features / capf_lifter_forward_train / capf_backward_maps)
     def feature_shapes(self):
@@ -425,34 +419,21 @@ class Engine:
     def set_features(self, feats_nhwc, stream):
         """Copy four contiguous fp32 NHWC maps [B, H_l, W_l, C_l] into the workspace's feat0..3."""
         B = feats_nhwc[0].shape[0]
-        self.ensure_workspace(B)
-        self._check(self.lib.capf_set_features(self.h, c_void_p(stream), self._ptrs4(feats_nhwc), B), "set_features")
+        self._run("set_features", B, stream, self._ptrs4(feats_nhwc), B)
 
     def lifter_forward_train(self, k2d, kcrop, out, stream, masks=None):
         B = k2d.shape[0]
-        self.ensure_workspace(B)
-        self._check(self.lib.capf_lifter_forward_train(self.h, c_void_p(stream), c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B,
-                                                       c_void_p(out.data_ptr()),
-                                                       c_void_p(masks.data_ptr()) if masks is not None else c_void_p(0)),
-                    "lifter_forward_train")
+        self._run("lifter_forward_train", B, stream, _p(k2d), _p(kcrop), B, _p(out), _p(masks))
 
     def backward_maps(self, grad_out, flat_grad, dfeat_nhwc, stream, masks=None):
         """capf_backward plus the gradient w.r.t. the context maps, written into four contiguous fp32 NHWC tensors."""
-        B = grad_out.shape[0]
-        self._check(self.lib.capf_backward_maps(self.h, c_void_p(stream), c_void_p(grad_out.data_ptr()), B,
-                                                c_void_p(flat_grad.data_ptr()),
-                                                c_void_p(masks.data_ptr()) if masks is not None else c_void_p(0),
-                                                self._ptrs4(dfeat_nhwc)), "backward_maps")
+        self._run("backward_maps", None, stream, _p(grad_out), grad_out.shape[0], _p(flat_grad), _p(masks), self._ptrs4(dfeat_nhwc))
 
     def backward_points(self, grad_out, flat_grad, stream, masks=None, dfeat_nhwc=None, dk2d=None, dref=None):
         """capf_backward plus any of: the map gradient (four contiguous fp32 NHWC tensors, as backward_maps), dk2d and dref (contiguous
         fp32 [B, J, 2]; dref is w.r.t. the NORMALISED crop keypoints).  None: that output is not computed."""
-        B = grad_out.shape[0]
-        ptr = lambda t: c_void_p(t.data_ptr()) if t is not None else c_void_p(0)
-        self._check(self.lib.capf_backward_points(self.h, c_void_p(stream), c_void_p(grad_out.data_ptr()), B,
-                                                  c_void_p(flat_grad.data_ptr()), ptr(masks),
-                                                  self._ptrs4(dfeat_nhwc) if dfeat_nhwc is not None else None, ptr(dk2d), ptr(dref)),
-                    "backward_points")
+        self._run("backward_points", None, stream, _p(grad_out), grad_out.shape[0], _p(flat_grad), _p(masks),
+                  self._ptrs4(dfeat_nhwc) if dfeat_nhwc is not None else None, _p(dk2d), _p(dref))
 
     def set_map_grad_mode(self, mode):
         """How capf_backward_maps sums the map gradient: 0 fp32 atomic adds (default), 1 the ordered, bit-reproducible sum."""
@@ -463,24 +444,17 @@ class Engine:
 
     def backbone_forward(self, images, stream):
         B = images.shape[0]
-        self.ensure_workspace(B)
-        self._check(self.lib.capf_backbone_forward(self.h, c_void_p(stream), c_void_p(images.data_ptr()), B),
-                    "backbone_forward")
+        self._run("backbone_forward", B, stream, _p(images), B)
 
     def backbone_forward_bn(self, images, stream, momentum=0.1):
         """capf_backbone_forward_bn: the backbone with batch statistics (a PLAN_BN_BATCH_STATS handle); the bound running_mean /
         running_var tensors are updated in place."""
         B = images.shape[0]
-        self.ensure_workspace(B)
-        self._check(self.lib.capf_backbone_forward_bn(self.h, c_void_p(stream), c_void_p(images.data_ptr()), B, float(momentum)),
-                    "backbone_forward_bn")
+        self._run("backbone_forward_bn", B, stream, _p(images), B, float(momentum))
 
     def lifter_forward(self, k2d, kcrop, out, stream):
         B = k2d.shape[0]
-        self.ensure_workspace(B)
-        self._check(self.lib.capf_lifter_forward(self.h, c_void_p(stream), c_void_p(k2d.data_ptr()),
-                                                 c_void_p(kcrop.data_ptr()), B, c_void_p(out.data_ptr())),
-                    "lifter_forward")
+        self._run("lifter_forward", B, stream, _p(k2d), _p(kcrop), B, _p(out))
 
     def set_lanes(self, on):
         self._check(self.lib.capf_set_lanes(self.h, int(on)), "set_lanes")
@@ -551,11 +525,8 @@ class Engine:
     # ---- layer-wise parity aids (capf_forward_prefix / capf_op_describe / capf_op_tensor)
     def forward_prefix(self, images, n_ops, stream, k2d=None, kcrop=None, out=None):
         B = images.shape[0]
-        self.ensure_workspace(B)
         self._prefix_images = images
-        P = lambda t: c_void_p(t.data_ptr()) if t is not None else c_void_p(0)
-        self._check(self.lib.capf_forward_prefix(self.h, c_void_p(stream), P(images), P(k2d), P(kcrop), B, P(out), int(n_ops)),
-                    "forward_prefix")
+        self._run("forward_prefix", B, stream, _p(images), _p(k2d), _p(kcrop), B, _p(out), int(n_ops))
 
     def op_describe(self, index):
         d = OpDesc()
@@ -607,12 +578,9 @@ class Engine:
         """One forward with a HIP event pair around every launch (on `stream`); returns ms per op.
         Synchronises the stream — measurement aid for bench.py, not the product path."""
         B = images.shape[0]
-        self.ensure_workspace(B)
         n = self.lib.capf_num_ops(self.h)
         ms = (c_float * n)()
-        self._check(self.lib.capf_forward_profile(self.h, c_void_p(stream), c_void_p(images.data_ptr()),
-                                                  c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B,
-                                                  c_void_p(out.data_ptr()), ms, n), "forward_profile")
+        self._run("forward_profile", B, stream, _p(images), _p(k2d), _p(kcrop), B, _p(out), ms, n)
         return list(ms)
 
     def op_schedule(self):
@@ -631,13 +599,10 @@ class Engine:
         """One forward of the product schedule with an event pair around every LAUNCH (grouped launches
         included); returns (ms per op, leader per op): see capf_forward_profile_launches."""
         B = images.shape[0]
-        self.ensure_workspace(B)
         n = self.lib.capf_num_ops(self.h)
         ms = (c_float * n)()
         leader = (c_int32 * n)()
-        self._check(self.lib.capf_forward_profile_launches(self.h, c_void_p(stream), c_void_p(images.data_ptr()),
-                                                           c_void_p(k2d.data_ptr()), c_void_p(kcrop.data_ptr()), B,
-                                                           c_void_p(out.data_ptr()), ms, leader, n), "forward_profile_launches")
+        self._run("forward_profile_launches", B, stream, _p(images), _p(k2d), _p(kcrop), B, _p(out), ms, leader, n)
         return list(ms), list(leader)
 
     def op_stream_classes(self, batch):
@@ -661,10 +626,6 @@ class Engine:
 
 
 # ---- stateless operators (op-level tests / micro-benchmarks) ---------------------------------------
-def _p(t):
-    return c_void_p(t.data_ptr()) if t is not None else c_void_p(0)
-
-
 def _stream(t):
     import torch
     return c_void_p(torch.cuda.current_stream(t.device).cuda_stream)

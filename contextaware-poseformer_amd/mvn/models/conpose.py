@@ -9,34 +9,66 @@ including the reference's in-place normalisation of the third argument (conpose.
 compute is one capf_forward call: hand-written gfx950 kernels, enqueued on torch's current stream.
 There is no eager / CPU fallback: CPU tensors or a missing libcapf.so raise.
 """
+import collections
+
 import torch
 from torch import nn
 
-from capf.lib import KP_INTEGRAL, KP_MODES, PLAN_BN_BATCH_STATS, CapfError, Engine, kp_head_backward, kp_head_forward
+from capf.lib import (KP_INTEGRAL, KP_MODES, PLAN_BN_BATCH_STATS, CapfError, Engine, input_constants, kp_head_backward,
+                      kp_head_forward)
 
 from . import _native
 
 
-class _U8Images:
-    """The `images` argument of _LifterStep on the uint8 route (CA_PF.forward_u8): the uint8 BGR crops with the normalisation
-    constants and capf_preprocess's mode; shape[0] counts engine frames (2 * Bsrc for a flip-test pair)."""
-
-    def __init__(self, crops, mean, std, mode):
-        self.crops, self.mean, self.std, self.mode = crops, mean, std, mode
-        self.device = crops.device
-        self.shape = (crops.shape[0] * (2 if mode == 2 else 1),) + tuple(crops.shape[1:])
-
-
-class _WorkspaceMaps:
-    """The `images` argument of _LifterStep when the context maps are already in the workspace (CA_PF.forward_detect ran the backbone and
-    the keypoint head on them): the step is capf_lifter_forward_train alone."""
-
-    def __init__(self, batch, device):
-        self.shape, self.device = (batch,), device
-
-
 MIRROR_MODES = {"none": 0, "all": 1, "pair": 2}       # CA_PF.forward_u8's `mirror` -> capf_preprocess's mode
 CROP_HALF = (192 // 2, 256 // 2)                      # conpose.py:34: ref = kcrop / (96, 128) - 1, so d(ref)/d(kcrop) = 1 / (96, 128)
+
+# Where the context maps of one call come from.  An entry point builds this record and nothing downstream looks at the entry any more.
+#   kind "images"     data = the fp32 NHWC images: the backbone runs on them
+#        "u8"         data = (uint8 BGR crops, mean, std, capf_preprocess's mode): the same, the stem reads the crops
+#        "workspace"  data = None: the maps of this batch are in the workspace already (forward_detect ran the backbone and the head)
+#        "maps"       data = four contiguous NHWC maps of the caller's
+# batch counts ENGINE frames (2 * Bsrc for a flip-test pair); word is what the messages call the source.
+_Source = collections.namedtuple("_Source", "kind device batch word data")
+
+
+def _require_cuda(dev):
+    if dev.type != "cuda":
+        raise CapfError("CA_PF runs on an MI355X only: inputs are on {} (no CPU fallback)".format(dev))
+
+
+def _run_backbone(owner, eng, src, stream):
+    """The backbone alone on an image source: its maps stay in the workspace (no gradient reaches it)."""
+    if src.kind == "u8":
+        eng.backbone_forward_u8(*src.data, stream)
+    elif owner._bn_batch_active():
+        owner._backbone_forward_bn(eng, src.data, stream)
+    else:
+        eng.backbone_forward(src.data, stream)
+
+
+def _run_source(owner, eng, src, k2d, kcrop, out, stream, train, masks=None):
+    """(source, training step?, batch statistics active?) -> engine calls: the one place that states this table, and with _run_backbone
+    the only caller of the engine's forward entries.  `train`: the native training step (activations kept for ONE backward)."""
+    if src.kind == "u8":            # the stem reads the crops (nothing in the backward reads the image)
+        if train:
+            eng.forward_train_u8(*src.data, k2d, kcrop, out, stream, masks)
+        else:
+            eng.forward_u8(*src.data, k2d, kcrop, out, stream)
+    elif src.kind == "images" and not owner._bn_batch_active():
+        if train:
+            eng.forward_train(src.data, k2d, kcrop, out, stream, masks)
+        else:
+            eng.forward(src.data, k2d, kcrop, out, stream)
+    else:                           # the lifter alone, on maps that ...
+        if src.kind == "images":    # ... the backbone makes with batch statistics (backbone_bn="batch", backbone in train mode)
+            owner._backbone_forward_bn(eng, src.data, stream)
+        elif src.kind == "maps":    # ... the caller supplies ("workspace": they are there)
+            eng.set_features(src.data, stream)
+        if train:
+            eng.lifter_forward_train(k2d, kcrop, out, stream, masks)
+        else:
+            eng.lifter_forward(k2d, kcrop, out, stream)
 
 
 def _private_ref(ctx, index, kcrop):
@@ -54,28 +86,25 @@ def _crop_grad(owner, dref):
 
 
 class _LifterStep(torch.autograd.Function):
-    """Autograd boundary of the native training step: forward = capf_forward_train, backward =
-    capf_backward into one flat gradient buffer whose slices are returned as the parameter gradients
-    (so torch optimizers, DDP hooks and `capf.dist.allreduce_mean_` all see ordinary .grad tensors).  When k2d or kcrop takes part in the
-    graph, backward = capf_backward_points and their gradients are returned too (kcrop's w.r.t. the pixel values the caller passed)."""
+    """Autograd boundary of the native training step on any source: forward = _run_source(..., train), backward = capf_backward into one flat
+    gradient buffer whose slices are returned as the parameter gradients (so torch optimizers, DDP hooks and `capf.dist.allreduce_mean_`
+    all see ordinary .grad tensors).  Caller-supplied maps travel as n_maps (0 or 4) leading tensor arguments, contiguous NHWC (the permute
+    from the backbone's NCHW, and its transpose on the way back, are torch's): backward = capf_backward_maps, which returns their gradient
+    too.  When k2d or kcrop takes part in the graph, backward = capf_backward_points and their gradients are returned as well (kcrop's
+    w.r.t. the pixel values the caller passed)."""
 
     @staticmethod
-    def forward(ctx, owner, eng, images, k2d, kcrop, masks, names, *params):
-        out = torch.empty(images.shape[0], 1, owner.num_joints, 3, dtype=torch.float32, device=images.device)
-        stream = torch.cuda.current_stream(images.device).cuda_stream
+    def forward(ctx, owner, eng, src, k2d, kcrop, masks, names, n_maps, *maps_and_params):
+        feats, params = maps_and_params[:n_maps], maps_and_params[n_maps:]
+        out = torch.empty(src.batch, 1, owner.num_joints, 3, dtype=torch.float32, device=src.device)
         kcrop = _private_ref(ctx, 4, kcrop)
-        if isinstance(images, _WorkspaceMaps):  # forward_detect: the backbone already ran; the maps of this batch are in the workspace
-            eng.lifter_forward_train(k2d, kcrop, out, stream, masks)
-        elif isinstance(images, _U8Images):   # the uint8 route: the same step, the stem reads the crops (nothing in the backward reads the image)
-            eng.forward_train_u8(images.crops, images.mean, images.std, images.mode, k2d, kcrop, out, stream, masks)
-        elif owner._bn_batch_active():        # backbone_bn="batch", backbone in train mode: batch statistics, then the same lifter step on its maps
-            owner._backbone_forward_bn(eng, images, stream)
-            eng.lifter_forward_train(k2d, kcrop, out, stream, masks)
-        else:
-            eng.forward_train(images, k2d, kcrop, out, stream, masks)
+        _run_source(owner, eng, src, k2d, kcrop, out, torch.cuda.current_stream(src.device).cuda_stream, True, masks)
         ctx.token = eng.train_generation()
-        ctx.eng, ctx.masks, ctx.names, ctx.owner = eng, masks, names, owner
-        ctx.keep = (k2d, kcrop)     # capf_backward re-reads the keypoints / normalised ref: keep them alive
+        ctx.eng, ctx.masks, ctx.names, ctx.owner, ctx.n_maps = eng, masks, names, owner, n_maps
+        if n_maps:
+            ctx.map_grad_mode = resolve_map_grad_mode(owner.map_grad_mode)      # (the step's mode is the one in force at its forward)
+        ctx.keep = (k2d, kcrop)     # the backward re-reads the keypoints / normalised ref: keep them alive
+        ctx.map_shapes = [f.shape for f in feats]
         ctx.shapes = [p.shape for p in params]
         return out
 
@@ -88,18 +117,25 @@ class _LifterStep(torch.autograd.Function):
                             "before the next forward of this model")
         layout, total = eng.grad_layout_cached()
         flat = torch.empty(total, dtype=torch.float32, device=grad_out.device)
+        dfeat = [torch.empty(shp, dtype=torch.float32, device=grad_out.device) for shp in ctx.map_shapes] if ctx.n_maps else None
         stream = torch.cuda.current_stream(grad_out.device).cuda_stream
+        if dfeat is not None and eng.map_grad_mode() != ctx.map_grad_mode:      # a state change of the handle: once per change, not per step
+            eng.set_map_grad_mode(ctx.map_grad_mode)
         need_k2d, need_ref = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
         dk2d = dkcrop = None
         if need_k2d or need_ref:
             dk2d = torch.empty_like(ctx.keep[0]) if need_k2d else None
             dref = torch.empty_like(ctx.keep[1]) if need_ref else None
-            eng.backward_points(grad_out.contiguous(), flat, stream, ctx.masks, None, dk2d, dref)
+            eng.backward_points(grad_out.contiguous(), flat, stream, ctx.masks, dfeat, dk2d, dref)
             dkcrop = _crop_grad(ctx.owner, dref) if need_ref else None
+        elif dfeat is not None:
+            eng.backward_maps(grad_out.contiguous(), flat, dfeat, stream, ctx.masks)
         else:
             eng.backward(grad_out.contiguous(), flat, stream, ctx.masks)
         ctx.owner.last_flat_grad = flat
-        head = (None, None, None, dk2d, dkcrop, None, None)
+        head = (None, None, None, dk2d, dkcrop, None, None, None)
+        if dfeat is not None:           # (map gradients only for maps that require grad)
+            head += tuple(g if need else None for g, need in zip(dfeat, ctx.needs_input_grad[8:8 + ctx.n_maps]))
         if ctx.owner.flat_grad_only:      # the caller consumes last_flat_grad itself (capf.optim.FusedAdamW + capf.dist)
             return head + (None,) * len(ctx.names)
         grads = tuple(flat[layout[n][0]: layout[n][0] + layout[n][1]].view(shp) for n, shp in zip(ctx.names, ctx.shapes))
@@ -181,59 +217,6 @@ def resolve_map_grad_mode(value):
     if not isinstance(value, str) or value not in MAP_GRAD_MODES:
         raise ValueError("map_grad_mode must be None, 'atomic' or 'ordered', got {!r}".format(value))
     return MAP_GRAD_MODES[value]
-
-
-class _FeatureStep(torch.autograd.Function):
-    """_LifterStep on caller-supplied context maps: forward = capf_set_features + capf_lifter_forward_train, backward =
-    capf_backward_maps, which returns the gradient w.r.t. the four maps next to the flat parameter gradient.  The maps arrive as
-    contiguous NHWC tensors (the permute from the backbone's NCHW, and its transpose on the way back, are torch's).  When k2d or kcrop takes
-    part in the graph, backward = capf_backward_points with the same four maps, and their gradients are returned too."""
-
-    @staticmethod
-    def forward(ctx, owner, eng, k2d, kcrop, masks, names, n_maps, *maps_and_params):
-        feats, params = maps_and_params[:n_maps], maps_and_params[n_maps:]
-        out = torch.empty(k2d.shape[0], 1, owner.num_joints, 3, dtype=torch.float32, device=k2d.device)
-        stream = torch.cuda.current_stream(k2d.device).cuda_stream
-        kcrop = _private_ref(ctx, 3, kcrop)
-        eng.set_features(feats, stream)
-        eng.lifter_forward_train(k2d, kcrop, out, stream, masks)
-        ctx.token = eng.train_generation()
-        ctx.eng, ctx.masks, ctx.names, ctx.owner, ctx.n_maps = eng, masks, names, owner, n_maps
-        ctx.map_grad_mode = resolve_map_grad_mode(owner.map_grad_mode)      # (the step's mode is the one in force at its forward)
-        ctx.keep = (k2d, kcrop)     # capf_backward_maps re-reads the keypoints / normalised ref: keep them alive
-        ctx.map_shapes = [f.shape for f in feats]
-        ctx.shapes = [p.shape for p in params]
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        eng = ctx.eng
-        if eng.train_generation() != ctx.token:
-            raise CapfError("backward of a CA_PF forward whose saved activations were overwritten by a later forward on the "
-                            "same engine (the native step keeps ONE set of activations in its workspace): call backward "
-                            "before the next forward of this model")
-        layout, total = eng.grad_layout_cached()
-        flat = torch.empty(total, dtype=torch.float32, device=grad_out.device)
-        dfeat = [torch.empty(shp, dtype=torch.float32, device=grad_out.device) for shp in ctx.map_shapes]
-        stream = torch.cuda.current_stream(grad_out.device).cuda_stream
-        if eng.map_grad_mode() != ctx.map_grad_mode:      # a state change of the handle: once per change, not per step
-            eng.set_map_grad_mode(ctx.map_grad_mode)
-        need_k2d, need_ref = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        dk2d = dkcrop = None
-        if need_k2d or need_ref:
-            dk2d = torch.empty_like(ctx.keep[0]) if need_k2d else None
-            dref = torch.empty_like(ctx.keep[1]) if need_ref else None
-            eng.backward_points(grad_out.contiguous(), flat, stream, ctx.masks, dfeat, dk2d, dref)
-            dkcrop = _crop_grad(ctx.owner, dref) if need_ref else None
-        else:
-            eng.backward_maps(grad_out.contiguous(), flat, dfeat, stream, ctx.masks)
-        ctx.owner.last_flat_grad = flat
-        head = (None, None, dk2d, dkcrop, None, None, None)
-        dmaps = tuple(g if need else None for g, need in zip(dfeat, ctx.needs_input_grad[7:7 + ctx.n_maps]))
-        if ctx.owner.flat_grad_only:      # the caller consumes last_flat_grad itself (capf.optim.FusedAdamW + capf.dist)
-            return head + dmaps + (None,) * len(ctx.names)
-        grads = tuple(flat[layout[n][0]: layout[n][0] + layout[n][1]].view(shp) for n, shp in zip(ctx.names, ctx.shapes))
-        return head + dmaps + grads
 
 
 class CA_PF(nn.Module):
@@ -358,8 +341,7 @@ class CA_PF(nn.Module):
 
     def _engine(self, images):
         dev = images.device
-        if dev.type != "cuda":
-            raise CapfError("CA_PF runs on an MI355X only: inputs are on {} (no CPU fallback)".format(dev))
+        _require_cuda(dev)
         B, H, W, C = images.shape
         if C != 3:
             raise ValueError("images must be [B,H,W,3] NHWC")
@@ -424,9 +406,10 @@ class CA_PF(nn.Module):
             return t.contiguous(), False
         return (t if t.is_contiguous() else t.contiguous()), True
 
-    def _lifter_step_params(self, keypoint_grads):
+    def _lifter_step_params(self, input_grads):
         """[(name, parameter)] of volume_net when this call runs the native training step (None: the plain forward): grad mode on and
-        either the lifter trains or a keypoint tensor needs its gradient (then with a frozen lifter: no parameter gradients)."""
+        either the lifter trains or an input (a keypoint tensor, a context map) needs its gradient (then with a frozen lifter: no
+        parameter gradients)."""
         if not torch.is_grad_enabled():
             return None
         named = [(n, p) for n, p in self.volume_net.named_parameters()]
@@ -434,7 +417,52 @@ class CA_PF(nn.Module):
             if not all(p.requires_grad for _, p in named):
                 raise NotImplementedError("partially frozen volume_net is not supported by the native backward")
             return named
-        return [] if keypoint_grads else None
+        return [] if input_grads else None
+
+    # ---- what every entry ends in ---------------------------------------------------------------------
+    def _image_source(self, images, mode=0):
+        """The source record of [B,H,W,3] images: fp32, or uint8 BGR crops with the configured backbone's normalisation constants and
+        capf_preprocess's mode."""
+        if images.dtype != torch.uint8:
+            return _Source("images", images.device, images.shape[0], "images", images)
+        mean, std = input_constants("cpn" if self._backbone_type == "cpn" else "hrnet_32")
+        return _Source("u8", images.device, images.shape[0] * (2 if mode == 2 else 1), "images", (images, mean, std, mode))
+
+    def _run_lifter(self, eng, src, k2d, kcrop, named):
+        """The native training step on `named` (_lifter_step_params) or, with None, the plain call; returns joints3d [B,1,J,3]."""
+        if named is None:
+            out = torch.empty(src.batch, 1, self.num_joints, 3, dtype=torch.float32, device=src.device)
+            _run_source(self, eng, src, k2d, kcrop, out, torch.cuda.current_stream(src.device).cuda_stream, False)
+            return out
+        names = tuple("volume_net." + n for n, _ in named)
+        maps = src.data if src.kind == "maps" else ()
+        return _LifterStep.apply(self, eng, src, k2d, kcrop, self._drop_masks(src.batch, src.device), names, len(maps), *maps,
+                                 *[p for _, p in named])
+
+    def _lift(self, src, crop_size, keypoints_2d_cpn, keypoints_2d_cpn_crop, input_grads):
+        """The shared end of forward / forward_u8 / forward_features: the keypoint checks, the engine of crop_size = (H, W), the lifter
+        on the source's maps as a training step or a plain call, and the normalised crop keypoints written back."""
+        B, dev = src.batch, src.device
+        for name, t in (("keypoints_2d_cpn", keypoints_2d_cpn), ("keypoints_2d_cpn_crop", keypoints_2d_cpn_crop)):
+            if t.dtype != torch.float32:
+                raise TypeError("{} must be float32, got {}".format(name, t.dtype))
+            if t.device != dev:
+                raise ValueError("{} is on {} but {} are on {}".format(name, t.device, src.word, dev))
+            if tuple(t.shape) != (B, self.num_joints, 2):
+                pair = src.kind == "u8" and src.data[3] == 2
+                raise ValueError("{} must have shape ({}, {}, 2){}, got {}".format(
+                    name, B, self.num_joints, " for mirror='pair' (two sets of {} frames)".format(B // 2) if pair else "", tuple(t.shape)))
+        with torch.cuda.device(dev):
+            eng = self._engine(src.data) if crop_size is None else self._engine_at(dev, *crop_size)
+            k2d = keypoints_2d_cpn.contiguous()
+            # the third argument is normalised IN PLACE (conpose.py:34-35); a non-contiguous view (which the reference
+            # accepts) goes through a contiguous staging copy that is written back
+            kcrop, write_back = self._crop_buffer(keypoints_2d_cpn_crop)
+            out = self._run_lifter(eng, src, k2d, kcrop, self._lifter_step_params(input_grads))
+            if write_back and kcrop is not keypoints_2d_cpn_crop:
+                with torch.no_grad():
+                    keypoints_2d_cpn_crop.copy_(kcrop)
+        return out
 
     # ---- conpose.py:30-42 --------------------------------------------------------------------
     def forward(self, images, keypoints_2d_cpn, keypoints_2d_cpn_crop):
@@ -444,40 +472,11 @@ class CA_PF(nn.Module):
         kp_grads = self._keypoint_grads(keypoints_2d_cpn, keypoints_2d_cpn_crop)
         if images.dtype != torch.float32:
             raise TypeError("images must be float32")
-        if images.device.type != "cuda":
-            raise CapfError("CA_PF runs on an MI355X only: inputs are on {} (no CPU fallback)".format(images.device))
+        _require_cuda(images.device)
         images = images.contiguous()
-        B = images.shape[0]
-        for name, t in (("keypoints_2d_cpn", keypoints_2d_cpn), ("keypoints_2d_cpn_crop", keypoints_2d_cpn_crop)):
-            if t.dtype != torch.float32:
-                raise TypeError("{} must be float32, got {}".format(name, t.dtype))
-            if t.device != images.device:
-                raise ValueError("{} is on {} but images are on {}".format(name, t.device, images.device))
-            if tuple(t.shape) != (B, self.num_joints, 2):
-                raise ValueError("{} must have shape ({}, {}, 2), got {}".format(name, B, self.num_joints, tuple(t.shape)))
-        with torch.cuda.device(images.device):
-            eng = self._engine(images)
-            k2d = keypoints_2d_cpn.contiguous()
-            # the third argument is normalised IN PLACE (conpose.py:34-35); a non-contiguous view (which the reference
-            # accepts) goes through a contiguous staging copy that is written back
-            kcrop, write_back = self._crop_buffer(keypoints_2d_cpn_crop)
-            stream = torch.cuda.current_stream(images.device).cuda_stream
-            named = self._lifter_step_params(kp_grads)
-            if named is not None:
-                names = tuple("volume_net." + n for n, _ in named)
-                out = _LifterStep.apply(self, eng, images, k2d, kcrop, self._drop_masks(B, images.device),
-                                        names, *[p for _, p in named])
-            else:
-                out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=images.device)
-                if self._bn_batch_active():
-                    self._backbone_forward_bn(eng, images, stream)
-                    eng.lifter_forward(k2d, kcrop, out, stream)
-                else:
-                    eng.forward(images, k2d, kcrop, out, stream)
-            if write_back and kcrop is not keypoints_2d_cpn_crop:
-                with torch.no_grad():
-                    keypoints_2d_cpn_crop.copy_(kcrop)
-        return out
+        # (crop size None: _engine reads it off the images, with its [B,H,W,3] refusal behind the keypoint checks)
+        return self._lift(_Source("images", images.device, images.shape[0], "images", images), None,
+                          keypoints_2d_cpn, keypoints_2d_cpn_crop, kp_grads)
 
     # ---- the same forward from uint8 crops: normalisation, BGR flip and mirror in the stem conv's load (capf_forward_u8) ----------
     def forward_u8(self, images_u8, keypoints_2d_cpn, keypoints_2d_cpn_crop, mirror="none"):
@@ -488,7 +487,6 @@ class CA_PF(nn.Module):
         capf_preprocess mode 2's layout ([2,B,17,2] flattened: capf.lib.preprocess_points) and the result is [2B,1,17,3].  The keypoints
         are NOT mirrored here (preprocess_points does that); the third argument is normalised in place like forward's.  Under grad the
         native training step runs.  Every result bit equals forward() on capf.lib.preprocess()'s images."""
-        from capf.lib import input_constants
         if not isinstance(mirror, str) or mirror not in MIRROR_MODES:
             raise ValueError("mirror must be 'none', 'all' or 'pair', got {!r}".format(mirror))
         mode = MIRROR_MODES[mirror]
@@ -498,41 +496,12 @@ class CA_PF(nn.Module):
                                       "call backbone.eval(), or forward() on capf.lib.preprocess()'s fp32 images")
         if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8:
             raise TypeError("images_u8 must be uint8, got {}".format(getattr(images_u8, "dtype", type(images_u8))))
-        if images_u8.device.type != "cuda":
-            raise CapfError("CA_PF runs on an MI355X only: inputs are on {} (no CPU fallback)".format(images_u8.device))
+        _require_cuda(images_u8.device)
         if images_u8.dim() != 4 or images_u8.shape[3] != 3:
             raise ValueError("images_u8 must be [B,H,W,3] NHWC, got {}".format(tuple(images_u8.shape)))
         if not images_u8.is_contiguous():
             raise ValueError("images_u8 must be contiguous (a copy would be the image round trip this entry removes)")
-        dev = images_u8.device
-        Bsrc, H, W, _ = images_u8.shape
-        B = 2 * Bsrc if mode == 2 else Bsrc
-        for name, t in (("keypoints_2d_cpn", keypoints_2d_cpn), ("keypoints_2d_cpn_crop", keypoints_2d_cpn_crop)):
-            if t.dtype != torch.float32:
-                raise TypeError("{} must be float32, got {}".format(name, t.dtype))
-            if t.device != dev:
-                raise ValueError("{} is on {} but images are on {}".format(name, t.device, dev))
-            if tuple(t.shape) != (B, self.num_joints, 2):
-                raise ValueError("{} must have shape ({}, {}, 2){}, got {}".format(
-                    name, B, self.num_joints, " for mirror='pair' (two sets of {} frames)".format(Bsrc) if mode == 2 else "", tuple(t.shape)))
-        mean, std = input_constants("cpn" if self._backbone_type == "cpn" else "hrnet_32")
-        with torch.cuda.device(dev):
-            eng = self._engine_at(dev, H, W)
-            k2d = keypoints_2d_cpn.contiguous()
-            kcrop, write_back = self._crop_buffer(keypoints_2d_cpn_crop)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            named = self._lifter_step_params(kp_grads)
-            if named is not None:
-                names = tuple("volume_net." + n for n, _ in named)
-                out = _LifterStep.apply(self, eng, _U8Images(images_u8, mean, std, mode), k2d, kcrop, self._drop_masks(B, dev),
-                                        names, *[p for _, p in named])
-            else:
-                out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=dev)
-                eng.forward_u8(images_u8, mean, std, mode, k2d, kcrop, out, stream)
-            if write_back and kcrop is not keypoints_2d_cpn_crop:
-                with torch.no_grad():
-                    keypoints_2d_cpn_crop.copy_(kcrop)
-        return out
+        return self._lift(self._image_source(images_u8, mode), images_u8.shape[1:3], keypoints_2d_cpn, keypoints_2d_cpn_crop, kp_grads)
 
     # ---- detector-free: the 2-D keypoints from the native head on feat0 -------------------------
     def _head_params(self):
@@ -558,8 +527,7 @@ class CA_PF(nn.Module):
     def _detect_inputs(self, images, to_image):
         if not torch.is_tensor(images) or images.dtype not in (torch.float32, torch.uint8):
             raise TypeError("images must be float32 or uint8, got {}".format(getattr(images, "dtype", type(images))))
-        if images.device.type != "cuda":
-            raise CapfError("CA_PF runs on an MI355X only: inputs are on {} (no CPU fallback)".format(images.device))
+        _require_cuda(images.device)
         if images.dim() != 4 or images.shape[3] != 3:
             raise ValueError("images must be [B,H,W,3] NHWC, got {}".format(tuple(images.shape)))
         if images.dtype == torch.uint8 and self._bn_batch_active():
@@ -577,14 +545,7 @@ class CA_PF(nn.Module):
 
     def _backbone_maps(self, eng, images, stream):
         """One backbone pass (no gradient reaches it); returns feat0 as a view of the engine's workspace, NHWC in the plan's dtype."""
-        if images.dtype == torch.uint8:
-            from capf.lib import input_constants
-            mean, std = input_constants("cpn" if self._backbone_type == "cpn" else "hrnet_32")
-            eng.backbone_forward_u8(images, mean, std, 0, stream)
-        elif self._bn_batch_active():
-            self._backbone_forward_bn(eng, images, stream)
-        else:
-            eng.backbone_forward(images, stream)
+        _run_backbone(self, eng, self._image_source(images), stream)
         return eng.tensor_view("feat0", images.shape[0])
 
     def _run_head(self, eng, feat0, to_image, H, W, trains):
@@ -634,16 +595,11 @@ class CA_PF(nn.Module):
             with torch.no_grad():
                 feat0 = self._backbone_maps(eng, images, stream)
             kcrop, score, k2d, guard = self._run_head(eng, feat0, to_image, H, W, trains)
-            if named is not None:
-                names = tuple("volume_net." + n for n, _ in named)
-                # (a crop-keypoint tensor outside the graph would be normalised in place by the step: it gets a copy, the caller the pixels)
-                out = _LifterStep.apply(self, eng, _WorkspaceMaps(B, dev), k2d, kcrop if kcrop.requires_grad else kcrop.clone(),
-                                        self._drop_masks(B, dev), names, *[p for _, p in named])
-                if guard is not None:
-                    guard["token"] = eng.train_generation()
-            else:
-                out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=dev)
-                eng.lifter_forward(k2d, kcrop.detach().clone(), out, stream)
+            # (a crop-keypoint tensor outside the graph would be normalised in place by the lifter: it gets a copy, the caller the pixels)
+            ref = kcrop.detach().clone() if named is None else kcrop if kcrop.requires_grad else kcrop.clone()
+            out = self._run_lifter(eng, _Source("workspace", dev, B, "the maps", None), k2d, ref, named)
+            if named is not None and guard is not None:
+                guard["token"] = eng.train_generation()
         return out, kcrop, score
 
     # ---- conpose.py:40 on maps of the caller's own backbone ------------------------------------
@@ -693,38 +649,10 @@ class CA_PF(nn.Module):
                 raise ValueError("features_list[{}] is on {} but features_list[0] is on {} (maps are NCHW {})".format(
                     l, f.device, feats[0].device, want))
         dev = feats[0].device
-        if dev.type != "cuda":
-            raise CapfError("CA_PF runs on an MI355X only: inputs are on {} (no CPU fallback)".format(dev))
-        for name, t in (("keypoints_2d_cpn", keypoints_2d_cpn), ("keypoints_2d_cpn_crop", keypoints_2d_cpn_crop)):
-            if t.dtype != torch.float32:
-                raise TypeError("{} must be float32, got {}".format(name, t.dtype))
-            if t.device != dev:
-                raise ValueError("{} is on {} but the maps are on {}".format(name, t.device, dev))
-            if tuple(t.shape) != (B, self.num_joints, 2):
-                raise ValueError("{} must have shape ({}, {}, 2), got {}".format(name, B, self.num_joints, tuple(t.shape)))
-        with torch.cuda.device(dev):
-            eng = self._engine_at(dev, H, W)
-            k2d = keypoints_2d_cpn.contiguous()
-            kcrop, write_back = self._crop_buffer(keypoints_2d_cpn_crop)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            nhwc = [f.permute(0, 2, 3, 1).contiguous() for f in feats]
-            named = [(n, p) for n, p in self.volume_net.named_parameters()]
-            train_lifter = any(p.requires_grad for _, p in named)
-            if torch.is_grad_enabled() and (train_lifter or kp_grads or any(f.requires_grad for f in feats)):
-                if train_lifter and not all(p.requires_grad for _, p in named):
-                    raise NotImplementedError("partially frozen volume_net is not supported by the native backward")
-                if not train_lifter:
-                    named = []
-                names = tuple("volume_net." + n for n, _ in named)
-                out = _FeatureStep.apply(self, eng, k2d, kcrop, self._drop_masks(B, dev), names, 4, *nhwc, *[p for _, p in named])
-            else:
-                out = torch.empty(B, 1, self.num_joints, 3, dtype=torch.float32, device=dev)
-                eng.set_features(nhwc, stream)
-                eng.lifter_forward(k2d, kcrop, out, stream)
-            if write_back and kcrop is not keypoints_2d_cpn_crop:
-                with torch.no_grad():
-                    keypoints_2d_cpn_crop.copy_(kcrop)
-        return out
+        _require_cuda(dev)
+        map_grads = torch.is_grad_enabled() and any(f.requires_grad for f in feats)
+        nhwc = [f.permute(0, 2, 3, 1).contiguous() for f in feats]
+        return self._lift(_Source("maps", dev, B, "the maps", nhwc), (H, W), keypoints_2d_cpn, keypoints_2d_cpn_crop, kp_grads or map_grads)
 
     def _drop_masks(self, B, device):
         """DropPath multipliers for one training step (timm semantics: keep-mask / keep_prob per sample;

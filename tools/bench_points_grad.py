@@ -7,7 +7,7 @@ only reads them), each call bracketed by device events; medians and (max - min) 
     backward              capf_backward
     backward_maps         capf_backward_maps (the handle's map-gradient mode: atomic unless --ordered)
     backward_points       capf_backward_points with all three outputs (the four maps, dk2d, dref)
-    backward_points_kp    capf_backward_points with dk2d and dref only (what _LifterStep runs: no map gradient)
+    backward_points_kp    capf_backward_points with dk2d and dref only (what _LifterStep runs on an image source: no map gradient)
 
     python tools/bench_points_grad.py [--batches 64 512] [--repeats 20] [--warmup 3] [--ordered]        (needs the MI355X)
 
