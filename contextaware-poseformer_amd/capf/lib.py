@@ -42,6 +42,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_backbone_forward_bn", "capf_op_bn_stats_scratch_bytes", "capf_op_bn_stats", "capf_op_bn_apply",
     "capf_backward_points",
     "capf_kp_head_scratch_bytes", "capf_kp_head_forward", "capf_kp_head_backward",
+    "capf_kp_head_pair_scratch_bytes", "capf_kp_head_forward_pair",
 ]
 
 
@@ -254,6 +255,9 @@ def load_library():
     lib.capf_kp_head_scratch_bytes.restype = c_size_t
     lib.capf_kp_head_forward.argtypes = [P, P, c_int, P, P] + [c_int] * 6 + [c_float, F3, P, P, P, P, P, P, c_size_t]
     lib.capf_kp_head_backward.argtypes = [P, P, P, P, c_int, P, P] + [c_int] * 6 + [c_float, F3, P, P, P, P, c_int, P, c_size_t]
+    lib.capf_kp_head_pair_scratch_bytes.argtypes = [c_int] * 5
+    lib.capf_kp_head_pair_scratch_bytes.restype = c_size_t
+    lib.capf_kp_head_forward_pair.argtypes = [P, P, c_int, P, P] + [c_int] * 6 + [c_float, POINTER(c_int32), c_int, F3, P, c_float, P, P, P, P, P, c_size_t]
     _lib = lib
     return lib
 
@@ -1090,6 +1094,50 @@ def kp_head_backward(x, weight, bias=None, dkcrop=None, dk2d=None, beta=1.0, dec
     _call("capf_kp_head_backward", _stream(x), _p(dkcrop), _p(dk2d), _p(x), dtype, _p(w), _p(bias), B, H, W, C, J, KP_INTEGRAL, float(beta),
           dec, _p(to_image), _p(dw), _p(db), _p(dmap), 1 if accumulate else 0, _p(scratch), nbytes)
     return dw, db, dmap
+
+
+# the H36M skeleton's mirror table: joints_left [4, 5, 6, 11, 12, 13] <-> joints_right [1, 2, 3, 14, 15, 16] (mvn/datasets/utils.py:12-13;
+# kSwap of csrc/preprocess.hip, the table capf_fliptest_fuse and capf_preprocess_points apply)
+H36M_SWAP = (0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13)
+
+
+def kp_head_forward_pair(x2, weight, bias=None, mode=KP_ARGMAX, beta=1.0, swap=None, shift=True, decode=(1.0, 0.0, 1.0, 0.0), to_image=None,
+                         mirror_width=192.0, want_score=True, want_heat=False):
+    """capf_kp_head_forward_pair on the contiguous NHWC map x2 [2 * Bsrc, H, W, C] of a flip-test pair (frame Bsrc + b the mirror of frame b,
+    the order of capf_preprocess mode 2): the heatmaps of each crop and of its flipped-back mirror are averaged (`shift`: HRNet's one-column
+    SHIFT_HEATMAP) and decoded once.  swap: J ints, swap[j] = the joint of the mirror that lands on joint j, its own inverse; None: H36M_SWAP
+    (J = 17 only).  to_image [Bsrc, 2, 3].  Returns (kcrop2 [2, Bsrc, J, 2], score [Bsrc, J] | None, k2d2 [2, Bsrc, J, 2] | None,
+    heat [Bsrc, J, H, W] | None -- the fused logits): kcrop2 / k2d2 are the stacks forward_flip_test takes, set 1 mirrored like
+    preprocess_points(mode=2) with `mirror_width` in place of its 192."""
+    import torch
+    dtype = _kp_map_dtype(x2)
+    if x2.shape[0] % 2:
+        raise CapfError(f"a flip-test pair holds 2 * Bsrc frames ([orig | mirrored]), not {x2.shape[0]}")
+    Bsrc, H, W, C = x2.shape[0] // 2, x2.shape[1], x2.shape[2], x2.shape[3]
+    w = weight.reshape(weight.shape[0], -1)
+    if w.shape[1] != C or w.dtype != torch.float32 or not w.is_contiguous():
+        raise CapfError(f"the keypoint head's weight must be contiguous fp32 [J, {C}] (or [J, {C}, 1, 1]), not {tuple(weight.shape)} {weight.dtype}")
+    J = w.shape[0]
+    if swap is None:
+        if J != 17:
+            raise CapfError(f"swap=None means the H36M table (17 joints); a head of {J} joints needs its own table")
+        swap = H36M_SWAP
+    tab = [int(v) for v in swap]
+    if len(tab) != J:
+        raise CapfError(f"swap has {len(tab)} entries for {J} joints")
+    if to_image is not None and (tuple(to_image.shape) != (Bsrc, 2, 3) or to_image.dtype != torch.float32 or not to_image.is_contiguous()):
+        raise CapfError(f"to_image must be contiguous fp32 [{Bsrc}, 2, 3], not {tuple(to_image.shape)} {to_image.dtype}")
+    nbytes = load_library().capf_kp_head_pair_scratch_bytes(Bsrc, H, W, C, J)
+    scratch = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x2.device)
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x2.device)
+    kcrop2 = new(2, Bsrc, J, 2)
+    k2d2 = new(2, Bsrc, J, 2) if to_image is not None else None
+    score = new(Bsrc, J) if want_score else None
+    heat = new(Bsrc, J, H, W) if want_heat else None
+    _call("capf_kp_head_forward_pair", _stream(x2), _p(x2), dtype, _p(w), _p(bias), Bsrc, H, W, C, J, int(mode), float(beta), (c_int32 * J)(*tab),
+          1 if shift else 0, (c_float * 4)(*[float(v) for v in decode]), _p(to_image), float(mirror_width), _p(kcrop2), _p(k2d2), _p(score),
+          _p(heat), _p(scratch), nbytes)
+    return kcrop2, score, k2d2, heat
 
 
 def linear_bf16(x, w, bias=None, residual=None, gelu=False):

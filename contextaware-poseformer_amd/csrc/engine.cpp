@@ -1702,6 +1702,29 @@ int capf_kp_head_forward(void* stream, const void* map_nhwc, int map_dtype, cons
     return capf::launch_kp_head_forward(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
+// the flip-test pair: the map holds 2 * Bsrc frames, everything else is sized by Bsrc
+size_t capf_kp_head_pair_scratch_bytes(int Bsrc, int H, int W, int C, int J) {
+    if (Bsrc > (1 << 30)) return 0;                                                         // (frame Bsrc + b is an int)
+    return capf_kp_head_scratch_bytes(Bsrc, H, W, C, J, 0);
+}
+
+int capf_kp_head_forward_pair(void* stream, const void* map_nhwc, int map_dtype, const float* weight, const float* bias, int Bsrc, int H, int W,
+                              int C, int J, int mode, float beta, const int32_t* swap, int shift, const float decode[4], const float* to_image,
+                              float mirror_width, float* kcrop2, float* k2d2, float* score, float* heat, void* scratch, size_t scratch_bytes) {
+    if (!kcrop2 || !swap || (k2d2 && !to_image) || (shift != 0 && shift != 1) || !std::isfinite(mirror_width) || Bsrc > (1 << 30)) return CAPF_ERR_INVALID;
+    if (const int rc = kp_head_check(map_nhwc, map_dtype, weight, Bsrc, H, W, C, J, mode, beta, decode, scratch, scratch_bytes, 0)) return rc;
+    capf::KpPairArgs a{};
+    for (int j = 0; j < J; ++j) {              // a permutation that is its own inverse (capf_fliptest_fuse_swap's rule)
+        if (swap[j] < 0 || swap[j] >= J || swap[swap[j]] != j) return CAPF_ERR_INVALID;
+        a.swap.j[j] = swap[j];
+    }
+    a.x = map_nhwc; a.dtype = map_dtype; a.wt = weight; a.bias = bias; a.to_image = to_image;
+    a.kcrop = kcrop2; a.k2d = to_image ? k2d2 : nullptr; a.score = score; a.heat = heat; a.part = static_cast<float*>(scratch);
+    a.B = Bsrc; a.H = H; a.W = W; a.C = C; a.J = J; a.mode = mode; a.beta = beta; a.shift = shift; a.mirror_w = mirror_width;
+    for (int i = 0; i < 4; ++i) a.dec[i] = decode[i];
+    return capf::launch_kp_head_forward_pair(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+}
+
 int capf_kp_head_backward(void* stream, const float* dkcrop, const float* dk2d, const void* map_nhwc, int map_dtype, const float* weight,
                           const float* bias, int B, int H, int W, int C, int J, int mode, float beta, const float decode[4],
                           const float* to_image, float* dweight, float* dbias, float* dmap, int accumulate, void* scratch, size_t scratch_bytes) {

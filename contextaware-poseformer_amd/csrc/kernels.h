@@ -774,5 +774,15 @@ struct KpHeadArgs {
 };
 hipError_t launch_kp_head_forward(KpHeadArgs a, hipStream_t s);
 hipError_t launch_kp_head_backward(KpHeadArgs a, hipStream_t s);
+// the flip-test pair (capf_kp_head_forward_pair): x holds [2 B, H, W, C], frame B + b the mirror of source frame b; B counts SOURCE frames
+// (grids, scratch and to_image [B, 2, 3] are the single entry's at B); kcrop / k2d are the stacks [2, B, J, 2], score [B, J], heat
+// [B, J, H, W] the fused logits.  Forward only.
+struct KpSwap { int j[KP_MAX_JOINTS]; };     // swap[j] = the joint of the mirror whose heatmap lands on joint j; travels in the kernel arguments
+struct KpPairArgs : KpHeadArgs {
+    KpSwap swap;
+    int shift;               // 1: HRNet's SHIFT_HEATMAP (the flipped-back heatmap moved one column to the right, column 0 kept)
+    float mirror_w;          // kcrop2[1].x = (mirror_w - x) - 1
+};
+hipError_t launch_kp_head_forward_pair(KpPairArgs a, hipStream_t s);
 
 }  // namespace capf

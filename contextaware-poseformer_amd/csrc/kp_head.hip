@@ -15,6 +15,11 @@
 //            (frame, slab, joint) goes to the scratch.  The heatmaps never reach memory.
 //   combine  one thread per (frame, joint) folds the slabs in ascending order, decodes, and writes kcrop / k2d / score.  The argmax's quarter
 //            shift recomputes the winner's four neighbours from the map (4 C values per joint; the only second read).
+// Flip-test pair (capf_kp_head_forward_pair), the PAIR instantiations of the same two kernels: the map holds [2 B] frames, frame B + b the mirror of
+//   frame b.  slab: after its own pixel's logits, thread t computes those of the mirror frame's pixel that flip_back + SHIFT_HEATMAP put on pixel t
+//   (same row, column kp_mirror_col; 256-pixel tiles are not row-aligned, so it lies in another tile and is read from memory) and folds them into its
+//   OWN LDS column at swap[j]: zf = 0.5 (zo + zm).  No extra barrier, no runtime-indexed registers; the walk, the merges and the records are the
+//   single form's.  combine: the quarter shift's neighbours are fused logits recomputed from both frames; both sets of the [2, B, J, 2] stacks.
 // Backward (integral, fp32 map), four launches: slab + combine as above leave (max, sum, x, y) per (frame, joint) in the scratch; kp_bwd_kernel
 // recomputes the logits tile by tile, forms dz in LDS, writes dmap (every element by one thread) and adds per-block partials of dW = sum dz X
 // (pixels ascending inside a tile, tiles ascending inside a block); kp_dw_reduce_kernel sums the partials (part q of 16 takes blocks
@@ -128,13 +133,24 @@ __device__ __forceinline__ void kp_run_merge(KpRun& r, const KpRun& o) {
     }
 }
 
-template <class L, int MODE>
-__global__ void __launch_bounds__(KP_THREADS) kp_fwd_slab_kernel(const KpHeadArgs a) {
+// the column of the mirror frame whose logit the flip test puts on column x: flip_back mirrors in x, SHIFT_HEATMAP then moves the flipped-back
+// heatmap one column to the right (column 0 keeps its own value)
+__device__ __forceinline__ int kp_mirror_col(const int x, const int W, const int shift) { return W - 1 - (shift && x >= 1 ? x - 1 : x); }
+
+template <bool PAIR> struct KpArgsOf { typedef KpHeadArgs type; };
+template <> struct KpArgsOf<true> { typedef KpPairArgs type; };
+
+// PAIR: the tile holds the FUSED logits of source frame b, zf = 0.5 (zo + zm) -- thread t adds, into its own LDS column, the logits of the
+// pixel of frame B + b that the flip test puts on pixel t (joint js of the mirror lands on joint swap[js]); nobody else touches that column,
+// so the fold needs no barrier.  Everything after it is the single decode.
+template <class L, int MODE, bool PAIR>
+__global__ void __launch_bounds__(KP_THREADS) kp_fwd_slab_kernel(const typename KpArgsOf<PAIR>::type a) {
     __shared__ float zs[KP_MAX_JOINTS * KP_ZS];
     const int tid = threadIdx.x;
     const int b = (int)blockIdx.x / a.g.nslab, s = (int)blockIdx.x - b * a.g.nslab;
     const int HW = a.H * a.W, J = a.J;
     const typename L::T* __restrict__ xb = static_cast<const typename L::T*>(a.x) + (size_t)b * HW * a.C;
+    const typename L::T* __restrict__ xm = xb + (size_t)a.B * HW * a.C;        // (PAIR) frame B + b
     const int jl = tid >> 3, l = tid & 7;
     KpRun r = kp_run_init();
     const int t0 = s * a.g.slab_tiles;
@@ -148,8 +164,21 @@ __global__ void __launch_bounds__(KP_THREADS) kp_fwd_slab_kernel(const KpHeadArg
             for (int j = 0; j < KP_MAX_JOINTS; ++j) {
                 if (j < J) {
                     zs[j * KP_ZS + tid] = acc[j];
-                    if (a.heat) a.heat[((size_t)b * J + j) * HW + pix] = acc[j];
+                    if (!PAIR && a.heat) a.heat[((size_t)b * J + j) * HW + pix] = acc[j];
                 }
+            }
+            if constexpr (PAIR) {
+                const int row = pix / a.W, col = pix - row * a.W;
+                kp_logits<L>(xm + ((size_t)row * a.W + kp_mirror_col(col, a.W, a.shift)) * a.C, a.wt, a.bias, a.C, J, acc);
+#pragma unroll
+                for (int js = 0; js < KP_MAX_JOINTS; ++js) {
+                    if (js < J) {
+                        float* z = zs + a.swap.j[js] * KP_ZS + tid;
+                        *z = __fmul_rn(0.5f, __fadd_rn(*z, acc[js]));  // the fp32 sum rounded once, then halved
+                    }
+                }
+                if (a.heat)
+                    for (int j = 0; j < J; ++j) a.heat[((size_t)b * J + j) * HW + pix] = zs[j * KP_ZS + tid];
             }
         }
         __syncthreads();
@@ -180,6 +209,20 @@ __global__ void __launch_bounds__(KP_THREADS) kp_fwd_slab_kernel(const KpHeadArg
         }
         __syncthreads();
     }
+    if constexpr (PAIR) {
+        // with the shift no pixel reads the mirror's column 0, and its logits still count for the NaN rule: the joint's lanes recompute
+        // those of the rows that start inside this slab
+        if (a.shift && a.W > 1 && jl < J) {
+            const int js = a.swap.j[jl];
+            const float* w = a.wt + (size_t)js * a.C;
+            const float bj = a.bias ? a.bias[js] : 0.f;
+            const int p1 = t1 * KP_THREADS < HW ? t1 * KP_THREADS : HW;
+            for (int row = (t0 * KP_THREADS + a.W - 1) / a.W + l; row * a.W < p1; row += 8) {
+                const float z = kp_logit1<L>(xm + (size_t)row * a.W * a.C, w, bj, a.C);
+                if (z != z) r.nan = 1;
+            }
+        }
+    }
     // the 8 lanes of a joint, ascending (every thread takes part in the shuffles)
     KpRun tot = r;
     for (int q = 1; q < 8; ++q) {
@@ -195,8 +238,45 @@ __global__ void __launch_bounds__(KP_THREADS) kp_fwd_slab_kernel(const KpHeadArg
     }
 }
 
-template <class L, int MODE>
-__global__ void __launch_bounds__(KP_THREADS) kp_fwd_combine_kernel(const KpHeadArgs a) {
+// one fused logit of the pair, from the map: the expression of the slab kernel's fold
+template <class L>
+__device__ __forceinline__ float kp_pair_logit1(const KpPairArgs& a, const int b, const int j, const int py, const int px) {
+    const typename L::T* x = static_cast<const typename L::T*>(a.x);
+    const size_t HW = (size_t)a.H * a.W;
+    const int js = a.swap.j[j];
+    const float zo = kp_logit1<L>(x + ((size_t)b * HW + (size_t)py * a.W + px) * a.C, a.wt + (size_t)j * a.C, a.bias ? a.bias[j] : 0.f, a.C);
+    const float zm = kp_logit1<L>(x + ((size_t)(a.B + b) * HW + (size_t)py * a.W + kp_mirror_col(px, a.W, a.shift)) * a.C,
+                                  a.wt + (size_t)js * a.C, a.bias ? a.bias[js] : 0.f, a.C);
+    return __fmul_rn(0.5f, __fadd_rn(zo, zm));
+}
+
+// The pair's outputs from the decoded heatmap coordinates (x, y) of (b, j): both sets of the stacks -- the thread also fills joint swap[j] of
+// the mirrored set, and swap is a permutation, so every element has one writer.  Every operation is rounded on its own, as capf.h writes the
+// expressions: __fmul_rn / __fadd_rn are plain operators to this compiler, which contracts A00 kx + A01 ky of the single form below into an
+// fma (that form keeps the code it always had); here contraction is off, so k2d2[0] is the float32 expression itself and k2d2 / kcrop2 are
+// capf_preprocess_points' bits.
+__device__ __forceinline__ void kp_pair_outputs(const KpPairArgs& a, const int b, const int j, const float x, const float y, const float score) {
+#pragma clang fp contract(off)
+    const size_t i = ((size_t)b * a.J + j) * 2, im = ((size_t)(a.B + b) * a.J + a.swap.j[j]) * 2;
+    const float kx = a.dec[0] * x + a.dec[1], ky = a.dec[2] * y + a.dec[3];
+    a.kcrop[i] = kx;
+    a.kcrop[i + 1] = ky;
+    a.kcrop[im] = (a.mirror_w - kx) - 1.0f;
+    a.kcrop[im + 1] = ky;
+    if (a.score) a.score[i / 2] = score;
+    if (a.to_image && a.k2d) {
+        const float* A = a.to_image + (size_t)b * 6;
+        const float ix = (A[0] * kx + A[1] * ky) + A[2], iy = (A[3] * kx + A[4] * ky) + A[5];
+        a.k2d[i] = ix;
+        a.k2d[i + 1] = iy;
+        a.k2d[im] = -ix;
+        a.k2d[im + 1] = iy;
+    }
+}
+
+// PAIR: the neighbours of the quarter shift are fused logits; the outputs are kp_pair_outputs'
+template <class L, int MODE, bool PAIR>
+__global__ void __launch_bounds__(KP_THREADS) kp_fwd_combine_kernel(const typename KpArgsOf<PAIR>::type a) {
     const int i = (int)blockIdx.x * KP_THREADS + threadIdx.x;
     if (i >= a.B * a.J) return;
     const int b = i / a.J, j = i - b * a.J, J = a.J, H = a.H, W = a.W;
@@ -213,7 +293,14 @@ __global__ void __launch_bounds__(KP_THREADS) kp_fwd_combine_kernel(const KpHead
         const int py = r.idx / W, px = r.idx - py * W;
         x = (float)px;
         y = (float)py;
-        if (!r.nan && 1 < px && px < W - 1 && 1 < py && py < H - 1) {
+        if constexpr (PAIR) {
+            if (!r.nan && 1 < px && px < W - 1 && 1 < py && py < H - 1) {
+                const float dx = kp_pair_logit1<L>(a, b, j, py, px + 1) - kp_pair_logit1<L>(a, b, j, py, px - 1);
+                const float dy = kp_pair_logit1<L>(a, b, j, py + 1, px) - kp_pair_logit1<L>(a, b, j, py - 1, px);
+                x += dx > 0.f ? 0.25f : dx < 0.f ? -0.25f : 0.f;
+                y += dy > 0.f ? 0.25f : dy < 0.f ? -0.25f : 0.f;
+            }
+        } else if (!r.nan && 1 < px && px < W - 1 && 1 < py && py < H - 1) {
             const typename L::T* xp = static_cast<const typename L::T*>(a.x) + ((size_t)b * H * W + r.idx) * a.C;
             const float* w = a.wt + (size_t)j * a.C;
             const float bj = a.bias ? a.bias[j] : 0.f;
@@ -228,6 +315,10 @@ __global__ void __launch_bounds__(KP_THREADS) kp_fwd_combine_kernel(const KpHead
         y = r.sy / r.s;
     }
     if (r.nan) x = y = score = __builtin_nanf("");
+    if constexpr (PAIR) {
+        kp_pair_outputs(a, b, j, x, y, score);
+        return;
+    }
     if (a.stats) {
         float* st = a.stats + (size_t)i * 4;
         st[0] = r.m; st[1] = r.s; st[2] = x; st[3] = y;
@@ -336,15 +427,15 @@ __global__ void __launch_bounds__(KP_THREADS) kp_dw_reduce_kernel(const float* _
     if (blockIdx.x == 0 && dbias && (int)threadIdx.x < J) dbias[threadIdx.x] = 0.f;     // softmax is shift-invariant: exactly zero
 }
 
-template <class L>
-static void kp_forward_launches(const KpHeadArgs& a, hipStream_t s) {
+template <class L, bool PAIR = false>
+static void kp_forward_launches(const typename KpArgsOf<PAIR>::type& a, hipStream_t s) {
     const dim3 g1((unsigned)(a.B * a.g.nslab)), g2((unsigned)((a.B * a.J + KP_THREADS - 1) / KP_THREADS));
     if (a.mode == 0) {
-        hipLaunchKernelGGL((kp_fwd_slab_kernel<L, 0>), g1, dim3(KP_THREADS), 0, s, a);
-        hipLaunchKernelGGL((kp_fwd_combine_kernel<L, 0>), g2, dim3(KP_THREADS), 0, s, a);
+        hipLaunchKernelGGL((kp_fwd_slab_kernel<L, 0, PAIR>), g1, dim3(KP_THREADS), 0, s, a);
+        hipLaunchKernelGGL((kp_fwd_combine_kernel<L, 0, PAIR>), g2, dim3(KP_THREADS), 0, s, a);
     } else {
-        hipLaunchKernelGGL((kp_fwd_slab_kernel<L, 1>), g1, dim3(KP_THREADS), 0, s, a);
-        hipLaunchKernelGGL((kp_fwd_combine_kernel<L, 1>), g2, dim3(KP_THREADS), 0, s, a);
+        hipLaunchKernelGGL((kp_fwd_slab_kernel<L, 1, PAIR>), g1, dim3(KP_THREADS), 0, s, a);
+        hipLaunchKernelGGL((kp_fwd_combine_kernel<L, 1, PAIR>), g2, dim3(KP_THREADS), 0, s, a);
     }
 }
 
@@ -359,6 +450,18 @@ hipError_t launch_kp_head_forward(KpHeadArgs a, hipStream_t s) {
     if (a.dtype == 0) kp_forward_launches<KpLdF32>(a, s);
     else if (a.dtype == 1) kp_forward_launches<KpLd16<Bf16Fmt>>(a, s);
     else kp_forward_launches<KpLd16<F16Fmt>>(a, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_kp_head_forward_pair(KpPairArgs a, hipStream_t s) {
+    a.g = kp_geom(a.B, a.H, a.W, a.C, a.J);
+    if (!kp_args_ok(a) || !a.kcrop || a.B > (1 << 30) || (a.shift != 0 && a.shift != 1)) return hipErrorInvalidValue;
+    for (int j = 0; j < a.J; ++j)
+        if (a.swap.j[j] < 0 || a.swap.j[j] >= a.J || a.swap.j[a.swap.j[j]] != j) return hipErrorInvalidValue;
+    a.stats = nullptr;
+    if (a.dtype == 0) kp_forward_launches<KpLdF32, true>(a, s);
+    else if (a.dtype == 1) kp_forward_launches<KpLd16<Bf16Fmt>, true>(a, s);
+    else kp_forward_launches<KpLd16<F16Fmt>, true>(a, s);
     return hipGetLastError();
 }
 

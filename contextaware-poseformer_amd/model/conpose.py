@@ -39,6 +39,18 @@ class VolumetricTriangulationNet(CA_PF):
         x, kcrop, score = super().forward_detect(images, to_image)
         return self._layout(x), kcrop, score
 
+    def detect_flip_test(self, images, to_image=None, shift=True, flip_pairs=None):
+        """CA_PF.detect_flip_test; flip_pairs None: this variant's skeleton (capf.lib.MPI_SWAP, as forward_flip_test)."""
+        from capf.lib import MPI_SWAP
+        return super().detect_flip_test(images, to_image, shift, MPI_SWAP if flip_pairs is None else flip_pairs)
+
+    def forward_detect_flip_test(self, images, to_image, shift=True, flip_pairs=None):
+        """CA_PF.forward_detect_flip_test in this variant's output layout: (x [B, 3, 1, 17, 1], kcrop_px, score); flip_pairs None: this
+        variant's skeleton (capf.lib.MPI_SWAP, as forward_flip_test)."""
+        from capf.lib import MPI_SWAP
+        x, kcrop, score = super().forward_detect_flip_test(images, to_image, shift, MPI_SWAP if flip_pairs is None else flip_pairs)
+        return self._layout(x), kcrop, score
+
     @staticmethod
     def _layout(x):
         b, _, p, _ = x.shape

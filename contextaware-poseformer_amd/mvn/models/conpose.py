@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from capf.lib import (KP_INTEGRAL, KP_MODES, PLAN_BN_BATCH_STATS, CapfError, Engine, input_constants, kp_head_backward,
-                      kp_head_forward)
+                      kp_head_forward, kp_head_forward_pair)
 
 from . import _native
 
@@ -601,6 +601,86 @@ class CA_PF(nn.Module):
             if named is not None and guard is not None:
                 guard["token"] = eng.train_generation()
         return out, kcrop, score
+
+    # ---- detector-free flip test: the heatmaps of each crop and of its flipped-back mirror averaged, then decoded once -----------
+    def _swap_table(self, flip_pairs):
+        """flip_pairs -> the J-entry swap table of capf_kp_head_forward_pair / capf_fliptest_fuse_swap (capf.lib.MPI_SWAP's form: entry j names
+        the joint that the mirror exchanges with joint j); None stays None: the H36M table, which both entries then apply themselves."""
+        if flip_pairs is None:
+            return None
+        table = [int(v) for v in flip_pairs]
+        if len(table) != self.num_joints or any(not 0 <= v < len(table) or table[v] != j for j, v in enumerate(table)):
+            raise ValueError("flip_pairs must be a table of {} joint indices that is its own inverse (capf.lib.H36M_SWAP, MPI_SWAP), got {!r}".format(
+                self.num_joints, flip_pairs))
+        return tuple(table)
+
+    def _flip_test_source(self, images, to_image):
+        """(source record of the 2B engine frames [orig | mirrored], B, H, W, to_image) for detect_flip_test / forward_detect_flip_test."""
+        if self._bn_batch_active():
+            raise NotImplementedError("the flip test has no batch-statistics route (backbone_bn='batch' with the backbone in train mode): the "
+                                      "2B-frame pair would change every frame's statistics -- call backbone.eval()")
+        if torch.is_tensor(images) and images.dim() == 5:        # the [2,B,H,W,3] stack capf_preprocess(mode=2) emits
+            if images.dtype != torch.float32 or images.shape[0] != 2:
+                raise TypeError("a 5-D images tensor must be the float32 [2,B,H,W,3] stack of capf.lib.preprocess(mode=2), got {} {}".format(
+                    tuple(images.shape), images.dtype))
+            first, to_image = self._detect_inputs(images[0], to_image)
+            pair = images.contiguous().view(-1, *images.shape[2:])
+            src = _Source("images", pair.device, pair.shape[0], "images", pair)
+        else:
+            first, to_image = self._detect_inputs(images, to_image)
+            if first.dtype == torch.uint8:                       # mirrored in the stem conv's load: no mirrored image is built
+                src = self._image_source(first, 2)
+            else:
+                pair = torch.cat([first, torch.flip(first, [2])])
+                src = _Source("images", pair.device, pair.shape[0], "images", pair)
+        return src, first.shape[0], first.shape[1], first.shape[2], to_image
+
+    def _run_pair_head(self, eng, src, to_image, H, W, shift, swap):
+        """One backbone pass over the pair and the paired head on its feat0: (kcrop2 [2,B,J,2], score [B,J], k2d2 [2,B,J,2] | None)."""
+        weight, bias = self._head_params()
+        _run_backbone(self, eng, src, torch.cuda.current_stream(src.device).cuda_stream)
+        feat0 = eng.tensor_view("feat0", src.batch)
+        decode = (float(W) / feat0.shape[2], 0.0, float(H) / feat0.shape[1], 0.0)
+        kcrop2, score, k2d2, _ = kp_head_forward_pair(feat0, weight.detach(), bias.detach(), KP_MODES[self.keypoint_head_mode], self.keypoint_beta,
+                                                      swap, bool(shift), decode, to_image, float(2 * CROP_HALF[0]))
+        return kcrop2, score, k2d2
+
+    def detect_flip_test(self, images, to_image=None, shift=True, flip_pairs=None):
+        """detect() under HRNet's flip test: ONE backbone pass over the crops and their mirrors, then capf_kp_head_forward_pair -- per joint
+        the heatmap of the crop and the flipped-back heatmap of the mirror (x mirrored, left / right joints exchanged, moved one column to
+        the right when `shift`, HRNet's SHIFT_HEATMAP) are averaged and decoded once.  images: uint8 BGR crops [B,H,W,3] (mirrored in the
+        stem's load), float32 [B,H,W,3] (the mirrored half is torch.flip(images, [2])), or the float32 [2,B,H,W,3] stack of
+        capf.lib.preprocess(mode=2) -- the same bits.  to_image as in detect.  flip_pairs: None -- the H36M table -- or a swap table of J ints
+        (capf.lib.MPI_SWAP).  Returns (kcrop_px [B,J,2], score [B,J], k2d [B,J,2] | None).  Always runs without
+        grad and returns detached tensors: the paired decode has no backward."""
+        self._head_params()
+        swap = self._swap_table(flip_pairs)
+        src, B, H, W, to_image = self._flip_test_source(images, to_image)
+        with torch.cuda.device(src.device), torch.no_grad():
+            kcrop2, score, k2d2 = self._run_pair_head(self._engine_at(src.device, H, W), src, to_image, H, W, shift, swap)
+        return kcrop2[0], score, (None if k2d2 is None else k2d2[0])
+
+    def forward_detect_flip_test(self, images, to_image, shift=True, flip_pairs=None):
+        """The reference's flip-test evaluation (train.py:170-181) without detections from outside: ONE backbone pass over the 2B engine
+        frames, the paired head (detect_flip_test; images / shift / flip_pairs as there), the lifter on the maps still in the workspace with
+        the stacked keypoints the head wrote (set 1 mirrored as capf_preprocess_points(mode=2) does), capf_fliptest_fuse (its _swap form with
+        flip_pairs).  Returns (joints3d [B,1,J,3], kcrop_px [B,J,2], score [B,J]); kcrop_px stays in crop pixels.  The result equals
+        forward_flip_test on the stack with detect_flip_test's keypoints pushed through preprocess_points(mode=2), bit for bit.  Always runs
+        without grad and returns detached tensors."""
+        from capf.lib import fliptest_fuse
+        self._head_params()
+        if to_image is None:
+            raise ValueError("forward_detect_flip_test needs to_image [B, 2, 3]: the lifter takes the keypoints in normalised image coordinates too")
+        swap = self._swap_table(flip_pairs)
+        src, B, H, W, to_image = self._flip_test_source(images, to_image)
+        J = self.num_joints
+        with torch.cuda.device(src.device), torch.no_grad():
+            eng = self._engine_at(src.device, H, W)
+            kcrop2, score, k2d2 = self._run_pair_head(eng, src, to_image, H, W, shift, swap)
+            ref = kcrop2.clone().view(2 * B, J, 2)               # (the lifter normalises its crop keypoints in place: the caller keeps the pixels)
+            pred = self._run_lifter(eng, _Source("workspace", src.device, 2 * B, "the maps", None), k2d2.view(2 * B, J, 2), ref, None)
+            out = fliptest_fuse(pred.view(2, B, 1, J, 3), swap)
+        return out, kcrop2[0], score
 
     # ---- conpose.py:40 on maps of the caller's own backbone ------------------------------------
     def _feature_geometry(self, H, W):

@@ -154,7 +154,8 @@ const char* capf_version(void);
  * layouts unchanged.  Revision 12 (additive): compute_dtype = CAPF_F16, tensor dtype code 3 (fp16) in capf_tensor / capf_op_desc, the
  * capf_op_*_16 entry points (the 16-bit kernels for either element format) and capf_debug_f16_round; struct layouts unchanged
  * (additive: capf_set_map_grad_mode, capf_map_grad_mode; CAPF_PLAN_BN_BATCH_STATS, capf_backbone_forward_bn, capf_op_bn_stats_scratch_bytes,
- * capf_op_bn_stats, capf_op_bn_apply; capf_backward_points; capf_kp_head_scratch_bytes, capf_kp_head_forward, capf_kp_head_backward).      */
+ * capf_op_bn_stats, capf_op_bn_apply; capf_backward_points; capf_kp_head_scratch_bytes, capf_kp_head_forward, capf_kp_head_backward;
+ * capf_kp_head_pair_scratch_bytes, capf_kp_head_forward_pair).                                                                              */
 #define CAPF_ABI_VERSION 12
 int capf_abi_version(void);
 
@@ -789,6 +790,44 @@ int capf_kp_head_forward(void* stream, const void* map_nhwc, int map_dtype, cons
 int capf_kp_head_backward(void* stream, const float* dkcrop, const float* dk2d, const void* map_nhwc, int map_dtype, const float* weight,
                           const float* bias, int B, int H, int W, int C, int J, int mode, float beta, const float decode[4],
                           const float* to_image, float* dweight, float* dbias, float* dmap, int accumulate, void* scratch, size_t scratch_bytes);
+/* ---- 2-D keypoint head on a flip-test pair: the heatmaps of a crop and of its flipped-back mirror averaged, then ONE decode -------------------
+ * HRNet's own flip test (lib/core/function.py validate: FLIP_TEST, flip_back, SHIFT_HEATMAP) on the maps capf_backbone_forward(_u8) leaves for
+ * the 2 * Bsrc engine frames of mode 2: map_nhwc [2 * Bsrc, H, W, C], frame b < Bsrc the source frame, frame Bsrc + b its mirror.  Dtypes, shape
+ * limits (on Bsrc, H, W, C, J), alignment, weight, bias, mode, beta, decode: capf_kp_head_forward's.  Forward only.  Additive inside revision 12.
+ * Fused logit of source frame b, joint j, pixel (y, x), z being capf_kp_head_forward's chain on the 2 * Bsrc-frame map, bit for bit:
+ *       zo = z[b, j, y, x]
+ *       xs = (shift && x >= 1) ? x - 1 : x        (SHIFT_HEATMAP: flipped[:, :, :, 1:] = flipped[:, :, :, :-1]; column 0 keeps its own value)
+ *       zm = z[Bsrc + b, swap[j], y, W - 1 - xs]  (flip_back: mirrored in x, left / right joints exchanged)
+ *       zf = 0.5f * (zo + zm)                     (the fp32 sum rounded once, then halved)
+ *   swap: HOST int32[J], a permutation that is its own inverse (capf_fliptest_fuse_swap's rule and tables); it travels in the kernel arguments.
+ *   shift: 0 / 1.  The fused heatmaps are never written unless `heat` [Bsrc, J, H, W] (the zf the decode used, bit for bit) is given.
+ * Decode of zf: capf_kp_head_forward's, rule for rule -- argmax: first maximum in row-major order, the quarter shift (its four neighbours are
+ *   recomputed from BOTH frames with the expression above), score <= 0 -> (0, 0); integral: the same tiles of 256, slabs, 8 lanes per joint,
+ *   online maximum and sums, merge orders and second launch (the summation orders are unchanged).  No atomics, no signalling between workgroups.
+ * NaN: the keypoint (both coordinate systems, both sets) and the score of (b, j) are NaN if any logit of (b, j) OR of (Bsrc + b, swap[j]) is NaN
+ *   -- also one in the mirror's column 0, which no pixel reads under shift = 1.  Other joints and frames are untouched.
+ * A source frame's result bits depend on frames b and Bsrc + b alone: not on Bsrc, the frame's position, the run or the scratch buffer.
+ * Outputs: with kcrop / k2d / score [Bsrc, J(, 2)] the decode -> decode[4] -> to_image [Bsrc, 2, 3] arithmetic of capf_kp_head_forward on zf, the
+ *   stacks capf_forward takes for the 2 * Bsrc frames (no further launch):
+ *       kcrop2[0, b, j] = kcrop[b, j]      kcrop2[1, b, j] = ((mirror_width - kcrop[b, swap[j]].x) - 1, kcrop[b, swap[j]].y)   (two rounded fp32
+ *       k2d2 [0, b, j] = k2d[b, j]         k2d2 [1, b, j] = (-k2d[b, swap[j]].x, k2d[b, swap[j]].y)                            subtractions)
+ *   kcrop2 [2, Bsrc, J, 2]; k2d2 [2, Bsrc, J, 2] or NULL (needs to_image); score [Bsrc, J] or NULL.  With J = 17, the H36M table and
+ *   mirror_width = 192 (the reference's constant, datasets/utils.py:76) the stacks are capf_preprocess_points(mode = 2) of (k2d, kcrop) bit for bit.
+ * scratch: capf_kp_head_pair_scratch_bytes(Bsrc, H, W, C, J) bytes, 4-byte aligned (0: a shape the kernels do not take).
+ * Refusals, all before anything is launched (no device needed), CAPF_ERR_INVALID: a NULL map / weight / decode / swap / kcrop2 / scratch, k2d2
+ *   without to_image, Bsrc, J, C, H or W out of range, beta <= 0 or not finite, mirror_width not finite, shift outside 0 / 1, an unknown mode or
+ *   dtype, a misaligned map, scratch_bytes too small, a swap entry outside [0, J) or a table that is not its own inverse.  (H * W > 2^24, or a
+ *   grid beyond 2^31 blocks: CAPF_ERR_UNSUPPORTED, as capf_kp_head_forward.)
+ * Cost (MI355X, medians of 20 around the host call, tools/bench_kp_head.py --pair, EXPERIMENTS.md R28.1), against capf_kp_head_forward on the
+ *   SAME 2 * Bsrc-frame map (the same bytes read, the same FMAs, half the (frame, joint) items):
+ *   HRNet-32 fp32, feat0 64 x 64 x 32: Bsrc 32 -- 0.074 (argmax) / 0.071 ms (integral) against 0.073 / 0.071 ms (ratio 1.02 / 1.00); Bsrc 256 -- 0.276 /
+ *   0.284 ms against 0.301 / 0.300 ms (0.92 / 0.95); fp16 HRNet-48 map, Bsrc 128 -- 0.197 / 0.191 ms against 0.186 / 0.206 ms (1.05 / 0.93): the same cost
+ *   within 5 % either way, slower in two of the six.  CA_PF.forward_detect_flip_test against detect + preprocess_points + forward_flip_test: 6.86
+ *   against 10.75 ms (Bsrc 32), 46.1 against 68.2 ms (Bsrc 256), 19.2 against 27.5 ms (fp16 HRNet-48, Bsrc 128). */
+size_t capf_kp_head_pair_scratch_bytes(int Bsrc, int H, int W, int C, int J);
+int capf_kp_head_forward_pair(void* stream, const void* map_nhwc, int map_dtype, const float* weight, const float* bias, int Bsrc, int H, int W,
+                              int C, int J, int mode, float beta, const int32_t* swap, int shift, const float decode[4], const float* to_image,
+                              float mirror_width, float* kcrop2, float* k2d2, float* score, float* heat, void* scratch, size_t scratch_bytes);
 /* capf_pck_counts: the MPI-INF-3DHP evaluation (ContextPose_mpi/3dhp_test/test_util, MATLAB: mpii_test_predictions_py.m,
  *   mpii_evaluate_errors.m, mpii_compute_3d_pck.m), which callers otherwise export to .mat files and run off the GPU; capf_pose_errors /
  *   capf_segment_sums serve H36M only.  Per pose i of pred / gt [n, joints, 3] (same unit; to_mm converts it to mm): gt made relative to

@@ -4,6 +4,11 @@ against forward on given keypoints.  One process, device events around every cal
 the machine; medians with min / max over the repeats.
 
     python tools/bench_kp_head.py [--configs hrnet_32:fp32:64 hrnet_32:fp32:512 hrnet_48:fp16:256] [--repeats 20] [--warmup 3]   (needs the MI355X)
+    python tools/bench_kp_head.py --pair [--configs hrnet_32:fp32:32 hrnet_32:fp32:256 hrnet_48:fp16:128]     (EXPERIMENTS.md R28.1)
+
+--pair: the flip-test pair.  The batch of a config counts SOURCE frames; feat0 holds the 2 * Bsrc frames [orig | mirrored] of one backbone
+pass.  capf_kp_head_forward_pair against capf_kp_head_forward on the SAME map (the same bytes read, the same FMAs, half the (frame, joint)
+items), then forward_detect_flip_test against the route without it: detect + preprocess_points + forward_flip_test.
 
 The floor is feat0's bytes over --hbm-gbs (default 4000 GB/s, roughly what a streaming read reaches on an MI355X); the backward reads the
 map three times (statistics, dz, the dW products) and, with dmap, writes it once.
@@ -33,13 +38,52 @@ def timed(runs, repeats, warmup):
     return {k: {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)} for k, v in times.items()}
 
 
+def pair_row(args, spec, model, eng, img, A, s):
+    import torch
+    from capf import lib as capf
+    B = img.shape[0]
+    images2 = torch.stack([img, torch.flip(img, [2])]).contiguous()
+    pair = images2.view(2 * B, *img.shape[1:])
+    eng.backbone_forward(pair, s)
+    feat0 = eng.tensor_view("feat0", 2 * B)
+    fl = model.keypoint_head.final_layer
+    w, b = fl.weight.detach().reshape(17, -1).contiguous(), fl.bias.detach()
+    dec, A2 = (4.0, 0.0, 4.0, 0.0), torch.cat([A, A]).contiguous()
+
+    def route_today():
+        kcrop, _, k2d = model.detect(img, A)
+        _, k2d2, kcrop2 = capf.preprocess_points(None, k2d, kcrop, mode=2)
+        return model.forward_flip_test(images2, k2d2, kcrop2)
+
+    runs = {
+        "backbone_forward_2B": lambda: eng.backbone_forward(pair, s),
+        "single_2B_argmax": lambda: capf.kp_head_forward(feat0, w, b, capf.KP_ARGMAX, 1.0, dec, A2),
+        "pair_argmax": lambda: capf.kp_head_forward_pair(feat0, w, b, capf.KP_ARGMAX, 1.0, None, True, dec, A),
+        "single_2B_integral": lambda: capf.kp_head_forward(feat0, w, b, capf.KP_INTEGRAL, 2.0, dec, A2),
+        "pair_integral": lambda: capf.kp_head_forward_pair(feat0, w, b, capf.KP_INTEGRAL, 2.0, None, True, dec, A),
+    }
+    with torch.no_grad():
+        runs["detect+preprocess_points+forward_flip_test"] = route_today
+        runs["forward_detect_flip_test"] = lambda: model.forward_detect_flip_test(images2, A)
+        row = {"config": spec, "pair": True, "feat0": list(feat0.shape), "feat0_MB": round(feat0.numel() * feat0.element_size() / 1e6, 2),
+               "one_read_floor_ms": round(feat0.numel() * feat0.element_size() / (args.hbm_gbs * 1e9) * 1e3, 4), "repeats": args.repeats}
+        row.update(timed(runs, args.repeats, args.warmup))
+    for mode in ("argmax", "integral"):
+        row[f"pair_over_single_{mode}"] = round(row[f"pair_{mode}"]["median_ms"] / row[f"single_2B_{mode}"]["median_ms"], 3)
+    row["flip_test_over_route_today"] = round(row["forward_detect_flip_test"]["median_ms"] / row["detect+preprocess_points+forward_flip_test"]["median_ms"], 3)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--configs", nargs="+", default=["hrnet_32:fp32:64", "hrnet_32:fp32:512", "hrnet_48:fp16:256"], help="backbone:dtype:batch")
+    ap.add_argument("--configs", nargs="+", default=None, help="backbone:dtype:batch (source frames with --pair)")
+    ap.add_argument("--pair", action="store_true", help="the flip-test pair: capf_kp_head_forward_pair / forward_detect_flip_test")
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--hbm-gbs", type=float, default=4000.0)
     args = ap.parse_args()
+    if args.configs is None:
+        args.configs = ["hrnet_32:fp32:32", "hrnet_32:fp32:256", "hrnet_48:fp16:128"] if args.pair else ["hrnet_32:fp32:64", "hrnet_32:fp32:512", "hrnet_48:fp16:256"]
     sys.path.insert(0, os.path.join(ROOT, "contextaware-poseformer_amd"))
     import numpy as np
     import torch
@@ -60,6 +104,12 @@ def main():
         A = torch.from_numpy(np.stack([capf.crop_to_image_matrix((500.0, 500.0), (1.5, 1.5), (256, 256), 1000, 1000)] * B).astype(np.float32)).cuda()
         eng = model.engine_for(img)
         s = torch.cuda.current_stream().cuda_stream
+        if args.pair:
+            print(json.dumps(pair_row(args, spec, model, eng, img, A, s)), flush=True)
+            for e in model._engines.values():
+                e.close()
+            model._engines.clear()
+            continue
         eng.backbone_forward(img, s)
         feat0 = eng.tensor_view("feat0", B)
         fl = model.keypoint_head.final_layer
