@@ -11,6 +11,7 @@ F32, BF16, F16 = 0, 1, 2      # capf_dtype
 PLAN_NO_FUSED_LIFTER, PLAN_NO_WINOGRAD, PLAN_NO_ROW_HALO, PLAN_WINOGRAD_F23_ONLY, PLAN_NO_PWCHAIN, PLAN_NO_WS, PLAN_LIFTER_FP32, PLAN_NO_F32X3, PLAN_F32X3_EXACT, PLAN_NO_F32H2_GEMM, PLAN_NO_UPADD, PLAN_H2_PLANES, PLAN_NO_BNECK, PLAN_NO_BATCHED_REDUCE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192     # capf_plan_flag
 PLAN_BF16_F32_STREAM = 32768     # (1 << 14 stays unassigned)
 PLAN_BN_BATCH_STATS = 65536      # opt-in: the handle also carries the batch-statistics backbone route (capf_backbone_forward_bn)
+PLAN_CPN_PREDICT = 131072        # opt-in, CPN50 (fp32 / bf16): the backbone also runs refine_net.final_predict into the named tensor "heat"
 ABI_VERSION = 12       # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
 
 EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.py)
@@ -43,6 +44,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_backward_points",
     "capf_kp_head_scratch_bytes", "capf_kp_head_forward", "capf_kp_head_backward",
     "capf_kp_head_pair_scratch_bytes", "capf_kp_head_forward_pair",
+    "capf_cpn_decode", "capf_cpn_decode_taps", "capf_cpn_decode_lds_bytes",
 ]
 
 
@@ -258,6 +260,11 @@ def load_library():
     lib.capf_kp_head_pair_scratch_bytes.argtypes = [c_int] * 5
     lib.capf_kp_head_pair_scratch_bytes.restype = c_size_t
     lib.capf_kp_head_forward_pair.argtypes = [P, P, c_int, P, P] + [c_int] * 6 + [c_float, POINTER(c_int32), c_int, F3, P, c_float, P, P, P, P, P, c_size_t]
+    lib.capf_cpn_decode.argtypes = [P, P] + [c_int] * 6 + [F3, P, P, P, P, P]
+    lib.capf_cpn_decode_taps.argtypes = [POINTER(c_double)]
+    lib.capf_cpn_decode_taps.restype = None
+    lib.capf_cpn_decode_lds_bytes.argtypes = [c_int, c_int]
+    lib.capf_cpn_decode_lds_bytes.restype = c_size_t
     _lib = lib
     return lib
 
@@ -415,6 +422,13 @@ class Engine:
                 out.append((shape[1], shape[2], shape[3]))
             self._feature_shapes = out
         return self._feature_shapes
+
+    def tensor_shape(self, name):
+        """(dtype code, per-frame shape) of a named tensor of this plan -- capf_tensor's return value (0 fp32, 1 int32, 2 bf16, 3 fp16) and
+        its shape without the batch; works on a plan-only handle.  An unknown name raises ("heat" exists under PLAN_CPN_PREDICT only)."""
+        shape, nd = (c_int64 * 4)(), c_int()
+        rc = self._check(self.lib.capf_tensor(self.h, name.encode(), None, shape, byref(nd)), f"tensor({name})")
+        return rc, tuple(shape[i] for i in range(1, nd.value))
 
     @staticmethod
     def _ptrs4(tensors):
@@ -1094,6 +1108,35 @@ def kp_head_backward(x, weight, bias=None, dkcrop=None, dk2d=None, beta=1.0, dec
     _call("capf_kp_head_backward", _stream(x), _p(dkcrop), _p(dk2d), _p(x), dtype, _p(w), _p(bias), B, H, W, C, J, KP_INTEGRAL, float(beta),
           dec, _p(to_image), _p(dw), _p(db), _p(dmap), 1 if accumulate else 0, _p(scratch), nbytes)
     return dw, db, dmap
+
+
+def cpn_decode_taps():
+    """capf_cpn_decode_taps: the 21 Gaussian taps of capf_cpn_decode's blur as Python floats (host code, no GPU needed)"""
+    g = (c_double * 21)()
+    load_library().capf_cpn_decode_taps(g)
+    return list(g)
+
+
+def cpn_decode(heat, joints=None, decode=(1.0, 0.0, 1.0, 0.0), to_image=None, want_score=True, want_blurred=False):
+    """capf_cpn_decode on a contiguous NHWC heatmap tensor heat [B, H, W, C] (fp32 / bf16 / fp16; Engine.tensor_view("heat", B) of a
+    PLAN_CPN_PREDICT handle): CPN's two-peak decode of channels 0 .. joints - 1 (default: all C).  decode = (sx, ox, sy, oy) maps heatmap
+    to crop coordinates (CPN: sx = W_img / W, ox = sx / 2, the same in y); to_image [B, 2, 3] fp32 (crop_to_image_matrix) maps those to the
+    lifter's normalised image coordinates.
+    Returns (kcrop [B, J, 2], score [B, J] | None, k2d [B, J, 2] | None, blurred [B, J, H + 20, W + 20] float64 | None)."""
+    import torch
+    dtype = _kp_map_dtype(heat)
+    B, H, W, C = heat.shape
+    J = C if joints is None else int(joints)
+    if to_image is not None and (tuple(to_image.shape) != (B, 2, 3) or to_image.dtype != torch.float32 or not to_image.is_contiguous()):
+        raise CapfError(f"to_image must be contiguous fp32 [{B}, 2, 3], not {tuple(to_image.shape)} {to_image.dtype}")
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=heat.device)
+    kcrop = new(B, J, 2)
+    k2d = new(B, J, 2) if to_image is not None else None
+    score = new(B, J) if want_score else None
+    blurred = torch.empty(B, J, H + 20, W + 20, dtype=torch.float64, device=heat.device) if want_blurred else None
+    dec = (c_float * 4)(*[float(v) for v in decode])
+    _call("capf_cpn_decode", _stream(heat), _p(heat), dtype, B, H, W, C, J, dec, _p(to_image), _p(kcrop), _p(k2d), _p(score), _p(blurred))
+    return kcrop, score, k2d, blurred
 
 
 # the H36M skeleton's mirror table: joints_left [4, 5, 6, 11, 12, 13] <-> joints_right [1, 2, 3, 14, 15, 16] (mvn/datasets/utils.py:12-13;

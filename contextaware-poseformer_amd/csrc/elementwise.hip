@@ -446,4 +446,32 @@ hipError_t launch_copy_segments(const CopySegment* table_dev, int n, hipStream_t
     return hipGetLastError();
 }
 
+// ---- channel concatenation of up to 4 NHWC maps with one channel count (CAPF_PLAN_CPN_PREDICT: torch.cat(refine_fms, 1) in front of
+// final_predict): a plain copy in 16-byte chunks, `q` chunks per source row; consecutive lanes write consecutive chunks of the output
+struct ConcatArgs { const f32x4* in[4]; f32x4* out; long pixels; int n, q; };
+__global__ __launch_bounds__(256) void concat_channels_kernel(const ConcatArgs a) {
+    const long row = (long)a.n * a.q, total = a.pixels * row;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
+        const long p = i / row;
+        const int r = (int)(i - p * row), src = r / a.q, k = r - src * a.q;
+        // (a uniform choice per chunk run: no runtime-indexed pointer array in registers)
+        const f32x4* in = src == 0 ? a.in[0] : src == 1 ? a.in[1] : src == 2 ? a.in[2] : a.in[3];
+        a.out[i] = in[p * a.q + k];
+    }
+}
+
+hipError_t launch_concat_channels(const float* const in[4], int n, float* out, long pixels, int row_bytes, hipStream_t s) {
+    if (n < 1 || n > 4 || row_bytes < 16 || row_bytes % 16 != 0 || pixels < 1 || !out) return hipErrorInvalidValue;
+    ConcatArgs a{};
+    for (int i = 0; i < n; ++i) {
+        if (!in[i] || (reinterpret_cast<uintptr_t>(in[i]) & 15)) return hipErrorInvalidValue;
+        a.in[i] = reinterpret_cast<const f32x4*>(in[i]);
+    }
+    if (reinterpret_cast<uintptr_t>(out) & 15) return hipErrorInvalidValue;
+    a.out = reinterpret_cast<f32x4*>(out);
+    a.pixels = pixels; a.n = n; a.q = row_bytes / 16;
+    hipLaunchKernelGGL(concat_channels_kernel, dim3(grid_1d(pixels * n * a.q, 16384)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace capf

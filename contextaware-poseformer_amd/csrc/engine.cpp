@@ -53,6 +53,13 @@ int Engine::repack(hipStream_t s, bool lifter_only) {
         if (pk.kind == CONV_BN) {
             if (lifter_only) continue;                  // conv+BN packs belong to the frozen backbone
             const ConvSrc c = conv_src(pk);
+            if (pk.n_src) {                             // fewer parameter rows than pack rows: zeros first, then the parameter's rows of the primary layout
+                HIP_TRY(hipMemsetAsync(W, 0, (size_t)pk.N * pk.Kpad * (pk.bf16 ? 2 : 4), s));
+                HIP_TRY(hipMemsetAsync(B, 0, (size_t)pk.N * sizeof(float), s));
+                if (pk.bf16) HIP_TRY(launch_pack_conv_bf16(c.w, c.g, c.b, c.m, c.v, c.eps, W, B, pk.n_src, pk.Cin, pk.ks, pk.Kpad, s, f16()));
+                else HIP_TRY(launch_pack_conv(c.w, c.g, c.b, c.m, c.v, c.eps, W, B, pk.n_src, pk.Cin, pk.ks, pk.Kpad, s));
+                continue;
+            }
             if (pk.bf16) {
                 HIP_TRY(launch_pack_conv_bf16(c.w, c.g, c.b, c.m, c.v, c.eps, W, B, pk.N, pk.Cin, pk.ks, pk.Kpad, s, f16()));
                 if (pk.rh) HIP_TRY(launch_pack_conv_bf16_rh(c.w, c.g, c.b, c.m, c.v, c.eps, pack_arena + pk.rh_off, B, pk.N, pk.Cin, bf16_rh_width(pk.Cin), s, f16()));
@@ -258,7 +265,7 @@ bool Engine::tile_takes(const Op& op, int batch) const {
 // 16-bit pipe, whose peak is 16 x the fp32 pipe's
 Engine::OpRoute Engine::op_route(const Op& op, int batch) const {
     static const char* kn[] = {"", "fuse_sum", "maxpool3x3s2", "bilinear_resize", "prep_embed", "sample_ref",
-                               "layernorm", "deform_sample", "attention", "head", "", "", "embed", "ctx_attn", "res_chain", "mlp_chain"};
+                               "layernorm", "deform_sample", "attention", "head", "", "", "embed", "ctx_attn", "res_chain", "mlp_chain", "concat_channels"};
     if (op.kind != OP_GEMM) return {Family::NONE, kn[op.kind], op.flops_per_frame * batch};
     const Pack& pk = packs[op.pack];
     const double MN = 2.0 * (double)op.rows_per_frame * batch * op.N;
@@ -331,6 +338,11 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch, bool side_chain) {
         case OP_RESIZE:
             HIP_TRY(launch_bilinear_resize(ptr(op.in[0]), ptr(op.out), batch, op.H, op.W, op.C, op.Ho, op.Wo, s, op.bf16, ptr(op.aux), f16()));
             break;
+        case OP_CONCAT: {
+            const float* src[4] = {ptr(op.in[0]), ptr(op.in[1]), ptr(op.in[2]), ptr(op.in[3])};
+            HIP_TRY(launch_concat_channels(src, op.n_in, ptr(op.out), (long)batch * op.H * op.W, op.C * (op.bf16 ? 2 : 4), s));
+            break;
+        }
         case OP_PREP_EMBED:
             HIP_TRY(launch_prep_embed(kcrop, k2d, params[op.coord.w].ptr, params[op.coord.b].ptr, params[op.pos].ptr,
                                       ptr(op.out), batch, op.smp.J, op.smp.L1, op.C, s));
@@ -788,7 +800,12 @@ int capf_create(const capf_config* cfg, int device, capf_handle** out) {
             return CAPF_ERR_UNSUPPORTED;
         }
     }
-    if (cfg->plan_flags & ~(16383 | CAPF_PLAN_BF16_F32_STREAM | CAPF_PLAN_BN_BATCH_STATS)) {
+    if ((cfg->plan_flags & CAPF_PLAN_CPN_PREDICT) && cfg->backbone != CAPF_CPN50) {      // the head of a CPN checkpoint: no other backbone has it
+        g_create_error = "CAPF_PLAN_CPN_PREDICT is a CPN50 plan (refine_net.final_predict; HRNet is not supported)";
+        delete h;
+        return CAPF_ERR_UNSUPPORTED;
+    }
+    if (cfg->plan_flags & ~(16383 | CAPF_PLAN_BF16_F32_STREAM | CAPF_PLAN_BN_BATCH_STATS | CAPF_PLAN_CPN_PREDICT)) {
         g_create_error = "unknown capf_plan_flag bits";
         delete h;
         return CAPF_ERR_INVALID;
@@ -1739,6 +1756,31 @@ int capf_kp_head_backward(void* stream, const float* dkcrop, const float* dk2d, 
     return capf::launch_kp_head_backward(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
+// ---- CPN's two-peak decode (cpn_decode.hip): every argument is judged here, before anything is launched ----
+void capf_cpn_decode_taps(double taps[21]) {
+    if (taps) capf::cpn_decode_taps(taps);
+}
+
+size_t capf_cpn_decode_lds_bytes(int H, int W) {
+    const size_t n = capf::cpn_decode_lds_bytes(H, W);
+    return n == (size_t)-1 ? 0 : n;
+}
+
+int capf_cpn_decode(void* stream, const void* heat_nhwc, int heat_dtype, int B, int H, int W, int C, int J, const float decode[4],
+                    const float* to_image, float* kcrop, float* k2d, float* score, double* blurred) {
+    if (!heat_nhwc || !kcrop || !decode || (k2d && !to_image)) return CAPF_ERR_INVALID;
+    if (B < 1 || H < 1 || W < 1 || J < 1 || J > C || C > 32 || (long)B * J >= (1L << 31)) return CAPF_ERR_INVALID;
+    if (heat_dtype < CAPF_F32 || heat_dtype > CAPF_F16) return CAPF_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(heat_nhwc) & (heat_dtype == CAPF_F32 ? 15 : 7)) return CAPF_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(kcrop) & 3) || (reinterpret_cast<uintptr_t>(blurred) & 7)) return CAPF_ERR_INVALID;
+    if (capf::cpn_decode_lds_bytes(H, W) > capf::CPN_LDS_LIMIT) return CAPF_ERR_UNSUPPORTED;      // (the two planes of a workgroup must fit the 160 KiB of a CU)
+    capf::CpnDecodeArgs a{};
+    a.heat = heat_nhwc; a.dtype = heat_dtype; a.B = B; a.H = H; a.W = W; a.C = C; a.J = J;
+    for (int i = 0; i < 4; ++i) a.dec[i] = decode[i];
+    a.to_image = to_image; a.kcrop = kcrop; a.k2d = to_image ? k2d : nullptr; a.score = score; a.blurred = blurred;
+    return capf::launch_cpn_decode(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+}
+
 int capf_num_ops(const capf_handle* h) { return h ? (int)h->e.ops.size() : CAPF_ERR_INVALID; }
 
 int capf_op_info(const capf_handle* h, int index, int batch, const char** name, const char** kernel, double* flops) {
@@ -1799,6 +1841,9 @@ int capf_op_bytes(const capf_handle* h, int index, int batch, double* bytes) {
         case capf::OP_MAXPOOL:
         case capf::OP_RESIZE:
             b = B * op.C * act * ((double)op.H * op.W + (double)op.Ho * op.Wo * (op.aux >= 0 ? 2.0 : 1.0));   // (+ the added map)
+            break;
+        case capf::OP_CONCAT:
+            b = 2.0 * B * op.H * op.W * op.n_in * op.C * act;                   // every source read once, the concatenation written once
             break;
         case capf::OP_LAYERNORM:
             b = (double)op.rows_per_frame * B * op.C * 4.0 * (op.aux >= 0 ? 3.0 : 2.0);

@@ -56,6 +56,8 @@ struct Pack {
     int n_lin = 0;
     BnRef bn;
     int N = 0, K = 0, Cin = 0, ks = 1;
+    int n_src = 0;                 // conv: rows the parameter and its BatchNorm have when that is fewer than N (0: N) -- the pack's rows n_src .. N - 1 are
+                                   // zero weights with a zero folded bias (CPN's final_predict.1: 17 rows packed as 20); such a pack keeps the primary layout alone
     // ---- the primary layout: [N][Kpad] at w_off, the folded bias (conv) or the concatenated biases (linear) at b_off
     size_t w_off = 0, b_off = 0;
     int Kpad = 0;
@@ -107,7 +109,8 @@ struct LifterSchema {
 
 enum OpKind {
     OP_GEMM = 0, OP_FUSE, OP_MAXPOOL, OP_RESIZE, OP_PREP_EMBED, OP_SAMPLE_REF, OP_LAYERNORM, OP_DEFORM,
-    OP_ATTENTION, OP_HEAD, OP_FORK, OP_JOIN, OP_EMBED, OP_CTX_ATTN, OP_RES_CHAIN, OP_MLP_CHAIN
+    OP_ATTENTION, OP_HEAD, OP_FORK, OP_JOIN, OP_EMBED, OP_CTX_ATTN, OP_RES_CHAIN, OP_MLP_CHAIN,
+    OP_CONCAT            // in[0..n_in) [B, H, W, C] each -> out [B, H, W, n_in * C], channels in input order (CAPF_PLAN_CPN_PREDICT: torch.cat(refine_fms, 1))
 };
 
 // Per-kind payloads of an Op, held by value (an op of another kind leaves them at their defaults)
@@ -339,7 +342,7 @@ struct Engine {
     int add_param(const std::string& name, int kind, std::initializer_list<int64_t> shape);
     int new_buffer(size_t elems, const std::string& tag);
     Tensor conv_bn(const std::string& conv, const std::string& bn, const Tensor& x, int Cout, int ks, int stride,
-                   int act, const Tensor* residual);
+                   int act, const Tensor* residual, int pad_rows_to = 0);
     void build_hrnet(Tensor img, Tensor feats[4]);
     void build_cpn(Tensor img, Tensor feats[4]);
     void build_lifter(const Tensor feats[4]);

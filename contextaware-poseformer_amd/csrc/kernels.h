@@ -785,4 +785,28 @@ struct KpPairArgs : KpHeadArgs {
 };
 hipError_t launch_kp_head_forward_pair(KpPairArgs a, hipStream_t s);
 
+// ---- CPN's detector head (CAPF_PLAN_CPN_PREDICT) ---------------------------------------------------------------------------------------
+// elementwise.hip: out[p][i * row_bytes ..] = in[i][p][0 .. row_bytes) for the `pixels` NHWC pixels of n <= 4 maps of one channel count
+// (row_bytes = channels x element size, a multiple of 16; 16 bytes per lane)
+hipError_t launch_concat_channels(const float* const in[4], int n, float* out, long pixels, int row_bytes, hipStream_t s);
+// cpn_decode.hip: CPN's two-peak heatmap decode (cpn/test.py:79-108; include/capf.h capf_cpn_decode has the rules), one workgroup per
+// (frame, joint), the normalised plane (fp32) and the row pass of the blur (fp64) in LDS
+constexpr int CPN_BORDER = 10, CPN_TAPS = 2 * CPN_BORDER + 1;
+constexpr size_t CPN_LDS_LIMIT = 160 * 1024;
+struct CpnDecodeArgs {
+    const void* heat;        // [B, H, W, C] NHWC, dtype 0 fp32 / 1 bf16 / 2 fp16 (capf_dtype); joint j is channel j
+    int dtype;
+    int B, H, W, C, J;
+    float dec[4];            // sx, ox, sy, oy
+    const float* to_image;   // [B, 2, 3] or NULL
+    float* kcrop;            // [B, J, 2]
+    float* k2d;              // [B, J, 2] or NULL
+    float* score;            // [B, J] or NULL
+    double* blurred;         // [B, J, H + 20, W + 20] or NULL
+    double g[CPN_TAPS];      // the Gaussian taps (cpn_decode_taps), filled by the launcher
+};
+void cpn_decode_taps(double g[CPN_TAPS]);
+size_t cpn_decode_lds_bytes(int H, int W);       // what one workgroup needs (the launcher refuses more than CPN_LDS_LIMIT)
+hipError_t launch_cpn_decode(CpnDecodeArgs a, hipStream_t s);
+
 }  // namespace capf

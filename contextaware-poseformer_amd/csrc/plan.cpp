@@ -105,18 +105,22 @@ static BnRef reg_bn(Engine& e, const std::string& bn, int C) {      // nn.BatchN
 }
 
 // conv (bias=False) + eval BatchNorm (+ residual) (+ ReLU) as ONE implicit-GEMM launch.
+// pad_rows_to > Cout: the parameter and its BatchNorm keep their Cout rows, the pack, the op and the output map have pad_rows_to (rows and
+// channels Cout .. pad_rows_to - 1: zero weights, zero bias -- exact zeros behind ACT_NONE), so that a width no kernel takes rides one that all do
 Tensor Engine::conv_bn(const std::string& conv, const std::string& bn, const Tensor& x, int Cout, int ks,
-                       int stride, int act, const Tensor* residual) {
+                       int stride, int act, const Tensor* residual, int pad_rows_to) {
     const int pad = ks / 2;
     Tensor y;
     y.H = (x.H + 2 * pad - ks) / stride + 1;
     y.W = (x.W + 2 * pad - ks) / stride + 1;
-    y.C = Cout;
 
     Pack pk;
     pk.kind = CONV_BN;
     pk.w[0] = add_param(conv + ".weight", CAPF_P_CONV_W, {Cout, x.C, ks, ks});
     pk.bn = reg_bn(*this, bn, Cout);
+    const bool padded = pad_rows_to > Cout;
+    if (padded) { pk.n_src = Cout; Cout = pad_rows_to; }
+    y.C = Cout;
     pk.N = Cout;
     pk.Cin = x.C;
     pk.ks = ks;
@@ -128,24 +132,24 @@ Tensor Engine::conv_bn(const std::string& conv, const std::string& bn, const Ten
     // split-fp32 tile, or to Winograd along W (igemm_wino.hip: 1.5x fewer MFMAs with F(2,3)).  ONE eligibility rule for both routes, the
     // Winograd kernels': Cin % 32 == 0, Cout % 32 == 0, even W -- the tile is offered to no other conv (HRNet-48's 48-channel branch stays on
     // the direct kernel), and CAPF_PLAN_NO_WINOGRAD takes the tile away with the Winograd kernels
-    const bool fast3x3 = plan.use_wino && !use_bf16 && ks == 3 && stride == 1 && x.C % 32 == 0 && x.W % 2 == 0 && Cout % 32 == 0;
+    const bool fast3x3 = plan.use_wino && !use_bf16 && ks == 3 && stride == 1 && x.C % 32 == 0 && x.W % 2 == 0 && Cout % 32 == 0 && !padded;
     pk.fast3x3 = fast3x3;
     // F(4,3) (half the MFMAs of the direct conv) where the row length allows four-pixel tiles, F(2,3) (two thirds) otherwise.
     // HRNet only: F(4,3) pays inside the grouped multi-branch launches (+3.2 % end to end), not for CPN's lone convs (-0.8 %).
     if (fast3x3) { pk.direct_Kpad = pk.Kpad; pk.Kpad = ((x.W % 4 == 0 && plan.wino_f43 && (cfg.backbone == CAPF_HRNET || plan.wino_f43_cpn) && x.H * x.W >= plan.wino_f43_min_hw && x.H * x.W <= plan.wino_f43_max_hw) ? 18 : 12) * x.C; }
     // bf16: the 3x3 stride-1 convs also keep their weights in the row-halo layout (igemm_bf16.hip: one staged activation tile
     // for the three kw taps); launches of >= 2048 tiles run that kernel, smaller ones the ring kernel on the standard layout
-    if (use_bf16 && plan.use_rh && ks == 3 && stride == 1 && bf16_rh_width(x.C) && Cout % 4 == 0) { pk.rh = true; pk.rh_Kpad = 9 * x.C; }
+    if (use_bf16 && plan.use_rh && ks == 3 && stride == 1 && bf16_rh_width(x.C) && Cout % 4 == 0 && !padded) { pk.rh = true; pk.rh_Kpad = 9 * x.C; }
     // ... and in the layout of the 2-D halo tile (igemm_bf16_ws.hip), which runs them from 1 GFLOP per conv and batch 24 up (build() finds
     // the batches: tile_takes)
-    if (use_bf16 && plan.use_ws && ks == 3 && stride == 1 && x.C % 16 == 0 && Cout % 8 == 0) pk.ws = true;
+    if (use_bf16 && plan.use_ws && ks == 3 && stride == 1 && x.C % 16 == 0 && Cout % 8 == 0 && !padded) pk.ws = true;
     // fp32: the fast3x3 convs also keep their weights as the pieces the plan's split-fp32 tile takes (igemm_f32h2_ws.hip / igemm_f32x3_ws.hip),
     // which runs them from 370 MFLOP per conv and batch 5 up (build() finds the batches: tile_takes)
     if (fast3x3 && plan.use_x3 && x.W <= 256) pk.x3 = true;
     // fp32: every conv with 16-byte-aligned channel counts also keeps its weights as two block-scaled fp16 pieces in the direct layout's
     // geometry (igemm_f32h2.hip): what runs on the plain fp32 MFMA kernel at batch < 5 runs there from batch 5 (1x1 / stride-2 fuse and
     // transition convs, lone convs; the HBM-bound pointwise kernels of layer1 keep theirs)
-    if (!use_bf16 && plan.use_h2g && x.C % 4 == 0 && Cout % 4 == 0) { pk.h2g = true; pk.h2g_Kpad = fast3x3 ? pk.direct_Kpad : pk.Kpad; }
+    if (!use_bf16 && plan.use_h2g && x.C % 4 == 0 && Cout % 4 == 0 && !padded) { pk.h2g = true; pk.h2g_Kpad = fast3x3 ? pk.direct_Kpad : pk.Kpad; }
     packs.push_back(pk);
 
     Op op;
@@ -479,8 +483,43 @@ void Engine::build_cpn(Tensor img, Tensor feats[4]) {
         feats[i] = pool_or_resize(*this, OP_RESIZE, F + ".cascade." + std::to_string(i) + ".resize", y, oh, ow);
     }
     join();
-    // final_predict is never called (:76-88): parameters only
     const std::string fp = F + ".final_predict";
+    if (cfg.plan_flags & CAPF_PLAN_CPN_PREDICT) {
+        // CPN's own detector head (refineNet.py:64-70, :86-88): final_predict(torch.cat(refine_fms, 1)) = Bottleneck(1024 -> 128 -> 256), then
+        // conv3x3(256 -> 17) + BatchNorm, no activation.  The parameters register in the order of the unflagged plan (same schema).
+        // The concatenation is a copy into a buffer of its own: feat0..3 stay where and what they are (the lifter samples them)
+        Tensor cat{-1, oh, ow, 0};
+        Op op;
+        op.kind = OP_CONCAT;
+        op.name = fp + ".cat";
+        op.n_in = 4;
+        for (int i = 0; i < 4; ++i) {
+            op.in[i] = feats[i].buf;
+            use(feats[i].buf);
+            cat.C += feats[i].C;
+        }
+        op.H = oh; op.W = ow; op.C = feats[0].C; op.Ho = oh; op.Wo = ow;
+        op.bf16 = b16() ? 1 : 0;
+        cat.buf = new_buffer(act_elems((size_t)oh * ow * cat.C), op.name);
+        op.out = cat.buf;
+        push(op);
+        fork(2);                  // the projection shortcut only reads the concatenation
+        Tensor t = conv_bn(fp + ".0.conv1", fp + ".0.bn1", cat, 128, 1, 1, ACT_RELU, nullptr);
+        t = conv_bn(fp + ".0.conv2", fp + ".0.bn2", t, 128, 3, 1, ACT_RELU, nullptr);
+        // (conv3 is REGISTERED ahead of the downsample pair, as nn.Module orders a Bottleneck's children and the unflagged plan does)
+        const std::string c3 = fp + ".0.conv3", b3 = fp + ".0.bn3";
+        add_param(c3 + ".weight", CAPF_P_CONV_W, {256, 128, 1, 1});
+        reg_bn(*this, b3, 256);
+        set_lane(1);
+        Tensor r = conv_bn(fp + ".0.downsample.0", fp + ".0.downsample.1", cat, 256, 1, 1, ACT_NONE, nullptr);
+        join();
+        t = conv_bn(c3, b3, t, 256, 1, 1, ACT_RELU, &r);
+        // 17 output channels fit no conv kernel's width rule (N % 4 == 0): the pack carries 20 rows, three of them zero, and the map 20 channels
+        Tensor heat = conv_bn(fp + ".1", fp + ".2", t, 17, 3, 1, ACT_NONE, nullptr, 20);
+        name_tensor(*this, "heat", heat.buf, {-1, heat.H, heat.W, heat.C}, maps_bf16() ? dt16() : 0);
+        return;
+    }
+    // final_predict is never called (:76-88): parameters only
     register_unused_conv_bn(*this, fp + ".0.conv1", fp + ".0.bn1", 128, 1024, 1);
     register_unused_conv_bn(*this, fp + ".0.conv2", fp + ".0.bn2", 128, 128, 3);
     register_unused_conv_bn(*this, fp + ".0.conv3", fp + ".0.bn3", 256, 128, 1);

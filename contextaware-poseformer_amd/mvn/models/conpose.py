@@ -14,8 +14,8 @@ import collections
 import torch
 from torch import nn
 
-from capf.lib import (KP_INTEGRAL, KP_MODES, PLAN_BN_BATCH_STATS, CapfError, Engine, input_constants, kp_head_backward,
-                      kp_head_forward, kp_head_forward_pair)
+from capf.lib import (KP_INTEGRAL, KP_MODES, PLAN_BN_BATCH_STATS, PLAN_CPN_PREDICT, CapfError, Engine, cpn_decode, input_constants,
+                      kp_head_backward, kp_head_forward, kp_head_forward_pair)
 
 from . import _native
 
@@ -227,6 +227,11 @@ class CA_PF(nn.Module):
         checkpoint's final_layer.* load by name, CPN gets a fresh head on its 256-channel feat0) and detect / forward_detect run it on
         feat0: "argmax" is the hard decode HRNet checkpoints are evaluated with (no gradient), "integral" the soft-argmax
         softmax(keypoint_beta * heatmap) whose weights train through the lifter (forward_detect under grad, fp32 models).
+        "cpn" (CPN backbones only, fp32 / bf16; anything else: ValueError): the head the CPN checkpoint itself carries,
+        backbone.refine_net.final_predict.* (refineNet.py:64-70), and CPN's own two-peak decode (cpn/test.py:79-108).  NO module and NO
+        parameter is added -- state_dict() is the default module's, the checkpoint's weights are the head --; the engines are created with
+        PLAN_CPN_PREDICT, so the backbone pass also leaves the heatmaps ("heat"), and detect / forward_detect decode them with
+        capf_cpn_decode.  The head has no derivative and belongs to the frozen backbone; the flip-test entries are not implemented for it.
         backbone_bn: what the frozen backbone's BatchNorm layers do while `self.backbone.training` is set.  "running" (default): the
         running statistics, folded into the convs, whatever the mode -- i.e. a frozen backbone left in .train() silently gets eval-mode
         BatchNorm.  "batch" (HRNet, fp32): the module honours self.backbone.training as torch does -- in train mode every forward
@@ -242,8 +247,11 @@ class CA_PF(nn.Module):
         if backbone_bn == "batch" and (compute_dtype != "fp32" or config.model.backbone.type not in ("hrnet_32", "hrnet_48")):
             raise ValueError("backbone_bn='batch' needs an HRNet backbone and compute_dtype='fp32' (got {!r}, {!r})".format(
                 config.model.backbone.type, compute_dtype))
-        if keypoint_head is not None and (not isinstance(keypoint_head, str) or keypoint_head not in KP_MODES):
-            raise ValueError("keypoint_head must be None, 'argmax' or 'integral', got {!r}".format(keypoint_head))
+        if keypoint_head is not None and (not isinstance(keypoint_head, str) or (keypoint_head not in KP_MODES and keypoint_head != "cpn")):
+            raise ValueError("keypoint_head must be None, 'argmax', 'integral' or 'cpn', got {!r}".format(keypoint_head))
+        if keypoint_head == "cpn" and config.model.backbone.type != "cpn":
+            raise ValueError("keypoint_head='cpn' is the CPN checkpoint's own head (refine_net.final_predict): it needs a CPN backbone, "
+                             "got {!r}".format(config.model.backbone.type))
         if not (isinstance(keypoint_beta, (int, float)) and 0.0 < float(keypoint_beta) < float("inf")):
             raise ValueError("keypoint_beta must be a positive finite number, got {!r}".format(keypoint_beta))
         super().__init__()
@@ -253,6 +261,8 @@ class CA_PF(nn.Module):
         self.keypoint_beta = float(keypoint_beta)
         if backbone_bn == "batch":
             plan_flags |= PLAN_BN_BATCH_STATS
+        if keypoint_head == "cpn":
+            plan_flags |= PLAN_CPN_PREDICT
         self.plan_flags = plan_flags               # capf.lib.PLAN_* bits: parity tests compare kernel families; 0 = product plan
         self.context_blocks = context_blocks       # False: the MPI-INF-3DHP variant (model/conpose.py)
         self.num_joints = config.model.backbone.num_joints
@@ -268,7 +278,8 @@ class CA_PF(nn.Module):
         if self._backbone_type == "cpn":
             _native.init_cpn_convs(self.backbone)
         _native.init_deformable_blocks(self.volume_net)
-        if keypoint_head is not None:             # (registered last, and only then: the default module's state_dict is the reference's)
+        if keypoint_head in KP_MODES:             # (registered last, and only then: the default module's state_dict is the reference's;
+                                                  # "cpn" registers nothing: its head is backbone.refine_net.final_predict)
             self.keypoint_head = KeypointHead(feat0_channels, self.num_joints)
 
         if config.model.backbone.fix_weights:
@@ -506,7 +517,7 @@ class CA_PF(nn.Module):
     # ---- detector-free: the 2-D keypoints from the native head on feat0 -------------------------
     def _head_params(self):
         if self.keypoint_head_mode is None:
-            raise CapfError("this model has no keypoint head: build it with keypoint_head='argmax' or 'integral'")
+            raise CapfError("this model has no keypoint head: build it with keypoint_head='argmax', 'integral' or 'cpn'")
         fl = self.keypoint_head.final_layer
         return fl.weight, fl.bias
 
@@ -557,17 +568,46 @@ class CA_PF(nn.Module):
                                                       decode, guard)
         return kcrop, score, (k2d if to_image is not None else None), guard
 
+    # ---- keypoint_head="cpn": the checkpoint's own final_predict (run by the backbone pass) and CPN's two-peak decode -------------
+    def _cpn_head_frozen(self):
+        """The head is part of the frozen backbone and has no derivative: a final_predict parameter that asks for a gradient is refused
+        as forward refuses backbone gradients."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.backbone.refine_net.final_predict.parameters()):
+            raise NotImplementedError("gradients of refine_net.final_predict are outside the hot path (keypoint_head='cpn' has no derivative): "
+                                      "freeze the backbone (fix_weights) or call under torch.no_grad()")
+
+    def _no_cpn_flip_test(self):
+        if self.keypoint_head_mode == "cpn":
+            raise NotImplementedError("keypoint_head='cpn' has no flip-test entry (CPN's own test-time flip averages the heatmaps without "
+                                      "a column shift; it is not implemented): use detect / forward_detect")
+
+    def _run_cpn_head(self, eng, images, to_image, stream):
+        """One backbone pass (final_predict included) and capf_cpn_decode on "heat": (kcrop_px, score, k2d | None), outside the graph."""
+        with torch.no_grad():
+            _run_backbone(self, eng, self._image_source(images), stream)
+            heat = eng.tensor_view("heat", images.shape[0])
+            sx, sy = float(images.shape[2]) / heat.shape[2], float(images.shape[1]) / heat.shape[1]
+            # CPN's convention, (4 x + 2) / data_shape of cpn/test.py:106-107 in crop pixels: a heatmap cell's centre
+            kcrop, score, k2d, _ = cpn_decode(heat, self.num_joints, (sx, 0.5 * sx, sy, 0.5 * sy), to_image)
+        return kcrop, score, k2d
+
     def detect(self, images, to_image=None):
         """The 2-D keypoints of the crops from the native head: backbone (one pass), final_layer on feat0 and the heatmap decode.
         images: [B,H,W,3] float32 (normalised, as forward takes them) or uint8 BGR crops (as forward_u8 takes them; the same bits).
         to_image: None, or float32 [B, 2, 3] -- per frame the matrix capf.lib.crop_to_image_matrix builds from the crop's center / scale
         and the camera resolution.  Returns (kcrop_px [B,J,2] in crop pixels, score [B,J], k2d [B,J,2] normalised image coordinates or
-        None): what forward() takes as its third and second argument.  No gradients (see forward_detect)."""
-        self._head_params()
+        None): what forward() takes as its third and second argument.  No gradients (see forward_detect).
+        keypoint_head="cpn": the backbone pass runs final_predict too and capf_cpn_decode decodes its heatmaps; score is CPN's
+        r0 = heatmap / 255 + 0.5 at the keypoint."""
+        cpn = self.keypoint_head_mode == "cpn"
+        if not cpn:
+            self._head_params()
         images, to_image = self._detect_inputs(images, to_image)
         dev = images.device
         with torch.cuda.device(dev), torch.no_grad():
             eng = self._engine_at(dev, images.shape[1], images.shape[2])
+            if cpn:
+                return self._run_cpn_head(eng, images, to_image, torch.cuda.current_stream(dev).cuda_stream)
             feat0 = self._backbone_maps(eng, images, torch.cuda.current_stream(dev).cuda_stream)
             kcrop, score, k2d, _ = self._run_head(eng, feat0, to_image, images.shape[1], images.shape[2], False)
         return kcrop, score, k2d
@@ -582,8 +622,13 @@ class CA_PF(nn.Module):
         ignores a shift).  A loss on kcrop_px itself (KeypointsMSELoss against 2-D labels) trains the head too.  The backward re-reads feat0
         from the workspace (the lifter's training forward and backward only read the maps): run it before the next forward of this model.
         An "argmax" head with trainable parameters, or a 16-bit model with a trainable head, raises under grad instead of dropping the
-        gradients."""
-        trains = self._head_trains()
+        gradients.
+        keypoint_head="cpn": final_predict and capf_cpn_decode take the head's place; the head has no derivative (a final_predict
+        parameter that requires grad raises under grad), the lifter trains as in forward()."""
+        cpn = self.keypoint_head_mode == "cpn"
+        if cpn:
+            self._cpn_head_frozen()
+        trains = False if cpn else self._head_trains()
         if to_image is None:
             raise ValueError("forward_detect needs to_image [B, 2, 3]: the lifter takes the keypoints in normalised image coordinates too")
         images, to_image = self._detect_inputs(images, to_image)
@@ -592,9 +637,12 @@ class CA_PF(nn.Module):
             eng = self._engine_at(dev, H, W)
             stream = torch.cuda.current_stream(dev).cuda_stream
             named = self._lifter_step_params(trains)
-            with torch.no_grad():
-                feat0 = self._backbone_maps(eng, images, stream)
-            kcrop, score, k2d, guard = self._run_head(eng, feat0, to_image, H, W, trains)
+            if cpn:
+                (kcrop, score, k2d), guard = self._run_cpn_head(eng, images, to_image, stream), None
+            else:
+                with torch.no_grad():
+                    feat0 = self._backbone_maps(eng, images, stream)
+                kcrop, score, k2d, guard = self._run_head(eng, feat0, to_image, H, W, trains)
             # (a crop-keypoint tensor outside the graph would be normalised in place by the lifter: it gets a copy, the caller the pixels)
             ref = kcrop.detach().clone() if named is None else kcrop if kcrop.requires_grad else kcrop.clone()
             out = self._run_lifter(eng, _Source("workspace", dev, B, "the maps", None), k2d, ref, named)
@@ -652,7 +700,8 @@ class CA_PF(nn.Module):
         stem's load), float32 [B,H,W,3] (the mirrored half is torch.flip(images, [2])), or the float32 [2,B,H,W,3] stack of
         capf.lib.preprocess(mode=2) -- the same bits.  to_image as in detect.  flip_pairs: None -- the H36M table -- or a swap table of J ints
         (capf.lib.MPI_SWAP).  Returns (kcrop_px [B,J,2], score [B,J], k2d [B,J,2] | None).  Always runs without
-        grad and returns detached tensors: the paired decode has no backward."""
+        grad and returns detached tensors: the paired decode has no backward.  keypoint_head="cpn": NotImplementedError."""
+        self._no_cpn_flip_test()
         self._head_params()
         swap = self._swap_table(flip_pairs)
         src, B, H, W, to_image = self._flip_test_source(images, to_image)
@@ -666,8 +715,9 @@ class CA_PF(nn.Module):
         the stacked keypoints the head wrote (set 1 mirrored as capf_preprocess_points(mode=2) does), capf_fliptest_fuse (its _swap form with
         flip_pairs).  Returns (joints3d [B,1,J,3], kcrop_px [B,J,2], score [B,J]); kcrop_px stays in crop pixels.  The result equals
         forward_flip_test on the stack with detect_flip_test's keypoints pushed through preprocess_points(mode=2), bit for bit.  Always runs
-        without grad and returns detached tensors."""
+        without grad and returns detached tensors.  keypoint_head="cpn": NotImplementedError."""
         from capf.lib import fliptest_fuse
+        self._no_cpn_flip_test()
         self._head_params()
         if to_image is None:
             raise ValueError("forward_detect_flip_test needs to_image [B, 2, 3]: the lifter takes the keypoints in normalised image coordinates too")

@@ -124,7 +124,17 @@ enum capf_plan_flag {
                                      * capf_num_ops, capf_op_info, the accounting entries, every other entry's bits -- is the flagless handle's and
                                      * describes the running-statistics route; capf_workspace_bytes grows by the statistics scratch and the pack arena
                                      * by an unfolded copy of every conv pack.  Cannot be combined with CAPF_PLAN_BF16_F32_STREAM.                  */
-    CAPF_PLAN_F32X3_EXACT = 256     /* ... on round 4's tile instead of the default one: every operand split EXACTLY into three bf16 pieces,
+    CAPF_PLAN_CPN_PREDICT = 131072, /* OPT-IN, CAPF_CPN50 with CAPF_F32 or CAPF_BF16 (CAPF_HRNET: CAPF_ERR_UNSUPPORTED): the backbone also runs the detector head a
+                                     * CPN checkpoint was trained with, backbone.refine_net.final_predict (refineNet.py:64-70, :86-88), behind the four cascades:
+                                     * a channel concatenation of feat0..3 into a [B, 64, 48, 1024] buffer of its own (torch.cat(refine_fms, 1); feat0..3 are
+                                     * neither moved nor aliased), the Bottleneck's four conv + BatchNorm ops (final_predict.0.conv1 / conv2 / downsample.0 /
+                                     * conv3, the shortcut on a second lane) and final_predict.1 / .2, conv3x3(256 -> 17) + BatchNorm without activation, whose
+                                     * pack carries 20 rows (17..19: zero weights, zero folded bias) because no conv kernel takes N % 4 != 0.  Result: the
+                                     * named tensor "heat" [B, 64, 48, 20] in the plan's activation dtype, channels 17..19 exact zeros, alive to the end of the
+                                     * run like feat0..3 -- the input of capf_cpn_decode.  These are backbone ops: capf_backbone_forward(_u8) and capf_forward*
+                                     * run them.  The schema (names, order, shapes) is the unflagged plan's; the unflagged plan itself is unchanged and keeps
+                                     * the head as parameters only.  capf_workspace_bytes grows by the concatenation, the head's intermediates and heat.   */
+    CAPF_PLAN_F32X3_EXACT = 256    /* ... on round 4's tile instead of the default one: every operand split EXACTLY into three bf16 pieces,
                                      * six piece products per fp32 MAC (igemm_f32x3_ws.hip).  The default (ABI 5) carries an operand as two
                                      * block-scaled fp16 pieces (to 2^-23) and issues three products: half the MFMAs, the same measured
                                      * distance to an fp64 evaluation (see capf_op_conv_f32h2_group)                                      */
@@ -155,7 +165,8 @@ const char* capf_version(void);
  * capf_op_*_16 entry points (the 16-bit kernels for either element format) and capf_debug_f16_round; struct layouts unchanged
  * (additive: capf_set_map_grad_mode, capf_map_grad_mode; CAPF_PLAN_BN_BATCH_STATS, capf_backbone_forward_bn, capf_op_bn_stats_scratch_bytes,
  * capf_op_bn_stats, capf_op_bn_apply; capf_backward_points; capf_kp_head_scratch_bytes, capf_kp_head_forward, capf_kp_head_backward;
- * capf_kp_head_pair_scratch_bytes, capf_kp_head_forward_pair).                                                                              */
+ * capf_kp_head_pair_scratch_bytes, capf_kp_head_forward_pair; CAPF_PLAN_CPN_PREDICT, the named tensor "heat", capf_cpn_decode,
+ * capf_cpn_decode_taps, capf_cpn_decode_lds_bytes).                                                                                         */
 #define CAPF_ABI_VERSION 12
 int capf_abi_version(void);
 
@@ -415,6 +426,8 @@ int capf_set_debug(capf_handle* h, int on);
 
 /* Intermediates of the LAST forward, for stage-level parity tests.  Names:
  *   feat0..feat3   context maps, NHWC [B,h,w,C_l]
+ *   heat           CAPF_PLAN_CPN_PREDICT handles only: final_predict's heatmaps, NHWC [B,64,48,20] in the context maps' format (fp32 / bf16),
+ *                  channels 17..19 exact zeros; reserved to the end of the run like feat0..3 (the input of capf_cpn_decode)
  *   sampled0..3    reference-point samples [B,17,C_l]          (pose_dformer.py:216-218)
  *   idx0..idx3     int32 [B,17,2] (ix0, iy0) bilinear NW corner of those samples (bit-exact check)
  *   cpos0..3       with capf_set_debug: sampling positions of DeformableBlock i, fp32 [B,17,L*16,2] (level, head*4+sample)
@@ -828,6 +841,48 @@ size_t capf_kp_head_pair_scratch_bytes(int Bsrc, int H, int W, int C, int J);
 int capf_kp_head_forward_pair(void* stream, const void* map_nhwc, int map_dtype, const float* weight, const float* bias, int Bsrc, int H, int W,
                               int C, int J, int mode, float beta, const int32_t* swap, int shift, const float decode[4], const float* to_image,
                               float mirror_width, float* kcrop2, float* k2d2, float* score, float* heat, void* scratch, size_t scratch_bytes);
+/* ---- CPN's own heatmap decode: two peaks of the blurred map, a quarter pixel from the first towards the second ------------------------------
+ * What cpn/test.py:79-108 does with the heatmaps of refine_net.final_predict (the named tensor "heat" of a CAPF_PLAN_CPN_PREDICT handle; any
+ * other NHWC map of that layout does too), as ONE launch: one workgroup per (frame, joint), the planes in LDS, no scratch, no atomics
+ * (csrc/cpn_decode.hip).  Stand-alone entry on device pointers.  Additive inside revision 12.
+ *   heat_nhwc [B, H, W, C] of heat_dtype (capf_dtype: fp32, bf16 or fp16; a 16-bit value is widened exactly), 16-byte aligned (8 for a 16-bit map);
+ *   joint j is channel j.  1 <= J <= C <= 32, H, W >= 1, and capf_cpn_decode_lds_bytes(H, W) = 256 + 8 (H + 20)(W + 20) + 4 H W <= 160 KiB, the
+ *   LDS of a compute unit: 64 x 48 (this plan) and 96 x 72 (upstream CPN at 384 x 288) fit; what does not: CAPF_ERR_UNSUPPORTED.
+ * Per (b, j), z = the H x W heatmap as fp32:
+ *   M  = max z;  r0 = z / 255 + 0.5 (fp32, both operations rounded);  n = z / M (fp32, IEEE division)
+ *   P  = (H + 20) x (W + 20) float64, zero but for P[10 + y][10 + x] = n[y][x]
+ *   g  = the 21 taps of capf_cpn_decode_taps: g_i = e_i / sum(e), e_i = exp(-(i - 10)^2 / (2 * 3.5^2)) in double on the host (3.5 is OpenCV's
+ *        sigma for ksize 21, sigma 0: 0.3 ((21 - 1) / 2 - 1) + 0.8); bit-symmetric (g_i == g_{20 - i}) and summing to 1 within 2^-52
+ *   D  = the separable blur of P, rows pass first, reflect-101 borders ON P (r(t) = -t for t < 0, 2 (n - 1) - t for t >= n), float64, in ONE
+ *        summation order, every step an fma rounded once:
+ *            R[y][x] = acc after  acc = +0;  for i = 0 .. 20 ascending:  acc = fma(g_i, P[y][r(x + i - 10)], acc)        (all rows of P)
+ *            D[y][x] = acc after  acc = +0;  for i = 0 .. 20 ascending:  acc = fma(g_i, R[r(y + i - 10)][x], acc)
+ *   (y1, x1) = the FIRST maximum of D in row-major order;  D[y1][x1] = 0;  (y2, x2) = the first maximum again (the zeroed cell competes)
+ *   x = x1 - 10, y = y1 - 10, px = x2 - x1, py = y2 - y1, ln = sqrt(px^2 + py^2) in double;  if ln > 1e-3: x += (0.25 px) / ln, y += (0.25 py) / ln
+ *   x clamped to [0, W - 1], y to [0, H - 1];  score = r0[round(y)][round(x)] (the fraction is 0 or at most 0.25 either way: never a half)
+ * Outputs: x and y are converted to fp32 first; kcrop[b, j] = (sx x + ox, sy y + oy) with decode = {sx, ox, sy, oy}, product rounded, then the sum
+ *   (CPN's convention: sx = W_img / W, ox = sx / 2, the same in y -- (4 x + 2) / data_shape of cpn/test.py:106-107 for any crop whose heatmap is
+ *   a quarter of it per axis, and for the 384 x 288 crops whose heatmap is still 64 x 48); k2d[b, j] = ((A00 kx + A01 ky) + A02, (A10 kx + A11 ky)
+ *   + A12) for to_image [B, 2, 3] fp32, every operation rounded on its own, as capf_kp_head_forward states it; to_image == NULL: k2d is not
+ *   written.  score [B, J] and blurred [B, J, H + 20, W + 20] float64 (D before the zeroing; 8-byte aligned) are optional (NULL).
+ * Degenerate maps: M == 0, or any NaN / +-Inf among the H W values of (b, j): its keypoint (both coordinate systems), its score and its plane of
+ *   `blurred` are NaN; every other joint and frame is untouched.  M < 0 follows the arithmetic literally, as the reference would (n = z / M is then
+ *   >= 1 wherever z <= M: the "peaks" are the map's minima).  A quotient z / M that overflows (|M| subnormal) is outside the contract: a NaN or
+ *   Inf of D never wins a comparison here, where numpy's argmax would take a NaN.
+ * A (frame, joint)'s result bits depend on its H W values alone: not on B, J, C, its position, the run or the device buffer.
+ * PARITY UNPINNED in the last bits of D: OpenCV is absent from the build machine, so nothing pins cv2.GaussianBlur's own summation order, its tap
+ *   rounding or its vector width; D is bit-exact against the restatement above (tests/cpn_decode_oracle.py holds it within 44 x 2^-53 x blur(|P|),
+ *   two passes of 21 fma), and the integer peaks and the direction of the shift do not depend on those bits whenever the peaks are separated by more than
+ *   that -- which is what the tests establish (they count the cases that are not, and bound their share).
+ * Refusals, all before anything is launched (no device needed): a NULL map / decode / kcrop, k2d without to_image, B, H, W, J or C out of range
+ *   (J > C, C > 32), an unknown dtype, a misaligned map / kcrop / blurred: CAPF_ERR_INVALID; planes beyond the LDS: CAPF_ERR_UNSUPPORTED.
+ * Cost (MI355X, medians of 20 around the host call, tools/bench_cpn_detect.py, EXPERIMENTS.md R29.1): 0.25 ms for 128 frames x 17 joints of a
+ *   bf16 64 x 48 map, 0.19 ms for 64 frames of an fp32 one, against 7.2 / 5.8 ms of capf_backbone_forward under CAPF_PLAN_CPN_PREDICT (which the
+ *   head itself makes 1.3 / 1.5 ms longer than the unflagged plan's 6.0 / 4.4 ms: the concat 0.31, the five convs 0.96 / 1.15 ms). */
+void capf_cpn_decode_taps(double taps[21]);
+size_t capf_cpn_decode_lds_bytes(int H, int W);       /* 0: H or W out of range */
+int capf_cpn_decode(void* stream, const void* heat_nhwc, int heat_dtype, int B, int H, int W, int C, int J, const float decode[4],
+                    const float* to_image, float* kcrop, float* k2d, float* score, double* blurred);
 /* capf_pck_counts: the MPI-INF-3DHP evaluation (ContextPose_mpi/3dhp_test/test_util, MATLAB: mpii_test_predictions_py.m,
  *   mpii_evaluate_errors.m, mpii_compute_3d_pck.m), which callers otherwise export to .mat files and run off the GPU; capf_pose_errors /
  *   capf_segment_sums serve H36M only.  Per pose i of pred / gt [n, joints, 3] (same unit; to_mm converts it to mm): gt made relative to

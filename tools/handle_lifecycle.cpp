@@ -1,6 +1,6 @@
 // Host sanitizer check of a handle's life, no GPU needed: creates and destroys plan-only handles of the three backbones, asks each the
 // questions a host asks before it has a device (schema, workspace size, op table), makes every run entry refuse it, walks the refusal paths
-// of the stand-alone keypoint head entries (capf_kp_head_forward / capf_kp_head_backward: arguments judged before any launch), and lets capf_create
+// of the stand-alone keypoint head entries (capf_kp_head_forward / capf_kp_head_backward / capf_cpn_decode: arguments judged before any launch), and lets capf_create
 // fail both in front of the plan (a refused configuration) and behind it (a device that is not there: the branch that releases what a
 // handle already owns).  Built by `make -C contextaware-poseformer_amd/csrc hostcheck`: the engine's host sources with
 // -fsanitize=address,undefined, the device objects of the product build; it runs on the build machine and is not loaded into Python.
@@ -42,9 +42,17 @@ int main() {
     for (int backbone : {CAPF_HRNET, CAPF_CPN50})
         for (int width : {32, 48})
             for (int dtype : {CAPF_F32, CAPF_BF16})
-            for (int flags : {0, (int)CAPF_PLAN_BN_BATCH_STATS}) {      // (the flag: the batch-statistics route's units and unfolded packs next to the plan)
+            for (int flags : {0, (int)CAPF_PLAN_BN_BATCH_STATS, (int)CAPF_PLAN_CPN_PREDICT}) {      // (the batch-statistics route's units and unfolded packs
+                                                                                                    // next to the plan; CPN's final_predict head behind the cascades)
                 if (backbone == CAPF_CPN50 && width == 48) continue;
-                if (flags && (backbone != CAPF_HRNET || dtype != CAPF_F32)) continue;
+                if (flags == CAPF_PLAN_BN_BATCH_STATS && (backbone != CAPF_HRNET || dtype != CAPF_F32)) continue;
+                if (flags == CAPF_PLAN_CPN_PREDICT && backbone != CAPF_CPN50) {      // refused in front of the plan, by name
+                    capf_config r = config(backbone, width, dtype, 1);
+                    r.plan_flags = flags;
+                    capf_handle* none = nullptr;
+                    CHECK(capf_create(&r, -1, &none) == CAPF_ERR_UNSUPPORTED && !none && strstr(capf_last_error(nullptr), "CAPF_PLAN_CPN_PREDICT"));
+                    continue;
+                }
                 capf_config c = config(backbone, width, dtype, 1);
                 c.plan_flags = flags;
                 capf_handle* h = nullptr;
@@ -68,6 +76,13 @@ int main() {
                 CHECK(capf_set_features(h, nullptr, maps, 2) == (dtype == CAPF_F32 ? CAPF_ERR_STATE : CAPF_ERR_UNSUPPORTED));
                 CHECK(capf_forward_prefix(h, nullptr, mem, nullptr, nullptr, 2, nullptr, 1) == CAPF_ERR_STATE);
                 CHECK(capf_forward_profile(h, nullptr, mem, mem, mem, 2, mem, mem, n - 1) == CAPF_ERR_INVALID);
+                {   // the named tensor of the head exists under its flag alone
+                    int64_t shape[4];
+                    int nd = 0;
+                    const int rc = capf_tensor(h, "heat", nullptr, shape, &nd);
+                    CHECK(flags == CAPF_PLAN_CPN_PREDICT ? (rc == (dtype == CAPF_F32 ? 0 : 2) && nd == 4 && shape[1] == 64 && shape[2] == 48 && shape[3] == 20)
+                                                         : rc == CAPF_ERR_INVALID);
+                }
                 CHECK(capf_set_workspace(h, mem, sizeof(mem)) == CAPF_OK && capf_train_generation(h) == 1);
                 capf_destroy(h);
                 ++handles;
@@ -94,6 +109,26 @@ int main() {
         CHECK(capf_kp_head_backward(nullptr, mem, nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, nullptr, mem, nullptr, 0, big, sizeof(big)) == CAPF_ERR_INVALID);
         CHECK(capf_kp_head_backward(nullptr, mem, nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, mem, mem, big + 1, 1, big, sizeof(big)) == CAPF_ERR_INVALID);
         CHECK(capf_kp_head_backward(nullptr, mem, nullptr, big, CAPF_F32, mem, mem, 2, 8, 8, 32, 17, 1, 1.f, dec, nullptr, mem, mem, nullptr, 0, big, fwd) == CAPF_ERR_INVALID);
+    }
+    // ... and capf_cpn_decode
+    {
+        const float dec[4] = {4.f, 2.f, 4.f, 2.f};
+        alignas(16) static float big[64];
+        double taps[21];
+        capf_cpn_decode_taps(taps);
+        double sum = 0.0;
+        for (int i = 0; i < 21; ++i) { CHECK(taps[i] == taps[20 - i] && taps[i] > 0.0); sum += taps[i]; }
+        CHECK(sum > 1.0 - 1e-14 && sum < 1.0 + 1e-14);
+        CHECK(capf_cpn_decode_lds_bytes(64, 48) == 256 + 8 * 84 * 68 + 4 * 64 * 48 && capf_cpn_decode_lds_bytes(0, 48) == 0);
+        CHECK(capf_cpn_decode(nullptr, nullptr, CAPF_F32, 2, 8, 8, 20, 17, dec, nullptr, mem, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode(nullptr, big, CAPF_F32, 2, 8, 8, 20, 17, dec, nullptr, nullptr, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode(nullptr, big, CAPF_F32, 2, 8, 8, 20, 21, dec, nullptr, mem, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode(nullptr, big, CAPF_F32, 2, 8, 8, 33, 17, dec, nullptr, mem, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode(nullptr, big, CAPF_F32, 2, 0, 8, 20, 17, dec, nullptr, mem, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode(nullptr, big + 1, CAPF_F32, 2, 8, 8, 20, 17, dec, nullptr, mem, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode(nullptr, big, 3, 2, 8, 8, 20, 17, dec, nullptr, mem, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode(nullptr, big, CAPF_F32, 2, 8, 8, 20, 17, dec, nullptr, mem, mem, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode(nullptr, big, CAPF_BF16, 2, 128, 128, 20, 17, dec, nullptr, mem, nullptr, nullptr, nullptr) == CAPF_ERR_UNSUPPORTED);
     }
     // refused in front of the plan, inside it, and behind it (no device 0 on a machine without a GPU: what the handle owns is released)
     capf_handle* h = nullptr;
