@@ -45,6 +45,7 @@ EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.p
     "capf_kp_head_scratch_bytes", "capf_kp_head_forward", "capf_kp_head_backward",
     "capf_kp_head_pair_scratch_bytes", "capf_kp_head_forward_pair",
     "capf_cpn_decode", "capf_cpn_decode_taps", "capf_cpn_decode_lds_bytes",
+    "capf_cpn_decode_pair",
 ]
 
 
@@ -261,6 +262,7 @@ def load_library():
     lib.capf_kp_head_pair_scratch_bytes.restype = c_size_t
     lib.capf_kp_head_forward_pair.argtypes = [P, P, c_int, P, P] + [c_int] * 6 + [c_float, POINTER(c_int32), c_int, F3, P, c_float, P, P, P, P, P, c_size_t]
     lib.capf_cpn_decode.argtypes = [P, P] + [c_int] * 6 + [F3, P, P, P, P, P]
+    lib.capf_cpn_decode_pair.argtypes = [P, P] + [c_int] * 6 + [POINTER(c_int32), F3, P, c_float, P, P, P, P, P]
     lib.capf_cpn_decode_taps.argtypes = [POINTER(c_double)]
     lib.capf_cpn_decode_taps.restype = None
     lib.capf_cpn_decode_lds_bytes.argtypes = [c_int, c_int]
@@ -1142,6 +1144,45 @@ def cpn_decode(heat, joints=None, decode=(1.0, 0.0, 1.0, 0.0), to_image=None, wa
 # the H36M skeleton's mirror table: joints_left [4, 5, 6, 11, 12, 13] <-> joints_right [1, 2, 3, 14, 15, 16] (mvn/datasets/utils.py:12-13;
 # kSwap of csrc/preprocess.hip, the table capf_fliptest_fuse and capf_preprocess_points apply)
 H36M_SWAP = (0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13)
+# the mirror table of a checkpoint whose 17 channels are in COCO order: nose | eyes | ears | shoulders | elbows | wrists | hips | knees | ankles
+# (upstream CPN's cfg.symmetry).  The defaults stay H36M_SWAP: the keypoints of this module feed the H36M lifter.
+COCO_SWAP = (0, 2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11, 14, 13, 16, 15)
+
+
+def cpn_decode_pair(heat2, joints=None, swap=None, decode=(1.0, 0.0, 1.0, 0.0), to_image=None, mirror_width=192.0, want_score=True,
+                    want_blurred=False, want_fused=False):
+    """capf_cpn_decode_pair on the contiguous NHWC heatmaps heat2 [2 * Bsrc, H, W, C] of a flip-test pair (frame Bsrc + b the mirror of frame b,
+    the order of capf_preprocess mode 2; Engine.tensor_view("heat", 2 * Bsrc) of a PLAN_CPN_PREDICT handle): CPN's test-time flip -- per joint
+    the heatmap of the crop and the mirrored-back heatmap of its mirror (x mirrored, joints exchanged by `swap`, no column shift) are averaged
+    and decoded once with cpn_decode's rule.  joints: channels 0 .. joints - 1 (default: all C).  swap: J ints, swap[j] = the joint of the
+    mirror that lands on joint j, its own inverse; None: H36M_SWAP (J = 17 only).  to_image [Bsrc, 2, 3].
+    Returns (kcrop2 [2, Bsrc, J, 2], score [Bsrc, J] | None, k2d2 [2, Bsrc, J, 2] | None, blurred [Bsrc, J, H + 20, W + 20] float64 | None,
+    fused [Bsrc, J, H, W] | None -- the averaged heatmaps): kcrop2 / k2d2 are the stacks forward_flip_test takes, set 1 mirrored like
+    preprocess_points(mode=2) with `mirror_width` in place of its 192."""
+    import torch
+    dtype = _kp_map_dtype(heat2)
+    if heat2.shape[0] % 2:
+        raise CapfError(f"a flip-test pair holds 2 * Bsrc frames ([orig | mirrored]), not {heat2.shape[0]}")
+    Bsrc, H, W, C = heat2.shape[0] // 2, heat2.shape[1], heat2.shape[2], heat2.shape[3]
+    J = C if joints is None else int(joints)
+    if swap is None:
+        if J != 17:
+            raise CapfError(f"swap=None means the H36M table (17 joints); a decode of {J} joints needs its own table")
+        swap = H36M_SWAP
+    tab = [int(v) for v in swap]
+    if len(tab) != J:
+        raise CapfError(f"swap has {len(tab)} entries for {J} joints")
+    if to_image is not None and (tuple(to_image.shape) != (Bsrc, 2, 3) or to_image.dtype != torch.float32 or not to_image.is_contiguous()):
+        raise CapfError(f"to_image must be contiguous fp32 [{Bsrc}, 2, 3], not {tuple(to_image.shape)} {to_image.dtype}")
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=heat2.device)
+    kcrop2 = new(2, Bsrc, J, 2)
+    k2d2 = new(2, Bsrc, J, 2) if to_image is not None else None
+    score = new(Bsrc, J) if want_score else None
+    blurred = torch.empty(Bsrc, J, H + 20, W + 20, dtype=torch.float64, device=heat2.device) if want_blurred else None
+    fused = new(Bsrc, J, H, W) if want_fused else None
+    _call("capf_cpn_decode_pair", _stream(heat2), _p(heat2), dtype, Bsrc, H, W, C, J, (c_int32 * max(J, 1))(*tab),
+          (c_float * 4)(*[float(v) for v in decode]), _p(to_image), float(mirror_width), _p(kcrop2), _p(k2d2), _p(score), _p(blurred), _p(fused))
+    return kcrop2, score, k2d2, blurred, fused
 
 
 def kp_head_forward_pair(x2, weight, bias=None, mode=KP_ARGMAX, beta=1.0, swap=None, shift=True, decode=(1.0, 0.0, 1.0, 0.0), to_image=None,

@@ -14,6 +14,12 @@
 // LDS banking: both planes are dense (pitch = width), a wave's 64 cells are 64 consecutive indices, and tap i of either pass reads them at one
 // common offset -- 64 consecutive fp32 / fp64 words (two at a row end), conflict-free for ds_read_b32 / ds_read_b64 at any pitch, even ones
 // included; the column pass needs no padding column.
+//
+// Flip-test pair (capf_cpn_decode_pair), the PAIR instantiations of the same kernel: the map holds [2 B] frames, frame B + b the mirror of source
+// frame b, and workgroup (b, j) loads zf = 0.5f * (z[b, y, x, j] + z[B + b, y, W - 1 - x, swap[j]]) where the single form loads z (cpn/test.py:62-70:
+// cv2.flip(.., 1), the symmetric joints exchanged, no column shift; the fp32 sum rounded once, then halved).  Planes, passes, reductions and
+// their orders are the single form's; the score re-reads BOTH frames, and the workgroup also writes joint swap[j] of the mirrored set of the
+// stacks -- swap is a permutation, so every element has one writer.
 #include <math.h>
 
 #include "fmt16.h"
@@ -61,6 +67,24 @@ void cpn_decode_taps(double g[CPN_TAPS]) {
     }
 }
 
+template <bool PAIR> struct CpnArgsOf { typedef CpnDecodeArgs type; };
+template <> struct CpnArgsOf<true> { typedef CpnPairArgs type; };
+
+// pixel p of the map the decode works on: the frame's own value, or (PAIR) its fold with the mirror frame's -- zm points at channel swap[j] of
+// frame B + b
+template <class L, bool PAIR>
+__device__ __forceinline__ float cpn_pixel(const typename L::T* __restrict__ z, const typename L::T* __restrict__ zm, const int p, const int W,
+                                           const int C) {
+    const float zo = L::ld(z + (size_t)p * C);
+    if constexpr (PAIR) {
+        const int x = p % W;                                             // row y = p / W: column W - 1 - x of it is pixel p - x + (W - 1 - x)
+        const float sum = zo + L::ld(zm + (size_t)(p - x + (W - 1 - x)) * C);       // (the sum rounded to fp32 ...
+        return 0.5f * sum;                                               //  ... then halved)
+    } else {
+        return zo;
+    }
+}
+
 struct CpnBest { double v; int i; };
 __device__ __forceinline__ bool cpn_better(const double v, const int i, const CpnBest& b) { return v > b.v || (v == b.v && i < b.i); }
 
@@ -84,8 +108,8 @@ __device__ __forceinline__ CpnBest cpn_block_best(CpnBest b, double* red_v, int*
 
 __device__ __forceinline__ int cpn_reflect(const int t, const int n) { return t < 0 ? -t : t >= n ? 2 * (n - 1) - t : t; }   // reflect-101, |overhang| <= 10 < n
 
-template <class L>
-__global__ void __launch_bounds__(CPN_THREADS) cpn_decode_kernel(const CpnDecodeArgs a) {
+template <class L, bool PAIR>
+__global__ void __launch_bounds__(CPN_THREADS) cpn_decode_kernel(const typename CpnArgsOf<PAIR>::type a) {
     extern __shared__ double cpn_lds[];
     const int tid = threadIdx.x;
     const int H = a.H, W = a.W, HW = H * W, Hp = H + 2 * CPN_BORDER, Wp = W + 2 * CPN_BORDER, cells = Hp * Wp;
@@ -97,13 +121,22 @@ __global__ void __launch_bounds__(CPN_THREADS) cpn_decode_kernel(const CpnDecode
     const int b = (int)blockIdx.x / a.J, j = (int)blockIdx.x - b * a.J;
     const typename L::T* __restrict__ z = static_cast<const typename L::T*>(a.heat) + (size_t)b * HW * a.C + j;
     const size_t o = (size_t)blockIdx.x;                                 // = b * J + j
+    const typename L::T* __restrict__ zm = nullptr;
+    size_t om = 0;                                                       // PAIR: (b, swap[j]) of the mirrored set of the stacks
+    if constexpr (PAIR) {
+        const int js = a.swap.j[j];
+        zm = static_cast<const typename L::T*>(a.heat) + ((size_t)a.B + b) * HW * a.C + js;
+        om = ((size_t)a.B + b) * a.J + js;
+    }
 
     // ---- the map, its maximum, and whether every value is finite
     float m = -INFINITY;
     int bad = 0;
     for (int p = tid; p < HW; p += CPN_THREADS) {
-        const float v = L::ld(z + (size_t)p * a.C);
+        const float v = cpn_pixel<L, PAIR>(z, zm, p, W, a.C);
         n[p] = v;
+        if constexpr (PAIR)
+            if (a.fused) a.fused[o * HW + p] = v;
         if (!(fabsf(v) <= 3.4028234663852886e38f)) bad = 1;              // NaN or +-Inf
         if (v > m) m = v;
     }
@@ -131,6 +164,10 @@ __global__ void __launch_bounds__(CPN_THREADS) cpn_decode_kernel(const CpnDecode
             a.kcrop[o * 2] = fn; a.kcrop[o * 2 + 1] = fn;
             if (a.k2d) { a.k2d[o * 2] = fn; a.k2d[o * 2 + 1] = fn; }
             if (a.score) a.score[o] = fn;
+            if constexpr (PAIR) {
+                a.kcrop[om * 2] = fn; a.kcrop[om * 2 + 1] = fn;
+                if (a.k2d) { a.k2d[om * 2] = fn; a.k2d[om * 2 + 1] = fn; }
+            }
         }
         return;
     }
@@ -184,39 +221,61 @@ __global__ void __launch_bounds__(CPN_THREADS) cpn_decode_kernel(const CpnDecode
     x = fmax(0.0, fmin(x, (double)(W - 1)));
     y = fmax(0.0, fmin(y, (double)(H - 1)));
     const int rx = (int)rint(x), ry = (int)rint(y);                      // (the fraction is 0 or at most 0.25 either way: never a half)
-    const float zs = L::ld(z + (size_t)(ry * W + rx) * a.C);
+    const float zs = cpn_pixel<L, PAIR>(z, zm, ry * W + rx, W, a.C);     // (PAIR: r0 is taken from the fused map -- both frames again)
     const float sc = zs / 255.0f + 0.5f;                                 // r0 = z / 255 + 0.5, both rounded to fp32
     const float xf = (float)x, yf = (float)y;
     const float kx = a.dec[0] * xf + a.dec[1], ky = a.dec[2] * yf + a.dec[3];      // (contraction is off: product rounded, then the sum)
     a.kcrop[o * 2] = kx;
     a.kcrop[o * 2 + 1] = ky;
     if (a.score) a.score[o] = sc;
+    if constexpr (PAIR) {                                                // capf_preprocess_points(mode = 2)'s mirrored set, joint swap[j]
+        a.kcrop[om * 2] = (a.mirror_w - kx) - 1.0f;                      // (two rounded subtractions)
+        a.kcrop[om * 2 + 1] = ky;
+    }
     if (a.k2d) {
         const float* A = a.to_image + (size_t)b * 6;
-        a.k2d[o * 2] = (A[0] * kx + A[1] * ky) + A[2];
-        a.k2d[o * 2 + 1] = (A[3] * kx + A[4] * ky) + A[5];
+        if constexpr (PAIR) {
+            const float ix = (A[0] * kx + A[1] * ky) + A[2], iy = (A[3] * kx + A[4] * ky) + A[5];
+            a.k2d[o * 2] = ix;
+            a.k2d[o * 2 + 1] = iy;
+            a.k2d[om * 2] = -ix;
+            a.k2d[om * 2 + 1] = iy;
+        } else {                                                         // (statement for statement what the single form always was)
+            a.k2d[o * 2] = (A[0] * kx + A[1] * ky) + A[2];
+            a.k2d[o * 2 + 1] = (A[3] * kx + A[4] * ky) + A[5];
+        }
     }
 }
 
-template <class L>
-static hipError_t launch_cpn_decode_t(const CpnDecodeArgs& a, size_t lds, hipStream_t s) {
+template <class L, bool PAIR>
+static hipError_t launch_cpn_decode_t(const typename CpnArgsOf<PAIR>::type& a, size_t lds, hipStream_t s) {
     static DynLdsAttr attr;
-    const hipError_t e = attr.ensure(reinterpret_cast<const void*>(&cpn_decode_kernel<L>), (int)CPN_LDS_LIMIT);
+    const hipError_t e = attr.ensure(reinterpret_cast<const void*>(&cpn_decode_kernel<L, PAIR>), (int)CPN_LDS_LIMIT);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((cpn_decode_kernel<L>), dim3((unsigned)(a.B * a.J)), dim3(CPN_THREADS), lds, s, a);
+    hipLaunchKernelGGL((cpn_decode_kernel<L, PAIR>), dim3((unsigned)(a.B * a.J)), dim3(CPN_THREADS), lds, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_cpn_decode(CpnDecodeArgs a, hipStream_t s) {
+template <bool PAIR>
+static hipError_t launch_cpn_decode_any(typename CpnArgsOf<PAIR>::type& a, hipStream_t s) {
     const size_t lds = cpn_decode_lds_bytes(a.H, a.W);
     if (!a.heat || !a.kcrop || a.B < 1 || a.J < 1 || a.J > a.C || a.C > 32 || lds > CPN_LDS_LIMIT || (long)a.B * a.J >= (1L << 31) ||
         (a.k2d && !a.to_image))
         return hipErrorInvalidValue;
     cpn_decode_taps(a.g);
-    if (a.dtype == CAPF_F32) return launch_cpn_decode_t<CpnLdF32>(a, lds, s);
-    if (a.dtype == CAPF_BF16) return launch_cpn_decode_t<CpnLd16<Bf16Fmt>>(a, lds, s);
-    if (a.dtype == CAPF_F16) return launch_cpn_decode_t<CpnLd16<F16Fmt>>(a, lds, s);
+    if (a.dtype == CAPF_F32) return launch_cpn_decode_t<CpnLdF32, PAIR>(a, lds, s);
+    if (a.dtype == CAPF_BF16) return launch_cpn_decode_t<CpnLd16<Bf16Fmt>, PAIR>(a, lds, s);
+    if (a.dtype == CAPF_F16) return launch_cpn_decode_t<CpnLd16<F16Fmt>, PAIR>(a, lds, s);
     return hipErrorInvalidValue;
+}
+
+hipError_t launch_cpn_decode(CpnDecodeArgs a, hipStream_t s) { return launch_cpn_decode_any<false>(a, s); }
+
+hipError_t launch_cpn_decode_pair(CpnPairArgs a, hipStream_t s) {
+    if (a.J < 1 || a.J > 32) return hipErrorInvalidValue;
+    for (int j = 0; j < a.J; ++j)                                        // (capf_cpn_decode_pair has judged the table; a kernel never indexes past it)
+        if (a.swap.j[j] < 0 || a.swap.j[j] >= a.J || a.swap.j[a.swap.j[j]] != j) return hipErrorInvalidValue;
+    return launch_cpn_decode_any<true>(a, s);
 }
 
 }  // namespace capf

@@ -1781,6 +1781,28 @@ int capf_cpn_decode(void* stream, const void* heat_nhwc, int heat_dtype, int B, 
     return capf::launch_cpn_decode(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
+// the flip-test pair: the map holds 2 * Bsrc frames, everything else is sized by Bsrc
+int capf_cpn_decode_pair(void* stream, const void* heat_nhwc, int heat_dtype, int Bsrc, int H, int W, int C, int J, const int32_t* swap,
+                         const float decode[4], const float* to_image, float mirror_width, float* kcrop2, float* k2d2, float* score,
+                         double* blurred, float* fused) {
+    if (!heat_nhwc || !kcrop2 || !decode || !swap || (k2d2 && !to_image) || !std::isfinite(mirror_width)) return CAPF_ERR_INVALID;
+    if (Bsrc < 1 || H < 1 || W < 1 || J < 1 || J > C || C > 32) return CAPF_ERR_INVALID;
+    if (heat_dtype < CAPF_F32 || heat_dtype > CAPF_F16) return CAPF_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(heat_nhwc) & (heat_dtype == CAPF_F32 ? 15 : 7)) return CAPF_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(kcrop2) & 3) || (reinterpret_cast<uintptr_t>(blurred) & 7) || (reinterpret_cast<uintptr_t>(fused) & 3)) return CAPF_ERR_INVALID;
+    capf::CpnPairArgs a{};
+    for (int j = 0; j < J; ++j) {              // a permutation that is its own inverse (capf_fliptest_fuse_swap's rule)
+        if (swap[j] < 0 || swap[j] >= J || swap[swap[j]] != j) return CAPF_ERR_INVALID;
+        a.swap.j[j] = swap[j];
+    }
+    if (capf::cpn_decode_lds_bytes(H, W) > capf::CPN_LDS_LIMIT || (long)Bsrc * J >= (1L << 31)) return CAPF_ERR_UNSUPPORTED;
+    a.heat = heat_nhwc; a.dtype = heat_dtype; a.B = Bsrc; a.H = H; a.W = W; a.C = C; a.J = J;
+    for (int i = 0; i < 4; ++i) a.dec[i] = decode[i];
+    a.to_image = to_image; a.kcrop = kcrop2; a.k2d = to_image ? k2d2 : nullptr; a.score = score; a.blurred = blurred;
+    a.mirror_w = mirror_width; a.fused = fused;
+    return capf::launch_cpn_decode_pair(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+}
+
 int capf_num_ops(const capf_handle* h) { return h ? (int)h->e.ops.size() : CAPF_ERR_INVALID; }
 
 int capf_op_info(const capf_handle* h, int index, int batch, const char** name, const char** kernel, double* flops) {

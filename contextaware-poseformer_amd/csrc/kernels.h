@@ -808,5 +808,15 @@ struct CpnDecodeArgs {
 void cpn_decode_taps(double g[CPN_TAPS]);
 size_t cpn_decode_lds_bytes(int H, int W);       // what one workgroup needs (the launcher refuses more than CPN_LDS_LIMIT)
 hipError_t launch_cpn_decode(CpnDecodeArgs a, hipStream_t s);
+// CPN's test-time flip (capf_cpn_decode_pair; cpn/test.py:62-70): heat holds [2 B, H, W, C], frame B + b the mirror of source frame b; B counts
+// SOURCE frames (the grid and to_image [B, 2, 3] are the single entry's at B).  The fold zf = 0.5 (zo + zm) happens in the load, the decode of zf
+// is the single form's; kcrop / k2d are the stacks [2, B, J, 2], score [B, J], blurred [B, J, H + 20, W + 20].
+struct CpnSwap { int j[32]; };               // swap[j] = the joint of the mirror whose heatmap lands on joint j; travels in the kernel arguments
+struct CpnPairArgs : CpnDecodeArgs {
+    CpnSwap swap;
+    float mirror_w;          // kcrop2[1].x = (mirror_w - x) - 1
+    float* fused;            // [B, J, H, W] or NULL: zf, as the decode used it
+};
+hipError_t launch_cpn_decode_pair(CpnPairArgs a, hipStream_t s);
 
 }  // namespace capf

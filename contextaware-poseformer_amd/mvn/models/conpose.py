@@ -14,7 +14,7 @@ import collections
 import torch
 from torch import nn
 
-from capf.lib import (KP_INTEGRAL, KP_MODES, PLAN_BN_BATCH_STATS, PLAN_CPN_PREDICT, CapfError, Engine, cpn_decode, input_constants,
+from capf.lib import (KP_INTEGRAL, KP_MODES, PLAN_BN_BATCH_STATS, PLAN_CPN_PREDICT, CapfError, Engine, cpn_decode, cpn_decode_pair, input_constants,
                       kp_head_backward, kp_head_forward, kp_head_forward_pair)
 
 from . import _native
@@ -231,7 +231,9 @@ class CA_PF(nn.Module):
         backbone.refine_net.final_predict.* (refineNet.py:64-70), and CPN's own two-peak decode (cpn/test.py:79-108).  NO module and NO
         parameter is added -- state_dict() is the default module's, the checkpoint's weights are the head --; the engines are created with
         PLAN_CPN_PREDICT, so the backbone pass also leaves the heatmaps ("heat"), and detect / forward_detect decode them with
-        capf_cpn_decode.  The head has no derivative and belongs to the frozen backbone; the flip-test entries are not implemented for it.
+        capf_cpn_decode.  The head has no derivative and belongs to the frozen backbone.  CPN's own test-time flip (the heatmaps of the crop
+        and of its mirror averaged without a column shift, cpn/test.py:44-70) has entries of its own, detect_cpn_flip /
+        forward_detect_cpn_flip; HRNet's detect_flip_test / forward_detect_flip_test raise for this head.
         backbone_bn: what the frozen backbone's BatchNorm layers do while `self.backbone.training` is set.  "running" (default): the
         running statistics, folded into the convs, whatever the mode -- i.e. a frozen backbone left in .train() silently gets eval-mode
         BatchNorm.  "batch" (HRNet, fp32): the module honours self.backbone.training as torch does -- in train mode every forward
@@ -578,8 +580,8 @@ class CA_PF(nn.Module):
 
     def _no_cpn_flip_test(self):
         if self.keypoint_head_mode == "cpn":
-            raise NotImplementedError("keypoint_head='cpn' has no flip-test entry (CPN's own test-time flip averages the heatmaps without "
-                                      "a column shift; it is not implemented): use detect / forward_detect")
+            raise NotImplementedError("keypoint_head='cpn' is not served by HRNet's shifted flip test (CPN's own test-time flip averages the "
+                                      "heatmaps without a column shift): use detect_cpn_flip / forward_detect_cpn_flip")
 
     def _run_cpn_head(self, eng, images, to_image, stream):
         """One backbone pass (final_predict included) and capf_cpn_decode on "heat": (kcrop_px, score, k2d | None), outside the graph."""
@@ -727,6 +729,62 @@ class CA_PF(nn.Module):
         with torch.cuda.device(src.device), torch.no_grad():
             eng = self._engine_at(src.device, H, W)
             kcrop2, score, k2d2 = self._run_pair_head(eng, src, to_image, H, W, shift, swap)
+            ref = kcrop2.clone().view(2 * B, J, 2)               # (the lifter normalises its crop keypoints in place: the caller keeps the pixels)
+            pred = self._run_lifter(eng, _Source("workspace", src.device, 2 * B, "the maps", None), k2d2.view(2 * B, J, 2), ref, None)
+            out = fliptest_fuse(pred.view(2, B, 1, J, 3), swap)
+        return out, kcrop2[0], score
+
+    # ---- keypoint_head="cpn" under CPN's own test-time flip (cpn/test.py:44-70): fold of the two heatmaps, ONE two-peak decode ----
+    def _cpn_flip_entry(self, name):
+        if self.keypoint_head_mode != "cpn":
+            raise ValueError("{} is CPN's test-time flip: it needs CA_PF(..., keypoint_head='cpn'), not keypoint_head={!r} (HRNet's flip "
+                             "test: detect_flip_test / forward_detect_flip_test)".format(name, self.keypoint_head_mode))
+        self._cpn_head_frozen()
+
+    def _run_cpn_pair_head(self, eng, src, to_image, H, W, swap):
+        """One backbone pass over the pair (final_predict included) and capf_cpn_decode_pair on its "heat":
+        (kcrop2 [2,B,J,2], score [B,J], k2d2 [2,B,J,2] | None)."""
+        _run_backbone(self, eng, src, torch.cuda.current_stream(src.device).cuda_stream)
+        heat = eng.tensor_view("heat", src.batch)
+        sx, sy = float(W) / heat.shape[2], float(H) / heat.shape[1]
+        kcrop2, score, k2d2, _, _ = cpn_decode_pair(heat, self.num_joints, swap, (sx, 0.5 * sx, sy, 0.5 * sy), to_image, float(2 * CROP_HALF[0]))
+        return kcrop2, score, k2d2
+
+    def detect_cpn_flip(self, images, to_image=None, flip_pairs=None):
+        """detect() under CPN's own test-time flip (cpn/test.py:44-70, upstream's default and the procedure behind keypoints_2d_cpn): ONE
+        backbone pass over the crops and their mirrors, then capf_cpn_decode_pair -- per joint the heatmap of the crop and the heatmap of
+        the mirror (x mirrored back, left / right joints exchanged, NO column shift) are averaged and decoded once with CPN's two-peak
+        rule.  keypoint_head="cpn" only (anything else: ValueError).  images: the three forms of detect_flip_test -- uint8 BGR crops
+        [B,H,W,3] (mirrored in the stem's load), float32 [B,H,W,3] (the mirrored half is torch.flip(images, [2])), or the float32
+        [2,B,H,W,3] stack of capf.lib.preprocess(mode=2) -- the same bits.  to_image as in detect.  flip_pairs: None -- the H36M table -- or a
+        swap table of J ints (capf.lib.COCO_SWAP for a checkpoint whose channels are in COCO order).  Returns (kcrop_px [B,J,2],
+        score [B,J], k2d [B,J,2] | None).  Always runs without grad and returns detached tensors: the decode has no backward (a
+        final_predict parameter that requires grad raises under grad)."""
+        self._cpn_flip_entry("detect_cpn_flip")
+        swap = self._swap_table(flip_pairs)
+        src, B, H, W, to_image = self._flip_test_source(images, to_image)
+        with torch.cuda.device(src.device), torch.no_grad():
+            kcrop2, score, k2d2 = self._run_cpn_pair_head(self._engine_at(src.device, H, W), src, to_image, H, W, swap)
+        return kcrop2[0], score, (None if k2d2 is None else k2d2[0])
+
+    def forward_detect_cpn_flip(self, images, to_image, flip_pairs=None):
+        """The reference's flip-test evaluation (train.py:170-181) on a CPN backbone without detections from outside, from crop to
+        flip-tested 3-D pose in ONE backbone pass over the 2B engine frames: the paired decode (detect_cpn_flip; images / flip_pairs as
+        there), the lifter on the maps still in the workspace with the stacked keypoints the kernel wrote (set 1 mirrored as
+        capf_preprocess_points(mode=2) does), capf_fliptest_fuse (its _swap form with flip_pairs).  Returns (joints3d [B,1,J,3],
+        kcrop_px [B,J,2], score [B,J]); kcrop_px stays in crop pixels.  The result equals forward_flip_test on the stack with
+        detect_cpn_flip's keypoints pushed through preprocess_points(mode=2), bit for bit.  Always runs without grad and returns detached
+        tensors."""
+        from capf.lib import fliptest_fuse
+        self._cpn_flip_entry("forward_detect_cpn_flip")
+        if to_image is None:
+            raise ValueError("forward_detect_cpn_flip needs to_image [B, 2, 3]: the lifter takes the keypoints in normalised image coordinates too")
+        swap = self._swap_table(flip_pairs)
+        src, B, H, W, to_image = self._flip_test_source(images, to_image)
+        J = self.num_joints
+        with torch.cuda.device(src.device), torch.no_grad():
+            eng = self._engine_at(src.device, H, W)
+            kcrop2, score, k2d2 = self._run_cpn_pair_head(eng, src, to_image, H, W, swap)
             ref = kcrop2.clone().view(2 * B, J, 2)               # (the lifter normalises its crop keypoints in place: the caller keeps the pixels)
             pred = self._run_lifter(eng, _Source("workspace", src.device, 2 * B, "the maps", None), k2d2.view(2 * B, J, 2), ref, None)
             out = fliptest_fuse(pred.view(2, B, 1, J, 3), swap)

@@ -166,7 +166,7 @@ const char* capf_version(void);
  * (additive: capf_set_map_grad_mode, capf_map_grad_mode; CAPF_PLAN_BN_BATCH_STATS, capf_backbone_forward_bn, capf_op_bn_stats_scratch_bytes,
  * capf_op_bn_stats, capf_op_bn_apply; capf_backward_points; capf_kp_head_scratch_bytes, capf_kp_head_forward, capf_kp_head_backward;
  * capf_kp_head_pair_scratch_bytes, capf_kp_head_forward_pair; CAPF_PLAN_CPN_PREDICT, the named tensor "heat", capf_cpn_decode,
- * capf_cpn_decode_taps, capf_cpn_decode_lds_bytes).                                                                                         */
+ * capf_cpn_decode_taps, capf_cpn_decode_lds_bytes; capf_cpn_decode_pair).                                                                   */
 #define CAPF_ABI_VERSION 12
 int capf_abi_version(void);
 
@@ -883,6 +883,49 @@ void capf_cpn_decode_taps(double taps[21]);
 size_t capf_cpn_decode_lds_bytes(int H, int W);       /* 0: H or W out of range */
 int capf_cpn_decode(void* stream, const void* heat_nhwc, int heat_dtype, int B, int H, int W, int C, int J, const float decode[4],
                     const float* to_image, float* kcrop, float* k2d, float* score, double* blurred);
+/* ---- CPN's decode on a flip-test pair: the heatmaps of a crop and of its mirror averaged, then ONE two-peak decode ----------------------------
+ * CPN's own test-time flip (cpn/test.py:44-70, --flip defaults to True: the procedure that made the keypoints_2d_cpn the lifter was trained on)
+ * on the heatmaps one backbone pass leaves for the 2 * Bsrc engine frames of capf_preprocess mode 2: heat_nhwc [2 * Bsrc, H, W, C], frame
+ * b < Bsrc the source frame, frame Bsrc + b its mirror.  Dtypes, shape limits (on Bsrc, H, W, C, J), alignment, the LDS limit, decode, the taps:
+ * capf_cpn_decode's.  ONE launch of the PAIR instantiation of the same kernel: one workgroup per (source frame, joint), the same LDS planes, no
+ * scratch, no atomics, no second launch (csrc/cpn_decode.hip).  Forward only.  Additive inside revision 12.
+ * Fused heatmap of source frame b, joint j, pixel (y, x), z being the 2 * Bsrc-frame map widened to fp32 (test.py:62-70 restated):
+ *       zo = z[b,        y, x,         j]
+ *       zm = z[Bsrc + b, y, W - 1 - x, swap[j]]   (cv2.flip(.., 1), then the symmetric joints exchanged; NO column shift -- HRNet's SHIFT_HEATMAP
+ *                                                  is not CPN's)
+ *       zf = 0.5f * (zo + zm)                     (the fp32 sum rounded once, then halved: numpy's `+=` then `/= 2` on float32)
+ *   swap: HOST int32[J], a permutation that is its own inverse (capf_fliptest_fuse_swap's rule); it travels in the kernel arguments.  The H36M
+ *   table serves a head whose channels feed the H36M lifter; upstream's cfg.symmetry for COCO-ordered channels is capf.lib.COCO_SWAP.
+ * Decode of zf: capf_cpn_decode's, rule for rule and in the same summation order -- M = max zf, n = zf / M, the padded plane, the row pass, then
+ *   the column pass, first and second maximum, quarter shift, clamp.  r0 = zf / 255 + 0.5 is taken from the FUSED map, as the reference takes it
+ *   (r0 = single_map.copy() after the fold): the score at (round(y), round(x)) recomputes zf from both frames.  The result equals
+ *   capf_cpn_decode on a map that holds zf, bit for bit, decided or not.
+ * Degenerate maps: capf_cpn_decode's rule on zf -- any zf of (b, j) not finite (a NaN or +-Inf in either frame, a sum that overflows), or a fused
+ *   maximum of 0 (zo = -zm everywhere): the keypoint of (b, j) in both coordinate systems and BOTH sets (slot swap[j] of set 1), its score and its
+ *   plane of `blurred` are NaN; every other joint and frame is untouched.  A negative fused maximum follows the arithmetic.
+ * A source frame's result bits depend on frames b and Bsrc + b alone: not on Bsrc, J, C, the frame's position, the run or the device buffer.
+ * Outputs: with kcrop / k2d / score [Bsrc, J(, 2)] the decode[4] -> to_image [Bsrc, 2, 3] arithmetic of capf_cpn_decode on zf, the stacks
+ *   capf_forward takes for the 2 * Bsrc frames (no further launch; swap is its own inverse, so workgroup (b, j) writes its own two slots):
+ *       kcrop2[0, b, j] = kcrop[b, j]      kcrop2[1, b, swap[j]] = ((mirror_width - kcrop[b, j].x) - 1, kcrop[b, j].y)   (two rounded fp32 subtractions)
+ *       k2d2 [0, b, j] = k2d[b, j]         k2d2 [1, b, swap[j]] = (-k2d[b, j].x, k2d[b, j].y)
+ *   kcrop2 [2, Bsrc, J, 2]; k2d2 [2, Bsrc, J, 2] or NULL (needs to_image); score [Bsrc, J] or NULL.  With J = 17, the H36M table and
+ *   mirror_width = 192 (the reference's constant, datasets/utils.py:76) the stacks are capf_preprocess_points(mode = 2) of (k2d, kcrop) bit for
+ *   bit, and capf_kp_head_forward_pair's layout.  Optional (NULL): blurred [Bsrc, J, H + 20, W + 20] float64 (D of zf before the zeroing, 8-byte
+ *   aligned) and fused [Bsrc, J, H, W] fp32 -- the zf the decode used, bit for bit (written for degenerate maps too).
+ * PARITY UNPINNED in the last bits of D exactly as for capf_cpn_decode: nothing pins cv2.GaussianBlur's own summation order; the fold
+ *   itself is exact arithmetic on two fp32 values and is pinned bit for bit (tests/cpn_flip_oracle.py, two restatements).
+ * Refusals, all before anything is launched (no device needed), CAPF_ERR_INVALID: a NULL map / decode / swap / kcrop2, k2d2 without to_image,
+ *   Bsrc, H, W, J or C out of range (J > C, C > 32), an unknown dtype, a misaligned map / kcrop2 / blurred / fused, mirror_width not finite, a swap
+ *   entry outside [0, J) or a table that is not its own inverse; CAPF_ERR_UNSUPPORTED: planes beyond the LDS limit, a grid of 2^31 blocks or more.
+ * Cost (MI355X, medians of 20 around the host call, two runs, tools/bench_cpn_detect.py --pair, EXPERIMENTS.md R30.1; 64 x 48 x 20 maps, 17 joints):
+ *   fp32, Bsrc 32 -- 0.126 / 0.136 ms against capf_cpn_decode's 0.159 ms on the same 2 * Bsrc-frame map (twice the items) and 0.103 ms on Bsrc
+ *   frames (the same items, half the map bytes); bf16, Bsrc 64 -- 0.180 / 0.165 ms against 0.239 and 0.145 ms.  SLOWER than the single decode at
+ *   Bsrc by 14 - 31 % (the second strided gather of the load and the score), 14 - 30 % faster than decoding all 2 * Bsrc frames.
+ *   CA_PF.forward_detect_cpn_flip against a backbone pass over the pair + the fold in torch + capf_cpn_decode + capf_preprocess_points +
+ *   forward_flip_test: 7.2 against 13.0 ms (fp32, Bsrc 32), 5.7 against 9.8 ms (bf16, Bsrc 64) -- one backbone pass over the pair saved. */
+int capf_cpn_decode_pair(void* stream, const void* heat_nhwc, int heat_dtype, int Bsrc, int H, int W, int C, int J, const int32_t* swap,
+                         const float decode[4], const float* to_image, float mirror_width, float* kcrop2, float* k2d2, float* score,
+                         double* blurred, float* fused);
 /* capf_pck_counts: the MPI-INF-3DHP evaluation (ContextPose_mpi/3dhp_test/test_util, MATLAB: mpii_test_predictions_py.m,
  *   mpii_evaluate_errors.m, mpii_compute_3d_pck.m), which callers otherwise export to .mat files and run off the GPU; capf_pose_errors /
  *   capf_segment_sums serve H36M only.  Per pose i of pred / gt [n, joints, 3] (same unit; to_mm converts it to mm): gt made relative to

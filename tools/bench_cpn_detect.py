@@ -9,7 +9,15 @@
 
 One process, device events around every call, medians with min / max over the repeats (tools/bench_kp_head.py's scheme).
 
+--pair: CPN's test-time flip (EXPERIMENTS.md R30.1), per config dtype:HxW:Bsrc (default fp32:256x192:32 bf16:256x192:64):
+  (a) capf_cpn_decode_pair at Bsrc against capf_cpn_decode on the SAME 2 * Bsrc-frame "heat" (twice the (frame, joint) items, the same map
+      bytes) and on its first Bsrc frames (the same items, half the map bytes);
+  (b) CA_PF.forward_detect_cpn_flip against the route available without it: a backbone pass over [orig | mirrored], the fold of the two
+      heatmaps in torch, capf_cpn_decode, preprocess_points(mode=2) and forward_flip_test (a second backbone pass over the pair); the two
+      routes' joints are compared bit for bit once.
+
     python tools/bench_cpn_detect.py [--configs bf16:384x288:128 fp32:256x192:64] [--repeats 20] [--warmup 3]      (needs the MI355X)
+    python tools/bench_cpn_detect.py --pair [--configs fp32:256x192:32 bf16:256x192:64]
 """
 import argparse
 import copy
@@ -36,9 +44,69 @@ def timed(runs, repeats, warmup):
     return {k: {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)} for k, v in times.items()}
 
 
+def pair_mode(args):
+    import numpy as np
+    import torch
+    from capf import lib as capf
+    from capf import synth
+    from mvn.models.conpose import CA_PF
+    from mvn.utils.cfg import backbone_preset, config
+    swap = list(capf.H36M_SWAP)
+    for spec in args.configs:
+        dtype, hw, B = spec.split(":")
+        H, W = (int(v) for v in hw.split("x"))
+        B = int(B)
+        cfg = backbone_preset(copy.deepcopy(config), "cpn")
+        cfg.model.backbone.fix_weights = True
+        model = CA_PF(cfg, compute_dtype=dtype, keypoint_head="cpn")
+        synth.load_synthetic(model, seed=1, bn_mode="random")
+        model = model.cuda().eval()
+        img = synth.synth_inputs(B, H, W, seed=2, crop_range=(W, H))[0].cuda()
+        A = torch.from_numpy(np.stack([capf.crop_to_image_matrix((500.0, 500.0), (1.5, 1.5), (W, H), 1000, 1000)] * B).astype(np.float32)).cuda()
+        s = torch.cuda.current_stream().cuda_stream
+        eng = model.engine_for(img)
+        pair = torch.cat([img, torch.flip(img, [2])])
+        with torch.no_grad():
+            eng.backbone_forward(pair, s)
+            heat2 = eng.tensor_view("heat", 2 * B).clone()
+            half = heat2[:B].contiguous()
+            sx, sy = W / heat2.shape[2], H / heat2.shape[1]
+            dec = (sx, sx / 2, sy, sy / 2)
+
+            def without_the_pair_entry():
+                eng.backbone_forward(pair, s)
+                z = eng.tensor_view("heat", 2 * B).float()
+                zf = (0.5 * (z[:B, :, :, :17] + z[B:].flip(2)[..., swap])).contiguous()
+                kcrop, _, k2d, _ = capf.cpn_decode(zf, 17, dec, A)
+                _, k2d2, kcrop2 = capf.preprocess_points(None, k2d, kcrop, mode=2)
+                return model.forward_flip_test(pair.view(2, B, H, W, 3), k2d2, kcrop2)
+
+            same = bool(torch.equal(without_the_pair_entry(), model.forward_detect_cpn_flip(img, A)[0]))
+            runs = {
+                "cpn_decode_pair_Bsrc": lambda: capf.cpn_decode_pair(heat2, 17, None, dec, A),
+                "cpn_decode_2Bsrc_frames": lambda: capf.cpn_decode(heat2, 17, dec, None),
+                "cpn_decode_Bsrc_frames": lambda: capf.cpn_decode(half, 17, dec, A),
+                "backbone_forward_2Bsrc": lambda: eng.backbone_forward(pair, s),
+                "forward_detect_cpn_flip": lambda: model.forward_detect_cpn_flip(img, A),
+                "fold_in_torch_route": without_the_pair_entry,
+            }
+            row = {"config": spec, "mode": "pair", "Bsrc": B, "heat2": list(heat2.shape), "heat2_MB": round(heat2.numel() * heat2.element_size() / 1e6, 2),
+                   "workgroups_pair": B * 17, "repeats": args.repeats, "routes_bit_equal": same}
+            row.update(timed(runs, args.repeats, args.warmup))
+        ms = lambda k: row[k]["median_ms"]
+        row["pair_over_single_2Bsrc"] = round(ms("cpn_decode_pair_Bsrc") / ms("cpn_decode_2Bsrc_frames"), 3)
+        row["pair_over_single_Bsrc"] = round(ms("cpn_decode_pair_Bsrc") / ms("cpn_decode_Bsrc_frames"), 3)
+        row["entry_saves_ms"] = round(ms("fold_in_torch_route") - ms("forward_detect_cpn_flip"), 4)
+        print(json.dumps(row), flush=True)
+        for e in model._engines.values():
+            e.close()
+        model._engines.clear()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--configs", nargs="+", default=["bf16:384x288:128"], help="dtype:HxW:batch")
+    ap.add_argument("--configs", nargs="+", default=None, help="dtype:HxW:batch (--pair: dtype:HxW:Bsrc)")
+    ap.add_argument("--pair", action="store_true", help="CPN's test-time flip: capf_cpn_decode_pair / forward_detect_cpn_flip")
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args()
@@ -46,6 +114,10 @@ def main():
     import numpy as np
     import torch
     assert torch.cuda.is_available(), "bench_cpn_detect.py needs the MI355X"
+    if args.configs is None:
+        args.configs = ["fp32:256x192:32", "bf16:256x192:64"] if args.pair else ["bf16:384x288:128"]
+    if args.pair:
+        return pair_mode(args)
     from capf import lib as capf
     from capf import synth
     from mvn.models.conpose import CA_PF

@@ -1,7 +1,7 @@
 // Host sanitizer check of a handle's life, no GPU needed: creates and destroys plan-only handles of the three backbones, asks each the
 // questions a host asks before it has a device (schema, workspace size, op table), makes every run entry refuse it, walks the refusal paths
-// of the stand-alone keypoint head entries (capf_kp_head_forward / capf_kp_head_backward / capf_cpn_decode: arguments judged before any launch), and lets capf_create
-// fail both in front of the plan (a refused configuration) and behind it (a device that is not there: the branch that releases what a
+// of the stand-alone keypoint head entries (capf_kp_head_forward / capf_kp_head_backward / capf_cpn_decode / capf_cpn_decode_pair:
+// arguments judged before any launch), and lets capf_create fail both in front of the plan (a refused configuration) and behind it (a device that is not there: the branch that releases what a
 // handle already owns).  Built by `make -C contextaware-poseformer_amd/csrc hostcheck`: the engine's host sources with
 // -fsanitize=address,undefined, the device objects of the product build; it runs on the build machine and is not loaded into Python.
 #include <stdio.h>
@@ -129,6 +129,21 @@ int main() {
         CHECK(capf_cpn_decode(nullptr, big, 3, 2, 8, 8, 20, 17, dec, nullptr, mem, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
         CHECK(capf_cpn_decode(nullptr, big, CAPF_F32, 2, 8, 8, 20, 17, dec, nullptr, mem, mem, nullptr, nullptr) == CAPF_ERR_INVALID);
         CHECK(capf_cpn_decode(nullptr, big, CAPF_BF16, 2, 128, 128, 20, 17, dec, nullptr, mem, nullptr, nullptr, nullptr) == CAPF_ERR_UNSUPPORTED);
+        // ... and its flip-test pair: the swap table is the one argument that is read (on the host) before any refusal behind it
+        const int32_t h36m[17] = {0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13};
+        int32_t cycle[17], outside[17];
+        for (int j = 0; j < 17; ++j) cycle[j] = outside[j] = j;
+        cycle[1] = 2; cycle[2] = 3; cycle[3] = 1;
+        outside[16] = 17;
+        CHECK(capf_cpn_decode_pair(nullptr, nullptr, CAPF_F32, 2, 8, 8, 20, 17, h36m, dec, nullptr, 192.f, mem, nullptr, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode_pair(nullptr, big, CAPF_F32, 2, 8, 8, 20, 17, nullptr, dec, nullptr, 192.f, mem, nullptr, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode_pair(nullptr, big, CAPF_F32, 2, 8, 8, 20, 17, h36m, dec, nullptr, 192.f, nullptr, nullptr, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode_pair(nullptr, big, CAPF_F32, 2, 8, 8, 20, 17, h36m, dec, nullptr, 192.f, mem, mem, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode_pair(nullptr, big, CAPF_F32, 2, 8, 8, 20, 17, cycle, dec, nullptr, 192.f, mem, nullptr, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode_pair(nullptr, big, CAPF_F32, 2, 8, 8, 20, 17, outside, dec, nullptr, 192.f, mem, nullptr, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode_pair(nullptr, big, CAPF_F32, 2, 8, 8, 20, 17, h36m, dec, nullptr, INFINITY, mem, nullptr, nullptr, nullptr, nullptr) == CAPF_ERR_INVALID);
+        CHECK(capf_cpn_decode_pair(nullptr, big, CAPF_BF16, 2, 128, 128, 20, 17, h36m, dec, nullptr, 192.f, mem, nullptr, nullptr, nullptr, nullptr) == CAPF_ERR_UNSUPPORTED);
+        CHECK(capf_cpn_decode_pair(nullptr, big, CAPF_F32, 1 << 27, 8, 8, 20, 16, outside, dec, nullptr, 192.f, mem, nullptr, nullptr, nullptr, nullptr) == CAPF_ERR_UNSUPPORTED);
     }
     // refused in front of the plan, inside it, and behind it (no device 0 on a machine without a GPU: what the handle owns is released)
     capf_handle* h = nullptr;
