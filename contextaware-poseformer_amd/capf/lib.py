@@ -1056,18 +1056,59 @@ def _kp_map_dtype(x):
     return code
 
 
-def _kp_common(x, weight, decode, to_image, backward):
+def _kp_weight(weight, C):
+    """the 1x1 conv weight [J, C] or [J, C, 1, 1] as (contiguous fp32 [J, C], J)"""
     import torch
-    B, H, W, C = x.shape
     w = weight.reshape(weight.shape[0], -1)
     if w.shape[1] != C or w.dtype != torch.float32 or not w.is_contiguous():
         raise CapfError(f"the keypoint head's weight must be contiguous fp32 [J, {C}] (or [J, {C}, 1, 1]), not {tuple(weight.shape)} {weight.dtype}")
-    J = w.shape[0]
+    return w, w.shape[0]
+
+
+def _kp_to_image(to_image, B):
+    import torch
     if to_image is not None and (tuple(to_image.shape) != (B, 2, 3) or to_image.dtype != torch.float32 or not to_image.is_contiguous()):
         raise CapfError(f"to_image must be contiguous fp32 [{B}, 2, 3], not {tuple(to_image.shape)} {to_image.dtype}")
+
+
+def _kp_pair_split(x2):
+    """(Bsrc, H, W, C) of a flip-test pair's map [2 * Bsrc, H, W, C]"""
+    if x2.shape[0] % 2:
+        raise CapfError(f"a flip-test pair holds 2 * Bsrc frames ([orig | mirrored]), not {x2.shape[0]}")
+    return x2.shape[0] // 2, x2.shape[1], x2.shape[2], x2.shape[3]
+
+
+def _kp_swap(swap, J, what):
+    """a pair entry's `swap` as the C array of J ints: None is H36M_SWAP, at 17 joints only; `what`: "a head of" / "a decode of" """
+    if swap is None:
+        if J != 17:
+            raise CapfError(f"swap=None means the H36M table (17 joints); {what} {J} joints needs its own table")
+        swap = H36M_SWAP
+    tab = [int(v) for v in swap]
+    if len(tab) != J:
+        raise CapfError(f"swap has {len(tab)} entries for {J} joints")
+    return (c_int32 * max(J, 1))(*tab)
+
+
+def _kp_outputs(x, lead, J, to_image, want_score):
+    """fresh fp32 (kcrop, k2d | None, score | None) beside the map x: lead = (B,), or (2, Bsrc) for a pair's stacks"""
+    import torch
+    f32, dev = torch.float32, x.device
+    return (torch.empty(*lead, J, 2, dtype=f32, device=dev), torch.empty(*lead, J, 2, dtype=f32, device=dev) if to_image is not None else None,
+            torch.empty(lead[-1], J, dtype=f32, device=dev) if want_score else None)
+
+
+def _kp_decode(decode):
+    return (c_float * 4)(*[float(v) for v in decode])
+
+
+def _kp_common(x, weight, decode, to_image, backward):
+    import torch
+    B, H, W, C = x.shape
+    w, J = _kp_weight(weight, C)
+    _kp_to_image(to_image, B)
     nbytes = load_library().capf_kp_head_scratch_bytes(B, H, W, C, J, 1 if backward else 0)
-    scratch = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
-    return (B, H, W, C, J), w, (c_float * 4)(*[float(v) for v in decode]), scratch, nbytes
+    return (B, H, W, C, J), w, _kp_decode(decode), torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device), nbytes
 
 
 def kp_head_forward(x, weight, bias=None, mode=KP_ARGMAX, beta=1.0, decode=(1.0, 0.0, 1.0, 0.0), to_image=None, want_score=True,
@@ -1079,11 +1120,8 @@ def kp_head_forward(x, weight, bias=None, mode=KP_ARGMAX, beta=1.0, decode=(1.0,
     import torch
     dtype = _kp_map_dtype(x)
     (B, H, W, C, J), w, dec, scratch, nbytes = _kp_common(x, weight, decode, to_image, False)
-    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x.device)
-    kcrop = new(B, J, 2)
-    k2d = new(B, J, 2) if to_image is not None else None
-    score = new(B, J) if want_score else None
-    heat = new(B, J, H, W) if want_heat else None
+    kcrop, k2d, score = _kp_outputs(x, (B,), J, to_image, want_score)
+    heat = torch.empty(B, J, H, W, dtype=torch.float32, device=x.device) if want_heat else None
     _call("capf_kp_head_forward", _stream(x), _p(x), dtype, _p(w), _p(bias), B, H, W, C, J, int(mode), float(beta), dec, _p(to_image),
           _p(kcrop), _p(k2d), _p(score), _p(heat), _p(scratch), nbytes)
     return kcrop, score, k2d, heat
@@ -1129,15 +1167,11 @@ def cpn_decode(heat, joints=None, decode=(1.0, 0.0, 1.0, 0.0), to_image=None, wa
     dtype = _kp_map_dtype(heat)
     B, H, W, C = heat.shape
     J = C if joints is None else int(joints)
-    if to_image is not None and (tuple(to_image.shape) != (B, 2, 3) or to_image.dtype != torch.float32 or not to_image.is_contiguous()):
-        raise CapfError(f"to_image must be contiguous fp32 [{B}, 2, 3], not {tuple(to_image.shape)} {to_image.dtype}")
-    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=heat.device)
-    kcrop = new(B, J, 2)
-    k2d = new(B, J, 2) if to_image is not None else None
-    score = new(B, J) if want_score else None
+    _kp_to_image(to_image, B)
+    kcrop, k2d, score = _kp_outputs(heat, (B,), J, to_image, want_score)
     blurred = torch.empty(B, J, H + 20, W + 20, dtype=torch.float64, device=heat.device) if want_blurred else None
-    dec = (c_float * 4)(*[float(v) for v in decode])
-    _call("capf_cpn_decode", _stream(heat), _p(heat), dtype, B, H, W, C, J, dec, _p(to_image), _p(kcrop), _p(k2d), _p(score), _p(blurred))
+    _call("capf_cpn_decode", _stream(heat), _p(heat), dtype, B, H, W, C, J, _kp_decode(decode), _p(to_image), _p(kcrop), _p(k2d), _p(score),
+          _p(blurred))
     return kcrop, score, k2d, blurred
 
 
@@ -1161,27 +1195,15 @@ def cpn_decode_pair(heat2, joints=None, swap=None, decode=(1.0, 0.0, 1.0, 0.0), 
     preprocess_points(mode=2) with `mirror_width` in place of its 192."""
     import torch
     dtype = _kp_map_dtype(heat2)
-    if heat2.shape[0] % 2:
-        raise CapfError(f"a flip-test pair holds 2 * Bsrc frames ([orig | mirrored]), not {heat2.shape[0]}")
-    Bsrc, H, W, C = heat2.shape[0] // 2, heat2.shape[1], heat2.shape[2], heat2.shape[3]
+    Bsrc, H, W, C = _kp_pair_split(heat2)
     J = C if joints is None else int(joints)
-    if swap is None:
-        if J != 17:
-            raise CapfError(f"swap=None means the H36M table (17 joints); a decode of {J} joints needs its own table")
-        swap = H36M_SWAP
-    tab = [int(v) for v in swap]
-    if len(tab) != J:
-        raise CapfError(f"swap has {len(tab)} entries for {J} joints")
-    if to_image is not None and (tuple(to_image.shape) != (Bsrc, 2, 3) or to_image.dtype != torch.float32 or not to_image.is_contiguous()):
-        raise CapfError(f"to_image must be contiguous fp32 [{Bsrc}, 2, 3], not {tuple(to_image.shape)} {to_image.dtype}")
-    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=heat2.device)
-    kcrop2 = new(2, Bsrc, J, 2)
-    k2d2 = new(2, Bsrc, J, 2) if to_image is not None else None
-    score = new(Bsrc, J) if want_score else None
+    tab = _kp_swap(swap, J, "a decode of")
+    _kp_to_image(to_image, Bsrc)
+    kcrop2, k2d2, score = _kp_outputs(heat2, (2, Bsrc), J, to_image, want_score)
     blurred = torch.empty(Bsrc, J, H + 20, W + 20, dtype=torch.float64, device=heat2.device) if want_blurred else None
-    fused = new(Bsrc, J, H, W) if want_fused else None
-    _call("capf_cpn_decode_pair", _stream(heat2), _p(heat2), dtype, Bsrc, H, W, C, J, (c_int32 * max(J, 1))(*tab),
-          (c_float * 4)(*[float(v) for v in decode]), _p(to_image), float(mirror_width), _p(kcrop2), _p(k2d2), _p(score), _p(blurred), _p(fused))
+    fused = torch.empty(Bsrc, J, H, W, dtype=torch.float32, device=heat2.device) if want_fused else None
+    _call("capf_cpn_decode_pair", _stream(heat2), _p(heat2), dtype, Bsrc, H, W, C, J, tab, _kp_decode(decode), _p(to_image), float(mirror_width),
+          _p(kcrop2), _p(k2d2), _p(score), _p(blurred), _p(fused))
     return kcrop2, score, k2d2, blurred, fused
 
 
@@ -1195,32 +1217,16 @@ def kp_head_forward_pair(x2, weight, bias=None, mode=KP_ARGMAX, beta=1.0, swap=N
     preprocess_points(mode=2) with `mirror_width` in place of its 192."""
     import torch
     dtype = _kp_map_dtype(x2)
-    if x2.shape[0] % 2:
-        raise CapfError(f"a flip-test pair holds 2 * Bsrc frames ([orig | mirrored]), not {x2.shape[0]}")
-    Bsrc, H, W, C = x2.shape[0] // 2, x2.shape[1], x2.shape[2], x2.shape[3]
-    w = weight.reshape(weight.shape[0], -1)
-    if w.shape[1] != C or w.dtype != torch.float32 or not w.is_contiguous():
-        raise CapfError(f"the keypoint head's weight must be contiguous fp32 [J, {C}] (or [J, {C}, 1, 1]), not {tuple(weight.shape)} {weight.dtype}")
-    J = w.shape[0]
-    if swap is None:
-        if J != 17:
-            raise CapfError(f"swap=None means the H36M table (17 joints); a head of {J} joints needs its own table")
-        swap = H36M_SWAP
-    tab = [int(v) for v in swap]
-    if len(tab) != J:
-        raise CapfError(f"swap has {len(tab)} entries for {J} joints")
-    if to_image is not None and (tuple(to_image.shape) != (Bsrc, 2, 3) or to_image.dtype != torch.float32 or not to_image.is_contiguous()):
-        raise CapfError(f"to_image must be contiguous fp32 [{Bsrc}, 2, 3], not {tuple(to_image.shape)} {to_image.dtype}")
+    Bsrc, H, W, C = _kp_pair_split(x2)
+    w, J = _kp_weight(weight, C)
+    tab = _kp_swap(swap, J, "a head of")
+    _kp_to_image(to_image, Bsrc)
     nbytes = load_library().capf_kp_head_pair_scratch_bytes(Bsrc, H, W, C, J)
     scratch = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x2.device)
-    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x2.device)
-    kcrop2 = new(2, Bsrc, J, 2)
-    k2d2 = new(2, Bsrc, J, 2) if to_image is not None else None
-    score = new(Bsrc, J) if want_score else None
-    heat = new(Bsrc, J, H, W) if want_heat else None
-    _call("capf_kp_head_forward_pair", _stream(x2), _p(x2), dtype, _p(w), _p(bias), Bsrc, H, W, C, J, int(mode), float(beta), (c_int32 * J)(*tab),
-          1 if shift else 0, (c_float * 4)(*[float(v) for v in decode]), _p(to_image), float(mirror_width), _p(kcrop2), _p(k2d2), _p(score),
-          _p(heat), _p(scratch), nbytes)
+    kcrop2, k2d2, score = _kp_outputs(x2, (2, Bsrc), J, to_image, want_score)
+    heat = torch.empty(Bsrc, J, H, W, dtype=torch.float32, device=x2.device) if want_heat else None
+    _call("capf_kp_head_forward_pair", _stream(x2), _p(x2), dtype, _p(w), _p(bias), Bsrc, H, W, C, J, int(mode), float(beta), tab,
+          1 if shift else 0, _kp_decode(decode), _p(to_image), float(mirror_width), _p(kcrop2), _p(k2d2), _p(score), _p(heat), _p(scratch), nbytes)
     return kcrop2, score, k2d2, heat
 
 

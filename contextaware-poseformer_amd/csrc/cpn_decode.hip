@@ -24,6 +24,7 @@
 
 #include "fmt16.h"
 #include "kernels.h"
+#include "pair_stacks.h"
 
 namespace capf {
 
@@ -225,22 +226,14 @@ __global__ void __launch_bounds__(CPN_THREADS) cpn_decode_kernel(const typename 
     const float sc = zs / 255.0f + 0.5f;                                 // r0 = z / 255 + 0.5, both rounded to fp32
     const float xf = (float)x, yf = (float)y;
     const float kx = a.dec[0] * xf + a.dec[1], ky = a.dec[2] * yf + a.dec[3];      // (contraction is off: product rounded, then the sum)
-    a.kcrop[o * 2] = kx;
-    a.kcrop[o * 2 + 1] = ky;
-    if (a.score) a.score[o] = sc;
-    if constexpr (PAIR) {                                                // capf_preprocess_points(mode = 2)'s mirrored set, joint swap[j]
-        a.kcrop[om * 2] = (a.mirror_w - kx) - 1.0f;                      // (two rounded subtractions)
-        a.kcrop[om * 2 + 1] = ky;
-    }
-    if (a.k2d) {
-        const float* A = a.to_image + (size_t)b * 6;
-        if constexpr (PAIR) {
-            const float ix = (A[0] * kx + A[1] * ky) + A[2], iy = (A[3] * kx + A[4] * ky) + A[5];
-            a.k2d[o * 2] = ix;
-            a.k2d[o * 2 + 1] = iy;
-            a.k2d[om * 2] = -ix;
-            a.k2d[om * 2 + 1] = iy;
-        } else {                                                         // (statement for statement what the single form always was)
+    if constexpr (PAIR) {                                                // both sets of the stacks, the mirrored one at joint swap[j]
+        write_pair_stacks(a.kcrop, a.k2d, a.score, o, om, a.k2d ? a.to_image + (size_t)b * 6 : nullptr, a.mirror_w, kx, ky, sc);
+    } else {                                                             // (statement for statement what the single form always was)
+        a.kcrop[o * 2] = kx;
+        a.kcrop[o * 2 + 1] = ky;
+        if (a.score) a.score[o] = sc;
+        if (a.k2d) {
+            const float* A = a.to_image + (size_t)b * 6;
             a.k2d[o * 2] = (A[0] * kx + A[1] * ky) + A[2];
             a.k2d[o * 2 + 1] = (A[3] * kx + A[4] * ky) + A[5];
         }
@@ -259,7 +252,7 @@ static hipError_t launch_cpn_decode_t(const typename CpnArgsOf<PAIR>::type& a, s
 template <bool PAIR>
 static hipError_t launch_cpn_decode_any(typename CpnArgsOf<PAIR>::type& a, hipStream_t s) {
     const size_t lds = cpn_decode_lds_bytes(a.H, a.W);
-    if (!a.heat || !a.kcrop || a.B < 1 || a.J < 1 || a.J > a.C || a.C > 32 || lds > CPN_LDS_LIMIT || (long)a.B * a.J >= (1L << 31) ||
+    if (!a.heat || !a.kcrop || a.B < 1 || a.J < 1 || a.J > a.C || a.C > MAX_JOINTS || lds > CPN_LDS_LIMIT || (long)a.B * a.J >= (1L << 31) ||
         (a.k2d && !a.to_image))
         return hipErrorInvalidValue;
     cpn_decode_taps(a.g);
@@ -272,9 +265,7 @@ static hipError_t launch_cpn_decode_any(typename CpnArgsOf<PAIR>::type& a, hipSt
 hipError_t launch_cpn_decode(CpnDecodeArgs a, hipStream_t s) { return launch_cpn_decode_any<false>(a, s); }
 
 hipError_t launch_cpn_decode_pair(CpnPairArgs a, hipStream_t s) {
-    if (a.J < 1 || a.J > 32) return hipErrorInvalidValue;
-    for (int j = 0; j < a.J; ++j)                                        // (capf_cpn_decode_pair has judged the table; a kernel never indexes past it)
-        if (a.swap.j[j] < 0 || a.swap.j[j] >= a.J || a.swap.j[a.swap.j[j]] != j) return hipErrorInvalidValue;
+    if (!swap_table_ok(a.swap.j, a.J)) return hipErrorInvalidValue;      // (capf_cpn_decode_pair has judged the table; a kernel never indexes past it)
     return launch_cpn_decode_any<true>(a, s);
 }
 

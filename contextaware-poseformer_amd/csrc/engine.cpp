@@ -1637,11 +1637,8 @@ int capf_fliptest_fuse(void* stream, const float* pred2, int batch, float* out) 
 }
 
 int capf_fliptest_fuse_swap(void* stream, const float* pred2, int batch, int joints, const int32_t* swap, float* out) {
-    if (!pred2 || !out || !swap || batch <= 0 || joints <= 0 || joints > capf::FLIP_MAX_JOINTS) return CAPF_ERR_INVALID;
-    for (int j = 0; j < joints; ++j)           // a permutation that is its own inverse (left <-> right pairs, the rest fixed)
-        if (swap[j] < 0 || swap[j] >= joints || swap[swap[j]] != j) return CAPF_ERR_INVALID;
-    return capf::launch_fliptest_fuse_swap(pred2, batch, joints, swap, out, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK
-                                                                                                                       : CAPF_ERR_HIP;
+    if (!pred2 || !out || batch <= 0 || !capf::swap_table_ok(swap, joints)) return CAPF_ERR_INVALID;
+    return capf::launch_fliptest_fuse_swap(pred2, batch, joints, swap, out, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
 int capf_affine_from_center_scale(const double center[2], const double scale[2], int out_w, int out_h, double m[6]) {
@@ -1692,18 +1689,33 @@ size_t capf_kp_head_scratch_bytes(int B, int H, int W, int C, int J, int backwar
     return (g.fwd_elems + (backward ? g.stat_elems + g.bw_elems : 0)) * sizeof(float);
 }
 
+// a map's base address serves its widest load: 16 bytes of fp32, 8 of a 16-bit format
+static bool map_aligned(const void* map, int dtype) { return (reinterpret_cast<uintptr_t>(map) & (dtype == CAPF_F32 ? 15 : 7)) == 0; }
+
 static int kp_head_check(const void* map, int map_dtype, const float* weight, int B, int H, int W, int C, int J, int mode, float beta,
                          const float* decode, const void* scratch, size_t scratch_bytes, int backward) {
     if (!map || !weight || !decode || !scratch) return CAPF_ERR_INVALID;
-    if (B < 1 || H < 1 || W < 1 || J < 1 || J > capf::KP_MAX_JOINTS || C < 4 || C % 4 != 0 || C > capf::KP_MAX_CHANNELS) return CAPF_ERR_INVALID;
+    if (B < 1 || H < 1 || W < 1 || J < 1 || J > capf::MAX_JOINTS || C < 4 || C % 4 != 0 || C > capf::KP_MAX_CHANNELS) return CAPF_ERR_INVALID;
     if (!(beta > 0.f) || !std::isfinite(beta)) return CAPF_ERR_INVALID;
     if ((mode != 0 && mode != 1) || map_dtype < CAPF_F32 || map_dtype > CAPF_F16) return CAPF_ERR_INVALID;
     if (backward && (mode != 1 || map_dtype != CAPF_F32)) return CAPF_ERR_UNSUPPORTED;
     const size_t need = capf_kp_head_scratch_bytes(B, H, W, C, J, backward);
     if (need == 0) return CAPF_ERR_UNSUPPORTED;                                             // (more than 2^24 pixels a frame, a grid beyond 2^31)
     if (scratch_bytes < need) return CAPF_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(map) & (map_dtype == CAPF_F32 ? 15 : 7)) || (reinterpret_cast<uintptr_t>(scratch) & 3)) return CAPF_ERR_INVALID;
+    if (!map_aligned(map, map_dtype) || (reinterpret_cast<uintptr_t>(scratch) & 3)) return CAPF_ERR_INVALID;
     return CAPF_OK;
+}
+
+// the record of a judged call: what the forward, the pair and the backward have in common, and the outputs of the two forward forms
+static capf::KpHeadArgs kp_head_args(const void* map, int map_dtype, const float* weight, const float* bias, int B, int H, int W, int C, int J,
+                                     int mode, float beta, const float* decode, const float* to_image, void* scratch, float* kcrop = nullptr,
+                                     float* k2d = nullptr, float* score = nullptr, float* heat = nullptr) {
+    capf::KpHeadArgs a{};
+    a.x = map; a.dtype = map_dtype; a.wt = weight; a.bias = bias; a.to_image = to_image; a.part = static_cast<float*>(scratch);
+    a.B = B; a.H = H; a.W = W; a.C = C; a.J = J; a.mode = mode; a.beta = beta;
+    std::copy(decode, decode + 4, a.dec);
+    a.kcrop = kcrop; a.k2d = to_image ? k2d : nullptr; a.score = score; a.heat = heat;
+    return a;
 }
 
 int capf_kp_head_forward(void* stream, const void* map_nhwc, int map_dtype, const float* weight, const float* bias, int B, int H, int W, int C,
@@ -1711,12 +1723,8 @@ int capf_kp_head_forward(void* stream, const void* map_nhwc, int map_dtype, cons
                          float* heat, void* scratch, size_t scratch_bytes) {
     if (!kcrop) return CAPF_ERR_INVALID;
     if (const int rc = kp_head_check(map_nhwc, map_dtype, weight, B, H, W, C, J, mode, beta, decode, scratch, scratch_bytes, 0)) return rc;
-    capf::KpHeadArgs a{};
-    a.x = map_nhwc; a.dtype = map_dtype; a.wt = weight; a.bias = bias; a.to_image = to_image;
-    a.kcrop = kcrop; a.k2d = to_image ? k2d : nullptr; a.score = score; a.heat = heat; a.part = static_cast<float*>(scratch);
-    a.B = B; a.H = H; a.W = W; a.C = C; a.J = J; a.mode = mode; a.beta = beta;
-    for (int i = 0; i < 4; ++i) a.dec[i] = decode[i];
-    return capf::launch_kp_head_forward(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+    return capf::launch_kp_head_forward(kp_head_args(map_nhwc, map_dtype, weight, bias, B, H, W, C, J, mode, beta, decode, to_image, scratch, kcrop,
+                                                     k2d, score, heat), static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
 // the flip-test pair: the map holds 2 * Bsrc frames, everything else is sized by Bsrc
@@ -1730,15 +1738,12 @@ int capf_kp_head_forward_pair(void* stream, const void* map_nhwc, int map_dtype,
                               float mirror_width, float* kcrop2, float* k2d2, float* score, float* heat, void* scratch, size_t scratch_bytes) {
     if (!kcrop2 || !swap || (k2d2 && !to_image) || (shift != 0 && shift != 1) || !std::isfinite(mirror_width) || Bsrc > (1 << 30)) return CAPF_ERR_INVALID;
     if (const int rc = kp_head_check(map_nhwc, map_dtype, weight, Bsrc, H, W, C, J, mode, beta, decode, scratch, scratch_bytes, 0)) return rc;
+    if (!capf::swap_table_ok(swap, J)) return CAPF_ERR_INVALID;
     capf::KpPairArgs a{};
-    for (int j = 0; j < J; ++j) {              // a permutation that is its own inverse (capf_fliptest_fuse_swap's rule)
-        if (swap[j] < 0 || swap[j] >= J || swap[swap[j]] != j) return CAPF_ERR_INVALID;
-        a.swap.j[j] = swap[j];
-    }
-    a.x = map_nhwc; a.dtype = map_dtype; a.wt = weight; a.bias = bias; a.to_image = to_image;
-    a.kcrop = kcrop2; a.k2d = to_image ? k2d2 : nullptr; a.score = score; a.heat = heat; a.part = static_cast<float*>(scratch);
-    a.B = Bsrc; a.H = H; a.W = W; a.C = C; a.J = J; a.mode = mode; a.beta = beta; a.shift = shift; a.mirror_w = mirror_width;
-    for (int i = 0; i < 4; ++i) a.dec[i] = decode[i];
+    static_cast<capf::KpHeadArgs&>(a) = kp_head_args(map_nhwc, map_dtype, weight, bias, Bsrc, H, W, C, J, mode, beta, decode, to_image, scratch,
+                                                     kcrop2, k2d2, score, heat);
+    std::copy(swap, swap + J, a.swap.j);
+    a.shift = shift; a.mirror_w = mirror_width;
     return capf::launch_kp_head_forward_pair(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
@@ -1748,10 +1753,7 @@ int capf_kp_head_backward(void* stream, const float* dkcrop, const float* dk2d, 
     if (!dweight || !dbias || (!dkcrop && !dk2d) || (dk2d && !to_image) || (accumulate != 0 && accumulate != 1)) return CAPF_ERR_INVALID;
     if (const int rc = kp_head_check(map_nhwc, map_dtype, weight, B, H, W, C, J, mode, beta, decode, scratch, scratch_bytes, 1)) return rc;
     if (reinterpret_cast<uintptr_t>(dmap) & 15) return CAPF_ERR_INVALID;
-    capf::KpHeadArgs a{};
-    a.x = map_nhwc; a.dtype = map_dtype; a.wt = weight; a.bias = bias; a.to_image = to_image; a.part = static_cast<float*>(scratch);
-    a.B = B; a.H = H; a.W = W; a.C = C; a.J = J; a.mode = mode; a.beta = beta;
-    for (int i = 0; i < 4; ++i) a.dec[i] = decode[i];
+    capf::KpHeadArgs a = kp_head_args(map_nhwc, map_dtype, weight, bias, B, H, W, C, J, mode, beta, decode, to_image, scratch);
     a.dkcrop = dkcrop; a.dk2d = dk2d; a.dW = dweight; a.dbias = dbias; a.dmap = dmap; a.accumulate = accumulate;
     return capf::launch_kp_head_backward(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
@@ -1766,18 +1768,31 @@ size_t capf_cpn_decode_lds_bytes(int H, int W) {
     return n == (size_t)-1 ? 0 : n;
 }
 
+// the record of a call, filled before it is judged (B: the frames decoded, the pair's Bsrc) ...
+static capf::CpnDecodeArgs cpn_decode_args(const void* heat, int heat_dtype, int B, int H, int W, int C, int J, const float* decode,
+                                           const float* to_image, float* kcrop, float* k2d, float* score, double* blurred) {
+    capf::CpnDecodeArgs a{};
+    a.heat = heat; a.dtype = heat_dtype; a.B = B; a.H = H; a.W = W; a.C = C; a.J = J;
+    if (decode) std::copy(decode, decode + 4, a.dec);
+    a.to_image = to_image; a.kcrop = kcrop; a.k2d = k2d; a.score = score; a.blurred = blurred;      // (k2d without to_image: cpn_decode_check refuses it)
+    return a;
+}
+
+// ... and what the single decode and the pair judge alike.  Not the limit on B * J: the two entries answer it with different codes, each keeps
+// its own comparison.
+static int cpn_decode_check(const capf::CpnDecodeArgs& a, const float* decode) {
+    if (!a.heat || !a.kcrop || !decode || (a.k2d && !a.to_image)) return CAPF_ERR_INVALID;
+    if (a.B < 1 || a.H < 1 || a.W < 1 || a.J < 1 || a.J > a.C || a.C > capf::MAX_JOINTS) return CAPF_ERR_INVALID;
+    if (a.dtype < CAPF_F32 || a.dtype > CAPF_F16) return CAPF_ERR_INVALID;
+    if (!map_aligned(a.heat, a.dtype) || (reinterpret_cast<uintptr_t>(a.kcrop) & 3) || (reinterpret_cast<uintptr_t>(a.blurred) & 7)) return CAPF_ERR_INVALID;
+    return capf::cpn_decode_lds_bytes(a.H, a.W) > capf::CPN_LDS_LIMIT ? CAPF_ERR_UNSUPPORTED : CAPF_OK;   // (a workgroup's two planes must fit the 160 KiB of a CU)
+}
+
 int capf_cpn_decode(void* stream, const void* heat_nhwc, int heat_dtype, int B, int H, int W, int C, int J, const float decode[4],
                     const float* to_image, float* kcrop, float* k2d, float* score, double* blurred) {
-    if (!heat_nhwc || !kcrop || !decode || (k2d && !to_image)) return CAPF_ERR_INVALID;
-    if (B < 1 || H < 1 || W < 1 || J < 1 || J > C || C > 32 || (long)B * J >= (1L << 31)) return CAPF_ERR_INVALID;
-    if (heat_dtype < CAPF_F32 || heat_dtype > CAPF_F16) return CAPF_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(heat_nhwc) & (heat_dtype == CAPF_F32 ? 15 : 7)) return CAPF_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(kcrop) & 3) || (reinterpret_cast<uintptr_t>(blurred) & 7)) return CAPF_ERR_INVALID;
-    if (capf::cpn_decode_lds_bytes(H, W) > capf::CPN_LDS_LIMIT) return CAPF_ERR_UNSUPPORTED;      // (the two planes of a workgroup must fit the 160 KiB of a CU)
-    capf::CpnDecodeArgs a{};
-    a.heat = heat_nhwc; a.dtype = heat_dtype; a.B = B; a.H = H; a.W = W; a.C = C; a.J = J;
-    for (int i = 0; i < 4; ++i) a.dec[i] = decode[i];
-    a.to_image = to_image; a.kcrop = kcrop; a.k2d = to_image ? k2d : nullptr; a.score = score; a.blurred = blurred;
+    const capf::CpnDecodeArgs a = cpn_decode_args(heat_nhwc, heat_dtype, B, H, W, C, J, decode, to_image, kcrop, k2d, score, blurred);
+    if ((long)B * J >= (1L << 31)) return CAPF_ERR_INVALID;
+    if (const int rc = cpn_decode_check(a, decode)) return rc;
     return capf::launch_cpn_decode(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
@@ -1785,20 +1800,13 @@ int capf_cpn_decode(void* stream, const void* heat_nhwc, int heat_dtype, int B, 
 int capf_cpn_decode_pair(void* stream, const void* heat_nhwc, int heat_dtype, int Bsrc, int H, int W, int C, int J, const int32_t* swap,
                          const float decode[4], const float* to_image, float mirror_width, float* kcrop2, float* k2d2, float* score,
                          double* blurred, float* fused) {
-    if (!heat_nhwc || !kcrop2 || !decode || !swap || (k2d2 && !to_image) || !std::isfinite(mirror_width)) return CAPF_ERR_INVALID;
-    if (Bsrc < 1 || H < 1 || W < 1 || J < 1 || J > C || C > 32) return CAPF_ERR_INVALID;
-    if (heat_dtype < CAPF_F32 || heat_dtype > CAPF_F16) return CAPF_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(heat_nhwc) & (heat_dtype == CAPF_F32 ? 15 : 7)) return CAPF_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(kcrop2) & 3) || (reinterpret_cast<uintptr_t>(blurred) & 7) || (reinterpret_cast<uintptr_t>(fused) & 3)) return CAPF_ERR_INVALID;
     capf::CpnPairArgs a{};
-    for (int j = 0; j < J; ++j) {              // a permutation that is its own inverse (capf_fliptest_fuse_swap's rule)
-        if (swap[j] < 0 || swap[j] >= J || swap[swap[j]] != j) return CAPF_ERR_INVALID;
-        a.swap.j[j] = swap[j];
-    }
-    if (capf::cpn_decode_lds_bytes(H, W) > capf::CPN_LDS_LIMIT || (long)Bsrc * J >= (1L << 31)) return CAPF_ERR_UNSUPPORTED;
-    a.heat = heat_nhwc; a.dtype = heat_dtype; a.B = Bsrc; a.H = H; a.W = W; a.C = C; a.J = J;
-    for (int i = 0; i < 4; ++i) a.dec[i] = decode[i];
-    a.to_image = to_image; a.kcrop = kcrop2; a.k2d = to_image ? k2d2 : nullptr; a.score = score; a.blurred = blurred;
+    static_cast<capf::CpnDecodeArgs&>(a) = cpn_decode_args(heat_nhwc, heat_dtype, Bsrc, H, W, C, J, decode, to_image, kcrop2, k2d2, score, blurred);
+    if (!swap || !std::isfinite(mirror_width) || (reinterpret_cast<uintptr_t>(fused) & 3)) return CAPF_ERR_INVALID;
+    const int rc = cpn_decode_check(a, decode);
+    if (rc == CAPF_ERR_INVALID || !capf::swap_table_ok(swap, J)) return CAPF_ERR_INVALID;      // (a bad table outranks a plane too large for LDS)
+    if (rc || (long)Bsrc * J >= (1L << 31)) return CAPF_ERR_UNSUPPORTED;       // (rc: cpn_decode_check answers OK, INVALID or UNSUPPORTED, nothing else)
+    std::copy(swap, swap + J, a.swap.j);
     a.mirror_w = mirror_width; a.fused = fused;
     return capf::launch_cpn_decode_pair(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }

@@ -716,8 +716,18 @@ hipError_t launch_preprocess(const unsigned char* images_bgr, int B, int H, int 
 hipError_t launch_preprocess_points(int B, int mode, const float* gt_in, float* gt_out, const float* k2d_in, float* k2d_out,
                                     const float* kc_in, float* kc_out, hipStream_t s);
 hipError_t launch_fliptest_fuse(const float* pred2, int B, float* out, hipStream_t s);     // the H36M table (kSwap)
-// any skeleton: swap[j] = the joint whose mirrored prediction lands on joint j (J <= FLIP_MAX_JOINTS; a kernel argument)
-constexpr int FLIP_MAX_JOINTS = 32;
+// A mirror's joint exchange for any skeleton of J <= MAX_JOINTS joints: swap[j] = the joint of the mirror that lands on joint j.  The table
+// travels in the kernel arguments (no per-call device allocation).  It is a permutation that is its own inverse (left <-> right pairs, the
+// rest fixed) -- the ONE statement of that rule: the C ABI entries that take a table judge it with this, and the three launchers that put a
+// table into kernel arguments call it again before a kernel indexes by it.
+constexpr int MAX_JOINTS = 32;
+struct SwapTable { int j[MAX_JOINTS]; };
+inline bool swap_table_ok(const int* swap, int J) {
+    if (!swap || J < 1 || J > MAX_JOINTS) return false;
+    for (int j = 0; j < J; ++j)
+        if (swap[j] < 0 || swap[j] >= J || swap[swap[j]] != j) return false;
+    return true;
+}
 hipError_t launch_fliptest_fuse_swap(const float* pred2, int B, int J, const int* swap, float* out, hipStream_t s);
 // N3 (preprocess.hip): get_affine_transform (host) and cv2.warpAffine INTER_LINEAR for 8-bit BGR frames
 bool affine_from_center_scale(const double center[2], const double scale[2], int out_w, int out_h, double M[6]);
@@ -736,7 +746,6 @@ hipError_t launch_keypoints_loss(const float* pred, const float* gt, const float
                                  float* loss, float* dpred, hipStream_t s);
 
 // ---- 2-D keypoint head (kp_head.hip): final_layer (1x1 conv) on feat0 + heatmap decode, one pass over the map ------------------------
-constexpr int KP_MAX_JOINTS = 32;
 constexpr int KP_MAX_CHANNELS = 512;
 constexpr int KP_MAX_SLABS = 64;             // forward: slabs of 256-pixel tiles per frame (a function of H * W alone)
 constexpr int KP_BW_SLABS = 8;               // backward: blocks per frame, each leaves one partial of dW
@@ -777,9 +786,8 @@ hipError_t launch_kp_head_backward(KpHeadArgs a, hipStream_t s);
 // the flip-test pair (capf_kp_head_forward_pair): x holds [2 B, H, W, C], frame B + b the mirror of source frame b; B counts SOURCE frames
 // (grids, scratch and to_image [B, 2, 3] are the single entry's at B); kcrop / k2d are the stacks [2, B, J, 2], score [B, J], heat
 // [B, J, H, W] the fused logits.  Forward only.
-struct KpSwap { int j[KP_MAX_JOINTS]; };     // swap[j] = the joint of the mirror whose heatmap lands on joint j; travels in the kernel arguments
 struct KpPairArgs : KpHeadArgs {
-    KpSwap swap;
+    SwapTable swap;
     int shift;               // 1: HRNet's SHIFT_HEATMAP (the flipped-back heatmap moved one column to the right, column 0 kept)
     float mirror_w;          // kcrop2[1].x = (mirror_w - x) - 1
 };
@@ -811,9 +819,8 @@ hipError_t launch_cpn_decode(CpnDecodeArgs a, hipStream_t s);
 // CPN's test-time flip (capf_cpn_decode_pair; cpn/test.py:62-70): heat holds [2 B, H, W, C], frame B + b the mirror of source frame b; B counts
 // SOURCE frames (the grid and to_image [B, 2, 3] are the single entry's at B).  The fold zf = 0.5 (zo + zm) happens in the load, the decode of zf
 // is the single form's; kcrop / k2d are the stacks [2, B, J, 2], score [B, J], blurred [B, J, H + 20, W + 20].
-struct CpnSwap { int j[32]; };               // swap[j] = the joint of the mirror whose heatmap lands on joint j; travels in the kernel arguments
 struct CpnPairArgs : CpnDecodeArgs {
-    CpnSwap swap;
+    SwapTable swap;
     float mirror_w;          // kcrop2[1].x = (mirror_w - x) - 1
     float* fused;            // [B, J, H, W] or NULL: zf, as the decode used it
 };

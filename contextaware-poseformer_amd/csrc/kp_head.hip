@@ -27,6 +27,7 @@
 #include <math.h>
 
 #include "kernels.h"
+#include "pair_stacks.h"
 
 namespace capf {
 
@@ -52,7 +53,7 @@ struct KpLd16 {
 
 KpGeom kp_geom(int B, int H, int W, int C, int J) {
     KpGeom g{};
-    if (B < 1 || H < 1 || W < 1 || J < 1 || J > KP_MAX_JOINTS || C < 4 || C % 4 != 0 || C > KP_MAX_CHANNELS) return g;
+    if (B < 1 || H < 1 || W < 1 || J < 1 || J > MAX_JOINTS || C < 4 || C % 4 != 0 || C > KP_MAX_CHANNELS) return g;
     const long HW = (long)H * W;
     if (HW > (1L << 24)) return g;                                  // (a pixel index and its row / column are exact in fp32)
     g.ntiles = (int)((HW + KP_THREADS - 1) / KP_THREADS);
@@ -71,13 +72,13 @@ KpGeom kp_geom(int B, int H, int W, int C, int J) {
 // the J logits of one pixel: acc[j] = bias[j], then one fmaf per channel, ascending
 template <class L>
 __device__ __forceinline__ void kp_logits(const typename L::T* __restrict__ xp, const float* __restrict__ wt, const float* __restrict__ bias,
-                                          const int C, const int J, float (&acc)[KP_MAX_JOINTS]) {
+                                          const int C, const int J, float (&acc)[MAX_JOINTS]) {
 #pragma unroll
-    for (int j = 0; j < KP_MAX_JOINTS; ++j) acc[j] = bias ? bias[j < J ? j : J - 1] : 0.f;
+    for (int j = 0; j < MAX_JOINTS; ++j) acc[j] = bias ? bias[j < J ? j : J - 1] : 0.f;
     for (int c = 0; c < C; c += 4) {                                // (loads grouped 16 channels ahead of their FMAs measured no faster: R24.1)
         const f32x4 v = L::ld4(xp + c);
 #pragma unroll
-        for (int jg = 0; jg < KP_MAX_JOINTS / 4; ++jg) {
+        for (int jg = 0; jg < MAX_JOINTS / 4; ++jg) {
             if (jg * 4 < J) {                                       // (uniform; the joints of a group beyond J compute a copy of joint J - 1)
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
@@ -145,7 +146,7 @@ template <> struct KpArgsOf<true> { typedef KpPairArgs type; };
 // so the fold needs no barrier.  Everything after it is the single decode.
 template <class L, int MODE, bool PAIR>
 __global__ void __launch_bounds__(KP_THREADS) kp_fwd_slab_kernel(const typename KpArgsOf<PAIR>::type a) {
-    __shared__ float zs[KP_MAX_JOINTS * KP_ZS];
+    __shared__ float zs[MAX_JOINTS * KP_ZS];
     const int tid = threadIdx.x;
     const int b = (int)blockIdx.x / a.g.nslab, s = (int)blockIdx.x - b * a.g.nslab;
     const int HW = a.H * a.W, J = a.J;
@@ -158,10 +159,10 @@ __global__ void __launch_bounds__(KP_THREADS) kp_fwd_slab_kernel(const typename 
     for (int t = t0; t < t1; ++t) {
         const int pix = t * KP_THREADS + tid;
         if (pix < HW) {
-            float acc[KP_MAX_JOINTS];
+            float acc[MAX_JOINTS];
             kp_logits<L>(xb + (size_t)pix * a.C, a.wt, a.bias, a.C, J, acc);
 #pragma unroll
-            for (int j = 0; j < KP_MAX_JOINTS; ++j) {
+            for (int j = 0; j < MAX_JOINTS; ++j) {
                 if (j < J) {
                     zs[j * KP_ZS + tid] = acc[j];
                     if (!PAIR && a.heat) a.heat[((size_t)b * J + j) * HW + pix] = acc[j];
@@ -171,7 +172,7 @@ __global__ void __launch_bounds__(KP_THREADS) kp_fwd_slab_kernel(const typename 
                 const int row = pix / a.W, col = pix - row * a.W;
                 kp_logits<L>(xm + ((size_t)row * a.W + kp_mirror_col(col, a.W, a.shift)) * a.C, a.wt, a.bias, a.C, J, acc);
 #pragma unroll
-                for (int js = 0; js < KP_MAX_JOINTS; ++js) {
+                for (int js = 0; js < MAX_JOINTS; ++js) {
                     if (js < J) {
                         float* z = zs + a.swap.j[js] * KP_ZS + tid;
                         *z = __fmul_rn(0.5f, __fadd_rn(*z, acc[js]));  // the fp32 sum rounded once, then halved
@@ -250,28 +251,14 @@ __device__ __forceinline__ float kp_pair_logit1(const KpPairArgs& a, const int b
     return __fmul_rn(0.5f, __fadd_rn(zo, zm));
 }
 
-// The pair's outputs from the decoded heatmap coordinates (x, y) of (b, j): both sets of the stacks -- the thread also fills joint swap[j] of
-// the mirrored set, and swap is a permutation, so every element has one writer.  Every operation is rounded on its own, as capf.h writes the
-// expressions: __fmul_rn / __fadd_rn are plain operators to this compiler, which contracts A00 kx + A01 ky of the single form below into an
-// fma (that form keeps the code it always had); here contraction is off, so k2d2[0] is the float32 expression itself and k2d2 / kcrop2 are
-// capf_preprocess_points' bits.
+// The pair's outputs from the decoded heatmap coordinates (x, y) of (b, j): write_pair_stacks' (pair_stacks.h).  Every operation is rounded on
+// its own, as capf.h writes the expressions: __fmul_rn / __fadd_rn are plain operators to this compiler, which contracts A00 kx + A01 ky of the
+// single form below into an fma (that form keeps the code it always had); here contraction is off, for the decode scale as in the writer.
 __device__ __forceinline__ void kp_pair_outputs(const KpPairArgs& a, const int b, const int j, const float x, const float y, const float score) {
 #pragma clang fp contract(off)
-    const size_t i = ((size_t)b * a.J + j) * 2, im = ((size_t)(a.B + b) * a.J + a.swap.j[j]) * 2;
-    const float kx = a.dec[0] * x + a.dec[1], ky = a.dec[2] * y + a.dec[3];
-    a.kcrop[i] = kx;
-    a.kcrop[i + 1] = ky;
-    a.kcrop[im] = (a.mirror_w - kx) - 1.0f;
-    a.kcrop[im + 1] = ky;
-    if (a.score) a.score[i / 2] = score;
-    if (a.to_image && a.k2d) {
-        const float* A = a.to_image + (size_t)b * 6;
-        const float ix = (A[0] * kx + A[1] * ky) + A[2], iy = (A[3] * kx + A[4] * ky) + A[5];
-        a.k2d[i] = ix;
-        a.k2d[i + 1] = iy;
-        a.k2d[im] = -ix;
-        a.k2d[im + 1] = iy;
-    }
+    const size_t o = (size_t)b * a.J + j, om = (size_t)(a.B + b) * a.J + a.swap.j[j];       // (B <= 2^30: B + b is an int)
+    write_pair_stacks(a.kcrop, a.k2d, a.score, o, om, a.to_image && a.k2d ? a.to_image + (size_t)b * 6 : nullptr, a.mirror_w,
+                      a.dec[0] * x + a.dec[1], a.dec[2] * y + a.dec[3], score);
 }
 
 // PAIR: the neighbours of the quarter shift are fused logits; the outputs are kp_pair_outputs'
@@ -337,8 +324,8 @@ __global__ void __launch_bounds__(KP_THREADS) kp_fwd_combine_kernel(const typena
 
 // ---- backward of the integral decode --------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(KP_THREADS) kp_bwd_kernel(const KpHeadArgs a) {
-    __shared__ float zs[KP_MAX_JOINTS * KP_ZS];
-    __shared__ float st[KP_MAX_JOINTS][6];                          // m, 1 / sum, x, y, gx, gy
+    __shared__ float zs[MAX_JOINTS * KP_ZS];
+    __shared__ float st[MAX_JOINTS][6];                             // m, 1 / sum, x, y, gx, gy
     const int tid = threadIdx.x;
     const int b = (int)blockIdx.x / a.g.nbw, s = (int)blockIdx.x - b * a.g.nbw;
     const int HW = a.H * a.W, J = a.J, C = a.C;
@@ -364,11 +351,11 @@ __global__ void __launch_bounds__(KP_THREADS) kp_bwd_kernel(const KpHeadArgs a) 
         const int base = t * KP_THREADS, pix = base + tid;
         const int n = HW - base < KP_THREADS ? HW - base : KP_THREADS;
         if (pix < HW) {
-            float acc[KP_MAX_JOINTS];
+            float acc[MAX_JOINTS];
             kp_logits<KpLdF32>(xb + (size_t)pix * C, a.wt, a.bias, C, J, acc);
             const int row = pix / a.W, col = pix - row * a.W;
 #pragma unroll
-            for (int j = 0; j < KP_MAX_JOINTS; ++j) {
+            for (int j = 0; j < MAX_JOINTS; ++j) {
                 if (j < J) {
                     const float p = expf(a.beta * acc[j] - st[j][0]) * st[j][1];
                     const float dz = a.beta * p * (st[j][4] * ((float)col - st[j][2]) + st[j][5] * ((float)row - st[j][3]));
@@ -381,7 +368,7 @@ __global__ void __launch_bounds__(KP_THREADS) kp_bwd_kernel(const KpHeadArgs a) 
                 for (int c = 0; c < C; c += 4) {
                     f32x4 d = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int j = 0; j < KP_MAX_JOINTS; ++j) {
+                    for (int j = 0; j < MAX_JOINTS; ++j) {
                         if (j < J) {
                             const float* __restrict__ w = a.wt + (size_t)j * C + c;
                             d[0] = fmaf(acc[j], w[0], d[0]);
@@ -455,9 +442,7 @@ hipError_t launch_kp_head_forward(KpHeadArgs a, hipStream_t s) {
 
 hipError_t launch_kp_head_forward_pair(KpPairArgs a, hipStream_t s) {
     a.g = kp_geom(a.B, a.H, a.W, a.C, a.J);
-    if (!kp_args_ok(a) || !a.kcrop || a.B > (1 << 30) || (a.shift != 0 && a.shift != 1)) return hipErrorInvalidValue;
-    for (int j = 0; j < a.J; ++j)
-        if (a.swap.j[j] < 0 || a.swap.j[j] >= a.J || a.swap.j[a.swap.j[j]] != j) return hipErrorInvalidValue;
+    if (!kp_args_ok(a) || !a.kcrop || a.B > (1 << 30) || (a.shift != 0 && a.shift != 1) || !swap_table_ok(a.swap.j, a.J)) return hipErrorInvalidValue;
     a.stats = nullptr;
     if (a.dtype == 0) kp_forward_launches<KpLdF32, true>(a, s);
     else if (a.dtype == 1) kp_forward_launches<KpLd16<Bf16Fmt>, true>(a, s);

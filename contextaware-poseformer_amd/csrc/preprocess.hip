@@ -94,11 +94,8 @@ hipError_t launch_preprocess_points(int B, int mode, const float* gt_in, float* 
 }
 
 // out[b, j, :] = 0.5 * (pred[0, b, j, :] + unmirror(pred[1, b, :, :])[j])     (train.py:177-180)
-// the swap table travels in the kernel arguments (no per-call device allocation): swap[j] = the joint of the mirrored
-// prediction that lands on joint j
-struct FlipSwap { int j[FLIP_MAX_JOINTS]; };
-
-__global__ void fliptest_fuse_kernel(const float* __restrict__ pred2, float* __restrict__ out, int B, int J, FlipSwap sw) {
+// (the swap table is kernels.h' SwapTable)
+__global__ void fliptest_fuse_kernel(const float* __restrict__ pred2, float* __restrict__ out, int B, int J, SwapTable sw) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= B * J) return;
     const int j = t % J, b = t / J;
@@ -112,12 +109,9 @@ __global__ void fliptest_fuse_kernel(const float* __restrict__ pred2, float* __r
 }
 
 hipError_t launch_fliptest_fuse_swap(const float* pred2, int B, int J, const int* swap, float* out, hipStream_t s) {
-    if (B <= 0 || J <= 0 || J > FLIP_MAX_JOINTS || (long)B * J > 0x7fffffffL) return hipErrorInvalidValue;
-    FlipSwap sw{};
-    for (int j = 0; j < J; ++j) {
-        if (swap[j] < 0 || swap[j] >= J) return hipErrorInvalidValue;
-        sw.j[j] = swap[j];
-    }
+    if (B <= 0 || !swap_table_ok(swap, J) || (long)B * J > 0x7fffffffL) return hipErrorInvalidValue;
+    SwapTable sw{};
+    for (int j = 0; j < J; ++j) sw.j[j] = swap[j];
     hipLaunchKernelGGL(fliptest_fuse_kernel, dim3((B * J + 127) / 128), dim3(128), 0, s, pred2, out, B, J, sw);
     return hipGetLastError();
 }

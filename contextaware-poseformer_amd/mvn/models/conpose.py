@@ -14,8 +14,8 @@ import collections
 import torch
 from torch import nn
 
-from capf.lib import (KP_INTEGRAL, KP_MODES, PLAN_BN_BATCH_STATS, PLAN_CPN_PREDICT, CapfError, Engine, cpn_decode, cpn_decode_pair, input_constants,
-                      kp_head_backward, kp_head_forward, kp_head_forward_pair)
+from capf.lib import (KP_INTEGRAL, KP_MODES, PLAN_BN_BATCH_STATS, PLAN_CPN_PREDICT, CapfError, Engine, cpn_decode, cpn_decode_pair, fliptest_fuse,
+                      input_constants, kp_head_backward, kp_head_forward, kp_head_forward_pair)
 
 from . import _native
 
@@ -204,6 +204,68 @@ def keypoint_head(map_nhwc, weight, bias=None, to_image=None, mode="integral", b
     return kcrop, score, (k2d if to_image is not None else None)
 
 
+# What CA_PF's two detect flows (_single_flow, _pair_flow) need to know about a keypoint head -- everything that differs between the heads is
+# here and nowhere else; CA_PF.__init__ picks one from keypoint_head.  `m` is the CA_PF.
+#   maps                            the workspace tensor the head reads, as Engine.tensor_view names it
+#   decode(H, W, h, w)              heatmap [h, w] -> pixels of the H x W crop, as (sx, ox, sy, oy)
+#   trains(m)                       this call must produce gradients of the head's parameters; refuses what has no derivative
+#   single(m, eng, maps, decode, to_image, trains) -> (kcrop, score, k2d | None, guard | None)
+#   pair(m, maps, decode, to_image, swap, ...)     -> (kcrop2 [2,B,J,2], score [B,J], k2d2 [2,B,J,2] | None); always without grad.  What only
+#                                   one head's pair takes follows `swap` as a keyword of the entry's: `shift` (_FinalLayerHead: HRNet's
+#                                   SHIFT_HEATMAP; detect_flip_test / forward_detect_flip_test pass it), nothing for _CpnHead
+# The record is fixed at construction.  keypoint_head_mode may still be switched between "argmax" and "integral" afterwards (both are
+# _FinalLayerHead, which reads the mode at each call); switching to or from "cpn" that way is not supported (other plan, other parameters).
+class _FinalLayerHead:
+    """keypoint_head="argmax" / "integral": self.keypoint_head.final_layer and the heatmap decode, one native pass over feat0."""
+    maps = "feat0"
+
+    @staticmethod
+    def decode(H, W, h, w):
+        return (float(W) / w, 0.0, float(H) / h, 0.0)       # HRNet's convention: heatmap cell -> crop pixel
+
+    @staticmethod
+    def trains(m):
+        return m._head_trains()
+
+    @staticmethod
+    def single(m, eng, feat0, decode, to_image, trains):
+        weight, bias = m._head_params()
+        guard = {"eng": eng, "token": None} if trains else None
+        with torch.set_grad_enabled(trains):
+            kcrop, score, k2d = _KeypointHeadFn.apply(feat0, weight, bias, to_image, KP_MODES[m.keypoint_head_mode], m.keypoint_beta, decode, guard)
+        return kcrop, score, (k2d if to_image is not None else None), guard
+
+    @staticmethod
+    def pair(m, feat0, decode, to_image, swap, shift):
+        weight, bias = m._head_params()
+        return kp_head_forward_pair(feat0, weight.detach(), bias.detach(), KP_MODES[m.keypoint_head_mode], m.keypoint_beta, swap, bool(shift),
+                                    decode, to_image, float(2 * CROP_HALF[0]))[:3]
+
+
+class _CpnHead:
+    """keypoint_head="cpn": the backbone pass ran refine_net.final_predict too; CPN's two-peak decode of its heatmaps.  No derivative."""
+    maps = "heat"
+
+    @staticmethod
+    def decode(H, W, h, w):
+        sx, sy = float(W) / w, float(H) / h
+        return (sx, 0.5 * sx, sy, 0.5 * sy)      # CPN's convention, (4 x + 2) / data_shape of cpn/test.py:106-107 in crop pixels: a cell's centre
+
+    @staticmethod
+    def trains(m):
+        m._cpn_head_frozen()
+        return False
+
+    @staticmethod
+    def single(m, eng, heat, decode, to_image, trains):
+        with torch.no_grad():
+            return cpn_decode(heat, m.num_joints, decode, to_image)[:3] + (None,)
+
+    @staticmethod
+    def pair(m, heat, decode, to_image, swap):
+        return cpn_decode_pair(heat, m.num_joints, swap, decode, to_image, float(2 * CROP_HALF[0]))[:3]
+
+
 MAP_GRAD_MODES = {"atomic": 0, "ordered": 1}
 BACKBONE_BN_MODES = ("running", "batch")
 BN_MOMENTUM = 0.1      # nn.BatchNorm2d's default, which every BatchNorm of the reference backbones keeps (pose_hrnet.py BN_MOMENTUM = 0.1)
@@ -260,6 +322,7 @@ class CA_PF(nn.Module):
         self.compute_dtype = compute_dtype
         self.backbone_bn = backbone_bn
         self.keypoint_head_mode = keypoint_head
+        self._head = None if keypoint_head is None else _CpnHead if keypoint_head == "cpn" else _FinalLayerHead
         self.keypoint_beta = float(keypoint_beta)
         if backbone_bn == "batch":
             plan_flags |= PLAN_BN_BATCH_STATS
@@ -517,9 +580,13 @@ class CA_PF(nn.Module):
         return self._lift(self._image_source(images_u8, mode), images_u8.shape[1:3], keypoints_2d_cpn, keypoints_2d_cpn_crop, kp_grads)
 
     # ---- detector-free: the 2-D keypoints from the native head on feat0 -------------------------
-    def _head_params(self):
-        if self.keypoint_head_mode is None:
+    def _head_record(self):
+        if self._head is None:
             raise CapfError("this model has no keypoint head: build it with keypoint_head='argmax', 'integral' or 'cpn'")
+        return self._head
+
+    def _head_params(self):
+        self._head_record()
         fl = self.keypoint_head.final_layer
         return fl.weight, fl.bias
 
@@ -556,19 +623,52 @@ class CA_PF(nn.Module):
             to_image = to_image.detach().contiguous()
         return images.contiguous(), to_image
 
-    def _backbone_maps(self, eng, images, stream):
-        """One backbone pass (no gradient reaches it); returns feat0 as a view of the engine's workspace, NHWC in the plan's dtype."""
-        _run_backbone(self, eng, self._image_source(images), stream)
-        return eng.tensor_view("feat0", images.shape[0])
+    # ---- the two detect flows: everything head-specific is in self._head (_FinalLayerHead / _CpnHead) ---------------------------
+    def _lift_workspace(self, eng, dev, batch, k2d, ref, named):
+        """The lifter on the maps the backbone pass of this call left in the workspace (_run_lifter's `named`)."""
+        return self._run_lifter(eng, _Source("workspace", dev, batch, "the maps", None), k2d, ref, named)
 
-    def _run_head(self, eng, feat0, to_image, H, W, trains):
-        weight, bias = self._head_params()
-        decode = (float(W) / feat0.shape[2], 0.0, float(H) / feat0.shape[1], 0.0)       # HRNet's convention: heatmap cell -> crop pixel
-        guard = {"eng": eng, "token": None} if trains else None
-        with torch.set_grad_enabled(trains):
-            kcrop, score, k2d = _KeypointHeadFn.apply(feat0, weight, bias, to_image, KP_MODES[self.keypoint_head_mode], self.keypoint_beta,
-                                                      decode, guard)
-        return kcrop, score, (k2d if to_image is not None else None), guard
+    def _single_flow(self, images, to_image, lift, trains):
+        """detect / forward_detect: inputs, engine, ONE backbone pass (no gradient reaches it), the head on its workspace tensor; with
+        `lift` the lifter on the maps still in the workspace, as a training step when the lifter or the head (`trains`) needs gradients,
+        and the token that lets the head's backward refuse a workspace a later run has overwritten."""
+        head = self._head
+        images, to_image = self._detect_inputs(images, to_image)
+        dev, B, H, W = images.device, images.shape[0], images.shape[1], images.shape[2]
+        with torch.cuda.device(dev):
+            eng = self._engine_at(dev, H, W)
+            named = self._lifter_step_params(trains) if lift else None
+            with torch.no_grad():
+                _run_backbone(self, eng, self._image_source(images), torch.cuda.current_stream(dev).cuda_stream)
+                maps = eng.tensor_view(head.maps, B)
+            kcrop, score, k2d, guard = head.single(self, eng, maps, head.decode(H, W, maps.shape[1], maps.shape[2]), to_image, trains)
+            if not lift:
+                return kcrop, score, k2d
+            # (a crop-keypoint tensor outside the graph would be normalised in place by the lifter: it gets a copy, the caller the pixels)
+            ref = kcrop.detach().clone() if named is None else kcrop if kcrop.requires_grad else kcrop.clone()
+            out = self._lift_workspace(eng, dev, B, k2d, ref, named)
+            if named is not None and guard is not None:
+                guard["token"] = eng.train_generation()
+        return out, kcrop, score
+
+    def _pair_flow(self, images, to_image, flip_pairs, lift, **head_args):
+        """The four flip entries, always without grad: the 2B engine frames [orig | mirrored], engine, ONE backbone pass over them, the
+        paired head (head_args: what only one head's pair takes -- HRNet's shift); with `lift` the lifter on the maps still in the
+        workspace with the stacked keypoints the head wrote, and capf_fliptest_fuse."""
+        head, J = self._head, self.num_joints
+        swap = self._swap_table(flip_pairs)
+        src, B, H, W, to_image = self._flip_test_source(images, to_image)
+        with torch.cuda.device(src.device), torch.no_grad():
+            eng = self._engine_at(src.device, H, W)
+            _run_backbone(self, eng, src, torch.cuda.current_stream(src.device).cuda_stream)
+            maps = eng.tensor_view(head.maps, src.batch)
+            kcrop2, score, k2d2 = head.pair(self, maps, head.decode(H, W, maps.shape[1], maps.shape[2]), to_image, swap, **head_args)
+            if not lift:
+                return kcrop2[0], score, (None if k2d2 is None else k2d2[0])
+            ref = kcrop2.clone().view(2 * B, J, 2)               # (the lifter normalises its crop keypoints in place: the caller keeps the pixels)
+            pred = self._lift_workspace(eng, src.device, 2 * B, k2d2.view(2 * B, J, 2), ref, None)
+            out = fliptest_fuse(pred.view(2, B, 1, J, 3), swap)
+        return out, kcrop2[0], score
 
     # ---- keypoint_head="cpn": the checkpoint's own final_predict (run by the backbone pass) and CPN's two-peak decode -------------
     def _cpn_head_frozen(self):
@@ -583,15 +683,11 @@ class CA_PF(nn.Module):
             raise NotImplementedError("keypoint_head='cpn' is not served by HRNet's shifted flip test (CPN's own test-time flip averages the "
                                       "heatmaps without a column shift): use detect_cpn_flip / forward_detect_cpn_flip")
 
-    def _run_cpn_head(self, eng, images, to_image, stream):
-        """One backbone pass (final_predict included) and capf_cpn_decode on "heat": (kcrop_px, score, k2d | None), outside the graph."""
-        with torch.no_grad():
-            _run_backbone(self, eng, self._image_source(images), stream)
-            heat = eng.tensor_view("heat", images.shape[0])
-            sx, sy = float(images.shape[2]) / heat.shape[2], float(images.shape[1]) / heat.shape[1]
-            # CPN's convention, (4 x + 2) / data_shape of cpn/test.py:106-107 in crop pixels: a heatmap cell's centre
-            kcrop, score, k2d, _ = cpn_decode(heat, self.num_joints, (sx, 0.5 * sx, sy, 0.5 * sy), to_image)
-        return kcrop, score, k2d
+    def _cpn_flip_entry(self, name):
+        if self.keypoint_head_mode != "cpn":
+            raise ValueError("{} is CPN's test-time flip: it needs CA_PF(..., keypoint_head='cpn'), not keypoint_head={!r} (HRNet's flip "
+                             "test: detect_flip_test / forward_detect_flip_test)".format(name, self.keypoint_head_mode))
+        self._cpn_head_frozen()
 
     def detect(self, images, to_image=None):
         """The 2-D keypoints of the crops from the native head: backbone (one pass), final_layer on feat0 and the heatmap decode.
@@ -601,18 +697,9 @@ class CA_PF(nn.Module):
         None): what forward() takes as its third and second argument.  No gradients (see forward_detect).
         keypoint_head="cpn": the backbone pass runs final_predict too and capf_cpn_decode decodes its heatmaps; score is CPN's
         r0 = heatmap / 255 + 0.5 at the keypoint."""
-        cpn = self.keypoint_head_mode == "cpn"
-        if not cpn:
-            self._head_params()
-        images, to_image = self._detect_inputs(images, to_image)
-        dev = images.device
-        with torch.cuda.device(dev), torch.no_grad():
-            eng = self._engine_at(dev, images.shape[1], images.shape[2])
-            if cpn:
-                return self._run_cpn_head(eng, images, to_image, torch.cuda.current_stream(dev).cuda_stream)
-            feat0 = self._backbone_maps(eng, images, torch.cuda.current_stream(dev).cuda_stream)
-            kcrop, score, k2d, _ = self._run_head(eng, feat0, to_image, images.shape[1], images.shape[2], False)
-        return kcrop, score, k2d
+        self._head_record()
+        with torch.no_grad():
+            return self._single_flow(images, to_image, False, False)
 
     def forward_detect(self, images, to_image):
         """forward() without detections from outside: ONE backbone pass, the keypoint head on feat0, the lifter on the maps still in the
@@ -627,30 +714,10 @@ class CA_PF(nn.Module):
         gradients.
         keypoint_head="cpn": final_predict and capf_cpn_decode take the head's place; the head has no derivative (a final_predict
         parameter that requires grad raises under grad), the lifter trains as in forward()."""
-        cpn = self.keypoint_head_mode == "cpn"
-        if cpn:
-            self._cpn_head_frozen()
-        trains = False if cpn else self._head_trains()
+        trains = self._head_record().trains(self)
         if to_image is None:
             raise ValueError("forward_detect needs to_image [B, 2, 3]: the lifter takes the keypoints in normalised image coordinates too")
-        images, to_image = self._detect_inputs(images, to_image)
-        dev, B, H, W = images.device, images.shape[0], images.shape[1], images.shape[2]
-        with torch.cuda.device(dev):
-            eng = self._engine_at(dev, H, W)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            named = self._lifter_step_params(trains)
-            if cpn:
-                (kcrop, score, k2d), guard = self._run_cpn_head(eng, images, to_image, stream), None
-            else:
-                with torch.no_grad():
-                    feat0 = self._backbone_maps(eng, images, stream)
-                kcrop, score, k2d, guard = self._run_head(eng, feat0, to_image, H, W, trains)
-            # (a crop-keypoint tensor outside the graph would be normalised in place by the lifter: it gets a copy, the caller the pixels)
-            ref = kcrop.detach().clone() if named is None else kcrop if kcrop.requires_grad else kcrop.clone()
-            out = self._run_lifter(eng, _Source("workspace", dev, B, "the maps", None), k2d, ref, named)
-            if named is not None and guard is not None:
-                guard["token"] = eng.train_generation()
-        return out, kcrop, score
+        return self._single_flow(images, to_image, True, trains)
 
     # ---- detector-free flip test: the heatmaps of each crop and of its flipped-back mirror averaged, then decoded once -----------
     def _swap_table(self, flip_pairs):
@@ -685,16 +752,6 @@ class CA_PF(nn.Module):
                 src = _Source("images", pair.device, pair.shape[0], "images", pair)
         return src, first.shape[0], first.shape[1], first.shape[2], to_image
 
-    def _run_pair_head(self, eng, src, to_image, H, W, shift, swap):
-        """One backbone pass over the pair and the paired head on its feat0: (kcrop2 [2,B,J,2], score [B,J], k2d2 [2,B,J,2] | None)."""
-        weight, bias = self._head_params()
-        _run_backbone(self, eng, src, torch.cuda.current_stream(src.device).cuda_stream)
-        feat0 = eng.tensor_view("feat0", src.batch)
-        decode = (float(W) / feat0.shape[2], 0.0, float(H) / feat0.shape[1], 0.0)
-        kcrop2, score, k2d2, _ = kp_head_forward_pair(feat0, weight.detach(), bias.detach(), KP_MODES[self.keypoint_head_mode], self.keypoint_beta,
-                                                      swap, bool(shift), decode, to_image, float(2 * CROP_HALF[0]))
-        return kcrop2, score, k2d2
-
     def detect_flip_test(self, images, to_image=None, shift=True, flip_pairs=None):
         """detect() under HRNet's flip test: ONE backbone pass over the crops and their mirrors, then capf_kp_head_forward_pair -- per joint
         the heatmap of the crop and the flipped-back heatmap of the mirror (x mirrored, left / right joints exchanged, moved one column to
@@ -704,12 +761,8 @@ class CA_PF(nn.Module):
         (capf.lib.MPI_SWAP).  Returns (kcrop_px [B,J,2], score [B,J], k2d [B,J,2] | None).  Always runs without
         grad and returns detached tensors: the paired decode has no backward.  keypoint_head="cpn": NotImplementedError."""
         self._no_cpn_flip_test()
-        self._head_params()
-        swap = self._swap_table(flip_pairs)
-        src, B, H, W, to_image = self._flip_test_source(images, to_image)
-        with torch.cuda.device(src.device), torch.no_grad():
-            kcrop2, score, k2d2 = self._run_pair_head(self._engine_at(src.device, H, W), src, to_image, H, W, shift, swap)
-        return kcrop2[0], score, (None if k2d2 is None else k2d2[0])
+        self._head_record()
+        return self._pair_flow(images, to_image, flip_pairs, False, shift=shift)
 
     def forward_detect_flip_test(self, images, to_image, shift=True, flip_pairs=None):
         """The reference's flip-test evaluation (train.py:170-181) without detections from outside: ONE backbone pass over the 2B engine
@@ -718,38 +771,13 @@ class CA_PF(nn.Module):
         flip_pairs).  Returns (joints3d [B,1,J,3], kcrop_px [B,J,2], score [B,J]); kcrop_px stays in crop pixels.  The result equals
         forward_flip_test on the stack with detect_flip_test's keypoints pushed through preprocess_points(mode=2), bit for bit.  Always runs
         without grad and returns detached tensors.  keypoint_head="cpn": NotImplementedError."""
-        from capf.lib import fliptest_fuse
         self._no_cpn_flip_test()
-        self._head_params()
+        self._head_record()
         if to_image is None:
             raise ValueError("forward_detect_flip_test needs to_image [B, 2, 3]: the lifter takes the keypoints in normalised image coordinates too")
-        swap = self._swap_table(flip_pairs)
-        src, B, H, W, to_image = self._flip_test_source(images, to_image)
-        J = self.num_joints
-        with torch.cuda.device(src.device), torch.no_grad():
-            eng = self._engine_at(src.device, H, W)
-            kcrop2, score, k2d2 = self._run_pair_head(eng, src, to_image, H, W, shift, swap)
-            ref = kcrop2.clone().view(2 * B, J, 2)               # (the lifter normalises its crop keypoints in place: the caller keeps the pixels)
-            pred = self._run_lifter(eng, _Source("workspace", src.device, 2 * B, "the maps", None), k2d2.view(2 * B, J, 2), ref, None)
-            out = fliptest_fuse(pred.view(2, B, 1, J, 3), swap)
-        return out, kcrop2[0], score
+        return self._pair_flow(images, to_image, flip_pairs, True, shift=shift)
 
     # ---- keypoint_head="cpn" under CPN's own test-time flip (cpn/test.py:44-70): fold of the two heatmaps, ONE two-peak decode ----
-    def _cpn_flip_entry(self, name):
-        if self.keypoint_head_mode != "cpn":
-            raise ValueError("{} is CPN's test-time flip: it needs CA_PF(..., keypoint_head='cpn'), not keypoint_head={!r} (HRNet's flip "
-                             "test: detect_flip_test / forward_detect_flip_test)".format(name, self.keypoint_head_mode))
-        self._cpn_head_frozen()
-
-    def _run_cpn_pair_head(self, eng, src, to_image, H, W, swap):
-        """One backbone pass over the pair (final_predict included) and capf_cpn_decode_pair on its "heat":
-        (kcrop2 [2,B,J,2], score [B,J], k2d2 [2,B,J,2] | None)."""
-        _run_backbone(self, eng, src, torch.cuda.current_stream(src.device).cuda_stream)
-        heat = eng.tensor_view("heat", src.batch)
-        sx, sy = float(W) / heat.shape[2], float(H) / heat.shape[1]
-        kcrop2, score, k2d2, _, _ = cpn_decode_pair(heat, self.num_joints, swap, (sx, 0.5 * sx, sy, 0.5 * sy), to_image, float(2 * CROP_HALF[0]))
-        return kcrop2, score, k2d2
-
     def detect_cpn_flip(self, images, to_image=None, flip_pairs=None):
         """detect() under CPN's own test-time flip (cpn/test.py:44-70, upstream's default and the procedure behind keypoints_2d_cpn): ONE
         backbone pass over the crops and their mirrors, then capf_cpn_decode_pair -- per joint the heatmap of the crop and the heatmap of
@@ -761,11 +789,7 @@ class CA_PF(nn.Module):
         score [B,J], k2d [B,J,2] | None).  Always runs without grad and returns detached tensors: the decode has no backward (a
         final_predict parameter that requires grad raises under grad)."""
         self._cpn_flip_entry("detect_cpn_flip")
-        swap = self._swap_table(flip_pairs)
-        src, B, H, W, to_image = self._flip_test_source(images, to_image)
-        with torch.cuda.device(src.device), torch.no_grad():
-            kcrop2, score, k2d2 = self._run_cpn_pair_head(self._engine_at(src.device, H, W), src, to_image, H, W, swap)
-        return kcrop2[0], score, (None if k2d2 is None else k2d2[0])
+        return self._pair_flow(images, to_image, flip_pairs, False)
 
     def forward_detect_cpn_flip(self, images, to_image, flip_pairs=None):
         """The reference's flip-test evaluation (train.py:170-181) on a CPN backbone without detections from outside, from crop to
@@ -775,20 +799,10 @@ class CA_PF(nn.Module):
         kcrop_px [B,J,2], score [B,J]); kcrop_px stays in crop pixels.  The result equals forward_flip_test on the stack with
         detect_cpn_flip's keypoints pushed through preprocess_points(mode=2), bit for bit.  Always runs without grad and returns detached
         tensors."""
-        from capf.lib import fliptest_fuse
         self._cpn_flip_entry("forward_detect_cpn_flip")
         if to_image is None:
             raise ValueError("forward_detect_cpn_flip needs to_image [B, 2, 3]: the lifter takes the keypoints in normalised image coordinates too")
-        swap = self._swap_table(flip_pairs)
-        src, B, H, W, to_image = self._flip_test_source(images, to_image)
-        J = self.num_joints
-        with torch.cuda.device(src.device), torch.no_grad():
-            eng = self._engine_at(src.device, H, W)
-            kcrop2, score, k2d2 = self._run_cpn_pair_head(eng, src, to_image, H, W, swap)
-            ref = kcrop2.clone().view(2 * B, J, 2)               # (the lifter normalises its crop keypoints in place: the caller keeps the pixels)
-            pred = self._run_lifter(eng, _Source("workspace", src.device, 2 * B, "the maps", None), k2d2.view(2 * B, J, 2), ref, None)
-            out = fliptest_fuse(pred.view(2, B, 1, J, 3), swap)
-        return out, kcrop2[0], score
+        return self._pair_flow(images, to_image, flip_pairs, True)
 
     # ---- conpose.py:40 on maps of the caller's own backbone ------------------------------------
     def _feature_geometry(self, H, W):
@@ -871,7 +885,6 @@ class CA_PF(nn.Module):
         """Flip-test evaluation (train.py:170-181) as ONE forward: inputs are the [2,B,...] stacks that
         capf_preprocess(mode=2) emits (original, mirrored); the two predictions are un-mirrored and averaged
         by capf_fliptest_fuse.  Returns [B,1,17,3].  The crop keypoints are normalised in place."""
-        from capf.lib import fliptest_fuse
         two, B = images2.shape[0], images2.shape[1]
         assert two == 2 and images2.is_contiguous() and keypoints_2d_cpn_crop2.is_contiguous()
         pred = self.forward(images2.view(2 * B, *images2.shape[2:]), keypoints_2d_cpn2.reshape(2 * B, 17, 2),

@@ -11,6 +11,7 @@ beyond what a row of the table says about tensors of the caller's."""
 import pytest
 import torch
 
+import test_gpu_cpn_flip as cpn
 from capf import synth
 from capf.lib import Engine
 from feature_cases import synth_maps
@@ -264,3 +265,70 @@ def test_forward_features_sets_the_map_gradient_mode_once(head_model, log):
         m.map_grad_mode = None
         eng.set_map_grad_mode(0)
         m.zero_grad(set_to_none=True)
+
+
+# ---- the flip entries: one backbone pass over the 2B engine frames, whatever the image form ----------------------------------------------------
+def _pair_forms(images, crops):
+    """(image form, the backbone entry it reaches): float crops, the [2,B,H,W,3] stack of preprocess(mode=2), uint8 crops"""
+    return ((images, "backbone_forward"), (torch.stack([images, torch.flip(images, [2])]), "backbone_forward"), (crops, "backbone_forward_u8"))
+
+
+def test_detect_flip_test(head_model, log):
+    m = head_model
+    images, A, _ = _inputs(B, H, W)
+    crops, _, _ = _inputs(B, H, W, u8=True)
+    for form, backbone in _pair_forms(images, crops):
+        calls, (kcrop, score, k2d) = _plain(log, lambda: m.detect_flip_test(form, A))
+        assert calls == [backbone] and kcrop.shape == (B, J, 2) and score.shape == (B, J) and k2d.shape == (B, J, 2)
+
+
+def test_forward_detect_flip_test(head_model, log):
+    m = head_model
+    images, A, _ = _inputs(B, H, W)
+    crops, _, _ = _inputs(B, H, W, u8=True)
+    for form, backbone in _pair_forms(images, crops):
+        calls, (out, kcrop, _) = _plain(log, lambda: m.forward_detect_flip_test(form, A))
+        assert calls == [backbone, "lifter_forward"] and out.shape == (B, 1, J, 3) and kcrop.shape == (B, J, 2)
+
+
+# ---- keypoint_head="cpn": bf16, 256x192 (the smallest crop the CPN module tests use), one source crop ---------------------------------------
+CPN_H, CPN_W = 256, 192
+
+
+@pytest.fixture(scope="module")
+def cpn_model():
+    """keypoint_head="cpn", warmed up: its 256x192 engine exists and is bound"""
+    m = cpn._model("bf16")
+    images, A = cpn._inputs(1, CPN_H, CPN_W)
+    m.detect(images, A)
+    yield m
+    cpn._release(m)
+
+
+def _cpn_inputs(u8=False):
+    return cpn._inputs(1, CPN_H, CPN_W, u8=u8)
+
+
+def test_cpn_detect_and_forward_detect(cpn_model, log):
+    m = cpn_model
+    images, A = _cpn_inputs()
+    assert _plain(log, lambda: m.detect(images, A))[0] == ["backbone_forward"]
+    calls, (out, kcrop, score) = _plain(log, lambda: m.forward_detect(images, A))
+    assert calls == ["backbone_forward", "lifter_forward"] and out.shape == (1, 1, J, 3) and kcrop.shape == (1, J, 2) and score.shape == (1, J)
+    assert any(p.requires_grad for p in m.volume_net.parameters())          # the lifter trains: the native step, the head outside the graph
+    m.zero_grad(set_to_none=True)
+    fwd, bwd, _ = _step(log, lambda: m.forward_detect(images, A))
+    assert (fwd, bwd) == (["backbone_forward", "lifter_forward_train"], ["backward"])
+    assert all(p.grad is not None for p in m.volume_net.parameters())
+    m.zero_grad(set_to_none=True)
+
+
+@pytest.mark.parametrize("u8", [False, True], ids=["float", "u8"])
+def test_cpn_flip_entries(cpn_model, log, u8):
+    m = cpn_model
+    images, A = _cpn_inputs(u8)
+    backbone = "backbone_forward_u8" if u8 else "backbone_forward"
+    calls, (kcrop, score, k2d) = _plain(log, lambda: m.detect_cpn_flip(images, A))
+    assert calls == [backbone] and kcrop.shape == (1, J, 2) and score.shape == (1, J) and k2d.shape == (1, J, 2)
+    calls, (out, kcrop, _) = _plain(log, lambda: m.forward_detect_cpn_flip(images, A))
+    assert calls == [backbone, "lifter_forward"] and out.shape == (1, 1, J, 3) and kcrop.shape == (1, J, 2)
