@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI in include/capf.h.  PyTorch is used for device memory and streams
 only (tensor.data_ptr(), torch.cuda.current_stream()); no torch type crosses the ABI."""
 import ctypes
+import math
 import os
 from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
@@ -13,40 +14,6 @@ PLAN_BF16_F32_STREAM = 32768     # (1 << 14 stays unassigned)
 PLAN_BN_BATCH_STATS = 65536      # opt-in: the handle also carries the batch-statistics backbone route (capf_backbone_forward_bn)
 PLAN_CPN_PREDICT = 131072        # opt-in, CPN50 (fp32 / bf16): the backbone also runs refine_net.final_predict into the named tensor "heat"
 ABI_VERSION = 12       # include/capf.h :: CAPF_ABI_VERSION (checked against capf_abi_version() at load)
-
-EXPORTS = [  # every symbol include/capf.h declares (checked by tests/test_abi.py)
-    "capf_create", "capf_destroy", "capf_last_error", "capf_version", "capf_num_params", "capf_param_info",
-    "capf_set_param", "capf_params_changed", "capf_lifter_params_changed", "capf_workspace_bytes", "capf_set_workspace", "capf_forward",
-    "capf_backbone_forward", "capf_lifter_forward", "capf_set_debug", "capf_set_lanes", "capf_op_conv_group", "capf_affine_from_center_scale", "capf_warp_affine", "capf_op_schedule", "capf_forward_profile_launches", "capf_forward_profile_variants", "capf_tensor", "capf_forward_stats",
-    "capf_num_ops", "capf_op_info", "capf_forward_profile", "capf_op_pack_conv", "capf_op_conv", "capf_op_linear",
-    "capf_preprocess", "capf_fliptest_fuse", "capf_op_pack_conv_bf16", "capf_op_conv_bf16", "capf_op_conv_bf16_rh_width", "capf_op_pack_conv_bf16_rh", "capf_op_conv_bf16_rh", "capf_op_conv_bf16_group", "capf_forward_train", "capf_backward", "capf_grad_elems", "capf_grad_info", "capf_train_h2_matrices", "capf_mpjpe", "capf_adamw_step",
-    "capf_pose_errors", "capf_segment_sums", "capf_keypoints_loss", "capf_train_generation", "capf_max_batch", "capf_op_bytes", "capf_op_linear_bf16", "capf_op_pack_conv_wino", "capf_op_conv_wino", "capf_op_conv_wino_group",
-    "capf_op_bilinear_corners", "capf_mpjpe_nd", "capf_op_executed_flops",
-    "capf_forward_prefix", "capf_op_describe", "capf_op_tensor",
-    "capf_op_conv_bf16_ws_pack_elems", "capf_op_pack_conv_bf16_ws", "capf_op_conv_bf16_ws_group",
-    "capf_op_conv_f32x3_pack_elems", "capf_op_pack_conv_f32x3", "capf_op_conv_f32x3_group",
-    "capf_op_conv_f32h2_pack_elems", "capf_op_pack_conv_f32h2", "capf_op_conv_f32h2_group",
-    "capf_abi_version", "capf_op_describe_sized",
-    "capf_jpeg_info", "capf_jpeg_coefficients", "capf_jpeg_decode",
-    "capf_jpeg_batch_info", "capf_jpeg_decode_batch", "capf_jpeg_coefficients_subseq",
-    "capf_jpeg_crop_rect", "capf_jpeg_crop_batch_info", "capf_jpeg_decode_crop_batch",
-    "capf_op_f32h2_gemm_pack_elems", "capf_op_pack_f32h2_gemm", "capf_op_conv_f32h2g", "capf_op_conv_f32h2g_group", "capf_op_linear_f32h2g", "capf_op_linear_ln_f32h2g", "capf_op_wgrad", "capf_op_conv_f32h2_tiles", "capf_op_conv_f32h2_planes", "capf_op_h2_planes",
-    "capf_fliptest_fuse_swap", "capf_pck_counts",
-    "capf_optim_ctrl_bytes", "capf_optim_ctrl_init", "capf_grad_sumsq", "capf_adamw_step_guarded",
-    "capf_op_pack_conv_16", "capf_op_conv_16", "capf_op_conv_16_group", "capf_op_conv_16_ws_group", "capf_op_linear_16", "capf_op_bneck_16",
-    "capf_debug_f16_round",
-    "capf_op_stream_class",
-    "capf_set_features", "capf_lifter_forward_train", "capf_backward_maps",
-    "capf_set_map_grad_mode", "capf_map_grad_mode",
-    "capf_forward_u8", "capf_backbone_forward_u8", "capf_forward_train_u8", "capf_preprocess_points", "capf_input_rule_host",
-    "capf_op_conv_u8", "capf_op_conv_u8_kernel_name", "capf_op_conv_stem_kernel_name",
-    "capf_backbone_forward_bn", "capf_op_bn_stats_scratch_bytes", "capf_op_bn_stats", "capf_op_bn_apply",
-    "capf_backward_points",
-    "capf_kp_head_scratch_bytes", "capf_kp_head_forward", "capf_kp_head_backward",
-    "capf_kp_head_pair_scratch_bytes", "capf_kp_head_forward_pair",
-    "capf_cpn_decode", "capf_cpn_decode_taps", "capf_cpn_decode_lds_bytes",
-    "capf_cpn_decode_pair",
-]
 
 
 class CapfError(RuntimeError):
@@ -106,6 +73,154 @@ class OptimSegment(ctypes.Structure):
 
 OPTIM_MAX_SEGMENTS = 64       # include/capf.h :: CAPF_OPTIM_MAX_SEGMENTS
 
+# ---- the C ABI, declared once: one row per function of include/capf.h, in the header's order, name -> (restype, argtypes).  load_library()
+# applies the rows; tests/test_abi.py holds every row, the struct mirrors above and the constants to the header.
+# A pointer whose pointee is a scalar or a mirrored struct that the HOST reads or writes is POINTER(T); a device pointer, a stream, a void*
+# and an opaque handle are c_void_p, and so is the address of a numpy buffer (the JPEG coefficient and matrix arguments).
+I, I64, Z, F, S = c_int, c_int64, c_size_t, c_float, c_char_p
+H = P = c_void_p                                # the handle; a device pointer / stream / void*
+pP, pS = POINTER(c_void_p), POINTER(c_char_p)
+pI32, pI64, pZ, pF, pD = POINTER(c_int32), POINTER(c_int64), POINTER(c_size_t), POINTER(c_float), POINTER(c_double)
+D = POINTER(ConvDesc)
+FOLD = [P, P, P, P, P, P, F, P, P]              # the head of every fold-and-pack entry: stream, w, gamma, beta, mean, var, eps, w_packed, bias
+RUN = [H, P, P, P, P, I, P]                     # capf_forward's arguments: handle, stream, images, k2d, kcrop_inout, batch, out
+
+PROTOTYPES = {
+    "capf_create": (I, [POINTER(CapfConfig), I, POINTER(H)]),
+    "capf_destroy": (None, [H]),
+    "capf_max_batch": (I, [H]),
+    "capf_last_error": (S, [H]),
+    "capf_version": (S, []),
+    "capf_abi_version": (I, []),
+    "capf_num_params": (I, [H]),
+    "capf_param_info": (I, [H, I, pS, pI64, pI32, pI32]),
+    "capf_set_param": (I, [H, S, P, pI64, I]),
+    "capf_params_changed": (I, [H, P]),
+    "capf_lifter_params_changed": (I, [H, P]),
+    "capf_workspace_bytes": (Z, [H, I]),
+    "capf_set_workspace": (I, [H, P, Z]),
+    "capf_forward": (I, RUN),
+    "capf_backbone_forward": (I, [H, P, P, I]),
+    "capf_backbone_forward_bn": (I, [H, P, P, I, F]),
+    "capf_forward_train": (I, RUN + [P]),
+    "capf_backward": (I, [H, P, P, I, P, P]),
+    "capf_train_generation": (I64, [H]),
+    "capf_grad_elems": (I64, [H]),
+    "capf_grad_info": (I, [H, I, pI64]),
+    "capf_train_h2_matrices": (I, [H]),
+    "capf_mpjpe": (I, [P, P, P, I, P, P, F]),
+    "capf_mpjpe_nd": (I, [P, P, P, I, I, P, P, F]),
+    "capf_adamw_step": (I, [P, P, P, P, P, I64, F, F, F, F, F, I, F]),
+    "capf_optim_ctrl_bytes": (Z, []),
+    "capf_optim_ctrl_init": (I, [P, P, I64]),
+    "capf_grad_sumsq": (I, [P, P, I64, F, P]),
+    "capf_adamw_step_guarded": (I, [P, P, P, P, P, I64, POINTER(OptimSegment), I, F, F, F, F, F, I64, P, I, P]),
+    "capf_lifter_forward": (I, [H, P, P, P, I, P]),
+    "capf_set_features": (I, [H, P, pP, I]),
+    "capf_lifter_forward_train": (I, [H, P, P, P, I, P, P]),
+    "capf_backward_maps": (I, [H, P, P, I, P, P, pP]),
+    "capf_set_map_grad_mode": (I, [H, I]),
+    "capf_map_grad_mode": (I, [H]),
+    "capf_backward_points": (I, [H, P, P, I, P, P, pP, P, P]),
+    "capf_set_lanes": (I, [H, I]),
+    "capf_set_debug": (I, [H, I]),
+    "capf_tensor": (I, [H, S, pP, pI64, pI32]),
+    "capf_forward_profile_variants": (I, [H, pI32, I]),
+    "capf_forward_stats": (I, [H, I, pI64, pD]),
+    "capf_op_pack_conv": (I, FOLD + [I, I, I]),
+    "capf_op_conv": (I, [P] * 6 + [I] * 8),
+    "capf_op_conv_group": (I, [P, I, D]),
+    "capf_op_pack_conv_wino": (I, FOLD + [I, I, I]),
+    "capf_op_conv_wino": (I, [P] * 6 + [I] * 7),
+    "capf_op_conv_wino_group": (I, [P, I, D, I]),
+    "capf_op_linear": (I, [P] * 6 + [I] * 4),
+    "capf_op_bn_stats_scratch_bytes": (Z, [I64, I]),
+    "capf_op_bn_stats": (I, [P, P, I64, I, P, P, F, F, P, P, P, P, P, Z]),
+    "capf_op_bn_apply": (I, [P] * 6 + [I64, I, I]),
+    "capf_op_bilinear_corners": (I, [P, P, I, I, I, I, P, P]),
+    "capf_op_pack_conv_bf16": (I, FOLD + [I, I, I]),
+    "capf_op_conv_bf16": (I, [P] * 6 + [I] * 8),
+    "capf_op_conv_bf16_rh_width": (I, [I]),
+    "capf_op_pack_conv_bf16_rh": (I, FOLD + [I, I]),
+    "capf_op_conv_bf16_rh": (I, [P] * 6 + [I] * 6),
+    "capf_op_conv_bf16_ws_pack_elems": (I64, [I, I]),
+    "capf_op_pack_conv_bf16_ws": (I, FOLD + [I, I]),
+    "capf_op_conv_bf16_ws_group": (I, [P, I, D]),
+    "capf_op_conv_f32x3_pack_elems": (I64, [I, I]),
+    "capf_op_pack_conv_f32x3": (I, FOLD + [I, I]),
+    "capf_op_conv_f32x3_group": (I, [P, I, D]),
+    "capf_op_conv_f32h2_pack_elems": (I64, [I, I]),
+    "capf_op_pack_conv_f32h2": (I, FOLD + [I, I]),
+    "capf_op_conv_f32h2_group": (I, [P, I, D]),
+    "capf_op_conv_f32h2_tiles": (I, [I, I, I, pI32]),
+    "capf_op_conv_f32h2_planes": (I, [P, D, P, P]),
+    "capf_op_f32h2_gemm_pack_elems": (I64, [I, I]),
+    "capf_op_pack_f32h2_gemm": (I, FOLD + [I, I, I, I]),
+    "capf_op_conv_f32h2g": (I, [P] * 6 + [I] * 8),
+    "capf_op_conv_f32h2g_group": (I, [P, I, D]),
+    "capf_op_linear_f32h2g": (I, [P] * 6 + [I] * 4),
+    "capf_op_wgrad": (I, [P, P, P, I, I, I, P, I]),
+    "capf_op_linear_ln_f32h2g": (I, [P, P, P, P, F, P, P, P, P] + [I] * 4),
+    "capf_op_conv_bf16_group": (I, [P, I, D, pP, pI32]),
+    "capf_op_linear_bf16": (I, [P] * 6 + [I] * 4),
+    "capf_op_pack_conv_16": (I, FOLD + [I] * 5),
+    "capf_op_conv_16": (I, [P] * 6 + [I] * 9),
+    "capf_op_conv_16_group": (I, [P, I, D, pP, pI32, I]),
+    "capf_op_conv_16_ws_group": (I, [P, I, D, I]),
+    "capf_op_linear_16": (I, [P] * 6 + [I] * 5),
+    "capf_op_bneck_16": (I, [P, P, pP, pP, P, P, P, P] + [I] * 5),
+    "capf_debug_f16_round": (I, [P, P, I]),
+    "capf_preprocess": (I, [P, P, I, I, I, pF, pF, I] + [P] * 7),
+    "capf_fliptest_fuse": (I, [P, P, I, P]),
+    "capf_forward_u8": (I, [H, P, P, pF, pF, I, P, P, I, P]),
+    "capf_backbone_forward_u8": (I, [H, P, P, pF, pF, I, I]),
+    "capf_forward_train_u8": (I, [H, P, P, pF, pF, I, P, P, I, P, P]),
+    "capf_preprocess_points": (I, [P, I, I] + [P] * 6),
+    "capf_input_rule_host": (I, [P, I, I, pF, pF, P]),
+    "capf_op_conv_u8": (I, [P] * 5 + [I] * 8 + [pF, pF, I]),
+    "capf_op_conv_u8_kernel_name": (S, [I] * 8),
+    "capf_op_conv_stem_kernel_name": (S, [I] * 7),
+    "capf_fliptest_fuse_swap": (I, [P, P, I, I, pI32, P]),
+    "capf_pose_errors": (I, [P, P, P, I, I, P, P]),
+    "capf_segment_sums": (I, [P, P, P, P, I, I, P, P]),
+    "capf_keypoints_loss": (I, [P, I, P, P, P, I, I, F, P, P]),
+    "capf_kp_head_scratch_bytes": (Z, [I] * 6),
+    "capf_kp_head_forward": (I, [P, P, I, P, P] + [I] * 6 + [F, pF, P, P, P, P, P, P, Z]),
+    "capf_kp_head_backward": (I, [P, P, P, P, I, P, P] + [I] * 6 + [F, pF, P, P, P, P, I, P, Z]),
+    "capf_kp_head_pair_scratch_bytes": (Z, [I] * 5),
+    "capf_kp_head_forward_pair": (I, [P, P, I, P, P] + [I] * 6 + [F, pI32, I, pF, P, F, P, P, P, P, P, Z]),
+    "capf_cpn_decode_taps": (None, [pD]),
+    "capf_cpn_decode_lds_bytes": (Z, [I, I]),
+    "capf_cpn_decode": (I, [P, P] + [I] * 6 + [pF, P, P, P, P, P]),
+    "capf_cpn_decode_pair": (I, [P, P] + [I] * 6 + [pI32, pF, P, F, P, P, P, P, P]),
+    "capf_pck_counts": (I, [P, P, P, I, I, I, c_double, P, I, P, P, P]),
+    "capf_jpeg_info": (I, [S, Z, pI32, pI32, pI32, pI32, pI32, pZ]),
+    "capf_jpeg_coefficients": (I, [S, Z, P, Z]),
+    "capf_jpeg_decode": (I, [P, S, Z, P, Z, P, Z]),
+    "capf_jpeg_batch_info": (I, [I, P, pZ, I, pI32, pZ]),
+    "capf_jpeg_decode_batch": (I, [P, I, P, pZ, P, pZ, P, P, Z, P, I]),
+    "capf_jpeg_coefficients_subseq": (I, [S, Z, P, Z, I]),
+    "capf_jpeg_crop_rect": (I, [I, I, I, I, pD, I, I, pI32, pI32]),
+    "capf_jpeg_crop_batch_info": (I, [I, P, pZ, P, I, I, I, pI32, pZ]),
+    "capf_jpeg_decode_crop_batch": (I, [P, I, P, pZ, P, I, I, P, P, Z, P, I]),
+    "capf_affine_from_center_scale": (I, [pD, pD, I, I, pD]),
+    "capf_warp_affine": (I, [P, P, P, P, I, I, I, P]),
+    "capf_num_ops": (I, [H]),
+    "capf_op_info": (I, [H, I, I, pS, pS, pD]),
+    "capf_op_executed_flops": (I, [H, I, I, pD]),
+    "capf_op_bytes": (I, [H, I, I, pD]),
+    "capf_op_schedule": (I, [H, I, pI32, pI32, pI32, pI32, pI32]),
+    "capf_op_stream_class": (I, [H, I, I]),
+    "capf_forward_prefix": (I, RUN + [I]),
+    "capf_op_describe": (I, [H, I, POINTER(OpDesc)]),
+    "capf_op_describe_sized": (I, [H, I, P, Z]),
+    "capf_op_tensor": (I, [H, I, I, pP]),
+    "capf_op_h2_planes": (I, [H, I, I, pP, pI32]),
+    "capf_forward_profile": (I, RUN + [pF, I]),
+    "capf_forward_profile_launches": (I, RUN + [pF, pI32, I]),
+}
+EXPORTS = list(PROTOTYPES)    # every symbol include/capf.h declares
+
 _lib = None
 
 
@@ -123,150 +238,13 @@ def load_library():
     lib = ctypes.CDLL(LIB_PATH)
     # structs cross this boundary (CapfConfig, ConvDesc, OpDesc): a library built from another revision of capf.h must not be driven
     # with this file's layouts
-    abi = lib.capf_abi_version() if hasattr(lib, "capf_abi_version") else None
+    abi = lib.capf_abi_version()
     if abi != ABI_VERSION:
         raise CapfError(f"{LIB_PATH} implements ABI revision {abi}, this binding expects {ABI_VERSION}: rebuild the library")
-    H = c_void_p
-    lib.capf_create.argtypes = [POINTER(CapfConfig), c_int, POINTER(H)]
-    lib.capf_create.restype = c_int
-    lib.capf_destroy.argtypes = [H]
-    lib.capf_destroy.restype = None
-    lib.capf_last_error.argtypes = [H]
-    lib.capf_last_error.restype = c_char_p
-    lib.capf_version.restype = c_char_p
-    lib.capf_num_params.argtypes = [H]
-    lib.capf_param_info.argtypes = [H, c_int, POINTER(c_char_p), POINTER(c_int64), POINTER(c_int), POINTER(c_int)]
-    lib.capf_set_param.argtypes = [H, c_char_p, c_void_p, POINTER(c_int64), c_int]
-    lib.capf_params_changed.argtypes = [H, c_void_p]
-    lib.capf_lifter_params_changed.argtypes = [H, c_void_p]
-    lib.capf_workspace_bytes.argtypes = [H, c_int]
-    lib.capf_workspace_bytes.restype = c_size_t
-    lib.capf_set_workspace.argtypes = [H, c_void_p, c_size_t]
-    lib.capf_forward.argtypes = [H, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
-    lib.capf_backbone_forward.argtypes = [H, c_void_p, c_void_p, c_int]
-    lib.capf_backbone_forward_bn.argtypes = [H, c_void_p, c_void_p, c_int, c_float]
-    lib.capf_op_bn_stats_scratch_bytes.argtypes = [c_int64, c_int]
-    lib.capf_op_bn_stats_scratch_bytes.restype = c_size_t
-    lib.capf_op_bn_stats.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_float, c_float] + [c_void_p] * 5 + [c_size_t]
-    lib.capf_op_bn_apply.argtypes = [c_void_p] * 6 + [c_int64, c_int, c_int]
-    lib.capf_lifter_forward.argtypes = [H, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
-    lib.capf_set_debug.argtypes = [H, c_int]
-    lib.capf_set_lanes.argtypes = [H, c_int]
-    lib.capf_tensor.argtypes = [H, c_char_p, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int)]
-    lib.capf_forward_stats.argtypes = [H, c_int, POINTER(c_int64), POINTER(c_double)]
-    lib.capf_forward_profile_variants.argtypes = [H, POINTER(c_int32), c_int]
-    lib.capf_num_ops.argtypes = [H]
-    lib.capf_op_info.argtypes = [H, c_int, c_int, POINTER(c_char_p), POINTER(c_char_p), POINTER(c_double)]
-    lib.capf_op_bytes.argtypes = [H, c_int, c_int, POINTER(c_double)]
-    lib.capf_op_executed_flops.argtypes = [H, c_int, c_int, POINTER(c_double)]
-    lib.capf_forward_prefix.argtypes = [H, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int]
-    lib.capf_op_describe.argtypes = [H, c_int, POINTER(OpDesc)]
-    lib.capf_op_describe_sized.argtypes = [H, c_int, c_void_p, c_size_t]
-    lib.capf_op_tensor.argtypes = [H, c_int, c_int, POINTER(c_void_p)]
-    lib.capf_forward_profile.argtypes = [H, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                                         POINTER(c_float), c_int]
-    lib.capf_forward_profile_launches.argtypes = [H, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                                                  POINTER(c_float), POINTER(c_int32), c_int]
-    P = c_void_p
-    lib.capf_forward_train.argtypes = [H, P, P, P, P, c_int, P, P]
-    lib.capf_backward.argtypes = [H, P, P, c_int, P, P]
-    lib.capf_set_features.argtypes = [H, P, POINTER(P), c_int]
-    lib.capf_lifter_forward_train.argtypes = [H, P, P, P, c_int, P, P]
-    lib.capf_backward_maps.argtypes = [H, P, P, c_int, P, P, POINTER(P)]
-    lib.capf_backward_points.argtypes = [H, P, P, c_int, P, P, POINTER(P), P, P]
-    lib.capf_set_map_grad_mode.argtypes = [H, c_int]
-    lib.capf_map_grad_mode.argtypes = [H]
-    lib.capf_map_grad_mode.restype = c_int
-    lib.capf_train_generation.argtypes = [H]
-    lib.capf_train_generation.restype = c_int64
-    lib.capf_max_batch.argtypes = [H]
-    lib.capf_grad_elems.argtypes = [H]
-    lib.capf_grad_elems.restype = c_int64
-    lib.capf_grad_info.argtypes = [H, c_int, POINTER(c_int64)]
-    lib.capf_train_h2_matrices.argtypes = [H]
-    lib.capf_train_h2_matrices.restype = c_int
-    lib.capf_mpjpe.argtypes = [P, P, P, c_int, P, P, c_float]
-    lib.capf_mpjpe_nd.argtypes = [P, P, P, c_int, c_int, P, P, c_float]
-    lib.capf_adamw_step.argtypes = [P, P, P, P, P, c_int64] + [c_float] * 5 + [c_int, c_float]
-    lib.capf_optim_ctrl_bytes.argtypes = []
-    lib.capf_optim_ctrl_bytes.restype = c_size_t
-    lib.capf_optim_ctrl_init.argtypes = [P, P, c_int64]
-    lib.capf_grad_sumsq.argtypes = [P, P, c_int64, c_float, P]
-    lib.capf_adamw_step_guarded.argtypes = [P, P, P, P, P, c_int64, POINTER(OptimSegment), c_int] + [c_float] * 5 + [c_int64, P, c_int, P]
-    lib.capf_op_bilinear_corners.argtypes = [P, P, c_int, c_int, c_int, c_int, P, P]
-    lib.capf_op_pack_conv.argtypes = [P, P, P, P, P, P, c_float, P, P, c_int, c_int, c_int]
-    lib.capf_op_conv.argtypes = [P, P, P, P, P, P] + [c_int] * 8
-    lib.capf_op_linear.argtypes = [P, P, P, P, P, P] + [c_int] * 4
-    lib.capf_preprocess.argtypes = [P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_int, P, P, P, P, P, P, P]
-    lib.capf_fliptest_fuse.argtypes = [P, P, c_int, P]
-    lib.capf_op_pack_conv_bf16.argtypes = [P, P, P, P, P, P, c_float, P, P, c_int, c_int, c_int]
-    lib.capf_op_conv_bf16.argtypes = [P, P, P, P, P, P] + [c_int] * 8
-    lib.capf_op_conv_bf16_rh_width.argtypes = [c_int]
-    lib.capf_op_pack_conv_bf16_rh.argtypes = [P, P, P, P, P, P, c_float, P, P, c_int, c_int]
-    lib.capf_op_conv_bf16_rh.argtypes = [P, P, P, P, P, P] + [c_int] * 6
-    lib.capf_op_conv_bf16_ws_pack_elems.argtypes = [c_int, c_int]
-    lib.capf_op_conv_bf16_ws_pack_elems.restype = c_int64
-    lib.capf_op_pack_conv_bf16_ws.argtypes = [P, P, P, P, P, P, c_float, P, P, c_int, c_int]
-    lib.capf_op_conv_f32x3_pack_elems.argtypes = [c_int, c_int]
-    lib.capf_op_conv_f32x3_pack_elems.restype = c_int64
-    lib.capf_op_pack_conv_f32x3.argtypes = [P, P, P, P, P, P, c_float, P, P, c_int, c_int]
-    lib.capf_op_conv_f32h2_pack_elems.argtypes = [c_int, c_int]
-    lib.capf_op_conv_f32h2_pack_elems.restype = c_int64
-    lib.capf_op_pack_conv_f32h2.argtypes = [P, P, P, P, P, P, c_float, P, P, c_int, c_int]
-    lib.capf_op_f32h2_gemm_pack_elems.argtypes = [c_int, c_int]
-    lib.capf_op_f32h2_gemm_pack_elems.restype = c_int64
-    lib.capf_op_pack_f32h2_gemm.argtypes = [P, P, P, P, P, P, c_float, P, P, c_int, c_int, c_int, c_int]
-    lib.capf_op_conv_f32h2g.argtypes = [P, P, P, P, P, P] + [c_int] * 8
-    lib.capf_op_linear_f32h2g.argtypes = [P, P, P, P, P, P] + [c_int] * 4
-    lib.capf_op_linear_ln_f32h2g.argtypes = [P, P, P, P, c_float, P, P, P, P] + [c_int] * 4
-    lib.capf_op_wgrad.argtypes = [P, P, P, c_int, c_int, c_int, P, c_int]
-    lib.capf_op_pack_conv_wino.argtypes = [P, P, P, P, P, P, c_float, P, P, c_int, c_int, c_int]
-    lib.capf_op_conv_wino.argtypes = [P, P, P, P, P, P] + [c_int] * 7
-    lib.capf_op_linear_bf16.argtypes = [P, P, P, P, P, P] + [c_int] * 4
-    D = POINTER(ConvDesc)
-    for name in ("capf_op_conv_group", "capf_op_conv_bf16_ws_group", "capf_op_conv_f32x3_group", "capf_op_conv_f32h2_group",
-                 "capf_op_conv_f32h2g_group"):
-        getattr(lib, name).argtypes = [P, c_int, D]
-    lib.capf_op_conv_wino_group.argtypes = [P, c_int, D, c_int]
-    lib.capf_op_conv_bf16_group.argtypes = [P, c_int, D, POINTER(c_void_p), POINTER(c_int32)]
-    lib.capf_op_pack_conv_16.argtypes = [P, P, P, P, P, P, c_float, P, P] + [c_int] * 5
-    lib.capf_op_conv_16.argtypes = [P, P, P, P, P, P] + [c_int] * 9
-    lib.capf_op_conv_16_group.argtypes = [P, c_int, D, POINTER(c_void_p), POINTER(c_int32), c_int]
-    lib.capf_op_conv_16_ws_group.argtypes = [P, c_int, D, c_int]
-    lib.capf_op_linear_16.argtypes = [P, P, P, P, P, P] + [c_int] * 5
-    lib.capf_op_bneck_16.argtypes = [P, P, POINTER(c_void_p), POINTER(c_void_p), P, P, P, P] + [c_int] * 5
-    lib.capf_debug_f16_round.argtypes = [P, P, c_int]
-    lib.capf_op_conv_f32h2_planes.argtypes = [P, D, P, P]
-    lib.capf_op_conv_f32h2_tiles.argtypes = [c_int, c_int, c_int, POINTER(c_int)]
-    lib.capf_pose_errors.argtypes = [P, P, P, c_int, c_int, P, P]
-    lib.capf_segment_sums.argtypes = [P, P, P, P, c_int, c_int, P, P]
-    lib.capf_keypoints_loss.argtypes = [P, c_int, P, P, P, c_int, c_int, c_float, P, P]
-    lib.capf_fliptest_fuse_swap.argtypes = [P, P, c_int, c_int, POINTER(c_int32), P]
-    lib.capf_pck_counts.argtypes = [P, P, P, c_int, c_int, c_int, c_double, P, c_int, P, P, P]
-    F3 = POINTER(c_float)
-    lib.capf_forward_u8.argtypes = [H, P, P, F3, F3, c_int, P, P, c_int, P]
-    lib.capf_backbone_forward_u8.argtypes = [H, P, P, F3, F3, c_int, c_int]
-    lib.capf_forward_train_u8.argtypes = [H, P, P, F3, F3, c_int, P, P, c_int, P, P]
-    lib.capf_preprocess_points.argtypes = [P, c_int, c_int, P, P, P, P, P, P]
-    lib.capf_input_rule_host.argtypes = [P, c_int, c_int, F3, F3, P]
-    lib.capf_op_conv_u8.argtypes = [P, P, P, P, P] + [c_int] * 8 + [F3, F3, c_int]
-    lib.capf_op_conv_u8_kernel_name.argtypes = [c_int] * 8
-    lib.capf_op_conv_u8_kernel_name.restype = c_char_p
-    lib.capf_op_conv_stem_kernel_name.argtypes = [c_int] * 7
-    lib.capf_op_conv_stem_kernel_name.restype = c_char_p
-    lib.capf_kp_head_scratch_bytes.argtypes = [c_int] * 6
-    lib.capf_kp_head_scratch_bytes.restype = c_size_t
-    lib.capf_kp_head_forward.argtypes = [P, P, c_int, P, P] + [c_int] * 6 + [c_float, F3, P, P, P, P, P, P, c_size_t]
-    lib.capf_kp_head_backward.argtypes = [P, P, P, P, c_int, P, P] + [c_int] * 6 + [c_float, F3, P, P, P, P, c_int, P, c_size_t]
-    lib.capf_kp_head_pair_scratch_bytes.argtypes = [c_int] * 5
-    lib.capf_kp_head_pair_scratch_bytes.restype = c_size_t
-    lib.capf_kp_head_forward_pair.argtypes = [P, P, c_int, P, P] + [c_int] * 6 + [c_float, POINTER(c_int32), c_int, F3, P, c_float, P, P, P, P, P, c_size_t]
-    lib.capf_cpn_decode.argtypes = [P, P] + [c_int] * 6 + [F3, P, P, P, P, P]
-    lib.capf_cpn_decode_pair.argtypes = [P, P] + [c_int] * 6 + [POINTER(c_int32), F3, P, c_float, P, P, P, P, P]
-    lib.capf_cpn_decode_taps.argtypes = [POINTER(c_double)]
-    lib.capf_cpn_decode_taps.restype = None
-    lib.capf_cpn_decode_lds_bytes.argtypes = [c_int, c_int]
-    lib.capf_cpn_decode_lds_bytes.restype = c_size_t
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
     _lib = lib
     return lib
 
@@ -482,22 +460,22 @@ class Engine:
     def set_debug(self, on):
         self._check(self.lib.capf_set_debug(self.h, int(on)), "set_debug")
 
+    def _ws_view(self, ptr, n, code):
+        """The n elements at device address `ptr` inside the workspace as a flat view (no copy) of the dtype that `code` names (capf_tensor's
+        convention: 0 fp32, 1 int32, 2 bf16, 3 fp16)."""
+        import torch
+        off = (ptr - self._ws.data_ptr()) // 4
+        if code in (2, 3):  # bf16 / fp16 tensor: two elements per float slot
+            return self._ws[off:off + (n + 1) // 2].view(_TORCH16[code]())[:n]
+        flat = self._ws[off:off + n]
+        return flat.view(torch.int32) if code == 1 else flat
+
     def tensor(self, name):
         """Copy of a named intermediate of the last forward (torch tensor on the device)."""
-        import torch
         ptr, shape, nd = c_void_p(), (c_int64 * 4)(), c_int()
         rc = self._check(self.lib.capf_tensor(self.h, name.encode(), byref(ptr), shape, byref(nd)), f"tensor({name})")
         shp = [shape[i] for i in range(nd.value)]
-        n = 1
-        for s in shp:
-            n *= s
-        off = (ptr.value - self._ws.data_ptr()) // 4
-        if rc in (2, 3):  # bf16 / fp16 tensor: two elements per float slot
-            return self._ws[off:off + (n + 1) // 2].view(_TORCH16[rc]())[:n].view(*shp).clone()
-        flat = self._ws[off:off + n]
-        if rc == 1:
-            flat = flat.view(torch.int32)
-        return flat.view(*shp).clone()
+        return self._ws_view(ptr.value, math.prod(shp), rc).view(*shp).clone()
 
     def tensor_view(self, name, batch):
         """A named intermediate of the last forward of `batch` frames as a VIEW into the workspace (no copy; fp32 / bf16 / fp16 names only):
@@ -509,13 +487,7 @@ class Engine:
         shp = [shape[i] for i in range(nd.value)]
         if shp[0] != batch:
             raise CapfError(f"tensor_view({name}): the workspace holds {shp[0]} frames, not {batch}")
-        n = 1
-        for s in shp:
-            n *= s
-        off = (ptr.value - self._ws.data_ptr()) // 4
-        if rc in (2, 3):
-            return self._ws[off:off + (n + 1) // 2].view(_TORCH16[rc]())[:n].view(*shp)
-        return self._ws[off:off + n].view(*shp)
+        return self._ws_view(ptr.value, math.prod(shp), rc).view(*shp)
 
     def op_table(self, batch):
         """[(op name, kernel name, algorithmic flops at `batch`)] in launch order."""
@@ -556,34 +528,24 @@ class Engine:
     def op_tensor(self, index, slot, shape, dtype_code):
         """View (no copy) of one operand of op `index` after a forward_prefix: slot 0..3 inputs, 4 residual, 5 output, 6 the output's bf16
         shadow (PLAN_BF16_F32_STREAM); shape = full [B, ...] shape, dtype_code 0 fp32 / 2 bf16 / 3 fp16."""
-        import torch
         ptr = c_void_p()
         self._check(self.lib.capf_op_tensor(self.h, index, slot, byref(ptr)), f"op_tensor({index}, {slot})")
-        n = 1
-        for v in shape:
-            n *= v
         img = getattr(self, "_prefix_images", None)
         if img is not None and ptr.value == img.data_ptr():
             return img.view(*shape)
-        off = (ptr.value - self._ws.data_ptr()) // 4
-        if dtype_code in (2, 3):
-            return self._ws[off:off + (n + 1) // 2].view(_TORCH16[dtype_code]())[:n].view(*shape)
-        return self._ws[off:off + n].view(*shape)
+        return self._ws_view(ptr.value, math.prod(shape), dtype_code).view(*shape)
 
     def op_h2_planes(self, index, batch):
         """(role, exps [tiles, C / 16] int32 view, tile_pixels) of op `index` at this batch: role 0 = plain fp32 tensors, 1 = its output holds split
         fp16 planes, 2 = its input does (capf_op_h2_planes); C = the planes tensor's channels."""
-        import torch
         ptr, tp = c_void_p(), c_int(0)
-        self.lib.capf_op_h2_planes.argtypes = [c_void_p, c_int, c_int, POINTER(c_void_p), POINTER(c_int)]
         role = self.lib.capf_op_h2_planes(self.h, index, batch, byref(ptr), byref(tp))
         if role <= 0:
             return 0, None, 0
         d = self.op_describe(index)
         C = d.Cout if role == 1 else d.Cin
         tiles = self.lib.capf_op_conv_f32h2_tiles(batch, d.H, d.W, None)
-        off = (ptr.value - self._ws.data_ptr()) // 4
-        return role, self._ws[off:off + tiles * (C // 16)].view(torch.int32).view(tiles, C // 16), tp.value
+        return role, self._ws_view(ptr.value, tiles * (C // 16), 1).view(tiles, C // 16), tp.value
 
     def op_tensor_fp32(self, index, slot, shape, dtype_code):
         """op_tensor, with a planes tensor (a BasicBlock's conv1 -> conv2 operand where both run the two-fp16-piece tile) decoded to the fp32 values
@@ -605,8 +567,6 @@ class Engine:
 
     def op_schedule(self):
         """[(region, level, lane, reads, writes)] per op: see capf_op_schedule."""
-        self.lib.capf_op_schedule.argtypes = [c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
-                                              POINTER(c_int32), POINTER(c_int32)]
         out = []
         for i in range(self.lib.capf_num_ops(self.h)):
             rg, lv, ln = c_int32(), c_int32(), c_int32()
@@ -628,7 +588,6 @@ class Engine:
     def op_stream_classes(self, batch):
         """Per op at `batch` under the current set_lanes mode: 0 the caller's stream, 1 a side lane's stream (mode 1) or the side chain's
         (mode 3, batch 16..128): see capf_op_stream_class."""
-        self.lib.capf_op_stream_class.argtypes = [c_void_p, c_int, c_int]
         return [self._check(self.lib.capf_op_stream_class(self.h, i, batch), "op_stream_class") for i in range(self.lib.capf_num_ops(self.h))]
 
     def profile_variants(self):
@@ -1361,7 +1320,6 @@ def affine_from_center_scale(center, scale, output_size):
     """get_affine_transform(center, scale, 0, output_size) -> 2x3 float64 numpy matrix (host code, no GPU)."""
     import numpy as np
     lib = load_library()
-    lib.capf_affine_from_center_scale.argtypes = [POINTER(c_double), POINTER(c_double), c_int, c_int, POINTER(c_double)]
     c = (c_double * 2)(float(center[0]), float(center[1]))
     sc = (c_double * 2)(float(scale[0]), float(scale[1]))
     m = (c_double * 6)()
@@ -1390,7 +1348,6 @@ def warp_affine(frames, mats, output_size):
     import numpy as np
     import torch
     lib = load_library()
-    lib.capf_warp_affine.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
     dev = frames[0].device
     B = len(frames)
     for f in frames:
@@ -1411,7 +1368,6 @@ def jpeg_info(data):
     """data: bytes of a JPEG file -> dict(width, height, components, h_samp, v_samp, scratch_bytes); CapfError for what capf_jpeg_decode does
     not take (progressive, arithmetic, CMYK, ...).  Host code, no GPU."""
     lib = load_library()
-    lib.capf_jpeg_info.argtypes = [c_char_p, c_size_t] + [POINTER(c_int32)] * 5 + [POINTER(c_size_t)]
     w, h, nc, hs, vs, sb = c_int32(), c_int32(), c_int32(), c_int32(), c_int32(), c_size_t()
     rc = lib.capf_jpeg_info(data, len(data), byref(w), byref(h), byref(nc), byref(hs), byref(vs), byref(sb))
     if rc:
@@ -1425,7 +1381,6 @@ def jpeg_coefficients(data):
     import numpy as np
     lib = load_library()
     info = jpeg_info(data)
-    lib.capf_jpeg_coefficients.argtypes = [c_char_p, c_size_t, c_void_p, c_size_t]
     hs, vs, nc = info["h_samp"], info["v_samp"], info["components"]
     mx, my = -(-info["width"] // (8 * hs)), -(-info["height"] // (8 * vs))
     shapes = [(my * vs, mx * hs)] + [(my, mx)] * (nc - 1)
@@ -1447,7 +1402,6 @@ def jpeg_decode(data, device="cuda"):
     import torch
     lib = load_library()
     info = jpeg_info(data)
-    lib.capf_jpeg_decode.argtypes = [c_void_p, c_char_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
     out = torch.empty(info["height"], info["width"], 3, dtype=torch.uint8, device=device)
     scratch = torch.empty(info["scratch_bytes"], dtype=torch.uint8, device=device)
     rc = lib.capf_jpeg_decode(_stream(out), data, len(data), _p(out), out.stride(0), _p(scratch), scratch.numel())
@@ -1475,7 +1429,6 @@ def jpeg_coefficients_subseq(data, subseq_bytes=0):
     import numpy as np
     lib = load_library()
     info = jpeg_info(data)
-    lib.capf_jpeg_coefficients_subseq.argtypes = [c_char_p, c_size_t, c_void_p, c_size_t, c_int]
     shapes = _coef_shapes(info["width"], info["height"], info["components"], info["h_samp"], info["v_samp"])
     total = sum(a * b * 64 for a, b in shapes)
     buf = np.zeros(total, np.int16)
@@ -1499,7 +1452,6 @@ def jpeg_batch_info(datas, subseq_bytes=0):
     lib = load_library()
     datas, ptrs, sizes = _byte_arrays(datas)
     n = len(datas)
-    lib.capf_jpeg_batch_info.argtypes = [c_int, c_void_p, c_void_p, c_int, c_void_p, POINTER(c_size_t)]
     info = (c_int32 * (5 * max(n, 1)))()
     sb = c_size_t()
     rc = lib.capf_jpeg_batch_info(n, ptrs, sizes, int(subseq_bytes), info, byref(sb))
@@ -1526,7 +1478,6 @@ def jpeg_decode_batch(datas, device="cuda", subseq_bytes=0, coefficients=False):
     coef = torch.empty(sum(r["coef_elems"] for r in rows), dtype=torch.int16, device=device) if coefficients else None
     out_ptrs = (c_void_p * n)(*[o.data_ptr() for o in outs])
     pitches = (c_size_t * n)(*[o.stride(0) for o in outs])
-    lib.capf_jpeg_decode_batch.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int]
     rc = lib.capf_jpeg_decode_batch(_stream(status), n, ptrs, sizes, out_ptrs, pitches, _p(coef), _p(scratch), scratch_bytes, _p(status),
                                     int(subseq_bytes))
     if rc:
@@ -1549,7 +1500,6 @@ def jpeg_crop_rect(width, height, h_samp, v_samp, mat, output_size):
     when the crop lies wholly outside the image.  Host code, no GPU."""
     import numpy as np
     lib = load_library()
-    lib.capf_jpeg_crop_rect.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_double), c_int, c_int, POINTER(c_int32), POINTER(c_int32)]
     m = (c_double * 6)(*np.asarray(mat, dtype=np.float64).reshape(6).tolist())
     px, mc = (c_int32 * 4)(), (c_int32 * 4)()
     rc = lib.capf_jpeg_crop_rect(int(width), int(height), int(h_samp), int(v_samp), m, int(output_size[0]), int(output_size[1]), px, mc)
@@ -1559,7 +1509,6 @@ def jpeg_crop_rect(width, height, h_samp, v_samp, mat, output_size):
 
 
 def _crop_batch_info(lib, n, ptrs, sizes, m, out_w, out_h, subseq_bytes):
-    lib.capf_jpeg_crop_batch_info.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_size_t)]
     info = (c_int32 * (13 * max(n, 1)))()
     sb = c_size_t()
     rc = lib.capf_jpeg_crop_batch_info(n, ptrs, sizes, m.ctypes.data_as(c_void_p), out_w, out_h, int(subseq_bytes), info, byref(sb))
@@ -1603,7 +1552,6 @@ def jpeg_decode_crop_batch(datas, mats, output_size, device="cuda", subseq_bytes
     out = torch.empty(n, out_h, out_w, 3, dtype=torch.uint8, device=device)
     status = torch.empty(n, dtype=torch.int32, device=device)
     scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
-    lib.capf_jpeg_decode_crop_batch.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_int]
     rc = lib.capf_jpeg_decode_crop_batch(_stream(out), n, ptrs, sizes, m.ctypes.data_as(c_void_p), out_h, out_w, _p(out), _p(scratch), scratch_bytes,
                                          _p(status), int(subseq_bytes))
     if rc:

@@ -2,6 +2,7 @@
 schema / host module state_dict equal the reference's state_dict (captured in tests/golden/schema_*.json
 by oracle/make_goldens.py).  No compute calls — there is no GPU here."""
 import copy
+import ctypes
 import json
 import os
 import re
@@ -557,3 +558,202 @@ def test_two_piece_table_of_a_training_plan_follows_the_restated_rule_at_every_w
             assert eng.lib.capf_train_h2_matrices(eng.h) == len(want), (dtype, embed)
             assert (len(want) == 0) == (dtype == "bf16")
             eng.close()
+
+
+# ---- the binding's prototype table, struct mirrors and constants against include/capf.h ------------------------------------------------
+def parse_header(text):
+    """include/capf.h -> (functions {name: (return type, [parameter type])} in declaration order,
+                          structs {name: [(field, type, array extents)]},
+                          constants {name: value} of every CAPF_* enumerator and #define).
+    A type is (base type without const, pointer depth); an array parameter counts as a pointer to its element."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    consts = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(CAPF_\w+)[ \t]+(-?\w+)[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#[^\n]*$", ";", text, flags=re.M)          # a directive ends a statement: it cannot run into the next declaration
+    text = re.sub(r'extern\s+"C"\s*\{', ";", text)
+
+    def typ(decl):
+        """'const float* const feat[4]' -> ('feat', ('float', 1), [4])"""
+        extents = [int(v) for v in re.findall(r"\[(\d+)\]", decl)]
+        words = re.sub(r"\[\d+\]", " ", decl).replace("*", " * ").split()
+        depth = words.count("*")
+        words = [w for w in words if w not in ("*", "const", "struct")]
+        return words[-1], (" ".join(words[:-1]), depth), extents
+
+    depth, stmt, stmts = 0, "", []
+    for ch in text:                                                   # statements: split at the semicolons outside braces
+        if ch == "}" and depth == 0:
+            continue                                                  # (the brace that closes extern "C")
+        depth += (ch == "{") - (ch == "}")
+        if ch == ";" and depth == 0:
+            stmts.append(" ".join(stmt.split()))
+            stmt = ""
+        else:
+            stmt += ch
+    funcs, structs = {}, {}
+    for s in stmts:
+        m = re.fullmatch(r"enum \w+ \{(.*)\}", s)
+        if m:
+            nxt = 0
+            for item in filter(None, (v.strip() for v in m.group(1).split(","))):
+                name, _, val = (v.strip() for v in item.partition("="))
+                consts[name] = nxt = int(val, 0) if val else nxt
+                nxt += 1
+            continue
+        m = re.fullmatch(r"typedef struct (capf_\w+) \{(.*)\} \1", s)
+        if m:
+            fields = structs[m.group(1)] = []
+            for decl in filter(None, (v.strip() for v in m.group(2).split(";"))):
+                first, *more = (v.strip() for v in decl.split(","))
+                fields.append(typ(first))
+                fields += [typ(fields[-1][1][0] + " " + v) for v in more]        # "int32_t height, width": one base type, several names
+            continue
+        m = re.fullmatch(r"(.*?)\b(capf_\w+) ?\((.*)\)", s)
+        if m and not s.startswith("typedef"):
+            params = [] if m.group(3).strip() == "void" else [typ(p) for p in m.group(3).split(",")]
+            funcs[m.group(2)] = (typ(m.group(1) + " _")[1], [(base, d + len(ext)) for _, (base, d), ext in params])
+    return funcs, structs, consts
+
+
+_HEADER = []
+
+
+def _header():
+    if not _HEADER:
+        _HEADER.append(parse_header(open(os.path.join(ROOT, "include", "capf.h")).read()))
+    return _HEADER[0]
+
+
+def _mirrors():
+    """{header struct name: ctypes.Structure of capf.lib}: CapfConfig -> capf_config, OpDesc -> capf_op_desc, ..."""
+    from capf import lib as capf_lib
+    snake = lambda n: "capf_" + re.sub(r"(?<!^)([A-Z])", r"_\1", n[4:] if n.startswith("Capf") else n).lower()
+    return {snake(n): c for n, c in vars(capf_lib).items()
+            if isinstance(c, type) and issubclass(c, ctypes.Structure) and c.__module__ == capf_lib.__name__}
+
+
+def _scalar(base):
+    return {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double, "int16_t": ctypes.c_int16, "uint16_t": ctypes.c_uint16, "uint8_t": ctypes.c_uint8}.get(base)
+
+
+def _type_fault(bound, base, depth, mirrors):
+    """None when the ctypes type `bound` may stand for the header type (base, depth), else what is wrong with it"""
+    if depth == 0:
+        want = None if base == "void" else _scalar(base)
+        return None if bound is want else f"{base} bound as {getattr(bound, '__name__', bound)}"
+    if bound is ctypes.c_void_p:                                       # a device pointer, a void*, an opaque handle; any address
+        return None
+    if bound is ctypes.c_char_p:                                       # a string or bytes
+        return None if depth == 1 and base in ("char", "uint8_t") else f"{base}{'*' * depth} bound as c_char_p"
+    if isinstance(bound, type) and issubclass(bound, ctypes._Pointer):
+        pointee = bound._type_
+        if depth > 1:
+            return _type_fault(pointee, base, depth - 1, mirrors)
+        if pointee is (mirrors.get(base) or _scalar(base)):
+            return None
+        return f"{base}* bound as POINTER({pointee.__name__})"
+    return f"{base}{'*' * depth} bound as {getattr(bound, '__name__', bound)}, which is no pointer"
+
+
+def prototype_faults(table, funcs, mirrors):
+    """[(function, what is wrong)] of a prototype table against the header's functions: return type, argument count, kind per position,
+    pointee of every POINTER(T)"""
+    faults = [(n, "not in the header") for n in table if n not in funcs]
+    for name, (ret, params) in funcs.items():
+        if name not in table:
+            faults.append((name, "no row"))
+            continue
+        (restype, argtypes) = table[name]
+        bad = _type_fault(restype, *ret, mirrors)
+        if ret == ("char", 1) and restype is not ctypes.c_char_p:      # a string result is read, not passed on: c_void_p will not do
+            bad = f"char* returned as {getattr(restype, '__name__', restype)}"
+        if bad:
+            faults.append((name, "result: " + bad))
+        if len(argtypes) != len(params):
+            faults.append((name, f"{len(params)} parameters, {len(argtypes)} argtypes"))
+            continue
+        faults += [(name, f"argument {i}: {bad}") for i, (t, p) in enumerate(zip(argtypes, params)) for bad in [_type_fault(t, *p, mirrors)] if bad]
+    return faults
+
+
+def test_prototype_table_follows_the_header():
+    from capf.lib import EXPORTS, PROTOTYPES
+    funcs, _, _ = _header()
+    assert len(funcs) > 100
+    assert list(PROTOTYPES) == list(funcs) == EXPORTS                  # one row per declaration, in the header's order
+    assert all(isinstance(a, list) for _, a in PROTOTYPES.values())
+    assert prototype_faults(PROTOTYPES, funcs, _mirrors()) == []
+
+
+def _mutate(name, index, new):
+    """the binding's table with argument `index` of one row replaced ("last": dropped; "result": its restype replaced)"""
+    from capf.lib import PROTOTYPES
+    table = dict(PROTOTYPES)
+    (restype, argtypes) = table[name]
+    if index == "result":
+        table[name] = (new, argtypes)
+    elif index == "last":
+        table[name] = (restype, argtypes[:-1])
+    else:
+        table[name] = (restype, argtypes[:index] + [new] + argtypes[index + 1:])
+    return table
+
+
+@pytest.mark.parametrize("name,index,new,header", [
+    ("capf_optim_ctrl_init", 2, "c_int", ("int64_t", 0)),              # an int64_t argument bound as c_int
+    ("capf_set_workspace", "last", None, ("size_t", 0)),               # a missing last argument
+    ("capf_workspace_bytes", "result", "c_int", ("size_t", 0)),        # a size_t result on c_int
+    ("capf_preprocess", 5, "pI32", ("float", 1)),                      # POINTER(c_int32) where the header has float*
+], ids=["int64-as-int", "missing-last-argument", "size_t-result-as-int", "float-pointer-as-int32-pointer"])
+def test_prototype_comparison_reports_a_planted_fault_and_nothing_else(name, index, new, header):
+    funcs, _, _ = _header()
+    ret, params = funcs[name]
+    assert (ret if index == "result" else params[-1 if index == "last" else index]) == header      # the row is what the case says it is
+    new = {"c_int": ctypes.c_int, "pI32": ctypes.POINTER(ctypes.c_int32), None: None}[new]
+    faults = prototype_faults(_mutate(name, index, new), funcs, _mirrors())
+    assert faults and {n for n, _ in faults} == {name}, faults
+
+
+def test_loaded_library_carries_exactly_the_table():
+    import capf
+    from capf.lib import PROTOTYPES
+    lib = capf.load_library()
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, name
+        assert fn.argtypes is not None and len(fn.argtypes) == len(argtypes) and all(a is b for a, b in zip(fn.argtypes, argtypes)), name
+
+
+def test_struct_mirrors_follow_the_header():
+    _, structs, _ = _header()
+    mirrors = _mirrors()
+    assert set(mirrors) == set(structs) and len(structs) == 5         # every header struct has a mirror and the reverse (capf_handle is opaque)
+
+    def ctype(base, depth, extents):
+        t = ctypes.c_void_p if depth else _scalar(base)
+        for n in reversed(extents):
+            t = t * n
+        return t
+
+    def same(a, b):
+        if isinstance(a, type) and issubclass(a, ctypes.Array):
+            return isinstance(b, type) and issubclass(b, ctypes.Array) and a._length_ == b._length_ and same(a._type_, b._type_)
+        return a is b
+
+    for name, fields in structs.items():
+        bound = mirrors[name]._fields_
+        assert [f[0] for f in bound] == [f[0] for f in fields], name
+        for (field, t), (_, (base, depth), extents) in zip(bound, fields):
+            assert same(t, ctype(base, depth, extents)), (name, field, t)
+
+
+def test_constants_follow_the_header():
+    from capf import lib as capf_lib
+    _, _, consts = _header()
+    named = {n: v for n, v in vars(capf_lib).items() if "CAPF_" + n in consts}
+    assert {"HRNET", "CPN50", "F32", "BF16", "F16", "ABI_VERSION", "OPTIM_MAX_SEGMENTS"} <= set(named)
+    assert {n for n in named if n.startswith("PLAN_")} == {n[5:] for n in consts if n.startswith("CAPF_PLAN_")}
+    for n, v in named.items():
+        assert v == consts["CAPF_" + n], n
+    assert capf_lib.PARAM_KINDS == {v: n[len("CAPF_P_"):].lower() for n, v in consts.items() if n.startswith("CAPF_P_")}

@@ -37,7 +37,6 @@ def _n_backbone(eng):
 
 def _sched(eng):
     """[(reads[5], writes[6])] per op, slots kept (capf_op_schedule: reads 0..3 inputs, 4 residual; writes 0 output)"""
-    eng.op_schedule()                                            # (sets the argtypes)
     out = []
     for i in range(eng.lib.capf_num_ops(eng.h)):
         rg, lv, ln = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()

@@ -127,7 +127,6 @@ def test_unsupported_files_and_bad_arguments_are_refused(frame420):
     buf = io.BytesIO()
     Image.fromarray(cc.make_image(32, 32, 1)).save(buf, "JPEG", quality=80, progressive=True)
     prog = buf.getvalue()
-    lib.capf_jpeg_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t] + [ctypes.c_void_p] * 6
     want = lib.capf_jpeg_info(prog, len(prog), None, None, None, None, None, None)
     assert want != 0
     eye = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
@@ -141,8 +140,6 @@ def test_unsupported_files_and_bad_arguments_are_refused(frame420):
     for n, out_w, out_h in ((0, 192, 256), (-1, 192, 256), (1, 0, 256), (1, 192, 0), (1, -192, 256), (1, 192, -1)):
         rc, _, _ = capf._crop_batch_info(lib, n, ptrs, sizes, m, out_w, out_h, 0)
         assert rc == INVALID, (n, out_w, out_h, rc)
-    lib.capf_jpeg_decode_crop_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                                ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]
     mp = m.ctypes.data_as(ctypes.c_void_p)
     for n, out_h, out_w in ((0, 256, 192), (-1, 256, 192), (1, 0, 192), (1, 256, 0)):                    # (checked before any pointer is used)
         assert lib.capf_jpeg_decode_crop_batch(None, n, ptrs, sizes, mp, out_h, out_w, 4096, 4096, 1 << 30, 4096, 0) == INVALID
