@@ -189,6 +189,8 @@ PROTOTYPES = {
     "capf_kp_head_backward": (I, [P, P, P, P, I, P, P] + [I] * 6 + [F, pF, P, P, P, P, I, P, Z]),
     "capf_kp_head_pair_scratch_bytes": (Z, [I] * 5),
     "capf_kp_head_forward_pair": (I, [P, P, I, P, P] + [I] * 6 + [F, pI32, I, pF, P, F, P, P, P, P, P, Z]),
+    "capf_kp_heatmap_loss_scratch_bytes": (Z, [I] * 6),
+    "capf_kp_heatmap_loss": (I, [P, P, I, P, P] + [I] * 5 + [P, P, pF, F, I, I, F, P, P, P, P, P, I, P, Z]),
     "capf_cpn_decode_taps": (None, [pD]),
     "capf_cpn_decode_lds_bytes": (Z, [I, I]),
     "capf_cpn_decode": (I, [P, P] + [I] * 6 + [pF, P, P, P, P, P]),
@@ -1107,6 +1109,50 @@ def kp_head_backward(x, weight, bias=None, dkcrop=None, dk2d=None, beta=1.0, dec
     _call("capf_kp_head_backward", _stream(x), _p(dkcrop), _p(dk2d), _p(x), dtype, _p(w), _p(bias), B, H, W, C, J, KP_INTEGRAL, float(beta),
           dec, _p(to_image), _p(dw), _p(db), _p(dmap), 1 if accumulate else 0, _p(scratch), nbytes)
     return dw, db, dmap
+
+
+KP_LOSS_MEAN, KP_LOSS_OHKM = 0, 1     # capf_kp_heatmap_loss's `reduction`
+KP_LOSS_REDUCTIONS = {"mean": KP_LOSS_MEAN, "ohkm": KP_LOSS_OHKM}
+
+
+def kp_heatmap_loss(x, weight, bias=None, kcrop_gt=None, target_weight=None, decode=(1.0, 0.0, 1.0, 0.0), sigma=2.0, reduction="mean", topk=8,
+                    scale=0.5, want_grads=True, want_dmap=False, dmap_accumulate_into=None):
+    """capf_kp_heatmap_loss on a contiguous NHWC map x [B, H, W, C] (fp32 / bf16 / fp16): the 1x1 conv weight [J, C] (+ bias [J]), the Gaussian
+    targets around kcrop_gt [B, J, 2] (crop pixels; decode = (sx, ox, sy, oy) maps heatmap to crop coordinates), the weighted mean-squared
+    error (reduction "mean" / "ohkm" with `topk`, or KP_LOSS_MEAN / KP_LOSS_OHKM) and its gradients in one native call.
+    Returns (loss [1], joint_loss [B, J], dweight [J, C] | None, dbias [J] | None, dmap | None).  dmap_accumulate_into given: the map gradient
+    is ADDED to it (capf_backward_points' dfeat_nhwc[0]); want_dmap without it: a fresh tensor, overwritten.  The map gradient needs an fp32 map."""
+    import torch
+    if isinstance(reduction, str):
+        if reduction not in KP_LOSS_REDUCTIONS:
+            raise ValueError(f"reduction must be 'mean' or 'ohkm', got {reduction!r}")
+        reduction = KP_LOSS_REDUCTIONS[reduction]
+    dtype = _kp_map_dtype(x)
+    B, H, W, C = x.shape
+    w, J = _kp_weight(weight, C)
+    f32, dev = torch.float32, x.device
+    if kcrop_gt is None or tuple(kcrop_gt.shape) != (B, J, 2) or kcrop_gt.dtype != f32 or not kcrop_gt.is_contiguous():
+        raise CapfError(f"kcrop_gt must be contiguous fp32 [{B}, {J}, 2], not {None if kcrop_gt is None else (tuple(kcrop_gt.shape), kcrop_gt.dtype)}")
+    if target_weight is not None:
+        target_weight = target_weight.reshape(B, J) if target_weight.numel() == B * J else target_weight
+        if tuple(target_weight.shape) != (B, J) or target_weight.dtype != f32 or not target_weight.is_contiguous():
+            raise CapfError(f"target_weight must be contiguous fp32 [{B}, {J}] (or [{B}, {J}, 1]), not {tuple(target_weight.shape)} {target_weight.dtype}")
+    dmap = dmap_accumulate_into
+    accumulate = dmap is not None
+    if accumulate and (dmap.shape != x.shape or dmap.dtype != f32 or not dmap.is_contiguous()):
+        raise CapfError(f"dmap_accumulate_into must be contiguous fp32 {tuple(x.shape)}, not {tuple(dmap.shape)} {dmap.dtype}")
+    if dmap is None and want_dmap:
+        dmap = torch.empty(B, H, W, C, dtype=f32, device=dev)
+    nbytes = load_library().capf_kp_heatmap_loss_scratch_bytes(B, H, W, C, J, int(reduction))
+    scratch = torch.empty(max(nbytes, 4) // 4, dtype=f32, device=dev)
+    loss = torch.empty(1, dtype=f32, device=dev)
+    joint_loss = torch.empty(B, J, dtype=f32, device=dev)
+    dw = torch.empty(J, C, dtype=f32, device=dev) if want_grads else None
+    db = torch.empty(J, dtype=f32, device=dev) if want_grads else None
+    _call("capf_kp_heatmap_loss", _stream(x), _p(x), dtype, _p(w), _p(bias), B, H, W, C, J, _p(kcrop_gt), _p(target_weight), _kp_decode(decode),
+          float(sigma), int(reduction), int(topk), float(scale), _p(loss), _p(joint_loss), _p(dw), _p(db), _p(dmap), 1 if accumulate else 0,
+          _p(scratch), nbytes)
+    return loss, joint_loss, dw, db, dmap
 
 
 def cpn_decode_taps():

@@ -1758,6 +1758,38 @@ int capf_kp_head_backward(void* stream, const float* dkcrop, const float* dk2d, 
     return capf::launch_kp_head_backward(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
+// heatmap supervision of the head: the scratch holds the block sums, (OHKM) g_bj, the frame sums and the dweight / dbias partials
+size_t capf_kp_heatmap_loss_scratch_bytes(int B, int H, int W, int C, int J, int reduction) {
+    const capf::KpLossGeom lg = capf::kp_loss_geom(B, H, W, C, J);
+    if (!lg.ok || (reduction != 0 && reduction != 1)) return 0;
+    return (lg.sq_elems + (reduction == 1 ? lg.item_elems : 0) + lg.frame_elems + lg.bw_elems) * sizeof(float);
+}
+
+int capf_kp_heatmap_loss(void* stream, const void* map_nhwc, int map_dtype, const float* weight, const float* bias, int B, int H, int W, int C,
+                         int J, const float* kcrop_gt, const float* target_weight, const float decode[4], float sigma, int reduction, int topk,
+                         float scale, float* loss, float* joint_loss, float* dweight, float* dbias, float* dmap, int accumulate, void* scratch,
+                         size_t scratch_bytes) {
+    if (!map_nhwc || !weight || !kcrop_gt || !decode || !loss || !scratch) return CAPF_ERR_INVALID;
+    if (B < 1 || H < 1 || W < 1 || J < 1 || J > capf::MAX_JOINTS || C < 4 || C % 4 != 0 || C > capf::KP_MAX_CHANNELS) return CAPF_ERR_INVALID;
+    if (!std::isfinite(decode[0]) || !std::isfinite(decode[2]) || decode[0] == 0.f || decode[2] == 0.f) return CAPF_ERR_INVALID;
+    if (!(sigma > 0.f) || !std::isfinite(sigma) || std::ceil(3.f * sigma) > (float)capf::KP_LOSS_MAX_RADIUS) return CAPF_ERR_INVALID;
+    if ((reduction != 0 && reduction != 1) || map_dtype < CAPF_F32 || map_dtype > CAPF_F16) return CAPF_ERR_INVALID;
+    if (topk < 1 || !std::isfinite(scale) || (accumulate != 0 && accumulate != 1)) return CAPF_ERR_INVALID;
+    if (dmap && map_dtype != CAPF_F32) return CAPF_ERR_UNSUPPORTED;
+    const size_t need = capf_kp_heatmap_loss_scratch_bytes(B, H, W, C, J, reduction);
+    if (need == 0) return CAPF_ERR_UNSUPPORTED;                                             // (more than 2^24 pixels a frame, a grid beyond 2^31)
+    if (scratch_bytes < need) return CAPF_ERR_INVALID;
+    if (!map_aligned(map_nhwc, map_dtype) || (reinterpret_cast<uintptr_t>(dmap) & 15) || (reinterpret_cast<uintptr_t>(scratch) & 3)) return CAPF_ERR_INVALID;
+    capf::KpLossArgs a{};
+    a.x = map_nhwc; a.dtype = map_dtype; a.wt = weight; a.bias = bias; a.gt = kcrop_gt; a.tw = target_weight;
+    a.B = B; a.H = H; a.W = W; a.C = C; a.J = J;
+    std::copy(decode, decode + 4, a.dec);
+    a.sigma = sigma; a.radius = (int)std::ceil(3.f * sigma); a.reduction = reduction; a.topk = topk; a.scale = scale;
+    a.loss = loss; a.joint_loss = joint_loss; a.dW = dweight; a.dbias = dbias; a.dmap = dmap; a.accumulate = accumulate;
+    a.scratch = static_cast<float*>(scratch);
+    return capf::launch_kp_heatmap_loss(a, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+}
+
 // ---- CPN's two-peak decode (cpn_decode.hip): every argument is judged here, before anything is launched ----
 void capf_cpn_decode_taps(double taps[21]) {
     if (taps) capf::cpn_decode_taps(taps);

@@ -792,6 +792,39 @@ struct KpPairArgs : KpHeadArgs {
     float mirror_w;          // kcrop2[1].x = (mirror_w - x) - 1
 };
 hipError_t launch_kp_head_forward_pair(KpPairArgs a, hipStream_t s);
+// heatmap supervision (capf_kp_heatmap_loss): the head's logits against analytic Gaussian targets, loss and parameter gradients in one entry
+constexpr int KP_LOSS_MAX_RADIUS = 64;
+struct KpLossGeom {                          // kp_loss_geom: floats of scratch, in this order; ok = false: a shape the kernels do not take
+    KpGeom g;
+    size_t sq_elems, item_elems, frame_elems, bw_elems;      // block sums of (z - t)^2 | g_bj (OHKM only) | frame sums | dW and dbias partials
+    bool ok;
+};
+KpLossGeom kp_loss_geom(int B, int H, int W, int C, int J);
+struct KpLossArgs {
+    const void* x;           // [B, H, W, C] NHWC, dtype 0 fp32 / 1 bf16 / 2 fp16 (capf_dtype)
+    int dtype;
+    const float* wt;         // [J, C]
+    const float* bias;       // [J] or NULL
+    const float* gt;         // [B, J, 2] crop pixels
+    const float* tw;         // [B, J] or NULL: 1
+    int B, H, W, C, J;
+    float dec[4];            // sx, ox, sy, oy
+    float sigma;
+    int radius;              // ceil(3 sigma)
+    int reduction, topk;     // 0 mean, 1 OHKM
+    float scale;
+    float* loss;             // [1]
+    float* joint_loss;       // [B, J] or NULL
+    float* dW;               // [J, C] or NULL
+    float* dbias;            // [J] or NULL
+    float* dmap;             // [B, H, W, C] or NULL (fp32 map)
+    int accumulate;
+    float* scratch;
+    // filled by the launcher
+    KpLossGeom lg;
+    float *sq_part, *gsel, *frame, *bw_part;
+};
+hipError_t launch_kp_heatmap_loss(KpLossArgs a, hipStream_t s);
 
 // ---- CPN's detector head (CAPF_PLAN_CPN_PREDICT) ---------------------------------------------------------------------------------------
 // elementwise.hip: out[p][i * row_bytes ..] = in[i][p][0 .. row_bytes) for the `pixels` NHWC pixels of n <= 4 maps of one channel count

@@ -24,6 +24,7 @@
 // recomputes the logits tile by tile, forms dz in LDS, writes dmap (every element by one thread) and adds per-block partials of dW = sum dz X
 // (pixels ascending inside a tile, tiles ascending inside a block); kp_dw_reduce_kernel sums the partials (part q of 16 takes blocks
 // q, q + 16, ... ascending, the parts ascending) and writes dbias = 0.
+// Heatmap supervision (capf_kp_heatmap_loss): the same logits against analytic Gaussian targets, loss and gradients -- the section at the end.
 #include <math.h>
 
 #include "kernels.h"
@@ -41,6 +42,7 @@ static constexpr int KP_RED_PARTS = 16;
 struct KpLdF32 {
     typedef float T;
     static __device__ __forceinline__ f32x4 ld4(const T* p) { return *reinterpret_cast<const f32x4*>(p); }
+    static __device__ __forceinline__ float ld1(const T* p) { return *p; }
 };
 template <class F>
 struct KpLd16 {
@@ -49,6 +51,7 @@ struct KpLd16 {
         const uint2 u = *reinterpret_cast<const uint2*>(p);
         return f32x4{F::lo(u.x), F::hi(u.x), F::lo(u.y), F::hi(u.y)};
     }
+    static __device__ __forceinline__ float ld1(const T* p) { return F::widen(*p); }
 };
 
 KpGeom kp_geom(int B, int H, int W, int C, int J) {
@@ -460,6 +463,245 @@ hipError_t launch_kp_head_backward(KpHeadArgs a, hipStream_t s) {
     hipLaunchKernelGGL(kp_bwd_kernel, dim3((unsigned)(a.B * a.g.nbw)), dim3(KP_THREADS), 0, s, a);
     const int JC = a.J * a.C;
     hipLaunchKernelGGL(kp_dw_reduce_kernel, dim3((unsigned)((JC + 15) / 16)), dim3(KP_THREADS), 0, s, a.bw_part, a.B * a.g.nbw, JC, a.J, a.dW, a.dbias);
+    return hipGetLastError();
+}
+
+// ---- heatmap supervision (capf_kp_heatmap_loss; include/capf.h has the rules) ----------------------------------------------------------
+// d = z - t per (pixel, joint) in the LDS tile, z being kp_logits' chain and t the analytic Gaussian target (a product of two entries of a
+// per-block fp64 table; the difference is formed in fp64 and rounded once); neither reaches memory.
+//   kp_loss_kernel<LOSS>   8 lanes per joint add d^2 (lane l: pixels l, l + 8, ... of each tile, tiles ascending; lanes ascending): one sum per
+//                          (block, joint), a block being a frame's eighth of the tiles (the backward's cut)
+//   kp_loss_items_kernel   one thread per (frame, joint): blocks ascending -> l_bj; the OHKM rank and g_bj; the frame's sum, joints ascending
+//   kp_loss_kernel<GRAD>   dz = g_bj d in registers -> dmap; per block partials of sum d X and sum d, scaled by g_bj per tile
+//   kp_loss_reduce_kernel  the partials (kp_dw_reduce_kernel's order) -> dweight, dbias; its last block the frames' sums -> loss
+// reduction 0 knows g_bj up front: <LOSS, GRAD> is one pass over the map.  OHKM: <LOSS>, items, <GRAD> (the logits recomputed).
+KpLossGeom kp_loss_geom(int B, int H, int W, int C, int J) {
+    KpLossGeom lg{};
+    lg.g = kp_geom(B, H, W, C, J);
+    if (!lg.g.ok) return lg;
+    lg.sq_elems = (size_t)B * lg.g.nbw * J;
+    lg.item_elems = (size_t)B * J;
+    lg.frame_elems = (size_t)B;
+    lg.bw_elems = (size_t)B * lg.g.nbw * ((size_t)J * C + J);
+    lg.ok = true;
+    return lg;
+}
+
+struct KpLossItem { int mux, muy; float w; };   // the target's centre and the effective weight of one (frame, joint)
+static constexpr int KP_LOSS_NOWHERE = -(1 << 25);   // a centre whose window holds no pixel (columns and rows are below 2^24)
+
+__device__ __forceinline__ KpLossItem kp_loss_item(const KpLossArgs& a, const size_t i) {
+    const float cx = __fdiv_rn(__fsub_rn(a.gt[i * 2], a.dec[1]), a.dec[0]);
+    const float cy = __fdiv_rn(__fsub_rn(a.gt[i * 2 + 1], a.dec[3]), a.dec[2]);
+    KpLossItem it{KP_LOSS_NOWHERE, KP_LOSS_NOWHERE, 0.f};
+    if (fabsf(cx) <= 1048576.f && fabsf(cy) <= 1048576.f) {         // (false for a NaN)
+        it.mux = (int)__fadd_rn(cx, 0.5f);
+        it.muy = (int)__fadd_rn(cy, 0.5f);
+        const int R = a.radius;
+        const bool outside = it.mux - R >= a.W || it.muy - R >= a.H || it.mux + R < 0 || it.muy + R < 0;
+        it.w = outside ? 0.f : a.tw ? a.tw[i] : 1.f;
+    }
+    return it;
+}
+__device__ __forceinline__ float kp_loss_norm(const KpLossArgs& a) { return __fmul_rn((float)a.B, (float)(a.reduction == 0 ? a.J : a.topk)); }
+// g_bj of a selected item: 2 scale w^2 / (H W norm)
+__device__ __forceinline__ float kp_loss_g(const KpLossArgs& a, const float w) {
+    return __fdiv_rn(__fmul_rn(__fmul_rn(__fmul_rn(2.f, a.scale), w), w), __fmul_rn((float)(a.H * a.W), kp_loss_norm(a)));
+}
+
+template <class L, bool LOSS, bool GRAD>
+__global__ void __launch_bounds__(KP_THREADS) kp_loss_kernel(const KpLossArgs a) {
+    __shared__ float zs[MAX_JOINTS * KP_ZS];
+    __shared__ int mu[MAX_JOINTS][2];
+    __shared__ float gj[MAX_JOINTS];
+    __shared__ double eg[KP_LOSS_MAX_RADIUS + 1];                   // exp(-k^2 / (2 sigma^2)), k = 0 .. R: the target is eg[|dx|] eg[|dy|]
+    const int tid = threadIdx.x;
+    const int nbw = a.lg.g.nbw, bw_tiles = a.lg.g.bw_tiles, ntiles = a.lg.g.ntiles;
+    const int b = (int)blockIdx.x / nbw, s = (int)blockIdx.x - b * nbw;
+    const int HW = a.H * a.W, J = a.J, C = a.C, R = a.radius;
+    const typename L::T* __restrict__ xb = static_cast<const typename L::T*>(a.x) + (size_t)b * HW * C;
+    if (tid <= R) eg[tid] = exp(-(double)(tid * tid) / (2.0 * (double)a.sigma * (double)a.sigma));
+    if (tid < J) {
+        const size_t i = (size_t)b * J + tid;
+        const KpLossItem it = kp_loss_item(a, i);
+        mu[tid][0] = it.mux; mu[tid][1] = it.muy;
+        gj[tid] = !GRAD ? 0.f : LOSS ? kp_loss_g(a, it.w) : a.gsel[i];
+    }
+    __syncthreads();
+    const int JC = J * C, nout = JC + J;
+    const bool wgrad = GRAD && (a.dW || a.dbias);
+    float* part = a.bw_part + (size_t)blockIdx.x * nout;
+    const int jl = tid >> 3, l = tid & 7;
+    float sq = 0.f;
+    const int t0 = s * bw_tiles;
+    const int t1 = t0 + bw_tiles < ntiles ? t0 + bw_tiles : ntiles;
+    for (int t = t0; t < t1; ++t) {
+        const int base = t * KP_THREADS, pix = base + tid;
+        const int n = HW - base < KP_THREADS ? HW - base : KP_THREADS;
+        if (pix < HW) {
+            float acc[MAX_JOINTS];
+            kp_logits<L>(xb + (size_t)pix * C, a.wt, a.bias, C, J, acc);
+            const int row = pix / a.W, col = pix - row * a.W;
+#pragma unroll
+            for (int j = 0; j < MAX_JOINTS; ++j) {
+                if (j < J) {
+                    const int dx = col - mu[j][0], dy = row - mu[j][1];
+                    // z - t in double, rounded once: its error is relative to |z - t|, not to t, also where the two nearly cancel
+                    float d = acc[j];
+                    if (dx >= -R && dx <= R && dy >= -R && dy <= R) d = (float)__fma_rn(-eg[abs(dx)], eg[abs(dy)], (double)acc[j]);
+                    zs[j * KP_ZS + tid] = d;
+                    acc[j] = gj[j] == 0.f ? 0.f : __fmul_rn(gj[j], d);      // (an item without weight: exact zeros, whatever its logits)
+                }
+            }
+            if (GRAD && a.dmap) {                                   // dmap[pixel, c] = sum_j dz[j] Wt[j, c], joints ascending
+                float* dp = a.dmap + ((size_t)b * HW + pix) * C;
+                for (int c = 0; c < C; c += 4) {
+                    f32x4 dv = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int j = 0; j < MAX_JOINTS; ++j) {
+                        if (j < J) {
+                            const float* __restrict__ w = a.wt + (size_t)j * C + c;
+                            dv[0] = fmaf(acc[j], w[0], dv[0]);
+                            dv[1] = fmaf(acc[j], w[1], dv[1]);
+                            dv[2] = fmaf(acc[j], w[2], dv[2]);
+                            dv[3] = fmaf(acc[j], w[3], dv[3]);
+                        }
+                    }
+                    f32x4* q = reinterpret_cast<f32x4*>(dp + c);
+                    *q = a.accumulate ? *q + dv : dv;
+                }
+            }
+        }
+        __syncthreads();
+        if (LOSS && jl < J) {
+            for (int p = l; p < n; p += 8) {
+                const float d = zs[jl * KP_ZS + p];
+                sq = fmaf(d, d, sq);
+            }
+        }
+        if (wgrad) {
+            for (int o = tid; o < nout; o += KP_THREADS) {          // o >= JC: the bias of joint o - JC, whose "X" is 1
+                const bool isb = o >= JC;
+                const int j = isb ? o - JC : o / C, c = isb ? 0 : o - j * C;
+                const typename L::T* __restrict__ xc = xb + (size_t)base * C + c;
+                const float* zj = zs + j * KP_ZS;
+                float sum = 0.f;
+                if (isb) {
+                    for (int p = 0; p < n; ++p) sum = __fadd_rn(sum, zj[p]);
+                } else {
+#pragma unroll 8
+                    for (int p = 0; p < n; ++p) sum = fmaf(zj[p], L::ld1(xc + (size_t)p * C), sum);
+                }
+                const float gs = gj[j] == 0.f ? 0.f : __fmul_rn(gj[j], sum);
+                part[o] = t == t0 ? gs : __fadd_rn(part[o], gs);
+            }
+        }
+        __syncthreads();
+    }
+    if (LOSS) {                                                     // the 8 lanes of a joint, ascending (every thread takes part in the shuffles)
+        float tot = __shfl(sq, 0, 8);
+        for (int q = 1; q < 8; ++q) tot = __fadd_rn(tot, __shfl(sq, q, 8));
+        if (l == 0 && jl < J) a.sq_part[(size_t)blockIdx.x * J + jl] = tot;
+    }
+}
+
+// 8 frames a block, 32 threads a frame: l_bj, the OHKM selection (rank = how many joints of the frame come before this one: a NaN first,
+// then the larger loss, then the smaller index), g_bj of the gradient pass, and the frame's sum over its selected joints, ascending
+__global__ void __launch_bounds__(KP_THREADS) kp_loss_items_kernel(const KpLossArgs a) {
+    __shared__ float lv[8][MAX_JOINTS];
+    __shared__ int sl[8][MAX_JOINTS];
+    const int fl = threadIdx.x >> 5, j = threadIdx.x & 31;
+    const long bl = (long)blockIdx.x * 8 + fl;
+    const int J = a.J, nbw = a.lg.g.nbw;
+    const bool live = bl < a.B && j < J;
+    const int b = (int)(bl < a.B ? bl : 0);
+    const size_t i = (size_t)b * J + j;
+    float lj = 0.f, w = 0.f;
+    if (live) {
+        w = kp_loss_item(a, i).w;
+        float sum = 0.f;
+        for (int s = 0; s < nbw; ++s) sum = __fadd_rn(sum, a.sq_part[((size_t)b * nbw + s) * J + j]);
+        lj = w == 0.f ? 0.f : __fmul_rn(__fmul_rn(__fmul_rn(a.scale, w), w), __fdiv_rn(sum, (float)(a.H * a.W)));
+        if (a.joint_loss) a.joint_loss[i] = lj;
+    }
+    lv[fl][j] = lj;
+    __syncthreads();
+    int sel = live;
+    if (live && a.reduction == 1) {
+        int rank = 0;
+        for (int jj = 0; jj < J; ++jj) {
+            const float o = lv[fl][jj];
+            const bool before = jj == j ? false : o != o ? (lj == lj || jj < j) : (lj == lj && (o > lj || (o == lj && jj < j)));
+            rank += before;
+        }
+        sel = rank < a.topk;
+        a.gsel[i] = sel ? kp_loss_g(a, w) : 0.f;
+    }
+    sl[fl][j] = sel;
+    __syncthreads();
+    if (live && j == 0) {
+        float fs = 0.f;
+        for (int jj = 0; jj < J; ++jj)
+            if (sl[fl][jj]) fs = __fadd_rn(fs, lv[fl][jj]);
+        a.frame[b] = fs;
+    }
+}
+
+// blocks 0 .. gridDim - 2: kp_dw_reduce_kernel's sum of the blocks' partials, outputs [0, JC) to dweight and [JC, JC + J) to dbias;
+// the last block: the frames' sums in the same two stages (part q of 16 takes frames q, q + 16, ... ascending, parts ascending) -> loss
+__global__ void __launch_bounds__(KP_THREADS) kp_loss_reduce_kernel(const KpLossArgs a, const int nparts, const int JC, const int nout) {
+    __shared__ float sh[KP_RED_PARTS][16];
+    const int lc = threadIdx.x & 15, q = threadIdx.x >> 4;
+    float s = 0.f;
+    if (blockIdx.x == gridDim.x - 1) {
+        if (lc == 0)
+            for (int p = q; p < a.B; p += KP_RED_PARTS) s = __fadd_rn(s, a.frame[p]);
+        sh[q][lc] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            s = 0.f;
+            for (int p = 0; p < KP_RED_PARTS; ++p) s = __fadd_rn(s, sh[p][0]);
+            a.loss[0] = __fdiv_rn(s, kp_loss_norm(a));
+        }
+        return;
+    }
+    const int o = (int)blockIdx.x * 16 + lc;
+    if (o < nout)
+        for (int p = q; p < nparts; p += KP_RED_PARTS) s = __fadd_rn(s, a.bw_part[(size_t)p * nout + o]);
+    sh[q][lc] = s;
+    __syncthreads();
+    if (q == 0 && o < nout) {
+        s = 0.f;
+        for (int p = 0; p < KP_RED_PARTS; ++p) s = __fadd_rn(s, sh[p][lc]);
+        if (o < JC) { if (a.dW) a.dW[o] = s; }
+        else if (a.dbias) a.dbias[o - JC] = s;
+    }
+}
+
+template <class L>
+static void kp_loss_launches(const KpLossArgs& a, hipStream_t s) {
+    const dim3 blk(KP_THREADS), g1((unsigned)(a.B * a.lg.g.nbw)), g2((unsigned)((a.B + 7) / 8));
+    const bool grads = a.dW || a.dbias || a.dmap;
+    if (grads && a.reduction == 0) hipLaunchKernelGGL((kp_loss_kernel<L, true, true>), g1, blk, 0, s, a);
+    else hipLaunchKernelGGL((kp_loss_kernel<L, true, false>), g1, blk, 0, s, a);
+    hipLaunchKernelGGL(kp_loss_items_kernel, g2, blk, 0, s, a);
+    if (grads && a.reduction == 1) hipLaunchKernelGGL((kp_loss_kernel<L, false, true>), g1, blk, 0, s, a);
+    const int JC = a.J * a.C, nout = a.dW || a.dbias ? JC + a.J : 0;
+    hipLaunchKernelGGL(kp_loss_reduce_kernel, dim3((unsigned)((nout + 15) / 16 + 1)), blk, 0, s, a, a.B * a.lg.g.nbw, JC, nout);
+}
+
+hipError_t launch_kp_heatmap_loss(KpLossArgs a, hipStream_t s) {
+    a.lg = kp_loss_geom(a.B, a.H, a.W, a.C, a.J);
+    if (!a.lg.ok || !a.x || !a.wt || !a.gt || !a.loss || !a.scratch || a.dtype < 0 || a.dtype > 2 || (a.reduction != 0 && a.reduction != 1) ||
+        a.topk < 1 || a.radius < 0 || a.radius > KP_LOSS_MAX_RADIUS || (a.dmap && a.dtype != 0))
+        return hipErrorInvalidValue;
+    a.sq_part = a.scratch;
+    a.gsel = a.sq_part + a.lg.sq_elems;
+    a.frame = a.gsel + (a.reduction == 1 ? a.lg.item_elems : 0);
+    a.bw_part = a.frame + a.lg.frame_elems;
+    if (a.dtype == 0) kp_loss_launches<KpLdF32>(a, s);
+    else if (a.dtype == 1) kp_loss_launches<KpLd16<Bf16Fmt>>(a, s);
+    else kp_loss_launches<KpLd16<F16Fmt>>(a, s);
     return hipGetLastError();
 }
 

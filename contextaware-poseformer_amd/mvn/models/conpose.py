@@ -14,8 +14,8 @@ import collections
 import torch
 from torch import nn
 
-from capf.lib import (KP_INTEGRAL, KP_MODES, PLAN_BN_BATCH_STATS, PLAN_CPN_PREDICT, CapfError, Engine, cpn_decode, cpn_decode_pair, fliptest_fuse,
-                      input_constants, kp_head_backward, kp_head_forward, kp_head_forward_pair)
+from capf.lib import (KP_INTEGRAL, KP_LOSS_REDUCTIONS, KP_MODES, PLAN_BN_BATCH_STATS, PLAN_CPN_PREDICT, CapfError, Engine, cpn_decode,
+                      cpn_decode_pair, fliptest_fuse, input_constants, kp_head_backward, kp_head_forward, kp_head_forward_pair, kp_heatmap_loss)
 
 from . import _native
 
@@ -202,6 +202,43 @@ def keypoint_head(map_nhwc, weight, bias=None, to_image=None, mode="integral", b
     kcrop, score, k2d = _KeypointHeadFn.apply(map_nhwc, weight, bias, to_image, KP_MODES[mode], float(beta),
                                               tuple(float(v) for v in decode), None)
     return kcrop, score, (k2d if to_image is not None else None)
+
+
+class _HeatmapLossFn(torch.autograd.Function):
+    """Autograd boundary of the native heatmap loss: forward = capf_kp_heatmap_loss on an NHWC map, which produces the gradients of the loss in
+    the same call; they are kept and backward multiplies them by grad_output.  Nothing is re-read later, so a map in an engine's workspace
+    needs no guard."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, kcrop_gt, target_weight, decode, sigma, reduction, topk, scale):
+        need_map = ctx.needs_input_grad[0]
+        if need_map and x.dtype != torch.float32:
+            raise NotImplementedError("the heatmap loss's map gradient needs an fp32 map (capf_kp_heatmap_loss), got {}".format(x.dtype))
+        need_params = ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])
+        loss, _, dw, db, dmap = kp_heatmap_loss(x.detach(), weight.detach(), None if bias is None else bias.detach(), kcrop_gt, target_weight,
+                                                decode, sigma, reduction, topk, scale, want_grads=need_params, want_dmap=need_map)
+        ctx.grads = (dmap, None if dw is None else dw.view(weight.shape), db if bias is not None else None)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return tuple(g * grad_out if g is not None and need else None for g, need in zip(ctx.grads, ctx.needs_input_grad[:3])) + (None,) * 7
+
+
+def keypoint_heatmap_loss(map_nhwc, weight, bias, keypoints_crop, target_weight=None, decode=(1.0, 0.0, 1.0, 0.0), sigma=2.0, reduction="mean",
+                          topk=8, scale=0.5):
+    """Heatmap supervision of the native keypoint head as a free function on ANY contiguous NHWC map [B, H, W, C] (fp32 / bf16 / fp16): the
+    mean-squared error of final_layer's heatmaps against Gaussians of `sigma` cells around keypoints_crop [B, J, 2] (crop pixels; decode =
+    (sx, ox, sy, oy): heatmap -> crop pixels), weighted per joint by target_weight [B, J] -- upstream HRNet's JointsMSELoss (reduction "mean",
+    scale 0.5) / JointsOHKMMSELoss ("ohkm": the topk hardest joints of each frame).  Returns a 0-d loss, differentiable in weight [J, C] or
+    [J, C, 1, 1], in bias (a real gradient) and, for an fp32 map, in the map; a 16-bit map that requires grad raises NotImplementedError.
+    Neither the heatmaps nor the targets are materialised (capf_kp_heatmap_loss)."""
+    if not isinstance(reduction, str) or reduction not in KP_LOSS_REDUCTIONS:
+        raise ValueError("reduction must be 'mean' or 'ohkm', got {!r}".format(reduction))
+    gt = keypoints_crop.detach().to(torch.float32).contiguous()
+    tw = None if target_weight is None else target_weight.detach().to(torch.float32).reshape(gt.shape[0], gt.shape[1]).contiguous()
+    return _HeatmapLossFn.apply(map_nhwc, weight, bias, gt, tw, tuple(float(v) for v in decode), float(sigma), KP_LOSS_REDUCTIONS[reduction],
+                                int(topk), float(scale))
 
 
 # What CA_PF's two detect flows (_single_flow, _pair_flow) need to know about a keypoint head -- everything that differs between the heads is
@@ -718,6 +755,35 @@ class CA_PF(nn.Module):
         if to_image is None:
             raise ValueError("forward_detect needs to_image [B, 2, 3]: the lifter takes the keypoints in normalised image coordinates too")
         return self._single_flow(images, to_image, True, trains)
+
+    def keypoint_loss(self, images, keypoints_2d_crop, target_weight=None, sigma=2.0, reduction="mean", topk=8):
+        """Heatmap supervision of the native head against 2-D ground truth: ONE backbone pass (no gradient reaches it), then
+        capf_kp_heatmap_loss on feat0 -- final_layer's 1x1 conv, Gaussian targets of `sigma` heatmap cells around keypoints_2d_crop [B,J,2]
+        (crop pixels, what detect() returns as kcrop_px; the heatmap <-> crop convention is detect()'s), HRNet's JointsMSELoss
+        (reduction "mean") or JointsOHKMMSELoss ("ohkm", the `topk` hardest joints of each frame) with per-joint target_weight [B,J],
+        and its gradients, in one native call.  images: detect()'s forms (float32 or uint8 BGR crops).  Returns the 0-d loss; backward()
+        leaves gradients in keypoint_head.final_layer.weight / .bias and nowhere else.  This is how an "argmax" head is trained (its decode
+        has no derivative) and the only path that moves final_layer.bias; it serves "integral" models and every compute dtype alike.
+        keypoint_head=None: CapfError; "cpn": NotImplementedError (that head belongs to the frozen backbone)."""
+        head = self._head_record()
+        if head is not _FinalLayerHead:
+            raise NotImplementedError("keypoint_loss trains keypoint_head.final_layer: keypoint_head='cpn' has none (refine_net.final_predict "
+                                      "belongs to the frozen backbone)")
+        if not isinstance(reduction, str) or reduction not in KP_LOSS_REDUCTIONS:
+            raise ValueError("reduction must be 'mean' or 'ohkm', got {!r}".format(reduction))
+        images, _ = self._detect_inputs(images, None)
+        dev, B, H, W = images.device, images.shape[0], images.shape[1], images.shape[2]
+        if not torch.is_tensor(keypoints_2d_crop) or tuple(keypoints_2d_crop.shape) != (B, self.num_joints, 2):
+            raise ValueError("keypoints_2d_crop must be a tensor [{}, {}, 2] in crop pixels, got {}".format(
+                B, self.num_joints, tuple(getattr(keypoints_2d_crop, "shape", ()))))
+        weight, bias = self._head_params()
+        with torch.cuda.device(dev):
+            eng = self._engine_at(dev, H, W)
+            with torch.no_grad():
+                _run_backbone(self, eng, self._image_source(images), torch.cuda.current_stream(dev).cuda_stream)
+                feat0 = eng.tensor_view(head.maps, B)
+            return keypoint_heatmap_loss(feat0, weight, bias, keypoints_2d_crop.to(dev), None if target_weight is None else target_weight.to(dev),
+                                         head.decode(H, W, feat0.shape[1], feat0.shape[2]), sigma, reduction, topk)
 
     # ---- detector-free flip test: the heatmaps of each crop and of its flipped-back mirror averaged, then decoded once -----------
     def _swap_table(self, flip_pairs):

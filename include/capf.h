@@ -166,7 +166,7 @@ const char* capf_version(void);
  * (additive: capf_set_map_grad_mode, capf_map_grad_mode; CAPF_PLAN_BN_BATCH_STATS, capf_backbone_forward_bn, capf_op_bn_stats_scratch_bytes,
  * capf_op_bn_stats, capf_op_bn_apply; capf_backward_points; capf_kp_head_scratch_bytes, capf_kp_head_forward, capf_kp_head_backward;
  * capf_kp_head_pair_scratch_bytes, capf_kp_head_forward_pair; CAPF_PLAN_CPN_PREDICT, the named tensor "heat", capf_cpn_decode,
- * capf_cpn_decode_taps, capf_cpn_decode_lds_bytes; capf_cpn_decode_pair).                                                                   */
+ * capf_cpn_decode_taps, capf_cpn_decode_lds_bytes; capf_cpn_decode_pair; capf_kp_heatmap_loss_scratch_bytes, capf_kp_heatmap_loss).         */
 #define CAPF_ABI_VERSION 12
 int capf_abi_version(void);
 
@@ -841,6 +841,62 @@ size_t capf_kp_head_pair_scratch_bytes(int Bsrc, int H, int W, int C, int J);
 int capf_kp_head_forward_pair(void* stream, const void* map_nhwc, int map_dtype, const float* weight, const float* bias, int Bsrc, int H, int W,
                               int C, int J, int mode, float beta, const int32_t* swap, int shift, const float decode[4], const float* to_image,
                               float mirror_width, float* kcrop2, float* k2d2, float* score, float* heat, void* scratch, size_t scratch_bytes);
+/* ---- heatmap supervision of the 2-D keypoint head: MSE against Gaussian targets, loss and parameter gradients in one entry -------------------
+ * The loss heatmap heads are trained with -- upstream HRNet's JointsMSELoss / JointsOHKMMSELoss on generate_target's Gaussians; the reduction
+ * of cpn/train.py:85-93, 124-127 (ohkm(refine_loss, 8)) -- fused with final_layer's 1x1 conv: neither the logits nor the targets reach memory
+ * (csrc/kp_head.hip).  It is what trains an "argmax" head, and the only path on which final_layer.bias receives a gradient.  Stand-alone entry
+ * on device pointers; additive inside revision 12.  map, weight, bias, shape limits, alignment, dtypes: capf_kp_head_forward's.
+ * Logits: z[b, j, y, x] is capf_kp_head_forward's chain, bit for bit (its `heat` output).
+ * Target of (b, j), (kx, ky) = kcrop_gt[b, j] in crop pixels, decode = {sx, ox, sy, oy} as in the forward (heatmap -> crop pixels):
+ *       cx = (kx - ox) / sx, cy = (ky - oy) / sy      (fp32, the difference rounded, then the quotient)
+ *       mu = (int)(c + 0.5f)                          (the fp32 sum truncated toward zero, Python's int(): c = -0.7 gives 0, not -1)
+ *       R  = (int)ceilf(3.f * sigma)
+ *       t(y, x) = exp(-((x - mu_x)^2 + (y - mu_y)^2) / (2 sigma^2)) where |x - mu_x| <= R and |y - mu_y| <= R, 0 elsewhere
+ *           (in DOUBLE, as e[|x - mu_x|] e[|y - mu_y|] with e[k] = exp(-k^2 / (2 sigma^2)) and sigma the fp32 value widened; z - t is formed
+ *           in double and rounded ONCE to fp32, so its error is half an ulp of z - t even where z and t nearly cancel -- an fp32 expf would
+ *           leave an error relative to t, which no bound relative to the terms (z - t)^2 covers)
+ *   w_bj = target_weight[b, j] (NULL: 1), forced to 0 when the window lies wholly outside the map (mu_x - R >= W, mu_y - R >= H, mu_x + R < 0 or
+ *   mu_y + R < 0), when a coordinate of c is not finite, or when |c| > 2^20.
+ * Per item: l_bj = scale w_bj^2 (1 / (H W)) sum_pix (z - t)^2.  HRNet's criterion multiplies prediction and target by w (hence w^2) and has
+ *   scale = 0.5; scale = 1 with w in {0, 1} is cpn/train.py:124-126.
+ * reduction 0, mean: loss = (1 / (B J)) sum_bj l_bj.
+ * reduction 1, OHKM: loss = (1 / B) sum_b (1 / topk) sum_{j in top_b} l_bj; top_b holds the min(topk, J) largest l_bj of frame b, a NaN ranking
+ *   first and ties going to the smaller joint index; the divisor stays topk (cpn/train.py:85-93); only selected items receive gradient.
+ * Outputs: loss [1]; joint_loss [B, J] (l_bj, optional).  Gradients of `loss`, each optional (all NULL: the loss alone):
+ *       g_bj = 2 scale w_bj^2 sel_bj / (H W norm)  (norm = B J or B topk; sel = 1 under reduction 0),  dz = g_bj (z - t)
+ *       dweight [J, C] = sum_{b, pix} dz X      dbias [J] = sum_{b, pix} dz  (a real gradient here, unlike capf_kp_head_backward's zeros)
+ *       dmap [B, H, W, C] fp32, 16-byte aligned = sum_j dz weight[j, c], joints ascending, each element by one thread; accumulate = 1 adds it to
+ *           what is there (capf_backward_points' dfeat_nhwc[0]), 0 overwrites.  It needs an fp32 map: a 16-bit one is CAPF_ERR_UNSUPPORTED.
+ * Summation orders (no atomics, no signalling between workgroups): pixels are numbered row-major and cut into capf_kp_head_forward's tiles of
+ *   256; a block owns a frame's eighth of the tiles, ceil(tiles / 8) consecutive ones (capf_kp_head_backward's cut; a function of H * W alone).
+ *   sum (z - t)^2 of (b, j): 8 lanes share the joint, lane l adds (by fma) pixels l, l + 8, ... of each tile, tiles ascending; the lanes are added
+ *   in ascending l; a SECOND launch adds the blocks ascending, forms l_bj, ranks the joints of a frame and adds the selected l_bj of a frame in
+ *   ascending j; the last launch adds the frames -- part q of 16 takes frames q, q + 16, ... ascending, the parts ascending -- and divides by
+ *   norm.  dweight, dbias: per block and tile sum_pix (z - t) X (pixels ascending, by fma; X = 1 for dbias), times g_bj, added over the
+ *   block's tiles ascending; the last launch adds the blocks' partials -- part q of 16 takes blocks q, q + 16, ... ascending, parts ascending.
+ *   joint_loss[b, j] bits depend on frame b alone: not on B, the frame's position, the run or the scratch buffer.
+ * Passes: reduction 0 knows g up front -- loss and gradients come from ONE pass over the map (3 launches); OHKM needs every l_b. before any dz:
+ *   a loss pass, the selection, a gradient pass that recomputes the logits (4 launches).
+ * NaN: a NaN logit makes that l_bj and the loss NaN (under OHKM it ranks first); other items' joint_loss are untouched.  An item with
+ *   w_bj = 0, and under OHKM an item that is not selected, contributes EXACT zeros to every output, whatever its logits (0 is not multiplied
+ *   with them).
+ * scratch: capf_kp_heatmap_loss_scratch_bytes(B, H, W, C, J, reduction) bytes of device memory, 4-byte aligned (0: a shape the kernels do not
+ *   take, or an unknown reduction).
+ * Refusals, all before anything is launched (no device needed), CAPF_ERR_INVALID: a NULL map / weight / kcrop_gt / decode / loss / scratch,
+ *   B, J, C, H or W out of range, sx or sy zero or not finite, sigma <= 0 or not finite or R > 64, an unknown reduction or dtype, topk < 1,
+ *   scale not finite, accumulate not 0 / 1, a misaligned map / dmap, scratch_bytes too small.
+ * Cost (MI355X, feat0 64 x 64 x 32 of HRNet-32 fp32, sigma 2, medians of 20 around the host call, tools/bench_kp_head.py --loss, EXPERIMENTS.md
+ *   R33.1), mean / OHKM, against capf_kp_head_backward re-timed on the same map in the same session and a one-read floor of bytes / 8 TB/s:
+ *   batch 64 (floor 0.004 ms) -- the loss alone 0.053 / 0.054 ms, with dweight and dbias 0.120 / 0.150 ms against the backward's 0.155 ms
+ *   (ratio 0.77 / 0.97), with dmap 0.179 / 0.212 ms against 0.214 ms (0.84 / 0.99); batch 512 (floor 0.034 ms) -- 0.171 / 0.171 ms alone,
+ *   0.654 / 0.782 ms against 0.999 ms (0.66 / 0.78), with dmap 1.095 / 1.226 ms against 1.450 ms (0.76 / 0.85); fp16 HRNet-48 map, batch 256
+ *   (floor 0.013 ms; the backward takes no 16-bit map) -- 0.119 / 0.120 ms alone, 0.405 / 0.507 ms with dweight and dbias, against
+ *   capf_kp_head_forward's 0.196 ms (2.07 / 2.59).  5 - 50 x the floor: not memory-bound, like the head. */
+size_t capf_kp_heatmap_loss_scratch_bytes(int B, int H, int W, int C, int J, int reduction);
+int capf_kp_heatmap_loss(void* stream, const void* map_nhwc, int map_dtype, const float* weight, const float* bias, int B, int H, int W, int C,
+                         int J, const float* kcrop_gt, const float* target_weight, const float decode[4], float sigma, int reduction, int topk,
+                         float scale, float* loss, float* joint_loss, float* dweight, float* dbias, float* dmap, int accumulate, void* scratch,
+                         size_t scratch_bytes);
 /* ---- CPN's own heatmap decode: two peaks of the blurred map, a quarter pixel from the first towards the second ------------------------------
  * What cpn/test.py:79-108 does with the heatmaps of refine_net.final_predict (the named tensor "heat" of a CAPF_PLAN_CPN_PREDICT handle; any
  * other NHWC map of that layout does too), as ONE launch: one workgroup per (frame, joint), the planes in LDS, no scratch, no atomics

@@ -5,10 +5,15 @@ the machine; medians with min / max over the repeats.
 
     python tools/bench_kp_head.py [--configs hrnet_32:fp32:64 hrnet_32:fp32:512 hrnet_48:fp16:256] [--repeats 20] [--warmup 3]   (needs the MI355X)
     python tools/bench_kp_head.py --pair [--configs hrnet_32:fp32:32 hrnet_32:fp32:256 hrnet_48:fp16:128]     (EXPERIMENTS.md R28.1)
+    python tools/bench_kp_head.py --loss [--configs hrnet_32:fp32:64 hrnet_32:fp32:512 hrnet_48:fp16:256]     (EXPERIMENTS.md R33.1)
 
 --pair: the flip-test pair.  The batch of a config counts SOURCE frames; feat0 holds the 2 * Bsrc frames [orig | mirrored] of one backbone
 pass.  capf_kp_head_forward_pair against capf_kp_head_forward on the SAME map (the same bytes read, the same FMAs, half the (frame, joint)
 items), then forward_detect_flip_test against the route without it: detect + preprocess_points + forward_flip_test.
+
+--loss: heatmap supervision.  capf_kp_heatmap_loss (mean and OHKM; the loss alone, with dweight / dbias, with dmap on an fp32 map) against
+capf_kp_head_backward re-timed on the SAME map in the same session (fp32 maps: the backward takes no 16-bit map; there the comparison point is
+capf_kp_head_forward), with the one-read floor at 8 TB/s beside --hbm-gbs's.
 
 The floor is feat0's bytes over --hbm-gbs (default 4000 GB/s, roughly what a streaming read reaches on an MI355X); the backward reads the
 map three times (statistics, dz, the dW products) and, with dmap, writes it once.
@@ -74,10 +79,52 @@ def pair_row(args, spec, model, eng, img, A, s):
     return row
 
 
+def loss_row(args, spec, model, eng, img, A, s, dtype):
+    import torch
+    from capf import lib as capf
+    B = img.shape[0]
+    eng.backbone_forward(img, s)
+    feat0 = eng.tensor_view("feat0", B)
+    fl = model.keypoint_head.final_layer
+    w, b = fl.weight.detach().reshape(17, -1).contiguous(), fl.bias.detach()
+    dec = (4.0, 0.0, 4.0, 0.0)
+    g = torch.Generator().manual_seed(3)
+    gt = (torch.rand(B, 17, 2, generator=g) * 256).cuda()
+    tw = torch.ones(B, 17).cuda()
+    loss = lambda red, **kw: (lambda: capf.kp_heatmap_loss(feat0, w, b, gt, tw, dec, 2.0, red, 8, 0.5, **kw))
+    runs = {
+        "head_integral": lambda: capf.kp_head_forward(feat0, w, b, capf.KP_INTEGRAL, 2.0, dec, A),
+        "loss_mean_alone": loss("mean", want_grads=False),
+        "loss_mean_dW": loss("mean"),
+        "loss_ohkm_alone": loss("ohkm", want_grads=False),
+        "loss_ohkm_dW": loss("ohkm"),
+    }
+    if dtype == "fp32":
+        g1, g2 = torch.randn(B, 17, 2, device="cuda"), torch.randn(B, 17, 2, device="cuda")
+        dmap = torch.zeros_like(feat0)
+        runs["loss_mean_dW_dmap"] = loss("mean", dmap_accumulate_into=dmap)
+        runs["loss_ohkm_dW_dmap"] = loss("ohkm", dmap_accumulate_into=dmap)
+        runs["head_backward_dW"] = lambda: capf.kp_head_backward(feat0, w, b, g1, g2, 2.0, dec, A)
+        runs["head_backward_dW_dmap"] = lambda: capf.kp_head_backward(feat0, w, b, g1, g2, 2.0, dec, A, dmap=dmap)
+    nbytes = feat0.numel() * feat0.element_size()
+    row = {"config": spec, "loss": True, "feat0": list(feat0.shape), "feat0_MB": round(nbytes / 1e6, 2),
+           "one_read_floor_ms": round(nbytes / (args.hbm_gbs * 1e9) * 1e3, 4), "one_read_floor_8TBs_ms": round(nbytes / 8e12 * 1e3, 4),
+           "repeats": args.repeats}
+    with torch.no_grad():
+        row.update(timed(runs, args.repeats, args.warmup))
+    base = "head_backward_dW" if dtype == "fp32" else "head_integral"
+    row["compared_with"] = base
+    for k in [k for k in runs if k.startswith("loss_")]:
+        ref = "head_backward_dW_dmap" if k.endswith("_dmap") else base
+        row[k + "_over_" + ref] = round(row[k]["median_ms"] / row[ref]["median_ms"], 3)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="+", default=None, help="backbone:dtype:batch (source frames with --pair)")
     ap.add_argument("--pair", action="store_true", help="the flip-test pair: capf_kp_head_forward_pair / forward_detect_flip_test")
+    ap.add_argument("--loss", action="store_true", help="heatmap supervision: capf_kp_heatmap_loss against capf_kp_head_backward on the same map")
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--hbm-gbs", type=float, default=4000.0)
@@ -106,6 +153,12 @@ def main():
         s = torch.cuda.current_stream().cuda_stream
         if args.pair:
             print(json.dumps(pair_row(args, spec, model, eng, img, A, s)), flush=True)
+            for e in model._engines.values():
+                e.close()
+            model._engines.clear()
+            continue
+        if args.loss:
+            print(json.dumps(loss_row(args, spec, model, eng, img, A, s, dtype)), flush=True)
             for e in model._engines.values():
                 e.close()
             model._engines.clear()
