@@ -318,7 +318,7 @@ int Engine::exec_op(const Op& op, hipStream_t s, int batch, bool side_chain) {
                 case Family::F32_TILE: HIP_TRY(launch_f32_tile(&a, 1, s)); break;
                 case Family::WINO: HIP_TRY(launch_gemm_wino(a, s)); break;
                 default:
-                    if (op.in[0] == -2 && ses.u8()) HIP_TRY(launch_gemm_f32_u8(a, *ses.u8(), s));   // the stem from the uint8 crop: same route, U8 form
+                    if (op.in[0] == -2 && ses.u8()) HIP_TRY(launch_gemm_stem(a, ses.u8(), s));   // the stem from the uint8 crop: same route, U8 form
                     else HIP_TRY(launch_gemm_f32(a, s));
             }
             if (bn_run) {
@@ -697,7 +697,7 @@ int Engine::check_run(int batch) {
 }
 
 // The checks in the order every entry has always made them: training, the uint8 source's own (capf_forward_u8 and its siblings: nothing but
-// the stem's load differs from the float entries, launch_gemm_f32_u8), check_run, the maps, the uint8 stem.  Then, and only then, the state
+// the stem's load differs from the float entries, launch_gemm_stem), check_run, the maps, the uint8 stem.  Then, and only then, the state
 int Engine::begin(const Call& c) {
     if (c.training && !cfg.training) {
         err = "handle was created with training = 0";
@@ -1468,6 +1468,8 @@ int capf_op_linear_bf16(void* stream, const void* x_bf16, const void* w_bf16, co
 
 // ---- the 16-bit kernel families for either element format (dtype = CAPF_BF16 or CAPF_F16): the entries above are these at CAPF_BF16
 static bool dtype16(int dtype) { return dtype == CAPF_BF16 || dtype == CAPF_F16; }
+// a stand-alone 16-bit stem op is an op of the 16-bit stem kernels: a problem they do not take is refused, not handed on to the fp32 ones
+static bool stem_op_takes(const capf::GemmArgs& a) { return !a.out_bf16 || capf::stem_is_16bit(capf::gemm_stem_route(a).kernel); }
 
 int capf_op_pack_conv_16(void* stream, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
                          void* wp, float* bias, int Cout, int Cin, int ks, int layout, int dtype) {
@@ -1496,7 +1498,8 @@ int capf_op_conv_16(void* stream, const void* x, const void* wp, const float* bi
         capf::GemmArgs a = conv_args(conv_desc(x, wp, bias, nullptr, y, B, H, W, Cin, Cout, ks, stride, act), &capf::GemmArgs::Wp, 32);
         a.out_bf16 = 1;
         a.f16 = dtype == CAPF_F16;
-        return hip_rc(capf::launch_gemm_bf16_smallc(a, static_cast<hipStream_t>(stream)), CAPF_ERR_UNSUPPORTED);
+        if (!stem_op_takes(a)) return CAPF_ERR_UNSUPPORTED;
+        return hip_rc(capf::launch_gemm_stem(a, nullptr, static_cast<hipStream_t>(stream)), CAPF_ERR_UNSUPPORTED);
     }
     capf::GemmArgs a = conv_args(conv_desc(x, wp, bias, residual, y, B, H, W, Cin, Cout, ks, stride, act), &capf::GemmArgs::Wp, 64);
     a.f16 = dtype == CAPF_F16;
@@ -1608,8 +1611,8 @@ int capf_op_conv_u8(void* stream, const uint8_t* images_bgr_u8, const float* wp,
     capf::U8Input in;
     if (const int rc = conv_u8_args(wp, bias, y, Bsrc, mode, H, W, Cout, ks, stride, act, mean, std3, out_dtype, a, in)) return rc;
     in.img = images_bgr_u8;
-    if (out_dtype != CAPF_F32 && !capf::gemm_bf16_smallc_ok(a)) return CAPF_ERR_UNSUPPORTED;
-    return hip_rc(capf::launch_gemm_f32_u8(a, in, static_cast<hipStream_t>(stream)), CAPF_ERR_UNSUPPORTED);
+    if (!stem_op_takes(a)) return CAPF_ERR_UNSUPPORTED;
+    return hip_rc(capf::launch_gemm_stem(a, &in, static_cast<hipStream_t>(stream)), CAPF_ERR_UNSUPPORTED);
 }
 
 const char* capf_op_conv_u8_kernel_name(int Bsrc, int mode, int H, int W, int Cout, int ks, int stride, int out_dtype) {
@@ -1617,8 +1620,7 @@ const char* capf_op_conv_u8_kernel_name(int Bsrc, int mode, int H, int W, int Co
     capf::GemmArgs a;
     capf::U8Input in;
     if (conv_u8_args(nullptr, nullptr, nullptr, Bsrc, mode, H, W, Cout, ks, stride, 0, zero, nullptr, out_dtype, a, in)) return "";
-    if (out_dtype != CAPF_F32 && !capf::gemm_bf16_smallc_ok(a)) return "";
-    return capf::gemm_f32_u8_kernel_name(a);
+    return stem_op_takes(a) ? capf::gemm_stem_kernel_name(a, true) : "";
 }
 
 // ... and of the float stem op of the same shape at B frames (capf_op_conv; capf_op_conv_16's Cin = 3 branch)
@@ -1627,8 +1629,7 @@ const char* capf_op_conv_stem_kernel_name(int B, int H, int W, int Cout, int ks,
     capf::GemmArgs a;
     capf::U8Input in;
     if (conv_u8_args(nullptr, nullptr, nullptr, B, 0, H, W, Cout, ks, stride, 0, zero, nullptr, out_dtype, a, in)) return "";
-    if (out_dtype != CAPF_F32) return capf::gemm_bf16_smallc_ok(a) ? capf::gemm_bf16_smallc_kernel_name(a) : "";
-    return capf::gemm_f32_kernel_name(a);
+    return stem_op_takes(a) ? capf::gemm_stem_kernel_name(a, false) : "";
 }
 
 int capf_fliptest_fuse(void* stream, const float* pred2, int batch, float* out) {

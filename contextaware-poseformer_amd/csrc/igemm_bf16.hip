@@ -20,7 +20,7 @@
 //   igemm_bf16_rh_tile   3x3 / stride-1 "row-halo" tile: one staged activation tile for the three kw taps
 //   igemm_bf16_group_kernel / _pp_kernel / _rh_kernel   up to 8 independent convs in one grid (ring / ping-pong / ping-pong
 //                        with row-halo tiles); igemm_bf16_kernel / igemm_bf16_rh_kernel: one conv
-//   igemm_bf16_stem_kernel (+ igemm_bf16_smallc_kernel)   Cin = 3 stem under compute_dtype = bf16
+// (the Cin = 3 stem under compute_dtype = bf16 / fp16: igemm_stem.hip)
 #include <stdlib.h>
 
 #include <map>
@@ -865,611 +865,6 @@ __global__ __launch_bounds__(256) void igemm_bf16_stream_kernel(GemmArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned short lds[HALVES];
     igemm_bf16_tile<BM, BN, WM, WN, S, false, false, false, true, F>(p, xcd_remap_b(blockIdx.x, gridDim.x), lds);
 #endif
-}
-
-// =====================================================================================================
-// Small-Cin stem (Cin = 3, k = 3 or 7) under compute_dtype = bf16: the fp32 image is gathered element-wise (K order
-// (kh, kw, c), like the fp32 igemm_f32_smallc kernel whose packed fp32 weights it shares), rounded to bf16 on the way into
-// a padded LDS tile, and multiplied on v_mfma_f32_32x32x16_bf16: 1/8 of the matrix cycles of the fp32 stem, which was
-// 1.1 ms of CPN's 9.7 ms at batch 128 (384x288) -- the gather is what remains.  Output bf16 NHWC.
-// =====================================================================================================
-[[maybe_unused]] static constexpr int SPITCH = 40;          // halves per LDS row: 32 k-values + 8 pad (80 B: 16-byte aligned fragment reads)
-
-// U8 (all three stem kernels below): the uint8 forms -- the image is the BGR crop itself, see igemm_f32_smallc_body (igemm_f32.hip) for the
-// scheme: a per-block value table filled with pixel_rule(), one byte load per tap with its own validity, the same tile / K order / MFMA
-// sequence as the float form, the descriptor as an extra argument of the *_u8_kernel entry points.
-template <class F, bool U8>
-__device__ __forceinline__ void igemm_bf16_smallc_body(const GemmArgs& p, const U8Input* u8) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int BM = 128, BN = 64, WM = 64, WN = 32, SBK = 32;
-    constexpr int WAVES_N = BN / WN, TM = WM / 32, TN = WN / 32, RA = BM / 32, RB = BN / 32;
-    __shared__ __attribute__((aligned(16))) unsigned short lds[(BM + BN) * SPITCH + (U8 ? 2 * U8_TAB : 0)];
-    unsigned short* As = lds;
-    unsigned short* Bs = lds + BM * SPITCH;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* tab = reinterpret_cast<const float*>(lds + (BM + BN) * SPITCH);
-    if (U8) {
-        u8_fill_table(reinterpret_cast<float*>(lds + (BM + BN) * SPITCH), *u8, tid, 256);
-        __syncthreads();
-    }
-    const int nbn = (p.N + BN - 1) / BN;
-    const int bid = xcd_remap_b(blockIdx.x, gridDim.x);
-    const int tile_m = bid / nbn, tile_n = bid - tile_m * nbn;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const int srow = tid >> 3, kq = (tid & 7) * 4;
-
-    long a_base[RA];
-    int a_h0[RA], a_w0[RA], a_f[RA];                  // (a_f: the frame, read by the U8 form alone)
-#pragma unroll
-    for (int i = 0; i < RA; ++i) {
-        const int m = m0 + srow + 32 * i;
-        a_base[i] = 0; a_h0[i] = -(1 << 20); a_w0[i] = 0; a_f[i] = 0;
-        if (m < p.M) {
-            const int b = fast_div_b(m, p.fd_hw), rem = m - b * p.Ho * p.Wo;
-            const int ho = fast_div_b(rem, p.fd_wo), wo = rem - ho * p.Wo;
-            a_f[i] = b;
-            a_base[i] = (long)b * p.H * p.W * p.Cin;
-            a_h0[i] = ho * p.stride - p.pad;
-            a_w0[i] = wo * p.stride - p.pad;
-        }
-    }
-    float a_reg[RA][4];
-    f32x4 b_reg[RB];
-    auto load_chunk = [&](int c) {
-        int dh[4], dw[4], doff[4], dc[4];
-        bool kok[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {          // the (kh, kw, c) of this thread's four k-values: the same for every row
-            const int ke = c * SBK + kq + e;
-            const int t = ke / p.Cin, c1 = ke - t * p.Cin;
-            dh[e] = t / p.ks;
-            dw[e] = t - dh[e] * p.ks;
-            doff[e] = (dh[e] * p.W + dw[e]) * p.Cin + c1;
-            kok[e] = ke < p.K;
-            dc[e] = kok[e] ? c1 : 0;
-        }
-#pragma unroll
-        for (int i = 0; i < RA; ++i) {
-            const long row = a_base[i] + ((long)a_h0[i] * p.W + a_w0[i]) * p.Cin;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int hi = a_h0[i] + dh[e], wi = a_w0[i] + dw[e];
-                const bool ok = kok[e] && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-                if (U8) a_reg[i][e] = u8_value(tab, ok, u8_load(*u8, ok, u8_pixel(*u8, a_f[i], hi, wi, p.H, p.W), dc[e]), dc[e]);
-                else a_reg[i][e] = ok ? p.A[row + doff[e]] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            const int n = n0 + srow + 32 * i;
-            b_reg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (n < p.N) b_reg[i] = *reinterpret_cast<const f32x4*>(p.Wp + (long)n * p.Kpad + c * SBK + kq);
-        }
-    };
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    const int wm0 = (wave / WAVES_N) * WM, wn0 = (wave % WAVES_N) * WN;
-    const int frow = lane & 31, fhalf = lane >> 5;
-    const int nchunks = p.Kpad / SBK;          // the fp32 pack pads K to a multiple of 32
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    load_chunk(0);
-    for (int c = 0; c < nchunks; ++c) {
-#pragma unroll
-        for (int i = 0; i < RA; ++i)
-            *reinterpret_cast<u32x2*>(&As[(srow + 32 * i) * SPITCH + kq]) =
-                u32x2{F::pack2(a_reg[i][0], a_reg[i][1]), F::pack2(a_reg[i][2], a_reg[i][3])};
-#pragma unroll
-        for (int i = 0; i < RB; ++i)
-            *reinterpret_cast<u32x2*>(&Bs[(srow + 32 * i) * SPITCH + kq]) =
-                u32x2{F::pack2(b_reg[i][0], b_reg[i][1]), F::pack2(b_reg[i][2], b_reg[i][3])};
-        __syncthreads();
-        if (c + 1 < nchunks) load_chunk(c + 1);
-#pragma unroll
-        for (int step = 0; step < SBK / 16; ++step) {
-            typename F::x8 af[TM], bfr[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-                af[i] = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + frow) * SPITCH + step * 16 + fhalf * 8]));
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                bfr[j] = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + j * 32 + frow) * SPITCH + step * 16 + fhalf * 8]));
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = F::mfma(bfr[j], af[i], acc[i][j]);
-        }
-        __syncthreads();
-    }
-    // transposed accumulator (lane = row m, register group g = channels 8 g + 4 (lane >> 5) .. + 3): 8-byte stores
-    unsigned short* Out = reinterpret_cast<unsigned short*>(p.out);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int m = m0 + wm0 + i * 32 + frow;
-        if (m >= p.M) continue;
-        const long o_row = (long)m * p.omap.S1 + p.omap.off;
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int n = n0 + wn0 + j * 32 + 4 * fhalf + 8 * g;
-                if (n >= p.N) continue;
-                u16x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float t = acc[i][j][4 * g + e] + (p.bias ? p.bias[n + e] : 0.f);
-                    if (p.act == ACT_RELU) t = relu_f(t);
-                    v[e] = F::narrow(t);
-                }
-                *reinterpret_cast<u16x4*>(Out + o_row + n) = v;
-            }
-    }
-#endif
-}
-
-template <class F>
-__global__ __launch_bounds__(256) void igemm_bf16_smallc_kernel(GemmArgs p) { igemm_bf16_smallc_body<F, false>(p, nullptr); }
-template <class F>
-__global__ __launch_bounds__(256) void igemm_bf16_smallc_u8_kernel(GemmArgs p, U8Input in) { igemm_bf16_smallc_body<F, true>(p, &in); }
-
-// Stem, second version (Cin = 3, k = 7 or 3): for a fixed (output pixel, kh) the 3 k input values are CONTIGUOUS in the NHWC
-// image (and in the (kh, kw, c)-ordered weights), so a thread fetches one such run with 16-byte loads (dword-aligned
-// addresses) instead of 21 / 9 scalar gathers, zeroes what lies outside the image, and writes it as bf16 into an LDS tile
-// whose K axis is (kh, 24 | 16): the whole K of a 128 x 64 tile is staged once (no chunk loop), then 11 / 3 MFMA k-steps.
-template <int KS, int BM, class F, bool U8>
-__device__ __forceinline__ void igemm_bf16_stem_body(const GemmArgs& p, const U8Input* u8) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int BN = 64, WM = BM / 2, WN = 32, TM = WM / 32;
-    constexpr int RUN = KS * 3;                      // contiguous floats per (pixel, kh)
-    constexpr int NX4 = (RUN + 3) / 4;               // 16-byte loads per run
-    constexpr int PKH = (RUN + 7) / 8 * 8;           // halves per kh in LDS (24 / 16)
-    constexpr int KP = (KS * PKH + 15) / 16 * 16;    // staged K (176 / 48)
-    constexpr int PITCH = KP + 8;                    // halves per LDS row: 16-byte aligned, conflict-free b128 reads
-    __shared__ __attribute__((aligned(16))) unsigned short lds[(BM + BN) * PITCH + (U8 ? 2 * U8_TAB : 0)];
-    unsigned short* As = lds;
-    unsigned short* Bs = lds + BM * PITCH;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nbn = (p.N + BN - 1) / BN;
-    const int bid = xcd_remap_b(blockIdx.x, gridDim.x);
-    const int tile_m = bid / nbn, tile_n = bid - tile_m * nbn;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const long total = (long)(p.M / (p.Ho * p.Wo)) * p.H * p.W * 3;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const float* tab = reinterpret_cast<const float*>(lds + (BM + BN) * PITCH);
-    if (U8) {
-        u8_fill_table(reinterpret_cast<float*>(lds + (BM + BN) * PITCH), *u8, tid, 256);
-        __syncthreads();
-    }
-
-    auto put_run = [&](unsigned short* dst, const float (&v)[NX4 * 4], int kh) {     // RUN values (+ zero padding) -> LDS as bf16
-        unsigned pk[PKH / 2];
-#pragma unroll
-        for (int e = 0; e < PKH / 2; ++e)
-            pk[e] = F::pack2(2 * e < NX4 * 4 ? v[2 * e] : 0.f, 2 * e + 1 < NX4 * 4 ? v[2 * e + 1] : 0.f);
-#pragma unroll
-        for (int q = 0; q < PKH / 8; ++q)
-            *reinterpret_cast<u32x4*>(dst + kh * PKH + q * 8) = u32x4{pk[4 * q], pk[4 * q + 1], pk[4 * q + 2], pk[4 * q + 3]};
-        if (KP > KS * PKH && kh == KS - 1)                                         // the tail of the last k-step
-            *reinterpret_cast<u32x4*>(dst + KS * PKH) = u32x4{0u, 0u, 0u, 0u};
-    };
-    for (int t = tid; t < BM * KS; t += 256) {               // activation runs: consecutive lanes = consecutive pixels
-        const int kh = t / BM, row = t - kh * BM;
-        const int m = m0 + row;
-        float v[NX4 * 4];
-#pragma unroll
-        for (int e = 0; e < NX4 * 4; ++e) v[e] = 0.f;
-        if (m < p.M) {
-            const int b = fast_div_b(m, p.fd_hw), rem = m - b * p.Ho * p.Wo;
-            const int ho = fast_div_b(rem, p.fd_wo), wo = rem - ho * p.Wo;
-            const int hi = ho * p.stride - p.pad + kh, wi0 = wo * p.stride - p.pad;
-            if (U8 && (unsigned)hi < (unsigned)p.H) {
-#pragma unroll
-                for (int kw = 0; kw < KS; ++kw) {
-                    const bool ok = (unsigned)(wi0 + kw) < (unsigned)p.W;
-                    const long px = u8_pixel(*u8, b, hi, wi0 + kw, p.H, p.W);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) v[3 * kw + c] = u8_value(tab, ok, u8_load(*u8, ok, px, c), c);
-                }
-            } else if ((unsigned)hi < (unsigned)p.H) {
-                const long src = (((long)b * p.H + hi) * p.W + wi0) * 3;
-#pragma unroll
-                for (int x = 0; x < NX4; ++x) {
-                    const long o = src + 4 * x;
-                    if (o >= 0 && o + 4 <= total) {
-                        __builtin_memcpy(&v[4 * x], p.A + o, 16);
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (o + e >= 0 && o + e < total) v[4 * x + e] = p.A[o + e];
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < NX4 * 4; ++e)
-                    if (e >= RUN || (unsigned)(wi0 + e / 3) >= (unsigned)p.W) v[e] = 0.f;
-            }
-        }
-        put_run(As + row * PITCH, v, kh);
-    }
-    for (int t = tid; t < BN * KS; t += 256) {               // weight runs from the fp32 pack [N][Kpad], K order (kh, kw, c)
-        const int kh = t / BN, n = t - kh * BN;
-        float v[NX4 * 4];
-#pragma unroll
-        for (int e = 0; e < NX4 * 4; ++e) v[e] = 0.f;
-        if (n0 + n < p.N) {
-            const float* src = p.Wp + (long)(n0 + n) * p.Kpad + kh * RUN;          // (kh * RUN + 4 NX4 <= Kpad: launcher checks)
-#pragma unroll
-            for (int x = 0; x < NX4; ++x) __builtin_memcpy(&v[4 * x], src + 4 * x, 16);
-#pragma unroll
-            for (int e = RUN; e < NX4 * 4; ++e) v[e] = 0.f;
-        }
-        put_run(Bs + n * PITCH, v, kh);
-    }
-    __syncthreads();
-
-    f32x16 acc[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    const int wm0 = (wave >> 1) * WM, wn0 = (wave & 1) * WN;
-    const int frow = lane & 31, fhalf = lane >> 5;
-#pragma unroll
-    for (int step = 0; step < KP / 16; ++step) {
-        const typename F::x8 bfr = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + frow) * PITCH + step * 16 + fhalf * 8]));
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const typename F::x8 af = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + frow) * PITCH + step * 16 + fhalf * 8]));
-            acc[i] = F::mfma(bfr, af, acc[i]);
-        }
-    }
-    // transposed accumulator (lane = row m, register group g = channels 8 g + 4 fhalf .. + 3): 8-byte stores
-    unsigned short* Out = reinterpret_cast<unsigned short*>(p.out);
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int n = n0 + wn0 + 4 * fhalf + 8 * g;
-        if (n >= p.N) continue;
-        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-        if (p.bias) bv = *reinterpret_cast<const f32x4*>(p.bias + n);
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int m = m0 + wm0 + i * 32 + frow;
-            if (m >= p.M) continue;
-            float t[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                t[e] = acc[i][4 * g + e] + bv[e];
-                if (p.act == ACT_RELU) t[e] = relu_f(t[e]);
-            }
-            *reinterpret_cast<u32x2*>(Out + (long)m * p.omap.S1 + p.omap.off + n) = u32x2{F::pack2(t[0], t[1]), F::pack2(t[2], t[3])};
-        }
-    }
-#endif
-}
-
-template <int KS, int BM, class F>
-__global__ __launch_bounds__(256) void igemm_bf16_stem_kernel(GemmArgs p) { igemm_bf16_stem_body<KS, BM, F, false>(p, nullptr); }
-template <int KS, int BM, class F>
-__global__ __launch_bounds__(256) void igemm_bf16_stem_u8_kernel(GemmArgs p, U8Input in) { igemm_bf16_stem_body<KS, BM, F, true>(p, &in); }
-
-// Stem, third version: PERSISTENT blocks with the weights staged once and the next tile's runs in flight while the current
-// tile is multiplied and stored.  The second version above is one latency chain per block -- gather (6 x 16-byte loads per run
-// behind per-quad branches, i.e. one L2 round trip after the other), LDS, 11 MFMAs, 8-byte strided stores -- with only two
-// 70 KiB blocks per CU to hide it: 488 us for CPN's 7x7 at batch 128 (1.3 TB/s; 453 MB out + 170 MB in would take 125 us at
-// 5 TB/s).  Here: 64-pixel tiles (47 KiB of operands + 18 KiB of epilogue scratch: two blocks per CU), every run fetched with
-// raw buffer loads on ONE descriptor over the whole image tensor (a quad outside it, or of a row above / below the image,
-// gets an out-of-range offset; a quad only PARTLY beyond the tensor's end returns its in-range dwords -- range checking is
-// per dword, tools/buffer_oob.hip), so all of a thread's 12 / 3 loads are in flight at once and stay in flight across the
-// MFMAs and the stores of the previous tile; the epilogue transposes through LDS and stores 16 bytes per lane, 64 B
-// contiguous per row.  XCD-aware tile order: each XCD walks its own contiguous eighth of the tiles, so the 7 / 3 input rows
-// that vertically adjacent tiles share are fetched into ONE L2.  Only the handful of runs at the very start of the tensor (negative
-// offsets cannot be expressed) are patched element-wise by the blocks that own those pixels.
-// U8: issue() requests the runs' 21 / 9 bytes one by one -- in flight across the previous tile's MFMAs and stores like the float form's
-// loads -- and the table turns them into the float run just before put_run.  Every byte carries its own validity, so the patch of the runs
-// that start before the tensor has nothing to do in that form.
-template <int KS, class F, bool U8>
-__device__ __forceinline__ void igemm_bf16_stem_stream_body(const GemmArgs& p, const int ntiles, const U8Input* u8) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int BM = 64, BN = 64;
-    constexpr int RUN = KS * 3;                      // contiguous floats per (pixel, kh)
-    constexpr int NX4 = RUN / 4;                     // 16-byte loads per run (5 / 2) ...
-    static_assert(RUN % 4 == 1, "... plus ONE dword: a 16-byte load whose upper dwords nobody reads leaves dead destination "
-                                "registers that the allocator reuses -- and a vmcnt(0) in front of that reuse");
-    constexpr int PKH = (RUN + 7) / 8 * 8;           // halves per kh in LDS (24 / 16)
-    constexpr int KP = (KS * PKH + 15) / 16 * 16;    // staged K (176 / 48)
-    constexpr int PITCH = KP + 8;                    // halves per LDS row: 16-byte aligned, conflict-free b128 reads
-    constexpr int NT = (BM * KS + 255) / 256;        // runs per thread and tile (2 / 1)
-    constexpr int EPS = 36;
-    constexpr unsigned OOB = 0x80000000u;
-    __shared__ __attribute__((aligned(16))) unsigned short lds[(BM + BN) * PITCH + 4 * 32 * EPS * 2 + (U8 ? 2 * U8_TAB : 0)];
-    unsigned short* As = lds;
-    unsigned short* Bs = lds + BM * PITCH;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float* ep = reinterpret_cast<float*>(lds + (BM + BN) * PITCH) + wave * (32 * EPS);
-    const float* tab = reinterpret_cast<const float*>(lds + (BM + BN) * PITCH + 4 * 32 * EPS * 2);
-    if (U8) u8_fill_table(reinterpret_cast<float*>(lds + (BM + BN) * PITCH + 4 * 32 * EPS * 2), *u8, tid, 256);   // (its barrier: in front of the tile loop)
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    unsigned short* Out = reinterpret_cast<unsigned short*>(p.out);
-    const long total = (long)(p.M / (p.Ho * p.Wo)) * p.H * p.W * 3;              // floats of the image tensor (< 2^29: launcher)
-    const rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(U8 ? (void*)Out : (void*)p.A, 0, U8 ? 0u : (unsigned)(total * 4), 0x00020000);
-    const rsrc_t rs_bias = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)p.bias : (void*)Out, 0,
-                                                             p.bias ? (unsigned)p.N * 4u : 0u, 0x00020000);
-
-    auto put_run = [&](unsigned short* dst, const f32x4 (&q)[NX4], float last, unsigned mask, int kh) {   // RUN values (+ zeros) -> LDS
-        auto val = [&](int e) { return e < NX4 * 4 ? q[e >> 2][e & 3] : (e == NX4 * 4 ? last : 0.f); };
-        unsigned pk[PKH / 2];
-        if (mask == (1u << RUN) - 1u) {              // interior pixel (all but ~1 run in 70): no per-element selects
-#pragma unroll
-            for (int e = 0; e < PKH / 2; ++e) pk[e] = F::pack2(2 * e < RUN ? val(2 * e) : 0.f, 2 * e + 1 < RUN ? val(2 * e + 1) : 0.f);
-        } else {
-#pragma unroll
-            for (int e = 0; e < PKH / 2; ++e) {
-                const float a = 2 * e < RUN && ((mask >> (2 * e)) & 1u) ? val(2 * e) : 0.f;
-                const float b = 2 * e + 1 < RUN && ((mask >> (2 * e + 1)) & 1u) ? val(2 * e + 1) : 0.f;
-                pk[e] = F::pack2(a, b);
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < PKH / 8; ++g)
-            *reinterpret_cast<u32x4*>(dst + kh * PKH + g * 8) = u32x4{pk[4 * g], pk[4 * g + 1], pk[4 * g + 2], pk[4 * g + 3]};
-        if (KP > KS * PKH && kh == KS - 1)                                         // the tail of the last k-step
-            *reinterpret_cast<u32x4*>(dst + KS * PKH) = u32x4{0u, 0u, 0u, 0u};
-    };
-
-    // ---- weights, once per block: runs of the fp32 pack [N][Kpad], K order (kh, kw, c)
-    {
-        const rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wp, 0, (unsigned)p.N * (unsigned)p.Kpad * 4u, 0x00020000);
-        for (int t = tid; t < BN * KS; t += 256) {
-            const int kh = t / BN, n = t - kh * BN;
-            f32x4 q[NX4];
-            const unsigned wo = n < p.N ? (unsigned)(n * p.Kpad + kh * RUN) * 4u : OOB;
-#pragma unroll
-            for (int x = 0; x < NX4; ++x)
-                q[x] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, n < p.N ? wo + 16u * x : OOB, 0, 0));
-            const float last = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_w, n < p.N ? wo + 16u * NX4 : OOB, 0, 0));
-            put_run(Bs + n * PITCH, q, last, (1u << RUN) - 1u, kh);
-        }
-    }
-    // XCD-aware persistent walk: XCD x owns tiles [x * per_xcd, (x + 1) * per_xcd); its blocks take them round-robin
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;        // (gridDim.x % 8 == 0: launcher)
-    const int per_xcd = (ntiles + 7) >> 3;
-    const int t_end = min(ntiles, (xcd + 1) * per_xcd);
-    int tile = xcd * per_xcd + slot;
-
-    f32x4 q[NT][NX4];
-    float qlast[NT];
-    unsigned mask[NT];
-    unsigned raw[NT][RUN];                           // U8: the runs' bytes, (kw, c) order like the float runs
-    // run i of this thread; a thread without an i-th run repeats another one (same loads, the same LDS bytes written twice) --
-    // a branch around put_run would leave "maybe pending" loads behind it and cost a vmcnt(0) in front of the next requests
-    auto run_of = [&](int i) { return (tid + 256 * i) % (BM * KS); };
-    auto issue = [&](int tl) {                       // request the runs of tile tl (tl >= t_end: every offset out of range)
-        const int m0 = tl * BM;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const int t = run_of(i);
-            const int kh = t / BM, row = t - kh * BM;
-            const int m = m0 + row;
-            bool ok = tl < t_end && m < p.M;
-            const int mm = ok ? m : 0;
-            const int b = fast_div_b(mm, p.fd_hw), rem = mm - b * p.Ho * p.Wo;
-            const int ho = fast_div_b(rem, p.fd_wo), wo = rem - ho * p.Wo;
-            const int hi = ho * p.stride - p.pad + kh, wi0 = wo * p.stride - p.pad;
-            ok = ok && (unsigned)hi < (unsigned)p.H;
-            const int o = ((b * p.H + hi) * p.W + wi0) * 3;                      // floats from the tensor start (may be < 0 at its start)
-            // elements 3 lo .. 3 hn - 1 of the run lie inside the image row
-            const int lo = max(0, -wi0), hn = max(lo, min(KS, p.W - wi0));
-            const unsigned mk = ((1u << (3 * hn)) - 1u) & ~((1u << (3 * lo)) - 1u);
-            mask[i] = ok ? mk : 0u;
-            if (U8) {
-#pragma unroll
-                for (int kw = 0; kw < KS; ++kw) {
-                    const bool v = (mask[i] >> (3 * kw)) & 1u;
-                    const long px = u8_pixel(*u8, b, hi, wi0 + kw, p.H, p.W);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) raw[i][3 * kw + c] = u8_load(*u8, v, px, c);
-                }
-                continue;
-            }
-#pragma unroll
-            for (int x = 0; x < NX4; ++x)
-                q[i][x] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                        rs_in, (ok && o + 4 * x >= 0) ? (unsigned)(o + 4 * x) * 4u : OOB, 0, 0));
-            qlast[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                     rs_in, (ok && o + 4 * NX4 >= 0) ? (unsigned)(o + 4 * NX4) * 4u : OOB, 0, 0));
-        }
-    };
-    const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * 32;
-    const int frow = lane & 31, fhalf = lane >> 5;
-    const int er = lane >> 2, ec = (lane & 3) * 8;
-    const f32x4 b0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_bias, (unsigned)(wn0 + ec) * 4u, 0, 0));
-    const f32x4 b1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_bias, (unsigned)(wn0 + ec + 4) * 4u, 0, 0));
-
-    issue(tile);
-    {   // two dropped stores: the loop is entered with the same "loads, then two stores" in flight as its back edge leaves, so the
-        // wait in front of the LDS writes is a counted vmcnt(2) -- not a vmcnt(0) that would sit out the previous tile's stores
-        const rsrc_t rs_none = __builtin_amdgcn_make_buffer_rsrc((void*)Out, 0, 0u, 0x00020000);
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, rs_none, OOB, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, rs_none, OOB + 16u, 0, 0);   // (distinct: identical stores are merged)
-    }
-    if (U8) __syncthreads();                          // the value table is complete
-    for (; tile < t_end; tile += nslots) {
-        const int m0 = tile * BM;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const int t = run_of(i);
-            const int kh = t / BM, row = t - kh * BM;
-            if (U8) {                                  // bytes -> the float run (masked elements are zeroed by put_run)
-#pragma unroll
-                for (int e = 0; e < RUN; ++e) {
-                    const float v = tab[(e % 3) * 256 + raw[i][e]];
-                    if (e < NX4 * 4) q[i][e >> 2][e & 3] = v; else qlast[i] = v;
-                }
-            }
-            put_run(As + row * PITCH, q[i], qlast[i], mask[i], kh);
-        }
-        const int ho_max = p.pad / p.stride;           // output rows (of frame 0) with a window row on input row 0
-        if (!U8 && m0 < (ho_max + 1) * p.Wo) {
-            // Frame 0, input row 0, window starting left of the image: the run begins at a NEGATIVE offset from the tensor start,
-            // which a buffer offset cannot express -- its first quads were requested out of range above.  The few such runs
-            // (output rows ho = (pad - kh) / stride, columns wo * stride < pad) are rewritten here element by element.
-            __syncthreads();
-            const int nw = min(p.Wo, (p.pad + p.stride - 1) / p.stride);
-            for (int idx = tid; idx < (ho_max + 1) * nw * PKH; idx += 256) {
-                const int e = idx % PKH, r = idx / PKH, wo = r % nw, ho = r / nw;
-                const int kh = p.pad - ho * p.stride, m = ho * p.Wo + wo;
-                if (kh >= 0 && kh < KS && m >= m0 && m < m0 + BM) {
-                    const int wi = wo * p.stride - p.pad + e / 3;
-                    float v = 0.f;
-                    if (e < RUN && (unsigned)wi < (unsigned)p.W) v = p.A[wi * 3 + e % 3];
-                    As[(m - m0) * PITCH + kh * PKH + e] = F::narrow(v);
-                }
-            }
-        }
-        __syncthreads();
-        issue(tile + nslots);                         // in flight across this tile's MFMAs and stores
-
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int step = 0; step < KP / 16; ++step) {
-            const typename F::x8 bfr = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&Bs[(wn0 + frow) * PITCH + step * 16 + fhalf * 8]));
-            const typename F::x8 af = __builtin_bit_cast(typename F::x8, *reinterpret_cast<const f32x4*>(&As[(wm0 + frow) * PITCH + step * 16 + fhalf * 8]));
-            acc = F::mfma(bfr, af, acc);
-        }
-        // transposed accumulator (lane = row, register group g = channels 8 g + 4 fhalf ..) -> LDS -> 8 channels of a row per lane
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<f32x4*>(&ep[frow * EPS + 8 * g + 4 * fhalf]) = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-        __builtin_amdgcn_wave_barrier();
-        const rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc((void*)(Out + (long)m0 * p.omap.S1 + p.omap.off), 0, 0x7FFFFF00u, 0x00020000);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int row = h * 16 + er, ml = wm0 + row, nl = wn0 + ec;
-            const f32x4 x0 = *reinterpret_cast<const f32x4*>(&ep[row * EPS + ec]);
-            const f32x4 x1 = *reinterpret_cast<const f32x4*>(&ep[row * EPS + ec + 4]);
-            float t[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { t[e] = x0[e] + b0[e]; t[4 + e] = x1[e] + b1[e]; }
-            if (p.act == ACT_RELU) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) t[e] = relu_f(t[e]);
-            }
-            const u32x4 o = u32x4{F::pack2(t[0], t[1]), F::pack2(t[2], t[3]), F::pack2(t[4], t[5]), F::pack2(t[6], t[7])};
-            __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, (m0 + ml < p.M && nl < p.N) ? (unsigned)(ml * (int)p.omap.S1 + nl) * 2u : OOB, 0, 0);
-        }
-        __syncthreads();                              // every wave has read As: the next tile's runs may overwrite it
-    }
-#endif
-}
-
-template <int KS, class F>
-__global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_kernel(GemmArgs p, int ntiles) {
-    igemm_bf16_stem_stream_body<KS, F, false>(p, ntiles, nullptr);
-}
-template <int KS, class F>
-__global__ __launch_bounds__(256, 2) void igemm_bf16_stem_stream_u8_kernel(GemmArgs p, int ntiles, U8Input in) {
-    igemm_bf16_stem_stream_body<KS, F, true>(p, ntiles, &in);
-}
-
-// fp32 NHWC image (Cin % 4 != 0), fp32 packed weights [N][Kpad32], bf16 NHWC result; no residual.
-bool gemm_bf16_smallc_ok(const GemmArgs& a) {
-    return a.conv && a.out_bf16 && !a.res && a.omap.G == 1 && a.N % 4 == 0 && a.omap.S1 % 4 == 0 && a.omap.off % 4 == 0 &&
-           a.Kpad % 32 == 0 && a.act != ACT_GELU;
-}
-
-static int stem_runs_ks(const GemmArgs& a) {     // 7 / 3: the run-based stem kernel applies; 0: the element-wise gather kernel
-    static const int v2 = [] { const char* e = diag_env("CAPF_STEM_V2"); return e ? atoi(e) : 1; }();     // A/B runs only
-    if (!v2 || a.Cin != 3 || a.pad != a.ks / 2 || a.K != a.ks * a.ks * 3) return 0;
-    if (a.ks == 7 && a.Kpad >= 6 * 21 + 24) return 7;
-    if (a.ks == 3 && a.Kpad >= 2 * 9 + 12) return 3;
-    return 0;
-}
-
-// the persistent streaming stem: one 64-column tile, 8-channel vector stores, 32-bit float offsets into the image tensor
-static bool stem_stream_ok(const GemmArgs& a) {
-    static const int on = [] { const char* e = diag_env("CAPF_STEM_STREAM"); return e ? atoi(e) : 1; }();        // A/B runs only
-    const long total = (long)(a.M / (a.Ho * a.Wo)) * a.H * a.W * 3;
-    return on && a.N <= 64 && a.N % 8 == 0 && a.omap.S1 % 8 == 0 && a.omap.off % 8 == 0 && total < (1L << 29) && a.Wo >= 4;
-}
-
-const char* gemm_bf16_smallc_kernel_name(const GemmArgs& a) {
-    if (!stem_runs_ks(a)) return fmt_kernel_name("igemm_bf16_smallc<w4,128x64>", a.f16);
-    return fmt_kernel_name(stem_stream_ok(a) ? "igemm_bf16_stem_stream<w4,64x64>" : "igemm_bf16_stem<w4,128x64>", a.f16);
-}
-
-hipError_t launch_gemm_bf16_smallc(const GemmArgs& a_in, hipStream_t s) {
-    if (!gemm_bf16_smallc_ok(a_in)) return hipErrorInvalidValue;
-    GemmArgs a = a_in;
-    a.fd_hw = make_fastdiv((unsigned)(a.Ho * a.Wo));
-    a.fd_wo = make_fastdiv((unsigned)a.Wo);
-    const int ks = stem_runs_ks(a);
-    if (ks && stem_stream_ok(a)) {
-        const int ntiles = (a.M + 63) / 64;
-        int blocks = 512;                              // two per CU
-        while (blocks > 8 && blocks / 2 >= ntiles) blocks /= 2;
-        with_fmt(a.f16, [&](auto f) {
-            using F = decltype(f);
-            if (ks == 7) hipLaunchKernelGGL((igemm_bf16_stem_stream_kernel<7, F>), dim3(blocks), dim3(256), 0, s, a, ntiles);
-            else hipLaunchKernelGGL((igemm_bf16_stem_stream_kernel<3, F>), dim3(blocks), dim3(256), 0, s, a, ntiles);
-            return 0;
-        });
-        return hipGetLastError();
-    }
-    const dim3 grid(((a.M + 127) / 128) * ((a.N + 63) / 64));
-    // (64-pixel tiles -- 47 KiB, three blocks per CU for the 7x7 -- measured slower: 0.50 -> 0.59 ms for CPN, 0.30 -> 0.35 for HRNet)
-    with_fmt(a.f16, [&](auto f) {
-        using F = decltype(f);
-        if (ks == 7) hipLaunchKernelGGL((igemm_bf16_stem_kernel<7, 128, F>), grid, dim3(256), 0, s, a);
-        else if (ks == 3) hipLaunchKernelGGL((igemm_bf16_stem_kernel<3, 128, F>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(igemm_bf16_smallc_kernel<F>, grid, dim3(256), 0, s, a);
-        return 0;
-    });
-    return hipGetLastError();
-}
-
-// ... and from the uint8 crop: the same decisions (stem_runs_ks, stem_stream_ok), the U8 form of the kernel they name
-const char* gemm_bf16_smallc_u8_kernel_name(const GemmArgs& a) {
-    if (!stem_runs_ks(a)) return fmt_kernel_name("igemm_bf16_smallc<w4,128x64,u8>", a.f16);
-    return fmt_kernel_name(stem_stream_ok(a) ? "igemm_bf16_stem_stream<w4,64x64,u8>" : "igemm_bf16_stem<w4,128x64,u8>", a.f16);
-}
-
-hipError_t launch_gemm_bf16_smallc_u8(const GemmArgs& a_in, const U8Input& in, hipStream_t s) {
-    if (!gemm_bf16_smallc_ok(a_in) || !gemm_u8_ok(a_in, in)) return hipErrorInvalidValue;
-    GemmArgs a = a_in;
-    a.A = nullptr;
-    a.fd_hw = make_fastdiv((unsigned)(a.Ho * a.Wo));
-    a.fd_wo = make_fastdiv((unsigned)a.Wo);
-    const int ks = stem_runs_ks(a);
-    if (ks && stem_stream_ok(a)) {
-        const int ntiles = (a.M + 63) / 64;
-        int blocks = 512;                              // two per CU
-        while (blocks > 8 && blocks / 2 >= ntiles) blocks /= 2;
-        with_fmt(a.f16, [&](auto f) {
-            using F = decltype(f);
-            if (ks == 7) hipLaunchKernelGGL((igemm_bf16_stem_stream_u8_kernel<7, F>), dim3(blocks), dim3(256), 0, s, a, ntiles, in);
-            else hipLaunchKernelGGL((igemm_bf16_stem_stream_u8_kernel<3, F>), dim3(blocks), dim3(256), 0, s, a, ntiles, in);
-            return 0;
-        });
-        return hipGetLastError();
-    }
-    const dim3 grid(((a.M + 127) / 128) * ((a.N + 63) / 64));
-    with_fmt(a.f16, [&](auto f) {
-        using F = decltype(f);
-        if (ks == 7) hipLaunchKernelGGL((igemm_bf16_stem_u8_kernel<7, 128, F>), grid, dim3(256), 0, s, a, in);
-        else if (ks == 3) hipLaunchKernelGGL((igemm_bf16_stem_u8_kernel<3, 128, F>), grid, dim3(256), 0, s, a, in);
-        else hipLaunchKernelGGL(igemm_bf16_smallc_u8_kernel<F>, grid, dim3(256), 0, s, a, in);
-        return 0;
-    });
-    return hipGetLastError();
 }
 
 static constexpr int rh_lds_halves(int cw, int tm, int tn) { return (128 * tm + 96 * tn) * cw < 9216 ? 9216 : (128 * tm + 96 * tn) * cw; }

@@ -4,7 +4,8 @@
 //
 // Covers every dense contraction on the hot path: the HRNet / CPN 3x3, 1x1 and 7x7 convolutions with
 // folded BatchNorm (+ReLU, +residual) — pose_hrnet.py:66-136, networks/resnet.py:58-93 — and the
-// lifter's nn.Linear layers (+bias, +GELU, +residual) — pose_dformer.py:15-59.
+// lifter's nn.Linear layers (+bias, +GELU, +residual) — pose_dformer.py:15-59.  (The Cin = 3 stem convs, which launch_gemm_f32
+// forwards: igemm_stem.hip.)
 //
 // Design (MI355X-first, not a translation of a warp-32 tiling):
 //   * activations are NHWC, weights are pre-packed [N][Kpad] with k = (kh, kw, ci): both MFMA operands
@@ -31,7 +32,6 @@
 #include <stdlib.h>
 
 #include "kernels.h"
-#include "pixel_rule.h"
 
 namespace capf {
 
@@ -659,352 +659,6 @@ __global__ __launch_bounds__(256) void igemm_f32_group_kernel(GroupArgs ga) {
 }
 
 // =====================================================================================================
-// Small-Cin (stem: Cin = 3, k = 3 or 7) variant: K is gathered element-wise into registers, staged with
-// ds_write_b128 into a padded LDS tile (pitch 36 floats: conflict-free b128 without a swizzle).  0.3 % of
-// the FLOPs of the path; kept simple.
-// =====================================================================================================
-static constexpr int PITCH = 36;
-
-//
-// U8 (every Cin = 3 kernel of this file and of igemm_bf16.hip): the image is the uint8 BGR crop itself (pixel_rule.h U8Input: normalisation,
-// BGR -> RGB, mirror and the flip-test frame mapping of capf_preprocess happen in this load).  The form differs from the float one ONLY in how
-// a tap's value reaches the register that the float form fills from p.A: same tile, same K order, same MFMA sequence, hence the same bits as
-// the float kernel on capf_preprocess's output.
-//   * values: a per-block table tab[c][u] = pixel_rule(u, c) in LDS (3 KiB, 768 evaluations per block -- against one IEEE division per tap
-//     and pixel, 27 / 147 per output pixel, in the gather): the same function as preprocess_images_kernel's, so the same bits by construction;
-//   * bytes: one byte load per tap (global_load_ubyte in the ISA), each with its own validity -- a run of 9 / 21 bytes starts at any byte
-//     offset of a base of any alignment, runs backwards pixel by pixel in a mirrored frame, and the first / last run of the tensor would
-//     start before / end behind it: dword loads would have to be split at both ends or read outside the tensor.  An invalid tap reads byte 0
-//     and drops it, so no load leaves [img, img + Bsrc H W 3) and none is behind a branch; padding is 0.0f AFTER normalisation;
-//   * GemmArgs keeps its layout: the descriptor is an extra argument of the *_u8_kernel entry points alone (p.A is not read).
-template <int BM, int BN, int WM, int WN, bool U8>
-__device__ __forceinline__ void igemm_f32_smallc_body(const GemmArgs& p, const U8Input* u8) {
-    constexpr int WAVES_N = BN / WN;
-    constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int RA = BM / 32, RB = BN / 32;
-    static_assert((BM / WM) * (BN / WN) == 4, "4 waves per block");
-    __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * PITCH + (U8 ? U8_TAB : 0)];
-    float* As = lds;
-    float* Bs = lds + BM * PITCH;
-    const float* tab = lds + (BM + BN) * PITCH;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (U8) {
-        u8_fill_table(lds + (BM + BN) * PITCH, *u8, tid, 256);
-        __syncthreads();
-    }
-    const int nbn = (p.N + BN - 1) / BN;
-    const int tile_m = blockIdx.x / nbn, tile_n = blockIdx.x - tile_m * nbn;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const int srow = tid >> 3, kq = (tid & 7) * 4;
-
-    long a_base[RA];
-    int a_h0[RA], a_w0[RA], a_f[RA];                 // (a_f: the frame, read by the U8 form alone)
-#pragma unroll
-    for (int i = 0; i < RA; ++i) {
-        const int m = m0 + srow + 32 * i;
-        if (m < p.M) {
-            const int b = fast_div(m, p.fd_hw), rem = m - b * p.Ho * p.Wo;
-            const int ho = fast_div(rem, p.fd_wo), wo = rem - ho * p.Wo;
-            a_base[i] = (long)b * p.H * p.W * p.Cin;
-            a_h0[i] = ho * p.stride - p.pad;
-            a_w0[i] = wo * p.stride - p.pad;
-            a_f[i] = b;
-        } else {
-            a_base[i] = 0;
-            a_h0[i] = -(1 << 20);
-            a_w0[i] = 0;
-            a_f[i] = 0;
-        }
-    }
-    f32x4 a_reg[RA], b_reg[RB];
-    auto load_chunk = [&](int c) {
-        const int k = c * BK + kq;
-#pragma unroll
-        for (int i = 0; i < RA; ++i) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int ke = k + e;
-                const int t = ke / p.Cin, c1 = ke - t * p.Cin;
-                const int kh = t / p.ks, kw = t - kh * p.ks;
-                const int hi = a_h0[i] + kh, wi = a_w0[i] + kw;
-                const bool ok = ke < p.K && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-                if (U8) {
-                    v[e] = u8_value(tab, ok, u8_load(*u8, ok, u8_pixel(*u8, a_f[i], hi, wi, p.H, p.W), c1), ok ? c1 : 0);
-                } else if (ok)
-                    v[e] = p.A[a_base[i] + ((long)hi * p.W + wi) * p.Cin + c1];
-            }
-            a_reg[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            const int n = n0 + srow + 32 * i;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (n < p.N) v = *reinterpret_cast<const f32x4*>(p.Wp + (long)n * p.Kpad + c * BK + kq);
-            b_reg[i] = v;
-        }
-    };
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    const int wm0 = (wave / WAVES_N) * WM, wn0 = (wave % WAVES_N) * WN;
-    const int frow = lane & 31, fk = (lane >> 5) * 4;
-    const int nchunks = p.Kpad / BK;
-    load_chunk(0);
-    for (int c = 0; c < nchunks; ++c) {
-#pragma unroll
-        for (int i = 0; i < RA; ++i) *reinterpret_cast<f32x4*>(&As[(srow + 32 * i) * PITCH + kq]) = a_reg[i];
-#pragma unroll
-        for (int i = 0; i < RB; ++i) *reinterpret_cast<f32x4*>(&Bs[(srow + 32 * i) * PITCH + kq]) = b_reg[i];
-        __syncthreads();
-        if (c + 1 < nchunks) load_chunk(c + 1);
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 8) {
-            f32x4 af[TM], bf[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-                af[i] = *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + frow) * PITCH + kk + fk]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                bf[j] = *reinterpret_cast<const f32x4*>(&Bs[(wn0 + j * 32 + frow) * PITCH + kk + fk]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][e], bf[j][e], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn0 + j * 32 + (lane & 31);
-        const bool n_ok = n < p.N;
-        const float bv = (p.bias && n_ok) ? p.bias[n] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (n_ok && m < p.M) {
-                    float v = acc[i][j][r] + bv;
-                    if (p.res) v += p.res[rowmap(p.rmap, m) + n];
-                    if (p.act == ACT_RELU) v = relu_f(v);
-                    if (p.out_bf16) {
-                        reinterpret_cast<unsigned short*>(p.out)[rowmap(p.omap, m) + n] = to_bf16(v);
-                    } else
-                    p.out[rowmap(p.omap, m) + n] = v;
-                }
-            }
-        }
-    }
-}
-
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256) void igemm_f32_smallc_kernel(GemmArgs p) {
-    igemm_f32_smallc_body<BM, BN, WM, WN, false>(p, nullptr);
-}
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256) void igemm_f32_smallc_u8_kernel(GemmArgs p, U8Input in) {
-    igemm_f32_smallc_body<BM, BN, WM, WN, true>(p, &in);
-}
-
-// =====================================================================================================
-// The 3x3 / stride-2 fp32 stem as a persistent streaming kernel -- the fp32 twin of igemm_bf16_stem_stream_kernel
-// (igemm_bf16.hip, where the scheme is described): weights staged once per block, the next 64-pixel tile's runs (for a fixed
-// (pixel, kh) the 9 input floats are contiguous in the NHWC image: two 16-byte loads + one dword, raw buffer loads with
-// out-of-range offsets instead of branches) in flight across the MFMAs and stores of the current tile, LDS-transposed 16-byte
-// stores (128 B contiguous per row), XCD-contiguous tile walk.  K in LDS = (kh, 12): 9 values + 3 zeros per kh, 40 staged
-// floats per row.  The element-wise kernel above moved 2.0 TB/s at batch 64 (155 us for 268 MB out + 50 MB in).
-// =====================================================================================================
-// U8 (see igemm_f32_smallc_body): issue() requests the run's 9 bytes one by one -- they stay in flight across the previous tile's MFMAs and
-// stores exactly as the float form's three loads do -- and the table turns them into the float run just before put_run.  Every byte carries
-// its own validity, so the float form's patch of the runs that start before the tensor has nothing to do here.
-template <int KS, bool U8>
-__device__ __forceinline__ void igemm_f32_stem_stream_body(const GemmArgs& p, const int ntiles, const U8Input* u8) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int BM = 64, BN = 64;
-    constexpr int RUN = KS * 3, NX4 = RUN / 4;      // 9 floats = 2 quads + 1 dword
-    static_assert(RUN % 4 == 1, "one dword behind the quads (a 16-byte load with dead upper dwords costs a vmcnt(0))");
-    constexpr int PKH = (RUN + 3) / 4 * 4;          // floats per kh in LDS (12)
-    constexpr int KP = (KS * PKH + 7) / 8 * 8;      // staged K (40)
-    constexpr int SP = KP + 4;                      // floats per LDS row: conflict-free b128 reads
-    constexpr int EPS = 36;
-    constexpr unsigned OOB = 0x80000000u;
-    static_assert(BM * KS <= 256, "one run per thread");
-    __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * SP + 4 * 32 * EPS + (U8 ? U8_TAB : 0)];
-    float* As = lds;
-    float* Bs = lds + BM * SP;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float* ep = lds + (BM + BN) * SP + wave * (32 * EPS);
-    const float* tab = lds + (BM + BN) * SP + 4 * 32 * EPS;
-    if (U8) u8_fill_table(lds + (BM + BN) * SP + 4 * 32 * EPS, *u8, tid, 256);     // (the barrier behind the first put_run's comes before its first lookup: below)
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const long total = (long)(p.M / (p.Ho * p.Wo)) * p.H * p.W * 3;              // floats of the image tensor (< 2^29: launcher)
-    const rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(U8 ? (void*)p.out : (void*)p.A, 0, U8 ? 0u : (unsigned)(total * 4), 0x00020000);
-    const rsrc_t rs_bias = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)p.bias : (void*)p.out, 0,
-                                                             p.bias ? (unsigned)p.N * 4u : 0u, 0x00020000);
-    auto ldq = [&](rsrc_t r, unsigned off) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0)); };
-    auto ldd = [&](rsrc_t r, unsigned off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0)); };
-    auto put_run = [&](float* dst, const f32x4 (&q)[NX4], float last, unsigned mask, int kh) {
-        auto val = [&](int e) { return e < NX4 * 4 ? q[e >> 2][e & 3] : (e == NX4 * 4 ? last : 0.f); };
-#pragma unroll
-        for (int g = 0; g < PKH / 4; ++g) {
-            f32x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (4 * g + e < RUN && ((mask >> (4 * g + e)) & 1u)) ? val(4 * g + e) : 0.f;
-            *reinterpret_cast<f32x4*>(dst + kh * PKH + 4 * g) = v;
-        }
-        if (KP > KS * PKH && kh == KS - 1) *reinterpret_cast<f32x4*>(dst + KS * PKH) = f32x4{0.f, 0.f, 0.f, 0.f};
-    };
-    {   // weights, once per block: runs of the fp32 pack [N][Kpad], K order (kh, kw, c)
-        const rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wp, 0, (unsigned)p.N * (unsigned)p.Kpad * 4u, 0x00020000);
-        for (int t = tid; t < BN * KS; t += 256) {
-            const int kh = t / BN, n = t - kh * BN;
-            const unsigned wo = n < p.N ? (unsigned)(n * p.Kpad + kh * RUN) * 4u : OOB;
-            f32x4 q[NX4];
-#pragma unroll
-            for (int x = 0; x < NX4; ++x) q[x] = ldq(rs_w, n < p.N ? wo + 16u * x : OOB);
-            const float last = ldd(rs_w, n < p.N ? wo + 16u * NX4 : OOB);
-            put_run(Bs + n * SP, q, last, (1u << RUN) - 1u, kh);
-        }
-    }
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-    const int per_xcd = (ntiles + 7) >> 3;
-    const int t_end = min(ntiles, (xcd + 1) * per_xcd);
-    int tile = xcd * per_xcd + slot;
-
-    f32x4 q[NX4];
-    float qlast;
-    unsigned mask;
-    unsigned raw[RUN];                               // U8: the run's bytes, (kw, c) order like the float run
-    const int t_run = tid % (BM * KS);              // (threads beyond the 192 runs repeat one: same loads, same LDS bytes)
-    const int r_kh = t_run / BM, r_row = t_run - r_kh * BM;
-    auto issue = [&](int tl) {
-        const int m = tl * BM + r_row;
-        bool ok = tl < t_end && m < p.M;
-        const int mm = ok ? m : 0;
-        const int b = fast_div(mm, p.fd_hw), rem = mm - b * p.Ho * p.Wo;
-        const int ho = fast_div(rem, p.fd_wo), wo = rem - ho * p.Wo;
-        const int hi = ho * p.stride - p.pad + r_kh, wi0 = wo * p.stride - p.pad;
-        ok = ok && (unsigned)hi < (unsigned)p.H;
-        const int o = ((b * p.H + hi) * p.W + wi0) * 3;
-        const int lo = max(0, -wi0), hn = max(lo, min(KS, p.W - wi0));
-        mask = ok ? (((1u << (3 * hn)) - 1u) & ~((1u << (3 * lo)) - 1u)) : 0u;
-        if (U8) {
-#pragma unroll
-            for (int kw = 0; kw < KS; ++kw) {
-                const bool v = (mask >> (3 * kw)) & 1u;
-                const long px = u8_pixel(*u8, b, hi, wi0 + kw, p.H, p.W);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) raw[3 * kw + c] = u8_load(*u8, v, px, c);
-            }
-            return;
-        }
-#pragma unroll
-        for (int x = 0; x < NX4; ++x) q[x] = ldq(rs_in, (ok && o + 4 * x >= 0) ? (unsigned)(o + 4 * x) * 4u : OOB);
-        qlast = ldd(rs_in, (ok && o + 4 * NX4 >= 0) ? (unsigned)(o + 4 * NX4) * 4u : OOB);
-    };
-    auto decode = [&]() {                            // U8: bytes -> the float run (masked elements are zeroed by put_run)
-#pragma unroll
-        for (int e = 0; e < RUN; ++e) {
-            const float v = tab[(e % 3) * 256 + raw[e]];
-            if (e < NX4 * 4) q[e >> 2][e & 3] = v; else qlast = v;
-        }
-    };
-    const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * 32;
-    const int frow = lane & 31, fhalf = lane >> 5, fk = fhalf * 4;
-    const int er = lane >> 3, ec = (lane & 7) * 4;          // epilogue: 8 lanes x 16 B = one 128-B row of the wave's 32 channels
-    const f32x4 bv = ldq(rs_bias, (unsigned)(wn0 + ec) * 4u);
-
-    issue(tile);
-    {   // four dropped stores: the loop is entered with the same "loads, then four stores" in flight as its back edge leaves
-        const rsrc_t rs_none = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, 0u, 0x00020000);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)                 // (distinct offsets: identical stores would be merged into one)
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, rs_none, OOB + 16u * k, 0, 0);
-    }
-    if (U8) __syncthreads();                         // the value table is complete
-    for (; tile < t_end; tile += nslots) {
-        const int m0 = tile * BM;
-        if (U8) decode();
-        put_run(As + r_row * SP, q, qlast, mask, r_kh);
-        const int ho_max = p.pad / p.stride;
-        if (!U8 && m0 < (ho_max + 1) * p.Wo) {      // frame 0, input row 0, window left of the image: negative tensor offsets
-            __syncthreads();
-            const int nw = min(p.Wo, (p.pad + p.stride - 1) / p.stride);
-            for (int idx = tid; idx < (ho_max + 1) * nw * PKH; idx += 256) {
-                const int e = idx % PKH, r = idx / PKH, wo = r % nw, ho = r / nw;
-                const int kh = p.pad - ho * p.stride, m = ho * p.Wo + wo;
-                if (kh >= 0 && kh < KS && m >= m0 && m < m0 + BM) {
-                    const int wi = wo * p.stride - p.pad + e / 3;
-                    float v = 0.f;
-                    if (e < RUN && (unsigned)wi < (unsigned)p.W) v = p.A[wi * 3 + e % 3];
-                    As[(m - m0) * SP + kh * PKH + e] = v;
-                }
-            }
-        }
-        __syncthreads();
-        issue(tile + nslots);
-
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < KP; kk += 8) {
-            const f32x4 af = *reinterpret_cast<const f32x4*>(&As[(wm0 + frow) * SP + kk + fk]);
-            const f32x4 bf = *reinterpret_cast<const f32x4*>(&Bs[(wn0 + frow) * SP + kk + fk]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[e], af[e], acc, 0, 0, 0);
-        }
-        // transposed accumulator: lane = row m (lane & 31), register 4 g + e = channel 8 g + 4 fhalf + e
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<f32x4*>(&ep[frow * EPS + 8 * g + 4 * fhalf]) = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-        __builtin_amdgcn_wave_barrier();
-        const rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out + (long)m0 * p.omap.S1 + p.omap.off), 0, 0x7FFFFF00u, 0x00020000);
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const int row = h * 8 + er, ml = wm0 + row, nl = wn0 + ec;
-            f32x4 x = *reinterpret_cast<const f32x4*>(&ep[row * EPS + ec]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                x[e] += bv[e];
-                if (p.act == ACT_RELU) x[e] = relu_f(x[e]);
-            }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), rs_out,
-                                                   (m0 + ml < p.M && nl < p.N) ? (unsigned)(ml * (int)p.omap.S1 + nl) * 4u : OOB, 0, 0);
-        }
-        __syncthreads();
-    }
-#endif
-}
-
-template <int KS>
-__global__ __launch_bounds__(256, 2) void igemm_f32_stem_stream_kernel(GemmArgs p, int ntiles) {
-    igemm_f32_stem_stream_body<KS, false>(p, ntiles, nullptr);
-}
-template <int KS>
-__global__ __launch_bounds__(256, 2) void igemm_f32_stem_stream_u8_kernel(GemmArgs p, int ntiles, U8Input in) {
-    igemm_f32_stem_stream_body<KS, true>(p, ntiles, &in);
-}
-
-static bool stem_stream_f32_ok(const GemmArgs& a) {
-    static const int on = [] { const char* e = diag_env("CAPF_STEM_STREAM"); return e ? atoi(e) : 1; }();        // A/B runs only
-    const long total = (long)(a.M / (a.Ho * a.Wo)) * a.H * a.W * 3;
-    return on && a.conv && a.Cin == 3 && a.ks == 3 && a.pad == 1 && a.K == 27 && a.Kpad >= 2 * 9 + 12 && !a.res && !a.out_bf16 &&
-           !a.rscale && a.act != ACT_GELU && a.omap.G == 1 && a.rmap.G <= 1 && a.N <= 64 && a.N % 4 == 0 && a.omap.S1 % 4 == 0 &&
-           a.omap.off % 4 == 0 && total < (1L << 29) && a.Wo >= 4;
-}
-
-// =====================================================================================================
 // host side: tile selection + launch
 // =====================================================================================================
 FastDiv make_fastdiv(unsigned d) {
@@ -1048,12 +702,6 @@ static TileCfg pick_tile(const GemmArgs& a) {
         if (best == 0.0 || cost < best) { best = cost; pick = c.cfg; }
     }
     return pick;
-}
-
-// compute_dtype = bf16 (the op writes bf16): the stem runs on the bf16 MFMA too (igemm_bf16.hip); CAPF_STEM_BF16=0 keeps it fp32
-static bool stem_on_bf16(const GemmArgs& a) {
-    static const int on = [] { const char* e = diag_env("CAPF_STEM_BF16"); return e ? atoi(e) : 1; }();
-    return on && gemm_bf16_smallc_ok(a);
 }
 
 // The pointwise kernel or the two-fp16-piece GEMM for a 1x1 conv that both take?  A function of the conv alone (every schedule must pick
@@ -1153,7 +801,7 @@ F32Route gemm_f32_route(const GemmArgs& a) {
     if (gemm_f32h2g_ok(a)) return {F32Path::H2G, 0};
     if (worth_splitting(a)) return {F32Path::SPLITK_GROUP, 0};
     if (gemm_f32_rows_splitk(a)) return {F32Path::ROWS_SPLITK, 0};
-    if (a.conv && a.Cin % 4 != 0) return {stem_on_bf16(a) ? F32Path::STEM_BF16 : stem_stream_f32_ok(a) ? F32Path::STEM_STREAM : F32Path::SMALLC, 0};
+    if (a.conv && a.Cin % 4 != 0) return {F32Path::STEM, 0};
     return {F32Path::TILE, pick_tile(a)};
 }
 
@@ -1172,9 +820,7 @@ const char* gemm_f32_kernel_name(const GemmArgs& a) {
         case F32Path::H2G: return gemm_f32h2g_kernel_name(a, false);
         case F32Path::SPLITK_GROUP: return "igemm_f32_group";
         case F32Path::ROWS_SPLITK: return "igemm_f32_rows_splitk";
-        case F32Path::STEM_BF16: return gemm_bf16_smallc_kernel_name(a);
-        case F32Path::STEM_STREAM: return "igemm_f32_stem_stream<w4,64x64>";
-        case F32Path::SMALLC: return "igemm_f32_smallc<w4,128x64>";
+        case F32Path::STEM: return gemm_stem_kernel_name(a, false);
         default: return buf[r.tile][a.conv ? 1 : 0];
     }
 }
@@ -1305,6 +951,7 @@ hipError_t launch_gemm_f32(const GemmArgs& a_in, hipStream_t s) {
             else hipLaunchKernelGGL(igemm_f32_rows_splitk_kernel<false>, dim3(tiles * a.splits), dim3(256), 0, s, a);
             return hipGetLastError();
         }
+        case F32Path::STEM: return launch_gemm_stem(a_in, nullptr, s);
         default: break;
     }
     a.split_ws = nullptr; a.split_cnt = nullptr;                           // (the in-kernel reduction belongs to the grouped / split kernels)
@@ -1320,74 +967,11 @@ hipError_t launch_gemm_f32(const GemmArgs& a_in, hipStream_t s) {
         if (span * 4.0 >= 4.0e9) return hipErrorInvalidValue;
     }
     if (a.conv && !prep_conv(a)) return hipErrorInvalidValue;
-    switch (r.path) {
-        case F32Path::STEM_BF16: return launch_gemm_bf16_smallc(a, s);
-        case F32Path::STEM_STREAM: {
-            const int ntiles = (a.M + 63) / 64;
-            int blocks = 512;                          // two per CU
-            while (blocks > 8 && blocks / 2 >= ntiles) blocks /= 2;
-            hipLaunchKernelGGL((igemm_f32_stem_stream_kernel<3>), dim3(blocks), dim3(256), 0, s, a, ntiles);
-            return hipGetLastError();
-        }
-        case F32Path::SMALLC: {
-            dim3 grid(((a.M + 127) / 128) * ((a.N + 63) / 64)), block(256);
-            hipLaunchKernelGGL((igemm_f32_smallc_kernel<128, 64, 64, 32>), grid, block, 0, s, a);
-            return hipGetLastError();
-        }
-        default: break;
-    }
     switch (r.tile) {
         case W4_128x64: return launch_cfg<4, 128, 64, 64, 32, 2>(a, s);
         case W4_64x64: return launch_cfg<4, 64, 64, 32, 32, 3>(a, s);
         case W4_128x128: return launch_cfg<4, 128, 128, 64, 64, 2>(a, s);
         case W4_256x32: return launch_cfg<4, 256, 32, 64, 32, 2>(a, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-// ---- the stem conv from the uint8 crop (pixel_rule.h U8Input): the route launch_gemm_f32 takes for the same problem -- no threshold of its
-// own -- and the U8 form of that route's kernel; a.A is not read.  Anything but a Cin = 3 conv whose frame count matches the descriptor's
-// mode is an error, never another kernel
-bool gemm_u8_ok(const GemmArgs& a, const U8Input& in) {
-    if (!a.conv || a.Cin != 3 || a.M <= 0 || a.N <= 0 || a.Ho <= 0 || a.Wo <= 0 || a.M % (a.Ho * a.Wo) != 0) return false;
-    if (!in.img || in.Bsrc <= 0 || in.mode < 0 || in.mode > 2) return false;
-    return a.M / (a.Ho * a.Wo) == (in.mode == 2 ? 2 * in.Bsrc : in.Bsrc);
-}
-
-const char* gemm_f32_u8_kernel_name(const GemmArgs& a) {
-    switch (gemm_f32_route(a).path) {
-        case F32Path::STEM_BF16: return gemm_bf16_smallc_u8_kernel_name(a);
-        case F32Path::STEM_STREAM: return "igemm_f32_stem_stream<w4,64x64,u8>";
-        case F32Path::SMALLC: return "igemm_f32_smallc<w4,128x64,u8>";
-        default: return "";
-    }
-}
-
-hipError_t launch_gemm_f32_u8(const GemmArgs& a_in, const U8Input& in, hipStream_t s) {
-    if (!gemm_u8_ok(a_in, in) || a_in.Kpad % BK != 0 || a_in.splits > 1) return hipErrorInvalidValue;
-    const F32Route r = gemm_f32_route(a_in);
-    GemmArgs a = a_in;
-    a.A = nullptr;
-    a.split_ws = nullptr; a.split_cnt = nullptr;
-    a.splits = 1; a.cps = a.Kpad / BK; a.split_stride = 0;
-    if (a.rs_div <= 0) a.rs_div = 1;
-    if (a.omap.G == 1 && (double)a.M * (double)a.omap.S1 >= 4.0e9) return hipErrorInvalidValue;
-    if (a.res && a.rmap.G == 1 && (double)a.M * (double)a.rmap.S1 >= 4.0e9) return hipErrorInvalidValue;
-    if (!prep_conv(a)) return hipErrorInvalidValue;
-    switch (r.path) {
-        case F32Path::STEM_BF16: return launch_gemm_bf16_smallc_u8(a, in, s);
-        case F32Path::STEM_STREAM: {
-            const int ntiles = (a.M + 63) / 64;
-            int blocks = 512;                          // two per CU
-            while (blocks > 8 && blocks / 2 >= ntiles) blocks /= 2;
-            hipLaunchKernelGGL((igemm_f32_stem_stream_u8_kernel<3>), dim3(blocks), dim3(256), 0, s, a, ntiles, in);
-            return hipGetLastError();
-        }
-        case F32Path::SMALLC: {
-            dim3 grid(((a.M + 127) / 128) * ((a.N + 63) / 64)), block(256);
-            hipLaunchKernelGGL((igemm_f32_smallc_u8_kernel<128, 64, 64, 32>), grid, block, 0, s, a, in);
-            return hipGetLastError();
-        }
         default: return hipErrorInvalidValue;
     }
 }

@@ -274,9 +274,9 @@ bool gemm_f32_groupable(const GemmArgs& a);
 bool gemm_f32_rows_splitk(const GemmArgs& a);        // rows-mode GEMM that launch_gemm_f32 splits along K (few tiles, long K, scratch lent)
 hipError_t launch_gemm_f32_group(const GemmArgs* list, int n, hipStream_t s);
 // The path launch_gemm_f32 takes for a problem, in its order: the pointwise kernel, the two-fp16-piece GEMM (igemm_f32h2.hip), a lone conv
-// split along K on the grouped kernel, a rows-mode GEMM split along K, the Cin = 3 stem (bf16 MFMA / streaming / small-C kernel), the tile
+// split along K on the grouped kernel, a rows-mode GEMM split along K, the Cin = 3 stem (gemm_stem_route below picks its kernel), the tile
 // kernel (tile = its configuration).  One decision: the launcher switches on it, gemm_f32_kernel_name names it, the engine counts by it
-enum class F32Path { PW, H2G, SPLITK_GROUP, ROWS_SPLITK, STEM_BF16, STEM_STREAM, SMALLC, TILE };
+enum class F32Path { PW, H2G, SPLITK_GROUP, ROWS_SPLITK, STEM, TILE };
 struct F32Route { F32Path path; int tile; };
 F32Route gemm_f32_route(const GemmArgs& a);
 const char* gemm_f32_kernel_name(const GemmArgs& a);   // what rocprofv3 calls the launch of launch_gemm_f32
@@ -411,17 +411,20 @@ struct H2TrainW {
     int N, K, ld, tile_start, max_off, pad_;
 };
 hipError_t launch_pack_f32h2_train(const H2TrainW* tab_dev, int n, int tiles, float* base, int* maxima, long maxima_elems, hipStream_t s);
-bool gemm_bf16_smallc_ok(const GemmArgs& a);            // the stem conv (Cin = 3) with a bf16 result
-hipError_t launch_gemm_bf16_smallc(const GemmArgs& a, hipStream_t s);
-const char* gemm_bf16_smallc_kernel_name(const GemmArgs& a);
-// The stem conv straight from the uint8 BGR crop (pixel_rule.h U8Input; GemmArgs::A is not read): launch_gemm_f32's route for the same
-// problem, the U8 form of that route's kernel, bit-identical to the float kernel on launch_preprocess's output.  The names are the float
-// kernels' with a ",u8" tag.  launch_gemm_bf16_smallc_u8: the 16-bit stems (what launch_gemm_f32_u8 forwards an out_bf16 problem to)
-bool gemm_u8_ok(const GemmArgs& a, const U8Input& in);
-hipError_t launch_gemm_f32_u8(const GemmArgs& a, const U8Input& in, hipStream_t s);
-const char* gemm_f32_u8_kernel_name(const GemmArgs& a);
-hipError_t launch_gemm_bf16_smallc_u8(const GemmArgs& a, const U8Input& in, hipStream_t s);
-const char* gemm_bf16_smallc_u8_kernel_name(const GemmArgs& a);
+// The small-Cin stem conv (igemm_stem.hip; what gemm_f32_route calls F32Path::STEM: a conv with Cin % 4 != 0, and capf_op_conv_16's
+// Cin % 8 != 0 branch): fp32 image and fp32 pack in, fp32 or -- out_bf16 -- 16-bit result.  One decision, a function of the problem alone:
+// the 16-bit kernels where they take the problem (element-wise gather / one run per (pixel, kh) / the persistent streaming form of that),
+// else the fp32 ones (streaming / element-wise gather).  ks: 7 / 3 for the run-based kernels
+enum class StemKernel { F32_SMALLC, F32_STREAM, B16_SMALLC, B16_RUNS, B16_STREAM };
+inline bool stem_is_16bit(StemKernel k) { return k >= StemKernel::B16_SMALLC; }
+struct StemRoute { StemKernel kernel; int ks; };
+StemRoute gemm_stem_route(const GemmArgs& a);
+// in == nullptr: the fp32 image at GemmArgs::A.  Otherwise the uint8 BGR crop itself (pixel_rule.h U8Input; GemmArgs::A is not read): the same
+// route, the same grid, the U8 form of the same kernel -- bit-identical to the float form on launch_preprocess's output; its name is the float
+// kernel's with a ",u8" tag
+bool gemm_stem_ok(const GemmArgs& a, const U8Input* in);
+hipError_t launch_gemm_stem(const GemmArgs& a, const U8Input* in, hipStream_t s);
+const char* gemm_stem_kernel_name(const GemmArgs& a, bool u8);
 hipError_t launch_pack_linear(const float* w, float* Wp, int N, int K, int Kpad, hipStream_t s);
 // quad-interleaved pack for the fused lifter kernels: Wq[(k / 4) * Ntot + n0 + n][k % 4] = w[n][k]  (K % 4 == 0): lane n of a
 // wave reads the 16-byte quad next to lane n - 1's instead of a row K floats away

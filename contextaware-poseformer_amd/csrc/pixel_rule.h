@@ -1,6 +1,6 @@
 // N1: the normalisation rule of the input image (data_prefetcher.preload, ContextPose/mvn/datasets/utils.py:45-50) as __host__ __device__
-// code, written once: preprocess_images_kernel expands a uint8 crop with it, the uint8 forms of the stem kernels (igemm_f32.hip,
-// igemm_bf16.hip: U8) fill their per-block value table with it, and capf_input_rule_host evaluates it on the host -- as warp_rule.h shares
+// code, written once: preprocess_images_kernel expands a uint8 crop with it, the uint8 forms of the stem kernels (igemm_stem.hip:
+// U8) fill their per-block value table with it, and capf_input_rule_host evaluates it on the host -- as warp_rule.h shares
 // the crop's coordinate rule.
 //
 // Every step is a single rounded fp32 operation (contraction off, IEEE division), in the order of the torch expressions as they run on a

@@ -10,7 +10,10 @@ The one bound that is not "equal" is the suite's bound for fp32 convs against fp
 import contextlib
 import copy
 import functools
+import hashlib
 import io
+import json
+import os
 import random
 
 import numpy as np
@@ -22,6 +25,7 @@ import small_geometry_cases as sg
 import workspace_guard as wg
 from capf import lib as capf
 from capf import synth
+from conftest import ROOT
 from test_gpu_workspace_hygiene import _inference_engine, _plan_model
 from test_u8_input import STEMS
 
@@ -146,11 +150,28 @@ def _random_pack(ks, cout):
     return wp, bias, w.double() * sc.view(-1, 1, 1, 1), wp.cpu()[:, :ks * ks * 3], bias.cpu()
 
 
+def _digest(t):
+    return hashlib.sha256(t.contiguous().cpu().view(torch.uint8).numpy().tobytes()).hexdigest()
+
+
+def _bits_key(dtype, ks, cout, H, W, bsrc, mode, act):
+    return f"{dtype},{ks},{cout},{H},{W},{bsrc},{mode},{act}"
+
+
+@functools.lru_cache(maxsize=None)
+def _stem_bits():
+    """sha256 of the float stem op's output bytes per case of the test below, recorded from the library as it stood before the five stem
+    kernels got a translation unit, a route and a launcher of their own (tests/golden/stem_bits.json: case keys and digests only)"""
+    with open(os.path.join(ROOT, "tests", "golden", "stem_bits.json")) as f:
+        return json.load(f)
+
+
 @pytest.mark.parametrize("dtype", [F32, BF16, F16], ids=["fp32", "bf16", "fp16"])
 @pytest.mark.parametrize("ks,cout", STEM_OPS, ids=[f"k{k}c{c}" for k, c in STEM_OPS])
 def test_u8_op_equals_the_float_op_on_preprocessed_images(dtype, ks, cout):
     """random weights with random BatchNorm, ReLU on / off; 9 x 11, 33 x 35 (several tiles, ragged last tile) and 64 x 48; 1 and 5 source
-    frames; modes 0 / 1 / 2.  fp32 outputs also against fp64 F.conv2d of the normalised image at 1e-6 of each output's sum of |terms|"""
+    frames; modes 0 / 1 / 2.  fp32 outputs also against fp64 F.conv2d of the normalised image at 1e-6 of each output's sum of |terms|.
+    The float op's own bits are the recorded ones (_stem_bits)"""
     wp, bias, w_fold, w_packed, bias_cpu = _random_pack(ks, cout)
     mean, std, backbone = _constants(ks)
     pad = ks // 2
@@ -174,6 +195,8 @@ def test_u8_op_equals_the_float_op_on_preprocessed_images(dtype, ks, cout):
                         want = capf.conv_nhwc(x, wp, bias, ks, 2, act)
                     else:
                         want = capf.conv_nhwc_16(x, wp, bias, ks, 2, act, dtype=dtype)
+                    assert _digest(want) == _stem_bits()[_bits_key(dtype, ks, cout, H, W, bsrc, mode, act)], \
+                        f"{ref_name}: {H}x{W} Bsrc {bsrc} mode {mode} act {act}: the float stem op's bits are not the recorded ones"
                     got = capf.op_conv_u8(view, wp, bias, ks, 2, act, mode, mean, std, dtype)
                     assert got.dtype == TORCH_DT[dtype]
                     compares += 1

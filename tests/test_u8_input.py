@@ -3,6 +3,7 @@ normalisation rule, the ABI surface, the argument checks that come before any la
 the ",u8" form of exactly the kernel the float stem op runs at the same shape, batch and dtype.  The kernels themselves:
 tests/test_gpu_u8_input.py."""
 import ctypes
+import json
 import os
 import re
 
@@ -156,10 +157,16 @@ def test_u8_op_names_the_u8_form_of_the_float_ops_kernel(dtype, ks, cout, H, W, 
     from capf import lib
     want = lib.stem_kernel_name(B, H, W, cout, ks, 2, dtype)
     assert want.endswith(">") and "u8" not in want
+    got_u8 = []
     for mode, bsrc in ((0, B), (1, B), (2, (B + 1) // 2)):
         frames = 2 * bsrc if mode == 2 else bsrc
         ref = lib.stem_kernel_name(frames, H, W, cout, ks, 2, dtype)
-        assert lib.op_conv_u8_kernel_name(bsrc, mode, H, W, cout, ks, 2, dtype) == ref[:-1] + ",u8>"
+        got_u8.append(lib.op_conv_u8_kernel_name(bsrc, mode, H, W, cout, ks, 2, dtype))
+        assert got_u8[-1] == ref[:-1] + ",u8>"
+    # ... and both are, character for character, the names recorded before the stem got one route and one name function
+    with open(os.path.join(ROOT, "tests", "golden", "stem_routes.json")) as f:
+        recorded = json.load(f)[f"{dtype},{ks},{cout},{H},{W},{B}"]
+    assert want == recorded["stem_kernel_name"] and got_u8 == recorded["op_conv_u8_kernel_name"]
 
 
 def test_the_enumerated_routes_are_the_five_stem_kernels():
