@@ -31,16 +31,6 @@ namespace capf {
 static constexpr int CPN_THREADS = 512, CPN_WAVES = CPN_THREADS / 64;
 static constexpr size_t CPN_RED_BYTES = 256;       // reduction scratch in front of the planes: CPN_WAVES (double, int) pairs + flags
 
-struct CpnLdF32 {
-    typedef float T;
-    static __device__ __forceinline__ float ld(const T* p) { return *p; }
-};
-template <class F>
-struct CpnLd16 {
-    typedef unsigned short T;
-    static __device__ __forceinline__ float ld(const T* p) { return F::widen(*p); }
-};
-
 size_t cpn_decode_lds_bytes(int H, int W) {
     if (H < 1 || W < 1 || H > (1 << 14) || W > (1 << 14)) return (size_t)-1;
     return CPN_RED_BYTES + (size_t)(H + 2 * CPN_BORDER) * (W + 2 * CPN_BORDER) * sizeof(double) + (size_t)H * W * sizeof(float);
@@ -76,10 +66,10 @@ template <> struct CpnArgsOf<true> { typedef CpnPairArgs type; };
 template <class L, bool PAIR>
 __device__ __forceinline__ float cpn_pixel(const typename L::T* __restrict__ z, const typename L::T* __restrict__ zm, const int p, const int W,
                                            const int C) {
-    const float zo = L::ld(z + (size_t)p * C);
+    const float zo = L::ld1(z + (size_t)p * C);
     if constexpr (PAIR) {
         const int x = p % W;                                             // row y = p / W: column W - 1 - x of it is pixel p - x + (W - 1 - x)
-        const float sum = zo + L::ld(zm + (size_t)(p - x + (W - 1 - x)) * C);       // (the sum rounded to fp32 ...
+        const float sum = zo + L::ld1(zm + (size_t)(p - x + (W - 1 - x)) * C);       // (the sum rounded to fp32 ...
         return 0.5f * sum;                                               //  ... then halved)
     } else {
         return zo;
@@ -253,13 +243,10 @@ template <bool PAIR>
 static hipError_t launch_cpn_decode_any(typename CpnArgsOf<PAIR>::type& a, hipStream_t s) {
     const size_t lds = cpn_decode_lds_bytes(a.H, a.W);
     if (!a.heat || !a.kcrop || a.B < 1 || a.J < 1 || a.J > a.C || a.C > MAX_JOINTS || lds > CPN_LDS_LIMIT || (long)a.B * a.J >= (1L << 31) ||
-        (a.k2d && !a.to_image))
+        (a.k2d && !a.to_image) || a.dtype < CAPF_F32 || a.dtype > CAPF_F16)
         return hipErrorInvalidValue;
     cpn_decode_taps(a.g);
-    if (a.dtype == CAPF_F32) return launch_cpn_decode_t<CpnLdF32, PAIR>(a, lds, s);
-    if (a.dtype == CAPF_BF16) return launch_cpn_decode_t<CpnLd16<Bf16Fmt>, PAIR>(a, lds, s);
-    if (a.dtype == CAPF_F16) return launch_cpn_decode_t<CpnLd16<F16Fmt>, PAIR>(a, lds, s);
-    return hipErrorInvalidValue;
+    return with_map_loader(a.dtype, [&](auto l) { return launch_cpn_decode_t<decltype(l), PAIR>(a, lds, s); });
 }
 
 hipError_t launch_cpn_decode(CpnDecodeArgs a, hipStream_t s) { return launch_cpn_decode_any<false>(a, s); }

@@ -1693,18 +1693,25 @@ size_t capf_kp_head_scratch_bytes(int B, int H, int W, int C, int J, int backwar
 // a map's base address serves its widest load: 16 bytes of fp32, 8 of a 16-bit format
 static bool map_aligned(const void* map, int dtype) { return (reinterpret_cast<uintptr_t>(map) & (dtype == CAPF_F32 ? 15 : 7)) == 0; }
 
-static int kp_head_check(const void* map, int map_dtype, const float* weight, int B, int H, int W, int C, int J, int mode, float beta,
-                         const float* decode, const void* scratch, size_t scratch_bytes, int backward) {
-    if (!map || !weight || !decode || !scratch) return CAPF_ERR_INVALID;
-    if (B < 1 || H < 1 || W < 1 || J < 1 || J > capf::MAX_JOINTS || C < 4 || C % 4 != 0 || C > capf::KP_MAX_CHANNELS) return CAPF_ERR_INVALID;
-    if (!(beta > 0.f) || !std::isfinite(beta)) return CAPF_ERR_INVALID;
-    if ((mode != 0 && mode != 1) || map_dtype < CAPF_F32 || map_dtype > CAPF_F16) return CAPF_ERR_INVALID;
-    if (backward && (mode != 1 || map_dtype != CAPF_F32)) return CAPF_ERR_UNSUPPORTED;
-    const size_t need = capf_kp_head_scratch_bytes(B, H, W, C, J, backward);
+// what the head's entries and capf_kp_heatmap_loss judge alike: the shape ...
+static int kp_shape_check(int B, int H, int W, int C, int J) { return capf::kp_shape_ok(B, H, W, C, J) ? CAPF_OK : CAPF_ERR_INVALID; }
+
+// ... and, after each entry's own tests, the scratch (`need`: what the entry's own size query answers) and the addresses
+static int kp_scratch_check(const void* map, int map_dtype, const void* scratch, size_t scratch_bytes, size_t need) {
     if (need == 0) return CAPF_ERR_UNSUPPORTED;                                             // (more than 2^24 pixels a frame, a grid beyond 2^31)
     if (scratch_bytes < need) return CAPF_ERR_INVALID;
     if (!map_aligned(map, map_dtype) || (reinterpret_cast<uintptr_t>(scratch) & 3)) return CAPF_ERR_INVALID;
     return CAPF_OK;
+}
+
+static int kp_head_check(const void* map, int map_dtype, const float* weight, int B, int H, int W, int C, int J, int mode, float beta,
+                         const float* decode, const void* scratch, size_t scratch_bytes, int backward) {
+    if (!map || !weight || !decode || !scratch) return CAPF_ERR_INVALID;
+    if (const int rc = kp_shape_check(B, H, W, C, J)) return rc;
+    if (!(beta > 0.f) || !std::isfinite(beta)) return CAPF_ERR_INVALID;
+    if ((mode != 0 && mode != 1) || map_dtype < CAPF_F32 || map_dtype > CAPF_F16) return CAPF_ERR_INVALID;
+    if (backward && (mode != 1 || map_dtype != CAPF_F32)) return CAPF_ERR_UNSUPPORTED;
+    return kp_scratch_check(map, map_dtype, scratch, scratch_bytes, capf_kp_head_scratch_bytes(B, H, W, C, J, backward));
 }
 
 // the record of a judged call: what the forward, the pair and the backward have in common, and the outputs of the two forward forms
@@ -1771,16 +1778,14 @@ int capf_kp_heatmap_loss(void* stream, const void* map_nhwc, int map_dtype, cons
                          float scale, float* loss, float* joint_loss, float* dweight, float* dbias, float* dmap, int accumulate, void* scratch,
                          size_t scratch_bytes) {
     if (!map_nhwc || !weight || !kcrop_gt || !decode || !loss || !scratch) return CAPF_ERR_INVALID;
-    if (B < 1 || H < 1 || W < 1 || J < 1 || J > capf::MAX_JOINTS || C < 4 || C % 4 != 0 || C > capf::KP_MAX_CHANNELS) return CAPF_ERR_INVALID;
+    if (const int rc = kp_shape_check(B, H, W, C, J)) return rc;
     if (!std::isfinite(decode[0]) || !std::isfinite(decode[2]) || decode[0] == 0.f || decode[2] == 0.f) return CAPF_ERR_INVALID;
     if (!(sigma > 0.f) || !std::isfinite(sigma) || std::ceil(3.f * sigma) > (float)capf::KP_LOSS_MAX_RADIUS) return CAPF_ERR_INVALID;
     if ((reduction != 0 && reduction != 1) || map_dtype < CAPF_F32 || map_dtype > CAPF_F16) return CAPF_ERR_INVALID;
     if (topk < 1 || !std::isfinite(scale) || (accumulate != 0 && accumulate != 1)) return CAPF_ERR_INVALID;
     if (dmap && map_dtype != CAPF_F32) return CAPF_ERR_UNSUPPORTED;
-    const size_t need = capf_kp_heatmap_loss_scratch_bytes(B, H, W, C, J, reduction);
-    if (need == 0) return CAPF_ERR_UNSUPPORTED;                                             // (more than 2^24 pixels a frame, a grid beyond 2^31)
-    if (scratch_bytes < need) return CAPF_ERR_INVALID;
-    if (!map_aligned(map_nhwc, map_dtype) || (reinterpret_cast<uintptr_t>(dmap) & 15) || (reinterpret_cast<uintptr_t>(scratch) & 3)) return CAPF_ERR_INVALID;
+    if (const int rc = kp_scratch_check(map_nhwc, map_dtype, scratch, scratch_bytes, capf_kp_heatmap_loss_scratch_bytes(B, H, W, C, J, reduction))) return rc;
+    if (reinterpret_cast<uintptr_t>(dmap) & 15) return CAPF_ERR_INVALID;
     capf::KpLossArgs a{};
     a.x = map_nhwc; a.dtype = map_dtype; a.wt = weight; a.bias = bias; a.gt = kcrop_gt; a.tw = target_weight;
     a.B = B; a.H = H; a.W = W; a.C = C; a.J = J;

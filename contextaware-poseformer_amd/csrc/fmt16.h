@@ -71,6 +71,31 @@ struct F16Fmt {
 // format a code stands for (0 bf16, 1 fp16)
 template <class Fn>
 inline auto with_fmt(int f16, Fn&& fn) { return f16 ? fn(F16Fmt{}) : fn(Bf16Fmt{}); }
+// How a kernel that takes an activation map in any capf_dtype (the keypoint head, CPN's decode) reads it: one element, or four consecutive
+// ones in one load, widened to fp32.  T is the element as it lies in memory; the loaders hold no arithmetic.
+typedef float fmt_f32x4 __attribute__((ext_vector_type(4)));
+struct MapLdF32 {
+    typedef float T;
+    static __device__ __forceinline__ fmt_f32x4 ld4(const T* p) { return *reinterpret_cast<const fmt_f32x4*>(p); }
+    static __device__ __forceinline__ float ld1(const T* p) { return *p; }
+};
+template <class F>
+struct MapLd16 {
+    typedef unsigned short T;
+    static __device__ __forceinline__ fmt_f32x4 ld4(const T* p) {
+        const uint2 u = *reinterpret_cast<const uint2*>(p);
+        return fmt_f32x4{F::lo(u.x), F::hi(u.x), F::lo(u.y), F::hi(u.y)};
+    }
+    static __device__ __forceinline__ float ld1(const T* p) { return F::widen(*p); }
+};
+// ... and its launch site: with_map_loader(dtype, [&](auto l) { using L = decltype(l); ... kernel<L, ..> ... }) runs the body for the loader
+// of a capf_dtype code (0 fp32, 1 bf16, 2 fp16; the caller has refused every other code)
+template <class Fn>
+inline auto with_map_loader(int dtype, Fn&& fn) {
+    if (dtype == 0) return fn(MapLdF32{});
+    if (dtype == 1) return fn(MapLd16<Bf16Fmt>{});
+    return fn(MapLd16<F16Fmt>{});
+}
 // a 16-bit kernel's reported name for a format: the bf16 name as it is, or with every "bf16" replaced by "f16" (interned, never freed)
 const char* fmt_kernel_name(const char* bf16_name, int f16);
 

@@ -752,6 +752,10 @@ hipError_t launch_keypoints_loss(const float* pred, const float* gt, const float
 constexpr int KP_MAX_CHANNELS = 512;
 constexpr int KP_MAX_SLABS = 64;             // forward: slabs of 256-pixel tiles per frame (a function of H * W alone)
 constexpr int KP_BW_SLABS = 8;               // backward: blocks per frame, each leaves one partial of dW
+// the ONE statement of the shapes the head takes (kp_geom, and the C ABI entries through engine.cpp's kp_shape_check)
+inline bool kp_shape_ok(int B, int H, int W, int C, int J) {
+    return B >= 1 && H >= 1 && W >= 1 && J >= 1 && J <= MAX_JOINTS && C >= 4 && C % 4 == 0 && C <= KP_MAX_CHANNELS;
+}
 struct KpGeom {                              // kp_geom: how a shape is cut; ok = false: a shape the kernels do not take
     int ntiles, slab_tiles, nslab, bw_tiles, nbw;
     size_t fwd_elems, stat_elems, bw_elems;  // floats of scratch: slab records | (max, sum, x, y) per (frame, joint) | dW partials

@@ -1,5 +1,5 @@
 // 2-D keypoint head on the highest-resolution context map (gfx950): HRNet's final_layer (a 1x1 conv, pose_hrnet.py:497-501) and the decode
-// of its heatmaps in one pass over the map, plus the backward of the integral decode.  include/capf.h (capf_kp_head_forward) has the rules.
+// of its heatmaps in one pass over the map, plus the two backwards (integral decode, heatmap loss).  include/capf.h (capf_kp_head_forward) has the rules.
 //
 // Map X [B, H, W, C] NHWC (fp32 / bf16 / fp16, widened on load), Wt [J, C] fp32, bias [J] fp32 or NULL; J <= 32, C % 4 == 0, C <= 512.
 // A logit is ONE fp32 expression, plain FMAs on the vector pipe (no matrix pipe: block scales shared across pixels would tie a frame's argmax
@@ -20,11 +20,17 @@
 //   (same row, column kp_mirror_col; 256-pixel tiles are not row-aligned, so it lies in another tile and is read from memory) and folds them into its
 //   OWN LDS column at swap[j]: zf = 0.5 (zo + zm).  No extra barrier, no runtime-indexed registers; the walk, the merges and the records are the
 //   single form's.  combine: the quarter shift's neighbours are fused logits recomputed from both frames; both sets of the [2, B, J, 2] stacks.
-// Backward (integral, fp32 map), four launches: slab + combine as above leave (max, sum, x, y) per (frame, joint) in the scratch; kp_bwd_kernel
-// recomputes the logits tile by tile, forms dz in LDS, writes dmap (every element by one thread) and adds per-block partials of dW = sum dz X
-// (pixels ascending inside a tile, tiles ascending inside a block); kp_dw_reduce_kernel sums the partials (part q of 16 takes blocks
-// q, q + 16, ... ascending, the parts ascending) and writes dbias = 0.
-// Heatmap supervision (capf_kp_heatmap_loss): the same logits against analytic Gaussian targets, loss and gradients -- the section at the end.
+// Gradients, ONE kernel body and ONE reduce for every producer of dz = dL/dz -- the section at the end:
+//   kp_grad_kernel<L, Rule>  a block owns a frame's eighth of the tiles.  Per tile it recomputes the logits, asks the rule for the value of each
+//            (pixel, joint) -- what goes to the LDS tile and the dz that multiplies Wt --, writes dmap[pixel, c] = sum_j dz Wt[j, c] (every element by
+//            one thread) and adds per-block partials of dW = sum dz X (pixels ascending inside a tile, tiles ascending inside a block).
+//   kp_reduce_kernel         sums the partials: part q of 16 takes blocks q, q + 16, ... ascending, the parts ascending.
+//   A rule is the per-block LDS state beside the tile, the set-up in front of the first barrier, the value of one (pixel, joint), and two
+//   policies (a tile's sum scaled per joint; J bias columns):
+//     KpIntegralRule  the backward of the integral decode (capf_kp_head_backward; fp32 map), four launches: slab + combine as above leave
+//                     (max, sum, x, y) per (frame, joint) in the scratch, the rule forms dz from them; the reduce writes dbias = 0.
+//     KpGaussRule     heatmap supervision (capf_kp_heatmap_loss): d = z - t against analytic Gaussian targets, dz = g_bj d; the same body also
+//                     adds the d^2 of the loss (LOSS), and the reduce's extra last block sums the frames.
 #include <math.h>
 
 #include "kernels.h"
@@ -32,31 +38,16 @@
 
 namespace capf {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef fmt_f32x4 f32x4;
 
 static constexpr int KP_THREADS = 256;            // = pixels of a tile
 static constexpr int KP_ZS = KP_THREADS + 8;      // LDS pitch of a joint's tile of logits: the 8 joints x 8 lanes of a wave hit 64 banks
 static constexpr int KP_REC = 8;                  // floats per (frame, slab, joint) record: m, sum, sum_x, sum_y, zmax, nan, idx, -
 static constexpr int KP_RED_PARTS = 16;
 
-struct KpLdF32 {
-    typedef float T;
-    static __device__ __forceinline__ f32x4 ld4(const T* p) { return *reinterpret_cast<const f32x4*>(p); }
-    static __device__ __forceinline__ float ld1(const T* p) { return *p; }
-};
-template <class F>
-struct KpLd16 {
-    typedef unsigned short T;
-    static __device__ __forceinline__ f32x4 ld4(const T* p) {
-        const uint2 u = *reinterpret_cast<const uint2*>(p);
-        return f32x4{F::lo(u.x), F::hi(u.x), F::lo(u.y), F::hi(u.y)};
-    }
-    static __device__ __forceinline__ float ld1(const T* p) { return F::widen(*p); }
-};
-
 KpGeom kp_geom(int B, int H, int W, int C, int J) {
     KpGeom g{};
-    if (B < 1 || H < 1 || W < 1 || J < 1 || J > MAX_JOINTS || C < 4 || C % 4 != 0 || C > KP_MAX_CHANNELS) return g;
+    if (!kp_shape_ok(B, H, W, C, J)) return g;
     const long HW = (long)H * W;
     if (HW > (1L << 24)) return g;                                  // (a pixel index and its row / column are exact in fp32)
     g.ntiles = (int)((HW + KP_THREADS - 1) / KP_THREADS);
@@ -325,98 +316,6 @@ __global__ void __launch_bounds__(KP_THREADS) kp_fwd_combine_kernel(const typena
     }
 }
 
-// ---- backward of the integral decode --------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(KP_THREADS) kp_bwd_kernel(const KpHeadArgs a) {
-    __shared__ float zs[MAX_JOINTS * KP_ZS];
-    __shared__ float st[MAX_JOINTS][6];                             // m, 1 / sum, x, y, gx, gy
-    const int tid = threadIdx.x;
-    const int b = (int)blockIdx.x / a.g.nbw, s = (int)blockIdx.x - b * a.g.nbw;
-    const int HW = a.H * a.W, J = a.J, C = a.C;
-    const float* __restrict__ xb = static_cast<const float*>(a.x) + (size_t)b * HW * C;
-    if (tid < J) {
-        const size_t i = (size_t)b * J + tid;
-        const float* sv = a.stats + i * 4;
-        float gx = a.dkcrop ? a.dkcrop[i * 2] : 0.f, gy = a.dkcrop ? a.dkcrop[i * 2 + 1] : 0.f;
-        if (a.dk2d) {                                               // g += A[:, :2]^T dk2d
-            const float* A = a.to_image + (size_t)b * 6;
-            const float d0 = a.dk2d[i * 2], d1 = a.dk2d[i * 2 + 1];
-            gx += A[0] * d0 + A[3] * d1;
-            gy += A[1] * d0 + A[4] * d1;
-        }
-        st[tid][0] = sv[0]; st[tid][1] = 1.f / sv[1]; st[tid][2] = sv[2]; st[tid][3] = sv[3];
-        st[tid][4] = gx * a.dec[0]; st[tid][5] = gy * a.dec[2];
-    }
-    __syncthreads();
-    float* part = a.bw_part + (size_t)blockIdx.x * J * C;
-    const int t0 = s * a.g.bw_tiles;
-    const int t1 = t0 + a.g.bw_tiles < a.g.ntiles ? t0 + a.g.bw_tiles : a.g.ntiles;
-    for (int t = t0; t < t1; ++t) {
-        const int base = t * KP_THREADS, pix = base + tid;
-        const int n = HW - base < KP_THREADS ? HW - base : KP_THREADS;
-        if (pix < HW) {
-            float acc[MAX_JOINTS];
-            kp_logits<KpLdF32>(xb + (size_t)pix * C, a.wt, a.bias, C, J, acc);
-            const int row = pix / a.W, col = pix - row * a.W;
-#pragma unroll
-            for (int j = 0; j < MAX_JOINTS; ++j) {
-                if (j < J) {
-                    const float p = expf(a.beta * acc[j] - st[j][0]) * st[j][1];
-                    const float dz = a.beta * p * (st[j][4] * ((float)col - st[j][2]) + st[j][5] * ((float)row - st[j][3]));
-                    acc[j] = dz;
-                    zs[j * KP_ZS + tid] = dz;
-                }
-            }
-            if (a.dmap) {                                           // dmap[pixel, c] = sum_j dz[j] Wt[j, c], joints ascending
-                float* dp = a.dmap + ((size_t)b * HW + pix) * C;
-                for (int c = 0; c < C; c += 4) {
-                    f32x4 d = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int j = 0; j < MAX_JOINTS; ++j) {
-                        if (j < J) {
-                            const float* __restrict__ w = a.wt + (size_t)j * C + c;
-                            d[0] = fmaf(acc[j], w[0], d[0]);
-                            d[1] = fmaf(acc[j], w[1], d[1]);
-                            d[2] = fmaf(acc[j], w[2], d[2]);
-                            d[3] = fmaf(acc[j], w[3], d[3]);
-                        }
-                    }
-                    f32x4* q = reinterpret_cast<f32x4*>(dp + c);
-                    *q = a.accumulate ? *q + d : d;
-                }
-            }
-        }
-        __syncthreads();
-        for (int o = tid; o < J * C; o += KP_THREADS) {
-            const int j = o / C, c = o - j * C;
-            const float* __restrict__ xc = xb + (size_t)base * C + c;
-            const float* zj = zs + j * KP_ZS;
-            float sum = 0.f;
-#pragma unroll 8
-            for (int p = 0; p < n; ++p) sum = fmaf(zj[p], xc[(size_t)p * C], sum);
-            part[o] = t == t0 ? sum : part[o] + sum;
-        }
-        __syncthreads();
-    }
-}
-
-__global__ void __launch_bounds__(KP_THREADS) kp_dw_reduce_kernel(const float* __restrict__ part, const int nparts, const int JC, const int J,
-                                                                  float* __restrict__ dW, float* __restrict__ dbias) {
-    __shared__ float sh[KP_RED_PARTS][16];
-    const int lc = threadIdx.x & 15, q = threadIdx.x >> 4;
-    const int o = (int)blockIdx.x * 16 + lc;
-    float s = 0.f;
-    if (o < JC)
-        for (int p = q; p < nparts; p += KP_RED_PARTS) s += part[(size_t)p * JC + o];
-    sh[q][lc] = s;
-    __syncthreads();
-    if (q == 0 && o < JC) {
-        s = 0.f;
-        for (int p = 0; p < KP_RED_PARTS; ++p) s += sh[p][lc];
-        dW[o] = s;
-    }
-    if (blockIdx.x == 0 && dbias && (int)threadIdx.x < J) dbias[threadIdx.x] = 0.f;     // softmax is shift-invariant: exactly zero
-}
-
 template <class L, bool PAIR = false>
 static void kp_forward_launches(const typename KpArgsOf<PAIR>::type& a, hipStream_t s) {
     const dim3 g1((unsigned)(a.B * a.g.nslab)), g2((unsigned)((a.B * a.J + KP_THREADS - 1) / KP_THREADS));
@@ -437,9 +336,7 @@ hipError_t launch_kp_head_forward(KpHeadArgs a, hipStream_t s) {
     a.g = kp_geom(a.B, a.H, a.W, a.C, a.J);
     if (!kp_args_ok(a) || !a.kcrop) return hipErrorInvalidValue;
     a.stats = nullptr;
-    if (a.dtype == 0) kp_forward_launches<KpLdF32>(a, s);
-    else if (a.dtype == 1) kp_forward_launches<KpLd16<Bf16Fmt>>(a, s);
-    else kp_forward_launches<KpLd16<F16Fmt>>(a, s);
+    with_map_loader(a.dtype, [&](auto l) { kp_forward_launches<decltype(l)>(a, s); });
     return hipGetLastError();
 }
 
@@ -447,33 +344,19 @@ hipError_t launch_kp_head_forward_pair(KpPairArgs a, hipStream_t s) {
     a.g = kp_geom(a.B, a.H, a.W, a.C, a.J);
     if (!kp_args_ok(a) || !a.kcrop || a.B > (1 << 30) || (a.shift != 0 && a.shift != 1) || !swap_table_ok(a.swap.j, a.J)) return hipErrorInvalidValue;
     a.stats = nullptr;
-    if (a.dtype == 0) kp_forward_launches<KpLdF32, true>(a, s);
-    else if (a.dtype == 1) kp_forward_launches<KpLd16<Bf16Fmt>, true>(a, s);
-    else kp_forward_launches<KpLd16<F16Fmt>, true>(a, s);
+    with_map_loader(a.dtype, [&](auto l) { kp_forward_launches<decltype(l), true>(a, s); });
     return hipGetLastError();
 }
 
-hipError_t launch_kp_head_backward(KpHeadArgs a, hipStream_t s) {
-    a.g = kp_geom(a.B, a.H, a.W, a.C, a.J);
-    if (!kp_args_ok(a) || a.mode != 1 || a.dtype != 0 || !a.dW || (!a.dkcrop && !a.dk2d) || (a.dk2d && !a.to_image)) return hipErrorInvalidValue;
-    a.stats = a.part + a.g.fwd_elems;
-    a.bw_part = a.stats + a.g.stat_elems;
-    a.kcrop = a.k2d = a.score = a.heat = nullptr;
-    kp_forward_launches<KpLdF32>(a, s);
-    hipLaunchKernelGGL(kp_bwd_kernel, dim3((unsigned)(a.B * a.g.nbw)), dim3(KP_THREADS), 0, s, a);
-    const int JC = a.J * a.C;
-    hipLaunchKernelGGL(kp_dw_reduce_kernel, dim3((unsigned)((JC + 15) / 16)), dim3(KP_THREADS), 0, s, a.bw_part, a.B * a.g.nbw, JC, a.J, a.dW, a.dbias);
-    return hipGetLastError();
-}
-
-// ---- heatmap supervision (capf_kp_heatmap_loss; include/capf.h has the rules) ----------------------------------------------------------
-// d = z - t per (pixel, joint) in the LDS tile, z being kp_logits' chain and t the analytic Gaussian target (a product of two entries of a
-// per-block fp64 table; the difference is formed in fp64 and rounded once); neither reaches memory.
-//   kp_loss_kernel<LOSS>   8 lanes per joint add d^2 (lane l: pixels l, l + 8, ... of each tile, tiles ascending; lanes ascending): one sum per
-//                          (block, joint), a block being a frame's eighth of the tiles (the backward's cut)
-//   kp_loss_items_kernel   one thread per (frame, joint): blocks ascending -> l_bj; the OHKM rank and g_bj; the frame's sum, joints ascending
-//   kp_loss_kernel<GRAD>   dz = g_bj d in registers -> dmap; per block partials of sum d X and sum d, scaled by g_bj per tile
-//   kp_loss_reduce_kernel  the partials (kp_dw_reduce_kernel's order) -> dweight, dbias; its last block the frames' sums -> loss
+// ---- gradients: one kernel body, one reduce; a rule per producer of dz ----------------------------------------------------------------
+// Heatmap supervision (capf_kp_heatmap_loss; include/capf.h has the rules): d = z - t per (pixel, joint) in the LDS tile, z being kp_logits'
+// chain and t the analytic Gaussian target (a product of two entries of a per-block fp64 table; the difference is formed in fp64 and rounded
+// once); neither reaches memory.
+//   kp_grad_kernel<KpGaussRule, LOSS>  8 lanes per joint add d^2 (lane l: pixels l, l + 8, ... of each tile, tiles ascending; lanes ascending):
+//                                      one sum per (block, joint)
+//   kp_loss_items_kernel               one thread per (frame, joint): blocks ascending -> l_bj; the OHKM rank and g_bj; the frame's sum, joints ascending
+//   kp_grad_kernel<KpGaussRule, GRAD>  dz = g_bj d in registers -> dmap; per block partials of sum d X and sum d, scaled by g_bj per tile
+//   kp_reduce_kernel                   the partials -> dweight, dbias; its last block the frames' sums -> loss
 // reduction 0 knows g_bj up front: <LOSS, GRAD> is one pass over the map.  OHKM: <LOSS>, items, <GRAD> (the logits recomputed).
 KpLossGeom kp_loss_geom(int B, int H, int W, int C, int J) {
     KpLossGeom lg{};
@@ -503,32 +386,97 @@ __device__ __forceinline__ KpLossItem kp_loss_item(const KpLossArgs& a, const si
     }
     return it;
 }
-__device__ __forceinline__ float kp_loss_norm(const KpLossArgs& a) { return __fmul_rn((float)a.B, (float)(a.reduction == 0 ? a.J : a.topk)); }
+// the loss is the frames' sums over B * count, count being the joints a frame's sum takes: all J (mean) or topk (OHKM)
+__host__ __device__ __forceinline__ int kp_loss_count(const KpLossArgs& a) { return a.reduction == 0 ? a.J : a.topk; }
+__device__ __forceinline__ float kp_loss_norm(const int B, const int count) { return __fmul_rn((float)B, (float)count); }
 // g_bj of a selected item: 2 scale w^2 / (H W norm)
 __device__ __forceinline__ float kp_loss_g(const KpLossArgs& a, const float w) {
-    return __fdiv_rn(__fmul_rn(__fmul_rn(__fmul_rn(2.f, a.scale), w), w), __fmul_rn((float)(a.H * a.W), kp_loss_norm(a)));
+    return __fdiv_rn(__fmul_rn(__fmul_rn(__fmul_rn(2.f, a.scale), w), w), __fmul_rn((float)(a.H * a.W), kp_loss_norm(a.B, kp_loss_count(a))));
 }
 
-template <class L, bool LOSS, bool GRAD>
-__global__ void __launch_bounds__(KP_THREADS) kp_loss_kernel(const KpLossArgs a) {
-    __shared__ float zs[MAX_JOINTS * KP_ZS];
-    __shared__ int mu[MAX_JOINTS][2];
-    __shared__ float gj[MAX_JOINTS];
-    __shared__ double eg[KP_LOSS_MAX_RADIUS + 1];                   // exp(-k^2 / (2 sigma^2)), k = 0 .. R: the target is eg[|dx|] eg[|dy|]
-    const int tid = threadIdx.x;
-    const int nbw = a.lg.g.nbw, bw_tiles = a.lg.g.bw_tiles, ntiles = a.lg.g.ntiles;
-    const int b = (int)blockIdx.x / nbw, s = (int)blockIdx.x - b * nbw;
-    const int HW = a.H * a.W, J = a.J, C = a.C, R = a.radius;
-    const typename L::T* __restrict__ xb = static_cast<const typename L::T*>(a.x) + (size_t)b * HW * C;
-    if (tid <= R) eg[tid] = exp(-(double)(tid * tid) / (2.0 * (double)a.sigma * (double)a.sigma));
-    if (tid < J) {
-        const size_t i = (size_t)b * J + tid;
-        const KpLossItem it = kp_loss_item(a, i);
-        mu[tid][0] = it.mux; mu[tid][1] = it.muy;
-        gj[tid] = !GRAD ? 0.f : LOSS ? kp_loss_g(a, it.w) : a.gsel[i];
+// the backward of the integral decode: dz = beta p (gx (col - x) + gy (row - y)), p the softmax of beta z, (gx, gy) the cotangent of the
+// heatmap coordinates.  The LDS tile holds dz itself; no bias column (softmax is shift-invariant: dbias is exactly zero)
+struct KpIntegralRule {
+    typedef KpHeadArgs Args;
+    struct Shared { float st[MAX_JOINTS][6]; };                     // m, 1 / sum, x, y, gx, gy
+    static constexpr bool SCALE_TILE = false, BIAS_COLS = false;
+    static __device__ __forceinline__ const KpGeom& geom(const Args& a) { return a.g; }
+    template <bool LOSS, bool GRAD>
+    static __device__ __forceinline__ void setup(const Args& a, const int b, const int tid, Shared& sh) {
+        float (&st)[MAX_JOINTS][6] = sh.st;
+        const int J = a.J;
+        if (tid < J) {
+            const size_t i = (size_t)b * J + tid;
+            const float* sv = a.stats + i * 4;
+            float gx = a.dkcrop ? a.dkcrop[i * 2] : 0.f, gy = a.dkcrop ? a.dkcrop[i * 2 + 1] : 0.f;
+            if (a.dk2d) {                                               // g += A[:, :2]^T dk2d
+                const float* A = a.to_image + (size_t)b * 6;
+                const float d0 = a.dk2d[i * 2], d1 = a.dk2d[i * 2 + 1];
+                gx += A[0] * d0 + A[3] * d1;
+                gy += A[1] * d0 + A[4] * d1;
+            }
+            st[tid][0] = sv[0]; st[tid][1] = 1.f / sv[1]; st[tid][2] = sv[2]; st[tid][3] = sv[3];
+            st[tid][4] = gx * a.dec[0]; st[tid][5] = gy * a.dec[2];
+        }
     }
+    static __device__ __forceinline__ void value(const Args& a, const Shared& sh, const int j, const int row, const int col, const float z,
+                                                 float& lds, float& dzo) {
+        const float (&st)[MAX_JOINTS][6] = sh.st;
+        const float p = expf(a.beta * z - st[j][0]) * st[j][1];
+        const float dz = a.beta * p * (st[j][4] * ((float)col - st[j][2]) + st[j][5] * ((float)row - st[j][3]));
+        lds = dz;
+        dzo = dz;
+    }
+};
+
+// heatmap supervision: the LDS tile holds the unscaled d = z - t (the loss adds its squares), dz = g_bj d; a tile's sums of d X and of d are
+// scaled by g_bj, and the J bias columns are real
+struct KpGaussRule {
+    typedef KpLossArgs Args;
+    struct alignas(16) Shared {                                     // (16: the alignment, and with it the size, the fp64 table has as an LDS array)
+        int mu[MAX_JOINTS][2];
+        float gj[MAX_JOINTS];
+        double eg[KP_LOSS_MAX_RADIUS + 1];                          // exp(-k^2 / (2 sigma^2)), k = 0 .. R: the target is eg[|dx|] eg[|dy|]
+    };
+    static constexpr bool SCALE_TILE = true, BIAS_COLS = true;
+    static __device__ __forceinline__ const KpGeom& geom(const Args& a) { return a.lg.g; }
+    template <bool LOSS, bool GRAD>
+    static __device__ __forceinline__ void setup(const Args& a, const int b, const int tid, Shared& sh) {
+        const int J = a.J, R = a.radius;
+        if (tid <= R) sh.eg[tid] = exp(-(double)(tid * tid) / (2.0 * (double)a.sigma * (double)a.sigma));
+        if (tid < J) {
+            const size_t i = (size_t)b * J + tid;
+            const KpLossItem it = kp_loss_item(a, i);
+            sh.mu[tid][0] = it.mux; sh.mu[tid][1] = it.muy;
+            sh.gj[tid] = !GRAD ? 0.f : LOSS ? kp_loss_g(a, it.w) : a.gsel[i];
+        }
+    }
+    static __device__ __forceinline__ void value(const Args& a, const Shared& sh, const int j, const int row, const int col, const float z,
+                                                 float& lds, float& dzo) {
+        const int R = a.radius;
+        const int dx = col - sh.mu[j][0], dy = row - sh.mu[j][1];
+        // z - t in double, rounded once: its error is relative to |z - t|, not to t, also where the two nearly cancel
+        float d = z;
+        if (dx >= -R && dx <= R && dy >= -R && dy <= R) d = (float)__fma_rn(-sh.eg[abs(dx)], sh.eg[abs(dy)], (double)z);
+        lds = d;
+        dzo = sh.gj[j] == 0.f ? 0.f : __fmul_rn(sh.gj[j], d);      // (an item without weight: exact zeros, whatever its logits)
+    }
+};
+
+// LOSS: the sums of the tile values' squares per (block, joint) -> a.sq_part.  GRAD: dmap and the block's partials -> a.bw_part
+// ([nout] per block, nout = J C (+ J with BIAS_COLS)), either only where the caller asked for it.
+template <class L, class Rule, bool LOSS, bool GRAD>
+__global__ void __launch_bounds__(KP_THREADS) kp_grad_kernel(const typename Rule::Args a) {
+    __shared__ float zs[MAX_JOINTS * KP_ZS];
+    __shared__ typename Rule::Shared sh;
+    const int tid = threadIdx.x;
+    const int nbw = Rule::geom(a).nbw, bw_tiles = Rule::geom(a).bw_tiles, ntiles = Rule::geom(a).ntiles;
+    const int b = (int)blockIdx.x / nbw, s = (int)blockIdx.x - b * nbw;
+    const int HW = a.H * a.W, J = a.J, C = a.C;
+    const typename L::T* __restrict__ xb = static_cast<const typename L::T*>(a.x) + (size_t)b * HW * C;
+    Rule::template setup<LOSS, GRAD>(a, b, tid, sh);
     __syncthreads();
-    const int JC = J * C, nout = JC + J;
+    const int JC = J * C, nout = Rule::BIAS_COLS ? JC + J : JC;
     const bool wgrad = GRAD && (a.dW || a.dbias);
     float* part = a.bw_part + (size_t)blockIdx.x * nout;
     const int jl = tid >> 3, l = tid & 7;
@@ -545,30 +493,28 @@ __global__ void __launch_bounds__(KP_THREADS) kp_loss_kernel(const KpLossArgs a)
 #pragma unroll
             for (int j = 0; j < MAX_JOINTS; ++j) {
                 if (j < J) {
-                    const int dx = col - mu[j][0], dy = row - mu[j][1];
-                    // z - t in double, rounded once: its error is relative to |z - t|, not to t, also where the two nearly cancel
-                    float d = acc[j];
-                    if (dx >= -R && dx <= R && dy >= -R && dy <= R) d = (float)__fma_rn(-eg[abs(dx)], eg[abs(dy)], (double)acc[j]);
-                    zs[j * KP_ZS + tid] = d;
-                    acc[j] = gj[j] == 0.f ? 0.f : __fmul_rn(gj[j], d);      // (an item without weight: exact zeros, whatever its logits)
+                    float v, dz;
+                    Rule::value(a, sh, j, row, col, acc[j], v, dz);
+                    zs[j * KP_ZS + tid] = v;
+                    acc[j] = dz;
                 }
             }
             if (GRAD && a.dmap) {                                   // dmap[pixel, c] = sum_j dz[j] Wt[j, c], joints ascending
                 float* dp = a.dmap + ((size_t)b * HW + pix) * C;
                 for (int c = 0; c < C; c += 4) {
-                    f32x4 dv = {0.f, 0.f, 0.f, 0.f};
+                    f32x4 d = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int j = 0; j < MAX_JOINTS; ++j) {
                         if (j < J) {
                             const float* __restrict__ w = a.wt + (size_t)j * C + c;
-                            dv[0] = fmaf(acc[j], w[0], dv[0]);
-                            dv[1] = fmaf(acc[j], w[1], dv[1]);
-                            dv[2] = fmaf(acc[j], w[2], dv[2]);
-                            dv[3] = fmaf(acc[j], w[3], dv[3]);
+                            d[0] = fmaf(acc[j], w[0], d[0]);
+                            d[1] = fmaf(acc[j], w[1], d[1]);
+                            d[2] = fmaf(acc[j], w[2], d[2]);
+                            d[3] = fmaf(acc[j], w[3], d[3]);
                         }
                     }
                     f32x4* q = reinterpret_cast<f32x4*>(dp + c);
-                    *q = a.accumulate ? *q + dv : dv;
+                    *q = a.accumulate ? *q + d : d;
                 }
             }
         }
@@ -581,7 +527,7 @@ __global__ void __launch_bounds__(KP_THREADS) kp_loss_kernel(const KpLossArgs a)
         }
         if (wgrad) {
             for (int o = tid; o < nout; o += KP_THREADS) {          // o >= JC: the bias of joint o - JC, whose "X" is 1
-                const bool isb = o >= JC;
+                const bool isb = Rule::BIAS_COLS && o >= JC;
                 const int j = isb ? o - JC : o / C, c = isb ? 0 : o - j * C;
                 const typename L::T* __restrict__ xc = xb + (size_t)base * C + c;
                 const float* zj = zs + j * KP_ZS;
@@ -592,13 +538,13 @@ __global__ void __launch_bounds__(KP_THREADS) kp_loss_kernel(const KpLossArgs a)
 #pragma unroll 8
                     for (int p = 0; p < n; ++p) sum = fmaf(zj[p], L::ld1(xc + (size_t)p * C), sum);
                 }
-                const float gs = gj[j] == 0.f ? 0.f : __fmul_rn(gj[j], sum);
-                part[o] = t == t0 ? gs : __fadd_rn(part[o], gs);
+                if constexpr (Rule::SCALE_TILE) sum = sh.gj[j] == 0.f ? 0.f : __fmul_rn(sh.gj[j], sum);
+                part[o] = t == t0 ? sum : __fadd_rn(part[o], sum);
             }
         }
         __syncthreads();
     }
-    if (LOSS) {                                                     // the 8 lanes of a joint, ascending (every thread takes part in the shuffles)
+    if constexpr (LOSS) {                                           // the 8 lanes of a joint, ascending (every thread takes part in the shuffles)
         float tot = __shfl(sq, 0, 8);
         for (int q = 1; q < 8; ++q) tot = __fadd_rn(tot, __shfl(sq, q, 8));
         if (l == 0 && jl < J) a.sq_part[(size_t)blockIdx.x * J + jl] = tot;
@@ -647,47 +593,66 @@ __global__ void __launch_bounds__(KP_THREADS) kp_loss_items_kernel(const KpLossA
     }
 }
 
-// blocks 0 .. gridDim - 2: kp_dw_reduce_kernel's sum of the blocks' partials, outputs [0, JC) to dweight and [JC, JC + J) to dbias;
-// the last block: the frames' sums in the same two stages (part q of 16 takes frames q, q + 16, ... ascending, parts ascending) -> loss
-__global__ void __launch_bounds__(KP_THREADS) kp_loss_reduce_kernel(const KpLossArgs a, const int nparts, const int JC, const int nout) {
+// blocks 0 .. ceil(nout / 16) - 1: column o of the blocks' partials in two stages (part q of 16 takes blocks q, q + 16, ... ascending, the parts
+// ascending); o < JC goes to dW, the rest to dbias, either where it is not NULL.  zero_bias = J: no bias column exists and dbias is exact
+// zeros.  loss != NULL: the grid has one more block, the last, for the frames' sums in the same two stages (frames for blocks) -> loss
+__global__ void __launch_bounds__(KP_THREADS) kp_reduce_kernel(const float* __restrict__ part, const int nparts, const int nout, const int JC,
+                                                               float* __restrict__ dW, float* __restrict__ dbias, const int zero_bias,
+                                                               const float* __restrict__ frame, const int B, const int count, float* __restrict__ loss) {
     __shared__ float sh[KP_RED_PARTS][16];
     const int lc = threadIdx.x & 15, q = threadIdx.x >> 4;
     float s = 0.f;
-    if (blockIdx.x == gridDim.x - 1) {
+    if (loss && blockIdx.x == gridDim.x - 1) {
         if (lc == 0)
-            for (int p = q; p < a.B; p += KP_RED_PARTS) s = __fadd_rn(s, a.frame[p]);
+            for (int p = q; p < B; p += KP_RED_PARTS) s = __fadd_rn(s, frame[p]);
         sh[q][lc] = s;
         __syncthreads();
         if (threadIdx.x == 0) {
             s = 0.f;
             for (int p = 0; p < KP_RED_PARTS; ++p) s = __fadd_rn(s, sh[p][0]);
-            a.loss[0] = __fdiv_rn(s, kp_loss_norm(a));
+            loss[0] = __fdiv_rn(s, kp_loss_norm(B, count));
         }
         return;
     }
     const int o = (int)blockIdx.x * 16 + lc;
     if (o < nout)
-        for (int p = q; p < nparts; p += KP_RED_PARTS) s = __fadd_rn(s, a.bw_part[(size_t)p * nout + o]);
+        for (int p = q; p < nparts; p += KP_RED_PARTS) s = __fadd_rn(s, part[(size_t)p * nout + o]);
     sh[q][lc] = s;
     __syncthreads();
     if (q == 0 && o < nout) {
         s = 0.f;
         for (int p = 0; p < KP_RED_PARTS; ++p) s = __fadd_rn(s, sh[p][lc]);
-        if (o < JC) { if (a.dW) a.dW[o] = s; }
-        else if (a.dbias) a.dbias[o - JC] = s;
+        if (o < JC) { if (dW) dW[o] = s; }
+        else if (dbias) dbias[o - JC] = s;
     }
+    if (blockIdx.x == 0 && dbias && (int)threadIdx.x < zero_bias) dbias[threadIdx.x] = 0.f;
+}
+
+hipError_t launch_kp_head_backward(KpHeadArgs a, hipStream_t s) {
+    a.g = kp_geom(a.B, a.H, a.W, a.C, a.J);
+    if (!kp_args_ok(a) || a.mode != 1 || a.dtype != 0 || !a.dW || (!a.dkcrop && !a.dk2d) || (a.dk2d && !a.to_image)) return hipErrorInvalidValue;
+    a.stats = a.part + a.g.fwd_elems;
+    a.bw_part = a.stats + a.g.stat_elems;
+    a.kcrop = a.k2d = a.score = a.heat = nullptr;
+    kp_forward_launches<MapLdF32>(a, s);
+    const int nblocks = a.B * a.g.nbw, JC = a.J * a.C;
+    hipLaunchKernelGGL((kp_grad_kernel<MapLdF32, KpIntegralRule, false, true>), dim3((unsigned)nblocks), dim3(KP_THREADS), 0, s, a);
+    hipLaunchKernelGGL(kp_reduce_kernel, dim3((unsigned)((JC + 15) / 16)), dim3(KP_THREADS), 0, s, a.bw_part, nblocks, JC, JC, a.dW, a.dbias, a.J,
+                       nullptr, 0, 0, nullptr);
+    return hipGetLastError();
 }
 
 template <class L>
 static void kp_loss_launches(const KpLossArgs& a, hipStream_t s) {
     const dim3 blk(KP_THREADS), g1((unsigned)(a.B * a.lg.g.nbw)), g2((unsigned)((a.B + 7) / 8));
     const bool grads = a.dW || a.dbias || a.dmap;
-    if (grads && a.reduction == 0) hipLaunchKernelGGL((kp_loss_kernel<L, true, true>), g1, blk, 0, s, a);
-    else hipLaunchKernelGGL((kp_loss_kernel<L, true, false>), g1, blk, 0, s, a);
+    if (grads && a.reduction == 0) hipLaunchKernelGGL((kp_grad_kernel<L, KpGaussRule, true, true>), g1, blk, 0, s, a);
+    else hipLaunchKernelGGL((kp_grad_kernel<L, KpGaussRule, true, false>), g1, blk, 0, s, a);
     hipLaunchKernelGGL(kp_loss_items_kernel, g2, blk, 0, s, a);
-    if (grads && a.reduction == 1) hipLaunchKernelGGL((kp_loss_kernel<L, false, true>), g1, blk, 0, s, a);
+    if (grads && a.reduction == 1) hipLaunchKernelGGL((kp_grad_kernel<L, KpGaussRule, false, true>), g1, blk, 0, s, a);
     const int JC = a.J * a.C, nout = a.dW || a.dbias ? JC + a.J : 0;
-    hipLaunchKernelGGL(kp_loss_reduce_kernel, dim3((unsigned)((nout + 15) / 16 + 1)), blk, 0, s, a, a.B * a.lg.g.nbw, JC, nout);
+    hipLaunchKernelGGL(kp_reduce_kernel, dim3((unsigned)((nout + 15) / 16 + 1)), blk, 0, s, a.bw_part, a.B * a.lg.g.nbw, nout, JC, a.dW, a.dbias, 0,
+                       a.frame, a.B, kp_loss_count(a), a.loss);
 }
 
 hipError_t launch_kp_heatmap_loss(KpLossArgs a, hipStream_t s) {
@@ -699,10 +664,9 @@ hipError_t launch_kp_heatmap_loss(KpLossArgs a, hipStream_t s) {
     a.gsel = a.sq_part + a.lg.sq_elems;
     a.frame = a.gsel + (a.reduction == 1 ? a.lg.item_elems : 0);
     a.bw_part = a.frame + a.lg.frame_elems;
-    if (a.dtype == 0) kp_loss_launches<KpLdF32>(a, s);
-    else if (a.dtype == 1) kp_loss_launches<KpLd16<Bf16Fmt>>(a, s);
-    else kp_loss_launches<KpLd16<F16Fmt>>(a, s);
+    with_map_loader(a.dtype, [&](auto l) { kp_loss_launches<decltype(l)>(a, s); });
     return hipGetLastError();
 }
 
 }  // namespace capf
+
