@@ -196,6 +196,7 @@ PROTOTYPES = {
     "capf_cpn_decode": (I, [P, P] + [I] * 6 + [pF, P, P, P, P, P]),
     "capf_cpn_decode_pair": (I, [P, P] + [I] * 6 + [pI32, pF, P, F, P, P, P, P, P]),
     "capf_pck_counts": (I, [P, P, P, I, I, I, c_double, P, I, P, P, P]),
+    "capf_pck2d_counts": (I, [P, P, P, I, I, P, P, pD, I, I, P, I, P, P, P]),
     "capf_jpeg_info": (I, [S, Z, pI32, pI32, pI32, pI32, pI32, pZ]),
     "capf_jpeg_coefficients": (I, [S, Z, P, Z]),
     "capf_jpeg_decode": (I, [P, S, Z, P, Z, P, Z]),
@@ -1655,6 +1656,49 @@ def pck_counts(pred, gt, root=14, to_mm=1.0, segment=None, n_segments=1):
     if rc:
         raise CapfError(f"capf_pck_counts failed ({rc})")
     return counts, sums, frames
+
+
+PCK2D_MAX_THRESHOLDS = 32
+
+
+def pck2d_counts(pred, gt, thresholds, norm=None, weight=None, strict=False, segment=None, n_segments=1, out=None):
+    """capf_pck2d_counts.  pred / gt: CUDA fp32 [n, J, 2]; thresholds: 1..32 Python floats (host; for the reference's PCKh rule already
+    multiplied by headsize, with norm=None); norm: CUDA fp32 [n, 2] per-pose (nx, ny) or None = (1, 1); weight: CUDA fp32 [n, J] or
+    None; strict: `<` instead of `<=`; segment: CUDA int32 [n] or None (n_segments 1).  out: None, or (counts, valid, err_sums) to write
+    into.  -> (counts int32 [n_segments, K, J], valid int32 [n_segments, J], err_sums float64 [n_segments, J]) on the device; enqueued
+    on the current stream of that device, no synchronisation."""
+    import torch
+    lib = load_library()
+    n, J, two = gt.shape
+    dev, f32 = gt.device, torch.float32
+    thr = [float(t) for t in thresholds]
+    K = len(thr)
+    if two != 2 or tuple(pred.shape) != (n, J, 2) or pred.dtype != f32 or gt.dtype != f32:
+        raise CapfError(f"pred / gt must be fp32 [n, J, 2], not {tuple(pred.shape)} {pred.dtype} / {tuple(gt.shape)} {gt.dtype}")
+    if norm is not None and (tuple(norm.shape) != (n, 2) or norm.dtype != f32):
+        raise CapfError(f"norm must be fp32 [{n}, 2], not {tuple(norm.shape)} {norm.dtype}")
+    if weight is not None:
+        weight = weight.reshape(n, J) if weight.numel() == n * J else weight
+        if tuple(weight.shape) != (n, J) or weight.dtype != f32:
+            raise CapfError(f"weight must be fp32 [{n}, {J}] (or [{n}, {J}, 1]), not {tuple(weight.shape)} {weight.dtype}")
+    if segment is not None and (tuple(segment.shape) != (n,) or segment.dtype != torch.int32):
+        raise CapfError(f"segment must be int32 [{n}], not {tuple(segment.shape)} {segment.dtype}")
+    shapes = ((n_segments, K, J), torch.int32), ((n_segments, J), torch.int32), ((n_segments, J), torch.float64)
+    if out is None:
+        out = tuple(torch.empty(*s, dtype=d, device=dev) for s, d in shapes)
+    for t, (s, d) in zip(out, shapes):
+        if tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() or t.device != dev:
+            raise CapfError(f"out must be contiguous (counts, valid, err_sums) {[x[0] for x in shapes]} on {dev}, got {tuple(t.shape)} {t.dtype}")
+    counts, valid, sums = out
+    pred, gt = pred.contiguous(), gt.contiguous()
+    norm, weight, segment = (None if t is None else t.contiguous() for t in (norm, weight, segment))
+    if n == 0:                     # (an empty tensor has no address; the entry reads none of them and takes NULL for each)
+        pred = gt = norm = weight = segment = None
+    rc = lib.capf_pck2d_counts(_stream(counts), _p(pred), _p(gt), n, J, _p(norm), _p(weight), (c_double * max(K, 1))(*thr), K,
+                               1 if strict else 0, _p(segment), n_segments, _p(counts), _p(valid), _p(sums))
+    if rc:
+        raise CapfError(f"capf_pck2d_counts failed ({rc})")
+    return counts, valid, sums
 
 
 def keypoints_loss(mode, pred, gt, validity, threshold=0.0, want_grad=False):

@@ -1676,6 +1676,19 @@ int capf_pck_counts(void* stream, const float* pred, const float* gt, int n, int
                                    static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
+int capf_pck2d_counts(void* stream, const float* pred, const float* gt, int n, int joints, const float* norm, const float* weight,
+                      const double* thresholds, int n_thresholds, int strict, const int32_t* segment, int n_segments, int32_t* counts,
+                      int32_t* valid, double* err_sums) {
+    if (!counts || !valid || !err_sums || !thresholds || n_thresholds < 1 || n_thresholds > capf::PCK2D_MAX_THRESHOLDS || joints <= 0 ||
+        n < 0 || n_segments <= 0 || (strict != 0 && strict != 1) || (n > 0 && (!pred || !gt || (!segment && n_segments != 1))))
+        return CAPF_ERR_INVALID;
+    for (int k = 0; k < n_thresholds; ++k)
+        if (thresholds[k] != thresholds[k]) return CAPF_ERR_INVALID;                      // a NaN threshold
+    if (joints > 32 || (long)n_segments * joints > 0x7fffffffL) return CAPF_ERR_UNSUPPORTED;
+    return capf::launch_pck2d_counts(pred, gt, n, joints, norm, weight, thresholds, n_thresholds, strict, segment, n_segments, counts, valid,
+                                     err_sums, static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+}
+
 int capf_keypoints_loss(void* stream, int mode, const float* pred, const float* gt, const float* validity, int rows, int dim,
                         float threshold, float* loss, float* dpred) {
     if (!pred || !gt || !validity || !loss || rows <= 0 || dim <= 0 || mode < 0 || mode > 2) return CAPF_ERR_INVALID;

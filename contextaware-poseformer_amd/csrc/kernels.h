@@ -745,6 +745,13 @@ hipError_t launch_segment_sums(const float* err, const int* seg, const int* prev
 constexpr int PCK_THRESHOLDS = 31;
 hipError_t launch_pck_counts(const float* pred, const float* gt, int n, int J, int root, double to_mm, const int* seg, int n_seg,
                              int* counts, double* sums, int* frames, hipStream_t s);
+// 2-D PCKh counts: counts [n_seg][K][J] int32, valid [n_seg][J] int32, sums [n_seg][J] fp64; thresholds: K host doubles, carried to the
+// kernel in its arguments
+constexpr int PCK2D_MAX_THRESHOLDS = 32;
+struct Pck2dThresholds { double v[PCK2D_MAX_THRESHOLDS]; };
+hipError_t launch_pck2d_counts(const float* pred, const float* gt, int n, int J, const float* norm, const float* weight,
+                               const double* thresholds, int K, int strict, const int* seg, int n_seg, int* counts, int* valid, double* sums,
+                               hipStream_t s);
 hipError_t launch_keypoints_loss(const float* pred, const float* gt, const float* validity, int rows, int D, int mode, float thr,
                                  float* loss, float* dpred, hipStream_t s);
 

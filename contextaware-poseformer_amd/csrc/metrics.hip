@@ -257,6 +257,76 @@ hipError_t launch_pck_counts(const float* pred, const float* gt, int n, int J, i
     return hipGetLastError();
 }
 
+// 2-D PCKh counts (evaluate_2d_joint, ContextPose/mvn/datasets/human36m.py:438-449, and the accuracy figure of CA_PF.keypoint_loss): per
+// pose and joint the normalised distance e = sqrt(u u + v v), u = (px - gx) / nx, v = (py - gy) / ny, counted against up to 32
+// thresholds that arrive in the kernel arguments (`<=`, the reference's rule, or `<` when strict).  pck_counts_kernel's structure: one
+// block per (segment, joint); thread t takes poses t, t + 256, ... in order and the block reduces in a fixed tree, so the integer counts
+// are exact and the fp64 error sum has the same bits on every call.  fp64 throughout, every operation rounded on its own (no contraction;
+// division and sqrt correctly rounded): a float64 restatement gets the same e, hence the same counts, and -- adding in the same order --
+// the same sum.  A sample is valid iff weight (if any) > 0, both norm entries (if any) are finite and > 0, and the pose belongs to this
+// block's segment; only valid samples are counted.  A NaN / inf e fails the comparisons, counts as valid and goes into the sum.
+__global__ __launch_bounds__(256) void pck2d_counts_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int n, int J,
+                                                           const float* __restrict__ norm, const float* __restrict__ weight,
+                                                           Pck2dThresholds thr, int K, int strict, const int* __restrict__ seg,
+                                                           int* __restrict__ counts, int* __restrict__ valid, double* __restrict__ sums) {
+#pragma clang fp contract(off)
+    __shared__ int cnt[256][PCK2D_MAX_THRESHOLDS + 1];    // (+1: the valid samples)
+    __shared__ double red[256];
+    const int sid = blockIdx.x / J, j = blockIdx.x - sid * J, t = threadIdx.x;
+    int c[PCK2D_MAX_THRESHOLDS + 1];
+#pragma unroll
+    for (int k = 0; k <= PCK2D_MAX_THRESHOLDS; ++k) c[k] = 0;
+    double acc = 0.0;
+    for (int i = t; i < n; i += 256) {
+        if (seg && seg[i] != sid) continue;
+        if (weight && !(weight[(size_t)i * J + j] > 0.f)) continue;
+        double nx = 1.0, ny = 1.0;
+        if (norm) {
+            nx = (double)norm[(size_t)i * 2 + 0];
+            ny = (double)norm[(size_t)i * 2 + 1];
+            if (!(nx > 0.0 && ny > 0.0 && nx < HUGE_VAL && ny < HUGE_VAL)) continue;      // (a NaN fails `>`)
+        }
+        const float* p = pred + ((size_t)i * J + j) * 2;
+        const float* g = gt + ((size_t)i * J + j) * 2;
+        const double u = ((double)p[0] - (double)g[0]) / nx;
+        const double v = ((double)p[1] - (double)g[1]) / ny;
+        const double uu = u * u, vv = v * v;
+        const double e = sqrt(uu + vv);
+#pragma unroll
+        for (int k = 0; k < PCK2D_MAX_THRESHOLDS; ++k) c[k] += (k < K && (strict ? e < thr.v[k] : e <= thr.v[k])) ? 1 : 0;
+        ++c[PCK2D_MAX_THRESHOLDS];
+        acc += e;
+    }
+#pragma unroll
+    for (int k = 0; k <= PCK2D_MAX_THRESHOLDS; ++k) cnt[t][k] = c[k];
+    red[t] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            for (int k = 0; k <= PCK2D_MAX_THRESHOLDS; ++k) cnt[t][k] += cnt[t + o][k];
+            red[t] += red[t + o];
+        }
+        __syncthreads();
+    }
+    if (t < K) counts[((size_t)sid * K + t) * J + j] = cnt[0][t];
+    if (t == 0) {
+        valid[(size_t)sid * J + j] = cnt[0][PCK2D_MAX_THRESHOLDS];
+        sums[(size_t)sid * J + j] = red[0];
+    }
+}
+
+hipError_t launch_pck2d_counts(const float* pred, const float* gt, int n, int J, const float* norm, const float* weight,
+                               const double* thresholds, int K, int strict, const int* seg, int n_seg, int* counts, int* valid, double* sums,
+                               hipStream_t s) {
+    if (n < 0 || J <= 0 || J > MAXJ || K < 1 || K > PCK2D_MAX_THRESHOLDS || n_seg <= 0 || (long)n_seg * J > 0x7fffffffL)
+        return hipErrorInvalidValue;
+    Pck2dThresholds thr;
+    for (int k = 0; k < PCK2D_MAX_THRESHOLDS; ++k) thr.v[k] = k < K ? thresholds[k] : 0.0;
+    hipLaunchKernelGGL(pck2d_counts_kernel, dim3(n_seg * J), dim3(256), 0, s, pred, gt, n, J, norm, weight, thr, K, strict, seg, counts, valid,
+                       sums);
+    return hipGetLastError();
+}
+
 // KeypointsMSELoss / KeypointsMSESmoothLoss / KeypointsMAELoss (loss.py:104-137):
 //   loss = sum(f(gt - pred) * validity) / (D * max(1, sum(validity)));  validity is [rows, 1] broadcast over D
 //   mode 0: f = d^2;  1: d^2, and terms above `thr` replaced by term^0.1 * thr^0.9;  2: |d|

@@ -39,9 +39,10 @@ class VolumetricTriangulationNet(CA_PF):
         x, kcrop, score = super().forward_detect(images, to_image)
         return self._layout(x), kcrop, score
 
-    def keypoint_loss(self, images, keypoints_2d_crop, target_weight=None, sigma=2.0, reduction="mean", topk=8):
-        """CA_PF.keypoint_loss: heatmap supervision of the native head (a 0-d loss; there is no layout to change)."""
-        return super().keypoint_loss(images, keypoints_2d_crop, target_weight, sigma, reduction, topk)
+    def keypoint_loss(self, images, keypoints_2d_crop, target_weight=None, sigma=2.0, reduction="mean", topk=8, return_accuracy=False):
+        """CA_PF.keypoint_loss: heatmap supervision of the native head (a 0-d loss, or (loss, acc) with return_accuracy; there is no layout
+        to change)."""
+        return super().keypoint_loss(images, keypoints_2d_crop, target_weight, sigma, reduction, topk, return_accuracy)
 
     def detect_flip_test(self, images, to_image=None, shift=True, flip_pairs=None):
         """CA_PF.detect_flip_test; flip_pairs None: this variant's skeleton (capf.lib.MPI_SWAP, as forward_flip_test)."""

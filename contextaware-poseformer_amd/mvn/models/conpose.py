@@ -15,7 +15,8 @@ import torch
 from torch import nn
 
 from capf.lib import (KP_INTEGRAL, KP_LOSS_REDUCTIONS, KP_MODES, PLAN_BN_BATCH_STATS, PLAN_CPN_PREDICT, CapfError, Engine, cpn_decode,
-                      cpn_decode_pair, fliptest_fuse, input_constants, kp_head_backward, kp_head_forward, kp_head_forward_pair, kp_heatmap_loss)
+                      cpn_decode_pair, fliptest_fuse, input_constants, kp_head_backward, kp_head_forward, kp_head_forward_pair, kp_heatmap_loss,
+                      pck2d_counts)
 
 from . import _native
 
@@ -756,7 +757,7 @@ class CA_PF(nn.Module):
             raise ValueError("forward_detect needs to_image [B, 2, 3]: the lifter takes the keypoints in normalised image coordinates too")
         return self._single_flow(images, to_image, True, trains)
 
-    def keypoint_loss(self, images, keypoints_2d_crop, target_weight=None, sigma=2.0, reduction="mean", topk=8):
+    def keypoint_loss(self, images, keypoints_2d_crop, target_weight=None, sigma=2.0, reduction="mean", topk=8, return_accuracy=False):
         """Heatmap supervision of the native head against 2-D ground truth: ONE backbone pass (no gradient reaches it), then
         capf_kp_heatmap_loss on feat0 -- final_layer's 1x1 conv, Gaussian targets of `sigma` heatmap cells around keypoints_2d_crop [B,J,2]
         (crop pixels, what detect() returns as kcrop_px; the heatmap <-> crop convention is detect()'s), HRNet's JointsMSELoss
@@ -764,6 +765,12 @@ class CA_PF(nn.Module):
         and its gradients, in one native call.  images: detect()'s forms (float32 or uint8 BGR crops).  Returns the 0-d loss; backward()
         leaves gradients in keypoint_head.final_layer.weight / .bias and nowhere else.  This is how an "argmax" head is trained (its decode
         has no derivative) and the only path that moves final_layer.bias; it serves "integral" models and every compute dtype alike.
+        return_accuracy=True: returns (loss, acc) -- the same loss and the same gradients, bit for bit, and acc, a 0-d float64 device
+        tensor without gradient: the PCK of this model's own decode on the feat0 the loss just read, the figure HRNet's training loop
+        logs beside the loss, taken on decoded keypoints.  No second backbone pass, no host synchronisation: capf_kp_head_forward in the
+        model's mode writes kcrop_px (detect()'s bits), capf_pck2d_counts compares it with keypoints_2d_crop under norm = (W / 10, H / 10)
+        of the crop (as fp32) for every pose, strict `<`, the single threshold 0.5 and weight = target_weight, and acc is the mean over
+        the joints with a valid sample of counts / valid (NaN if no joint has one).
         keypoint_head=None: CapfError; "cpn": NotImplementedError (that head belongs to the frozen backbone)."""
         head = self._head_record()
         if head is not _FinalLayerHead:
@@ -782,8 +789,33 @@ class CA_PF(nn.Module):
             with torch.no_grad():
                 _run_backbone(self, eng, self._image_source(images), torch.cuda.current_stream(dev).cuda_stream)
                 feat0 = eng.tensor_view(head.maps, B)
-            return keypoint_heatmap_loss(feat0, weight, bias, keypoints_2d_crop.to(dev), None if target_weight is None else target_weight.to(dev),
-                                         head.decode(H, W, feat0.shape[1], feat0.shape[2]), sigma, reduction, topk)
+            decode = head.decode(H, W, feat0.shape[1], feat0.shape[2])
+            gt, tw = keypoints_2d_crop.to(dev), None if target_weight is None else target_weight.to(dev)
+            loss = keypoint_heatmap_loss(feat0, weight, bias, gt, tw, decode, sigma, reduction, topk)
+            if not return_accuracy:
+                return loss
+            with torch.no_grad():
+                return loss, self._decode_accuracy(feat0, weight, bias, decode, gt, tw, H, W)
+
+    @staticmethod
+    def _accuracy_norm(B, H, W, device):
+        """capf_pck2d_counts' norm for B crops of H rows x W columns: (nx, ny) = (W / 10, H / 10) per pose, x over the width; filled on the
+        device (no host-to-device copy)"""
+        norm = torch.empty(B, 2, dtype=torch.float32, device=device)
+        norm[:, 0] = W / 10.0
+        norm[:, 1] = H / 10.0
+        return norm
+
+    def _decode_accuracy(self, feat0, weight, bias, decode, gt, tw, H, W, threshold=0.5):
+        """keypoint_loss's accuracy figure (its docstring has the rule); everything stays on the device"""
+        B, J = gt.shape[0], gt.shape[1]
+        kcrop, _, _, _ = kp_head_forward(feat0, weight.detach(), None if bias is None else bias.detach(), KP_MODES[self.keypoint_head_mode],
+                                         self.keypoint_beta, decode, None, want_score=False)
+        counts, valid, _ = pck2d_counts(kcrop, gt.detach().to(torch.float32).contiguous(), (threshold,), norm=self._accuracy_norm(B, H, W, gt.device),
+                                        weight=None if tw is None else tw.detach().to(torch.float32).reshape(B, J).contiguous(), strict=True)
+        seen = valid[0] > 0
+        rate = torch.where(seen, counts[0, 0].to(torch.float64) / valid[0].clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=gt.device))
+        return rate.sum() / seen.sum()                          # (0 / 0 = NaN: no joint has a valid sample)
 
     # ---- detector-free flip test: the heatmaps of each crop and of its flipped-back mirror averaged, then decoded once -----------
     def _swap_table(self, flip_pairs):

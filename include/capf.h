@@ -166,7 +166,8 @@ const char* capf_version(void);
  * (additive: capf_set_map_grad_mode, capf_map_grad_mode; CAPF_PLAN_BN_BATCH_STATS, capf_backbone_forward_bn, capf_op_bn_stats_scratch_bytes,
  * capf_op_bn_stats, capf_op_bn_apply; capf_backward_points; capf_kp_head_scratch_bytes, capf_kp_head_forward, capf_kp_head_backward;
  * capf_kp_head_pair_scratch_bytes, capf_kp_head_forward_pair; CAPF_PLAN_CPN_PREDICT, the named tensor "heat", capf_cpn_decode,
- * capf_cpn_decode_taps, capf_cpn_decode_lds_bytes; capf_cpn_decode_pair; capf_kp_heatmap_loss_scratch_bytes, capf_kp_heatmap_loss).         */
+ * capf_cpn_decode_taps, capf_cpn_decode_lds_bytes; capf_cpn_decode_pair; capf_kp_heatmap_loss_scratch_bytes, capf_kp_heatmap_loss;
+ * capf_pck2d_counts).                                                                                                                       */
 #define CAPF_ABI_VERSION 12
 int capf_abi_version(void);
 
@@ -993,6 +994,35 @@ int capf_cpn_decode_pair(void* stream, const void* heat_nhwc, int heat_dtype, in
  *   (mvn/datasets/mpi_inf_3dhp.py::evaluate).                                                                                          */
 int capf_pck_counts(void* stream, const float* pred, const float* gt, int n, int joints, int root, double to_mm, const int32_t* segment,
                     int n_segments, int32_t* counts, double* mpjpe_sums, int32_t* frames);
+/* capf_pck2d_counts: the 2-D PCKh counts of evaluate2d / evaluate_2d_joint (ContextPose/mvn/datasets/human36m.py:438-479) and of the
+ *   accuracy figure of CA_PF.keypoint_loss(return_accuracy=True).  pred / gt: device fp32 [n, joints, 2].
+ *   Arithmetic, all fp64, every operation rounded on its own (no contraction; division and sqrt correctly rounded), so that a float64
+ *   restatement gets the same numbers (tests/pck2d_oracle.py):  u = ((double)px - (double)gx) / (double)nx,  v likewise with ny,
+ *   e = sqrt(u u + v v).  strict == 0: sample (i, j) is detected at threshold k iff e <= thresholds[k] -- the reference's rule
+ *   `distance <= headsize * threshold`: the caller passes norm = NULL and thresholds already multiplied by headsize in double, the
+ *   product the reference forms; strict == 1: iff e < thresholds[k].
+ *   norm: device fp32 [n, 2] = per-pose (nx, ny), or NULL = (1, 1).  weight: device fp32 [n, joints], or NULL = every sample valid.
+ *   thresholds: HOST doubles, n_thresholds of them (1..32); they travel in the kernel's arguments (no upload, no synchronisation; the
+ *   array may be reused as soon as the call returns).  segment: device int32 [n], or NULL (with poses, n_segments must then be 1: all poses).
+ *   Validity: sample (i, j) is valid iff (weight is NULL or weight[i, j] > 0) and (norm is NULL or both of pose i's entries are finite
+ *   and > 0) and (segment is NULL or segment[i] lies in [0, n_segments)).  Only valid samples enter the outputs, for segment s =
+ *   segment[i] (0 without segments):  counts[s][k][j] int32 = detected samples,  valid[s][j] int32 = valid samples,  err_sums[s][j] fp64 =
+ *   the sum of e.  One block per (segment, joint): thread t of 256 adds its poses t, t + 256, ... in that order, then the 256 partials are
+ *   added in a fixed tree (partial t += partial t + o for o = 128, 64, .., 1): the same bits on every call.
+ *   Non-finite distances: a NaN e (a NaN coordinate) fails every threshold, counts as valid and makes that (segment, joint)'s err_sums NaN;
+ *   e = +inf likewise with an inf sum (IEEE: it passes `<=` only against a threshold that is itself +inf).  No other joint or segment is
+ *   affected.  n may be 0: all outputs are zero, and pred, gt and segment may be NULL at any n_segments (no pose, nothing to read).  Every element of the three
+ *   outputs is written by every successful call.
+ *   Refused before anything is launched, no device needed -- CAPF_ERR_INVALID: NULL counts / valid / err_sums / thresholds, n_thresholds
+ *   outside 1..32, a NaN threshold, joints <= 0, n < 0, n_segments <= 0, strict not 0 or 1, and with n > 0: NULL pred or gt,
+ *   segment == NULL with n_segments != 1; CAPF_ERR_UNSUPPORTED: joints > 32 (capf_pose_errors' rule), n_segments * joints >= 2^31.
+ *   Rates (counts / valid; NaN where valid == 0) and the tables follow on the host: mvn/datasets/human36m.py::evaluate2d, Pck2dAccumulator.
+ *   Cost (MI355X, medians of 20 around the host call, two runs, tools/bench_pck2d.py, EXPERIMENTS.md R36.1; 17 joints, 10 thresholds):
+ *   0.024 ms at n = 512, 0.82 ms at n = 100 000 (0.89 ms with 2 segments); CA_PF.keypoint_loss + backward at batch 64 (HRNet-32 fp32):
+ *   5.90 - 5.96 ms with return_accuracy against 5.81 - 5.87 ms without, + 0.09 ms.  Not a hot path: one block per (segment, joint). */
+int capf_pck2d_counts(void* stream, const float* pred, const float* gt, int n, int joints, const float* norm, const float* weight,
+                      const double* thresholds, int n_thresholds, int strict, const int32_t* segment, int n_segments, int32_t* counts,
+                      int32_t* valid, double* err_sums);
 
 /* ---- N3: the per-frame affine crop in front of the prefetcher ------------------------
  * capf_affine_from_center_scale: get_affine_transform(center, scale, 0, (out_w, out_h)) of
