@@ -208,6 +208,8 @@ PROTOTYPES = {
     "capf_jpeg_decode_crop_batch": (I, [P, I, P, pZ, P, I, I, P, P, Z, P, I]),
     "capf_affine_from_center_scale": (I, [pD, pD, I, I, pD]),
     "capf_warp_affine": (I, [P, P, P, P, I, I, I, P]),
+    "capf_erase_scratch_bytes": (Z, [I, I]),
+    "capf_erase_patches": (I, [P, P, I, I, I, P, P, I, I, I, P, P, Z]),
     "capf_num_ops": (I, [H]),
     "capf_op_info": (I, [H, I, I, pS, pS, pD]),
     "capf_op_executed_flops": (I, [H, I, I, pD]),
@@ -1408,6 +1410,47 @@ def warp_affine(frames, mats, output_size):
     rc = lib.capf_warp_affine(_stream(out), _p(ptrs), _p(dims), _p(m), B, out_h, out_w, _p(out))
     if rc:
         raise CapfError(f"capf_warp_affine failed ({rc})")
+    return out
+
+
+ERASE_MAX_PATCHES = 32        # include/capf.h :: capf_erase_patches (the joint cap)
+
+
+def erase_patches(images_u8, centers, mask=None, size=70, use_mean=True, out=None):
+    """capf_erase_patches: erase_image (mvn/utils/img.py:179-198) for a batch.  images_u8: uint8 CUDA [B, H, W, 3]; centers: fp32 CUDA [B, P, 2]
+    = (x, y) in crop pixels, P <= 32; mask: uint8 (or bool) CUDA [B, P] or None = every patch; out: None (a new tensor), images_u8 itself (in
+    place) or a uint8 tensor of its shape sharing no byte with it.  Every input is contiguous, else ValueError (nothing is copied behind the
+    caller's back).  A patch whose centre is NaN or infinite is skipped (the reference raises).  -> out; enqueued on the current stream of
+    that device, no synchronisation."""
+    import torch
+    lib = load_library()
+    if images_u8.dim() != 4 or images_u8.shape[-1] != 3 or images_u8.dtype != torch.uint8 or not images_u8.is_cuda or not images_u8.is_contiguous():
+        raise ValueError(f"images must be a contiguous uint8 CUDA tensor [B, H, W, 3], not {tuple(images_u8.shape)} {images_u8.dtype} {images_u8.device}")
+    B, H, W, _ = images_u8.shape
+    dev = images_u8.device
+    if centers.dim() != 3 or centers.shape[0] != B or centers.shape[2] != 2 or centers.dtype != torch.float32 or centers.device != dev or not centers.is_contiguous():
+        raise ValueError(f"centers must be a contiguous fp32 tensor [{B}, P, 2] on {dev}, not {tuple(centers.shape)} {centers.dtype} {centers.device}")
+    P = centers.shape[1]
+    if mask is not None:
+        if tuple(mask.shape) != (B, P) or mask.dtype not in (torch.uint8, torch.bool) or mask.device != dev or not mask.is_contiguous():
+            raise ValueError(f"mask must be a contiguous uint8 / bool tensor [{B}, {P}] on {dev}, not {tuple(mask.shape)} {mask.dtype} {mask.device}")
+    if out is None:
+        out = torch.empty_like(images_u8)
+    elif out.shape != images_u8.shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor {tuple(images_u8.shape)} on {dev}, not {tuple(out.shape)} {out.dtype} {out.device}")
+    if int(size) < 0:
+        raise ValueError(f"size must not be negative, got {size}")
+    if B == 0 or P == 0 or H == 0 or W == 0:          # nothing to erase (an empty tensor has no address)
+        if out.data_ptr() != images_u8.data_ptr():
+            out.copy_(images_u8)
+        return out
+    need = lib.capf_erase_scratch_bytes(B, P)
+    # (freed on return: the caching allocator hands it out again only to work ordered after these kernels on this stream)
+    scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    rc = lib.capf_erase_patches(_stream(images_u8), _p(images_u8), B, H, W, _p(centers), _p(mask), P, int(size), 1 if use_mean else 0, _p(out),
+                                _p(scratch), need)
+    if rc:
+        raise CapfError(f"capf_erase_patches failed ({rc})")
     return out
 
 

@@ -1654,6 +1654,27 @@ int capf_warp_affine(void* stream, const uint8_t* const* frames, const int32_t* 
                ? CAPF_OK : CAPF_ERR_HIP;
 }
 
+// ---- erase_image for crop batches (erase.hip): every argument is judged here, before anything is launched ----
+size_t capf_erase_scratch_bytes(int batch, int patches) {
+    if (batch < 1 || patches < 1 || patches > capf::MAX_JOINTS) return 0;
+    return (size_t)batch * (size_t)patches * capf::ERASE_PATCH_BYTES;
+}
+
+int capf_erase_patches(void* stream, const uint8_t* images, int batch, int height, int width, const float* centers, const uint8_t* mask,
+                       int patches, int size, int use_mean, uint8_t* out, void* scratch, size_t scratch_bytes) {
+    if (!images || !centers || !out || !scratch || batch < 1 || height < 1 || width < 1 || patches < 1 || size < 0) return CAPF_ERR_INVALID;
+    const long long frame = (long long)height * width * 3, per_frame = (frame / 3 + 255) / 256;          // (the pixel-per-thread grid is the larger one)
+    if (patches > capf::MAX_JOINTS || frame > 0x7fffffffLL || per_frame * batch > 0x7fffffffLL) return CAPF_ERR_UNSUPPORTED;
+    if (scratch_bytes < capf_erase_scratch_bytes(batch, patches) || (reinterpret_cast<uintptr_t>(scratch) & 15)) return CAPF_ERR_INVALID;
+    // out is images itself or shares no byte with it; the scratch shares none with either
+    const uintptr_t a = reinterpret_cast<uintptr_t>(images), o = reinterpret_cast<uintptr_t>(out), w = reinterpret_cast<uintptr_t>(scratch);
+    const uintptr_t n = (uintptr_t)frame * (uintptr_t)batch, nw = capf_erase_scratch_bytes(batch, patches);
+    if (o != a && o < a + n && a < o + n) return CAPF_ERR_INVALID;
+    if ((w < a + n && a < w + nw) || (w < o + n && o < w + nw)) return CAPF_ERR_INVALID;
+    return capf::launch_erase_patches(images, batch, height, width, centers, mask, patches, size, use_mean, out, scratch,
+                                      static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+}
+
 int capf_pose_errors(void* stream, const float* pred, const float* gt, int n, int joints, const int32_t* prev, float* err) {
     if (!pred || !gt || !err || n <= 0 || joints <= 0) return CAPF_ERR_INVALID;
     hipError_t r = capf::launch_pose_errors(pred, gt, n, joints, prev, err, static_cast<hipStream_t>(stream));

@@ -736,6 +736,11 @@ hipError_t launch_fliptest_fuse_swap(const float* pred2, int B, int J, const int
 bool affine_from_center_scale(const double center[2], const double scale[2], int out_w, int out_h, double M[6]);
 hipError_t launch_warp_affine_u8(const unsigned char* const* frames, const int* dims, const double* M, unsigned char* out,
                                  int B, int out_h, int out_w, hipStream_t s);
+// N1 (erase.hip): erase_image (mvn/utils/img.py:179-198) for a batch of uint8 crops -- P <= MAX_JOINTS patches a frame, a frame of at most
+// 2^31 - 1 bytes, scratch = ERASE_PATCH_BYTES per (frame, patch), 16-byte aligned; out == images or disjoint from it
+constexpr int ERASE_PATCH_BYTES = 32;
+hipError_t launch_erase_patches(const unsigned char* images, int B, int H, int W, const float* centers, const unsigned char* mask, int P,
+                                int size, int use_mean, unsigned char* out, void* scratch, hipStream_t s);
 
 // ---- evaluation metrics (metrics.hip): N2 -------------------------------------------------------------------
 hipError_t launch_pose_errors(const float* pred, const float* gt, int n, int J, const int* prev, float* err, hipStream_t s);

@@ -27,6 +27,37 @@ def crop_image_batch(images, centers, scales, output_size):
     return _capf.warp_affine(list(images), mats, output_size)
 
 
+def erase_image(image, center_list, size=70, use_mean=True):
+    """img.py:179-198, the joint-centred cut-out behind the configuration's train.erase / val.erase: a square of side 2 * (size // 2) + 1
+    around each centre of `center_list` that lies inside the image becomes the patch's own mean colour in the ORIGINAL image (use_mean) or 0;
+    later centres paint over earlier ones.  `image`: uint8 [H, W, 3], a numpy array (uploaded, erased on the device, downloaded: a new
+    array, as the reference returns) or a CUDA tensor (a new CUDA tensor).  Every centre goes through Python's own int() here, as in the
+    reference (:188), before the device sees it, so a float64 centre such as 4.999999999999 truncates to 4 and a non-finite one raises; at most 32
+    of them may lie inside the image (ValueError)."""
+    import torch
+    as_numpy = not torch.is_tensor(image)
+    img = torch.as_tensor(np.ascontiguousarray(image)).cuda() if as_numpy else image
+    H, W = img.shape[:2]
+    # the reference's own test (:189) on the Python ints: what is left lies inside the image, where fp32 holds every column and row exactly
+    pts = [(x, y) for x, y in ((int(x), int(y)) for x, y in center_list) if 0 <= x < W and 0 <= y < H]
+    if len(pts) > _capf.ERASE_MAX_PATCHES or max(H, W) > 1 << 24:
+        raise ValueError(f"at most {_capf.ERASE_MAX_PATCHES} centres inside an image of at most 2^24 columns and rows, got {len(pts)} in {W} x {H}")
+    if not pts:
+        out = img.clone()
+    else:
+        out = erase_image_batch(img.contiguous()[None], torch.tensor(pts, dtype=torch.float32, device=img.device).view(1, -1, 2), None, size, use_mean)[0]
+    return out.cpu().numpy() if as_numpy else out
+
+
+def erase_image_batch(images_u8, centers, mask=None, size=70, use_mean=True, out=None):
+    """erase_image for a batch in one native call (capf_erase_patches): images_u8 uint8 CUDA [B, H, W, 3]; centers fp32 CUDA [B, P, 2] in crop
+    pixels (the prefetcher's kcrop); mask uint8 / bool CUDA [B, P] or None: frame b is erased at centers[b, p] for the p with mask[b, p] != 0, in
+    ascending p.  A centre counts iff -1 < x < W and -1 < y < H, the reference's truncation and range test on the fp32 values; a NaN or
+    infinite centre is skipped where the reference raises.  out: None, images_u8 itself (in place) or a tensor of its own.  At most 32
+    centres a frame (the project's joint cap): more raise CapfError."""
+    return _capf.erase_patches(images_u8, centers, mask, size, use_mean, out)
+
+
 def imread(path_or_bytes, device="cuda"):
     """cv2.imread(path, cv2.IMREAD_COLOR | cv2.IMREAD_IGNORE_ORIENTATION) of Human36M.__getitem__ (datasets/human36m.py:292-295) for a baseline
     JPEG: uint8 CUDA tensor [H, W, 3], BGR.  The host walks the Huffman stream, the GPU does the rest (capf_jpeg_decode); files this path does

@@ -167,7 +167,7 @@ const char* capf_version(void);
  * capf_op_bn_stats, capf_op_bn_apply; capf_backward_points; capf_kp_head_scratch_bytes, capf_kp_head_forward, capf_kp_head_backward;
  * capf_kp_head_pair_scratch_bytes, capf_kp_head_forward_pair; CAPF_PLAN_CPN_PREDICT, the named tensor "heat", capf_cpn_decode,
  * capf_cpn_decode_taps, capf_cpn_decode_lds_bytes; capf_cpn_decode_pair; capf_kp_heatmap_loss_scratch_bytes, capf_kp_heatmap_loss;
- * capf_pck2d_counts).                                                                                                                       */
+ * capf_pck2d_counts; capf_erase_scratch_bytes, capf_erase_patches).                                                                         */
 #define CAPF_ABI_VERSION 12
 int capf_abi_version(void);
 
@@ -1107,6 +1107,31 @@ int capf_jpeg_decode_crop_batch(void* stream, int n, const uint8_t* const* data,
 int capf_affine_from_center_scale(const double center[2], const double scale[2], int out_w, int out_h, double m[6]);
 int capf_warp_affine(void* stream, const uint8_t* const* frames, const int32_t* dims, const double* m, int batch,
                      int out_h, int out_w, uint8_t* out);
+/* capf_erase_scratch_bytes / capf_erase_patches: erase_image (ContextPose/mvn/utils/img.py:179-198), the joint-centred cut-out behind the
+ *   configuration's train.erase / val.erase, for a batch of uint8 crops on the device -- between capf_jpeg_decode_crop_batch / capf_warp_affine
+ *   and capf_preprocess / capf_forward_u8.  images / out: uint8 [batch, height, width, 3]; centers: fp32 [batch, patches, 2] = (x, y) in crop
+ *   pixels; mask: uint8 [batch, patches] or NULL (every patch).  Frame b becomes
+ *       erase_image(images[b], [centers[b, p] for p ascending if mask == NULL or mask[b, p] != 0], size, use_mean)
+ *   bit for bit (tests/golden/erase_reference.npz holds the reference's own outputs; tests/erase_oracle.py is the integer restatement):
+ *   Truncation.  A centre counts iff x > -1 && x < width && y > -1 && y < height, evaluated on the floats: the reference's int() (toward
+ *     zero) followed by its range test, so -0.5 truncates to 0 and counts, -1.0 does not, width - 0.25 does, width does not.
+ *   Patch.  xc = (int)x, yc = (int)y; columns [max(0, xc - size / 2), min(width, xc + size / 2 + 1)), rows likewise with height (integer
+ *     division: size 0 and 1 paint one pixel).  use_mean == 0: the patch becomes 0.  Otherwise each channel becomes the mean of that channel
+ *     over the patch in the ORIGINAL image, truncated as numpy stores a float64 into a uint8 array: the integer sum / count, from 64-bit sums.
+ *   Overlap order.  Patches apply in ascending p: a pixel under several counting patches takes the value of the highest p, a mean never
+ *     sees an earlier patch's paint, a pixel under none is copied.
+ *   The one divergence.  A NaN or infinite centre fails the test above and is skipped (1e30 too, without a float-to-int conversion); the
+ *     reference's int() raises on a non-finite one.
+ *   out == images (in place) gives the bits of the out-of-place call.  Two launches on `stream`, no atomics, no allocation, no
+ *   synchronisation; results do not depend on the launch geometry.  scratch: device memory, 16-byte aligned, at least
+ *   capf_erase_scratch_bytes(batch, patches) bytes (32 per patch; 0 for batch < 1, patches < 1 or patches > 32), sharing no byte with images / out.
+ *   Refused before anything is launched, no device needed -- CAPF_ERR_INVALID: NULL images / centers / out / scratch, batch / height / width /
+ *   patches < 1, size < 0, scratch_bytes too small or scratch misaligned, out overlapping images other than out == images, scratch
+ *   overlapping either; CAPF_ERR_UNSUPPORTED: patches > 32 (the joint cap), a frame of more than 2^31 - 1 bytes, batch * ceil(height *
+ *   width / 256) >= 2^31.                                                                                                                  */
+size_t capf_erase_scratch_bytes(int batch, int patches);
+int capf_erase_patches(void* stream, const uint8_t* images, int batch, int height, int width, const float* centers, const uint8_t* mask,
+                       int patches, int size, int use_mean, uint8_t* out, void* scratch, size_t scratch_bytes);
 
 /* ---- measurement aids (bench.py roofline line; no reference counterpart) -------------------------
  * capf_op_info: op `index` in launch order: its plan name, the kernel (template instantiation) it
