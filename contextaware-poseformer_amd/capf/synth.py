@@ -81,22 +81,23 @@ def load_synthetic(model, seed=0, bn_mode="random"):
     return sd
 
 
-def synth_inputs(batch, height=256, width=256, seed=0, crop_range=(192, 256), with_gt=False):
+def synth_inputs(batch, height=256, width=256, seed=0, crop_range=(192, 256), with_gt=False, joints=17):
     """Synthetic H36M-shaped inputs:
     images  [B,H,W,3] fp32 NHWC ~ N(0,1)          (post mean/std normalisation, datasets/utils.py:47-50)
     k2d     [B,17,2]  ~ U(-1,1)                   (screen-normalised, H36M-Toolbox/transform.py:92-96)
     kcrop   [B,17,2]  pixel coords U(0,cw-1)xU(0,ch-1); crop_range=(192,256) is reference-faithful,
                       (W,H) exercises out-of-range ref for 256x256 / 384x288 inputs
     gt      [B,1,17,3] ~ N(0,0.3^2), joint 0 zeroed (datasets/utils.py:52-53)
+    joints: the joint count in place of 17 (the same generator keys: 17 gives the bits it always gave)
     """
     images = _normal(seed, f"images/{batch}x{height}x{width}", (batch, height, width, 3), 1.0)
-    k2d = _uniform(seed, f"k2d/{batch}", (batch, 17, 2), -1.0, 1.0)
+    k2d = _uniform(seed, f"k2d/{batch}", (batch, joints, 2), -1.0, 1.0)
     cw, ch = crop_range
-    kx = _uniform(seed, f"kcrop.x/{batch}/{cw}", (batch, 17, 1), 0.0, cw - 1.0)
-    ky = _uniform(seed, f"kcrop.y/{batch}/{ch}", (batch, 17, 1), 0.0, ch - 1.0)
+    kx = _uniform(seed, f"kcrop.x/{batch}/{cw}", (batch, joints, 1), 0.0, cw - 1.0)
+    ky = _uniform(seed, f"kcrop.y/{batch}/{ch}", (batch, joints, 1), 0.0, ch - 1.0)
     out = [torch.from_numpy(images), torch.from_numpy(k2d), torch.from_numpy(np.concatenate([kx, ky], -1))]
     if with_gt:
-        gt = _normal(seed, f"gt/{batch}", (batch, 1, 17, 3), 0.3)
+        gt = _normal(seed, f"gt/{batch}", (batch, 1, joints, 3), 0.3)
         gt[:, :, 0] = 0.0
         out.append(torch.from_numpy(gt))
     return tuple(out)

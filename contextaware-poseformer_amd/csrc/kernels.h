@@ -561,6 +561,9 @@ struct CtxAttnArgs {
 hipError_t launch_ctx_attn(const CtxAttnArgs& a, hipStream_t s);
 // tiny multi-head attention: QKV [G*N, 3*heads*d] -> O [G*N, heads*d]; N tokens per group
 hipError_t launch_attention(const float* qkv, float* out, int groups, int N, int heads, int d, hipStream_t s, int out_bf16 = 0);
+// the token counts and head dimensions launch_attention takes: 1 <= N <= ATTENTION_MAX_TOKENS, d a positive multiple of 4
+static constexpr int ATTENTION_MAX_TOKENS = 17;
+bool attention_ok(int N, int d);
 // head (pose_dformer.py:240): out[r, 0..2] = Linear(LN(X[r,:]))
 hipError_t launch_head(const float* X, const float* g, const float* b, float eps, const float* w,
                        const float* wb, float* out, int rows, int C, int NO, hipStream_t s);
@@ -612,6 +615,11 @@ hipError_t launch_gelu_bwd(const float* x, const float* dy, float* dx, long n, h
 hipError_t launch_transpose_pad(const float* in, RowMap imap, int M, int C, float* out, int Mp, hipStream_t s);
 hipError_t launch_attention_bwd(const float* qkv, const float* dO, float* dqkv, int groups, int N, int heads, int d,
                                 hipStream_t s);
+// what launch_attention_bwd takes: attention_ok(N, d) and its instance's dynamic LDS (attention_bwd_lds_bytes: q, k, v, dO [NMAX][d + 1]
+// and P, dS [NMAX][NMAX + 1] floats, NMAX = 5 up to 5 tokens, else 17) within ATTENTION_BWD_MAX_LDS
+static constexpr size_t ATTENTION_BWD_MAX_LDS = 64 * 1024;
+size_t attention_bwd_lds_bytes(int N, int d);
+bool attention_bwd_ok(int N, int d);
 // dref (optional, capf_backward_points; fp32 maps only): [B*J, 2], the block's position gradients are added to it -- the kernel's PTS form
 hipError_t launch_deform_bwd(const DeformArgs& a, float* dAO, int ldd, hipStream_t s, float* dref = nullptr);
 // ---- gradient w.r.t. the keypoints (capf_backward_points).  dref [B*J, 2] is dL/d(normalised crop keypoints): zeroed by the caller, then

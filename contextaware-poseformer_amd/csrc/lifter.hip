@@ -466,17 +466,19 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(const float* __restr
     }
 }
 
+bool attention_ok(int N, int d) { return N >= 1 && N <= ATTENTION_MAX_TOKENS && d >= 4 && d % 4 == 0; }
+
 hipError_t launch_attention(const float* qkv, float* out, int groups, int N, int heads, int d, hipStream_t s, int out_bf16) {
-    if (d % 4 != 0) return hipErrorInvalidValue;
+    if (!attention_ok(N, d)) return hipErrorInvalidValue;
     const float scale = 1.0f / sqrtf((float)d);
-    if (N > 5 && N <= 17 && (size_t)(3 * 17 * (d + 1) + 17 * 18) * sizeof(float) <= 64 * 1024 && (long)groups * heads <= 0x7fffffffL) {
+    if (N > 5 && (size_t)(3 * 17 * (d + 1) + 17 * 18) * sizeof(float) <= 64 * 1024 && (long)groups * heads <= 0x7fffffffL) {
         const size_t lds = (size_t)(3 * 17 * (d + 1) + 17 * 18) * sizeof(float);
         const dim3 grid((unsigned)((long)groups * heads)), block(256);
         if (out_bf16) with_fmt(out_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((attention_lds_kernel<17, true, decltype(f)>), grid, block, lds, s, qkv, out, N, heads, d, scale); return 0; });
         else hipLaunchKernelGGL((attention_lds_kernel<17, false>), grid, block, lds, s, qkv, out, N, heads, d, scale);
         return hipGetLastError();
     }
-    if (d % 16 == 0 && N <= 17) {
+    if (d % 16 == 0) {
         const long total = (long)groups * heads * N * 4;
         dim3 grid((unsigned)((total + 255) / 256)), block(256);
         if (N <= 5) {
@@ -493,11 +495,9 @@ hipError_t launch_attention(const float* qkv, float* out, int groups, int N, int
     if (N <= 5) {
         if (out_bf16) with_fmt(out_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((attention_kernel<5, true, decltype(f)>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale); return 0; });
         else hipLaunchKernelGGL((attention_kernel<5, false>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale);
-    } else if (N <= 17) {
+    } else {                                   // (N <= 17: attention_ok)
         if (out_bf16) with_fmt(out_bf16 == 2, [&](auto f) { hipLaunchKernelGGL((attention_kernel<17, true, decltype(f)>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale); return 0; });
         else hipLaunchKernelGGL((attention_kernel<17, false>), grid, block, 0, s, qkv, out, groups, N, heads, d, scale);
-    } else {
-        return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

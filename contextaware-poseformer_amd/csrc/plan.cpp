@@ -1168,10 +1168,35 @@ bool Engine::build() {
         err = "height and width must be multiples of 32";
         return false;
     }
-    if (cfg.levels != 4 || cfg.num_joints <= 0 || cfg.embed_dim_ratio % (4 * cfg.num_heads) != 0 ||
-        cfg.embed_dim_ratio % (4 * cfg.deform_heads) != 0 || cfg.deform_samples != 4 || cfg.deform_heads != 4) {
-        err = "unsupported lifter configuration (levels must be 4, 4x4 deformable sampling, embed_dim_ratio % 32 == 0)";
+    if (cfg.levels != 4 || cfg.deform_samples != 4 || cfg.deform_heads != 4 || cfg.embed_dim_ratio <= 0 ||
+        cfg.embed_dim_ratio % (4 * cfg.deform_heads) != 0) {
+        err = "unsupported lifter configuration (levels must be 4, 4x4 deformable sampling, embed_dim_ratio % 16 == 0)";
         return false;
+    }
+    if (cfg.num_heads < 1 || cfg.embed_dim_ratio % (4 * cfg.num_heads) != 0) {
+        err = "num_heads must be at least 1 and divide embed_dim_ratio / 4 (the attention kernels read a head's embed_dim_ratio / num_heads "
+              "values four at a time): got num_heads " + std::to_string(cfg.num_heads) + " at embed_dim_ratio " + std::to_string(cfg.embed_dim_ratio);
+        return false;
+    }
+    // the attention launchers' own conditions (attention_ok, attention_bwd_ok: kernels.h) at the two shapes the lifter runs -- the res blocks
+    // over the levels + 1 tokens of a joint, the joint blocks over the num_joints tokens of a frame -- refused here, not by a launcher in the
+    // middle of a forward or of a backward.  Inference plans keep every head count: only the backward stages a head in LDS
+    {
+        const int res_d = cfg.embed_dim_ratio / cfg.num_heads, joint_d = (cfg.levels + 1) * res_d;
+        if (cfg.num_joints < 1 || !attention_ok(cfg.num_joints, joint_d) || !attention_ok(cfg.levels + 1, res_d)) {
+            err = "num_joints must be 1.." + std::to_string(ATTENTION_MAX_TOKENS) + " (the attention kernels hold at most " +
+                  std::to_string(ATTENTION_MAX_TOKENS) + " tokens): got " + std::to_string(cfg.num_joints);
+            return false;
+        }
+        if (cfg.training && (!attention_bwd_ok(cfg.num_joints, joint_d) || !attention_bwd_ok(cfg.levels + 1, res_d))) {
+            const bool joint = !attention_bwd_ok(cfg.num_joints, joint_d);
+            err = "num_heads " + std::to_string(cfg.num_heads) + " with training = 1: the attention backward stages a head of the " +
+                  (joint ? "joint" : "res") + " blocks (" + std::to_string(joint ? cfg.num_joints : cfg.levels + 1) + " tokens, head dimension " +
+                  std::to_string(joint ? joint_d : res_d) + ") in " +
+                  std::to_string(joint ? attention_bwd_lds_bytes(cfg.num_joints, joint_d) : attention_bwd_lds_bytes(cfg.levels + 1, res_d)) +
+                  " bytes of LDS, over the limit of " + std::to_string(ATTENTION_BWD_MAX_LDS) + ": use more heads, or an inference plan";
+            return false;
+        }
     }
     // the LayerNorm and head kernels (lifter.hip, train_kernels.hip) hold a joint row of (levels + 1) * embed_dim_ratio values in 24 values
     // per lane of one wave: 1536 at the most, i.e. embed_dim_ratio <= 288 -- refused here, not by a launcher in the middle of a forward

@@ -758,23 +758,24 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const float* __restr
     }
 }
 
+size_t attention_bwd_lds_bytes(int N, int d) {
+    const size_t nmax = N <= 5 ? 5 : 17;
+    return (4 * nmax * ((size_t)d + 1) + 2 * nmax * (nmax + 1)) * sizeof(float);
+}
+
+bool attention_bwd_ok(int N, int d) { return attention_ok(N, d) && attention_bwd_lds_bytes(N, d) <= ATTENTION_BWD_MAX_LDS; }
+
 hipError_t launch_attention_bwd(const float* qkv, const float* dO, float* dqkv, int groups, int N, int heads, int d,
                                 hipStream_t s) {
+    if (!attention_bwd_ok(N, d)) return hipErrorInvalidValue;
     const float scale = 1.0f / sqrtf((float)d);
     const long pairs = (long)groups * heads;
     if (pairs <= 0) return hipSuccess;
     if (pairs > 0x7fffffffL) return hipErrorInvalidValue;
     dim3 grid((unsigned)pairs), block(N <= 5 ? 64 : 256);
-    if (N <= 5) {
-        const size_t lds = (size_t)(4 * 5 * (d + 1) + 2 * 5 * 6) * sizeof(float);
-        hipLaunchKernelGGL(attention_bwd_kernel<5>, grid, block, lds, s, qkv, dO, dqkv, N, heads, d, scale);
-    } else if (N <= 17) {
-        const size_t lds = (size_t)(4 * 17 * (d + 1) + 2 * 17 * 18) * sizeof(float);
-        if (lds > 64 * 1024) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(attention_bwd_kernel<17>, grid, block, lds, s, qkv, dO, dqkv, N, heads, d, scale);
-    } else {
-        return hipErrorInvalidValue;
-    }
+    const size_t lds = attention_bwd_lds_bytes(N, d);
+    if (N <= 5) hipLaunchKernelGGL(attention_bwd_kernel<5>, grid, block, lds, s, qkv, dO, dqkv, N, heads, d, scale);
+    else hipLaunchKernelGGL(attention_bwd_kernel<17>, grid, block, lds, s, qkv, dO, dqkv, N, heads, d, scale);
     return hipGetLastError();
 }
 

@@ -52,8 +52,10 @@ def make_capf_config(config, height=256, width=192, context_blocks=True, compute
     c.levels = pf.levels            # depth = config.levels (pose_dformer.py:169)
     # the sibling app's PoseTransformer builds config.depth blocks per group instead (ContextPose_mpi/model/pose_dformer.py:199)
     c.depth = 0 if context_blocks else int(getattr(pf, "depth", pf.levels))
-    c.num_joints = 17
-    c.num_heads = 8
+    # the joint count CA_PF checks its inputs against, and the Blocks' head count (pose_dformer.py:147 builds them with num_heads=8; an
+    # optional poseformer.num_heads overrides it): the parameter tree, the shape checks and the engine agree by construction
+    c.num_joints = int(bb.num_joints)
+    c.num_heads = int(getattr(pf, "num_heads", 8))
     c.deform_heads = 4
     c.deform_samples = 4
     c.context_blocks = 1 if context_blocks else 0
@@ -68,7 +70,23 @@ def make_capf_config(config, height=256, width=192, context_blocks=True, compute
     # (fp16 is an inference plan: capf_create refuses it with training = 1)
     c.training = 1 if (c.depth in (0, c.levels) or mpi_width) and compute_dtype != "fp16" else 0
     c.plan_flags = int(plan_flags)  # 0 = the product plan (capf.lib.PLAN_*: take a kernel family out, parity tests only)
+    # a head count whose attention backward does not fit (capf_create names it: joint head dimension above 230 at 6..17 joints) still gets
+    # the inference plan the library accepts for it.  Asked of the library on plan-only handles, not restated here; a configuration it
+    # refuses either way keeps training = 1, so that the engine's constructor reports the first refusal
+    if c.training and "num_heads" in _plan_refusal(c):
+        c.training = 0
+        if _plan_refusal(c):
+            c.training = 1
     return c
+
+
+def _plan_refusal(c):
+    """capf_create's refusal of a configuration on a plan-only handle ('' when it is accepted)"""
+    try:
+        Engine(c, device=None).close()
+        return ""
+    except CapfError as e:
+        return str(e)
 
 
 class Container(nn.Module):

@@ -67,8 +67,10 @@ typedef struct capf_config {
     int32_t embed_dim_ratio;   /* 128.  A multiple of 32 with embed_dim_ratio * (levels + 1) <= 1536, i.e. at most 288: the LayerNorm and head
                                   kernels hold a joint row in 24 values per lane of a 64-lane wave; capf_create refuses a wider one */
     int32_t levels;            /* 4 feature levels (H36M model: also the depth of every block group, pose_dformer.py:169) */
-    int32_t num_joints;        /* 17 */
-    int32_t num_heads;         /* 8  (Block) */
+    int32_t num_joints;        /* 17.  1..17: the attention kernels hold at most 17 tokens; capf_create refuses more */
+    int32_t num_heads;         /* 8  (Block).  Any count that divides embed_dim_ratio / 4.  With training = 1 the attention backward stages a head
+                                  (q, k, v, dO) in LDS: capf_create refuses a count whose joint-block head dimension, (levels + 1) * embed_dim_ratio /
+                                  num_heads, needs more than 64 KiB there (above 230 at 6..17 joints, above 815 at 1..5); inference plans keep it */
     int32_t deform_heads;      /* 4  (DeformableBlock, pose_dformer.py:202) */
     int32_t deform_samples;    /* 4 */
     int32_t context_blocks;    /* 1 = H36M model; 0 = MPI-INF-3DHP variant without DeformableBlocks */
@@ -367,8 +369,9 @@ int capf_lifter_forward(capf_handle* h, void* stream, const float* k2d, float* k
  *     S[pixel][c] = sum over the items that fall into the pixel, in ascending it, in fp32, of weight_it * row_it[c], and
  *         dfeat = ((((0 + S_ctx[levels-1]) + S_ctx[levels-2]) + ...) + S_ctx[0]) + S_ref
  *     (context blocks in the order the backward visits them, then the reference pass; without context blocks dfeat = 0 + S_ref).  No
- *     atomics, no extra workspace: capf_workspace_bytes is the same in both modes.  At most 2048 items per frame and level in a pass
- *     (joints * heads * samples * 4; 1088 at the shipped configurations), otherwise capf_backward_maps returns CAPF_ERR_HIP.
+ *     atomics, no extra workspace: capf_workspace_bytes is the same in both modes.  The kernel's key space is 2048 items per frame and level
+ *     in a pass (joints * heads * samples * 4); every configuration capf_create accepts stays within it (64 items a joint, at most 17 joints:
+ *     1088 at the most, at the shipped configurations too).
  * capf_map_grad_mode: the current mode (-1 for a NULL handle). */
 int capf_set_features(capf_handle* h, void* stream, const float* const feat_nhwc[4], int batch);
 int capf_lifter_forward_train(capf_handle* h, void* stream, const float* k2d, float* kcrop_inout, int batch, float* out,

@@ -444,7 +444,7 @@ def split_drop_masks(masks, B, J=17, levels=4):
 
 
 def lifter_forward(P, k2d, ref, feats, pre="volume_net", levels=4, explicit=False, taps=None,
-                   context_blocks=True, drop_masks=None, emulate_bf16=False, depth=None, cells=None, unclipped=None):
+                   context_blocks=True, drop_masks=None, emulate_bf16=False, depth=None, cells=None, unclipped=None, heads=8):
     """PoseTransformer.forward pose_dformer.py:210-241.
 
     k2d [B,17,2], ref [B,17,2] (already normalised), feats: 4 NCHW maps -> [B,1,17,3].
@@ -453,6 +453,7 @@ def lifter_forward(P, k2d, ref, feats, pre="volume_net", levels=4, explicit=Fals
     grid_sample_in_cells with them (gradient tests: same bilinear cells as the implementation under test).
     unclipped: optional list (one per context block) of bool [B,17,levels,16,2], with cells: the coordinates that implementation did
     not clip to the border (grid_sample_in_cells).
+    heads: the head count of the res and joint Blocks (pose_dformer.py:147 num_heads=8).  The joint count is k2d's.
     """
     b, p, _ = k2d.shape
     nm = BF16 if emulate_bf16 else FP32
@@ -483,12 +484,12 @@ def lifter_forward(P, k2d, ref, feats, pre="volume_net", levels=4, explicit=Fals
     x = x.permute(0, 2, 1, 3).reshape(b * p, L, -1)                          # 'b l p c -> (b p) l c' :231
     depth = levels if depth is None else depth        # ContextPose_mpi/model/pose_dformer.py:199: its own config key there
     for i in range(depth):
-        x = _attn_block(P, f"{pre}.res_blocks.{i}", x, 8, keep=keep["res"][i] if keep else None, nm=nm)   # :233-234
+        x = _attn_block(P, f"{pre}.res_blocks.{i}", x, heads, keep=keep["res"][i] if keep else None, nm=nm)   # :233-234
     x = x.reshape(b, p, -1)                                                 # '(b p) l c -> b p (l c)' :235
     if taps is not None:
         taps["tokens_res"] = x
     for i in range(depth):
-        x = _attn_block(P, f"{pre}.joint_blocks.{i}", x, 8, keep=keep["joint"][i] if keep else None, nm=nm)   # :237-238
+        x = _attn_block(P, f"{pre}.joint_blocks.{i}", x, heads, keep=keep["joint"][i] if keep else None, nm=nm)   # :237-238
     if taps is not None:
         taps["tokens_joint"] = x
     x = _linear(P, pre + ".head.1", _ln(P, pre + ".head.0", x, 1e-5))       # :240
@@ -506,7 +507,7 @@ def normalise_crop_keypoints_(kcrop):
 
 
 def ca_pf_forward(P, images, k2d, kcrop, backbone="hrnet_32", levels=4, explicit=False, taps=None, drop_masks=None,
-                  emulate_bf16=False, cells=None):
+                  emulate_bf16=False, cells=None, heads=8):
     """CA_PF.forward conpose.py:30-42.  images [B,H,W,3] NHWC fp32; mutates kcrop in place.
     drop_masks: training-mode DropPath multipliers (see split_drop_masks), None = eval / no drop.
     emulate_bf16: the engine's compute_dtype = bf16 storage roundings (module docstring); False = the reference's fp32.
@@ -523,7 +524,7 @@ def ca_pf_forward(P, images, k2d, kcrop, backbone="hrnet_32", levels=4, explicit
         taps["ref"] = ref.clone()
         taps["features"] = feats
     return lifter_forward(P, k2d, ref, feats, levels=levels, explicit=explicit, taps=taps, drop_masks=drop_masks,
-                          emulate_bf16=bool(emulate_bf16), cells=cells)
+                          emulate_bf16=bool(emulate_bf16), cells=cells, heads=heads)
 
 
 def mpjpe(pred, gt):

@@ -7,9 +7,9 @@ import io
 from capf import synth
 
 
-def lifter_model(backbone, dtype="fp32", embed=None, plan_flags=0, mpi=False, depth=None, wseed=81, tweak=None):
+def lifter_model(backbone, dtype="fp32", embed=None, plan_flags=0, mpi=False, depth=None, wseed=81, tweak=None, joints=None, heads=None):
     """CA_PF (mpi: the MPI-INF-3DHP variant at `depth`) in eval mode on the GPU with cfg.model.poseformer.embed_dim_ratio = embed (None: the
-    preset's); returns (model, the state_dict it was loaded with, on the CPU).  tweak(sd) edits the checkpoint before it is loaded."""
+    preset's), cfg.model.backbone.num_joints = joints and cfg.model.poseformer.num_heads = heads (None: 17 and 8); returns (model, the state_dict it was loaded with, on the CPU).  tweak(sd) edits the checkpoint before it is loaded."""
     from mvn.utils.cfg import backbone_preset, config
     if mpi:
         from model.conpose import VolumetricTriangulationNet, mpi_preset
@@ -24,6 +24,10 @@ def lifter_model(backbone, dtype="fp32", embed=None, plan_flags=0, mpi=False, de
         cfg.model.backbone.fix_weights = True
         if embed:
             cfg.model.poseformer.embed_dim_ratio = embed
+        if joints:
+            cfg.model.backbone.num_joints = joints
+        if heads:
+            cfg.model.poseformer.num_heads = heads
         with contextlib.redirect_stdout(io.StringIO()):
             model = CA_PF(cfg, compute_dtype=dtype, plan_flags=plan_flags).eval()
     sd = synth.load_synthetic(model, seed=wseed, bn_mode="random")

@@ -55,14 +55,18 @@ def _compare(got, want, bf16, mass=None, inexact_cap=True):
 
 
 def lifter_ops(model, sd, B, H, W, iseed=82, kcrop=None, inexact_cap=True):
-    """Walk every non-backbone op of the inference schedule; returns {kernel instance: (count, worst error)}."""
-    img, k2d, kc = synth.synth_inputs(B, H, W, seed=iseed, crop_range=(192, 256))
+    """Walk every non-backbone op of the inference schedule; returns {kernel instance: (count, worst error)}.  The joint count is the
+    checkpoint's (Spatial_pos_embed [1, L1, J, C]), the Blocks' head count the model's configuration's."""
+    J = sd[V + ".Spatial_pos_embed"].shape[2]
+    heads = int(getattr(model._config.model.poseformer, "num_heads", 8))
+    img, k2d, kc = synth.synth_inputs(B, H, W, seed=iseed, crop_range=(192, 256), joints=J)
     if kcrop is not None:
         kc = kcrop
     img_d, k2d_d, kc_d = img.cuda(), k2d.cuda(), kc.cuda()
     ref = oracle.normalise_crop_keypoints_(kc.clone())                        # (bit for bit what the embedding writes back: test_oracle_golden)
-    out = torch.zeros(B, 1, 17, 3, device="cuda")
+    out = torch.zeros(B, 1, J, 3, device="cuda")
     eng = model.engine_for(img_d)
+    assert (eng.cfg.num_joints, eng.cfg.num_heads) == (J, heads)
     eng.set_debug(True)                                                       # (cpos / cidx taps of the context samplers)
     names = [n for n, _, _ in eng.schema()]
     n_ops = eng.lib.capf_num_ops(eng.h)
@@ -72,7 +76,7 @@ def lifter_ops(model, sd, B, H, W, iseed=82, kcrop=None, inexact_cap=True):
     P = op_oracle.lifter_params64(sd)
     C = P[V + ".coord_embed.weight"].shape[0]
     L1 = P[V + ".Spatial_pos_embed"].shape[1]
-    J, L, D = 17, L1 - 1, L1 * C
+    L, D = L1 - 1, L1 * C
     lifter = [i for i, d in enumerate(descs) if not d.backbone]
     copies = [i for i in lifter if table[i][0].startswith("copy.")]
     todo = [i for i in lifter if i not in copies]
@@ -173,7 +177,7 @@ def lifter_ops(model, sd, B, H, W, iseed=82, kcrop=None, inexact_cap=True):
             elif kern == "res_chain":
                 x = tokens(i, 5)
                 prefix(i + 1)
-                want, mass = op_oracle.res_chain_rows(P, x, depth)
+                want, mass = op_oracle.res_chain_rows(P, x, depth, heads=heads)
                 results.append((kern, name, _compare(tokens(i, 5), want, False, mass)))
             elif kern == "head":
                 x = tokens(i, 0)
@@ -213,6 +217,7 @@ def lifter_ops(model, sd, B, H, W, iseed=82, kcrop=None, inexact_cap=True):
                     inst = layernorm_instance(d.Cin, out_bf) + f" eps {d.eps:.0e}"
                 else:
                     g, t, h, hd = (int(v) for v in d.attn)
+                    assert h == heads and t in (L1, J)
                     want, mass = op_oracle.attention_rows64(a, g * B, t, h, hd)
                     inst = attention_instance(t, hd, out_bf)
                 if out_bf:

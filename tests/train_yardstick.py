@@ -25,14 +25,19 @@ GRAD_MAX_BOUND = 2e-5
 N_LIFTER_GRADS = 191
 
 
+def _joints(eng):
+    """the engine's joint count (capf_config.num_joints: the tap views below are [B, J, 4, 16, 2])"""
+    return int(eng.cfg.num_joints)
+
+
 def check_cells_against_index_rule(eng, B, tag):
     """At a PRODUCTION batch: the NW corners the deformable sampler gathered from (cidx{i}) == oracle.bilinear_corners(the positions the
-    kernel itself computed (cpos{i}), 'border') bit for bit, for all 4 blocks x 4 levels x B x 17 x 16 samples; prints how many samples
+    kernel itself computed (cpos{i}), 'border') bit for bit, for all 4 blocks x 4 levels x B x J x 16 samples; prints how many samples
     sit within 4 ulp of a cell boundary (where grid_sample's one-sided derivative makes the choice of cell matter)."""
-    n, near = 0, 0
+    n, near, J = 0, 0, _joints(eng)
     for i in range(4):
-        pos = eng.tensor(f"cpos{i}")[:B].cpu().view(B, 17, 4, 16, 2).numpy()
-        idx = eng.tensor(f"cidx{i}")[:B].cpu().view(B, 17, 4, 16, 2).numpy()
+        pos = eng.tensor(f"cpos{i}")[:B].cpu().view(B, J, 4, 16, 2).numpy()
+        idx = eng.tensor(f"cidx{i}")[:B].cpu().view(B, J, 4, 16, 2).numpy()
         for l in range(4):
             f = eng.tensor(f"feat{l}")
             H, W = f.shape[1], f.shape[2]
@@ -46,7 +51,7 @@ def check_cells_against_index_rule(eng, B, tag):
             n += want["ix0"].size
     print(f"  {tag}: {n} deformable samples, corner indices == ATen's rule on the kernel's own positions bit for bit; "
           f"{near} unclipped coordinates within 4 ulp of a cell boundary")
-    assert n == 4 * 4 * B * 17 * 16
+    assert n == 4 * 4 * B * J * 16
     return near
 
 
@@ -60,17 +65,17 @@ def independent_of_cells(k):
 
 
 def engine_cells(eng, B):
-    """The bilinear cells the engine's deformable samplers used (cidx{i} taps of a set_debug(True) step): int64 [B, 17, 4, 16, 2] per block."""
-    return [eng.tensor(f"cidx{i}")[:B].cpu().view(B, 17, 4, 16, 2).long() for i in range(4)]
+    """The bilinear cells the engine's deformable samplers used (cidx{i} taps of a set_debug(True) step): int64 [B, J, 4, 16, 2] per block."""
+    return [eng.tensor(f"cidx{i}")[:B].cpu().view(B, _joints(eng), 4, 16, 2).long() for i in range(4)]
 
 
 def engine_clip_sides(eng, B):
     """Which coordinates of the deformable samplers the border clip left alone, by ATen's rule (0 < x < size - 1 on the unnormalised
     coordinate) in the kernels' fp32 arithmetic on the positions the engine computed (cpos{i} taps of a set_debug(True) step): bool
-    [B, 17, 4, 16, 2] per block."""
+    [B, J, 4, 16, 2] per block."""
     out = []
     for i in range(4):
-        pos = eng.tensor(f"cpos{i}")[:B].cpu().view(B, 17, 4, 16, 2).numpy()
+        pos = eng.tensor(f"cpos{i}")[:B].cpu().view(B, _joints(eng), 4, 16, 2).numpy()
         free = np.zeros(pos.shape, dtype=bool)
         for l in range(4):
             f = eng.tensor(f"feat{l}")
@@ -82,12 +87,12 @@ def engine_clip_sides(eng, B):
     return out
 
 
-def lifter64(params, k2d, ref, gt, feats, cells=None, drop_masks=None, sides=None):
+def lifter64(params, k2d, ref, gt, feats, cells=None, drop_masks=None, sides=None, heads=8):
     """oracle.lifter_forward in float64 on `feats` (NCHW), MPJPE against gt, backward.  params: name -> tensor (the volume_net.* entries
-    are used).  cells / sides: engine_cells / engine_clip_sides.  Returns ({name: fp64 gradient}, fp64 prediction, fp64 loss)."""
+    are used).  cells / sides: engine_cells / engine_clip_sides; heads: the Blocks' head count.  Returns ({name: fp64 gradient}, fp64 prediction, fp64 loss)."""
     Q = {k: v.detach().cpu().double().clone().requires_grad_(True) for k, v in params.items() if k.startswith("volume_net.")}
     w = oracle.lifter_forward(Q, k2d.cpu().double(), ref.cpu().double(), feats, cells=cells, unclipped=sides,
-                              drop_masks=drop_masks.cpu().double() if drop_masks is not None else None)
+                              drop_masks=drop_masks.cpu().double() if drop_masks is not None else None, heads=heads)
     loss = oracle.mpjpe(w, gt.cpu().double())
     loss.backward()
     return {k: q.grad for k, q in Q.items()}, w.detach(), loss.item()
@@ -99,7 +104,7 @@ def engine_yardstick(model, eng, B, k2d, ref, gt, drop_masks=None):
     third argument after it returned).  Returns ({'volume_net.<name>': fp64 gradient}, fp64 prediction, fp64 loss)."""
     feats = [eng.tensor(f"feat{l}")[:B].cpu().double().permute(0, 3, 1, 2).contiguous() for l in range(4)]
     params = {"volume_net." + n: p for n, p in model.volume_net.named_parameters()}
-    return lifter64(params, k2d, ref, gt, feats, engine_cells(eng, B), drop_masks, engine_clip_sides(eng, B))
+    return lifter64(params, k2d, ref, gt, feats, engine_cells(eng, B), drop_masks, engine_clip_sides(eng, B), heads=int(eng.cfg.num_heads))
 
 
 def engine_gradients(model, eng):
