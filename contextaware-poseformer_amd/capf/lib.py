@@ -184,6 +184,10 @@ PROTOTYPES = {
     "capf_pose_errors": (I, [P, P, P, I, I, P, P]),
     "capf_segment_sums": (I, [P, P, P, P, I, I, P, P]),
     "capf_keypoints_loss": (I, [P, I, P, P, P, I, I, F, P, P]),
+    "capf_keypoints_l2_loss": (I, [P, P, P, P, I, I, P, P, F]),
+    "capf_limb_length_errors": (I, [P, P, P, I, I, pI32, I, P, P, F]),
+    "capf_limb_length_sums": (I, [P, P, P, I, I, I, P, P]),
+    "capf_uncertainty_loss": (I, [P, P, P, I, I, pP, pI32, I, P, P, pP, F]),
     "capf_kp_head_scratch_bytes": (Z, [I] * 6),
     "capf_kp_head_forward": (I, [P, P, I, P, P] + [I] * 6 + [F, pF, P, P, P, P, P, P, Z]),
     "capf_kp_head_backward": (I, [P, P, P, P, I, P, P] + [I] * 6 + [F, pF, P, P, P, P, I, P, Z]),
@@ -1758,3 +1762,128 @@ def keypoints_loss(mode, pred, gt, validity, threshold=0.0, want_grad=False):
     if rc:
         raise CapfError(f"capf_keypoints_loss failed ({rc})")
     return loss, dpred
+
+
+# ---- the remaining pose losses of mvn/models/loss.py: KeypointsL2Loss (:140-147), LimbLengthError (:181-201), UNCERTAINTY (:7-13) ----
+LIMB_MAX = 64                     # csrc/kernels.h :: LIMB_MAX
+UNCERTAINTY_MAX_SIGMAS = 8        # csrc/kernels.h :: UNCERTAINTY_MAX_SIGMAS
+
+
+def _loss_operands(what, pred, gt):
+    """pred / gt of one shape [..., D], fp32, on the GPU -> (contiguous pred, contiguous gt, rows, D); shapes are judged before devices"""
+    import torch
+    if tuple(pred.shape) != tuple(gt.shape) or pred.dim() < 1 or pred.numel() == 0:
+        raise CapfError(f"{what}: pred and gt must have one non-empty shape [..., D], got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    if not (pred.is_cuda and gt.is_cuda):
+        raise CapfError(f"{what} runs on the MI355X only: got a CPU tensor (no CPU fallback)")
+    if pred.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise CapfError(f"{what}: pred and gt must be fp32, got {pred.dtype} and {gt.dtype}")
+    D = pred.shape[-1]
+    return pred.contiguous(), gt.contiguous(), pred.numel() // D, D
+
+
+def keypoints_l2_loss(pred, gt, validity, want_grad=False, grad_scale=1.0):
+    """capf_keypoints_l2_loss (loss.py:140-147).  pred / gt: CUDA fp32 [..., D]; validity: [..., 1] or [...] (one weight per row).
+    -> (loss [1], dpred | None); dpred = grad_scale * dloss/dpred, exactly 0 in a masked row and at pred == gt."""
+    import torch
+    lib = load_library()
+    lead = tuple(pred.shape[:-1])
+    if tuple(validity.shape) not in (lead, lead + (1,)):
+        raise CapfError(f"keypoints_l2_loss: validity must be {lead + (1,)} (one weight per row), got {tuple(validity.shape)}")
+    p, g, rows, D = _loss_operands("keypoints_l2_loss", pred, gt)
+    if not validity.is_cuda:
+        raise CapfError("keypoints_l2_loss runs on the MI355X only: got a CPU validity mask (no CPU fallback)")
+    v = validity.to(torch.float32).contiguous()
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    dpred = torch.empty(pred.shape, dtype=torch.float32, device=pred.device) if want_grad else None
+    rc = lib.capf_keypoints_l2_loss(_stream(pred), _p(p), _p(g), _p(v), rows, D, _p(loss), _p(dpred), float(grad_scale))
+    if rc:
+        raise CapfError(f"capf_keypoints_l2_loss failed ({rc})")
+    return loss, dpred
+
+
+def limb_table(limbs, joints):
+    """a sequence of (a, b) joint pairs -> the host int32 [L, 2] array capf_limb_length_errors takes; refuses what the entry refuses"""
+    pairs = [tuple(int(v) for v in pair) for pair in limbs]
+    if not 1 <= len(pairs) <= LIMB_MAX or any(len(pair) != 2 for pair in pairs):
+        raise CapfError(f"limbs must be 1..{LIMB_MAX} pairs of joints, got {len(pairs)} entries")
+    bad = [pair for pair in pairs if not (0 <= pair[0] < joints and 0 <= pair[1] < joints)]
+    if bad:
+        raise CapfError(f"limb {bad[0]} names a joint outside [0, {joints})")
+    return (c_int32 * (2 * len(pairs)))(*[v for pair in pairs for v in pair]), len(pairs)
+
+
+def limb_length_errors(pred, gt, limbs, want_grad=False, grad_scale=1.0):
+    """capf_limb_length_errors (loss.py:181-201 per pose).  pred / gt: CUDA fp32 [n, J, 3], J <= 32; limbs: 1..64 (a, b) pairs (host).
+    -> (err fp32 [n, L], dpred | None); dpred [n, J, 3] = grad_scale * d(sum_l err[i, l]) / dpred (exchange pred and gt for the target's)."""
+    import torch
+    lib = load_library()
+    if pred.dim() != 3 or pred.shape[-1] != 3:
+        raise CapfError(f"limb_length_errors: pred and gt must be [n, J, 3], got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    table, L = limb_table(limbs, pred.shape[1])
+    p, g, _, _ = _loss_operands("limb_length_errors", pred, gt)
+    n, J, _ = p.shape
+    err = torch.empty(n, L, dtype=torch.float32, device=pred.device)
+    dpred = torch.empty(n, J, 3, dtype=torch.float32, device=pred.device) if want_grad else None
+    rc = lib.capf_limb_length_errors(_stream(pred), _p(p), _p(g), n, J, table, L, _p(err), _p(dpred), float(grad_scale))
+    if rc:
+        raise CapfError(f"capf_limb_length_errors failed ({rc})")
+    return err, dpred
+
+
+def limb_length_sums(err, segment=None, n_segments=1):
+    """capf_limb_length_sums.  err: CUDA fp32 [n, L]; segment: CUDA int32 [n] or None (n_segments 1).
+    -> (sums float64 [n_segments, L], counts int64 [n_segments]) on the device; no synchronisation."""
+    import torch
+    lib = load_library()
+    if err.dim() != 2 or err.numel() == 0 or err.dtype != torch.float32:
+        raise CapfError(f"limb_length_sums: err must be a non-empty fp32 [n, L], got {tuple(err.shape)} {err.dtype}")
+    n, L = err.shape
+    if segment is None and n_segments != 1:
+        raise CapfError("limb_length_sums: n_segments > 1 needs a segment table")
+    if segment is not None and (tuple(segment.shape) != (n,) or segment.dtype != torch.int32):
+        raise CapfError(f"limb_length_sums: segment must be int32 [{n}], got {tuple(segment.shape)} {segment.dtype}")
+    if not err.is_cuda or (segment is not None and not segment.is_cuda):
+        raise CapfError("limb_length_sums runs on the MI355X only: got a CPU tensor (no CPU fallback)")
+    sums = torch.empty(n_segments, L, dtype=torch.float64, device=err.device)
+    counts = torch.empty(n_segments, dtype=torch.int64, device=err.device)
+    seg = None if segment is None else segment.contiguous()
+    rc = lib.capf_limb_length_sums(_stream(err), _p(err.contiguous()), _p(seg), n, L, int(n_segments), _p(sums), _p(counts))
+    if rc:
+        raise CapfError(f"capf_limb_length_sums failed ({rc})")
+    return sums, counts
+
+
+def uncertainty_loss(pred, gt, sigmas, want_dpred=False, want_dsigma=None, grad_scale=1.0):
+    """capf_uncertainty_loss (loss.py:7-13).  pred / gt: CUDA fp32 [..., D]; sigmas: 1..8 CUDA fp32 tensors, each [..., D] or [..., 1];
+    want_dsigma: None (none) or one bool per sigma.  -> (loss [1], dpred | None, [dsigma_k | None per sigma]); every gradient is
+    multiplied by grad_scale, dsigma_k has sigma k's own shape."""
+    import torch
+    lib = load_library()
+    sigmas = list(sigmas)
+    K = len(sigmas)
+    if not 1 <= K <= UNCERTAINTY_MAX_SIGMAS:
+        raise CapfError(f"uncertainty_loss takes 1..{UNCERTAINTY_MAX_SIGMAS} sigma tensors, got {K}")
+    lead, D = tuple(pred.shape[:-1]), (pred.shape[-1] if pred.dim() else 0)
+    for k, s in enumerate(sigmas):
+        if tuple(s.shape) not in (lead + (D,), lead + (1,)):
+            raise CapfError(f"uncertainty_loss: sigma {k} must be {lead + (D,)} or {lead + (1,)}, got {tuple(s.shape)}")
+    want_dsigma = [False] * K if want_dsigma is None else [bool(w) for w in want_dsigma]
+    if len(want_dsigma) != K:
+        raise CapfError(f"uncertainty_loss: want_dsigma must have one entry per sigma ({K}), got {len(want_dsigma)}")
+    p, g, rows, D = _loss_operands("uncertainty_loss", pred, gt)
+    if not all(s.is_cuda for s in sigmas):
+        raise CapfError("uncertainty_loss runs on the MI355X only: got a CPU sigma (no CPU fallback)")
+    if any(s.dtype != torch.float32 for s in sigmas):
+        raise CapfError("uncertainty_loss: every sigma must be fp32")
+    sig = [s.contiguous() for s in sigmas]
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    dpred = torch.empty(pred.shape, dtype=torch.float32, device=pred.device) if want_dpred else None
+    dsig = [torch.empty(s.shape, dtype=torch.float32, device=pred.device) if w else None for s, w in zip(sig, want_dsigma)]
+    ptrs = (c_void_p * K)(*[s.data_ptr() for s in sig])
+    widths = (c_int32 * K)(*[s.shape[-1] for s in sig])
+    dptrs = (c_void_p * K)(*[d.data_ptr() if d is not None else None for d in dsig])
+    rc = lib.capf_uncertainty_loss(_stream(pred), _p(p), _p(g), rows, D, ptrs, widths, K, _p(loss), _p(dpred), dptrs, float(grad_scale))
+    if rc:
+        raise CapfError(f"capf_uncertainty_loss failed ({rc})")
+    return loss, dpred, dsig

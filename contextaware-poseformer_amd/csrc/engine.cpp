@@ -1717,6 +1717,53 @@ int capf_keypoints_loss(void* stream, int mode, const float* pred, const float* 
                                        static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
 }
 
+// ---- the remaining pose losses (pose_losses.hip): every argument is judged here, before anything is launched ----
+int capf_keypoints_l2_loss(void* stream, const float* pred, const float* gt, const float* validity, int rows, int dim, float* loss,
+                           float* dpred, float grad_scale) {
+    if (!pred || !gt || !validity || !loss || rows <= 0 || dim <= 0) return CAPF_ERR_INVALID;
+    return capf::launch_keypoints_l2_loss(pred, gt, validity, rows, dim, loss, dpred, grad_scale, static_cast<hipStream_t>(stream)) == hipSuccess
+               ? CAPF_OK : CAPF_ERR_HIP;
+}
+
+int capf_limb_length_errors(void* stream, const float* pred, const float* gt, int n, int joints, const int32_t* limbs, int n_limbs,
+                            float* err, float* dpred, float grad_scale) {
+    if (!pred || !gt || !err || !limbs || n <= 0 || joints <= 0 || n_limbs < 1 || n_limbs > capf::LIMB_MAX) return CAPF_ERR_INVALID;
+    if (joints > capf::MAX_JOINTS) return CAPF_ERR_UNSUPPORTED;
+    capf::LimbTable t = {};
+    for (int l = 0; l < n_limbs; ++l) {
+        const int32_t a = limbs[2 * l], b = limbs[2 * l + 1];
+        if (a < 0 || a >= joints || b < 0 || b >= joints) return CAPF_ERR_INVALID;
+        t.a[l] = (unsigned char)a;
+        t.b[l] = (unsigned char)b;
+    }
+    return capf::launch_limb_length_errors(pred, gt, n, joints, t, n_limbs, err, dpred, grad_scale, static_cast<hipStream_t>(stream)) == hipSuccess
+               ? CAPF_OK : CAPF_ERR_HIP;
+}
+
+int capf_limb_length_sums(void* stream, const float* err, const int32_t* segment, int n, int n_limbs, int n_segments, double* sums,
+                          int64_t* counts) {
+    if (!err || !sums || !counts || n <= 0 || n_limbs < 1 || n_limbs > capf::LIMB_MAX || n_segments <= 0 || (!segment && n_segments != 1) ||
+        (long long)n_segments * n_limbs > 0x7fffffffLL)
+        return CAPF_ERR_INVALID;
+    return capf::launch_limb_length_sums(err, segment, n, n_limbs, n_segments, sums, reinterpret_cast<long long*>(counts),
+                                         static_cast<hipStream_t>(stream)) == hipSuccess ? CAPF_OK : CAPF_ERR_HIP;
+}
+
+int capf_uncertainty_loss(void* stream, const float* pred, const float* gt, int rows, int dim, const float* const* sigmas,
+                          const int32_t* sigma_widths, int n_sigmas, float* loss, float* dpred, float* const* dsigmas, float grad_scale) {
+    if (!pred || !gt || !loss || !sigmas || !sigma_widths || rows <= 0 || dim <= 0 || n_sigmas < 1 || n_sigmas > capf::UNCERTAINTY_MAX_SIGMAS)
+        return CAPF_ERR_INVALID;
+    capf::UncertaintySigmas sg = {};
+    for (int k = 0; k < n_sigmas; ++k) {
+        if (!sigmas[k] || (sigma_widths[k] != dim && sigma_widths[k] != 1)) return CAPF_ERR_INVALID;
+        sg.sigma[k] = sigmas[k];
+        sg.dsigma[k] = dsigmas ? dsigmas[k] : nullptr;
+        sg.width[k] = sigma_widths[k];
+    }
+    return capf::launch_uncertainty_loss(pred, gt, rows, dim, sg, n_sigmas, loss, dpred, grad_scale, static_cast<hipStream_t>(stream)) == hipSuccess
+               ? CAPF_OK : CAPF_ERR_HIP;
+}
+
 // ---- the 2-D keypoint head (kp_head.hip): every argument is judged here, before anything is launched ----
 size_t capf_kp_head_scratch_bytes(int B, int H, int W, int C, int J, int backward) {
     const capf::KpGeom g = capf::kp_geom(B, H, W, C, J);

@@ -767,6 +767,27 @@ hipError_t launch_pck2d_counts(const float* pred, const float* gt, int n, int J,
                                hipStream_t s);
 hipError_t launch_keypoints_loss(const float* pred, const float* gt, const float* validity, int rows, int D, int mode, float thr,
                                  float* loss, float* dpred, hipStream_t s);
+// ---- the remaining pose losses of ContextPose/mvn/models/loss.py (pose_losses.hip) ---------------------------------------------------
+// KeypointsL2Loss (loss.py:140-147): one block; dpred (or nullptr) = gscale * dloss/dpred, exactly 0 where the row's square root is 0
+hipError_t launch_keypoints_l2_loss(const float* pred, const float* gt, const float* validity, int rows, int D, float* loss, float* dpred,
+                                    float gscale, hipStream_t s);
+// LimbLengthError (loss.py:181-201): err [n][L] fp32 per pose and limb; dpred (or nullptr) [n][J][3] = gscale * d(sum_l err[i][l])/dpred.
+// The limb table (L <= LIMB_MAX pairs of joints in [0, J), checked by the caller) travels in the kernel's arguments.
+constexpr int LIMB_MAX = 64;
+struct LimbTable { unsigned char a[LIMB_MAX], b[LIMB_MAX]; };
+hipError_t launch_limb_length_errors(const float* pred, const float* gt, int n, int J, const LimbTable& limbs, int L, float* err, float* dpred,
+                                     float gscale, hipStream_t s);
+// sums [n_seg][L] fp64 in a fixed order, counts [n_seg] int64
+hipError_t launch_limb_length_sums(const float* err, const int* seg, int n, int L, int n_seg, double* sums, long long* counts, hipStream_t s);
+// UNCERTAINTY (loss.py:7-13): K <= UNCERTAINTY_MAX_SIGMAS sigma tensors of width D or 1; one block
+constexpr int UNCERTAINTY_MAX_SIGMAS = 8;
+struct UncertaintySigmas {
+    const float* sigma[UNCERTAINTY_MAX_SIGMAS];
+    float* dsigma[UNCERTAINTY_MAX_SIGMAS];           // nullptr: not wanted
+    int width[UNCERTAINTY_MAX_SIGMAS];               // D or 1
+};
+hipError_t launch_uncertainty_loss(const float* pred, const float* gt, int rows, int D, const UncertaintySigmas& sg, int K, float* loss,
+                                   float* dpred, float gscale, hipStream_t s);
 
 // ---- 2-D keypoint head (kp_head.hip): final_layer (1x1 conv) on feat0 + heatmap decode, one pass over the map ------------------------
 constexpr int KP_MAX_CHANNELS = 512;

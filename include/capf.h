@@ -754,6 +754,51 @@ int capf_segment_sums(void* stream, const float* err, const int32_t* segment, co
                       double* sums, int32_t* counts);
 int capf_keypoints_loss(void* stream, int mode, const float* pred, const float* gt, const float* validity, int rows, int dim,
                         float threshold, float* loss, float* dpred);
+/* ---- the remaining pose losses of ContextPose/mvn/models/loss.py, with gradients (csrc/pose_losses.hip).  Additive inside revision 12.
+ * Every entry enqueues on `stream`, allocates nothing, never synchronises, and adds in fixed orders without atomics: the same bits on
+ * every call.  All sums are fp64 from the fp32 inputs; every output element is one fp32 store of its fp64 value.  grad_scale multiplies
+ * the gradients only (capf_mpjpe's rule); an output gradient pointer that is NULL is not written, and the loss bits do not depend on it.
+ *
+ * capf_keypoints_l2_loss: KeypointsL2Loss, loss.py:140-147.  pred / gt [rows, dim] (dim >= 1), validity [rows] (the reference's [B, J, 1] mask):
+ *     loss = sum_r sqrt(v_r * sum_c (gt - pred)^2) / max(1, sum_r v_r)
+ *     dpred[r, c] = grad_scale * v_r (pred - gt) / (sqrt(v_r d2_r) * max(1, sum v)),  and EXACTLY 0 where that square root is 0
+ *   -- capf_mpjpe's rule at zero distance.  It covers the masked row (v_r = 0) and the exact hit (pred == gt), at both of which the
+ *   reference's autograd returns NaN (sqrt'(0) * 0), so a mask that holds zeros cannot be trained through there.  dloss/dgt = -dpred; the
+ *   mask gets no gradient.  One block (training batches: at most 512 x 17 rows; any row count works).
+ *
+ * capf_limb_length_errors: LimbLengthError, loss.py:181-201, per pose.  pred / gt [n, joints, 3], joints <= 32; limbs: HOST int32
+ *   [n_limbs, 2], 1 <= n_limbs <= 64, pairs (a_l, b_l) of joints.  The table travels in the kernel's arguments like
+ *   capf_fliptest_fuse_swap's (no upload; the array may be reused as soon as the call returns) and is checked HERE: an index outside
+ *   [0, joints) returns CAPF_ERR_INVALID and nothing is launched.  a_l == b_l and a repeated limb are legal.
+ *     err[i, l] = | |pred[i, a_l] - pred[i, b_l]| - |gt[i, a_l] - gt[i, b_l]| |                        (err: [n, n_limbs])
+ *     dpred[i] [joints, 3] = grad_scale * d(sum_l err[i, l]) / dpred[i]: per joint the sum, in limb order, over the limbs that touch it of
+ *     +-sign(|pred limb| - |gt limb|) (pred[a_l] - pred[b_l]) / |pred limb|.  sign(0) = 0 (equal lengths), a predicted limb of length 0
+ *     contributes 0 (no direction to move along), a_l == b_l contributes 0.  Every element of dpred is written (joints that no limb
+ *     touches: 0).  The gradient with respect to gt is the same call with pred and gt exchanged.  One pose per thread.
+ * capf_limb_length_sums: sums[s, l] fp64 = sum of err[i, l] over the poses with segment[i] == s, counts[s] int64 = those poses.
+ *   segment: device int32 [n], or NULL with n_segments == 1 (all poses); ids outside [0, n_segments) are counted nowhere.  One block per
+ *   (segment, limb): thread t of 256 adds its poses t, t + 256, ... in order, then a fixed tree.  The reference's figure is
+ *   sum_l (sums[0, l] / n) / n_limbs.
+ *
+ * capf_uncertainty_loss: UNCERTAINTY, loss.py:7-13.  pred / gt [rows, dim]; sigmas: HOST array of n_sigmas (1..8) device pointers,
+ *   sigma_widths: HOST int32 [n_sigmas], sigma k is [rows, sigma_widths[k]] with width dim or 1 (broadcast over the row), anything else
+ *   CAPF_ERR_INVALID.  With s = sigma + 1e-6 (formed in fp64), u = (pred - gt) / s:
+ *     loss = sum_k ( mean_r |u_k[r, :]|_2 + 0.01 * mean over sigma_k's own elements of log s )
+ *   dpred (or NULL) [rows, dim]; dloss/dgt = -dpred.  dsigmas: NULL, or a HOST array of n_sigmas device pointers, each NULL or sigma k's
+ *   own shape (the [rows, 1] form is summed over the row inside the thread).  The norm term contributes 0 to every gradient where
+ *   |u_k[r, :]| is 0 (whatever torch.norm's backward does at 0 in the caller's torch version).  s <= 0 is not clamped: the loss is NaN, as the reference's log gives, and so are the row's
+ *   dpred and that sigma's gradient in that row -- the guarded optimizer step (capf_adamw_step_guarded) is what catches it.  One block.
+ * Refused before anything is launched (CAPF_ERR_INVALID): a NULL input or loss / err / sums / counts pointer, rows, n, dim, joints or
+ * n_segments <= 0, n_limbs outside 1..64, n_sigmas outside 1..8, segment == NULL with n_segments != 1; joints > 32: CAPF_ERR_UNSUPPORTED.
+ * Cost (MI355X, tools/bench_losses.py): EXPERIMENTS.md R39.1.                                                                               */
+int capf_keypoints_l2_loss(void* stream, const float* pred, const float* gt, const float* validity, int rows, int dim, float* loss,
+                           float* dpred, float grad_scale);
+int capf_limb_length_errors(void* stream, const float* pred, const float* gt, int n, int joints, const int32_t* limbs, int n_limbs,
+                            float* err, float* dpred, float grad_scale);
+int capf_limb_length_sums(void* stream, const float* err, const int32_t* segment, int n, int n_limbs, int n_segments, double* sums,
+                          int64_t* counts);
+int capf_uncertainty_loss(void* stream, const float* pred, const float* gt, int rows, int dim, const float* const* sigmas,
+                          const int32_t* sigma_widths, int n_sigmas, float* loss, float* dpred, float* const* dsigmas, float grad_scale);
 
 /* ---- 2-D keypoint head: final_layer + heatmap decode on the highest-resolution context map --------------------------------------------
  * What an HRNet COCO checkpoint's final_layer (nn.Conv2d(C0, 17, 1), pose_hrnet.py:497-501, commented out in the reference) computes on
